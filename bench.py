@@ -9,7 +9,12 @@ Rays are counted exactly (one per hitScene invocation) by the device.
 N > 1: pixels are sharded across ranks in tiles; `--scaling weak` (default) multiplies spp by N so that the rays
 per GPU stay fixed, `--scaling strong` keeps the total spp (BASELINE configs[3]/[4] are fixed totals).
 
-What the line carries besides the contract's fields (N = 1):
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline figure needs: set-up, W warm-up steps, the N timed steps, the
+outputs if `--dump-outputs DIR` is given, one line (value, ms_per_step, the workload and its set-up times).  `--dump-outputs DIR` writes what the
+timed path computed in its last step: DIR/framebuffer.npy (the float32 H x W x 4 accumulation buffer a caller reads back; above 64 MB a fixed,
+seeded sample of its pixels, framebuffer_sample.npy + framebuffer_sample_pixels.npy) and DIR/rays_per_step.npy (float64).
+
+What the line carries besides that with `--full` (N = 1; N > 1: the other scaling mode's figure and the roofline):
   roofline      for the kernel with the largest share of the timed step: its launch time is measured live with HIP events
                 on the context's stream inside the timed region; VALU-busy cycles and HBM bytes per launch come from
                 rocprofv3 --pmc passes that THIS run makes over the same workload before it touches the GPU itself
@@ -409,9 +414,11 @@ class _NoDist:
         return value
 
 
-def measure(pkg, torch, pdist, ctx, wl, spp, steps, warmup, reduce_fn):
+def measure(pkg, torch, pdist, ctx, wl, spp, steps, warmup, reduce_fn, full=True, read_back=False):
     """reduce_fn: the step's collective (None on one GPU) — torch.distributed's reduce of the bound framebuffer tensor when the driver starts one
-    process per GPU, ptmi_reduce_framebuffer (ncclReduce inside the library) when one process drives all GPUs."""
+    process per GPU, ptmi_reduce_framebuffer (ncclReduce inside the library) when one process drives all GPUs.
+    full=False (a plain run): the timed steps alone — no per-kernel split before them, no HIP events inside them, no counted pass after them.
+    read_back: the framebuffer of the last timed step, read back after the timed region (m["framebuffer"], for --dump-outputs)."""
     view = wl["view"]
     coll = [0.0]  # seconds this rank spent in the step's collective (the wait for the slowest rank included)
 
@@ -426,17 +433,20 @@ def measure(pkg, torch, pdist, ctx, wl, spp, steps, warmup, reduce_fn):
 
     for _ in range(warmup):
         step()
-    # per-kernel split of one step (HIP events around every launch; the kernels are the timed ones, not the counted variants)
+    split = dom = None
     ctx.synchronize()
+    if full:
+        # per-kernel split of one step (HIP events around every launch; the kernels are the timed ones, not the counted variants)
+        ctx.reset_stats()
+        ctx.set_timing(1)
+        step()
+        split = ctx.stats()
+        ctx.set_timing(0)
+        dom = max(KERNELS, key=lambda k: split[MS_KEY[k]])
+    # the timed region (--full: events only around the dominant kernel; every event is a stream marker)
     ctx.reset_stats()
-    ctx.set_timing(1)
-    step()
-    split = ctx.stats()
-    ctx.set_timing(0)
-    dom = max(KERNELS, key=lambda k: split[MS_KEY[k]])
-    # the timed region: events only around the dominant kernel (every event is a stream marker)
-    ctx.reset_stats()
-    ctx.set_timing(TIMING_MODE[dom])
+    if full:
+        ctx.set_timing(TIMING_MODE[dom])
     if torch is not None:
         torch.cuda.synchronize()
     pdist.barrier()
@@ -455,15 +465,18 @@ def measure(pkg, torch, pdist, ctx, wl, spp, steps, warmup, reduce_fn):
     coll_ms = coll[0] / max(steps, 1) * 1e3
     st = ctx.stats()
     ctx.set_timing(0)
-    # exact work counters of one step (counted variants of the same kernels, untimed)
-    ctx.reset_stats()
-    ctx.set_counters(True)
-    ctx.clear()
-    ctx.render(view, 1, spp)
-    cst = ctx.stats()
-    ctx.set_counters(False)
-    assert cst["rays"] * steps == st["rays"], "ray count differs between the counted and the timed pass"
-    return {"dt": dt, "st": st, "split": split, "cst": cst, "dom": dom, "collective_ms_per_step": coll_ms, "step_ms": step_ms}
+    fb = ctx.read_framebuffer() if read_back else None  # (before anything else renders into the context)
+    cst = None
+    if full:
+        # exact work counters of one step (counted variants of the same kernels, untimed)
+        ctx.reset_stats()
+        ctx.set_counters(True)
+        ctx.clear()
+        ctx.render(view, 1, spp)
+        cst = ctx.stats()
+        ctx.set_counters(False)
+        assert cst["rays"] * steps == st["rays"], "ray count differs between the counted and the timed pass"
+    return {"dt": dt, "st": st, "split": split, "cst": cst, "dom": dom, "collective_ms_per_step": coll_ms, "step_ms": step_ms, "framebuffer": fb}
 
 
 def measure_short(torch, pdist, ctx, wl, spp, steps, reduce_fn):
@@ -489,6 +502,26 @@ def measure_short(torch, pdist, ctx, wl, spp, steps, reduce_fn):
         torch.cuda.synchronize()
     pdist.barrier()
     return time.perf_counter() - t0, ctx.stats()
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(d, fb, rays_per_step):
+    """--dump-outputs DIR: what the timed path computed in its last step — the accumulation buffer a caller reads back (ptmi_read_framebuffer:
+    float32 RGBA sums over the step's frames, H x W x 4) and the step's exact ray count (float64).  A buffer that would take the files past 64 MB
+    goes out as a fixed, seeded sample of its pixels (framebuffer_sample.npy, N x 4) with their flat indices (framebuffer_sample_pixels.npy, float64)."""
+    os.makedirs(d, exist_ok=True)
+    room = DUMP_LIMIT_BYTES - 4 * 10 ** 6  # (headers, the ray count, a margin)
+    if fb.nbytes <= room:
+        np.save(os.path.join(d, "framebuffer.npy"), fb)
+    else:
+        px = fb.reshape(-1, fb.shape[-1])
+        n = room // (px.shape[1] * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))
+        np.save(os.path.join(d, "framebuffer_sample.npy"), np.ascontiguousarray(px[idx]))
+        np.save(os.path.join(d, "framebuffer_sample_pixels.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "rays_per_step.npy"), np.array([rays_per_step], np.float64))
 
 
 def cpu_baseline(pkg, wl, spp, args):
@@ -617,11 +650,16 @@ def main():
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="N>1 on ONE GPU for rehearsal: ranks share cuda:0, the framebuffer reduce goes through gloo on host copies "
                          "(RCCL wants one device per rank); numbers from this mode are not bench results")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: per-kernel split and roofline (with the rocprofv3 passes of --pmc), the exact-work counted pass, "
+                         "the two-shards leg, configs[2] (--extra-configs), the CPU baselines (--cpu-seconds); N > 1: the other scaling mode.  Off: the timed steps alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (framebuffer.npy, rays_per_step.npy; a seeded sample above 64 MB)")
     ap.add_argument("--cpu-threads", type=int, default=16, help="OpenMP threads of the cpu_baseline (the 1-GPU box's CPU share)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the cpu_baseline's all-cores sample (0 = skip the CPU legs)")
-    ap.add_argument("--pmc", default="auto", choices=["auto", "off"], help="auto = rocprofv3 --pmc passes over the workload before the timed run (N = 1 only)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: target CPU time of the cpu_baseline's all-cores sample (0 = skip the CPU legs)")
+    ap.add_argument("--pmc", default="auto", choices=["auto", "off"], help="--full: auto = rocprofv3 --pmc passes over the workload before the timed run (N = 1 only)")
     ap.add_argument("--pmc-timeout", type=float, default=240.0)
-    ap.add_argument("--extra-configs", default="auto", choices=["auto", "off"], help="auto = append the configs[2] (871k-triangle) run to the line (N = 1, default workload only)")
+    ap.add_argument("--extra-configs", default="auto", choices=["auto", "off"], help="--full: auto = append the configs[2] (871k-triangle) run to the line (N = 1, default workload only)")
     ap.add_argument("--c3-steps", type=int, default=6, help="timed steps of the appended configs[2] leg (the line carries their median and min-max)")
     ap.add_argument("--c3-warmup", type=int, default=2)
     ap.add_argument("--host-collective", action="store_true",
@@ -636,6 +674,8 @@ def main():
     ap.add_argument("--fallback-reason", default="", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.pmc_child:
         pmc_child(args)
@@ -710,11 +750,11 @@ def worker(args):
     if inlib and devices is None:
         devices = list(range(args.gpus))
     solo = world_env == 1 and not inlib
-    extra_c3 = solo and args.extra_configs == "auto" and args.workload == "c2"
+    extra_c3 = solo and args.full and args.extra_configs == "auto" and args.workload == "c2"
 
     # rocprofv3 passes first: child processes, before this process has touched the GPU
     pmc, pmc_note, pmc_log = {}, {}, []
-    if solo and args.pmc == "auto":
+    if solo and args.full and args.pmc == "auto":
         for w in [args.workload] + (["c3"] if extra_c3 else []):
             pmc[w], why = pmc_passes(args, w, pmc_log)
             if why:
@@ -738,7 +778,7 @@ def worker(args):
         pdist, rank, local = _NoDist, 0, 0
         world = len(devices) if inlib else 1
 
-    def run_workload(name, steps, warmup, spp_arg, wl_args=None):
+    def run_workload(name, steps, warmup, spp_arg, wl_args=None, read_back=False):
         wl_args = wl_args or args
         wl = make_workload(pkg, name, wl_args)
         per = spp_arg or SPP[name]
@@ -767,8 +807,8 @@ def worker(args):
                     collective(fb_t)
                 torch.cuda.synchronize()  # the collective runs on torch's stream; the next clear runs on the context's
 
-        m = measure(pkg, torch, pdist, ctx, wl, spp, steps, warmup, reduce_fn)
-        if world > 1:  # the other scaling mode, briefly: strong next to the default weak (fixed total spp: the reading of BASELINE configs[3] / [4]), or the reverse
+        m = measure(pkg, torch, pdist, ctx, wl, spp, steps, warmup, reduce_fn, args.full, read_back)
+        if world > 1 and args.full:  # the other scaling mode, briefly: strong next to the default weak (fixed total spp: the reading of BASELINE configs[3] / [4]), or the reverse
             spp_o = per if args.scaling == "weak" else per * world
             dt_o, st_o = measure_short(torch, pdist, ctx, wl, spp_o, max(1, min(steps, 5)), reduce_fn)
             m["other"] = {"scaling": "strong" if args.scaling == "weak" else "weak", "spp": spp_o, "steps": max(1, min(steps, 5)), "dt": dt_o, "rays": st_o["rays"]}
@@ -776,46 +816,50 @@ def worker(args):
         m["reduce_mode"] = ctx.stats().get("reduce_mode") if inlib else None
         return wl, ctx, spp, per, m
 
-    wl, ctx, spp, per, m = run_workload(args.workload, args.steps, args.warmup, args.spp)
-    st, cst, dom = m["st"], m["cst"], m["dom"]
+    wl, ctx, spp, per, m = run_workload(args.workload, args.steps, args.warmup, args.spp, read_back=bool(args.dump_outputs) and rank == 0)
+    st = m["st"]
     dt_max = pdist.all_reduce_scalar(m["dt"], "max")
     rays_all = pdist.all_reduce_scalar(st["rays"], "sum")
     paths_all = pdist.all_reduce_scalar(st["paths"], "sum")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, m.pop("framebuffer"), rays_all / args.steps)
     o_rays = o_dt = None
-    if world > 1:  # (collectives: every rank takes part)
+    if world > 1 and args.full:  # (collectives: every rank takes part)
         o_rays, o_dt = pdist.all_reduce_scalar(m["other"]["rays"], "sum"), pdist.all_reduce_scalar(m["other"]["dt"], "max")
 
     def describe(wl, spp, per, m, steps, rays, paths, dt, pm):
         """value / roofline / kernel table of one measured workload."""
         st, cst, dom = m["st"], m["cst"], m["dom"]
-        tab = kernel_table(m["split"], 1, pm, "k_shade<true, true, false, false>" if wl["extra"].get("importance_sampling") else "k_shade6<false, false>")
-        n_dom = max(st[LAUNCH_KEY[dom]], 1)
-        bvh_launches = max(m["split"][LAUNCH_KEY["k_bvh"]], 1)
-        gather = (cst["bvh_node_visits"] / 2.0 + cst["tri_tests"]) / bvh_launches  # 64-byte records k_bvh fetches per launch (pair records + triangle records)
-        roof = roofline_of(tab, dom, st[MS_KEY[dom]] / n_dom, n_dom, gather)
-        if tab["k_bvh"]["ms_per_step"] > 0:
-            tab["k_bvh"]["l1_gather_frac"] = gather * bvh_launches / (tab["k_bvh"]["ms_per_step"] * 1e-3) / gather_peak()[0]  # (not clamped: coherent lanes sharing a record count per lane)
-            tab["k_bvh"]["records_per_launch"] = gather
-        # What SURVEY §8d's yardstick calls waste: HBM bytes the step moves beyond what the reference's megakernel must move — its framebuffer read-modify-write
-        # once per frame (32 B per pixel and frame) and the scene once.  The wavefront design pays the rest as path state crossing HBM between kernels.
-        if any(tab[k].get("fabric_bytes_per_launch") is not None for k in KERNELS):  # (a kernel the batch never launched has no counters and moved nothing)
-            step_bytes = sum((tab[k].get("fabric_bytes_per_launch") or 0.0) * tab[k]["launches_per_step"] for k in KERNELS)
-            scene_bytes = sum(np.asarray(wl["buffers"][k]).nbytes for k in ("spheres", "quads", "triangles", "meshes", "transforms", "materials", "bvh"))
-            compulsory = 32.0 * wl["W"] * wl["H"] * spp / max(world, 1) + scene_bytes
-            roof["step_fabric_bytes"] = step_bytes
-            roof["compulsory_bytes"] = compulsory
-            roof["state_traffic_bytes"] = step_bytes - compulsory
-            roof["state_over_compulsory"] = (step_bytes - compulsory) / compulsory if compulsory else None
-            roof["step_fabric_frac_of_hbm_peak"] = step_bytes / (dt / steps) / (HBM_PEAK_GBS * 1e9)
-            roof["dram_vs_mall"] = MALL_NOTE
-            roof["traffic_note"] = ("step_fabric_bytes = measured fabric bytes of all kernels of one step (this run's FETCH_SIZE / WRITE_SIZE passes: Infinity-Cache hits count, "
-                                    "so DRAM bytes are at most this); compulsory_bytes = the reference "
-                                    "megakernel's own HBM need (framebuffer RMW per pixel and frame + the scene once); the difference is wavefront path state (queues, hit "
-                                    "records, per-path radiance) that the reference never moves — waste by SURVEY §8d's yardstick, the price of compaction and lane refill")
-        hit_scene_gbs = alg_bytes(cst) / (m["split"]["render_ms"] / 1e3) / 1e9 if m["split"]["render_ms"] > 0 else None
-        roof["algorithmic_hit_scene_gbs_informational"] = hit_scene_gbs  # SURVEY §8d reference-layout bytes / render time: cache-oblivious, NOT a fraction of HBM peak
-        roof["work_per_ray"] = {k: cst[k] / max(cst["rays"], 1) for k in ("node_visits", "bvh_node_visits", "tri_tests", "quad_tests", "sphere_tests", "mat_fetches")}
-        roof["kernels"] = tab
+        roof = None
+        if dom is not None:  # --full: the per-kernel split and the counted pass of this workload were measured
+            tab = kernel_table(m["split"], 1, pm, "k_shade<true, true, false, false>" if wl["extra"].get("importance_sampling") else "k_shade6<false, false>")
+            n_dom = max(st[LAUNCH_KEY[dom]], 1)
+            bvh_launches = max(m["split"][LAUNCH_KEY["k_bvh"]], 1)
+            gather = (cst["bvh_node_visits"] / 2.0 + cst["tri_tests"]) / bvh_launches  # 64-byte records k_bvh fetches per launch (pair records + triangle records)
+            roof = roofline_of(tab, dom, st[MS_KEY[dom]] / n_dom, n_dom, gather)
+            if tab["k_bvh"]["ms_per_step"] > 0:
+                tab["k_bvh"]["l1_gather_frac"] = gather * bvh_launches / (tab["k_bvh"]["ms_per_step"] * 1e-3) / gather_peak()[0]  # (not clamped: coherent lanes sharing a record count per lane)
+                tab["k_bvh"]["records_per_launch"] = gather
+            # What SURVEY §8d's yardstick calls waste: HBM bytes the step moves beyond what the reference's megakernel must move — its framebuffer read-modify-write
+            # once per frame (32 B per pixel and frame) and the scene once.  The wavefront design pays the rest as path state crossing HBM between kernels.
+            if any(tab[k].get("fabric_bytes_per_launch") is not None for k in KERNELS):  # (a kernel the batch never launched has no counters and moved nothing)
+                step_bytes = sum((tab[k].get("fabric_bytes_per_launch") or 0.0) * tab[k]["launches_per_step"] for k in KERNELS)
+                scene_bytes = sum(np.asarray(wl["buffers"][k]).nbytes for k in ("spheres", "quads", "triangles", "meshes", "transforms", "materials", "bvh"))
+                compulsory = 32.0 * wl["W"] * wl["H"] * spp / max(world, 1) + scene_bytes
+                roof["step_fabric_bytes"] = step_bytes
+                roof["compulsory_bytes"] = compulsory
+                roof["state_traffic_bytes"] = step_bytes - compulsory
+                roof["state_over_compulsory"] = (step_bytes - compulsory) / compulsory if compulsory else None
+                roof["step_fabric_frac_of_hbm_peak"] = step_bytes / (dt / steps) / (HBM_PEAK_GBS * 1e9)
+                roof["dram_vs_mall"] = MALL_NOTE
+                roof["traffic_note"] = ("step_fabric_bytes = measured fabric bytes of all kernels of one step (this run's FETCH_SIZE / WRITE_SIZE passes: Infinity-Cache hits count, "
+                                        "so DRAM bytes are at most this); compulsory_bytes = the reference "
+                                        "megakernel's own HBM need (framebuffer RMW per pixel and frame + the scene once); the difference is wavefront path state (queues, hit "
+                                        "records, per-path radiance) that the reference never moves — waste by SURVEY §8d's yardstick, the price of compaction and lane refill")
+            hit_scene_gbs = alg_bytes(cst) / (m["split"]["render_ms"] / 1e3) / 1e9 if m["split"]["render_ms"] > 0 else None
+            roof["algorithmic_hit_scene_gbs_informational"] = hit_scene_gbs  # SURVEY §8d reference-layout bytes / render time: cache-oblivious, NOT a fraction of HBM peak
+            roof["work_per_ray"] = {k: cst[k] / max(cst["rays"], 1) for k in ("node_visits", "bvh_node_visits", "tri_tests", "quad_tests", "sphere_tests", "mat_fetches")}
+            roof["kernels"] = tab
         return {
             "value": rays / dt / 1e6, "ms_per_step": dt / steps * 1e3, "rays_per_step": rays / steps, "mpaths_per_s": paths / dt / 1e6,
             "ms_per_step_stats": {"median": float(np.median(m["step_ms"])), "min": float(np.min(m["step_ms"])), "max": float(np.max(m["step_ms"])), "steps": len(m["step_ms"]),
@@ -856,11 +900,13 @@ def worker(args):
                         "; REHEARSAL: the ranks share cuda:0" if args.rehearse_gloo else ""))
                     if world > 1 else "1 GPU") + ("; FALLBACK after the first attempt failed: %s" % args.fallback_reason if args.fallback_reason else ""),
             },
-            "roofline": d["roofline"],
         }
+        if d["roofline"] is not None:
+            out["roofline"] = d["roofline"]
         if world > 1:
             out["config"]["collective_ms_per_step"] = m["collective_ms_per_step"]  # rank 0's wall time inside the collective, its wait for the slowest rank included
             out["config"]["collective_bytes_into_root"] = (world - 1) * wl["W"] * wl["H"] * 16 // (world if ((inlib and m["reduce_mode"] == 4) or (not inlib and args.collective == "gather")) else 1)
+        if world > 1 and args.full:
             o = m["other"]
             out["config"]["other_scaling"] = {"scaling": o["scaling"], "spp_total": o["spp"], "steps": o["steps"], "value": o_rays / o_dt / 1e6, "unit": "Mrays/s",
                                               "ms_per_step": o_dt / o["steps"] * 1e3, "note": "informational: the same ranks and collective in the other scaling mode; `value` above is --scaling %s" % args.scaling}
@@ -870,7 +916,9 @@ def worker(args):
             out["roofline"]["pmc_source"] = "rocprofv3 --pmc passes made by this run (%s), %.0f s" % (" | ".join(c for _, c in PMC_PASSES), pmc[args.workload]["_seconds"])
     ctx.close()
 
-    if rank == 0 and solo:
+    if rank == 0 and solo and not args.full:
+        out["setup_ms"] = wl["setup"]
+    elif rank == 0 and solo:
         # Informational: the same workload through ONE context with two shards on this GPU (ptmi_create_multi with the device listed twice:
         # two streams, pixel tiles dealt to them, summed at read-back) — the shards fill each other's k_bvh tails.  Not `value`: the kernels
         # of the two streams overlap, so a per-kernel roofline of that mode would not mean what the one above means.

@@ -1,5 +1,8 @@
+import glob
+import gzip
 import importlib.util
 import os
+import shutil
 import sys
 
 import numpy as np
@@ -30,6 +33,17 @@ def pytest_configure(config):
 @pytest.fixture(scope="session")
 def pkg():
     return load_pkg()
+
+
+@pytest.fixture(scope="session")
+def ref_assets(tmp_path_factory):
+    """Directory holding the reference's own assets/*.obj meshes, unpacked once per session from tests/golden/assets/*.obj.gz
+    (stored gzip-compressed, byte-identical after unpacking)."""
+    d = tmp_path_factory.mktemp("ref_assets")
+    for f in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "assets", "*.obj.gz"))):
+        with gzip.open(f, "rb") as src, open(os.path.join(str(d), os.path.basename(f)[: -len(".gz")]), "wb") as dst:
+            shutil.copyfileobj(src, dst)
+    return str(d)
 
 
 @pytest.fixture(scope="session")

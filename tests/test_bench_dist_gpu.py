@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_two_ranks_on_one_gpu():
-    common = ["--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--pmc", "off", "--extra-configs", "off", "--width", "320", "--height", "180", "--spp", "4"]
+    common = ["--full", "--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--pmc", "off", "--extra-configs", "off", "--width", "320", "--height", "180", "--spp", "4"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     one = subprocess.run([sys.executable, "bench.py"] + common, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -53,7 +53,7 @@ def test_bench_two_ranks_on_one_gpu():
 def test_bench_line_contract_with_its_own_pmc_passes():
     """The driver's line: contract keys, a roofline for the dominant kernel whose fractions come from rocprofv3 passes made by the run
     itself (frac <= 1 by construction, in the unit of the bound it names), per-kernel table, CPU baselines incl. the single thread."""
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--width", "640", "--height", "360", "--spp", "8", "--cpu-seconds", "1",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--width", "640", "--height", "360", "--spp", "8", "--cpu-seconds", "1",
                         "--extra-configs", "off"], cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -87,7 +87,7 @@ def test_bench_line_contract_with_its_own_pmc_passes():
 def test_bench_in_library_multi_device_path_without_a_launcher():
     """`python bench.py --gpus N` with no torch.distributed.run around it: ONE process, ONE context over the N GPUs (ptmi_create_multi), the reduce
     inside the library (ptmi_reduce_framebuffer).  Rehearsed on one GPU with --devices 0,0 (the shards share the GPU and are summed by a kernel)."""
-    common = ["--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--pmc", "off", "--extra-configs", "off", "--width", "320", "--height", "180", "--spp", "4"]
+    common = ["--full", "--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--pmc", "off", "--extra-configs", "off", "--width", "320", "--height", "180", "--spp", "4"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)

@@ -7,10 +7,6 @@ import os
 import numpy as np
 import pytest
 
-ASSETS = "/root/reference/assets"  # only present in the build container; never on the GPU box
-needs_assets = pytest.mark.skipif(not os.path.isdir(ASSETS), reason="reference assets not mounted")
-
-
 def _same(a, b):
     a, b = np.asarray(a), np.asarray(b)
     return a.size == b.size and np.array_equal(a.reshape(-1).view(np.uint32), b.reshape(-1).view(np.uint32))
@@ -23,17 +19,16 @@ def test_c1_buffers_match_reference_js(pkg):
         assert _same(b[k], g[k]), k
 
 
-@needs_assets
 @pytest.mark.parametrize("native", [False, True])
-def test_mesh_scenes_match_reference_js(pkg, native):
+def test_mesh_scenes_match_reference_js(pkg, native, ref_assets):
     from webgpu_path_tracer_amd.host import ObjReader
 
     nat = pkg.ptmi.NativeHost() if native else None
-    cube = ObjReader.load_model(ASSETS + "/cube.obj")
+    cube = ObjReader.load_model(os.path.join(ref_assets, "cube.obj"))
     cases = {
         "default": pkg.scenes.DefaultScene(cube),
-        "c2": pkg.scenes.c2_scene(ObjReader.load_model(ASSETS + "/monkey_968.obj")),
-        "c2m": pkg.scenes.c2m_scene(ObjReader.load_model(ASSETS + "/icosphere.obj"), cube),
+        "c2": pkg.scenes.c2_scene(ObjReader.load_model(os.path.join(ref_assets, "monkey_968.obj"))),
+        "c2m": pkg.scenes.c2m_scene(ObjReader.load_model(os.path.join(ref_assets, "icosphere.obj")), cube),
     }
     for name, sc in cases.items():
         b = sc.buffers(native=nat)
@@ -42,24 +37,22 @@ def test_mesh_scenes_match_reference_js(pkg, native):
             assert _same(b[k], g[k]), (name, k)
 
 
-@needs_assets
-def test_obj_reader_matches_reference_js(pkg):
+def test_obj_reader_matches_reference_js(pkg, ref_assets):
     from webgpu_path_tracer_amd.host import ObjReader
 
-    cube = ObjReader.load_model(ASSETS + "/cube.obj")
+    cube = ObjReader.load_model(os.path.join(ref_assets, "cube.obj"))
     for k in ("vertices", "normals"):
         g = np.fromfile(os.path.join(pkg.scenes.GOLDEN_DIR, "objcube_%s.bin" % k), np.float32)
         assert _same(cube[k], g), k
 
 
-@needs_assets
 @pytest.mark.parametrize("tag,fname", [("m5802", "monkey_5802.obj"), ("m15744", "monkey_smooth_15744.obj")])
-def test_large_mesh_bvh_hashes(pkg, tag, fname):
+def test_large_mesh_bvh_hashes(pkg, tag, fname, ref_assets):
     """5.8k / 15.7k triangle meshes: sha256 of bvh / triangles / transforms equal the reference's."""
     from webgpu_path_tracer_amd.host import ObjReader
 
     man = pkg.scenes.golden_manifest()[tag]
-    sc = pkg.scenes.mesh_scene(ObjReader.load_model(os.path.join(ASSETS, fname)), scale=(1.1, 1.1, 1.1), rotate=(math.pi / 4, [0, 1, 0]), translate=(0.65, -0.64, 0))
+    sc = pkg.scenes.mesh_scene(ObjReader.load_model(os.path.join(ref_assets, fname)), scale=(1.1, 1.1, 1.1), rotate=(math.pi / 4, [0, 1, 0]), translate=(0.65, -0.64, 0))
     b = sc.buffers(native=pkg.ptmi.NativeHost())
     for k in ("bvh", "triangles", "transforms"):
         assert hashlib.sha256(np.ascontiguousarray(b[k]).tobytes()).hexdigest() == man[k]["sha256"], k
@@ -209,14 +202,13 @@ def test_native_obj_parser_is_thread_count_invariant(pkg, monkeypatch):
             assert r[k].size == want[k].size and np.array_equal(r[k].view(np.uint32), want[k].view(np.uint32)), (t, k)
 
 
-@needs_assets
-def test_native_obj_parser_matches_python_on_reference_meshes(pkg):
+def test_native_obj_parser_matches_python_on_reference_meshes(pkg, ref_assets):
     import glob
 
     from webgpu_path_tracer_amd.host import ObjReader
 
     nat = pkg.ptmi.NativeHost()
-    files = sorted(glob.glob(ASSETS + "/*.obj"))
+    files = sorted(glob.glob(os.path.join(ref_assets, "*.obj")))
     assert len(files) >= 8
     for f in files:
         a, b = ObjReader.load_model(f), nat.load_obj(f)
@@ -244,12 +236,10 @@ def test_native_bvh_builder_is_thread_count_invariant(pkg, monkeypatch):
 
 
 @pytest.mark.parametrize("tag,fname,stored", [("c2sah", "monkey_968.obj", True), ("m5802sah", "monkey_5802.obj", False), ("m15744sah", "monkey_smooth_15744.obj", False)])
-def test_native_sah_builder_matches_reference_js(pkg, tag, fname, stored):
+def test_native_sah_builder_matches_reference_js(pkg, tag, fname, stored, ref_assets):
     """ptmi_build_bvh_sah vs the reference's own BVH.generate_bvh_heirarchy_SAH (dead code in the reference, run unchanged by
     oracle/capture/capture.mjs through the reference's populate_links / flattenBVH): byte-identical nodes and triangle order."""
-    path = os.path.join(ASSETS, fname)
-    if not os.path.exists(path):
-        pytest.skip("reference assets not present")
+    path = os.path.join(ref_assets, fname)
     from webgpu_path_tracer_amd.host import ObjReader
 
     man = pkg.scenes.golden_manifest()[tag]

@@ -41,13 +41,11 @@ def test_addon_loads_and_exports_surface(pkg):
 
 
 @needs_node
-def test_js_scene_code_matches_reference_buffers():
-    assets = os.path.join(REF, "assets")
-    out = _run([node, "check_host.mjs", os.path.join(ROOT, "tests", "golden"), assets], cwd=JS)
+def test_js_scene_code_matches_reference_buffers(ref_assets):
+    out = _run([node, "check_host.mjs", os.path.join(ROOT, "tests", "golden"), ref_assets], cwd=JS)
     rep = json.loads(out)
     assert len(rep) >= 17 and all(rep.values()), [k for k, v in rep.items() if not v]
-    if os.path.isdir(assets):
-        assert len(rep) == 49
+    assert len(rep) == 49
 
 
 @needs_node

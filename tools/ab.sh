@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/ab.sh "<bench args>" name1 name2 ...   — runs bench.py (no PMC, no CPU legs, no extra configs) with each A/B build
 # webgpu-path-tracer_amd/variants/libptmi_<name>.so ("base" = the in-tree library) and prints value + per-kernel ms
-args=$1; shift
+args="--full $1"; shift  # (the per-kernel table printed below is --full's)
 mkdir -p gpurun_out/ab
 for v in "$@"; do
   lib=""; [ "$v" != base ] && lib=$(pwd)/webgpu-path-tracer_amd/variants/libptmi_$v.so

@@ -13,7 +13,7 @@ for v in "$@"; do
     [[ "$item" == *:* ]] && { s=${item#*:}; spp="--spp ${s%%@*}"; }
     [[ "$item" == *@* ]] && { d=${item##*@}; dims="--width ${d%%x*} --height ${d##*x}"; }
     tag=$(echo "${v}_${item}" | tr '=+:@ /' '______')
-    env $envs PTMI_LIB=$lib timeout -k 10 300 python bench.py --workload $w --steps ${STEPS:-2} --warmup 1 --cpu-seconds 0 --pmc off --extra-configs off $spp $dims \
+    env $envs PTMI_LIB=$lib timeout -k 10 300 python bench.py --full --workload $w --steps ${STEPS:-2} --warmup 1 --cpu-seconds 0 --pmc off --extra-configs off $spp $dims \
       > gpurun_out/abq/$tag.json 2> gpurun_out/abq/$tag.err || { echo "$v $item FAILED"; tail -3 gpurun_out/abq/$tag.err; continue; }
     python3 - gpurun_out/abq/$tag.json "$v" "$item" <<'PY'
 import json, sys

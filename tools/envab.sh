@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: envab.sh "<bench args>" "VAR=val VAR2=val" ...
-args=$1; shift
+args="--full $1"; shift  # (the per-kernel table printed below is --full's)
 for e in "$@"; do
   env $e timeout -k 10 300 python bench.py $args --pmc off --cpu-seconds 0 --extra-configs off > /tmp/envab.json 2>/tmp/envab.err || { echo "$e FAILED"; tail -2 /tmp/envab.err; continue; }
   python3 - "$e" <<'PY'

@@ -12,21 +12,21 @@ if [ "$1" != quick ] && [ "$1" != extras ]; then
 fi
 if [ "$1" != extras ]; then
 SECONDS=0
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $R/bench_c2.json 2> $R/bench_c2.err || exit 1
-echo "bench.py --steps 20 --warmup 5: wall ${SECONDS} s" | tee $R/bench_c2_wall.txt
-timeout -k 10 600 python bench.py --workload c3 --steps 2 --cpu-seconds 10 --extra-configs off > $R/bench_c3.json 2> $R/bench_c3.err || exit 1
-timeout -k 10 600 python bench.py --workload c4 --steps 1 --cpu-seconds 10 --pmc-timeout 400 > $R/bench_c4.json 2> $R/bench_c4.err || exit 1
-timeout -k 10 600 python bench.py --workload c5 --width 3840 --height 2160 --spp 128 --steps 1 --cpu-seconds 10 --pmc-timeout 400 > $R/bench_c5.json 2> $R/bench_c5.err || exit 1
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $R/bench_c2.json 2> $R/bench_c2.err || exit 1
+echo "bench.py --full --steps 20 --warmup 5: wall ${SECONDS} s" | tee $R/bench_c2_wall.txt
+timeout -k 10 600 python bench.py --full --workload c3 --steps 2 --cpu-seconds 10 --extra-configs off > $R/bench_c3.json 2> $R/bench_c3.err || exit 1
+timeout -k 10 600 python bench.py --full --workload c4 --steps 1 --cpu-seconds 10 --pmc-timeout 400 > $R/bench_c4.json 2> $R/bench_c4.err || exit 1
+timeout -k 10 600 python bench.py --full --workload c5 --width 3840 --height 2160 --spp 128 --steps 1 --cpu-seconds 10 --pmc-timeout 400 > $R/bench_c5.json 2> $R/bench_c5.err || exit 1
 # the opt-in SAH tree (lib/BVH/bvhNode.js:108-283, built on the GPU: ptmi_build_scene_bvh_sah) on the same box, with its own counter passes
-timeout -k 10 600 python bench.py --workload c3 --bvh sah --steps 2 --cpu-seconds 0 --extra-configs off > $R/bench_c3_sah.json 2> $R/bench_c3_sah.err || exit 1
-timeout -k 10 600 python bench.py --workload c4 --bvh sah --steps 1 --cpu-seconds 0 --pmc-timeout 400 > $R/bench_c4_sah.json 2> $R/bench_c4_sah.err || exit 1
-timeout -k 10 600 python bench.py --workload c5 --bvh sah --width 3840 --height 2160 --spp 128 --steps 1 --cpu-seconds 0 --pmc-timeout 400 > $R/bench_c5_sah.json 2> $R/bench_c5_sah.err || exit 1
+timeout -k 10 600 python bench.py --full --workload c3 --bvh sah --steps 2 --cpu-seconds 0 --extra-configs off > $R/bench_c3_sah.json 2> $R/bench_c3_sah.err || exit 1
+timeout -k 10 600 python bench.py --full --workload c4 --bvh sah --steps 1 --cpu-seconds 0 --pmc-timeout 400 > $R/bench_c4_sah.json 2> $R/bench_c4_sah.err || exit 1
+timeout -k 10 600 python bench.py --full --workload c5 --bvh sah --width 3840 --height 2160 --spp 128 --steps 1 --cpu-seconds 0 --pmc-timeout 400 > $R/bench_c5_sah.json 2> $R/bench_c5_sah.err || exit 1
 # rocprofv3 kernel stats of the bench command itself (its own --pmc child passes off: one profiler at a time)
 export PTMI_PLACEMENT_TRIES=1  # (the placement search's dry runs are launches of the same kernels: kept out of the averages)
 for w in c2 c3 c4 c5; do
   rm -rf /tmp/ks_$w
   x=""; [ $w = c4 ] && x="--spp 128"; [ $w = c5 ] && x="--width 3840 --height 2160 --spp 64"
-  (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$w -o run -- python3 $root/bench.py --workload $w $x --steps 3 --warmup 1 --cpu-seconds 0 --pmc off --extra-configs off > $root/$R/ks_$w.log 2>&1) || exit 1
+  (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$w -o run -- python3 $root/bench.py --full --workload $w $x --steps 3 --warmup 1 --cpu-seconds 0 --pmc off --extra-configs off > $root/$R/ks_$w.log 2>&1) || exit 1
   cp $(find /tmp/ks_$w -name '*kernel_stats.csv' | head -1) $R/kernel_stats_$w.csv || exit 1
 done
 unset PTMI_PLACEMENT_TRIES

@@ -9,7 +9,7 @@ import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; k=r['kernels']; w=r['work_per_ray']
 rays=d['config']['rays_per_step']; bv=k['k_bvh']['ms_per_step']
 print('$1: %.0f Mrays/s  %.2f ms/step  bvh %.1f ms  shade %.1f ms  visits/ray %.1f tri/ray %.2f -> %.1f G bvh-visits/s' % (d['value'], d['ms_per_step'], bv, k['k_shade']['ms_per_step'], w['bvh_node_visits'], w['tri_tests'], rays*w['bvh_node_visits']/max(bv,1e-9)/1e6))"; }
-B="--steps 2 --warmup 1 --cpu-seconds 0 --pmc off --extra-configs off"
+B="--full --steps 2 --warmup 1 --cpu-seconds 0 --pmc off --extra-configs off"  # (line() reads the per-kernel table: --full's)
 case $1 in
 size)
   for t in 8000 26000 65000 131000 262267 524000 1048000; do
