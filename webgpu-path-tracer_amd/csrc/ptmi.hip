@@ -133,6 +133,7 @@ struct Tuning {
   int bvh_carry_min_paths = 4 << 20, bvh_carry_min_depth = 12;  // PTMI_BVH_CARRY_MIN_PATHS / _MIN_DEPTH: batches and trees below these are traced without carrying (tests: 0)
   int sort = -1;               // PTMI_SORT: k_shade sorts its chunks by material class (-1 = when the scene has more than one)
   int shade_blocks_per_cu = 0; // PTMI_SHADE_BLOCKS_PER_CU (0 = from the variant's occupancy)
+  int shade_cont = 16;         // PTMI_SHADE_CONT: k_shade shades a flush pass's new rays that need no tree walk in the same launch when at least this many lanes have one (progressive mode, one material class; 0 = never)
   int tail_limit = -1;         // PTMI_TAIL_LIMIT: k_tail takes queues of at most this many slots (-1 = kTailLimitFirst / kTailLimitLater, 0 = never)
   bool render_ahead = true;    // PTMI_RENDER_AHEAD=0
   int path_budget_log2 = 30;   // PTMI_PATH_BUDGET_LOG2: paths per wavefront pass with frames_in_flight = auto (round 5: 29 -> 30)
@@ -691,6 +692,7 @@ void load_tuning(ptmi_ctx* c) {
   t.bvh_carry_min_depth = std::max(0, env_int("PTMI_BVH_CARRY_MIN_DEPTH", t.bvh_carry_min_depth));
   t.sort = env_int("PTMI_SORT", -1);
   t.shade_blocks_per_cu = env_int("PTMI_SHADE_BLOCKS_PER_CU", 0);
+  t.shade_cont = std::max(0, std::min(64, env_int("PTMI_SHADE_CONT", t.shade_cont)));
   t.tail_limit = env_int("PTMI_TAIL_LIMIT", -1);
   t.render_ahead = env_int("PTMI_RENDER_AHEAD", 1) != 0;
   t.path_budget_log2 = std::max(16, std::min(31, env_int("PTMI_PATH_BUDGET_LOG2", t.path_budget_log2)));
@@ -952,6 +954,7 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   rc.reset_first = reset_first;
   rc.rank = c->rank, rc.world = c->world, rc.tile = c->tile;
   rc.n_local = count_local(rc.npix, c->rank, c->world, c->tile);
+  rc.shade_cont = (uint32_t)c->tun.shade_cont;
   if (rc.n_local == 0) return PTMI_OK;
 
   const int n_steps = rc.num_samples * p.max_bounces;

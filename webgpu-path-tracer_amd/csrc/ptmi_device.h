@@ -64,7 +64,7 @@ enum : int {
   LT_GROUP = 0, LT_VALID = 1, LT_MISS = 2, LT_HIT = 3, LT_RH_SPHERE = 4, LT_RH_VOLUME = 5, LT_RH_QUAD = 6, LT_RH_TRI = 7, LT_MS_LAMBERT = 8, LT_MS_MIRROR = 9,
   LT_MS_GLASS = 10, LT_MS_ISO = 11, LT_RR = 12, LT_ACC_CONT = 13, LT_END_SAMPLE = 14, LT_END_CHANGES = 15, LT_FLUSH = 16, LT_QUAD_LOOP = 17, LT_QUAD_FRONT = 18,
   LT_QUAD_DENOM = 19, LT_QUAD_T = 20, LT_QUAD_ACCEPT = 21, LT_ROOT_BOX = 22, LT_MISS_SHORTCUT = 23, LT_KEEP = 24, LT_DIV3_SLOW = 25, LT_RCP_SLOW = 26, LT_SQRT_SLOW = 27,
-  LT_SPHERE_LOOP = 28, LT_IS_LIGHT = 29, LT_STAGE = 30
+  LT_SPHERE_LOOP = 28, LT_IS_LIGHT = 29, LT_STAGE = 30, LT_CONT = 31, LT_HOLE = 32
 };
 
 // ---- constants of shaders/header.wgsl:1-13,37 (abstract-float consts folded in f64, rounded once) ----
@@ -360,6 +360,7 @@ struct RenderConst {
   // shard
   uint32_t n_local;
   int rank, world, tile;
+  uint32_t shade_cont;  // k_shade: a flush pass whose new rays need no tree walk on at least this many lanes shades them at once (0 = never; Tuning::shade_cont)
 };
 
 DEV uint32_t local_to_pixel(const RenderConst& rc, uint32_t j) {

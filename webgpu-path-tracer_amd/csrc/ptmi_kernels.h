@@ -598,6 +598,7 @@ DEV bool shade_one(const DevScene& S, const RenderConst& rc, const Paths& P, con
 // (Measured and settled, so no longer build options: the sorted variants wave by wave with per-class bins instead of the block version's LDS counting sort
 // — bit-exact, 2.5 % slower on configs[4], profiles/r04_sort_wave_ab.txt —; every variant through the block version; other region / chunk sizes.)
 constexpr uint32_t kRegionDiv = 16;  // a block's share of the queue is claimed in this many regions (x4: every wave claims its own)
+constexpr uint32_t kRegionDivCont = 64;  // ... when k_shade continues paths in the launch (rc.shade_cont): a wave then writes a few tenths of what it reads, in smaller regions
 constexpr int kTailLimitFirst = 2 << 20, kTailLimitLater = 1 << 20;  // k_tail takes a queue over when it is at most this long (slots): at step 0 (a lone 1080p frame fits) / later (round 4: 512 Ki -> 1 Mi since its tree walk waits for 24 lanes — 8-frame batches of configs[1] +5 %, 64-frame ones and configs[2] unchanged: profiles/r04_tail_limit_ab.txt)
 constexpr int kTailLimitFirstShallow = 24 << 20, kTailLimitLaterShallow = 2 << 20;  // ... on trees under 12 levels (render_batch)
 constexpr int kTailLimitFirstDeep = 6 << 20;  // ... on deeper ones, whose walks park their stragglers (render_batch)
@@ -839,6 +840,8 @@ DEV void shade_body(const DevScene& S, const RenderConst& rc, const Paths& P, St
 // ray_color's loop body for scenes with ONE material class (no sort): every WAVE on its own, no barrier inside the loop.  A wave shades
 // the same 64-slot groups of the block's chunks as in shade_body, stages its survivors in an LDS ring of its own (128 entries) and runs a
 // flush pass — hitScene part 1 for 64 new rays, all lanes busy — whenever 64 are waiting; what is left goes out in one last, partial pass.
+// In progressive mode, a flush pass in which at least rc.shade_cont new rays have their final hit record (no root box entered) keeps those rays:
+// the wave shades them next, as a pass of its own, and only the rays that need k_bvh go to the next queue (continuation, round 6).
 // (shade_body's three barriers per chunk had every wave wait for the block's slowest three times per 128 slots of its own work.)
 template <bool IS, bool COUNT, bool MULTI>
 DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
@@ -863,14 +866,19 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
   const uint32_t n_carried = resv ? min(ctl->n_carried, resv) : 0u;  // (Carry: slots [n_carried, resv) of this queue hold nothing)
   uint32_t n = ctl->n_rays;
   if (n <= resv && n_carried == 0u) n = 0u;
-  const uint32_t region = max((uint32_t)kSChunk, ((n / gridDim.x / kRegionDiv) + 511u) & ~511u);
-  const uint32_t wregion = region / kWaves;
+  const uint32_t cont_min = MULTI ? 0u : rc.shade_cont;  // (wave-uniform) continuation passes: see the main loop
+  const uint32_t region_full = max((uint32_t)kSChunk, ((n / gridDim.x / kRegionDiv) + 511u) & ~511u);
+  const uint32_t region = cont_min ? max((uint32_t)kSChunk, ((n / gridDim.x / kRegionDivCont) + 511u) & ~511u) : region_full;  // (the block's first claim)
+  const uint32_t wregion = region / kWaves, wregion_full = region_full / kWaves;
+  bool pred = true;  // (wave-uniform) the wave's last flush pass had cont_min lanes that need no tree walk: its next one is expected to continue too
   uint32_t w_cur = 0, w_rend = 0;  // this wave's current output region of the next queue (wave-uniform)
   uint32_t head = 0, cnt = 0;      // the ring: `cnt` survivors wait from entry `head` on (wave-uniform)
   uint32_t my_valid = 0, my_missed = 0;
   Counters cn = {0, 0, 0, 0, 0};
-  // hitScene part 1 for the first `take` (<= 64) waiting survivors, one per lane; settles definite misses, places the others in the next queue
-  auto flush_pass = [&](uint32_t take) {
+  // hitScene part 1 for the first `take` (<= 64) waiting survivors, one per lane; settles definite misses, places the others in the next queue —
+  // except, with `cont` and at least cont_min of them, the rays whose hit record is final already (no root box entered): their complete state goes
+  // to `cs` instead, and the lanes that return true are the wave's next shade pass
+  auto flush_pass = [&](uint32_t take, SlotState& cs, bool cont) {
     const uint32_t q = (head + (uint32_t)lane) & (kRing - 1u);
     bool keep = false;
     float2 tp = make_float2(0.0f, 0.0f);
@@ -890,16 +898,25 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
         keep = true;
       }
     }
+    bool go = false;
+    if (cont_min) {
+      const bool final_hit = keep && (hm & HITMAT_BVH) == 0u;  // (a continued ray never has a triangle hit, and it is never a step-0 ray)
+      pred = (uint32_t)__popcll(__ballot(final_hit)) >= cont_min;
+      if (cont && pred) {
+        go = final_hit;
+        keep = keep && !final_hit;
+      }
+    }
     const uint64_t km = __ballot(keep);
     const uint32_t kept = (uint32_t)__popcll(km);
-    my_missed += take - kept;
+    my_missed += take - kept - (uint32_t)__popcll(__ballot(go));  // (a continued ray's hitScene invocation is tallied where it is shaded, as my_valid)
     if (kept) {
       const uint32_t rank = lanes_below(km);
       const uint32_t b0 = w_cur, n0 = min(kept, w_rend - w_cur);
       uint32_t b1 = 0xffffffffu;
       w_cur += n0;
       if (kept > n0) {  // claim the wave's next region for the rest
-        uint32_t nb = 0;
+        uint32_t nb = 0, wregion_next = wregion;
         bool full;
         if (w_rend == 0u) {  // the wave's first region: its quarter of the block's claim
           if (lane == 0) nb = atomicCAS(&s_region0, kR0Empty, kR0Busy);
@@ -924,19 +941,21 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
           }
           full = nb == kR0Full;
           nb += wv * wregion;
-        } else {
-          if (lane == 0) nb = atomicAdd(&ctl[1].n_rays, wregion);
+        } else {  // (a wave that stores most of its rays claims as much as without continuation: as many atomics, as few holes)
+          const uint32_t wr = pred ? wregion : wregion_full;
+          if (lane == 0) nb = atomicAdd(&ctl[1].n_rays, wr);
           nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
-          full = nb + wregion > P.cap;
+          full = nb + wr > P.cap;
           if (full && lane == 0) {
             atomicAdd(&totals[15], 1ull);
-            atomicSub(&ctl[1].n_rays, wregion);
+            atomicSub(&ctl[1].n_rays, wr);
           }
+          wregion_next = wr;
         }
         if (!full) {  // (full: what still fitted is written, the rest is dropped and flagged — see shade_body)
           b1 = nb;
           w_cur = nb + (kept - n0);
-          w_rend = nb + wregion;
+          w_rend = nb + wregion_next;
         }
       }
       if (keep && (rank < n0 || b1 != 0xffffffffu)) {
@@ -951,9 +970,21 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
         P.hout.mat[dst] = hm;
       }
     }
+    if (cont) {  // (read before the pass that shades them stages its survivors over these entries; written on every lane, so that nothing of the
+                 // group `cs` held before stays live across the flush)
+      if (go) LT(LT_CONT);
+      cs.q0 = r0[q];
+      cs.q0.w = __uint_as_float(rng);
+      cs.q1 = r1[q];
+      cs.q2 = r2[q];
+      cs.tp = tp;
+      cs.hitmat = hm;
+      cs.slot = 0u;  // (read by tri_fetch for triangle hits only)
+    }
     head = (head + take) & (kRing - 1u);
     cnt -= take;
     TT(TT_FLUSH_STORE, 0.0f);
+    return go;
   };
   // ray_color's loop body for the slots of the lanes with `active`, their state in `st` (load_slot); survivors go into the ring
   auto shade_group = [&](bool active, const SlotState& st) {
@@ -1002,23 +1033,35 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
       if (act) st = load_slot(P, base + j, first != 0, rc);
       return act;
     };
+    // Continuation (cont_min > 0): a flush pass whose rays need no tree walk on at least cont_min lanes hands their state, in registers, to the next
+    // iteration, which shades exactly those lanes instead of an input group.  When a flush is due and expected to continue (`pred`: the wave's last one
+    // did), the next input group is asked for after it, not before: prefetched, its 16 registers would be live across the continuation pass.  A wave
+    // whose flushes do not qualify (rays inside the tree's root box: configs[3]) keeps the prefetch and stores everything, as without continuation.
     SlotState cur;
-    bool have = settle(), cur_act = false;
+    bool have = settle(), cur_act = false, again = false;  // again: `cur` holds a continuation pass, not the input group (base, j0) (wave-uniform)
     if (have) cur_act = fetch(cur);
 #pragma unroll 1
-    while (have) {
+    while (have || again) {
       shade_group(cur_act, cur);
-      j0 += kBlock;
-      have = settle();
+      if (!again) {
+        j0 += kBlock;
+        have = settle();
+      }
+      const bool flush_due = cnt >= 64u;
+      const bool pre = have && !(cont_min && flush_due && pred);
       SlotState nxt;
       bool nxt_act = false;
-      if (have) nxt_act = fetch(nxt);
-      if (cnt >= 64u) flush_pass(64u);
+      if (pre) nxt_act = fetch(nxt);
+      bool go = false;
+      if (flush_due) go = flush_pass(64u, nxt, cont_min != 0u && !pre);  // (prefetched: everything is stored, the pass only renews `pred`)
+      again = __ballot(go) != 0ull;
+      if (again) nxt_act = go;
+      else if (have && !pre) nxt_act = fetch(nxt);
       cur = nxt;
       cur_act = nxt_act;
     }
+    if (cnt) flush_pass(cnt, cur, false);
   }
-  if (cnt) flush_pass(cnt);
   if (MULTI) my_missed = 0;  // (no path ends in the flush phase then)
   if (lane == 0 && my_missed + my_valid) atomicAdd(tally_line(totals, blockIdx.x), my_missed + my_valid);
   __syncthreads();  // the block's claim, if any wave made one, is in s_region0 now
@@ -1035,9 +1078,14 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
     w_rend = w_cur + wregion;
   }
   for (uint32_t i = w_cur + (uint32_t)lane; i < w_rend; i += 64u) {
+    LT(LT_HOLE);
     reinterpret_cast<uint32_t*>(P.out.q1 + i)[3] = PID_HOLE;
     P.hout.mat[i] = HITMAT_HOLE;
   }
+#ifdef PTMI_LANE_TALLY
+  __syncthreads();
+  if (threadIdx.x >= 2 * LT_HOLE && threadIdx.x < 2 * LT_HOLE + 2 && s_lane_tally[threadIdx.x]) atomicAdd(&g_lane_tally[threadIdx.x], (unsigned long long)s_lane_tally[threadIdx.x]);
+#endif
   if (COUNT) reduce_counters(cn, totals, false);
 }
 
@@ -1045,10 +1093,11 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
 //  * the new rays BINNED BY THE SIGNS OF THEIR DIRECTION before the flush pass (eight waves of a 512-thread block sharing eight lock-free LDS rings): rays of one octant agree
 //    on every axis-aligned quad's facing test, so the pass runs 2.0 quads instead of 3.9 per group at 63 lanes instead of 32 — a quarter of the kernel's vector instructions
 //    gone, and its time unchanged (7.9 against 7.75 ms on configs[1]);
-//  * the body AS A LOOP: a lane keeps its path from bounce to bounce while the new ray needs no tree walk, only rays that entered the root box go through the next queue
-//    (one in twelve on configs[1]: most of the kernel's traffic gone, k_bvh -16 % on dense queues) — and k_shade +7 %, its passes at 45-56 lanes instead of 63.
-//  Together with a probe that ADDS traffic (16 bytes more per kept ray, +12 %: +6-8 % time) they say what the kernel is bound by: neither issue slots nor bytes but the
-//  round trips of a wave's dependent chain at six waves per SIMD.  profiles/r05_shade_bins_ab.txt, r05_shade_loop_ab.txt, NOTES_r05 §3.)
+//  * the body AS A LOOP: a lane kept its path from bounce to bounce while the new ray needed no tree walk and took a new slot only once 16 lanes were idle — k_bvh -16 % on
+//    dense queues, k_shade +7 %, its passes at 45-56 lanes instead of 63.
+//  The continuation passes above keep the loop's gain without its cost: they are whole passes of the rays one flush made ready (46 lanes wide on configs[1], 39 on
+//  configs[2]) between full-width input groups and flushes, and the state of a continued ray never leaves the CU.  configs[1]: k_shade -9 %, k_bvh -20 %, +9 % in all;
+//  configs[2]-[4] within +-0.3 %.  profiles/r05_shade_bins_ab.txt, r05_shade_loop_ab.txt, r06_shade_cont_ab.txt, NOTES_r05 §3.)
 // The kernel proper, twice: the progressive-mode variants without importance sampling fit 80 VGPRs — 6 waves per SIMD, which this
 // latency-bound kernel turns into throughput (round 3: 5 -> 6 blocks per CU, -8 %) —, the others need up to 96 (5 waves; at 80 they spill).
 template <bool IS, bool SORT, bool COUNT, bool MULTI>
