@@ -1,7 +1,8 @@
 #!/bin/bash
-# usage: res.sh out.s [extra flags]  -- compile ptmi.hip device-only to asm and list per-kernel resources
+# usage: tools/kernel_resources.sh out.s [extra flags]  -- compile ptmi.hip device-only to asm and list per-kernel resources
 out=$1; shift
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize -Wno-unused-command-line-argument "$@" --cuda-device-only -S -o $out /root/repo/webgpu-path-tracer_amd/csrc/ptmi.hip 2>&1 | grep -v warning | head
+src=$(cd "$(dirname "$0")/.." && pwd)/webgpu-path-tracer_amd/csrc/ptmi.hip
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize -Wno-unused-command-line-argument "$@" --cuda-device-only -S -o $out "$src" 2>&1 | grep -v warning | head
 python3 - $out <<'PY'
 import re,sys,subprocess
 txt=open(sys.argv[1]).read()

@@ -12,9 +12,11 @@
 #include <condition_variable>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ptmi.h"
@@ -169,7 +171,7 @@ struct ptmi_ctx {
   int bvh_depth = 0;             // max number of inner nodes on a root-to-leaf path
   bool has_unknown_material = false;
   int material_classes = 0;      // distinct shade bins among the materials: k_shade sorts only when > 1
-  int shade_blocks_per_cu[16] = {0};  // per k_shade variant: resident 256-thread blocks per CU (0 = not asked yet)
+  std::map<const void*, int> shade_blocks_per_cu;  // per k_shade instance (shade_kernel): resident 256-thread blocks per CU, asked once
 
   int W = 0, H = 0;
   DBuf d_fb_own;
@@ -651,23 +653,68 @@ Paths paths_of(ptmi_ctx* c, int step, bool with_pixsum) {
   return P;
 }
 
-// the k_shade instance for a parameter combination (occupancy queries)
-const void* shade_kernel(bool is, bool so, bool cn, bool mu) {
-  if (!is && !mu) {  // progressive mode without importance sampling: the 80-VGPR build (k_shade6)
-    if (so) return cn ? reinterpret_cast<const void*>(&k_shade6<true, true>) : reinterpret_cast<const void*>(&k_shade6<true, false>);
-    return cn ? reinterpret_cast<const void*>(&k_shade6<false, true>) : reinterpret_cast<const void*>(&k_shade6<false, false>);
-  }
-#define PTMI_SK(I, S, C, M) \
-  if (is == I && so == S && cn == C && mu == M) return reinterpret_cast<const void*>(&k_shade<I, S, C, M>)
-  PTMI_SK(false, false, false, true); PTMI_SK(false, false, true, true);  // (IS = MULTI = false is k_shade6 above: those four are never instantiated)
-  PTMI_SK(false, true, false, true); PTMI_SK(false, true, true, true);
-  PTMI_SK(true, false, false, false); PTMI_SK(true, false, false, true); PTMI_SK(true, false, true, false); PTMI_SK(true, false, true, true);
-  PTMI_SK(true, true, false, false); PTMI_SK(true, true, false, true); PTMI_SK(true, true, true, false); PTMI_SK(true, true, true, true);
-#undef PTMI_SK
-  return nullptr;
+// Run-time flags -> template instance: with_flags(f, a, b, ...) returns f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...).  Every templated
+// launch picks its kernel through it; only the instances that f's body names for some combination are compiled.
+template <class F>
+auto with_flags(F&& f) {
+  return f();
+}
+template <class F, class... B>
+auto with_flags(F&& f, bool b, B... rest) {
+  if (b) return with_flags([&](auto... t) { return f(std::true_type{}, t...); }, rest...);
+  return with_flags([&](auto... t) { return f(std::false_type{}, t...); }, rest...);
+}
+
+// Progressive mode without importance sampling runs the 80-VGPR builds, 6 waves per SIMD: k_shade6 (the k_shade instances it replaces are never made)
+// and, on scenes without spheres, k_tail6.  Each pair takes the same arguments: the pointer serves the launch and the occupancy query alike.
+template <bool IS, bool SORT, bool COUNT, bool MULTI>
+constexpr auto shade_kernel() {
+  if constexpr (!IS && !MULTI) return &k_shade6<SORT, COUNT>;
+  else return &k_shade<IS, SORT, COUNT, MULTI>;
+}
+template <bool SIX, bool IS, bool COUNT, bool MULTI, bool NOABORT>
+constexpr auto tail_kernel() {
+  if constexpr (SIX) return &k_tail6<COUNT, NOABORT>;
+  else return &k_tail<IS, COUNT, MULTI, NOABORT>;
 }
 
 int stack_alloc_for(const ptmi_ctx* c) { return std::max(1, std::min(c->prm.stack_size, std::max(c->bvh_depth, 1))); }
+
+// A tree walk's stack (k_bvh, k_tail): stack_alloc_for + `extra` entries per lane, the first tun.lds_stack (10) in LDS — 2 words per entry and lane —,
+// the rest (rarely reached) in a per-wave spill area.
+struct StackLayout {
+  int lds_entries, spill_entries;
+  size_t lds_bytes;
+  bool noabort;
+};
+StackLayout stack_layout(const ptmi_ctx* c, int extra) {
+  const int sa = stack_alloc_for(c) + extra;
+  const int le = std::min(sa, c->tun.lds_stack);
+  // The abort of Q7 (hitRay.wgsl:106-109) needs sp to reach STACK_SIZE; sp never exceeds the number of inner nodes on a
+  // root-to-leaf path.  PTMI_NOABORT=0 keeps the literal stack discipline for A/B runs.
+  const bool noabort = c->bvh_depth < c->prm.stack_size && c->tun.noabort;
+  return StackLayout{le, sa - le, (size_t)le * 2 * 64 * sizeof(int), noabort};
+}
+
+// k_tail's build, and the queues it traces to the end in one launch instead of a k_bvh + k_shade pair per bounce: at most limit_first slots at step 0
+// (a whole small batch — a lone 1080p frame), limit_later at later steps (only their thin ends: on deep trees a lane-per-path wave waits for its longest
+// traversal, and the wavefront kernels with their lane refill stay ahead down to ~0.5 Mi slots).  0 = never launched.
+struct TailPlan {
+  bool six;  // progressive mode without importance sampling on a scene without spheres: the 80-VGPR build, 6 waves per SIMD (k_tail6)
+  uint32_t limit_first, limit_later;
+};
+TailPlan tail_plan(const ptmi_ctx* c, const RenderConst& rc) {
+  // Where k_tail's weak spot — the tree walk, as long as the wave's longest ray — is short, it stays ahead of the per-bounce kernels far longer (round 5,
+  // profiles/r05_tail_first_sweep*.txt): on configs[1]'s 11-level tree it wins up to ~24 Mi paths per batch (4 Mi paths: 0.94 ms against 1.54; 16.6 Mi — one rank of eight at
+  // fixed total spp, or an 8-frame render-ahead batch — 2.87 against 3.26).  On deep trees, since its walks park their stragglers (launch_tail), up to ~16 Mi paths on the
+  // 871 k-triangle scene (4 Mi: 3.5 ms against 6.5; 8 Mi: 4.9 against 6.4) but only ~4 Mi inside the 262 k-triangle room (8 Mi: 22.1 against 20.8): 6 Mi.  The builds with
+  // importance sampling, several samples or spheres (100-130 VGPRs, 4 waves per SIMD) keep 2 Mi.  Later steps' queues: from 2 Mi down on shallow trees, 1 Mi otherwise.
+  const bool six = !c->prm.importance_sampling && rc.num_samples == 1 && c->S.n_spheres == 0 && c->tun.tail6;
+  const bool shallow = six && c->S.n_nodes > 0 && c->bvh_depth < 12, deep = six && c->S.n_nodes > 0 && c->bvh_depth >= 12 && c->tun.tail_park > 0;
+  const int env = c->tun.tail_limit;
+  return TailPlan{six, (uint32_t)(env >= 0 ? env : shallow ? kTailLimitFirstShallow : deep ? kTailLimitFirstDeep : kTailLimitFirst),
+                  (uint32_t)(env >= 0 ? env : shallow ? kTailLimitLaterShallow : kTailLimitLater)};
+}
 
 int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
@@ -708,23 +755,17 @@ int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_ite
   const uint32_t pgrid = std::max<uint32_t>(1, std::min<uint32_t>((max_items + kBlock - 1) / kBlock, (uint32_t)c->num_cus * 32));
   if (with_prims) {
     ScopedSpan sp(c, T_PRIMS);
-    if (c->counters) hipLaunchKernelGGL(k_prims<true>, dim3(pgrid), dim3(kBlock), 0, c->stream, c->S, P, ctl, c->d_heads.as<uint32_t>(), tot);
-    else hipLaunchKernelGGL(k_prims<false>, dim3(pgrid), dim3(kBlock), 0, c->stream, c->S, P, ctl, c->d_heads.as<uint32_t>(), tot);
+    const auto prims = with_flags([](auto cn) { return &k_prims<cn>; }, c->counters);
+    hipLaunchKernelGGL(prims, dim3(pgrid), dim3(kBlock), 0, c->stream, c->S, P, ctl, c->d_heads.as<uint32_t>(), tot);
   }
   if (c->S.n_nodes <= 0) return PTMI_OK;
   ScopedSpan sp(c, T_BVH);
-  // Stack entries per lane: the first tun.lds_stack (10) in LDS, the rest (rarely reached) in a per-wave spill area.
-  // 10 entries x 512 B + the candidate buffer (1 KB since round 4's three-group scan) = 6 KB per wave: 26 waves fit a CU's 160 KB, and the kernel's 66 VGPRs
+  // 10 stack entries x 512 B + the candidate buffer (1 KB since round 4's three-group scan) = 6 KB per wave: 26 waves fit a CU's 160 KB, and the kernel's 66 VGPRs
   // admit 7 waves per SIMD.  (Round 3: the kernel runs at the rate of the CU's L1 gather path — tools/gather_probe*.hip, 2.8 clocks per
   // 64-byte record — so occupancy beyond ~18 waves buys 0-3 %: configs[1] 4.53 -> 4.18 ms, configs[3] 482 -> 481.)
   const Tuning& tun = c->tun;
-  const int sa = stack_alloc_for(c);
-  const int le = std::min(sa, tun.lds_stack);
-  const int se = sa - le;
-  const size_t lds = (size_t)le * 2 * 64 * sizeof(int) + kCandSlots * sizeof(uint32_t);  // stacks (2 words/entry) + candidate buffer
-  // The abort of Q7 (hitRay.wgsl:106-109) needs sp to reach STACK_SIZE; sp never exceeds the number of inner nodes on a
-  // root-to-leaf path.  PTMI_NOABORT=0 keeps the literal stack discipline for A/B runs.
-  const bool noabort = c->bvh_depth < c->prm.stack_size && tun.noabort;
+  const StackLayout st = stack_layout(c, 0);
+  const size_t lds = st.lds_bytes + kCandSlots * sizeof(uint32_t);  // stacks + candidate buffer
   int waves_per_cu = (int)std::min<size_t>(28, (size_t)(160 * 1024) / (lds + 64));
   if (tun.waves_per_cu > 0) waves_per_cu = tun.waves_per_cu;  // tuning aid; 0/unset = auto
   const uint32_t want = (max_items + 63) / 64;
@@ -733,88 +774,35 @@ int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_ite
   // same-address global atomics serialise at ~11 ns each (configs[1]: +2 %).
   const uint32_t n_teams = (uint32_t)tun.bvh_teams;
   // (the counters are zeroed by the kernel that filled this queue)
-  HIP_TRY(c, c->d_spill.ensure(std::max<size_t>(16, (size_t)std::max<uint32_t>(grid, (uint32_t)c->num_cus * 32) * (size_t)se * 64 * sizeof(int2))));
-  const int thr = tun.refill, leaf_batch = tun.leaf_batch;
-  const uint32_t range_cap = (uint32_t)tun.bvh_range;
+  HIP_TRY(c, c->d_spill.ensure(std::max<size_t>(16, (size_t)std::max<uint32_t>(grid, (uint32_t)c->num_cus * 32) * (size_t)st.spill_entries * 64 * sizeof(int2))));
   // step 0's queue does not store the rays' common origin (k_generate): the kernel is handed cam_origin
   float4 cam = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (first_rc) cam = make_float4(first_rc->cam_o[0], first_rc->cam_o[1], first_rc->cam_o[2], 1.0f);
-#define PTMI_LAUNCH_BVH(CNT, NA)                                                                                                                                       \
-  hipLaunchKernelGGL((k_bvh2<CNT, NA>), dim3(grid), dim3(64), lds, c->stream, c->S, P, ctl, c->d_heads.as<uint32_t>(), n_teams, c->prm.stack_size, le, se, \
-                     c->d_spill.as<int2>(), thr, leaf_batch, tot, range_cap, cam, cy)
-  if (c->counters) {
-    if (noabort) PTMI_LAUNCH_BVH(true, true);
-    else PTMI_LAUNCH_BVH(true, false);
-  } else {
-    if (noabort) PTMI_LAUNCH_BVH(false, true);
-    else PTMI_LAUNCH_BVH(false, false);
-  }
-#undef PTMI_LAUNCH_BVH
+  const auto bvh = with_flags([](auto cn, auto na) { return &k_bvh2<cn, na>; }, c->counters, st.noabort);
+  hipLaunchKernelGGL(bvh, dim3(grid), dim3(64), lds, c->stream, c->S, P, ctl, c->d_heads.as<uint32_t>(), n_teams, c->prm.stack_size, st.lds_entries, st.spill_entries,
+                     c->d_spill.as<int2>(), tun.refill, tun.leaf_batch, tot, (uint32_t)tun.bvh_range, cam, cy);
   HIP_TRY(c, hipGetLastError());
   return PTMI_OK;
 }
 
-// k_tail in front of a step: traces the step's queue to the end if it is short (PTMI_TAIL_LIMIT slots, 0 = never launched), else returns at once.
-int launch_tail(ptmi_ctx* c, const RenderConst& rc, const Paths& P, StepCtl* ctl, int first, uint32_t limit, const Carry& cy_in) {
+// k_tail in front of a step: traces the step's queue to the end if it is short (at most `limit` slots), else returns at once.  `six`: k_tail6 (tail_plan).
+int launch_tail(ptmi_ctx* c, const RenderConst& rc, const Paths& P, StepCtl* ctl, int first, uint32_t limit, bool six, const Carry& cy_in) {
   // On trees of 12 levels and more a walk stops once fewer than tun.tail_park lanes are left in it while other lanes have work; the stragglers' state waits in three entries
   // on top of their stacks (tail_body).  Shallow trees never park: their walks are short, and a parked ray's path waits for the next walk (round 4 measured both).
   Carry cy = cy_in;
   cy.park_below = (c->S.n_nodes > 0 && c->bvh_depth >= 12) ? c->tun.tail_park : 0;  // (shallower: configs[1] -4 % at 8 lanes, +4 % at 16, the default scene +37 %: profiles/r05_tail_park_shallow.txt)
-  const int sa = stack_alloc_for(c) + (cy.park_below > 0 ? 3 : 0);
-  const int le = std::min(sa, c->tun.lds_stack);
-  const int se = sa - le;
-  const size_t lds = (size_t)le * 2 * 64 * sizeof(int);
-  const bool noabort = c->bvh_depth < c->prm.stack_size && c->tun.noabort;
-  // progressive mode without importance sampling on a scene without spheres: the 80-VGPR build, 6 waves per SIMD (k_tail6)
-  const bool six = !c->prm.importance_sampling && rc.num_samples == 1 && c->S.n_spheres == 0 && c->tun.tail6;
+  const StackLayout st = stack_layout(c, cy.park_below > 0 ? 3 : 0);
   const int waves_per_cu = c->tun.tail_waves_per_cu > 0 ? c->tun.tail_waves_per_cu : (six ? 24 : 16);
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)limit + 63) / 64, (uint64_t)c->num_cus * (uint64_t)waves_per_cu));
-  HIP_TRY(c, c->d_spill.ensure(std::max<size_t>(16, (size_t)c->num_cus * 32 * (size_t)se * 64 * sizeof(int2))));  // (k_bvh's grids are no larger: one size for both)
-  unsigned long long* tot = c->d_totals.as<unsigned long long>();
+  HIP_TRY(c, c->d_spill.ensure(std::max<size_t>(16, (size_t)c->num_cus * 32 * (size_t)st.spill_entries * 64 * sizeof(int2))));  // (k_bvh's grids are no larger: one size for both)
   ScopedSpan sp(c, T_TAIL);
-#define PTMI_LAUNCH_TAIL(IS, CN, MU, NA) \
-  hipLaunchKernelGGL((k_tail<IS, CN, MU, NA>), dim3(grid), dim3(64), lds, c->stream, c->S, rc, P, ctl, tot, first, limit, c->prm.stack_size, le, se, c->d_spill.as<int2>(), cy)
-#define PTMI_LAUNCH_TAIL3(IS, CN, MU)          \
-  do {                                         \
-    if (noabort) PTMI_LAUNCH_TAIL(IS, CN, MU, true); \
-    else PTMI_LAUNCH_TAIL(IS, CN, MU, false);  \
-  } while (0)
-#define PTMI_LAUNCH_TAIL2(IS, CN)                             \
-  do {                                                        \
-    if (rc.num_samples > 1) PTMI_LAUNCH_TAIL3(IS, CN, true);  \
-    else PTMI_LAUNCH_TAIL3(IS, CN, false);                    \
-  } while (0)
-  if (six) {
-#define PTMI_LAUNCH_TAIL6(CN, NA) \
-  hipLaunchKernelGGL((k_tail6<CN, NA>), dim3(grid), dim3(64), lds, c->stream, c->S, rc, P, ctl, tot, first, limit, c->prm.stack_size, le, se, c->d_spill.as<int2>(), cy)
-    if (c->counters) {
-      if (noabort) PTMI_LAUNCH_TAIL6(true, true);
-      else PTMI_LAUNCH_TAIL6(true, false);
-    } else {
-      if (noabort) PTMI_LAUNCH_TAIL6(false, true);
-      else PTMI_LAUNCH_TAIL6(false, false);
-    }
-#undef PTMI_LAUNCH_TAIL6
-  } else if (c->prm.importance_sampling) {
-    if (c->counters) PTMI_LAUNCH_TAIL2(true, true);
-    else PTMI_LAUNCH_TAIL2(true, false);
-  } else {
-    if (c->counters) PTMI_LAUNCH_TAIL2(false, true);
-    else PTMI_LAUNCH_TAIL2(false, false);
-  }
-#undef PTMI_LAUNCH_TAIL2
-#undef PTMI_LAUNCH_TAIL3
-#undef PTMI_LAUNCH_TAIL
+  const auto tail = with_flags([](auto s6, auto is, auto cn, auto mu, auto na) { return tail_kernel<s6, is, cn, mu, na>(); }, six, c->prm.importance_sampling != 0,
+                               c->counters, rc.num_samples > 1, st.noabort);
+  hipLaunchKernelGGL(tail, dim3(grid), dim3(64), st.lds_bytes, c->stream, c->S, rc, P, ctl, c->d_totals.as<unsigned long long>(), first, limit, c->prm.stack_size,
+                     st.lds_entries, st.spill_entries, c->d_spill.as<int2>(), cy);
   HIP_TRY(c, hipGetLastError());
   c->stats.tail_launches++;
   return PTMI_OK;
-}
-
-// progressive mode without importance sampling is k_shade6 (80 VGPRs); the k_shade instances for it are never made
-template <bool IS, bool SO, bool CN, bool MU>
-void launch_shade(ptmi_ctx* c, uint32_t sgrid, const RenderConst& rc, const Paths& P, StepCtl* ctl, unsigned long long* tot, int first, uint32_t resv) {
-  if constexpr (!IS && !MU) hipLaunchKernelGGL((k_shade6<SO, CN>), dim3(sgrid), dim3(kBlock), 0, c->stream, c->S, rc, P, ctl, c->d_heads.as<uint32_t>(), tot, first, resv);
-  else hipLaunchKernelGGL((k_shade<IS, SO, CN, MU>), dim3(sgrid), dim3(kBlock), 0, c->stream, c->S, rc, P, ctl, c->d_heads.as<uint32_t>(), tot, first, resv);
 }
 
 // Placement search (DESIGN.md §3 "placement"): where the driver puts the queue arrays decides how often their streams meet in the same HBM channels — k_shade runs up to 12 %
@@ -915,10 +903,9 @@ int placement_search(ptmi_ctx* c, const std::function<int()>& dry) {
   return rc_out;
 }
 
-// `fold` = how many of the batch's leading frames are added to the framebuffer now (-1 = all of them); dry_steps > 0: placement_search's timing run
-int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames, int reset_first, int fold = -1, int dry_steps = 0) {
+// The batch's constants: camera, sampling, the shard's pixels (reads the context, changes nothing)
+RenderConst make_render_const(const ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames, int reset_first) {
   const ptmi_params& p = c->prm;
-  c->ahead.valid = false;  // the path buffers are about to be overwritten
   RenderConst rc{};
   rc.W = (float)c->W;
   rc.H = (float)c->H;
@@ -955,6 +942,14 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   rc.rank = c->rank, rc.world = c->world, rc.tile = c->tile;
   rc.n_local = count_local(rc.npix, c->rank, c->world, c->tile);
   rc.shade_cont = (uint32_t)c->tun.shade_cont;
+  return rc;
+}
+
+// `fold` = how many of the batch's leading frames are added to the framebuffer now (-1 = all of them); dry_steps > 0: placement_search's timing run
+int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames, int reset_first, int fold = -1, int dry_steps = 0) {
+  const ptmi_params& p = c->prm;
+  c->ahead.valid = false;  // the path buffers are about to be overwritten
+  const RenderConst rc = make_render_const(c, view16, frame0, n_frames, reset_first);
   if (rc.n_local == 0) return PTMI_OK;
 
   const int n_steps = rc.num_samples * p.max_bounces;
@@ -988,38 +983,27 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   const int sort_env = c->tun.sort;
   const bool sort = sort_env >= 0 ? sort_env != 0 : c->material_classes > 1;
 
-  // k_shade's grid: as many blocks per CU as the variant's registers and LDS admit (the progressive-mode variants need 79 VGPRs since
-  // the build dropped the SLP vectoriser: 6 blocks = 6 waves per SIMD; the importance-sampling ones 93: 5) — asked of the runtime once per variant
-  const bool shade_multi = rc.num_samples > 1;
+  const auto shade = with_flags([](auto is, auto so, auto cn, auto mu) { return shade_kernel<is, so, cn, mu>(); }, p.importance_sampling != 0, sort, c->counters,
+                                rc.num_samples > 1);
+  // k_shade's grid: as many blocks per CU as the instance's registers and LDS admit (the progressive-mode ones need 79 VGPRs since
+  // the build dropped the SLP vectoriser: 6 blocks = 6 waves per SIMD; the importance-sampling ones 93: 5) — asked of the runtime once per instance
   int shade_bpc = c->tun.shade_blocks_per_cu;
   if (shade_bpc <= 0) {
-    int& cached = c->shade_blocks_per_cu[(p.importance_sampling ? 8 : 0) | (sort ? 4 : 0) | (c->counters ? 2 : 0) | (shade_multi ? 1 : 0)];
+    int& cached = c->shade_blocks_per_cu[reinterpret_cast<const void*>(shade)];
     if (cached == 0) {
       int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, shade_kernel(p.importance_sampling != 0, sort, c->counters, shade_multi), kBlock, 0) != hipSuccess || nb < 1) nb = 5;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, shade, kBlock, 0) != hipSuccess || nb < 1) nb = 5;
       cached = nb;
     }
     shade_bpc = cached;
   }
   const uint32_t sgrid = std::max<uint32_t>(1, std::min<uint32_t>((bound + kSChunk - 1) / kSChunk, (uint32_t)c->num_cus * (uint32_t)std::min(8, std::max(1, shade_bpc))));  // <= 8: the queue buffers' slack is sized for that (ensure_paths)
   unsigned long long* tot = c->d_totals.as<unsigned long long>();
-  // queues of at most this many slots are traced to the end by one k_tail launch instead of a k_bvh + k_shade pair per bounce
-  // (a whole small batch — a lone 1080p frame — at step 0; later steps hand over only their thin ends: on deep trees a lane-per-path
-  // wave waits for its longest traversal, and the wavefront kernels with their lane refill stay ahead down to ~0.5 Mi slots)
-  const int tail_env = c->tun.tail_limit;
-  // Where k_tail's weak spot — the tree walk, as long as the wave's longest ray — is short, it stays ahead of the per-bounce kernels far longer (round 5,
-  // profiles/r05_tail_first_sweep*.txt): on configs[1]'s 11-level tree it wins up to ~24 Mi paths per batch (4 Mi paths: 0.94 ms against 1.54; 16.6 Mi — one rank of eight at
-  // fixed total spp, or an 8-frame render-ahead batch — 2.87 against 3.26).  On deep trees, since its walks park their stragglers (launch_tail), up to ~16 Mi paths on the
-  // 871 k-triangle scene (4 Mi: 3.5 ms against 6.5; 8 Mi: 4.9 against 6.4) but only ~4 Mi inside the 262 k-triangle room (8 Mi: 22.1 against 20.8): 6 Mi.  The builds with
-  // importance sampling, several samples or spheres (100-130 VGPRs, 4 waves per SIMD) keep 2 Mi.  Later steps' queues: from 2 Mi down on shallow trees, 1 Mi otherwise.
-  const bool six = !p.importance_sampling && rc.num_samples == 1 && c->S.n_spheres == 0 && c->tun.tail6;
-  const bool shallow = six && c->S.n_nodes > 0 && c->bvh_depth < 12, deep = six && c->S.n_nodes > 0 && c->bvh_depth >= 12 && c->tun.tail_park > 0;
-  const uint32_t tail_limit_first = (uint32_t)(tail_env >= 0 ? tail_env : shallow ? kTailLimitFirstShallow : deep ? kTailLimitFirstDeep : kTailLimitFirst),
-                 tail_limit_later = (uint32_t)(tail_env >= 0 ? tail_env : shallow ? kTailLimitLaterShallow : kTailLimitLater);
+  const TailPlan tail = tail_plan(c, rc);
 
   if (dry_steps == 0 && c->placement_pending) {
     c->placement_pending = false;
-    if (total > tail_limit_first) {  // (a batch that k_tail takes whole reads its queue once: nothing to search for)
+    if (total > tail.limit_first) {  // (a batch that k_tail takes whole reads its queue once: nothing to search for)
       // (two steps: the whole batch as the probe — eight steps — chose no better: profiles/r05_placement_dry_run.txt)
       int r = placement_search(c, [&]() { return render_batch(c, view16, frame0, n_frames, reset_first, fold, 2); });
       if (r) return r;
@@ -1032,8 +1016,8 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   {
     ScopedSpan s(c, T_GENERATE);
     if (rc.num_samples == 1) HIP_TRY(c, hipMemsetAsync(c->d_touched.p, 0, npaths, c->stream));
-    if (c->counters) hipLaunchKernelGGL(k_generate<true>, dim3(ew_grid), dim3(kBlock), 0, c->stream, c->S, rc, paths_of(c, 0, rc.num_samples > 1), ctl, c->d_heads.as<uint32_t>(), tot);
-    else hipLaunchKernelGGL(k_generate<false>, dim3(ew_grid), dim3(kBlock), 0, c->stream, c->S, rc, paths_of(c, 0, rc.num_samples > 1), ctl, c->d_heads.as<uint32_t>(), tot);
+    const auto generate = with_flags([](auto cn) { return &k_generate<cn>; }, c->counters);
+    hipLaunchKernelGGL(generate, dim3(ew_grid), dim3(kBlock), 0, c->stream, c->S, rc, paths_of(c, 0, rc.num_samples > 1), ctl, c->d_heads.as<uint32_t>(), tot);
     HIP_TRY(c, hipGetLastError());
     c->stats.generate_launches++;
   }
@@ -1056,8 +1040,8 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     Paths P = paths_of(c, s, rc.num_samples > 1);
     // (dry runs: k_generate and k_shade only — the kernels whose time depends on where the queue arrays lie; k_bvh reads them sparsely, and on a deep tree it would
     // be nine tenths of the search's time.  Rays that entered the root box are then shaded with what part 1 of hitScene found: other paths, the same access pattern.)
-    if (const uint32_t tail_limit = dry_steps > 0 ? 0u : (s == 0 ? tail_limit_first : tail_limit_later)) {
-      int lr = launch_tail(c, rc, P, ctl + s, s == 0 ? 1 : 0, tail_limit, carry_of(s));
+    if (const uint32_t tail_limit = dry_steps > 0 ? 0u : (s == 0 ? tail.limit_first : tail.limit_later)) {
+      int lr = launch_tail(c, rc, P, ctl + s, s == 0 ? 1 : 0, tail_limit, tail.six, carry_of(s));
       if (lr) return lr;
       // step 0's queue is the whole batch (k_generate fills one slot per path): if that fits the limit k_tail has just been handed all of it —
       // nothing is left for the per-bounce kernels, and a lone frame is three launches instead of 3 x MAX_BOUNCES + 2
@@ -1074,26 +1058,7 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     }
     {
       ScopedSpan sp(c, T_SHADE);
-#define PTMI_LAUNCH_SHADE(IS, SO, CN, MU) launch_shade<IS, SO, CN, MU>(c, sgrid, rc, P, ctl + s, tot, s == 0 ? 1 : 0, s == 0 ? 0u : resv)
-#define PTMI_LAUNCH_SHADE2(IS, SO)                          \
-  do {                                                      \
-    if (rc.num_samples > 1) {                               \
-      if (c->counters) PTMI_LAUNCH_SHADE(IS, SO, true, true); \
-      else PTMI_LAUNCH_SHADE(IS, SO, false, true);          \
-    } else {                                                \
-      if (c->counters) PTMI_LAUNCH_SHADE(IS, SO, true, false); \
-      else PTMI_LAUNCH_SHADE(IS, SO, false, false);         \
-    }                                                       \
-  } while (0)
-      if (p.importance_sampling) {
-        if (sort) PTMI_LAUNCH_SHADE2(true, true);
-        else PTMI_LAUNCH_SHADE2(true, false);
-      } else {
-        if (sort) PTMI_LAUNCH_SHADE2(false, true);
-        else PTMI_LAUNCH_SHADE2(false, false);
-      }
-#undef PTMI_LAUNCH_SHADE2
-#undef PTMI_LAUNCH_SHADE
+      hipLaunchKernelGGL(shade, dim3(sgrid), dim3(kBlock), 0, c->stream, c->S, rc, P, ctl + s, c->d_heads.as<uint32_t>(), tot, s == 0 ? 1 : 0, s == 0 ? 0u : resv);
       HIP_TRY(c, hipGetLastError());  // launch errors surface per step, before k_accumulate touches the framebuffer
     }
     c->stats.intersect_launches++;
@@ -1103,7 +1068,7 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   if (carry && !drained && n_steps > 0) {
     // paths that were carried over lag behind the step count: whatever the last k_shade left in the queue (and what the last k_bvh carried) is
     // traced to its end by one k_tail launch — a few thousand paths at most
-    int lr = launch_tail(c, rc, paths_of(c, n_steps, rc.num_samples > 1), ctl + n_steps, 0, 0xffffffffu, carry_of(n_steps));
+    int lr = launch_tail(c, rc, paths_of(c, n_steps, rc.num_samples > 1), ctl + n_steps, 0, 0xffffffffu, tail.six, carry_of(n_steps));
     if (lr) return lr;
   }
   {
