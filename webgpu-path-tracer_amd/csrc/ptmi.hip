@@ -13,6 +13,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "../../include/ptmi.h"
+#include "ptmi_dbuf.h"
 #include "ptmi_kernels.h"
 
 using namespace ptmi;
@@ -32,39 +34,6 @@ int ptmi_bvhdev_make_pairs(void* stream, const float* d_rows, uint32_t nn, float
 namespace {
 
 thread_local std::string g_create_error;
-
-struct DBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (bytes == 0) return hipSuccess;
-    size_t ask = bytes;
-#ifdef PTMI_TEST_HOOKS  // the tests' own build of the library (_build.build_testhooks): pretend the board is smaller — through a hipMalloc that really fails
-    if (const char* lim = getenv("PTMI_TEST_ALLOC_LIMIT"))
-      if (bytes > strtoull(lim, nullptr, 10)) ask = (size_t)1 << 60;
-#endif
-    hipError_t e = hipMalloc(&p, ask);
-    if (e == hipSuccess) cap = bytes;
-    else {
-      p = nullptr;
-      (void)hipGetLastError();  // the failure is reported through the return value; do not leave it behind as the runtime's "last error"
-    }
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const {
-    return reinterpret_cast<T*>(p);
-  }
-};
 
 enum TimerTag { T_PRIMS = 0, T_SHADE = 1, T_GENERATE = 2, T_RENDER = 3, T_BVH = 4, T_ACCUM = 5, T_TAIL = 6 };
 
@@ -210,7 +179,7 @@ struct ptmi_ctx {
   bool multi = false;
   bool shares_device = false;  // another shard of the same multi-device context lives on this GPU
   std::vector<ptmi_ctx*> peers;
-  PeerWorker* worker = nullptr;  // a peer's host thread (created on first use)
+  std::unique_ptr<PeerWorker> worker;  // a peer's host thread (created on first use)
   int proc_rank = 0, proc_world = 1, proc_tile = 4032;  // (63 waves of pixels; not 4096: see dist.py — a rank's pixel count must not be a large power of two)
   bool use_rccl = false;
   bool use_gather = false;        // the default collective of a multi-device context: every device's OWN tiles are copied into place on the root (1/N of the bytes, no arithmetic)
@@ -243,6 +212,14 @@ int fail(ptmi_ctx* c, int code, const std::string& msg) {
   else g_create_error = msg;
   return code;
 }
+
+// The local devices of a context, root first: local device #i is element i (a single-device context is just itself)
+std::vector<ptmi_ctx*> local_devices(ptmi_ctx* c) {
+  std::vector<ptmi_ctx*> v{c};
+  v.insert(v.end(), c->peers.begin(), c->peers.end());
+  return v;
+}
+
 #define HIP_TRY(c, expr)                                                                              \
   do {                                                                                                \
     hipError_t _e = (expr);                                                                           \
@@ -854,22 +831,15 @@ int placement_search(ptmi_ctx* c, const std::function<int()>& dry) {
   int rc_out = PTMI_OK;
   // The sets that lost stay allocated until the search is over (while the board has room for them): a set that is freed at once hands its pages to the next
   // candidate, which then scores the same to the microsecond.
-  struct Losers {
-    std::vector<DBuf> bufs;
-    void drop() {
-      for (DBuf& b : bufs) b.release();
-      bufs.clear();
-    }
-    ~Losers() { drop(); }
-  } losers;
+  std::vector<DBuf> losers;
   size_t set_bytes = 0;
   for (int k = 0; k < 10; k++) set_bytes += slots * width[k];
   for (int t = 1; t < c->tun.placement_tries; t++) {
     size_t mem_free = 0, mem_total = 0;
     if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) mem_free = 0, (void)hipGetLastError();
     if (mem_free < set_bytes + ((size_t)8 << 30)) {
-      if (losers.bufs.empty()) break;
-      losers.drop();
+      if (losers.empty()) break;
+      losers.clear();
     }
     DBuf cand[10];
     bool ok = true;
@@ -887,16 +857,12 @@ int placement_search(ptmi_ctx* c, const std::function<int()>& dry) {
         best = ms;
       }
     }
-    if (!ok) (void)hipStreamSynchronize(c->stream);  // nothing may still run on a set that is about to go
-    for (int k = 0; k < 10; k++) {
-      if (ok && cand[k].p) {
-        losers.bufs.emplace_back();
-        std::swap(losers.bufs.back(), cand[k]);
-      } else {
-        cand[k].release();
-      }
+    if (!ok) {
+      (void)hipStreamSynchronize(c->stream);  // nothing may still run on a set that is about to go (cand's, as the loop ends)
+      break;
     }
-    if (!ok) break;
+    for (DBuf& b : cand)
+      if (b.p) losers.push_back(std::move(b));
   }
   restore.stats.placement_sets = sets;
   restore.stats.placement_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_search).count();
@@ -1171,24 +1137,22 @@ bool rccl_loaded() {
 // (allocation, the occasional queue-length readback of a long render) do not serialise the GPUs.
 template <class F>
 int on_all_devices(ptmi_ctx* c, F fn, bool parallel = false) {
-  const size_t n = c->peers.size();
-  if (n == 0) return fn(c);
-  std::vector<int> rcs(n + 1, PTMI_OK);
+  const std::vector<ptmi_ctx*> devs = local_devices(c);
+  std::vector<int> rcs(devs.size(), PTMI_OK);
   if (parallel) {
-    for (size_t i = 0; i < n; i++) {
-      ptmi_ctx* q = c->peers[i];
-      if (!q->worker) q->worker = new PeerWorker();
+    for (ptmi_ctx* q : c->peers) {
+      if (!q->worker) q->worker = std::make_unique<PeerWorker>();
       q->worker->post([&fn, q] { return fn(q); });
     }
     rcs[0] = fn(c);
-    for (size_t i = 0; i < n; i++) rcs[i + 1] = c->peers[i]->worker->wait();
+    for (size_t i = 1; i < devs.size(); i++) rcs[i] = devs[i]->worker->wait();
   } else {
-    rcs[0] = fn(c);
-    for (size_t i = 0; i < n && !rcs[i]; i++) rcs[i + 1] = fn(c->peers[i]);  // stop at the first device that fails
+    for (size_t i = 0; i < devs.size(); i++)
+      if ((rcs[i] = fn(devs[i]))) break;  // stop at the first device that fails
   }
-  for (size_t i = 1; i <= n; i++)
+  for (size_t i = 1; i < devs.size(); i++)
     if (rcs[i] && !rcs[0]) {
-      c->err = "local device #" + std::to_string(i) + " (GPU " + std::to_string(c->peers[i - 1]->device) + "): " + c->peers[i - 1]->err;
+      c->err = "local device #" + std::to_string(i) + " (GPU " + std::to_string(devs[i]->device) + "): " + devs[i]->err;
       return rcs[i];
     }
   return rcs[0];
@@ -1220,6 +1184,7 @@ int gather_framebuffer(ptmi_ctx* c, float4** out) {
     return PTMI_OK;
   }
   const size_t bytes = c->fb_bytes, n4 = bytes / 16;
+  const std::vector<ptmi_ctx*> devs = local_devices(c);
   int r = on_all_devices(c, [](ptmi_ctx* q) -> int {
     HIP_TRY(q, hipSetDevice(q->device));
     HIP_TRY(q, hipStreamSynchronize(q->stream));
@@ -1239,8 +1204,8 @@ int gather_framebuffer(ptmi_ctx* c, float4** out) {
     if (gs != ncclSuccess) {
       first_error = std::string("ncclGroupStart: ") + (rccl_fail_hook(c) == 2 ? "simulated failure (PTMI_TEST_RCCL_FAIL=reduce)" : g_rccl.GetErrorString(gs));
     } else {
-      for (size_t i = 0; i <= c->peers.size() && first_error.empty(); i++) {
-        ptmi_ctx* q = i ? c->peers[i - 1] : c;
+      for (size_t i = 0; i < devs.size() && first_error.empty(); i++) {
+        ptmi_ctx* q = devs[i];
         const hipError_t he = hipSetDevice(q->device);
         if (he != hipSuccess) {
           first_error = std::string("hipSetDevice: ") + hipGetErrorString(he);
@@ -1262,10 +1227,10 @@ int gather_framebuffer(ptmi_ctx* c, float4** out) {
       c->comms.clear();
     }
     hipError_t se = hipSuccess;
-    for (size_t i = 0; i <= c->peers.size() && se == hipSuccess; i++) {  // whatever was enqueued has to drain before anybody reads or re-sums the buffers
-      ptmi_ctx* q = i ? c->peers[i - 1] : c;
+    for (ptmi_ctx* q : devs) {  // whatever was enqueued has to drain before anybody reads or re-sums the buffers
       se = hipSetDevice(q->device);
       if (se == hipSuccess) se = hipStreamSynchronize(q->stream);
+      if (se != hipSuccess) break;
     }
     (void)hipSetDevice(c->device);
     if (first_error.empty() && se != hipSuccess) {
@@ -1288,8 +1253,7 @@ int gather_framebuffer(ptmi_ctx* c, float4** out) {
     HIP_TRY(c, hipMemsetAsync(g, 0, bytes, c->stream));
     const uint32_t npix = (uint32_t)c->W * (uint32_t)c->H;
     c->gather_bytes = 0;
-    for (size_t i = 0; i <= c->peers.size(); i++) {
-      ptmi_ctx* q = i ? c->peers[i - 1] : c;
+    for (ptmi_ctx* q : devs) {
       const uint32_t n_local = count_local(npix, q->rank, q->world, q->tile);
       if (n_local == 0) continue;
       const float4* src = q->fb;
@@ -1331,9 +1295,10 @@ int gather_framebuffer(ptmi_ctx* c, float4** out) {
 }
 
 int apply_shard(ptmi_ctx* c) {  // deal the caller's shard to the local devices
-  const int n = (int)c->peers.size() + 1;
+  const std::vector<ptmi_ctx*> devs = local_devices(c);
+  const int n = (int)devs.size();
   for (int i = 0; i < n; i++) {
-    ptmi_ctx* q = i ? c->peers[i - 1] : c;
+    ptmi_ctx* q = devs[i];
     q->rank = c->proc_rank * n + i;
     q->world = c->proc_world * n;
     q->tile = c->proc_tile;
@@ -1449,10 +1414,8 @@ int ptmi_create_multi(ptmi_ctx** out, const int* device_ids, int n_devices) {
     c->peers.push_back(q);
     for (int j = 0; j < i; j++) distinct = distinct && device_ids[j] != device_ids[i];
   }
-  if (!distinct) {
-    c->shares_device = true;
-    for (ptmi_ctx* q : c->peers) q->shares_device = true;
-  }
+  if (!distinct)
+    for (ptmi_ctx* q : local_devices(c)) q->shares_device = true;
   // The reduce: RCCL whenever every shard has a GPU of its own (a communicator cannot hold one GPU twice); shards that
   // share a GPU are summed by a kernel.  PTMI_MULTI_REDUCE=copy forces the peer-copy path, =rccl forces RCCL even for a
   // single device (a one-rank communicator: exercises the library on a one-GPU box).
@@ -1541,14 +1504,8 @@ void ptmi_destroy(ptmi_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   drain_spans(c);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-  for (DBuf* b : {&c->d_quad_unit_n, &c->d_spheres, &c->d_sphere_info, &c->d_quads, &c->d_quad_mat, &c->d_tris, &c->d_pretri, &c->d_trinorm, &c->d_meshes, &c->d_xforms,
-                  &c->d_mats, &c->d_pairs, &c->d_leaf_table, &c->d_fb_own, &c->d_q0[0], &c->d_q0[1], &c->d_q1[0], &c->d_q1[1], &c->d_q2[0],
-                  &c->d_q2[1], &c->d_tp[0], &c->d_tp[1], &c->d_hm[0], &c->d_hm[1], &c->d_uv, &c->d_acc, &c->d_pixsum, &c->d_touched, &c->d_ctl, &c->d_totals,
-                  &c->d_scratch, &c->d_spill, &c->d_heads, &c->d_fb_gather, &c->d_fb_stage, &c->d_bvh_rows, &c->d_carry[0], &c->d_carry[1]})
-    b->release();
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c->worker;
-  delete c;
+  delete c;  // its device buffers (DBuf) are freed here, with its device current and its stream drained
 }
 
 int ptmi_set_params(ptmi_ctx* c, const ptmi_params* p) {
@@ -1560,12 +1517,9 @@ int ptmi_set_params(ptmi_ctx* c, const ptmi_params* p) {
   if (!(p->fov_degrees > 0.0f && p->fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_set_params: fov_degrees must be in (0,180)");
   if (!(p->tmin >= 0.0f && p->tmin < 3.0e38f)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_set_params: tmin must be finite and >= 0 (the reference: 0.000001)");
   if (!(p->light_mix >= 0.0f && p->light_mix <= 1.0f)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_set_params: light_mix must be in [0,1] (the reference: 0.2)");
-  c->prm = *p;
-  c->S.tmin = p->tmin;  // (the kernels take it with the scene; prepare_scene sets it too)
-  c->ahead.valid = false;
-  for (ptmi_ctx* q : c->peers) {
+  for (ptmi_ctx* q : local_devices(c)) {
     q->prm = *p;
-    q->S.tmin = p->tmin;
+    q->S.tmin = p->tmin;  // (the kernels take it with the scene; prepare_scene sets it too)
     q->ahead.valid = false;
   }
   return PTMI_OK;
@@ -1573,8 +1527,7 @@ int ptmi_set_params(ptmi_ctx* c, const ptmi_params* p) {
 
 int ptmi_reload_tuning(ptmi_ctx* c) {
   if (!c) return PTMI_ERR_INVALID_ARG;
-  for (size_t i = 0; i <= c->peers.size(); i++) {
-    ptmi_ctx* q = i ? c->peers[i - 1] : c;
+  for (ptmi_ctx* q : local_devices(c)) {
     const int slots_before = q->tun.bvh_carry_slots;
     load_tuning(q);
     q->ahead.valid = false;
@@ -1606,11 +1559,7 @@ static int upload_commit(ptmi_ctx* c, int which, const void* data, size_t bytes,
     case PTMI_BUF_TRIANGLES: {
       hipError_t e = hipSetDevice(c->device);
       if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // nothing in flight may still read the old triangles
-      if (e == hipSuccess && fresh->p) {
-        c->d_tris.release();
-        c->d_tris = *fresh;
-        *fresh = DBuf();
-      }
+      if (e == hipSuccess && fresh->p) c->d_tris = std::move(*fresh);
       if (e == hipSuccess && bytes) e = hipMemcpy(c->d_tris.p, data, bytes, hipMemcpyHostToDevice);
       if (e != hipSuccess) {
         // the device no longer holds a valid triangle array: make the context say so instead of tracing stale or freed memory
@@ -1652,27 +1601,24 @@ int ptmi_upload(ptmi_ctx* c, int which, const void* data, size_t bytes) {
   if (bytes && !data) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_upload: data is null");
   if (bytes / stride > 0x0fffffffull) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_upload: more than 2^28-1 elements");
   // the scene is replicated on every device of a multi-device context: stage everywhere first, commit only when every device can take it
-  const size_t n = c->peers.size() + 1;
-  std::vector<DBuf> fresh(n);
-  for (size_t i = 0; i < n; i++) {
-    ptmi_ctx* q = i ? c->peers[i - 1] : c;
-    const int r = upload_stage(q, which, bytes, &fresh[i]);
+  const std::vector<ptmi_ctx*> devs = local_devices(c);
+  std::vector<DBuf> fresh(devs.size());  // (still holding a buffer at the end only after a device error during the commit)
+  for (size_t i = 0; i < devs.size(); i++) {
+    const int r = upload_stage(devs[i], which, bytes, &fresh[i]);
     if (r) {
       for (size_t k = 0; k <= i; k++) {
-        (void)hipSetDevice((k ? c->peers[k - 1] : c)->device);
+        (void)hipSetDevice(devs[k]->device);
         fresh[k].release();
       }
       (void)hipSetDevice(c->device);
-      return i ? fail(c, r, "local device #" + std::to_string(i) + ": " + q->err + " (no device was changed)") : r;
+      return i ? fail(c, r, "local device #" + std::to_string(i) + ": " + devs[i]->err + " (no device was changed)") : r;
     }
   }
   int rc = PTMI_OK;
-  for (size_t i = 0; i < n; i++) {
-    ptmi_ctx* q = i ? c->peers[i - 1] : c;
-    const int r = upload_commit(q, which, data, bytes, &fresh[i]);
-    if (r && !rc) rc = i ? fail(c, r, "local device #" + std::to_string(i) + ": " + q->err) : r;
+  for (size_t i = 0; i < devs.size(); i++) {
+    const int r = upload_commit(devs[i], which, data, bytes, &fresh[i]);
+    if (r && !rc) rc = i ? fail(c, r, "local device #" + std::to_string(i) + ": " + devs[i]->err) : r;
   }
-  for (size_t k = 0; k < n; k++) fresh[k].release();  // (only after a device error during the commit)
   (void)hipSetDevice(c->device);
   return rc;
 }
@@ -1695,28 +1641,20 @@ static int build_scene_bvh_one(ptmi_ctx* c, bool sah) {
   DBuf rows, tris2;
   hipError_t e = rows.ensure((2 * n - 1) * 48);
   if (e == hipSuccess) e = tris2.ensure(n * 96);
-  if (e != hipSuccess) {
-    rows.release();
-    tris2.release();
-    return fail(c, PTMI_ERR_NO_MEMORY, std::string("ptmi_build_scene_bvh: ") + hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(c, PTMI_ERR_NO_MEMORY, std::string("ptmi_build_scene_bvh: ") + hipGetErrorString(e));
   int depth = 0;
   uint32_t bad = 0xffffffffu, n_nodes = 0;
   const int r = ptmi_bvhdev_build_scene((void*)c->stream, c->d_tris.as<float>(), (uint32_t)n, c->h_meshes.data(), n_mesh, c->h_xforms.data(), n_xf, rows.as<float>(), tris2.as<float>(),
                                          &depth, &bad, sah ? 1 : 0, &n_nodes);
   if (r || bad != 0xffffffffu) {
-    rows.release();
-    tris2.release();
     if (r == (int)hipErrorNotSupported) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_build_scene_bvh_sah: the SAH tree of these triangles is deeper than 4096 levels (no STACK_SIZE <= 64 can traverse it)");
     if (r) return fail(c, r == (int)hipErrorOutOfMemory ? PTMI_ERR_NO_MEMORY : PTMI_ERR_DEVICE, std::string("ptmi_build_scene_bvh: ") + hipGetErrorString((hipError_t)r));
     char msg[160];
     snprintf(msg, sizeof msg, "ptmi_build_scene_bvh: triangle %u: mesh_id / the mesh's global_id out of range (meshes %d, transforms %d)", bad, n_mesh, n_xf);
     return fail(c, PTMI_ERR_BAD_SCENE, msg);
   }
-  c->d_tris.release();  // the triangles now sit in leaf order (the reference reorders them on the host, lib/scene.js:257)
-  c->d_tris = tris2;
-  c->d_bvh_rows.release();
-  c->d_bvh_rows = rows;
+  c->d_tris = std::move(tris2);  // the triangles now sit in leaf order (the reference reorders them on the host, lib/scene.js:257)
+  c->d_bvh_rows = std::move(rows);
   c->bvh_on_device = true;
   c->bvh_dev_stale = false;
   c->bvh_dev_prims = n;
@@ -1965,8 +1903,7 @@ int ptmi_write_framebuffer(ptmi_ctx* c, const float* src, size_t bytes) {
     // every device gets its own tiles of the image and zeros elsewhere, as if it had rendered them itself
     const size_t npix = (size_t)c->W * c->H;
     std::vector<float> part(npix * 4);
-    for (size_t i = 0; i <= c->peers.size(); i++) {
-      ptmi_ctx* q = i ? c->peers[i - 1] : c;
+    for (ptmi_ctx* q : local_devices(c)) {
       for (size_t px = 0; px < npix; px++) {
         const bool mine = (px / (size_t)q->tile) % (size_t)q->world == (size_t)q->rank;
         for (int k = 0; k < 4; k++) part[4 * px + k] = mine ? src[4 * px + k] : 0.0f;
@@ -2034,14 +1971,12 @@ int ptmi_resolve_rgba8(ptmi_ctx* c, float frame_num, uint8_t* dst, size_t bytes)
 
 int ptmi_set_counters(ptmi_ctx* c, int on) {
   if (!c) return PTMI_ERR_INVALID_ARG;
-  c->counters = on != 0;
-  for (ptmi_ctx* q : c->peers) q->counters = c->counters;
+  for (ptmi_ctx* q : local_devices(c)) q->counters = on != 0;
   return PTMI_OK;
 }
 int ptmi_set_timing(ptmi_ctx* c, int on) {
   if (!c) return PTMI_ERR_INVALID_ARG;
-  c->timing = (on < 0 || on > 6) ? 0 : on;
-  for (ptmi_ctx* q : c->peers) q->timing = c->timing;
+  for (ptmi_ctx* q : local_devices(c)) q->timing = (on < 0 || on > 6) ? 0 : on;
   return PTMI_OK;
 }
 
@@ -2192,22 +2127,18 @@ int ptmi_selftest(ptmi_ctx* c, int which, uint64_t* mismatches, uint32_t* first_
   HIP_TRY(c, hipSetDevice(c->device));
   DBuf d;
   HIP_TRY(c, d.ensure(16));
-  int rc = PTMI_OK;
-  do {
-    unsigned long long init[2] = {0ull, 0xffffffffull};
-    hipError_t e = hipMemcpyAsync(d.p, init, 16, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_selftest, dim3((unsigned)c->num_cus * 16), dim3(256), 0, c->stream, which, d.as<unsigned long long>(), reinterpret_cast<uint32_t*>(d.as<unsigned long long>() + 1));
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(init, d.p, 16, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) rc = fail(c, PTMI_ERR_DEVICE, std::string("ptmi_selftest: ") + hipGetErrorString(e));
-    *mismatches = init[0];
-    if (first_bad_bits) *first_bad_bits = (uint32_t)init[1];
-  } while (0);
-  d.release();
-  return rc;
+  unsigned long long init[2] = {0ull, 0xffffffffull};
+  hipError_t e = hipMemcpyAsync(d.p, init, 16, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_selftest, dim3((unsigned)c->num_cus * 16), dim3(256), 0, c->stream, which, d.as<unsigned long long>(), reinterpret_cast<uint32_t*>(d.as<unsigned long long>() + 1));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(init, d.p, 16, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  *mismatches = init[0];
+  if (first_bad_bits) *first_bad_bits = (uint32_t)init[1];
+  if (e != hipSuccess) return fail(c, PTMI_ERR_DEVICE, std::string("ptmi_selftest: ") + hipGetErrorString(e));
+  return PTMI_OK;
 }
 
 int ptmi_math_eval(ptmi_ctx* c, int fn, size_t n, const float* x, const float* y, float* out) {
@@ -2219,23 +2150,17 @@ int ptmi_math_eval(ptmi_ctx* c, int fn, size_t n, const float* x, const float* y
   HIP_TRY(c, dx.ensure(n * 4));
   HIP_TRY(c, dout.ensure(n * 4));
   if (y) HIP_TRY(c, dy.ensure(n * 4));
-  int rc = PTMI_OK;
-  do {
-    hipError_t e = hipMemcpyAsync(dx.p, x, n * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && y) e = hipMemcpyAsync(dy.p, y, n * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_math_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, fn, n, dx.as<float>(), y ? dy.as<float>() : nullptr,
-                         dout.as<float>());
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, n * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) rc = fail(c, PTMI_ERR_DEVICE, std::string("ptmi_math_eval: ") + hipGetErrorString(e));
-  } while (0);
-  dx.release();
-  dy.release();
-  dout.release();
-  return rc;
+  hipError_t e = hipMemcpyAsync(dx.p, x, n * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && y) e = hipMemcpyAsync(dy.p, y, n * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_math_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, fn, n, dx.as<float>(), y ? dy.as<float>() : nullptr,
+                       dout.as<float>());
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, n * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(c, PTMI_ERR_DEVICE, std::string("ptmi_math_eval: ") + hipGetErrorString(e));
+  return PTMI_OK;
 }
 
 }  // extern "C"

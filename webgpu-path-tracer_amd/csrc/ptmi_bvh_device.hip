@@ -25,6 +25,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/ptmi.h"
+#include "ptmi_dbuf.h"
 
 namespace {
 
@@ -631,14 +632,7 @@ hipError_t build_levels_sah(hipStream_t stream, Dev& d, uint32_t n, const double
   const size_t t_bytes = std::max(std::max(t_reduce, t_scan), std::max(t_sort1, t_sort2));
   TRY(d.alloc(&temp, t_bytes));
   // the bins of the level's nodes: grown to the widest level seen (a level has at most n nodes, the widest one of a real mesh about n / 2)
-  SahBin* bins = nullptr;
-  size_t bins_cap = 0;
-  struct BinsGuard {
-    SahBin*& p;
-    ~BinsGuard() {
-      if (p) (void)hipFree(p);
-    }
-  } guard{bins};
+  ptmi::DBuf bins;
 
   const unsigned B = 256;
   hipLaunchKernelGGL(k_iota, dim3((n + B - 1) / B), dim3(B), 0, stream, order[0], seg_of, n);
@@ -662,18 +656,13 @@ hipError_t build_levels_sah(hipStream_t stream, Dev& d, uint32_t n, const double
     }
     hipLaunchKernelGGL(k_sah_scatter, dim3((n + B - 1) / B), dim3(B), 0, stream, run_key, run_val, n_runs, n, agg);
     const size_t need = (size_t)m * 3 * kSahBins;
-    if (need > bins_cap) {
-      TRY(hipStreamSynchronize(stream));
-      if (bins) (void)hipFree(bins);
-      bins = nullptr;
-      bins_cap = 0;
-      const size_t ask = std::max(need, std::min<size_t>((size_t)n * 3 * kSahBins, need * 2));
-      TRY(hipMalloc((void**)&bins, ask * sizeof(SahBin)));
-      bins_cap = ask;
+    if (need * sizeof(SahBin) > bins.cap) {
+      TRY(hipStreamSynchronize(stream));  // the previous level's kernels may still read the bins that ensure() frees
+      TRY(bins.ensure(std::max(need, std::min<size_t>((size_t)n * 3 * kSahBins, need * 2)) * sizeof(SahBin)));
     }
-    hipLaunchKernelGGL(k_sah_bins_init, dim3((unsigned)((need + B - 1) / B)), dim3(B), 0, stream, bins, (uint32_t)need);
-    hipLaunchKernelGGL(k_sah_bins, dim3((n + kSahChunk - 1) / kSahChunk), dim3(256), 0, stream, order[ocur], seg_of, agg, bmin, bmax, n, bins);
-    hipLaunchKernelGGL(k_sah_decide, dim3((m + B - 1) / B), dim3(B), 0, stream, level[cur], agg, bins, m, tree, axis, split_pos, inner, split_first);
+    hipLaunchKernelGGL(k_sah_bins_init, dim3((unsigned)((need + B - 1) / B)), dim3(B), 0, stream, bins.as<SahBin>(), (uint32_t)need);
+    hipLaunchKernelGGL(k_sah_bins, dim3((n + kSahChunk - 1) / kSahChunk), dim3(256), 0, stream, order[ocur], seg_of, agg, bmin, bmax, n, bins.as<SahBin>());
+    hipLaunchKernelGGL(k_sah_decide, dim3((m + B - 1) / B), dim3(B), 0, stream, level[cur], agg, bins.as<SahBin>(), m, tree, axis, split_pos, inner, split_first);
     {
       size_t tb = t_bytes;
       TRY(rocprim::exclusive_scan(temp, tb, inner, rank, 0u, m, rocprim::plus<uint32_t>(), stream));
@@ -713,7 +702,7 @@ hipError_t build_levels_sah(hipStream_t stream, Dev& d, uint32_t n, const double
   hipLaunchKernelGGL(k_sah_rows, dim3((total + B - 1) / B), dim3(B), 0, stream, tree, total, flat, next, prim_type, rows);
   TRY(hipGetLastError());
   TRY(hipMemcpyAsync(order_out, order[ocur], (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
-  TRY(hipStreamSynchronize(stream));  // (`zero` / `none` are stack variables; the bins die with the guard)
+  TRY(hipStreamSynchronize(stream));  // (`zero` / `none` are stack variables; the bins die with `bins`)
   *n_nodes_out = total;
   if (depth_out) *depth_out = (int)levels.size() - 1;  // inner nodes on the longest root-to-leaf path
   return hipSuccess;
