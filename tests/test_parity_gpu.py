@@ -488,7 +488,7 @@ def test_reference_default_max_bounces_100(ctx, pkg, oracle):
 def test_sah_bvh_bit_exact(ctx, pkg, oracle):
     """The opt-in SAH builder's trees (deeper, leaves of 1-2 triangles) through the same kernels: both the NOABORT path
     (stack 64 > depth) and the literal stack discipline with the Q7 abort live (stack 20), incl. stack entries beyond the
-    14 kept in LDS."""
+    10 kept in LDS by default (PTMI_LDS_STACK)."""
     b = pkg.scenes.c4_scene(40000).buffers(native=pkg.ptmi.NativeHost(), sah=True)
     nodes = b["bvh"].reshape(-1, 12)
     assert (nodes[nodes[:, 7] == 2][:, 9] > 1).any()  # multi-triangle leaves are present

@@ -23,6 +23,7 @@
 #include "../../include/ptmi.h"
 #include "ptmi_dbuf.h"
 #include "ptmi_kernels.h"
+#include "ptmi_tuning.h"
 
 using namespace ptmi;
 
@@ -86,31 +87,7 @@ struct PeerWorker {
   }
 };
 
-// Tuning knobs (PTMI_* environment variables): read ONCE, when the context is created (ptmi_reload_tuning reads them again — tests and A/B
-// scripts that change a variable under a live context call it); the render path itself never touches the environment.
-struct Tuning {
-  int lds_stack = 10;          // PTMI_LDS_STACK: traversal stack entries per lane kept in LDS (deeper ones: per-wave global spill area)
-  bool noabort = true;         // PTMI_NOABORT=0: keep the literal stack discipline even where Q7's abort cannot trigger
-  int waves_per_cu = 0;        // PTMI_WAVES_PER_CU: k_bvh's grid (0 = auto)
-  int bvh_teams = 16;          // PTMI_BVH_TEAMS: claim counters of k_bvh
-  int refill = kRefillThreshold, leaf_batch = kLeafBatch, bvh_range = (int)kBvhRange;  // PTMI_REFILL, PTMI_LEAF_BATCH, PTMI_BVH_RANGE
-  int tail_waves_per_cu = 0;   // PTMI_TAIL_WAVES_PER_CU (0 = 16, or 24 for the 6-wave build)
-  bool tail6 = true;           // PTMI_TAIL6=0: never the 80-VGPR build of k_tail
-  int tail_park = 16;          // PTMI_TAIL_PARK: k_tail's tree walk parks its last lanes once fewer than this many are left in it (trees of >= 12 levels only; 0 = never)
-  int bvh_carry = 32;          // PTMI_BVH_CARRY: iterations a k_bvh wave goes on after the queue is exhausted before it carries its unfinished rays into the next
-                               // step's queue (Carry, ptmi_device.h); 0 = never (every launch traces its longest ray to the end)
-  int bvh_carry_slots = 1 << 18;  // PTMI_BVH_CARRY_SLOTS: the queues' carry prefix
-  int bvh_carry_last = 0;      // PTMI_BVH_CARRY_LAST: the last this-many steps carry nothing over (measured: 0 is best — the drain launch costs 1.5-2.5 ms either way)
-  int bvh_carry_min_paths = 4 << 20, bvh_carry_min_depth = 12;  // PTMI_BVH_CARRY_MIN_PATHS / _MIN_DEPTH: batches and trees below these are traced without carrying (tests: 0)
-  int sort = -1;               // PTMI_SORT: k_shade sorts its chunks by material class (-1 = when the scene has more than one)
-  int shade_blocks_per_cu = 0; // PTMI_SHADE_BLOCKS_PER_CU (0 = from the variant's occupancy)
-  int shade_cont = 16;         // PTMI_SHADE_CONT: k_shade shades a flush pass's new rays that need no tree walk in the same launch when at least this many lanes have one (progressive mode, one material class; 0 = never)
-  int tail_limit = -1;         // PTMI_TAIL_LIMIT: k_tail takes queues of at most this many slots (-1 = kTailLimitFirst / kTailLimitLater, 0 = never)
-  bool render_ahead = true;    // PTMI_RENDER_AHEAD=0
-  int path_budget_log2 = 30;   // PTMI_PATH_BUDGET_LOG2: paths per wavefront pass with frames_in_flight = auto (round 5: 29 -> 30)
-  int placement_tries = 6;     // PTMI_PLACEMENT_TRIES (round 5: 4 -> 6 — the sets now differ, the losers staying allocated during the search: best of 8 ran 0.7 % ahead of best of 4)
-  bool debug_placement = false;
-};
+// (Tuning — the PTMI_* environment knobs, their domains and their parsing: ptmi_tuning.h)
 
 struct ptmi_ctx {
   int device = 0;
@@ -693,37 +670,7 @@ TailPlan tail_plan(const ptmi_ctx* c, const RenderConst& rc) {
                   (uint32_t)(env >= 0 ? env : shallow ? kTailLimitLaterShallow : kTailLimitLater)};
 }
 
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && *v) ? atoi(v) : dflt;
-}
-void load_tuning(ptmi_ctx* c) {
-  Tuning t;
-  t.lds_stack = std::max(1, env_int("PTMI_LDS_STACK", t.lds_stack));
-  t.noabort = env_int("PTMI_NOABORT", 1) != 0;
-  t.waves_per_cu = env_int("PTMI_WAVES_PER_CU", 0);
-  t.bvh_teams = (int)std::max<uint32_t>(1, std::min<uint32_t>(kMaxTeams, (uint32_t)env_int("PTMI_BVH_TEAMS", t.bvh_teams)));
-  t.refill = env_int("PTMI_REFILL", t.refill);
-  t.leaf_batch = env_int("PTMI_LEAF_BATCH", t.leaf_batch);
-  t.bvh_range = std::max(64, std::min(1 << 16, env_int("PTMI_BVH_RANGE", t.bvh_range))) & ~63;
-  t.tail_waves_per_cu = std::max(0, std::min(32, env_int("PTMI_TAIL_WAVES_PER_CU", t.tail_waves_per_cu)));
-  t.tail6 = env_int("PTMI_TAIL6", 1) != 0;
-  t.tail_park = std::max(0, std::min(63, env_int("PTMI_TAIL_PARK", t.tail_park)));
-  t.bvh_carry = std::max(0, env_int("PTMI_BVH_CARRY", t.bvh_carry));
-  t.bvh_carry_slots = std::max(64, std::min(1 << 22, env_int("PTMI_BVH_CARRY_SLOTS", t.bvh_carry_slots)));
-  t.bvh_carry_last = std::max(0, env_int("PTMI_BVH_CARRY_LAST", t.bvh_carry_last));
-  t.bvh_carry_min_paths = std::max(0, env_int("PTMI_BVH_CARRY_MIN_PATHS", t.bvh_carry_min_paths));
-  t.bvh_carry_min_depth = std::max(0, env_int("PTMI_BVH_CARRY_MIN_DEPTH", t.bvh_carry_min_depth));
-  t.sort = env_int("PTMI_SORT", -1);
-  t.shade_blocks_per_cu = env_int("PTMI_SHADE_BLOCKS_PER_CU", 0);
-  t.shade_cont = std::max(0, std::min(64, env_int("PTMI_SHADE_CONT", t.shade_cont)));
-  t.tail_limit = env_int("PTMI_TAIL_LIMIT", -1);
-  t.render_ahead = env_int("PTMI_RENDER_AHEAD", 1) != 0;
-  t.path_budget_log2 = std::max(16, std::min(31, env_int("PTMI_PATH_BUDGET_LOG2", t.path_budget_log2)));
-  t.placement_tries = env_int("PTMI_PLACEMENT_TRIES", t.placement_tries);
-  t.debug_placement = getenv("PTMI_DEBUG_PLACEMENT") != nullptr;
-  c->tun = t;
-}
+void load_tuning(ptmi_ctx* c) { c->tun = load_tuning_env(); }  // (every value inside its knob's domain: ptmi_tuning.h)
 
 // hitScene, part 2 for the step's queue (k_bvh).  Part 1 has already been run by whoever created the rays (k_generate,
 // k_shade); ptmi_trace's rays come from the host, so it asks for k_prims first.
@@ -749,7 +696,7 @@ int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_ite
   const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(want, (uint32_t)c->num_cus * (uint32_t)waves_per_cu));
   // Range claims go through 16 team counters (128 B apart) instead of one: a launch makes tens of thousands of claims and
   // same-address global atomics serialise at ~11 ns each (configs[1]: +2 %).
-  const uint32_t n_teams = (uint32_t)tun.bvh_teams;
+  const uint32_t n_teams = std::min<uint32_t>((uint32_t)tun.bvh_teams, grid);  // (a team without a wave would leave its ranges unclaimed: wave w is in team w % n_teams)
   // (the counters are zeroed by the kernel that filled this queue)
   HIP_TRY(c, c->d_spill.ensure(std::max<size_t>(16, (size_t)std::max<uint32_t>(grid, (uint32_t)c->num_cus * 32) * (size_t)st.spill_entries * 64 * sizeof(int2))));
   // step 0's queue does not store the rays' common origin (k_generate): the kernel is handed cam_origin

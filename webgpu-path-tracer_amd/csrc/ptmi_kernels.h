@@ -12,14 +12,13 @@
 //   k_accumulate framebuffer read-modify-write of main.wgsl:22-27 for every frame slot, in frame order.
 #pragma once
 #include "ptmi_device.h"
+#include "ptmi_tuning.h"
 
 namespace ptmi {
 
 constexpr int kBlock = 256;
 
-// k_bvh's claim counters: one per team of waves, 128 bytes apart.  Whoever fills a queue (k_generate, k_shade, k_prims)
-// zeroes them for the k_bvh launch that follows.
-constexpr uint32_t kHeadStride = 32, kMaxTeams = 64;
+// (k_bvh's claim counters, kHeadStride / kMaxTeams: ptmi_tuning.h)
 DEV void reset_heads(uint32_t* __restrict__ heads) {
   if (blockIdx.x == 0 && threadIdx.x < kMaxTeams) heads[threadIdx.x * kHeadStride] = 0u;
 }
@@ -136,13 +135,7 @@ __global__ __launch_bounds__(kBlock) void k_prims(DevScene S, Paths P, const Ste
   if (COUNT) reduce_counters(cn, totals, false);
 }
 
-// A wave refills its idle lanes once this many lanes are idle (or all are).
-constexpr int kRefillThreshold = 32;  // (round 3: 16 -> 32, configs[3] -3 %: idle lanes cost nothing on the gather path, and rays picked up together share their first fetches)
-// The triangle phase of the flat traversal runs once this many lanes hold a pending leaf (or nothing else can run).
-constexpr int kLeafBatch = 16;
-constexpr uint32_t kBvhRange = 512;  // slots a wave claims per global atomic (less when the queue is short); round 3: 256..1024 equal within noise, 2048 +1 %, 8192 +6 % (the last ranges are a tail)
-
-
+// (kRefillThreshold, kLeafBatch, kBvhRange — k_bvh's knob defaults: ptmi_tuning.h)
 
 // k_bvh, second edition (round 3).  Same scheduling (persistent single-wave blocks, team counters, flag scan, ballot refill),
 // same per-ray visit order, outcomes and counters; three changes to where the instructions and the round trips go:
