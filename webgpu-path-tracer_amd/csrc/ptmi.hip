@@ -711,11 +711,11 @@ int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_ite
 
 // k_tail in front of a step: traces the step's queue to the end if it is short (at most `limit` slots), else returns at once.  `six`: k_tail6 (tail_plan).
 int launch_tail(ptmi_ctx* c, const RenderConst& rc, const Paths& P, StepCtl* ctl, int first, uint32_t limit, bool six, const Carry& cy_in) {
-  // On trees of 12 levels and more a walk stops once fewer than tun.tail_park lanes are left in it while other lanes have work; the stragglers' state waits in three entries
-  // on top of their stacks (tail_body).  Shallow trees never park: their walks are short, and a parked ray's path waits for the next walk (round 4 measured both).
+  // On trees of 12 levels and more a walk stops once fewer than tun.tail_park lanes are left in it while other lanes have work; the stragglers' state waits in kParkEntries
+  // entries on top of their stacks (park, ptmi_device.h).  Shallow trees never park: their walks are short, and a parked ray's path waits for the next walk (round 4 measured both).
   Carry cy = cy_in;
   cy.park_below = (c->S.n_nodes > 0 && c->bvh_depth >= 12) ? c->tun.tail_park : 0;  // (shallower: configs[1] -4 % at 8 lanes, +4 % at 16, the default scene +37 %: profiles/r05_tail_park_shallow.txt)
-  const StackLayout st = stack_layout(c, cy.park_below > 0 ? 3 : 0);
+  const StackLayout st = stack_layout(c, cy.park_below > 0 ? kParkEntries : 0);
   const int waves_per_cu = c->tun.tail_waves_per_cu > 0 ? c->tun.tail_waves_per_cu : (six ? 24 : 16);
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)limit + 63) / 64, (uint64_t)c->num_cus * (uint64_t)waves_per_cu));
   HIP_TRY(c, c->d_spill.ensure(std::max<size_t>(16, (size_t)c->num_cus * 32 * (size_t)st.spill_entries * 64 * sizeof(int2))));  // (k_bvh's grids are no larger: one size for both)
@@ -877,7 +877,7 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   const int sa_carry = stack_alloc_for(c);
   const bool carry = c->tun.bvh_carry > 0 && c->S.n_nodes > 0 && c->bvh_depth >= c->tun.bvh_carry_min_depth && total >= (uint32_t)c->tun.bvh_carry_min_paths && p.max_bounces > 1;
   const uint32_t resv = carry ? (uint32_t)c->tun.bvh_carry_slots : 0u;
-  const int rec_words = 8 + 2 * sa_carry;
+  const int rec_words = carry_rec_words(sa_carry);
   if (carry)
     for (int k = 0; k < 2; k++) HIP_TRY(c, c->d_carry[k].ensure((size_t)resv * (size_t)rec_words * 4));
   auto carry_of = [&](int s) {  // what step s's kernels need to know: its queue's prefix, the next one's, the two pools

@@ -306,6 +306,19 @@ struct Paths {
                      // batch starts with one small memset of these flags instead of k_generate streaming 16 bytes of zeros per path
   uint32_t cap;      // slots per queue buffer
 };
+// Slot i of queue (q, h) holds no path: every reader passes it by.
+DEV void mark_hole(const Slots& q, const HitBuf& h, uint32_t i) {
+  reinterpret_cast<uint32_t*>(q.q1 + i)[3] = PID_HOLE;
+  h.mat[i] = HITMAT_HOLE;
+}
+// A slot's state and hit record, written in one go.
+DEV void store_slot(const Slots& q, const HitBuf& h, uint32_t i, float4 q0, float4 q1, float4 q2, float2 tp, uint32_t mat) {
+  q.q0[i] = q0;
+  q.q1[i] = q1;
+  q.q2[i] = q2;
+  h.tp[i] = tp;
+  h.mat[i] = mat;
+}
 
 // One 128-byte line per step: k_shade's blocks and waves claim their output regions of the NEXT step's queue with atomics on n_rays, and
 // same-line atomics serialise in one L2 channel at ~11 ns each — nothing else may share the line.
@@ -324,13 +337,27 @@ struct Carry {
   uint32_t resv;       // reserved prefix of THIS queue
   uint32_t resv_next;  // of the next one; 0 = this launch carries nothing over
   int after;           // iterations a wave goes on after the queue is exhausted
-  int rec_words;       // words per pool record: 8 (state word, sp, closest t, u, v, prim, material word, -) + 2 per stack entry
+  int rec_words;       // words per pool record: carry_rec_words(stack entries)
   uint32_t* pool_in;   // records of this queue's carried rays, by slot
   uint32_t* pool_out;  // records of the next queue's
   int park_below;      // k_tail only (round 5): its tree walk stops once fewer than this many lanes are still in it while other lanes have work, and the stragglers resume
                        // in the next walk (0 = a walk always runs to its longest ray's end) — tail_body
 };
+// A pool record: words 0-6 = state word, sp, closest t, u, v, prim, material word (a Walk: carry_save / carry_restore), word 7 unused, then 2 words per stack entry.
+constexpr int kCarryHeaderWords = 8;
+constexpr int carry_rec_words(int stack_entries) { return kCarryHeaderWords + 2 * stack_entries; }
 DEV bool dead_slot(uint32_t slot, uint32_t n_carried, uint32_t resv) { return slot >= n_carried && slot < resv; }
+// What a queue with the reserved prefix [0, resv) holds: slots [0, n_carried) rays the previous launch carried over, [n_carried, resv) nothing, [resv, n) the step's own.
+struct QueueExtent {
+  uint32_t n, n_carried;
+};
+DEV QueueExtent queue_extent(const StepCtl* ctl, uint32_t resv) {
+  QueueExtent q;
+  q.n_carried = resv ? min(ctl->n_carried, resv) : 0u;
+  q.n = ctl->n_rays;
+  if (q.n <= resv && q.n_carried == 0u) q.n = 0u;  // nothing but the empty carry prefix
+  return q;
+}
 // The hitScene tally of the batch being traced (slots that held a path, summed over its steps) is spread over kTallyLines counters on
 // lines of their own behind the 16 persistent totals (zeroed when a batch starts, added up by the k_accumulate call that folds its slot 0).
 constexpr int kTallyLines = 32;
@@ -725,6 +752,52 @@ DEV void tri_test2(const DevScene& S, int k, float4 t0, float4 t1, float4 t2, fl
   h.prim = (K_TRI << 28) | (uint32_t)k;
   h.mat = __float_as_uint(t1.w);
   if (COUNT) cn.mat_fetches++;
+}
+
+// A ray's place in its tree walk: what a walk iteration changes, what a carried ray's pool record and a parked ray's stack entries hold.
+struct Walk {
+  uint32_t node;  // state word
+  int sp;
+  float ct;       // closest_so_far
+  TriHit hit;
+};
+// Carry: the walk goes on from / moves into the pool record of queue slot `slot` (layout: kCarryHeaderWords)
+DEV void carry_restore(const Carry& cy, uint32_t slot, const LaneStack2& stk, Walk& w) {
+  const uint32_t* rec = cy.pool_in + (size_t)slot * (size_t)cy.rec_words;
+  w.node = rec[0];
+  w.sp = (int)rec[1];
+  w.ct = __uint_as_float(rec[2]);
+  w.hit.u = __uint_as_float(rec[3]), w.hit.v = __uint_as_float(rec[4]), w.hit.prim = rec[5], w.hit.mat = rec[6];
+  for (int e = 0; e < w.sp; e++) stack2_write(stk, e, rec[kCarryHeaderWords + 2 * e], __uint_as_float(rec[kCarryHeaderWords + 1 + 2 * e]));
+}
+DEV void carry_save(const Carry& cy, uint32_t slot, const LaneStack2& stk, const Walk& w) {
+  uint32_t* rec = cy.pool_out + (size_t)slot * (size_t)cy.rec_words;
+  rec[0] = w.node, rec[1] = (uint32_t)w.sp, rec[2] = __float_as_uint(w.ct), rec[3] = __float_as_uint(w.hit.u), rec[4] = __float_as_uint(w.hit.v), rec[5] = w.hit.prim, rec[6] = w.hit.mat;
+  for (int e = 0; e < w.sp; e++) {
+    uint32_t w0;
+    float w1;
+    stack2_read(stk, e, w0, w1);
+    rec[kCarryHeaderWords + 2 * e] = w0, rec[kCarryHeaderWords + 1 + 2 * e] = __float_as_uint(w1);
+  }
+}
+// k_tail's parked rays (Carry::park_below): the walk waits in kParkEntries entries on top of the lane's own stack, from entry w.sp on (the entries below stay
+// where they are) — the stack is laid out that much deeper (launch_tail).
+constexpr int kParkEntries = 3;
+DEV void park(const LaneStack2& stk, const Walk& w) {
+  stack2_write(stk, w.sp, w.node, w.ct);
+  stack2_write(stk, w.sp + 1, __float_as_uint(w.hit.u), w.hit.v);
+  stack2_write(stk, w.sp + 2, w.hit.prim, __uint_as_float(w.hit.mat));
+}
+DEV void unpark(const LaneStack2& stk, int sp, Walk& w) {
+  uint32_t w0;
+  float w1;
+  w.sp = sp;
+  stack2_read(stk, sp, w0, w1);
+  w.node = w0, w.ct = w1;
+  stack2_read(stk, sp + 1, w0, w1);
+  w.hit.u = __uint_as_float(w0), w.hit.v = w1;
+  stack2_read(stk, sp + 2, w0, w1);
+  w.hit.prim = w0, w.hit.mat = __float_as_uint(w1);
 }
 
 // ---- HitRecord reconstruction (the accepting branch of the winning primitive test) ------------------

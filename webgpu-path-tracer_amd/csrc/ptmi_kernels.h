@@ -137,6 +137,86 @@ __global__ __launch_bounds__(kBlock) void k_prims(DevScene S, Paths P, const Ste
 
 // (kRefillThreshold, kLeafBatch, kBvhRange — k_bvh's knob defaults: ptmi_tuning.h)
 
+// k_bvh's and k_tail's stopwatch (measurement builds with PTMI_LANE_TALLY, tools/bvh_regions.py): a wave keeps cycles, marks and lanes per region in registers and
+// adds them to g_bvh_tally / g_tail_tally when it ends.  BT(k, dep, lanes) closes the interval since the previous mark and charges it to region k of the
+// Stopwatch `sw` in scope.  Without the macro the struct is empty and BT() is nothing.
+enum : int { BT_SCAN = 0, BT_PICKUP = 1, BT_INNER_FETCH = 2, BT_INNER_STEP = 3, BT_LEAF_FETCH = 4, BT_LEAF_TEST = 5, BT_RETIRE = 6, BT_VOTE = 7, BT_CARRY = 8, BT_START = 9, kBvhTallies = 10 };
+enum : int { TB_TAKE = 0, TB_WALK_FETCH = 1, TB_WALK_STEP = 2, TB_WALK_LEAF = 3, TB_SHADE = 4, TB_PRIMS = 5, TB_VOTE = 6 };  // k_tail's regions (same stopwatch)
+#ifdef PTMI_LANE_TALLY
+__device__ unsigned long long g_bvh_tally[3 * kBvhTallies];  // {cycles, marks, lanes} per region
+__device__ unsigned long long g_tail_tally[3 * kBvhTallies];
+struct Stopwatch {
+  unsigned long long cyc[kBvhTallies], last;
+  uint32_t marks[kBvhTallies], lanes[kBvhTallies];
+  DEV void begin() {
+    for (int k = 0; k < kBvhTallies; k++) cyc[k] = 0ull, marks[k] = 0u, lanes[k] = 0u;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(last)::"memory");
+  }
+  DEV void mark(int k, float dep, uint32_t n_lanes) {
+    unsigned long long now;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now) : "v"(dep) : "memory");
+    cyc[k] += now - last, marks[k] += 1u, lanes[k] += n_lanes;
+    last = now;
+  }
+  DEV void flush(unsigned long long* __restrict__ tally) const {
+    if (lane_id() != 0) return;
+    for (int k = 0; k < kBvhTallies; k++) {
+      if (marks[k] == 0u) continue;
+      atomicAdd(&tally[3 * k], cyc[k]);
+      atomicAdd(&tally[3 * k + 1], (unsigned long long)marks[k]);
+      atomicAdd(&tally[3 * k + 2], (unsigned long long)lanes[k]);
+    }
+  }
+};
+#define BT(k, dep, lanes) sw.mark(k, dep, (uint32_t)(lanes))
+#define BT_FLUSH(tally) sw.flush(tally)
+#else
+struct Stopwatch {
+  DEV void begin() {}
+};
+#define BT(k, dep, lanes) ((void)0)
+#define BT_FLUSH(tally) ((void)0)
+#endif
+
+// ---- a ray's tree walk (hitScene part 2), as k_bvh and k_tail both run it: what stays the same for the ray, and one iteration's two phases ----
+struct WalkRay {
+  f3 o, d, inv;
+  uint32_t negmask;  // bit a: d[a] < 0
+  ObjRay orr;
+};
+DEV WalkRay make_walk_ray(const DevScene& S, f3 o, f3 d) {
+  WalkRay r;
+  r.o = o, r.d = d;
+  r.inv = rcp3_exact_il(d);
+  r.negmask = (d.x < 0 ? 1u : 0u) | (d.y < 0 ? 2u : 0u) | (d.z < 0 ? 4u : 0u);
+  r.orr.mesh = -1;
+  r.orr.o = r.orr.d = o;
+  if (S.uniform_gid >= 0) obj_ray_uniform(S, o, d, r.orr);
+  return r;
+}
+// Leaf phase, for a lane whose state word is a leaf ref: its triangles are tested (one per leaf with the reference's builder), then the stack is popped.
+// FETCH_MARK >= 0: the stopwatch region that the wait for the first triangle record is charged to.
+template <bool COUNT, int FETCH_MARK = -1>
+DEV void walk_leaf(const DevScene& S, WalkRay& ray, const LaneStack2& stk, Walk& w, Counters& cn, Stopwatch& sw) {
+  const int2 lc = (w.node & REF_MULTI) ? S.leaf_table[w.node & REF_IDX] : make_int2((int)(w.node & REF_IDX), 1);
+  for (int j = 0; j < lc.y; j++) {
+    const float4* rec = S.pretri + 4 * (size_t)(lc.x + j);
+    const float4 g0 = rec[0], g1 = rec[1], g2 = rec[2], g3 = rec[3];
+    if (FETCH_MARK >= 0 && j == 0) BT(FETCH_MARK, g0.x + g1.x + g2.x + g3.x, __popcll(__ballot(1)));
+    tri_test2<COUNT>(S, lc.x + j, g0, g1, g2, g3, ray.o, ray.d, ray.orr, w.ct, w.hit, cn);
+  }
+  w.node = pop_until_pass2(stk, w.sp, w.ct, cn, COUNT);
+}
+// Inner phase, for a lane whose state word is a pair index: the near child is visited, the far one pushed; a near child that fails pops.
+template <bool COUNT, bool NOABORT, int FETCH_MARK>
+DEV void walk_inner(const DevScene& S, const WalkRay& ray, const LaneStack2& stk, Walk& w, int stack_size, Counters& cn, Stopwatch& sw) {
+  const float4* rec = S.pairs + 4 * (size_t)w.node;
+  const float4 f0 = rec[0], f1 = rec[1], f2 = rec[2], f3v = rec[3];
+  BT(FETCH_MARK, f0.x + f1.x + f2.x + f3v.x, __popcll(__ballot(1)));
+  w.node = inner_step2<COUNT, NOABORT>(f0, f1, f2, f3v, ray.o, ray.inv, S.tmin, ray.negmask, w.ct, stack_size, stk, w.sp, cn);
+  if (w.node == N_POP) w.node = pop_until_pass2(stk, w.sp, w.ct, cn, COUNT);
+}
+
 // k_bvh, second edition (round 3).  Same scheduling (persistent single-wave blocks, team counters, flag scan, ballot refill),
 // same per-ray visit order, outcomes and counters; three changes to where the instructions and the round trips go:
 //   * ONE fetch per lane per iteration whatever the lane is about to do — the pair record of its inner node or the pretri record
@@ -146,23 +226,6 @@ __global__ __launch_bounds__(kBlock) void k_prims(DevScene S, Paths P, const Ste
 //   * one shared pop section behind both kinds of step, on 8-byte LDS stack entries (ptmi_device.h).
 // (Storing an accepted hit at once instead of at the end of the ray saved four registers and lost 12 %: on gfx9 stores count on
 // vmcnt like loads, so every later fetch waited for them.)
-#ifdef PTMI_LANE_TALLY
-// k_bvh's stopwatch (measurement builds, tools/bvh_regions.py): a wave keeps cycles, marks and lanes per region in registers and adds them to
-// g_bvh_tally when it ends.  BT(k, dep, lanes) closes the interval since the previous mark and charges it to region k.
-enum : int { BT_SCAN = 0, BT_PICKUP = 1, BT_INNER_FETCH = 2, BT_INNER_STEP = 3, BT_LEAF_FETCH = 4, BT_LEAF_TEST = 5, BT_RETIRE = 6, BT_VOTE = 7, BT_CARRY = 8, BT_START = 9, kBvhTallies = 10 };
-__device__ unsigned long long g_bvh_tally[3 * kBvhTallies];  // {cycles, marks, lanes} per region
-enum : int { TB_TAKE = 0, TB_WALK_FETCH = 1, TB_WALK_STEP = 2, TB_WALK_LEAF = 3, TB_SHADE = 4, TB_PRIMS = 5, TB_VOTE = 6 };  // k_tail's regions (same stopwatch)
-__device__ unsigned long long g_tail_tally[3 * kBvhTallies];
-#define BT(k, dep, lanes)                                                                                  \
-  do {                                                                                                     \
-    unsigned long long now_;                                                                               \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_) : "v"(dep) : "memory");               \
-    bt_cyc[k] += now_ - bt_last, bt_marks[k] += 1u, bt_lanes[k] += (uint32_t)(lanes);                      \
-    bt_last = now_;                                                                                        \
-  } while (0)
-#else
-#define BT(k, dep, lanes) ((void)0)
-#endif
 constexpr int kScanGroups = 3, kCandSlots = 64 * (kScanGroups + 1);  // a pass adds at most 64 x kScanGroups candidates to fewer than 64
 template <bool COUNT, bool NOABORT>
 DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads, uint32_t n_teams, int stack_size, int lds_entries, int spill_entries,
@@ -175,9 +238,8 @@ DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl,
   stk.spill = spill + (size_t)wave_id * (size_t)spill_entries * 64 + lane;
   stk.lds_entries = lds_entries;
   uint32_t* cand = reinterpret_cast<uint32_t*>(lds_stack + lds_entries * 2 * 64);  // [kCandSlots] candidate slots
-  const uint32_t n_carried = cy.resv ? min(ctl->n_carried, cy.resv) : 0u;  // slots [0, n_carried) hold rays the previous launch carried over, [n_carried, resv) nothing
-  uint32_t n = ctl->n_rays;
-  if (n <= cy.resv && n_carried == 0u) n = 0u;  // nothing but the empty carry prefix
+  const QueueExtent qe = queue_extent(ctl, cy.resv);
+  const uint32_t n = qe.n, n_carried = qe.n_carried;
   const uint32_t range = min(range_cap, max(64u, ((n / (2u * n_waves)) + 63u) & ~63u));
   const uint32_t team = wave_id % n_teams;
   Counters cn = {0, 0, 0, 0, 0};
@@ -187,35 +249,30 @@ DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl,
   int tail_iters = 0;        // iterations since this wave found the queue exhausted (wave-uniform)
   bool may_carry = cy.resv_next != 0u;
   // the lane's ray
-  uint32_t node = N_DONE, myslot = 0, negmask = 0;
-  int sp = 0;
-  f3 o = mk3(0, 0, 0), d = o, inv = o;
-  float ct = 0.0f;
-  ObjRay orr;
-  orr.mesh = -1;
-  orr.o = orr.d = o;
-  TriHit hit = {0.0f, 0.0f, 0u, 0u};
+  uint32_t myslot = 0;
+  Walk w = {N_DONE, 0, 0.0f, {0.0f, 0.0f, 0u, 0u}};
+  WalkRay ray;
+  ray.o = ray.d = ray.inv = ray.orr.o = ray.orr.d = mk3(0, 0, 0);
+  ray.negmask = 0;
+  ray.orr.mesh = -1;
   bool has = false;  // this lane holds a ray (traversing, or finished and not yet retired)
   const uint32_t root = __float_as_uint(S.root_lo.w);
   const uint32_t root_node = (root & REF_LEAF) ? root : (root & REF_IDX);
-#ifdef PTMI_LANE_TALLY
-  unsigned long long bt_cyc[kBvhTallies] = {0}, bt_last;
-  uint32_t bt_marks[kBvhTallies] = {0}, bt_lanes[kBvhTallies] = {0};
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(bt_last)::"memory");
-#endif
+  Stopwatch sw;
+  sw.begin();
   for (;;) {
     // retire finished rays (stores only): a triangle beat what part 1 had found; otherwise the record stands as it is
     BT(BT_VOTE, 0.0f, 0);
-    if (has && node == N_DONE) {
-      if (hit.prim != 0u) {
-        P.hin.tp[myslot] = make_float2(ct, __uint_as_float(hit.prim));
-        P.uv[myslot] = make_float2(hit.u, hit.v);
-        P.hin.mat[myslot] = hit.mat;
+    if (has && w.node == N_DONE) {
+      if (w.hit.prim != 0u) {
+        P.hin.tp[myslot] = make_float2(w.ct, __uint_as_float(w.hit.prim));
+        P.uv[myslot] = make_float2(w.hit.u, w.hit.v);
+        P.hin.mat[myslot] = w.hit.mat;
       }
       has = false;
     }
     BT(BT_RETIRE, 0.0f, 0);
-    uint64_t hm = __ballot(node != N_DONE);
+    uint64_t hm = __ballot(w.node != N_DONE);
     int nact = __popcll(hm);
     if ((64 - nact) >= (nact == 0 ? 1 : refill_threshold)) {
       const uint32_t want = (uint32_t)(64 - nact);
@@ -258,34 +315,23 @@ DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl,
         const uint64_t idle = ~hm;
         const uint32_t k = lanes_below(idle);
         const uint32_t take = min(ncand, want);
-        if (node == N_DONE && k < take) {
+        if (w.node == N_DONE && k < take) {
           myslot = cand[ncand - 1u - k];
           const float4 r1 = P.in.q1[myslot];
-          ct = P.hin.tp[myslot].x;  // closest_so_far after part 1 of hitScene; the rest of that record stands unless a triangle wins
-          o = mk3(cam);
+          w.ct = P.hin.tp[myslot].x;  // closest_so_far after part 1 of hitScene; the rest of that record stands unless a triangle wins
+          f3 o = mk3(cam);
           if (cam.w == 0.0f) o = mk3(P.in.q0[myslot]);  // (wave-uniform: step 0 picks a ray up with two gathers instead of three)
-          d = mk3(r1);
-          inv = rcp3_exact_il(d);
-          negmask = (d.x < 0 ? 1u : 0u) | (d.y < 0 ? 2u : 0u) | (d.z < 0 ? 4u : 0u);
-          orr.mesh = -1;
-          if (S.uniform_gid >= 0) obj_ray_uniform(S, o, d, orr);
-          sp = 0;
-          hit.prim = 0u;
+          ray = make_walk_ray(S, o, mk3(r1));
+          w.sp = 0;
+          w.hit.prim = 0u;
           has = true;
-          node = root_node;
-          if (myslot < cy.resv) {  // a ray the previous launch carried over: its traversal goes on where it stopped
-            const uint32_t* rec = cy.pool_in + (size_t)myslot * (size_t)cy.rec_words;
-            node = rec[0];
-            sp = (int)rec[1];
-            ct = __uint_as_float(rec[2]);
-            hit.u = __uint_as_float(rec[3]), hit.v = __uint_as_float(rec[4]), hit.prim = rec[5], hit.mat = rec[6];
-            for (int e = 0; e < sp; e++) stack2_write(stk, e, rec[8 + 2 * e], __uint_as_float(rec[9 + 2 * e]));
-          }
+          w.node = root_node;
+          if (myslot < cy.resv) carry_restore(cy, myslot, stk, w);  // a ray the previous launch carried over: its traversal goes on where it stopped
         }
         ncand -= take;
-        hm = __ballot(node != N_DONE);
+        hm = __ballot(w.node != N_DONE);
         nact = __popcll(hm);
-        BT(BT_PICKUP, inv.x + ct, take);
+        BT(BT_PICKUP, ray.inv.x + w.ct, take);
       }
     }
     if (nact == 0) break;  // nothing in flight, nothing buffered, queue exhausted
@@ -297,32 +343,15 @@ DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl,
     // scene, and a wave waits for the slowest lane of a fetch — mixing them into every pair fetch (UNIFIED) made every wait a slow one
     // (configs[3]: 581 ms against 514 per 128 spp although it issues 11 % fewer vector and 46 % fewer memory instructions).
     do {
-      const uint64_t pm = __ballot((int)node < 0), im = __ballot(node < N_INNER_LIMIT);
+      const uint64_t pm = __ballot((int)w.node < 0), im = __ballot(w.node < N_INNER_LIMIT);
       BT(BT_VOTE, 0.0f, 0);
       if (pm != 0ull && (__popcll(pm) >= leaf_batch || im == 0ull)) {
-        if ((int)node < 0) {
-          const int2 lc = (node & REF_MULTI) ? S.leaf_table[node & REF_IDX] : make_int2((int)(node & REF_IDX), 1);
-          for (int j = 0; j < lc.y; j++) {  // one triangle per leaf with the reference's builder
-            const float4* rec = S.pretri + 4 * (size_t)(lc.x + j);
-            const float4 g0 = rec[0], g1 = rec[1], g2 = rec[2], g3 = rec[3];
-#ifdef PTMI_LANE_TALLY
-            if (j == 0) BT(BT_LEAF_FETCH, g0.x + g1.x + g2.x + g3.x, __popcll(__ballot(1)));
-#endif
-            tri_test2<COUNT>(S, lc.x + j, g0, g1, g2, g3, o, d, orr, ct, hit, cn);
-          }
-          node = pop_until_pass2(stk, sp, ct, cn, COUNT);
-        }
-        BT(BT_LEAF_TEST, ct, __popcll(pm));
+        if ((int)w.node < 0) walk_leaf<COUNT, BT_LEAF_FETCH>(S, ray, stk, w, cn, sw);
+        BT(BT_LEAF_TEST, w.ct, __popcll(pm));
       }
-      if (node < N_INNER_LIMIT) {
-        const float4* rec = S.pairs + 4 * (size_t)node;
-        const float4 f0 = rec[0], f1 = rec[1], f2 = rec[2], f3v = rec[3];
-        BT(BT_INNER_FETCH, f0.x + f1.x + f2.x + f3v.x, __popcll(__ballot(1)));
-        node = inner_step2<COUNT, NOABORT>(f0, f1, f2, f3v, o, inv, S.tmin, negmask, ct, stack_size, stk, sp, cn);
-        if (node == N_POP) node = pop_until_pass2(stk, sp, ct, cn, COUNT);
-      }
-      BT(BT_INNER_STEP, __uint_as_float(node), __popcll(im));
-      working = __popcll(__ballot(node != N_DONE));
+      if (w.node < N_INNER_LIMIT) walk_inner<COUNT, NOABORT, BT_INNER_FETCH>(S, ray, stk, w, stack_size, cn, sw);
+      BT(BT_INNER_STEP, __uint_as_float(w.node), __popcll(im));
+      working = __popcll(__ballot(w.node != N_DONE));
       if (!more && may_carry && ++tail_iters >= cy.after) break;  // (wave-uniform)
     } while (working >= min_working);
     }
@@ -330,7 +359,7 @@ DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl,
       // The queue is exhausted and this wave has gone on for `after` iterations: what it still holds are the launch's long rays.  Each one moves
       // into a slot of the next step's queue with its traversal state in the pool; its slot here becomes a hole, so this step's k_shade passes it by.
       bool failed = false;
-      if (node != N_DONE) {
+      if (w.node != N_DONE) {
         const uint32_t ns = atomicAdd(&ctl[1].n_carried, 1u);
         if (ns < cy.resv_next) {
           const float4 r1 = P.in.q1[myslot];
@@ -340,17 +369,9 @@ DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl,
           P.out.q0[ns] = r0, P.out.q1[ns] = r1, P.out.q2[ns] = r2;
           P.hout.tp[ns] = P.hin.tp[myslot];    // hitScene part 1's record: stands unless a triangle has won or wins later
           P.hout.mat[ns] = P.hin.mat[myslot];  // (HITMAT_BVH still set)
-          uint32_t* rec = cy.pool_out + (size_t)ns * (size_t)cy.rec_words;
-          rec[0] = node, rec[1] = (uint32_t)sp, rec[2] = __float_as_uint(ct), rec[3] = __float_as_uint(hit.u), rec[4] = __float_as_uint(hit.v), rec[5] = hit.prim, rec[6] = hit.mat;
-          for (int e = 0; e < sp; e++) {
-            uint32_t w0;
-            float w1;
-            stack2_read(stk, e, w0, w1);
-            rec[8 + 2 * e] = w0, rec[9 + 2 * e] = __float_as_uint(w1);
-          }
-          reinterpret_cast<uint32_t*>(P.in.q1 + myslot)[3] = PID_HOLE;
-          P.hin.mat[myslot] = HITMAT_HOLE;
-          node = N_DONE;
+          carry_save(cy, ns, stk, w);
+          mark_hole(P.in, P.hin, myslot);
+          w.node = N_DONE;
           has = false;
         } else {  // the pool is full: this ray is traversed to its end here after all
           atomicSub(&ctl[1].n_carried, 1u);
@@ -361,15 +382,7 @@ DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl,
       BT(BT_CARRY, 0.0f, 0);
     }
   }
-#ifdef PTMI_LANE_TALLY
-  if (lane == 0)
-    for (int k = 0; k < kBvhTallies; k++) {
-      if (bt_marks[k] == 0u) continue;
-      atomicAdd(&g_bvh_tally[3 * k], bt_cyc[k]);
-      atomicAdd(&g_bvh_tally[3 * k + 1], (unsigned long long)bt_marks[k]);
-      atomicAdd(&g_bvh_tally[3 * k + 2], (unsigned long long)bt_lanes[k]);
-    }
-#endif
+  BT_FLUSH(g_bvh_tally);
   if (COUNT) reduce_counters(cn, totals, true);
 }
 
@@ -392,6 +405,17 @@ struct NewState {
   int bounce;
   uint32_t rng, pid;
 };
+// (A state is zeroed before shade_one although only the survivors' values are read: left undefined, the allocator needs 8 registers more — scratch at 80 VGPRs.)
+DEV NewState zero_state() {
+  NewState ns;
+  ns.o = ns.d = ns.T = mk3(0, 0, 0);
+  ns.bounce = 0, ns.rng = 0, ns.pid = 0;
+  return ns;
+}
+// ... as the three words of its slot (Slots)
+DEV float4 pack_q0(const NewState& ns) { return make_float4(ns.o.x, ns.o.y, ns.o.z, __uint_as_float(ns.rng)); }
+DEV float4 pack_q1(const NewState& ns) { return make_float4(ns.d.x, ns.d.y, ns.d.z, __uint_as_float(ns.pid)); }
+DEV float4 pack_q2(const NewState& ns) { return make_float4(ns.T.x, ns.T.y, ns.T.z, __int_as_float(ns.bounce)); }
 
 // One path's iteration of the `for i < MAX_BOUNCES` loop body after hitScene (traceRay.wgsl:10-80).
 // Returns true when the path continues (its state for the next step is in `ns`), false when the slot is done.
@@ -599,6 +623,87 @@ constexpr int kTailRefill = 16;  // k_tail: idle lanes before a wave takes new p
 constexpr bool kMissShortcut = true;  // definite misses are settled in k_shade's flush phase
 constexpr int kSChunk = 512;  // slots a k_shade block sorts, shades and compacts at a time
 
+// A wave's OUTPUT REGION [cur, rend) of the next queue (wave-uniform): every wave of a k_shade block fills regions of its own (>= 128 slots) — no barrier, no
+// serial section where the survivors are placed.
+// The waves' FIRST regions come from one claim per block (`region` slots), made by whichever wave needs a region first; the others pick their quarter
+// (`wregion`) up from LDS (a launch made at least one claim per wave before: 6144 atomics on one address ~ 70 us — of a tail step with 100 us of
+// work).  A block without survivors claims nothing, so a queue of holes still dies out.  Later regions a wave claims for itself on ctl[1].n_rays.
+constexpr uint32_t kR0Empty = 0xffffffffu, kR0Busy = 0xfffffffeu, kR0Full = 0xfffffffdu;
+__shared__ uint32_t s_region0;  // the block's first claim: kR0Empty until a wave makes it (set by thread 0, visible after the block's first barrier)
+constexpr uint32_t kNoSlot = 0xffffffffu;
+struct OutRegion {
+  uint32_t cur, rend;
+  // The slot of the next queue for this lane's survivor (`keep`), kNoSlot for a lane without one.  What no longer fits the current region continues in the
+  // wave's next one, of `wregion_later` slots unless it is the wave's first.
+  DEV uint32_t place(bool keep, uint32_t region, uint32_t wregion, uint32_t wregion_later, StepCtl* __restrict__ ctl, uint32_t cap, unsigned long long* __restrict__ totals) {
+    const int lane = lane_id();
+    const uint64_t km = __ballot(keep);
+    const uint32_t kept = (uint32_t)__popcll(km), rank = lanes_below(km);
+    const uint32_t b0 = cur, n0 = min(kept, rend - cur);  // what still fits this wave's current region (wave-uniform)
+    uint32_t b1 = kNoSlot;
+    cur += n0;
+    if (kept > n0) {  // claim the wave's next region for the rest
+      uint32_t nb = 0, claimed = wregion;
+      bool full;
+      if (rend == 0u) {  // the wave's first region: its quarter of the block's claim
+        if (lane == 0) nb = atomicCAS(&s_region0, kR0Empty, kR0Busy);
+        nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
+        if (nb == kR0Empty) {  // ours to make
+          if (lane == 0) {
+            nb = atomicAdd(&ctl[1].n_rays, region);
+            if (nb + region > cap) {  // (see below)
+              atomicAdd(&totals[15], 1ull);
+              atomicSub(&ctl[1].n_rays, region);
+              nb = kR0Full;
+            }
+            atomicExch(&s_region0, nb);
+          }
+          nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
+        } else {
+          while (nb == kR0Busy) {  // another wave of the block is at it: a global atomic's round trip
+            __builtin_amdgcn_s_sleep(8);
+            if (lane == 0) nb = atomicAdd(&s_region0, 0u);
+            nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
+          }
+        }
+        full = nb == kR0Full;
+        nb += (threadIdx.x >> 6) * wregion;
+      } else {
+        claimed = wregion_later;
+        if (lane == 0) nb = atomicAdd(&ctl[1].n_rays, claimed);
+        nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
+        full = nb + claimed > cap;
+        if (full && lane == 0) {
+          atomicAdd(&totals[15], 1ull);
+          atomicSub(&ctl[1].n_rays, claimed);
+        }
+      }
+      // full cannot happen with the host's sizing; never write out of bounds.  The survivors that still fit the current region are written as usual, the
+      // rest is dropped and the claim is handed back (every later claim overflows too and does the same, so the queue length ends up within the buffer);
+      // the host reports the flag as an error on the next synchronising call.
+      if (!full) {
+        b1 = nb;
+        cur = nb + (kept - n0);
+        rend = nb + claimed;
+      }
+    }
+    if (keep && (rank < n0 || b1 != kNoSlot)) return (rank < n0) ? (b0 + rank) : (b1 + (rank - n0));
+    return kNoSlot;
+  }
+  // At the wave's end, what is left of its last region becomes holes — all of its quarter of the block's claim if it never needed one.
+  // `block_claim`: s_region0 is this wave's to read (a barrier lies between the block's last place() and here).
+  DEV void close(const Paths& P, uint32_t wregion, bool block_claim) {
+    if (rend == 0u && block_claim && s_region0 < kR0Full) {
+      cur = s_region0 + (threadIdx.x >> 6) * wregion;
+      rend = cur + wregion;
+    }
+    for (uint32_t i = cur + (uint32_t)lane_id(); i < rend; i += 64u) {
+      LT(LT_HOLE);
+      mark_hole(P.out, P.hout, i);
+    }
+  }
+};
+
 // ray_color's loop body for one step, 512 slots at a time per block:
 //   1  (SORT) LDS counting sort of the chunk by the shade bin in each slot's material word (ballot ranks), so that
 //      the waves are (almost) uniform in the 4-way material switch of scatterRay.wgsl; holes drop out here.  Scenes
@@ -618,19 +723,13 @@ DEV void shade_body(const DevScene& S, const RenderConst& rc, const Paths& P, St
   __shared__ uint32_t s_nout, s_next;
   const QuadL L = load_light(S);
   const int lane = lane_id();
-  const uint32_t n_carried = resv ? min(ctl->n_carried, resv) : 0u;  // (Carry: slots [n_carried, resv) of this queue hold nothing)
-  uint32_t n = ctl->n_rays;
-  if (n <= resv && n_carried == 0u) n = 0u;
+  const QueueExtent qe = queue_extent(ctl, resv);
+  const uint32_t n = qe.n, n_carried = qe.n_carried;
   // region size: a block handles about n / gridDim slots per launch; 1/16 of that per claim keeps both the
   // number of atomics and the holes left at the end (at most one region per block) small
   const uint32_t region = max((uint32_t)kSChunk, ((n / gridDim.x / kRegionDiv) + 511u) & ~511u);
-  const uint32_t wregion = region / (kBlock / 64);  // every wave fills output regions of its own (>= 128 slots): no barrier, no serial section in the flush phase
-  uint32_t w_cur = 0, w_rend = 0;                   // this wave's current output region [w_cur, w_rend) of the next queue (wave-uniform)
-  // The waves' FIRST regions come from one claim per block, made by whichever wave needs a region first; the others pick their quarter
-  // up from LDS (a launch made at least one claim per wave before: 6144 atomics on one address ~ 70 us — of a tail step with 100 us of
-  // work).  A block without survivors claims nothing, so a queue of holes still dies out.
-  constexpr uint32_t kR0Empty = 0xffffffffu, kR0Busy = 0xfffffffeu, kR0Full = 0xfffffffdu;
-  __shared__ uint32_t s_region0;
+  const uint32_t wregion = region / (kBlock / 64);  // every wave fills output regions of its own (OutRegion)
+  OutRegion out = {0u, 0u};
   if (threadIdx.x == 0) s_region0 = kR0Empty;  // (visible after the first barrier of the chunk loop)
   uint32_t my_valid = 0;  // lane 0 of a wave: slots holding a path seen so far (= hitScene invocations)
   uint32_t my_missed = 0;  // lane 0 of a wave: new rays that turned out to be misses in the flush phase (progressive mode)
@@ -645,9 +744,9 @@ DEV void shade_body(const DevScene& S, const RenderConst& rc, const Paths& P, St
       bb = (uint32_t)__shfl((int)bb, leader, 64);
       if (survive) {
         const uint32_t q = bb + lanes_below(mk);
-        s_q0[q] = make_float4(ns.o.x, ns.o.y, ns.o.z, __uint_as_float(ns.rng));
-        s_q1[q] = make_float4(ns.d.x, ns.d.y, ns.d.z, __uint_as_float(ns.pid));
-        s_q2[q] = make_float4(ns.T.x, ns.T.y, ns.T.z, __int_as_float(ns.bounce));
+        s_q0[q] = pack_q0(ns);
+        s_q1[q] = pack_q1(ns);
+        s_q2[q] = pack_q2(ns);
       }
     }
   };
@@ -710,9 +809,7 @@ DEV void shade_body(const DevScene& S, const RenderConst& rc, const Paths& P, St
         if (k0 >= nvalid) break;
         const uint32_t k = k0 + lane;
         bool survive = false;
-        NewState ns;
-        ns.o = ns.d = ns.T = mk3(0, 0, 0);
-        ns.bounce = 0, ns.rng = 0, ns.pid = 0;
+        NewState ns = zero_state();
         if (k < nvalid) {
           const SlotState st = load_slot(P, base + s_sorted[k], first != 0, rc);
           const TriFetch tf = tri_fetch(S, P.uv, st.slot, __float_as_uint(st.tp.y));  // (issued ahead of the material's loads, consumed after them)
@@ -747,67 +844,12 @@ DEV void shade_body(const DevScene& S, const RenderConst& rc, const Paths& P, St
           keep = true;
         }
       }
-      const uint64_t km = __ballot(keep);
-      const uint32_t kept = (uint32_t)__popcll(km);
-      if (kept == 0) continue;
-      const uint32_t rank = lanes_below(km);
-      const uint32_t b0 = w_cur, n0 = min(kept, w_rend - w_cur);  // what still fits this wave's current region (wave-uniform)
-      uint32_t b1 = 0xffffffffu;
-      w_cur += n0;
-      if (kept > n0) {  // claim the wave's next region for the rest
-        uint32_t nb = 0;
-        bool full;
-        if (w_rend == 0u) {  // the wave's first region: its quarter of the block's claim
-          if (lane == 0) nb = atomicCAS(&s_region0, kR0Empty, kR0Busy);
-          nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
-          if (nb == kR0Empty) {  // ours to make
-            if (lane == 0) {
-              nb = atomicAdd(&ctl[1].n_rays, region);
-              if (nb + region > P.cap) {  // cannot happen with the host's sizing, see below
-                atomicAdd(&totals[15], 1ull);
-                atomicSub(&ctl[1].n_rays, region);
-                nb = kR0Full;
-              }
-              atomicExch(&s_region0, nb);
-            }
-            nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
-          } else {
-            while (nb == kR0Busy) {  // another wave of the block is at it: a global atomic's round trip
-              __builtin_amdgcn_s_sleep(8);
-              if (lane == 0) nb = atomicAdd(&s_region0, 0u);
-              nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
-            }
-          }
-          full = nb == kR0Full;
-          nb += (threadIdx.x >> 6) * wregion;
-        } else {
-          if (lane == 0) nb = atomicAdd(&ctl[1].n_rays, wregion);
-          nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
-          full = nb + wregion > P.cap;
-          if (full && lane == 0) {
-            atomicAdd(&totals[15], 1ull);
-            atomicSub(&ctl[1].n_rays, wregion);
-          }
-        }
-        if (full) {  // cannot happen with the host's sizing; never write out of bounds
-          // The survivors that still fit the current region are written as usual, the rest is dropped and the claim is
-          // handed back (every later claim overflows too and does the same, so the queue length ends up within the buffer);
-          // the host reports the flag as an error on the next synchronising call.
-        } else {
-          b1 = nb;
-          w_cur = nb + (kept - n0);
-          w_rend = nb + wregion;
-        }
-      }
-      if (keep && (rank < n0 || b1 != 0xffffffffu)) {
-        const uint32_t dst = (rank < n0) ? (b0 + rank) : (b1 + (rank - n0));
+      if (__ballot(keep) == 0ull) continue;
+      const uint32_t dst = out.place(keep, region, wregion, wregion, ctl, P.cap, totals);
+      if (dst != kNoSlot) {
         float4 a0 = s_q0[q];
         a0.w = __uint_as_float(rng);
-        P.out.q0[dst] = a0;
-        P.out.q1[dst] = s_q1[q];
-        P.out.q2[dst] = s_q2[q];
-        P.hout.tp[dst] = tp;
-        P.hout.mat[dst] = hm;
+        store_slot(P.out, P.hout, dst, a0, s_q1[q], s_q2[q], tp, hm);
       }
     }
     if (!MULTI) {
@@ -818,15 +860,7 @@ DEV void shade_body(const DevScene& S, const RenderConst& rc, const Paths& P, St
   }
   // hitScene invocations: this step's slots that held a path + the next step's that were settled here; one of kTallyLines counters per block
   if (lane == 0 && my_missed + my_valid) atomicAdd(tally_line(totals, blockIdx.x), my_missed + my_valid);
-  // what is left of each wave's last region becomes holes — all of its quarter of the block's claim if it never needed one
-  if (w_rend == 0u && blockIdx.x * (uint32_t)kSChunk < n && s_region0 < kR0Full) {  // (a block without a chunk passed no barrier: s_region0 is not its to read)
-    w_cur = s_region0 + (threadIdx.x >> 6) * wregion;
-    w_rend = w_cur + wregion;
-  }
-  for (uint32_t i = w_cur + (uint32_t)lane; i < w_rend; i += 64u) {
-    reinterpret_cast<uint32_t*>(P.out.q1 + i)[3] = PID_HOLE;
-    P.hout.mat[i] = HITMAT_HOLE;
-  }
+  out.close(P, wregion, blockIdx.x * (uint32_t)kSChunk < n);  // (a block without a chunk passed no barrier: s_region0 is not its to read)
   if (COUNT) reduce_counters(cn, totals, false);
 }
 
@@ -843,8 +877,6 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
   constexpr uint32_t kRing = 128, kWaves = kBlock / 64;
   static_assert((size_t)kWaves * kRing == (size_t)kSChunk, "the rings take the LDS the block version's staging arrays take");
   __shared__ float4 s_q0[kWaves * kRing], s_q1[kWaves * kRing], s_q2[kWaves * kRing];
-  constexpr uint32_t kR0Empty = 0xffffffffu, kR0Busy = 0xfffffffeu, kR0Full = 0xfffffffdu;
-  __shared__ uint32_t s_region0;  // the waves' first regions: one claim per block (see shade_body)
   if (threadIdx.x == 0) s_region0 = kR0Empty;
 #ifdef PTMI_LANE_TALLY
   if (threadIdx.x < kLaneTallies * 2) s_lane_tally[threadIdx.x] = 0u;
@@ -856,15 +888,14 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
   const int lane = lane_id();
   const uint32_t wv = threadIdx.x >> 6;
   float4 *const r0 = s_q0 + wv * kRing, *const r1 = s_q1 + wv * kRing, *const r2 = s_q2 + wv * kRing;
-  const uint32_t n_carried = resv ? min(ctl->n_carried, resv) : 0u;  // (Carry: slots [n_carried, resv) of this queue hold nothing)
-  uint32_t n = ctl->n_rays;
-  if (n <= resv && n_carried == 0u) n = 0u;
+  const QueueExtent qe = queue_extent(ctl, resv);
+  const uint32_t n = qe.n, n_carried = qe.n_carried;
   const uint32_t cont_min = MULTI ? 0u : rc.shade_cont;  // (wave-uniform) continuation passes: see the main loop
   const uint32_t region_full = max((uint32_t)kSChunk, ((n / gridDim.x / kRegionDiv) + 511u) & ~511u);
   const uint32_t region = cont_min ? max((uint32_t)kSChunk, ((n / gridDim.x / kRegionDivCont) + 511u) & ~511u) : region_full;  // (the block's first claim)
   const uint32_t wregion = region / kWaves, wregion_full = region_full / kWaves;
   bool pred = true;  // (wave-uniform) the wave's last flush pass had cont_min lanes that need no tree walk: its next one is expected to continue too
-  uint32_t w_cur = 0, w_rend = 0;  // this wave's current output region of the next queue (wave-uniform)
+  OutRegion out = {0u, 0u};
   uint32_t head = 0, cnt = 0;      // the ring: `cnt` survivors wait from entry `head` on (wave-uniform)
   uint32_t my_valid = 0, my_missed = 0;
   Counters cn = {0, 0, 0, 0, 0};
@@ -904,63 +935,13 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
     const uint32_t kept = (uint32_t)__popcll(km);
     my_missed += take - kept - (uint32_t)__popcll(__ballot(go));  // (a continued ray's hitScene invocation is tallied where it is shaded, as my_valid)
     if (kept) {
-      const uint32_t rank = lanes_below(km);
-      const uint32_t b0 = w_cur, n0 = min(kept, w_rend - w_cur);
-      uint32_t b1 = 0xffffffffu;
-      w_cur += n0;
-      if (kept > n0) {  // claim the wave's next region for the rest
-        uint32_t nb = 0, wregion_next = wregion;
-        bool full;
-        if (w_rend == 0u) {  // the wave's first region: its quarter of the block's claim
-          if (lane == 0) nb = atomicCAS(&s_region0, kR0Empty, kR0Busy);
-          nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
-          if (nb == kR0Empty) {
-            if (lane == 0) {
-              nb = atomicAdd(&ctl[1].n_rays, region);
-              if (nb + region > P.cap) {  // cannot happen with the host's sizing
-                atomicAdd(&totals[15], 1ull);
-                atomicSub(&ctl[1].n_rays, region);
-                nb = kR0Full;
-              }
-              atomicExch(&s_region0, nb);
-            }
-            nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
-          } else {
-            while (nb == kR0Busy) {
-              __builtin_amdgcn_s_sleep(8);
-              if (lane == 0) nb = atomicAdd(&s_region0, 0u);
-              nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
-            }
-          }
-          full = nb == kR0Full;
-          nb += wv * wregion;
-        } else {  // (a wave that stores most of its rays claims as much as without continuation: as many atomics, as few holes)
-          const uint32_t wr = pred ? wregion : wregion_full;
-          if (lane == 0) nb = atomicAdd(&ctl[1].n_rays, wr);
-          nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
-          full = nb + wr > P.cap;
-          if (full && lane == 0) {
-            atomicAdd(&totals[15], 1ull);
-            atomicSub(&ctl[1].n_rays, wr);
-          }
-          wregion_next = wr;
-        }
-        if (!full) {  // (full: what still fitted is written, the rest is dropped and flagged — see shade_body)
-          b1 = nb;
-          w_cur = nb + (kept - n0);
-          w_rend = nb + wregion_next;
-        }
-      }
-      if (keep && (rank < n0 || b1 != 0xffffffffu)) {
+      // (a wave that stores most of its rays claims as much as without continuation: as many atomics, as few holes)
+      const uint32_t dst = out.place(keep, region, wregion, pred ? wregion : wregion_full, ctl, P.cap, totals);
+      if (dst != kNoSlot) {
         LT(LT_KEEP);
-        const uint32_t dst = (rank < n0) ? (b0 + rank) : (b1 + (rank - n0));
         float4 a0 = r0[q];
         a0.w = __uint_as_float(rng);
-        P.out.q0[dst] = a0;
-        P.out.q1[dst] = r1[q];
-        P.out.q2[dst] = r2[q];
-        P.hout.tp[dst] = tp;
-        P.hout.mat[dst] = hm;
+        store_slot(P.out, P.hout, dst, a0, r1[q], r2[q], tp, hm);
       }
     }
     if (cont) {  // (read before the pass that shades them stages its survivors over these entries; written on every lane, so that nothing of the
@@ -982,9 +963,7 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
   // ray_color's loop body for the slots of the lanes with `active`, their state in `st` (load_slot); survivors go into the ring
   auto shade_group = [&](bool active, const SlotState& st) {
     bool survive = false, valid = false;
-    NewState ns;  // (zeroed although only the survivors' values are read: left undefined, the allocator needs 8 registers more — scratch at 80 VGPRs)
-    ns.o = ns.d = ns.T = mk3(0, 0, 0);
-    ns.bounce = 0, ns.rng = 0, ns.pid = 0;
+    NewState ns = zero_state();
     TT(TT_OTHER, 0.0f);  // (what came before this group: loop bookkeeping, the previous flush's tail)
     if (active) {
       LT(LT_GROUP);
@@ -1002,9 +981,9 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
     if (survive) {
       LT(LT_STAGE);
       const uint32_t q = (head + cnt + lanes_below(mk)) & (kRing - 1u);
-      r0[q] = make_float4(ns.o.x, ns.o.y, ns.o.z, __uint_as_float(ns.rng));
-      r1[q] = make_float4(ns.d.x, ns.d.y, ns.d.z, __uint_as_float(ns.pid));
-      r2[q] = make_float4(ns.T.x, ns.T.y, ns.T.z, __int_as_float(ns.bounce));
+      r0[q] = pack_q0(ns);
+      r1[q] = pack_q1(ns);
+      r2[q] = pack_q2(ns);
     }
     cnt += (uint32_t)__popcll(mk);
     TT(TT_STAGE, 0.0f);
@@ -1066,15 +1045,7 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
     if (t) atomicAdd(&g_time_tally[threadIdx.x], t);
   }
 #endif
-  if (w_rend == 0u && s_region0 < kR0Full) {  // never needed a region: all of this wave's quarter of the block's claim becomes holes
-    w_cur = s_region0 + wv * wregion;
-    w_rend = w_cur + wregion;
-  }
-  for (uint32_t i = w_cur + (uint32_t)lane; i < w_rend; i += 64u) {
-    LT(LT_HOLE);
-    reinterpret_cast<uint32_t*>(P.out.q1 + i)[3] = PID_HOLE;
-    P.hout.mat[i] = HITMAT_HOLE;
-  }
+  out.close(P, wregion, true);
 #ifdef PTMI_LANE_TALLY
   __syncthreads();
   if (threadIdx.x >= 2 * LT_HOLE && threadIdx.x < 2 * LT_HOLE + 2 && s_lane_tally[threadIdx.x]) atomicAdd(&g_lane_tally[threadIdx.x], (unsigned long long)s_lane_tally[threadIdx.x]);
@@ -1117,9 +1088,9 @@ constexpr int kTailTravBatch = 24;  // (12 / 32 / 40 lanes measured: profiles/r0
 template <bool IS, bool COUNT, bool MULTI, bool NOABORT>
 DEV void tail_body(const DevScene& S, const RenderConst& rc, const Paths& P, StepCtl* __restrict__ ctl, unsigned long long* __restrict__ totals, int first, uint32_t limit,
                    int stack_size, int lds_entries, int spill_entries, int2* __restrict__ spill, const Carry& cy) {
-  const uint32_t n_carried = cy.resv ? min(ctl->n_carried, cy.resv) : 0u;  // (Carry: slots [n_carried, resv) hold nothing, [0, n_carried) rays whose traversal goes on)
-  const uint32_t n = ctl->n_rays;
-  if (n <= cy.resv && n_carried == 0u) return;            // empty
+  const QueueExtent qe = queue_extent(ctl, cy.resv);  // (Carry: the rays in [0, n_carried) go on with their traversal)
+  const uint32_t n = qe.n, n_carried = qe.n_carried;
+  if (n == 0u) return;                                               // empty
   if ((n > cy.resv ? n - cy.resv : 0u) + n_carried > limit) return;  // too long for this kernel: the per-bounce kernels take the step
   extern __shared__ int lds_stack[];
   const int lane = lane_id();
@@ -1140,14 +1111,11 @@ DEV void tail_body(const DevScene& S, const RenderConst& rc, const Paths& P, Ste
   st.hitmat = HITMAT_HOLE, st.slot = 0;
   bool alive = false;
   bool resume = false;  // the lane's path was taken from the carry prefix: its hitScene part 2 goes on from the pool's record (first iteration only)
-  int park_sp = -1;     // >= 0: the lane's walk was interrupted (Carry::park_below); its state waits in three entries on top of its own stack, from this one on
+  int park_sp = -1;     // >= 0: the lane's walk was interrupted (Carry::park_below); its state waits on top of its own stack, from this entry on (park)
   float2 uv = make_float2(0.0f, 0.0f);  // barycentrics of the lane's triangle hit (the queue comes from k_generate / k_shade: none in it yet)
   uint32_t gnext = blockIdx.x, gbase = 0, pos = 64;  // next group to open; the open group's first slot and how many of its slots are taken
-#ifdef PTMI_LANE_TALLY
-  unsigned long long bt_cyc[kBvhTallies] = {0}, bt_last;
-  uint32_t bt_marks[kBvhTallies] = {0}, bt_lanes[kBvhTallies] = {0};
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(bt_last)::"memory");
-#endif
+  Stopwatch sw;
+  sw.begin();
 #pragma unroll 1
   for (;;) {
     BT(TB_VOTE, 0.0f, 0);
@@ -1188,84 +1156,44 @@ DEV void tail_body(const DevScene& S, const RenderConst& rc, const Paths& P, Ste
       const uint64_t fmask = __ballot(flagged);
       const bool more_to_take = !(pos == 64u && gnext * 64u >= n);  // (once the queue is used up there is nothing to gain by waiting: every pass the walk is put off lengthens the wave's end)
       if (fmask != 0ull && ((int)__popcll(fmask) >= (more_to_take ? kTailTravBatch : 1) || __ballot(alive && !flagged) == 0ull)) {
-        uint32_t node = flagged ? root_node : N_DONE;
-        int sp = 0;
-        const f3 o = mk3(st.q0), d = mk3(st.q1);
-        const f3 inv = rcp3_exact_il(d);
-        const uint32_t negmask = (d.x < 0 ? 1u : 0u) | (d.y < 0 ? 2u : 0u) | (d.z < 0 ? 4u : 0u);
-        float ct = st.tp.x;
-        ObjRay orr;
-        orr.mesh = -1;
-        orr.o = orr.d = o;
-        if (S.uniform_gid >= 0) obj_ray_uniform(S, o, d, orr);
-        TriHit hit = {0.0f, 0.0f, 0u, 0u};
-        if (flagged && resume) {  // carried over by the last k_bvh launch: state word, stack and the closest hit so far come from the pool
-          const uint32_t* rec = cy.pool_in + (size_t)st.slot * (size_t)cy.rec_words;
-          node = rec[0];
-          sp = (int)rec[1];
-          ct = __uint_as_float(rec[2]);
-          hit.u = __uint_as_float(rec[3]), hit.v = __uint_as_float(rec[4]), hit.prim = rec[5], hit.mat = rec[6];
-          for (int e = 0; e < sp; e++) stack2_write(stk, e, rec[8 + 2 * e], __uint_as_float(rec[9 + 2 * e]));
-        }
+        Walk w = {flagged ? root_node : N_DONE, 0, st.tp.x, {0.0f, 0.0f, 0u, 0u}};
+        WalkRay ray = make_walk_ray(S, mk3(st.q0), mk3(st.q1));
+        if (flagged && resume) carry_restore(cy, st.slot, stk, w);  // carried over by the last k_bvh launch: state word, stack and the closest hit so far come from the pool
         resume = false;
         if (flagged && park_sp >= 0) {  // interrupted in an earlier walk: on from where it stopped
-          uint32_t w0;
-          float w1;
-          sp = park_sp;
-          stack2_read(stk, sp, w0, w1);
-          node = w0, ct = w1;
-          stack2_read(stk, sp + 1, w0, w1);
-          hit.u = __uint_as_float(w0), hit.v = w1;
-          stack2_read(stk, sp + 2, w0, w1);
-          hit.prim = w0, hit.mat = __float_as_uint(w1);
+          unpark(stk, park_sp, w);
           park_sp = -1;
         }
 #pragma unroll 1
         for (;;) {
-          const uint64_t wm = __ballot(node != N_DONE);
+          const uint64_t wm = __ballot(w.node != N_DONE);
           if (wm == 0ull) break;
           // A walk lasts as long as its longest ray, and on a deep tree most of it runs a handful of lanes wide (871 k triangles: 7 of 64 on average, two thirds of a lone
           // frame's wave-cycles).  Once fewer than park_below lanes are left in it and another lane has something to do — a path to shade, or the queue a path to
           // take — the stragglers are parked and join the next walk.
-          if (cy.park_below > 0 && (int)__popcll(wm) < cy.park_below && (more_to_take || __ballot(alive && !(flagged && node != N_DONE)) != 0ull)) break;
-          if ((int)node < 0) {
-            const int2 lc = (node & REF_MULTI) ? S.leaf_table[node & REF_IDX] : make_int2((int)(node & REF_IDX), 1);
-            for (int j = 0; j < lc.y; j++) {
-              const float4* rec = S.pretri + 4 * (size_t)(lc.x + j);
-              const float4 g0 = rec[0], g1 = rec[1], g2 = rec[2], g3 = rec[3];
-              tri_test2<COUNT>(S, lc.x + j, g0, g1, g2, g3, o, d, orr, ct, hit, cb);
-            }
-            node = pop_until_pass2(stk, sp, ct, cb, COUNT);
-            BT(TB_WALK_LEAF, ct, __popcll(__ballot(1)));
+          if (cy.park_below > 0 && (int)__popcll(wm) < cy.park_below && (more_to_take || __ballot(alive && !(flagged && w.node != N_DONE)) != 0ull)) break;
+          if ((int)w.node < 0) {
+            walk_leaf<COUNT>(S, ray, stk, w, cb, sw);
+            BT(TB_WALK_LEAF, w.ct, __popcll(__ballot(1)));
           }
-          if (node < N_INNER_LIMIT) {
-            const float4* rec = S.pairs + 4 * (size_t)node;
-            const float4 f0 = rec[0], f1 = rec[1], f2 = rec[2], f3v = rec[3];
-            BT(TB_WALK_FETCH, f0.x + f1.x + f2.x + f3v.x, __popcll(__ballot(1)));
-            node = inner_step2<COUNT, NOABORT>(f0, f1, f2, f3v, o, inv, S.tmin, negmask, ct, stack_size, stk, sp, cb);
-            if (node == N_POP) node = pop_until_pass2(stk, sp, ct, cb, COUNT);
-          }
-          BT(TB_WALK_STEP, __uint_as_float(node), __popcll(__ballot(node != N_DONE)));
+          if (w.node < N_INNER_LIMIT) walk_inner<COUNT, NOABORT, TB_WALK_FETCH>(S, ray, stk, w, stack_size, cb, sw);
+          BT(TB_WALK_STEP, __uint_as_float(w.node), __popcll(__ballot(w.node != N_DONE)));
         }
-        if (flagged && node != N_DONE) {  // parked: node / closest hit so far on top of the lane's own stack (its entries below stay where they are); HITMAT_BVH stays set
-          stack2_write(stk, sp, node, ct);
-          stack2_write(stk, sp + 1, __float_as_uint(hit.u), hit.v);
-          stack2_write(stk, sp + 2, hit.prim, __uint_as_float(hit.mat));
-          park_sp = sp;
+        if (flagged && w.node != N_DONE) {  // parked (HITMAT_BVH stays set)
+          park(stk, w);
+          park_sp = w.sp;
         } else {
-          if (hit.prim != 0u) {  // a triangle beat what part 1 had found
-            st.tp = make_float2(ct, __uint_as_float(hit.prim));
-            uv = make_float2(hit.u, hit.v);
-            st.hitmat = hit.mat;
+          if (w.hit.prim != 0u) {  // a triangle beat what part 1 had found
+            st.tp = make_float2(w.ct, __uint_as_float(w.hit.prim));
+            uv = make_float2(w.hit.u, w.hit.v);
+            st.hitmat = w.hit.mat;
           }
           st.hitmat &= ~HITMAT_BVH;  // (the walk is done: the lane shades now)
         }
       }
       // ---- ray_color's loop body (traceRay.wgsl:10-80), for the lanes that do not wait for the tree ----
       const bool go = alive && (st.hitmat & HITMAT_BVH) == 0u;
-      NewState ns;  // (zeroed although only the survivors' values are read: left undefined, the allocator needs 8 registers more — scratch at 80 VGPRs)
-      ns.o = ns.d = ns.T = mk3(0, 0, 0);
-      ns.bounce = 0, ns.rng = 0, ns.pid = 0;
+      NewState ns = zero_state();
       bool survive = false;
       if (go) {
         tally++;
@@ -1276,17 +1204,17 @@ DEV void tail_body(const DevScene& S, const RenderConst& rc, const Paths& P, Ste
       BT(TB_SHADE, ns.o.x + ns.T.x, __popcll(__ballot(go)));
       // ---- hitScene part 1 for the new ray (hitRay.wgsl:6-54) ----
       if (go && alive) {
-        uint32_t rng = ns.rng, hm;
+        uint32_t hm;
         float2 tp;
-        prims_for_ray<COUNT>(S, ns.o, ns.d, rng, tp, hm, cn);
+        prims_for_ray<COUNT>(S, ns.o, ns.d, ns.rng, tp, hm, cn);  // (hit_volume draws from the path's stream: rng goes back into the state)
         if (kMissShortcut && !MULTI && hm == HITMAT_MISS) {  // traceRay.wgsl:12-16, as in k_shade's flush phase
           end_sample_progressive(P, ns.pid, mk3(rc.bg[0], rc.bg[1], rc.bg[2]) * ns.T, (ns.bounce & kAccWritten) != 0);
           tally++;
           alive = false;
         } else {
-          st.q0 = make_float4(ns.o.x, ns.o.y, ns.o.z, __uint_as_float(rng));
-          st.q1 = make_float4(ns.d.x, ns.d.y, ns.d.z, __uint_as_float(ns.pid));
-          st.q2 = make_float4(ns.T.x, ns.T.y, ns.T.z, __int_as_float(ns.bounce));
+          st.q0 = pack_q0(ns);
+          st.q1 = pack_q1(ns);
+          st.q2 = pack_q2(ns);
           st.tp = tp;
           st.hitmat = hm;
         }
@@ -1294,15 +1222,7 @@ DEV void tail_body(const DevScene& S, const RenderConst& rc, const Paths& P, Ste
       BT(TB_PRIMS, st.tp.x, __popcll(__ballot(go && survive)));
     }
   }
-#ifdef PTMI_LANE_TALLY
-  if (lane == 0)
-    for (int k = 0; k < kBvhTallies; k++) {
-      if (bt_marks[k] == 0u) continue;
-      atomicAdd(&g_tail_tally[3 * k], bt_cyc[k]);
-      atomicAdd(&g_tail_tally[3 * k + 1], (unsigned long long)bt_marks[k]);
-      atomicAdd(&g_tail_tally[3 * k + 2], (unsigned long long)bt_lanes[k]);
-    }
-#endif
+  BT_FLUSH(g_tail_tally);
   for (int off2 = 32; off2 > 0; off2 >>= 1) tally += __shfl_down(tally, off2, 64);
   if (lane == 0 && tally) atomicAdd(tally_line(totals, blockIdx.x), tally);
   if (COUNT) {
