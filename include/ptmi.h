@@ -180,6 +180,28 @@ int ptmi_render_frame(ptmi_ctx* ctx, const float* uniforms20);
  * Result is bit-identical to the frame-by-frame calls. */
 int ptmi_render(ptmi_ctx* ctx, const float* view16, uint32_t first_frame, uint32_t n_frames);
 
+/* A camera path in one pass: replaces n_views x frames_per_view animation frames of a MOVING camera (renderer.js:173-188 with resetBuffer = 1 on
+ * every move, renderer.js:173-181), which would otherwise be one ptmi_render / ptmi_render_frame call — one lone wavefront pass — per view.  View v is
+ * rendered from views16 + 16*v (column-major, as ptmi_render's) for frameNum = first_frame .. first_frame + frames_per_view - 1, every view with the same
+ * frame numbers, and its frames are folded in frame order into image v of the context's VIEW STACK: n_views images of W x H RGBA f32 sums in one device
+ * allocation, zeroed when this call allocates it (first call, another n_views; ptmi_resize drops it).  reset != 0: a view's first frame overwrites its image
+ * (resetBuffer = 1); reset == 0: the frames are added to what the stack holds.  Image v is bit for bit what ptmi_clear_framebuffer + ptmi_render(view v,
+ * first_frame, frames_per_view) + ptmi_read_framebuffer give.  The frame slots of different views share wavefront passes (ptmi_params.frames_in_flight
+ * counts slots).  A call that cannot allocate its stack returns PTMI_ERR_NO_MEMORY before anything is enqueued and leaves the stack it found as it
+ * was.  Asynchronous like ptmi_render; the accumulation buffer of ptmi_resize is neither read nor written.  n_views * frames_per_view < 2^31. */
+int ptmi_render_views(ptmi_ctx* ctx, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t frames_per_view, int reset);
+/* ptmi_read_framebuffer for image `view` of the stack (no counterpart in renderer.js, which never reads back): synchronises; bytes must be W*H*16.  On a
+ * multi-device context every device keeps the stack of its own tiles and this runs the context's collective (ptmi_create_multi) on that one image. */
+int ptmi_read_view(ptmi_ctx* ctx, uint32_t view, float* rgba_sum, size_t bytes);
+/* ptmi_resolve_rgba8 — the display pass of shaders/fragment.js:22-36 — for image `view` of the stack. */
+int ptmi_resolve_view_rgba8(ptmi_ctx* ctx, uint32_t view, float frame_num, uint8_t* dst, size_t bytes);
+/* The stack as one contiguous [n_views][H][W][4] f32 device array (ptmi_framebuffer_device_ptr's counterpart), for a consumer that wraps it without a
+ * host copy; valid until the next ptmi_render_views with another n_views, ptmi_resize or ptmi_release_views.  bytes / n_views may be NULL.
+ * Single-device contexts only: a multi-device context returns PTMI_ERR_UNSUPPORTED. */
+int ptmi_views_device_ptr(ptmi_ctx* ctx, void** dev_ptr, size_t* bytes, uint32_t* n_views);
+/* Frees the stack (ptmi_destroy does too); synchronises. */
+int ptmi_release_views(ptmi_ctx* ctx);
+
 int ptmi_synchronize(ptmi_ctx* ctx);
 
 /* Validates the uploaded buffers and builds the device-side digests now instead of inside the first render call

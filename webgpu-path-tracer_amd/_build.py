@@ -48,9 +48,9 @@ def _deps():
     return [os.path.join(CSRC, f) for f in SOURCES + ("ptmi_dbuf.h", "ptmi_device.h", "ptmi_kernels.h", "ptmi_tuning.h")] + [os.path.join(ROOT, "include", "ptmi.h"), os.path.join(ROOT, "include", "ptmi_math.h")]
 
 
-def _link(out, units):
+def _link(out, units, csrc=None):
     """units: [(source file name, extra flags, tag)].  One hipcc -c per translation unit, all at once (the three compile independently: ptmi.hip
-    is ~45 s of the 55 a single command takes), then one link.  Objects: webgpu-path-tracer_amd/build/ (not shipped)."""
+    is ~45 s of the 55 a single command takes), then one link.  Objects: webgpu-path-tracer_amd/build/ (not shipped).  `csrc`: another source directory."""
     from concurrent.futures import ThreadPoolExecutor
 
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -60,7 +60,7 @@ def _link(out, units):
     flags = [f for f in HIP_FLAGS if f != "-shared"]
     objs = [os.path.join(odir, "%s%s.o" % (os.path.splitext(src)[0], tag)) for src, _, tag in units]
     with ThreadPoolExecutor(max_workers=len(units)) as ex:
-        list(ex.map(lambda u: _run([hipcc] + flags + list(u[0][1]) + ["-c", os.path.join(CSRC, u[0][0]), "-o", u[1]]), zip(units, objs)))
+        list(ex.map(lambda u: _run([hipcc] + flags + list(u[0][1]) + ["-c", os.path.join(csrc or CSRC, u[0][0]), "-o", u[1]]), zip(units, objs)))
     _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs)
     return out
 
@@ -80,9 +80,10 @@ def build_testhooks(force=False):
     return _link(TESTHOOKS_LIB, [(src, ("-DPTMI_TEST_HOOKS",), "_testhooks") for src in SOURCES])
 
 
-def build_variant(name, extra_flags):
-    """A/B builds of the library with extra -D flags: webgpu-path-tracer_amd/variants/libptmi_<name>.so; run with PTMI_LIB=<path>."""
-    return _link(os.path.join(PKG, "variants", "libptmi_%s.so" % name), [(src, tuple(extra_flags), "_" + name) for src in SOURCES])
+def build_variant(name, extra_flags, csrc=None):
+    """A/B builds of the library with extra -D flags: webgpu-path-tracer_amd/variants/libptmi_<name>.so; run with PTMI_LIB=<path>.
+    `csrc`: build another tree's sources (a csrc/ directory that finds its ../../include/ptmi.h), e.g. an earlier commit's (tools/views_probe.py)."""
+    return _link(os.path.join(PKG, "variants", "libptmi_%s.so" % name), [(src, tuple(extra_flags), "_" + name) for src in SOURCES], csrc=csrc)
 
 
 def build_addon(force=False):

@@ -123,6 +123,13 @@ struct ptmi_ctx {
   DBuf d_fb_own;
   float4* fb = nullptr;
   size_t fb_bytes = 0;
+  // ptmi_render_views: the view stack — n_views images of W x H RGBA f32 sums, one allocation — and the last call's view table (ViewTab: kViewRow float4 per view),
+  // uploaded from a pinned staging copy so that the call stays asynchronous; `view_rows_sent` marks the point where the stream has read that copy
+  DBuf d_views, d_view_rows;
+  uint32_t n_views = 0;
+  float* h_view_rows = nullptr;
+  size_t h_view_rows_cap = 0;
+  hipEvent_t view_rows_sent = nullptr;
   int rank = 0, world = 1, tile = 64;
 
   size_t path_cap = 0;
@@ -631,6 +638,18 @@ constexpr auto tail_kernel() {
   if constexpr (SIX) return &k_tail6<COUNT, NOABORT>;
   else return &k_tail<IS, COUNT, MULTI, NOABORT>;
 }
+// The same choices for a multi-view batch (ptmi_render_views): the k_*_views kernels take the batch's ViewTab as one more argument, so they are picked by
+// dispatch calls of their own and the kernels of a batch with one view keep their signatures — and their code, instruction for instruction.
+template <bool IS, bool SORT, bool COUNT, bool MULTI>
+constexpr auto shade_views_kernel() {
+  if constexpr (!IS && !MULTI) return &k_shade6_views<SORT, COUNT>;
+  else return &k_shade_views<IS, SORT, COUNT, MULTI>;
+}
+template <bool SIX, bool IS, bool COUNT, bool MULTI, bool NOABORT>
+constexpr auto tail_views_kernel() {
+  if constexpr (SIX) return &k_tail6_views<COUNT, NOABORT>;
+  else return &k_tail_views<IS, COUNT, MULTI, NOABORT>;
+}
 
 int stack_alloc_for(const ptmi_ctx* c) { return std::max(1, std::min(c->prm.stack_size, std::max(c->bvh_depth, 1))); }
 
@@ -674,7 +693,9 @@ void load_tuning(ptmi_ctx* c) { c->tun = load_tuning_env(); }  // (every value i
 
 // hitScene, part 2 for the step's queue (k_bvh).  Part 1 has already been run by whoever created the rays (k_generate,
 // k_shade); ptmi_trace's rays come from the host, so it asks for k_prims first.
-int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_items, bool with_prims, const RenderConst* first_rc = nullptr, const Carry& cy = Carry{}) {
+// `vt`: the batch is a multi-view one (only step 0's launch, `first_rc`, reads the table)
+int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_items, bool with_prims, const RenderConst* first_rc = nullptr, const Carry& cy = Carry{},
+                     const ViewTab* vt = nullptr) {
   unsigned long long* tot = c->d_totals.as<unsigned long long>();
   const uint32_t pgrid = std::max<uint32_t>(1, std::min<uint32_t>((max_items + kBlock - 1) / kBlock, (uint32_t)c->num_cus * 32));
   if (with_prims) {
@@ -702,15 +723,21 @@ int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_ite
   // step 0's queue does not store the rays' common origin (k_generate): the kernel is handed cam_origin
   float4 cam = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (first_rc) cam = make_float4(first_rc->cam_o[0], first_rc->cam_o[1], first_rc->cam_o[2], 1.0f);
-  const auto bvh = with_flags([](auto cn, auto na) { return &k_bvh2<cn, na>; }, c->counters, st.noabort);
-  hipLaunchKernelGGL(bvh, dim3(grid), dim3(64), lds, c->stream, c->S, P, ctl, c->d_heads.as<uint32_t>(), n_teams, c->prm.stack_size, st.lds_entries, st.spill_entries,
-                     c->d_spill.as<int2>(), tun.refill, tun.leaf_batch, tot, (uint32_t)tun.bvh_range, cam, cy);
+  if (vt && first_rc) {
+    const auto bvh = with_flags([](auto cn, auto na) { return &k_bvh2_views<cn, na>; }, c->counters, st.noabort);
+    hipLaunchKernelGGL(bvh, dim3(grid), dim3(64), lds, c->stream, c->S, P, ctl, c->d_heads.as<uint32_t>(), n_teams, c->prm.stack_size, st.lds_entries, st.spill_entries,
+                       c->d_spill.as<int2>(), tun.refill, tun.leaf_batch, tot, (uint32_t)tun.bvh_range, cam, cy, *vt);
+  } else {
+    const auto bvh = with_flags([](auto cn, auto na) { return &k_bvh2<cn, na>; }, c->counters, st.noabort);
+    hipLaunchKernelGGL(bvh, dim3(grid), dim3(64), lds, c->stream, c->S, P, ctl, c->d_heads.as<uint32_t>(), n_teams, c->prm.stack_size, st.lds_entries, st.spill_entries,
+                       c->d_spill.as<int2>(), tun.refill, tun.leaf_batch, tot, (uint32_t)tun.bvh_range, cam, cy);
+  }
   HIP_TRY(c, hipGetLastError());
   return PTMI_OK;
 }
 
 // k_tail in front of a step: traces the step's queue to the end if it is short (at most `limit` slots), else returns at once.  `six`: k_tail6 (tail_plan).
-int launch_tail(ptmi_ctx* c, const RenderConst& rc, const Paths& P, StepCtl* ctl, int first, uint32_t limit, bool six, const Carry& cy_in) {
+int launch_tail(ptmi_ctx* c, const RenderConst& rc, const Paths& P, StepCtl* ctl, int first, uint32_t limit, bool six, const Carry& cy_in, const ViewTab* vt) {
   // On trees of 12 levels and more a walk stops once fewer than tun.tail_park lanes are left in it while other lanes have work; the stragglers' state waits in kParkEntries
   // entries on top of their stacks (park, ptmi_device.h).  Shallow trees never park: their walks are short, and a parked ray's path waits for the next walk (round 4 measured both).
   Carry cy = cy_in;
@@ -720,10 +747,17 @@ int launch_tail(ptmi_ctx* c, const RenderConst& rc, const Paths& P, StepCtl* ctl
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)limit + 63) / 64, (uint64_t)c->num_cus * (uint64_t)waves_per_cu));
   HIP_TRY(c, c->d_spill.ensure(std::max<size_t>(16, (size_t)c->num_cus * 32 * (size_t)st.spill_entries * 64 * sizeof(int2))));  // (k_bvh's grids are no larger: one size for both)
   ScopedSpan sp(c, T_TAIL);
-  const auto tail = with_flags([](auto s6, auto is, auto cn, auto mu, auto na) { return tail_kernel<s6, is, cn, mu, na>(); }, six, c->prm.importance_sampling != 0,
-                               c->counters, rc.num_samples > 1, st.noabort);
-  hipLaunchKernelGGL(tail, dim3(grid), dim3(64), st.lds_bytes, c->stream, c->S, rc, P, ctl, c->d_totals.as<unsigned long long>(), first, limit, c->prm.stack_size,
-                     st.lds_entries, st.spill_entries, c->d_spill.as<int2>(), cy);
+  if (vt) {
+    const auto tail = with_flags([](auto s6, auto is, auto cn, auto mu, auto na) { return tail_views_kernel<s6, is, cn, mu, na>(); }, six, c->prm.importance_sampling != 0,
+                                 c->counters, rc.num_samples > 1, st.noabort);
+    hipLaunchKernelGGL(tail, dim3(grid), dim3(64), st.lds_bytes, c->stream, c->S, rc, P, ctl, c->d_totals.as<unsigned long long>(), first, limit, c->prm.stack_size,
+                       st.lds_entries, st.spill_entries, c->d_spill.as<int2>(), cy, *vt);
+  } else {
+    const auto tail = with_flags([](auto s6, auto is, auto cn, auto mu, auto na) { return tail_kernel<s6, is, cn, mu, na>(); }, six, c->prm.importance_sampling != 0,
+                                 c->counters, rc.num_samples > 1, st.noabort);
+    hipLaunchKernelGGL(tail, dim3(grid), dim3(64), st.lds_bytes, c->stream, c->S, rc, P, ctl, c->d_totals.as<unsigned long long>(), first, limit, c->prm.stack_size,
+                       st.lds_entries, st.spill_entries, c->d_spill.as<int2>(), cy);
+  }
   HIP_TRY(c, hipGetLastError());
   c->stats.tail_launches++;
   return PTMI_OK;
@@ -858,12 +892,22 @@ RenderConst make_render_const(const ptmi_ctx* c, const float* view16, uint32_t f
   return rc;
 }
 
+// A multi-view batch (ptmi_render_views): its n_frames frame slots are slots [vt.slot0, vt.slot0 + n_frames) of the call's views x frames-per-view, every view with the
+// frame numbers frame0 .. frame0 + fpv - 1, and they are folded into the images of `stack` instead of the framebuffer.  `view16` is not used by such a batch's kernels.
+struct ViewBatch {
+  ViewTab vt;
+  float4* stack;
+};
+
 // `fold` = how many of the batch's leading frames are added to the framebuffer now (-1 = all of them); dry_steps > 0: placement_search's timing run
-int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames, int reset_first, int fold = -1, int dry_steps = 0) {
+int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames, int reset_first, int fold = -1, int dry_steps = 0, const ViewBatch* views = nullptr) {
   const ptmi_params& p = c->prm;
   c->ahead.valid = false;  // the path buffers are about to be overwritten
   const RenderConst rc = make_render_const(c, view16, frame0, n_frames, reset_first);
   if (rc.n_local == 0) return PTMI_OK;
+  ViewTab vtab{};
+  if (views) vtab = views->vt, vtab.n_local = rc.n_local;
+  const ViewTab* vt = views ? &vtab : nullptr;
 
   const int n_steps = rc.num_samples * p.max_bounces;
   const size_t npaths = (size_t)rc.n_local * (size_t)n_frames;
@@ -898,14 +942,17 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
 
   const auto shade = with_flags([](auto is, auto so, auto cn, auto mu) { return shade_kernel<is, so, cn, mu>(); }, p.importance_sampling != 0, sort, c->counters,
                                 rc.num_samples > 1);
+  const auto shade_views = with_flags([](auto is, auto so, auto cn, auto mu) { return shade_views_kernel<is, so, cn, mu>(); }, p.importance_sampling != 0, sort, c->counters,
+                                      rc.num_samples > 1);
   // k_shade's grid: as many blocks per CU as the instance's registers and LDS admit (the progressive-mode ones need 79 VGPRs since
   // the build dropped the SLP vectoriser: 6 blocks = 6 waves per SIMD; the importance-sampling ones 93: 5) — asked of the runtime once per instance
   int shade_bpc = c->tun.shade_blocks_per_cu;
   if (shade_bpc <= 0) {
-    int& cached = c->shade_blocks_per_cu[reinterpret_cast<const void*>(shade)];
+    int& cached = c->shade_blocks_per_cu[views ? reinterpret_cast<const void*>(shade_views) : reinterpret_cast<const void*>(shade)];
     if (cached == 0) {
       int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, shade, kBlock, 0) != hipSuccess || nb < 1) nb = 5;
+      const hipError_t oe = views ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, shade_views, kBlock, 0) : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, shade, kBlock, 0);
+      if (oe != hipSuccess || nb < 1) nb = 5;
       cached = nb;
     }
     shade_bpc = cached;
@@ -918,7 +965,7 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     c->placement_pending = false;
     if (total > tail.limit_first) {  // (a batch that k_tail takes whole reads its queue once: nothing to search for)
       // (two steps: the whole batch as the probe — eight steps — chose no better: profiles/r05_placement_dry_run.txt)
-      int r = placement_search(c, [&]() { return render_batch(c, view16, frame0, n_frames, reset_first, fold, 2); });
+      int r = placement_search(c, [&]() { return render_batch(c, view16, frame0, n_frames, reset_first, fold, 2, views); });
       if (r) return r;
     }
   }
@@ -929,8 +976,13 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   {
     ScopedSpan s(c, T_GENERATE);
     if (rc.num_samples == 1) HIP_TRY(c, hipMemsetAsync(c->d_touched.p, 0, npaths, c->stream));
-    const auto generate = with_flags([](auto cn) { return &k_generate<cn>; }, c->counters);
-    hipLaunchKernelGGL(generate, dim3(ew_grid), dim3(kBlock), 0, c->stream, c->S, rc, paths_of(c, 0, rc.num_samples > 1), ctl, c->d_heads.as<uint32_t>(), tot);
+    if (views) {
+      const auto generate = with_flags([](auto cn) { return &k_generate_views<cn>; }, c->counters);
+      hipLaunchKernelGGL(generate, dim3(ew_grid), dim3(kBlock), 0, c->stream, c->S, rc, paths_of(c, 0, rc.num_samples > 1), ctl, c->d_heads.as<uint32_t>(), tot, vtab);
+    } else {
+      const auto generate = with_flags([](auto cn) { return &k_generate<cn>; }, c->counters);
+      hipLaunchKernelGGL(generate, dim3(ew_grid), dim3(kBlock), 0, c->stream, c->S, rc, paths_of(c, 0, rc.num_samples > 1), ctl, c->d_heads.as<uint32_t>(), tot);
+    }
     HIP_TRY(c, hipGetLastError());
     c->stats.generate_launches++;
   }
@@ -954,7 +1006,7 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     // (dry runs: k_generate and k_shade only — the kernels whose time depends on where the queue arrays lie; k_bvh reads them sparsely, and on a deep tree it would
     // be nine tenths of the search's time.  Rays that entered the root box are then shaded with what part 1 of hitScene found: other paths, the same access pattern.)
     if (const uint32_t tail_limit = dry_steps > 0 ? 0u : (s == 0 ? tail.limit_first : tail.limit_later)) {
-      int lr = launch_tail(c, rc, P, ctl + s, s == 0 ? 1 : 0, tail_limit, tail.six, carry_of(s));
+      int lr = launch_tail(c, rc, P, ctl + s, s == 0 ? 1 : 0, tail_limit, tail.six, carry_of(s), vt);
       if (lr) return lr;
       // step 0's queue is the whole batch (k_generate fills one slot per path): if that fits the limit k_tail has just been handed all of it —
       // nothing is left for the per-bounce kernels, and a lone frame is three launches instead of 3 x MAX_BOUNCES + 2
@@ -966,12 +1018,13 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     if (dry_steps == 0) {
       Carry cy = carry_of(s);
       if (!carry || s >= n_steps - c->tun.bvh_carry_last) cy.resv_next = 0u;
-      int lr = launch_intersect(c, P, ctl + s, bound, false, s == 0 ? &rc : nullptr, cy);
+      int lr = launch_intersect(c, P, ctl + s, bound, false, s == 0 ? &rc : nullptr, cy, vt);
       if (lr) return lr;
     }
     {
       ScopedSpan sp(c, T_SHADE);
-      hipLaunchKernelGGL(shade, dim3(sgrid), dim3(kBlock), 0, c->stream, c->S, rc, P, ctl + s, c->d_heads.as<uint32_t>(), tot, s == 0 ? 1 : 0, s == 0 ? 0u : resv);
+      if (views) hipLaunchKernelGGL(shade_views, dim3(sgrid), dim3(kBlock), 0, c->stream, c->S, rc, P, ctl + s, c->d_heads.as<uint32_t>(), tot, s == 0 ? 1 : 0, s == 0 ? 0u : resv, vtab);
+      else hipLaunchKernelGGL(shade, dim3(sgrid), dim3(kBlock), 0, c->stream, c->S, rc, P, ctl + s, c->d_heads.as<uint32_t>(), tot, s == 0 ? 1 : 0, s == 0 ? 0u : resv);
       HIP_TRY(c, hipGetLastError());  // launch errors surface per step, before k_accumulate touches the framebuffer
     }
     c->stats.intersect_launches++;
@@ -981,13 +1034,14 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   if (carry && !drained && n_steps > 0) {
     // paths that were carried over lag behind the step count: whatever the last k_shade left in the queue (and what the last k_bvh carried) is
     // traced to its end by one k_tail launch — a few thousand paths at most
-    int lr = launch_tail(c, rc, paths_of(c, n_steps, rc.num_samples > 1), ctl + n_steps, 0, 0xffffffffu, tail.six, carry_of(n_steps));
+    int lr = launch_tail(c, rc, paths_of(c, n_steps, rc.num_samples > 1), ctl + n_steps, 0, 0xffffffffu, tail.six, carry_of(n_steps), vt);
     if (lr) return lr;
   }
   {
     ScopedSpan s(c, T_ACCUM);
-    hipLaunchKernelGGL(k_accumulate, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), c->fb, n_steps, tot, 0,
-                       fold < 0 ? n_frames : std::min(fold, n_frames));
+    const int f_end = fold < 0 ? n_frames : std::min(fold, n_frames);
+    if (views) hipLaunchKernelGGL(k_accumulate<true>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), views->stack, n_steps, tot, 0, f_end, vtab);
+    else hipLaunchKernelGGL(k_accumulate<false>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), c->fb, n_steps, tot, 0, f_end, vtab);
     c->stats.accumulate_launches++;
   }
   HIP_TRY(c, hipGetLastError());
@@ -1125,12 +1179,14 @@ __global__ __launch_bounds__(kBlock) void k_add_into(float4* __restrict__ dst, c
 // The one collective of a multi-device render: sum the per-device accumulation buffers into d_fb_gather on local device 0.
 // Every pixel is non-zero in exactly one of them (x + 0 = x), so the sum is the single-GPU image bit for bit whatever
 // the order.  The per-device buffers are left as they are, so rendering can go on afterwards.
-int gather_framebuffer(ptmi_ctx* c, float4** out) {
+// `view` >= 0: the same for image `view` of the devices' view stacks (ptmi_render_views) instead of their accumulation buffers.
+float4* image_of(const ptmi_ctx* q, int view) { return view < 0 ? q->fb : q->d_views.as<float4>() + (size_t)view * (size_t)q->W * (size_t)q->H; }
+int gather_framebuffer(ptmi_ctx* c, float4** out, int view = -1) {
   if (!c->multi) {
-    *out = c->fb;
+    *out = image_of(c, view);
     return PTMI_OK;
   }
-  const size_t bytes = c->fb_bytes, n4 = bytes / 16;
+  const size_t bytes = (size_t)c->W * (size_t)c->H * 16, n4 = bytes / 16;
   const std::vector<ptmi_ctx*> devs = local_devices(c);
   int r = on_all_devices(c, [](ptmi_ctx* q) -> int {
     HIP_TRY(q, hipSetDevice(q->device));
@@ -1158,7 +1214,7 @@ int gather_framebuffer(ptmi_ctx* c, float4** out) {
           first_error = std::string("hipSetDevice: ") + hipGetErrorString(he);
           break;
         }
-        const ncclResult_t nr = g_rccl.Reduce(q->fb, i ? (void*)q->fb : (void*)g, n4 * 4, ncclFloat, ncclSum, 0, c->comms[i], q->stream);
+        const ncclResult_t nr = g_rccl.Reduce(image_of(q, view), i ? (void*)image_of(q, view) : (void*)g, n4 * 4, ncclFloat, ncclSum, 0, c->comms[i], q->stream);
         if (nr != ncclSuccess) first_error = std::string("ncclReduce (local device #") + std::to_string(i) + "): " + g_rccl.GetErrorString(nr);
         else if (rccl_fail_hook(c) == 3) first_error = "simulated failure after the first ncclReduce was enqueued (PTMI_TEST_RCCL_FAIL=mid)";
       }
@@ -1203,10 +1259,10 @@ int gather_framebuffer(ptmi_ctx* c, float4** out) {
     for (ptmi_ctx* q : devs) {
       const uint32_t n_local = count_local(npix, q->rank, q->world, q->tile);
       if (n_local == 0) continue;
-      const float4* src = q->fb;
+      const float4* src = image_of(q, view);
       if (q->device != c->device && !q->root_reads) {
         HIP_TRY(c, c->d_fb_stage.ensure(bytes));
-        HIP_TRY(c, hipMemcpyPeerAsync(c->d_fb_stage.p, c->device, q->fb, q->device, bytes, c->stream));
+        HIP_TRY(c, hipMemcpyPeerAsync(c->d_fb_stage.p, c->device, src, q->device, bytes, c->stream));
         src = c->d_fb_stage.as<float4>();
         c->gather_bytes += bytes;
       } else if (q->device != c->device) {
@@ -1223,13 +1279,13 @@ int gather_framebuffer(ptmi_ctx* c, float4** out) {
     c->reduce_info = msg;
   } else if (!c->use_rccl) {
     // shards that share this GPU (tests on a one-GPU box), or PTMI_MULTI_REDUCE=copy: peer copy + add kernel
-    HIP_TRY(c, hipMemcpyAsync(g, c->fb, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(g, image_of(c, view), bytes, hipMemcpyDeviceToDevice, c->stream));
     const unsigned grid = (unsigned)std::min<size_t>((n4 + kBlock - 1) / kBlock, (size_t)c->num_cus * 8);
     for (ptmi_ctx* q : c->peers) {
-      const float4* src = q->fb;
+      const float4* src = image_of(q, view);
       if (q->device != c->device) {
         HIP_TRY(c, c->d_fb_stage.ensure(bytes));
-        HIP_TRY(c, hipMemcpyPeerAsync(c->d_fb_stage.p, c->device, q->fb, q->device, bytes, c->stream));
+        HIP_TRY(c, hipMemcpyPeerAsync(c->d_fb_stage.p, c->device, src, q->device, bytes, c->stream));
         src = c->d_fb_stage.as<float4>();
       }
       hipLaunchKernelGGL(k_add_into, dim3(grid), dim3(kBlock), 0, c->stream, g, src, n4);
@@ -1451,6 +1507,8 @@ void ptmi_destroy(ptmi_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   drain_spans(c);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
+  if (c->view_rows_sent) (void)hipEventDestroy(c->view_rows_sent);
+  if (c->h_view_rows) (void)hipHostFree(c->h_view_rows);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;  // its device buffers (DBuf) are freed here, with its device current and its stream drained
 }
@@ -1663,6 +1721,8 @@ int ptmi_resize(ptmi_ctx* c, int width, int height) {
   c->fb_bytes = bytes;
   c->W = width;
   c->H = height;
+  c->d_views.release();  // the view stack belongs to the old size
+  c->n_views = 0;
   HIP_TRY(c, hipMemsetAsync(c->fb, 0, bytes, c->stream));
   for (ptmi_ctx* q : c->peers) {
     int r = ptmi_resize(q, width, height);
@@ -1719,8 +1779,8 @@ static int render_frame_one(ptmi_ctx* c, const float* u) {
   c->last_frame = k;
   memcpy(c->last_view, view, 64);
   if (A.valid && follows && A.next < A.count && k == A.frame0 + (uint32_t)A.next && memcmp(view, A.view, 64) == 0) {
-    hipLaunchKernelGGL(k_accumulate, dim3(A.grid), dim3(kBlock), 0, c->stream, A.rc, paths_of(c, 0, A.rc.num_samples > 1), c->fb, 0,
-                       c->d_totals.as<unsigned long long>(), A.next, A.next + 1);
+    hipLaunchKernelGGL(k_accumulate<false>, dim3(A.grid), dim3(kBlock), 0, c->stream, A.rc, paths_of(c, 0, A.rc.num_samples > 1), c->fb, 0,
+                       c->d_totals.as<unsigned long long>(), A.next, A.next + 1, ViewTab{});
     HIP_TRY(c, hipGetLastError());
     A.next++;
     return PTMI_OK;
@@ -1790,6 +1850,145 @@ int ptmi_render(ptmi_ctx* c, const float* view16, uint32_t first_frame, uint32_t
   return on_all_devices(c, [=](ptmi_ctx* q) { return render_one(q, view16, first_frame, n_frames); }, true);
 }
 
+// One device's part of ptmi_render_views: render_one's loop over batches of at most F frame slots, the slots being the call's n_views x frames_per_view.
+static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t fpv, int reset) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();  // a stale error of an earlier, already reported failure must not be blamed on this call
+  int r = prepare_scene(c);
+  if (r) return r;
+  r = check_renderable(c);
+  if (r) return r;
+  // the stack and the table: allocated before anything is enqueued
+  const size_t image_bytes = (size_t)c->W * (size_t)c->H * 16, row_bytes = (size_t)n_views * kViewRow * 16;
+  const bool fresh = !c->d_views.p || c->n_views != n_views;
+  if (fresh) {  // the new stack first: a call that fails for want of memory leaves the old images as they were
+    DBuf stack;
+    HIP_TRY(c, stack.ensure(image_bytes * n_views));
+    c->d_views = std::move(stack);
+    c->n_views = 0;  // (until it is zeroed, below)
+  }
+  HIP_TRY(c, c->d_view_rows.ensure(row_bytes));
+  if (row_bytes > c->h_view_rows_cap) {
+    if (c->view_rows_sent) HIP_TRY(c, hipEventSynchronize(c->view_rows_sent));
+    if (c->h_view_rows) (void)hipHostFree(c->h_view_rows);
+    c->h_view_rows = nullptr, c->h_view_rows_cap = 0;
+    HIP_TRY(c, hipHostMalloc((void**)&c->h_view_rows, row_bytes, hipHostMallocDefault));
+    c->h_view_rows_cap = row_bytes;
+  }
+  if (!c->view_rows_sent) HIP_TRY(c, hipEventCreateWithFlags(&c->view_rows_sent, hipEventDisableTiming));
+  else HIP_TRY(c, hipEventSynchronize(c->view_rows_sent));  // the last call's upload has read the staging copy
+  for (uint32_t v = 0; v < n_views; v++) {
+    const float* m = views16 + 16 * (size_t)v;
+    float* row = c->h_view_rows + (size_t)v * kViewRow * 4;
+    memcpy(row, m, 64);
+    for (int k = 0; k < 3; k++) row[16 + k] = ((m[k] * 0.0f + m[4 + k] * 0.0f) + m[8 + k] * 0.0f) + m[12 + k] * 1.0f;  // cam_origin, as make_render_const computes it
+    row[19] = 0.0f;
+  }
+  if (fresh) {
+    HIP_TRY(c, hipMemsetAsync(c->d_views.p, 0, image_bytes * n_views, c->stream));
+    c->n_views = n_views;
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->d_view_rows.p, c->h_view_rows, row_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->view_rows_sent, c->stream));
+  // (the same budget of frame slots per wavefront pass as render_one's, and the same halving)
+  const size_t npix = std::max<size_t>(1, count_local((uint32_t)c->W * (uint32_t)c->H, c->rank, c->world, c->tile));
+  uint32_t F = c->prm.frames_in_flight > 0 ? (uint32_t)c->prm.frames_in_flight : (uint32_t)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)1 << c->tun.path_budget_log2) / npix));
+  F = (uint32_t)std::min<size_t>(F, std::max<size_t>(1, ((size_t)1 << 31) / npix));
+  const uint32_t n_slots = n_views * fpv;
+  for (uint32_t done = 0; done < n_slots;) {
+    const uint32_t nb = std::min(F, n_slots - done);
+    const ViewBatch vb{ViewTab{c->d_view_rows.as<float4>(), done, fpv, 0u}, c->d_views.as<float4>()};
+    r = render_batch(c, views16 + 16 * (size_t)(done / fpv), first_frame, (int)nb, reset ? 1 : 0, -1, 0, &vb);
+    if (r == PTMI_ERR_NO_MEMORY && !c->batch_enqueued && nb > 1 && c->prm.frames_in_flight <= 0) {
+      F = std::max<uint32_t>(1, nb / 2);
+      continue;
+    }
+    if (r) return r;
+    done += nb;
+  }
+  return PTMI_OK;
+}
+
+int ptmi_render_views(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t frames_per_view, int reset) {
+  if (!c || !views16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views: null argument");
+  if (n_views == 0 || frames_per_view == 0) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views: need n_views >= 1 and frames_per_view >= 1");
+  if ((uint64_t)n_views * frames_per_view > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views: n_views * frames_per_view must stay below 2^31");
+  return on_all_devices(c, [=](ptmi_ctx* q) { return render_views_one(q, views16, n_views, first_frame, frames_per_view, reset); }, true);
+}
+
+// what ptmi_read_view / ptmi_resolve_view_rgba8 / ptmi_views_device_ptr ask of the stack
+static int check_view(ptmi_ctx* c, const char* who, uint32_t view) {
+  if (!c->d_views.p || c->n_views == 0) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no view stack: call ptmi_render_views first");
+  if (view >= c->n_views) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": view " + std::to_string(view) + " of " + std::to_string(c->n_views));
+  return PTMI_OK;
+}
+
+// ptmi_read_framebuffer (view < 0) / ptmi_read_view: the image, gathered from the devices of a multi-device context, copied to the host
+static int read_image(ptmi_ctx* c, int view, float* dst, size_t bytes) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  float4* src = nullptr;
+  int r = gather_framebuffer(c, &src, view);  // multi-device: the one reduce of the render (RCCL over xGMI); else the image itself
+  if (r) return r;
+  HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  drain_spans(c);
+  return on_all_devices(c, [](ptmi_ctx* q) -> int {
+    HIP_TRY(q, hipSetDevice(q->device));
+    drain_spans(q);
+    return check_queue_overflow(q);
+  });
+}
+// ptmi_resolve_rgba8 (view < 0) / ptmi_resolve_view_rgba8: the display pass on the gathered image
+static int resolve_image(ptmi_ctx* c, int view, float frame_num, uint8_t* dst, size_t bytes) {
+  const size_t npix = (size_t)c->W * c->H;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, c->d_scratch.ensure(bytes));
+  float4* src = nullptr;
+  int gr = gather_framebuffer(c, &src, view);
+  if (gr) return gr;
+  hipLaunchKernelGGL(k_resolve_rgba8, dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, src, (uint32_t)npix, frame_num,
+                     c->d_scratch.as<uchar4>());
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(dst, c->d_scratch.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return PTMI_OK;
+}
+
+int ptmi_read_view(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_view: null argument");
+  if (int r = check_view(c, "ptmi_read_view", view)) return r;
+  if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_view: bytes != W*H*16");
+  return read_image(c, (int)view, dst, bytes);
+}
+
+int ptmi_resolve_view_rgba8(ptmi_ctx* c, uint32_t view, float frame_num, uint8_t* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_view_rgba8: null argument");
+  if (int r = check_view(c, "ptmi_resolve_view_rgba8", view)) return r;
+  if (bytes != (size_t)c->W * c->H * 4) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_view_rgba8: bytes != W*H*4");
+  return resolve_image(c, (int)view, frame_num, dst, bytes);
+}
+
+int ptmi_views_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
+  if (!c || !p) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_views_device_ptr: null argument");
+  if (!c->peers.empty()) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_views_device_ptr: a multi-device context has one stack per GPU; use ptmi_read_view");
+  if (int r = check_view(c, "ptmi_views_device_ptr", 0)) return r;
+  *p = c->d_views.p;
+  if (bytes) *bytes = (size_t)c->n_views * c->W * c->H * 16;
+  if (n_views) *n_views = c->n_views;
+  return PTMI_OK;
+}
+
+int ptmi_release_views(ptmi_ctx* c) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  return on_all_devices(c, [](ptmi_ctx* q) -> int {
+    HIP_TRY(q, hipSetDevice(q->device));
+    HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still fold into a stack that is about to go
+    q->d_views.release();
+    q->n_views = 0;
+    return PTMI_OK;
+  });
+}
+
 static int synchronize_one(ptmi_ctx* c) {
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1817,18 +2016,7 @@ int ptmi_read_framebuffer(ptmi_ctx* c, float* dst, size_t bytes) {
   if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_framebuffer: null argument");
   if (!c->fb) return fail(c, PTMI_ERR_STATE, "ptmi_read_framebuffer: no framebuffer");
   if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_framebuffer: bytes != W*H*16");
-  HIP_TRY(c, hipSetDevice(c->device));
-  float4* src = nullptr;
-  int r = gather_framebuffer(c, &src);  // multi-device: the one reduce of the render (RCCL over xGMI); else c->fb itself
-  if (r) return r;
-  HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  drain_spans(c);
-  return on_all_devices(c, [](ptmi_ctx* q) -> int {
-    HIP_TRY(q, hipSetDevice(q->device));
-    drain_spans(q);
-    return check_queue_overflow(q);
-  });
+  return read_image(c, -1, dst, bytes);
 }
 
 int ptmi_reduce_framebuffer(ptmi_ctx* c) {
@@ -1901,19 +2089,8 @@ int ptmi_stream(ptmi_ctx* c, void** stream) {
 int ptmi_resolve_rgba8(ptmi_ctx* c, float frame_num, uint8_t* dst, size_t bytes) {
   if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_rgba8: null argument");
   if (!c->fb) return fail(c, PTMI_ERR_STATE, "ptmi_resolve_rgba8: no framebuffer");
-  size_t npix = (size_t)c->W * c->H;
-  if (bytes != npix * 4) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_rgba8: bytes != W*H*4");
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, c->d_scratch.ensure(bytes));
-  float4* src = nullptr;
-  int gr = gather_framebuffer(c, &src);
-  if (gr) return gr;
-  hipLaunchKernelGGL(k_resolve_rgba8, dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, src, (uint32_t)npix, frame_num,
-                     c->d_scratch.as<uchar4>());
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(dst, c->d_scratch.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return PTMI_OK;
+  if (bytes != (size_t)c->W * c->H * 4) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_rgba8: bytes != W*H*4");
+  return resolve_image(c, -1, frame_num, dst, bytes);
 }
 
 int ptmi_set_counters(ptmi_ctx* c, int on) {

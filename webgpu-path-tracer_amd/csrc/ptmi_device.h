@@ -410,9 +410,9 @@ DEV void camera_pixel(const RenderConst& rc, uint32_t pix, float& px, float& py)
   px = fidx - W * truncf(q);  // f32 %: x - y*trunc(x/y)
   py = q;                     // not floored (Q1)
 }
-DEV void camera_ray_at(const RenderConst& rc, float px, float py, int k, uint32_t& rng, f3& o, f3& d) {
+// ... the rest in two halves: the jittered image-plane point (draws from the path's stream), and the view matrix applied to it
+DEV void camera_plane(const RenderConst& rc, float px, float py, int k, uint32_t& rng, float& a, float& b) {
   const float W = rc.W, H = rc.H;
-  float a, b;
   if (rc.stratify) {
     float i = (float)(k / rc.strat_side), j = (float)(k % rc.strat_side);
     a = (W / H) * (2.0f * ((px - 0.5f + (rc.recip_sqrt_spp * (i + rand2D(rng)))) / W) - 1.0f);
@@ -421,14 +421,19 @@ DEV void camera_ray_at(const RenderConst& rc, float px, float py, int k, uint32_
     a = (W / H) * (2.0f * ((px - 0.5f + rand2D(rng)) / W) - 1.0f);
     b = -1.0f * (2.0f * ((py - 0.5f + rand2D(rng)) / H) - 1.0f);
   }
-  const float* m = rc.view;
-  float nf = -rc.fov_factor;
+}
+DEV f3 camera_dir(const float* m, float nf, float a, float b) {  // m: the view matrix, column-major; nf = -fov_factor
   float dx = ((m[0] * a + m[4] * b) + m[8] * nf) + m[12] * 0.0f;
   float dy = ((m[1] * a + m[5] * b) + m[9] * nf) + m[13] * 0.0f;
   float dz = ((m[2] * a + m[6] * b) + m[10] * nf) + m[14] * 0.0f;
   float dw = ((m[3] * a + m[7] * b) + m[11] * nf) + m[15] * 0.0f;
   float len = sqrt_exact(((dx * dx + dy * dy) + dz * dz) + dw * dw);  // normalize() of the vec4, then .xyz
-  d = mk3(dx, dy, dz) / len;
+  return mk3(dx, dy, dz) / len;
+}
+DEV void camera_ray_at(const RenderConst& rc, float px, float py, int k, uint32_t& rng, f3& o, f3& d) {
+  float a, b;
+  camera_plane(rc, px, py, k, rng, a, b);
+  d = camera_dir(rc.view, -rc.fov_factor, a, b);
   o = cam_origin(rc);
 }
 DEV void camera_ray(const RenderConst& rc, uint32_t pix, int k, uint32_t& rng, f3& o, f3& d) {
@@ -452,6 +457,54 @@ DEV int2 ldu(const int2* p) {
   return make_int2(v.x, v.y);
 }
 DEV int ldu(const int* p) { return *(const PTMI_CONST_AS int*)(p); }
+
+// ---- multi-view batches (ptmi_render_views) ------------------------------------------------------------
+// A batch whose frame slots belong to different views.  The call's V views lie in a device table, kViewRow float4 per view: the matrix's four columns, then
+// {cam_origin.xyz, 0} as make_render_const computes it.  Frame slot f of the batch is slot slot0 + f of the call's V * fpv: view (slot0 + f) / fpv, frame number
+// rc.frame0 + (slot0 + f) % fpv.  Only the kernel instances with MV = true read any of this; the others are handed an empty ViewTab and never touch it.
+constexpr int kViewRow = 5;
+struct ViewTab {
+  const float4* rows;
+  uint32_t slot0;    // the batch's first frame slot among the call's
+  uint32_t fpv;      // frames per view
+  uint32_t n_local;  // = rc.n_local, for the kernels that are not handed rc (k_bvh)
+};
+struct ViewRow {
+  float m[16];
+  f3 o;
+};
+DEV ViewRow unpack_view_row(float4 c0, float4 c1, float4 c2, float4 c3, float4 o) {
+  ViewRow r;
+  r.m[0] = c0.x, r.m[1] = c0.y, r.m[2] = c0.z, r.m[3] = c0.w, r.m[4] = c1.x, r.m[5] = c1.y, r.m[6] = c1.z, r.m[7] = c1.w;
+  r.m[8] = c2.x, r.m[9] = c2.y, r.m[10] = c2.z, r.m[11] = c2.w, r.m[12] = c3.x, r.m[13] = c3.y, r.m[14] = c3.z, r.m[15] = c3.w;
+  r.o = mk3(o);
+  return r;
+}
+// View v's row for this lane.  The lanes of a wave nearly always agree on v (k_generate: a wave's 64 pixels of one frame slot): then the row comes through
+// scalar loads; a wave that straddles two views gathers per lane.  Call from converged or diverged code alike: the vote is among the active lanes.
+DEV ViewRow load_view_row(const ViewTab& vt, uint32_t v) {
+  const uint32_t vu = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+  if (__ballot(v != vu) == 0ull) {
+    const float4* p = vt.rows + (size_t)kViewRow * vu;
+    return unpack_view_row(ldu(p), ldu(p + 1), ldu(p + 2), ldu(p + 3), ldu(p + 4));
+  }
+  const float4* p = vt.rows + (size_t)kViewRow * v;
+  return unpack_view_row(p[0], p[1], p[2], p[3], p[4]);
+}
+// The view a slot of STEP 0's queue belongs to (slot = path id = frame_slot * n_local + local pixel), and where its camera ray starts.  Step 0's queue stays
+// 32 bytes per path in a multi-view batch too: its readers look the origin up — two integer divisions by wave-uniform divisors and a 16-byte load that hits a
+// table of a few KB — instead of every path carrying 12 more bytes through HBM.
+DEV uint32_t view_of_path(const ViewTab& vt, uint32_t pid) { return (vt.slot0 + pid / vt.n_local) / vt.fpv; }
+DEV f3 view_origin_of_path(const ViewTab& vt, uint32_t pid) { return mk3(vt.rows[(size_t)kViewRow * view_of_path(vt, pid) + 4]); }
+DEV void camera_ray_view(const RenderConst& rc, const ViewTab& vt, uint32_t pid, int k, uint32_t& rng, f3& o, f3& d) {
+  float px, py, a, b;
+  camera_pixel(rc, local_to_pixel(rc, pid % rc.n_local), px, py);
+  camera_plane(rc, px, py, k, rng, a, b);
+  const float4* p = vt.rows + (size_t)kViewRow * view_of_path(vt, pid);
+  const ViewRow r = unpack_view_row(p[0], p[1], p[2], p[3], p[4]);
+  d = camera_dir(r.m, -rc.fov_factor, a, b);
+  o = r.o;
+}
 
 // ---- closest-hit record carried in registers during hitScene ----------------------------------------
 struct Closest {

@@ -40,9 +40,12 @@ DEV void reduce_counters(const Counters& cn, unsigned long long* __restrict__ to
 // step 0's queue: the randState of slot g (see Slots::q0)
 DEV uint32_t* rng0_of(const Paths& P) { return reinterpret_cast<uint32_t*>(P.in.q0); }
 
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_generate(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
-                                                     unsigned long long* __restrict__ totals) {
+// MV (a multi-view batch, ViewTab): the frame number and the view of a slot follow from its place among the call's slots.  Both are derived once per chunk — the
+// one integer division — and stepped from slot to slot; the view's row is loaded anew only where the view changes (every slot with one frame per view).
+// Every render kernel comes twice: under its own name for a batch with one view — rc carries it, the ViewTab is empty and never read — and as k_*_views, the MV
+// instances of the same body with the table as one more argument (ptmi_render_views).
+template <bool COUNT, bool MV>
+DEV void generate_body(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads, unsigned long long* __restrict__ totals, ViewTab vt) {
   reset_heads(heads);
   const bool trace = rc.max_bounces > 0;  // MAX_BOUNCES = 0: ray_color's loop body never runs, no hitScene at all
   uint32_t total = rc.n_local * (uint32_t)rc.n_frames;
@@ -58,14 +61,32 @@ __global__ __launch_bounds__(kBlock) void k_generate(DevScene S, RenderConst rc,
    float px, py;
    camera_pixel(rc, pix, px, py);
    const uint32_t f_end = min((chunk + 1u) * kGenFrames, (uint32_t)rc.n_frames);
+   uint32_t view = 0, fiv = 0;  // (MV) the slot's view and its frame within the view
+   ViewRow vr;
+   if (MV) {
+     const uint32_t s = vt.slot0 + chunk * kGenFrames;
+     view = s / vt.fpv, fiv = s - view * vt.fpv;
+     vr = load_view_row(vt, view);
+   }
 #pragma unroll 1
    for (uint32_t f = chunk * kGenFrames; f < f_end; f++) {
     const uint32_t g = f * rc.n_local + j;
     uint32_t pid = g;  // path id = frame_slot * n_local + local pixel index (dense per rank)
     // u32(uniforms.frameNum): the frame number travels through an f32 uniform (renderer.js:173)
-    uint32_t rng = pix + (uint32_t)(float)(rc.frame0 + f) * 719393u;
+    uint32_t rng = pix + (uint32_t)(float)(rc.frame0 + (MV ? fiv : f)) * 719393u;
     f3 o, d;
-    camera_ray_at(rc, px, py, 0, rng, o, d);
+    if (MV) {
+      float a, b;
+      camera_plane(rc, px, py, 0, rng, a, b);
+      d = camera_dir(vr.m, -rc.fov_factor, a, b);
+      o = vr.o;
+      if (++fiv == vt.fpv) {  // the next slot opens the next view
+        fiv = 0, view++;
+        if (f + 1u < f_end) vr = load_view_row(vt, view);
+      }
+    } else {
+      camera_ray_at(rc, px, py, 0, rng, o, d);
+    }
     float2 tp = make_float2(0.0f, 0.0f);
     uint32_t hm = HITMAT_MISS;
     if (trace) prims_for_ray<COUNT>(S, o, d, rng, tp, hm, cn);
@@ -83,6 +104,16 @@ __global__ __launch_bounds__(kBlock) void k_generate(DevScene S, RenderConst rc,
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) ctl[0].n_rays = total;
   if (COUNT) reduce_counters(cn, totals, false);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_generate(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
+                                                     unsigned long long* __restrict__ totals) {
+  generate_body<COUNT, false>(S, rc, P, ctl, heads, totals, ViewTab{});
+}
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_generate_views(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
+                                                           unsigned long long* __restrict__ totals, ViewTab vt) {
+  generate_body<COUNT, true>(S, rc, P, ctl, heads, totals, vt);
 }
 
 // 96 VGPRs (5 waves/SIMD, no spills) measured 27 % faster than the compiler's default 106 VGPRs / 4 waves: the kernel
@@ -227,9 +258,9 @@ DEV void walk_inner(const DevScene& S, const WalkRay& ray, const LaneStack2& stk
 // (Storing an accepted hit at once instead of at the end of the ray saved four registers and lost 12 %: on gfx9 stores count on
 // vmcnt like loads, so every later fetch waited for them.)
 constexpr int kScanGroups = 3, kCandSlots = 64 * (kScanGroups + 1);  // a pass adds at most 64 x kScanGroups candidates to fewer than 64
-template <bool COUNT, bool NOABORT>
+template <bool COUNT, bool NOABORT, bool MV>
 DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads, uint32_t n_teams, int stack_size, int lds_entries, int spill_entries,
-                   int2* __restrict__ spill, int refill_threshold, int leaf_batch, unsigned long long* __restrict__ totals, uint32_t range_cap, float4 cam, const Carry& cy,
+                   int2* __restrict__ spill, int refill_threshold, int leaf_batch, unsigned long long* __restrict__ totals, uint32_t range_cap, float4 cam, const Carry& cy, const ViewTab& vt,
                    int* lds_stack, uint32_t wave_id, uint32_t n_waves  // (stand where blockIdx.x / gridDim.x would: a wave works on its own)
 ) {
   const int lane = lane_id();
@@ -321,6 +352,7 @@ DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl,
           w.ct = P.hin.tp[myslot].x;  // closest_so_far after part 1 of hitScene; the rest of that record stands unless a triangle wins
           f3 o = mk3(cam);
           if (cam.w == 0.0f) o = mk3(P.in.q0[myslot]);  // (wave-uniform: step 0 picks a ray up with two gathers instead of three)
+          else if (MV) o = view_origin_of_path(vt, myslot);  // (step 0: slot = path id)
           ray = make_walk_ray(S, o, mk3(r1));
           w.sp = 0;
           w.hit.prim = 0u;
@@ -365,7 +397,10 @@ DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl,
           const float4 r1 = P.in.q1[myslot];
           float4 r0 = cam, r2 = make_float4(1.0f, 1.0f, 1.0f, __int_as_float(0));  // (step 0's queue stores neither the origin nor the initial throughput / bounce)
           if (cam.w == 0.0f) r0 = P.in.q0[myslot], r2 = P.in.q2[myslot];
-          else r0.w = __uint_as_float(rng0_of(P)[myslot]);
+          else {
+            if (MV) r0 = make_float4(ray.o.x, ray.o.y, ray.o.z, 0.0f);  // (the origin of the lane's own view: picked up above)
+            r0.w = __uint_as_float(rng0_of(P)[myslot]);
+          }
           P.out.q0[ns] = r0, P.out.q1[ns] = r1, P.out.q2[ns] = r2;
           P.hout.tp[ns] = P.hin.tp[myslot];    // hitScene part 1's record: stands unless a triangle has won or wins later
           P.hout.mat[ns] = P.hin.mat[myslot];  // (HITMAT_BVH still set)
@@ -393,9 +428,18 @@ __global__ __launch_bounds__(64) PTMI_BVH_ATTR void k_bvh2(DevScene S, Paths P, 
                                                            Carry cy
 ) {
   extern __shared__ int lds_stack[];
-  bvh2_body<COUNT, NOABORT>(S, P, ctl, heads, n_teams, stack_size, lds_entries, spill_entries, spill, refill_threshold, leaf_batch, totals, range_cap, cam, cy, lds_stack,
-                                     blockIdx.x, gridDim.x
+  bvh2_body<COUNT, NOABORT, false>(S, P, ctl, heads, n_teams, stack_size, lds_entries, spill_entries, spill, refill_threshold, leaf_batch, totals, range_cap, cam, cy, ViewTab{},
+                                            lds_stack, blockIdx.x, gridDim.x
   );
+}
+// step 0 of a multi-view batch: every ray starts at the origin of its slot's view (cam.w != 0 still marks step 0; cam.xyz is not read)
+template <bool COUNT, bool NOABORT>
+__global__ __launch_bounds__(64) PTMI_BVH_ATTR void k_bvh2_views(DevScene S, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads, uint32_t n_teams, int stack_size,
+                                                                 int lds_entries, int spill_entries, int2* __restrict__ spill, int refill_threshold, int leaf_batch,
+                                                                 unsigned long long* __restrict__ totals, uint32_t range_cap, float4 cam, Carry cy, ViewTab vt) {
+  extern __shared__ int lds_stack[];
+  bvh2_body<COUNT, NOABORT, true>(S, P, ctl, heads, n_teams, stack_size, lds_entries, spill_entries, spill, refill_threshold, leaf_batch, totals, range_cap, cam, cy, vt, lds_stack,
+                                           blockIdx.x, gridDim.x);
 }
 
 
@@ -428,13 +472,14 @@ struct SlotState {
   float2 tp;
   uint32_t hitmat, slot;
 };
-DEV SlotState load_slot(const Paths& P, uint32_t slot, bool first, const RenderConst& rc) {
+template <bool MV>
+DEV SlotState load_slot(const Paths& P, uint32_t slot, bool first, const RenderConst& rc, const ViewTab& vt) {
   SlotState st;
   st.slot = slot;
   st.hitmat = P.hin.mat[slot];
   st.q1 = P.in.q1[slot];
   if (first) {  // step 0: k_generate does not store what every path starts with
-    const f3 co = cam_origin(rc);
+    const f3 co = MV ? view_origin_of_path(vt, slot) : cam_origin(rc);  // (step 0: slot = path id)
     st.q0 = make_float4(co.x, co.y, co.z, __uint_as_float(rng0_of(P)[slot]));
     st.q2 = make_float4(1.0f, 1.0f, 1.0f, __int_as_float(0));
   } else {
@@ -474,8 +519,8 @@ DEV void end_sample_progressive(const Paths& P, uint32_t pid, f3 add, bool writt
 // MULTI = NUM_SAMPLES > 1 (the per-pixel sample loop of shootRay.wgsl:5-49 lives in the slot: pixsum, in-slot camera ray); the
 // reference's progressive mode (NUM_SAMPLES = 1) compiles without it, which also frees the scalar registers the view matrix and
 // the image constants would occupy through the whole kernel.
-template <bool IS, bool MULTI>
-DEV bool shade_one(const DevScene& S, const RenderConst& rc, const Paths& P, const SlotState& st, const TriFetch& tf, const QuadL& L, NewState& ns) {
+template <bool IS, bool MULTI, bool MV>
+DEV bool shade_one(const DevScene& S, const RenderConst& rc, const Paths& P, const SlotState& st, const TriFetch& tf, const QuadL& L, NewState& ns, const ViewTab& vt) {
   const uint32_t pid = __float_as_uint(st.q1.w);
   const f3 o = mk3(st.q0), d = mk3(st.q1);
   const float4 T4 = st.q2;
@@ -601,7 +646,8 @@ DEV bool shade_one(const DevScene& S, const RenderConst& rc, const Paths& P, con
   sample++;
   if (sample < rc.num_samples) {  // the next sample continues the same RNG stream in the same slot
     P.pixsum[pid] = make_float4(sum.x, sum.y, sum.z, 0.0f);
-    camera_ray(rc, local_to_pixel(rc, pid % rc.n_local), sample, rng, no, nd);
+    if (MV) camera_ray_view(rc, vt, pid, sample, rng, no, nd);
+    else camera_ray(rc, local_to_pixel(rc, pid % rc.n_local), sample, rng, no, nd);
     P.acc[pid] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(sample));
     ns.o = no, ns.d = nd, ns.T = mk3(1.0f, 1.0f, 1.0f), ns.bounce = 0, ns.rng = rng;
     return true;
@@ -713,9 +759,9 @@ struct OutRegion {
 //      record go to the block's current OUTPUT REGION of the next queue, coalesced.  A block claims a region with one
 //      global atomic (16 or so per launch), fills it across chunks — an entry that does not fit any more continues in
 //      the next region — and marks what is left at the end as holes.
-template <bool IS, bool COUNT, bool MULTI>
+template <bool IS, bool COUNT, bool MULTI, bool MV>
 DEV void shade_body(const DevScene& S, const RenderConst& rc, const Paths& P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads, unsigned long long* __restrict__ totals,
-                    int first, uint32_t resv) {
+                    int first, uint32_t resv, const ViewTab& vt) {
   reset_heads(heads);
   __shared__ float4 s_q0[kSChunk], s_q1[kSChunk], s_q2[kSChunk];
   __shared__ uint16_t s_sorted[kSChunk];
@@ -811,9 +857,9 @@ DEV void shade_body(const DevScene& S, const RenderConst& rc, const Paths& P, St
         bool survive = false;
         NewState ns = zero_state();
         if (k < nvalid) {
-          const SlotState st = load_slot(P, base + s_sorted[k], first != 0, rc);
+          const SlotState st = load_slot<MV>(P, base + s_sorted[k], first != 0, rc, vt);
           const TriFetch tf = tri_fetch(S, P.uv, st.slot, __float_as_uint(st.tp.y));  // (issued ahead of the material's loads, consumed after them)
-          survive = shade_one<IS, MULTI>(S, rc, P, st, tf, L, ns);
+          survive = shade_one<IS, MULTI, MV>(S, rc, P, st, tf, L, ns, vt);
         }
         stage(survive, ns);
       }
@@ -870,9 +916,9 @@ DEV void shade_body(const DevScene& S, const RenderConst& rc, const Paths& P, St
 // In progressive mode, a flush pass in which at least rc.shade_cont new rays have their final hit record (no root box entered) keeps those rays:
 // the wave shades them next, as a pass of its own, and only the rays that need k_bvh go to the next queue (continuation, round 6).
 // (shade_body's three barriers per chunk had every wave wait for the block's slowest three times per 128 slots of its own work.)
-template <bool IS, bool COUNT, bool MULTI>
+template <bool IS, bool COUNT, bool MULTI, bool MV>
 DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
-                         unsigned long long* __restrict__ totals, int first, uint32_t resv) {
+                         unsigned long long* __restrict__ totals, int first, uint32_t resv, const ViewTab& vt) {
   reset_heads(heads);
   constexpr uint32_t kRing = 128, kWaves = kBlock / 64;
   static_assert((size_t)kWaves * kRing == (size_t)kSChunk, "the rings take the LDS the block version's staging arrays take");
@@ -972,7 +1018,7 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
       if (valid) {
         LT(LT_VALID);
         const TriFetch tf = tri_fetch(S, P.uv, st.slot, __float_as_uint(st.tp.y));  // (issued ahead of the material's loads, consumed after them)
-        survive = shade_one<IS, MULTI>(S, rc, P, st, tf, L, ns);
+        survive = shade_one<IS, MULTI, MV>(S, rc, P, st, tf, L, ns, vt);
       }
     }
     TT(TT_SHADE, ns.o.x + ns.T.x);  // material + hit geometry fetched (TT_LOAD2, marked inside shade_one) and the bounce computed
@@ -1002,7 +1048,7 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
     auto fetch = [&](SlotState& st) {  // -> this lane's slot of group (base, j0) holds something; its state is on its way then
       const uint32_t j = j0 + (uint32_t)lane;
       const bool act = j < min((uint32_t)kSChunk, n - base) && !dead_slot(base + j, n_carried, resv);
-      if (act) st = load_slot(P, base + j, first != 0, rc);
+      if (act) st = load_slot<MV>(P, base + j, first != 0, rc, vt);
       return act;
     };
     // Continuation (cont_min > 0): a flush pass whose rays need no tree walk on at least cont_min lanes hands their state, in registers, to the next
@@ -1067,14 +1113,28 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
 template <bool IS, bool SORT, bool COUNT, bool MULTI>
 __global__ __launch_bounds__(kBlock) PTMI_SHADE_ATTR void k_shade(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
                                                                   unsigned long long* __restrict__ totals, int first, uint32_t resv) {
-  if constexpr (SORT) shade_body<IS, COUNT, MULTI>(S, rc, P, ctl, heads, totals, first, resv);  // several material classes: block by block, sorted
-  else shade_body_wave<IS, COUNT, MULTI>(S, rc, P, ctl, heads, totals, first, resv);            // one class: wave by wave
+  if constexpr (SORT) shade_body<IS, COUNT, MULTI, false>(S, rc, P, ctl, heads, totals, first, resv, ViewTab{});  // several material classes: block by block, sorted
+  else shade_body_wave<IS, COUNT, MULTI, false>(S, rc, P, ctl, heads, totals, first, resv, ViewTab{});            // one class: wave by wave
 }
 template <bool SORT, bool COUNT>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_shade6(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl,
                                                                                                 uint32_t* __restrict__ heads, unsigned long long* __restrict__ totals, int first, uint32_t resv) {
-  if constexpr (SORT) shade_body<false, COUNT, false>(S, rc, P, ctl, heads, totals, first, resv);
-  else shade_body_wave<false, COUNT, false>(S, rc, P, ctl, heads, totals, first, resv);
+  if constexpr (SORT) shade_body<false, COUNT, false, false>(S, rc, P, ctl, heads, totals, first, resv, ViewTab{});
+  else shade_body_wave<false, COUNT, false, false>(S, rc, P, ctl, heads, totals, first, resv, ViewTab{});
+}
+// ... of a multi-view batch: step 0's origins and the in-slot camera rays of NUM_SAMPLES > 1 come from the view of the path's slot
+template <bool IS, bool SORT, bool COUNT, bool MULTI>
+__global__ __launch_bounds__(kBlock) PTMI_SHADE_ATTR void k_shade_views(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
+                                                                        unsigned long long* __restrict__ totals, int first, uint32_t resv, ViewTab vt) {
+  if constexpr (SORT) shade_body<IS, COUNT, MULTI, true>(S, rc, P, ctl, heads, totals, first, resv, vt);
+  else shade_body_wave<IS, COUNT, MULTI, true>(S, rc, P, ctl, heads, totals, first, resv, vt);
+}
+template <bool SORT, bool COUNT>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_shade6_views(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl,
+                                                                                                      uint32_t* __restrict__ heads, unsigned long long* __restrict__ totals, int first,
+                                                                                                      uint32_t resv, ViewTab vt) {
+  if constexpr (SORT) shade_body<false, COUNT, false, true>(S, rc, P, ctl, heads, totals, first, resv, vt);
+  else shade_body_wave<false, COUNT, false, true>(S, rc, P, ctl, heads, totals, first, resv, vt);
 }
 
 // k_tail — a SHORT queue traced to the end in one launch: every lane takes a path and runs ray_color's loop for it (hitScene part 2 on
@@ -1085,9 +1145,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) 
 // when it has run, the block that finishes last zeroes the queue length, so the step's k_bvh / k_shade and every later step find nothing.
 // Same per-ray arithmetic and visit order as the wavefront kernels (the same device functions), same counters and tallies.
 constexpr int kTailTravBatch = 24;  // (12 / 32 / 40 lanes measured: profiles/r04_tail_trav_batch.txt)
-template <bool IS, bool COUNT, bool MULTI, bool NOABORT>
+template <bool IS, bool COUNT, bool MULTI, bool NOABORT, bool MV>
 DEV void tail_body(const DevScene& S, const RenderConst& rc, const Paths& P, StepCtl* __restrict__ ctl, unsigned long long* __restrict__ totals, int first, uint32_t limit,
-                   int stack_size, int lds_entries, int spill_entries, int2* __restrict__ spill, const Carry& cy) {
+                   int stack_size, int lds_entries, int spill_entries, int2* __restrict__ spill, const Carry& cy, const ViewTab& vt) {
   const QueueExtent qe = queue_extent(ctl, cy.resv);  // (Carry: the rays in [0, n_carried) go on with their traversal)
   const uint32_t n = qe.n, n_carried = qe.n_carried;
   if (n == 0u) return;                                               // empty
@@ -1132,7 +1192,7 @@ DEV void tail_body(const DevScene& S, const RenderConst& rc, const Paths& P, Ste
         if (!alive && rank < take) {
           const uint32_t slot = gbase + pos + rank;
           if (slot < n && !dead_slot(slot, n_carried, cy.resv)) {
-            st = load_slot(P, slot, first != 0, rc);
+            st = load_slot<MV>(P, slot, first != 0, rc, vt);
             alive = __float_as_uint(st.q1.w) != PID_HOLE;
             uv = make_float2(0.0f, 0.0f);
             resume = alive && slot < cy.resv;
@@ -1198,7 +1258,7 @@ DEV void tail_body(const DevScene& S, const RenderConst& rc, const Paths& P, Ste
       if (go) {
         tally++;
         const TriFetch tf = tri_fetch_uv(S, uv, __float_as_uint(st.tp.y));
-        survive = shade_one<IS, MULTI>(S, rc, P, st, tf, L, ns);
+        survive = shade_one<IS, MULTI, MV>(S, rc, P, st, tf, L, ns, vt);
         alive = survive;
       }
       BT(TB_SHADE, ns.o.x + ns.T.x, __popcll(__ballot(go)));
@@ -1245,13 +1305,25 @@ DEV void tail_body(const DevScene& S, const RenderConst& rc, const Paths& P, Ste
 template <bool IS, bool COUNT, bool MULTI, bool NOABORT>
 __global__ __launch_bounds__(64) void k_tail(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, unsigned long long* __restrict__ totals, int first, uint32_t limit,
                                              int stack_size, int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy) {
-  tail_body<IS, COUNT, MULTI, NOABORT>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy);
+  tail_body<IS, COUNT, MULTI, NOABORT, false>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, ViewTab{});
 }
 template <bool COUNT, bool NOABORT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_tail6(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl,
                                                                                          unsigned long long* __restrict__ totals, int first, uint32_t limit, int stack_size,
                                                                                          int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy) {
-  tail_body<false, COUNT, false, NOABORT>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy);
+  tail_body<false, COUNT, false, NOABORT, false>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, ViewTab{});
+}
+// ... of a multi-view batch (step 0's origins, the in-slot camera rays of NUM_SAMPLES > 1)
+template <bool IS, bool COUNT, bool MULTI, bool NOABORT>
+__global__ __launch_bounds__(64) void k_tail_views(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, unsigned long long* __restrict__ totals, int first,
+                                                   uint32_t limit, int stack_size, int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy, ViewTab vt) {
+  tail_body<IS, COUNT, MULTI, NOABORT, true>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, vt);
+}
+template <bool COUNT, bool NOABORT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_tail6_views(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl,
+                                                                                               unsigned long long* __restrict__ totals, int first, uint32_t limit, int stack_size,
+                                                                                               int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy, ViewTab vt) {
+  tail_body<false, COUNT, false, NOABORT, true>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, vt);
 }
 
 // A batch's step records: every queue but step 0's starts behind its carry prefix (Carry)
@@ -1265,11 +1337,24 @@ __global__ void k_init_ctl(StepCtl* __restrict__ ctl, int n, uint32_t resv) {
 
 // main.wgsl:22-27 for the frame slots [f_begin, f_end) of the batch, in frame order; the call that folds slot 0 also
 // tallies the batch's rays/paths.  (ptmi_render_frame's render-ahead folds one slot per call.)
+// MV (a multi-view batch): `fb` is the context's view stack, [views][npix]; a slot is folded into the image of its view — the image changes where the slot's
+// frame-in-view wraps — and rc.reset_first applies to every view's frame 0.
+// (One kernel template here, not a k_*_views twin around a shared body: inlined into two kernels the loop below was scheduled differently — one more SGPR in the
+// instance every render uses.  k_accumulate<false> is handed an empty ViewTab and compiles to what the kernel without the flag compiled to.)
+template <bool MV>
 __global__ __launch_bounds__(kBlock) void k_accumulate(RenderConst rc, Paths P, float4* __restrict__ fb, int n_steps,
-                                                       unsigned long long* __restrict__ totals, int f_begin, int f_end) {
+                                                       unsigned long long* __restrict__ totals, int f_begin, int f_end, ViewTab vt) {
   for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < rc.n_local; j += gridDim.x * kBlock) {
     uint32_t pix = local_to_pixel(rc, j);
-    float4 cur = fb[pix];
+    uint32_t fiv = 0;  // (MV) frame-in-view of the slot about to be folded
+    float4* img = fb;  // the image `c` belongs to
+    if (MV) {
+      const uint32_t s = vt.slot0 + (uint32_t)f_begin, view = s / vt.fpv;
+      fiv = s - view * vt.fpv;
+      img = fb + (size_t)view * rc.npix;
+    }
+    bool pending = !MV;  // `c` has still to be stored
+    float4 cur = (MV && f_begin >= f_end) ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : img[pix];
     f3 c = mk3(cur);
     // The frames are added in frame order (the f32 sum is the reference's), but their colours are FETCHED eight at a time: a pixel's thread used to walk
     // flag -> colour -> add one frame after the other, two dependent round trips per frame — with pixel tiles sharded over 8 GPUs that is 512 frames per
@@ -1293,14 +1378,24 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(RenderConst rc, Paths P, 
         const int f = f0 + k;
         if (f >= f_end) break;
         const f3 col = mk3(colv[k]);
-        if (f == 0 && rc.reset_first) {
+        if ((MV ? fiv == 0u : f == 0) && rc.reset_first) {
           c = col;
         } else {
           c = c + col;
         }
+        if (MV) {
+          pending = true;
+          if (++fiv == vt.fpv) {  // the view's last frame: its image is done, the next slot opens the next one
+            img[pix] = make_float4(c.x, c.y, c.z, 1.0f);
+            pending = false;
+            fiv = 0;
+            img += rc.npix;
+            if (f + 1 < f_end && !rc.reset_first) c = mk3(img[pix]);  // (with reset the next slot's colour overwrites c)
+          }
+        }
       }
     }
-    fb[pix] = make_float4(c.x, c.y, c.z, 1.0f);
+    if (pending) img[pix] = make_float4(c.x, c.y, c.z, 1.0f);
   }
   if (f_begin == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
     unsigned long long rays = 0;

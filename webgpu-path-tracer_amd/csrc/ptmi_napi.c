@@ -36,6 +36,10 @@ FN(ptmi_clear_framebuffer)
 FN(ptmi_set_shard)
 FN(ptmi_render_frame)
 FN(ptmi_render)
+FN(ptmi_render_views)
+FN(ptmi_read_view)
+FN(ptmi_resolve_view_rgba8)
+FN(ptmi_release_views)
 FN(ptmi_synchronize)
 FN(ptmi_read_framebuffer)
 FN(ptmi_write_framebuffer)
@@ -84,7 +88,7 @@ static int load_lib(char* err, size_t errlen) {
   }
   LOAD(ptmi_version) LOAD(ptmi_last_error) LOAD(ptmi_create) LOAD(ptmi_create_multi) LOAD(ptmi_prepare) LOAD(ptmi_destroy) LOAD(ptmi_default_params) LOAD(ptmi_set_params)
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
-  LOAD(ptmi_render) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
+  LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
   LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah)
   LOAD(ptmi_obj_parse) LOAD(ptmi_free) LOAD(ptmi_device_count) LOAD(ptmi_reduce_info)
   return 0;
@@ -388,6 +392,73 @@ static napi_value js_render(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* renderViews(ctx, Float32Array(V*16), firstFrame, framesPerView, reset): a camera path in one pass (ptmi_render_views) — what renderer.js:173-188 does with
+ * resetBuffer = 1 on every move, for V views at once; image v of the context's view stack receives view v's frames */
+static napi_value js_render_views(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (get_args(env, info, 5, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  void* data;
+  size_t len;
+  if (typed(env, a[1], napi_float32_array, "renderViews(views)", &data, &len)) return NULL;
+  if (len == 0 || len % 16 != 0 || len / 16 > 0xffffffffu) {
+    napi_throw_range_error(env, NULL, "renderViews: views must hold 16 floats per view, one view at least");
+    return NULL;
+  }
+  uint32_t first, fpv;
+  CHECK_NAPI(napi_get_value_uint32(env, a[2], &first));
+  CHECK_NAPI(napi_get_value_uint32(env, a[3], &fpv));
+  bool reset = false;
+  napi_coerce_to_bool(env, a[4], &a[4]);
+  napi_get_value_bool(env, a[4], &reset);
+  int st = p_ptmi_render_views(c, (const float*)data, (uint32_t)(len / 16), first, fpv, reset ? 1 : 0);
+  if (st) return throw_status(env, c, st, "ptmi_render_views");
+  return NULL;
+}
+
+static napi_value js_read_view(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (get_args(env, info, 3, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  uint32_t view;
+  CHECK_NAPI(napi_get_value_uint32(env, a[1], &view));
+  void* data;
+  size_t len;
+  if (typed(env, a[2], napi_float32_array, "readView(out)", &data, &len)) return NULL;
+  int st = p_ptmi_read_view(c, view, (float*)data, len * 4);
+  if (st) return throw_status(env, c, st, "ptmi_read_view");
+  return a[2];
+}
+
+static napi_value js_resolve_view(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (get_args(env, info, 4, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  uint32_t view;
+  CHECK_NAPI(napi_get_value_uint32(env, a[1], &view));
+  double fn;
+  CHECK_NAPI(napi_get_value_double(env, a[2], &fn));
+  void* data;
+  size_t len;
+  if (typed(env, a[3], napi_uint8_array, "resolveViewRGBA8(out)", &data, &len)) return NULL;
+  int st = p_ptmi_resolve_view_rgba8(c, view, (float)fn, (uint8_t*)data, len);
+  if (st) return throw_status(env, c, st, "ptmi_resolve_view_rgba8");
+  return a[3];
+}
+
+static napi_value js_release_views(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (get_args(env, info, 1, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  int st = p_ptmi_release_views(c);
+  if (st) return throw_status(env, c, st, "ptmi_release_views");
+  return NULL;
+}
+
 static napi_value js_synchronize(napi_env env, napi_callback_info info) {
   napi_value a[1];
   if (get_args(env, info, 1, a)) return NULL;
@@ -672,7 +743,7 @@ static napi_value init(napi_env env, napi_value exports) {
   } fns[] = {
       {"version", js_version}, {"create", js_create}, {"destroy", js_destroy}, {"defaultParams", js_default_params}, {"setParams", js_set_params},
       {"upload", js_upload}, {"resize", js_resize}, {"clear", js_clear}, {"setShard", js_set_shard}, {"renderFrame", js_render_frame},
-      {"render", js_render}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
+      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
       {"resolveRGBA8", js_resolve}, {"setCounters", js_set_counters}, {"setTiming", js_set_timing}, {"stats", js_stats},
       {"resetStats", js_reset_stats}, {"buildBVH", js_build_bvh}, {"buildBVHSAH", js_build_bvh_sah}, {"buildBVHDevice", js_build_bvh_device}, {"parseObj", js_parse_obj},
       {"deviceCount", js_device_count}, {"reduceInfo", js_reduce_info},

@@ -30,6 +30,12 @@ export class Ptmi {
   setShard(rank, world, tile) { this.native.setShard(this.h, rank, world, tile); }
   renderFrame(uniforms20) { this.native.renderFrame(this.h, uniforms20); }
   render(view16, firstFrame, nFrames) { this.native.render(this.h, view16, firstFrame, nFrames); }
+  // A camera path in one pass (ptmi_render_views): views = Float32Array(V * 16), one column-major view matrix after the other; image v of the context's view stack
+  // receives frames firstFrame .. firstFrame + framesPerView - 1 of view v (reset: a view's first frame overwrites, as resetBuffer = 1 does).
+  renderViews(views, firstFrame, framesPerView, reset = true) { this.native.renderViews(this.h, views, firstFrame, framesPerView, reset); }
+  readView(v, out = new Float32Array(this.width * this.height * 4)) { return this.native.readView(this.h, v, out); }
+  resolveViewRGBA8(v, frameNum, out = new Uint8Array(this.width * this.height * 4)) { return this.native.resolveViewRGBA8(this.h, v, frameNum, out); }
+  releaseViews() { this.native.releaseViews(this.h); }
   synchronize() { this.native.synchronize(this.h); }
   prepare() { this.native.prepare(this.h); }
   buildSceneBVHSAH() { this.native.buildSceneBVHSAH(this.h); }   // the same with the reference's never-called SAH builder (lib/BVH/bvhNode.js:108-283): opt-in

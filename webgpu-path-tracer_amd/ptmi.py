@@ -20,6 +20,7 @@ SYMBOLS = [
     "ptmi_set_timing", "ptmi_get_stats", "ptmi_reset_stats", "ptmi_trace", "ptmi_math_eval", "ptmi_selftest", "ptmi_build_bvh",
     "ptmi_build_bvh_sah", "ptmi_build_bvh_device", "ptmi_build_scene_bvh", "ptmi_read_scene_buffer", "ptmi_obj_parse", "ptmi_free",
     "ptmi_device_count", "ptmi_reduce_info", "ptmi_reload_tuning", "ptmi_build_scene_bvh_sah", "ptmi_scene_bvh_info", "ptmi_build_bvh_sah_device",
+    "ptmi_render_views", "ptmi_read_view", "ptmi_resolve_view_rgba8", "ptmi_views_device_ptr", "ptmi_release_views",
 ]
 
 
@@ -127,6 +128,12 @@ def load_library(build=False, path=None):
     L.ptmi_reduce_info.restype = ctypes.c_char_p
     L.ptmi_reduce_info.argtypes = [vp]
     L.ptmi_reload_tuning.argtypes = [vp]
+    if hasattr(L, "ptmi_render_views"):  # (an older A/B build loaded through PTMI_LIB renders one view per call)
+        L.ptmi_render_views.argtypes = [vp, fp, u32, u32, u32, i32]
+        L.ptmi_read_view.argtypes = [vp, u32, fp, sz]
+        L.ptmi_resolve_view_rgba8.argtypes = [vp, u32, ctypes.c_float, fp, sz]
+        L.ptmi_views_device_ptr.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(u32)]
+        L.ptmi_release_views.argtypes = [vp]
     if explicit:
         _libs[path] = L
     else:
@@ -274,6 +281,32 @@ class Context:
         v = np.ascontiguousarray(view16, np.float32)
         assert v.size == 16
         self._ck(self.lib.ptmi_render(self.h, _ptr(v), first_frame, n_frames))
+
+    def render_views(self, views, first_frame, frames_per_view, reset=True):
+        """A camera path in one pass (ptmi_render_views): `views` is (V, 16) float32, one column-major view matrix per row; image v of the context's
+        view stack receives frames first_frame .. first_frame + frames_per_view - 1 of view v.  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32)
+        assert v.ndim == 2 and v.shape[1] == 16, "views: (V, 16) float32"
+        self._ck(self.lib.ptmi_render_views(self.h, _ptr(v), v.shape[0], first_frame, frames_per_view, 1 if reset else 0))
+
+    def read_view(self, view):
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(self.lib.ptmi_read_view(self.h, view, _ptr(out), out.nbytes))
+        return out
+
+    def resolve_view_rgba8(self, view, frame_num):
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        self._ck(self.lib.ptmi_resolve_view_rgba8(self.h, view, float(frame_num), _ptr(out), out.nbytes))
+        return out
+
+    def views_device_ptr(self):
+        """(device pointer, bytes, n_views) of the view stack: one contiguous [n_views][H][W][4] float32 array (single-device contexts)."""
+        p, n, v = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_uint32()
+        self._ck(self.lib.ptmi_views_device_ptr(self.h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(v)))
+        return p.value, n.value, v.value
+
+    def release_views(self):
+        self._ck(self.lib.ptmi_release_views(self.h))
 
     def synchronize(self):
         self._ck(self.lib.ptmi_synchronize(self.h))
