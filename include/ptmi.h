@@ -202,6 +202,41 @@ int ptmi_views_device_ptr(ptmi_ctx* ctx, void** dev_ptr, size_t* bytes, uint32_t
 /* Frees the stack (ptmi_destroy does too); synchronises. */
 int ptmi_release_views(ptmi_ctx* ctx);
 
+/* Feature buffers (no counterpart in the reference, whose only output is colour): what the FIRST hit of every frame's path saw — for a denoiser, a data-set
+ * writer, picking.  The feature sample of (view, frame, pixel) is the HitRecord H (shaders/header.wgsl:119-125) of the hitScene call (shaders/hitRay.wgsl:1) on the
+ * frame's first camera ray of that pixel: seed pixelIndex + u32(frameNum) * 719393 (main.wgsl:16), sample 0 of pathTrace (shootRay.wgsl:5-60) under the context's
+ * num_samples / stratify / fov_degrees — with num_samples > 1 still the frame's FIRST camera ray only —, the RNG state the jitter draws leave (hit_volume consumes
+ * it), traversal under stack_size and tmin: exactly what the colour path's first hitScene sees when max_bounces >= 1; this pass traces it whatever max_bounces is.
+ * Arguments and frame numbering are ptmi_render_views'; n_views = 1 is the single-image case.  Writes the context's FEATURE STACK, [n_views][3][H][W][4] f32 in one
+ * device allocation, zeroed when this call allocates it (first call, another n_views; ptmi_resize drops it).  Three layers per view, f32 VALUES throughout:
+ *
+ *   layer                 x, y, z                                                      w
+ *   0 normal_depth        sum of H.normal                                              sum of H.t
+ *   1 albedo_coverage     sum of H.material.color                                      sum of 1.0 (frames that hit)
+ *   2 ids                 kind (0 miss, 1 sphere, 2 quad, 3 triangle),                 front_face (1 / 0)
+ *                         primitive index in its buffer (triangles: current device
+ *                         order, as ptmi_read_scene_buffer(5) returns them),
+ *                         material index
+ *
+ * Layers 0 and 1 are f32 sums in frame order, one add per frame and component, a miss adding +0.0; reset != 0: a view's first frame overwrites (main.wgsl:22-27, so
+ * a -0.0 stays -0.0), reset == 0: the frames are added to what the image holds.  Layer 2 is not summed: every frame overwrites it (a miss with (0,0,0,0)), the
+ * call's last frame stays; its ids are exact below 2^24, the triangle format's own limit.  Pixels outside the context's shard are neither read nor written.  One call
+ * with frames a .. a+n-1 leaves the same bits as n one-frame calls that pass reset only on the first.  A call that cannot allocate its stack returns
+ * PTMI_ERR_NO_MEMORY before anything is enqueued and leaves the stack it found as it was.  Asynchronous on the context's stream (time it with events on
+ * ptmi_stream: it leaves every ptmi_stats field alone); touches neither the accumulation buffer nor the view stack.  n_views * frames_per_view < 2^31. */
+int ptmi_render_aov(ptmi_ctx* ctx, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t frames_per_view, int reset);
+/* ptmi_read_view's counterpart for layer `layer` (0..2) of view `view` of the feature stack (no counterpart in renderer.js): synchronises; bytes must be W*H*16.  On a
+ * multi-device context it runs the context's collective (ptmi_create_multi) on that one image: the default tile gather moves bits, and the peer-copy sum
+ * (PTMI_MULTI_REDUCE=copy, shards that share a GPU) keeps the sign of a zero; only ncclReduce's f32 sum (PTMI_MULTI_REDUCE=rccl) turns a -0.0 of layer 0 into
+ * +0.0 (-0.0 + +0.0), nothing else. */
+int ptmi_read_aov(ptmi_ctx* ctx, uint32_t view, int layer, float* dst, size_t bytes);
+/* The feature stack as one contiguous [n_views][3][H][W][4] f32 device array (ptmi_views_device_ptr's counterpart; none in the reference); valid until the next
+ * ptmi_render_aov with another n_views, ptmi_resize or ptmi_release_aov.  bytes / n_views may be NULL.  Single-device contexts only: a multi-device context
+ * returns PTMI_ERR_UNSUPPORTED. */
+int ptmi_aov_device_ptr(ptmi_ctx* ctx, void** dev_ptr, size_t* bytes, uint32_t* n_views);
+/* Frees the feature stack (ptmi_destroy does too; no counterpart in the reference); synchronises. */
+int ptmi_release_aov(ptmi_ctx* ctx);
+
 int ptmi_synchronize(ptmi_ctx* ctx);
 
 /* Validates the uploaded buffers and builds the device-side digests now instead of inside the first render call
@@ -238,6 +273,10 @@ int ptmi_reset_stats(ptmi_ctx* ctx);
 /* Test hook: hitScene (shaders/hitRay.wgsl:1-113) for n caller-supplied rays (6 f32 each: origin,
  * dir), each with its own RNG state (consumed by hit_volume only; may be NULL). */
 int ptmi_trace(ptmi_ctx* ctx, size_t n, const float* rays6, uint32_t* rng_inout, ptmi_hit* out);
+/* Test hook, ptmi_trace's counterpart: for all W*H pixels, whatever the shard, origin and direction (6 f32) of the first camera ray of frame `frame` under `view16`
+ * (main.wgsl:3-16 + shootRay.wgsl:5-60, sample 0 — made by the device functions the render kernels call) and the RNG state its hitScene starts with: the rays
+ * ptmi_render_aov traces, in the form ptmi_trace and the oracle's hit_scene take them.  Synchronises; needs ptmi_resize. */
+int ptmi_camera_rays(ptmi_ctx* ctx, const float* view16, uint32_t frame, float* rays6, uint32_t* rng_out);
 /* Test hook: evaluates include/ptmi_math.h functions ON THE DEVICE.
  * fn: 0 sin 1 cos 2 acos 3 log 4 log2 5 exp2 6 pow(x,y) 7 sqrt 8 min(x,y) 9 max(x,y) 10 x/y
  *     11..13 = components of (x, x*2^-20, x*2^20) / y through the device's vector division */

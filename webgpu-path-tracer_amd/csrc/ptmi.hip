@@ -130,6 +130,9 @@ struct ptmi_ctx {
   float* h_view_rows = nullptr;
   size_t h_view_rows_cap = 0;
   hipEvent_t view_rows_sent = nullptr;
+  // ptmi_render_aov: the feature stack — n_aov_views x 3 images of W x H float4 (k_aov), one allocation; its calls share the view table above
+  DBuf d_aov;
+  uint32_t n_aov_views = 0;
   int rank = 0, world = 1, tile = 64;
 
   size_t path_cap = 0;
@@ -1176,14 +1179,37 @@ __global__ __launch_bounds__(kBlock) void k_add_into(float4* __restrict__ dst, c
   }
 }
 
+// k_add_into for the images of the feature stack (ptmi_render_aov), whose layer 0 holds -0.0 wherever a normal has such a component: IEEE addition gives
+// -0.0 + +0.0 = +0.0, so a plain sum with the other devices' zeros would clear that sign.  Where both terms are zero the result is the zero that carries either sign —
+// a device's own pixels are the only ones that can hold -0.0, the others are +0.0 from the allocation — and everywhere else x + 0 is x as before.
+DEV float add_keep_zero_sign(float a, float b) {
+  const float r = a + b;
+  return (a == 0.0f && b == 0.0f) ? __uint_as_float(__float_as_uint(a) | __float_as_uint(b)) : r;
+}
+__global__ __launch_bounds__(kBlock) void k_add_into_signed_zero(float4* __restrict__ dst, const float4* __restrict__ src, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+    const float4 a = dst[i], b = src[i];
+    dst[i] = make_float4(add_keep_zero_sign(a.x, b.x), add_keep_zero_sign(a.y, b.y), add_keep_zero_sign(a.z, b.z), add_keep_zero_sign(a.w, b.w));
+  }
+}
+
 // The one collective of a multi-device render: sum the per-device accumulation buffers into d_fb_gather on local device 0.
 // Every pixel is non-zero in exactly one of them (x + 0 = x), so the sum is the single-GPU image bit for bit whatever
 // the order.  The per-device buffers are left as they are, so rendering can go on afterwards.
-// `view` >= 0: the same for image `view` of the devices' view stacks (ptmi_render_views) instead of their accumulation buffers.
-float4* image_of(const ptmi_ctx* q, int view) { return view < 0 ? q->fb : q->d_views.as<float4>() + (size_t)view * (size_t)q->W * (size_t)q->H; }
-int gather_framebuffer(ptmi_ctx* c, float4** out, int view = -1) {
+// `img`: which W x H float4 image of every device — its accumulation buffer, image `index` of its view stack (ptmi_render_views), or image `index` = 3 * view + layer
+// of its feature stack (ptmi_render_aov).
+enum ImageStack { IMG_FRAMEBUFFER = 0, IMG_VIEWS = 1, IMG_AOV = 2 };
+struct ImageRef {
+  ImageStack of = IMG_FRAMEBUFFER;
+  size_t index = 0;
+};
+float4* image_of(const ptmi_ctx* q, ImageRef img) {
+  if (img.of == IMG_FRAMEBUFFER) return q->fb;
+  return (img.of == IMG_VIEWS ? q->d_views : q->d_aov).as<float4>() + img.index * (size_t)q->W * (size_t)q->H;
+}
+int gather_framebuffer(ptmi_ctx* c, float4** out, ImageRef img = ImageRef{}) {
   if (!c->multi) {
-    *out = image_of(c, view);
+    *out = image_of(c, img);
     return PTMI_OK;
   }
   const size_t bytes = (size_t)c->W * (size_t)c->H * 16, n4 = bytes / 16;
@@ -1214,7 +1240,7 @@ int gather_framebuffer(ptmi_ctx* c, float4** out, int view = -1) {
           first_error = std::string("hipSetDevice: ") + hipGetErrorString(he);
           break;
         }
-        const ncclResult_t nr = g_rccl.Reduce(image_of(q, view), i ? (void*)image_of(q, view) : (void*)g, n4 * 4, ncclFloat, ncclSum, 0, c->comms[i], q->stream);
+        const ncclResult_t nr = g_rccl.Reduce(image_of(q, img), i ? (void*)image_of(q, img) : (void*)g, n4 * 4, ncclFloat, ncclSum, 0, c->comms[i], q->stream);
         if (nr != ncclSuccess) first_error = std::string("ncclReduce (local device #") + std::to_string(i) + "): " + g_rccl.GetErrorString(nr);
         else if (rccl_fail_hook(c) == 3) first_error = "simulated failure after the first ncclReduce was enqueued (PTMI_TEST_RCCL_FAIL=mid)";
       }
@@ -1259,7 +1285,7 @@ int gather_framebuffer(ptmi_ctx* c, float4** out, int view = -1) {
     for (ptmi_ctx* q : devs) {
       const uint32_t n_local = count_local(npix, q->rank, q->world, q->tile);
       if (n_local == 0) continue;
-      const float4* src = image_of(q, view);
+      const float4* src = image_of(q, img);
       if (q->device != c->device && !q->root_reads) {
         HIP_TRY(c, c->d_fb_stage.ensure(bytes));
         HIP_TRY(c, hipMemcpyPeerAsync(c->d_fb_stage.p, c->device, src, q->device, bytes, c->stream));
@@ -1279,16 +1305,17 @@ int gather_framebuffer(ptmi_ctx* c, float4** out, int view = -1) {
     c->reduce_info = msg;
   } else if (!c->use_rccl) {
     // shards that share this GPU (tests on a one-GPU box), or PTMI_MULTI_REDUCE=copy: peer copy + add kernel
-    HIP_TRY(c, hipMemcpyAsync(g, image_of(c, view), bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(g, image_of(c, img), bytes, hipMemcpyDeviceToDevice, c->stream));
     const unsigned grid = (unsigned)std::min<size_t>((n4 + kBlock - 1) / kBlock, (size_t)c->num_cus * 8);
     for (ptmi_ctx* q : c->peers) {
-      const float4* src = image_of(q, view);
+      const float4* src = image_of(q, img);
       if (q->device != c->device) {
         HIP_TRY(c, c->d_fb_stage.ensure(bytes));
         HIP_TRY(c, hipMemcpyPeerAsync(c->d_fb_stage.p, c->device, src, q->device, bytes, c->stream));
         src = c->d_fb_stage.as<float4>();
       }
-      hipLaunchKernelGGL(k_add_into, dim3(grid), dim3(kBlock), 0, c->stream, g, src, n4);
+      if (img.of == IMG_AOV) hipLaunchKernelGGL(k_add_into_signed_zero, dim3(grid), dim3(kBlock), 0, c->stream, g, src, n4);  // (a -0.0 normal component stays -0.0)
+      else hipLaunchKernelGGL(k_add_into, dim3(grid), dim3(kBlock), 0, c->stream, g, src, n4);
       HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1723,6 +1750,8 @@ int ptmi_resize(ptmi_ctx* c, int width, int height) {
   c->H = height;
   c->d_views.release();  // the view stack belongs to the old size
   c->n_views = 0;
+  c->d_aov.release();  // ... and so does the feature stack
+  c->n_aov_views = 0;
   HIP_TRY(c, hipMemsetAsync(c->fb, 0, bytes, c->stream));
   for (ptmi_ctx* q : c->peers) {
     int r = ptmi_resize(q, width, height);
@@ -1850,23 +1879,10 @@ int ptmi_render(ptmi_ctx* c, const float* view16, uint32_t first_frame, uint32_t
   return on_all_devices(c, [=](ptmi_ctx* q) { return render_one(q, view16, first_frame, n_frames); }, true);
 }
 
-// One device's part of ptmi_render_views: render_one's loop over batches of at most F frame slots, the slots being the call's n_views x frames_per_view.
-static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t fpv, int reset) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  (void)hipGetLastError();  // a stale error of an earlier, already reported failure must not be blamed on this call
-  int r = prepare_scene(c);
-  if (r) return r;
-  r = check_renderable(c);
-  if (r) return r;
-  // the stack and the table: allocated before anything is enqueued
-  const size_t image_bytes = (size_t)c->W * (size_t)c->H * 16, row_bytes = (size_t)n_views * kViewRow * 16;
-  const bool fresh = !c->d_views.p || c->n_views != n_views;
-  if (fresh) {  // the new stack first: a call that fails for want of memory leaves the old images as they were
-    DBuf stack;
-    HIP_TRY(c, stack.ensure(image_bytes * n_views));
-    c->d_views = std::move(stack);
-    c->n_views = 0;  // (until it is zeroed, below)
-  }
+// A call's view table (ViewTab: kViewRow float4 per view) for ptmi_render_views and ptmi_render_aov, in two halves so that everything that can fail for want of
+// memory happens before anything is enqueued: stage_view_rows allocates and fills the pinned staging copy, send_view_rows puts the upload on the stream.
+static int stage_view_rows(ptmi_ctx* c, const float* views16, uint32_t n_views) {
+  const size_t row_bytes = (size_t)n_views * kViewRow * 16;
   HIP_TRY(c, c->d_view_rows.ensure(row_bytes));
   if (row_bytes > c->h_view_rows_cap) {
     if (c->view_rows_sent) HIP_TRY(c, hipEventSynchronize(c->view_rows_sent));
@@ -1884,12 +1900,39 @@ static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views,
     for (int k = 0; k < 3; k++) row[16 + k] = ((m[k] * 0.0f + m[4 + k] * 0.0f) + m[8 + k] * 0.0f) + m[12 + k] * 1.0f;  // cam_origin, as make_render_const computes it
     row[19] = 0.0f;
   }
+  return PTMI_OK;
+}
+static int send_view_rows(ptmi_ctx* c, uint32_t n_views) {
+  HIP_TRY(c, hipMemcpyAsync(c->d_view_rows.p, c->h_view_rows, (size_t)n_views * kViewRow * 16, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->view_rows_sent, c->stream));
+  return PTMI_OK;
+}
+
+// One device's part of ptmi_render_views: render_one's loop over batches of at most F frame slots, the slots being the call's n_views x frames_per_view.
+static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t fpv, int reset) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();  // a stale error of an earlier, already reported failure must not be blamed on this call
+  int r = prepare_scene(c);
+  if (r) return r;
+  r = check_renderable(c);
+  if (r) return r;
+  // the stack and the table: allocated before anything is enqueued
+  const size_t image_bytes = (size_t)c->W * (size_t)c->H * 16;
+  const bool fresh = !c->d_views.p || c->n_views != n_views;
+  if (fresh) {  // the new stack first: a call that fails for want of memory leaves the old images as they were
+    DBuf stack;
+    HIP_TRY(c, stack.ensure(image_bytes * n_views));
+    c->d_views = std::move(stack);
+    c->n_views = 0;  // (until it is zeroed, below)
+  }
+  r = stage_view_rows(c, views16, n_views);
+  if (r) return r;
   if (fresh) {
     HIP_TRY(c, hipMemsetAsync(c->d_views.p, 0, image_bytes * n_views, c->stream));
     c->n_views = n_views;
   }
-  HIP_TRY(c, hipMemcpyAsync(c->d_view_rows.p, c->h_view_rows, row_bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipEventRecord(c->view_rows_sent, c->stream));
+  r = send_view_rows(c, n_views);
+  if (r) return r;
   // (the same budget of frame slots per wavefront pass as render_one's, and the same halving)
   const size_t npix = std::max<size_t>(1, count_local((uint32_t)c->W * (uint32_t)c->H, c->rank, c->world, c->tile));
   uint32_t F = c->prm.frames_in_flight > 0 ? (uint32_t)c->prm.frames_in_flight : (uint32_t)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)1 << c->tun.path_budget_log2) / npix));
@@ -1923,11 +1966,11 @@ static int check_view(ptmi_ctx* c, const char* who, uint32_t view) {
   return PTMI_OK;
 }
 
-// ptmi_read_framebuffer (view < 0) / ptmi_read_view: the image, gathered from the devices of a multi-device context, copied to the host
-static int read_image(ptmi_ctx* c, int view, float* dst, size_t bytes) {
+// ptmi_read_framebuffer / ptmi_read_view / ptmi_read_aov: the image, gathered from the devices of a multi-device context, copied to the host
+static int read_image(ptmi_ctx* c, ImageRef img, float* dst, size_t bytes) {
   HIP_TRY(c, hipSetDevice(c->device));
   float4* src = nullptr;
-  int r = gather_framebuffer(c, &src, view);  // multi-device: the one reduce of the render (RCCL over xGMI); else the image itself
+  int r = gather_framebuffer(c, &src, img);  // multi-device: the one reduce of the render (RCCL over xGMI); else the image itself
   if (r) return r;
   HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1938,13 +1981,13 @@ static int read_image(ptmi_ctx* c, int view, float* dst, size_t bytes) {
     return check_queue_overflow(q);
   });
 }
-// ptmi_resolve_rgba8 (view < 0) / ptmi_resolve_view_rgba8: the display pass on the gathered image
-static int resolve_image(ptmi_ctx* c, int view, float frame_num, uint8_t* dst, size_t bytes) {
+// ptmi_resolve_rgba8 / ptmi_resolve_view_rgba8: the display pass on the gathered image
+static int resolve_image(ptmi_ctx* c, ImageRef img, float frame_num, uint8_t* dst, size_t bytes) {
   const size_t npix = (size_t)c->W * c->H;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, c->d_scratch.ensure(bytes));
   float4* src = nullptr;
-  int gr = gather_framebuffer(c, &src, view);
+  int gr = gather_framebuffer(c, &src, img);
   if (gr) return gr;
   hipLaunchKernelGGL(k_resolve_rgba8, dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, src, (uint32_t)npix, frame_num,
                      c->d_scratch.as<uchar4>());
@@ -1958,14 +2001,14 @@ int ptmi_read_view(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) {
   if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_view: null argument");
   if (int r = check_view(c, "ptmi_read_view", view)) return r;
   if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_view: bytes != W*H*16");
-  return read_image(c, (int)view, dst, bytes);
+  return read_image(c, ImageRef{IMG_VIEWS, view}, dst, bytes);
 }
 
 int ptmi_resolve_view_rgba8(ptmi_ctx* c, uint32_t view, float frame_num, uint8_t* dst, size_t bytes) {
   if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_view_rgba8: null argument");
   if (int r = check_view(c, "ptmi_resolve_view_rgba8", view)) return r;
   if (bytes != (size_t)c->W * c->H * 4) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_view_rgba8: bytes != W*H*4");
-  return resolve_image(c, (int)view, frame_num, dst, bytes);
+  return resolve_image(c, ImageRef{IMG_VIEWS, view}, frame_num, dst, bytes);
 }
 
 int ptmi_views_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
@@ -1987,6 +2030,100 @@ int ptmi_release_views(ptmi_ctx* c) {
     q->n_views = 0;
     return PTMI_OK;
   });
+}
+
+// ---- the feature stack (ptmi_render_aov) ----
+// One device's part of ptmi_render_aov: the stack and the view table first, then one k_aov launch — one per batch of views where views x owned pixels would reach 2^31.
+static int render_aov_one(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t fpv, int reset) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();  // a stale error of an earlier, already reported failure must not be blamed on this call
+  int r = prepare_scene(c);
+  if (r) return r;
+  r = check_renderable(c);
+  if (r) return r;
+  const size_t image_bytes = (size_t)c->W * (size_t)c->H * 16;
+  const bool fresh = !c->d_aov.p || c->n_aov_views != n_views;
+  DBuf stack;  // the new stack first: a call that fails for want of memory leaves the old images as they were
+  if (fresh) HIP_TRY(c, stack.ensure(image_bytes * 3 * n_views));
+  r = stage_view_rows(c, views16, n_views);
+  if (r) return r;
+  const RenderConst rc = make_render_const(c, views16, first_frame, (int)fpv, reset ? 1 : 0);
+  const StackLayout st = stack_layout(c, 0);
+  HIP_TRY(c, c->d_spill.ensure(std::max<size_t>(16, (size_t)c->num_cus * 32 * (size_t)st.spill_entries * 64 * sizeof(int2))));  // (k_bvh's and k_tail's rows: one size for all)
+  if (fresh) {
+    c->d_aov = std::move(stack);
+    c->n_aov_views = n_views;
+    HIP_TRY(c, hipMemsetAsync(c->d_aov.p, 0, image_bytes * 3 * n_views, c->stream));
+  }
+  r = send_view_rows(c, n_views);
+  if (r) return r;
+  if (rc.n_local == 0) return PTMI_OK;
+  const ViewTab vt{c->d_view_rows.as<float4>(), 0u, fpv, rc.n_local};
+  const auto aov = with_flags([](auto na) { return &k_aov<na>; }, st.noabort);
+  const uint32_t per_launch = std::max<uint32_t>(1u, 0x7fffffffu / rc.n_local);
+  for (uint32_t v0 = 0; v0 < n_views; v0 += per_launch) {
+    const uint32_t nv = std::min(per_launch, n_views - v0);
+    const uint64_t waves = ((uint64_t)nv * rc.n_local + 63) / 64;
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(waves, (uint64_t)c->num_cus * 32));  // (at most as many blocks as d_spill has rows)
+    hipLaunchKernelGGL(aov, dim3(grid), dim3(64), st.lds_bytes, c->stream, c->S, rc, vt, c->d_aov.as<float4>(), v0, nv, reset ? 1 : 0, c->prm.stack_size, st.lds_entries,
+                       st.spill_entries, c->d_spill.as<int2>());
+    HIP_TRY(c, hipGetLastError());
+  }
+  return PTMI_OK;
+}
+
+int ptmi_render_aov(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t frames_per_view, int reset) {
+  if (!c || !views16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_aov: null argument");
+  if (n_views == 0 || frames_per_view == 0) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_aov: need n_views >= 1 and frames_per_view >= 1");
+  if ((uint64_t)n_views * frames_per_view > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_aov: n_views * frames_per_view must stay below 2^31");
+  return on_all_devices(c, [=](ptmi_ctx* q) { return render_aov_one(q, views16, n_views, first_frame, frames_per_view, reset); }, true);
+}
+
+int ptmi_read_aov(ptmi_ctx* c, uint32_t view, int layer, float* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_aov: null argument");
+  if (!c->d_aov.p || c->n_aov_views == 0) return fail(c, PTMI_ERR_STATE, "ptmi_read_aov: no feature stack: call ptmi_render_aov first");
+  if (view >= c->n_aov_views) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_aov: view " + std::to_string(view) + " of " + std::to_string(c->n_aov_views));
+  if (layer < 0 || layer > 2) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_aov: layer " + std::to_string(layer) + " of 3");
+  if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_aov: bytes != W*H*16");
+  return read_image(c, ImageRef{IMG_AOV, (size_t)view * 3 + (size_t)layer}, dst, bytes);
+}
+
+int ptmi_aov_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
+  if (!c || !p) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_aov_device_ptr: null argument");
+  if (!c->peers.empty()) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_aov_device_ptr: a multi-device context has one stack per GPU; use ptmi_read_aov");
+  if (!c->d_aov.p || c->n_aov_views == 0) return fail(c, PTMI_ERR_STATE, "ptmi_aov_device_ptr: no feature stack: call ptmi_render_aov first");
+  *p = c->d_aov.p;
+  if (bytes) *bytes = (size_t)c->n_aov_views * 3 * c->W * c->H * 16;
+  if (n_views) *n_views = c->n_aov_views;
+  return PTMI_OK;
+}
+
+int ptmi_release_aov(ptmi_ctx* c) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  return on_all_devices(c, [](ptmi_ctx* q) -> int {
+    HIP_TRY(q, hipSetDevice(q->device));
+    HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still write a stack that is about to go
+    q->d_aov.release();
+    q->n_aov_views = 0;
+    return PTMI_OK;
+  });
+}
+
+int ptmi_camera_rays(ptmi_ctx* c, const float* view16, uint32_t frame, float* rays6, uint32_t* rng_out) {
+  if (!c || !view16 || !rays6 || !rng_out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_camera_rays: null argument");
+  if (c->W <= 0) return fail(c, PTMI_ERR_STATE, "ptmi_camera_rays: no image size: call ptmi_resize first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const RenderConst rc = make_render_const(c, view16, frame, 1, 0);
+  const size_t n = rc.npix;
+  HIP_TRY(c, c->d_scratch.ensure(n * 28));
+  float* d_rays = c->d_scratch.as<float>();
+  uint32_t* d_rng = reinterpret_cast<uint32_t*>(d_rays + 6 * n);
+  hipLaunchKernelGGL(k_camera_rays, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, rc, d_rays, d_rng);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(rays6, d_rays, n * 24, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(rng_out, d_rng, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return PTMI_OK;
 }
 
 static int synchronize_one(ptmi_ctx* c) {
@@ -2016,7 +2153,7 @@ int ptmi_read_framebuffer(ptmi_ctx* c, float* dst, size_t bytes) {
   if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_framebuffer: null argument");
   if (!c->fb) return fail(c, PTMI_ERR_STATE, "ptmi_read_framebuffer: no framebuffer");
   if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_framebuffer: bytes != W*H*16");
-  return read_image(c, -1, dst, bytes);
+  return read_image(c, ImageRef{}, dst, bytes);
 }
 
 int ptmi_reduce_framebuffer(ptmi_ctx* c) {
@@ -2090,7 +2227,7 @@ int ptmi_resolve_rgba8(ptmi_ctx* c, float frame_num, uint8_t* dst, size_t bytes)
   if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_rgba8: null argument");
   if (!c->fb) return fail(c, PTMI_ERR_STATE, "ptmi_resolve_rgba8: no framebuffer");
   if (bytes != (size_t)c->W * c->H * 4) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_rgba8: bytes != W*H*4");
-  return resolve_image(c, -1, frame_num, dst, bytes);
+  return resolve_image(c, ImageRef{}, frame_num, dst, bytes);
 }
 
 int ptmi_set_counters(ptmi_ctx* c, int on) {

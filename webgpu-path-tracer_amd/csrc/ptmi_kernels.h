@@ -1326,6 +1326,112 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void
   tail_body<false, COUNT, false, NOABORT, true>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, vt);
 }
 
+// k_aov — the feature pass (ptmi_render_aov): what the FIRST hitScene call of every frame's path sees, and nothing after it.  No queues, no path state, no
+// k_accumulate: a lane owns one (view, owned pixel) of the launch's views, runs the view's frames in frame order — the frame's first camera ray as k_generate_views
+// makes it (sample 0 of pathTrace, the jitter draws leave the RNG state hit_volume then consumes), hitScene part 1, the tree walk of k_tail on per-lane LDS stacks
+// where the root box was entered, resolve_hit — and keeps the three images' values of its pixel in registers: one read-modify-write per call, not one per frame.
+// The images of view v are stack[3 v + 0 .. 2], npix float4 each: {sum normal.xyz, sum t}, {sum material.color.xyz, frames that hit}, and — not summed, the
+// call's last frame stays — {kind (0 miss, 1 sphere, 2 quad, 3 triangle), primitive index, material index, front_face} as f32 VALUES, so that a multi-device
+// context's f32 sum with the other devices' zeros leaves them alone.  A miss adds +0.0 and writes (0,0,0,0).
+// Primary rays of neighbouring pixels are coherent: a wave's 64 lanes are 64 neighbouring pixels of one view, and the walk has neither refill nor parking.
+// Waves per SIMD from the register count (tools/kernel_resources.sh): 123 VGPRs without scratch as the compiler allocates it — 4 waves; held to 96 (5 waves) it
+// spills 48 bytes, to 80 (6 waves) 96-112.  4 it is until a run shows a spilling build ahead (-DPTMI_AOV_WAVES=5 builds one: tools/aov_probe.py); the LDS stacks
+// (5 KB per wave at the default 10 entries) admit 32 waves per CU, so the registers alone decide.
+template <bool NOABORT>
+#ifndef PTMI_AOV_WAVES
+#define PTMI_AOV_WAVES 4
+#endif
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PTMI_AOV_WAVES, 8))) void k_aov(DevScene S, RenderConst rc, ViewTab vt, float4* __restrict__ stack, uint32_t view0, uint32_t n_views, int reset, int stack_size,
+                                            int lds_entries, int spill_entries, int2* __restrict__ spill) {
+  extern __shared__ int lds_stack[];
+  const int lane = lane_id();
+  LaneStack2 stk;
+  stk.lds = (lds_v2i_t*)lds_stack + lane;
+  stk.spill = spill + (size_t)blockIdx.x * (size_t)spill_entries * 64 + lane;
+  stk.lds_entries = lds_entries;
+  Counters cn = {0, 0, 0, 0, 0};  // (never reported: the pass leaves ptmi_stats alone)
+  const uint32_t root = __float_as_uint(S.root_lo.w);
+  const uint32_t root_node = (root & REF_LEAF) ? root : (root & REF_IDX);
+  const uint32_t work = n_views * rc.n_local;  // (the host keeps a launch's views x owned pixels below 2^31)
+  Stopwatch sw;
+  sw.begin();
+#pragma unroll 1
+  for (uint32_t w0 = blockIdx.x * 64u; w0 < work; w0 += gridDim.x * 64u) {
+    // (a lane past the end repeats the last item and stores nothing: the wave stays converged for the walk's votes)
+    const bool mine = w0 + (uint32_t)lane < work;
+    const uint32_t item = min(w0 + (uint32_t)lane, work - 1u);
+    const uint32_t vl = item / rc.n_local, j = item - vl * rc.n_local;
+    const uint32_t pix = local_to_pixel(rc, j);
+    float px, py;
+    camera_pixel(rc, pix, px, py);
+    const ViewRow vr = load_view_row(vt, view0 + vl);
+    float4* const img = stack + (size_t)(view0 + vl) * 3u * rc.npix + pix;
+    float4 nd = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ac = nd, ids = nd;
+    if (!reset) nd = img[0], ac = img[rc.npix];
+#pragma unroll 1
+    for (uint32_t f = 0; f < vt.fpv; f++) {
+      // u32(uniforms.frameNum): the frame number travels through an f32 uniform (renderer.js:173)
+      uint32_t rng = pix + (uint32_t)(float)(rc.frame0 + f) * 719393u;
+      float a, b;
+      camera_plane(rc, px, py, 0, rng, a, b);
+      const f3 d = camera_dir(vr.m, -rc.fov_factor, a, b), o = vr.o;
+      float2 tp;
+      uint32_t hm;
+      prims_for_ray<false>(S, o, d, rng, tp, hm, cn);
+      float2 uv = make_float2(0.0f, 0.0f);
+      const bool flagged = (hm & HITMAT_BVH) != 0u;
+      if (__ballot(flagged) != 0ull) {  // hitScene part 2 (hitRay.wgsl:42-110), as k_tail walks it
+        Walk w = {flagged ? root_node : N_DONE, 0, tp.x, {0.0f, 0.0f, 0u, 0u}};
+        WalkRay ray = make_walk_ray(S, o, d);
+#pragma unroll 1
+        for (;;) {
+          if (__ballot(w.node != N_DONE) == 0ull) break;
+          if ((int)w.node < 0) walk_leaf<false>(S, ray, stk, w, cn, sw);
+          if (w.node < N_INNER_LIMIT) walk_inner<false, NOABORT, TB_WALK_FETCH>(S, ray, stk, w, stack_size, cn, sw);
+        }
+        if (w.hit.prim != 0u) {  // a triangle beat what part 1 had found
+          tp = make_float2(w.ct, __uint_as_float(w.hit.prim));
+          uv = make_float2(w.hit.u, w.hit.v);
+          hm = w.hit.mat;
+        }
+      }
+      const uint32_t prim = __float_as_uint(tp.y), kind = prim >> 28;
+      float4 hn = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ha = hn;  // a miss adds +0.0
+      ids = hn;
+      if (kind != K_NONE) {
+        const uint32_t mat = hm & HITMAT_ID;
+        const float4 col = S.mats[4 * (size_t)mat];
+        const HitGeom g = resolve_hit(S, o, d, tp.x, tri_fetch_uv(S, uv, prim), prim);
+        hn = make_float4(g.n.x, g.n.y, g.n.z, tp.x);
+        ha = make_float4(col.x, col.y, col.z, 1.0f);
+        ids = make_float4(kind == K_TRI ? 3.0f : kind == K_QUAD ? 2.0f : 1.0f, (float)(prim & 0x0fffffffu), (float)mat, g.front ? 1.0f : 0.0f);
+      }
+      if (f == 0u && reset) {  // main.wgsl:22-27 with resetBuffer = 1
+        nd = hn, ac = ha;
+      } else {
+        nd = make_float4(nd.x + hn.x, nd.y + hn.y, nd.z + hn.z, nd.w + hn.w);
+        ac = make_float4(ac.x + ha.x, ac.y + ha.y, ac.z + ha.z, ac.w + ha.w);
+      }
+    }
+    if (mine) img[0] = nd, img[rc.npix] = ac, img[2 * (size_t)rc.npix] = ids;
+  }
+}
+
+// Test hook (ptmi_camera_rays): the first camera ray of frame rc.frame0 for EVERY pixel, whatever the shard — seed, jitter draws and view transform by the device
+// functions k_generate calls — and the RNG state its hitScene starts with.
+__global__ __launch_bounds__(kBlock) void k_camera_rays(RenderConst rc, float* __restrict__ rays6, uint32_t* __restrict__ rng_out) {
+  const uint32_t pix = blockIdx.x * kBlock + threadIdx.x;
+  if (pix >= rc.npix) return;
+  float px, py;
+  camera_pixel(rc, pix, px, py);
+  uint32_t rng = pix + (uint32_t)(float)rc.frame0 * 719393u;
+  f3 o, d;
+  camera_ray_at(rc, px, py, 0, rng, o, d);
+  float* r = rays6 + 6 * (size_t)pix;
+  r[0] = o.x, r[1] = o.y, r[2] = o.z, r[3] = d.x, r[4] = d.y, r[5] = d.z;
+  rng_out[pix] = rng;
+}
+
 // A batch's step records: every queue but step 0's starts behind its carry prefix (Carry)
 __global__ void k_init_ctl(StepCtl* __restrict__ ctl, int n, uint32_t resv) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);

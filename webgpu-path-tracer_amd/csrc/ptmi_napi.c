@@ -40,6 +40,9 @@ FN(ptmi_render_views)
 FN(ptmi_read_view)
 FN(ptmi_resolve_view_rgba8)
 FN(ptmi_release_views)
+FN(ptmi_render_aov)
+FN(ptmi_read_aov)
+FN(ptmi_release_aov)
 FN(ptmi_synchronize)
 FN(ptmi_read_framebuffer)
 FN(ptmi_write_framebuffer)
@@ -88,7 +91,7 @@ static int load_lib(char* err, size_t errlen) {
   }
   LOAD(ptmi_version) LOAD(ptmi_last_error) LOAD(ptmi_create) LOAD(ptmi_create_multi) LOAD(ptmi_prepare) LOAD(ptmi_destroy) LOAD(ptmi_default_params) LOAD(ptmi_set_params)
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
-  LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
+  LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
   LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah)
   LOAD(ptmi_obj_parse) LOAD(ptmi_free) LOAD(ptmi_device_count) LOAD(ptmi_reduce_info)
   return 0;
@@ -459,6 +462,59 @@ static napi_value js_release_views(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* renderAov(ctx, Float32Array(V*16), nViews, firstFrame, framesPerView, reset): the feature pass (ptmi_render_aov; the reference renders colour only) — view v's
+ * three layers of the context's feature stack receive what the first hit of each of view v's frames saw */
+static napi_value js_render_aov(napi_env env, napi_callback_info info) {
+  napi_value a[6];
+  if (get_args(env, info, 6, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  void* data;
+  size_t len;
+  if (typed(env, a[1], napi_float32_array, "renderAov(views)", &data, &len)) return NULL;
+  uint32_t n_views, first, fpv;
+  CHECK_NAPI(napi_get_value_uint32(env, a[2], &n_views));
+  CHECK_NAPI(napi_get_value_uint32(env, a[3], &first));
+  CHECK_NAPI(napi_get_value_uint32(env, a[4], &fpv));
+  if (n_views == 0 || len / 16 != n_views || len % 16 != 0) {
+    napi_throw_range_error(env, NULL, "renderAov: views must hold 16 floats for each of the nViews views, one view at least");
+    return NULL;
+  }
+  bool reset = false;
+  napi_coerce_to_bool(env, a[5], &a[5]);
+  napi_get_value_bool(env, a[5], &reset);
+  int st = p_ptmi_render_aov(c, (const float*)data, n_views, first, fpv, reset ? 1 : 0);
+  if (st) return throw_status(env, c, st, "ptmi_render_aov");
+  return NULL;
+}
+
+static napi_value js_read_aov(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (get_args(env, info, 4, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  uint32_t view;
+  int32_t layer;
+  CHECK_NAPI(napi_get_value_uint32(env, a[1], &view));
+  CHECK_NAPI(napi_get_value_int32(env, a[2], &layer));
+  void* data;
+  size_t len;
+  if (typed(env, a[3], napi_float32_array, "readAov(out)", &data, &len)) return NULL;
+  int st = p_ptmi_read_aov(c, view, layer, (float*)data, len * 4);
+  if (st) return throw_status(env, c, st, "ptmi_read_aov");
+  return a[3];
+}
+
+static napi_value js_release_aov(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (get_args(env, info, 1, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  int st = p_ptmi_release_aov(c);
+  if (st) return throw_status(env, c, st, "ptmi_release_aov");
+  return NULL;
+}
+
 static napi_value js_synchronize(napi_env env, napi_callback_info info) {
   napi_value a[1];
   if (get_args(env, info, 1, a)) return NULL;
@@ -743,7 +799,7 @@ static napi_value init(napi_env env, napi_value exports) {
   } fns[] = {
       {"version", js_version}, {"create", js_create}, {"destroy", js_destroy}, {"defaultParams", js_default_params}, {"setParams", js_set_params},
       {"upload", js_upload}, {"resize", js_resize}, {"clear", js_clear}, {"setShard", js_set_shard}, {"renderFrame", js_render_frame},
-      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
+      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
       {"resolveRGBA8", js_resolve}, {"setCounters", js_set_counters}, {"setTiming", js_set_timing}, {"stats", js_stats},
       {"resetStats", js_reset_stats}, {"buildBVH", js_build_bvh}, {"buildBVHSAH", js_build_bvh_sah}, {"buildBVHDevice", js_build_bvh_device}, {"parseObj", js_parse_obj},
       {"deviceCount", js_device_count}, {"reduceInfo", js_reduce_info},

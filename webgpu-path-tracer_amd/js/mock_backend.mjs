@@ -8,5 +8,8 @@ export class MockBackend {
   writeFramebuffer() { this.calls.push(['writeFramebuffer']); }
   renderFrame(u) { this.frames.push(Array.from(u)); this.calls.push(['renderFrame', u[2], u[3]]); }
   resolveRGBA8(fn, out) { this.calls.push(['resolve', fn]); return out || new Uint8Array(this.width * this.height * 4); }
+  renderAov(views, nViews, firstFrame, framesPerView, reset = true) { this.calls.push(['renderAov', nViews, firstFrame, framesPerView, !!reset]); }
+  readAov(view, layer, out) { this.calls.push(['readAov', view, layer]); return out || new Float32Array(this.width * this.height * 4); }
+  releaseAov() { this.calls.push(['releaseAov']); }
   synchronize() {}
 }

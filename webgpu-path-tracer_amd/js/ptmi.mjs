@@ -36,6 +36,11 @@ export class Ptmi {
   readView(v, out = new Float32Array(this.width * this.height * 4)) { return this.native.readView(this.h, v, out); }
   resolveViewRGBA8(v, frameNum, out = new Uint8Array(this.width * this.height * 4)) { return this.native.resolveViewRGBA8(this.h, v, frameNum, out); }
   releaseViews() { this.native.releaseViews(this.h); }
+  // The feature pass (ptmi_render_aov): views = Float32Array(nViews * 16) as for renderViews; per view three layers of width x height float4 — 0: normal sum + depth sum,
+  // 1: albedo sum + hit count, 2: kind / primitive index / material index / front_face of the call's last frame — of what the first hit of every frame's path saw.
+  renderAov(views, nViews, firstFrame, framesPerView, reset = true) { this.native.renderAov(this.h, views, nViews, firstFrame, framesPerView, reset); }
+  readAov(view, layer, out = new Float32Array(this.width * this.height * 4)) { return this.native.readAov(this.h, view, layer, out); }
+  releaseAov() { this.native.releaseAov(this.h); }
   synchronize() { this.native.synchronize(this.h); }
   prepare() { this.native.prepare(this.h); }
   buildSceneBVHSAH() { this.native.buildSceneBVHSAH(this.h); }   // the same with the reference's never-called SAH builder (lib/BVH/bvhNode.js:108-283): opt-in

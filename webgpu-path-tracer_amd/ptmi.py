@@ -21,6 +21,7 @@ SYMBOLS = [
     "ptmi_build_bvh_sah", "ptmi_build_bvh_device", "ptmi_build_scene_bvh", "ptmi_read_scene_buffer", "ptmi_obj_parse", "ptmi_free",
     "ptmi_device_count", "ptmi_reduce_info", "ptmi_reload_tuning", "ptmi_build_scene_bvh_sah", "ptmi_scene_bvh_info", "ptmi_build_bvh_sah_device",
     "ptmi_render_views", "ptmi_read_view", "ptmi_resolve_view_rgba8", "ptmi_views_device_ptr", "ptmi_release_views",
+    "ptmi_render_aov", "ptmi_read_aov", "ptmi_aov_device_ptr", "ptmi_release_aov", "ptmi_camera_rays",
 ]
 
 
@@ -134,6 +135,12 @@ def load_library(build=False, path=None):
         L.ptmi_resolve_view_rgba8.argtypes = [vp, u32, ctypes.c_float, fp, sz]
         L.ptmi_views_device_ptr.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(u32)]
         L.ptmi_release_views.argtypes = [vp]
+    if hasattr(L, "ptmi_render_aov"):  # (an older A/B build loaded through PTMI_LIB has no feature pass)
+        L.ptmi_render_aov.argtypes = [vp, fp, u32, u32, u32, i32]
+        L.ptmi_read_aov.argtypes = [vp, u32, i32, fp, sz]
+        L.ptmi_aov_device_ptr.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(u32)]
+        L.ptmi_release_aov.argtypes = [vp]
+        L.ptmi_camera_rays.argtypes = [vp, fp, u32, fp, fp]
     if explicit:
         _libs[path] = L
     else:
@@ -307,6 +314,40 @@ class Context:
 
     def release_views(self):
         self._ck(self.lib.ptmi_release_views(self.h))
+
+    def render_aov(self, views, first_frame, frames_per_view, reset=True):
+        """The feature pass (ptmi_render_aov): `views` is (V, 16) float32 as for render_views; view v's three layers of the context's feature stack receive
+        the first hits of frames first_frame .. first_frame + frames_per_view - 1.  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        self._ck(self.lib.ptmi_render_aov(self.h, _ptr(v), v.shape[0], first_frame, frames_per_view, 1 if reset else 0))
+
+    def read_aov(self, view, layer=None):
+        """Layer `layer` of view `view` of the feature stack as (H, W, 4) float32 — 0: normal sum + depth sum, 1: albedo sum + hit count, 2: kind, primitive
+        index, material index, front_face — or, with layer=None, all three as (3, H, W, 4)."""
+        layers = range(3) if layer is None else [layer]
+        out = np.empty((len(layers), self.height, self.width, 4), np.float32)
+        for k, l in enumerate(layers):
+            self._ck(self.lib.ptmi_read_aov(self.h, view, l, _ptr(out[k]), out[k].nbytes))
+        return out if layer is None else out[0]
+
+    def aov_device_ptr(self):
+        """(device pointer, bytes, n_views) of the feature stack: one contiguous [n_views][3][H][W][4] float32 array (single-device contexts)."""
+        p, n, v = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_uint32()
+        self._ck(self.lib.ptmi_aov_device_ptr(self.h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(v)))
+        return p.value, n.value, v.value
+
+    def release_aov(self):
+        self._ck(self.lib.ptmi_release_aov(self.h))
+
+    def camera_rays(self, view16, frame):
+        """Test hook (ptmi_camera_rays): (rays (W*H, 6) float32, rng (W*H,) uint32) — the first camera ray of `frame` for every pixel and the RNG state its
+        hitScene starts with."""
+        v = np.ascontiguousarray(view16, np.float32)
+        assert v.size == 16
+        n = self.width * self.height
+        rays, rng = np.empty((n, 6), np.float32), np.empty(n, np.uint32)
+        self._ck(self.lib.ptmi_camera_rays(self.h, _ptr(v), frame, _ptr(rays), _ptr(rng)))
+        return rays, rng
 
     def synchronize(self):
         self._ck(self.lib.ptmi_synchronize(self.h))
