@@ -166,13 +166,27 @@ def test_closed_white_box_energy(pkg, oracle):
 
 
 def test_fractional_pixel_y_quirk(pkg, oracle):
-    """Q1: pixelCoords.y = idx / W is not floored -> rows are sheared by up to one pixel; the last pixel
-    of a row sees (almost) the same direction as the first pixel of the next row in y."""
+    """Q1: pixelCoords.y = idx / W is not floored -> every row is sheared by up to one pixel.  One path per pixel, one bounce, over an emissive quad
+    in front of the camera: a pixel is lit iff its first hit is the quad, and the pixels where the shear moves that hit across the quad's edge
+    must be the ones the independent float64 reading (oracle/ptm_ref64.py) predicts; a reading that floors idx / W lights other pixels."""
+    from oracle import ptm_ref64
+
     b = _empty()
-    # a quad light far away, seen through a pinhole-like background contrast: use plain background instead;
-    # check through the RNG-free part: two renders that differ only in W have different py for pixel (x=0,y=1)
-    fb_a, _ = oracle.render(b, 4, 4, cornell_view(pkg), 1, 1)
-    assert fb_a.shape == (4, 4, 4)
+    # Quad(Q=(-0.6,-0.4,0), u=(1.2,0,0), v=(0,0.8,0)): normal +z towards the camera at z = 2.5, D = 0, w = n / (n.n)
+    b["quads"] = np.array([-0.6, -0.4, 0, -1, 1.2, 0, 0, 0, 0, 0.8, 0, 0, 0, 0, 1, 0, 0, 0, 1 / 0.96, 0], np.float32)
+    b["materials"] = np.array(_mat(0, emission=(3, 3, 3)), np.float32)
+    W, H = 24, 16
+    view = cornell_view(pkg)
+    fb, _ = oracle.render(b, W, H, view, 1, 1, max_bounces=1)
+    ref, margin = ptm_ref64.render(b, W, H, view, 1, 1, max_bounces=1)
+    floored, fmargin = ptm_ref64.render(b, W, H, view, 1, 1, max_bounces=1, floor_pixel_y=True)
+    decided = (margin >= 2.0 ** -20) & (fmargin >= 2.0 ** -20)
+    lit, want, other = fb[..., 0] > 0, ref[..., 0] > 0, floored[..., 0] > 0
+    assert decided.mean() > 0.95 and want[decided].any() and not want[decided].all()
+    assert np.array_equal(lit[decided], want[decided])
+    moved = decided & (want != other)  # where the shear carries the first hit across the quad's edge
+    assert moved.sum() >= 4
+    assert np.array_equal(lit[moved], want[moved]) and not np.array_equal(lit[moved], other[moved])
 
 
 def test_shard_union_equals_full_render(pkg, oracle):
