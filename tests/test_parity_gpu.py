@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import assert_same_bits, cornell_view
+from full_frames import whole_frame_with_counters
 
 pytestmark = pytest.mark.gpu
 
@@ -340,26 +341,18 @@ def test_resolve_rgba8(ctx, pkg, oracle):
         assert np.array_equal(ctx.resolve_rgba8(frame_num), oracle.resolve_rgba8(sweep, frame_num)), frame_num
 
 
-def _full_size_windows(ctx, oracle, b, view, W, H, frames, params, label):
-    """The scene at a BASELINE configuration's FULL resolution against the oracle on 6000-pixel windows of the image: one across the
-    middle (through the mesh), one in the last rows (the largest pixel indices: `f32(pixelIndex) % W`, `/ W` of main.wgsl:3-5, Q1,
-    and the largest path ids), one at the very start.  The whole frame is rendered (frames_in_flight auto); counters are not compared
-    (the oracle sees only the windows)."""
-    ctx.set_params(**params)
-    ctx.resize(W, H)
-    ctx.reset_stats()
-    ctx.render(view, 1, frames)
-    got = ctx.read_framebuffer().reshape(-1, 4)
-    st = ctx.stats()
-    assert st["paths"] == W * H * frames and st["frames"] == frames
-    assert (got[:, 3] == 1.0).all()
-    for p0 in ((H // 2) * W + W // 3, W * H - 6000, 0):
-        want, _ = oracle.render(b, W, H, view, 1, frames, pixel_range=(p0, p0 + 6000), **_oracle_params(params))
-        assert_same_bits(got[p0 : p0 + 6000], want.reshape(-1, 4)[p0 : p0 + 6000], "%s %dx%d window at pixel %d" % (label, W, H, p0))
+def _full_size_frame(ctx, oracle, pipeline, b, view, W, H, frames, params, label):
+    """The scene at a BASELINE configuration's FULL resolution, the whole frame against the oracle (computed once per session and label): every pixel and
+    the seven work counters from the counted kernels, every pixel and rays / paths from the uncounted ones, in one batch (frames_in_flight auto) of enough
+    frames to cross the library's default thresholds — more paths than k_tail takes whole, a tree and a batch at which k_bvh carries rays over —, the route
+    asserted from the launch statistics: full_frames.whole_frame_with_counters.  (Until this helper compared whole frames it compared 6000-pixel windows
+    across the middle, in the last rows — the largest pixel indices: `f32(pixelIndex) % W`, `/ W` of main.wgsl:3-5, Q1, and the largest path ids — and at
+    the very start, without counters.)"""
+    whole_frame_with_counters(ctx, oracle, pipeline, b, view, W, H, frames, params, label)
     ctx.resize(64, 64)  # give the frame-sized buffers back
 
 
-def test_dragon_class_scene_bit_exact(ctx, pkg, oracle):
+def test_dragon_class_scene_bit_exact(ctx, pkg, oracle, pipeline):
     """BASELINE configs[2] geometry (871,414 triangles, BVH depth 20, stack_size 24) at reduced resolution."""
     b = pkg.scenes.c3_scene().buffers(native=pkg.ptmi.NativeHost())
     assert b["triangles"].size // 24 == 871414 and b["bvh"].size // 12 == 2 * 871414 - 1
@@ -378,15 +371,15 @@ def test_dragon_class_scene_bit_exact(ctx, pkg, oracle):
         assert_same_bits(got, want, "c3 stack %d" % stack)
         for k in ("rays", "node_visits", "tri_tests", "quad_tests", "mat_fetches"):
             assert st[k] == ost[k], (stack, k)
-    # configs[2] itself at its full image size: the 871,414-triangle scene, 1920x1080, stack_size 24, three oracle windows of 6000 pixels
-    _full_size_windows(ctx, oracle, b, view, 1920, 1080, 3, dict(max_bounces=8, stack_size=24), "configs[2] (871,414 triangles) at 1080p")
+    # configs[2] itself at its full image size: the 871,414-triangle scene, 1920x1080, stack_size 24, the whole frame; 4 frames = 8.29 M paths in the batch
+    _full_size_frame(ctx, oracle, pipeline, b, view, 1920, 1080, 4, dict(max_bounces=8, stack_size=24), "configs[2] (871,414 triangles) at 1080p")
 
 
 @pytest.mark.parametrize("name,cam,params", [
     ("c4", "interior", dict(max_bounces=8, stack_size=24)),  # BASELINE configs[3]: sponza-class interior, camera inside
     ("c5", "cornell", dict(max_bounces=16, stack_size=24, importance_sampling=1)),  # configs[4]: buddha-class, glass, IS
 ])
-def test_large_procedural_scenes_bit_exact(ctx, pkg, oracle, name, cam, params):
+def test_large_procedural_scenes_bit_exact(ctx, pkg, oracle, pipeline, name, cam, params):
     b = getattr(pkg.scenes, name + "_scene")().buffers(native=pkg.ptmi.NativeHost())
     assert b["triangles"].size // 24 == {"c4": 262267, "c5": 1087716}[name]
     ctx.upload_scene(b)
@@ -403,9 +396,9 @@ def test_large_procedural_scenes_bit_exact(ctx, pkg, oracle, name, cam, params):
     assert_same_bits(got, want, name)
     for k in ("rays", "node_visits", "tri_tests", "quad_tests", "mat_fetches"):
         assert st[k] == ost[k], (name, k)
-    # configs[3] at 1920x1080, configs[4] at 3840x2160 (8.3 M pixels: pixel indices beyond 2^23, 16 bounces, importance sampling)
+    # configs[3] at 1920x1080 x 4 frames, configs[4] at 3840x2160 x 1 frame (8.3 M pixels: pixel indices beyond 2^23, 16 bounces, importance sampling): 8.29 M paths each
     W, H = (3840, 2160) if name == "c5" else (1920, 1080)
-    _full_size_windows(ctx, oracle, b, view, W, H, 3 if name == "c5" else 2, params, "configs[%d]" % (4 if name == "c5" else 3))
+    _full_size_frame(ctx, oracle, pipeline, b, view, W, H, 1 if name == "c5" else 4, params, "configs[%d]" % (4 if name == "c5" else 3))
 
 
 def _collapse_bottom_level(bvh, n_tris):
@@ -485,7 +478,7 @@ def test_reference_default_max_bounces_100(ctx, pkg, oracle):
     assert st["rays"] == ost["rays"] and st["intersect_launches"] < 100  # early exit happened
 
 
-def test_sah_bvh_bit_exact(ctx, pkg, oracle):
+def test_sah_bvh_bit_exact(ctx, pkg, oracle, pipeline):
     """The opt-in SAH builder's trees (deeper, leaves of 1-2 triangles) through the same kernels: both the NOABORT path
     (stack 64 > depth) and the literal stack discipline with the Q7 abort live (stack 20), incl. stack entries beyond the
     10 kept in LDS by default (PTMI_LDS_STACK)."""
@@ -508,7 +501,7 @@ def test_sah_bvh_bit_exact(ctx, pkg, oracle):
         for k in ("rays", "node_visits", "tri_tests", "quad_tests", "mat_fetches"):
             assert st[k] == ost[k], (stack, k)
     # the same 40 k-triangle SAH interior at a full 1920x1080 frame (the image size of configs[2] / [3], not their scenes), stack_size 24
-    _full_size_windows(ctx, oracle, b, view, 1920, 1080, 3, dict(max_bounces=8, stack_size=24), "40 k-triangle SAH interior at 1080p")
+    _full_size_frame(ctx, oracle, pipeline, b, view, 1920, 1080, 4, dict(max_bounces=8, stack_size=24), "40 k-triangle SAH interior at 1080p")
 
 
 def _random_scene(pkg, seed):
@@ -673,11 +666,11 @@ def test_device_sah_builder_is_byte_identical_to_host(ctx, pkg):
         assert a.shape == b.shape and np.array_equal(oa, ob) and np.array_equal(a.view(np.uint32), b.view(np.uint32)), make.__name__
 
 
-def test_scene_sah_bvh_built_on_the_device_is_the_host_pipeline_bit_for_bit(ctx, pkg, oracle):
+def test_scene_sah_bvh_built_on_the_device_is_the_host_pipeline_bit_for_bit(ctx, pkg, oracle, pipeline):
     """ptmi_build_scene_bvh_sah: the whole of Scene.create_bvh(sah=True) on the GPU — boxes, the binned-SAH build, the triangles into leaf order, pair
     records AND the leaf table of the leaves that hold several triangles — against the host pipeline: same rows, same triangle order, same image and
     counters (stack_size above the tree's depth, and 20: the literal stack discipline with the Q7 abort live); then configs[3]'s own scene
-    (262,267 triangles) from its device-built SAH tree at 1920x1080 on oracle windows."""
+    (262,267 triangles) from its device-built SAH tree at 1920x1080, the whole frame with counters."""
     for name, make, view in (("40 k-triangle interior", lambda: pkg.scenes.c4_scene(40000), cornell_view(pkg, "interior")), ("two transformed meshes", lambda: _two_mesh_scene(pkg), cornell_view(pkg))):
         host = make().buffers(native=pkg.ptmi.NativeHost(), sah=True)
         raw = make().buffers_unbuilt()
@@ -708,7 +701,7 @@ def test_scene_sah_bvh_built_on_the_device_is_the_host_pipeline_bit_for_bit(ctx,
     ctx.build_scene_bvh(sah=True)
     info = ctx.scene_bvh_info()
     assert info["nodes"] == host["bvh"].size // 12 and info["depth"] < 40
-    _full_size_windows(ctx, oracle, host, cornell_view(pkg, "interior"), 1920, 1080, 2, dict(max_bounces=8, stack_size=40), "configs[3] from its device-built SAH tree at 1080p")
+    _full_size_frame(ctx, oracle, pipeline, host, cornell_view(pkg, "interior"), 1920, 1080, 4, dict(max_bounces=8, stack_size=40), "configs[3] from its device-built SAH tree at 1080p")
 
 
 def test_render_frame_render_ahead_is_invisible(ctx, pkg, oracle, monkeypatch):
