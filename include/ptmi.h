@@ -237,6 +237,57 @@ int ptmi_aov_device_ptr(ptmi_ctx* ctx, void** dev_ptr, size_t* bytes, uint32_t* 
 /* Frees the feature stack (ptmi_destroy does too; no counterpart in the reference); synchronises. */
 int ptmi_release_aov(ptmi_ctx* ctx);
 
+/* Denoising (no counterpart in the reference, which shows the noisy running mean): an edge-avoiding a-trous filter of view-stack images under the feature
+ * stack's images of the same views — what ptmi_render_aov's layers are for.  Per pixel p of one W x H image, with S the view-stack image (RGBA f32 sums), N, A, I
+ * layers 0, 1, 2 of the feature stack, F = frame_num:
+ *
+ *   prepare   k = A.w;  c = S.rgb / F;  for k > 0: n = N.xyz / k, z = N.w / k, a = A.rgb / k, a' = max(a, albedo_floor) per component, d0 = c / a', m = I.z.
+ *             p is VALID iff k > 0 and every component of c, n, z, a and d0 is finite (and m is no NaN).
+ *   level l = 0 .. levels-1, step s = 2^l, for every valid p: taps q = p + s (i, j), j = -2..2 outer, i = -2..2 inner, skipping q outside the image, invalid q and
+ *             m(q) != m(p); with h = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *               e = |n(q) - n(p)|^2 / sigma_normal^2 + ((z(q) - z(p)) / (sigma_depth (|z(p)| + 1e-6)))^2
+ *                   [+ |d_l(q) - d_l(p)|^2 / (sigma_colour 2^-l)^2 when sigma_colour > 0; absent otherwise]
+ *               w = h_i h_j exp2(-e) (ptm_exp2; a tap whose e is not finite contributes nothing);  num += w d_l(q), den += w;  d_{l+1}(p) = num / den.
+ *             The centre tap always contributes 9/64.  Invalid pixels are carried through unchanged and are never a tap.
+ *   output    MEAN radiance, not sums: valid p: rgb = d_levels a'; invalid p: rgb = S.rgb / F (misses, NaN and inf pixels pass through); alpha = S.a / F everywhere.
+ *
+ * The f32 operation order is fixed in include/ptmi_denoise.h, which the kernels and ptmi_denoise_reference both compile: their results agree bit for bit.
+ * The defaults (ptmi_default_denoise_params: levels 5, sigma_normal 0.25, sigma_depth 0.1, sigma_colour 0 = off, albedo_floor 1e-3) are a starting point. */
+typedef struct ptmi_denoise_params {
+  int32_t levels;      /* 1 .. 6 */
+  float sigma_normal;  /* > 0 */
+  float sigma_depth;   /* > 0, relative to the centre's depth */
+  float sigma_colour;  /* >= 0; 0 = no colour term */
+  float albedo_floor;  /* > 0 */
+  int32_t reserved[3];
+} ptmi_denoise_params;
+void ptmi_default_denoise_params(ptmi_denoise_params* p);
+/* Filters images [first_view, first_view + n_views) of the view stack (ptmi_render_views) with the same images of the feature stack (ptmi_render_aov) into the
+ * context's DENOISED STACK: [n_views of the view stack][H][W][4] f32 in one device allocation, zeroed when this call allocates it; images outside the range keep what
+ * they held.  ptmi_resize and any change of the view stack's size (ptmi_render_views with another n_views, ptmi_release_views) drop it.  params = NULL: the
+ * defaults.  THE CALLER is responsible for both stacks coming from the same views and frames (frame_num = the frames each image of the view stack sums); the
+ * library only checks that they hold the same number of views.  Asynchronous on the context's stream; reads the two stacks and touches neither them, the
+ * accumulation buffer nor any ptmi_stats field.  The views go through each level in one launch (a grid over views) per batch: the filter's scratch, 48 bytes per
+ * pixel and view, is held to 1 GiB (10 views at 1080p), so a call on a large stack does not need another copy of it.
+ * PTMI_ERR_STATE: a stack is missing, or they differ in n_views.  PTMI_ERR_INVALID_ARG: a parameter outside its domain, a range past the stack, frame_num not finite
+ * or not > 0.  PTMI_ERR_NO_MEMORY: before anything is enqueued; the denoised stack the call found stays as it was.  PTMI_ERR_UNSUPPORTED: a multi-device context or
+ * a shard (ptmi_set_shard with world > 1) — a pixel's neighbours live elsewhere; gather the images first (ptmi_read_view / ptmi_read_aov) and use ptmi_denoise_images. */
+int ptmi_denoise_views(ptmi_ctx* ctx, const ptmi_denoise_params* params, float frame_num, uint32_t first_view, uint32_t n_views);
+/* ptmi_read_view's counterpart for image `view` of the denoised stack: synchronises; bytes must be W*H*16. */
+int ptmi_read_denoised(ptmi_ctx* ctx, uint32_t view, float* dst, size_t bytes);
+/* The display pass (ptmi_resolve_rgba8) for image `view` of the denoised stack, at frameNum 1: the stack holds means. */
+int ptmi_resolve_denoised_rgba8(ptmi_ctx* ctx, uint32_t view, uint8_t* dst, size_t bytes);
+/* The denoised stack as one contiguous [n_views][H][W][4] f32 device array (ptmi_views_device_ptr's counterpart); valid until it is dropped (above) or
+ * ptmi_release_denoised.  bytes / n_views may be NULL. */
+int ptmi_denoised_device_ptr(ptmi_ctx* ctx, void** dev_ptr, size_t* bytes, uint32_t* n_views);
+/* Frees the denoised stack and the filter's scratch (ptmi_destroy does too); synchronises. */
+int ptmi_release_denoised(ptmi_ctx* ctx);
+/* The same kernels on host arrays, for images that come from elsewhere: colour_sums [n_images][h][w][4], layers [n_images][3][h][w][4] (the feature stack's layout),
+ * out [n_images][h][w][4], all f32; w and h need not be the context's size.  Synchronous; uses device copies of its own and leaves the context's stacks alone.
+ * Errors as above (no PTMI_ERR_STATE). */
+int ptmi_denoise_images(ptmi_ctx* ctx, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num,
+                        const ptmi_denoise_params* params, float* out);
+
 int ptmi_synchronize(ptmi_ctx* ctx);
 
 /* Validates the uploaded buffers and builds the device-side digests now instead of inside the first render call
@@ -337,6 +388,11 @@ int ptmi_build_bvh_device(ptmi_ctx* ctx, size_t n_prims, const double* bmin, con
  * ids from subtree sizes).  Same arguments, byte-identical output.  Synchronous. */
 int ptmi_build_bvh_sah_device(ptmi_ctx* ctx, size_t n_prims, const double* bmin, const double* bmax, int prim_type, float* nodes_out,
                               int64_t* order_out, size_t* n_nodes_out);
+
+/* ptmi_denoise_images without a GPU: a plain loop over pixels through include/ptmi_denoise.h, the arithmetic the kernels compile — the same arguments, the same
+ * bits.  PTMI_ERR_INVALID_ARG / PTMI_ERR_NO_MEMORY as there. */
+int ptmi_denoise_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params,
+                           float* out);
 
 /* OBJ text -> de-indexed vertex / normal arrays with the reference's accepted grammar and quirks
  * (lib/primitives/objReader.js:10-68: `v`, `vn`, `f a/b/c` triangles; tokens go through JS Number()).  The arrays are

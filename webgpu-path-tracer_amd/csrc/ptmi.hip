@@ -23,6 +23,7 @@
 #include "../../include/ptmi.h"
 #include "ptmi_dbuf.h"
 #include "ptmi_kernels.h"
+#include "ptmi_denoise_kernels.h"
 #include "ptmi_tuning.h"
 
 using namespace ptmi;
@@ -133,6 +134,10 @@ struct ptmi_ctx {
   // ptmi_render_aov: the feature stack — n_aov_views x 3 images of W x H float4 (k_aov), one allocation; its calls share the view table above
   DBuf d_aov;
   uint32_t n_aov_views = 0;
+  // ptmi_denoise_views: the denoised stack — as many images as the view stack has, W x H RGBA f32 means, one allocation that goes when the view stack's size changes —
+  // and the filter's scratch: three packed float4 images (d ping, d pong, n + z) per view of a batch (denoise_batch_views)
+  DBuf d_denoised, d_denoise_scratch;
+  uint32_t n_denoised = 0;
   int rank = 0, world = 1, tile = 64;
 
   size_t path_cap = 0;
@@ -1197,15 +1202,15 @@ __global__ __launch_bounds__(kBlock) void k_add_into_signed_zero(float4* __restr
 // Every pixel is non-zero in exactly one of them (x + 0 = x), so the sum is the single-GPU image bit for bit whatever
 // the order.  The per-device buffers are left as they are, so rendering can go on afterwards.
 // `img`: which W x H float4 image of every device — its accumulation buffer, image `index` of its view stack (ptmi_render_views), or image `index` = 3 * view + layer
-// of its feature stack (ptmi_render_aov).
-enum ImageStack { IMG_FRAMEBUFFER = 0, IMG_VIEWS = 1, IMG_AOV = 2 };
+// of its feature stack (ptmi_render_aov), or image `index` of its denoised stack (ptmi_denoise_views: single-device contexts only).
+enum ImageStack { IMG_FRAMEBUFFER = 0, IMG_VIEWS = 1, IMG_AOV = 2, IMG_DENOISED = 3 };
 struct ImageRef {
   ImageStack of = IMG_FRAMEBUFFER;
   size_t index = 0;
 };
 float4* image_of(const ptmi_ctx* q, ImageRef img) {
   if (img.of == IMG_FRAMEBUFFER) return q->fb;
-  return (img.of == IMG_VIEWS ? q->d_views : q->d_aov).as<float4>() + img.index * (size_t)q->W * (size_t)q->H;
+  return (img.of == IMG_VIEWS ? q->d_views : img.of == IMG_AOV ? q->d_aov : q->d_denoised).as<float4>() + img.index * (size_t)q->W * (size_t)q->H;
 }
 int gather_framebuffer(ptmi_ctx* c, float4** out, ImageRef img = ImageRef{}) {
   if (!c->multi) {
@@ -1752,6 +1757,9 @@ int ptmi_resize(ptmi_ctx* c, int width, int height) {
   c->n_views = 0;
   c->d_aov.release();  // ... and so does the feature stack
   c->n_aov_views = 0;
+  c->d_denoised.release();  // ... and what was filtered from them, with the filter's scratch
+  c->n_denoised = 0;
+  c->d_denoise_scratch.release();
   HIP_TRY(c, hipMemsetAsync(c->fb, 0, bytes, c->stream));
   for (ptmi_ctx* q : c->peers) {
     int r = ptmi_resize(q, width, height);
@@ -1924,6 +1932,8 @@ static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views,
     HIP_TRY(c, stack.ensure(image_bytes * n_views));
     c->d_views = std::move(stack);
     c->n_views = 0;  // (until it is zeroed, below)
+    c->d_denoised.release();  // the denoised stack has the view stack's size: it goes with the old one
+    c->n_denoised = 0;
   }
   r = stage_view_rows(c, views16, n_views);
   if (r) return r;
@@ -2028,6 +2038,8 @@ int ptmi_release_views(ptmi_ctx* c) {
     HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still fold into a stack that is about to go
     q->d_views.release();
     q->n_views = 0;
+    q->d_denoised.release();  // (it had the view stack's size)
+    q->n_denoised = 0;
     return PTMI_OK;
   });
 }
@@ -2124,6 +2136,148 @@ int ptmi_camera_rays(ptmi_ctx* c, const float* view16, uint32_t frame, float* ra
   HIP_TRY(c, hipMemcpyAsync(rng_out, d_rng, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return PTMI_OK;
+}
+
+// ---- the denoised stack (ptmi_denoise_views, ptmi_denoise_images) ----
+// (ptmi_default_denoise_params and ptmi_denoise_reference need no GPU: ptmi_host.cpp)
+// Views per batch of the filter: its scratch is three float4 images per view, held to 1 GiB (10 views at 1080p) so that a call on a large stack does not need
+// another full copy of it; the views of a batch go through every level in one launch.
+static uint32_t denoise_batch_views(size_t npix, uint32_t n) {
+  return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / (npix * 48)));
+}
+static size_t denoise_scratch_bytes(size_t npix, uint32_t n) { return (size_t)denoise_batch_views(npix, n) * npix * 48; }
+
+// The filter on device arrays: colour [n][H][W] float4 sums, layers [n][3][H][W] float4, out [n][H][W] float4.  c->d_denoise_scratch holds denoise_scratch_bytes already:
+// nothing here allocates.  Per batch one k_denoise_prepare and one k_denoise_level per level, the last of which writes `out`.
+static int denoise_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, uint32_t n, int W, int H, float F, const ptmi_denoise_params& P) {
+  const size_t npix = (size_t)W * (size_t)H;
+  const uint32_t B = denoise_batch_views(npix, n);
+  float4* d[2] = {c->d_denoise_scratch.as<float4>(), c->d_denoise_scratch.as<float4>() + (size_t)B * npix};
+  float4* g = c->d_denoise_scratch.as<float4>() + 2 * (size_t)B * npix;
+  for (uint32_t v0 = 0; v0 < n; v0 += B) {
+    const uint32_t nv = std::min(B, n - v0);
+    const float4* col = colour + (size_t)v0 * npix;
+    const float4* lay = layers + (size_t)v0 * 3 * npix;
+    const size_t items = (size_t)nv * npix;
+    const unsigned pgrid = (unsigned)std::min<size_t>((items + kBlock - 1) / kBlock, (size_t)c->num_cus * 32);
+    hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, F, P.albedo_floor, d[0], g);
+    HIP_TRY(c, hipGetLastError());
+    for (int l = 0; l < P.levels; l++) {
+      const int step = 1 << l, ty = step >= 32 ? 4 : 8;
+      const ptmd_consts k = ptmd_level_consts(P.sigma_normal, P.sigma_depth, P.sigma_colour, P.albedo_floor, l);
+      const dim3 grid((unsigned)((W + kDenoiseTX - 1) / kDenoiseTX), (unsigned)(((H + step * ty - 1) / (step * ty)) * step), nv);
+      const size_t lds = (size_t)2 * (ty + 4) * (kDenoiseTX + 4 * step) * sizeof(float4);  // 48 KB at most (step 16 and 32)
+      if (l == P.levels - 1)
+        hipLaunchKernelGGL(k_denoise_level<true>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, out + (size_t)v0 * npix, col, lay, W, H, step, ty, k, F);
+      else
+        hipLaunchKernelGGL(k_denoise_level<false>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, d[(l + 1) & 1], col, lay, W, H, step, ty, k, F);
+      HIP_TRY(c, hipGetLastError());
+    }
+  }
+  return PTMI_OK;
+}
+
+static int denoise_check_args(ptmi_ctx* c, const char* who, const ptmi_denoise_params* params, float frame_num, ptmi_denoise_params* P) {
+  if (!c->peers.empty() || c->multi) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a multi-device context keeps a pixel's neighbours on other GPUs");
+  if (c->world > 1) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a sharded context (ptmi_set_shard) keeps a pixel's neighbours in other processes");
+  if (params) *P = *params;
+  else ptmi_default_denoise_params(P);
+  if (!ptmd_params_ok(P->levels, P->sigma_normal, P->sigma_depth, P->sigma_colour, P->albedo_floor))
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need levels in 1..6, sigma_normal, sigma_depth and albedo_floor > 0, sigma_colour >= 0, all finite");
+  if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": frame_num must be finite and > 0");
+  return PTMI_OK;
+}
+
+int ptmi_denoise_views(ptmi_ctx* c, const ptmi_denoise_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  ptmi_denoise_params P;
+  if (int r = denoise_check_args(c, "ptmi_denoise_views", params, frame_num, &P)) return r;
+  if (!c->d_views.p || c->n_views == 0) return fail(c, PTMI_ERR_STATE, "ptmi_denoise_views: no view stack: call ptmi_render_views first");
+  if (!c->d_aov.p || c->n_aov_views == 0) return fail(c, PTMI_ERR_STATE, "ptmi_denoise_views: no feature stack: call ptmi_render_aov first");
+  if (c->n_views != c->n_aov_views)
+    return fail(c, PTMI_ERR_STATE, "ptmi_denoise_views: the view stack has " + std::to_string(c->n_views) + " views, the feature stack " + std::to_string(c->n_aov_views));
+  if (n_views == 0 || first_view >= c->n_views || n_views > c->n_views - first_view)
+    return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_views: views [" + std::to_string(first_view) + ", " + std::to_string((uint64_t)first_view + n_views) + ") of " + std::to_string(c->n_views));
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  const size_t npix = (size_t)c->W * (size_t)c->H;
+  const bool fresh = !c->d_denoised.p || c->n_denoised != c->n_views;
+  DBuf stack;  // the new stack first: a call that fails for want of memory leaves the old images as they were
+  if (fresh) HIP_TRY(c, stack.ensure(npix * 16 * c->n_views));
+  HIP_TRY(c, c->d_denoise_scratch.ensure(denoise_scratch_bytes(npix, n_views)));
+  if (fresh) {
+    c->d_denoised = std::move(stack);
+    c->n_denoised = c->n_views;
+    HIP_TRY(c, hipMemsetAsync(c->d_denoised.p, 0, npix * 16 * c->n_views, c->stream));
+  }
+  return denoise_enqueue(c, c->d_views.as<float4>() + (size_t)first_view * npix, c->d_aov.as<float4>() + (size_t)first_view * 3 * npix,
+                         c->d_denoised.as<float4>() + (size_t)first_view * npix, n_views, c->W, c->H, frame_num, P);
+}
+
+static int check_denoised(ptmi_ctx* c, const char* who, uint32_t view) {
+  if (!c->d_denoised.p || c->n_denoised == 0) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no denoised stack: call ptmi_denoise_views first");
+  if (view >= c->n_denoised) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": view " + std::to_string(view) + " of " + std::to_string(c->n_denoised));
+  return PTMI_OK;
+}
+
+int ptmi_read_denoised(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_denoised: null argument");
+  if (int r = check_denoised(c, "ptmi_read_denoised", view)) return r;
+  if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_denoised: bytes != W*H*16");
+  return read_image(c, ImageRef{IMG_DENOISED, view}, dst, bytes);
+}
+
+int ptmi_resolve_denoised_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_denoised_rgba8: null argument");
+  if (int r = check_denoised(c, "ptmi_resolve_denoised_rgba8", view)) return r;
+  if (bytes != (size_t)c->W * c->H * 4) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_denoised_rgba8: bytes != W*H*4");
+  return resolve_image(c, ImageRef{IMG_DENOISED, view}, 1.0f, dst, bytes);  // (the stack holds means: the display pass at frameNum 1)
+}
+
+int ptmi_denoised_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
+  if (!c || !p) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoised_device_ptr: null argument");
+  if (!c->d_denoised.p || c->n_denoised == 0) return fail(c, PTMI_ERR_STATE, "ptmi_denoised_device_ptr: no denoised stack: call ptmi_denoise_views first");
+  *p = c->d_denoised.p;
+  if (bytes) *bytes = (size_t)c->n_denoised * c->W * c->H * 16;
+  if (n_views) *n_views = c->n_denoised;
+  return PTMI_OK;
+}
+
+int ptmi_release_denoised(ptmi_ctx* c) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  return on_all_devices(c, [](ptmi_ctx* q) -> int {
+    HIP_TRY(q, hipSetDevice(q->device));
+    HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still write a stack that is about to go
+    q->d_denoised.release();
+    q->n_denoised = 0;
+    q->d_denoise_scratch.release();
+    return PTMI_OK;
+  });
+}
+
+int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params, float* out) {
+  if (!c || !colour_sums || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images: null argument");
+  ptmi_denoise_params P;
+  if (int r = denoise_check_args(c, "ptmi_denoise_images", params, frame_num, &P)) return r;
+  if (w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images: need w, h, n_images >= 1 and w * h < 2^31");
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  const size_t npix = (size_t)w * (size_t)h, image_bytes = npix * 16;
+  DBuf col, lay, res;  // this call's own device copies: the context's stacks are not touched
+  HIP_TRY(c, col.ensure(image_bytes * n_images));
+  HIP_TRY(c, lay.ensure(image_bytes * 3 * n_images));
+  HIP_TRY(c, res.ensure(image_bytes * n_images));
+  HIP_TRY(c, c->d_denoise_scratch.ensure(denoise_scratch_bytes(npix, n_images)));
+  HIP_TRY(c, hipMemcpyAsync(col.p, colour_sums, image_bytes * n_images, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(lay.p, layers, image_bytes * 3 * n_images, hipMemcpyHostToDevice, c->stream));
+  int r = denoise_enqueue(c, col.as<float4>(), lay.as<float4>(), res.as<float4>(), n_images, w, h, frame_num, P);
+  if (r == PTMI_OK) {
+    hipError_t e = hipMemcpyAsync(out, res.p, image_bytes * n_images, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) r = fail(c, PTMI_ERR_DEVICE, std::string("ptmi_denoise_images: ") + hipGetErrorString(e));
+  }
+  hipError_t e = hipStreamSynchronize(c->stream);  // (also before the copies above are freed)
+  if (e != hipSuccess && r == PTMI_OK) r = fail(c, PTMI_ERR_DEVICE, std::string("ptmi_denoise_images: ") + hipGetErrorString(e));
+  return r;
 }
 
 static int synchronize_one(ptmi_ctx* c) {

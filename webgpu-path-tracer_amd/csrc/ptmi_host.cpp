@@ -13,11 +13,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <future>
+#include <new>
 #include <thread>
 #include <string>
 #include <vector>
 
 #include "../../include/ptmi.h"
+#include "../../include/ptmi_denoise.h"
 
 namespace {
 // Math.min / Math.max (lib/BVH/AABB.js:8-28) on finite values: -0 < +0 whatever the argument order
@@ -645,6 +647,71 @@ extern "C" int ptmi_obj_parse(const char* text, size_t len, float** vertices_out
     }
   } catch (...) {
     return PTMI_ERR_NO_MEMORY;
+  }
+  return PTMI_OK;
+}
+
+// ---- the denoising filter on the host (ptmi_denoise_reference) ----
+extern "C" void ptmi_default_denoise_params(ptmi_denoise_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->levels = 5;
+  p->sigma_normal = 0.25f;
+  p->sigma_depth = 0.1f;
+  p->sigma_colour = 0.0f;
+  p->albedo_floor = 1e-3f;
+}
+
+// A plain loop over pixels through include/ptmi_denoise.h, the header the kernels of ptmi_denoise_views compile: prepare, the levels between two packed images,
+// remodulate.  One image after the other; nothing is tiled, threaded or reordered.
+extern "C" int ptmi_denoise_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params,
+                                      float* out) {
+  if (!colour_sums || !layers || !out || w <= 0 || h <= 0 || n_images == 0) return PTMI_ERR_INVALID_ARG;
+  ptmi_denoise_params P;
+  if (params) P = *params;
+  else ptmi_default_denoise_params(&P);
+  if (!ptmd_params_ok(P.levels, P.sigma_normal, P.sigma_depth, P.sigma_colour, P.albedo_floor)) return PTMI_ERR_INVALID_ARG;
+  if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
+  const size_t npix = (size_t)w * (size_t)h;
+  std::vector<ptmd_f4> d[2], g;
+  try {
+    d[0].resize(npix), d[1].resize(npix), g.resize(npix);
+  } catch (const std::bad_alloc&) {
+    return PTMI_ERR_NO_MEMORY;
+  }
+  const ptmd_f4 outside{0.0f, 0.0f, 0.0f, ptmd_nan()};
+  for (uint32_t v = 0; v < n_images; v++) {
+    const ptmd_f4* S = reinterpret_cast<const ptmd_f4*>(colour_sums) + (size_t)v * npix;
+    const ptmd_f4* L = reinterpret_cast<const ptmd_f4*>(layers) + (size_t)v * 3 * npix;
+    ptmd_f4* O = reinterpret_cast<ptmd_f4*>(out) + (size_t)v * npix;
+    for (size_t p = 0; p < npix; p++) ptmd_prepare(S[p], L[p], L[npix + p], L[2 * npix + p], frame_num, P.albedo_floor, &d[0][p], &g[p]);
+    for (int l = 0; l < P.levels; l++) {
+      const int step = 1 << l;
+      const ptmd_consts k = ptmd_level_consts(P.sigma_normal, P.sigma_depth, P.sigma_colour, P.albedo_floor, l);
+      const std::vector<ptmd_f4>& in = d[l & 1];
+      std::vector<ptmd_f4>& to = d[(l + 1) & 1];
+      for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+          const size_t p = (size_t)y * w + x;
+          ptmd_f4 dp = in[p];
+          if (dp.w == dp.w) {
+            const ptmd_f4 gp = g[p];
+            const float zs = ptmd_depth_scale(k.sigma_depth, gp.w);
+            float num[3] = {0.0f, 0.0f, 0.0f}, den = 0.0f;
+            for (int j = -2; j <= 2; j++)
+              for (int i = -2; i <= 2; i++) {
+                const int qx = x + i * step, qy = y + j * step;
+                const bool inside = qx >= 0 && qx < w && qy >= 0 && qy < h;
+                const size_t q = inside ? (size_t)qy * w + qx : p;
+                ptmd_tap(&k, dp, gp, zs, inside ? in[q] : outside, g[q], ptmd_h(i) * ptmd_h(j), num, &den);
+              }
+            dp.x = num[0] / den, dp.y = num[1] / den, dp.z = num[2] / den;
+          }
+          to[p] = dp;
+        }
+    }
+    const std::vector<ptmd_f4>& last = d[P.levels & 1];
+    for (size_t p = 0; p < npix; p++) O[p] = ptmd_remodulate(S[p], L[npix + p], frame_num, P.albedo_floor, last[p]);
   }
   return PTMI_OK;
 }

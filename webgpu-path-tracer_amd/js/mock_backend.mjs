@@ -11,5 +11,8 @@ export class MockBackend {
   renderAov(views, nViews, firstFrame, framesPerView, reset = true) { this.calls.push(['renderAov', nViews, firstFrame, framesPerView, !!reset]); }
   readAov(view, layer, out) { this.calls.push(['readAov', view, layer]); return out || new Float32Array(this.width * this.height * 4); }
   releaseAov() { this.calls.push(['releaseAov']); }
+  denoiseViews(frameNum, firstView, nViews, params = null) { this.calls.push(['denoiseViews', frameNum, firstView, nViews, params]); }
+  readDenoised(view, out) { this.calls.push(['readDenoised', view]); return out || new Float32Array(this.width * this.height * 4); }
+  releaseDenoised() { this.calls.push(['releaseDenoised']); }
   synchronize() {}
 }

@@ -41,6 +41,11 @@ export class Ptmi {
   renderAov(views, nViews, firstFrame, framesPerView, reset = true) { this.native.renderAov(this.h, views, nViews, firstFrame, framesPerView, reset); }
   readAov(view, layer, out = new Float32Array(this.width * this.height * 4)) { return this.native.readAov(this.h, view, layer, out); }
   releaseAov() { this.native.releaseAov(this.h); }
+  // The denoiser (ptmi_denoise_views): filters images [firstView, firstView + nViews) of the view stack under the same images of the feature stack into the denoised
+  // stack (mean radiance); frameNum = the frames each view-stack image sums; params = {levels, sigmaNormal, sigmaDepth, sigmaColour, albedoFloor}, all optional.
+  denoiseViews(frameNum, firstView, nViews, params = null) { this.native.denoiseViews(this.h, frameNum, firstView, nViews, params); }
+  readDenoised(view, out = new Float32Array(this.width * this.height * 4)) { return this.native.readDenoised(this.h, view, out); }
+  releaseDenoised() { this.native.releaseDenoised(this.h); }
   synchronize() { this.native.synchronize(this.h); }
   prepare() { this.native.prepare(this.h); }
   buildSceneBVHSAH() { this.native.buildSceneBVHSAH(this.h); }   // the same with the reference's never-called SAH builder (lib/BVH/bvhNode.js:108-283): opt-in

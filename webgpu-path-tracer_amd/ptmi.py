@@ -22,6 +22,8 @@ SYMBOLS = [
     "ptmi_device_count", "ptmi_reduce_info", "ptmi_reload_tuning", "ptmi_build_scene_bvh_sah", "ptmi_scene_bvh_info", "ptmi_build_bvh_sah_device",
     "ptmi_render_views", "ptmi_read_view", "ptmi_resolve_view_rgba8", "ptmi_views_device_ptr", "ptmi_release_views",
     "ptmi_render_aov", "ptmi_read_aov", "ptmi_aov_device_ptr", "ptmi_release_aov", "ptmi_camera_rays",
+    "ptmi_default_denoise_params", "ptmi_denoise_views", "ptmi_read_denoised", "ptmi_resolve_denoised_rgba8", "ptmi_denoised_device_ptr", "ptmi_release_denoised",
+    "ptmi_denoise_images", "ptmi_denoise_reference",
 ]
 
 
@@ -30,6 +32,13 @@ class Params(ctypes.Structure):
         ("num_samples", ctypes.c_int32), ("max_bounces", ctypes.c_int32), ("stratify", ctypes.c_int32),
         ("importance_sampling", ctypes.c_int32), ("stack_size", ctypes.c_int32), ("background", ctypes.c_float * 3),
         ("fov_degrees", ctypes.c_float), ("frames_in_flight", ctypes.c_int32), ("tmin", ctypes.c_float), ("light_mix", ctypes.c_float), ("reserved", ctypes.c_int32 * 3),
+    ]
+
+
+class DenoiseParams(ctypes.Structure):
+    _fields_ = [
+        ("levels", ctypes.c_int32), ("sigma_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float), ("sigma_colour", ctypes.c_float),
+        ("albedo_floor", ctypes.c_float), ("reserved", ctypes.c_int32 * 3),
     ]
 
 
@@ -141,6 +150,17 @@ def load_library(build=False, path=None):
         L.ptmi_aov_device_ptr.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(u32)]
         L.ptmi_release_aov.argtypes = [vp]
         L.ptmi_camera_rays.argtypes = [vp, fp, u32, fp, fp]
+    if hasattr(L, "ptmi_denoise_views"):  # (an older A/B build loaded through PTMI_LIB has no denoiser)
+        dp = ctypes.POINTER(DenoiseParams)
+        L.ptmi_default_denoise_params.argtypes = [dp]
+        L.ptmi_default_denoise_params.restype = None
+        L.ptmi_denoise_views.argtypes = [vp, dp, ctypes.c_float, u32, u32]
+        L.ptmi_read_denoised.argtypes = [vp, u32, fp, sz]
+        L.ptmi_resolve_denoised_rgba8.argtypes = [vp, u32, fp, sz]
+        L.ptmi_denoised_device_ptr.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(u32)]
+        L.ptmi_release_denoised.argtypes = [vp]
+        L.ptmi_denoise_images.argtypes = [vp, fp, fp, i32, i32, u32, ctypes.c_float, dp, fp]
+        L.ptmi_denoise_reference.argtypes = [fp, fp, i32, i32, u32, ctypes.c_float, dp, fp]
     if explicit:
         _libs[path] = L
     else:
@@ -161,6 +181,35 @@ def default_params(**kw):
         else:
             setattr(p, k, v)
     return p
+
+
+def default_denoise_params(lib=None, **kw):
+    """ptmi_default_denoise_params (levels 5, sigma_normal 0.25, sigma_depth 0.1, sigma_colour 0 = off, albedo_floor 1e-3) with fields replaced by keyword."""
+    p = DenoiseParams()
+    (lib or load_library()).ptmi_default_denoise_params(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _denoise_arrays(colour_sums, layers):
+    c = np.ascontiguousarray(colour_sums, np.float32)
+    if c.ndim == 3:
+        c = c[None]
+    n, h, w = c.shape[:3]
+    l = np.ascontiguousarray(layers, np.float32).reshape(n, 3, h, w, 4)
+    assert c.shape == (n, h, w, 4), "colour_sums: (n, H, W, 4) float32, layers: (n, 3, H, W, 4)"
+    return c, l, np.empty((n, h, w, 4), np.float32)
+
+
+def denoise_reference(colour_sums, layers, frame_num, params=None, lib=None):
+    """ptmi_denoise_reference: the denoising filter of Context.denoise_views on host arrays, on the CPU (no GPU needed) — colour_sums (n, H, W, 4) RGBA sums,
+    layers (n, 3, H, W, 4) as Context.read_aov gives them; returns (n, H, W, 4) mean radiance, the kernels' bits."""
+    c, l, out = _denoise_arrays(colour_sums, layers)
+    st = (lib or load_library()).ptmi_denoise_reference(_ptr(c), _ptr(l), c.shape[2], c.shape[1], c.shape[0], float(frame_num), None if params is None else ctypes.byref(params), _ptr(out))
+    if st != 0:
+        raise PtmiError(st, "ptmi_denoise_reference failed")
+    return out
 
 
 class NativeHost:
@@ -338,6 +387,39 @@ class Context:
 
     def release_aov(self):
         self._ck(self.lib.ptmi_release_aov(self.h))
+
+    def denoise_views(self, frame_num, first_view=0, n_views=None, params=None):
+        """ptmi_denoise_views: filters images [first_view, first_view + n_views) of the view stack (render_views) under the same images of the feature stack
+        (render_aov) into the context's denoised stack; `frame_num` = the frames each view-stack image sums.  params: DenoiseParams (default_denoise_params).
+        n_views=None: up to the end of the stack.  Asynchronous."""
+        if n_views is None:
+            n_views = self.views_device_ptr()[2] - first_view
+        self._ck(self.lib.ptmi_denoise_views(self.h, None if params is None else ctypes.byref(params), float(frame_num), first_view, n_views))
+
+    def read_denoised(self, view):
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(self.lib.ptmi_read_denoised(self.h, view, _ptr(out), out.nbytes))
+        return out
+
+    def resolve_denoised_rgba8(self, view):
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        self._ck(self.lib.ptmi_resolve_denoised_rgba8(self.h, view, _ptr(out), out.nbytes))
+        return out
+
+    def denoised_device_ptr(self):
+        """(device pointer, bytes, n_views) of the denoised stack: one contiguous [n_views][H][W][4] float32 array of mean radiance."""
+        p, n, v = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_uint32()
+        self._ck(self.lib.ptmi_denoised_device_ptr(self.h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(v)))
+        return p.value, n.value, v.value
+
+    def release_denoised(self):
+        self._ck(self.lib.ptmi_release_denoised(self.h))
+
+    def denoise_images(self, colour_sums, layers, frame_num, params=None):
+        """ptmi_denoise_images: the kernels of denoise_views on host arrays of any size (see denoise_reference for the shapes); synchronous."""
+        c, l, out = _denoise_arrays(colour_sums, layers)
+        self._ck(self.lib.ptmi_denoise_images(self.h, _ptr(c), _ptr(l), c.shape[2], c.shape[1], c.shape[0], float(frame_num), None if params is None else ctypes.byref(params), _ptr(out)))
+        return out
 
     def camera_rays(self, view16, frame):
         """Test hook (ptmi_camera_rays): (rays (W*H, 6) float32, rng (W*H,) uint32) — the first camera ray of `frame` for every pixel and the RNG state its
