@@ -288,6 +288,66 @@ int ptmi_release_denoised(ptmi_ctx* ctx);
 int ptmi_denoise_images(ptmi_ctx* ctx, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num,
                         const ptmi_denoise_params* params, float* out);
 
+/* Fusion (no counterpart in the reference, which shows one camera at a time): cross-view accumulation by reprojection — the views of a camera path are mostly
+ * samples of the same surfaces, and everything needed to bring them together is in the feature stack.  A stack of n views with view matrices M_u (column-major, as
+ * ptmi_render_views takes them): S_u the colour image of view u; N_u, A_u, I_u layers 0, 1, 2 of the feature stack; F the divisor of S (frame_num when `source` is
+ * the view stack, 1 when it is the denoised stack); f the context's fovFactor (main.wgsl:7); o_u = M_u (0,0,0,1); B_u the inverse of the upper-left 3x3 of M_u, which
+ * the host computes once per view in f64 and rounds to f32 — the CPU and the GPU path use that one table.  Per pixel p of view u, exactly as the denoiser's "prepare"
+ * makes them: k, c, n, z, a', d = c / a', m, and validity.  A pixel is FUSABLE when it is valid and its material's type is LAMBERTIAN (header.wgsl:4): radiance that
+ * leaves a diffuse point is the same in every view, a mirror's or a glass's is not.  For every fusable pixel p = (x, y) of an output view v:
+ *
+ *   1 world point     X = o_v + z(p) dir_v(p), dir_v(p) the camera ray through the CENTRE of p's sample footprint: xs = x, ys = idx / W with idx = y W + x evaluated as
+ *                     main.wgsl:5 does (quirk Q1 of SURVEY.md: the row coordinate is fractional, one pixel of vertical shear per row), s = (W/H)(2 xs/W - 1),
+ *                     t = -(2 ys/H - 1), dir = normalize(M_v (s, t, -f, 0)).
+ *   2 neighbour views u = max(0, v-R) .. min(n-1, v+R) in ascending order, R = radius; the window is clipped at the ends of the STACK, not of the call's range.
+ *                     u = v contributes w = 1 with d(p).  For u != v: wv = X - o_u, r = |wv|, (a, b, c) = B_u wv; skip the view unless c < 0; s = -f a / c, t = -f b / c;
+ *                     xs = (s H / W + 1) W / 2, ys = (1 - t) H / 2; column qx = floor(xs + 0.5), row qy = floor(ys - qx / W + 0.5): the pixel whose footprint contains
+ *                     the projection, the inverse of step 1.  Skip unless q lies inside the image, q is valid in view u and m_u(q) == m_v(p).
+ *                       e = |n_u(q) - n_v(p)|^2 / sigma_normal^2 + ((z_u(q) - r) / (sigma_depth (r + 1e-6)))^2;  skip if e is not finite;
+ *                       w = exp2(-e) (ptm_exp2);  num += w d_u(q), den += w.
+ *   3 output          rgb = (num / den) a'(p): MEAN radiance, as in the denoised stack.
+ *
+ * Every other pixel (invalid, or valid but not fusable) passes through: rgb = S.rgb / F.  alpha = S.a / F everywhere.  The f32 operation order is fixed in
+ * include/ptmi_fuse.h, which the kernel and ptmi_fuse_reference both compile: their results agree bit for bit.
+ * CAVEAT.  ptmi_render_views gives every view the SAME frame numbers, so pixel idx draws the same random stream in every view.  Where the camera moves by less
+ * than a pixel between views the fused samples are the same sample, and fusion gains nothing there; where it moves further, the samples of one surface point come
+ * from different pixels and therefore from different streams.  That is how the seeds work; fusion does not alter it. */
+typedef struct ptmi_fuse_params {
+  int32_t radius;      /* 1 .. 8: views on either side of the output view */
+  float sigma_normal;  /* > 0 */
+  float sigma_depth;   /* > 0, relative to the distance of the reprojected point */
+  float albedo_floor;  /* > 0 */
+  int32_t reserved[4];
+} ptmi_fuse_params;
+/* radius 4, sigma_normal 0.25, sigma_depth 0.1, albedo_floor 1e-3 */
+void ptmi_default_fuse_params(ptmi_fuse_params* p);
+/* Fuses output views [first_view, first_view + n_views) into the context's FUSED STACK: [n_views of the view stack][H][W][4] f32 in one device allocation, zeroed when
+ * this call allocates it; images outside the range keep what they held (their window still reads the neighbours outside it).  ptmi_resize and any change of the view
+ * stack's size (ptmi_render_views with another n_views, ptmi_release_views) drop it.  views16 holds the matrices of ALL views of the stack — THE CALLER is responsible
+ * for their being the ones the stacks were rendered from.  source 0: S is the view stack (ptmi_render_views) and frame_num the frames each of its images sums;
+ * source 1: S is the denoised stack (ptmi_denoise_views), frame_num is ignored.  The material types are those of the uploaded materials.  params = NULL: the defaults.
+ * One kernel launch (a grid over output views) reads the stacks directly; asynchronous on the context's stream; touches no other stack, nor the accumulation buffer,
+ * nor any ptmi_stats field.
+ * PTMI_ERR_STATE: a needed stack is missing, or the stacks differ in n_views.  PTMI_ERR_INVALID_ARG: a parameter outside its domain, a source other than 0 / 1, a
+ * range past the stack, frame_num not finite or not > 0 with source 0, a view matrix whose 3x3 has a zero or non-finite determinant.  PTMI_ERR_NO_MEMORY: before
+ * anything is enqueued; the fused stack the call found stays as it was.  PTMI_ERR_UNSUPPORTED: a multi-device context or a shard (ptmi_set_shard with world > 1) —
+ * gather the images first and use ptmi_fuse_images. */
+int ptmi_fuse_views(ptmi_ctx* ctx, const ptmi_fuse_params* params, const float* views16, float frame_num, int source, uint32_t first_view, uint32_t n_views);
+/* ptmi_read_view's counterpart for image `view` of the fused stack: synchronises; bytes must be W*H*16. */
+int ptmi_read_fused(ptmi_ctx* ctx, uint32_t view, float* dst, size_t bytes);
+/* The display pass (ptmi_resolve_rgba8) for image `view` of the fused stack, at frameNum 1: the stack holds means. */
+int ptmi_resolve_fused_rgba8(ptmi_ctx* ctx, uint32_t view, uint8_t* dst, size_t bytes);
+/* The fused stack as one contiguous [n_views][H][W][4] f32 device array; valid until it is dropped (above) or ptmi_release_fused.  bytes / n_views may be NULL. */
+int ptmi_fused_device_ptr(ptmi_ctx* ctx, void** dev_ptr, size_t* bytes, uint32_t* n_views);
+/* Frees the fused stack and the call's view table (ptmi_destroy does too); synchronises. */
+int ptmi_release_fused(ptmi_ctx* ctx);
+/* The same kernel on host arrays of any size: colour [n_images][h][w][4] (sums of frame_num frames; means with frame_num 1), layers [n_images][3][h][w][4] (the
+ * feature stack's layout), views16 [n_images][16], out [n_images][h][w][4], all f32; fovFactor = 1 / tan(fov_degrees / 2), fov_degrees in (0, 180).  lambertian: one
+ * byte per material index, non-zero = fusable; NULL: every material is fusable; an index outside the table is not.  Every image is an output view.  Synchronous; uses
+ * device copies of its own and leaves the context's stacks alone.  Errors as above (no PTMI_ERR_STATE). */
+int ptmi_fuse_images(ptmi_ctx* ctx, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
+                     float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out);
+
 int ptmi_synchronize(ptmi_ctx* ctx);
 
 /* Validates the uploaded buffers and builds the device-side digests now instead of inside the first render call
@@ -393,6 +453,11 @@ int ptmi_build_bvh_sah_device(ptmi_ctx* ctx, size_t n_prims, const double* bmin,
  * bits.  PTMI_ERR_INVALID_ARG / PTMI_ERR_NO_MEMORY as there. */
 int ptmi_denoise_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params,
                            float* out);
+
+/* ptmi_fuse_images without a GPU: a plain loop over views and pixels through include/ptmi_fuse.h, the arithmetic the kernel compiles — the same arguments, the same
+ * bits.  PTMI_ERR_INVALID_ARG / PTMI_ERR_NO_MEMORY as there. */
+int ptmi_fuse_reference(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
+                        const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out);
 
 /* OBJ text -> de-indexed vertex / normal arrays with the reference's accepted grammar and quirks
  * (lib/primitives/objReader.js:10-68: `v`, `vn`, `f a/b/c` triangles; tokens go through JS Number()).  The arrays are

@@ -1,6 +1,7 @@
-// Sanitizer driver for the host natives of libptmi (ptmi_host.cpp): both BVH builders (1 thread vs many) and the OBJ parser.
+// Sanitizer driver for the host natives of libptmi (ptmi_host.cpp): both BVH builders (1 thread vs many), the OBJ parser and cross-view fusion.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -pthread tools/sanitize_host.cpp webgpu-path-tracer_amd/csrc/ptmi_host.cpp -o /tmp/san/asan && /tmp/san/asan
 //   g++ -std=c++17 -O1 -g -fsanitize=thread -pthread ... -o /tmp/san/tsan && /tmp/san/tsan
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,6 +47,36 @@ int main() {
   if (ptmi_obj_parse(obj.data(), obj.size(), &v, &nv, &nn, &nnn)) return 4;
   ptmi_free(v);
   ptmi_free(nn);
+  {  // ptmi_fuse_reference on a 7 x 5 stack of three views: a wall at z = -3 seen from eyes one unit apart (projections land inside, outside and on other materials),
+     // the third camera turned round (c >= 0), a miss, a NaN colour, a material index outside the table
+    const int w = 7, h = 5, n = 3, npix = w * h;
+    std::vector<float> S(n * npix * 4), L(n * 3 * npix * 4, 0.0f), views(n * 16, 0.0f), out(n * npix * 4);
+    for (int v = 0; v < n; v++) {
+      float* m = &views[16 * v];
+      m[0] = m[5] = m[10] = m[15] = 1.0f;
+      m[12] = (float)v - 1.0f;
+      if (v == 2) m[0] = m[10] = -1.0f;
+      for (int p = 0; p < npix; p++) {
+        float* s = &S[(v * npix + p) * 4];
+        s[0] = 0.1f * (p % 5), s[1] = 0.5f, s[2] = (p == 9) ? NAN : 1.0f + v, s[3] = 2.0f;
+        if (p == 3) continue;  // a miss: k = 0
+        float* l0 = &L[((v * 3 + 0) * npix + p) * 4];
+        float* l1 = &L[((v * 3 + 1) * npix + p) * 4];
+        float* l2 = &L[((v * 3 + 2) * npix + p) * 4];
+        l0[2] = 2.0f, l0[3] = 2.0f * (3.0f + 0.05f * (p % w));
+        l1[0] = 1.2f, l1[1] = 0.0005f, l1[2] = 0.8f, l1[3] = 2.0f;
+        l2[0] = 2.0f, l2[2] = (p == 11) ? 7.0f : (float)(p % 2);
+      }
+    }
+    const uint8_t lamb[2] = {1, 1};
+    ptmi_fuse_params P;
+    ptmi_default_fuse_params(&P);
+    P.radius = 8;
+    if (ptmi_fuse_reference(S.data(), L.data(), views.data(), w, h, n, 2.0f, 60.0f, lamb, 2, &P, out.data())) return 6;
+    if (ptmi_fuse_reference(S.data(), L.data(), views.data(), w, h, n, 2.0f, 60.0f, nullptr, 0, nullptr, out.data())) return 7;
+    views[0] = 0.0f;
+    if (ptmi_fuse_reference(S.data(), L.data(), views.data(), w, h, n, 2.0f, 60.0f, nullptr, 0, nullptr, out.data()) != PTMI_ERR_INVALID_ARG) return 8;  // a singular matrix
+  }
   puts("host natives: sanitizer run clean");
   return 0;
 }

@@ -24,6 +24,7 @@
 #include "ptmi_dbuf.h"
 #include "ptmi_kernels.h"
 #include "ptmi_denoise_kernels.h"
+#include "ptmi_fuse_kernels.h"
 #include "ptmi_tuning.h"
 
 using namespace ptmi;
@@ -138,6 +139,13 @@ struct ptmi_ctx {
   // and the filter's scratch: three packed float4 images (d ping, d pong, n + z) per view of a batch (denoise_batch_views)
   DBuf d_denoised, d_denoise_scratch;
   uint32_t n_denoised = 0;
+  // ptmi_fuse_views: the fused stack — as many images as the view stack has, W x H RGBA f32 means, one allocation that goes when the view stack's size changes — and
+  // the call's table (kFuseRow float4 per view of the stack, then one byte per material), uploaded from a pinned staging copy like the view table above
+  DBuf d_fused, d_fuse_tab;
+  uint32_t n_fused = 0;
+  float* h_fuse_tab = nullptr;
+  size_t h_fuse_tab_cap = 0;
+  hipEvent_t fuse_tab_sent = nullptr;
   int rank = 0, world = 1, tile = 64;
 
   size_t path_cap = 0;
@@ -1202,15 +1210,16 @@ __global__ __launch_bounds__(kBlock) void k_add_into_signed_zero(float4* __restr
 // Every pixel is non-zero in exactly one of them (x + 0 = x), so the sum is the single-GPU image bit for bit whatever
 // the order.  The per-device buffers are left as they are, so rendering can go on afterwards.
 // `img`: which W x H float4 image of every device — its accumulation buffer, image `index` of its view stack (ptmi_render_views), or image `index` = 3 * view + layer
-// of its feature stack (ptmi_render_aov), or image `index` of its denoised stack (ptmi_denoise_views: single-device contexts only).
-enum ImageStack { IMG_FRAMEBUFFER = 0, IMG_VIEWS = 1, IMG_AOV = 2, IMG_DENOISED = 3 };
+// of its feature stack (ptmi_render_aov), or image `index` of its denoised stack (ptmi_denoise_views: single-device contexts only) or of its fused stack
+// (ptmi_fuse_views: the same).
+enum ImageStack { IMG_FRAMEBUFFER = 0, IMG_VIEWS = 1, IMG_AOV = 2, IMG_DENOISED = 3, IMG_FUSED = 4 };
 struct ImageRef {
   ImageStack of = IMG_FRAMEBUFFER;
   size_t index = 0;
 };
 float4* image_of(const ptmi_ctx* q, ImageRef img) {
   if (img.of == IMG_FRAMEBUFFER) return q->fb;
-  return (img.of == IMG_VIEWS ? q->d_views : img.of == IMG_AOV ? q->d_aov : q->d_denoised).as<float4>() + img.index * (size_t)q->W * (size_t)q->H;
+  return (img.of == IMG_VIEWS ? q->d_views : img.of == IMG_AOV ? q->d_aov : img.of == IMG_DENOISED ? q->d_denoised : q->d_fused).as<float4>() + img.index * (size_t)q->W * (size_t)q->H;
 }
 int gather_framebuffer(ptmi_ctx* c, float4** out, ImageRef img = ImageRef{}) {
   if (!c->multi) {
@@ -1541,6 +1550,8 @@ void ptmi_destroy(ptmi_ctx* c) {
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   if (c->view_rows_sent) (void)hipEventDestroy(c->view_rows_sent);
   if (c->h_view_rows) (void)hipHostFree(c->h_view_rows);
+  if (c->fuse_tab_sent) (void)hipEventDestroy(c->fuse_tab_sent);
+  if (c->h_fuse_tab) (void)hipHostFree(c->h_fuse_tab);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;  // its device buffers (DBuf) are freed here, with its device current and its stream drained
 }
@@ -1760,6 +1771,8 @@ int ptmi_resize(ptmi_ctx* c, int width, int height) {
   c->d_denoised.release();  // ... and what was filtered from them, with the filter's scratch
   c->n_denoised = 0;
   c->d_denoise_scratch.release();
+  c->d_fused.release();  // ... and what was fused from them
+  c->n_fused = 0;
   HIP_TRY(c, hipMemsetAsync(c->fb, 0, bytes, c->stream));
   for (ptmi_ctx* q : c->peers) {
     int r = ptmi_resize(q, width, height);
@@ -1934,6 +1947,8 @@ static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views,
     c->n_views = 0;  // (until it is zeroed, below)
     c->d_denoised.release();  // the denoised stack has the view stack's size: it goes with the old one
     c->n_denoised = 0;
+    c->d_fused.release();  // ... and so does the fused stack
+    c->n_fused = 0;
   }
   r = stage_view_rows(c, views16, n_views);
   if (r) return r;
@@ -2040,6 +2055,8 @@ int ptmi_release_views(ptmi_ctx* c) {
     q->n_views = 0;
     q->d_denoised.release();  // (it had the view stack's size)
     q->n_denoised = 0;
+    q->d_fused.release();
+    q->n_fused = 0;
     return PTMI_OK;
   });
 }
@@ -2277,6 +2294,186 @@ int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* laye
   }
   hipError_t e = hipStreamSynchronize(c->stream);  // (also before the copies above are freed)
   if (e != hipSuccess && r == PTMI_OK) r = fail(c, PTMI_ERR_DEVICE, std::string("ptmi_denoise_images: ") + hipGetErrorString(e));
+  return r;
+}
+
+// ---- the fused stack (ptmi_fuse_views, ptmi_fuse_images) ----
+// (ptmi_default_fuse_params and ptmi_fuse_reference need no GPU: ptmi_host.cpp)
+// The call's table as the kernel reads it: kFuseRow float4 per view of the stack, then one byte per material index.
+static size_t fuse_tab_bytes(uint32_t n_stack, uint32_t n_materials) { return (size_t)n_stack * kFuseRow * 16 + std::max<size_t>(16, n_materials); }
+
+// Fills `tab` (fuse_tab_bytes) from the matrices of all views and the material-type bytes; PTMI_ERR_INVALID_ARG for a matrix that cannot be inverted.
+static int fuse_fill_tab(ptmi_ctx* c, const char* who, const float* views16, uint32_t n_stack, const uint8_t* lamb, uint32_t n_materials, float* tab) {
+  for (uint32_t v = 0; v < n_stack; v++) {
+    ptmf_view row;
+    if (!ptmf_make_view(views16 + 16 * (size_t)v, &row))
+      return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the 3x3 of view matrix " + std::to_string(v) + " has a zero or non-finite determinant");
+    fuse_pack_row(row, tab + (size_t)v * kFuseRow * 4);
+  }
+  uint8_t* bytes = reinterpret_cast<uint8_t*>(tab + (size_t)n_stack * kFuseRow * 4);
+  memset(bytes, 0, std::max<size_t>(16, n_materials));
+  if (lamb) memcpy(bytes, lamb, n_materials);
+  return PTMI_OK;
+}
+
+// The kernel on device arrays: colour [n_stack][H][W] float4, layers [n_stack][3][H][W] float4, out [n_stack][H][W] float4, of which views [first, first + n) are
+// written; `tab` as fuse_fill_tab made it, `has_lamb`: whether its material bytes are to be used.  One launch; more only where n exceeds the grid's z limit.
+static int fuse_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, const void* tab, bool has_lamb, uint32_t n_materials, int W, int H,
+                        uint32_t n_stack, uint32_t first, uint32_t n, const ptmf_consts& k) {
+  const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
+  const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
+  const uint8_t* lamb = has_lamb ? reinterpret_cast<const uint8_t*>(tab) + (size_t)n_stack * kFuseRow * 16 : nullptr;
+  for (uint32_t v0 = 0; v0 < n; v0 += 65535u) {
+    const uint32_t nv = std::min(65535u, n - v0);
+    hipLaunchKernelGGL(k_fuse, dim3(gx, 1, nv), dim3(kBlock), 0, c->stream, colour, layers, out, reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, n_stack,
+                       first + v0, k);
+    HIP_TRY(c, hipGetLastError());
+  }
+  return PTMI_OK;
+}
+
+static int fuse_check_args(ptmi_ctx* c, const char* who, const ptmi_fuse_params* params, float frame_num, bool need_frames, ptmi_fuse_params* P) {
+  if (!c->peers.empty() || c->multi) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a multi-device context keeps a view's pixels on several GPUs");
+  if (c->world > 1) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a sharded context (ptmi_set_shard) keeps a view's pixels in several processes");
+  if (params) *P = *params;
+  else ptmi_default_fuse_params(P);
+  if (!ptmf_params_ok(P->radius, P->sigma_normal, P->sigma_depth, P->albedo_floor))
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need radius in 1..8, sigma_normal, sigma_depth and albedo_floor > 0, all finite");
+  if (need_frames && (!(frame_num > 0.0f) || !ptmd_finite(frame_num))) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": frame_num must be finite and > 0");
+  return PTMI_OK;
+}
+
+int ptmi_fuse_views(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, float frame_num, int source, uint32_t first_view, uint32_t n_views) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_views: null argument");
+  if (source != 0 && source != 1) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_views: source must be 0 (the view stack) or 1 (the denoised stack)");
+  ptmi_fuse_params P;
+  if (int r = fuse_check_args(c, "ptmi_fuse_views", params, frame_num, source == 0, &P)) return r;
+  if (!c->d_views.p || c->n_views == 0) return fail(c, PTMI_ERR_STATE, "ptmi_fuse_views: no view stack: call ptmi_render_views first");
+  if (!c->d_aov.p || c->n_aov_views == 0) return fail(c, PTMI_ERR_STATE, "ptmi_fuse_views: no feature stack: call ptmi_render_aov first");
+  if (c->n_views != c->n_aov_views)
+    return fail(c, PTMI_ERR_STATE, "ptmi_fuse_views: the view stack has " + std::to_string(c->n_views) + " views, the feature stack " + std::to_string(c->n_aov_views));
+  if (source == 1 && (!c->d_denoised.p || c->n_denoised != c->n_views)) return fail(c, PTMI_ERR_STATE, "ptmi_fuse_views: no denoised stack: call ptmi_denoise_views first");
+  if (n_views == 0 || first_view >= c->n_views || n_views > c->n_views - first_view)
+    return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_views: views [" + std::to_string(first_view) + ", " + std::to_string((uint64_t)first_view + n_views) + ") of " + std::to_string(c->n_views));
+  const uint32_t n_stack = c->n_views, n_mat = (uint32_t)(c->h_mats.size() / 16);
+  const size_t tab_bytes = fuse_tab_bytes(n_stack, n_mat);
+  std::vector<float> tab;
+  std::vector<uint8_t> lamb(n_mat);
+  try {
+    tab.resize(tab_bytes / 4 + 1);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_fuse_views: no host memory for the view table");
+  }
+  for (uint32_t i = 0; i < n_mat; i++) lamb[i] = c->h_mats[16 * (size_t)i + 14] == PTMF_LAMBERTIAN;
+  if (int r = fuse_fill_tab(c, "ptmi_fuse_views", views16, n_stack, lamb.data(), n_mat, tab.data())) return r;
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  // the stack, the table and its staging copy: everything that can fail for want of memory, before anything is enqueued
+  const size_t npix = (size_t)c->W * (size_t)c->H;
+  const bool fresh = !c->d_fused.p || c->n_fused != n_stack;
+  DBuf stack;  // the new stack first: a call that fails for want of memory leaves the old images as they were
+  if (fresh) HIP_TRY(c, stack.ensure(npix * 16 * n_stack));
+  if (c->fuse_tab_sent) HIP_TRY(c, hipEventSynchronize(c->fuse_tab_sent));  // the last call's upload has read the staging copy
+  else HIP_TRY(c, hipEventCreateWithFlags(&c->fuse_tab_sent, hipEventDisableTiming));
+  if (tab_bytes > c->d_fuse_tab.cap) HIP_TRY(c, hipStreamSynchronize(c->stream));  // (an earlier call's kernel may still read the table that ensure() is about to free)
+  HIP_TRY(c, c->d_fuse_tab.ensure(tab_bytes));
+  if (tab_bytes > c->h_fuse_tab_cap) {
+    if (c->h_fuse_tab) (void)hipHostFree(c->h_fuse_tab);
+    c->h_fuse_tab = nullptr, c->h_fuse_tab_cap = 0;
+    HIP_TRY(c, hipHostMalloc((void**)&c->h_fuse_tab, tab_bytes, hipHostMallocDefault));
+    c->h_fuse_tab_cap = tab_bytes;
+  }
+  memcpy(c->h_fuse_tab, tab.data(), tab_bytes);
+  if (fresh) {
+    c->d_fused = std::move(stack);
+    c->n_fused = n_stack;
+    HIP_TRY(c, hipMemsetAsync(c->d_fused.p, 0, npix * 16 * n_stack, c->stream));
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->d_fuse_tab.p, c->h_fuse_tab, tab_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->fuse_tab_sent, c->stream));
+  const float fov_factor = (float)(1.0 / std::tan((double)c->prm.fov_degrees * (3.14159265358979323846 / 180.0) / 2.0));  // as make_render_const folds it
+  const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, source == 0 ? frame_num : 1.0f, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
+  return fuse_enqueue(c, (source == 0 ? c->d_views : c->d_denoised).as<float4>(), c->d_aov.as<float4>(), c->d_fused.as<float4>(), c->d_fuse_tab.p, true, n_mat, c->W, c->H, n_stack,
+                      first_view, n_views, k);
+}
+
+static int check_fused(ptmi_ctx* c, const char* who, uint32_t view) {
+  if (!c->d_fused.p || c->n_fused == 0) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no fused stack: call ptmi_fuse_views first");
+  if (view >= c->n_fused) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": view " + std::to_string(view) + " of " + std::to_string(c->n_fused));
+  return PTMI_OK;
+}
+
+int ptmi_read_fused(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_fused: null argument");
+  if (int r = check_fused(c, "ptmi_read_fused", view)) return r;
+  if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_fused: bytes != W*H*16");
+  return read_image(c, ImageRef{IMG_FUSED, view}, dst, bytes);
+}
+
+int ptmi_resolve_fused_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_fused_rgba8: null argument");
+  if (int r = check_fused(c, "ptmi_resolve_fused_rgba8", view)) return r;
+  if (bytes != (size_t)c->W * c->H * 4) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_fused_rgba8: bytes != W*H*4");
+  return resolve_image(c, ImageRef{IMG_FUSED, view}, 1.0f, dst, bytes);  // (the stack holds means: the display pass at frameNum 1)
+}
+
+int ptmi_fused_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
+  if (!c || !p) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fused_device_ptr: null argument");
+  if (!c->d_fused.p || c->n_fused == 0) return fail(c, PTMI_ERR_STATE, "ptmi_fused_device_ptr: no fused stack: call ptmi_fuse_views first");
+  *p = c->d_fused.p;
+  if (bytes) *bytes = (size_t)c->n_fused * c->W * c->H * 16;
+  if (n_views) *n_views = c->n_fused;
+  return PTMI_OK;
+}
+
+int ptmi_release_fused(ptmi_ctx* c) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  return on_all_devices(c, [](ptmi_ctx* q) -> int {
+    HIP_TRY(q, hipSetDevice(q->device));
+    HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still write a stack that is about to go
+    q->d_fused.release();
+    q->n_fused = 0;
+    q->d_fuse_tab.release();
+    return PTMI_OK;
+  });
+}
+
+int ptmi_fuse_images(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
+                     const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
+  if (!c || !colour || !layers || !views16 || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_images: null argument");
+  ptmi_fuse_params P;
+  if (int r = fuse_check_args(c, "ptmi_fuse_images", params, frame_num, true, &P)) return r;
+  if (w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_images: need w, h, n_images >= 1 and w * h < 2^31");
+  if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_images: fov_degrees must be in (0,180)");
+  if (!lambertian) n_materials = 0;
+  const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials);
+  std::vector<float> tab;
+  try {
+    tab.resize(tab_bytes / 4 + 1);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_fuse_images: no host memory for the view table");
+  }
+  if (int r = fuse_fill_tab(c, "ptmi_fuse_images", views16, n_images, lambertian, n_materials, tab.data())) return r;
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  const size_t npix = (size_t)w * (size_t)h, image_bytes = npix * 16;
+  DBuf col, lay, res, dtab;  // this call's own device copies: the context's stacks are not touched
+  HIP_TRY(c, col.ensure(image_bytes * n_images));
+  HIP_TRY(c, lay.ensure(image_bytes * 3 * n_images));
+  HIP_TRY(c, res.ensure(image_bytes * n_images));
+  HIP_TRY(c, dtab.ensure(tab_bytes));
+  HIP_TRY(c, hipMemcpyAsync(col.p, colour, image_bytes * n_images, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(lay.p, layers, image_bytes * 3 * n_images, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+  const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
+  int r = fuse_enqueue(c, col.as<float4>(), lay.as<float4>(), res.as<float4>(), dtab.p, lambertian != nullptr, n_materials, w, h, n_images, 0, n_images, k);
+  if (r == PTMI_OK) {
+    hipError_t e = hipMemcpyAsync(out, res.p, image_bytes * n_images, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) r = fail(c, PTMI_ERR_DEVICE, std::string("ptmi_fuse_images: ") + hipGetErrorString(e));
+  }
+  hipError_t e = hipStreamSynchronize(c->stream);  // (also before the copies above are freed)
+  if (e != hipSuccess && r == PTMI_OK) r = fail(c, PTMI_ERR_DEVICE, std::string("ptmi_fuse_images: ") + hipGetErrorString(e));
   return r;
 }
 

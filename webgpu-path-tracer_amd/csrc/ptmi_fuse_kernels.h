@@ -1,0 +1,99 @@
+// ptmi_fuse_kernels.h — the kernel of ptmi_fuse_views / ptmi_fuse_images (include/ptmi.h, "Fusion"): every fusable pixel of an output view gathers, from each
+// neighbour view of its window, the one pixel its first hit projects into.  Every f32 operation of a pixel is in include/ptmi_fuse.h, which the host native
+// ptmi_fuse_reference includes too; this file only decides where the operands come from.
+//
+// k_fuse   One lane owns one output pixel, a wave 64 neighbouring pixels of one row, a block four such waves; the grid's z axis runs over the call's output views, so
+//          a call is one launch.  The neighbour view u of the window loop is the same for the whole wave: its row of the view table (B_u, o_u: three float4) comes
+//          through scalar loads, as load_view_row's does, and so does the output view's own row (M_v, o_v).  An accepted projection reads S, N, A and I of q
+//          straight from the stacks — four 16-byte gathers that do not depend on one another, issued together; neighbouring lanes project to neighbouring q, so a
+//          wave's gather touches few lines.  No LDS tile (q's offset from p differs per view and per depth), no packed scratch images, no prepare pass: q's packed
+//          pixel is remade from its sums by the arithmetic ptmi_denoise.h's prepare uses.  The material-type table is read once per pixel, for p.
+#pragma once
+
+#include "../../include/ptmi_fuse.h"
+#include "ptmi_denoise_kernels.h"
+
+namespace ptmi {
+
+constexpr int kFuseRow = 7;  // float4 per view of the table: the matrix's four columns, then (B row 0, o.x), (B row 1, o.y), (B row 2, o.z)
+
+// The table row of view v packed for the device (host side of the layout above)
+inline void fuse_pack_row(const ptmf_view& v, float* row) {
+  for (int k = 0; k < 16; k++) row[k] = v.m[k];
+  for (int i = 0; i < 3; i++) {
+    row[16 + 4 * i + 0] = v.B[3 * i + 0], row[16 + 4 * i + 1] = v.B[3 * i + 1], row[16 + 4 * i + 2] = v.B[3 * i + 2];
+    row[16 + 4 * i + 3] = v.o[i];
+  }
+}
+
+// what the neighbour loop needs of view u (wave-uniform u: scalar loads)
+DEV void fuse_load_neighbour(const float4* __restrict__ tab, uint32_t u, ptmf_view& U) {
+  const float4* p = tab + (size_t)kFuseRow * u + 4;
+  const float4 r0 = ldu(p), r1 = ldu(p + 1), r2 = ldu(p + 2);
+  U.B[0] = r0.x, U.B[1] = r0.y, U.B[2] = r0.z, U.o[0] = r0.w;
+  U.B[3] = r1.x, U.B[4] = r1.y, U.B[5] = r1.z, U.o[1] = r1.w;
+  U.B[6] = r2.x, U.B[7] = r2.y, U.B[8] = r2.z, U.o[2] = r2.w;
+}
+// ... and of the output view v: its matrix and origin
+DEV void fuse_load_own(const float4* __restrict__ tab, uint32_t v, ptmf_view& V) {
+  const float4* p = tab + (size_t)kFuseRow * v;
+  const float4 c0 = ldu(p), c1 = ldu(p + 1), c2 = ldu(p + 2), c3 = ldu(p + 3);
+  V.m[0] = c0.x, V.m[1] = c0.y, V.m[2] = c0.z, V.m[3] = c0.w, V.m[4] = c1.x, V.m[5] = c1.y, V.m[6] = c1.z, V.m[7] = c1.w;
+  V.m[8] = c2.x, V.m[9] = c2.y, V.m[10] = c2.z, V.m[11] = c2.w, V.m[12] = c3.x, V.m[13] = c3.y, V.m[14] = c3.z, V.m[15] = c3.w;
+  V.o[0] = ldu(p + 4).w, V.o[1] = ldu(p + 5).w, V.o[2] = ldu(p + 6).w;
+}
+
+// Keeps the loads of one pixel's four sums together: every value the arithmetic reads is an operand here, so none of the loads can be sunk into one of the branches
+// that follow (validity is a chain of tests: left alone, the compiler loads A and I first, S behind the first test and N behind the second — three round trips).
+DEV void fuse_loaded(const float4& S, const float4& N, const float4& A, const float4& I) {
+  asm volatile("" ::"v"(S.x), "v"(S.y), "v"(S.z), "v"(S.w), "v"(N.x), "v"(N.y), "v"(N.z), "v"(N.w), "v"(A.x), "v"(A.y), "v"(A.z), "v"(A.w), "v"(I.z));
+}
+
+// colour: [n_stack][npix] float4 (sums, or means with k.F = 1); layers: [n_stack][3][npix] float4; out: [n_stack][npix] float4; tab: kFuseRow float4 per view of the
+// stack; lamb: one byte per material index or nullptr.  grid: x = (tiles of 64 columns x rows) / 4, z = output view - view0; block 256.
+__global__ __launch_bounds__(kBlock) void k_fuse(const float4* __restrict__ colour, const float4* __restrict__ layers, float4* __restrict__ out, const float4* __restrict__ tab,
+                                                 const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k) {
+  const uint32_t tiles_x = ((uint32_t)W + 63u) / 64u;
+  const uint32_t tile = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);  // wave-uniform
+  const uint32_t y = tile / tiles_x;
+  if (y >= (uint32_t)H) return;
+  const int x = (int)((tile - y * tiles_x) * 64u + (threadIdx.x & 63u));
+  if (x >= W) return;
+  const size_t npix = (size_t)W * (size_t)H;
+  const uint32_t v = view0 + blockIdx.z;
+  const uint32_t idx = y * (uint32_t)W + (uint32_t)x;
+  const float4* Lv = layers + (size_t)v * 3 * npix;
+  const float4 Sp = colour[(size_t)v * npix + idx], Np = Lv[idx], Ap = Lv[npix + idx], Ip = Lv[2 * npix + idx];
+  fuse_loaded(Sp, Np, Ap, Ip);
+  const ptmd_f4 S = dn_f4(Sp), N = dn_f4(Np), A = dn_f4(Ap), I = dn_f4(Ip);
+  ptmd_f4 dp, gp;
+  float num[3] = {0.0f, 0.0f, 0.0f}, den = 0.0f;
+  const int fused = ptmd_prepare(S, N, A, I, k.F, k.floor, &dp, &gp) && ptmf_fusable(dp.w, lamb, n_materials);
+  if (fused) {
+    ptmf_view V;
+    fuse_load_own(tab, v, V);
+    float X[3];
+    ptmf_world(&k, &V, x, idx, gp.w, X);
+    const uint32_t u0 = v > (uint32_t)k.radius ? v - (uint32_t)k.radius : 0u;
+    const uint32_t u1 = min(n_stack - 1u, v + (uint32_t)k.radius);
+    for (uint32_t u = u0; u <= u1; u++) {
+      if (u == v) {
+        ptmf_own(dp, num, &den);
+        continue;
+      }
+      ptmf_view U;
+      fuse_load_neighbour(tab, u, U);
+      int qx, qy;
+      float r;
+      if (!ptmf_project(&k, &U, X, &qx, &qy, &r)) continue;
+      const size_t q = (size_t)qy * (size_t)W + (size_t)qx;
+      const float4* Lu = layers + (size_t)u * 3 * npix;
+      const float4 Sq = colour[(size_t)u * npix + q], Nq = Lu[q], Aq = Lu[npix + q], Iq = Lu[2 * npix + q];  // four independent gathers
+      fuse_loaded(Sq, Nq, Aq, Iq);
+      ptmf_sample(&k, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), num, &den);
+    }
+  }
+  out[(size_t)v * npix + idx] = dn_float4(ptmf_output(&k, S, A, fused, num, den));
+}
+
+}  // namespace ptmi

@@ -20,6 +20,7 @@
 
 #include "../../include/ptmi.h"
 #include "../../include/ptmi_denoise.h"
+#include "../../include/ptmi_fuse.h"
 
 namespace {
 // Math.min / Math.max (lib/BVH/AABB.js:8-28) on finite values: -0 < +0 whatever the argument order
@@ -712,6 +713,72 @@ extern "C" int ptmi_denoise_reference(const float* colour_sums, const float* lay
     }
     const std::vector<ptmd_f4>& last = d[P.levels & 1];
     for (size_t p = 0; p < npix; p++) O[p] = ptmd_remodulate(S[p], L[npix + p], frame_num, P.albedo_floor, last[p]);
+  }
+  return PTMI_OK;
+}
+
+// ---- cross-view fusion on the host (ptmi_fuse_reference) ----
+extern "C" void ptmi_default_fuse_params(ptmi_fuse_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->radius = 4;
+  p->sigma_normal = 0.25f;
+  p->sigma_depth = 0.1f;
+  p->albedo_floor = 1e-3f;
+}
+
+// A plain loop over output views, pixels and neighbour views through include/ptmi_fuse.h, the header the kernel of ptmi_fuse_views compiles.  Nothing is tiled,
+// threaded or reordered.
+extern "C" int ptmi_fuse_reference(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
+                                   const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
+  if (!colour || !layers || !views16 || !out || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
+  ptmi_fuse_params P;
+  if (params) P = *params;
+  else ptmi_default_fuse_params(&P);
+  if (!ptmf_params_ok(P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor)) return PTMI_ERR_INVALID_ARG;
+  if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
+  if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return PTMI_ERR_INVALID_ARG;
+  std::vector<ptmf_view> tab;
+  try {
+    tab.resize(n_images);
+  } catch (const std::bad_alloc&) {
+    return PTMI_ERR_NO_MEMORY;
+  }
+  for (uint32_t v = 0; v < n_images; v++)
+    if (!ptmf_make_view(views16 + 16 * (size_t)v, &tab[v])) return PTMI_ERR_INVALID_ARG;
+  const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
+  const size_t npix = (size_t)w * (size_t)h;
+  const ptmd_f4* S = reinterpret_cast<const ptmd_f4*>(colour);
+  const ptmd_f4* L = reinterpret_cast<const ptmd_f4*>(layers);
+  ptmd_f4* O = reinterpret_cast<ptmd_f4*>(out);
+  for (uint32_t v = 0; v < n_images; v++) {
+    const ptmd_f4* Lv = L + (size_t)v * 3 * npix;
+    const uint32_t u0 = v > (uint32_t)P.radius ? v - (uint32_t)P.radius : 0u, u1 = std::min(n_images - 1u, v + (uint32_t)P.radius);
+    for (int y = 0; y < h; y++)
+      for (int x = 0; x < w; x++) {
+        const uint32_t idx = (uint32_t)y * (uint32_t)w + (uint32_t)x;
+        const ptmd_f4 Sp = S[(size_t)v * npix + idx], Ap = Lv[npix + idx];
+        ptmd_f4 dp, gp;
+        float num[3] = {0.0f, 0.0f, 0.0f}, den = 0.0f;
+        const int fused = ptmd_prepare(Sp, Lv[idx], Ap, Lv[2 * npix + idx], k.F, k.floor, &dp, &gp) && ptmf_fusable(dp.w, lambertian, n_materials);
+        if (fused) {
+          float X[3];
+          ptmf_world(&k, &tab[v], x, idx, gp.w, X);
+          for (uint32_t u = u0; u <= u1; u++) {
+            if (u == v) {
+              ptmf_own(dp, num, &den);
+              continue;
+            }
+            int qx, qy;
+            float r;
+            if (!ptmf_project(&k, &tab[u], X, &qx, &qy, &r)) continue;
+            const size_t q = (size_t)qy * (size_t)w + (size_t)qx;
+            const ptmd_f4* Lu = L + (size_t)u * 3 * npix;
+            ptmf_sample(&k, dp, gp, r, S[(size_t)u * npix + q], Lu[q], Lu[npix + q], Lu[2 * npix + q], num, &den);
+          }
+        }
+        O[(size_t)v * npix + idx] = ptmf_output(&k, Sp, Ap, fused, num, den);
+      }
   }
   return PTMI_OK;
 }

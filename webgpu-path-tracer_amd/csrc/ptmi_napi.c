@@ -47,6 +47,10 @@ FN(ptmi_release_aov)
 FN(ptmi_denoise_views)
 FN(ptmi_read_denoised)
 FN(ptmi_release_denoised)
+FN(ptmi_default_fuse_params)
+FN(ptmi_fuse_views)
+FN(ptmi_read_fused)
+FN(ptmi_release_fused)
 FN(ptmi_synchronize)
 FN(ptmi_read_framebuffer)
 FN(ptmi_write_framebuffer)
@@ -95,7 +99,7 @@ static int load_lib(char* err, size_t errlen) {
   }
   LOAD(ptmi_version) LOAD(ptmi_last_error) LOAD(ptmi_create) LOAD(ptmi_create_multi) LOAD(ptmi_prepare) LOAD(ptmi_destroy) LOAD(ptmi_default_params) LOAD(ptmi_default_denoise_params) LOAD(ptmi_set_params)
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
-  LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
+  LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
   LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah)
   LOAD(ptmi_obj_parse) LOAD(ptmi_free) LOAD(ptmi_device_count) LOAD(ptmi_reduce_info)
   return 0;
@@ -580,6 +584,80 @@ static napi_value js_release_denoised(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* fuseViews(ctx, views, frameNum, source, firstView, nViews, params | null): ptmi_fuse_views — views holds the matrices of ALL views of the stack; params =
+ * {radius, sigmaNormal, sigmaDepth, albedoFloor}, every field optional (ptmi_default_fuse_params fills the rest) */
+static napi_value js_fuse_views(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (get_args(env, info, 7, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  void* data;
+  size_t len;
+  if (typed(env, a[1], napi_float32_array, "fuseViews(views)", &data, &len)) return NULL;
+  if (len == 0 || len % 16 != 0) {
+    napi_throw_range_error(env, NULL, "fuseViews: views must hold 16 floats for each view of the stack, one view at least");
+    return NULL;
+  }
+  double frame_num;
+  int32_t source;
+  uint32_t first, n_views;
+  CHECK_NAPI(napi_get_value_double(env, a[2], &frame_num));
+  CHECK_NAPI(napi_get_value_int32(env, a[3], &source));
+  CHECK_NAPI(napi_get_value_uint32(env, a[4], &first));
+  CHECK_NAPI(napi_get_value_uint32(env, a[5], &n_views));
+  if ((uint64_t)first + n_views > len / 16) {
+    napi_throw_range_error(env, NULL, "fuseViews: views must hold the matrices of all views of the stack");
+    return NULL;
+  }
+  ptmi_fuse_params P;
+  p_ptmi_default_fuse_params(&P);
+  napi_valuetype t;
+  CHECK_NAPI(napi_typeof(env, a[6], &t));
+  if (t == napi_object) {
+    static const char* names[4] = {"radius", "sigmaNormal", "sigmaDepth", "albedoFloor"};
+    float* fields[4] = {NULL, &P.sigma_normal, &P.sigma_depth, &P.albedo_floor};
+    for (int k = 0; k < 4; k++) {
+      bool has = false;
+      napi_value v;
+      CHECK_NAPI(napi_has_named_property(env, a[6], names[k], &has));
+      if (!has) continue;
+      double d;
+      CHECK_NAPI(napi_get_named_property(env, a[6], names[k], &v));
+      CHECK_NAPI(napi_get_value_double(env, v, &d));
+      if (k == 0) P.radius = (int32_t)d;
+      else *fields[k] = (float)d;
+    }
+  }
+  int st = p_ptmi_fuse_views(c, &P, (const float*)data, (float)frame_num, source, first, n_views);
+  if (st) return throw_status(env, c, st, "ptmi_fuse_views");
+  return NULL;
+}
+
+static napi_value js_read_fused(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (get_args(env, info, 3, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  uint32_t view;
+  CHECK_NAPI(napi_get_value_uint32(env, a[1], &view));
+  void* data;
+  size_t len;
+  if (typed(env, a[2], napi_float32_array, "readFused(out)", &data, &len)) return NULL;
+  int st = p_ptmi_read_fused(c, view, (float*)data, len * 4);
+  if (st) return throw_status(env, c, st, "ptmi_read_fused");
+  return a[2];
+}
+
+static napi_value js_release_fused(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (get_args(env, info, 1, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  int st = p_ptmi_release_fused(c);
+  if (st) return throw_status(env, c, st, "ptmi_release_fused");
+  return NULL;
+}
+
 static napi_value js_synchronize(napi_env env, napi_callback_info info) {
   napi_value a[1];
   if (get_args(env, info, 1, a)) return NULL;
@@ -864,7 +942,7 @@ static napi_value init(napi_env env, napi_value exports) {
   } fns[] = {
       {"version", js_version}, {"create", js_create}, {"destroy", js_destroy}, {"defaultParams", js_default_params}, {"setParams", js_set_params},
       {"upload", js_upload}, {"resize", js_resize}, {"clear", js_clear}, {"setShard", js_set_shard}, {"renderFrame", js_render_frame},
-      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
+      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
       {"resolveRGBA8", js_resolve}, {"setCounters", js_set_counters}, {"setTiming", js_set_timing}, {"stats", js_stats},
       {"resetStats", js_reset_stats}, {"buildBVH", js_build_bvh}, {"buildBVHSAH", js_build_bvh_sah}, {"buildBVHDevice", js_build_bvh_device}, {"parseObj", js_parse_obj},
       {"deviceCount", js_device_count}, {"reduceInfo", js_reduce_info},

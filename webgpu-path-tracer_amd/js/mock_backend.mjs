@@ -14,5 +14,8 @@ export class MockBackend {
   denoiseViews(frameNum, firstView, nViews, params = null) { this.calls.push(['denoiseViews', frameNum, firstView, nViews, params]); }
   readDenoised(view, out) { this.calls.push(['readDenoised', view]); return out || new Float32Array(this.width * this.height * 4); }
   releaseDenoised() { this.calls.push(['releaseDenoised']); }
+  fuseViews(views, frameNum, source, firstView, nViews, params = null) { this.calls.push(['fuseViews', views.length / 16, frameNum, source, firstView, nViews, params]); }
+  readFused(view, out) { this.calls.push(['readFused', view]); return out || new Float32Array(this.width * this.height * 4); }
+  releaseFused() { this.calls.push(['releaseFused']); }
   synchronize() {}
 }

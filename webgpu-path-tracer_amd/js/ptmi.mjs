@@ -46,6 +46,12 @@ export class Ptmi {
   denoiseViews(frameNum, firstView, nViews, params = null) { this.native.denoiseViews(this.h, frameNum, firstView, nViews, params); }
   readDenoised(view, out = new Float32Array(this.width * this.height * 4)) { return this.native.readDenoised(this.h, view, out); }
   releaseDenoised() { this.native.releaseDenoised(this.h); }
+  // Cross-view fusion (ptmi_fuse_views): output views [firstView, firstView + nViews) gather their neighbours of the stack by reprojection into the fused stack (mean
+  // radiance); views = the matrices of ALL views of the stack; source 0 = the view stack (frameNum = the frames each image sums), 1 = the denoised stack;
+  // params = {radius, sigmaNormal, sigmaDepth, albedoFloor}, all optional.
+  fuseViews(views, frameNum, source, firstView, nViews, params = null) { this.native.fuseViews(this.h, views, frameNum, source, firstView, nViews, params); }
+  readFused(view, out = new Float32Array(this.width * this.height * 4)) { return this.native.readFused(this.h, view, out); }
+  releaseFused() { this.native.releaseFused(this.h); }
   synchronize() { this.native.synchronize(this.h); }
   prepare() { this.native.prepare(this.h); }
   buildSceneBVHSAH() { this.native.buildSceneBVHSAH(this.h); }   // the same with the reference's never-called SAH builder (lib/BVH/bvhNode.js:108-283): opt-in

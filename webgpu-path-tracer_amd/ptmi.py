@@ -24,6 +24,8 @@ SYMBOLS = [
     "ptmi_render_aov", "ptmi_read_aov", "ptmi_aov_device_ptr", "ptmi_release_aov", "ptmi_camera_rays",
     "ptmi_default_denoise_params", "ptmi_denoise_views", "ptmi_read_denoised", "ptmi_resolve_denoised_rgba8", "ptmi_denoised_device_ptr", "ptmi_release_denoised",
     "ptmi_denoise_images", "ptmi_denoise_reference",
+    "ptmi_default_fuse_params", "ptmi_fuse_views", "ptmi_read_fused", "ptmi_resolve_fused_rgba8", "ptmi_fused_device_ptr", "ptmi_release_fused",
+    "ptmi_fuse_images", "ptmi_fuse_reference",
 ]
 
 
@@ -39,6 +41,12 @@ class DenoiseParams(ctypes.Structure):
     _fields_ = [
         ("levels", ctypes.c_int32), ("sigma_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float), ("sigma_colour", ctypes.c_float),
         ("albedo_floor", ctypes.c_float), ("reserved", ctypes.c_int32 * 3),
+    ]
+
+
+class FuseParams(ctypes.Structure):
+    _fields_ = [
+        ("radius", ctypes.c_int32), ("sigma_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float), ("albedo_floor", ctypes.c_float), ("reserved", ctypes.c_int32 * 4),
     ]
 
 
@@ -161,6 +169,17 @@ def load_library(build=False, path=None):
         L.ptmi_release_denoised.argtypes = [vp]
         L.ptmi_denoise_images.argtypes = [vp, fp, fp, i32, i32, u32, ctypes.c_float, dp, fp]
         L.ptmi_denoise_reference.argtypes = [fp, fp, i32, i32, u32, ctypes.c_float, dp, fp]
+    if hasattr(L, "ptmi_fuse_views"):  # (an older A/B build loaded through PTMI_LIB has no cross-view fusion)
+        up = ctypes.POINTER(FuseParams)
+        L.ptmi_default_fuse_params.argtypes = [up]
+        L.ptmi_default_fuse_params.restype = None
+        L.ptmi_fuse_views.argtypes = [vp, up, fp, ctypes.c_float, i32, u32, u32]
+        L.ptmi_read_fused.argtypes = [vp, u32, fp, sz]
+        L.ptmi_resolve_fused_rgba8.argtypes = [vp, u32, fp, sz]
+        L.ptmi_fused_device_ptr.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(u32)]
+        L.ptmi_release_fused.argtypes = [vp]
+        L.ptmi_fuse_images.argtypes = [vp, fp, fp, fp, i32, i32, u32, ctypes.c_float, ctypes.c_float, fp, u32, up, fp]
+        L.ptmi_fuse_reference.argtypes = [fp, fp, fp, i32, i32, u32, ctypes.c_float, ctypes.c_float, fp, u32, up, fp]
     if explicit:
         _libs[path] = L
     else:
@@ -209,6 +228,35 @@ def denoise_reference(colour_sums, layers, frame_num, params=None, lib=None):
     st = (lib or load_library()).ptmi_denoise_reference(_ptr(c), _ptr(l), c.shape[2], c.shape[1], c.shape[0], float(frame_num), None if params is None else ctypes.byref(params), _ptr(out))
     if st != 0:
         raise PtmiError(st, "ptmi_denoise_reference failed")
+    return out
+
+
+def default_fuse_params(lib=None, **kw):
+    """ptmi_default_fuse_params (radius 4, sigma_normal 0.25, sigma_depth 0.1, albedo_floor 1e-3) with fields replaced by keyword."""
+    p = FuseParams()
+    (lib or load_library()).ptmi_default_fuse_params(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _fuse_arrays(colour, layers, views, lambertian):
+    c, l, out = _denoise_arrays(colour, layers)
+    v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+    assert v.shape[0] == c.shape[0], "views: one (16,) column-major matrix per image"
+    t = None if lambertian is None else np.ascontiguousarray(np.asarray(lambertian) != 0, np.uint8).reshape(-1)
+    return c, l, v, t, out
+
+
+def fuse_reference(colour, layers, views, frame_num, fov_degrees=60.0, lambertian=None, params=None, lib=None):
+    """ptmi_fuse_reference: the cross-view fusion of Context.fuse_views on host arrays, on the CPU (no GPU needed) — colour (n, H, W, 4) RGBA sums of `frame_num`
+    frames, layers (n, 3, H, W, 4) as Context.read_aov gives them, views (n, 16); lambertian: one truth value per material index (None: every material fuses).
+    Returns (n, H, W, 4) mean radiance, the kernel's bits."""
+    c, l, v, t, out = _fuse_arrays(colour, layers, views, lambertian)
+    st = (lib or load_library()).ptmi_fuse_reference(_ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], float(frame_num), float(fov_degrees),
+                                                     None if t is None else _ptr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params), _ptr(out))
+    if st != 0:
+        raise PtmiError(st, "ptmi_fuse_reference failed")
     return out
 
 
@@ -419,6 +467,43 @@ class Context:
         """ptmi_denoise_images: the kernels of denoise_views on host arrays of any size (see denoise_reference for the shapes); synchronous."""
         c, l, out = _denoise_arrays(colour_sums, layers)
         self._ck(self.lib.ptmi_denoise_images(self.h, _ptr(c), _ptr(l), c.shape[2], c.shape[1], c.shape[0], float(frame_num), None if params is None else ctypes.byref(params), _ptr(out)))
+        return out
+
+    def fuse_views(self, views, frame_num=1.0, source=0, first_view=0, n_views=None, params=None):
+        """ptmi_fuse_views: fuses output views [first_view, first_view + n_views) across their neighbours in the stack by reprojection into the context's fused
+        stack.  `views`: (V, 16), the matrices of ALL views of the stack; source 0: the view stack, whose images sum `frame_num` frames; source 1: the denoised
+        stack.  params: FuseParams (default_fuse_params).  n_views=None: up to the end of the stack.  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        n_stack = self.views_device_ptr()[2]
+        assert v.shape[0] == n_stack, "views: the matrices of all %d views of the stack" % n_stack
+        if n_views is None:
+            n_views = n_stack - first_view
+        self._ck(self.lib.ptmi_fuse_views(self.h, None if params is None else ctypes.byref(params), _ptr(v), float(frame_num), int(source), first_view, n_views))
+
+    def read_fused(self, view):
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(self.lib.ptmi_read_fused(self.h, view, _ptr(out), out.nbytes))
+        return out
+
+    def resolve_fused_rgba8(self, view):
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        self._ck(self.lib.ptmi_resolve_fused_rgba8(self.h, view, _ptr(out), out.nbytes))
+        return out
+
+    def fused_device_ptr(self):
+        """(device pointer, bytes, n_views) of the fused stack: one contiguous [n_views][H][W][4] float32 array of mean radiance."""
+        p, n, v = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_uint32()
+        self._ck(self.lib.ptmi_fused_device_ptr(self.h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(v)))
+        return p.value, n.value, v.value
+
+    def release_fused(self):
+        self._ck(self.lib.ptmi_release_fused(self.h))
+
+    def fuse_images(self, colour, layers, views, frame_num, fov_degrees=60.0, lambertian=None, params=None):
+        """ptmi_fuse_images: the kernel of fuse_views on host arrays of any size (see fuse_reference for the shapes); synchronous."""
+        c, l, v, t, out = _fuse_arrays(colour, layers, views, lambertian)
+        self._ck(self.lib.ptmi_fuse_images(self.h, _ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], float(frame_num), float(fov_degrees),
+                                           None if t is None else _ptr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params), _ptr(out)))
         return out
 
     def camera_rays(self, view16, frame):
