@@ -89,6 +89,25 @@ struct PeerWorker {
   }
 };
 
+// The context's stacks of W x H float4 images, one allocation per kind.  A row per kind: images per view, the noun and the making call of the error texts, and whether
+// the stack is derived from the view stack (it has that stack's size and goes with it).
+enum StackKind { STACK_NONE = -1, STACK_VIEWS = 0, STACK_FEATURES, STACK_DENOISED, STACK_FUSED, N_STACKS };  // (STACK_NONE: ImageRef's accumulation buffer)
+struct StackInfo {
+  uint32_t images_per_view;
+  const char *noun, *maker;
+  bool derived;
+};
+constexpr StackInfo kStackInfo[N_STACKS] = {
+    {1, "view stack", "ptmi_render_views", false},      // RGBA f32 sums
+    {3, "feature stack", "ptmi_render_aov", false},     // k_aov's three layers per view
+    {1, "denoised stack", "ptmi_denoise_views", true},  // RGBA f32 means
+    {1, "fused stack", "ptmi_fuse_views", true},        // RGBA f32 means
+};
+struct Stack {
+  DBuf buf;
+  uint32_t n = 0;  // views
+};
+
 // (Tuning — the PTMI_* environment knobs, their domains and their parsing: ptmi_tuning.h)
 
 struct ptmi_ctx {
@@ -125,27 +144,12 @@ struct ptmi_ctx {
   DBuf d_fb_own;
   float4* fb = nullptr;
   size_t fb_bytes = 0;
-  // ptmi_render_views: the view stack — n_views images of W x H RGBA f32 sums, one allocation — and the last call's view table (ViewTab: kViewRow float4 per view),
-  // uploaded from a pinned staging copy so that the call stays asynchronous; `view_rows_sent` marks the point where the stream has read that copy
-  DBuf d_views, d_view_rows;
-  uint32_t n_views = 0;
-  float* h_view_rows = nullptr;
-  size_t h_view_rows_cap = 0;
-  hipEvent_t view_rows_sent = nullptr;
-  // ptmi_render_aov: the feature stack — n_aov_views x 3 images of W x H float4 (k_aov), one allocation; its calls share the view table above
-  DBuf d_aov;
-  uint32_t n_aov_views = 0;
-  // ptmi_denoise_views: the denoised stack — as many images as the view stack has, W x H RGBA f32 means, one allocation that goes when the view stack's size changes —
-  // and the filter's scratch: three packed float4 images (d ping, d pong, n + z) per view of a batch (denoise_batch_views)
-  DBuf d_denoised, d_denoise_scratch;
-  uint32_t n_denoised = 0;
-  // ptmi_fuse_views: the fused stack — as many images as the view stack has, W x H RGBA f32 means, one allocation that goes when the view stack's size changes — and
-  // the call's table (kFuseRow float4 per view of the stack, then one byte per material), uploaded from a pinned staging copy like the view table above
-  DBuf d_fused, d_fuse_tab;
-  uint32_t n_fused = 0;
-  float* h_fuse_tab = nullptr;
-  size_t h_fuse_tab_cap = 0;
-  hipEvent_t fuse_tab_sent = nullptr;
+  // The image stacks (StackKind, kStackInfo): per kind one allocation of n x images-per-view images of W x H float4.  The denoised and fused stacks have the view stack's
+  // size and go with it (drop_stack).
+  Stack stacks[N_STACKS];
+  DBuf d_denoise_scratch;  // ptmi_denoise_views: three packed float4 images (d ping, d pong, n + z) per view of a batch (denoise_batch_views)
+  StagedTable view_rows;   // the last ptmi_render_views / ptmi_render_aov call's view table (ViewTab: kViewRow float4 per view)
+  StagedTable fuse_tab;    // the last ptmi_fuse_views call's table (kFuseRow float4 per view of the stack, then one byte per material)
   int rank = 0, world = 1, tile = 64;
 
   size_t path_cap = 0;
@@ -227,6 +231,42 @@ std::vector<ptmi_ctx*> local_devices(ptmi_ctx* c) {
       return fail((c), _e == hipErrorOutOfMemory ? PTMI_ERR_NO_MEMORY : PTMI_ERR_DEVICE,              \
                   std::string(#expr) + ": " + hipGetErrorString(_e));                                 \
   } while (0)
+
+// ---- the image stacks (StackKind): what their calls share ----
+size_t stack_bytes(const ptmi_ctx* c, StackKind k, uint32_t n) { return (size_t)n * kStackInfo[k].images_per_view * (size_t)c->W * (size_t)c->H * 16; }
+
+// One device's stack `k` goes — and with the view stack those derived from it, which have its size: the one place that says so.
+void drop_stack(ptmi_ctx* q, StackKind k) {
+  q->stacks[k].buf.release();
+  q->stacks[k].n = 0;
+  if (k == STACK_VIEWS)
+    for (int d = 0; d < N_STACKS; d++)
+      if (kStackInfo[d].derived) drop_stack(q, (StackKind)d);
+}
+
+// what a call that reads stack `k` asks of it: the stack exists, and `view` is one of its views
+int check_stack(ptmi_ctx* c, StackKind k, const char* who, uint32_t view) {
+  const Stack& s = c->stacks[k];
+  if (!s.buf.p || s.n == 0) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no " + kStackInfo[k].noun + ": call " + kStackInfo[k].maker + " first");
+  if (view >= s.n) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": view " + std::to_string(view) + " of " + std::to_string(s.n));
+  return PTMI_OK;
+}
+
+// Making a stack of n views, in two halves, so that a call that fails for want of memory leaves the old images as they were.  reserve_stack allocates the new stack aside —
+// only where the size differs or there is none — and touches nothing else; commit_stack, after everything else that can fail that way, moves it in and zeroes it.
+int reserve_stack(ptmi_ctx* c, StackKind k, uint32_t n, DBuf* fresh) {
+  if (c->stacks[k].buf.p && c->stacks[k].n == n) return PTMI_OK;
+  HIP_TRY(c, fresh->ensure(stack_bytes(c, k, n)));
+  return PTMI_OK;
+}
+int commit_stack(ptmi_ctx* c, StackKind k, uint32_t n, DBuf* fresh) {
+  if (!fresh->p) return PTMI_OK;
+  drop_stack(c, k);
+  c->stacks[k].buf = std::move(*fresh);
+  c->stacks[k].n = n;
+  HIP_TRY(c, hipMemsetAsync(c->stacks[k].buf.p, 0, stack_bytes(c, k, n), c->stream));
+  return PTMI_OK;
+}
 
 hipEvent_t get_event(ptmi_ctx* c) {
   if (!c->ev_pool.empty()) {
@@ -1209,17 +1249,15 @@ __global__ __launch_bounds__(kBlock) void k_add_into_signed_zero(float4* __restr
 // The one collective of a multi-device render: sum the per-device accumulation buffers into d_fb_gather on local device 0.
 // Every pixel is non-zero in exactly one of them (x + 0 = x), so the sum is the single-GPU image bit for bit whatever
 // the order.  The per-device buffers are left as they are, so rendering can go on afterwards.
-// `img`: which W x H float4 image of every device — its accumulation buffer, image `index` of its view stack (ptmi_render_views), or image `index` = 3 * view + layer
-// of its feature stack (ptmi_render_aov), or image `index` of its denoised stack (ptmi_denoise_views: single-device contexts only) or of its fused stack
-// (ptmi_fuse_views: the same).
-enum ImageStack { IMG_FRAMEBUFFER = 0, IMG_VIEWS = 1, IMG_AOV = 2, IMG_DENOISED = 3, IMG_FUSED = 4 };
+// `img`: which W x H float4 image of every device — its accumulation buffer, or image `index` (view x images per view + layer) of its stack `kind` (the denoised and
+// fused stacks: single-device contexts only).
 struct ImageRef {
-  ImageStack of = IMG_FRAMEBUFFER;
+  StackKind kind = STACK_NONE;  // STACK_NONE: the accumulation buffer
   size_t index = 0;
 };
 float4* image_of(const ptmi_ctx* q, ImageRef img) {
-  if (img.of == IMG_FRAMEBUFFER) return q->fb;
-  return (img.of == IMG_VIEWS ? q->d_views : img.of == IMG_AOV ? q->d_aov : img.of == IMG_DENOISED ? q->d_denoised : q->d_fused).as<float4>() + img.index * (size_t)q->W * (size_t)q->H;
+  if (img.kind == STACK_NONE) return q->fb;
+  return q->stacks[img.kind].buf.as<float4>() + img.index * (size_t)q->W * (size_t)q->H;
 }
 int gather_framebuffer(ptmi_ctx* c, float4** out, ImageRef img = ImageRef{}) {
   if (!c->multi) {
@@ -1328,7 +1366,7 @@ int gather_framebuffer(ptmi_ctx* c, float4** out, ImageRef img = ImageRef{}) {
         HIP_TRY(c, hipMemcpyPeerAsync(c->d_fb_stage.p, c->device, src, q->device, bytes, c->stream));
         src = c->d_fb_stage.as<float4>();
       }
-      if (img.of == IMG_AOV) hipLaunchKernelGGL(k_add_into_signed_zero, dim3(grid), dim3(kBlock), 0, c->stream, g, src, n4);  // (a -0.0 normal component stays -0.0)
+      if (img.kind == STACK_FEATURES) hipLaunchKernelGGL(k_add_into_signed_zero, dim3(grid), dim3(kBlock), 0, c->stream, g, src, n4);  // (a -0.0 normal component stays -0.0)
       else hipLaunchKernelGGL(k_add_into, dim3(grid), dim3(kBlock), 0, c->stream, g, src, n4);
       HIP_TRY(c, hipGetLastError());
     }
@@ -1548,10 +1586,8 @@ void ptmi_destroy(ptmi_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   drain_spans(c);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-  if (c->view_rows_sent) (void)hipEventDestroy(c->view_rows_sent);
-  if (c->h_view_rows) (void)hipHostFree(c->h_view_rows);
-  if (c->fuse_tab_sent) (void)hipEventDestroy(c->fuse_tab_sent);
-  if (c->h_fuse_tab) (void)hipHostFree(c->h_fuse_tab);
+  c->view_rows.release();
+  c->fuse_tab.release();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;  // its device buffers (DBuf) are freed here, with its device current and its stream drained
 }
@@ -1764,15 +1800,8 @@ int ptmi_resize(ptmi_ctx* c, int width, int height) {
   c->fb_bytes = bytes;
   c->W = width;
   c->H = height;
-  c->d_views.release();  // the view stack belongs to the old size
-  c->n_views = 0;
-  c->d_aov.release();  // ... and so does the feature stack
-  c->n_aov_views = 0;
-  c->d_denoised.release();  // ... and what was filtered from them, with the filter's scratch
-  c->n_denoised = 0;
-  c->d_denoise_scratch.release();
-  c->d_fused.release();  // ... and what was fused from them
-  c->n_fused = 0;
+  for (int k = 0; k < N_STACKS; k++) drop_stack(c, (StackKind)k);  // the stacks belong to the old size
+  c->d_denoise_scratch.release();                                  // ... and so does the filter's scratch
   HIP_TRY(c, hipMemsetAsync(c->fb, 0, bytes, c->stream));
   for (ptmi_ctx* q : c->peers) {
     int r = ptmi_resize(q, width, height);
@@ -1903,20 +1932,11 @@ int ptmi_render(ptmi_ctx* c, const float* view16, uint32_t first_frame, uint32_t
 // A call's view table (ViewTab: kViewRow float4 per view) for ptmi_render_views and ptmi_render_aov, in two halves so that everything that can fail for want of
 // memory happens before anything is enqueued: stage_view_rows allocates and fills the pinned staging copy, send_view_rows puts the upload on the stream.
 static int stage_view_rows(ptmi_ctx* c, const float* views16, uint32_t n_views) {
-  const size_t row_bytes = (size_t)n_views * kViewRow * 16;
-  HIP_TRY(c, c->d_view_rows.ensure(row_bytes));
-  if (row_bytes > c->h_view_rows_cap) {
-    if (c->view_rows_sent) HIP_TRY(c, hipEventSynchronize(c->view_rows_sent));
-    if (c->h_view_rows) (void)hipHostFree(c->h_view_rows);
-    c->h_view_rows = nullptr, c->h_view_rows_cap = 0;
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_view_rows, row_bytes, hipHostMallocDefault));
-    c->h_view_rows_cap = row_bytes;
-  }
-  if (!c->view_rows_sent) HIP_TRY(c, hipEventCreateWithFlags(&c->view_rows_sent, hipEventDisableTiming));
-  else HIP_TRY(c, hipEventSynchronize(c->view_rows_sent));  // the last call's upload has read the staging copy
+  float* rows = nullptr;
+  HIP_TRY(c, c->view_rows.stage((size_t)n_views * kViewRow * 16, c->stream, (void**)&rows));
   for (uint32_t v = 0; v < n_views; v++) {
     const float* m = views16 + 16 * (size_t)v;
-    float* row = c->h_view_rows + (size_t)v * kViewRow * 4;
+    float* row = rows + (size_t)v * kViewRow * 4;
     memcpy(row, m, 64);
     for (int k = 0; k < 3; k++) row[16 + k] = ((m[k] * 0.0f + m[4 + k] * 0.0f) + m[8 + k] * 0.0f) + m[12 + k] * 1.0f;  // cam_origin, as make_render_const computes it
     row[19] = 0.0f;
@@ -1924,8 +1944,7 @@ static int stage_view_rows(ptmi_ctx* c, const float* views16, uint32_t n_views) 
   return PTMI_OK;
 }
 static int send_view_rows(ptmi_ctx* c, uint32_t n_views) {
-  HIP_TRY(c, hipMemcpyAsync(c->d_view_rows.p, c->h_view_rows, (size_t)n_views * kViewRow * 16, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipEventRecord(c->view_rows_sent, c->stream));
+  HIP_TRY(c, c->view_rows.send((size_t)n_views * kViewRow * 16, c->stream));
   return PTMI_OK;
 }
 
@@ -1938,24 +1957,13 @@ static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views,
   r = check_renderable(c);
   if (r) return r;
   // the stack and the table: allocated before anything is enqueued
-  const size_t image_bytes = (size_t)c->W * (size_t)c->H * 16;
-  const bool fresh = !c->d_views.p || c->n_views != n_views;
-  if (fresh) {  // the new stack first: a call that fails for want of memory leaves the old images as they were
-    DBuf stack;
-    HIP_TRY(c, stack.ensure(image_bytes * n_views));
-    c->d_views = std::move(stack);
-    c->n_views = 0;  // (until it is zeroed, below)
-    c->d_denoised.release();  // the denoised stack has the view stack's size: it goes with the old one
-    c->n_denoised = 0;
-    c->d_fused.release();  // ... and so does the fused stack
-    c->n_fused = 0;
-  }
+  DBuf stack;
+  r = reserve_stack(c, STACK_VIEWS, n_views, &stack);
+  if (r) return r;
   r = stage_view_rows(c, views16, n_views);
   if (r) return r;
-  if (fresh) {
-    HIP_TRY(c, hipMemsetAsync(c->d_views.p, 0, image_bytes * n_views, c->stream));
-    c->n_views = n_views;
-  }
+  r = commit_stack(c, STACK_VIEWS, n_views, &stack);
+  if (r) return r;
   r = send_view_rows(c, n_views);
   if (r) return r;
   // (the same budget of frame slots per wavefront pass as render_one's, and the same halving)
@@ -1965,7 +1973,7 @@ static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views,
   const uint32_t n_slots = n_views * fpv;
   for (uint32_t done = 0; done < n_slots;) {
     const uint32_t nb = std::min(F, n_slots - done);
-    const ViewBatch vb{ViewTab{c->d_view_rows.as<float4>(), done, fpv, 0u}, c->d_views.as<float4>()};
+    const ViewBatch vb{ViewTab{c->view_rows.dev.as<float4>(), done, fpv, 0u}, c->stacks[STACK_VIEWS].buf.as<float4>()};
     r = render_batch(c, views16 + 16 * (size_t)(done / fpv), first_frame, (int)nb, reset ? 1 : 0, -1, 0, &vb);
     if (r == PTMI_ERR_NO_MEMORY && !c->batch_enqueued && nb > 1 && c->prm.frames_in_flight <= 0) {
       F = std::max<uint32_t>(1, nb / 2);
@@ -1982,13 +1990,6 @@ int ptmi_render_views(ptmi_ctx* c, const float* views16, uint32_t n_views, uint3
   if (n_views == 0 || frames_per_view == 0) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views: need n_views >= 1 and frames_per_view >= 1");
   if ((uint64_t)n_views * frames_per_view > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views: n_views * frames_per_view must stay below 2^31");
   return on_all_devices(c, [=](ptmi_ctx* q) { return render_views_one(q, views16, n_views, first_frame, frames_per_view, reset); }, true);
-}
-
-// what ptmi_read_view / ptmi_resolve_view_rgba8 / ptmi_views_device_ptr ask of the stack
-static int check_view(ptmi_ctx* c, const char* who, uint32_t view) {
-  if (!c->d_views.p || c->n_views == 0) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no view stack: call ptmi_render_views first");
-  if (view >= c->n_views) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": view " + std::to_string(view) + " of " + std::to_string(c->n_views));
-  return PTMI_OK;
 }
 
 // ptmi_read_framebuffer / ptmi_read_view / ptmi_read_aov: the image, gathered from the devices of a multi-device context, copied to the host
@@ -2022,44 +2023,53 @@ static int resolve_image(ptmi_ctx* c, ImageRef img, float frame_num, uint8_t* ds
   return PTMI_OK;
 }
 
-int ptmi_read_view(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) {
-  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_view: null argument");
-  if (int r = check_view(c, "ptmi_read_view", view)) return r;
-  if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_view: bytes != W*H*16");
-  return read_image(c, ImageRef{IMG_VIEWS, view}, dst, bytes);
+// What the exported calls on a stack come to after their own argument checks.  The order of the checks decides which status a caller sees: a null argument,
+// (the device pointer of a stack that exists once per GPU: a multi-device context,) the stack, the view, the layer, the byte count.
+static int read_stack(ptmi_ctx* c, StackKind k, const char* who, uint32_t view, int layer, float* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (int r = check_stack(c, k, who, view)) return r;
+  const int layers = (int)kStackInfo[k].images_per_view;
+  if (layer < 0 || layer >= layers) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": layer " + std::to_string(layer) + " of " + std::to_string(layers));
+  if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": bytes != W*H*16");
+  return read_image(c, ImageRef{k, (size_t)view * layers + (size_t)layer}, dst, bytes);
 }
-
-int ptmi_resolve_view_rgba8(ptmi_ctx* c, uint32_t view, float frame_num, uint8_t* dst, size_t bytes) {
-  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_view_rgba8: null argument");
-  if (int r = check_view(c, "ptmi_resolve_view_rgba8", view)) return r;
-  if (bytes != (size_t)c->W * c->H * 4) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_view_rgba8: bytes != W*H*4");
-  return resolve_image(c, ImageRef{IMG_VIEWS, view}, frame_num, dst, bytes);
+static int resolve_stack(ptmi_ctx* c, StackKind k, const char* who, uint32_t view, float frame_num, uint8_t* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (int r = check_stack(c, k, who, view)) return r;
+  if (bytes != (size_t)c->W * c->H * 4) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": bytes != W*H*4");
+  return resolve_image(c, ImageRef{k, view}, frame_num, dst, bytes);
 }
-
-int ptmi_views_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
-  if (!c || !p) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_views_device_ptr: null argument");
-  if (!c->peers.empty()) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_views_device_ptr: a multi-device context has one stack per GPU; use ptmi_read_view");
-  if (int r = check_view(c, "ptmi_views_device_ptr", 0)) return r;
-  *p = c->d_views.p;
-  if (bytes) *bytes = (size_t)c->n_views * c->W * c->H * 16;
-  if (n_views) *n_views = c->n_views;
+// `read_fn`: the call a multi-device context is sent to instead; nullptr for the stacks that only single-device contexts have
+static int stack_device_ptr(ptmi_ctx* c, StackKind k, const char* who, const char* read_fn, void** p, size_t* bytes, uint32_t* n_views) {
+  if (!c || !p) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (read_fn && !c->peers.empty()) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a multi-device context has one stack per GPU; use " + read_fn);
+  if (int r = check_stack(c, k, who, 0)) return r;
+  *p = c->stacks[k].buf.p;
+  if (bytes) *bytes = stack_bytes(c, k, c->stacks[k].n);
+  if (n_views) *n_views = c->stacks[k].n;
   return PTMI_OK;
 }
-
-int ptmi_release_views(ptmi_ctx* c) {
+// The stack goes on every device, and what only it needed: the filter's scratch with the denoised stack, the table with the fused one (and see drop_stack).
+static int release_stack(ptmi_ctx* c, StackKind k) {
   if (!c) return PTMI_ERR_INVALID_ARG;
-  return on_all_devices(c, [](ptmi_ctx* q) -> int {
+  return on_all_devices(c, [k](ptmi_ctx* q) -> int {
     HIP_TRY(q, hipSetDevice(q->device));
-    HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still fold into a stack that is about to go
-    q->d_views.release();
-    q->n_views = 0;
-    q->d_denoised.release();  // (it had the view stack's size)
-    q->n_denoised = 0;
-    q->d_fused.release();
-    q->n_fused = 0;
+    HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still read or write a stack that is about to go
+    drop_stack(q, k);
+    if (k == STACK_DENOISED) q->d_denoise_scratch.release();
+    if (k == STACK_FUSED) q->fuse_tab.dev.release();
     return PTMI_OK;
   });
 }
+
+int ptmi_read_view(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_VIEWS, "ptmi_read_view", view, 0, dst, bytes); }
+int ptmi_resolve_view_rgba8(ptmi_ctx* c, uint32_t view, float frame_num, uint8_t* dst, size_t bytes) {
+  return resolve_stack(c, STACK_VIEWS, "ptmi_resolve_view_rgba8", view, frame_num, dst, bytes);
+}
+int ptmi_views_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
+  return stack_device_ptr(c, STACK_VIEWS, "ptmi_views_device_ptr", "ptmi_read_view", p, bytes, n_views);
+}
+int ptmi_release_views(ptmi_ctx* c) { return release_stack(c, STACK_VIEWS); }
 
 // ---- the feature stack (ptmi_render_aov) ----
 // One device's part of ptmi_render_aov: the stack and the view table first, then one k_aov launch — one per batch of views where views x owned pixels would reach 2^31.
@@ -2070,31 +2080,27 @@ static int render_aov_one(ptmi_ctx* c, const float* views16, uint32_t n_views, u
   if (r) return r;
   r = check_renderable(c);
   if (r) return r;
-  const size_t image_bytes = (size_t)c->W * (size_t)c->H * 16;
-  const bool fresh = !c->d_aov.p || c->n_aov_views != n_views;
-  DBuf stack;  // the new stack first: a call that fails for want of memory leaves the old images as they were
-  if (fresh) HIP_TRY(c, stack.ensure(image_bytes * 3 * n_views));
+  DBuf stack;
+  r = reserve_stack(c, STACK_FEATURES, n_views, &stack);
+  if (r) return r;
   r = stage_view_rows(c, views16, n_views);
   if (r) return r;
   const RenderConst rc = make_render_const(c, views16, first_frame, (int)fpv, reset ? 1 : 0);
   const StackLayout st = stack_layout(c, 0);
   HIP_TRY(c, c->d_spill.ensure(std::max<size_t>(16, (size_t)c->num_cus * 32 * (size_t)st.spill_entries * 64 * sizeof(int2))));  // (k_bvh's and k_tail's rows: one size for all)
-  if (fresh) {
-    c->d_aov = std::move(stack);
-    c->n_aov_views = n_views;
-    HIP_TRY(c, hipMemsetAsync(c->d_aov.p, 0, image_bytes * 3 * n_views, c->stream));
-  }
+  r = commit_stack(c, STACK_FEATURES, n_views, &stack);
+  if (r) return r;
   r = send_view_rows(c, n_views);
   if (r) return r;
   if (rc.n_local == 0) return PTMI_OK;
-  const ViewTab vt{c->d_view_rows.as<float4>(), 0u, fpv, rc.n_local};
+  const ViewTab vt{c->view_rows.dev.as<float4>(), 0u, fpv, rc.n_local};
   const auto aov = with_flags([](auto na) { return &k_aov<na>; }, st.noabort);
   const uint32_t per_launch = std::max<uint32_t>(1u, 0x7fffffffu / rc.n_local);
   for (uint32_t v0 = 0; v0 < n_views; v0 += per_launch) {
     const uint32_t nv = std::min(per_launch, n_views - v0);
     const uint64_t waves = ((uint64_t)nv * rc.n_local + 63) / 64;
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(waves, (uint64_t)c->num_cus * 32));  // (at most as many blocks as d_spill has rows)
-    hipLaunchKernelGGL(aov, dim3(grid), dim3(64), st.lds_bytes, c->stream, c->S, rc, vt, c->d_aov.as<float4>(), v0, nv, reset ? 1 : 0, c->prm.stack_size, st.lds_entries,
+    hipLaunchKernelGGL(aov, dim3(grid), dim3(64), st.lds_bytes, c->stream, c->S, rc, vt, c->stacks[STACK_FEATURES].buf.as<float4>(), v0, nv, reset ? 1 : 0, c->prm.stack_size, st.lds_entries,
                        st.spill_entries, c->d_spill.as<int2>());
     HIP_TRY(c, hipGetLastError());
   }
@@ -2108,35 +2114,11 @@ int ptmi_render_aov(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_
   return on_all_devices(c, [=](ptmi_ctx* q) { return render_aov_one(q, views16, n_views, first_frame, frames_per_view, reset); }, true);
 }
 
-int ptmi_read_aov(ptmi_ctx* c, uint32_t view, int layer, float* dst, size_t bytes) {
-  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_aov: null argument");
-  if (!c->d_aov.p || c->n_aov_views == 0) return fail(c, PTMI_ERR_STATE, "ptmi_read_aov: no feature stack: call ptmi_render_aov first");
-  if (view >= c->n_aov_views) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_aov: view " + std::to_string(view) + " of " + std::to_string(c->n_aov_views));
-  if (layer < 0 || layer > 2) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_aov: layer " + std::to_string(layer) + " of 3");
-  if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_aov: bytes != W*H*16");
-  return read_image(c, ImageRef{IMG_AOV, (size_t)view * 3 + (size_t)layer}, dst, bytes);
-}
-
+int ptmi_read_aov(ptmi_ctx* c, uint32_t view, int layer, float* dst, size_t bytes) { return read_stack(c, STACK_FEATURES, "ptmi_read_aov", view, layer, dst, bytes); }
 int ptmi_aov_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
-  if (!c || !p) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_aov_device_ptr: null argument");
-  if (!c->peers.empty()) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_aov_device_ptr: a multi-device context has one stack per GPU; use ptmi_read_aov");
-  if (!c->d_aov.p || c->n_aov_views == 0) return fail(c, PTMI_ERR_STATE, "ptmi_aov_device_ptr: no feature stack: call ptmi_render_aov first");
-  *p = c->d_aov.p;
-  if (bytes) *bytes = (size_t)c->n_aov_views * 3 * c->W * c->H * 16;
-  if (n_views) *n_views = c->n_aov_views;
-  return PTMI_OK;
+  return stack_device_ptr(c, STACK_FEATURES, "ptmi_aov_device_ptr", "ptmi_read_aov", p, bytes, n_views);
 }
-
-int ptmi_release_aov(ptmi_ctx* c) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  return on_all_devices(c, [](ptmi_ctx* q) -> int {
-    HIP_TRY(q, hipSetDevice(q->device));
-    HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still write a stack that is about to go
-    q->d_aov.release();
-    q->n_aov_views = 0;
-    return PTMI_OK;
-  });
-}
+int ptmi_release_aov(ptmi_ctx* c) { return release_stack(c, STACK_FEATURES); }
 
 int ptmi_camera_rays(ptmi_ctx* c, const float* view16, uint32_t frame, float* rays6, uint32_t* rng_out) {
   if (!c || !view16 || !rays6 || !rng_out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_camera_rays: null argument");
@@ -2205,71 +2187,69 @@ static int denoise_check_args(ptmi_ctx* c, const char* who, const ptmi_denoise_p
   return PTMI_OK;
 }
 
+// What ptmi_denoise_views and ptmi_fuse_views ask of their inputs: a view stack and a feature stack of the same number of views, (the denoised stack too where it is
+// the source,) and a range of views inside them.
+static int check_source_stacks(ptmi_ctx* c, const char* who, bool need_denoised, uint32_t first_view, uint32_t n_views) {
+  if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
+  if (int r = check_stack(c, STACK_FEATURES, who, 0)) return r;
+  const uint32_t n = c->stacks[STACK_VIEWS].n, na = c->stacks[STACK_FEATURES].n;
+  if (n != na) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the view stack has " + std::to_string(n) + " views, the feature stack " + std::to_string(na));
+  if (need_denoised && c->stacks[STACK_DENOISED].n != n) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no denoised stack: call ptmi_denoise_views first");
+  if (n_views == 0 || first_view >= n || n_views > n - first_view)
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": views [" + std::to_string(first_view) + ", " + std::to_string((uint64_t)first_view + n_views) + ") of " + std::to_string(n));
+  return PTMI_OK;
+}
+
 int ptmi_denoise_views(ptmi_ctx* c, const ptmi_denoise_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   ptmi_denoise_params P;
   if (int r = denoise_check_args(c, "ptmi_denoise_views", params, frame_num, &P)) return r;
-  if (!c->d_views.p || c->n_views == 0) return fail(c, PTMI_ERR_STATE, "ptmi_denoise_views: no view stack: call ptmi_render_views first");
-  if (!c->d_aov.p || c->n_aov_views == 0) return fail(c, PTMI_ERR_STATE, "ptmi_denoise_views: no feature stack: call ptmi_render_aov first");
-  if (c->n_views != c->n_aov_views)
-    return fail(c, PTMI_ERR_STATE, "ptmi_denoise_views: the view stack has " + std::to_string(c->n_views) + " views, the feature stack " + std::to_string(c->n_aov_views));
-  if (n_views == 0 || first_view >= c->n_views || n_views > c->n_views - first_view)
-    return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_views: views [" + std::to_string(first_view) + ", " + std::to_string((uint64_t)first_view + n_views) + ") of " + std::to_string(c->n_views));
+  if (int r = check_source_stacks(c, "ptmi_denoise_views", false, first_view, n_views)) return r;
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
   const size_t npix = (size_t)c->W * (size_t)c->H;
-  const bool fresh = !c->d_denoised.p || c->n_denoised != c->n_views;
-  DBuf stack;  // the new stack first: a call that fails for want of memory leaves the old images as they were
-  if (fresh) HIP_TRY(c, stack.ensure(npix * 16 * c->n_views));
-  HIP_TRY(c, c->d_denoise_scratch.ensure(denoise_scratch_bytes(npix, n_views)));
-  if (fresh) {
-    c->d_denoised = std::move(stack);
-    c->n_denoised = c->n_views;
-    HIP_TRY(c, hipMemsetAsync(c->d_denoised.p, 0, npix * 16 * c->n_views, c->stream));
-  }
-  return denoise_enqueue(c, c->d_views.as<float4>() + (size_t)first_view * npix, c->d_aov.as<float4>() + (size_t)first_view * 3 * npix,
-                         c->d_denoised.as<float4>() + (size_t)first_view * npix, n_views, c->W, c->H, frame_num, P);
+  const uint32_t n_stack = c->stacks[STACK_VIEWS].n;
+  DBuf stack;
+  if (int r = reserve_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
+  HIP_TRY(c, c->d_denoise_scratch.ensure_idle(denoise_scratch_bytes(npix, n_views), c->stream));
+  if (int r = commit_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
+  return denoise_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)first_view * npix, c->stacks[STACK_FEATURES].buf.as<float4>() + (size_t)first_view * 3 * npix,
+                         c->stacks[STACK_DENOISED].buf.as<float4>() + (size_t)first_view * npix, n_views, c->W, c->H, frame_num, P);
 }
 
-static int check_denoised(ptmi_ctx* c, const char* who, uint32_t view) {
-  if (!c->d_denoised.p || c->n_denoised == 0) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no denoised stack: call ptmi_denoise_views first");
-  if (view >= c->n_denoised) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": view " + std::to_string(view) + " of " + std::to_string(c->n_denoised));
-  return PTMI_OK;
-}
-
-int ptmi_read_denoised(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) {
-  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_denoised: null argument");
-  if (int r = check_denoised(c, "ptmi_read_denoised", view)) return r;
-  if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_denoised: bytes != W*H*16");
-  return read_image(c, ImageRef{IMG_DENOISED, view}, dst, bytes);
-}
-
+int ptmi_read_denoised(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_DENOISED, "ptmi_read_denoised", view, 0, dst, bytes); }
 int ptmi_resolve_denoised_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t bytes) {
-  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_denoised_rgba8: null argument");
-  if (int r = check_denoised(c, "ptmi_resolve_denoised_rgba8", view)) return r;
-  if (bytes != (size_t)c->W * c->H * 4) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_denoised_rgba8: bytes != W*H*4");
-  return resolve_image(c, ImageRef{IMG_DENOISED, view}, 1.0f, dst, bytes);  // (the stack holds means: the display pass at frameNum 1)
+  return resolve_stack(c, STACK_DENOISED, "ptmi_resolve_denoised_rgba8", view, 1.0f, dst, bytes);  // (the stack holds means: the display pass at frameNum 1)
 }
-
 int ptmi_denoised_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
-  if (!c || !p) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoised_device_ptr: null argument");
-  if (!c->d_denoised.p || c->n_denoised == 0) return fail(c, PTMI_ERR_STATE, "ptmi_denoised_device_ptr: no denoised stack: call ptmi_denoise_views first");
-  *p = c->d_denoised.p;
-  if (bytes) *bytes = (size_t)c->n_denoised * c->W * c->H * 16;
-  if (n_views) *n_views = c->n_denoised;
-  return PTMI_OK;
+  return stack_device_ptr(c, STACK_DENOISED, "ptmi_denoised_device_ptr", nullptr, p, bytes, n_views);
 }
+int ptmi_release_denoised(ptmi_ctx* c) { return release_stack(c, STACK_DENOISED); }
 
-int ptmi_release_denoised(ptmi_ctx* c) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  return on_all_devices(c, [](ptmi_ctx* q) -> int {
-    HIP_TRY(q, hipSetDevice(q->device));
-    HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still write a stack that is about to go
-    q->d_denoised.release();
-    q->n_denoised = 0;
-    q->d_denoise_scratch.release();
-    return PTMI_OK;
-  });
+// ptmi_denoise_images / ptmi_fuse_images: the kernels on host arrays — colour [n][npix] float4, layers [n][3][npix] float4, out [n][npix] float4 — through device copies of
+// this call's own: the context's stacks are not touched.  `extra`: what else the kernels need on the device, allocated after the copies and, as everything that can fail
+// for want of memory, before anything is enqueued.  `enqueue(colour, layers, out)` puts the kernels on the stream; whatever it returns, the stream drains before the
+// copies (and whatever `enqueue` captured) die.  The first error wins.
+static int on_host_images(ptmi_ctx* c, const char* who, const float* colour, const float* layers, size_t npix, uint32_t n, float* out, DBuf& extra, size_t extra_bytes,
+                          const std::function<int(const float4*, const float4*, float4*)>& enqueue) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  const size_t bytes = npix * 16 * n;
+  DBuf col, lay, res;
+  HIP_TRY(c, col.ensure(bytes));
+  HIP_TRY(c, lay.ensure(bytes * 3));
+  HIP_TRY(c, res.ensure(bytes));
+  HIP_TRY(c, extra.ensure_idle(extra_bytes, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(col.p, colour, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(lay.p, layers, bytes * 3, hipMemcpyHostToDevice, c->stream));
+  int r = enqueue(col.as<float4>(), lay.as<float4>(), res.as<float4>());
+  if (r == PTMI_OK) {
+    const hipError_t e = hipMemcpyAsync(out, res.p, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) r = fail(c, PTMI_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+  }
+  const hipError_t e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess && r == PTMI_OK) r = fail(c, PTMI_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+  return r;
 }
 
 int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params, float* out) {
@@ -2277,24 +2257,9 @@ int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* laye
   ptmi_denoise_params P;
   if (int r = denoise_check_args(c, "ptmi_denoise_images", params, frame_num, &P)) return r;
   if (w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images: need w, h, n_images >= 1 and w * h < 2^31");
-  HIP_TRY(c, hipSetDevice(c->device));
-  (void)hipGetLastError();
-  const size_t npix = (size_t)w * (size_t)h, image_bytes = npix * 16;
-  DBuf col, lay, res;  // this call's own device copies: the context's stacks are not touched
-  HIP_TRY(c, col.ensure(image_bytes * n_images));
-  HIP_TRY(c, lay.ensure(image_bytes * 3 * n_images));
-  HIP_TRY(c, res.ensure(image_bytes * n_images));
-  HIP_TRY(c, c->d_denoise_scratch.ensure(denoise_scratch_bytes(npix, n_images)));
-  HIP_TRY(c, hipMemcpyAsync(col.p, colour_sums, image_bytes * n_images, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(lay.p, layers, image_bytes * 3 * n_images, hipMemcpyHostToDevice, c->stream));
-  int r = denoise_enqueue(c, col.as<float4>(), lay.as<float4>(), res.as<float4>(), n_images, w, h, frame_num, P);
-  if (r == PTMI_OK) {
-    hipError_t e = hipMemcpyAsync(out, res.p, image_bytes * n_images, hipMemcpyDeviceToHost, c->stream);
-    if (e != hipSuccess) r = fail(c, PTMI_ERR_DEVICE, std::string("ptmi_denoise_images: ") + hipGetErrorString(e));
-  }
-  hipError_t e = hipStreamSynchronize(c->stream);  // (also before the copies above are freed)
-  if (e != hipSuccess && r == PTMI_OK) r = fail(c, PTMI_ERR_DEVICE, std::string("ptmi_denoise_images: ") + hipGetErrorString(e));
-  return r;
+  const size_t npix = (size_t)w * (size_t)h;
+  return on_host_images(c, "ptmi_denoise_images", colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, denoise_scratch_bytes(npix, n_images),
+                        [&](const float4* col, const float4* lay, float4* res) { return denoise_enqueue(c, col, lay, res, n_images, w, h, frame_num, P); });
 }
 
 // ---- the fused stack (ptmi_fuse_views, ptmi_fuse_images) ----
@@ -2349,14 +2314,8 @@ int ptmi_fuse_views(ptmi_ctx* c, const ptmi_fuse_params* params, const float* vi
   if (source != 0 && source != 1) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_views: source must be 0 (the view stack) or 1 (the denoised stack)");
   ptmi_fuse_params P;
   if (int r = fuse_check_args(c, "ptmi_fuse_views", params, frame_num, source == 0, &P)) return r;
-  if (!c->d_views.p || c->n_views == 0) return fail(c, PTMI_ERR_STATE, "ptmi_fuse_views: no view stack: call ptmi_render_views first");
-  if (!c->d_aov.p || c->n_aov_views == 0) return fail(c, PTMI_ERR_STATE, "ptmi_fuse_views: no feature stack: call ptmi_render_aov first");
-  if (c->n_views != c->n_aov_views)
-    return fail(c, PTMI_ERR_STATE, "ptmi_fuse_views: the view stack has " + std::to_string(c->n_views) + " views, the feature stack " + std::to_string(c->n_aov_views));
-  if (source == 1 && (!c->d_denoised.p || c->n_denoised != c->n_views)) return fail(c, PTMI_ERR_STATE, "ptmi_fuse_views: no denoised stack: call ptmi_denoise_views first");
-  if (n_views == 0 || first_view >= c->n_views || n_views > c->n_views - first_view)
-    return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_views: views [" + std::to_string(first_view) + ", " + std::to_string((uint64_t)first_view + n_views) + ") of " + std::to_string(c->n_views));
-  const uint32_t n_stack = c->n_views, n_mat = (uint32_t)(c->h_mats.size() / 16);
+  if (int r = check_source_stacks(c, "ptmi_fuse_views", source == 1, first_view, n_views)) return r;
+  const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
   const size_t tab_bytes = fuse_tab_bytes(n_stack, n_mat);
   std::vector<float> tab;
   std::vector<uint8_t> lamb(n_mat);
@@ -2370,74 +2329,25 @@ int ptmi_fuse_views(ptmi_ctx* c, const ptmi_fuse_params* params, const float* vi
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
   // the stack, the table and its staging copy: everything that can fail for want of memory, before anything is enqueued
-  const size_t npix = (size_t)c->W * (size_t)c->H;
-  const bool fresh = !c->d_fused.p || c->n_fused != n_stack;
-  DBuf stack;  // the new stack first: a call that fails for want of memory leaves the old images as they were
-  if (fresh) HIP_TRY(c, stack.ensure(npix * 16 * n_stack));
-  if (c->fuse_tab_sent) HIP_TRY(c, hipEventSynchronize(c->fuse_tab_sent));  // the last call's upload has read the staging copy
-  else HIP_TRY(c, hipEventCreateWithFlags(&c->fuse_tab_sent, hipEventDisableTiming));
-  if (tab_bytes > c->d_fuse_tab.cap) HIP_TRY(c, hipStreamSynchronize(c->stream));  // (an earlier call's kernel may still read the table that ensure() is about to free)
-  HIP_TRY(c, c->d_fuse_tab.ensure(tab_bytes));
-  if (tab_bytes > c->h_fuse_tab_cap) {
-    if (c->h_fuse_tab) (void)hipHostFree(c->h_fuse_tab);
-    c->h_fuse_tab = nullptr, c->h_fuse_tab_cap = 0;
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_fuse_tab, tab_bytes, hipHostMallocDefault));
-    c->h_fuse_tab_cap = tab_bytes;
-  }
-  memcpy(c->h_fuse_tab, tab.data(), tab_bytes);
-  if (fresh) {
-    c->d_fused = std::move(stack);
-    c->n_fused = n_stack;
-    HIP_TRY(c, hipMemsetAsync(c->d_fused.p, 0, npix * 16 * n_stack, c->stream));
-  }
-  HIP_TRY(c, hipMemcpyAsync(c->d_fuse_tab.p, c->h_fuse_tab, tab_bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipEventRecord(c->fuse_tab_sent, c->stream));
+  DBuf stack;
+  if (int r = reserve_stack(c, STACK_FUSED, n_stack, &stack)) return r;
+  void* staged = nullptr;
+  HIP_TRY(c, c->fuse_tab.stage(tab_bytes, c->stream, &staged));
+  memcpy(staged, tab.data(), tab_bytes);
+  if (int r = commit_stack(c, STACK_FUSED, n_stack, &stack)) return r;
+  HIP_TRY(c, c->fuse_tab.send(tab_bytes, c->stream));
   const float fov_factor = (float)(1.0 / std::tan((double)c->prm.fov_degrees * (3.14159265358979323846 / 180.0) / 2.0));  // as make_render_const folds it
   const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, source == 0 ? frame_num : 1.0f, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
-  return fuse_enqueue(c, (source == 0 ? c->d_views : c->d_denoised).as<float4>(), c->d_aov.as<float4>(), c->d_fused.as<float4>(), c->d_fuse_tab.p, true, n_mat, c->W, c->H, n_stack,
-                      first_view, n_views, k);
+  return fuse_enqueue(c, c->stacks[source == 0 ? STACK_VIEWS : STACK_DENOISED].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(), c->stacks[STACK_FUSED].buf.as<float4>(),
+                      c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, k);
 }
 
-static int check_fused(ptmi_ctx* c, const char* who, uint32_t view) {
-  if (!c->d_fused.p || c->n_fused == 0) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no fused stack: call ptmi_fuse_views first");
-  if (view >= c->n_fused) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": view " + std::to_string(view) + " of " + std::to_string(c->n_fused));
-  return PTMI_OK;
-}
-
-int ptmi_read_fused(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) {
-  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_fused: null argument");
-  if (int r = check_fused(c, "ptmi_read_fused", view)) return r;
-  if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_fused: bytes != W*H*16");
-  return read_image(c, ImageRef{IMG_FUSED, view}, dst, bytes);
-}
-
+int ptmi_read_fused(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_FUSED, "ptmi_read_fused", view, 0, dst, bytes); }
 int ptmi_resolve_fused_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t bytes) {
-  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_fused_rgba8: null argument");
-  if (int r = check_fused(c, "ptmi_resolve_fused_rgba8", view)) return r;
-  if (bytes != (size_t)c->W * c->H * 4) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_fused_rgba8: bytes != W*H*4");
-  return resolve_image(c, ImageRef{IMG_FUSED, view}, 1.0f, dst, bytes);  // (the stack holds means: the display pass at frameNum 1)
+  return resolve_stack(c, STACK_FUSED, "ptmi_resolve_fused_rgba8", view, 1.0f, dst, bytes);  // (the stack holds means: the display pass at frameNum 1)
 }
-
-int ptmi_fused_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
-  if (!c || !p) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fused_device_ptr: null argument");
-  if (!c->d_fused.p || c->n_fused == 0) return fail(c, PTMI_ERR_STATE, "ptmi_fused_device_ptr: no fused stack: call ptmi_fuse_views first");
-  *p = c->d_fused.p;
-  if (bytes) *bytes = (size_t)c->n_fused * c->W * c->H * 16;
-  if (n_views) *n_views = c->n_fused;
-  return PTMI_OK;
-}
-
-int ptmi_release_fused(ptmi_ctx* c) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  return on_all_devices(c, [](ptmi_ctx* q) -> int {
-    HIP_TRY(q, hipSetDevice(q->device));
-    HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still write a stack that is about to go
-    q->d_fused.release();
-    q->n_fused = 0;
-    q->d_fuse_tab.release();
-    return PTMI_OK;
-  });
-}
+int ptmi_fused_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) { return stack_device_ptr(c, STACK_FUSED, "ptmi_fused_device_ptr", nullptr, p, bytes, n_views); }
+int ptmi_release_fused(ptmi_ctx* c) { return release_stack(c, STACK_FUSED); }
 
 int ptmi_fuse_images(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
                      const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
@@ -2455,26 +2365,12 @@ int ptmi_fuse_images(ptmi_ctx* c, const float* colour, const float* layers, cons
     return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_fuse_images: no host memory for the view table");
   }
   if (int r = fuse_fill_tab(c, "ptmi_fuse_images", views16, n_images, lambertian, n_materials, tab.data())) return r;
-  HIP_TRY(c, hipSetDevice(c->device));
-  (void)hipGetLastError();
-  const size_t npix = (size_t)w * (size_t)h, image_bytes = npix * 16;
-  DBuf col, lay, res, dtab;  // this call's own device copies: the context's stacks are not touched
-  HIP_TRY(c, col.ensure(image_bytes * n_images));
-  HIP_TRY(c, lay.ensure(image_bytes * 3 * n_images));
-  HIP_TRY(c, res.ensure(image_bytes * n_images));
-  HIP_TRY(c, dtab.ensure(tab_bytes));
-  HIP_TRY(c, hipMemcpyAsync(col.p, colour, image_bytes * n_images, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(lay.p, layers, image_bytes * 3 * n_images, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
   const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
-  int r = fuse_enqueue(c, col.as<float4>(), lay.as<float4>(), res.as<float4>(), dtab.p, lambertian != nullptr, n_materials, w, h, n_images, 0, n_images, k);
-  if (r == PTMI_OK) {
-    hipError_t e = hipMemcpyAsync(out, res.p, image_bytes * n_images, hipMemcpyDeviceToHost, c->stream);
-    if (e != hipSuccess) r = fail(c, PTMI_ERR_DEVICE, std::string("ptmi_fuse_images: ") + hipGetErrorString(e));
-  }
-  hipError_t e = hipStreamSynchronize(c->stream);  // (also before the copies above are freed)
-  if (e != hipSuccess && r == PTMI_OK) r = fail(c, PTMI_ERR_DEVICE, std::string("ptmi_fuse_images: ") + hipGetErrorString(e));
-  return r;
+  DBuf dtab;
+  return on_host_images(c, "ptmi_fuse_images", colour, layers, (size_t)w * (size_t)h, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
+    HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+    return fuse_enqueue(c, col, lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, 0, n_images, k);
+  });
 }
 
 static int synchronize_one(ptmi_ctx* c) {

@@ -1,4 +1,5 @@
-// ptmi_dbuf.h — DBuf: one device allocation, owned.  Freed when the owner goes (or by release()); moved, never copied.  Host code only.
+// ptmi_dbuf.h — DBuf: one device allocation, owned.  Freed when the owner goes (or by release()); moved, never copied.  StagedTable: a small table that every call
+// rewrites, uploaded from a pinned host copy.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -48,6 +49,12 @@ struct DBuf {
     }
     return e;
   }
+  // ensure() for a buffer that work already on `stream` may still use: where there is one and it has to be reallocated, the stream drains first.
+  hipError_t ensure_idle(size_t bytes, hipStream_t stream) {
+    if (p && bytes > cap)
+      if (hipError_t e = hipStreamSynchronize(stream); e != hipSuccess) return e;
+    return ensure(bytes);
+  }
   void release() {
     if (p) (void)hipFree(p);
     p = nullptr;
@@ -56,6 +63,45 @@ struct DBuf {
   template <class T>
   T* as() const {
     return reinterpret_cast<T*>(p);
+  }
+};
+
+// A table that kernels read and every call writes anew: the pinned host copy a call fills, the event that marks where the stream has read that copy — so the call stays
+// asynchronous — and the device copy.  In two halves, so that everything that can fail for want of memory happens before the call enqueues anything.
+struct StagedTable {
+  void* host = nullptr;
+  size_t host_cap = 0;
+  hipEvent_t sent = nullptr;
+  DBuf dev;
+
+  StagedTable() = default;
+  StagedTable(const StagedTable&) = delete;
+  StagedTable& operator=(const StagedTable&) = delete;
+  ~StagedTable() { release(); }
+
+  // Room for `bytes` in both copies; *out: the host copy, free to be written (the last upload has read it).  Enqueues nothing.
+  hipError_t stage(size_t bytes, hipStream_t stream, void** out) {
+    hipError_t e = sent ? hipEventSynchronize(sent) : hipEventCreateWithFlags(&sent, hipEventDisableTiming);
+    if (e == hipSuccess) e = dev.ensure_idle(bytes, stream);  // (an earlier call's kernel may still read the device copy)
+    if (e == hipSuccess && bytes > host_cap) {
+      if (host) (void)hipHostFree(host);
+      host = nullptr, host_cap = 0;
+      e = hipHostMalloc(&host, bytes, hipHostMallocDefault);
+      if (e == hipSuccess) host_cap = bytes;
+    }
+    *out = host;
+    return e;
+  }
+  // The upload of the first `bytes` of the host copy, on the stream.
+  hipError_t send(size_t bytes, hipStream_t stream) {
+    const hipError_t e = hipMemcpyAsync(dev.p, host, bytes, hipMemcpyHostToDevice, stream);
+    return e == hipSuccess ? hipEventRecord(sent, stream) : e;
+  }
+  void release() {  // (with the stream drained)
+    if (sent) (void)hipEventDestroy(sent);
+    if (host) (void)hipHostFree(host);
+    sent = nullptr, host = nullptr, host_cap = 0;
+    dev.release();
   }
 };
 

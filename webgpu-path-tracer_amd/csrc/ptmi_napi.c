@@ -428,7 +428,8 @@ static napi_value js_render_views(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
-static napi_value js_read_view(napi_env env, napi_callback_info info) {
+/* readView / readDenoised / readFused(ctx, view, Float32Array out): image `view` of a stack, through `fn` */
+static napi_value read_stack_common(napi_env env, napi_callback_info info, int (*fn)(ptmi_ctx*, uint32_t, float*, size_t), const char* arg, const char* what) {
   napi_value a[3];
   if (get_args(env, info, 3, a)) return NULL;
   ptmi_ctx* c = ctx_of(env, a[0]);
@@ -437,38 +438,51 @@ static napi_value js_read_view(napi_env env, napi_callback_info info) {
   CHECK_NAPI(napi_get_value_uint32(env, a[1], &view));
   void* data;
   size_t len;
-  if (typed(env, a[2], napi_float32_array, "readView(out)", &data, &len)) return NULL;
-  int st = p_ptmi_read_view(c, view, (float*)data, len * 4);
-  if (st) return throw_status(env, c, st, "ptmi_read_view");
+  if (typed(env, a[2], napi_float32_array, arg, &data, &len)) return NULL;
+  int st = fn(c, view, (float*)data, len * 4);
+  if (st) return throw_status(env, c, st, what);
   return a[2];
 }
+static napi_value js_read_view(napi_env env, napi_callback_info info) { return read_stack_common(env, info, p_ptmi_read_view, "readView(out)", "ptmi_read_view"); }
+static napi_value js_read_denoised(napi_env env, napi_callback_info info) { return read_stack_common(env, info, p_ptmi_read_denoised, "readDenoised(out)", "ptmi_read_denoised"); }
+static napi_value js_read_fused(napi_env env, napi_callback_info info) { return read_stack_common(env, info, p_ptmi_read_fused, "readFused(out)", "ptmi_read_fused"); }
 
-static napi_value js_resolve_view(napi_env env, napi_callback_info info) {
+/* resolveRGBA8(ctx, frameNum, Uint8Array out) / resolveViewRGBA8(ctx, view, frameNum, out): the display pass on the framebuffer, or on image `view` of the view stack */
+static napi_value resolve_common(napi_env env, napi_callback_info info, int with_view) {
   napi_value a[4];
-  if (get_args(env, info, 4, a)) return NULL;
+  if (get_args(env, info, 3 + with_view, a)) return NULL;
   ptmi_ctx* c = ctx_of(env, a[0]);
   if (!c) return NULL;
-  uint32_t view;
-  CHECK_NAPI(napi_get_value_uint32(env, a[1], &view));
+  uint32_t view = 0;
+  if (with_view) {
+    CHECK_NAPI(napi_get_value_uint32(env, a[1], &view));
+  }
   double fn;
-  CHECK_NAPI(napi_get_value_double(env, a[2], &fn));
+  CHECK_NAPI(napi_get_value_double(env, a[1 + with_view], &fn));
   void* data;
   size_t len;
-  if (typed(env, a[3], napi_uint8_array, "resolveViewRGBA8(out)", &data, &len)) return NULL;
-  int st = p_ptmi_resolve_view_rgba8(c, view, (float)fn, (uint8_t*)data, len);
-  if (st) return throw_status(env, c, st, "ptmi_resolve_view_rgba8");
-  return a[3];
+  if (typed(env, a[2 + with_view], napi_uint8_array, with_view ? "resolveViewRGBA8(out)" : "resolveRGBA8(out)", &data, &len)) return NULL;
+  int st = with_view ? p_ptmi_resolve_view_rgba8(c, view, (float)fn, (uint8_t*)data, len) : p_ptmi_resolve_rgba8(c, (float)fn, (uint8_t*)data, len);
+  if (st) return throw_status(env, c, st, with_view ? "ptmi_resolve_view_rgba8" : "ptmi_resolve_rgba8");
+  return a[2 + with_view];
 }
+static napi_value js_resolve_view(napi_env env, napi_callback_info info) { return resolve_common(env, info, 1); }
+static napi_value js_resolve(napi_env env, napi_callback_info info) { return resolve_common(env, info, 0); }
 
-static napi_value js_release_views(napi_env env, napi_callback_info info) {
+/* releaseViews / releaseAov / releaseDenoised / releaseFused(ctx): a stack goes, through `fn` */
+static napi_value release_stack_common(napi_env env, napi_callback_info info, int (*fn)(ptmi_ctx*), const char* what) {
   napi_value a[1];
   if (get_args(env, info, 1, a)) return NULL;
   ptmi_ctx* c = ctx_of(env, a[0]);
   if (!c) return NULL;
-  int st = p_ptmi_release_views(c);
-  if (st) return throw_status(env, c, st, "ptmi_release_views");
+  int st = fn(c);
+  if (st) return throw_status(env, c, st, what);
   return NULL;
 }
+static napi_value js_release_views(napi_env env, napi_callback_info info) { return release_stack_common(env, info, p_ptmi_release_views, "ptmi_release_views"); }
+static napi_value js_release_aov(napi_env env, napi_callback_info info) { return release_stack_common(env, info, p_ptmi_release_aov, "ptmi_release_aov"); }
+static napi_value js_release_denoised(napi_env env, napi_callback_info info) { return release_stack_common(env, info, p_ptmi_release_denoised, "ptmi_release_denoised"); }
+static napi_value js_release_fused(napi_env env, napi_callback_info info) { return release_stack_common(env, info, p_ptmi_release_fused, "ptmi_release_fused"); }
 
 /* renderAov(ctx, Float32Array(V*16), nViews, firstFrame, framesPerView, reset): the feature pass (ptmi_render_aov; the reference renders colour only) — view v's
  * three layers of the context's feature stack receive what the first hit of each of view v's frames saw */
@@ -513,16 +527,6 @@ static napi_value js_read_aov(napi_env env, napi_callback_info info) {
   return a[3];
 }
 
-static napi_value js_release_aov(napi_env env, napi_callback_info info) {
-  napi_value a[1];
-  if (get_args(env, info, 1, a)) return NULL;
-  ptmi_ctx* c = ctx_of(env, a[0]);
-  if (!c) return NULL;
-  int st = p_ptmi_release_aov(c);
-  if (st) return throw_status(env, c, st, "ptmi_release_aov");
-  return NULL;
-}
-
 /* denoiseViews(ctx, frameNum, firstView, nViews, params | null): ptmi_denoise_views — params = {levels, sigmaNormal, sigmaDepth, sigmaColour, albedoFloor}, every
  * field optional (ptmi_default_denoise_params fills the rest) */
 static napi_value js_denoise_views(napi_env env, napi_callback_info info) {
@@ -556,31 +560,6 @@ static napi_value js_denoise_views(napi_env env, napi_callback_info info) {
   }
   int st = p_ptmi_denoise_views(c, &P, (float)frame_num, first, n_views);
   if (st) return throw_status(env, c, st, "ptmi_denoise_views");
-  return NULL;
-}
-
-static napi_value js_read_denoised(napi_env env, napi_callback_info info) {
-  napi_value a[3];
-  if (get_args(env, info, 3, a)) return NULL;
-  ptmi_ctx* c = ctx_of(env, a[0]);
-  if (!c) return NULL;
-  uint32_t view;
-  CHECK_NAPI(napi_get_value_uint32(env, a[1], &view));
-  void* data;
-  size_t len;
-  if (typed(env, a[2], napi_float32_array, "readDenoised(out)", &data, &len)) return NULL;
-  int st = p_ptmi_read_denoised(c, view, (float*)data, len * 4);
-  if (st) return throw_status(env, c, st, "ptmi_read_denoised");
-  return a[2];
-}
-
-static napi_value js_release_denoised(napi_env env, napi_callback_info info) {
-  napi_value a[1];
-  if (get_args(env, info, 1, a)) return NULL;
-  ptmi_ctx* c = ctx_of(env, a[0]);
-  if (!c) return NULL;
-  int st = p_ptmi_release_denoised(c);
-  if (st) return throw_status(env, c, st, "ptmi_release_denoised");
   return NULL;
 }
 
@@ -630,31 +609,6 @@ static napi_value js_fuse_views(napi_env env, napi_callback_info info) {
   }
   int st = p_ptmi_fuse_views(c, &P, (const float*)data, (float)frame_num, source, first, n_views);
   if (st) return throw_status(env, c, st, "ptmi_fuse_views");
-  return NULL;
-}
-
-static napi_value js_read_fused(napi_env env, napi_callback_info info) {
-  napi_value a[3];
-  if (get_args(env, info, 3, a)) return NULL;
-  ptmi_ctx* c = ctx_of(env, a[0]);
-  if (!c) return NULL;
-  uint32_t view;
-  CHECK_NAPI(napi_get_value_uint32(env, a[1], &view));
-  void* data;
-  size_t len;
-  if (typed(env, a[2], napi_float32_array, "readFused(out)", &data, &len)) return NULL;
-  int st = p_ptmi_read_fused(c, view, (float*)data, len * 4);
-  if (st) return throw_status(env, c, st, "ptmi_read_fused");
-  return a[2];
-}
-
-static napi_value js_release_fused(napi_env env, napi_callback_info info) {
-  napi_value a[1];
-  if (get_args(env, info, 1, a)) return NULL;
-  ptmi_ctx* c = ctx_of(env, a[0]);
-  if (!c) return NULL;
-  int st = p_ptmi_release_fused(c);
-  if (st) return throw_status(env, c, st, "ptmi_release_fused");
   return NULL;
 }
 
@@ -724,21 +678,6 @@ static napi_value js_write_fb(napi_env env, napi_callback_info info) {
   int st = p_ptmi_write_framebuffer(c, (const float*)data, len * 4);
   if (st) return throw_status(env, c, st, "ptmi_write_framebuffer");
   return NULL;
-}
-
-static napi_value js_resolve(napi_env env, napi_callback_info info) {
-  napi_value a[3];
-  if (get_args(env, info, 3, a)) return NULL;
-  ptmi_ctx* c = ctx_of(env, a[0]);
-  if (!c) return NULL;
-  double fn;
-  CHECK_NAPI(napi_get_value_double(env, a[1], &fn));
-  void* data;
-  size_t len;
-  if (typed(env, a[2], napi_uint8_array, "resolveRGBA8(out)", &data, &len)) return NULL;
-  int st = p_ptmi_resolve_rgba8(c, (float)fn, (uint8_t*)data, len);
-  if (st) return throw_status(env, c, st, "ptmi_resolve_rgba8");
-  return a[2];
 }
 
 static napi_value js_set_flag(napi_env env, napi_callback_info info, int which) {

@@ -345,6 +345,24 @@ class Context:
         if st != 0:
             raise PtmiError(st, self.lib.ptmi_last_error(self.h).decode())
 
+    def _read_image(self, fn, *which):
+        """an (H, W, 4) float32 image through fn(ctx, *which, dst, bytes)"""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(fn(self.h, *which, _ptr(out), out.nbytes))
+        return out
+
+    def _resolve_image(self, fn, *which):
+        """an (H, W, 4) uint8 image through fn(ctx, *which, dst, bytes)"""
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        self._ck(fn(self.h, *which, _ptr(out), out.nbytes))
+        return out
+
+    def _device_ptr(self, fn):
+        """(device pointer, bytes, n_views) of a stack through fn"""
+        p, n, v = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_uint32()
+        self._ck(fn(self.h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(v)))
+        return p.value, n.value, v.value
+
     def set_params(self, params=None, **kw):
         p = params if params is not None else default_params(**kw)
         self._ck(self.lib.ptmi_set_params(self.h, ctypes.byref(p)))
@@ -394,20 +412,14 @@ class Context:
         self._ck(self.lib.ptmi_render_views(self.h, _ptr(v), v.shape[0], first_frame, frames_per_view, 1 if reset else 0))
 
     def read_view(self, view):
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self.lib.ptmi_read_view(self.h, view, _ptr(out), out.nbytes))
-        return out
+        return self._read_image(self.lib.ptmi_read_view, view)
 
     def resolve_view_rgba8(self, view, frame_num):
-        out = np.empty((self.height, self.width, 4), np.uint8)
-        self._ck(self.lib.ptmi_resolve_view_rgba8(self.h, view, float(frame_num), _ptr(out), out.nbytes))
-        return out
+        return self._resolve_image(self.lib.ptmi_resolve_view_rgba8, view, float(frame_num))
 
     def views_device_ptr(self):
         """(device pointer, bytes, n_views) of the view stack: one contiguous [n_views][H][W][4] float32 array (single-device contexts)."""
-        p, n, v = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_uint32()
-        self._ck(self.lib.ptmi_views_device_ptr(self.h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(v)))
-        return p.value, n.value, v.value
+        return self._device_ptr(self.lib.ptmi_views_device_ptr)
 
     def release_views(self):
         self._ck(self.lib.ptmi_release_views(self.h))
@@ -421,17 +433,13 @@ class Context:
     def read_aov(self, view, layer=None):
         """Layer `layer` of view `view` of the feature stack as (H, W, 4) float32 — 0: normal sum + depth sum, 1: albedo sum + hit count, 2: kind, primitive
         index, material index, front_face — or, with layer=None, all three as (3, H, W, 4)."""
-        layers = range(3) if layer is None else [layer]
-        out = np.empty((len(layers), self.height, self.width, 4), np.float32)
-        for k, l in enumerate(layers):
-            self._ck(self.lib.ptmi_read_aov(self.h, view, l, _ptr(out[k]), out[k].nbytes))
-        return out if layer is None else out[0]
+        if layer is not None:
+            return self._read_image(self.lib.ptmi_read_aov, view, layer)
+        return np.stack([self._read_image(self.lib.ptmi_read_aov, view, l) for l in range(3)])
 
     def aov_device_ptr(self):
         """(device pointer, bytes, n_views) of the feature stack: one contiguous [n_views][3][H][W][4] float32 array (single-device contexts)."""
-        p, n, v = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_uint32()
-        self._ck(self.lib.ptmi_aov_device_ptr(self.h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(v)))
-        return p.value, n.value, v.value
+        return self._device_ptr(self.lib.ptmi_aov_device_ptr)
 
     def release_aov(self):
         self._ck(self.lib.ptmi_release_aov(self.h))
@@ -445,20 +453,14 @@ class Context:
         self._ck(self.lib.ptmi_denoise_views(self.h, None if params is None else ctypes.byref(params), float(frame_num), first_view, n_views))
 
     def read_denoised(self, view):
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self.lib.ptmi_read_denoised(self.h, view, _ptr(out), out.nbytes))
-        return out
+        return self._read_image(self.lib.ptmi_read_denoised, view)
 
     def resolve_denoised_rgba8(self, view):
-        out = np.empty((self.height, self.width, 4), np.uint8)
-        self._ck(self.lib.ptmi_resolve_denoised_rgba8(self.h, view, _ptr(out), out.nbytes))
-        return out
+        return self._resolve_image(self.lib.ptmi_resolve_denoised_rgba8, view)
 
     def denoised_device_ptr(self):
         """(device pointer, bytes, n_views) of the denoised stack: one contiguous [n_views][H][W][4] float32 array of mean radiance."""
-        p, n, v = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_uint32()
-        self._ck(self.lib.ptmi_denoised_device_ptr(self.h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(v)))
-        return p.value, n.value, v.value
+        return self._device_ptr(self.lib.ptmi_denoised_device_ptr)
 
     def release_denoised(self):
         self._ck(self.lib.ptmi_release_denoised(self.h))
@@ -481,20 +483,14 @@ class Context:
         self._ck(self.lib.ptmi_fuse_views(self.h, None if params is None else ctypes.byref(params), _ptr(v), float(frame_num), int(source), first_view, n_views))
 
     def read_fused(self, view):
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self.lib.ptmi_read_fused(self.h, view, _ptr(out), out.nbytes))
-        return out
+        return self._read_image(self.lib.ptmi_read_fused, view)
 
     def resolve_fused_rgba8(self, view):
-        out = np.empty((self.height, self.width, 4), np.uint8)
-        self._ck(self.lib.ptmi_resolve_fused_rgba8(self.h, view, _ptr(out), out.nbytes))
-        return out
+        return self._resolve_image(self.lib.ptmi_resolve_fused_rgba8, view)
 
     def fused_device_ptr(self):
         """(device pointer, bytes, n_views) of the fused stack: one contiguous [n_views][H][W][4] float32 array of mean radiance."""
-        p, n, v = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_uint32()
-        self._ck(self.lib.ptmi_fused_device_ptr(self.h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(v)))
-        return p.value, n.value, v.value
+        return self._device_ptr(self.lib.ptmi_fused_device_ptr)
 
     def release_fused(self):
         self._ck(self.lib.ptmi_release_fused(self.h))
@@ -524,9 +520,7 @@ class Context:
         self._ck(self.lib.ptmi_prepare(self.h))
 
     def read_framebuffer(self):
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self.lib.ptmi_read_framebuffer(self.h, _ptr(out), out.nbytes))
-        return out
+        return self._read_image(self.lib.ptmi_read_framebuffer)
 
     def reduce_info(self):
         """One line about how this context sums its devices' buffers (RCCL, add kernel, or the FALLBACK after an RCCL failure)."""
@@ -558,9 +552,7 @@ class Context:
         return p.value
 
     def resolve_rgba8(self, frame_num):
-        out = np.empty((self.height, self.width, 4), np.uint8)
-        self._ck(self.lib.ptmi_resolve_rgba8(self.h, float(frame_num), _ptr(out), out.nbytes))
-        return out
+        return self._resolve_image(self.lib.ptmi_resolve_rgba8, float(frame_num))
 
     def set_counters(self, on):
         self._ck(self.lib.ptmi_set_counters(self.h, int(on)))
