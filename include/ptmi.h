@@ -348,6 +348,77 @@ int ptmi_release_fused(ptmi_ctx* ctx);
 int ptmi_fuse_images(ptmi_ctx* ctx, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
                      float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out);
 
+/* Second moments and noise (no counterpart in the reference, which renders for as long as the page is open): how noisy is an image of the view stack?
+ *
+ * THE MOMENT STACK.  While ptmi_set_view_moments is on, every ptmi_render_views call also folds into the context's MOMENT STACK: [n_views][H][W][4] f32, derived from
+ * the view stack — the same size, allocated, zeroed and dropped with it.  Image v, pixel p: xyz = the sum over the view's folded frames of c_f * c_f per channel,
+ * c_f being the frame's colour exactly as it is added to the view image (zero for a path that never wrote one; the per-frame mean with num_samples > 1) — a product,
+ * then an add, no contraction; w = the sum of 1.0f per folded frame.  Frame order, reset and the shard are the view image's: reset != 0: a view's first frame
+ * overwrites (xyz = c * c, w = 1); reset == 0: the frames add to what the image holds; pixels outside the shard are neither read nor written; the bits do not depend on
+ * how the frames are split into batches or into calls that pass reset only on the first.  The view stack itself, the counters and every launch but the fold's are what
+ * they are with moments off.  Turning moments on while a view stack exists without a moment stack is settled by the next ptmi_render_views: with reset != 0 the
+ * moment stack is allocated then; with reset == 0 the call returns PTMI_ERR_STATE (the earlier frames' squares are gone).  A call that cannot allocate returns
+ * PTMI_ERR_NO_MEMORY before anything is enqueued and leaves every stack as it found it.  Turning moments off frees the moment stack (synchronises).
+ * ptmi_render / ptmi_render_frame keep no moments. */
+int ptmi_set_view_moments(ptmi_ctx* ctx, int enabled);
+/* ptmi_read_view's counterpart for image `view` of the moment stack: synchronises; bytes must be W*H*16; runs the context's collective on a multi-device context. */
+int ptmi_read_moments(ptmi_ctx* ctx, uint32_t view, float* dst, size_t bytes);
+/* The moment stack as one contiguous [n_views][H][W][4] f32 device array (ptmi_views_device_ptr's counterpart, single-device contexts only); valid until the view
+ * stack changes size, ptmi_resize, ptmi_release_views, ptmi_release_moments or moments are turned off.  bytes / n_views may be NULL.  (No resolve call: a moment
+ * image is not a picture.) */
+int ptmi_moments_device_ptr(ptmi_ctx* ctx, void** dev_ptr, size_t* bytes, uint32_t* n_views);
+/* Frees the moment stack (ptmi_destroy does too); synchronises.  Moments stay on: the next ptmi_render_views with reset != 0 makes a new one. */
+int ptmi_release_moments(ptmi_ctx* ctx);
+
+/* THE NOISE STATISTIC.  Per pixel of one view, with S the view image, M the moment image and n = M.w:
+ *
+ *   counted   iff n >= 2 and the six stored values S.rgb, M.xyz are finite (exact tests on the stored f32) — and e below is no NaN
+ *   channel   mu = S / n;  var = max(M / n - mu * mu, 0)
+ *   V         (var_r + var_g + var_b) / (n - 1): the variance of the mean, summed over the channels
+ *   e         sqrt(V) / (max(mu_r + mu_g + mu_b, 0) + floor): a relative standard error
+ *   q         (uint32) rint(min(e, 255) * 65536): +inf clamps to 255
+ *
+ * and per view, in integers — so that the result does not depend on grid, wave or device order —, the record below; `above` counts the counted pixels with
+ * q > rint(threshold * 65536).  The mean noise of a view is sum_q / counted / 65536, taken by the caller in double.  M / n - mu^2 cancels in f32 for large n on
+ * quiet pixels: the statistic is an estimate and clamps at 0.  The f32 operation order is fixed in include/ptmi_noise.h, which the kernel and ptmi_noise_reference
+ * both compile: they agree bit for bit and integer for integer. */
+typedef struct ptmi_view_noise {
+  uint64_t counted; /* pixels that entered the sums */
+  uint64_t sum_q;   /* sum of q over them */
+  uint64_t above;   /* ... of which q > rint(threshold * 65536) */
+  uint32_t max_q;
+  uint32_t reserved;
+} ptmi_view_noise;
+typedef struct ptmi_noise_params {
+  float floor;     /* > 0: added to the mean luminance sum under the error */
+  float threshold; /* >= 0: `above` counts the pixels noisier than this */
+  int32_t reserved[6];
+} ptmi_noise_params;
+/* floor 1e-2, threshold 0.05 */
+void ptmi_default_noise_params(ptmi_noise_params* p);
+/* The statistic of views [first_view, first_view + n_views) of the view and moment stacks into out[0 .. n_views); synchronises.  params = NULL: the defaults.  One
+ * kernel launch over views x pixel chunks reads the two stacks (32 B per pixel), reduces in registers, across the wave and the block, and adds the block's integers to
+ * its view's record with vector atomics, every record on a 128-byte line of its own.  A shard (ptmi_set_shard) counts its own pixels only; on a multi-device context
+ * every device reduces its own tiles and the host adds the integers (no pixel needs a neighbour).  Touches no stack, nor the accumulation buffer, nor any ptmi_stats
+ * field.  PTMI_ERR_STATE: a stack is missing.  PTMI_ERR_INVALID_ARG: a range past the stack, floor not > 0, threshold < 0, either not finite. */
+int ptmi_view_noise_stats(ptmi_ctx* ctx, const ptmi_noise_params* params, uint32_t first_view, uint32_t n_views, ptmi_view_noise* out);
+/* The same kernel on host arrays of any size: colour_sums and moments [n_images][h][w][4] f32, out [n_images].  map_out, where not NULL, [n_images][h][w] f32,
+ * receives e per pixel before quantisation, NaN where the pixel is not counted.  Synchronous; uses device copies of its own and leaves the context's stacks alone.
+ * Errors as above (no PTMI_ERR_STATE). */
+int ptmi_noise_images(ptmi_ctx* ctx, const float* colour_sums, const float* moments, int w, int h, uint32_t n_images, const ptmi_noise_params* params,
+                      ptmi_view_noise* out, float* map_out);
+
+/* RENDERING TO A NOISE TARGET.  ptmi_render_views in rounds until every view is clean enough: round r renders min(frames_per_round, max_frames - done) frames of every
+ * view, frame numbers from first_frame + done, with reset on in round 0 only, then takes ptmi_view_noise_stats of all views, and the call returns after the first round
+ * in which every view has counted > 0 and
+ *     (double)sum_q <= (double)target * 65536.0 * (double)counted
+ * — its mean noise is at most `target` — or when done == max_frames.  *frames_done receives the frames each view then sums; out, where not NULL, the n_views records of
+ * the last round.  The stacks then hold exactly what one ptmi_render_views with frames_per_view = *frames_done and reset != 0 leaves.  A host loop over those two calls:
+ * it synchronises once per round, for a few bytes per view.  Needs ptmi_set_view_moments on: PTMI_ERR_STATE otherwise.  PTMI_ERR_INVALID_ARG: a null views16 or
+ * frames_done, n_views, frames_per_round or max_frames of 0, n_views * max_frames >= 2^31, a target that is negative or not finite, parameters outside their domain. */
+int ptmi_render_views_until(ptmi_ctx* ctx, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t frames_per_round, uint32_t max_frames,
+                            const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out);
+
 int ptmi_synchronize(ptmi_ctx* ctx);
 
 /* Validates the uploaded buffers and builds the device-side digests now instead of inside the first render call
@@ -458,6 +529,11 @@ int ptmi_denoise_reference(const float* colour_sums, const float* layers, int w,
  * bits.  PTMI_ERR_INVALID_ARG / PTMI_ERR_NO_MEMORY as there. */
 int ptmi_fuse_reference(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
                         const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out);
+
+/* ptmi_noise_images without a GPU: a plain loop over images and pixels through include/ptmi_noise.h, the arithmetic the kernel compiles — the same arguments, the
+ * same bits and the same integers.  PTMI_ERR_INVALID_ARG as there. */
+int ptmi_noise_reference(const float* colour_sums, const float* moments, int w, int h, uint32_t n_images, const ptmi_noise_params* params, ptmi_view_noise* out,
+                         float* map_out);
 
 /* OBJ text -> de-indexed vertex / normal arrays with the reference's accepted grammar and quirks
  * (lib/primitives/objReader.js:10-68: `v`, `vn`, `f a/b/c` triangles; tokens go through JS Number()).  The arrays are

@@ -1,4 +1,4 @@
-// Sanitizer driver for the host natives of libptmi (ptmi_host.cpp): both BVH builders (1 thread vs many), the OBJ parser and cross-view fusion.
+// Sanitizer driver for the host natives of libptmi (ptmi_host.cpp): both BVH builders (1 thread vs many), the OBJ parser, cross-view fusion and the noise statistic.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -pthread tools/sanitize_host.cpp webgpu-path-tracer_amd/csrc/ptmi_host.cpp -o /tmp/san/asan && /tmp/san/asan
 //   g++ -std=c++17 -O1 -g -fsanitize=thread -pthread ... -o /tmp/san/tsan && /tmp/san/tsan
 #include <cmath>
@@ -76,6 +76,24 @@ int main() {
     if (ptmi_fuse_reference(S.data(), L.data(), views.data(), w, h, n, 2.0f, 60.0f, nullptr, 0, nullptr, out.data())) return 7;
     views[0] = 0.0f;
     if (ptmi_fuse_reference(S.data(), L.data(), views.data(), w, h, n, 2.0f, 60.0f, nullptr, 0, nullptr, out.data()) != PTMI_ERR_INVALID_ARG) return 8;  // a singular matrix
+  }
+  {  // ptmi_noise_reference on two 7 x 5 images: frames of every count 0 .. 8, a NaN, an infinity and a huge moment among them; with and without the map
+    const int w = 7, h = 5;
+    const uint32_t n = 2;
+    std::vector<float> S((size_t)n * w * h * 4), M(S.size()), map((size_t)n * w * h);
+    for (size_t p = 0; p < (size_t)n * w * h; p++) {
+      const float k = (float)(p % 9);
+      for (int c = 0; c < 3; c++) S[4 * p + c] = k * (0.3f + 0.1f * (float)c), M[4 * p + c] = k * (0.2f + 0.05f * (float)((p + (size_t)c) % 5));
+      S[4 * p + 3] = 1.0f, M[4 * p + 3] = k;
+    }
+    S[4 * 11] = NAN, M[4 * 12 + 1] = INFINITY, M[4 * 13 + 2] = 3e38f, M[4 * 13] = 3e38f;
+    ptmi_view_noise rec[2];
+    ptmi_noise_params P;
+    ptmi_default_noise_params(&P);
+    if (ptmi_noise_reference(S.data(), M.data(), w, h, n, &P, rec, map.data())) return 9;
+    if (ptmi_noise_reference(S.data(), M.data(), w, h, n, nullptr, rec, nullptr) || rec[0].counted == 0 || rec[0].max_q != 255u * 65536u) return 10;
+    P.floor = 0.0f;
+    if (ptmi_noise_reference(S.data(), M.data(), w, h, n, &P, rec, nullptr) != PTMI_ERR_INVALID_ARG) return 11;
   }
   puts("host natives: sanitizer run clean");
   return 0;

@@ -25,6 +25,7 @@
 #include "ptmi_kernels.h"
 #include "ptmi_denoise_kernels.h"
 #include "ptmi_fuse_kernels.h"
+#include "ptmi_noise_kernels.h"
 #include "ptmi_tuning.h"
 
 using namespace ptmi;
@@ -91,7 +92,7 @@ struct PeerWorker {
 
 // The context's stacks of W x H float4 images, one allocation per kind.  A row per kind: images per view, the noun and the making call of the error texts, and whether
 // the stack is derived from the view stack (it has that stack's size and goes with it).
-enum StackKind { STACK_NONE = -1, STACK_VIEWS = 0, STACK_FEATURES, STACK_DENOISED, STACK_FUSED, N_STACKS };  // (STACK_NONE: ImageRef's accumulation buffer)
+enum StackKind { STACK_NONE = -1, STACK_VIEWS = 0, STACK_FEATURES, STACK_DENOISED, STACK_FUSED, STACK_MOMENTS, N_STACKS };  // (STACK_NONE: ImageRef's accumulation buffer)
 struct StackInfo {
   uint32_t images_per_view;
   const char *noun, *maker;
@@ -102,6 +103,7 @@ constexpr StackInfo kStackInfo[N_STACKS] = {
     {3, "feature stack", "ptmi_render_aov", false},     // k_aov's three layers per view
     {1, "denoised stack", "ptmi_denoise_views", true},  // RGBA f32 means
     {1, "fused stack", "ptmi_fuse_views", true},        // RGBA f32 means
+    {1, "moment stack", "ptmi_render_views with ptmi_set_view_moments on", true},  // sums of squared frame colours, frame count in w
 };
 struct Stack {
   DBuf buf;
@@ -150,6 +152,8 @@ struct ptmi_ctx {
   DBuf d_denoise_scratch;  // ptmi_denoise_views: three packed float4 images (d ping, d pong, n + z) per view of a batch (denoise_batch_views)
   StagedTable view_rows;   // the last ptmi_render_views / ptmi_render_aov call's view table (ViewTab: kViewRow float4 per view)
   StagedTable fuse_tab;    // the last ptmi_fuse_views call's table (kFuseRow float4 per view of the stack, then one byte per material)
+  bool view_moments = false;  // ptmi_set_view_moments: ptmi_render_views folds second moments into stacks[STACK_MOMENTS] too
+  DBuf d_noise_rec;           // ptmi_view_noise_stats: one record (kNoiseRecordBytes) per view of the call
   int rank = 0, world = 1, tile = 64;
 
   size_t path_cap = 0;
@@ -953,6 +957,7 @@ RenderConst make_render_const(const ptmi_ctx* c, const float* view16, uint32_t f
 struct ViewBatch {
   ViewTab vt;
   float4* stack;
+  float4* moments;  // the moment stack, or nullptr: moments are off (ptmi_set_view_moments)
 };
 
 // `fold` = how many of the batch's leading frames are added to the framebuffer now (-1 = all of them); dry_steps > 0: placement_search's timing run
@@ -1096,7 +1101,9 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   {
     ScopedSpan s(c, T_ACCUM);
     const int f_end = fold < 0 ? n_frames : std::min(fold, n_frames);
-    if (views) hipLaunchKernelGGL(k_accumulate<true>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), views->stack, n_steps, tot, 0, f_end, vtab);
+    if (views && views->moments)
+      hipLaunchKernelGGL(k_accumulate_moments, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), views->stack, views->moments, n_steps, tot, 0, f_end, vtab);
+    else if (views) hipLaunchKernelGGL(k_accumulate<true>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), views->stack, n_steps, tot, 0, f_end, vtab);
     else hipLaunchKernelGGL(k_accumulate<false>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), c->fb, n_steps, tot, 0, f_end, vtab);
     c->stats.accumulate_launches++;
   }
@@ -1956,13 +1963,21 @@ static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views,
   if (r) return r;
   r = check_renderable(c);
   if (r) return r;
-  // the stack and the table: allocated before anything is enqueued
-  DBuf stack;
+  // Moments (ptmi_set_view_moments) were turned on after this view stack was made: a call that overwrites can start the moment stack now, one that adds cannot.
+  const bool keeps_views = c->stacks[STACK_VIEWS].buf.p && c->stacks[STACK_VIEWS].n == n_views;
+  if (c->view_moments && keeps_views && !c->stacks[STACK_MOMENTS].buf.p && !reset)
+    return fail(c, PTMI_ERR_STATE, "ptmi_render_views: moments were turned on after the view stack's frames were folded, whose squares are gone: pass reset != 0");
+  // the stacks and the table: allocated before anything is enqueued
+  DBuf stack, moments;
   r = reserve_stack(c, STACK_VIEWS, n_views, &stack);
+  if (r) return r;
+  if (c->view_moments) r = reserve_stack(c, STACK_MOMENTS, n_views, &moments);
   if (r) return r;
   r = stage_view_rows(c, views16, n_views);
   if (r) return r;
-  r = commit_stack(c, STACK_VIEWS, n_views, &stack);
+  r = commit_stack(c, STACK_VIEWS, n_views, &stack);  // (a new view stack takes the old moment stack with it: drop_stack)
+  if (r) return r;
+  if (c->view_moments) r = commit_stack(c, STACK_MOMENTS, n_views, &moments);
   if (r) return r;
   r = send_view_rows(c, n_views);
   if (r) return r;
@@ -1973,7 +1988,8 @@ static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views,
   const uint32_t n_slots = n_views * fpv;
   for (uint32_t done = 0; done < n_slots;) {
     const uint32_t nb = std::min(F, n_slots - done);
-    const ViewBatch vb{ViewTab{c->view_rows.dev.as<float4>(), done, fpv, 0u}, c->stacks[STACK_VIEWS].buf.as<float4>()};
+    const ViewBatch vb{ViewTab{c->view_rows.dev.as<float4>(), done, fpv, 0u}, c->stacks[STACK_VIEWS].buf.as<float4>(),
+                       c->view_moments ? c->stacks[STACK_MOMENTS].buf.as<float4>() : nullptr};
     r = render_batch(c, views16 + 16 * (size_t)(done / fpv), first_frame, (int)nb, reset ? 1 : 0, -1, 0, &vb);
     if (r == PTMI_ERR_NO_MEMORY && !c->batch_enqueued && nb > 1 && c->prm.frames_in_flight <= 0) {
       F = std::max<uint32_t>(1, nb / 2);
@@ -2226,25 +2242,25 @@ int ptmi_denoised_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_v
 }
 int ptmi_release_denoised(ptmi_ctx* c) { return release_stack(c, STACK_DENOISED); }
 
-// ptmi_denoise_images / ptmi_fuse_images: the kernels on host arrays — colour [n][npix] float4, layers [n][3][npix] float4, out [n][npix] float4 — through device copies of
-// this call's own: the context's stacks are not touched.  `extra`: what else the kernels need on the device, allocated after the copies and, as everything that can fail
-// for want of memory, before anything is enqueued.  `enqueue(colour, layers, out)` puts the kernels on the stream; whatever it returns, the stream drains before the
+// ptmi_denoise_images / ptmi_fuse_images / ptmi_noise_images: the kernels on host arrays — colour [n][npix] float4, layers [n][layer_images][npix] float4, out [n][npix] of
+// out_pixel_bytes each (nullptr: the call wants none, and `enqueue` is handed nullptr) — through device copies of this call's own: the context's stacks are not touched.
+// `extra`: what else the kernels need on the device, allocated after the copies and, as everything that can fail for want of memory, before anything is enqueued.  `enqueue(colour, layers, out)` puts the kernels on the stream; whatever it returns, the stream drains before the
 // copies (and whatever `enqueue` captured) die.  The first error wins.
 static int on_host_images(ptmi_ctx* c, const char* who, const float* colour, const float* layers, size_t npix, uint32_t n, float* out, DBuf& extra, size_t extra_bytes,
-                          const std::function<int(const float4*, const float4*, float4*)>& enqueue) {
+                          const std::function<int(const float4*, const float4*, float4*)>& enqueue, size_t layer_images = 3, size_t out_pixel_bytes = 16) {
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
-  const size_t bytes = npix * 16 * n;
+  const size_t bytes = npix * 16 * n, out_bytes = out ? npix * out_pixel_bytes * n : 0;
   DBuf col, lay, res;
   HIP_TRY(c, col.ensure(bytes));
-  HIP_TRY(c, lay.ensure(bytes * 3));
-  HIP_TRY(c, res.ensure(bytes));
+  HIP_TRY(c, lay.ensure(bytes * layer_images));
+  HIP_TRY(c, res.ensure(out_bytes));
   HIP_TRY(c, extra.ensure_idle(extra_bytes, c->stream));
   HIP_TRY(c, hipMemcpyAsync(col.p, colour, bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(lay.p, layers, bytes * 3, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(lay.p, layers, bytes * layer_images, hipMemcpyHostToDevice, c->stream));
   int r = enqueue(col.as<float4>(), lay.as<float4>(), res.as<float4>());
-  if (r == PTMI_OK) {
-    const hipError_t e = hipMemcpyAsync(out, res.p, bytes, hipMemcpyDeviceToHost, c->stream);
+  if (r == PTMI_OK && out) {
+    const hipError_t e = hipMemcpyAsync(out, res.p, out_bytes, hipMemcpyDeviceToHost, c->stream);
     if (e != hipSuccess) r = fail(c, PTMI_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
   }
   const hipError_t e = hipStreamSynchronize(c->stream);
@@ -2371,6 +2387,157 @@ int ptmi_fuse_images(ptmi_ctx* c, const float* colour, const float* layers, cons
     HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
     return fuse_enqueue(c, col, lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, 0, n_images, k);
   });
+}
+
+// ---- the moment stack and the noise statistic (ptmi_set_view_moments, ptmi_view_noise_stats, ptmi_noise_images, ptmi_render_views_until) ----
+// (ptmi_default_noise_params and ptmi_noise_reference need no GPU: ptmi_host.cpp)
+int ptmi_set_view_moments(ptmi_ctx* c, int enabled) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  for (ptmi_ctx* q : local_devices(c)) q->view_moments = enabled != 0;
+  // off: the moment stack goes, so that one that exists always describes the frames its view stack sums
+  return enabled ? PTMI_OK : release_stack(c, STACK_MOMENTS);
+}
+int ptmi_read_moments(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_MOMENTS, "ptmi_read_moments", view, 0, dst, bytes); }
+int ptmi_moments_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
+  return stack_device_ptr(c, STACK_MOMENTS, "ptmi_moments_device_ptr", "ptmi_read_moments", p, bytes, n_views);
+}
+int ptmi_release_moments(ptmi_ctx* c) { return release_stack(c, STACK_MOMENTS); }
+
+static int noise_check_args(ptmi_ctx* c, const char* who, const ptmi_noise_params* params, ptmi_noise_params* P) {
+  if (params) *P = *params;
+  else ptmi_default_noise_params(P);
+  if (!ptmn_params_ok(P->floor, P->threshold)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need floor > 0 and threshold >= 0, both finite");
+  return PTMI_OK;
+}
+
+// The kernel on device arrays: colour and moments [n][npix] float4 of which a device reads its shard (n_local pixels of rank / world / tile), `records` n zeroed records,
+// map [n][npix] f32 or nullptr.  One launch; more only where n exceeds the grid's y limit.
+static int noise_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, uint32_t n, uint32_t npix, uint32_t n_local, int rank, int world, int tile,
+                         const ptmi_noise_params& P, unsigned char* records, float* map) {
+  HIP_TRY(c, hipMemsetAsync(records, 0, (size_t)n * kNoiseRecordBytes, c->stream));
+  if (n_local == 0) return PTMI_OK;
+  const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((n_local + kBlock - 1) / kBlock, kNoiseChunks));
+  for (uint32_t v0 = 0; v0 < n; v0 += 65535u) {
+    const uint32_t nv = std::min(65535u, n - v0);
+    hipLaunchKernelGGL(k_view_noise, dim3(gx, nv), dim3(kBlock), 0, c->stream, colour + (size_t)v0 * npix, moments + (size_t)v0 * npix, npix, n_local, rank, world, tile, P.floor,
+                       ptmn_threshold_q(P.threshold), records + (size_t)v0 * kNoiseRecordBytes, map ? map + (size_t)v0 * npix : nullptr);
+    HIP_TRY(c, hipGetLastError());
+  }
+  return PTMI_OK;
+}
+
+// records (kNoiseRecordBytes apart, on the host) added into out[0 .. n)
+static void noise_add_records(const unsigned char* rec, uint32_t n, ptmi_view_noise* out) {
+  for (uint32_t v = 0; v < n; v++) {
+    NoiseRecord r;
+    memcpy(&r, rec + (size_t)v * kNoiseRecordBytes, sizeof r);
+    out[v].counted += r.counted, out[v].sum_q += r.sum_q, out[v].above += r.above;
+    out[v].max_q = std::max(out[v].max_q, r.max_q);
+  }
+}
+
+int ptmi_view_noise_stats(ptmi_ctx* c, const ptmi_noise_params* params, uint32_t first_view, uint32_t n_views, ptmi_view_noise* out) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  if (!out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_view_noise_stats: null argument");
+  ptmi_noise_params P;
+  if (int r = noise_check_args(c, "ptmi_view_noise_stats", params, &P)) return r;
+  if (int r = check_stack(c, STACK_VIEWS, "ptmi_view_noise_stats", 0)) return r;
+  if (int r = check_stack(c, STACK_MOMENTS, "ptmi_view_noise_stats", 0)) return r;
+  const uint32_t n = c->stacks[STACK_VIEWS].n;
+  if (n_views == 0 || first_view >= n || n_views > n - first_view)
+    return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_view_noise_stats: views [" + std::to_string(first_view) + ", " + std::to_string((uint64_t)first_view + n_views) + ") of " + std::to_string(n));
+  const std::vector<ptmi_ctx*> devs = local_devices(c);
+  std::vector<unsigned char> host;
+  try {
+    host.resize(devs.size() * (size_t)n_views * kNoiseRecordBytes);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_view_noise_stats: no host memory for the records");
+  }
+  // every device reduces its own tiles of its own stacks, all of them at once; the copies land in `host`, which outlives the synchronisation below
+  int r = on_all_devices(c, [&](ptmi_ctx* q) -> int {
+    HIP_TRY(q, hipSetDevice(q->device));
+    (void)hipGetLastError();
+    const size_t i = (size_t)(std::find(devs.begin(), devs.end(), q) - devs.begin());
+    const uint32_t npix = (uint32_t)q->W * (uint32_t)q->H;
+    HIP_TRY(q, q->d_noise_rec.ensure_idle((size_t)n_views * kNoiseRecordBytes, q->stream));
+    int e = noise_enqueue(q, q->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)first_view * npix, q->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix, n_views, npix,
+                          count_local(npix, q->rank, q->world, q->tile), q->rank, q->world, q->tile, P, q->d_noise_rec.as<unsigned char>(), nullptr);
+    if (e) return e;
+    HIP_TRY(q, hipMemcpyAsync(host.data() + i * (size_t)n_views * kNoiseRecordBytes, q->d_noise_rec.p, (size_t)n_views * kNoiseRecordBytes, hipMemcpyDeviceToHost, q->stream));
+    return PTMI_OK;
+  });
+  const int s = on_all_devices(c, [](ptmi_ctx* q) -> int {  // (whatever was enqueued drains before `host` goes)
+    HIP_TRY(q, hipSetDevice(q->device));
+    HIP_TRY(q, hipStreamSynchronize(q->stream));
+    drain_spans(q);
+    return check_queue_overflow(q);
+  });
+  (void)hipSetDevice(c->device);
+  if (r) return r;
+  if (s) return s;
+  memset(out, 0, (size_t)n_views * sizeof(ptmi_view_noise));
+  for (size_t i = 0; i < devs.size(); i++) noise_add_records(host.data() + i * (size_t)n_views * kNoiseRecordBytes, n_views, out);
+  return PTMI_OK;
+}
+
+int ptmi_noise_images(ptmi_ctx* c, const float* colour_sums, const float* moments, int w, int h, uint32_t n_images, const ptmi_noise_params* params, ptmi_view_noise* out,
+                      float* map_out) {
+  if (!c || !colour_sums || !moments || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_noise_images: null argument");
+  ptmi_noise_params P;
+  if (int r = noise_check_args(c, "ptmi_noise_images", params, &P)) return r;
+  if (w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_noise_images: need w, h, n_images >= 1 and w * h < 2^31");
+  const uint32_t npix = (uint32_t)w * (uint32_t)h;
+  const size_t rec_bytes = (size_t)n_images * kNoiseRecordBytes;
+  std::vector<unsigned char> host;
+  try {
+    host.resize(rec_bytes);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_noise_images: no host memory for the records");
+  }
+  DBuf rec;
+  const int r = on_host_images(
+      c, "ptmi_noise_images", colour_sums, moments, npix, n_images, reinterpret_cast<float*>(map_out), rec, rec_bytes,
+      [&](const float4* col, const float4* mom, float4* map) -> int {
+        if (int e = noise_enqueue(c, col, mom, n_images, npix, npix, 0, 1, 64, P, rec.as<unsigned char>(), reinterpret_cast<float*>(map))) return e;
+        HIP_TRY(c, hipMemcpyAsync(host.data(), rec.p, rec_bytes, hipMemcpyDeviceToHost, c->stream));
+        return PTMI_OK;
+      },
+      1, sizeof(float));
+  if (r) return r;
+  memset(out, 0, (size_t)n_images * sizeof(ptmi_view_noise));
+  noise_add_records(host.data(), n_images, out);
+  return PTMI_OK;
+}
+
+int ptmi_render_views_until(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t frames_per_round, uint32_t max_frames,
+                            const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  if (!views16 || !frames_done) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until: null argument");
+  *frames_done = 0;
+  if (n_views == 0 || frames_per_round == 0 || max_frames == 0) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until: need n_views, frames_per_round and max_frames >= 1");
+  if ((uint64_t)n_views * max_frames > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until: n_views * max_frames must stay below 2^31");
+  if (!(target >= 0.0f) || !ptmn_finite(target)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until: target must be finite and >= 0");
+  ptmi_noise_params P;
+  if (int r = noise_check_args(c, "ptmi_render_views_until", params, &P)) return r;
+  if (!c->view_moments) return fail(c, PTMI_ERR_STATE, "ptmi_render_views_until: moments are off: call ptmi_set_view_moments first");
+  std::vector<ptmi_view_noise> stats;
+  try {
+    stats.resize(n_views);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_render_views_until: no host memory for the records");
+  }
+  for (uint32_t done = 0; done < max_frames;) {
+    const uint32_t nf = std::min(frames_per_round, max_frames - done);
+    if (int r = ptmi_render_views(c, views16, n_views, first_frame + done, nf, done == 0 ? 1 : 0)) return r;
+    done += nf;
+    *frames_done = done;
+    if (int r = ptmi_view_noise_stats(c, &P, 0, n_views, stats.data())) return r;
+    bool met = true;
+    for (uint32_t v = 0; v < n_views && met; v++) met = ptmn_target_met(stats[v].counted, stats[v].sum_q, target);
+    if (met) break;
+  }
+  if (out) memcpy(out, stats.data(), (size_t)n_views * sizeof(ptmi_view_noise));
+  return PTMI_OK;
 }
 
 static int synchronize_one(ptmi_ctx* c) {

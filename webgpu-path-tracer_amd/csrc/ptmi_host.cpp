@@ -21,6 +21,7 @@
 #include "../../include/ptmi.h"
 #include "../../include/ptmi_denoise.h"
 #include "../../include/ptmi_fuse.h"
+#include "../../include/ptmi_noise.h"
 
 namespace {
 // Math.min / Math.max (lib/BVH/AABB.js:8-28) on finite values: -0 < +0 whatever the argument order
@@ -779,6 +780,44 @@ extern "C" int ptmi_fuse_reference(const float* colour, const float* layers, con
         }
         O[(size_t)v * npix + idx] = ptmf_output(&k, Sp, Ap, fused, num, den);
       }
+  }
+  return PTMI_OK;
+}
+
+// ---- the noise statistic on the host (ptmi_noise_reference) ----
+extern "C" void ptmi_default_noise_params(ptmi_noise_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->floor = 1e-2f;
+  p->threshold = 0.05f;
+}
+
+// A plain loop over images and pixels through include/ptmi_noise.h, the header the kernel of ptmi_view_noise_stats compiles.  The per-view sums are integers: no order
+// to keep.
+extern "C" int ptmi_noise_reference(const float* colour_sums, const float* moments, int w, int h, uint32_t n_images, const ptmi_noise_params* params, ptmi_view_noise* out,
+                                    float* map_out) {
+  if (!colour_sums || !moments || !out || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
+  ptmi_noise_params P;
+  if (params) P = *params;
+  else ptmi_default_noise_params(&P);
+  if (!ptmn_params_ok(P.floor, P.threshold)) return PTMI_ERR_INVALID_ARG;
+  const uint32_t tq = ptmn_threshold_q(P.threshold);
+  const size_t npix = (size_t)w * (size_t)h;
+  const ptmn_f4* S = reinterpret_cast<const ptmn_f4*>(colour_sums);
+  const ptmn_f4* M = reinterpret_cast<const ptmn_f4*>(moments);
+  for (uint32_t v = 0; v < n_images; v++) {
+    ptmi_view_noise r{};
+    for (size_t p = 0; p < npix; p++) {
+      const float e = ptmn_error(S[(size_t)v * npix + p], M[(size_t)v * npix + p], P.floor);
+      if (map_out) map_out[(size_t)v * npix + p] = e;
+      if (e != e) continue;
+      const uint32_t q = ptmn_quantise(e);
+      r.counted++;
+      r.sum_q += q;
+      r.above += q > tq;
+      r.max_q = std::max(r.max_q, q);
+    }
+    out[v] = r;
   }
   return PTMI_OK;
 }

@@ -1512,6 +1512,75 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(RenderConst rc, Paths P, 
   }
 }
 
+// k_accumulate<true> with second moments (ptmi_set_view_moments): launched in its place for a multi-view batch while moments are on.  Every P.acc value is fetched once
+// — the same eight-ahead fetch — and folded into two images: c_f into the view image as above, c_f * c_f per channel (a product, then an add: no contraction) into the
+// pixel of `mom`, the context's moment stack, whose w counts the folded frames.  Both images change where the slot's frame-in-view wraps.
+// (An entry of its own, not a flag or an argument of k_accumulate: see the note above that kernel — the every-render instance keeps its schedule and its registers.)
+__global__ __launch_bounds__(kBlock) void k_accumulate_moments(RenderConst rc, Paths P, float4* __restrict__ fb, float4* __restrict__ mom, int n_steps,
+                                                               unsigned long long* __restrict__ totals, int f_begin, int f_end, ViewTab vt) {
+  for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < rc.n_local; j += gridDim.x * kBlock) {
+    if (f_begin >= f_end) break;
+    const uint32_t pix = local_to_pixel(rc, j);
+    const uint32_t s = vt.slot0 + (uint32_t)f_begin, view = s / vt.fpv;
+    uint32_t fiv = s - view * vt.fpv;  // frame-in-view of the slot about to be folded
+    size_t at = (size_t)view * rc.npix + pix;  // the pixel of the view's image, in either stack
+    const bool opens = fiv == 0u && rc.reset_first;  // the first slot overwrites: what the images hold is not needed
+    f3 c = mk3(0.0f, 0.0f, 0.0f);
+    float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!opens) c = mk3(fb[at]), m = mom[at];
+    bool pending = false;  // `c` and `m` have still to be stored
+    constexpr int kAhead = 8;
+    for (int f0 = f_begin; f0 < f_end; f0 += kAhead) {
+      bool have[kAhead];
+      float4 colv[kAhead];
+#pragma unroll
+      for (int k = 0; k < kAhead; k++) {
+        const int f = f0 + k;
+        have[k] = f < f_end && (!P.touched || P.touched[(size_t)f * rc.n_local + j]);
+      }
+#pragma unroll
+      for (int k = 0; k < kAhead; k++) {
+        colv[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // a path that never wrote its acc_radiance returned (0,0,0)
+        if (have[k]) colv[k] = P.acc[(size_t)(f0 + k) * rc.n_local + j];
+      }
+#pragma unroll
+      for (int k = 0; k < kAhead; k++) {
+        const int f = f0 + k;
+        if (f >= f_end) break;
+        const f3 col = mk3(colv[k]);
+        const f3 sq = mk3(col.x * col.x, col.y * col.y, col.z * col.z);
+        if (fiv == 0u && rc.reset_first) {
+          c = col;
+          m = make_float4(sq.x, sq.y, sq.z, 1.0f);
+        } else {
+          c = c + col;
+          m = make_float4(m.x + sq.x, m.y + sq.y, m.z + sq.z, m.w + 1.0f);
+        }
+        pending = true;
+        if (++fiv == vt.fpv) {  // the view's last frame: its images are done, the next slot opens the next view's
+          fb[at] = make_float4(c.x, c.y, c.z, 1.0f);
+          mom[at] = m;
+          pending = false;
+          fiv = 0;
+          at += rc.npix;
+          if (f + 1 < f_end && !rc.reset_first) c = mk3(fb[at]), m = mom[at];  // (with reset the next slot's colour overwrites both)
+        }
+      }
+    }
+    if (pending) {
+      fb[at] = make_float4(c.x, c.y, c.z, 1.0f);
+      mom[at] = m;
+    }
+  }
+  if (f_begin == 0 && blockIdx.x == 0 && threadIdx.x == 0) {  // the slot-0 tally, as k_accumulate's
+    unsigned long long rays = 0;
+    if (n_steps > 0)
+      for (int k = 0; k < kTallyLines; k++) rays += *tally_line(totals, (uint32_t)k);
+    totals[0] += rays;
+    totals[1] += (unsigned long long)rc.n_local * (unsigned long long)rc.n_frames * (unsigned long long)rc.num_samples;
+  }
+}
+
 // Upload-time digest: the unit normal resolve_hit needs for a quad hit (common.wgsl:176), computed once per quad by the
 // same device function the shading path would call per hit — same instructions, same bits.
 __global__ void k_quad_digest(const float4* __restrict__ quads, int n, float4* __restrict__ unit_n) {

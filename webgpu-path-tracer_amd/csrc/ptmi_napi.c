@@ -51,6 +51,12 @@ FN(ptmi_default_fuse_params)
 FN(ptmi_fuse_views)
 FN(ptmi_read_fused)
 FN(ptmi_release_fused)
+FN(ptmi_set_view_moments)
+FN(ptmi_read_moments)
+FN(ptmi_release_moments)
+FN(ptmi_default_noise_params)
+FN(ptmi_view_noise_stats)
+FN(ptmi_render_views_until)
 FN(ptmi_synchronize)
 FN(ptmi_read_framebuffer)
 FN(ptmi_write_framebuffer)
@@ -99,7 +105,7 @@ static int load_lib(char* err, size_t errlen) {
   }
   LOAD(ptmi_version) LOAD(ptmi_last_error) LOAD(ptmi_create) LOAD(ptmi_create_multi) LOAD(ptmi_prepare) LOAD(ptmi_destroy) LOAD(ptmi_default_params) LOAD(ptmi_default_denoise_params) LOAD(ptmi_set_params)
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
-  LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
+  LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_set_view_moments) LOAD(ptmi_read_moments) LOAD(ptmi_release_moments) LOAD(ptmi_default_noise_params) LOAD(ptmi_view_noise_stats) LOAD(ptmi_render_views_until) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
   LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah)
   LOAD(ptmi_obj_parse) LOAD(ptmi_free) LOAD(ptmi_device_count) LOAD(ptmi_reduce_info)
   return 0;
@@ -428,7 +434,7 @@ static napi_value js_render_views(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
-/* readView / readDenoised / readFused(ctx, view, Float32Array out): image `view` of a stack, through `fn` */
+/* readView / readDenoised / readFused / readMoments(ctx, view, Float32Array out): image `view` of a stack, through `fn` */
 static napi_value read_stack_common(napi_env env, napi_callback_info info, int (*fn)(ptmi_ctx*, uint32_t, float*, size_t), const char* arg, const char* what) {
   napi_value a[3];
   if (get_args(env, info, 3, a)) return NULL;
@@ -446,6 +452,7 @@ static napi_value read_stack_common(napi_env env, napi_callback_info info, int (
 static napi_value js_read_view(napi_env env, napi_callback_info info) { return read_stack_common(env, info, p_ptmi_read_view, "readView(out)", "ptmi_read_view"); }
 static napi_value js_read_denoised(napi_env env, napi_callback_info info) { return read_stack_common(env, info, p_ptmi_read_denoised, "readDenoised(out)", "ptmi_read_denoised"); }
 static napi_value js_read_fused(napi_env env, napi_callback_info info) { return read_stack_common(env, info, p_ptmi_read_fused, "readFused(out)", "ptmi_read_fused"); }
+static napi_value js_read_moments(napi_env env, napi_callback_info info) { return read_stack_common(env, info, p_ptmi_read_moments, "readMoments(out)", "ptmi_read_moments"); }
 
 /* resolveRGBA8(ctx, frameNum, Uint8Array out) / resolveViewRGBA8(ctx, view, frameNum, out): the display pass on the framebuffer, or on image `view` of the view stack */
 static napi_value resolve_common(napi_env env, napi_callback_info info, int with_view) {
@@ -469,7 +476,7 @@ static napi_value resolve_common(napi_env env, napi_callback_info info, int with
 static napi_value js_resolve_view(napi_env env, napi_callback_info info) { return resolve_common(env, info, 1); }
 static napi_value js_resolve(napi_env env, napi_callback_info info) { return resolve_common(env, info, 0); }
 
-/* releaseViews / releaseAov / releaseDenoised / releaseFused(ctx): a stack goes, through `fn` */
+/* releaseViews / releaseAov / releaseDenoised / releaseFused / releaseMoments(ctx): a stack goes, through `fn` */
 static napi_value release_stack_common(napi_env env, napi_callback_info info, int (*fn)(ptmi_ctx*), const char* what) {
   napi_value a[1];
   if (get_args(env, info, 1, a)) return NULL;
@@ -483,6 +490,7 @@ static napi_value js_release_views(napi_env env, napi_callback_info info) { retu
 static napi_value js_release_aov(napi_env env, napi_callback_info info) { return release_stack_common(env, info, p_ptmi_release_aov, "ptmi_release_aov"); }
 static napi_value js_release_denoised(napi_env env, napi_callback_info info) { return release_stack_common(env, info, p_ptmi_release_denoised, "ptmi_release_denoised"); }
 static napi_value js_release_fused(napi_env env, napi_callback_info info) { return release_stack_common(env, info, p_ptmi_release_fused, "ptmi_release_fused"); }
+static napi_value js_release_moments(napi_env env, napi_callback_info info) { return release_stack_common(env, info, p_ptmi_release_moments, "ptmi_release_moments"); }
 
 /* renderAov(ctx, Float32Array(V*16), nViews, firstFrame, framesPerView, reset): the feature pass (ptmi_render_aov; the reference renders colour only) — view v's
  * three layers of the context's feature stack receive what the first hit of each of view v's frames saw */
@@ -610,6 +618,136 @@ static napi_value js_fuse_views(napi_env env, napi_callback_info info) {
   int st = p_ptmi_fuse_views(c, &P, (const float*)data, (float)frame_num, source, first, n_views);
   if (st) return throw_status(env, c, st, "ptmi_fuse_views");
   return NULL;
+}
+
+/* setViewMoments(ctx, on): ptmi_set_view_moments — while on, renderViews also folds the frames' squared colours into the moment stack */
+static napi_value js_set_view_moments(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (get_args(env, info, 2, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  bool on = false;
+  napi_coerce_to_bool(env, a[1], &a[1]);
+  napi_get_value_bool(env, a[1], &on);
+  int st = p_ptmi_set_view_moments(c, on ? 1 : 0);
+  if (st) return throw_status(env, c, st, "ptmi_set_view_moments");
+  return NULL;
+}
+
+/* params | null -> ptmi_noise_params: {floor, threshold}, every field optional (ptmi_default_noise_params fills the rest); 0 on success */
+static int noise_params_of(napi_env env, napi_value v, ptmi_noise_params* P) {
+  p_ptmi_default_noise_params(P);
+  napi_valuetype t;
+  if (napi_typeof(env, v, &t) != napi_ok) return -1;
+  if (t != napi_object) return 0;
+  static const char* names[2] = {"floor", "threshold"};
+  float* fields[2] = {&P->floor, &P->threshold};
+  for (int k = 0; k < 2; k++) {
+    bool has = false;
+    napi_value f;
+    double d;
+    if (napi_has_named_property(env, v, names[k], &has) != napi_ok) return -1;
+    if (!has) continue;
+    if (napi_get_named_property(env, v, names[k], &f) != napi_ok || napi_get_value_double(env, f, &d) != napi_ok) return -1;
+    *fields[k] = (float)d;
+  }
+  return 0;
+}
+
+/* n records -> [{counted, sumQ, above, maxQ}, ...]; the 64-bit integers as doubles (exact below 2^53: 2^28 pixels x q < 2^24 stay below 2^52) */
+static napi_value noise_records_to_js(napi_env env, const ptmi_view_noise* r, uint32_t n) {
+  napi_value arr;
+  CHECK_NAPI(napi_create_array_with_length(env, n, &arr));
+  for (uint32_t v = 0; v < n; v++) {
+    napi_value o, x;
+    CHECK_NAPI(napi_create_object(env, &o));
+    CHECK_NAPI(napi_create_double(env, (double)r[v].counted, &x));
+    CHECK_NAPI(napi_set_named_property(env, o, "counted", x));
+    CHECK_NAPI(napi_create_double(env, (double)r[v].sum_q, &x));
+    CHECK_NAPI(napi_set_named_property(env, o, "sumQ", x));
+    CHECK_NAPI(napi_create_double(env, (double)r[v].above, &x));
+    CHECK_NAPI(napi_set_named_property(env, o, "above", x));
+    CHECK_NAPI(napi_create_uint32(env, r[v].max_q, &x));
+    CHECK_NAPI(napi_set_named_property(env, o, "maxQ", x));
+    CHECK_NAPI(napi_set_element(env, arr, v, o));
+  }
+  return arr;
+}
+
+/* viewNoise(ctx, firstView, nViews, params | null): ptmi_view_noise_stats — one {counted, sumQ, above, maxQ} per view; mean noise = sumQ / counted / 65536 */
+static napi_value js_view_noise(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (get_args(env, info, 4, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  uint32_t first, n_views;
+  CHECK_NAPI(napi_get_value_uint32(env, a[1], &first));
+  CHECK_NAPI(napi_get_value_uint32(env, a[2], &n_views));
+  ptmi_noise_params P;
+  if (noise_params_of(env, a[3], &P)) {
+    napi_throw_type_error(env, NULL, "viewNoise(params): {floor, threshold} of numbers, or null");
+    return NULL;
+  }
+  if (n_views == 0 || n_views > (1u << 24)) {
+    napi_throw_range_error(env, NULL, "viewNoise: nViews must be 1 .. 2^24");
+    return NULL;
+  }
+  ptmi_view_noise* rec = (ptmi_view_noise*)calloc(n_views, sizeof *rec);
+  if (!rec) {
+    napi_throw_error(env, NULL, "viewNoise: out of memory");
+    return NULL;
+  }
+  int st = p_ptmi_view_noise_stats(c, &P, first, n_views, rec);
+  napi_value out = st ? throw_status(env, c, st, "ptmi_view_noise_stats") : noise_records_to_js(env, rec, n_views);
+  free(rec);
+  return out;
+}
+
+/* renderViewsUntil(ctx, views, firstFrame, framesPerRound, maxFrames, target, params | null): ptmi_render_views_until -> {framesDone, noise: [records]} */
+static napi_value js_render_views_until(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (get_args(env, info, 7, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  void* data;
+  size_t len;
+  if (typed(env, a[1], napi_float32_array, "renderViewsUntil(views)", &data, &len)) return NULL;
+  if (len == 0 || len % 16 != 0 || len / 16 > (1u << 24)) {
+    napi_throw_range_error(env, NULL, "renderViewsUntil: views must hold 16 floats per view, one view at least");
+    return NULL;
+  }
+  uint32_t first, per_round, max_frames, done = 0;
+  double target;
+  CHECK_NAPI(napi_get_value_uint32(env, a[2], &first));
+  CHECK_NAPI(napi_get_value_uint32(env, a[3], &per_round));
+  CHECK_NAPI(napi_get_value_uint32(env, a[4], &max_frames));
+  CHECK_NAPI(napi_get_value_double(env, a[5], &target));
+  ptmi_noise_params P;
+  if (noise_params_of(env, a[6], &P)) {
+    napi_throw_type_error(env, NULL, "renderViewsUntil(params): {floor, threshold} of numbers, or null");
+    return NULL;
+  }
+  const uint32_t n_views = (uint32_t)(len / 16);
+  ptmi_view_noise* rec = (ptmi_view_noise*)calloc(n_views, sizeof *rec);
+  if (!rec) {
+    napi_throw_error(env, NULL, "renderViewsUntil: out of memory");
+    return NULL;
+  }
+  int st = p_ptmi_render_views_until(c, (const float*)data, n_views, first, per_round, max_frames, &P, (float)target, &done, rec);
+  napi_value out = NULL;
+  if (st) {
+    throw_status(env, c, st, "ptmi_render_views_until");
+  } else {
+    napi_value noise = noise_records_to_js(env, rec, n_views), x;
+    if (noise && napi_create_object(env, &out) == napi_ok && napi_create_uint32(env, done, &x) == napi_ok) {
+      napi_set_named_property(env, out, "framesDone", x);
+      napi_set_named_property(env, out, "noise", noise);
+    } else {
+      out = NULL;
+    }
+  }
+  free(rec);
+  return out;
 }
 
 static napi_value js_synchronize(napi_env env, napi_callback_info info) {
@@ -881,7 +1019,7 @@ static napi_value init(napi_env env, napi_value exports) {
   } fns[] = {
       {"version", js_version}, {"create", js_create}, {"destroy", js_destroy}, {"defaultParams", js_default_params}, {"setParams", js_set_params},
       {"upload", js_upload}, {"resize", js_resize}, {"clear", js_clear}, {"setShard", js_set_shard}, {"renderFrame", js_render_frame},
-      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
+      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
       {"resolveRGBA8", js_resolve}, {"setCounters", js_set_counters}, {"setTiming", js_set_timing}, {"stats", js_stats},
       {"resetStats", js_reset_stats}, {"buildBVH", js_build_bvh}, {"buildBVHSAH", js_build_bvh_sah}, {"buildBVHDevice", js_build_bvh_device}, {"parseObj", js_parse_obj},
       {"deviceCount", js_device_count}, {"reduceInfo", js_reduce_info},

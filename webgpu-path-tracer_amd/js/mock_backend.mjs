@@ -17,5 +17,13 @@ export class MockBackend {
   fuseViews(views, frameNum, source, firstView, nViews, params = null) { this.calls.push(['fuseViews', views.length / 16, frameNum, source, firstView, nViews, params]); }
   readFused(view, out) { this.calls.push(['readFused', view]); return out || new Float32Array(this.width * this.height * 4); }
   releaseFused() { this.calls.push(['releaseFused']); }
+  setViewMoments(on = true) { this.calls.push(['setViewMoments', on]); }
+  readMoments(view, out) { this.calls.push(['readMoments', view]); return out || new Float32Array(this.width * this.height * 4); }
+  releaseMoments() { this.calls.push(['releaseMoments']); }
+  viewNoise(firstView, nViews, params = null) { this.calls.push(['viewNoise', firstView, nViews, params]); return Array.from({ length: nViews }, () => ({ counted: 0, sumQ: 0, above: 0, maxQ: 0 })); }
+  renderViewsUntil(views, firstFrame, framesPerRound, maxFrames, target, params = null) {
+    this.calls.push(['renderViewsUntil', views.length / 16, firstFrame, framesPerRound, maxFrames, target, params]);
+    return { framesDone: maxFrames, noise: Array.from({ length: views.length / 16 }, () => ({ counted: 0, sumQ: 0, above: 0, maxQ: 0 })) };
+  }
   synchronize() {}
 }

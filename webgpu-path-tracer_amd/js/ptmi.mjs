@@ -52,6 +52,17 @@ export class Ptmi {
   fuseViews(views, frameNum, source, firstView, nViews, params = null) { this.native.fuseViews(this.h, views, frameNum, source, firstView, nViews, params); }
   readFused(view, out = new Float32Array(this.width * this.height * 4)) { return this.native.readFused(this.h, view, out); }
   releaseFused() { this.native.releaseFused(this.h); }
+  // Second moments and noise (ptmi_set_view_moments ...): while on, renderViews also folds the frames' squared colours (xyz) and their count (w) into the moment stack;
+  // viewNoise gives per view {counted, sumQ, above, maxQ} of the pixels' relative standard error in 16.16 fixed point — mean noise = sumQ / counted / 65536;
+  // renderViewsUntil renders rounds of framesPerRound frames per view until every view's mean noise is at most target or maxFrames are done:
+  // {framesDone, noise}.  params = {floor, threshold}, all optional.
+  setViewMoments(on = true) { this.native.setViewMoments(this.h, on); }
+  readMoments(view, out = new Float32Array(this.width * this.height * 4)) { return this.native.readMoments(this.h, view, out); }
+  releaseMoments() { this.native.releaseMoments(this.h); }
+  viewNoise(firstView, nViews, params = null) { return this.native.viewNoise(this.h, firstView, nViews, params); }
+  renderViewsUntil(views, firstFrame, framesPerRound, maxFrames, target, params = null) {
+    return this.native.renderViewsUntil(this.h, views, firstFrame, framesPerRound, maxFrames, target, params);
+  }
   synchronize() { this.native.synchronize(this.h); }
   prepare() { this.native.prepare(this.h); }
   buildSceneBVHSAH() { this.native.buildSceneBVHSAH(this.h); }   // the same with the reference's never-called SAH builder (lib/BVH/bvhNode.js:108-283): opt-in

@@ -26,6 +26,8 @@ SYMBOLS = [
     "ptmi_denoise_images", "ptmi_denoise_reference",
     "ptmi_default_fuse_params", "ptmi_fuse_views", "ptmi_read_fused", "ptmi_resolve_fused_rgba8", "ptmi_fused_device_ptr", "ptmi_release_fused",
     "ptmi_fuse_images", "ptmi_fuse_reference",
+    "ptmi_set_view_moments", "ptmi_read_moments", "ptmi_moments_device_ptr", "ptmi_release_moments",
+    "ptmi_default_noise_params", "ptmi_view_noise_stats", "ptmi_noise_images", "ptmi_noise_reference", "ptmi_render_views_until",
 ]
 
 
@@ -48,6 +50,17 @@ class FuseParams(ctypes.Structure):
     _fields_ = [
         ("radius", ctypes.c_int32), ("sigma_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float), ("albedo_floor", ctypes.c_float), ("reserved", ctypes.c_int32 * 4),
     ]
+
+
+class NoiseParams(ctypes.Structure):
+    _fields_ = [("floor", ctypes.c_float), ("threshold", ctypes.c_float), ("reserved", ctypes.c_int32 * 6)]
+
+
+class ViewNoise(ctypes.Structure):
+    _fields_ = [("counted", ctypes.c_uint64), ("sum_q", ctypes.c_uint64), ("above", ctypes.c_uint64), ("max_q", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+VIEW_NOISE_DTYPE = np.dtype([("counted", "<u8"), ("sum_q", "<u8"), ("above", "<u8"), ("max_q", "<u4"), ("reserved", "<u4")])
 
 
 class Stats(ctypes.Structure):
@@ -180,6 +193,18 @@ def load_library(build=False, path=None):
         L.ptmi_release_fused.argtypes = [vp]
         L.ptmi_fuse_images.argtypes = [vp, fp, fp, fp, i32, i32, u32, ctypes.c_float, ctypes.c_float, fp, u32, up, fp]
         L.ptmi_fuse_reference.argtypes = [fp, fp, fp, i32, i32, u32, ctypes.c_float, ctypes.c_float, fp, u32, up, fp]
+    if hasattr(L, "ptmi_set_view_moments"):  # (an older A/B build loaded through PTMI_LIB keeps no second moments)
+        qp = ctypes.POINTER(NoiseParams)
+        L.ptmi_set_view_moments.argtypes = [vp, i32]
+        L.ptmi_read_moments.argtypes = [vp, u32, fp, sz]
+        L.ptmi_moments_device_ptr.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(u32)]
+        L.ptmi_release_moments.argtypes = [vp]
+        L.ptmi_default_noise_params.argtypes = [qp]
+        L.ptmi_default_noise_params.restype = None
+        L.ptmi_view_noise_stats.argtypes = [vp, qp, u32, u32, fp]
+        L.ptmi_noise_images.argtypes = [vp, fp, fp, i32, i32, u32, qp, fp, fp]
+        L.ptmi_noise_reference.argtypes = [fp, fp, i32, i32, u32, qp, fp, fp]
+        L.ptmi_render_views_until.argtypes = [vp, fp, u32, u32, u32, u32, qp, ctypes.c_float, ctypes.POINTER(u32), fp]
     if explicit:
         _libs[path] = L
     else:
@@ -258,6 +283,37 @@ def fuse_reference(colour, layers, views, frame_num, fov_degrees=60.0, lambertia
     if st != 0:
         raise PtmiError(st, "ptmi_fuse_reference failed")
     return out
+
+
+def default_noise_params(lib=None, **kw):
+    """ptmi_default_noise_params (floor 1e-2, threshold 0.05) with fields replaced by keyword."""
+    p = NoiseParams()
+    (lib or load_library()).ptmi_default_noise_params(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _noise_arrays(colour_sums, moments, want_map):
+    c = np.ascontiguousarray(colour_sums, np.float32)
+    if c.ndim == 3:
+        c = c[None]
+    n, h, w = c.shape[:3]
+    m = np.ascontiguousarray(moments, np.float32).reshape(n, h, w, 4)
+    assert c.shape == (n, h, w, 4), "colour_sums and moments: (n, H, W, 4) float32"
+    return c, m, np.zeros(n, VIEW_NOISE_DTYPE), (np.empty((n, h, w), np.float32) if want_map else None)
+
+
+def noise_reference(colour_sums, moments, params=None, want_map=False, lib=None):
+    """ptmi_noise_reference: the noise statistic of Context.view_noise on host arrays, on the CPU (no GPU needed) — colour_sums (n, H, W, 4) as Context.read_view and
+    moments (n, H, W, 4) as Context.read_moments give them.  Returns one VIEW_NOISE_DTYPE record per image (counted, sum_q, above, max_q: the kernel's integers) — and,
+    with want_map, (records, map): map (n, H, W) float32, the relative standard error per pixel, NaN where the pixel is not counted."""
+    c, m, out, emap = _noise_arrays(colour_sums, moments, want_map)
+    st = (lib or load_library()).ptmi_noise_reference(_ptr(c), _ptr(m), c.shape[2], c.shape[1], c.shape[0], None if params is None else ctypes.byref(params), _ptr(out),
+                                                      None if emap is None else _ptr(emap))
+    if st != 0:
+        raise PtmiError(st, "ptmi_noise_reference failed")
+    return (out, emap) if want_map else out
 
 
 class NativeHost:
@@ -501,6 +557,48 @@ class Context:
         self._ck(self.lib.ptmi_fuse_images(self.h, _ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], float(frame_num), float(fov_degrees),
                                            None if t is None else _ptr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params), _ptr(out)))
         return out
+
+    def set_view_moments(self, on=True):
+        """ptmi_set_view_moments: while on, render_views also folds the frames' squared colours into the context's moment stack (read_moments); off frees it."""
+        self._ck(self.lib.ptmi_set_view_moments(self.h, 1 if on else 0))
+
+    def read_moments(self, view):
+        """Image `view` of the moment stack as (H, W, 4) float32: xyz the sums of the frames' squared colours, w the number of frames."""
+        return self._read_image(self.lib.ptmi_read_moments, view)
+
+    def moments_device_ptr(self):
+        """(device pointer, bytes, n_views) of the moment stack: one contiguous [n_views][H][W][4] float32 array (single-device contexts)."""
+        return self._device_ptr(self.lib.ptmi_moments_device_ptr)
+
+    def release_moments(self):
+        self._ck(self.lib.ptmi_release_moments(self.h))
+
+    def view_noise(self, first_view=0, n_views=None, params=None):
+        """ptmi_view_noise_stats: one VIEW_NOISE_DTYPE record (counted, sum_q, above, max_q) per view of [first_view, first_view + n_views) from the view and moment
+        stacks; the mean noise of a view is sum_q / counted / 65536.  params: NoiseParams (default_noise_params).  n_views=None: up to the end of the stack (single-device contexts).  Synchronises."""
+        if n_views is None:
+            n_views = self.moments_device_ptr()[2] - first_view
+        out = np.zeros(n_views, VIEW_NOISE_DTYPE)
+        self._ck(self.lib.ptmi_view_noise_stats(self.h, None if params is None else ctypes.byref(params), first_view, n_views, _ptr(out) if out.size else None))
+        return out
+
+    def noise_images(self, colour_sums, moments, params=None, want_map=False):
+        """ptmi_noise_images: the kernel of view_noise on host arrays of any size (see noise_reference for the shapes and the result); synchronous."""
+        c, m, out, emap = _noise_arrays(colour_sums, moments, want_map)
+        self._ck(self.lib.ptmi_noise_images(self.h, _ptr(c), _ptr(m), c.shape[2], c.shape[1], c.shape[0], None if params is None else ctypes.byref(params), _ptr(out),
+                                            None if emap is None else _ptr(emap)))
+        return (out, emap) if want_map else out
+
+    def render_views_until(self, views, first_frame, frames_per_round, max_frames, target, params=None):
+        """ptmi_render_views_until: render_views in rounds of frames_per_round frames per view until every view's mean noise is at most `target` or max_frames are
+        done.  Needs set_view_moments.  Returns (frames_done, records): the frames every view then sums and the last round's VIEW_NOISE_DTYPE records."""
+        v = np.ascontiguousarray(views, np.float32)
+        assert v.ndim == 2 and v.shape[1] == 16, "views: (V, 16) float32"
+        done = ctypes.c_uint32()
+        out = np.zeros(v.shape[0], VIEW_NOISE_DTYPE)
+        self._ck(self.lib.ptmi_render_views_until(self.h, _ptr(v), v.shape[0], first_frame, frames_per_round, max_frames, None if params is None else ctypes.byref(params),
+                                                  float(target), ctypes.byref(done), _ptr(out)))
+        return done.value, out
 
     def camera_rays(self, view16, frame):
         """Test hook (ptmi_camera_rays): (rays (W*H, 6) float32, rng (W*H,) uint32) — the first camera ray of `frame` for every pixel and the RNG state its
