@@ -288,6 +288,54 @@ int ptmi_release_denoised(ptmi_ctx* ctx);
 int ptmi_denoise_images(ptmi_ctx* ctx, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num,
                         const ptmi_denoise_params* params, float* out);
 
+/* Variance-guided denoising (no counterpart in the reference): the filter above made adaptive by the moment stack — the spatial half of SVGF (Schied et al. 2017).
+ * The denoiser above weighs taps by normal, depth and material only, so it blurs every illumination edge that lies inside one surface, and treats a converged pixel
+ * and a noisy one alike; here the per-pixel variance of the moment stack tells signal from noise.  With S, N, A, I, F as above, M the moment-stack image of the same
+ * view (xyz = sums of the frames' squared colours, w = nn, the frames summed) and l(d) = 0.2126 d.x + 0.7152 d.y + 0.0722 d.z:
+ *
+ *   prepare   exactly as above: d0, n, z, a', m and validity, the same bits.
+ *   v0        for valid p, the variance of the demodulated luminance of the pixel's MEAN.  TEMPORAL, when nn >= min_frames and M.xyz is finite: per channel
+ *             mu = S / nn, var = max(M / nn - mu^2, 0), s = sqrt(var) / a';  sigma = l(s);  v0 = sigma^2 / (nn - 1) — the channels of a path's radiance are strongly
+ *             correlated, so this is the perfectly-correlated bound, not the diagonal.  SPATIAL otherwise (one frame per view): over q = p + (i, j), j = -3..3 outer,
+ *             i = -3..3 inner, inside the image, valid, m(q) == m(p): cnt, s1 = sum l(d0(q)), s2 = sum l(d0(q))^2;  v0 = max(s2 / cnt - (s1 / cnt)^2, 0) for cnt >= 2,
+ *             else 0.  A v0 that is not finite (an overflow of f32) becomes 0: the pixel is taken as it is (include/ptmi_guided.h says why not an infinity).
+ *   level l = 0 .. levels-1, step s = 2^l, for every valid p:
+ *             vg(p) = sum g v_l(q) / sum g over the 3 x 3 neighbours at distance 1 (at every level), g = 1/4, 1/8, 1/16, q inside, valid, m(q) == m(p);
+ *             il(p) = 1 / (sigma_luma^2 vg(p) + var_eps);
+ *             the 25 taps of the filter above, the same skips and order, e = the normal term + the depth term (no colour term)
+ *               [+ (l(d_l(q)) - l(d_l(p)))^2 il(p) when sigma_luma > 0; absent otherwise]
+ *             w = h_i h_j exp2(-e);  num += w d_l(q), den += w, vnum += w^2 v_l(q);  d_{l+1}(p) = num / den,  v_{l+1}(p) = vnum / den^2.
+ *   output    as above (ptmd_remodulate); invalid pixels are never taps and pass through as S / F.
+ *
+ * With sigma_luma = 0 the colour output is ptmi_denoise_views' with sigma_colour = 0, bit for bit.  The f32 operation order is fixed in include/ptmi_guided.h, which
+ * the kernels and ptmi_denoise_guided_reference both compile: their results agree bit for bit.  The defaults (ptmi_default_guided_params: levels 5, sigma_normal
+ * 0.25, sigma_depth 0.1, sigma_luma 4, albedo_floor 1e-3, min_frames 4, var_eps 1e-10) are SVGF's. */
+typedef struct ptmi_guided_params {
+  int32_t levels;       /* 1 .. 6 */
+  float sigma_normal;   /* > 0 */
+  float sigma_depth;    /* > 0 */
+  float sigma_luma;     /* >= 0; 0 = no luminance term */
+  float albedo_floor;   /* > 0 */
+  int32_t min_frames;   /* >= 2: fewer folded frames than this and a pixel's variance comes from its neighbourhood */
+  float var_eps;        /* > 0, finite, and a normal f32 (>= 2^-126): its reciprocal has to be finite */
+  int32_t reserved[1];
+} ptmi_guided_params;
+void ptmi_default_guided_params(ptmi_guided_params* p);
+/* ptmi_denoise_views with the filter above: reads images [first_view, first_view + n_views) of the view stack, the MOMENT stack (ptmi_set_view_moments) and the
+ * feature stack and writes the same DENOISED STACK, so ptmi_read_denoised, ptmi_resolve_denoised_rgba8, ptmi_denoised_device_ptr, ptmi_release_denoised and
+ * ptmi_fuse_views(source = 1) work on its result unchanged; images outside the range keep what they held.  Everything else as ptmi_denoise_views: asynchronous on
+ * the context's stream, touches no other stack and no ptmi_stats field, the views of a batch go through each level in one launch; the scratch, which it shares with
+ * ptmi_denoise_views, is 60 bytes per pixel and view here (the variance, twice, and its blur) and held to 1 GiB (8 views at 1080p).
+ * PTMI_ERR_STATE: a stack is missing — the moment stack too, which is the case while moments are off —, or they differ in n_views.  PTMI_ERR_INVALID_ARG: a parameter
+ * outside its domain, a range past the stack, frame_num not finite or not > 0.  PTMI_ERR_NO_MEMORY: before anything is enqueued; the denoised stack the call found
+ * stays as it was.  PTMI_ERR_UNSUPPORTED: a multi-device context or a shard; gather the images first and use ptmi_denoise_images_guided. */
+int ptmi_denoise_views_guided(ptmi_ctx* ctx, const ptmi_guided_params* params, float frame_num, uint32_t first_view, uint32_t n_views);
+/* The same kernels on host arrays: colour_sums and moments [n_images][h][w][4], layers [n_images][3][h][w][4], out [n_images][h][w][4], all f32; var_out, where not
+ * NULL, [n_images][h][w] f32, receives v_levels, the final filtered variance, NaN on invalid pixels.  Synchronous; uses device copies of its own and leaves the
+ * context's stacks alone.  Errors as above (no PTMI_ERR_STATE). */
+int ptmi_denoise_images_guided(ptmi_ctx* ctx, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
+                               const ptmi_guided_params* params, float* out, float* var_out);
+
 /* Fusion (no counterpart in the reference, which shows one camera at a time): cross-view accumulation by reprojection — the views of a camera path are mostly
  * samples of the same surfaces, and everything needed to bring them together is in the feature stack.  A stack of n views with view matrices M_u (column-major, as
  * ptmi_render_views takes them): S_u the colour image of view u; N_u, A_u, I_u layers 0, 1, 2 of the feature stack; F the divisor of S (frame_num when `source` is
@@ -524,6 +572,11 @@ int ptmi_build_bvh_sah_device(ptmi_ctx* ctx, size_t n_prims, const double* bmin,
  * bits.  PTMI_ERR_INVALID_ARG / PTMI_ERR_NO_MEMORY as there. */
 int ptmi_denoise_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params,
                            float* out);
+
+/* ptmi_denoise_images_guided without a GPU: a plain loop over pixels through include/ptmi_guided.h, the arithmetic the kernels compile — the same arguments, the
+ * same bits, var_out (may be NULL) included.  PTMI_ERR_INVALID_ARG / PTMI_ERR_NO_MEMORY as there. */
+int ptmi_denoise_guided_reference(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
+                                  const ptmi_guided_params* params, float* out, float* var_out);
 
 /* ptmi_fuse_images without a GPU: a plain loop over views and pixels through include/ptmi_fuse.h, the arithmetic the kernel compiles — the same arguments, the same
  * bits.  PTMI_ERR_INVALID_ARG / PTMI_ERR_NO_MEMORY as there. */

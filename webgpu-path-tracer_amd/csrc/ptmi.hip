@@ -24,6 +24,7 @@
 #include "ptmi_dbuf.h"
 #include "ptmi_kernels.h"
 #include "ptmi_denoise_kernels.h"
+#include "ptmi_guided_kernels.h"
 #include "ptmi_fuse_kernels.h"
 #include "ptmi_noise_kernels.h"
 #include "ptmi_tuning.h"
@@ -149,7 +150,7 @@ struct ptmi_ctx {
   // The image stacks (StackKind, kStackInfo): per kind one allocation of n x images-per-view images of W x H float4.  The denoised and fused stacks have the view stack's
   // size and go with it (drop_stack).
   Stack stacks[N_STACKS];
-  DBuf d_denoise_scratch;  // ptmi_denoise_views: three packed float4 images (d ping, d pong, n + z) per view of a batch (denoise_batch_views)
+  DBuf d_denoise_scratch;  // ptmi_denoise_views: three packed float4 images (d ping, d pong, n + z) per view of a batch (denoise_batch_views); ptmi_denoise_views_guided: and three f32 images (v ping, v pong, vg)
   StagedTable view_rows;   // the last ptmi_render_views / ptmi_render_aov call's view table (ViewTab: kViewRow float4 per view)
   StagedTable fuse_tab;    // the last ptmi_fuse_views call's table (kFuseRow float4 per view of the stack, then one byte per material)
   bool view_moments = false;  // ptmi_set_view_moments: ptmi_render_views folds second moments into stacks[STACK_MOMENTS] too
@@ -2276,6 +2277,113 @@ int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* laye
   const size_t npix = (size_t)w * (size_t)h;
   return on_host_images(c, "ptmi_denoise_images", colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, denoise_scratch_bytes(npix, n_images),
                         [&](const float4* col, const float4* lay, float4* res) { return denoise_enqueue(c, col, lay, res, n_images, w, h, frame_num, P); });
+}
+
+// ---- the variance-guided filter (ptmi_denoise_views_guided, ptmi_denoise_images_guided) into the denoised stack ----
+// (ptmi_default_guided_params and ptmi_denoise_guided_reference need no GPU: ptmi_host.cpp)
+// Views per batch: the plain filter's three float4 images and three f32 images (v ping, v pong, vg) per view, 60 bytes per pixel, held to the same 1 GiB (8 views at
+// 1080p), in the same scratch buffer.
+static uint32_t guided_batch_views(size_t npix, uint32_t n) { return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / (npix * 60))); }
+static size_t guided_scratch_bytes(size_t npix, uint32_t n) { return (size_t)guided_batch_views(npix, n) * npix * 60; }
+
+// The filter on device arrays: colour, moments [n][H][W] float4 sums, layers [n][3][H][W] float4, out [n][H][W] float4, var_out [n][H][W] f32 or nullptr.
+// c->d_denoise_scratch holds guided_scratch_bytes already: nothing here allocates.  Per batch one k_denoise_prepare, one k_guided_variance and per level one
+// k_guided_blur (with a luminance term only: the blur feeds nothing else) and one k_guided_level, the last of which writes `out` and `var_out`.
+static int guided_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, const float4* layers, float4* out, float* var_out, uint32_t n, int W, int H, float F,
+                          const ptmi_guided_params& P) {
+  const size_t npix = (size_t)W * (size_t)H;
+  const uint32_t B = guided_batch_views(npix, n);
+  float4* d[2] = {c->d_denoise_scratch.as<float4>(), c->d_denoise_scratch.as<float4>() + (size_t)B * npix};
+  float4* g = c->d_denoise_scratch.as<float4>() + 2 * (size_t)B * npix;
+  float* f = reinterpret_cast<float*>(c->d_denoise_scratch.as<float4>() + 3 * (size_t)B * npix);
+  float* v[2] = {f, f + (size_t)B * npix};
+  float* vg = f + 2 * (size_t)B * npix;
+  const ptmg_consts kg = ptmg_make_consts(P.sigma_luma, P.var_eps);
+  for (uint32_t v0 = 0; v0 < n; v0 += B) {
+    const uint32_t nv = std::min(B, n - v0);
+    const float4* col = colour + (size_t)v0 * npix;
+    const float4* mom = moments + (size_t)v0 * npix;
+    const float4* lay = layers + (size_t)v0 * 3 * npix;
+    const size_t items = (size_t)nv * npix;
+    const unsigned pgrid = (unsigned)std::min<size_t>((items + kBlock - 1) / kBlock, (size_t)c->num_cus * 32);
+    hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, F, P.albedo_floor, d[0], g);
+    HIP_TRY(c, hipGetLastError());
+    const dim3 tgrid((unsigned)((W + kDenoiseTX - 1) / kDenoiseTX), (unsigned)((H + kGuidedTY - 1) / kGuidedTY), nv);
+    hipLaunchKernelGGL(k_guided_variance, tgrid, dim3(kBlock), 0, c->stream, d[0], col, mom, lay, W, H, P.albedo_floor, P.min_frames, v[0]);
+    HIP_TRY(c, hipGetLastError());
+    for (int l = 0; l < P.levels; l++) {
+      const int step = 1 << l, ty = step >= 32 ? 4 : 8;
+      const ptmd_consts k = ptmd_level_consts(P.sigma_normal, P.sigma_depth, 0.0f, P.albedo_floor, l);
+      if (kg.luma) {
+        hipLaunchKernelGGL(k_guided_blur, tgrid, dim3(kBlock), 0, c->stream, d[l & 1], v[l & 1], W, H, vg);
+        HIP_TRY(c, hipGetLastError());
+      }
+      const dim3 grid((unsigned)((W + kDenoiseTX - 1) / kDenoiseTX), (unsigned)(((H + step * ty - 1) / (step * ty)) * step), nv);
+      const size_t lds = (size_t)(ty + 4) * (kDenoiseTX + 4 * step) * (2 * sizeof(float4) + sizeof(float2));  // 60 KB at most (step 16 and 32)
+      if (l == P.levels - 1)
+        hipLaunchKernelGGL(k_guided_level<true>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, out + (size_t)v0 * npix, var_out ? var_out + (size_t)v0 * npix : nullptr, col,
+                           lay, W, H, step, ty, k, kg, F);
+      else
+        hipLaunchKernelGGL(k_guided_level<false>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, d[(l + 1) & 1], v[(l + 1) & 1], col, lay, W, H, step, ty, k, kg, F);
+      HIP_TRY(c, hipGetLastError());
+    }
+  }
+  return PTMI_OK;
+}
+
+static int guided_check_args(ptmi_ctx* c, const char* who, const ptmi_guided_params* params, float frame_num, ptmi_guided_params* P) {
+  if (!c->peers.empty() || c->multi) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a multi-device context keeps a pixel's neighbours on other GPUs");
+  if (c->world > 1) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a sharded context (ptmi_set_shard) keeps a pixel's neighbours in other processes");
+  if (params) *P = *params;
+  else ptmi_default_guided_params(P);
+  if (!ptmg_params_ok(P->levels, P->sigma_normal, P->sigma_depth, P->sigma_luma, P->albedo_floor, P->min_frames, P->var_eps))
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need levels in 1..6, sigma_normal, sigma_depth and albedo_floor > 0, sigma_luma >= 0, min_frames >= 2, var_eps a normal f32 > 0, all finite");
+  if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": frame_num must be finite and > 0");
+  return PTMI_OK;
+}
+
+int ptmi_denoise_views_guided(ptmi_ctx* c, const ptmi_guided_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  ptmi_guided_params P;
+  if (int r = guided_check_args(c, "ptmi_denoise_views_guided", params, frame_num, &P)) return r;
+  if (int r = check_stack(c, STACK_MOMENTS, "ptmi_denoise_views_guided", 0)) return r;
+  if (int r = check_stack(c, STACK_VIEWS, "ptmi_denoise_views_guided", 0)) return r;
+  if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
+    return fail(c, PTMI_ERR_STATE, "ptmi_denoise_views_guided: the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
+  if (int r = check_source_stacks(c, "ptmi_denoise_views_guided", false, first_view, n_views)) return r;
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  const size_t npix = (size_t)c->W * (size_t)c->H;
+  const uint32_t n_stack = c->stacks[STACK_VIEWS].n;
+  DBuf stack;
+  if (int r = reserve_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
+  HIP_TRY(c, c->d_denoise_scratch.ensure_idle(guided_scratch_bytes(npix, n_views), c->stream));
+  if (int r = commit_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
+  return guided_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)first_view * npix, c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix,
+                        c->stacks[STACK_FEATURES].buf.as<float4>() + (size_t)first_view * 3 * npix, c->stacks[STACK_DENOISED].buf.as<float4>() + (size_t)first_view * npix, nullptr, n_views,
+                        c->W, c->H, frame_num, P);
+}
+
+int ptmi_denoise_images_guided(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
+                               const ptmi_guided_params* params, float* out, float* var_out) {
+  if (!c || !colour_sums || !moments || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images_guided: null argument");
+  ptmi_guided_params P;
+  if (int r = guided_check_args(c, "ptmi_denoise_images_guided", params, frame_num, &P)) return r;
+  if (w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull)
+    return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images_guided: need w, h, n_images >= 1 and w * h < 2^31");
+  const size_t npix = (size_t)w * (size_t)h, bytes = npix * 16 * n_images, var_bytes = var_out ? npix * 4 * n_images : 0;
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  DBuf mom, var;  // (on_host_images brings the colour, the layers and the output; these two are this call's own, had before anything is enqueued)
+  HIP_TRY(c, mom.ensure(bytes));
+  HIP_TRY(c, var.ensure(var_bytes));
+  return on_host_images(c, "ptmi_denoise_images_guided", colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, guided_scratch_bytes(npix, n_images),
+                        [&](const float4* col, const float4* lay, float4* res) -> int {
+                          HIP_TRY(c, hipMemcpyAsync(mom.p, moments, bytes, hipMemcpyHostToDevice, c->stream));
+                          if (int e = guided_enqueue(c, col, mom.as<float4>(), lay, res, var.as<float>(), n_images, w, h, frame_num, P)) return e;
+                          if (var_out) HIP_TRY(c, hipMemcpyAsync(var_out, var.p, var_bytes, hipMemcpyDeviceToHost, c->stream));
+                          return PTMI_OK;
+                        });
 }
 
 // ---- the fused stack (ptmi_fuse_views, ptmi_fuse_images) ----

@@ -20,6 +20,7 @@
 
 #include "../../include/ptmi.h"
 #include "../../include/ptmi_denoise.h"
+#include "../../include/ptmi_guided.h"
 #include "../../include/ptmi_fuse.h"
 #include "../../include/ptmi_noise.h"
 
@@ -714,6 +715,125 @@ extern "C" int ptmi_denoise_reference(const float* colour_sums, const float* lay
     }
     const std::vector<ptmd_f4>& last = d[P.levels & 1];
     for (size_t p = 0; p < npix; p++) O[p] = ptmd_remodulate(S[p], L[npix + p], frame_num, P.albedo_floor, last[p]);
+  }
+  return PTMI_OK;
+}
+
+// ---- the variance-guided filter on the host (ptmi_denoise_guided_reference) ----
+extern "C" void ptmi_default_guided_params(ptmi_guided_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->levels = 5;
+  p->sigma_normal = 0.25f;
+  p->sigma_depth = 0.1f;
+  p->sigma_luma = 4.0f;
+  p->albedo_floor = 1e-3f;
+  p->min_frames = 4;
+  p->var_eps = 1e-10f;
+}
+
+// A plain loop over pixels through include/ptmi_guided.h, the header the kernels of ptmi_denoise_views_guided compile: prepare, the initial variance, per level the
+// blur of the variance and the 25 taps, remodulate.  One image after the other; nothing is tiled, threaded or reordered.
+extern "C" int ptmi_denoise_guided_reference(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
+                                             const ptmi_guided_params* params, float* out, float* var_out) {
+  if (!colour_sums || !moments || !layers || !out || w <= 0 || h <= 0 || n_images == 0) return PTMI_ERR_INVALID_ARG;
+  ptmi_guided_params P;
+  if (params) P = *params;
+  else ptmi_default_guided_params(&P);
+  if (!ptmg_params_ok(P.levels, P.sigma_normal, P.sigma_depth, P.sigma_luma, P.albedo_floor, P.min_frames, P.var_eps)) return PTMI_ERR_INVALID_ARG;
+  if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
+  const size_t npix = (size_t)w * (size_t)h;
+  std::vector<ptmd_f4> d[2], g;
+  std::vector<float> var[2], vg, lum;
+  try {
+    d[0].resize(npix), d[1].resize(npix), g.resize(npix), var[0].resize(npix), var[1].resize(npix), vg.resize(npix), lum.resize(npix);
+  } catch (const std::bad_alloc&) {
+    return PTMI_ERR_NO_MEMORY;
+  }
+  const ptmd_f4 outside{0.0f, 0.0f, 0.0f, ptmd_nan()};
+  const ptmg_consts kg = ptmg_make_consts(P.sigma_luma, P.var_eps);
+  for (uint32_t v = 0; v < n_images; v++) {
+    const ptmd_f4* S = reinterpret_cast<const ptmd_f4*>(colour_sums) + (size_t)v * npix;
+    const ptmd_f4* M = reinterpret_cast<const ptmd_f4*>(moments) + (size_t)v * npix;
+    const ptmd_f4* L = reinterpret_cast<const ptmd_f4*>(layers) + (size_t)v * 3 * npix;
+    ptmd_f4* O = reinterpret_cast<ptmd_f4*>(out) + (size_t)v * npix;
+    for (size_t p = 0; p < npix; p++) {
+      ptmd_prepare(S[p], L[p], L[npix + p], L[2 * npix + p], frame_num, P.albedo_floor, &d[0][p], &g[p]);
+      lum[p] = ptmg_luma(d[0][p].x, d[0][p].y, d[0][p].z);
+    }
+    for (int y = 0; y < h; y++)
+      for (int x = 0; x < w; x++) {
+        const size_t p = (size_t)y * w + x;
+        const float mp = d[0][p].w;
+        float v0 = 0.0f;
+        if (mp == mp && !ptmg_v0_temporal(S[p], M[p], L[npix + p], P.albedo_floor, P.min_frames, &v0)) {
+          float cnt = 0.0f, s1 = 0.0f, s2 = 0.0f;
+          for (int j = -3; j <= 3; j++)
+            for (int i = -3; i <= 3; i++) {
+              const int qx = x + i, qy = y + j;
+              if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+              const size_t q = (size_t)qy * w + qx;
+              ptmg_v0_add(mp, d[0][q].w, lum[q], &cnt, &s1, &s2);
+            }
+          v0 = ptmg_v0_spatial(cnt, s1, s2);
+        }
+        var[0][p] = v0;
+      }
+    for (int l = 0; l < P.levels; l++) {
+      const int step = 1 << l;
+      const ptmd_consts k = ptmd_level_consts(P.sigma_normal, P.sigma_depth, 0.0f, P.albedo_floor, l);
+      const std::vector<ptmd_f4>& in = d[l & 1];
+      std::vector<ptmd_f4>& to = d[(l + 1) & 1];
+      const std::vector<float>& vin = var[l & 1];
+      std::vector<float>& vto = var[(l + 1) & 1];
+      if (kg.luma)
+        for (int y = 0; y < h; y++)
+          for (int x = 0; x < w; x++) {
+            const size_t p = (size_t)y * w + x;
+            const float mp = in[p].w;
+            float gv = 0.0f, gs = 0.0f;
+            if (mp == mp)
+              for (int j = -1; j <= 1; j++)
+                for (int i = -1; i <= 1; i++) {
+                  const int qx = x + i, qy = y + j;
+                  if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+                  const size_t q = (size_t)qy * w + qx;
+                  ptmg_blur_add(mp, in[q].w, vin[q], ptmg_g(i) * ptmg_g(j), &gv, &gs);
+                }
+            vg[p] = mp == mp ? ptmg_blur(gv, gs) : 0.0f;
+          }
+      if (l > 0)
+        for (size_t p = 0; p < npix; p++) lum[p] = ptmg_luma(in[p].x, in[p].y, in[p].z);
+      for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+          const size_t p = (size_t)y * w + x;
+          ptmd_f4 dp = in[p];
+          float vp = vin[p];
+          if (dp.w == dp.w) {
+            const ptmd_f4 gp = g[p];
+            const float zs = ptmd_depth_scale(k.sigma_depth, gp.w);
+            const float il = kg.luma ? ptmg_inv_luma(&kg, vg[p]) : 0.0f;
+            float num[3] = {0.0f, 0.0f, 0.0f}, den = 0.0f, vnum = 0.0f;
+            for (int j = -2; j <= 2; j++)
+              for (int i = -2; i <= 2; i++) {
+                const int qx = x + i * step, qy = y + j * step;
+                const bool inside = qx >= 0 && qx < w && qy >= 0 && qy < h;
+                const size_t q = inside ? (size_t)qy * w + qx : p;
+                ptmg_tap(&k, &kg, dp, gp, zs, lum[p], il, inside ? in[q] : outside, g[q], lum[q], vin[q], ptmd_h(i) * ptmd_h(j), num, &den, &vnum);
+              }
+            dp.x = num[0] / den, dp.y = num[1] / den, dp.z = num[2] / den;
+            vp = vnum / (den * den);
+          }
+          to[p] = dp;
+          vto[p] = vp;
+        }
+    }
+    const std::vector<ptmd_f4>& last = d[P.levels & 1];
+    const std::vector<float>& vlast = var[P.levels & 1];
+    for (size_t p = 0; p < npix; p++) {
+      O[p] = ptmd_remodulate(S[p], L[npix + p], frame_num, P.albedo_floor, last[p]);
+      if (var_out) var_out[(size_t)v * npix + p] = last[p].w == last[p].w ? vlast[p] : ptmd_nan();
+    }
   }
   return PTMI_OK;
 }

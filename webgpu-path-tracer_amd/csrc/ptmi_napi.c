@@ -45,6 +45,8 @@ FN(ptmi_render_aov)
 FN(ptmi_read_aov)
 FN(ptmi_release_aov)
 FN(ptmi_denoise_views)
+FN(ptmi_default_guided_params)
+FN(ptmi_denoise_views_guided)
 FN(ptmi_read_denoised)
 FN(ptmi_release_denoised)
 FN(ptmi_default_fuse_params)
@@ -105,7 +107,7 @@ static int load_lib(char* err, size_t errlen) {
   }
   LOAD(ptmi_version) LOAD(ptmi_last_error) LOAD(ptmi_create) LOAD(ptmi_create_multi) LOAD(ptmi_prepare) LOAD(ptmi_destroy) LOAD(ptmi_default_params) LOAD(ptmi_default_denoise_params) LOAD(ptmi_set_params)
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
-  LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_set_view_moments) LOAD(ptmi_read_moments) LOAD(ptmi_release_moments) LOAD(ptmi_default_noise_params) LOAD(ptmi_view_noise_stats) LOAD(ptmi_render_views_until) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
+  LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_default_guided_params) LOAD(ptmi_denoise_views_guided) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_set_view_moments) LOAD(ptmi_read_moments) LOAD(ptmi_release_moments) LOAD(ptmi_default_noise_params) LOAD(ptmi_view_noise_stats) LOAD(ptmi_render_views_until) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
   LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah)
   LOAD(ptmi_obj_parse) LOAD(ptmi_free) LOAD(ptmi_device_count) LOAD(ptmi_reduce_info)
   return 0;
@@ -571,6 +573,43 @@ static napi_value js_denoise_views(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* denoiseViewsGuided(ctx, frameNum, firstView, nViews, params | null): ptmi_denoise_views_guided — params = {levels, sigmaNormal, sigmaDepth, sigmaLuma, albedoFloor,
+ * minFrames, varEps}, every field optional (ptmi_default_guided_params fills the rest) */
+static napi_value js_denoise_views_guided(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (get_args(env, info, 5, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  double frame_num;
+  uint32_t first, n_views;
+  CHECK_NAPI(napi_get_value_double(env, a[1], &frame_num));
+  CHECK_NAPI(napi_get_value_uint32(env, a[2], &first));
+  CHECK_NAPI(napi_get_value_uint32(env, a[3], &n_views));
+  ptmi_guided_params P;
+  p_ptmi_default_guided_params(&P);
+  napi_valuetype t;
+  CHECK_NAPI(napi_typeof(env, a[4], &t));
+  if (t == napi_object) {
+    static const char* names[7] = {"levels", "minFrames", "sigmaNormal", "sigmaDepth", "sigmaLuma", "albedoFloor", "varEps"};
+    int32_t* ints[2] = {&P.levels, &P.min_frames};
+    float* fields[7] = {NULL, NULL, &P.sigma_normal, &P.sigma_depth, &P.sigma_luma, &P.albedo_floor, &P.var_eps};
+    for (int k = 0; k < 7; k++) {
+      bool has = false;
+      napi_value v;
+      CHECK_NAPI(napi_has_named_property(env, a[4], names[k], &has));
+      if (!has) continue;
+      double d;
+      CHECK_NAPI(napi_get_named_property(env, a[4], names[k], &v));
+      CHECK_NAPI(napi_get_value_double(env, v, &d));
+      if (k < 2) *ints[k] = (int32_t)d;
+      else *fields[k] = (float)d;
+    }
+  }
+  int st = p_ptmi_denoise_views_guided(c, &P, (float)frame_num, first, n_views);
+  if (st) return throw_status(env, c, st, "ptmi_denoise_views_guided");
+  return NULL;
+}
+
 /* fuseViews(ctx, views, frameNum, source, firstView, nViews, params | null): ptmi_fuse_views — views holds the matrices of ALL views of the stack; params =
  * {radius, sigmaNormal, sigmaDepth, albedoFloor}, every field optional (ptmi_default_fuse_params fills the rest) */
 static napi_value js_fuse_views(napi_env env, napi_callback_info info) {
@@ -1019,7 +1058,7 @@ static napi_value init(napi_env env, napi_value exports) {
   } fns[] = {
       {"version", js_version}, {"create", js_create}, {"destroy", js_destroy}, {"defaultParams", js_default_params}, {"setParams", js_set_params},
       {"upload", js_upload}, {"resize", js_resize}, {"clear", js_clear}, {"setShard", js_set_shard}, {"renderFrame", js_render_frame},
-      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
+      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"denoiseViewsGuided", js_denoise_views_guided}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
       {"resolveRGBA8", js_resolve}, {"setCounters", js_set_counters}, {"setTiming", js_set_timing}, {"stats", js_stats},
       {"resetStats", js_reset_stats}, {"buildBVH", js_build_bvh}, {"buildBVHSAH", js_build_bvh_sah}, {"buildBVHDevice", js_build_bvh_device}, {"parseObj", js_parse_obj},
       {"deviceCount", js_device_count}, {"reduceInfo", js_reduce_info},

@@ -12,6 +12,7 @@ export class MockBackend {
   readAov(view, layer, out) { this.calls.push(['readAov', view, layer]); return out || new Float32Array(this.width * this.height * 4); }
   releaseAov() { this.calls.push(['releaseAov']); }
   denoiseViews(frameNum, firstView, nViews, params = null) { this.calls.push(['denoiseViews', frameNum, firstView, nViews, params]); }
+  denoiseViewsGuided(frameNum, firstView, nViews, params = null) { this.calls.push(['denoiseViewsGuided', frameNum, firstView, nViews, params]); }
   readDenoised(view, out) { this.calls.push(['readDenoised', view]); return out || new Float32Array(this.width * this.height * 4); }
   releaseDenoised() { this.calls.push(['releaseDenoised']); }
   fuseViews(views, frameNum, source, firstView, nViews, params = null) { this.calls.push(['fuseViews', views.length / 16, frameNum, source, firstView, nViews, params]); }

@@ -44,6 +44,10 @@ export class Ptmi {
   // The denoiser (ptmi_denoise_views): filters images [firstView, firstView + nViews) of the view stack under the same images of the feature stack into the denoised
   // stack (mean radiance); frameNum = the frames each view-stack image sums; params = {levels, sigmaNormal, sigmaDepth, sigmaColour, albedoFloor}, all optional.
   denoiseViews(frameNum, firstView, nViews, params = null) { this.native.denoiseViews(this.h, frameNum, firstView, nViews, params); }
+  // The variance-guided denoiser (ptmi_denoise_views_guided): denoiseViews with a luminance term scaled by the per-pixel variance of the moment stack (setViewMoments
+  // must have been on while the views were rendered); writes the same denoised stack; params = {levels, sigmaNormal, sigmaDepth, sigmaLuma, albedoFloor, minFrames,
+  // varEps}, all optional.
+  denoiseViewsGuided(frameNum, firstView, nViews, params = null) { this.native.denoiseViewsGuided(this.h, frameNum, firstView, nViews, params); }
   readDenoised(view, out = new Float32Array(this.width * this.height * 4)) { return this.native.readDenoised(this.h, view, out); }
   releaseDenoised() { this.native.releaseDenoised(this.h); }
   // Cross-view fusion (ptmi_fuse_views): output views [firstView, firstView + nViews) gather their neighbours of the stack by reprojection into the fused stack (mean

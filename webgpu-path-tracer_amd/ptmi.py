@@ -24,6 +24,7 @@ SYMBOLS = [
     "ptmi_render_aov", "ptmi_read_aov", "ptmi_aov_device_ptr", "ptmi_release_aov", "ptmi_camera_rays",
     "ptmi_default_denoise_params", "ptmi_denoise_views", "ptmi_read_denoised", "ptmi_resolve_denoised_rgba8", "ptmi_denoised_device_ptr", "ptmi_release_denoised",
     "ptmi_denoise_images", "ptmi_denoise_reference",
+    "ptmi_default_guided_params", "ptmi_denoise_views_guided", "ptmi_denoise_images_guided", "ptmi_denoise_guided_reference",
     "ptmi_default_fuse_params", "ptmi_fuse_views", "ptmi_read_fused", "ptmi_resolve_fused_rgba8", "ptmi_fused_device_ptr", "ptmi_release_fused",
     "ptmi_fuse_images", "ptmi_fuse_reference",
     "ptmi_set_view_moments", "ptmi_read_moments", "ptmi_moments_device_ptr", "ptmi_release_moments",
@@ -43,6 +44,13 @@ class DenoiseParams(ctypes.Structure):
     _fields_ = [
         ("levels", ctypes.c_int32), ("sigma_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float), ("sigma_colour", ctypes.c_float),
         ("albedo_floor", ctypes.c_float), ("reserved", ctypes.c_int32 * 3),
+    ]
+
+
+class GuidedParams(ctypes.Structure):
+    _fields_ = [
+        ("levels", ctypes.c_int32), ("sigma_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float), ("sigma_luma", ctypes.c_float),
+        ("albedo_floor", ctypes.c_float), ("min_frames", ctypes.c_int32), ("var_eps", ctypes.c_float), ("reserved", ctypes.c_int32 * 1),
     ]
 
 
@@ -182,6 +190,13 @@ def load_library(build=False, path=None):
         L.ptmi_release_denoised.argtypes = [vp]
         L.ptmi_denoise_images.argtypes = [vp, fp, fp, i32, i32, u32, ctypes.c_float, dp, fp]
         L.ptmi_denoise_reference.argtypes = [fp, fp, i32, i32, u32, ctypes.c_float, dp, fp]
+    if hasattr(L, "ptmi_denoise_views_guided"):  # (an older A/B build loaded through PTMI_LIB has no variance-guided filter)
+        gp = ctypes.POINTER(GuidedParams)
+        L.ptmi_default_guided_params.argtypes = [gp]
+        L.ptmi_default_guided_params.restype = None
+        L.ptmi_denoise_views_guided.argtypes = [vp, gp, ctypes.c_float, u32, u32]
+        L.ptmi_denoise_images_guided.argtypes = [vp, fp, fp, fp, i32, i32, u32, ctypes.c_float, gp, fp, fp]
+        L.ptmi_denoise_guided_reference.argtypes = [fp, fp, fp, i32, i32, u32, ctypes.c_float, gp, fp, fp]
     if hasattr(L, "ptmi_fuse_views"):  # (an older A/B build loaded through PTMI_LIB has no cross-view fusion)
         up = ctypes.POINTER(FuseParams)
         L.ptmi_default_fuse_params.argtypes = [up]
@@ -254,6 +269,34 @@ def denoise_reference(colour_sums, layers, frame_num, params=None, lib=None):
     if st != 0:
         raise PtmiError(st, "ptmi_denoise_reference failed")
     return out
+
+
+def default_guided_params(lib=None, **kw):
+    """ptmi_default_guided_params (levels 5, sigma_normal 0.25, sigma_depth 0.1, sigma_luma 4, albedo_floor 1e-3, min_frames 4, var_eps 1e-10) with fields replaced
+    by keyword."""
+    p = GuidedParams()
+    (lib or load_library()).ptmi_default_guided_params(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _guided_arrays(colour_sums, moments, layers, want_var):
+    c, l, out = _denoise_arrays(colour_sums, layers)
+    m = np.ascontiguousarray(moments, np.float32).reshape(c.shape)
+    return c, m, l, out, (np.empty(c.shape[:3], np.float32) if want_var else None)
+
+
+def denoise_guided_reference(colour_sums, moments, layers, frame_num, params=None, want_var=False, lib=None):
+    """ptmi_denoise_guided_reference: the variance-guided filter of Context.denoise_views_guided on host arrays, on the CPU (no GPU needed) — colour_sums and moments
+    (n, H, W, 4) as Context.read_view and Context.read_moments give them, layers (n, 3, H, W, 4) as Context.read_aov gives them; returns (n, H, W, 4) mean radiance,
+    the kernels' bits — and, with want_var, (radiance, var): var (n, H, W) float32, the final filtered variance, NaN on invalid pixels."""
+    c, m, l, out, var = _guided_arrays(colour_sums, moments, layers, want_var)
+    st = (lib or load_library()).ptmi_denoise_guided_reference(_ptr(c), _ptr(m), _ptr(l), c.shape[2], c.shape[1], c.shape[0], float(frame_num),
+                                                               None if params is None else ctypes.byref(params), _ptr(out), None if var is None else _ptr(var))
+    if st != 0:
+        raise PtmiError(st, "ptmi_denoise_guided_reference failed")
+    return (out, var) if want_var else out
 
 
 def default_fuse_params(lib=None, **kw):
@@ -526,6 +569,21 @@ class Context:
         c, l, out = _denoise_arrays(colour_sums, layers)
         self._ck(self.lib.ptmi_denoise_images(self.h, _ptr(c), _ptr(l), c.shape[2], c.shape[1], c.shape[0], float(frame_num), None if params is None else ctypes.byref(params), _ptr(out)))
         return out
+
+    def denoise_views_guided(self, frame_num, first_view=0, n_views=None, params=None):
+        """ptmi_denoise_views_guided: denoise_views with the variance-guided filter — reads the same images of the moment stack too (set_view_moments) and writes the
+        same denoised stack.  params: GuidedParams (default_guided_params).  n_views=None: up to the end of the stack.  Asynchronous."""
+        if n_views is None:
+            n_views = self.views_device_ptr()[2] - first_view
+        self._ck(self.lib.ptmi_denoise_views_guided(self.h, None if params is None else ctypes.byref(params), float(frame_num), first_view, n_views))
+
+    def denoise_images_guided(self, colour_sums, moments, layers, frame_num, params=None, want_var=False):
+        """ptmi_denoise_images_guided: the kernels of denoise_views_guided on host arrays of any size (see denoise_guided_reference for the shapes and the result);
+        synchronous."""
+        c, m, l, out, var = _guided_arrays(colour_sums, moments, layers, want_var)
+        self._ck(self.lib.ptmi_denoise_images_guided(self.h, _ptr(c), _ptr(m), _ptr(l), c.shape[2], c.shape[1], c.shape[0], float(frame_num),
+                                                     None if params is None else ctypes.byref(params), _ptr(out), None if var is None else _ptr(var)))
+        return (out, var) if want_var else out
 
     def fuse_views(self, views, frame_num=1.0, source=0, first_view=0, n_views=None, params=None):
         """ptmi_fuse_views: fuses output views [first_view, first_view + n_views) across their neighbours in the stack by reprojection into the context's fused
