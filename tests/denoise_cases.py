@@ -6,8 +6,8 @@ include/ptmi_denoise.h's operation order.  dtype=float64 is the reference; dtype
 
 THE TOLERANCE.  The library evaluates the definition in f32 in an order of its own (reciprocals for the sigmas, ptm_exp2), the twin in another; both are f32
 evaluations of the same real-valued function, so what one of them loses against the f64 reading measures what the number format loses on these inputs.  TOL is
-8 x the largest deviation the twin shows over every case below (sizes x levels x sigma_colour), following tests/ref64_cases.py.  `deviation` is the largest
-|x - ref| over the finite values of an image, relative to the larger of |ref| and the image's mean |ref| (so that a dark component is not held to a tighter
+8 x the largest deviation the twin shows over every case below (sizes x levels x sigma_colour, and the edge sizes at the default sigma_colour), following
+tests/ref64_cases.py.  `deviation` is the largest |x - ref| over the finite values of an image, relative to the larger of |ref| and the image's mean |ref| (so that a dark component is not held to a tighter
 absolute error than the filter's sums carry); non-finite values must agree in kind (NaN with NaN, inf with the same inf).  Skips cannot flip between the
 readings: they are decided by exact comparisons (validity of an input pixel, m(q) != m(p)), and the inputs keep every e of a valid pair finite in both formats.
 
@@ -15,12 +15,17 @@ MEASURED is what `python tests/denoise_cases.py` prints; test_denoise_cpu.py che
 import numpy as np
 
 SIZES = ((7, 5), (100, 37), (200, 70))  # smaller than every footprint; no multiple of any tile; several tiles in both axes at halo 32
+# Edge shapes of the tiled kernels (tests/test_stack_geometry_*.py; never part of SIZES' parametrisation): one pixel, one column, one row, a narrow image of three
+# chunks at step 8, exactly a tile wide and a chunk of steps 16 and 32 high, one past both, and a third chunk that is partly outside the image.
+EDGE_SIZES = ((1, 1), (1, 130), (130, 1), (3, 300), (64, 128), (65, 129), (70, 261))
+EDGE_LEVELS = (5, 6)
 LEVELS = (1, 2, 5, 6)
 SIGMA_COLOURS = (0.0, 2.0)
 FRAMES = 4.0
 DEFAULTS = dict(levels=5, sigma_normal=0.25, sigma_depth=0.1, sigma_colour=0.0, albedo_floor=1e-3)
 
-# Largest deviation of the f32 twin from the f64 reading over SIZES x LEVELS x SIGMA_COLOURS (the case that gives it: 200 x 70, 6 levels, sigma_colour 2).
+# Largest deviation of the f32 twin from the f64 reading over SIZES x LEVELS x SIGMA_COLOURS and EDGE_SIZES x EDGE_LEVELS at the default sigma_colour (the case that
+# gives it: 200 x 70, 6 levels, sigma_colour 2).
 MEASURED = dict(date="2026-10-18", deviation=1.6986493076935567e-06)
 TOL = 8 * MEASURED["deviation"]
 
@@ -203,9 +208,16 @@ def cases():
                 yield dict(id="%dx%d-L%d-sc%g" % (w, h, levels, sc), w=w, h=h, S=S, L=L, params=dict(levels=levels, sigma_colour=sc))
 
 
+def edge_cases():
+    for (w, h) in EDGE_SIZES:
+        S, L = synthetic(w, h)
+        for levels in EDGE_LEVELS:
+            yield dict(id="%dx%d-L%d-sc0" % (w, h, levels), w=w, h=h, S=S, L=L, params=dict(levels=levels, sigma_colour=0.0))
+
+
 def measure():
     worst = (0.0, None)
-    for c in cases():
+    for c in list(cases()) + list(edge_cases()):
         ref, _ = reading(c["S"], c["L"], FRAMES, c["params"], np.float64)
         twin, _ = reading(c["S"], c["L"], FRAMES, c["params"], np.float32)
         dev = deviation(twin, ref)

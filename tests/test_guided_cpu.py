@@ -96,7 +96,7 @@ def test_addon_wrapper_and_mock_list_the_guided_call(pkg):
 # ------------------------------------------------------------------------------------------------------------------- against the float64 reading
 def test_the_twin_stays_within_what_was_measured():
     """MEASURED, which the tolerance is 8 x, is still what the f32 twin shows on the case that gave it (`python tests/guided_cases.py` measures them all)."""
-    case = [c for c in gc.cases() if c["id"] == gc.MEASURED["case"]][0]
+    case = gc.case(gc.MEASURED["case"])  # (of SIZES or of EDGE_SIZES)
     dev = gc.twin_deviation(case)
     print("twin deviation %.6e, MEASURED %.6e" % (dev, gc.MEASURED["deviation"]))
     assert 0 < dev <= gc.MEASURED["deviation"] * (1 + 1e-9)

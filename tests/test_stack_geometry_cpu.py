@@ -1,0 +1,160 @@
+"""The launch limits of the image-stack kernels without a GPU: tests/stack_geometry.py reads them from the sources and its shapes cross them by as little as they
+can; the edge shapes of the three tiled filters reach the row regimes they are there for; and on those shapes the CPU references — the host loops through the headers
+the kernels compile — are held to the float64 readings of their case modules under the modules' own tolerances."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import denoise_cases as dc
+import fuse_cases as fc
+import guided_cases as gc
+import stack_geometry as sg
+from conftest import ROOT
+
+CUS = (256, 304, 64, 1)  # the MI355X, and other devices the formulas must hold on
+
+
+# ------------------------------------------------------------------------------------------------------------------- the limits
+def test_the_constants_are_the_ones_the_limits_were_written_for():
+    """If one of these moves, the shapes below move with it (they are computed); this records what the issue's table was read from."""
+    K = sg.constants()
+    assert K == dict(block=256, denoise_tx=64, guided_ty=16, noise_chunks=64, multi_tile=4032, ty_from_step=32, ty_wide=4, ty=8, scratch_cap=1 << 30, denoise_bytes=48, guided_bytes=60,
+                     prepare_blocks=32, aov_waves=32, fold_blocks=16, gather_blocks=8, add_blocks=8), K
+    assert [sg.chunk_rows(K, 1 << l) for l in range(6)] == [8, 16, 32, 64, 128, 128]
+    assert [sg.limit(K, 256, k) for k in ("prepare", "aov", "moments", "noise", "gather", "add")] == [2097152, 524288, 1048576, 16384, 524288, 524288]
+
+
+@pytest.mark.parametrize("cus", CUS)
+def test_each_shape_crosses_its_limit_by_less_than_a_row(cus):
+    K = sg.constants()
+    w, h = sg.prepare_shape(K, cus, 3)
+    assert sg.crosses(3 * w * h, K, cus, "prepare") and not sg.crosses(3 * w * (h - 1), K, cus, "prepare")
+    w, h = sg.aov_shape(K, cus, 5)
+    assert sg.crosses(5 * w * h, K, cus, "aov") and not sg.crosses(5 * w * (h - 1), K, cus, "aov")
+    w, h = sg.moments_shape(K, cus)
+    assert sg.crosses(w * h, K, cus, "moments") and not sg.crosses(w * (h - 1), K, cus, "moments")
+    w, h = sg.noise_shape(K)
+    assert sg.crosses(w * h, K, cus, "noise") and not sg.crosses(w * (h - 1), K, cus, "noise")
+    w, h = sg.readback_shape(K, cus, 2)
+    own = [sg.owned_pixels(w * h, r, 2, K["multi_tile"]) for r in range(2)]
+    assert sum(own) == w * h and all(sg.crosses(o, K, cus, "gather") for o in own) and sg.crosses(w * h, K, cus, "add")
+    assert not all(sg.crosses(sg.owned_pixels(w * (h - 1), r, 2, K["multi_tile"]), K, cus, "gather") for r in range(2))
+
+
+def test_the_shapes_on_256_compute_units():
+    K = sg.constants()
+    assert sg.prepare_shape(K, 256, 3) == (1000, 700) and sg.aov_shape(K, 256, 5) == (384, 274) and sg.moments_shape(K, 256) == (1216, 863)
+    assert sg.noise_shape(K) == (130, 127) and sg.readback_shape(K, 256, 2) == (1216, 866)
+    assert sg.crosses(sg.owned_pixels(256 * 160, 1, 2, 64), K, 256, "noise") and sg.owned_pixels(256 * 160, 1, 2, 64) == 20480
+
+
+def test_owned_pixels_is_the_shard_mapping():
+    for npix in (1, 63, 64, 65, 100 * 37, 256 * 160, 130 * 127):
+        for world, tile in ((1, 64), (2, 64), (3, 64), (2, 16), (2, 4032)):
+            for rank in range(world):
+                assert sg.owned_pixels(npix, rank, world, tile) == int(((np.arange(npix) // tile) % world == rank).sum()), (npix, rank, world, tile)
+
+
+def test_batches():
+    K = sg.constants()
+    w, h = 100, 37
+    for guided in (False, True):
+        assert sg.batch_views(K, w, h, 64, guided) == 64 and sg.batch_views(K, 1920, 1080, 64, guided) == (8 if guided else 10)  # (ptmi.hip's comments)
+        for B, n in ((1, 3), (2, 5), (2, 3)):
+            cap = sg.cap_for_batch(K, w, h, B, guided)
+            assert sg.batch_views(K, w, h, n, guided, cap) == B < n and sg.batch_views(K, w, h, n, guided, cap - 1) == max(1, B - 1)
+        assert sg.batch_views(K, w, h, 3, guided, 0) == 1, "a cap below one view still filters one view at a time"
+
+
+def test_the_hook_is_in_the_test_build_only():
+    src = open(os.path.join(ROOT, "webgpu-path-tracer_amd", "csrc", "ptmi.hip")).read()
+    body = re.search(r"static inline size_t denoise_scratch_cap\(\) \{(.*?)\n\}", src, re.S).group(1)
+    assert re.fullmatch(r'\s*#ifdef PTMI_TEST_HOOKS\s*if \(const char\* cap = getenv\("PTMI_TEST_DENOISE_SCRATCH"\)\) return \(size_t\)strtoull\(cap, nullptr, 10\);\s*#endif\s*'
+                        r"return \(size_t\)1 << 30;", body), body
+    assert src.count("PTMI_TEST_DENOISE_SCRATCH") == 2 and src.count("denoise_scratch_cap()") == 3  # the comment and the getenv; the definition and the two batch functions
+    for doc, name in (("DESIGN.md", ROOT), ("_build.py", os.path.join(ROOT, "webgpu-path-tracer_amd"))):
+        assert "PTMI_TEST_DENOISE_SCRATCH" in open(os.path.join(name, doc)).read(), doc
+
+
+# ------------------------------------------------------------------------------------------------------------------- the edge shapes
+def test_the_edge_shapes_reach_every_row_regime():
+    K = sg.constants()
+    assert dc.EDGE_SIZES == gc.EDGE_SIZES == ((1, 1), (1, 130), (130, 1), (3, 300), (64, 128), (65, 129), (70, 261))
+    assert not set(dc.EDGE_SIZES) & set(dc.SIZES) and len(list(dc.cases())) == 24 and len(list(gc.cases())) == 24, "SIZES' parametrisation stays as it is"
+    tallest = max(h for _, h in dc.SIZES + fc.SIZES)
+    assert all("second" not in sg.row_regimes(K, h, 6) - sg.row_regimes(K, h, 4) for _, h in dc.SIZES) and tallest < sg.tallest_chunk(K, 6), "what SIZES never reached"
+    R = {(w, h): sg.row_regimes(K, h, 6) for w, h in dc.EDGE_SIZES}
+    assert R[(1, 1)] == {"short"} and R[(130, 1)] == {"short"}
+    assert sg.chunks(K, 130, 16) == sg.chunks(K, 130, 32) == 2 and "partial" in R[(1, 130)]  # chunk 1 of steps 16 and 32: rows 128 and 129
+    assert sg.chunks(K, 128, 32) == 1 and "exact" in R[(64, 128)] and 64 % K["denoise_tx"] == 0 and 128 % K["guided_ty"] == 0
+    assert sg.chunks(K, 129, 32) == 2 and 65 % K["denoise_tx"] == 1
+    assert sg.chunks(K, 261, 32) == 3 and 261 % sg.chunk_rows(K, 32) == 5 and "partial" in R[(70, 261)]
+    assert sg.chunks(K, 300, 32) == 3 and sg.chunks(K, 300, 8) == 5
+    assert 130 > 2 * K["denoise_tx"] and 130 % K["denoise_tx"], "the one-row image: three tiles, the last one partial"
+
+
+@pytest.mark.parametrize("size", dc.EDGE_SIZES, ids=lambda s: "%dx%d" % s)
+def test_the_synthetic_inputs_on_the_edge_shapes(size):
+    w, h = size
+    S, L = dc.synthetic(w, h)
+    Sg, M, Lg = gc.synthetic(w, h)
+    valid = ~dc.all_invalid_mask(S, L)
+    assert np.array_equal(L, Lg) and np.array_equal(valid, ~dc.all_invalid_mask(Sg, Lg))
+    if (w, h) == (1, 1):
+        assert not valid.any(), "the one pixel is synthetic's corner miss: only the S / F path"
+        return
+    assert valid.any() and (~valid).any()
+    t = gc.temporal_mask(Sg, M, Lg)
+    n = M[t][:, 3:4].astype(np.float64)
+    mu = Sg[t][:, :3].astype(np.float64) / n
+    var = M[t][:, :3].astype(np.float64) / n - mu * mu
+    assert (var >= 2.0 ** -6 * mu * mu).all(), "guided_cases' condition on the temporal pixels"
+    if w * h > 64:
+        assert t.any() and (valid & ~t).any(), "both variance paths"
+        assert len(np.unique(L[2, ..., 2][valid])) >= 2, "a material edge"
+
+
+@pytest.mark.parametrize("case", list(dc.edge_cases()), ids=lambda c: c["id"])
+def test_denoise_reference_against_the_float64_reading(pkg, case):
+    got = pkg.ptmi.denoise_reference(case["S"], case["L"], dc.FRAMES, pkg.ptmi.default_denoise_params(**case["params"]))
+    ref, valid = dc.reading(case["S"], case["L"], dc.FRAMES, case["params"], np.float64)
+    twin, _ = dc.reading(case["S"], case["L"], dc.FRAMES, case["params"], np.float32)
+    dev, tdev = dc.deviation(got[0], ref), dc.deviation(twin, ref)
+    print("%s: deviation %.3e, the twin's %.3e (MEASURED %.3e), of %.3e allowed" % (case["id"], dev, tdev, dc.MEASURED["deviation"], dc.TOL))
+    assert tdev <= dc.MEASURED["deviation"] * (1 + 1e-9), "the twin leaves what TOL is 8 x of"
+    assert dev <= dc.TOL, (case["id"], dev, dc.TOL)
+    assert np.array_equal(valid, ~dc.all_invalid_mask(case["S"], case["L"]))
+
+
+@pytest.mark.parametrize("case", list(gc.edge_cases()), ids=lambda c: c["id"])
+def test_guided_reference_against_the_float64_reading(pkg, case):
+    got, var = pkg.ptmi.denoise_guided_reference(case["S"], case["M"], case["L"], gc.FRAMES, pkg.ptmi.default_guided_params(**case["params"]), want_var=True)
+    ref, vref, _ = gc.reading(case["S"], case["M"], case["L"], gc.FRAMES, case["params"], np.float64)
+    dev, vdev, tdev = gc.deviation(got[0], ref), gc.deviation(var[0], vref), gc.twin_deviation(case)
+    print("%s: deviation %.3e (colour) %.3e (variance), the twin's %.3e (MEASURED %.3e), of %.3e allowed" % (case["id"], dev, vdev, tdev, gc.MEASURED["deviation"], gc.TOL))
+    assert tdev <= gc.MEASURED["deviation"] * (1 + 1e-9), "the twin leaves what TOL is 8 x of"
+    assert dev <= gc.TOL and vdev <= gc.TOL, (case["id"], dev, vdev, gc.TOL)
+
+
+def test_the_twins_stay_within_measured_over_both_lists():
+    """test_guided_cpu.py and test_denoise_cpu.py check the case that gave MEASURED; the edge cases are held above; here: MEASURED's case is one of the lists'."""
+    assert gc.case(gc.MEASURED["case"])["id"] == gc.MEASURED["case"] and gc.TOL == 8 * gc.MEASURED["deviation"] and dc.TOL == 8 * dc.MEASURED["deviation"]
+    assert {c["id"] for c in gc.edge_cases()}.isdisjoint(c["id"] for c in gc.cases())
+
+
+@pytest.mark.parametrize("size", dc.EDGE_SIZES, ids=lambda s: "%dx%d" % s)
+def test_fuse_reference_against_the_float64_reading(pkg, size):
+    w, h = size
+    S, L, views = fc.inputs(w, h, 3)
+    got = pkg.ptmi.fuse_reference(S, L, views, fc.FRAMES, fc.FOV, fc.LAMBERTIAN)
+    ref, fus, aux = fc.reading(S, L, views, fc.FRAMES, fc.FOV, fc.LAMBERTIAN, None, np.float64)
+    dec = fc.decided(fus, aux, fc.EPS)
+    mask = fc.compare_mask(fus, dec)
+    dev = fc.deviation(got[mask], ref[mask])
+    print("%dx%d: %d fusable pixels, %d decided, deviation %.3e of %.3e allowed" % (w, h, fus.sum(), dec.sum(), dev, fc.TOL))
+    assert dev <= fc.TOL, (size, dev, fc.TOL)
+    assert got.shape == (3, h, w, 4) and mask.any()
+    if w * h > 64:
+        assert dec.any() and not np.array_equal(got[mask][..., :3], (S[mask] / np.float32(fc.FRAMES))[..., :3]), "nothing was fused: the comparison would show nothing"

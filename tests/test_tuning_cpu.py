@@ -49,6 +49,7 @@ NOT_TUNING = {
     "PTMI_LIB": "the bindings: a path",
     "PTMI_TEST_ALLOC_LIMIT": "the test-hooks build only",
     "PTMI_TEST_RCCL_FAIL": "the test-hooks build only",
+    "PTMI_TEST_DENOISE_SCRATCH": "the test-hooks build only: the cap of the denoisers' scratch in bytes (tests/test_stack_geometry_gpu.py)",
     "PTMI_BENCH_SIMULATE": "bench.py only",
 }
 FIELDS = [k[1] for k in INT_KNOBS + BOOL_KNOBS + FLAG_KNOBS]

@@ -73,7 +73,8 @@ def build_lib(force=False, extra_flags=()):
 
 def build_testhooks(force=False):
     """The tests' own build of the library: -DPTMI_TEST_HOOKS compiles in the fault injection the product build does not carry
-    (PTMI_TEST_ALLOC_LIMIT: device allocations above N bytes fail; PTMI_TEST_RCCL_FAIL=init|reduce|mid: that RCCL call reports an error).
+    (PTMI_TEST_ALLOC_LIMIT: device allocations above N bytes fail; PTMI_TEST_RCCL_FAIL=init|reduce|mid: that RCCL call reports an error) and
+    PTMI_TEST_DENOISE_SCRATCH=<bytes>, which takes the place of the 1 GiB cap of the denoisers' scratch, so that a small stack goes through several view batches.
     Only ptmi.hip differs; the tests load it next to the product library (ptmi.load_library(path=...))."""
     if not force and _newer(TESTHOOKS_LIB, _deps()):
         return TESTHOOKS_LIB

@@ -2158,8 +2158,16 @@ int ptmi_camera_rays(ptmi_ctx* c, const float* view16, uint32_t frame, float* ra
 // (ptmi_default_denoise_params and ptmi_denoise_reference need no GPU: ptmi_host.cpp)
 // Views per batch of the filter: its scratch is three float4 images per view, held to 1 GiB (10 views at 1080p) so that a call on a large stack does not need
 // another full copy of it; the views of a batch go through every level in one launch.
+// The cap itself: a constant in the product build, so that it folds into the divisions below; a -DPTMI_TEST_HOOKS build reads PTMI_TEST_DENOISE_SCRATCH=<bytes> at
+// every call, as ptmi_dbuf.h reads PTMI_TEST_ALLOC_LIMIT, so that a test can have several batches on a small stack.
+static inline size_t denoise_scratch_cap() {
+#ifdef PTMI_TEST_HOOKS
+  if (const char* cap = getenv("PTMI_TEST_DENOISE_SCRATCH")) return (size_t)strtoull(cap, nullptr, 10);
+#endif
+  return (size_t)1 << 30;
+}
 static uint32_t denoise_batch_views(size_t npix, uint32_t n) {
-  return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / (npix * 48)));
+  return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, denoise_scratch_cap() / (npix * 48)));
 }
 static size_t denoise_scratch_bytes(size_t npix, uint32_t n) { return (size_t)denoise_batch_views(npix, n) * npix * 48; }
 
@@ -2283,7 +2291,7 @@ int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* laye
 // (ptmi_default_guided_params and ptmi_denoise_guided_reference need no GPU: ptmi_host.cpp)
 // Views per batch: the plain filter's three float4 images and three f32 images (v ping, v pong, vg) per view, 60 bytes per pixel, held to the same 1 GiB (8 views at
 // 1080p), in the same scratch buffer.
-static uint32_t guided_batch_views(size_t npix, uint32_t n) { return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / (npix * 60))); }
+static uint32_t guided_batch_views(size_t npix, uint32_t n) { return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, denoise_scratch_cap() / (npix * 60))); }
 static size_t guided_scratch_bytes(size_t npix, uint32_t n) { return (size_t)guided_batch_views(npix, n) * npix * 60; }
 
 // The filter on device arrays: colour, moments [n][H][W] float4 sums, layers [n][3][H][W] float4, out [n][H][W] float4, var_out [n][H][W] f32 or nullptr.
