@@ -5,7 +5,7 @@ crosses the limit before it trusts a result: a cap that someone raises fails the
 
 The limits (ptmi.hip; `cus` = the device's CU count, full_frames.compute_units()):
   rows          k_denoise_level / k_guided_level: blockIdx.y covers chunks of step x ty rows (ty = 4 from step 32 on, else 8): 128 rows at steps 16 and 32
-  batch         denoise_enqueue / guided_enqueue: B views per batch, scratch cap / (pixels x 48 or 60 bytes); a -DPTMI_TEST_HOOKS build takes the cap from
+  batch         atrous_enqueue (both filters): B views per batch, scratch cap / (pixels x 48 or 60 bytes); a -DPTMI_TEST_HOOKS build takes the cap from
                 PTMI_TEST_DENOISE_SCRATCH
   prepare       k_denoise_prepare: at most cus x 32 blocks of kBlock lanes over views x pixels
   aov           k_aov: at most cus x 32 waves of 64 lanes over views x owned pixels
@@ -35,12 +35,17 @@ def constants():
     """Every number the limits are made of, as the compiler reads it."""
     src = _source()
     ty = re.findall(r"const int step = 1 << l, ty = step >= (\d+) \? (\d+) : (\d+);", src)
-    assert len(ty) == 2 and len(set(ty)) == 1, ty  # denoise_enqueue and guided_enqueue
+    assert len(ty) == 1, ty  # atrous_enqueue: the one launch plan of both filters
     cap = re.search(r"denoise_scratch_cap\(\) \{.*?return \(size_t\)(\d+) << (\d+);\s*\}", src, re.S)
     assert cap, "denoise_scratch_cap: no constant"
-    bpp = [int(re.search(r"static uint32_t %s_batch_views\(size_t npix, uint32_t n\) \{.*?denoise_scratch_cap\(\) / \(npix \* (\d+)\)" % f, src, re.S).group(1)) for f in ("denoise", "guided")]
-    for f, b in zip(("denoise", "guided"), bpp):
-        assert re.search(r"static size_t %s_scratch_bytes\(size_t npix, uint32_t n\) \{ return \(size_t\)%s_batch_views\(npix, n\) \* npix \* %d; \}" % (f, f, b), src), f
+    bpp = []
+    for name in ("kDenoiseScratchBytes", "kGuidedScratchBytes"):  # each defined once, and used by name wherever a batch is sized
+        assert len(re.findall(r"\b%s\s*=" % name, src)) == 1, name
+        bpp.append(_constant("ptmi.hip", name))
+    assert len(re.findall(r"denoise_scratch_cap\(\) /", src)) == 1 and re.search(
+        r"static uint32_t atrous_batch_views\(size_t npix, uint32_t n, size_t bytes_per_pixel\) \{\s*return \(uint32_t\)std::max<size_t>\(1, std::min<size_t>\(n, denoise_scratch_cap\(\) / \(npix \* bytes_per_pixel\)\)\);\s*\}", src), "the batch formula"
+    assert re.search(r"static size_t atrous_scratch_bytes\(size_t npix, uint32_t n, size_t bytes_per_pixel\) \{ return \(size_t\)atrous_batch_views\(npix, n, bytes_per_pixel\) \* npix \* bytes_per_pixel; \}", src), "the scratch size"
+    assert not re.search(r"npix \* (48|60)\b", src), "a batch sized by a literal"
     return dict(
         block=_constant("ptmi_kernels.h", "kBlock"),
         denoise_tx=_constant("ptmi_denoise_kernels.h", "kDenoiseTX"),
@@ -50,7 +55,7 @@ def constants():
         ty_from_step=int(ty[0][0]), ty_wide=int(ty[0][1]), ty=int(ty[0][2]),
         scratch_cap=int(cap.group(1)) << int(cap.group(2)),
         denoise_bytes=bpp[0], guided_bytes=bpp[1],
-        prepare_blocks=_factor(r"const unsigned pgrid = \(unsigned\)std::min<size_t>\(\(items \+ kBlock - 1\) / kBlock, \(size_t\)c->num_cus \* (\d+)\);", "k_denoise_prepare's grid", 2),
+        prepare_blocks=_factor(r"const unsigned pgrid = \(unsigned\)std::min<size_t>\(\(items \+ kBlock - 1\) / kBlock, \(size_t\)c->num_cus \* (\d+)\);", "k_denoise_prepare's grid"),
         aov_waves=_factor(r"const uint32_t grid = \(uint32_t\)std::max<uint64_t>\(1, std::min<uint64_t>\(waves, \(uint64_t\)c->num_cus \* (\d+)\)\);", "k_aov's grid"),
         fold_blocks=_factor(r"const uint32_t ew_grid = std::max<uint32_t>\(1, std::min<uint32_t>\(\(total \+ kBlock - 1\) / kBlock, \(uint32_t\)c->num_cus \* (\d+)\)\);", "k_accumulate's grid"),
         gather_blocks=_factor(r"std::min<size_t>\(\(\(size_t\)n_local \+ kBlock - 1\) / kBlock, \(size_t\)c->num_cus \* (\d+)\);", "k_gather_tiles' grid"),
@@ -91,7 +96,7 @@ def row_regimes(K, h, levels):
 
 
 def batch_views(K, w, h, n, guided, cap=None):
-    """denoise_batch_views / guided_batch_views"""
+    """atrous_batch_views"""
     return max(1, min(n, (K["scratch_cap"] if cap is None else cap) // (w * h * (K["guided_bytes"] if guided else K["denoise_bytes"]))))
 
 

@@ -150,7 +150,7 @@ struct ptmi_ctx {
   // The image stacks (StackKind, kStackInfo): per kind one allocation of n x images-per-view images of W x H float4.  The denoised and fused stacks have the view stack's
   // size and go with it (drop_stack).
   Stack stacks[N_STACKS];
-  DBuf d_denoise_scratch;  // ptmi_denoise_views: three packed float4 images (d ping, d pong, n + z) per view of a batch (denoise_batch_views); ptmi_denoise_views_guided: and three f32 images (v ping, v pong, vg)
+  DBuf d_denoise_scratch;  // ptmi_denoise_views: three packed float4 images (d ping, d pong, n + z) per view of a batch (atrous_batch_views); ptmi_denoise_views_guided: and three f32 images (v ping, v pong, vg)
   StagedTable view_rows;   // the last ptmi_render_views / ptmi_render_aov call's view table (ViewTab: kViewRow float4 per view)
   StagedTable fuse_tab;    // the last ptmi_fuse_views call's table (kFuseRow float4 per view of the stack, then one byte per material)
   bool view_moments = false;  // ptmi_set_view_moments: ptmi_render_views folds second moments into stacks[STACK_MOMENTS] too
@@ -2154,10 +2154,10 @@ int ptmi_camera_rays(ptmi_ctx* c, const float* view16, uint32_t frame, float* ra
   return PTMI_OK;
 }
 
-// ---- the denoised stack (ptmi_denoise_views, ptmi_denoise_images) ----
-// (ptmi_default_denoise_params and ptmi_denoise_reference need no GPU: ptmi_host.cpp)
-// Views per batch of the filter: its scratch is three float4 images per view, held to 1 GiB (10 views at 1080p) so that a call on a large stack does not need
-// another full copy of it; the views of a batch go through every level in one launch.
+// ---- the denoised stack: the plain filter (ptmi_denoise_views, ptmi_denoise_images) and the variance-guided one (ptmi_denoise_views_guided, ptmi_denoise_images_guided) ----
+// (the default params and ptmi_denoise_reference / ptmi_denoise_guided_reference need no GPU: ptmi_host.cpp)
+// Views per batch of either filter: its scratch is held to 1 GiB (plain: 10 views at 1080p, guided: 8) so that a call on a large stack does not need another full
+// copy of it; the views of a batch go through every level in one launch.  Both filters use the same scratch buffer.
 // The cap itself: a constant in the product build, so that it folds into the divisions below; a -DPTMI_TEST_HOOKS build reads PTMI_TEST_DENOISE_SCRATCH=<bytes> at
 // every call, as ptmi_dbuf.h reads PTMI_TEST_ALLOC_LIMIT, so that a test can have several batches on a small stack.
 static inline size_t denoise_scratch_cap() {
@@ -2166,18 +2166,35 @@ static inline size_t denoise_scratch_cap() {
 #endif
   return (size_t)1 << 30;
 }
-static uint32_t denoise_batch_views(size_t npix, uint32_t n) {
-  return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, denoise_scratch_cap() / (npix * 48)));
+// Scratch bytes per pixel of a view of the batch
+constexpr size_t kDenoiseScratchBytes = 48;  // the plain filter: three packed float4 images (d ping, d pong, n + z)
+constexpr size_t kGuidedScratchBytes = 60;   // the guided filter: those and three f32 images (v ping, v pong, vg)
+static uint32_t atrous_batch_views(size_t npix, uint32_t n, size_t bytes_per_pixel) {
+  return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, denoise_scratch_cap() / (npix * bytes_per_pixel)));
 }
-static size_t denoise_scratch_bytes(size_t npix, uint32_t n) { return (size_t)denoise_batch_views(npix, n) * npix * 48; }
+static size_t atrous_scratch_bytes(size_t npix, uint32_t n, size_t bytes_per_pixel) { return (size_t)atrous_batch_views(npix, n, bytes_per_pixel) * npix * bytes_per_pixel; }
 
-// The filter on device arrays: colour [n][H][W] float4 sums, layers [n][3][H][W] float4, out [n][H][W] float4.  c->d_denoise_scratch holds denoise_scratch_bytes already:
-// nothing here allocates.  Per batch one k_denoise_prepare and one k_denoise_level per level, the last of which writes `out`.
-static int denoise_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, uint32_t n, int W, int H, float F, const ptmi_denoise_params& P) {
+// What the guided filter has beside the plain one's operands: moments [n][H][W] float4 sums, var_out [n][H][W] f32 or nullptr
+struct AtrousGuide {
+  const float4* moments;
+  float* var_out;
+  ptmg_consts kg;
+  int min_frames;
+};
+
+// Either filter on device arrays: colour [n][H][W] float4 sums, layers [n][3][H][W] float4, out [n][H][W] float4; G = nullptr: the plain filter.  c->d_denoise_scratch
+// holds atrous_scratch_bytes already: nothing here allocates.  Per batch one k_denoise_prepare and one level kernel per level, the last of which writes `out`; the
+// guided filter also one k_guided_variance, per level one k_guided_blur (with a luminance term only: the blur feeds nothing else), and its last level writes `var_out`.
+static int atrous_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, uint32_t n, int W, int H, float F, const ptmi_denoise_params& P, const AtrousGuide* G) {
   const size_t npix = (size_t)W * (size_t)H;
-  const uint32_t B = denoise_batch_views(npix, n);
+  const uint32_t B = atrous_batch_views(npix, n, G ? kGuidedScratchBytes : kDenoiseScratchBytes);
   float4* d[2] = {c->d_denoise_scratch.as<float4>(), c->d_denoise_scratch.as<float4>() + (size_t)B * npix};
   float4* g = c->d_denoise_scratch.as<float4>() + 2 * (size_t)B * npix;
+  float *v[2] = {nullptr, nullptr}, *vg = nullptr;  // the guided filter's part of the scratch
+  if (G) {
+    float* f = reinterpret_cast<float*>(c->d_denoise_scratch.as<float4>() + 3 * (size_t)B * npix);
+    v[0] = f, v[1] = f + (size_t)B * npix, vg = f + 2 * (size_t)B * npix;
+  }
   for (uint32_t v0 = 0; v0 < n; v0 += B) {
     const uint32_t nv = std::min(B, n - v0);
     const float4* col = colour + (size_t)v0 * npix;
@@ -2186,30 +2203,63 @@ static int denoise_enqueue(ptmi_ctx* c, const float4* colour, const float4* laye
     const unsigned pgrid = (unsigned)std::min<size_t>((items + kBlock - 1) / kBlock, (size_t)c->num_cus * 32);
     hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, F, P.albedo_floor, d[0], g);
     HIP_TRY(c, hipGetLastError());
+    const dim3 tgrid((unsigned)((W + kDenoiseTX - 1) / kDenoiseTX), (unsigned)((H + kGuidedTY - 1) / kGuidedTY), nv);
+    if (G) {
+      hipLaunchKernelGGL(k_guided_variance, tgrid, dim3(kBlock), 0, c->stream, d[0], col, G->moments + (size_t)v0 * npix, lay, W, H, P.albedo_floor, G->min_frames, v[0]);
+      HIP_TRY(c, hipGetLastError());
+    }
     for (int l = 0; l < P.levels; l++) {
       const int step = 1 << l, ty = step >= 32 ? 4 : 8;
+      const bool last = l == P.levels - 1;
       const ptmd_consts k = ptmd_level_consts(P.sigma_normal, P.sigma_depth, P.sigma_colour, P.albedo_floor, l);
       const dim3 grid((unsigned)((W + kDenoiseTX - 1) / kDenoiseTX), (unsigned)(((H + step * ty - 1) / (step * ty)) * step), nv);
-      const size_t lds = (size_t)2 * (ty + 4) * (kDenoiseTX + 4 * step) * sizeof(float4);  // 48 KB at most (step 16 and 32)
-      if (l == P.levels - 1)
-        hipLaunchKernelGGL(k_denoise_level<true>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, out + (size_t)v0 * npix, col, lay, W, H, step, ty, k, F);
-      else
-        hipLaunchKernelGGL(k_denoise_level<false>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, d[(l + 1) & 1], col, lay, W, H, step, ty, k, F);
+      const size_t lds = (size_t)(ty + 4) * (kDenoiseTX + 4 * step) * (2 * sizeof(float4) + (G ? sizeof(float2) : 0));  // at most (step 16 and 32) 48 KB, guided 60 KB
+      float4* dout = last ? out + (size_t)v0 * npix : d[(l + 1) & 1];
+      if (G) {
+        if (G->kg.luma) {
+          hipLaunchKernelGGL(k_guided_blur, tgrid, dim3(kBlock), 0, c->stream, d[l & 1], v[l & 1], W, H, vg);
+          HIP_TRY(c, hipGetLastError());
+        }
+        float* vout = !last ? v[(l + 1) & 1] : G->var_out ? G->var_out + (size_t)v0 * npix : nullptr;
+        hipLaunchKernelGGL(last ? k_guided_level<true> : k_guided_level<false>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, dout, vout, col, lay, W, H, step, ty, k,
+                           G->kg, F);
+      } else {
+        hipLaunchKernelGGL(last ? k_denoise_level<true> : k_denoise_level<false>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, dout, col, lay, W, H, step, ty, k, F);
+      }
       HIP_TRY(c, hipGetLastError());
     }
   }
   return PTMI_OK;
 }
 
+// What the calls on whole image stacks check first, in this order: a context that deals an image's pixels to several devices or processes cannot run them (`what` such a
+// context keeps on `where` GPUs: the words of the call's refusal); the call's own params (`need`: nullptr, or what they have to be); frame_num where the call uses it.
+static int check_stack_call(ptmi_ctx* c, const char* who, const char* what, const char* where, const char* need, bool need_frames, float frame_num) {
+  if (!c->peers.empty() || c->multi) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a multi-device context keeps " + what + " on " + where + " GPUs");
+  if (c->world > 1) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a sharded context (ptmi_set_shard) keeps " + what + " in " + where + " processes");
+  if (need) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need " + need);
+  if (need_frames && (!(frame_num > 0.0f) || !ptmd_finite(frame_num))) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": frame_num must be finite and > 0");
+  return PTMI_OK;
+}
+
+// The shape of the host arrays of a *_images call
+static int check_image_size(ptmi_ctx* c, const char* who, int w, int h, uint32_t n_images) {
+  if (w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need w, h, n_images >= 1 and w * h < 2^31");
+  return PTMI_OK;
+}
+
+// Views [first_view, first_view + n_views) of a stack of n
+static int check_view_range(ptmi_ctx* c, const char* who, uint32_t first_view, uint32_t n_views, uint32_t n) {
+  if (n_views == 0 || first_view >= n || n_views > n - first_view)
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": views [" + std::to_string(first_view) + ", " + std::to_string((uint64_t)first_view + n_views) + ") of " + std::to_string(n));
+  return PTMI_OK;
+}
+
 static int denoise_check_args(ptmi_ctx* c, const char* who, const ptmi_denoise_params* params, float frame_num, ptmi_denoise_params* P) {
-  if (!c->peers.empty() || c->multi) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a multi-device context keeps a pixel's neighbours on other GPUs");
-  if (c->world > 1) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a sharded context (ptmi_set_shard) keeps a pixel's neighbours in other processes");
   if (params) *P = *params;
   else ptmi_default_denoise_params(P);
-  if (!ptmd_params_ok(P->levels, P->sigma_normal, P->sigma_depth, P->sigma_colour, P->albedo_floor))
-    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need levels in 1..6, sigma_normal, sigma_depth and albedo_floor > 0, sigma_colour >= 0, all finite");
-  if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": frame_num must be finite and > 0");
-  return PTMI_OK;
+  const bool ok = ptmd_params_ok(P->levels, P->sigma_normal, P->sigma_depth, P->sigma_colour, P->albedo_floor);
+  return check_stack_call(c, who, "a pixel's neighbours", "other", ok ? nullptr : "levels in 1..6, sigma_normal, sigma_depth and albedo_floor > 0, sigma_colour >= 0, all finite", true, frame_num);
 }
 
 // What ptmi_denoise_views and ptmi_fuse_views ask of their inputs: a view stack and a feature stack of the same number of views, (the denoised stack too where it is
@@ -2220,9 +2270,23 @@ static int check_source_stacks(ptmi_ctx* c, const char* who, bool need_denoised,
   const uint32_t n = c->stacks[STACK_VIEWS].n, na = c->stacks[STACK_FEATURES].n;
   if (n != na) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the view stack has " + std::to_string(n) + " views, the feature stack " + std::to_string(na));
   if (need_denoised && c->stacks[STACK_DENOISED].n != n) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no denoised stack: call ptmi_denoise_views first");
-  if (n_views == 0 || first_view >= n || n_views > n - first_view)
-    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": views [" + std::to_string(first_view) + ", " + std::to_string((uint64_t)first_view + n_views) + ") of " + std::to_string(n));
-  return PTMI_OK;
+  return check_view_range(c, who, first_view, n_views, n);
+}
+
+// Either filter from the context's stacks into its denoised stack, the arguments checked.  The stack and the scratch, everything that can fail for want of memory, come
+// before anything is enqueued.  G: as atrous_enqueue's, its `moments` filled in here.
+static int atrous_views(ptmi_ctx* c, const ptmi_denoise_params& P, AtrousGuide* G, float frame_num, uint32_t first_view, uint32_t n_views) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  const size_t npix = (size_t)c->W * (size_t)c->H;
+  const uint32_t n_stack = c->stacks[STACK_VIEWS].n;
+  DBuf stack;
+  if (int r = reserve_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
+  HIP_TRY(c, c->d_denoise_scratch.ensure_idle(atrous_scratch_bytes(npix, n_views, G ? kGuidedScratchBytes : kDenoiseScratchBytes), c->stream));
+  if (int r = commit_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
+  if (G) G->moments = c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix;
+  return atrous_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)first_view * npix, c->stacks[STACK_FEATURES].buf.as<float4>() + (size_t)first_view * 3 * npix,
+                        c->stacks[STACK_DENOISED].buf.as<float4>() + (size_t)first_view * npix, n_views, c->W, c->H, frame_num, P, G);
 }
 
 int ptmi_denoise_views(ptmi_ctx* c, const ptmi_denoise_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
@@ -2230,16 +2294,7 @@ int ptmi_denoise_views(ptmi_ctx* c, const ptmi_denoise_params* params, float fra
   ptmi_denoise_params P;
   if (int r = denoise_check_args(c, "ptmi_denoise_views", params, frame_num, &P)) return r;
   if (int r = check_source_stacks(c, "ptmi_denoise_views", false, first_view, n_views)) return r;
-  HIP_TRY(c, hipSetDevice(c->device));
-  (void)hipGetLastError();
-  const size_t npix = (size_t)c->W * (size_t)c->H;
-  const uint32_t n_stack = c->stacks[STACK_VIEWS].n;
-  DBuf stack;
-  if (int r = reserve_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
-  HIP_TRY(c, c->d_denoise_scratch.ensure_idle(denoise_scratch_bytes(npix, n_views), c->stream));
-  if (int r = commit_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
-  return denoise_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)first_view * npix, c->stacks[STACK_FEATURES].buf.as<float4>() + (size_t)first_view * 3 * npix,
-                         c->stacks[STACK_DENOISED].buf.as<float4>() + (size_t)first_view * npix, n_views, c->W, c->H, frame_num, P);
+  return atrous_views(c, P, nullptr, frame_num, first_view, n_views);
 }
 
 int ptmi_read_denoised(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_DENOISED, "ptmi_read_denoised", view, 0, dst, bytes); }
@@ -2281,114 +2336,55 @@ int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* laye
   if (!c || !colour_sums || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images: null argument");
   ptmi_denoise_params P;
   if (int r = denoise_check_args(c, "ptmi_denoise_images", params, frame_num, &P)) return r;
-  if (w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images: need w, h, n_images >= 1 and w * h < 2^31");
+  if (int r = check_image_size(c, "ptmi_denoise_images", w, h, n_images)) return r;
   const size_t npix = (size_t)w * (size_t)h;
-  return on_host_images(c, "ptmi_denoise_images", colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, denoise_scratch_bytes(npix, n_images),
-                        [&](const float4* col, const float4* lay, float4* res) { return denoise_enqueue(c, col, lay, res, n_images, w, h, frame_num, P); });
+  return on_host_images(c, "ptmi_denoise_images", colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kDenoiseScratchBytes),
+                        [&](const float4* col, const float4* lay, float4* res) { return atrous_enqueue(c, col, lay, res, n_images, w, h, frame_num, P, nullptr); });
 }
 
-// ---- the variance-guided filter (ptmi_denoise_views_guided, ptmi_denoise_images_guided) into the denoised stack ----
-// (ptmi_default_guided_params and ptmi_denoise_guided_reference need no GPU: ptmi_host.cpp)
-// Views per batch: the plain filter's three float4 images and three f32 images (v ping, v pong, vg) per view, 60 bytes per pixel, held to the same 1 GiB (8 views at
-// 1080p), in the same scratch buffer.
-static uint32_t guided_batch_views(size_t npix, uint32_t n) { return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, denoise_scratch_cap() / (npix * 60))); }
-static size_t guided_scratch_bytes(size_t npix, uint32_t n) { return (size_t)guided_batch_views(npix, n) * npix * 60; }
-
-// The filter on device arrays: colour, moments [n][H][W] float4 sums, layers [n][3][H][W] float4, out [n][H][W] float4, var_out [n][H][W] f32 or nullptr.
-// c->d_denoise_scratch holds guided_scratch_bytes already: nothing here allocates.  Per batch one k_denoise_prepare, one k_guided_variance and per level one
-// k_guided_blur (with a luminance term only: the blur feeds nothing else) and one k_guided_level, the last of which writes `out` and `var_out`.
-static int guided_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, const float4* layers, float4* out, float* var_out, uint32_t n, int W, int H, float F,
-                          const ptmi_guided_params& P) {
-  const size_t npix = (size_t)W * (size_t)H;
-  const uint32_t B = guided_batch_views(npix, n);
-  float4* d[2] = {c->d_denoise_scratch.as<float4>(), c->d_denoise_scratch.as<float4>() + (size_t)B * npix};
-  float4* g = c->d_denoise_scratch.as<float4>() + 2 * (size_t)B * npix;
-  float* f = reinterpret_cast<float*>(c->d_denoise_scratch.as<float4>() + 3 * (size_t)B * npix);
-  float* v[2] = {f, f + (size_t)B * npix};
-  float* vg = f + 2 * (size_t)B * npix;
-  const ptmg_consts kg = ptmg_make_consts(P.sigma_luma, P.var_eps);
-  for (uint32_t v0 = 0; v0 < n; v0 += B) {
-    const uint32_t nv = std::min(B, n - v0);
-    const float4* col = colour + (size_t)v0 * npix;
-    const float4* mom = moments + (size_t)v0 * npix;
-    const float4* lay = layers + (size_t)v0 * 3 * npix;
-    const size_t items = (size_t)nv * npix;
-    const unsigned pgrid = (unsigned)std::min<size_t>((items + kBlock - 1) / kBlock, (size_t)c->num_cus * 32);
-    hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, F, P.albedo_floor, d[0], g);
-    HIP_TRY(c, hipGetLastError());
-    const dim3 tgrid((unsigned)((W + kDenoiseTX - 1) / kDenoiseTX), (unsigned)((H + kGuidedTY - 1) / kGuidedTY), nv);
-    hipLaunchKernelGGL(k_guided_variance, tgrid, dim3(kBlock), 0, c->stream, d[0], col, mom, lay, W, H, P.albedo_floor, P.min_frames, v[0]);
-    HIP_TRY(c, hipGetLastError());
-    for (int l = 0; l < P.levels; l++) {
-      const int step = 1 << l, ty = step >= 32 ? 4 : 8;
-      const ptmd_consts k = ptmd_level_consts(P.sigma_normal, P.sigma_depth, 0.0f, P.albedo_floor, l);
-      if (kg.luma) {
-        hipLaunchKernelGGL(k_guided_blur, tgrid, dim3(kBlock), 0, c->stream, d[l & 1], v[l & 1], W, H, vg);
-        HIP_TRY(c, hipGetLastError());
-      }
-      const dim3 grid((unsigned)((W + kDenoiseTX - 1) / kDenoiseTX), (unsigned)(((H + step * ty - 1) / (step * ty)) * step), nv);
-      const size_t lds = (size_t)(ty + 4) * (kDenoiseTX + 4 * step) * (2 * sizeof(float4) + sizeof(float2));  // 60 KB at most (step 16 and 32)
-      if (l == P.levels - 1)
-        hipLaunchKernelGGL(k_guided_level<true>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, out + (size_t)v0 * npix, var_out ? var_out + (size_t)v0 * npix : nullptr, col,
-                           lay, W, H, step, ty, k, kg, F);
-      else
-        hipLaunchKernelGGL(k_guided_level<false>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, d[(l + 1) & 1], v[(l + 1) & 1], col, lay, W, H, step, ty, k, kg, F);
-      HIP_TRY(c, hipGetLastError());
-    }
-  }
-  return PTMI_OK;
-}
-
-static int guided_check_args(ptmi_ctx* c, const char* who, const ptmi_guided_params* params, float frame_num, ptmi_guided_params* P) {
-  if (!c->peers.empty() || c->multi) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a multi-device context keeps a pixel's neighbours on other GPUs");
-  if (c->world > 1) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a sharded context (ptmi_set_shard) keeps a pixel's neighbours in other processes");
-  if (params) *P = *params;
-  else ptmi_default_guided_params(P);
-  if (!ptmg_params_ok(P->levels, P->sigma_normal, P->sigma_depth, P->sigma_luma, P->albedo_floor, P->min_frames, P->var_eps))
-    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need levels in 1..6, sigma_normal, sigma_depth and albedo_floor > 0, sigma_luma >= 0, min_frames >= 2, var_eps a normal f32 > 0, all finite");
-  if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": frame_num must be finite and > 0");
-  return PTMI_OK;
+// The guided filter's params as the launch plan takes them: the levels' part, with no colour term (P), and the rest (G, whose arrays the caller fills in)
+static int guided_check_args(ptmi_ctx* c, const char* who, const ptmi_guided_params* params, float frame_num, ptmi_denoise_params* P, AtrousGuide* G) {
+  ptmi_guided_params Q;
+  if (params) Q = *params;
+  else ptmi_default_guided_params(&Q);
+  const bool ok = ptmg_params_ok(Q.levels, Q.sigma_normal, Q.sigma_depth, Q.sigma_luma, Q.albedo_floor, Q.min_frames, Q.var_eps);
+  *P = ptmi_denoise_params{Q.levels, Q.sigma_normal, Q.sigma_depth, 0.0f, Q.albedo_floor, {}};
+  *G = AtrousGuide{nullptr, nullptr, ptmg_make_consts(Q.sigma_luma, Q.var_eps), Q.min_frames};
+  return check_stack_call(c, who, "a pixel's neighbours", "other",
+                          ok ? nullptr : "levels in 1..6, sigma_normal, sigma_depth and albedo_floor > 0, sigma_luma >= 0, min_frames >= 2, var_eps a normal f32 > 0, all finite", true, frame_num);
 }
 
 int ptmi_denoise_views_guided(ptmi_ctx* c, const ptmi_guided_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
   if (!c) return PTMI_ERR_INVALID_ARG;
-  ptmi_guided_params P;
-  if (int r = guided_check_args(c, "ptmi_denoise_views_guided", params, frame_num, &P)) return r;
-  if (int r = check_stack(c, STACK_MOMENTS, "ptmi_denoise_views_guided", 0)) return r;
+  ptmi_denoise_params P;
+  AtrousGuide G;
+  if (int r = guided_check_args(c, "ptmi_denoise_views_guided", params, frame_num, &P, &G)) return r;
+  if (int r = check_stack(c, STACK_MOMENTS, "ptmi_denoise_views_guided", 0)) return r;  // (the moment stack first, then what ptmi_denoise_views asks: the order decides which error a caller sees)
   if (int r = check_stack(c, STACK_VIEWS, "ptmi_denoise_views_guided", 0)) return r;
   if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
     return fail(c, PTMI_ERR_STATE, "ptmi_denoise_views_guided: the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
   if (int r = check_source_stacks(c, "ptmi_denoise_views_guided", false, first_view, n_views)) return r;
-  HIP_TRY(c, hipSetDevice(c->device));
-  (void)hipGetLastError();
-  const size_t npix = (size_t)c->W * (size_t)c->H;
-  const uint32_t n_stack = c->stacks[STACK_VIEWS].n;
-  DBuf stack;
-  if (int r = reserve_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
-  HIP_TRY(c, c->d_denoise_scratch.ensure_idle(guided_scratch_bytes(npix, n_views), c->stream));
-  if (int r = commit_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
-  return guided_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)first_view * npix, c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix,
-                        c->stacks[STACK_FEATURES].buf.as<float4>() + (size_t)first_view * 3 * npix, c->stacks[STACK_DENOISED].buf.as<float4>() + (size_t)first_view * npix, nullptr, n_views,
-                        c->W, c->H, frame_num, P);
+  return atrous_views(c, P, &G, frame_num, first_view, n_views);
 }
 
 int ptmi_denoise_images_guided(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
                                const ptmi_guided_params* params, float* out, float* var_out) {
   if (!c || !colour_sums || !moments || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images_guided: null argument");
-  ptmi_guided_params P;
-  if (int r = guided_check_args(c, "ptmi_denoise_images_guided", params, frame_num, &P)) return r;
-  if (w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull)
-    return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images_guided: need w, h, n_images >= 1 and w * h < 2^31");
+  ptmi_denoise_params P;
+  AtrousGuide G;
+  if (int r = guided_check_args(c, "ptmi_denoise_images_guided", params, frame_num, &P, &G)) return r;
+  if (int r = check_image_size(c, "ptmi_denoise_images_guided", w, h, n_images)) return r;
   const size_t npix = (size_t)w * (size_t)h, bytes = npix * 16 * n_images, var_bytes = var_out ? npix * 4 * n_images : 0;
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
   DBuf mom, var;  // (on_host_images brings the colour, the layers and the output; these two are this call's own, had before anything is enqueued)
   HIP_TRY(c, mom.ensure(bytes));
   HIP_TRY(c, var.ensure(var_bytes));
-  return on_host_images(c, "ptmi_denoise_images_guided", colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, guided_scratch_bytes(npix, n_images),
+  G.moments = mom.as<float4>(), G.var_out = var.as<float>();
+  return on_host_images(c, "ptmi_denoise_images_guided", colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kGuidedScratchBytes),
                         [&](const float4* col, const float4* lay, float4* res) -> int {
                           HIP_TRY(c, hipMemcpyAsync(mom.p, moments, bytes, hipMemcpyHostToDevice, c->stream));
-                          if (int e = guided_enqueue(c, col, mom.as<float4>(), lay, res, var.as<float>(), n_images, w, h, frame_num, P)) return e;
+                          if (int e = atrous_enqueue(c, col, lay, res, n_images, w, h, frame_num, P, &G)) return e;
                           if (var_out) HIP_TRY(c, hipMemcpyAsync(var_out, var.p, var_bytes, hipMemcpyDeviceToHost, c->stream));
                           return PTMI_OK;
                         });
@@ -2430,14 +2426,10 @@ static int fuse_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers,
 }
 
 static int fuse_check_args(ptmi_ctx* c, const char* who, const ptmi_fuse_params* params, float frame_num, bool need_frames, ptmi_fuse_params* P) {
-  if (!c->peers.empty() || c->multi) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a multi-device context keeps a view's pixels on several GPUs");
-  if (c->world > 1) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a sharded context (ptmi_set_shard) keeps a view's pixels in several processes");
   if (params) *P = *params;
   else ptmi_default_fuse_params(P);
-  if (!ptmf_params_ok(P->radius, P->sigma_normal, P->sigma_depth, P->albedo_floor))
-    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need radius in 1..8, sigma_normal, sigma_depth and albedo_floor > 0, all finite");
-  if (need_frames && (!(frame_num > 0.0f) || !ptmd_finite(frame_num))) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": frame_num must be finite and > 0");
-  return PTMI_OK;
+  const bool ok = ptmf_params_ok(P->radius, P->sigma_normal, P->sigma_depth, P->albedo_floor);
+  return check_stack_call(c, who, "a view's pixels", "several", ok ? nullptr : "radius in 1..8, sigma_normal, sigma_depth and albedo_floor > 0, all finite", need_frames, frame_num);
 }
 
 int ptmi_fuse_views(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, float frame_num, int source, uint32_t first_view, uint32_t n_views) {
@@ -2486,7 +2478,7 @@ int ptmi_fuse_images(ptmi_ctx* c, const float* colour, const float* layers, cons
   if (!c || !colour || !layers || !views16 || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_images: null argument");
   ptmi_fuse_params P;
   if (int r = fuse_check_args(c, "ptmi_fuse_images", params, frame_num, true, &P)) return r;
-  if (w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_images: need w, h, n_images >= 1 and w * h < 2^31");
+  if (int r = check_image_size(c, "ptmi_fuse_images", w, h, n_images)) return r;
   if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_images: fov_degrees must be in (0,180)");
   if (!lambertian) n_materials = 0;
   const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials);
@@ -2560,8 +2552,7 @@ int ptmi_view_noise_stats(ptmi_ctx* c, const ptmi_noise_params* params, uint32_t
   if (int r = check_stack(c, STACK_VIEWS, "ptmi_view_noise_stats", 0)) return r;
   if (int r = check_stack(c, STACK_MOMENTS, "ptmi_view_noise_stats", 0)) return r;
   const uint32_t n = c->stacks[STACK_VIEWS].n;
-  if (n_views == 0 || first_view >= n || n_views > n - first_view)
-    return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_view_noise_stats: views [" + std::to_string(first_view) + ", " + std::to_string((uint64_t)first_view + n_views) + ") of " + std::to_string(n));
+  if (int r = check_view_range(c, "ptmi_view_noise_stats", first_view, n_views, n)) return r;
   const std::vector<ptmi_ctx*> devs = local_devices(c);
   std::vector<unsigned char> host;
   try {
@@ -2601,7 +2592,7 @@ int ptmi_noise_images(ptmi_ctx* c, const float* colour_sums, const float* moment
   if (!c || !colour_sums || !moments || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_noise_images: null argument");
   ptmi_noise_params P;
   if (int r = noise_check_args(c, "ptmi_noise_images", params, &P)) return r;
-  if (w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_noise_images: need w, h, n_images >= 1 and w * h < 2^31");
+  if (int r = check_image_size(c, "ptmi_noise_images", w, h, n_images)) return r;
   const uint32_t npix = (uint32_t)w * (uint32_t)h;
   const size_t rec_bytes = (size_t)n_images * kNoiseRecordBytes;
   std::vector<unsigned char> host;

@@ -1,18 +1,22 @@
-// ptmi_denoise_kernels.h — the kernels of ptmi_denoise_views / ptmi_denoise_images (include/ptmi.h): an edge-avoiding a-trous filter of a stack of colour images
-// under their feature images.  Every f32 operation of a pixel is in include/ptmi_denoise.h, which the host native ptmi_denoise_reference includes too; this file
-// only decides where the operands come from.
+// ptmi_denoise_kernels.h — the kernels that ptmi_denoise_views / ptmi_denoise_images and ptmi_denoise_views_guided / ptmi_denoise_images_guided (include/ptmi.h) share: an
+// edge-avoiding a-trous filter of a stack of colour images under their feature images, plain or variance-guided.  Every f32 operation of a pixel is in
+// include/ptmi_denoise.h and include/ptmi_guided.h, which the host natives ptmi_denoise_reference and ptmi_denoise_guided_reference include too; this file only decides
+// where the operands come from.  (The guided filter's two passes of its own, k_guided_variance and k_guided_blur, are in ptmi_guided_kernels.h.)
 //
 // k_denoise_prepare   one lane per (view, pixel): the sums of the view and feature stacks -> two packed float4, (d0.rgb, m) and (n.xyz, z); m = NaN marks an invalid pixel.
-// k_denoise_level     one level, step s = 2^l.  A 25-tap pixel read straight from memory is 50 float4 loads through the CU's vector-memory path; here a block of 256
-//                     threads stages a tile in LDS once and every tap is a ds_read_b128.  The tile is 64 pixels wide and `ty` rows tall, the rows s APART (the block
-//                     owns rows y0 + rho + r * s, r = 0..ty-1, of the chunk of s * ty rows starting at y0: residue rho of the chunk), so the vertical halo is 2 rows
-//                     on either side whatever s is; the horizontal one is 2 s columns on either side, rows contiguous in x so that a wave's load stays one
-//                     coalesced 1 KB request: (64 + 4 s) x (ty + 4) pixels of 32 B — 48 KB at s = 16 (ty = 8) and at s = 32 (ty = 4), 3 loads per pixel instead of
-//                     25 at s = 16.  A lane reads consecutive float4 of a row, so a ds_read_b128's 16-lane groups each cover one 256 B bank row: no conflicts.
-//                     Positions outside the image are staged as invalid pixels.  LAST: the level writes the output image (remodulated, or S / F where invalid).
+// atrous_level        one level of either filter, step s = 2^l; k_denoise_level<LAST> and k_guided_level<LAST> are its entry points and only forward.  A 25-tap pixel
+//                     read straight from memory is 50 float4 loads through the CU's vector-memory path; here a block of 256 threads stages a tile in LDS once and every
+//                     tap is a ds_read_b128.  The tile is 64 pixels wide and `ty` rows tall, the rows s APART (the block owns rows y0 + rho + r * s, r = 0..ty-1, of
+//                     the chunk of s * ty rows starting at y0: residue rho of the chunk), so the vertical halo is 2 rows on either side whatever s is; the horizontal
+//                     one is 2 s columns on either side, rows contiguous in x so that a wave's load stays one coalesced 1 KB request: (64 + 4 s) x (ty + 4) pixels of
+//                     32 B — 48 KB at s = 16 (ty = 8) and at s = 32 (ty = 4), 3 loads per pixel instead of 25 at s = 16.  A lane reads consecutive float4 of a row,
+//                     so a ds_read_b128's 16-lane groups each cover one 256 B bank row: no conflicts.  Positions outside the image are staged as invalid pixels.
+//                     GUIDED: a third plane of one float2 per tile pixel, v_l and l(d_l), the luminance taken once when the pixel is staged instead of once per tap
+//                     (the same bits): 40 B per tile pixel, 60 KB at s = 16 and at s = 32; vg(p) is one coalesced f32 load per pixel.
+//                     LAST: the level writes the output image (remodulated, or S / F where invalid) and, GUIDED and where asked for, v_levels (NaN where invalid).
 #pragma once
 
-#include "../../include/ptmi_denoise.h"
+#include "../../include/ptmi_guided.h"
 #include "ptmi_kernels.h"
 
 namespace ptmi {
@@ -35,17 +39,22 @@ __global__ __launch_bounds__(kBlock) void k_denoise_prepare(const float4* __rest
   }
 }
 
-// grid: x = tiles of 64 columns, y = chunks x step (chunk = blockIdx.y / step, residue = blockIdx.y % step), z = view of the batch; dynamic LDS 2 * (ty + 4) * (64 + 4 step) * 16 B
-template <bool LAST>
-__global__ __launch_bounds__(kBlock) void k_denoise_level(const float4* __restrict__ din, const float4* __restrict__ g, float4* __restrict__ dout, const float4* __restrict__ colour,
-                                                          const float4* __restrict__ layers, int W, int H, int step, int ty, ptmd_consts k, float F) {
+// One level of a block's tile.  grid: x = tiles of 64 columns, y = chunks x step (chunk = blockIdx.y / step, residue = blockIdx.y % step), z = view of the batch; dynamic LDS
+// (ty + 4) * (64 + 4 step) * 32 B, GUIDED 40 B.  GUIDED: vin, vg, vout: [n][npix] f32 of the batch; LAST: dout and vout (may be nullptr) are the call's output arrays
+// at the batch's first view.  Not GUIDED: vin, vg, vout and kg are not read.
+template <bool GUIDED, bool LAST>
+DEV void atrous_level(const float4* __restrict__ din, const float4* __restrict__ g, const float* __restrict__ vin, const float* __restrict__ vg, float4* __restrict__ dout,
+                      float* __restrict__ vout, const float4* __restrict__ colour, const float4* __restrict__ layers, int W, int H, int step, int ty, const ptmd_consts& k,
+                      const ptmg_consts& kg, float F) {
   extern __shared__ float4 dn_lds[];
   const int cols = kDenoiseTX + 4 * step, rows = ty + 4;
   float4* sd = dn_lds;
   float4* sg = dn_lds + rows * cols;
+  float2* sv = reinterpret_cast<float2*>(dn_lds + 2 * rows * cols);  // GUIDED: (v_l, l(d_l))
   const size_t npix = (size_t)W * (size_t)H, view = blockIdx.z;
   din += view * npix;
   g += view * npix;
+  if (GUIDED) vin += view * npix;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int x0 = (int)blockIdx.x * kDenoiseTX;
   const int chunk = (int)blockIdx.y / step, rho = (int)blockIdx.y - chunk * step;
@@ -56,13 +65,16 @@ __global__ __launch_bounds__(kBlock) void k_denoise_level(const float4* __restri
     for (int cc = lane; cc < cols; cc += 64) {
       const int x = x0 - 2 * step + cc;
       float4 d = make_float4(0.0f, 0.0f, 0.0f, ptmd_nan()), gg = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      float vv = 0.0f;
       if (row_in && x >= 0 && x < W) {
         const size_t q = (size_t)y * (size_t)W + (size_t)x;
         d = din[q];
         gg = g[q];
+        if (GUIDED) vv = vin[q];
       }
       sd[rr * cols + cc] = d;
       sg[rr * cols + cc] = gg;
+      if (GUIDED) sv[rr * cols + cc] = make_float2(vv, ptmg_luma(d.x, d.y, d.z));
     }
   }
   __syncthreads();
@@ -72,29 +84,53 @@ __global__ __launch_bounds__(kBlock) void k_denoise_level(const float4* __restri
     const int y = ybase + r * step;
     if (y >= H) break;
     const int centre = (r + 2) * cols + 2 * step + lane;
+    const size_t p = (size_t)y * (size_t)W + (size_t)x;
     ptmd_f4 d = dn_f4(sd[centre]);
+    const float2 vl = GUIDED ? sv[centre] : make_float2(0.0f, 0.0f);
+    float vp = vl.x;
     if (d.w == d.w) {
       const ptmd_f4 gp = dn_f4(sg[centre]);
       const float zs = ptmd_depth_scale(k.sigma_depth, gp.w);
-      float num[3] = {0.0f, 0.0f, 0.0f}, den = 0.0f;
+      const float il = GUIDED && kg.luma ? ptmg_inv_luma(&kg, vg[view * npix + p]) : 0.0f;
+      float num[3] = {0.0f, 0.0f, 0.0f}, den = 0.0f, vnum = 0.0f;
 #pragma unroll
       for (int j = -2; j <= 2; j++) {
 #pragma unroll
         for (int i = -2; i <= 2; i++) {
           const int q = centre + j * cols + i * step;
-          ptmd_tap(&k, d, gp, zs, dn_f4(sd[q]), dn_f4(sg[q]), ptmd_h(i) * ptmd_h(j), num, &den);
+          if (GUIDED) {
+            const float2 t = sv[q];
+            ptmg_tap(&k, &kg, d, gp, zs, vl.y, il, dn_f4(sd[q]), dn_f4(sg[q]), t.y, t.x, ptmd_h(i) * ptmd_h(j), num, &den, &vnum);
+          } else {
+            ptmd_tap(&k, d, gp, zs, dn_f4(sd[q]), dn_f4(sg[q]), ptmd_h(i) * ptmd_h(j), num, &den);
+          }
         }
       }
       d.x = num[0] / den, d.y = num[1] / den, d.z = num[2] / den;
+      if (GUIDED) vp = vnum / (den * den);
     }
-    const size_t p = (size_t)y * (size_t)W + (size_t)x;
     if (LAST) {
       const float4* L = layers + view * 3 * npix;
       dout[view * npix + p] = dn_float4(ptmd_remodulate(dn_f4(colour[view * npix + p]), dn_f4(L[npix + p]), F, k.floor, d));
+      if (GUIDED && vout) vout[view * npix + p] = d.w == d.w ? vp : ptmd_nan();
     } else {
       dout[view * npix + p] = dn_float4(d);
+      if (GUIDED) vout[view * npix + p] = vp;
     }
   }
+}
+
+template <bool LAST>
+__global__ __launch_bounds__(kBlock) void k_denoise_level(const float4* __restrict__ din, const float4* __restrict__ g, float4* __restrict__ dout, const float4* __restrict__ colour,
+                                                          const float4* __restrict__ layers, int W, int H, int step, int ty, ptmd_consts k, float F) {
+  atrous_level<false, LAST>(din, g, nullptr, nullptr, dout, nullptr, colour, layers, W, H, step, ty, k, ptmg_consts{}, F);
+}
+
+template <bool LAST>
+__global__ __launch_bounds__(kBlock) void k_guided_level(const float4* __restrict__ din, const float4* __restrict__ g, const float* __restrict__ vin, const float* __restrict__ vg,
+                                                         float4* __restrict__ dout, float* __restrict__ vout, const float4* __restrict__ colour, const float4* __restrict__ layers,
+                                                         int W, int H, int step, int ty, ptmd_consts k, ptmg_consts kg, float F) {
+  atrous_level<true, LAST>(din, g, vin, vg, dout, vout, colour, layers, W, H, step, ty, k, kg, F);
 }
 
 }  // namespace ptmi

@@ -654,7 +654,7 @@ extern "C" int ptmi_obj_parse(const char* text, size_t len, float** vertices_out
   return PTMI_OK;
 }
 
-// ---- the denoising filter on the host (ptmi_denoise_reference) ----
+// ---- the denoising filters on the host (ptmi_denoise_reference, ptmi_denoise_guided_reference) ----
 extern "C" void ptmi_default_denoise_params(ptmi_denoise_params* p) {
   if (!p) return;
   memset(p, 0, sizeof(*p));
@@ -665,61 +665,6 @@ extern "C" void ptmi_default_denoise_params(ptmi_denoise_params* p) {
   p->albedo_floor = 1e-3f;
 }
 
-// A plain loop over pixels through include/ptmi_denoise.h, the header the kernels of ptmi_denoise_views compile: prepare, the levels between two packed images,
-// remodulate.  One image after the other; nothing is tiled, threaded or reordered.
-extern "C" int ptmi_denoise_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params,
-                                      float* out) {
-  if (!colour_sums || !layers || !out || w <= 0 || h <= 0 || n_images == 0) return PTMI_ERR_INVALID_ARG;
-  ptmi_denoise_params P;
-  if (params) P = *params;
-  else ptmi_default_denoise_params(&P);
-  if (!ptmd_params_ok(P.levels, P.sigma_normal, P.sigma_depth, P.sigma_colour, P.albedo_floor)) return PTMI_ERR_INVALID_ARG;
-  if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
-  const size_t npix = (size_t)w * (size_t)h;
-  std::vector<ptmd_f4> d[2], g;
-  try {
-    d[0].resize(npix), d[1].resize(npix), g.resize(npix);
-  } catch (const std::bad_alloc&) {
-    return PTMI_ERR_NO_MEMORY;
-  }
-  const ptmd_f4 outside{0.0f, 0.0f, 0.0f, ptmd_nan()};
-  for (uint32_t v = 0; v < n_images; v++) {
-    const ptmd_f4* S = reinterpret_cast<const ptmd_f4*>(colour_sums) + (size_t)v * npix;
-    const ptmd_f4* L = reinterpret_cast<const ptmd_f4*>(layers) + (size_t)v * 3 * npix;
-    ptmd_f4* O = reinterpret_cast<ptmd_f4*>(out) + (size_t)v * npix;
-    for (size_t p = 0; p < npix; p++) ptmd_prepare(S[p], L[p], L[npix + p], L[2 * npix + p], frame_num, P.albedo_floor, &d[0][p], &g[p]);
-    for (int l = 0; l < P.levels; l++) {
-      const int step = 1 << l;
-      const ptmd_consts k = ptmd_level_consts(P.sigma_normal, P.sigma_depth, P.sigma_colour, P.albedo_floor, l);
-      const std::vector<ptmd_f4>& in = d[l & 1];
-      std::vector<ptmd_f4>& to = d[(l + 1) & 1];
-      for (int y = 0; y < h; y++)
-        for (int x = 0; x < w; x++) {
-          const size_t p = (size_t)y * w + x;
-          ptmd_f4 dp = in[p];
-          if (dp.w == dp.w) {
-            const ptmd_f4 gp = g[p];
-            const float zs = ptmd_depth_scale(k.sigma_depth, gp.w);
-            float num[3] = {0.0f, 0.0f, 0.0f}, den = 0.0f;
-            for (int j = -2; j <= 2; j++)
-              for (int i = -2; i <= 2; i++) {
-                const int qx = x + i * step, qy = y + j * step;
-                const bool inside = qx >= 0 && qx < w && qy >= 0 && qy < h;
-                const size_t q = inside ? (size_t)qy * w + qx : p;
-                ptmd_tap(&k, dp, gp, zs, inside ? in[q] : outside, g[q], ptmd_h(i) * ptmd_h(j), num, &den);
-              }
-            dp.x = num[0] / den, dp.y = num[1] / den, dp.z = num[2] / den;
-          }
-          to[p] = dp;
-        }
-    }
-    const std::vector<ptmd_f4>& last = d[P.levels & 1];
-    for (size_t p = 0; p < npix; p++) O[p] = ptmd_remodulate(S[p], L[npix + p], frame_num, P.albedo_floor, last[p]);
-  }
-  return PTMI_OK;
-}
-
-// ---- the variance-guided filter on the host (ptmi_denoise_guided_reference) ----
 extern "C" void ptmi_default_guided_params(ptmi_guided_params* p) {
   if (!p) return;
   memset(p, 0, sizeof(*p));
@@ -732,61 +677,65 @@ extern "C" void ptmi_default_guided_params(ptmi_guided_params* p) {
   p->var_eps = 1e-10f;
 }
 
-// A plain loop over pixels through include/ptmi_guided.h, the header the kernels of ptmi_denoise_views_guided compile: prepare, the initial variance, per level the
-// blur of the variance and the 25 taps, remodulate.  One image after the other; nothing is tiled, threaded or reordered.
-extern "C" int ptmi_denoise_guided_reference(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
-                                             const ptmi_guided_params* params, float* out, float* var_out) {
-  if (!colour_sums || !moments || !layers || !out || w <= 0 || h <= 0 || n_images == 0) return PTMI_ERR_INVALID_ARG;
-  ptmi_guided_params P;
-  if (params) P = *params;
-  else ptmi_default_guided_params(&P);
-  if (!ptmg_params_ok(P.levels, P.sigma_normal, P.sigma_depth, P.sigma_luma, P.albedo_floor, P.min_frames, P.var_eps)) return PTMI_ERR_INVALID_ARG;
-  if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
+// what the guided filter has beside the plain one's operands (var_out may be nullptr)
+struct HostGuide {
+  const float* moments;
+  float* var_out;
+  ptmg_consts kg;
+  int32_t min_frames;
+};
+
+// Both filters: a plain loop over pixels through include/ptmi_denoise.h and include/ptmi_guided.h, the headers the kernels of ptmi_denoise_views and
+// ptmi_denoise_views_guided compile: prepare, (guided: the initial variance,) per level (guided: the blur of the variance and) the 25 taps between two packed images,
+// remodulate.  One image after the other; nothing is tiled, threaded or reordered.  G = nullptr: the plain filter, which has no variance or luminance planes.
+static int atrous_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params& P, const HostGuide* G,
+                            float* out) {
   const size_t npix = (size_t)w * (size_t)h;
   std::vector<ptmd_f4> d[2], g;
   std::vector<float> var[2], vg, lum;
   try {
-    d[0].resize(npix), d[1].resize(npix), g.resize(npix), var[0].resize(npix), var[1].resize(npix), vg.resize(npix), lum.resize(npix);
+    d[0].resize(npix), d[1].resize(npix), g.resize(npix);
+    if (G) var[0].resize(npix), var[1].resize(npix), vg.resize(npix), lum.resize(npix);
   } catch (const std::bad_alloc&) {
     return PTMI_ERR_NO_MEMORY;
   }
   const ptmd_f4 outside{0.0f, 0.0f, 0.0f, ptmd_nan()};
-  const ptmg_consts kg = ptmg_make_consts(P.sigma_luma, P.var_eps);
   for (uint32_t v = 0; v < n_images; v++) {
     const ptmd_f4* S = reinterpret_cast<const ptmd_f4*>(colour_sums) + (size_t)v * npix;
-    const ptmd_f4* M = reinterpret_cast<const ptmd_f4*>(moments) + (size_t)v * npix;
+    const ptmd_f4* M = G ? reinterpret_cast<const ptmd_f4*>(G->moments) + (size_t)v * npix : nullptr;
     const ptmd_f4* L = reinterpret_cast<const ptmd_f4*>(layers) + (size_t)v * 3 * npix;
     ptmd_f4* O = reinterpret_cast<ptmd_f4*>(out) + (size_t)v * npix;
     for (size_t p = 0; p < npix; p++) {
       ptmd_prepare(S[p], L[p], L[npix + p], L[2 * npix + p], frame_num, P.albedo_floor, &d[0][p], &g[p]);
-      lum[p] = ptmg_luma(d[0][p].x, d[0][p].y, d[0][p].z);
+      if (G) lum[p] = ptmg_luma(d[0][p].x, d[0][p].y, d[0][p].z);
     }
-    for (int y = 0; y < h; y++)
-      for (int x = 0; x < w; x++) {
-        const size_t p = (size_t)y * w + x;
-        const float mp = d[0][p].w;
-        float v0 = 0.0f;
-        if (mp == mp && !ptmg_v0_temporal(S[p], M[p], L[npix + p], P.albedo_floor, P.min_frames, &v0)) {
-          float cnt = 0.0f, s1 = 0.0f, s2 = 0.0f;
-          for (int j = -3; j <= 3; j++)
-            for (int i = -3; i <= 3; i++) {
-              const int qx = x + i, qy = y + j;
-              if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
-              const size_t q = (size_t)qy * w + qx;
-              ptmg_v0_add(mp, d[0][q].w, lum[q], &cnt, &s1, &s2);
-            }
-          v0 = ptmg_v0_spatial(cnt, s1, s2);
+    if (G)
+      for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+          const size_t p = (size_t)y * w + x;
+          const float mp = d[0][p].w;
+          float v0 = 0.0f;
+          if (mp == mp && !ptmg_v0_temporal(S[p], M[p], L[npix + p], P.albedo_floor, G->min_frames, &v0)) {
+            float cnt = 0.0f, s1 = 0.0f, s2 = 0.0f;
+            for (int j = -3; j <= 3; j++)
+              for (int i = -3; i <= 3; i++) {
+                const int qx = x + i, qy = y + j;
+                if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+                const size_t q = (size_t)qy * w + qx;
+                ptmg_v0_add(mp, d[0][q].w, lum[q], &cnt, &s1, &s2);
+              }
+            v0 = ptmg_v0_spatial(cnt, s1, s2);
+          }
+          var[0][p] = v0;
         }
-        var[0][p] = v0;
-      }
     for (int l = 0; l < P.levels; l++) {
       const int step = 1 << l;
-      const ptmd_consts k = ptmd_level_consts(P.sigma_normal, P.sigma_depth, 0.0f, P.albedo_floor, l);
+      const ptmd_consts k = ptmd_level_consts(P.sigma_normal, P.sigma_depth, P.sigma_colour, P.albedo_floor, l);
       const std::vector<ptmd_f4>& in = d[l & 1];
       std::vector<ptmd_f4>& to = d[(l + 1) & 1];
       const std::vector<float>& vin = var[l & 1];
       std::vector<float>& vto = var[(l + 1) & 1];
-      if (kg.luma)
+      if (G && G->kg.luma)
         for (int y = 0; y < h; y++)
           for (int x = 0; x < w; x++) {
             const size_t p = (size_t)y * w + x;
@@ -802,40 +751,64 @@ extern "C" int ptmi_denoise_guided_reference(const float* colour_sums, const flo
                 }
             vg[p] = mp == mp ? ptmg_blur(gv, gs) : 0.0f;
           }
-      if (l > 0)
+      if (G && l > 0)
         for (size_t p = 0; p < npix; p++) lum[p] = ptmg_luma(in[p].x, in[p].y, in[p].z);
       for (int y = 0; y < h; y++)
         for (int x = 0; x < w; x++) {
           const size_t p = (size_t)y * w + x;
           ptmd_f4 dp = in[p];
-          float vp = vin[p];
+          float vp = G ? vin[p] : 0.0f;
           if (dp.w == dp.w) {
             const ptmd_f4 gp = g[p];
             const float zs = ptmd_depth_scale(k.sigma_depth, gp.w);
-            const float il = kg.luma ? ptmg_inv_luma(&kg, vg[p]) : 0.0f;
+            const float il = G && G->kg.luma ? ptmg_inv_luma(&G->kg, vg[p]) : 0.0f;
             float num[3] = {0.0f, 0.0f, 0.0f}, den = 0.0f, vnum = 0.0f;
             for (int j = -2; j <= 2; j++)
               for (int i = -2; i <= 2; i++) {
                 const int qx = x + i * step, qy = y + j * step;
                 const bool inside = qx >= 0 && qx < w && qy >= 0 && qy < h;
                 const size_t q = inside ? (size_t)qy * w + qx : p;
-                ptmg_tap(&k, &kg, dp, gp, zs, lum[p], il, inside ? in[q] : outside, g[q], lum[q], vin[q], ptmd_h(i) * ptmd_h(j), num, &den, &vnum);
+                const ptmd_f4 dq = inside ? in[q] : outside;
+                if (G) ptmg_tap(&k, &G->kg, dp, gp, zs, lum[p], il, dq, g[q], lum[q], vin[q], ptmd_h(i) * ptmd_h(j), num, &den, &vnum);
+                else ptmd_tap(&k, dp, gp, zs, dq, g[q], ptmd_h(i) * ptmd_h(j), num, &den);
               }
             dp.x = num[0] / den, dp.y = num[1] / den, dp.z = num[2] / den;
-            vp = vnum / (den * den);
+            if (G) vp = vnum / (den * den);
           }
           to[p] = dp;
-          vto[p] = vp;
+          if (G) vto[p] = vp;
         }
     }
     const std::vector<ptmd_f4>& last = d[P.levels & 1];
-    const std::vector<float>& vlast = var[P.levels & 1];
     for (size_t p = 0; p < npix; p++) {
       O[p] = ptmd_remodulate(S[p], L[npix + p], frame_num, P.albedo_floor, last[p]);
-      if (var_out) var_out[(size_t)v * npix + p] = last[p].w == last[p].w ? vlast[p] : ptmd_nan();
+      if (G && G->var_out) G->var_out[(size_t)v * npix + p] = last[p].w == last[p].w ? var[P.levels & 1][p] : ptmd_nan();
     }
   }
   return PTMI_OK;
+}
+
+extern "C" int ptmi_denoise_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params,
+                                      float* out) {
+  if (!colour_sums || !layers || !out || w <= 0 || h <= 0 || n_images == 0) return PTMI_ERR_INVALID_ARG;
+  ptmi_denoise_params P;
+  if (params) P = *params;
+  else ptmi_default_denoise_params(&P);
+  if (!ptmd_params_ok(P.levels, P.sigma_normal, P.sigma_depth, P.sigma_colour, P.albedo_floor)) return PTMI_ERR_INVALID_ARG;
+  if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
+  return atrous_reference(colour_sums, layers, w, h, n_images, frame_num, P, nullptr, out);
+}
+
+extern "C" int ptmi_denoise_guided_reference(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
+                                             const ptmi_guided_params* params, float* out, float* var_out) {
+  if (!colour_sums || !moments || !layers || !out || w <= 0 || h <= 0 || n_images == 0) return PTMI_ERR_INVALID_ARG;
+  ptmi_guided_params P;
+  if (params) P = *params;
+  else ptmi_default_guided_params(&P);
+  if (!ptmg_params_ok(P.levels, P.sigma_normal, P.sigma_depth, P.sigma_luma, P.albedo_floor, P.min_frames, P.var_eps)) return PTMI_ERR_INVALID_ARG;
+  if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
+  const HostGuide G{moments, var_out, ptmg_make_consts(P.sigma_luma, P.var_eps), P.min_frames};
+  return atrous_reference(colour_sums, layers, w, h, n_images, frame_num, ptmi_denoise_params{P.levels, P.sigma_normal, P.sigma_depth, 0.0f, P.albedo_floor, {}}, &G, out);
 }
 
 // ---- cross-view fusion on the host (ptmi_fuse_reference) ----

@@ -12,6 +12,7 @@
 #define _GNU_SOURCE
 #include <dlfcn.h>
 #include <node_api.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -162,6 +163,38 @@ static int typed(napi_env env, napi_value v, napi_typedarray_type want, const ch
   }
   return 0;
 }
+
+/* One field of a params object: its JS property, int32 or f32, and where it lives in the C struct */
+typedef struct param_field {
+  const char* name;
+  int is_int;
+  size_t offset;
+} param_field;
+#define NFIELDS(t) (sizeof(t) / sizeof((t)[0]))
+
+/* params | null -> *P, which holds the defaults already: every field of the table that the object has.  0 on success, -1 when an N-API call fails (a property that is
+ * no number, a getter that throws); the caller throws. */
+static int read_params(napi_env env, napi_value v, const param_field* fields, size_t n, void* P) {
+  napi_valuetype t;
+  if (napi_typeof(env, v, &t) != napi_ok) return -1;
+  if (t != napi_object) return 0;
+  for (size_t k = 0; k < n; k++) {
+    bool has = false;
+    napi_value f;
+    double d;
+    if (napi_has_named_property(env, v, fields[k].name, &has) != napi_ok) return -1;
+    if (!has) continue;
+    if (napi_get_named_property(env, v, fields[k].name, &f) != napi_ok || napi_get_value_double(env, f, &d) != napi_ok) return -1;
+    if (fields[k].is_int) *(int32_t*)((char*)P + fields[k].offset) = (int32_t)d;
+    else *(float*)((char*)P + fields[k].offset) = (float)d;
+  }
+  return 0;
+}
+#define CHECK_PARAMS(v, fields, P, what)                                \
+  if (read_params(env, v, fields, NFIELDS(fields), P)) {                \
+    napi_throw_error(env, NULL, "N-API call failed: " what "(params)"); \
+    return NULL;                                                        \
+  }
 
 static void finalize_ctx(napi_env env, void* data, void* hint) {
   (void)env;
@@ -551,23 +584,12 @@ static napi_value js_denoise_views(napi_env env, napi_callback_info info) {
   CHECK_NAPI(napi_get_value_uint32(env, a[3], &n_views));
   ptmi_denoise_params P;
   p_ptmi_default_denoise_params(&P);
-  napi_valuetype t;
-  CHECK_NAPI(napi_typeof(env, a[4], &t));
-  if (t == napi_object) {
-    static const char* names[5] = {"levels", "sigmaNormal", "sigmaDepth", "sigmaColour", "albedoFloor"};
-    float* fields[5] = {NULL, &P.sigma_normal, &P.sigma_depth, &P.sigma_colour, &P.albedo_floor};
-    for (int k = 0; k < 5; k++) {
-      bool has = false;
-      napi_value v;
-      CHECK_NAPI(napi_has_named_property(env, a[4], names[k], &has));
-      if (!has) continue;
-      double d;
-      CHECK_NAPI(napi_get_named_property(env, a[4], names[k], &v));
-      CHECK_NAPI(napi_get_value_double(env, v, &d));
-      if (k == 0) P.levels = (int32_t)d;
-      else *fields[k] = (float)d;
-    }
-  }
+  static const param_field fields[] = {{"levels", 1, offsetof(ptmi_denoise_params, levels)},
+                                       {"sigmaNormal", 0, offsetof(ptmi_denoise_params, sigma_normal)},
+                                       {"sigmaDepth", 0, offsetof(ptmi_denoise_params, sigma_depth)},
+                                       {"sigmaColour", 0, offsetof(ptmi_denoise_params, sigma_colour)},
+                                       {"albedoFloor", 0, offsetof(ptmi_denoise_params, albedo_floor)}};
+  CHECK_PARAMS(a[4], fields, &P, "denoiseViews")
   int st = p_ptmi_denoise_views(c, &P, (float)frame_num, first, n_views);
   if (st) return throw_status(env, c, st, "ptmi_denoise_views");
   return NULL;
@@ -587,24 +609,14 @@ static napi_value js_denoise_views_guided(napi_env env, napi_callback_info info)
   CHECK_NAPI(napi_get_value_uint32(env, a[3], &n_views));
   ptmi_guided_params P;
   p_ptmi_default_guided_params(&P);
-  napi_valuetype t;
-  CHECK_NAPI(napi_typeof(env, a[4], &t));
-  if (t == napi_object) {
-    static const char* names[7] = {"levels", "minFrames", "sigmaNormal", "sigmaDepth", "sigmaLuma", "albedoFloor", "varEps"};
-    int32_t* ints[2] = {&P.levels, &P.min_frames};
-    float* fields[7] = {NULL, NULL, &P.sigma_normal, &P.sigma_depth, &P.sigma_luma, &P.albedo_floor, &P.var_eps};
-    for (int k = 0; k < 7; k++) {
-      bool has = false;
-      napi_value v;
-      CHECK_NAPI(napi_has_named_property(env, a[4], names[k], &has));
-      if (!has) continue;
-      double d;
-      CHECK_NAPI(napi_get_named_property(env, a[4], names[k], &v));
-      CHECK_NAPI(napi_get_value_double(env, v, &d));
-      if (k < 2) *ints[k] = (int32_t)d;
-      else *fields[k] = (float)d;
-    }
-  }
+  static const param_field fields[] = {{"levels", 1, offsetof(ptmi_guided_params, levels)},
+                                       {"minFrames", 1, offsetof(ptmi_guided_params, min_frames)},
+                                       {"sigmaNormal", 0, offsetof(ptmi_guided_params, sigma_normal)},
+                                       {"sigmaDepth", 0, offsetof(ptmi_guided_params, sigma_depth)},
+                                       {"sigmaLuma", 0, offsetof(ptmi_guided_params, sigma_luma)},
+                                       {"albedoFloor", 0, offsetof(ptmi_guided_params, albedo_floor)},
+                                       {"varEps", 0, offsetof(ptmi_guided_params, var_eps)}};
+  CHECK_PARAMS(a[4], fields, &P, "denoiseViewsGuided")
   int st = p_ptmi_denoise_views_guided(c, &P, (float)frame_num, first, n_views);
   if (st) return throw_status(env, c, st, "ptmi_denoise_views_guided");
   return NULL;
@@ -637,23 +649,11 @@ static napi_value js_fuse_views(napi_env env, napi_callback_info info) {
   }
   ptmi_fuse_params P;
   p_ptmi_default_fuse_params(&P);
-  napi_valuetype t;
-  CHECK_NAPI(napi_typeof(env, a[6], &t));
-  if (t == napi_object) {
-    static const char* names[4] = {"radius", "sigmaNormal", "sigmaDepth", "albedoFloor"};
-    float* fields[4] = {NULL, &P.sigma_normal, &P.sigma_depth, &P.albedo_floor};
-    for (int k = 0; k < 4; k++) {
-      bool has = false;
-      napi_value v;
-      CHECK_NAPI(napi_has_named_property(env, a[6], names[k], &has));
-      if (!has) continue;
-      double d;
-      CHECK_NAPI(napi_get_named_property(env, a[6], names[k], &v));
-      CHECK_NAPI(napi_get_value_double(env, v, &d));
-      if (k == 0) P.radius = (int32_t)d;
-      else *fields[k] = (float)d;
-    }
-  }
+  static const param_field fields[] = {{"radius", 1, offsetof(ptmi_fuse_params, radius)},
+                                       {"sigmaNormal", 0, offsetof(ptmi_fuse_params, sigma_normal)},
+                                       {"sigmaDepth", 0, offsetof(ptmi_fuse_params, sigma_depth)},
+                                       {"albedoFloor", 0, offsetof(ptmi_fuse_params, albedo_floor)}};
+  CHECK_PARAMS(a[6], fields, &P, "fuseViews")
   int st = p_ptmi_fuse_views(c, &P, (const float*)data, (float)frame_num, source, first, n_views);
   if (st) return throw_status(env, c, st, "ptmi_fuse_views");
   return NULL;
@@ -675,22 +675,9 @@ static napi_value js_set_view_moments(napi_env env, napi_callback_info info) {
 
 /* params | null -> ptmi_noise_params: {floor, threshold}, every field optional (ptmi_default_noise_params fills the rest); 0 on success */
 static int noise_params_of(napi_env env, napi_value v, ptmi_noise_params* P) {
+  static const param_field fields[] = {{"floor", 0, offsetof(ptmi_noise_params, floor)}, {"threshold", 0, offsetof(ptmi_noise_params, threshold)}};
   p_ptmi_default_noise_params(P);
-  napi_valuetype t;
-  if (napi_typeof(env, v, &t) != napi_ok) return -1;
-  if (t != napi_object) return 0;
-  static const char* names[2] = {"floor", "threshold"};
-  float* fields[2] = {&P->floor, &P->threshold};
-  for (int k = 0; k < 2; k++) {
-    bool has = false;
-    napi_value f;
-    double d;
-    if (napi_has_named_property(env, v, names[k], &has) != napi_ok) return -1;
-    if (!has) continue;
-    if (napi_get_named_property(env, v, names[k], &f) != napi_ok || napi_get_value_double(env, f, &d) != napi_ok) return -1;
-    *fields[k] = (float)d;
-  }
-  return 0;
+  return read_params(env, v, fields, NFIELDS(fields), P);
 }
 
 /* n records -> [{counted, sumQ, above, maxQ}, ...]; the 64-bit integers as doubles (exact below 2^53: 2^28 pixels x q < 2^24 stay below 2^52) */
