@@ -396,6 +396,89 @@ int ptmi_release_fused(ptmi_ctx* ctx);
 int ptmi_fuse_images(ptmi_ctx* ctx, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
                      float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out);
 
+/* Temporal accumulation (no counterpart in the reference): the temporal half of SVGF (Schied et al. 2017) for a camera path.  View v of the path reprojects every
+ * diffuse pixel into view v-1, takes over the colour sum, the squared-colour sum and the frame count accumulated there, under the geometry tests of "Fusion" above,
+ * and adds its own frames: one lookup per pixel where fusion has up to sixteen, and a state that carries a sample count and a second moment, so that every view
+ * ends with a mean over up to max_history frames AND the variance of that mean — which ptmi_denoise_views_accumulated hands to the guided filter in place of a
+ * guess from the neighbourhood.  With S, N, A, I, F, f, M_u, o_u, B_u as in "Fusion", M the moment-stack image of the same view (xyz = sums of the frames' squared
+ * colours, w = nn, below: "THE MOMENT STACK") and k, c, n, z, a', d, m and validity exactly as the denoiser's "prepare" makes them:
+ *
+ * THE ACCUMULATED STACK holds three planes, each a full stack: [3][n_views of the view stack][H][W][4] f32 in one device allocation.
+ *   plane 0   rgb = mean radiance, a = S.a / F: what the denoised and the fused stack hold.
+ *   plane 1   xyz = D, the accumulated sum of demodulated frame colours;  w = n, the accumulated frame count (f32; fractional once a weight is below 1).
+ *   plane 2   xyz = Q, the accumulated sum of squared demodulated frame colours;  w = v0, the variance of the demodulated luminance of the pixel's accumulated
+ *             mean, NaN where none can be stated.
+ *
+ *   own       valid p: D0 = d nn, Q0 = (M.xyz / a') / a' per channel, n0 = nn.  Invalid p: D0 = Q0 = 0, n0 = 0.
+ *   history   looked for only when p is valid and FUSABLE (LAMBERTIAN, as in "Fusion") and v is not the first view of the recursion.  X = the world point of p in
+ *             view v and q = its projection into view v-1, at distance r from o_{v-1}: steps 1 and 2 of "Fusion" with u = v-1.  Nothing is taken over unless q lies
+ *             inside the image, q is valid in view v-1 (S, N, A, I of v-1 at q), m(q) == m(p),
+ *               e = |n(q) - n(p)|^2 / sigma_normal^2 + ((z(q) - r) / (sigma_depth (r + 1e-6)))^2 is finite,
+ *             and plane 1 of view v-1 at q has w = n_prev > 0 with D_prev, Q_prev and n_prev all finite.  Then wgt = exp2(-e) (ptm_exp2), hc = min(n_prev, max_history),
+ *             t = wgt hc, sc = t / n_prev:  D = D0 + sc D_prev, Q = Q0 + sc Q_prev, n = n0 + t.  Otherwise D = D0, Q = Q0, n = n0.
+ *   mean      valid and fusable p: rgb = (D / n) a'.  Every other p passes through: rgb = S.rgb / F, bit for bit fusion's pass-through.  alpha = S.a / F everywhere.
+ *   variance  valid p with n >= min_frames and D, Q finite: per channel var = max(Q / n - (D / n)^2, 0), s = sqrt(var);  sigma = l(s);  v0 = sigma^2 / (n - 1) — the
+ *             perfectly-correlated bound of the guided filter's temporal v0.  A v0 that is not finite becomes 0 (include/ptmi_guided.h says why).  Otherwise v0 = NaN.
+ *
+ * The f32 operation order is fixed in include/ptmi_accumulate.h, which the kernel and ptmi_accumulate_reference both compile: their results agree bit for bit.  A
+ * view identical to its predecessor has wgt exactly 1 and q = p; while max_history does not bind, n after k identical views of one frame each is exactly k.
+ * CAVEAT.  ptmi_render_views gives every view the SAME frame numbers, so pixel idx draws the same random stream in every view.  Where the camera moves by less
+ * than a pixel between views the accumulated samples are the same sample: accumulation gains nothing there, and the variance reads too low, since n counts frames
+ * that are one frame.  Where it moves further, the samples of one surface point come from different pixels and therefore from different streams. */
+typedef struct ptmi_accumulate_params {
+  float max_history;   /* > 0, finite: at most this many frames are taken over from the previous view */
+  int32_t min_frames;  /* >= 2: fewer accumulated frames than this and a pixel states no variance */
+  float sigma_normal;  /* > 0 */
+  float sigma_depth;   /* > 0, relative to the distance of the reprojected point */
+  float albedo_floor;  /* > 0 */
+  int32_t reserved[3];
+} ptmi_accumulate_params;
+/* max_history 32, min_frames 4, sigma_normal 0.25, sigma_depth 0.1, albedo_floor 1e-3 */
+void ptmi_default_accumulate_params(ptmi_accumulate_params* p);
+/* Accumulates views [first_view, first_view + n_views) in ascending order into the context's ACCUMULATED STACK (above), zeroed when this call allocates it; images
+ * outside the range keep what they held.  resume == 0: view first_view has no history.  resume != 0: view first_view takes its history from view first_view - 1 of
+ * the accumulated stack, which must exist (PTMI_ERR_STATE otherwise) with first_view > 0 (PTMI_ERR_INVALID_ARG otherwise): a caller extends a path without redoing
+ * it.  Needs the view stack, the MOMENT stack (ptmi_set_view_moments) and the feature stack, of equal n_views; frame_num = the frames each image of the view stack
+ * sums.  views16 holds the matrices of ALL views of the stack — THE CALLER is responsible for their being the ones the stacks were rendered from.  The material
+ * types are those of the uploaded materials.  params = NULL: the defaults.  ptmi_resize and any change of the view stack's size drop the stack, as they drop the
+ * denoised and the fused one.  One kernel launch per view, in order on the context's stream: view v reads what view v-1's launch wrote, no events and no host
+ * synchronisation; asynchronous; touches no other stack, nor the accumulation buffer, nor any ptmi_stats field.
+ * PTMI_ERR_STATE: a needed stack is missing — the moment stack too, which is the case while moments are off —, or the stacks differ in n_views.
+ * PTMI_ERR_INVALID_ARG: a parameter outside its domain, a range past the stack, frame_num not finite or not > 0, a view matrix whose 3x3 has a zero or non-finite
+ * determinant.  PTMI_ERR_NO_MEMORY: before anything is enqueued; the accumulated stack the call found stays as it was.  PTMI_ERR_UNSUPPORTED: a multi-device
+ * context or a shard (ptmi_set_shard with world > 1) — gather the images first and use ptmi_accumulate_images. */
+int ptmi_accumulate_views(ptmi_ctx* ctx, const ptmi_accumulate_params* params, const float* views16, float frame_num, uint32_t first_view, uint32_t n_views, int resume);
+/* ptmi_read_view's counterpart for image `view` of plane `plane` (0 .. 2) of the accumulated stack: synchronises; bytes must be W*H*16. */
+int ptmi_read_accumulated(ptmi_ctx* ctx, uint32_t view, int plane, float* dst, size_t bytes);
+/* The display pass (ptmi_resolve_rgba8) for image `view` of plane 0 of the accumulated stack, at frameNum 1: the plane holds means. */
+int ptmi_resolve_accumulated_rgba8(ptmi_ctx* ctx, uint32_t view, uint8_t* dst, size_t bytes);
+/* The accumulated stack as one contiguous [3][n_views][H][W][4] f32 device array; valid until it is dropped (above) or ptmi_release_accumulated.  bytes / n_views may be NULL. */
+int ptmi_accumulated_device_ptr(ptmi_ctx* ctx, void** dev_ptr, size_t* bytes, uint32_t* n_views);
+/* Frees the accumulated stack and the call's view table (ptmi_destroy does too); synchronises. */
+int ptmi_release_accumulated(ptmi_ctx* ctx);
+/* The same kernel on host arrays of any size: colour_sums and moments [n_images][h][w][4], layers [n_images][3][h][w][4] (the feature stack's layout), views16
+ * [n_images][16], out [3][n_images][h][w][4], all f32; fov_degrees, lambertian and n_materials as ptmi_fuse_images takes them.  history_in = NULL: image 0 has no
+ * history and every image is accumulated.  history_in [2][h][w][4]: ONE step of the recursion from a given state — image 0 is then the view before the first
+ * accumulated one: it is not accumulated itself, history_in is taken for its planes 1 and 2 (and written to `out` as they are; its plane 0 in `out` is zero), and
+ * image 1 takes its history from them; needs n_images >= 2.  Synchronous; uses device copies of its own and leaves the context's stacks alone.  Errors as above (no
+ * PTMI_ERR_STATE). */
+int ptmi_accumulate_images(ptmi_ctx* ctx, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                           float frame_num, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
+                           const float* history_in, float* out);
+
+/* The variance-guided filter ("Variance-guided denoising" above) on an accumulated stack: the levels, the blur, the taps and the remodulation are exactly
+ * ptmi_denoise_views_guided's; colour = plane 0 with F = 1 (means, the way ptmi_fuse_views(source = 1) reads the denoised stack); the one difference is where v0
+ * comes from: for a valid pixel whose plane-2 w is not NaN, v0 is that value (not finite: 0, as everywhere); otherwise the 7 x 7 spatial estimate over l(d0).
+ * params->min_frames is not read: the accumulation has applied its own.  Reads images [first_view, first_view + n_views) of the accumulated and the feature stack
+ * and writes the same DENOISED STACK, so ptmi_read_denoised, ptmi_resolve_denoised_rgba8, ptmi_denoised_device_ptr, ptmi_release_denoised and
+ * ptmi_fuse_views(source = 1) work on its result unchanged.  Errors as ptmi_denoise_views_guided; PTMI_ERR_STATE: the accumulated or the feature stack is missing, or they
+ * differ in n_views. */
+int ptmi_denoise_views_accumulated(ptmi_ctx* ctx, const ptmi_guided_params* params, uint32_t first_view, uint32_t n_views);
+/* The same kernels on host arrays: means and plane2 [n_images][h][w][4] (planes 0 and 2 of an accumulated stack; of plane2 only w is read), layers
+ * [n_images][3][h][w][4], out [n_images][h][w][4], all f32; var_out as ptmi_denoise_images_guided's.  Synchronous.  Errors as above (no PTMI_ERR_STATE). */
+int ptmi_denoise_images_accumulated(ptmi_ctx* ctx, const float* means, const float* plane2, const float* layers, int w, int h, uint32_t n_images,
+                                    const ptmi_guided_params* params, float* out, float* var_out);
+
 /* Second moments and noise (no counterpart in the reference, which renders for as long as the page is open): how noisy is an image of the view stack?
  *
  * THE MOMENT STACK.  While ptmi_set_view_moments is on, every ptmi_render_views call also folds into the context's MOMENT STACK: [n_views][H][W][4] f32, derived from
@@ -582,6 +665,19 @@ int ptmi_denoise_guided_reference(const float* colour_sums, const float* moments
  * bits.  PTMI_ERR_INVALID_ARG / PTMI_ERR_NO_MEMORY as there. */
 int ptmi_fuse_reference(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
                         const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out);
+
+/* ptmi_accumulate_images without a GPU: a plain loop over views and pixels through include/ptmi_accumulate.h, the arithmetic the kernel compiles — the same
+ * arguments, the same bits.  threads: host threads that share a view's rows (the views stay in order; a pixel's arithmetic does not depend on the number);
+ * <= 1: none beside the caller.  PTMI_ERR_INVALID_ARG / PTMI_ERR_NO_MEMORY as there. */
+int ptmi_accumulate_reference(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                              float frame_num, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
+                              const float* history_in, float* out, int threads);
+
+/* ptmi_denoise_images_accumulated without a GPU: ptmi_denoise_guided_reference's loop with the initial variance taken from plane2 — the same arguments, the same
+ * bits, var_out (may be NULL) included.  threads: accepted for symmetry with ptmi_accumulate_reference; the loop is sequential.  PTMI_ERR_INVALID_ARG /
+ * PTMI_ERR_NO_MEMORY as there. */
+int ptmi_denoise_accumulated_reference(const float* means, const float* plane2, const float* layers, int w, int h, uint32_t n_images, const ptmi_guided_params* params,
+                                       float* out, float* var_out, int threads);
 
 /* ptmi_noise_images without a GPU: a plain loop over images and pixels through include/ptmi_noise.h, the arithmetic the kernel compiles — the same arguments, the
  * same bits and the same integers.  PTMI_ERR_INVALID_ARG as there. */

@@ -1,4 +1,4 @@
-// Sanitizer driver for the host natives of libptmi (ptmi_host.cpp): both BVH builders (1 thread vs many), the OBJ parser, cross-view fusion, the noise statistic and the variance-guided filter.
+// Sanitizer driver for the host natives of libptmi (ptmi_host.cpp): both BVH builders (1 thread vs many), the OBJ parser, cross-view fusion, temporal accumulation, the noise statistic and the variance-guided filter.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -pthread tools/sanitize_host.cpp webgpu-path-tracer_amd/csrc/ptmi_host.cpp -o /tmp/san/asan && /tmp/san/asan
 //   g++ -std=c++17 -O1 -g -fsanitize=thread -pthread ... -o /tmp/san/tsan && /tmp/san/tsan
 #include <cmath>
@@ -74,6 +74,24 @@ int main() {
     P.radius = 8;
     if (ptmi_fuse_reference(S.data(), L.data(), views.data(), w, h, n, 2.0f, 60.0f, lamb, 2, &P, out.data())) return 6;
     if (ptmi_fuse_reference(S.data(), L.data(), views.data(), w, h, n, 2.0f, 60.0f, nullptr, 0, nullptr, out.data())) return 7;
+    {  // ptmi_accumulate_reference on the same stack with moments of two frames (one of them infinite): chained, on several host threads, one step from a given state
+       // (a NaN and a zero count in it), and ptmi_denoise_accumulated_reference on what it leaves
+      std::vector<float> M(S.size()), acc(3 * S.size()), acc3(acc.size()), step(3 * 2 * npix * 4), den(S.size()), var(n * npix);
+      for (size_t i = 0; i < S.size(); i++) M[i] = (i % 4 == 3) ? 2.0f : 0.6f * S[i] * S[i];
+      M[4 * 5 + 1] = INFINITY;
+      ptmi_accumulate_params A;
+      ptmi_default_accumulate_params(&A);
+      A.min_frames = 2, A.max_history = 3.0f;
+      if (ptmi_accumulate_reference(S.data(), M.data(), L.data(), views.data(), w, h, n, 2.0f, 60.0f, lamb, 2, &A, nullptr, acc.data(), 1)) return 16;
+      if (ptmi_accumulate_reference(S.data(), M.data(), L.data(), views.data(), w, h, n, 2.0f, 60.0f, lamb, 2, &A, nullptr, acc3.data(), 3) || memcmp(acc.data(), acc3.data(), acc.size() * 4)) return 17;
+      std::vector<float> hist(2 * npix * 4);
+      memcpy(hist.data(), &acc[(size_t)(1 * n + 0) * npix * 4], npix * 16);
+      memcpy(hist.data() + npix * 4, &acc[(size_t)(2 * n + 0) * npix * 4], npix * 16);
+      hist[4 * 6] = NAN, hist[4 * 8 + 3] = 0.0f;
+      if (ptmi_accumulate_reference(S.data(), M.data(), L.data(), views.data(), w, h, 2, 2.0f, 60.0f, nullptr, 0, nullptr, hist.data(), step.data(), 2)) return 18;
+      if (ptmi_accumulate_reference(S.data(), M.data(), L.data(), views.data(), w, h, 1, 2.0f, 60.0f, nullptr, 0, nullptr, hist.data(), step.data(), 1) != PTMI_ERR_INVALID_ARG) return 19;
+      if (ptmi_denoise_accumulated_reference(acc.data(), &acc[(size_t)2 * n * npix * 4], L.data(), w, h, n, nullptr, den.data(), var.data(), 1)) return 20;
+    }
     views[0] = 0.0f;
     if (ptmi_fuse_reference(S.data(), L.data(), views.data(), w, h, n, 2.0f, 60.0f, nullptr, 0, nullptr, out.data()) != PTMI_ERR_INVALID_ARG) return 8;  // a singular matrix
   }

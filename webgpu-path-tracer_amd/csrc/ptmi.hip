@@ -26,6 +26,7 @@
 #include "ptmi_denoise_kernels.h"
 #include "ptmi_guided_kernels.h"
 #include "ptmi_fuse_kernels.h"
+#include "ptmi_accumulate_kernels.h"
 #include "ptmi_noise_kernels.h"
 #include "ptmi_tuning.h"
 
@@ -92,12 +93,14 @@ struct PeerWorker {
 };
 
 // The context's stacks of W x H float4 images, one allocation per kind.  A row per kind: images per view, the noun and the making call of the error texts, and whether
-// the stack is derived from the view stack (it has that stack's size and goes with it).
-enum StackKind { STACK_NONE = -1, STACK_VIEWS = 0, STACK_FEATURES, STACK_DENOISED, STACK_FUSED, STACK_MOMENTS, N_STACKS };  // (STACK_NONE: ImageRef's accumulation buffer)
+// the stack is derived from the view stack (it has that stack's size and goes with it), and whether its images lie plane by plane ([images per view][n] instead of
+// [n][images per view]).
+enum StackKind { STACK_NONE = -1, STACK_VIEWS = 0, STACK_FEATURES, STACK_DENOISED, STACK_FUSED, STACK_MOMENTS, STACK_ACCUMULATED, N_STACKS };  // (STACK_NONE: ImageRef's accumulation buffer)
 struct StackInfo {
   uint32_t images_per_view;
   const char *noun, *maker;
   bool derived;
+  bool plane_major = false;
 };
 constexpr StackInfo kStackInfo[N_STACKS] = {
     {1, "view stack", "ptmi_render_views", false},      // RGBA f32 sums
@@ -105,6 +108,7 @@ constexpr StackInfo kStackInfo[N_STACKS] = {
     {1, "denoised stack", "ptmi_denoise_views", true},  // RGBA f32 means
     {1, "fused stack", "ptmi_fuse_views", true},        // RGBA f32 means
     {1, "moment stack", "ptmi_render_views with ptmi_set_view_moments on", true},  // sums of squared frame colours, frame count in w
+    {3, "accumulated stack", "ptmi_accumulate_views", true, true},  // planes: RGBA f32 means; (D, n); (Q, v0)
 };
 struct Stack {
   DBuf buf;
@@ -152,7 +156,7 @@ struct ptmi_ctx {
   Stack stacks[N_STACKS];
   DBuf d_denoise_scratch;  // ptmi_denoise_views: three packed float4 images (d ping, d pong, n + z) per view of a batch (atrous_batch_views); ptmi_denoise_views_guided: and three f32 images (v ping, v pong, vg)
   StagedTable view_rows;   // the last ptmi_render_views / ptmi_render_aov call's view table (ViewTab: kViewRow float4 per view)
-  StagedTable fuse_tab;    // the last ptmi_fuse_views call's table (kFuseRow float4 per view of the stack, then one byte per material)
+  StagedTable fuse_tab;    // the last ptmi_fuse_views / ptmi_accumulate_views call's table (kFuseRow float4 per view of the stack, then one byte per material)
   bool view_moments = false;  // ptmi_set_view_moments: ptmi_render_views folds second moments into stacks[STACK_MOMENTS] too
   DBuf d_noise_rec;           // ptmi_view_noise_stats: one record (kNoiseRecordBytes) per view of the call
   int rank = 0, world = 1, tile = 64;
@@ -2048,7 +2052,8 @@ static int read_stack(ptmi_ctx* c, StackKind k, const char* who, uint32_t view, 
   const int layers = (int)kStackInfo[k].images_per_view;
   if (layer < 0 || layer >= layers) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": layer " + std::to_string(layer) + " of " + std::to_string(layers));
   if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": bytes != W*H*16");
-  return read_image(c, ImageRef{k, (size_t)view * layers + (size_t)layer}, dst, bytes);
+  const size_t index = kStackInfo[k].plane_major ? (size_t)layer * c->stacks[k].n + (size_t)view : (size_t)view * layers + (size_t)layer;
+  return read_image(c, ImageRef{k, index}, dst, bytes);
 }
 static int resolve_stack(ptmi_ctx* c, StackKind k, const char* who, uint32_t view, float frame_num, uint8_t* dst, size_t bytes) {
   if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
@@ -2074,7 +2079,7 @@ static int release_stack(ptmi_ctx* c, StackKind k) {
     HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still read or write a stack that is about to go
     drop_stack(q, k);
     if (k == STACK_DENOISED) q->d_denoise_scratch.release();
-    if (k == STACK_FUSED) q->fuse_tab.dev.release();
+    if (k == STACK_FUSED || k == STACK_ACCUMULATED) q->fuse_tab.dev.release();  // (every call that reads the table stages it again)
     return PTMI_OK;
   });
 }
@@ -2180,6 +2185,7 @@ struct AtrousGuide {
   float* var_out;
   ptmg_consts kg;
   int min_frames;
+  const float4* given = nullptr;  // plane 2 of an accumulated stack, [n][H][W] float4: its w is v0 where it is not NaN (k_accumulated_variance); `moments` is then not read
 };
 
 // Either filter on device arrays: colour [n][H][W] float4 sums, layers [n][3][H][W] float4, out [n][H][W] float4; G = nullptr: the plain filter.  c->d_denoise_scratch
@@ -2204,7 +2210,10 @@ static int atrous_enqueue(ptmi_ctx* c, const float4* colour, const float4* layer
     hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, F, P.albedo_floor, d[0], g);
     HIP_TRY(c, hipGetLastError());
     const dim3 tgrid((unsigned)((W + kDenoiseTX - 1) / kDenoiseTX), (unsigned)((H + kGuidedTY - 1) / kGuidedTY), nv);
-    if (G) {
+    if (G && G->given) {
+      hipLaunchKernelGGL(k_accumulated_variance, tgrid, dim3(kBlock), 0, c->stream, d[0], G->given + (size_t)v0 * npix, W, H, v[0]);
+      HIP_TRY(c, hipGetLastError());
+    } else if (G) {
       hipLaunchKernelGGL(k_guided_variance, tgrid, dim3(kBlock), 0, c->stream, d[0], col, G->moments + (size_t)v0 * npix, lay, W, H, P.albedo_floor, G->min_frames, v[0]);
       HIP_TRY(c, hipGetLastError());
     }
@@ -2274,18 +2283,21 @@ static int check_source_stacks(ptmi_ctx* c, const char* who, bool need_denoised,
 }
 
 // Either filter from the context's stacks into its denoised stack, the arguments checked.  The stack and the scratch, everything that can fail for want of memory, come
-// before anything is enqueued.  G: as atrous_enqueue's, its `moments` filled in here.
-static int atrous_views(ptmi_ctx* c, const ptmi_denoise_params& P, AtrousGuide* G, float frame_num, uint32_t first_view, uint32_t n_views) {
+// before anything is enqueued.  G: as atrous_enqueue's, its `moments` (or, with `accumulated`, its `given`) filled in here.  accumulated: the colour is plane 0 of the
+// accumulated stack, not the view stack.
+static int atrous_views(ptmi_ctx* c, const ptmi_denoise_params& P, AtrousGuide* G, float frame_num, uint32_t first_view, uint32_t n_views, bool accumulated = false) {
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
   const size_t npix = (size_t)c->W * (size_t)c->H;
-  const uint32_t n_stack = c->stacks[STACK_VIEWS].n;
+  const StackKind source = accumulated ? STACK_ACCUMULATED : STACK_VIEWS;
+  const uint32_t n_stack = c->stacks[source].n;
   DBuf stack;
   if (int r = reserve_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
   HIP_TRY(c, c->d_denoise_scratch.ensure_idle(atrous_scratch_bytes(npix, n_views, G ? kGuidedScratchBytes : kDenoiseScratchBytes), c->stream));
   if (int r = commit_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
-  if (G) G->moments = c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix;
-  return atrous_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)first_view * npix, c->stacks[STACK_FEATURES].buf.as<float4>() + (size_t)first_view * 3 * npix,
+  if (G && accumulated) G->given = c->stacks[STACK_ACCUMULATED].buf.as<float4>() + ((size_t)2 * n_stack + first_view) * npix;
+  else if (G) G->moments = c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix;
+  return atrous_enqueue(c, c->stacks[source].buf.as<float4>() + (size_t)first_view * npix, c->stacks[STACK_FEATURES].buf.as<float4>() + (size_t)first_view * 3 * npix,
                         c->stacks[STACK_DENOISED].buf.as<float4>() + (size_t)first_view * npix, n_views, c->W, c->H, frame_num, P, G);
 }
 
@@ -2432,6 +2444,34 @@ static int fuse_check_args(ptmi_ctx* c, const char* who, const ptmi_fuse_params*
   return check_stack_call(c, who, "a view's pixels", "several", ok ? nullptr : "radius in 1..8, sigma_normal, sigma_depth and albedo_floor > 0, all finite", need_frames, frame_num);
 }
 
+// What ptmi_fuse_views and ptmi_accumulate_views do before they enqueue a kernel: the table of all views of the stack with the uploaded materials' types, the call's
+// stack `k` (of the view stack's size) and the table's two copies — everything that can fail for want of memory, before anything is enqueued — and then the
+// table's upload.
+static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, const float* views16) {
+  const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
+  const size_t tab_bytes = fuse_tab_bytes(n_stack, n_mat);
+  std::vector<float> tab;
+  std::vector<uint8_t> lamb;
+  try {
+    tab.resize(tab_bytes / 4 + 1);
+    lamb.resize(n_mat);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the view table");
+  }
+  for (uint32_t i = 0; i < n_mat; i++) lamb[i] = c->h_mats[16 * (size_t)i + 14] == PTMF_LAMBERTIAN;
+  if (int r = fuse_fill_tab(c, who, views16, n_stack, lamb.data(), n_mat, tab.data())) return r;
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  DBuf stack;
+  if (int r = reserve_stack(c, k, n_stack, &stack)) return r;
+  void* staged = nullptr;
+  HIP_TRY(c, c->fuse_tab.stage(tab_bytes, c->stream, &staged));
+  memcpy(staged, tab.data(), tab_bytes);
+  if (int r = commit_stack(c, k, n_stack, &stack)) return r;
+  HIP_TRY(c, c->fuse_tab.send(tab_bytes, c->stream));
+  return PTMI_OK;
+}
+
 int ptmi_fuse_views(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, float frame_num, int source, uint32_t first_view, uint32_t n_views) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_views: null argument");
@@ -2440,26 +2480,7 @@ int ptmi_fuse_views(ptmi_ctx* c, const ptmi_fuse_params* params, const float* vi
   if (int r = fuse_check_args(c, "ptmi_fuse_views", params, frame_num, source == 0, &P)) return r;
   if (int r = check_source_stacks(c, "ptmi_fuse_views", source == 1, first_view, n_views)) return r;
   const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  const size_t tab_bytes = fuse_tab_bytes(n_stack, n_mat);
-  std::vector<float> tab;
-  std::vector<uint8_t> lamb(n_mat);
-  try {
-    tab.resize(tab_bytes / 4 + 1);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_fuse_views: no host memory for the view table");
-  }
-  for (uint32_t i = 0; i < n_mat; i++) lamb[i] = c->h_mats[16 * (size_t)i + 14] == PTMF_LAMBERTIAN;
-  if (int r = fuse_fill_tab(c, "ptmi_fuse_views", views16, n_stack, lamb.data(), n_mat, tab.data())) return r;
-  HIP_TRY(c, hipSetDevice(c->device));
-  (void)hipGetLastError();
-  // the stack, the table and its staging copy: everything that can fail for want of memory, before anything is enqueued
-  DBuf stack;
-  if (int r = reserve_stack(c, STACK_FUSED, n_stack, &stack)) return r;
-  void* staged = nullptr;
-  HIP_TRY(c, c->fuse_tab.stage(tab_bytes, c->stream, &staged));
-  memcpy(staged, tab.data(), tab_bytes);
-  if (int r = commit_stack(c, STACK_FUSED, n_stack, &stack)) return r;
-  HIP_TRY(c, c->fuse_tab.send(tab_bytes, c->stream));
+  if (int r = make_stack_with_table(c, "ptmi_fuse_views", STACK_FUSED, views16)) return r;
   const float fov_factor = (float)(1.0 / std::tan((double)c->prm.fov_degrees * (3.14159265358979323846 / 180.0) / 2.0));  // as make_render_const folds it
   const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, source == 0 ? frame_num : 1.0f, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   return fuse_enqueue(c, c->stacks[source == 0 ? STACK_VIEWS : STACK_DENOISED].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(), c->stacks[STACK_FUSED].buf.as<float4>(),
@@ -2495,6 +2516,138 @@ int ptmi_fuse_images(ptmi_ctx* c, const float* colour, const float* layers, cons
     HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
     return fuse_enqueue(c, col, lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, 0, n_images, k);
   });
+}
+
+// ---- the accumulated stack (ptmi_accumulate_views, ptmi_accumulate_images) and the guided filter on it (ptmi_denoise_views_accumulated, ptmi_denoise_images_accumulated) ----
+// (ptmi_default_accumulate_params, ptmi_accumulate_reference and ptmi_denoise_accumulated_reference need no GPU: ptmi_host.cpp)
+// The kernel on device arrays: colour, moments [n_stack][H][W] float4, layers [n_stack][3][H][W] float4, planes [3][n_stack][H][W] float4, of which views
+// [first, first + n) are written, one launch per view in ascending order; view `first` takes its history from view first - 1 of `planes` when `resume`.
+static int accumulate_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, const float4* layers, float4* planes, const void* tab, bool has_lamb, uint32_t n_materials,
+                              int W, int H, uint32_t n_stack, uint32_t first, uint32_t n, bool resume, const ptmf_consts& k, const ptma_consts& ka) {
+  const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
+  const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
+  const uint8_t* lamb = has_lamb ? reinterpret_cast<const uint8_t*>(tab) + (size_t)n_stack * kFuseRow * 16 : nullptr;
+  const size_t npix = (size_t)W * (size_t)H;
+  auto plane = [&](uint32_t pl, uint32_t v) { return planes + ((size_t)pl * n_stack + v) * npix; };
+  for (uint32_t v = first; v < first + n; v++) {
+    const bool has_prev = v > 0 && (v > first || resume);
+    hipLaunchKernelGGL(k_accumulate_view, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr, has_prev ? plane(2, v - 1) : nullptr,
+                       plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka);
+    HIP_TRY(c, hipGetLastError());
+  }
+  return PTMI_OK;
+}
+
+static int accumulate_check_args(ptmi_ctx* c, const char* who, const ptmi_accumulate_params* params, float frame_num, ptmi_accumulate_params* P) {
+  if (params) *P = *params;
+  else ptmi_default_accumulate_params(P);
+  const bool ok = ptma_params_ok(P->max_history, P->min_frames, P->sigma_normal, P->sigma_depth, P->albedo_floor);
+  return check_stack_call(c, who, "a view's pixels", "several", ok ? nullptr : "max_history, sigma_normal, sigma_depth and albedo_floor > 0, all finite, and min_frames >= 2", true, frame_num);
+}
+
+int ptmi_accumulate_views(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, float frame_num, uint32_t first_view, uint32_t n_views, int resume) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_accumulate_views: null argument");
+  ptmi_accumulate_params P;
+  if (int r = accumulate_check_args(c, "ptmi_accumulate_views", params, frame_num, &P)) return r;
+  if (int r = check_stack(c, STACK_MOMENTS, "ptmi_accumulate_views", 0)) return r;  // (the moment stack first, as ptmi_denoise_views_guided asks)
+  if (int r = check_stack(c, STACK_VIEWS, "ptmi_accumulate_views", 0)) return r;
+  if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
+    return fail(c, PTMI_ERR_STATE, "ptmi_accumulate_views: the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
+  if (int r = check_source_stacks(c, "ptmi_accumulate_views", false, first_view, n_views)) return r;
+  if (resume) {
+    if (first_view == 0) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_accumulate_views: resume needs first_view > 0: view 0 has no predecessor");
+    if (int r = check_stack(c, STACK_ACCUMULATED, "ptmi_accumulate_views (resume)", 0)) return r;
+  }
+  const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
+  if (int r = make_stack_with_table(c, "ptmi_accumulate_views", STACK_ACCUMULATED, views16)) return r;
+  const float fov_factor = (float)(1.0 / std::tan((double)c->prm.fov_degrees * (3.14159265358979323846 / 180.0) / 2.0));  // as make_render_const folds it
+  const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
+  return accumulate_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>(), c->stacks[STACK_MOMENTS].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(),
+                            c->stacks[STACK_ACCUMULATED].buf.as<float4>(), c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, resume != 0, k,
+                            ptma_make_consts(P.max_history, P.min_frames));
+}
+
+int ptmi_read_accumulated(ptmi_ctx* c, uint32_t view, int plane, float* dst, size_t bytes) { return read_stack(c, STACK_ACCUMULATED, "ptmi_read_accumulated", view, plane, dst, bytes); }
+int ptmi_resolve_accumulated_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t bytes) {
+  return resolve_stack(c, STACK_ACCUMULATED, "ptmi_resolve_accumulated_rgba8", view, 1.0f, dst, bytes);  // (plane 0, whose image `view` is the stack's image `view`: means, the display pass at frameNum 1)
+}
+int ptmi_accumulated_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
+  return stack_device_ptr(c, STACK_ACCUMULATED, "ptmi_accumulated_device_ptr", nullptr, p, bytes, n_views);
+}
+int ptmi_release_accumulated(ptmi_ctx* c) { return release_stack(c, STACK_ACCUMULATED); }
+
+int ptmi_accumulate_images(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
+                           float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out) {
+  if (!c || !colour_sums || !moments || !layers || !views16 || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_accumulate_images: null argument");
+  ptmi_accumulate_params P;
+  if (int r = accumulate_check_args(c, "ptmi_accumulate_images", params, frame_num, &P)) return r;
+  if (int r = check_image_size(c, "ptmi_accumulate_images", w, h, n_images)) return r;
+  if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_accumulate_images: fov_degrees must be in (0,180)");
+  if (history_in && n_images < 2) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_accumulate_images: history_in makes image 0 the view before the first: need n_images >= 2");
+  if (!lambertian) n_materials = 0;
+  const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials);
+  std::vector<float> tab;
+  try {
+    tab.resize(tab_bytes / 4 + 1);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_accumulate_images: no host memory for the view table");
+  }
+  if (int r = fuse_fill_tab(c, "ptmi_accumulate_images", views16, n_images, lambertian, n_materials, tab.data())) return r;
+  const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
+  const ptma_consts ka = ptma_make_consts(P.max_history, P.min_frames);
+  const size_t npix = (size_t)w * (size_t)h, bytes = npix * 16 * n_images;
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  DBuf mom, dtab;  // (on_host_images brings the colour, the layers, the three planes and the table; the moments are this call's own, had before anything is enqueued)
+  HIP_TRY(c, mom.ensure(bytes));
+  return on_host_images(c, "ptmi_accumulate_images", colour_sums, layers, npix, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
+    HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(mom.p, moments, bytes, hipMemcpyHostToDevice, c->stream));
+    if (history_in) {  // image 0 is the view before the first: its state is given, its mean is not made
+      HIP_TRY(c, hipMemsetAsync(res, 0, npix * 16, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(res + (size_t)n_images * npix, history_in, npix * 16, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(res + (size_t)2 * n_images * npix, history_in + npix * 4, npix * 16, hipMemcpyHostToDevice, c->stream));
+    }
+    const uint32_t first = history_in ? 1u : 0u;
+    return accumulate_enqueue(c, col, mom.as<float4>(), lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, first, n_images - first, history_in != nullptr, k, ka);
+  }, 3, 48);
+}
+
+int ptmi_denoise_views_accumulated(ptmi_ctx* c, const ptmi_guided_params* params, uint32_t first_view, uint32_t n_views) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  ptmi_denoise_params P;
+  AtrousGuide G;
+  if (int r = guided_check_args(c, "ptmi_denoise_views_accumulated", params, 1.0f, &P, &G)) return r;
+  if (int r = check_stack(c, STACK_ACCUMULATED, "ptmi_denoise_views_accumulated", 0)) return r;
+  if (int r = check_stack(c, STACK_FEATURES, "ptmi_denoise_views_accumulated", 0)) return r;
+  const uint32_t n = c->stacks[STACK_ACCUMULATED].n, na = c->stacks[STACK_FEATURES].n;
+  if (n != na) return fail(c, PTMI_ERR_STATE, "ptmi_denoise_views_accumulated: the accumulated stack has " + std::to_string(n) + " views, the feature stack " + std::to_string(na));
+  if (int r = check_view_range(c, "ptmi_denoise_views_accumulated", first_view, n_views, n)) return r;
+  return atrous_views(c, P, &G, 1.0f, first_view, n_views, true);
+}
+
+int ptmi_denoise_images_accumulated(ptmi_ctx* c, const float* means, const float* plane2, const float* layers, int w, int h, uint32_t n_images, const ptmi_guided_params* params,
+                                    float* out, float* var_out) {
+  if (!c || !means || !plane2 || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images_accumulated: null argument");
+  ptmi_denoise_params P;
+  AtrousGuide G;
+  if (int r = guided_check_args(c, "ptmi_denoise_images_accumulated", params, 1.0f, &P, &G)) return r;
+  if (int r = check_image_size(c, "ptmi_denoise_images_accumulated", w, h, n_images)) return r;
+  const size_t npix = (size_t)w * (size_t)h, bytes = npix * 16 * n_images, var_bytes = var_out ? npix * 4 * n_images : 0;
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  DBuf giv, var;  // (as ptmi_denoise_images_guided's moments and variance)
+  HIP_TRY(c, giv.ensure(bytes));
+  HIP_TRY(c, var.ensure(var_bytes));
+  G.given = giv.as<float4>(), G.var_out = var.as<float>();
+  return on_host_images(c, "ptmi_denoise_images_accumulated", means, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kGuidedScratchBytes),
+                        [&](const float4* col, const float4* lay, float4* res) -> int {
+                          HIP_TRY(c, hipMemcpyAsync(giv.p, plane2, bytes, hipMemcpyHostToDevice, c->stream));
+                          if (int e = atrous_enqueue(c, col, lay, res, n_images, w, h, 1.0f, P, &G)) return e;
+                          if (var_out) HIP_TRY(c, hipMemcpyAsync(var_out, var.p, var_bytes, hipMemcpyDeviceToHost, c->stream));
+                          return PTMI_OK;
+                        });
 }
 
 // ---- the moment stack and the noise statistic (ptmi_set_view_moments, ptmi_view_noise_stats, ptmi_noise_images, ptmi_render_views_until) ----

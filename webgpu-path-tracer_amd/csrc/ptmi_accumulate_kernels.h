@@ -1,0 +1,121 @@
+// ptmi_accumulate_kernels.h — the kernels of ptmi_accumulate_views / ptmi_accumulate_images and of the guided filter on an accumulated stack (include/ptmi.h,
+// "Temporal accumulation").  Every f32 operation of a pixel is in include/ptmi_accumulate.h, which the host natives include too; this file only decides where the
+// operands come from.
+//
+// k_accumulate_view     One lane owns one pixel of ONE view, a wave 64 neighbouring pixels of one row, a block four such waves: k_fuse's row tiles.  A call launches
+//                       its views one after the other on one stream, so view v's launch finds what view v-1's wrote.  The own view's matrix and the previous view's
+//                       B, o come through scalar loads (fuse_load_own, fuse_load_neighbour).  The lane loads S, M, N, A, I of p together; after an accepted projection
+//                       it issues S, N, A, I and planes 1 and 2 of view v-1 at q as one group of six independent 16-byte gathers, kept together by an operand fence
+//                       as k_fuse's are.  Three float4 stores per pixel.  No LDS, no scratch, no atomics.  The planes read and the planes written are parts of one
+//                       allocation: none of the six pointers is __restrict__.  Per pixel, as compiled (of I only z is read, of plane 2 at q only
+//                       xyz): 68 B read of p, up to 80 B gathered at q, 48 B stored, and one material-type byte (profiles/accumulate_kernel_resources.txt).
+// k_accumulated_variance  k_guided_variance (ptmi_guided_kernels.h: the same tile, the same staging, the same 7 x 7 walk) for a stack that brings its variance
+//                       with it: v0 is plane 2's w where that is not NaN, the spatial estimate elsewhere.  A second kernel beside k_guided_variance, which stays as it is.
+#pragma once
+
+#include "../../include/ptmi_accumulate.h"
+#include "ptmi_fuse_kernels.h"
+#include "ptmi_guided_kernels.h"
+
+namespace ptmi {
+
+// the operand fence of the gathers at q: fuse_loaded's four sums and the two planes of the state
+DEV void accumulate_loaded(const float4& S, const float4& N, const float4& A, const float4& I, const float4& P1, const float4& P2) {
+  fuse_loaded(S, N, A, I);
+  asm volatile("" ::"v"(P1.x), "v"(P1.y), "v"(P1.z), "v"(P1.w), "v"(P2.x), "v"(P2.y), "v"(P2.z));
+}
+
+// colour, moments: [n_stack][npix] float4 sums; layers: [n_stack][3][npix] float4; prev1, prev2: planes 1 and 2 of view v - 1 ([npix] float4 each), nullptr: view v has
+// no history; out0, out1, out2: view v's image of planes 0, 1, 2; tab: kFuseRow float4 per view of the stack; lamb: one byte per material index or nullptr.
+// grid: x = (tiles of 64 columns x rows) / 4; block 256.
+__global__ __launch_bounds__(kBlock) void k_accumulate_view(const float4* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ layers,
+                                                            const float4* prev1, const float4* prev2, float4* out0, float4* out1, float4* out2,
+                                                            const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t v,
+                                                            ptmf_consts k, ptma_consts ka) {
+  const uint32_t tiles_x = ((uint32_t)W + 63u) / 64u;
+  const uint32_t tile = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);  // wave-uniform
+  const uint32_t y = tile / tiles_x;
+  if (y >= (uint32_t)H) return;
+  const int x = (int)((tile - y * tiles_x) * 64u + (threadIdx.x & 63u));
+  if (x >= W) return;
+  const size_t npix = (size_t)W * (size_t)H;
+  const uint32_t idx = y * (uint32_t)W + (uint32_t)x;
+  const float4* Lv = layers + (size_t)v * 3 * npix;
+  const float4 Sp = colour[(size_t)v * npix + idx], Mp = moments[(size_t)v * npix + idx], Np = Lv[idx], Ap = Lv[npix + idx], Ip = Lv[2 * npix + idx];
+  fuse_loaded(Sp, Np, Ap, Ip);
+  asm volatile("" ::"v"(Mp.x), "v"(Mp.y), "v"(Mp.z), "v"(Mp.w));
+  const ptmd_f4 S = dn_f4(Sp), A = dn_f4(Ap);
+  ptmd_f4 dp, gp, P1, P2;
+  const int valid = ptmd_prepare(S, dn_f4(Np), A, dn_f4(Ip), k.F, k.floor, &dp, &gp);
+  const int accumulates = valid && ptmf_fusable(dp.w, lamb, n_materials);
+  ptma_own(valid, dp, dn_f4(Mp), A, k.floor, &P1, &P2);
+  if (accumulates && prev1) {  // (prev1: uniform over the launch)
+    ptmf_view V, U;
+    fuse_load_own(tab, v, V);
+    fuse_load_neighbour(tab, v - 1u, U);
+    float X[3], r;
+    int qx, qy;
+    ptmf_world(&k, &V, x, idx, gp.w, X);
+    if (ptmf_project(&k, &U, X, &qx, &qy, &r)) {
+      const size_t q = (size_t)qy * (size_t)W + (size_t)qx;
+      const float4* Lu = layers + (size_t)(v - 1u) * 3 * npix;
+      const float4 Sq = colour[(size_t)(v - 1u) * npix + q], Nq = Lu[q], Aq = Lu[npix + q], Iq = Lu[2 * npix + q], H1 = prev1[q], H2 = prev2[q];  // six independent gathers
+      accumulate_loaded(Sq, Nq, Aq, Iq, H1, H2);
+      float wgt;
+      if (ptma_weight(&k, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), &wgt)) ptma_take(&ka, wgt, dn_f4(H1), dn_f4(H2), &P1, &P2);
+    }
+  }
+  P2.w = ptma_v0(&ka, valid, P1, P2);
+  out0[idx] = dn_float4(ptma_mean(&k, S, A, accumulates, P1));
+  out1[idx] = dn_float4(P1);
+  out2[idx] = dn_float4(P2);
+}
+
+// grid: x = tiles of 64 columns, y = tiles of kGuidedTY rows, z = view of the batch.  d0: [n][npix] packed (prepare); plane2: [n][npix] float4, w = the given v0 or NaN
+__global__ __launch_bounds__(kBlock) void k_accumulated_variance(const float4* __restrict__ d0, const float4* __restrict__ plane2, int W, int H, float* __restrict__ v0) {
+  constexpr int cols = kDenoiseTX + 6, rows = kGuidedTY + 6;
+  __shared__ float2 tile[rows * cols];
+  const size_t npix = (size_t)W * (size_t)H, view = blockIdx.z;
+  d0 += view * npix;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int x0 = (int)blockIdx.x * kDenoiseTX, y0 = (int)blockIdx.y * kGuidedTY;
+  for (int rr = wv; rr < rows; rr += kBlock / 64) {
+    const int y = y0 - 3 + rr;
+    const bool row_in = y >= 0 && y < H;
+    for (int cc = lane; cc < cols; cc += 64) {
+      const int x = x0 - 3 + cc;
+      float2 t = make_float2(0.0f, ptmd_nan());
+      if (row_in && x >= 0 && x < W) {
+        const float4 d = d0[(size_t)y * (size_t)W + (size_t)x];
+        t = make_float2(ptmg_luma(d.x, d.y, d.z), d.w);
+      }
+      tile[rr * cols + cc] = t;
+    }
+  }
+  __syncthreads();
+  const int x = x0 + lane;
+  if (x >= W) return;
+  for (int r = wv; r < kGuidedTY; r += kBlock / 64) {
+    const int y = y0 + r;
+    if (y >= H) break;
+    const int centre = (r + 3) * cols + 3 + lane;
+    const size_t p = (size_t)y * (size_t)W + (size_t)x;
+    const float mp = tile[centre].y;
+    float v = 0.0f;
+    if (mp == mp && !ptma_v0_given(plane2[view * npix + p].w, &v)) {
+      float cnt = 0.0f, s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+      for (int j = -3; j <= 3; j++) {
+#pragma unroll
+        for (int i = -3; i <= 3; i++) {
+          const float2 t = tile[centre + j * cols + i];
+          ptmg_v0_add(mp, t.y, t.x, &cnt, &s1, &s2);
+        }
+      }
+      v = ptmg_v0_spatial(cnt, s1, s2);
+    }
+    v0[view * npix + p] = v;
+  }
+}
+
+}  // namespace ptmi

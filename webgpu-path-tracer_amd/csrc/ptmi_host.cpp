@@ -22,6 +22,7 @@
 #include "../../include/ptmi_denoise.h"
 #include "../../include/ptmi_guided.h"
 #include "../../include/ptmi_fuse.h"
+#include "../../include/ptmi_accumulate.h"
 #include "../../include/ptmi_noise.h"
 
 namespace {
@@ -683,6 +684,7 @@ struct HostGuide {
   float* var_out;
   ptmg_consts kg;
   int32_t min_frames;
+  const float* given;  // ptmi_denoise_accumulated_reference: plane 2 of an accumulated stack, whose w is the initial variance where it is not NaN (moments is then nullptr)
 };
 
 // Both filters: a plain loop over pixels through include/ptmi_denoise.h and include/ptmi_guided.h, the headers the kernels of ptmi_denoise_views and
@@ -702,7 +704,8 @@ static int atrous_reference(const float* colour_sums, const float* layers, int w
   const ptmd_f4 outside{0.0f, 0.0f, 0.0f, ptmd_nan()};
   for (uint32_t v = 0; v < n_images; v++) {
     const ptmd_f4* S = reinterpret_cast<const ptmd_f4*>(colour_sums) + (size_t)v * npix;
-    const ptmd_f4* M = G ? reinterpret_cast<const ptmd_f4*>(G->moments) + (size_t)v * npix : nullptr;
+    const ptmd_f4* M = G && G->moments ? reinterpret_cast<const ptmd_f4*>(G->moments) + (size_t)v * npix : nullptr;
+    const ptmd_f4* P2 = G && G->given ? reinterpret_cast<const ptmd_f4*>(G->given) + (size_t)v * npix : nullptr;
     const ptmd_f4* L = reinterpret_cast<const ptmd_f4*>(layers) + (size_t)v * 3 * npix;
     ptmd_f4* O = reinterpret_cast<ptmd_f4*>(out) + (size_t)v * npix;
     for (size_t p = 0; p < npix; p++) {
@@ -715,7 +718,7 @@ static int atrous_reference(const float* colour_sums, const float* layers, int w
           const size_t p = (size_t)y * w + x;
           const float mp = d[0][p].w;
           float v0 = 0.0f;
-          if (mp == mp && !ptmg_v0_temporal(S[p], M[p], L[npix + p], P.albedo_floor, G->min_frames, &v0)) {
+          if (mp == mp && !(P2 ? ptma_v0_given(P2[p].w, &v0) : ptmg_v0_temporal(S[p], M[p], L[npix + p], P.albedo_floor, G->min_frames, &v0))) {
             float cnt = 0.0f, s1 = 0.0f, s2 = 0.0f;
             for (int j = -3; j <= 3; j++)
               for (int i = -3; i <= 3; i++) {
@@ -807,8 +810,20 @@ extern "C" int ptmi_denoise_guided_reference(const float* colour_sums, const flo
   else ptmi_default_guided_params(&P);
   if (!ptmg_params_ok(P.levels, P.sigma_normal, P.sigma_depth, P.sigma_luma, P.albedo_floor, P.min_frames, P.var_eps)) return PTMI_ERR_INVALID_ARG;
   if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
-  const HostGuide G{moments, var_out, ptmg_make_consts(P.sigma_luma, P.var_eps), P.min_frames};
+  const HostGuide G{moments, var_out, ptmg_make_consts(P.sigma_luma, P.var_eps), P.min_frames, nullptr};
   return atrous_reference(colour_sums, layers, w, h, n_images, frame_num, ptmi_denoise_params{P.levels, P.sigma_normal, P.sigma_depth, 0.0f, P.albedo_floor, {}}, &G, out);
+}
+
+extern "C" int ptmi_denoise_accumulated_reference(const float* means, const float* plane2, const float* layers, int w, int h, uint32_t n_images, const ptmi_guided_params* params,
+                                                  float* out, float* var_out, int threads) {
+  (void)threads;
+  if (!means || !plane2 || !layers || !out || w <= 0 || h <= 0 || n_images == 0) return PTMI_ERR_INVALID_ARG;
+  ptmi_guided_params P;
+  if (params) P = *params;
+  else ptmi_default_guided_params(&P);
+  if (!ptmg_params_ok(P.levels, P.sigma_normal, P.sigma_depth, P.sigma_luma, P.albedo_floor, P.min_frames, P.var_eps)) return PTMI_ERR_INVALID_ARG;
+  const HostGuide G{nullptr, var_out, ptmg_make_consts(P.sigma_luma, P.var_eps), P.min_frames, plane2};
+  return atrous_reference(means, layers, w, h, n_images, 1.0f, ptmi_denoise_params{P.levels, P.sigma_normal, P.sigma_depth, 0.0f, P.albedo_floor, {}}, &G, out);
 }
 
 // ---- cross-view fusion on the host (ptmi_fuse_reference) ----
@@ -873,6 +888,90 @@ extern "C" int ptmi_fuse_reference(const float* colour, const float* layers, con
         }
         O[(size_t)v * npix + idx] = ptmf_output(&k, Sp, Ap, fused, num, den);
       }
+  }
+  return PTMI_OK;
+}
+
+// ---- temporal accumulation on the host (ptmi_accumulate_reference) ----
+extern "C" void ptmi_default_accumulate_params(ptmi_accumulate_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->max_history = 32.0f;
+  p->min_frames = 4;
+  p->sigma_normal = 0.25f;
+  p->sigma_depth = 0.1f;
+  p->albedo_floor = 1e-3f;
+}
+
+// A plain loop over views, in order, and pixels through include/ptmi_accumulate.h, the header the kernel of ptmi_accumulate_views compiles.  View v reads planes 1 and 2
+// of view v-1 in `out`, as the kernel does.  Nothing is tiled or reordered; `threads` > 1 share the rows of a view, whose pixels do not depend on one another.
+extern "C" int ptmi_accumulate_reference(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                         float frame_num, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
+                                         const float* history_in, float* out, int threads) {
+  if (!colour_sums || !moments || !layers || !views16 || !out || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
+  ptmi_accumulate_params P;
+  if (params) P = *params;
+  else ptmi_default_accumulate_params(&P);
+  if (!ptma_params_ok(P.max_history, P.min_frames, P.sigma_normal, P.sigma_depth, P.albedo_floor)) return PTMI_ERR_INVALID_ARG;
+  if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
+  if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return PTMI_ERR_INVALID_ARG;
+  if (history_in && n_images < 2) return PTMI_ERR_INVALID_ARG;
+  std::vector<ptmf_view> tab;
+  try {
+    tab.resize(n_images);
+  } catch (const std::bad_alloc&) {
+    return PTMI_ERR_NO_MEMORY;
+  }
+  for (uint32_t v = 0; v < n_images; v++)
+    if (!ptmf_make_view(views16 + 16 * (size_t)v, &tab[v])) return PTMI_ERR_INVALID_ARG;
+  const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
+  const ptma_consts ka = ptma_make_consts(P.max_history, P.min_frames);
+  const size_t npix = (size_t)w * (size_t)h;
+  const ptmd_f4* S = reinterpret_cast<const ptmd_f4*>(colour_sums);
+  const ptmd_f4* M = reinterpret_cast<const ptmd_f4*>(moments);
+  const ptmd_f4* L = reinterpret_cast<const ptmd_f4*>(layers);
+  ptmd_f4* O = reinterpret_cast<ptmd_f4*>(out);
+  auto plane = [&](int pl, uint32_t v) { return O + ((size_t)pl * n_images + v) * npix; };
+  uint32_t first = 0;
+  if (history_in) {  // image 0 is the view before the first: its state is given
+    memset(plane(0, 0), 0, npix * 16);
+    memcpy(plane(1, 0), history_in, npix * 16);
+    memcpy(plane(2, 0), history_in + npix * 4, npix * 16);
+    first = 1;
+  }
+  const unsigned nt = (unsigned)std::max(1, std::min(std::min(threads, 64), h));
+  for (uint32_t v = first; v < n_images; v++) {
+    const ptmd_f4* Lv = L + (size_t)v * 3 * npix;
+    const bool has_prev = v > 0;
+    const ptmd_f4* Lu = has_prev ? L + (size_t)(v - 1) * 3 * npix : nullptr;
+    const ptmd_f4 *prev1 = has_prev ? plane(1, v - 1) : nullptr, *prev2 = has_prev ? plane(2, v - 1) : nullptr;
+    ptmd_f4 *o0 = plane(0, v), *o1 = plane(1, v), *o2 = plane(2, v);
+    auto rows = [&](unsigned t) {
+      for (int y = (int)(((size_t)h * t) / nt), y1 = (int)(((size_t)h * (t + 1)) / nt); y < y1; y++)
+        for (int x = 0; x < w; x++) {
+          const uint32_t idx = (uint32_t)y * (uint32_t)w + (uint32_t)x;
+          const ptmd_f4 Sp = S[(size_t)v * npix + idx], Ap = Lv[npix + idx];
+          ptmd_f4 dp, gp, P1, P2;
+          const int valid = ptmd_prepare(Sp, Lv[idx], Ap, Lv[2 * npix + idx], k.F, k.floor, &dp, &gp);
+          const int accumulates = valid && ptmf_fusable(dp.w, lambertian, n_materials);
+          ptma_own(valid, dp, M[(size_t)v * npix + idx], Ap, k.floor, &P1, &P2);
+          if (accumulates && has_prev) {
+            float X[3], r, wgt;
+            int qx, qy;
+            ptmf_world(&k, &tab[v], x, idx, gp.w, X);
+            if (ptmf_project(&k, &tab[v - 1], X, &qx, &qy, &r)) {
+              const size_t q = (size_t)qy * (size_t)w + (size_t)qx;
+              if (ptma_weight(&k, dp, gp, r, S[(size_t)(v - 1) * npix + q], Lu[q], Lu[npix + q], Lu[2 * npix + q], &wgt)) ptma_take(&ka, wgt, prev1[q], prev2[q], &P1, &P2);
+            }
+          }
+          P2.w = ptma_v0(&ka, valid, P1, P2);
+          o0[idx] = ptma_mean(&k, Sp, Ap, accumulates, P1);
+          o1[idx] = P1;
+          o2[idx] = P2;
+        }
+    };
+    if (nt == 1) rows(0);
+    else if (!run_workers(nt, rows)) return PTMI_ERR_NO_MEMORY;
   }
   return PTMI_OK;
 }

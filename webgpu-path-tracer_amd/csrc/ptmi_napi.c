@@ -54,6 +54,11 @@ FN(ptmi_default_fuse_params)
 FN(ptmi_fuse_views)
 FN(ptmi_read_fused)
 FN(ptmi_release_fused)
+FN(ptmi_default_accumulate_params)
+FN(ptmi_accumulate_views)
+FN(ptmi_read_accumulated)
+FN(ptmi_release_accumulated)
+FN(ptmi_denoise_views_accumulated)
 FN(ptmi_set_view_moments)
 FN(ptmi_read_moments)
 FN(ptmi_release_moments)
@@ -108,7 +113,7 @@ static int load_lib(char* err, size_t errlen) {
   }
   LOAD(ptmi_version) LOAD(ptmi_last_error) LOAD(ptmi_create) LOAD(ptmi_create_multi) LOAD(ptmi_prepare) LOAD(ptmi_destroy) LOAD(ptmi_default_params) LOAD(ptmi_default_denoise_params) LOAD(ptmi_set_params)
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
-  LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_default_guided_params) LOAD(ptmi_denoise_views_guided) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_set_view_moments) LOAD(ptmi_read_moments) LOAD(ptmi_release_moments) LOAD(ptmi_default_noise_params) LOAD(ptmi_view_noise_stats) LOAD(ptmi_render_views_until) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
+  LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_default_guided_params) LOAD(ptmi_denoise_views_guided) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_default_accumulate_params) LOAD(ptmi_accumulate_views) LOAD(ptmi_read_accumulated) LOAD(ptmi_release_accumulated) LOAD(ptmi_denoise_views_accumulated) LOAD(ptmi_set_view_moments) LOAD(ptmi_read_moments) LOAD(ptmi_release_moments) LOAD(ptmi_default_noise_params) LOAD(ptmi_view_noise_stats) LOAD(ptmi_render_views_until) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
   LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah)
   LOAD(ptmi_obj_parse) LOAD(ptmi_free) LOAD(ptmi_device_count) LOAD(ptmi_reduce_info)
   return 0;
@@ -659,6 +664,88 @@ static napi_value js_fuse_views(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* accumulateViews(ctx, views, frameNum, firstView, nViews, resume, params | null): ptmi_accumulate_views — views holds the matrices of ALL views of the stack; params =
+ * {maxHistory, minFrames, sigmaNormal, sigmaDepth, albedoFloor}, every field optional (ptmi_default_accumulate_params fills the rest) */
+static napi_value js_accumulate_views(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (get_args(env, info, 7, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  void* data;
+  size_t len;
+  if (typed(env, a[1], napi_float32_array, "accumulateViews(views)", &data, &len)) return NULL;
+  if (len == 0 || len % 16 != 0) {
+    napi_throw_range_error(env, NULL, "accumulateViews: views must hold 16 floats for each view of the stack, one view at least");
+    return NULL;
+  }
+  double frame_num;
+  uint32_t first, n_views;
+  CHECK_NAPI(napi_get_value_double(env, a[2], &frame_num));
+  CHECK_NAPI(napi_get_value_uint32(env, a[3], &first));
+  CHECK_NAPI(napi_get_value_uint32(env, a[4], &n_views));
+  if ((uint64_t)first + n_views > len / 16) {
+    napi_throw_range_error(env, NULL, "accumulateViews: views must hold the matrices of all views of the stack");
+    return NULL;
+  }
+  bool resume = false;
+  napi_coerce_to_bool(env, a[5], &a[5]);
+  napi_get_value_bool(env, a[5], &resume);
+  ptmi_accumulate_params P;
+  p_ptmi_default_accumulate_params(&P);
+  static const param_field fields[] = {{"minFrames", 1, offsetof(ptmi_accumulate_params, min_frames)},
+                                       {"maxHistory", 0, offsetof(ptmi_accumulate_params, max_history)},
+                                       {"sigmaNormal", 0, offsetof(ptmi_accumulate_params, sigma_normal)},
+                                       {"sigmaDepth", 0, offsetof(ptmi_accumulate_params, sigma_depth)},
+                                       {"albedoFloor", 0, offsetof(ptmi_accumulate_params, albedo_floor)}};
+  CHECK_PARAMS(a[6], fields, &P, "accumulateViews")
+  int st = p_ptmi_accumulate_views(c, &P, (const float*)data, (float)frame_num, first, n_views, resume ? 1 : 0);
+  if (st) return throw_status(env, c, st, "ptmi_accumulate_views");
+  return NULL;
+}
+
+/* readAccumulated(ctx, view, plane, Float32Array out): image `view` of plane `plane` (0 .. 2) of the accumulated stack */
+static napi_value js_read_accumulated(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (get_args(env, info, 4, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  uint32_t view;
+  int32_t plane;
+  CHECK_NAPI(napi_get_value_uint32(env, a[1], &view));
+  CHECK_NAPI(napi_get_value_int32(env, a[2], &plane));
+  void* data;
+  size_t len;
+  if (typed(env, a[3], napi_float32_array, "readAccumulated(out)", &data, &len)) return NULL;
+  int st = p_ptmi_read_accumulated(c, view, plane, (float*)data, len * 4);
+  if (st) return throw_status(env, c, st, "ptmi_read_accumulated");
+  return a[3];
+}
+static napi_value js_release_accumulated(napi_env env, napi_callback_info info) { return release_stack_common(env, info, p_ptmi_release_accumulated, "ptmi_release_accumulated"); }
+
+/* denoiseViewsAccumulated(ctx, firstView, nViews, params | null): ptmi_denoise_views_accumulated — params as denoiseViewsGuided's (minFrames is not read) */
+static napi_value js_denoise_views_accumulated(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (get_args(env, info, 4, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  uint32_t first, n_views;
+  CHECK_NAPI(napi_get_value_uint32(env, a[1], &first));
+  CHECK_NAPI(napi_get_value_uint32(env, a[2], &n_views));
+  ptmi_guided_params P;
+  p_ptmi_default_guided_params(&P);
+  static const param_field fields[] = {{"levels", 1, offsetof(ptmi_guided_params, levels)},
+                                       {"minFrames", 1, offsetof(ptmi_guided_params, min_frames)},
+                                       {"sigmaNormal", 0, offsetof(ptmi_guided_params, sigma_normal)},
+                                       {"sigmaDepth", 0, offsetof(ptmi_guided_params, sigma_depth)},
+                                       {"sigmaLuma", 0, offsetof(ptmi_guided_params, sigma_luma)},
+                                       {"albedoFloor", 0, offsetof(ptmi_guided_params, albedo_floor)},
+                                       {"varEps", 0, offsetof(ptmi_guided_params, var_eps)}};
+  CHECK_PARAMS(a[3], fields, &P, "denoiseViewsAccumulated")
+  int st = p_ptmi_denoise_views_accumulated(c, &P, first, n_views);
+  if (st) return throw_status(env, c, st, "ptmi_denoise_views_accumulated");
+  return NULL;
+}
+
 /* setViewMoments(ctx, on): ptmi_set_view_moments — while on, renderViews also folds the frames' squared colours into the moment stack */
 static napi_value js_set_view_moments(napi_env env, napi_callback_info info) {
   napi_value a[2];
@@ -1045,7 +1132,7 @@ static napi_value init(napi_env env, napi_value exports) {
   } fns[] = {
       {"version", js_version}, {"create", js_create}, {"destroy", js_destroy}, {"defaultParams", js_default_params}, {"setParams", js_set_params},
       {"upload", js_upload}, {"resize", js_resize}, {"clear", js_clear}, {"setShard", js_set_shard}, {"renderFrame", js_render_frame},
-      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"denoiseViewsGuided", js_denoise_views_guided}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
+      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"denoiseViewsGuided", js_denoise_views_guided}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"accumulateViews", js_accumulate_views}, {"readAccumulated", js_read_accumulated}, {"releaseAccumulated", js_release_accumulated}, {"denoiseViewsAccumulated", js_denoise_views_accumulated}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
       {"resolveRGBA8", js_resolve}, {"setCounters", js_set_counters}, {"setTiming", js_set_timing}, {"stats", js_stats},
       {"resetStats", js_reset_stats}, {"buildBVH", js_build_bvh}, {"buildBVHSAH", js_build_bvh_sah}, {"buildBVHDevice", js_build_bvh_device}, {"parseObj", js_parse_obj},
       {"deviceCount", js_device_count}, {"reduceInfo", js_reduce_info},

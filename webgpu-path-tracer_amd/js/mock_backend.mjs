@@ -18,6 +18,10 @@ export class MockBackend {
   fuseViews(views, frameNum, source, firstView, nViews, params = null) { this.calls.push(['fuseViews', views.length / 16, frameNum, source, firstView, nViews, params]); }
   readFused(view, out) { this.calls.push(['readFused', view]); return out || new Float32Array(this.width * this.height * 4); }
   releaseFused() { this.calls.push(['releaseFused']); }
+  accumulateViews(views, frameNum, firstView, nViews, resume = false, params = null) { this.calls.push(['accumulateViews', views.length / 16, frameNum, firstView, nViews, !!resume, params]); }
+  readAccumulated(view, plane, out) { this.calls.push(['readAccumulated', view, plane]); return out || new Float32Array(this.width * this.height * 4); }
+  releaseAccumulated() { this.calls.push(['releaseAccumulated']); }
+  denoiseViewsAccumulated(firstView, nViews, params = null) { this.calls.push(['denoiseViewsAccumulated', firstView, nViews, params]); }
   setViewMoments(on = true) { this.calls.push(['setViewMoments', on]); }
   readMoments(view, out) { this.calls.push(['readMoments', view]); return out || new Float32Array(this.width * this.height * 4); }
   releaseMoments() { this.calls.push(['releaseMoments']); }

@@ -56,6 +56,14 @@ export class Ptmi {
   fuseViews(views, frameNum, source, firstView, nViews, params = null) { this.native.fuseViews(this.h, views, frameNum, source, firstView, nViews, params); }
   readFused(view, out = new Float32Array(this.width * this.height * 4)) { return this.native.readFused(this.h, view, out); }
   releaseFused() { this.native.releaseFused(this.h); }
+  // Temporal accumulation (ptmi_accumulate_views): views [firstView, firstView + nViews) of the camera path, each on its predecessor, into the accumulated stack —
+  // plane 0 mean radiance, plane 1 (D, n), plane 2 (Q, v0); views = the matrices of ALL views of the stack; resume: view firstView takes its history from view
+  // firstView - 1 of the stack as it is; params = {maxHistory, minFrames, sigmaNormal, sigmaDepth, albedoFloor}, all optional.  setViewMoments must have been on
+  // while the views were rendered.  denoiseViewsAccumulated: the guided filter on it, whose plane 2 brings the initial variance; writes the denoised stack.
+  accumulateViews(views, frameNum, firstView, nViews, resume = false, params = null) { this.native.accumulateViews(this.h, views, frameNum, firstView, nViews, resume, params); }
+  readAccumulated(view, plane, out = new Float32Array(this.width * this.height * 4)) { return this.native.readAccumulated(this.h, view, plane, out); }
+  releaseAccumulated() { this.native.releaseAccumulated(this.h); }
+  denoiseViewsAccumulated(firstView, nViews, params = null) { this.native.denoiseViewsAccumulated(this.h, firstView, nViews, params); }
   // Second moments and noise (ptmi_set_view_moments ...): while on, renderViews also folds the frames' squared colours (xyz) and their count (w) into the moment stack;
   // viewNoise gives per view {counted, sumQ, above, maxQ} of the pixels' relative standard error in 16.16 fixed point — mean noise = sumQ / counted / 65536;
   // renderViewsUntil renders rounds of framesPerRound frames per view until every view's mean noise is at most target or maxFrames are done:

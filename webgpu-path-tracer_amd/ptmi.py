@@ -27,6 +27,9 @@ SYMBOLS = [
     "ptmi_default_guided_params", "ptmi_denoise_views_guided", "ptmi_denoise_images_guided", "ptmi_denoise_guided_reference",
     "ptmi_default_fuse_params", "ptmi_fuse_views", "ptmi_read_fused", "ptmi_resolve_fused_rgba8", "ptmi_fused_device_ptr", "ptmi_release_fused",
     "ptmi_fuse_images", "ptmi_fuse_reference",
+    "ptmi_default_accumulate_params", "ptmi_accumulate_views", "ptmi_read_accumulated", "ptmi_resolve_accumulated_rgba8", "ptmi_accumulated_device_ptr",
+    "ptmi_release_accumulated", "ptmi_accumulate_images", "ptmi_accumulate_reference",
+    "ptmi_denoise_views_accumulated", "ptmi_denoise_images_accumulated", "ptmi_denoise_accumulated_reference",
     "ptmi_set_view_moments", "ptmi_read_moments", "ptmi_moments_device_ptr", "ptmi_release_moments",
     "ptmi_default_noise_params", "ptmi_view_noise_stats", "ptmi_noise_images", "ptmi_noise_reference", "ptmi_render_views_until",
 ]
@@ -57,6 +60,13 @@ class GuidedParams(ctypes.Structure):
 class FuseParams(ctypes.Structure):
     _fields_ = [
         ("radius", ctypes.c_int32), ("sigma_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float), ("albedo_floor", ctypes.c_float), ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
+class AccumulateParams(ctypes.Structure):
+    _fields_ = [
+        ("max_history", ctypes.c_float), ("min_frames", ctypes.c_int32), ("sigma_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float),
+        ("albedo_floor", ctypes.c_float), ("reserved", ctypes.c_int32 * 3),
     ]
 
 
@@ -208,6 +218,20 @@ def load_library(build=False, path=None):
         L.ptmi_release_fused.argtypes = [vp]
         L.ptmi_fuse_images.argtypes = [vp, fp, fp, fp, i32, i32, u32, ctypes.c_float, ctypes.c_float, fp, u32, up, fp]
         L.ptmi_fuse_reference.argtypes = [fp, fp, fp, i32, i32, u32, ctypes.c_float, ctypes.c_float, fp, u32, up, fp]
+    if hasattr(L, "ptmi_accumulate_views"):  # (an older A/B build loaded through PTMI_LIB has no temporal accumulation)
+        ap, gp = ctypes.POINTER(AccumulateParams), ctypes.POINTER(GuidedParams)
+        L.ptmi_default_accumulate_params.argtypes = [ap]
+        L.ptmi_default_accumulate_params.restype = None
+        L.ptmi_accumulate_views.argtypes = [vp, ap, fp, ctypes.c_float, u32, u32, i32]
+        L.ptmi_read_accumulated.argtypes = [vp, u32, i32, fp, sz]
+        L.ptmi_resolve_accumulated_rgba8.argtypes = [vp, u32, fp, sz]
+        L.ptmi_accumulated_device_ptr.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(u32)]
+        L.ptmi_release_accumulated.argtypes = [vp]
+        L.ptmi_accumulate_images.argtypes = [vp, fp, fp, fp, fp, i32, i32, u32, ctypes.c_float, ctypes.c_float, fp, u32, ap, fp, fp]
+        L.ptmi_accumulate_reference.argtypes = [fp, fp, fp, fp, i32, i32, u32, ctypes.c_float, ctypes.c_float, fp, u32, ap, fp, fp, i32]
+        L.ptmi_denoise_views_accumulated.argtypes = [vp, gp, u32, u32]
+        L.ptmi_denoise_images_accumulated.argtypes = [vp, fp, fp, fp, i32, i32, u32, gp, fp, fp]
+        L.ptmi_denoise_accumulated_reference.argtypes = [fp, fp, fp, i32, i32, u32, gp, fp, fp, i32]
     if hasattr(L, "ptmi_set_view_moments"):  # (an older A/B build loaded through PTMI_LIB keeps no second moments)
         qp = ctypes.POINTER(NoiseParams)
         L.ptmi_set_view_moments.argtypes = [vp, i32]
@@ -326,6 +350,47 @@ def fuse_reference(colour, layers, views, frame_num, fov_degrees=60.0, lambertia
     if st != 0:
         raise PtmiError(st, "ptmi_fuse_reference failed")
     return out
+
+
+def default_accumulate_params(lib=None, **kw):
+    """ptmi_default_accumulate_params (max_history 32, min_frames 4, sigma_normal 0.25, sigma_depth 0.1, albedo_floor 1e-3) with fields replaced by keyword."""
+    p = AccumulateParams()
+    (lib or load_library()).ptmi_default_accumulate_params(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _accumulate_arrays(colour_sums, moments, layers, views, lambertian, history):
+    c, l, v, t, _ = _fuse_arrays(colour_sums, layers, views, lambertian)
+    m = np.ascontiguousarray(moments, np.float32).reshape(c.shape)
+    hist = None if history is None else np.ascontiguousarray(history, np.float32).reshape((2,) + c.shape[1:])
+    return c, m, l, v, t, hist, np.empty((3,) + c.shape, np.float32)
+
+
+def accumulate_reference(colour_sums, moments, layers, views, frame_num, fov_degrees=60.0, lambertian=None, params=None, history=None, threads=1, lib=None):
+    """ptmi_accumulate_reference: the temporal accumulation of Context.accumulate_views on host arrays, on the CPU (no GPU needed) — colour_sums and moments
+    (n, H, W, 4) as Context.read_view and Context.read_moments give them, layers (n, 3, H, W, 4), views (n, 16); lambertian: one truth value per material index
+    (None: every material accumulates).  history (2, H, W, 4): planes 1 and 2 that image 0 is taken to hold — image 0 is then the view before the first accumulated
+    one (see ptmi_accumulate_images).  Returns (3, n, H, W, 4): the planes of the accumulated stack, the kernel's bits."""
+    c, m, l, v, t, hist, out = _accumulate_arrays(colour_sums, moments, layers, views, lambertian, history)
+    st = (lib or load_library()).ptmi_accumulate_reference(_ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], float(frame_num), float(fov_degrees),
+                                                           None if t is None else _ptr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params),
+                                                           None if hist is None else _ptr(hist), _ptr(out), int(threads))
+    if st != 0:
+        raise PtmiError(st, "ptmi_accumulate_reference failed")
+    return out
+
+
+def denoise_accumulated_reference(means, plane2, layers, params=None, want_var=False, threads=1, lib=None):
+    """ptmi_denoise_accumulated_reference: the guided filter of Context.denoise_views_accumulated on host arrays, on the CPU (no GPU needed) — means and plane2
+    (n, H, W, 4): planes 0 and 2 of an accumulated stack; layers (n, 3, H, W, 4).  Returns what denoise_guided_reference returns."""
+    c, p2, l, out, var = _guided_arrays(means, plane2, layers, want_var)
+    st = (lib or load_library()).ptmi_denoise_accumulated_reference(_ptr(c), _ptr(p2), _ptr(l), c.shape[2], c.shape[1], c.shape[0], None if params is None else ctypes.byref(params),
+                                                                    _ptr(out), None if var is None else _ptr(var), int(threads))
+    if st != 0:
+        raise PtmiError(st, "ptmi_denoise_accumulated_reference failed")
+    return (out, var) if want_var else out
 
 
 def default_noise_params(lib=None, **kw):
@@ -615,6 +680,56 @@ class Context:
         self._ck(self.lib.ptmi_fuse_images(self.h, _ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], float(frame_num), float(fov_degrees),
                                            None if t is None else _ptr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params), _ptr(out)))
         return out
+
+    def accumulate_views(self, views, frame_num=1.0, first_view=0, n_views=None, resume=False, params=None):
+        """ptmi_accumulate_views: accumulates views [first_view, first_view + n_views) of the camera path, each on its predecessor, into the context's accumulated
+        stack.  `views`: (V, 16), the matrices of ALL views of the stack, whose images sum `frame_num` frames; resume: view first_view takes its history from view
+        first_view - 1 of the stack as it is.  params: AccumulateParams (default_accumulate_params).  n_views=None: up to the end of the stack.  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        n_stack = self.views_device_ptr()[2]
+        assert v.shape[0] == n_stack, "views: the matrices of all %d views of the stack" % n_stack
+        if n_views is None:
+            n_views = n_stack - first_view
+        self._ck(self.lib.ptmi_accumulate_views(self.h, None if params is None else ctypes.byref(params), _ptr(v), float(frame_num), first_view, n_views, 1 if resume else 0))
+
+    def read_accumulated(self, view, plane=None):
+        """Plane `plane` of view `view` of the accumulated stack as (H, W, 4) float32 — 0: mean radiance, 1: (D, n), 2: (Q, v0) — or, with plane=None, all three as
+        (3, H, W, 4)."""
+        if plane is not None:
+            return self._read_image(self.lib.ptmi_read_accumulated, view, plane)
+        return np.stack([self._read_image(self.lib.ptmi_read_accumulated, view, p) for p in range(3)])
+
+    def resolve_accumulated_rgba8(self, view):
+        return self._resolve_image(self.lib.ptmi_resolve_accumulated_rgba8, view)
+
+    def accumulated_device_ptr(self):
+        """(device pointer, bytes, n_views) of the accumulated stack: one contiguous [3][n_views][H][W][4] float32 array."""
+        return self._device_ptr(self.lib.ptmi_accumulated_device_ptr)
+
+    def release_accumulated(self):
+        self._ck(self.lib.ptmi_release_accumulated(self.h))
+
+    def accumulate_images(self, colour_sums, moments, layers, views, frame_num, fov_degrees=60.0, lambertian=None, params=None, history=None):
+        """ptmi_accumulate_images: the kernel of accumulate_views on host arrays of any size (see accumulate_reference for the shapes); synchronous."""
+        c, m, l, v, t, hist, out = _accumulate_arrays(colour_sums, moments, layers, views, lambertian, history)
+        self._ck(self.lib.ptmi_accumulate_images(self.h, _ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], float(frame_num), float(fov_degrees),
+                                                 None if t is None else _ptr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params),
+                                                 None if hist is None else _ptr(hist), _ptr(out)))
+        return out
+
+    def denoise_views_accumulated(self, first_view=0, n_views=None, params=None):
+        """ptmi_denoise_views_accumulated: the variance-guided filter on images [first_view, first_view + n_views) of the accumulated stack, whose plane 2 brings the
+        initial variance; writes the denoised stack.  params: GuidedParams.  n_views=None: up to the end of the stack.  Asynchronous."""
+        if n_views is None:
+            n_views = self.accumulated_device_ptr()[2] - first_view
+        self._ck(self.lib.ptmi_denoise_views_accumulated(self.h, None if params is None else ctypes.byref(params), first_view, n_views))
+
+    def denoise_images_accumulated(self, means, plane2, layers, params=None, want_var=False):
+        """ptmi_denoise_images_accumulated: the kernels of denoise_views_accumulated on host arrays of any size (see denoise_accumulated_reference); synchronous."""
+        c, p2, l, out, var = _guided_arrays(means, plane2, layers, want_var)
+        self._ck(self.lib.ptmi_denoise_images_accumulated(self.h, _ptr(c), _ptr(p2), _ptr(l), c.shape[2], c.shape[1], c.shape[0], None if params is None else ctypes.byref(params),
+                                                          _ptr(out), None if var is None else _ptr(var)))
+        return (out, var) if want_var else out
 
     def set_view_moments(self, on=True):
         """ptmi_set_view_moments: while on, render_views also folds the frames' squared colours into the context's moment stack (read_moments); off frees it."""
