@@ -550,6 +550,45 @@ int ptmi_noise_images(ptmi_ctx* ctx, const float* colour_sums, const float* mome
 int ptmi_render_views_until(ptmi_ctx* ctx, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t frames_per_round, uint32_t max_frames,
                             const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out);
 
+/* PER-VIEW FRAME NUMBERS AND COUNTS.  ptmi_render_views with a frame range of its own for every view: view v is rendered for frameNum = first_frames[v] ..
+ * first_frames[v] + frame_counts[v] - 1 (u32 arithmetic; a number reaches the seed as u32(f32(n)), as everywhere), and its frames are folded in frame order into image v
+ * of the view stack — and of the moment stack while moments are on.  Image v is bit for bit what ptmi_clear_framebuffer + ptmi_render(view v, first_frames[v],
+ * frame_counts[v]) + ptmi_read_framebuffer give.  frame_counts[v] == 0 is allowed: that view has no frame slot, and its images in both stacks are neither read nor
+ * written, with reset != 0 as well; at least one count must be non-zero.  reset is ptmi_render_views', per view: with reset != 0 a view's first frame OF THIS CALL
+ * overwrites its image, with reset == 0 the frames are added to what the image holds — for a view whose first frames come in a reset == 0 call that is the zeroes the
+ * stack was allocated with, as with ptmi_render_views.  A view's frames split over calls that pass reset only on the first, or over wavefront batches
+ * (ptmi_params.frames_in_flight), leave the same bits.  With all first_frames equal and all counts equal the stacks and every ptmi_stats counter are
+ * ptmi_render_views'.  The call's frame slots are packed — sum(frame_counts) of them, view after view — and frames_in_flight, the halving on PTMI_ERR_NO_MEMORY and the
+ * placement search act on them as on ptmi_render_views' n_views * frames_per_view.  The kernels find a slot's view and frame number in a table the call uploads with
+ * the views (ptmi_view_slot_plan, below); everything that can fail for want of memory — the stacks, the table — is allocated before anything is enqueued, and a failing
+ * call leaves the stacks as it found them.  PTMI_ERR_INVALID_ARG: a null array, n_views == 0, all counts zero, sum(frame_counts) >= 2^31, or a table of more than
+ * PTMI_VIEW_SLOT_TABLE_MAX_WORDS words.
+ * THE CONSUMERS of the stacks (ptmi_denoise_views*, ptmi_fuse_views, ptmi_accumulate_views, ptmi_resolve_view_rgba8) take ONE frame_num per call and a view range:
+ * views of equal count, however their frame numbers differ, go through them as before; a caller whose counts differ passes them runs of views of equal count. */
+int ptmi_render_views_frames(ptmi_ctx* ctx, const float* views16, uint32_t n_views, const uint32_t* first_frames, const uint32_t* frame_counts, int reset);
+/* ptmi_render_aov with ptmi_render_views_frames' numbering: view v's layers 0 and 1 sum its frames first_frames[v] .. + frame_counts[v] - 1 in frame order, layer 2
+ * keeps the view's last frame of the call; a view with count 0 is neither read nor written.  Arguments and errors as ptmi_render_views_frames. */
+int ptmi_render_aov_frames(ptmi_ctx* ctx, const float* views16, uint32_t n_views, const uint32_t* first_frames, const uint32_t* frame_counts, int reset);
+/* ptmi_render_views_until view by view: round r gives every view that has not yet met the target min(frames_per_round, max_frames - frames_done[v]) more frames,
+ * numbered from first_frames[v] + frames_done[v] (first_frames == NULL: 0 for every view), in ONE ptmi_render_views_frames call — reset in round 0, count 0 for the
+ * views that are done — then takes ptmi_view_noise_stats of all views.  A view is done after the first round in which it has counted > 0 and
+ * (double)sum_q <= (double)target * 65536.0 * (double)counted, and stays done; the call returns when every view is done or has reached max_frames.  frames_done[v]
+ * receives the frames view v then sums (n_views entries), out, where not NULL, the records last taken.  The stacks then hold exactly what one
+ * ptmi_render_views_frames(first_frames, frames_done, reset != 0) leaves.  Errors as ptmi_render_views_until. */
+int ptmi_render_views_until_each(ptmi_ctx* ctx, const float* views16, uint32_t n_views, const uint32_t* first_frames, uint32_t frames_per_round, uint32_t max_frames,
+                                 const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out);
+
+/* Test hook, no GPU: the SLOT TABLE ptmi_render_views_frames and ptmi_render_aov_frames upload behind the call's view matrices, u32 words:
+ *   words [4 v .. 4 v + 3], v < n_views   view v's record {first slot, frame count, first frame number, next view with a non-zero count or n_views}; a view with
+ *                                         count 0 has the first slot of the view that follows it (n_slots behind the last)
+ *   word  [4 n_views + s], s < n_slots    the view of slot s; the slots are packed in view order, n_slots = sum(frame_counts)
+ * Slot s of view v is frame number first_frames[v] + (s - first slot), the view's first slot of the call where s == first slot and its last where
+ * s + 1 == first slot + count.  table == NULL asks for the size alone; otherwise table_words must be at least 4 n_views + n_slots.  *n_slots, where not NULL, receives
+ * the sum.  PTMI_ERR_INVALID_ARG: null arrays, n_views == 0, all counts zero, a sum >= 2^31, 4 n_views + n_slots > PTMI_VIEW_SLOT_TABLE_MAX_WORDS (64 MiB of table), a
+ * table too small; nothing is written then. */
+#define PTMI_VIEW_SLOT_TABLE_MAX_WORDS (1u << 24)
+int ptmi_view_slot_plan(uint32_t n_views, const uint32_t* first_frames, const uint32_t* frame_counts, uint32_t* table, size_t table_words, uint32_t* n_slots);
+
 int ptmi_synchronize(ptmi_ctx* ctx);
 
 /* Validates the uploaded buffers and builds the device-side digests now instead of inside the first render call

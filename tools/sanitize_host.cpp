@@ -1,4 +1,4 @@
-// Sanitizer driver for the host natives of libptmi (ptmi_host.cpp): both BVH builders (1 thread vs many), the OBJ parser, cross-view fusion, temporal accumulation, the noise statistic and the variance-guided filter.
+// Sanitizer driver for the host natives of libptmi (ptmi_host.cpp): both BVH builders (1 thread vs many), the OBJ parser, cross-view fusion, temporal accumulation, the noise statistic, the variance-guided filter and the slot plan of ptmi_render_views_frames.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -pthread tools/sanitize_host.cpp webgpu-path-tracer_amd/csrc/ptmi_host.cpp -o /tmp/san/asan && /tmp/san/asan
 //   g++ -std=c++17 -O1 -g -fsanitize=thread -pthread ... -o /tmp/san/tsan && /tmp/san/tsan
 #include <cmath>
@@ -150,6 +150,30 @@ int main() {
     if (ptmi_denoise_guided_reference(S.data(), M.data(), L.data(), w, h, n, 4.0f, nullptr, out.data(), nullptr)) return 14;
     P.min_frames = 1;
     if (ptmi_denoise_guided_reference(S.data(), M.data(), L.data(), w, h, n, 4.0f, &P, out.data(), nullptr) != PTMI_ERR_INVALID_ARG) return 15;
+  }
+  {  // ptmi_view_slot_plan on the shapes of tests/test_view_frames_cpu.py: tables of exactly the size it asks for (a word more written would be caught), its errors
+    const std::vector<std::vector<uint32_t>> shapes = {{3, 0, 1, 5, 2}, {0, 0, 4}, {4, 0, 0}, {1}, {20, 1, 1, 17}, std::vector<uint32_t>(40, 1u)};
+    for (const auto& counts : shapes) {
+      const uint32_t n = (uint32_t)counts.size();
+      std::vector<uint32_t> firsts(n);
+      for (uint32_t v = 0; v < n; v++) firsts[v] = v % 7 == 0 ? 16777217u + 2u * v : (137u * v * v + 900u * (v % 2)) % 1000u;
+      uint32_t slots = 0;
+      if (ptmi_view_slot_plan(n, firsts.data(), counts.data(), nullptr, 0, &slots)) return 21;
+      std::vector<uint32_t> table(4 * (size_t)n + slots);
+      if (ptmi_view_slot_plan(n, firsts.data(), counts.data(), table.data(), table.size(), nullptr)) return 22;
+      uint32_t s = 0;
+      for (uint32_t v = 0; v < n; v++) {
+        if (table[4 * v] != s || table[4 * v + 1] != counts[v] || table[4 * v + 2] != firsts[v]) return 23;
+        for (uint32_t k = 0; k < counts[v]; k++)
+          if (table[4 * (size_t)n + s++] != v) return 24;
+      }
+      if (s != slots || ptmi_view_slot_plan(n, firsts.data(), counts.data(), table.data(), table.size() - 1, nullptr) != PTMI_ERR_INVALID_ARG) return 25;
+    }
+    const uint32_t zero[3] = {0, 0, 0}, big[2] = {0x7fffffffu, 1u}, wide[2] = {PTMI_VIEW_SLOT_TABLE_MAX_WORDS - 8u, 1u};
+    uint32_t one[1] = {0};
+    if (ptmi_view_slot_plan(3, zero, zero, one, 1, nullptr) != PTMI_ERR_INVALID_ARG || ptmi_view_slot_plan(2, zero, big, one, 1, nullptr) != PTMI_ERR_INVALID_ARG ||
+        ptmi_view_slot_plan(2, zero, wide, one, 1, nullptr) != PTMI_ERR_INVALID_ARG || ptmi_view_slot_plan(2, nullptr, big, one, 1, nullptr) != PTMI_ERR_INVALID_ARG || one[0] != 0)
+      return 26;
   }
   puts("host natives: sanitizer run clean");
   return 0;

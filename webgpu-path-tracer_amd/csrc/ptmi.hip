@@ -705,15 +705,27 @@ constexpr auto tail_kernel() {
 }
 // The same choices for a multi-view batch (ptmi_render_views): the k_*_views kernels take the batch's ViewTab as one more argument, so they are picked by
 // dispatch calls of their own and the kernels of a batch with one view keep their signatures — and their code, instruction for instruction.
-template <bool IS, bool SORT, bool COUNT, bool MULTI>
+// TAB: the batch's views have frame numbers and counts of their own (ptmi_render_views_frames) — the k_*_frames kernels, which take the same arguments and find a
+// slot's view in the slot table behind the ViewTab's rows instead of dividing.
+template <bool TAB, bool IS, bool SORT, bool COUNT, bool MULTI>
 constexpr auto shade_views_kernel() {
-  if constexpr (!IS && !MULTI) return &k_shade6_views<SORT, COUNT>;
-  else return &k_shade_views<IS, SORT, COUNT, MULTI>;
+  if constexpr (TAB) {
+    if constexpr (!IS && !MULTI) return &k_shade6_frames<SORT, COUNT>;
+    else return &k_shade_frames<IS, SORT, COUNT, MULTI>;
+  } else {
+    if constexpr (!IS && !MULTI) return &k_shade6_views<SORT, COUNT>;
+    else return &k_shade_views<IS, SORT, COUNT, MULTI>;
+  }
 }
-template <bool SIX, bool IS, bool COUNT, bool MULTI, bool NOABORT>
+template <bool TAB, bool SIX, bool IS, bool COUNT, bool MULTI, bool NOABORT>
 constexpr auto tail_views_kernel() {
-  if constexpr (SIX) return &k_tail6_views<COUNT, NOABORT>;
-  else return &k_tail_views<IS, COUNT, MULTI, NOABORT>;
+  if constexpr (TAB) {
+    if constexpr (SIX) return &k_tail6_frames<COUNT, NOABORT>;
+    else return &k_tail_frames<IS, COUNT, MULTI, NOABORT>;
+  } else {
+    if constexpr (SIX) return &k_tail6_views<COUNT, NOABORT>;
+    else return &k_tail_views<IS, COUNT, MULTI, NOABORT>;
+  }
 }
 
 int stack_alloc_for(const ptmi_ctx* c) { return std::max(1, std::min(c->prm.stack_size, std::max(c->bvh_depth, 1))); }
@@ -758,9 +770,9 @@ void load_tuning(ptmi_ctx* c) { c->tun = load_tuning_env(); }  // (every value i
 
 // hitScene, part 2 for the step's queue (k_bvh).  Part 1 has already been run by whoever created the rays (k_generate,
 // k_shade); ptmi_trace's rays come from the host, so it asks for k_prims first.
-// `vt`: the batch is a multi-view one (only step 0's launch, `first_rc`, reads the table)
+// `vt`: the batch is a multi-view one (only step 0's launch, `first_rc`, reads the table); `tab`: with a slot table (ptmi_render_views_frames)
 int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_items, bool with_prims, const RenderConst* first_rc = nullptr, const Carry& cy = Carry{},
-                     const ViewTab* vt = nullptr) {
+                     const ViewTab* vt = nullptr, bool tab = false) {
   unsigned long long* tot = c->d_totals.as<unsigned long long>();
   const uint32_t pgrid = std::max<uint32_t>(1, std::min<uint32_t>((max_items + kBlock - 1) / kBlock, (uint32_t)c->num_cus * 32));
   if (with_prims) {
@@ -789,7 +801,10 @@ int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_ite
   float4 cam = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (first_rc) cam = make_float4(first_rc->cam_o[0], first_rc->cam_o[1], first_rc->cam_o[2], 1.0f);
   if (vt && first_rc) {
-    const auto bvh = with_flags([](auto cn, auto na) { return &k_bvh2_views<cn, na>; }, c->counters, st.noabort);
+    const auto bvh = with_flags([](auto tb, auto cn, auto na) {
+      if constexpr (tb) return &k_bvh2_frames<cn, na>;
+      else return &k_bvh2_views<cn, na>;
+    }, tab, c->counters, st.noabort);
     hipLaunchKernelGGL(bvh, dim3(grid), dim3(64), lds, c->stream, c->S, P, ctl, c->d_heads.as<uint32_t>(), n_teams, c->prm.stack_size, st.lds_entries, st.spill_entries,
                        c->d_spill.as<int2>(), tun.refill, tun.leaf_batch, tot, (uint32_t)tun.bvh_range, cam, cy, *vt);
   } else {
@@ -802,7 +817,7 @@ int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_ite
 }
 
 // k_tail in front of a step: traces the step's queue to the end if it is short (at most `limit` slots), else returns at once.  `six`: k_tail6 (tail_plan).
-int launch_tail(ptmi_ctx* c, const RenderConst& rc, const Paths& P, StepCtl* ctl, int first, uint32_t limit, bool six, const Carry& cy_in, const ViewTab* vt) {
+int launch_tail(ptmi_ctx* c, const RenderConst& rc, const Paths& P, StepCtl* ctl, int first, uint32_t limit, bool six, const Carry& cy_in, const ViewTab* vt, bool tab) {
   // On trees of 12 levels and more a walk stops once fewer than tun.tail_park lanes are left in it while other lanes have work; the stragglers' state waits in kParkEntries
   // entries on top of their stacks (park, ptmi_device.h).  Shallow trees never park: their walks are short, and a parked ray's path waits for the next walk (round 4 measured both).
   Carry cy = cy_in;
@@ -813,8 +828,8 @@ int launch_tail(ptmi_ctx* c, const RenderConst& rc, const Paths& P, StepCtl* ctl
   HIP_TRY(c, c->d_spill.ensure(std::max<size_t>(16, (size_t)c->num_cus * 32 * (size_t)st.spill_entries * 64 * sizeof(int2))));  // (k_bvh's grids are no larger: one size for both)
   ScopedSpan sp(c, T_TAIL);
   if (vt) {
-    const auto tail = with_flags([](auto s6, auto is, auto cn, auto mu, auto na) { return tail_views_kernel<s6, is, cn, mu, na>(); }, six, c->prm.importance_sampling != 0,
-                                 c->counters, rc.num_samples > 1, st.noabort);
+    const auto tail = with_flags([](auto tb, auto s6, auto is, auto cn, auto mu, auto na) { return tail_views_kernel<tb, s6, is, cn, mu, na>(); }, tab, six,
+                                 c->prm.importance_sampling != 0, c->counters, rc.num_samples > 1, st.noabort);
     hipLaunchKernelGGL(tail, dim3(grid), dim3(64), st.lds_bytes, c->stream, c->S, rc, P, ctl, c->d_totals.as<unsigned long long>(), first, limit, c->prm.stack_size,
                        st.lds_entries, st.spill_entries, c->d_spill.as<int2>(), cy, *vt);
   } else {
@@ -959,10 +974,13 @@ RenderConst make_render_const(const ptmi_ctx* c, const float* view16, uint32_t f
 
 // A multi-view batch (ptmi_render_views): its n_frames frame slots are slots [vt.slot0, vt.slot0 + n_frames) of the call's views x frames-per-view, every view with the
 // frame numbers frame0 .. frame0 + fpv - 1, and they are folded into the images of `stack` instead of the framebuffer.  `view16` is not used by such a batch's kernels.
+// `tab` (ptmi_render_views_frames): the slots are those of the call's slot table instead, which lies behind vt's rows (vt.n_views in place of vt.fpv), every view with frame
+// numbers and a count of its own; `frame0` is not used then either.  render_batch picks the k_*_frames instances for such a batch wherever it picks k_*_views for the other.
 struct ViewBatch {
   ViewTab vt;
   float4* stack;
   float4* moments;  // the moment stack, or nullptr: moments are off (ptmi_set_view_moments)
+  bool tab = false;
 };
 
 // `fold` = how many of the batch's leading frames are added to the framebuffer now (-1 = all of them); dry_steps > 0: placement_search's timing run
@@ -974,6 +992,7 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   ViewTab vtab{};
   if (views) vtab = views->vt, vtab.n_local = rc.n_local;
   const ViewTab* vt = views ? &vtab : nullptr;
+  const bool tab = views && views->tab;
 
   const int n_steps = rc.num_samples * p.max_bounces;
   const size_t npaths = (size_t)rc.n_local * (size_t)n_frames;
@@ -1008,8 +1027,8 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
 
   const auto shade = with_flags([](auto is, auto so, auto cn, auto mu) { return shade_kernel<is, so, cn, mu>(); }, p.importance_sampling != 0, sort, c->counters,
                                 rc.num_samples > 1);
-  const auto shade_views = with_flags([](auto is, auto so, auto cn, auto mu) { return shade_views_kernel<is, so, cn, mu>(); }, p.importance_sampling != 0, sort, c->counters,
-                                      rc.num_samples > 1);
+  const auto shade_views = with_flags([](auto tb, auto is, auto so, auto cn, auto mu) { return shade_views_kernel<tb, is, so, cn, mu>(); }, tab, p.importance_sampling != 0, sort,
+                                      c->counters, rc.num_samples > 1);
   // k_shade's grid: as many blocks per CU as the instance's registers and LDS admit (the progressive-mode ones need 79 VGPRs since
   // the build dropped the SLP vectoriser: 6 blocks = 6 waves per SIMD; the importance-sampling ones 93: 5) — asked of the runtime once per instance
   int shade_bpc = c->tun.shade_blocks_per_cu;
@@ -1043,7 +1062,10 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     ScopedSpan s(c, T_GENERATE);
     if (rc.num_samples == 1) HIP_TRY(c, hipMemsetAsync(c->d_touched.p, 0, npaths, c->stream));
     if (views) {
-      const auto generate = with_flags([](auto cn) { return &k_generate_views<cn>; }, c->counters);
+      const auto generate = with_flags([](auto tb, auto cn) {
+        if constexpr (tb) return &k_generate_frames<cn>;
+        else return &k_generate_views<cn>;
+      }, tab, c->counters);
       hipLaunchKernelGGL(generate, dim3(ew_grid), dim3(kBlock), 0, c->stream, c->S, rc, paths_of(c, 0, rc.num_samples > 1), ctl, c->d_heads.as<uint32_t>(), tot, vtab);
     } else {
       const auto generate = with_flags([](auto cn) { return &k_generate<cn>; }, c->counters);
@@ -1072,7 +1094,7 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     // (dry runs: k_generate and k_shade only — the kernels whose time depends on where the queue arrays lie; k_bvh reads them sparsely, and on a deep tree it would
     // be nine tenths of the search's time.  Rays that entered the root box are then shaded with what part 1 of hitScene found: other paths, the same access pattern.)
     if (const uint32_t tail_limit = dry_steps > 0 ? 0u : (s == 0 ? tail.limit_first : tail.limit_later)) {
-      int lr = launch_tail(c, rc, P, ctl + s, s == 0 ? 1 : 0, tail_limit, tail.six, carry_of(s), vt);
+      int lr = launch_tail(c, rc, P, ctl + s, s == 0 ? 1 : 0, tail_limit, tail.six, carry_of(s), vt, tab);
       if (lr) return lr;
       // step 0's queue is the whole batch (k_generate fills one slot per path): if that fits the limit k_tail has just been handed all of it —
       // nothing is left for the per-bounce kernels, and a lone frame is three launches instead of 3 x MAX_BOUNCES + 2
@@ -1084,7 +1106,7 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     if (dry_steps == 0) {
       Carry cy = carry_of(s);
       if (!carry || s >= n_steps - c->tun.bvh_carry_last) cy.resv_next = 0u;
-      int lr = launch_intersect(c, P, ctl + s, bound, false, s == 0 ? &rc : nullptr, cy, vt);
+      int lr = launch_intersect(c, P, ctl + s, bound, false, s == 0 ? &rc : nullptr, cy, vt, tab);
       if (lr) return lr;
     }
     {
@@ -1100,13 +1122,17 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   if (carry && !drained && n_steps > 0) {
     // paths that were carried over lag behind the step count: whatever the last k_shade left in the queue (and what the last k_bvh carried) is
     // traced to its end by one k_tail launch — a few thousand paths at most
-    int lr = launch_tail(c, rc, paths_of(c, n_steps, rc.num_samples > 1), ctl + n_steps, 0, 0xffffffffu, tail.six, carry_of(n_steps), vt);
+    int lr = launch_tail(c, rc, paths_of(c, n_steps, rc.num_samples > 1), ctl + n_steps, 0, 0xffffffffu, tail.six, carry_of(n_steps), vt, tab);
     if (lr) return lr;
   }
   {
     ScopedSpan s(c, T_ACCUM);
     const int f_end = fold < 0 ? n_frames : std::min(fold, n_frames);
-    if (views && views->moments)
+    if (tab && views->moments)
+      hipLaunchKernelGGL(k_accumulate_frames<true>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), views->stack, views->moments, n_steps, tot, 0, f_end, vtab);
+    else if (tab)
+      hipLaunchKernelGGL(k_accumulate_frames<false>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), views->stack, (float4*)nullptr, n_steps, tot, 0, f_end, vtab);
+    else if (views && views->moments)
       hipLaunchKernelGGL(k_accumulate_moments, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), views->stack, views->moments, n_steps, tot, 0, f_end, vtab);
     else if (views) hipLaunchKernelGGL(k_accumulate<true>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), views->stack, n_steps, tot, 0, f_end, vtab);
     else hipLaunchKernelGGL(k_accumulate<false>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), c->fb, n_steps, tot, 0, f_end, vtab);
@@ -1943,9 +1969,23 @@ int ptmi_render(ptmi_ctx* c, const float* view16, uint32_t first_frame, uint32_t
 
 // A call's view table (ViewTab: kViewRow float4 per view) for ptmi_render_views and ptmi_render_aov, in two halves so that everything that can fail for want of
 // memory happens before anything is enqueued: stage_view_rows allocates and fills the pinned staging copy, send_view_rows puts the upload on the stream.
-static int stage_view_rows(ptmi_ctx* c, const float* views16, uint32_t n_views) {
+// `frames`: the call's per-view frame ranges (ptmi_render_views_frames, ptmi_render_aov_frames) — their slot table (ptmi_view_slot_plan, already checked by the caller)
+// goes behind the rows, where ViewTab's VK_TAB readers look for it.
+struct ViewFrames {
+  const uint32_t *first_frames, *frame_counts;
+  uint32_t n_slots;  // sum(frame_counts)
+};
+static size_t view_table_bytes(uint32_t n_views, const ViewFrames* frames) {
+  return (size_t)n_views * kViewRow * 16 + (frames ? (4 * (size_t)n_views + frames->n_slots) * 4 : 0);
+}
+static int stage_view_rows(ptmi_ctx* c, const float* views16, uint32_t n_views, const ViewFrames* frames = nullptr) {
   float* rows = nullptr;
-  HIP_TRY(c, c->view_rows.stage((size_t)n_views * kViewRow * 16, c->stream, (void**)&rows));
+  HIP_TRY(c, c->view_rows.stage(view_table_bytes(n_views, frames), c->stream, (void**)&rows));
+  if (frames) {
+    const int pr = ptmi_view_slot_plan(n_views, frames->first_frames, frames->frame_counts, reinterpret_cast<uint32_t*>(rows + (size_t)n_views * kViewRow * 4),
+                                       4 * (size_t)n_views + frames->n_slots, nullptr);
+    if (pr) return fail(c, pr, "internal: the slot table changed between the check and the upload");
+  }
   for (uint32_t v = 0; v < n_views; v++) {
     const float* m = views16 + 16 * (size_t)v;
     float* row = rows + (size_t)v * kViewRow * 4;
@@ -1955,13 +1995,14 @@ static int stage_view_rows(ptmi_ctx* c, const float* views16, uint32_t n_views) 
   }
   return PTMI_OK;
 }
-static int send_view_rows(ptmi_ctx* c, uint32_t n_views) {
-  HIP_TRY(c, c->view_rows.send((size_t)n_views * kViewRow * 16, c->stream));
+static int send_view_rows(ptmi_ctx* c, uint32_t n_views, const ViewFrames* frames = nullptr) {
+  HIP_TRY(c, c->view_rows.send(view_table_bytes(n_views, frames), c->stream));
   return PTMI_OK;
 }
 
 // One device's part of ptmi_render_views: render_one's loop over batches of at most F frame slots, the slots being the call's n_views x frames_per_view.
-static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t fpv, int reset) {
+// `frames` (ptmi_render_views_frames; first_frame and fpv are not used then): the slots are the packed sum(frame_counts) of the call's slot table.
+static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t fpv, int reset, const ViewFrames* frames = nullptr) {
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();  // a stale error of an earlier, already reported failure must not be blamed on this call
   int r = prepare_scene(c);
@@ -1978,24 +2019,24 @@ static int render_views_one(ptmi_ctx* c, const float* views16, uint32_t n_views,
   if (r) return r;
   if (c->view_moments) r = reserve_stack(c, STACK_MOMENTS, n_views, &moments);
   if (r) return r;
-  r = stage_view_rows(c, views16, n_views);
+  r = stage_view_rows(c, views16, n_views, frames);
   if (r) return r;
   r = commit_stack(c, STACK_VIEWS, n_views, &stack);  // (a new view stack takes the old moment stack with it: drop_stack)
   if (r) return r;
   if (c->view_moments) r = commit_stack(c, STACK_MOMENTS, n_views, &moments);
   if (r) return r;
-  r = send_view_rows(c, n_views);
+  r = send_view_rows(c, n_views, frames);
   if (r) return r;
   // (the same budget of frame slots per wavefront pass as render_one's, and the same halving)
   const size_t npix = std::max<size_t>(1, count_local((uint32_t)c->W * (uint32_t)c->H, c->rank, c->world, c->tile));
   uint32_t F = c->prm.frames_in_flight > 0 ? (uint32_t)c->prm.frames_in_flight : (uint32_t)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)1 << c->tun.path_budget_log2) / npix));
   F = (uint32_t)std::min<size_t>(F, std::max<size_t>(1, ((size_t)1 << 31) / npix));
-  const uint32_t n_slots = n_views * fpv;
+  const uint32_t n_slots = frames ? frames->n_slots : n_views * fpv;
   for (uint32_t done = 0; done < n_slots;) {
     const uint32_t nb = std::min(F, n_slots - done);
-    const ViewBatch vb{ViewTab{c->view_rows.dev.as<float4>(), done, fpv, 0u}, c->stacks[STACK_VIEWS].buf.as<float4>(),
-                       c->view_moments ? c->stacks[STACK_MOMENTS].buf.as<float4>() : nullptr};
-    r = render_batch(c, views16 + 16 * (size_t)(done / fpv), first_frame, (int)nb, reset ? 1 : 0, -1, 0, &vb);
+    const ViewBatch vb{ViewTab{c->view_rows.dev.as<float4>(), done, frames ? n_views : fpv, 0u}, c->stacks[STACK_VIEWS].buf.as<float4>(),
+                       c->view_moments ? c->stacks[STACK_MOMENTS].buf.as<float4>() : nullptr, frames != nullptr};
+    r = render_batch(c, frames ? views16 : views16 + 16 * (size_t)(done / fpv), first_frame, (int)nb, reset ? 1 : 0, -1, 0, &vb);
     if (r == PTMI_ERR_NO_MEMORY && !c->batch_enqueued && nb > 1 && c->prm.frames_in_flight <= 0) {
       F = std::max<uint32_t>(1, nb / 2);
       continue;
@@ -2011,6 +2052,20 @@ int ptmi_render_views(ptmi_ctx* c, const float* views16, uint32_t n_views, uint3
   if (n_views == 0 || frames_per_view == 0) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views: need n_views >= 1 and frames_per_view >= 1");
   if ((uint64_t)n_views * frames_per_view > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views: n_views * frames_per_view must stay below 2^31");
   return on_all_devices(c, [=](ptmi_ctx* q) { return render_views_one(q, views16, n_views, first_frame, frames_per_view, reset); }, true);
+}
+
+// The argument checks of the calls with per-view frame ranges; *n_slots: sum(frame_counts)
+static int check_view_frames(ptmi_ctx* c, const char* who, const float* views16, uint32_t n_views, const uint32_t* first_frames, const uint32_t* frame_counts, uint32_t* n_slots) {
+  if (!c || !views16 || !first_frames || !frame_counts) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (ptmi_view_slot_plan(n_views, first_frames, frame_counts, nullptr, 0, n_slots))
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need n_views >= 1, a frame_count that is not 0, sum(frame_counts) < 2^31 and a slot table of at most PTMI_VIEW_SLOT_TABLE_MAX_WORDS words");
+  return PTMI_OK;
+}
+
+int ptmi_render_views_frames(ptmi_ctx* c, const float* views16, uint32_t n_views, const uint32_t* first_frames, const uint32_t* frame_counts, int reset) {
+  ViewFrames vf{first_frames, frame_counts, 0u};
+  if (int r = check_view_frames(c, "ptmi_render_views_frames", views16, n_views, first_frames, frame_counts, &vf.n_slots)) return r;
+  return on_all_devices(c, [=](ptmi_ctx* q) { return render_views_one(q, views16, n_views, 0u, 0u, reset, &vf); }, true);
 }
 
 // ptmi_read_framebuffer / ptmi_read_view / ptmi_read_aov: the image, gathered from the devices of a multi-device context, copied to the host
@@ -2095,7 +2150,7 @@ int ptmi_release_views(ptmi_ctx* c) { return release_stack(c, STACK_VIEWS); }
 
 // ---- the feature stack (ptmi_render_aov) ----
 // One device's part of ptmi_render_aov: the stack and the view table first, then one k_aov launch — one per batch of views where views x owned pixels would reach 2^31.
-static int render_aov_one(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t fpv, int reset) {
+static int render_aov_one(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t fpv, int reset, const ViewFrames* frames = nullptr) {
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();  // a stale error of an earlier, already reported failure must not be blamed on this call
   int r = prepare_scene(c);
@@ -2105,18 +2160,21 @@ static int render_aov_one(ptmi_ctx* c, const float* views16, uint32_t n_views, u
   DBuf stack;
   r = reserve_stack(c, STACK_FEATURES, n_views, &stack);
   if (r) return r;
-  r = stage_view_rows(c, views16, n_views);
+  r = stage_view_rows(c, views16, n_views, frames);
   if (r) return r;
   const RenderConst rc = make_render_const(c, views16, first_frame, (int)fpv, reset ? 1 : 0);
   const StackLayout st = stack_layout(c, 0);
   HIP_TRY(c, c->d_spill.ensure(std::max<size_t>(16, (size_t)c->num_cus * 32 * (size_t)st.spill_entries * 64 * sizeof(int2))));  // (k_bvh's and k_tail's rows: one size for all)
   r = commit_stack(c, STACK_FEATURES, n_views, &stack);
   if (r) return r;
-  r = send_view_rows(c, n_views);
+  r = send_view_rows(c, n_views, frames);
   if (r) return r;
   if (rc.n_local == 0) return PTMI_OK;
-  const ViewTab vt{c->view_rows.dev.as<float4>(), 0u, fpv, rc.n_local};
-  const auto aov = with_flags([](auto na) { return &k_aov<na>; }, st.noabort);
+  const ViewTab vt{c->view_rows.dev.as<float4>(), 0u, frames ? n_views : fpv, rc.n_local};
+  const auto aov = with_flags([](auto tb, auto na) {
+    if constexpr (tb) return &k_aov<na, VK_TAB>;
+    else return &k_aov<na, VK_DIV>;
+  }, frames != nullptr, st.noabort);
   const uint32_t per_launch = std::max<uint32_t>(1u, 0x7fffffffu / rc.n_local);
   for (uint32_t v0 = 0; v0 < n_views; v0 += per_launch) {
     const uint32_t nv = std::min(per_launch, n_views - v0);
@@ -2134,6 +2192,12 @@ int ptmi_render_aov(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_
   if (n_views == 0 || frames_per_view == 0) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_aov: need n_views >= 1 and frames_per_view >= 1");
   if ((uint64_t)n_views * frames_per_view > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_aov: n_views * frames_per_view must stay below 2^31");
   return on_all_devices(c, [=](ptmi_ctx* q) { return render_aov_one(q, views16, n_views, first_frame, frames_per_view, reset); }, true);
+}
+
+int ptmi_render_aov_frames(ptmi_ctx* c, const float* views16, uint32_t n_views, const uint32_t* first_frames, const uint32_t* frame_counts, int reset) {
+  ViewFrames vf{first_frames, frame_counts, 0u};
+  if (int r = check_view_frames(c, "ptmi_render_aov_frames", views16, n_views, first_frames, frame_counts, &vf.n_slots)) return r;
+  return on_all_devices(c, [=](ptmi_ctx* q) { return render_aov_one(q, views16, n_views, 0u, 1u, reset, &vf); }, true);
 }
 
 int ptmi_read_aov(ptmi_ctx* c, uint32_t view, int layer, float* dst, size_t bytes) { return read_stack(c, STACK_FEATURES, "ptmi_read_aov", view, layer, dst, bytes); }
@@ -2795,6 +2859,46 @@ int ptmi_render_views_until(ptmi_ctx* c, const float* views16, uint32_t n_views,
     bool met = true;
     for (uint32_t v = 0; v < n_views && met; v++) met = ptmn_target_met(stats[v].counted, stats[v].sum_q, target);
     if (met) break;
+  }
+  if (out) memcpy(out, stats.data(), (size_t)n_views * sizeof(ptmi_view_noise));
+  return PTMI_OK;
+}
+
+int ptmi_render_views_until_each(ptmi_ctx* c, const float* views16, uint32_t n_views, const uint32_t* first_frames, uint32_t frames_per_round, uint32_t max_frames,
+                                 const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  if (!views16 || !frames_done) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until_each: null argument");
+  if (n_views == 0 || frames_per_round == 0 || max_frames == 0) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until_each: need n_views, frames_per_round and max_frames >= 1");
+  for (uint32_t v = 0; v < n_views; v++) frames_done[v] = 0;
+  if ((uint64_t)n_views * max_frames > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until_each: n_views * max_frames must stay below 2^31");
+  if (!(target >= 0.0f) || !ptmn_finite(target)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until_each: target must be finite and >= 0");
+  ptmi_noise_params P;
+  if (int r = noise_check_args(c, "ptmi_render_views_until_each", params, &P)) return r;
+  if (!c->view_moments) return fail(c, PTMI_ERR_STATE, "ptmi_render_views_until_each: moments are off: call ptmi_set_view_moments first");
+  std::vector<ptmi_view_noise> stats;
+  std::vector<uint32_t> firsts, counts;
+  std::vector<char> met;
+  try {
+    stats.resize(n_views);
+    firsts.resize(n_views);
+    counts.resize(n_views);
+    met.assign(n_views, 0);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_render_views_until_each: no host memory for the records");
+  }
+  for (bool round0 = true;; round0 = false) {
+    uint32_t open = 0;
+    for (uint32_t v = 0; v < n_views; v++) {
+      counts[v] = met[v] ? 0u : std::min(frames_per_round, max_frames - frames_done[v]);
+      firsts[v] = (first_frames ? first_frames[v] : 0u) + frames_done[v];
+      open += counts[v] != 0u;
+    }
+    if (!open) break;
+    if (int r = ptmi_render_views_frames(c, views16, n_views, firsts.data(), counts.data(), round0 ? 1 : 0)) return r;
+    for (uint32_t v = 0; v < n_views; v++) frames_done[v] += counts[v];
+    if (int r = ptmi_view_noise_stats(c, &P, 0, n_views, stats.data())) return r;
+    for (uint32_t v = 0; v < n_views; v++)
+      if (!met[v]) met[v] = ptmn_target_met(stats[v].counted, stats[v].sum_q, target);
   }
   if (out) memcpy(out, stats.data(), (size_t)n_views * sizeof(ptmi_view_noise));
   return PTMI_OK;

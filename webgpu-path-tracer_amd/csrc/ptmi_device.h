@@ -462,11 +462,20 @@ DEV int ldu(const int* p) { return *(const PTMI_CONST_AS int*)(p); }
 // A batch whose frame slots belong to different views.  The call's V views lie in a device table, kViewRow float4 per view: the matrix's four columns, then
 // {cam_origin.xyz, 0} as make_render_const computes it.  Frame slot f of the batch is slot slot0 + f of the call's V * fpv: view (slot0 + f) / fpv, frame number
 // rc.frame0 + (slot0 + f) % fpv.  Only the kernel instances with MV = true read any of this; the others are handed an empty ViewTab and never touch it.
+//
+// The third way to address a batch's views (ptmi_render_views_frames): every view with frame numbers and a frame count of its own, the call's slots packed view after
+// view.  A slot's view and frame number then come from the call's SLOT TABLE (include/ptmi.h, ptmi_view_slot_plan: one 16-byte record per view — first slot, count, first
+// frame number, next view with a frame — and a u32 view per slot), which lies behind the rows in the same allocation; `fpv` is not read, `n_views` says where the table begins.
+// The kernel instances are told apart by their MV template argument:
+enum ViewKind : int { VK_ONE = 0, VK_DIV = 1, VK_TAB = 2 };  // one view in rc / ViewTab's division / the slot table
 constexpr int kViewRow = 5;
 struct ViewTab {
   const float4* rows;
   uint32_t slot0;    // the batch's first frame slot among the call's
-  uint32_t fpv;      // frames per view
+  union {
+    uint32_t fpv;      // VK_DIV: frames per view
+    uint32_t n_views;  // VK_TAB: the call's views — the slot table begins at rows + kViewRow * n_views
+  };
   uint32_t n_local;  // = rc.n_local, for the kernels that are not handed rc (k_bvh)
 };
 struct ViewRow {
@@ -494,13 +503,40 @@ DEV ViewRow load_view_row(const ViewTab& vt, uint32_t v) {
 // The view a slot of STEP 0's queue belongs to (slot = path id = frame_slot * n_local + local pixel), and where its camera ray starts.  Step 0's queue stays
 // 32 bytes per path in a multi-view batch too: its readers look the origin up — two integer divisions by wave-uniform divisors and a 16-byte load that hits a
 // table of a few KB — instead of every path carrying 12 more bytes through HBM.
-DEV uint32_t view_of_path(const ViewTab& vt, uint32_t pid) { return (vt.slot0 + pid / vt.n_local) / vt.fpv; }
-DEV f3 view_origin_of_path(const ViewTab& vt, uint32_t pid) { return mk3(vt.rows[(size_t)kViewRow * view_of_path(vt, pid) + 4]); }
+// VK_TAB: the second division gives way to one 4-byte load from the slot table.
+struct ViewRec {
+  uint32_t first_slot, count, first_frame, next;
+};
+DEV const uint32_t* slot_table(const ViewTab& vt) { return reinterpret_cast<const uint32_t*>(vt.rows + (size_t)kViewRow * vt.n_views); }
+DEV uint32_t view_of_slot(const ViewTab& vt, uint32_t s) { return slot_table(vt)[4u * (size_t)vt.n_views + s]; }
+// ... for a slot the lanes of a wave nearly always agree on (k_generate's chunk, k_accumulate's f_begin): through a scalar load then, as load_view_row's row
+DEV uint32_t view_of_slot_voted(const ViewTab& vt, uint32_t s) {
+  const uint32_t su = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
+  if (__ballot(s != su) == 0ull) return (uint32_t)ldu(reinterpret_cast<const int*>(slot_table(vt)) + 4u * (size_t)vt.n_views + su);
+  return view_of_slot(vt, s);
+}
+// View v's record, the same way (the records lie at float4 alignment behind the rows)
+DEV ViewRec load_view_rec(const ViewTab& vt, uint32_t v) {
+  const float4* recs = vt.rows + (size_t)kViewRow * vt.n_views;
+  const uint32_t vu = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+  const float4 r = __ballot(v != vu) == 0ull ? ldu(recs + vu) : recs[v];
+  return ViewRec{__float_as_uint(r.x), __float_as_uint(r.y), __float_as_uint(r.z), __float_as_uint(r.w)};
+}
+template <int MV>
+DEV uint32_t view_of_path(const ViewTab& vt, uint32_t pid) {
+  if (MV == VK_TAB) return view_of_slot(vt, vt.slot0 + pid / vt.n_local);
+  return (vt.slot0 + pid / vt.n_local) / vt.fpv;
+}
+template <int MV>
+DEV f3 view_origin_of_path(const ViewTab& vt, uint32_t pid) {
+  return mk3(vt.rows[(size_t)kViewRow * view_of_path<MV>(vt, pid) + 4]);
+}
+template <int MV>
 DEV void camera_ray_view(const RenderConst& rc, const ViewTab& vt, uint32_t pid, int k, uint32_t& rng, f3& o, f3& d) {
   float px, py, a, b;
   camera_pixel(rc, local_to_pixel(rc, pid % rc.n_local), px, py);
   camera_plane(rc, px, py, k, rng, a, b);
-  const float4* p = vt.rows + (size_t)kViewRow * view_of_path(vt, pid);
+  const float4* p = vt.rows + (size_t)kViewRow * view_of_path<MV>(vt, pid);
   const ViewRow r = unpack_view_row(p[0], p[1], p[2], p[3], p[4]);
   d = camera_dir(r.m, -rc.fov_factor, a, b);
   o = r.o;

@@ -1013,3 +1013,33 @@ extern "C" int ptmi_noise_reference(const float* colour_sums, const float* momen
   }
   return PTMI_OK;
 }
+
+// ---- the slot table of a multi-view call with per-view frame numbers and counts (ptmi_render_views_frames, ptmi_render_aov_frames) ----
+// The layout is include/ptmi.h's (ptmi_view_slot_plan); the kernels read it through ptmi_device.h's ViewTab.  Everything is checked before anything is written.
+extern "C" int ptmi_view_slot_plan(uint32_t n_views, const uint32_t* first_frames, const uint32_t* frame_counts, uint32_t* table, size_t table_words, uint32_t* n_slots) {
+  if (!first_frames || !frame_counts || n_views == 0) return PTMI_ERR_INVALID_ARG;
+  uint64_t sum = 0;
+  for (uint32_t v = 0; v < n_views; v++) {
+    sum += frame_counts[v];
+    if (sum > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
+  }
+  if (sum == 0) return PTMI_ERR_INVALID_ARG;
+  const uint64_t words = 4ull * n_views + sum;
+  if (words > (uint64_t)PTMI_VIEW_SLOT_TABLE_MAX_WORDS) return PTMI_ERR_INVALID_ARG;
+  if (n_slots) *n_slots = (uint32_t)sum;
+  if (!table) return PTMI_OK;
+  if ((uint64_t)table_words < words) return PTMI_ERR_INVALID_ARG;
+  uint32_t* view_of = table + 4 * (size_t)n_views;
+  uint32_t slot = 0;
+  for (uint32_t v = 0; v < n_views; v++) {
+    uint32_t* rec = table + 4 * (size_t)v;
+    rec[0] = slot, rec[1] = frame_counts[v], rec[2] = first_frames[v];
+    for (uint32_t k = 0; k < frame_counts[v]; k++) view_of[slot++] = v;
+  }
+  uint32_t next = n_views;  // the next view with a frame, from the back
+  for (uint32_t v = n_views; v-- > 0;) {
+    table[4 * (size_t)v + 3] = next;
+    if (frame_counts[v]) next = v;
+  }
+  return PTMI_OK;
+}

@@ -44,7 +44,7 @@ DEV uint32_t* rng0_of(const Paths& P) { return reinterpret_cast<uint32_t*>(P.in.
 // one integer division — and stepped from slot to slot; the view's row is loaded anew only where the view changes (every slot with one frame per view).
 // Every render kernel comes twice: under its own name for a batch with one view — rc carries it, the ViewTab is empty and never read — and as k_*_views, the MV
 // instances of the same body with the table as one more argument (ptmi_render_views).
-template <bool COUNT, bool MV>
+template <bool COUNT, int MV>
 DEV void generate_body(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads, unsigned long long* __restrict__ totals, ViewTab vt) {
   reset_heads(heads);
   const bool trace = rc.max_bounces > 0;  // MAX_BOUNCES = 0: ray_color's loop body never runs, no hitScene at all
@@ -63,7 +63,15 @@ DEV void generate_body(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict_
    const uint32_t f_end = min((chunk + 1u) * kGenFrames, (uint32_t)rc.n_frames);
    uint32_t view = 0, fiv = 0;  // (MV) the slot's view and its frame within the view
    ViewRow vr;
-   if (MV) {
+   ViewRec rec = {0u, 0u, 0u, 0u};  // (VK_TAB) the view's record, and the frame number of the slot
+   uint32_t frame = 0;
+   if (MV == VK_TAB) {  // the chunk may begin in the middle of a view
+     const uint32_t s = vt.slot0 + chunk * kGenFrames;
+     view = view_of_slot_voted(vt, s);
+     rec = load_view_rec(vt, view);
+     fiv = s - rec.first_slot, frame = rec.first_frame + fiv;
+     vr = load_view_row(vt, view);
+   } else if (MV) {
      const uint32_t s = vt.slot0 + chunk * kGenFrames;
      view = s / vt.fpv, fiv = s - view * vt.fpv;
      vr = load_view_row(vt, view);
@@ -73,14 +81,24 @@ DEV void generate_body(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict_
     const uint32_t g = f * rc.n_local + j;
     uint32_t pid = g;  // path id = frame_slot * n_local + local pixel index (dense per rank)
     // u32(uniforms.frameNum): the frame number travels through an f32 uniform (renderer.js:173)
-    uint32_t rng = pix + (uint32_t)(float)(rc.frame0 + (MV ? fiv : f)) * 719393u;
+    uint32_t rng = pix + (uint32_t)(float)(MV == VK_TAB ? frame : rc.frame0 + (MV ? fiv : f)) * 719393u;
     f3 o, d;
     if (MV) {
       float a, b;
       camera_plane(rc, px, py, 0, rng, a, b);
       d = camera_dir(vr.m, -rc.fov_factor, a, b);
       o = vr.o;
-      if (++fiv == vt.fpv) {  // the next slot opens the next view
+      if (MV == VK_TAB) {
+        frame++;
+        if (++fiv == rec.count) {  // the next slot opens the next view that has a frame (the batch's last slot may be the call's last: nothing is loaded then)
+          view = rec.next;
+          if (f + 1u < f_end) {
+            rec = load_view_rec(vt, view);
+            vr = load_view_row(vt, view);
+            fiv = 0, frame = rec.first_frame;
+          }
+        }
+      } else if (++fiv == vt.fpv) {  // the next slot opens the next view
         fiv = 0, view++;
         if (f + 1u < f_end) vr = load_view_row(vt, view);
       }
@@ -108,12 +126,18 @@ DEV void generate_body(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict_
 template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_generate(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
                                                      unsigned long long* __restrict__ totals) {
-  generate_body<COUNT, false>(S, rc, P, ctl, heads, totals, ViewTab{});
+  generate_body<COUNT, VK_ONE>(S, rc, P, ctl, heads, totals, ViewTab{});
 }
 template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_generate_views(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
                                                            unsigned long long* __restrict__ totals, ViewTab vt) {
-  generate_body<COUNT, true>(S, rc, P, ctl, heads, totals, vt);
+  generate_body<COUNT, VK_DIV>(S, rc, P, ctl, heads, totals, vt);
+}
+// ... of a batch whose views have frame numbers and counts of their own (ptmi_render_views_frames): the slot table behind vt's rows
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_generate_frames(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
+                                                            unsigned long long* __restrict__ totals, ViewTab vt) {
+  generate_body<COUNT, VK_TAB>(S, rc, P, ctl, heads, totals, vt);
 }
 
 // 96 VGPRs (5 waves/SIMD, no spills) measured 27 % faster than the compiler's default 106 VGPRs / 4 waves: the kernel
@@ -258,7 +282,7 @@ DEV void walk_inner(const DevScene& S, const WalkRay& ray, const LaneStack2& stk
 // (Storing an accepted hit at once instead of at the end of the ray saved four registers and lost 12 %: on gfx9 stores count on
 // vmcnt like loads, so every later fetch waited for them.)
 constexpr int kScanGroups = 3, kCandSlots = 64 * (kScanGroups + 1);  // a pass adds at most 64 x kScanGroups candidates to fewer than 64
-template <bool COUNT, bool NOABORT, bool MV>
+template <bool COUNT, bool NOABORT, int MV>
 DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads, uint32_t n_teams, int stack_size, int lds_entries, int spill_entries,
                    int2* __restrict__ spill, int refill_threshold, int leaf_batch, unsigned long long* __restrict__ totals, uint32_t range_cap, float4 cam, const Carry& cy, const ViewTab& vt,
                    int* lds_stack, uint32_t wave_id, uint32_t n_waves  // (stand where blockIdx.x / gridDim.x would: a wave works on its own)
@@ -352,7 +376,7 @@ DEV void bvh2_body(const DevScene& S, const Paths& P, StepCtl* __restrict__ ctl,
           w.ct = P.hin.tp[myslot].x;  // closest_so_far after part 1 of hitScene; the rest of that record stands unless a triangle wins
           f3 o = mk3(cam);
           if (cam.w == 0.0f) o = mk3(P.in.q0[myslot]);  // (wave-uniform: step 0 picks a ray up with two gathers instead of three)
-          else if (MV) o = view_origin_of_path(vt, myslot);  // (step 0: slot = path id)
+          else if (MV) o = view_origin_of_path<MV>(vt, myslot);  // (step 0: slot = path id)
           ray = make_walk_ray(S, o, mk3(r1));
           w.sp = 0;
           w.hit.prim = 0u;
@@ -428,7 +452,7 @@ __global__ __launch_bounds__(64) PTMI_BVH_ATTR void k_bvh2(DevScene S, Paths P, 
                                                            Carry cy
 ) {
   extern __shared__ int lds_stack[];
-  bvh2_body<COUNT, NOABORT, false>(S, P, ctl, heads, n_teams, stack_size, lds_entries, spill_entries, spill, refill_threshold, leaf_batch, totals, range_cap, cam, cy, ViewTab{},
+  bvh2_body<COUNT, NOABORT, VK_ONE>(S, P, ctl, heads, n_teams, stack_size, lds_entries, spill_entries, spill, refill_threshold, leaf_batch, totals, range_cap, cam, cy, ViewTab{},
                                             lds_stack, blockIdx.x, gridDim.x
   );
 }
@@ -438,8 +462,17 @@ __global__ __launch_bounds__(64) PTMI_BVH_ATTR void k_bvh2_views(DevScene S, Pat
                                                                  int lds_entries, int spill_entries, int2* __restrict__ spill, int refill_threshold, int leaf_batch,
                                                                  unsigned long long* __restrict__ totals, uint32_t range_cap, float4 cam, Carry cy, ViewTab vt) {
   extern __shared__ int lds_stack[];
-  bvh2_body<COUNT, NOABORT, true>(S, P, ctl, heads, n_teams, stack_size, lds_entries, spill_entries, spill, refill_threshold, leaf_batch, totals, range_cap, cam, cy, vt, lds_stack,
+  bvh2_body<COUNT, NOABORT, VK_DIV>(S, P, ctl, heads, n_teams, stack_size, lds_entries, spill_entries, spill, refill_threshold, leaf_batch, totals, range_cap, cam, cy, vt, lds_stack,
                                            blockIdx.x, gridDim.x);
+}
+// ... of a ptmi_render_views_frames batch: the slot's view comes from the slot table
+template <bool COUNT, bool NOABORT>
+__global__ __launch_bounds__(64) PTMI_BVH_ATTR void k_bvh2_frames(DevScene S, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads, uint32_t n_teams, int stack_size,
+                                                                  int lds_entries, int spill_entries, int2* __restrict__ spill, int refill_threshold, int leaf_batch,
+                                                                  unsigned long long* __restrict__ totals, uint32_t range_cap, float4 cam, Carry cy, ViewTab vt) {
+  extern __shared__ int lds_stack[];
+  bvh2_body<COUNT, NOABORT, VK_TAB>(S, P, ctl, heads, n_teams, stack_size, lds_entries, spill_entries, spill, refill_threshold, leaf_batch, totals, range_cap, cam, cy, vt, lds_stack,
+                                    blockIdx.x, gridDim.x);
 }
 
 
@@ -472,14 +505,14 @@ struct SlotState {
   float2 tp;
   uint32_t hitmat, slot;
 };
-template <bool MV>
+template <int MV>
 DEV SlotState load_slot(const Paths& P, uint32_t slot, bool first, const RenderConst& rc, const ViewTab& vt) {
   SlotState st;
   st.slot = slot;
   st.hitmat = P.hin.mat[slot];
   st.q1 = P.in.q1[slot];
   if (first) {  // step 0: k_generate does not store what every path starts with
-    const f3 co = MV ? view_origin_of_path(vt, slot) : cam_origin(rc);  // (step 0: slot = path id)
+    const f3 co = MV ? view_origin_of_path<MV>(vt, slot) : cam_origin(rc);  // (step 0: slot = path id)
     st.q0 = make_float4(co.x, co.y, co.z, __uint_as_float(rng0_of(P)[slot]));
     st.q2 = make_float4(1.0f, 1.0f, 1.0f, __int_as_float(0));
   } else {
@@ -519,7 +552,7 @@ DEV void end_sample_progressive(const Paths& P, uint32_t pid, f3 add, bool writt
 // MULTI = NUM_SAMPLES > 1 (the per-pixel sample loop of shootRay.wgsl:5-49 lives in the slot: pixsum, in-slot camera ray); the
 // reference's progressive mode (NUM_SAMPLES = 1) compiles without it, which also frees the scalar registers the view matrix and
 // the image constants would occupy through the whole kernel.
-template <bool IS, bool MULTI, bool MV>
+template <bool IS, bool MULTI, int MV>
 DEV bool shade_one(const DevScene& S, const RenderConst& rc, const Paths& P, const SlotState& st, const TriFetch& tf, const QuadL& L, NewState& ns, const ViewTab& vt) {
   const uint32_t pid = __float_as_uint(st.q1.w);
   const f3 o = mk3(st.q0), d = mk3(st.q1);
@@ -646,7 +679,7 @@ DEV bool shade_one(const DevScene& S, const RenderConst& rc, const Paths& P, con
   sample++;
   if (sample < rc.num_samples) {  // the next sample continues the same RNG stream in the same slot
     P.pixsum[pid] = make_float4(sum.x, sum.y, sum.z, 0.0f);
-    if (MV) camera_ray_view(rc, vt, pid, sample, rng, no, nd);
+    if (MV) camera_ray_view<MV>(rc, vt, pid, sample, rng, no, nd);
     else camera_ray(rc, local_to_pixel(rc, pid % rc.n_local), sample, rng, no, nd);
     P.acc[pid] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(sample));
     ns.o = no, ns.d = nd, ns.T = mk3(1.0f, 1.0f, 1.0f), ns.bounce = 0, ns.rng = rng;
@@ -759,7 +792,7 @@ struct OutRegion {
 //      record go to the block's current OUTPUT REGION of the next queue, coalesced.  A block claims a region with one
 //      global atomic (16 or so per launch), fills it across chunks — an entry that does not fit any more continues in
 //      the next region — and marks what is left at the end as holes.
-template <bool IS, bool COUNT, bool MULTI, bool MV>
+template <bool IS, bool COUNT, bool MULTI, int MV>
 DEV void shade_body(const DevScene& S, const RenderConst& rc, const Paths& P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads, unsigned long long* __restrict__ totals,
                     int first, uint32_t resv, const ViewTab& vt) {
   reset_heads(heads);
@@ -916,7 +949,7 @@ DEV void shade_body(const DevScene& S, const RenderConst& rc, const Paths& P, St
 // In progressive mode, a flush pass in which at least rc.shade_cont new rays have their final hit record (no root box entered) keeps those rays:
 // the wave shades them next, as a pass of its own, and only the rays that need k_bvh go to the next queue (continuation, round 6).
 // (shade_body's three barriers per chunk had every wave wait for the block's slowest three times per 128 slots of its own work.)
-template <bool IS, bool COUNT, bool MULTI, bool MV>
+template <bool IS, bool COUNT, bool MULTI, int MV>
 DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
                          unsigned long long* __restrict__ totals, int first, uint32_t resv, const ViewTab& vt) {
   reset_heads(heads);
@@ -1113,28 +1146,42 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
 template <bool IS, bool SORT, bool COUNT, bool MULTI>
 __global__ __launch_bounds__(kBlock) PTMI_SHADE_ATTR void k_shade(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
                                                                   unsigned long long* __restrict__ totals, int first, uint32_t resv) {
-  if constexpr (SORT) shade_body<IS, COUNT, MULTI, false>(S, rc, P, ctl, heads, totals, first, resv, ViewTab{});  // several material classes: block by block, sorted
-  else shade_body_wave<IS, COUNT, MULTI, false>(S, rc, P, ctl, heads, totals, first, resv, ViewTab{});            // one class: wave by wave
+  if constexpr (SORT) shade_body<IS, COUNT, MULTI, VK_ONE>(S, rc, P, ctl, heads, totals, first, resv, ViewTab{});  // several material classes: block by block, sorted
+  else shade_body_wave<IS, COUNT, MULTI, VK_ONE>(S, rc, P, ctl, heads, totals, first, resv, ViewTab{});            // one class: wave by wave
 }
 template <bool SORT, bool COUNT>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_shade6(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl,
                                                                                                 uint32_t* __restrict__ heads, unsigned long long* __restrict__ totals, int first, uint32_t resv) {
-  if constexpr (SORT) shade_body<false, COUNT, false, false>(S, rc, P, ctl, heads, totals, first, resv, ViewTab{});
-  else shade_body_wave<false, COUNT, false, false>(S, rc, P, ctl, heads, totals, first, resv, ViewTab{});
+  if constexpr (SORT) shade_body<false, COUNT, false, VK_ONE>(S, rc, P, ctl, heads, totals, first, resv, ViewTab{});
+  else shade_body_wave<false, COUNT, false, VK_ONE>(S, rc, P, ctl, heads, totals, first, resv, ViewTab{});
 }
 // ... of a multi-view batch: step 0's origins and the in-slot camera rays of NUM_SAMPLES > 1 come from the view of the path's slot
 template <bool IS, bool SORT, bool COUNT, bool MULTI>
 __global__ __launch_bounds__(kBlock) PTMI_SHADE_ATTR void k_shade_views(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
                                                                         unsigned long long* __restrict__ totals, int first, uint32_t resv, ViewTab vt) {
-  if constexpr (SORT) shade_body<IS, COUNT, MULTI, true>(S, rc, P, ctl, heads, totals, first, resv, vt);
-  else shade_body_wave<IS, COUNT, MULTI, true>(S, rc, P, ctl, heads, totals, first, resv, vt);
+  if constexpr (SORT) shade_body<IS, COUNT, MULTI, VK_DIV>(S, rc, P, ctl, heads, totals, first, resv, vt);
+  else shade_body_wave<IS, COUNT, MULTI, VK_DIV>(S, rc, P, ctl, heads, totals, first, resv, vt);
 }
 template <bool SORT, bool COUNT>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_shade6_views(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl,
                                                                                                       uint32_t* __restrict__ heads, unsigned long long* __restrict__ totals, int first,
                                                                                                       uint32_t resv, ViewTab vt) {
-  if constexpr (SORT) shade_body<false, COUNT, false, true>(S, rc, P, ctl, heads, totals, first, resv, vt);
-  else shade_body_wave<false, COUNT, false, true>(S, rc, P, ctl, heads, totals, first, resv, vt);
+  if constexpr (SORT) shade_body<false, COUNT, false, VK_DIV>(S, rc, P, ctl, heads, totals, first, resv, vt);
+  else shade_body_wave<false, COUNT, false, VK_DIV>(S, rc, P, ctl, heads, totals, first, resv, vt);
+}
+// ... of a ptmi_render_views_frames batch
+template <bool IS, bool SORT, bool COUNT, bool MULTI>
+__global__ __launch_bounds__(kBlock) PTMI_SHADE_ATTR void k_shade_frames(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
+                                                                         unsigned long long* __restrict__ totals, int first, uint32_t resv, ViewTab vt) {
+  if constexpr (SORT) shade_body<IS, COUNT, MULTI, VK_TAB>(S, rc, P, ctl, heads, totals, first, resv, vt);
+  else shade_body_wave<IS, COUNT, MULTI, VK_TAB>(S, rc, P, ctl, heads, totals, first, resv, vt);
+}
+template <bool SORT, bool COUNT>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_shade6_frames(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl,
+                                                                                                       uint32_t* __restrict__ heads, unsigned long long* __restrict__ totals, int first,
+                                                                                                       uint32_t resv, ViewTab vt) {
+  if constexpr (SORT) shade_body<false, COUNT, false, VK_TAB>(S, rc, P, ctl, heads, totals, first, resv, vt);
+  else shade_body_wave<false, COUNT, false, VK_TAB>(S, rc, P, ctl, heads, totals, first, resv, vt);
 }
 
 // k_tail — a SHORT queue traced to the end in one launch: every lane takes a path and runs ray_color's loop for it (hitScene part 2 on
@@ -1145,7 +1192,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) 
 // when it has run, the block that finishes last zeroes the queue length, so the step's k_bvh / k_shade and every later step find nothing.
 // Same per-ray arithmetic and visit order as the wavefront kernels (the same device functions), same counters and tallies.
 constexpr int kTailTravBatch = 24;  // (12 / 32 / 40 lanes measured: profiles/r04_tail_trav_batch.txt)
-template <bool IS, bool COUNT, bool MULTI, bool NOABORT, bool MV>
+template <bool IS, bool COUNT, bool MULTI, bool NOABORT, int MV>
 DEV void tail_body(const DevScene& S, const RenderConst& rc, const Paths& P, StepCtl* __restrict__ ctl, unsigned long long* __restrict__ totals, int first, uint32_t limit,
                    int stack_size, int lds_entries, int spill_entries, int2* __restrict__ spill, const Carry& cy, const ViewTab& vt) {
   const QueueExtent qe = queue_extent(ctl, cy.resv);  // (Carry: the rays in [0, n_carried) go on with their traversal)
@@ -1305,25 +1352,37 @@ DEV void tail_body(const DevScene& S, const RenderConst& rc, const Paths& P, Ste
 template <bool IS, bool COUNT, bool MULTI, bool NOABORT>
 __global__ __launch_bounds__(64) void k_tail(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, unsigned long long* __restrict__ totals, int first, uint32_t limit,
                                              int stack_size, int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy) {
-  tail_body<IS, COUNT, MULTI, NOABORT, false>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, ViewTab{});
+  tail_body<IS, COUNT, MULTI, NOABORT, VK_ONE>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, ViewTab{});
 }
 template <bool COUNT, bool NOABORT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_tail6(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl,
                                                                                          unsigned long long* __restrict__ totals, int first, uint32_t limit, int stack_size,
                                                                                          int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy) {
-  tail_body<false, COUNT, false, NOABORT, false>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, ViewTab{});
+  tail_body<false, COUNT, false, NOABORT, VK_ONE>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, ViewTab{});
 }
 // ... of a multi-view batch (step 0's origins, the in-slot camera rays of NUM_SAMPLES > 1)
 template <bool IS, bool COUNT, bool MULTI, bool NOABORT>
 __global__ __launch_bounds__(64) void k_tail_views(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, unsigned long long* __restrict__ totals, int first,
                                                    uint32_t limit, int stack_size, int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy, ViewTab vt) {
-  tail_body<IS, COUNT, MULTI, NOABORT, true>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, vt);
+  tail_body<IS, COUNT, MULTI, NOABORT, VK_DIV>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, vt);
 }
 template <bool COUNT, bool NOABORT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_tail6_views(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl,
                                                                                                unsigned long long* __restrict__ totals, int first, uint32_t limit, int stack_size,
                                                                                                int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy, ViewTab vt) {
-  tail_body<false, COUNT, false, NOABORT, true>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, vt);
+  tail_body<false, COUNT, false, NOABORT, VK_DIV>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, vt);
+}
+// ... of a ptmi_render_views_frames batch
+template <bool IS, bool COUNT, bool MULTI, bool NOABORT>
+__global__ __launch_bounds__(64) void k_tail_frames(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, unsigned long long* __restrict__ totals, int first,
+                                                    uint32_t limit, int stack_size, int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy, ViewTab vt) {
+  tail_body<IS, COUNT, MULTI, NOABORT, VK_TAB>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, vt);
+}
+template <bool COUNT, bool NOABORT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_tail6_frames(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl,
+                                                                                                unsigned long long* __restrict__ totals, int first, uint32_t limit, int stack_size,
+                                                                                                int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy, ViewTab vt) {
+  tail_body<false, COUNT, false, NOABORT, VK_TAB>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, vt);
 }
 
 // k_aov — the feature pass (ptmi_render_aov): what the FIRST hitScene call of every frame's path sees, and nothing after it.  No queues, no path state, no
@@ -1337,10 +1396,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void
 // Waves per SIMD from the register count (tools/kernel_resources.sh): 123 VGPRs without scratch as the compiler allocates it — 4 waves; held to 96 (5 waves) it
 // spills 48 bytes, to 80 (6 waves) 96-112.  4 it is until a run shows a spilling build ahead (-DPTMI_AOV_WAVES=5 builds one: tools/aov_probe.py); the LDS stacks
 // (5 KB per wave at the default 10 entries) admit 32 waves per CU, so the registers alone decide.
-template <bool NOABORT>
+// MV = VK_TAB (ptmi_render_aov_frames): the view's first frame number and its count come from its record of the slot table; a view without a frame is neither read
+// nor written.  A wave that straddles views of different counts stays converged — the walk's votes need that — until its longest view is through: the lanes of the
+// shorter one trace on and fold nothing.
 #ifndef PTMI_AOV_WAVES
 #define PTMI_AOV_WAVES 4
 #endif
+// (One kernel template, not a k_aov_frames twin around a shared body, for the reason given above k_accumulate: inlined into two entries the VK_DIV instance was allocated
+// and scheduled differently.  k_aov<NOABORT, VK_DIV> compiles to what k_aov<NOABORT> compiled to.)
+template <bool NOABORT, int MV>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PTMI_AOV_WAVES, 8))) void k_aov(DevScene S, RenderConst rc, ViewTab vt, float4* __restrict__ stack, uint32_t view0, uint32_t n_views, int reset, int stack_size,
                                             int lds_entries, int spill_entries, int2* __restrict__ spill) {
   extern __shared__ int lds_stack[];
@@ -1365,13 +1429,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PTMI_AOV_WAV
     float px, py;
     camera_pixel(rc, pix, px, py);
     const ViewRow vr = load_view_row(vt, view0 + vl);
+    ViewRec rec = {0u, 0u, 0u, 0u};
+    if (MV == VK_TAB) rec = load_view_rec(vt, view0 + vl);
+    const uint32_t frame0 = MV == VK_TAB ? rec.first_frame : rc.frame0, nf = MV == VK_TAB ? rec.count : vt.fpv;
     float4* const img = stack + (size_t)(view0 + vl) * 3u * rc.npix + pix;
     float4 nd = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ac = nd, ids = nd;
-    if (!reset) nd = img[0], ac = img[rc.npix];
+    if (!reset && (MV != VK_TAB || nf != 0u)) nd = img[0], ac = img[rc.npix];
 #pragma unroll 1
-    for (uint32_t f = 0; f < vt.fpv; f++) {
+    for (uint32_t f = 0; MV == VK_TAB ? __ballot(f < nf) != 0ull : f < nf; f++) {
+      const bool folds = MV != VK_TAB || f < nf;
       // u32(uniforms.frameNum): the frame number travels through an f32 uniform (renderer.js:173)
-      uint32_t rng = pix + (uint32_t)(float)(rc.frame0 + f) * 719393u;
+      uint32_t rng = pix + (uint32_t)(float)(frame0 + f) * 719393u;
       float a, b;
       camera_plane(rc, px, py, 0, rng, a, b);
       const f3 d = camera_dir(vr.m, -rc.fov_factor, a, b), o = vr.o;
@@ -1397,6 +1465,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PTMI_AOV_WAV
       }
       const uint32_t prim = __float_as_uint(tp.y), kind = prim >> 28;
       float4 hn = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ha = hn;  // a miss adds +0.0
+      if (!folds) continue;
       ids = hn;
       if (kind != K_NONE) {
         const uint32_t mat = hm & HITMAT_ID;
@@ -1413,7 +1482,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PTMI_AOV_WAV
         ac = make_float4(ac.x + ha.x, ac.y + ha.y, ac.z + ha.z, ac.w + ha.w);
       }
     }
-    if (mine) img[0] = nd, img[rc.npix] = ac, img[2 * (size_t)rc.npix] = ids;
+    if (mine && (MV != VK_TAB || nf != 0u)) img[0] = nd, img[rc.npix] = ac, img[2 * (size_t)rc.npix] = ids;
   }
 }
 
@@ -1570,6 +1639,88 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_moments(RenderConst rc, P
     if (pending) {
       fb[at] = make_float4(c.x, c.y, c.z, 1.0f);
       mom[at] = m;
+    }
+  }
+  if (f_begin == 0 && blockIdx.x == 0 && threadIdx.x == 0) {  // the slot-0 tally, as k_accumulate's
+    unsigned long long rays = 0;
+    if (n_steps > 0)
+      for (int k = 0; k < kTallyLines; k++) rays += *tally_line(totals, (uint32_t)k);
+    totals[0] += rays;
+    totals[1] += (unsigned long long)rc.n_local * (unsigned long long)rc.n_frames * (unsigned long long)rc.num_samples;
+  }
+}
+
+// k_accumulate<true> / k_accumulate_moments for a ptmi_render_views_frames batch (VK_TAB): the image changes where the slot table says the view ends — the next one is the
+// record's `next`, views without a frame are stepped over and never touched — and rc.reset_first applies to each view's first slot OF THE CALL (a batch that begins
+// inside a view adds to what the batch before it stored).  The same eight-ahead fetch, the same f32 sums in frame order.  MOM: the moment stack is folded too.
+// (Entries of their own for the reason given above k_accumulate.)
+template <bool MOM>
+__global__ __launch_bounds__(kBlock) void k_accumulate_frames(RenderConst rc, Paths P, float4* __restrict__ fb, float4* __restrict__ mom, int n_steps,
+                                                              unsigned long long* __restrict__ totals, int f_begin, int f_end, ViewTab vt) {
+  for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < rc.n_local; j += gridDim.x * kBlock) {
+    if (f_begin >= f_end) break;
+    const uint32_t pix = local_to_pixel(rc, j);
+    const uint32_t s = vt.slot0 + (uint32_t)f_begin;
+    uint32_t view = view_of_slot_voted(vt, s);
+    ViewRec rec = load_view_rec(vt, view);
+    uint32_t fiv = s - rec.first_slot;  // frame-in-view, counted from the view's first slot of the call
+    size_t at = (size_t)view * rc.npix + pix;  // the pixel of the view's image, in either stack
+    const bool opens = fiv == 0u && rc.reset_first;  // the first slot overwrites: what the images hold is not needed
+    f3 c = mk3(0.0f, 0.0f, 0.0f);
+    float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!opens) {
+      c = mk3(fb[at]);
+      if (MOM) m = mom[at];
+    }
+    bool pending = false;  // `c` (and `m`) have still to be stored
+    constexpr int kAhead = 8;
+    for (int f0 = f_begin; f0 < f_end; f0 += kAhead) {
+      bool have[kAhead];
+      float4 colv[kAhead];
+#pragma unroll
+      for (int k = 0; k < kAhead; k++) {
+        const int f = f0 + k;
+        have[k] = f < f_end && (!P.touched || P.touched[(size_t)f * rc.n_local + j]);
+      }
+#pragma unroll
+      for (int k = 0; k < kAhead; k++) {
+        colv[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // a path that never wrote its acc_radiance returned (0,0,0)
+        if (have[k]) colv[k] = P.acc[(size_t)(f0 + k) * rc.n_local + j];
+      }
+#pragma unroll
+      for (int k = 0; k < kAhead; k++) {
+        const int f = f0 + k;
+        if (f >= f_end) break;
+        const f3 col = mk3(colv[k]);
+        const f3 sq = mk3(col.x * col.x, col.y * col.y, col.z * col.z);
+        if (fiv == 0u && rc.reset_first) {
+          c = col;
+          if (MOM) m = make_float4(sq.x, sq.y, sq.z, 1.0f);
+        } else {
+          c = c + col;
+          if (MOM) m = make_float4(m.x + sq.x, m.y + sq.y, m.z + sq.z, m.w + 1.0f);
+        }
+        pending = true;
+        if (++fiv == rec.count) {  // the view's last slot of the call: its images are done, the next slot opens the next view that has a frame
+          fb[at] = make_float4(c.x, c.y, c.z, 1.0f);
+          if (MOM) mom[at] = m;
+          pending = false;
+          if (f + 1 < f_end) {
+            view = rec.next;
+            rec = load_view_rec(vt, view);
+            fiv = 0;
+            at = (size_t)view * rc.npix + pix;
+            if (!rc.reset_first) {  // (with reset the next slot's colour overwrites both)
+              c = mk3(fb[at]);
+              if (MOM) m = mom[at];
+            }
+          }
+        }
+      }
+    }
+    if (pending) {
+      fb[at] = make_float4(c.x, c.y, c.z, 1.0f);
+      if (MOM) mom[at] = m;
     }
   }
   if (f_begin == 0 && blockIdx.x == 0 && threadIdx.x == 0) {  // the slot-0 tally, as k_accumulate's

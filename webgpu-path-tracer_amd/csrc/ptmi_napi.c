@@ -65,6 +65,9 @@ FN(ptmi_release_moments)
 FN(ptmi_default_noise_params)
 FN(ptmi_view_noise_stats)
 FN(ptmi_render_views_until)
+FN(ptmi_render_views_frames)
+FN(ptmi_render_aov_frames)
+FN(ptmi_render_views_until_each)
 FN(ptmi_synchronize)
 FN(ptmi_read_framebuffer)
 FN(ptmi_write_framebuffer)
@@ -113,6 +116,7 @@ static int load_lib(char* err, size_t errlen) {
   }
   LOAD(ptmi_version) LOAD(ptmi_last_error) LOAD(ptmi_create) LOAD(ptmi_create_multi) LOAD(ptmi_prepare) LOAD(ptmi_destroy) LOAD(ptmi_default_params) LOAD(ptmi_default_denoise_params) LOAD(ptmi_set_params)
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
+  LOAD(ptmi_render_views_frames) LOAD(ptmi_render_aov_frames) LOAD(ptmi_render_views_until_each)
   LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_default_guided_params) LOAD(ptmi_denoise_views_guided) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_default_accumulate_params) LOAD(ptmi_accumulate_views) LOAD(ptmi_read_accumulated) LOAD(ptmi_release_accumulated) LOAD(ptmi_denoise_views_accumulated) LOAD(ptmi_set_view_moments) LOAD(ptmi_read_moments) LOAD(ptmi_release_moments) LOAD(ptmi_default_noise_params) LOAD(ptmi_view_noise_stats) LOAD(ptmi_render_views_until) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
   LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah)
   LOAD(ptmi_obj_parse) LOAD(ptmi_free) LOAD(ptmi_device_count) LOAD(ptmi_reduce_info)
@@ -863,6 +867,94 @@ static napi_value js_render_views_until(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* renderViewsFrames / renderAovFrames(ctx, Float32Array(V*16), Uint32Array(V) firstFrames, Uint32Array(V) frameCounts, reset): ptmi_render_views_frames /
+ * ptmi_render_aov_frames — every view with frame numbers and a frame count of its own */
+static napi_value render_frames_common(napi_env env, napi_callback_info info, int (*fn)(ptmi_ctx*, const float*, uint32_t, const uint32_t*, const uint32_t*, int), const char* what) {
+  napi_value a[5];
+  if (get_args(env, info, 5, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  void *data, *firsts, *counts;
+  size_t len, nf, nc;
+  if (typed(env, a[1], napi_float32_array, "views", &data, &len) || typed(env, a[2], napi_uint32_array, "firstFrames", &firsts, &nf) ||
+      typed(env, a[3], napi_uint32_array, "frameCounts", &counts, &nc))
+    return NULL;
+  if (len == 0 || len % 16 != 0 || len / 16 > 0xffffffffu || nf != len / 16 || nc != len / 16) {
+    napi_throw_range_error(env, NULL, "views must hold 16 floats per view, one view at least, firstFrames and frameCounts one entry per view");
+    return NULL;
+  }
+  bool reset = false;
+  napi_coerce_to_bool(env, a[4], &a[4]);
+  napi_get_value_bool(env, a[4], &reset);
+  int st = fn(c, (const float*)data, (uint32_t)(len / 16), (const uint32_t*)firsts, (const uint32_t*)counts, reset ? 1 : 0);
+  if (st) return throw_status(env, c, st, what);
+  return NULL;
+}
+static napi_value js_render_views_frames(napi_env env, napi_callback_info info) { return render_frames_common(env, info, p_ptmi_render_views_frames, "ptmi_render_views_frames"); }
+static napi_value js_render_aov_frames(napi_env env, napi_callback_info info) { return render_frames_common(env, info, p_ptmi_render_aov_frames, "ptmi_render_aov_frames"); }
+
+/* renderViewsUntilEach(ctx, views, Uint32Array(V) firstFrames | null, framesPerRound, maxFrames, target, params | null): ptmi_render_views_until_each ->
+ * {framesDone: Uint32Array(V), noise: [records]} */
+static napi_value js_render_views_until_each(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (get_args(env, info, 7, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  void *data, *firsts = NULL;
+  size_t len, nf = 0;
+  if (typed(env, a[1], napi_float32_array, "renderViewsUntilEach(views)", &data, &len)) return NULL;
+  if (len == 0 || len % 16 != 0 || len / 16 > (1u << 24)) {
+    napi_throw_range_error(env, NULL, "renderViewsUntilEach: views must hold 16 floats per view, one view at least");
+    return NULL;
+  }
+  const uint32_t n_views = (uint32_t)(len / 16);
+  napi_valuetype vt;
+  CHECK_NAPI(napi_typeof(env, a[2], &vt));
+  if (vt != napi_null && vt != napi_undefined) {
+    if (typed(env, a[2], napi_uint32_array, "renderViewsUntilEach(firstFrames)", &firsts, &nf)) return NULL;
+    if (nf != n_views) {
+      napi_throw_range_error(env, NULL, "renderViewsUntilEach: firstFrames must hold one entry per view");
+      return NULL;
+    }
+  }
+  uint32_t per_round, max_frames;
+  double target;
+  CHECK_NAPI(napi_get_value_uint32(env, a[3], &per_round));
+  CHECK_NAPI(napi_get_value_uint32(env, a[4], &max_frames));
+  CHECK_NAPI(napi_get_value_double(env, a[5], &target));
+  ptmi_noise_params P;
+  if (noise_params_of(env, a[6], &P)) {
+    napi_throw_type_error(env, NULL, "renderViewsUntilEach(params): {floor, threshold} of numbers, or null");
+    return NULL;
+  }
+  ptmi_view_noise* rec = (ptmi_view_noise*)calloc(n_views, sizeof *rec);
+  if (!rec) {
+    napi_throw_error(env, NULL, "renderViewsUntilEach: out of memory");
+    return NULL;
+  }
+  napi_value out = NULL, ab, done_arr;
+  void* done = NULL;
+  if (napi_create_arraybuffer(env, (size_t)n_views * 4, &done, &ab) != napi_ok || napi_create_typedarray(env, napi_uint32_array, n_views, ab, 0, &done_arr) != napi_ok) {
+    free(rec);
+    napi_throw_error(env, NULL, "renderViewsUntilEach: out of memory");
+    return NULL;
+  }
+  int st = p_ptmi_render_views_until_each(c, (const float*)data, n_views, (const uint32_t*)firsts, per_round, max_frames, &P, (float)target, (uint32_t*)done, rec);
+  if (st) {
+    throw_status(env, c, st, "ptmi_render_views_until_each");
+  } else {
+    napi_value noise = noise_records_to_js(env, rec, n_views);
+    if (noise && napi_create_object(env, &out) == napi_ok) {
+      napi_set_named_property(env, out, "framesDone", done_arr);
+      napi_set_named_property(env, out, "noise", noise);
+    } else {
+      out = NULL;
+    }
+  }
+  free(rec);
+  return out;
+}
+
 static napi_value js_synchronize(napi_env env, napi_callback_info info) {
   napi_value a[1];
   if (get_args(env, info, 1, a)) return NULL;
@@ -1132,6 +1224,7 @@ static napi_value init(napi_env env, napi_value exports) {
   } fns[] = {
       {"version", js_version}, {"create", js_create}, {"destroy", js_destroy}, {"defaultParams", js_default_params}, {"setParams", js_set_params},
       {"upload", js_upload}, {"resize", js_resize}, {"clear", js_clear}, {"setShard", js_set_shard}, {"renderFrame", js_render_frame},
+      {"renderViewsFrames", js_render_views_frames}, {"renderAovFrames", js_render_aov_frames}, {"renderViewsUntilEach", js_render_views_until_each},
       {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"denoiseViewsGuided", js_denoise_views_guided}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"accumulateViews", js_accumulate_views}, {"readAccumulated", js_read_accumulated}, {"releaseAccumulated", js_release_accumulated}, {"denoiseViewsAccumulated", js_denoise_views_accumulated}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
       {"resolveRGBA8", js_resolve}, {"setCounters", js_set_counters}, {"setTiming", js_set_timing}, {"stats", js_stats},
       {"resetStats", js_reset_stats}, {"buildBVH", js_build_bvh}, {"buildBVHSAH", js_build_bvh_sah}, {"buildBVHDevice", js_build_bvh_device}, {"parseObj", js_parse_obj},

@@ -75,6 +75,13 @@ export class Ptmi {
   renderViewsUntil(views, firstFrame, framesPerRound, maxFrames, target, params = null) {
     return this.native.renderViewsUntil(this.h, views, firstFrame, framesPerRound, maxFrames, target, params);
   }
+  // Per-view frame numbers and counts (ptmi_render_views_frames ...): view v gets frames firstFrames[v] .. firstFrames[v] + frameCounts[v] - 1 (Uint32Array, one entry per
+  // view; a count of 0 leaves the view alone); renderViewsUntilEach stops each view once ITS mean noise is at most target: {framesDone: Uint32Array, noise}.
+  renderViewsFrames(views, firstFrames, frameCounts, reset = true) { this.native.renderViewsFrames(this.h, views, firstFrames, frameCounts, reset); }
+  renderAovFrames(views, firstFrames, frameCounts, reset = true) { this.native.renderAovFrames(this.h, views, firstFrames, frameCounts, reset); }
+  renderViewsUntilEach(views, firstFrames, framesPerRound, maxFrames, target, params = null) {
+    return this.native.renderViewsUntilEach(this.h, views, firstFrames, framesPerRound, maxFrames, target, params);
+  }
   synchronize() { this.native.synchronize(this.h); }
   prepare() { this.native.prepare(this.h); }
   buildSceneBVHSAH() { this.native.buildSceneBVHSAH(this.h); }   // the same with the reference's never-called SAH builder (lib/BVH/bvhNode.js:108-283): opt-in

@@ -32,7 +32,10 @@ SYMBOLS = [
     "ptmi_denoise_views_accumulated", "ptmi_denoise_images_accumulated", "ptmi_denoise_accumulated_reference",
     "ptmi_set_view_moments", "ptmi_read_moments", "ptmi_moments_device_ptr", "ptmi_release_moments",
     "ptmi_default_noise_params", "ptmi_view_noise_stats", "ptmi_noise_images", "ptmi_noise_reference", "ptmi_render_views_until",
+    "ptmi_render_views_frames", "ptmi_render_aov_frames", "ptmi_render_views_until_each", "ptmi_view_slot_plan",
 ]
+
+VIEW_SLOT_TABLE_MAX_WORDS = 1 << 24  # PTMI_VIEW_SLOT_TABLE_MAX_WORDS
 
 
 class Params(ctypes.Structure):
@@ -244,6 +247,12 @@ def load_library(build=False, path=None):
         L.ptmi_noise_images.argtypes = [vp, fp, fp, i32, i32, u32, qp, fp, fp]
         L.ptmi_noise_reference.argtypes = [fp, fp, i32, i32, u32, qp, fp, fp]
         L.ptmi_render_views_until.argtypes = [vp, fp, u32, u32, u32, u32, qp, ctypes.c_float, ctypes.POINTER(u32), fp]
+    if hasattr(L, "ptmi_render_views_frames"):  # (an older A/B build loaded through PTMI_LIB gives every view the same frame numbers)
+        up = ctypes.POINTER(u32)
+        L.ptmi_render_views_frames.argtypes = [vp, fp, u32, fp, fp, i32]
+        L.ptmi_render_aov_frames.argtypes = [vp, fp, u32, fp, fp, i32]
+        L.ptmi_render_views_until_each.argtypes = [vp, fp, u32, fp, u32, u32, ctypes.POINTER(NoiseParams), ctypes.c_float, fp, fp]
+        L.ptmi_view_slot_plan.argtypes = [u32, fp, fp, fp, sz, up]
     if explicit:
         _libs[path] = L
     else:
@@ -253,6 +262,31 @@ def load_library(build=False, path=None):
 
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _frame_arrays(n_views, first_frames, frame_counts):
+    """The per-view u32 arrays of the calls with per-view frame ranges; a scalar stands for every view."""
+    f = np.ascontiguousarray(np.broadcast_to(np.asarray(first_frames, np.uint32), (n_views,)))
+    k = np.ascontiguousarray(np.broadcast_to(np.asarray(frame_counts, np.uint32), (n_views,)))
+    return f, k
+
+
+def view_slot_plan(first_frames, frame_counts):
+    """Test hook, no GPU (ptmi_view_slot_plan): the slot table render_views_frames uploads for these per-view first frame numbers and frame counts, as
+    (records (V, 4) uint32 — first slot, count, first frame, next view with a frame —, view_of_slot (n_slots,) uint32).  Raises PtmiError where the call would."""
+    lib = load_library()
+    k = np.ascontiguousarray(frame_counts, np.uint32)
+    f = np.ascontiguousarray(first_frames, np.uint32)
+    assert f.shape == k.shape and f.ndim == 1
+    n = ctypes.c_uint32()
+    st = lib.ptmi_view_slot_plan(k.size, _ptr(f), _ptr(k), None, 0, ctypes.byref(n))
+    if st:
+        raise PtmiError(st, "ptmi_view_slot_plan")
+    table = np.zeros(4 * k.size + n.value, np.uint32)
+    st = lib.ptmi_view_slot_plan(k.size, _ptr(f), _ptr(k), _ptr(table), table.size, None)
+    if st:
+        raise PtmiError(st, "ptmi_view_slot_plan")
+    return table[:4 * k.size].reshape(-1, 4), table[4 * k.size:]
 
 
 def default_params(**kw):
@@ -575,6 +609,14 @@ class Context:
         assert v.ndim == 2 and v.shape[1] == 16, "views: (V, 16) float32"
         self._ck(self.lib.ptmi_render_views(self.h, _ptr(v), v.shape[0], first_frame, frames_per_view, 1 if reset else 0))
 
+    def render_views_frames(self, views, first_frames, frame_counts, reset=True):
+        """ptmi_render_views_frames: render_views with a frame range of its own per view — image v receives frames first_frames[v] .. first_frames[v] +
+        frame_counts[v] - 1 of view v; a view with count 0 is left alone.  first_frames / frame_counts: (V,) uint32 (a scalar stands for every view).  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32)
+        assert v.ndim == 2 and v.shape[1] == 16, "views: (V, 16) float32"
+        f, k = _frame_arrays(v.shape[0], first_frames, frame_counts)
+        self._ck(self.lib.ptmi_render_views_frames(self.h, _ptr(v), v.shape[0], _ptr(f), _ptr(k), 1 if reset else 0))
+
     def read_view(self, view):
         return self._read_image(self.lib.ptmi_read_view, view)
 
@@ -593,6 +635,12 @@ class Context:
         the first hits of frames first_frame .. first_frame + frames_per_view - 1.  Asynchronous."""
         v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
         self._ck(self.lib.ptmi_render_aov(self.h, _ptr(v), v.shape[0], first_frame, frames_per_view, 1 if reset else 0))
+
+    def render_aov_frames(self, views, first_frames, frame_counts, reset=True):
+        """ptmi_render_aov_frames: render_aov with render_views_frames' per-view frame ranges.  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        f, k = _frame_arrays(v.shape[0], first_frames, frame_counts)
+        self._ck(self.lib.ptmi_render_aov_frames(self.h, _ptr(v), v.shape[0], _ptr(f), _ptr(k), 1 if reset else 0))
 
     def read_aov(self, view, layer=None):
         """Layer `layer` of view `view` of the feature stack as (H, W, 4) float32 — 0: normal sum + depth sum, 1: albedo sum + hit count, 2: kind, primitive
@@ -772,6 +820,19 @@ class Context:
         self._ck(self.lib.ptmi_render_views_until(self.h, _ptr(v), v.shape[0], first_frame, frames_per_round, max_frames, None if params is None else ctypes.byref(params),
                                                   float(target), ctypes.byref(done), _ptr(out)))
         return done.value, out
+
+    def render_views_until_each(self, views, first_frames, frames_per_round, max_frames, target, params=None):
+        """ptmi_render_views_until_each: render_views_until view by view — a view stops getting frames once ITS mean noise is at most `target`.  first_frames: (V,)
+        uint32, a scalar, or None for 0.  Needs set_view_moments.  Returns (frames_done (V,) uint32, records): the frames each view then sums and the VIEW_NOISE_DTYPE
+        records last taken."""
+        v = np.ascontiguousarray(views, np.float32)
+        assert v.ndim == 2 and v.shape[1] == 16, "views: (V, 16) float32"
+        f = None if first_frames is None else _frame_arrays(v.shape[0], first_frames, 0)[0]
+        done = np.zeros(v.shape[0], np.uint32)
+        out = np.zeros(v.shape[0], VIEW_NOISE_DTYPE)
+        self._ck(self.lib.ptmi_render_views_until_each(self.h, _ptr(v), v.shape[0], None if f is None else _ptr(f), frames_per_round, max_frames,
+                                                       None if params is None else ctypes.byref(params), float(target), _ptr(done), _ptr(out)))
+        return done, out
 
     def camera_rays(self, view16, frame):
         """Test hook (ptmi_camera_rays): (rays (W*H, 6) float32, rng (W*H,) uint32) — the first camera ray of `frame` for every pixel and the RNG state its
