@@ -662,6 +662,27 @@ int ptmi_scene_bvh_info(ptmi_ctx* ctx, uint64_t* n_nodes, int32_t* depth, int32_
  * exactly the buffer's size (triangles x 96, ptmi_scene_bvh_info's n_nodes x 48 for a device-resident tree). */
 int ptmi_read_scene_buffer(ptmi_ctx* ctx, int which, void* dst, size_t bytes);
 
+/* ---- the builders' domain ----------------------------------------------------------------------
+ * Every BVH builder of this library (ptmi_build_bvh, ptmi_build_bvh_sah, their _device twins and ptmi_build_scene_bvh[_sah]) turns boxes
+ * into array indices, and does so for boxes that satisfy:
+ *   1. every coordinate of bmin and bmax is finite;
+ *   2. |x| < 1e30 for every coordinate: beyond that the reference's `new AABB()` sentinel (+1e30, -1e30; lib/BVH/AABB.js:2-5) is the
+ *      answer of a union, not the box;
+ *   3. bmin[k] <= bmax[k] on each axis;
+ *   4. SAH builders only: n_prims x area(union of all boxes) < 1e30, with area = e0*e1 + e1*e2 + e2*e0 in double as AABB.surface_area
+ *      computes it.  FindBestSplitPlane's "no plane" cost is the same 1e30 (lib/BVH/bvhNode.js:223) and a node is a leaf when its best
+ *      cost is no less than count x area; a node's box lies inside the root's, so below the bound a node without a plane is always a
+ *      leaf, every split leaves two non-empty ranges and the tree has at most 2n - 1 nodes.  At or above it (a lone cube of extent
+ *      2e16 is enough) the reference's loop only ends at its 500,000-entry stack limit; there is no reference behaviour to reproduce.
+ * Outside the domain every builder returns PTMI_ERR_BAD_SCENE, writes nothing out of bounds and launches no kernel that could; where
+ * there is a context, ptmi_last_error names the first offending primitive (for the scene builds: triangle, whose padded world-space box
+ * is held to rules 1-2; rule 3 holds of it by construction) and the rule, or for rule 4 the count and the cost.  A refused scene build
+ * leaves the context as it was before the call.  Inside the domain the output is the reference's, bit for bit. */
+
+/* The domain check on its own, without a build: PTMI_OK, or PTMI_ERR_BAD_SCENE with the sentence the builders with a context report in
+ * msg (msg may be NULL).  sah != 0 adds rule 4. */
+int ptmi_check_bvh_boxes(size_t n_prims, const double* bmin, const double* bmax, int sah, char* msg, size_t msg_len);
+
 /* ---- host-side natives (no GPU needed) -------------------------------------------------------- */
 
 /* Median-split BVH build + pre-order flatten with the reference's exact semantics

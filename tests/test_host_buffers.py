@@ -226,6 +226,7 @@ def test_native_bvh_builder_is_thread_count_invariant(pkg, monkeypatch):
     bmin, bmax = c - e, c + e
     bmin[:9000, 0] = 0.125  # many equal keys: stability decides
     bmin[20000:26000, 2] = -0.5
+    bmax = np.maximum(bmax, bmin)  # stay in the builders' domain (include/ptmi.h: bmin <= bmax); the forced keys are untouched
     nh = pkg.ptmi.NativeHost()
     monkeypatch.setenv("PTMI_BUILD_THREADS", "1")
     n1, o1 = nh.build_bvh(bmin, bmax, 2)

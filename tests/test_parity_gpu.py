@@ -609,13 +609,15 @@ def test_unknown_material_types_bit_exact(ctx, pkg, oracle, seed):
 
 def test_device_bvh_builder_is_byte_identical_to_host(ctx, pkg):
     """ptmi_build_bvh_device (level-synchronous, rocPRIM segmented reduce + stable segmented radix sort) against the host builder
-    — itself byte-identical to the reference's JavaScript (tests/test_host_buffers.py): random boxes with tied keys and -0, tiny
-    inputs, and the 871,414-triangle mesh of configs[2]."""
+    — itself byte-identical to the reference's JavaScript (tests/test_host_buffers.py): random boxes with a third of the centres coincident, tiny
+    inputs, and the 871,414-triangle mesh of configs[2].  (bmin = c - e with a random e > 0 per primitive: no two sort keys are tied and no
+    signed zero reaches the builder — `-0.0 - e` is `-e`.  Tied keys, signed zeros, flat axes and other binades are tests/builder_cases.py's,
+    through tests/test_builder_edges_gpu.py.)"""
     nh = pkg.ptmi.NativeHost()
     rng = np.random.default_rng(17)
     for n in (1, 2, 3, 5, 64, 1000, 70001):
         c = rng.uniform(-1, 1, (n, 3)).astype(np.float32).astype(np.float64)
-        c[rng.integers(0, n, n // 3)] = c[0]        # tied keys: stability decides
+        c[rng.integers(0, n, n // 3)] = c[0]        # coincident centres (the keys c - e still differ)
         c[rng.integers(0, n, max(n // 10, 1)), 1] = -0.0
         c[rng.integers(0, n, max(n // 10, 1)), 1] = 0.0
         e = rng.uniform(0, 0.05, (n, 3))
@@ -636,13 +638,15 @@ def test_device_bvh_builder_is_byte_identical_to_host(ctx, pkg):
 def test_device_sah_builder_is_byte_identical_to_host(ctx, pkg):
     """ptmi_build_bvh_sah_device (level-synchronous binned SAH: reduce-by-key, LDS-privatised bins, one thread per node for the 21 planes, stable
     radix sorts, atomicMin split) against ptmi_build_bvh_sah on the host — itself pinned to the reference's JavaScript (tests/golden/c2sah_bvh.bin,
-    tests/test_host_buffers.py): random boxes with tied keys and -0, coincident boxes (leaves of several primitives), tiny inputs, flat
-    distributions, and the meshes of configs[3] and configs[2]."""
+    tests/test_host_buffers.py): random boxes with coincident centres (leaves of several primitives), tiny inputs, a flat
+    distribution, and the meshes of configs[3] and configs[2].  (bmin = c - e with a random e > 0 per primitive: no two sort keys are tied and no signed
+    zero reaches the builder.  Tied keys, signed zeros, axes without extent and other binades are tests/builder_cases.py's, through
+    tests/test_builder_edges_gpu.py.)"""
     nh = pkg.ptmi.NativeHost()
     rng = np.random.default_rng(23)
     for n in (1, 2, 3, 5, 64, 1000, 70001):
         c = rng.uniform(-1, 1, (n, 3)).astype(np.float32).astype(np.float64)
-        c[rng.integers(0, n, n // 3)] = c[0]        # coincident boxes: no plane separates them -> leaves of several primitives; tied keys: stability decides
+        c[rng.integers(0, n, n // 3)] = c[0]        # coincident boxes: no plane separates them -> leaves of several primitives
         c[rng.integers(0, n, max(n // 10, 1)), 1] = -0.0
         c[rng.integers(0, n, max(n // 10, 1)), 1] = 0.0
         if n == 1000:

@@ -1,7 +1,9 @@
-// Sanitizer driver for the host natives of libptmi (ptmi_host.cpp): both BVH builders (1 thread vs many), the OBJ parser, cross-view fusion, temporal accumulation, the noise statistic, the variance-guided filter and the slot plan of ptmi_render_views_frames.
+// Sanitizer driver for the host natives of libptmi (ptmi_host.cpp): both BVH builders (1 thread vs many; the edge and the outside of their domain on tables of exactly 2n - 1 rows), the OBJ parser, cross-view fusion, temporal accumulation, the noise statistic, the variance-guided filter and the slot plan of ptmi_render_views_frames.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -pthread tools/sanitize_host.cpp webgpu-path-tracer_amd/csrc/ptmi_host.cpp -o /tmp/san/asan && /tmp/san/asan
 //   g++ -std=c++17 -O1 -g -fsanitize=thread -pthread ... -o /tmp/san/tsan && /tmp/san/tsan
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -174,6 +176,119 @@ int main() {
     if (ptmi_view_slot_plan(3, zero, zero, one, 1, nullptr) != PTMI_ERR_INVALID_ARG || ptmi_view_slot_plan(2, zero, big, one, 1, nullptr) != PTMI_ERR_INVALID_ARG ||
         ptmi_view_slot_plan(2, zero, wide, one, 1, nullptr) != PTMI_ERR_INVALID_ARG || ptmi_view_slot_plan(2, nullptr, big, one, 1, nullptr) != PTMI_ERR_INVALID_ARG || one[0] != 0)
       return 26;
+  }
+  {  // The builders' domain (include/ptmi.h) on both host builders, in the shapes of tests/builder_cases.py.  Tables of exactly 2n - 1 rows and n order entries on the
+     // heap: one row more written is caught here.  Refused: a NaN, +inf and -inf in bmin and in bmax at the first, a middle and the last primitive, |x| = 1e30,
+     // bmin > bmax, four unit boxes one of which has bmax.x = inf; SAH only: a lone cube of extent 2e16 and 1000 boxes with n x area = 1.1e30 (before the check, and
+     // the bound on the node allocation behind it, each of these last three and the non-finite ones wrote past the 2n - 1 node records).  In the domain: the lone cube
+     // of extent 5.7e14, four unit boxes with 4 x area = 9.95e29, and 257 boxes on a dyadic grid full of signed zeros and point boxes — the same bytes for 1 and 8 threads.
+    struct Set {
+      std::vector<double> lo, hi;
+      size_t n() const { return lo.size() / 3; }
+    };
+    uint64_t x = 977;
+    auto next = [&x] {
+      x = x * 6364136223846793005ull + 1442695040888963407ull;
+      return (uint32_t)(x >> 33);
+    };
+    auto grid = [&](size_t n, bool zeros) {
+      Set s;
+      s.lo.resize(3 * n), s.hi.resize(3 * n);
+      const double half[3] = {0.0, 1.0 / 16, 1.0 / 8};
+      for (size_t i = 0; i < 3 * n; i++) {
+        const double c = ((double)(next() % 17) - 8.0) / 8.0, h = half[next() % 3];
+        s.lo[i] = c - h, s.hi[i] = c + h;
+        if (!zeros) continue;
+        switch (next() % 6) {
+          case 0: s.lo[i] = -0.0, s.hi[i] = 0.0; break;
+          case 1: s.lo[i] = s.hi[i] = -0.0; break;
+          case 2: s.lo[i] = s.hi[i] = 0.0; break;
+          case 3: s.lo[i] = s.hi[i] = c; break;
+          default: break;
+        }
+      }
+      return s;
+    };
+    // status of both builders on exact-size tables; with `same_bytes`, also that 1 and 8 threads write the same rows and order
+    auto run = [](const Set& s, int want_median, int want_sah, bool same_bytes) {
+      const size_t n = s.n();
+      int bad = 0;
+      std::vector<float> keep_m, keep_s;
+      std::vector<int64_t> keep_om, keep_os;
+      size_t keep_rows = 0;
+      for (const char* threads : {"1", "8"}) {
+        setenv("PTMI_BUILD_THREADS", threads, 1);
+        std::vector<float> rm(12 * (2 * n - 1)), rs(12 * (2 * n - 1));
+        std::vector<int64_t> om(n), os(n);
+        size_t rows = 0;
+        if (ptmi_build_bvh(n, s.lo.data(), s.hi.data(), 2, rm.data(), om.data()) != want_median) bad |= 1;
+        if (ptmi_build_bvh_sah(n, s.lo.data(), s.hi.data(), 2, rs.data(), os.data(), &rows) != want_sah) bad |= 2;
+        if (want_sah == PTMI_OK && (rows == 0 || rows > 2 * n - 1)) bad |= 4;
+        if (want_sah != PTMI_OK && rows != 0) bad |= 8;
+        if (same_bytes && threads[0] == '8' && (rm != keep_m || om != keep_om || rows != keep_rows || memcmp(rs.data(), keep_s.data(), rows * 48) || os != keep_os)) bad |= 16;
+        keep_m = rm, keep_s = rs, keep_om = om, keep_os = os, keep_rows = rows;
+      }
+      return bad;
+    };
+    const Set base = grid(64, false);
+    int k = 0, refused_failed = 0;
+    for (int in_hi = 0; in_hi < 2; in_hi++)
+      for (double v : {(double)NAN, (double)INFINITY, -(double)INFINITY})
+        for (size_t prim : {size_t(0), size_t(31), size_t(63)}) {
+          Set s = base;
+          (in_hi ? s.hi : s.lo)[3 * prim + (size_t)(k++ % 3)] = v;
+          if (int bad = run(s, PTMI_ERR_BAD_SCENE, PTMI_ERR_BAD_SCENE, false)) {
+            printf("builders' domain: %g in %s of primitive %zu was not refused (%d)\n", v, in_hi ? "bmax" : "bmin", prim, bad);
+            refused_failed = 30;  // (reported at the end of the block: the sets that used to overrun the node records come first)
+          }
+        }
+    {
+      Set s = base;
+      s.hi[3 * 5 + 1] = 1e30;
+      if (run(s, PTMI_ERR_BAD_SCENE, PTMI_ERR_BAD_SCENE, false)) return 31;
+      s = base;
+      s.lo[3 * 7 + 2] = -1e30;
+      if (run(s, PTMI_ERR_BAD_SCENE, PTMI_ERR_BAD_SCENE, false)) return 32;
+      s = base;
+      s.lo[3 * 9] = s.hi[3 * 9] + 0.125;
+      if (run(s, PTMI_ERR_BAD_SCENE, PTMI_ERR_BAD_SCENE, false)) return 33;
+      Set four;
+      four.lo = {0, 0, 0, 2, 0, 0, 0, 2, 0, 0, 0, 2}, four.hi = {1, 1, 1, 3, 1, 1, 1, 3, 1, 1, 1, 3};
+      four.hi[3] = INFINITY;
+      if (run(four, PTMI_ERR_BAD_SCENE, PTMI_ERR_BAD_SCENE, false)) return 34;
+      Set cube;
+      cube.lo = {0, 0, 0}, cube.hi = {2e16, 2e16, 2e16};
+      if (int bad = run(cube, PTMI_OK, PTMI_ERR_BAD_SCENE, false)) {
+        printf("builders' domain: the lone cube of extent 2e16 (%d)\n", bad);
+        return 35;
+      }
+      Set big = grid(1000, false);  // union [-1.125, 1.125]^3 or a little less; scaled so that 1000 x area = 1.1e30
+      double lo[3] = {1e30, 1e30, 1e30}, hi[3] = {-1e30, -1e30, -1e30};
+      for (size_t i = 0; i < 3000; i++) lo[i % 3] = std::min(lo[i % 3], big.lo[i]), hi[i % 3] = std::max(hi[i % 3], big.hi[i]);
+      const double e0 = hi[0] - lo[0], e1 = hi[1] - lo[1], e2 = hi[2] - lo[2], scale = std::sqrt(1.1e30 / (1000.0 * (e0 * e1 + e1 * e2 + e2 * e0)));
+      for (size_t i = 0; i < 3000; i++) big.lo[i] *= scale, big.hi[i] *= scale;
+      if (int bad = run(big, PTMI_OK, PTMI_ERR_BAD_SCENE, true)) {
+        printf("builders' domain: 1000 boxes with n x area = 1.1e30 (%d)\n", bad);
+        return 36;
+      }
+      cube.hi = {5.7e14, 5.7e14, 5.7e14};
+      if (run(cube, PTMI_OK, PTMI_OK, true)) return 37;
+      const double s4 = 2.88e14;
+      four.lo = {0, 0, 0, s4 - 1, s4 - 1, s4 - 1, s4 - 1, 0, 0, 0, s4 - 1, 0};
+      for (size_t i = 0; i < 12; i++) four.hi[i] = four.lo[i] + 1.0;
+      if (run(four, PTMI_OK, PTMI_OK, true)) return 38;
+      for (size_t n : {size_t(1), size_t(3), size_t(257)})
+        if (int bad = run(grid(n, true), PTMI_OK, PTMI_OK, true)) {
+          printf("builders' domain: %zu boxes with signed zeros (%d)\n", n, bad);
+          return 39;
+        }
+      char msg[256];
+      if (ptmi_check_bvh_boxes(1, cube.lo.data(), cube.hi.data(), 1, msg, sizeof msg) != PTMI_OK || msg[0]) return 40;
+      cube.hi = {2e16, 2e16, 2e16};
+      if (ptmi_check_bvh_boxes(1, cube.lo.data(), cube.hi.data(), 1, msg, sizeof msg) != PTMI_ERR_BAD_SCENE || !strstr(msg, "rule 4")) return 41;
+      if (ptmi_check_bvh_boxes(1, cube.lo.data(), cube.hi.data(), 0, nullptr, 0) != PTMI_OK) return 42;
+      if (refused_failed) return refused_failed;
+    }
   }
   puts("host natives: sanitizer run clean");
   return 0;

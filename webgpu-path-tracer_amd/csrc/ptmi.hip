@@ -34,7 +34,7 @@ using namespace ptmi;
 
 // csrc/ptmi_bvh_device.hip
 int ptmi_bvhdev_build_scene(void* stream, const float* d_tris, uint32_t n, const int32_t* h_meshes, int n_meshes, const float* h_xforms, int n_xforms, float* d_rows,
-                            float* d_tris_out, int* depth_out, uint32_t* bad_tri, int sah, uint32_t* n_nodes_out);
+                            float* d_tris_out, int* depth_out, uint32_t* bad_tri, int sah, uint32_t* n_nodes_out, int* refused);
 int ptmi_bvhdev_make_pairs(void* stream, const float* d_rows, uint32_t nn, float* d_pairs, int* d_leaf_table, uint32_t* n_multi);
 
 namespace {
@@ -1765,14 +1765,24 @@ static int build_scene_bvh_one(ptmi_ctx* c, bool sah) {
   if (e == hipSuccess) e = tris2.ensure(n * 96);
   if (e != hipSuccess) return fail(c, PTMI_ERR_NO_MEMORY, std::string("ptmi_build_scene_bvh: ") + hipGetErrorString(e));
   int depth = 0;
-  uint32_t bad = 0xffffffffu, n_nodes = 0;
+  uint32_t bad_pair[2] = {0xffffffffu, 0xffffffffu}, n_nodes = 0;  // [0] an index out of range, [1] a box outside the builders' domain
+  int refused = 0;
   const int r = ptmi_bvhdev_build_scene((void*)c->stream, c->d_tris.as<float>(), (uint32_t)n, c->h_meshes.data(), n_mesh, c->h_xforms.data(), n_xf, rows.as<float>(), tris2.as<float>(),
-                                         &depth, &bad, sah ? 1 : 0, &n_nodes);
-  if (r || bad != 0xffffffffu) {
+                                         &depth, bad_pair, sah ? 1 : 0, &n_nodes, &refused);
+  const uint32_t bad = bad_pair[0];
+  if (r || bad != 0xffffffffu || bad_pair[1] != 0xffffffffu || refused) {
     if (r == (int)hipErrorNotSupported) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_build_scene_bvh_sah: the SAH tree of these triangles is deeper than 4096 levels (no STACK_SIZE <= 64 can traverse it)");
     if (r) return fail(c, r == (int)hipErrorOutOfMemory ? PTMI_ERR_NO_MEMORY : PTMI_ERR_DEVICE, std::string("ptmi_build_scene_bvh: ") + hipGetErrorString((hipError_t)r));
-    char msg[160];
-    snprintf(msg, sizeof msg, "ptmi_build_scene_bvh: triangle %u: mesh_id / the mesh's global_id out of range (meshes %d, transforms %d)", bad, n_mesh, n_xf);
+    // (the context's previous triangles, rows and flags are untouched: `rows` and `tris2` are dropped here)
+    char msg[200];
+    if (bad != 0xffffffffu)
+      snprintf(msg, sizeof msg, "ptmi_build_scene_bvh: triangle %u: mesh_id / the mesh's global_id out of range (meshes %d, transforms %d)", bad, n_mesh, n_xf);
+    else if (bad_pair[1] != 0xffffffffu)
+      snprintf(msg, sizeof msg, "ptmi_build_scene_bvh: triangle %u: its world-space box is outside the builders' domain (rules 1-2: every coordinate finite and |x| < 1e30)", bad_pair[1]);
+    else if (refused == 4)
+      snprintf(msg, sizeof msg, "ptmi_build_scene_bvh_sah: %zu triangles x area of the scene's box is outside the SAH builders' domain (rule 4: n x area < 1e30)", n);
+    else
+      snprintf(msg, sizeof msg, "ptmi_build_scene_bvh_sah: a level of the tree asked for more nodes than a tree over %zu triangles has", n);
     return fail(c, PTMI_ERR_BAD_SCENE, msg);
   }
   c->d_tris = std::move(tris2);  // the triangles now sit in leaf order (the reference reorders them on the host, lib/scene.js:257)

@@ -26,6 +26,7 @@
 
 #include "../../include/ptmi.h"
 #include "ptmi_dbuf.h"
+#include "ptmi_bvh_domain.h"
 
 namespace {
 
@@ -583,10 +584,15 @@ __global__ void k_sah_rows(const SahTreeNode* __restrict__ tree, uint32_t total,
   }
 }
 
+// Why build_levels_sah returned hipErrorInvalidValue without having launched anything that writes through a split-derived index
+struct SahRefusal {
+  int rule = 0;     // 4 = the root box breaks rule 4 of the builders' domain (ptmi_bvh_domain.h); 5 = a level asked for more nodes than a tree over n primitives has
+  double cost = 0;  // rule 4: n x area of the root box
+};
 // The SAH level loop on boxes that are on the device: rows (12 floats per node; room for 2n-1) and the primitive order into the caller's
 // buffers, the number of rows into *n_nodes_out.  `d` owns the scratch.
 hipError_t build_levels_sah(hipStream_t stream, Dev& d, uint32_t n, const double* bmin, const double* bmax, int prim_type, float* rows, uint32_t* order_out, uint32_t* n_nodes_out,
-                            int* depth_out = nullptr) {
+                            int* depth_out = nullptr, SahRefusal* refusal = nullptr) {
   double *keys[2], *split_pos;
   uint64_t* packed[2];
   uint32_t *order[2], *major[2], *inner, *rank, *n_runs, *split_first, *size, *flat;
@@ -668,12 +674,30 @@ hipError_t build_levels_sah(hipStream_t stream, Dev& d, uint32_t n, const double
       TRY(rocprim::exclusive_scan(temp, tb, inner, rank, 0u, m, rocprim::plus<uint32_t>(), stream));
     }
     uint32_t tail[2];
+    SahAgg root_agg;
+    const bool at_root = total == 0;
     TRY(hipMemcpyAsync(&tail[0], rank + (m - 1), 4, hipMemcpyDeviceToHost, stream));
     TRY(hipMemcpyAsync(&tail[1], inner + (m - 1), 4, hipMemcpyDeviceToHost, stream));
+    if (at_root) TRY(hipMemcpyAsync(&root_agg, agg, sizeof root_agg, hipMemcpyDeviceToHost, stream));
     TRY(hipStreamSynchronize(stream));
+    if (at_root) {
+      // Rule 4 of the builders' domain on the root box, read back where the loop waits anyway.  So far only k_sah_decide has written anything
+      // a split decides, and that into tree[0] and slot 0 of the per-node arrays; everything below indexes through splits.
+      const double cost = ptmi_bvh_domain::sah_root_cost(n, root_agg.box.lo, root_agg.box.hi);
+      if (!ptmi_bvh_domain::sah_root_cost_ok(cost)) {
+        if (refusal) refusal->rule = 4, refusal->cost = cost;
+        return hipErrorInvalidValue;
+      }
+    }
     const uint32_t n_inner = tail[0] + tail[1];
     total += m;
     if (n_inner == 0) break;
+    // Every inner node has two non-empty children, so a level of a tree over n primitives has at most n / 2 inner nodes and the tree 2n - 1 nodes.  The domain's
+    // rules imply it; the bounds of level[] (n records), tree[], size[], flat[] and next[] (max_nodes each) do not rest on that argument.
+    if (2ull * n_inner > (unsigned long long)n || (unsigned long long)total + 2ull * n_inner > (unsigned long long)max_nodes) {
+      if (refusal) refusal->rule = 5;
+      return hipErrorInvalidValue;
+    }
     hipLaunchKernelGGL(k_level_keys, dim3((n + B - 1) / B), dim3(B), 0, stream, order[ocur], seg_of, axis, inner, level[cur], bmin, n, keys[0], packed[0]);
     {
       size_t tb = t_bytes;
@@ -708,7 +732,7 @@ hipError_t build_levels_sah(hipStream_t stream, Dev& d, uint32_t n, const double
   return hipSuccess;
 }
 
-hipError_t build_sah_on_device(hipStream_t stream, uint32_t n, const double* h_bmin, const double* h_bmax, int prim_type, float* h_rows, int64_t* h_order, size_t* n_nodes_out) {
+hipError_t build_sah_on_device(hipStream_t stream, uint32_t n, const double* h_bmin, const double* h_bmax, int prim_type, float* h_rows, int64_t* h_order, size_t* n_nodes_out, SahRefusal* refusal) {
   Dev d;
   const uint32_t nn = 2 * n - 1;
   double *bmin, *bmax;
@@ -721,7 +745,7 @@ hipError_t build_sah_on_device(hipStream_t stream, uint32_t n, const double* h_b
   TRY(hipMemcpyAsync(bmin, h_bmin, 3 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream));
   TRY(hipMemcpyAsync(bmax, h_bmax, 3 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream));
   uint32_t total = 0;
-  TRY(build_levels_sah(stream, d, n, bmin, bmax, prim_type, rows, order, &total));
+  TRY(build_levels_sah(stream, d, n, bmin, bmax, prim_type, rows, order, &total, nullptr, refusal));
   std::vector<uint32_t> ord(n);
   TRY(hipMemcpyAsync(h_rows, rows, 12 * (size_t)total * sizeof(float), hipMemcpyDeviceToHost, stream));
   TRY(hipMemcpyAsync(ord.data(), order, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
@@ -737,7 +761,7 @@ hipError_t build_sah_on_device(hipStream_t stream, uint32_t n, const double* h_b
 // matrix in double (gl-matrix vec3.transformMat4 on f32 inputs, lib/primitives/triangle.js:27-39), stored as f32, min / max over
 // the three, then AABB.pad() (lib/BVH/AABB.js:35-51: an axis thinner than 0.00005 grows by that much on both sides).
 __global__ void k_scene_boxes(const float* __restrict__ tris, uint32_t n, const int32_t* __restrict__ meshes, int n_meshes, const float* __restrict__ xforms, int n_xforms,
-                              double* __restrict__ bmin, double* __restrict__ bmax, uint32_t* __restrict__ first_bad) {
+                              double* __restrict__ bmin, double* __restrict__ bmax, uint32_t* __restrict__ first_bad) {  // first_bad[0]: an index out of range; first_bad[1]: a box outside the builders' domain
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float* t = tris + 24 * (size_t)i;
@@ -752,6 +776,7 @@ __global__ void k_scene_boxes(const float* __restrict__ tris, uint32_t n, const 
   if (gid >= 0)
     for (int k = 0; k < 16; k++) m[k] = (double)xforms[32 * (size_t)gid + k];
   double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  bool in_domain = true;
   for (int v = 0; v < 3; v++) {
     const double x = (double)t[4 * v], y = (double)t[4 * v + 1], z = (double)t[4 * v + 2];
     double w = m[3] * x + m[7] * y + m[11] * z + m[15];
@@ -759,6 +784,9 @@ __global__ void k_scene_boxes(const float* __restrict__ tris, uint32_t n, const 
     const double p[3] = {(double)(float)((m[0] * x + m[4] * y + m[8] * z + m[12]) / w), (double)(float)((m[1] * x + m[5] * y + m[9] * z + m[13]) / w),
                          (double)(float)((m[2] * x + m[6] * y + m[10] * z + m[14]) / w)};
     for (int k = 0; k < 3; k++) {
+      // rules 1 and 2 of the builders' domain (ptmi_bvh_domain.h), written so that a NaN fails.  On the corners themselves: Math.min / Math.max hand a NaN on
+      // to the box, js_min / js_max (exact on numbers) drop one that comes first
+      if (!(fabs(p[k]) < 1e30)) in_domain = false;
       lo[k] = v == 0 ? p[k] : js_min(lo[k], p[k]);
       hi[k] = v == 0 ? p[k] : js_max(hi[k], p[k]);
     }
@@ -766,9 +794,13 @@ __global__ void k_scene_boxes(const float* __restrict__ tris, uint32_t n, const 
   const double delta = 0.0001 / 2;
   for (int k = 0; k < 3; k++) {
     const bool thin = (hi[k] - lo[k]) < delta;
-    bmin[3 * (size_t)i + k] = thin ? lo[k] - delta : lo[k];
-    bmax[3 * (size_t)i + k] = thin ? hi[k] + delta : hi[k];
+    const double a = thin ? lo[k] - delta : lo[k], b = thin ? hi[k] + delta : hi[k];
+    bmin[3 * (size_t)i + k] = a;
+    bmax[3 * (size_t)i + k] = b;
+    // ... and on the padded box (rule 3 holds of any min / max of numbers)
+    if (!(fabs(a) < 1e30) || !(fabs(b) < 1e30)) in_domain = false;
   }
+  if (!in_domain) atomicMin(first_bad + 1, i);
 }
 
 // triangles into BVH leaf order (lib/scene.js:257)
@@ -823,6 +855,8 @@ extern "C" int ptmi_build_bvh_device(ptmi_ctx* ctx, size_t n_prims, const double
   if (n_prims == 0) return PTMI_OK;
   if (!bmin || !bmax || !nodes_out || !order_out) return ptmi_ctx_fail(ctx, PTMI_ERR_INVALID_ARG, "ptmi_build_bvh_device: null argument");
   if (n_prims > (size_t)1 << 27) return ptmi_ctx_fail(ctx, PTMI_ERR_UNSUPPORTED, "ptmi_build_bvh_device: more than 2^27 primitives");
+  char why[256];
+  if (ptmi_bvh_domain::check(n_prims, bmin, bmax, false, why, sizeof why, "ptmi_build_bvh_device")) return ptmi_ctx_fail(ctx, PTMI_ERR_BAD_SCENE, why);  // before any allocation or launch
   int r = ptmi_ctx_set_device(ctx);
   if (r) return r;
   void* s = nullptr;
@@ -844,15 +878,23 @@ extern "C" int ptmi_build_bvh_sah_device(ptmi_ctx* ctx, size_t n_prims, const do
   if (n_prims == 0) return PTMI_OK;
   if (!bmin || !bmax || !nodes_out || !order_out) return ptmi_ctx_fail(ctx, PTMI_ERR_INVALID_ARG, "ptmi_build_bvh_sah_device: null argument");
   if (n_prims > (size_t)1 << 27) return ptmi_ctx_fail(ctx, PTMI_ERR_UNSUPPORTED, "ptmi_build_bvh_sah_device: more than 2^27 primitives");
+  char why[256];
+  if (ptmi_bvh_domain::check(n_prims, bmin, bmax, true, why, sizeof why, "ptmi_build_bvh_sah_device")) return ptmi_ctx_fail(ctx, PTMI_ERR_BAD_SCENE, why);  // before any allocation or launch
   int r = ptmi_ctx_set_device(ctx);
   if (r) return r;
   void* s = nullptr;
   ptmi_stream(ctx, &s);
   hipError_t e;
+  SahRefusal refusal;
   try {
-    e = build_sah_on_device((hipStream_t)s, (uint32_t)n_prims, bmin, bmax, prim_type, nodes_out, order_out, n_nodes_out);
+    e = build_sah_on_device((hipStream_t)s, (uint32_t)n_prims, bmin, bmax, prim_type, nodes_out, order_out, n_nodes_out, &refusal);
   } catch (...) {
     return ptmi_ctx_fail(ctx, PTMI_ERR_NO_MEMORY, "ptmi_build_bvh_sah_device: host allocation failed");
+  }
+  if (refusal.rule) {
+    *n_nodes_out = 0;
+    return ptmi_ctx_fail(ctx, PTMI_ERR_BAD_SCENE, refusal.rule == 4 ? "ptmi_build_bvh_sah_device: primitives x area of their union is outside the SAH builders' domain (rule 4: n x area < 1e30)"
+                                                                    : "ptmi_build_bvh_sah_device: a level of the tree asked for more nodes than a tree over these primitives has (boxes outside the builders' domain)");
   }
   if (e == hipErrorNotSupported) return ptmi_ctx_fail(ctx, PTMI_ERR_UNSUPPORTED, "ptmi_build_bvh_sah_device: the SAH tree of these boxes is deeper than 4096 levels (no STACK_SIZE <= 64 can traverse it)");
   if (e != hipSuccess) return ptmi_ctx_fail(ctx, e == hipErrorOutOfMemory ? PTMI_ERR_NO_MEMORY : PTMI_ERR_DEVICE, hipGetErrorString(e));
@@ -862,9 +904,11 @@ extern "C" int ptmi_build_bvh_sah_device(ptmi_ctx* ctx, size_t n_prims, const do
 // ---- for ptmi.hip (ptmi_build_scene_bvh / prepare_scene): everything stays on the device -------------------------------------------
 // Builds the reference's median-split BVH (sah = 0) or its binned-SAH one (sah = 1) over the n triangles at d_tris (24 f32 each, upload order):
 // boxes, level loop, rows into d_rows (12 f32 x *n_nodes_out, room for 2n-1), the triangles in leaf order into d_tris_out.  meshes / transforms are host arrays (small).  *bad_tri = first
-// triangle whose mesh / transform index is out of range (0xffffffff = none).  Returns a hipError_t.
+// triangle whose mesh / transform index is out of range, bad_tri[1] = first triangle whose padded box breaks rules 1-2 of the builders' domain (0xffffffff = none); *refused = 4 or
+// 5 when the SAH level loop stopped on rule 4 or on its node-count guard (SahRefusal).  In each of these cases nothing was written to d_rows / d_tris_out that matters and the
+// result is hipSuccess: the caller reports it.  Returns a hipError_t.
 int ptmi_bvhdev_build_scene(void* stream_, const float* d_tris, uint32_t n, const int32_t* h_meshes, int n_meshes, const float* h_xforms, int n_xforms, float* d_rows,
-                            float* d_tris_out, int* depth_out, uint32_t* bad_tri, int sah, uint32_t* n_nodes_out) {
+                            float* d_tris_out, int* depth_out, uint32_t* bad_tri, int sah, uint32_t* n_nodes_out, int* refused) {
   hipStream_t stream = (hipStream_t)stream_;
   try {
     Dev d;
@@ -877,19 +921,29 @@ int ptmi_bvhdev_build_scene(void* stream_, const float* d_tris, uint32_t n, cons
     TRY(d.alloc(&meshes, 4 * (size_t)n_meshes));
     TRY(d.alloc(&xforms, 32 * (size_t)n_xforms));
     TRY(d.alloc(&order, n));
-    TRY(d.alloc(&bad, 1));
-    const uint32_t none = 0xffffffffu;
-    TRY(hipMemcpyAsync(bad, &none, 4, hipMemcpyHostToDevice, stream));
+    TRY(d.alloc(&bad, 2));
+    const uint32_t none = 0xffffffffu, none2[2] = {none, none};
+    *refused = 0;
+    TRY(hipMemcpyAsync(bad, none2, 8, hipMemcpyHostToDevice, stream));
     if (n_meshes) TRY(hipMemcpyAsync(meshes, h_meshes, 16 * (size_t)n_meshes, hipMemcpyHostToDevice, stream));
     if (n_xforms) TRY(hipMemcpyAsync(xforms, h_xforms, 128 * (size_t)n_xforms, hipMemcpyHostToDevice, stream));
     const unsigned B = 256;
     hipLaunchKernelGGL(k_scene_boxes, dim3((n + B - 1) / B), dim3(B), 0, stream, d_tris, n, meshes, n_meshes, xforms, n_xforms, bmin, bmax, bad);
-    TRY(hipMemcpyAsync(bad_tri, bad, 4, hipMemcpyDeviceToHost, stream));
+    TRY(hipMemcpyAsync(bad_tri, bad, 8, hipMemcpyDeviceToHost, stream));
     TRY(hipStreamSynchronize(stream));
-    if (*bad_tri != none) return (int)hipSuccess;  // the caller reports it
+    if (bad_tri[0] != none || bad_tri[1] != none) return (int)hipSuccess;  // the caller reports it
     *n_nodes_out = 2 * n - 1;
-    if (sah) TRY(build_levels_sah(stream, d, n, bmin, bmax, 2, d_rows, order, n_nodes_out, depth_out));  // BVH.generate_bvh_heirarchy_SAH (bvhNode.js:108-283), the opt-in
-    else TRY(build_levels(stream, d, n, bmin, bmax, 2, d_rows, order, depth_out));
+    if (sah) {  // BVH.generate_bvh_heirarchy_SAH (bvhNode.js:108-283), the opt-in
+      SahRefusal refusal;
+      const hipError_t e = build_levels_sah(stream, d, n, bmin, bmax, 2, d_rows, order, n_nodes_out, depth_out, &refusal);
+      if (refusal.rule) {
+        *refused = refusal.rule;
+        return (int)hipSuccess;  // the caller reports it
+      }
+      TRY(e);
+    } else {
+      TRY(build_levels(stream, d, n, bmin, bmax, 2, d_rows, order, depth_out));
+    }
     hipLaunchKernelGGL(k_permute_triangles, dim3((6 * n + B - 1) / B), dim3(B), 0, stream, reinterpret_cast<const float4*>(d_tris), order, n,
                        reinterpret_cast<float4*>(d_tris_out));
     TRY(hipGetLastError());

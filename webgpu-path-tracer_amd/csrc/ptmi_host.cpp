@@ -24,6 +24,7 @@
 #include "../../include/ptmi_fuse.h"
 #include "../../include/ptmi_accumulate.h"
 #include "../../include/ptmi_noise.h"
+#include "ptmi_bvh_domain.h"
 
 namespace {
 // Math.min / Math.max (lib/BVH/AABB.js:8-28) on finite values: -0 < +0 whatever the argument order
@@ -129,6 +130,7 @@ extern "C" int ptmi_build_bvh(size_t n_prims, const double* bmin, const double* 
   if (n_prims == 0) return PTMI_OK;
   if (!bmin || !bmax || !nodes_out || !order_out) return PTMI_ERR_INVALID_ARG;
   if (n_prims > (size_t)1 << 27) return PTMI_ERR_UNSUPPORTED;
+  if (ptmi_bvh_domain::check(n_prims, bmin, bmax, false, nullptr, 0, "")) return PTMI_ERR_BAD_SCENE;
   Builder b;
   b.bmin = bmin;
   b.bmax = bmax;
@@ -261,6 +263,7 @@ struct SahBuilder {
   std::atomic<int64_t> n_alloc{1};
   std::atomic<int> running{1};  // threads at work on subtrees (SAH splits are lopsided: a fixed fork depth leaves most threads idle, so a subtree forks whenever one is free)
   int max_threads = 1;
+  std::atomic<bool> overrun{false};  // a split asked for records past the 2n - 1 there are: the build is abandoned
   void build_subtree(int64_t root) {
     std::vector<int64_t> todo{root};
     std::vector<std::future<void>> kids;
@@ -291,6 +294,12 @@ struct SahBuilder {
         else break;
       }
       const int64_t l = n_alloc.fetch_add(2), r = l + 1;
+      // Inside the domain (ptmi_bvh_domain.h) a tree has at most 2n - 1 nodes and this never fires; memory safety does not rest on that argument
+      if (r >= (int64_t)nodes.size()) {
+        overrun.store(true);
+        nodes[id].leaf = true;
+        continue;
+      }
       nodes[l].start = start, nodes[l].end = split;
       nodes[r].start = split + 1, nodes[r].end = end;
       nodes[id].left = l, nodes[id].right = r, nodes[id].axis = axis;
@@ -320,7 +329,7 @@ struct SahBuilder {
     nodes[0].start = 0;
     nodes[0].end = n - 1;
     build_subtree(0);
-    nodes.resize((size_t)n_alloc.load());
+    if (!overrun.load()) nodes.resize((size_t)n_alloc.load());
   }
 };
 
@@ -333,6 +342,7 @@ extern "C" int ptmi_build_bvh_sah(size_t n_prims, const double* bmin, const doub
   if (n_prims == 0) return PTMI_OK;
   if (!bmin || !bmax || !nodes_out || !order_out) return PTMI_ERR_INVALID_ARG;
   if (n_prims > (size_t)1 << 27) return PTMI_ERR_UNSUPPORTED;
+  if (ptmi_bvh_domain::check(n_prims, bmin, bmax, true, nullptr, 0, "")) return PTMI_ERR_BAD_SCENE;
   try {
     SahBuilder b;
     b.bmin = bmin, b.bmax = bmax, b.order = order_out;
@@ -341,6 +351,7 @@ extern "C" int ptmi_build_bvh_sah(size_t n_prims, const double* bmin, const doub
     if (const char* e = getenv("PTMI_BUILD_THREADS")) hw = (unsigned)std::max(1, atoi(e));
     hw = std::min(hw ? hw : 1u, 32u);
     b.build((int64_t)n_prims, (int)hw);
+    if (b.overrun.load()) return PTMI_ERR_BAD_SCENE;
     // flattenBVH (bvhBuilder.js:37-54): pre-order ids; populate_links (bvhNode.js:76-93): the skip link
     const size_t nn = b.nodes.size();
     std::vector<int64_t> flat_id(nn, -1);
@@ -386,6 +397,14 @@ extern "C" int ptmi_build_bvh_sah(size_t n_prims, const double* bmin, const doub
     return PTMI_ERR_NO_MEMORY;
   }
   return PTMI_OK;
+}
+
+
+extern "C" int ptmi_check_bvh_boxes(size_t n_prims, const double* bmin, const double* bmax, int sah, char* msg, size_t msg_len) {
+  if (msg && msg_len) msg[0] = 0;
+  if (n_prims == 0) return PTMI_OK;
+  if (!bmin || !bmax) return PTMI_ERR_INVALID_ARG;
+  return ptmi_bvh_domain::check(n_prims, bmin, bmax, sah != 0, msg_len ? msg : nullptr, msg_len, sah ? "ptmi_build_bvh_sah" : "ptmi_build_bvh") ? PTMI_ERR_BAD_SCENE : PTMI_OK;
 }
 
 

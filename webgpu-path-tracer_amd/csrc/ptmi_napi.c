@@ -78,6 +78,7 @@ FN(ptmi_get_stats)
 FN(ptmi_reset_stats)
 FN(ptmi_build_bvh)
 FN(ptmi_build_bvh_sah)
+FN(ptmi_check_bvh_boxes)
 FN(ptmi_build_bvh_device)
 FN(ptmi_build_scene_bvh)
 FN(ptmi_build_scene_bvh_sah)
@@ -118,7 +119,7 @@ static int load_lib(char* err, size_t errlen) {
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
   LOAD(ptmi_render_views_frames) LOAD(ptmi_render_aov_frames) LOAD(ptmi_render_views_until_each)
   LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_default_guided_params) LOAD(ptmi_denoise_views_guided) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_default_accumulate_params) LOAD(ptmi_accumulate_views) LOAD(ptmi_read_accumulated) LOAD(ptmi_release_accumulated) LOAD(ptmi_denoise_views_accumulated) LOAD(ptmi_set_view_moments) LOAD(ptmi_read_moments) LOAD(ptmi_release_moments) LOAD(ptmi_default_noise_params) LOAD(ptmi_view_noise_stats) LOAD(ptmi_render_views_until) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
-  LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah)
+  LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_check_bvh_boxes) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah)
   LOAD(ptmi_obj_parse) LOAD(ptmi_free) LOAD(ptmi_device_count) LOAD(ptmi_reduce_info)
   return 0;
 }
@@ -1141,6 +1142,13 @@ static napi_value build_bvh_common(napi_env env, napi_callback_info info, int sa
                       : p_ptmi_build_bvh(n, (const double*)bmin, (const double*)bmax, pt, (float*)pn, tmp);
   if (st) {
     free(tmp);
+    if (!c && st == PTMI_ERR_BAD_SCENE) {  // the host builders have no context to leave their sentence in: boxes outside the builders' domain (include/ptmi.h)
+      char why[256], msg[384];
+      p_ptmi_check_bvh_boxes(n, (const double*)bmin, (const double*)bmax, sah == 1, why, sizeof why);
+      snprintf(msg, sizeof msg, "ptmi status %d: %s", st, why);
+      napi_throw_error(env, NULL, msg);
+      return NULL;
+    }
     return throw_status(env, c, st, sah == 1 ? "ptmi_build_bvh_sah" : sah == 2 ? "ptmi_build_bvh_device" : "ptmi_build_bvh");
   }
   for (size_t i = 0; i < n; i++) ((int32_t*)po)[i] = (int32_t)tmp[i];

@@ -123,7 +123,13 @@ class Mesh:
         wy = ((m[1] * x + m[5] * y + m[9] * z + m[13]) / w).astype(np.float32)
         wz = ((m[2] * x + m[6] * y + m[10] * z + m[14]) / w).astype(np.float32)
         W = np.stack([wx, wy, wz], axis=-1).astype(np.float64)  # world-space, f32 values
-        self.bmin, self.bmax = _pad(W.min(axis=1), W.max(axis=1))
+        # Math.min / Math.max (AABB.bbox_triangle, lib/BVH/AABB.js:12-24) order -0 below +0 whatever the vertex order; numpy's min / max keep
+        # whichever zero they meet first
+        lo, hi = W.min(axis=1), W.max(axis=1)
+        zero = W == 0
+        lo = np.where((lo == 0) & (zero & np.signbit(W)).any(axis=1), -0.0, lo)
+        hi = np.where((hi == 0) & (zero & ~np.signbit(W)).any(axis=1), 0.0, hi)
+        self.bmin, self.bmax = _pad(lo, hi)
 
 
 # ----------------------------------------------------------------------------- lib/primitives/objReader.js

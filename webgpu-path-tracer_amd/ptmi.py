@@ -33,6 +33,7 @@ SYMBOLS = [
     "ptmi_set_view_moments", "ptmi_read_moments", "ptmi_moments_device_ptr", "ptmi_release_moments",
     "ptmi_default_noise_params", "ptmi_view_noise_stats", "ptmi_noise_images", "ptmi_noise_reference", "ptmi_render_views_until",
     "ptmi_render_views_frames", "ptmi_render_aov_frames", "ptmi_render_views_until_each", "ptmi_view_slot_plan",
+    "ptmi_check_bvh_boxes",
 ]
 
 VIEW_SLOT_TABLE_MAX_WORDS = 1 << 24  # PTMI_VIEW_SLOT_TABLE_MAX_WORDS
@@ -168,6 +169,8 @@ def load_library(build=False, path=None):
     L.ptmi_build_bvh.argtypes = [sz, fp, fp, i32, fp, fp]
     L.ptmi_build_bvh_sah.argtypes = [sz, fp, fp, i32, fp, fp, ctypes.POINTER(sz)]
     L.ptmi_build_bvh_device.argtypes = [vp, sz, fp, fp, i32, fp, fp]
+    if hasattr(L, "ptmi_check_bvh_boxes"):  # (an older A/B build loaded through PTMI_LIB has no stated domain)
+        L.ptmi_check_bvh_boxes.argtypes = [sz, fp, fp, i32, ctypes.c_char_p, sz]
     L.ptmi_build_scene_bvh.argtypes = [vp]
     L.ptmi_build_scene_bvh_sah.argtypes = [vp]
     L.ptmi_scene_bvh_info.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
@@ -464,6 +467,12 @@ class NativeHost:
     def __init__(self):
         self.lib = load_library()
 
+    def _why(self, bmin, bmax, sah):
+        """The sentence of ptmi_check_bvh_boxes for boxes a host builder refused (these have no context to leave it in)."""
+        msg = ctypes.create_string_buffer(256)
+        self.lib.ptmi_check_bvh_boxes(bmin.shape[0], _ptr(bmin), _ptr(bmax), 1 if sah else 0, msg, len(msg))
+        return msg.value.decode()
+
     def build_bvh(self, bmin, bmax, prim_type=2):
         bmin = np.ascontiguousarray(bmin, np.float64)
         bmax = np.ascontiguousarray(bmax, np.float64)
@@ -472,7 +481,7 @@ class NativeHost:
         order = np.zeros(n, np.int64)
         st = self.lib.ptmi_build_bvh(n, _ptr(bmin), _ptr(bmax), prim_type, _ptr(nodes), _ptr(order))
         if st != 0:
-            raise PtmiError(st, "ptmi_build_bvh failed")
+            raise PtmiError(st, self._why(bmin, bmax, False) or "ptmi_build_bvh failed")
         return nodes, order
 
 
@@ -486,7 +495,7 @@ class NativeHost:
         count = ctypes.c_size_t()
         st = self.lib.ptmi_build_bvh_sah(n, _ptr(bmin), _ptr(bmax), prim_type, _ptr(nodes), _ptr(order), ctypes.byref(count))
         if st != 0:
-            raise PtmiError(st, "ptmi_build_bvh_sah failed")
+            raise PtmiError(st, self._why(bmin, bmax, True) or "ptmi_build_bvh_sah failed")
         return nodes[: count.value].copy(), order
 
     def parse_obj(self, text):
