@@ -563,8 +563,12 @@ int ptmi_render_views_until(ptmi_ctx* ctx, const float* views16, uint32_t n_view
  * the views (ptmi_view_slot_plan, below); everything that can fail for want of memory — the stacks, the table — is allocated before anything is enqueued, and a failing
  * call leaves the stacks as it found them.  PTMI_ERR_INVALID_ARG: a null array, n_views == 0, all counts zero, sum(frame_counts) >= 2^31, or a table of more than
  * PTMI_VIEW_SLOT_TABLE_MAX_WORDS words.
- * THE CONSUMERS of the stacks (ptmi_denoise_views*, ptmi_fuse_views, ptmi_accumulate_views, ptmi_resolve_view_rgba8) take ONE frame_num per call and a view range:
- * views of equal count, however their frame numbers differ, go through them as before; a caller whose counts differ passes them runs of views of equal count. */
+ * THE CONSUMERS of such stacks are the *_frames calls below ("CONSUMERS WITH PER-VIEW FRAME COUNTS"): ptmi_denoise_views_frames, ptmi_denoise_views_guided_frames,
+ * ptmi_fuse_views_frames and ptmi_accumulate_views_frames take one count per view of the stack and a view range, in one call.  The calls that take ONE frame_num
+ * (ptmi_denoise_views, ptmi_denoise_views_guided, ptmi_fuse_views with source 0, ptmi_accumulate_views) stay what they were and are right for a stack whose views all sum
+ * the same number of frames, however their frame numbers differ.  Passing them runs of views of equal count is right for the two denoisers only, which look at one view
+ * at a time; fusion's window and accumulation's lookup cross the run's ends, where the neighbour's sums would be divided by the wrong count.  Three consumers need
+ * nothing new: ptmi_denoise_views_accumulated and ptmi_fuse_views(source = 1) read means (F = 1), and ptmi_resolve_view_rgba8 is one view per call. */
 int ptmi_render_views_frames(ptmi_ctx* ctx, const float* views16, uint32_t n_views, const uint32_t* first_frames, const uint32_t* frame_counts, int reset);
 /* ptmi_render_aov with ptmi_render_views_frames' numbering: view v's layers 0 and 1 sum its frames first_frames[v] .. + frame_counts[v] - 1 in frame order, layer 2
  * keeps the view's last frame of the call; a view with count 0 is neither read nor written.  Arguments and errors as ptmi_render_views_frames. */
@@ -577,6 +581,48 @@ int ptmi_render_aov_frames(ptmi_ctx* ctx, const float* views16, uint32_t n_views
  * ptmi_render_views_frames(first_frames, frames_done, reset != 0) leaves.  Errors as ptmi_render_views_until. */
 int ptmi_render_views_until_each(ptmi_ctx* ctx, const float* views16, uint32_t n_views, const uint32_t* first_frames, uint32_t frames_per_round, uint32_t max_frames,
                                  const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out);
+
+/* CONSUMERS WITH PER-VIEW FRAME COUNTS.  The four calls on the stacks, their *_images forms and their CPU references with one divisor PER VIEW in place of the one
+ * frame_num: everywhere a definition above divides a colour sum S by F — "prepare" (c = S.rgb / F), the denoisers' remodulation and pass-through (S.rgb / F, S.a / F),
+ * "Fusion" steps 2-3 and its pass-through, "Temporal accumulation" own, mean and pass-through — it divides by F_u, THE FRAME COUNT OF THE VIEW u THAT S BELONGS TO: the
+ * output view's own count for p and for the output, the neighbour's for the pixel q looked up in view u (fusion: every u of the window; accumulation: u = v - 1, whose
+ * validity test finite(S / F_{v-1}) is thereby the one view v-1 itself applied).  Nothing else in the arithmetic changes, and the operation order stays that of
+ * include/ptmi_denoise.h, ptmi_guided.h, ptmi_fuse.h and ptmi_accumulate.h; with all counts equal every result is the one-frame_num call's, bit for bit.
+ * *_views_frames: frame_nums has one f32 per view OF THE STACK, indexed by absolute view number as views16 is.  Only the entries a call reads are validated; the rest
+ * may hold anything, NaN and 0 included.  The entries read: the denoisers [first_view, first_view + n_views); fusion that range widened by `radius` on both sides and
+ * clipped to the stack; accumulation the range, and first_view - 1 when resume != 0.  *_images_frames and *_reference_frames: frame_nums has n_images entries and all are
+ * read (with history_in, image 0's entry serves the lookup).  An entry that is read and is not finite or not > 0 gives PTMI_ERR_INVALID_ARG naming the view; a null
+ * frame_nums gives the same error; both before any allocation or launch.  Every other error, and the order of the errors, is the sibling's.  ptmi_fuse_views_frames has no
+ * `source`: it reads the view stack (the denoised stack holds means and needs no count).  The calls stay asynchronous on the context's stream: the counts travel to
+ * the device in a staged table — behind the material bytes of the view table for fusion and accumulation, in a table of their own for the denoisers — which, like
+ * everything that can fail for want of memory, is allocated before anything is enqueued; a failing call leaves every stack as it found it.  The kernels that read a
+ * count (csrc/: k_denoise_prepare_frames, k_denoise_level_frames, k_guided_level_frames, k_fuse_frames, k_accumulate_view_frames) stand beside the ones above, which the
+ * one-frame_num calls keep launching; the levels before the last, k_guided_variance, k_guided_blur and k_accumulated_variance read no F and are shared.  Views with a
+ * count of 0 inside the range a call reads are refused, not skipped. */
+int ptmi_denoise_views_frames(ptmi_ctx* ctx, const ptmi_denoise_params* params, const float* frame_nums, uint32_t first_view, uint32_t n_views);
+int ptmi_denoise_views_guided_frames(ptmi_ctx* ctx, const ptmi_guided_params* params, const float* frame_nums, uint32_t first_view, uint32_t n_views);
+int ptmi_fuse_views_frames(ptmi_ctx* ctx, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, uint32_t first_view, uint32_t n_views);
+int ptmi_accumulate_views_frames(ptmi_ctx* ctx, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, uint32_t first_view, uint32_t n_views,
+                                 int resume);
+int ptmi_denoise_images_frames(ptmi_ctx* ctx, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const float* frame_nums,
+                               const ptmi_denoise_params* params, float* out);
+int ptmi_denoise_images_guided_frames(ptmi_ctx* ctx, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images,
+                                      const float* frame_nums, const ptmi_guided_params* params, float* out, float* var_out);
+int ptmi_fuse_images_frames(ptmi_ctx* ctx, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
+                            float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out);
+int ptmi_accumulate_images_frames(ptmi_ctx* ctx, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                  const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
+                                  const float* history_in, float* out);
+/* ... and without a GPU (ptmi_denoise_reference, ptmi_denoise_guided_reference, ptmi_fuse_reference, ptmi_accumulate_reference with frame_nums [n_images]) */
+int ptmi_denoise_reference_frames(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const float* frame_nums, const ptmi_denoise_params* params,
+                                  float* out);
+int ptmi_denoise_guided_reference_frames(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, const float* frame_nums,
+                                         const ptmi_guided_params* params, float* out, float* var_out);
+int ptmi_fuse_reference_frames(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums, float fov_degrees,
+                               const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out);
+int ptmi_accumulate_reference_frames(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                     const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
+                                     const float* history_in, float* out, int threads);
 
 /* Test hook, no GPU: the SLOT TABLE ptmi_render_views_frames and ptmi_render_aov_frames upload behind the call's view matrices, u32 words:
  *   words [4 v .. 4 v + 3], v < n_views   view v's record {first slot, frame count, first frame number, next view with a non-zero count or n_views}; a view with

@@ -1,0 +1,215 @@
+"""The consumers with one frame count per view, without a GPU: the calls are declared, bound and exported everywhere the C ABI is, and the four *_reference_frames are
+tied BIT FOR BIT to the references that exist by the two identities of tests/consumer_frames_cases.py — pre-division for fusion and accumulation, per view for the two
+denoisers — so they inherit those references' float64 readings and need no tolerance of their own."""
+import ctypes
+import json
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import accumulate_cases as ac
+import consumer_frames_cases as cf
+import denoise_cases as dc
+import fuse_cases as fc
+import guided_cases as gc
+from conftest import ROOT, assert_same_bits
+
+VIEWS = ["ptmi_denoise_views_frames", "ptmi_denoise_views_guided_frames", "ptmi_fuse_views_frames", "ptmi_accumulate_views_frames"]
+IMAGES = ["ptmi_denoise_images_frames", "ptmi_denoise_images_guided_frames", "ptmi_fuse_images_frames", "ptmi_accumulate_images_frames"]
+REFERENCES = ["ptmi_denoise_reference_frames", "ptmi_denoise_guided_reference_frames", "ptmi_fuse_reference_frames", "ptmi_accumulate_reference_frames"]
+SIZES = fc.SIZES[1:]  # 100 x 37 and 130 x 70 (the 7 x 5 image has no room for five views' disparities)
+
+
+def test_prototypes_bindings_and_exports(pkg, hooks):
+    hdr = open(os.path.join(ROOT, "include", "ptmi.h")).read()
+    declared = set(re.findall(r"\b(ptmi_[a-z0-9_]+)\s*\(", hdr))
+    L = pkg.load_library()
+    for name in VIEWS + IMAGES + REFERENCES:
+        assert name in declared, name
+        assert name in pkg.ptmi.SYMBOLS, name
+        assert hasattr(L, name) and hasattr(hooks, name), name
+        assert getattr(L, name).argtypes, name
+    assert L.ptmi_version() == 5 and "#define PTMI_API_VERSION 5" in hdr
+    assert "int ptmi_denoise_views_frames(ptmi_ctx* ctx, const ptmi_denoise_params* params, const float* frame_nums, uint32_t first_view, uint32_t n_views);" in hdr
+    assert "int ptmi_denoise_views_guided_frames(ptmi_ctx* ctx, const ptmi_guided_params* params, const float* frame_nums, uint32_t first_view, uint32_t n_views);" in hdr
+    assert "int ptmi_fuse_views_frames(ptmi_ctx* ctx, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, uint32_t first_view, uint32_t n_views);" in hdr
+    assert re.search(r"int ptmi_accumulate_views_frames\(ptmi_ctx\* ctx, const ptmi_accumulate_params\* params, const float\* views16, const float\* frame_nums, uint32_t first_view, uint32_t n_views,\s*int resume\);", hdr)
+    for m in ("denoise_views_frames", "denoise_views_guided_frames", "fuse_views_frames", "accumulate_views_frames", "denoise_images_frames", "denoise_images_guided_frames",
+              "fuse_images_frames", "accumulate_images_frames"):
+        assert callable(getattr(pkg.Context, m)), m
+    for f in ("denoise_reference_frames", "denoise_guided_reference_frames", "fuse_reference_frames", "accumulate_reference_frames"):
+        assert callable(getattr(pkg.ptmi, f)), f
+    doc = hdr[hdr.index("CONSUMERS WITH PER-VIEW FRAME COUNTS."):hdr.index("int ptmi_denoise_views_frames(")]
+    for word in ("THE FRAME COUNT OF THE VIEW u THAT S BELONGS TO", "OF THE STACK", "NaN and 0 included", "widened by `radius`", "first_view - 1 when resume != 0",
+                 "PTMI_ERR_INVALID_ARG naming the view", "before anything is enqueued", "refused, not skipped"):
+        assert word in doc, word
+    old = hdr[hdr.index("THE CONSUMERS of such stacks"):hdr.index("int ptmi_render_views_frames(")]
+    for word in ("ptmi_denoise_views_accumulated", "ptmi_fuse_views(source = 1)", "ptmi_resolve_view_rgba8", "one view per call"):
+        assert word in old, word
+    assert "passes them runs of views of equal count" not in hdr, "the advice that is wrong for fusion and accumulation"
+    assert len(re.findall(r"typedef struct ptmi_\w+ \{", hdr)) == 9, "no new struct"
+
+
+def test_null_context_null_counts_and_bad_counts(pkg, hooks):
+    a = np.zeros(64, np.float32)
+    vp = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    for L in (pkg.load_library(), hooks):
+        assert L.ptmi_denoise_views_frames(None, None, vp(a), 0, 1) == -1
+        assert L.ptmi_denoise_views_guided_frames(None, None, vp(a), 0, 1) == -1
+        assert L.ptmi_fuse_views_frames(None, None, vp(a), vp(a), 0, 1) == -1
+        assert L.ptmi_accumulate_views_frames(None, None, vp(a), vp(a), 0, 1, 0) == -1
+        assert L.ptmi_denoise_images_frames(None, vp(a), vp(a), 1, 1, 1, vp(a), None, vp(a)) == -1
+        assert L.ptmi_denoise_images_guided_frames(None, vp(a), vp(a), vp(a), 1, 1, 1, vp(a), None, vp(a), None) == -1
+        assert L.ptmi_fuse_images_frames(None, vp(a), vp(a), vp(a), 1, 1, 1, vp(a), 60.0, None, 0, None, vp(a)) == -1
+        assert L.ptmi_accumulate_images_frames(None, vp(a), vp(a), vp(a), vp(a), 1, 1, 1, vp(a), 60.0, None, 0, None, None, vp(a)) == -1
+    S, L3, views = fc.inputs(100, 37, 2)
+    _, M, _, _, _ = ac.inputs(100, 37, 2, 4)
+    calls = (lambda F: pkg.ptmi.denoise_reference_frames(S, L3, F), lambda F: pkg.ptmi.denoise_guided_reference_frames(S, M, L3, F),
+             lambda F: pkg.ptmi.fuse_reference_frames(S, L3, views, F, fc.FOV, fc.LAMBERTIAN), lambda F: pkg.ptmi.accumulate_reference_frames(S, M, L3, views, F, fc.FOV, fc.LAMBERTIAN))
+    for call in calls:
+        for bad in (None, (1.0, np.nan), (np.inf, 1.0), (0.0, 1.0), (1.0, -2.0)):
+            with pytest.raises(pkg.PtmiError) as e:
+                call(bad)
+            assert e.value.status == -1, bad
+        call((1.0, 3.0))
+    with pytest.raises(AssertionError):
+        pkg.ptmi.denoise_reference_frames(S, L3, (1.0, 2.0, 3.0))  # the binding: one count per image
+
+
+# ------------------------------------------------------------------------------------------------------------------- pre-division: fusion
+@pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d" % s)
+@pytest.mark.parametrize("radius", cf.RADII)
+def test_fusion_with_counts_is_fusion_of_the_predivided_sums(pkg, size, radius):
+    S, L, views = fc.inputs(size[0], size[1], 5)
+    F = cf.counts(5)
+    prm = pkg.ptmi.default_fuse_params(radius=radius)
+    got = pkg.ptmi.fuse_reference_frames(S, L, views, F, fc.FOV, fc.LAMBERTIAN, prm)
+    want = pkg.ptmi.fuse_reference(cf.predivided(S, F), L, views, 1.0, fc.FOV, fc.LAMBERTIAN, prm)
+    assert_same_bits(got, want, "fuse_reference_frames against the pre-divided sums")
+    for v in range(4):  # ... and the counts matter: one run per count, the header's old advice, gives another image (the last view looks away and gathers nothing)
+        runs = pkg.ptmi.fuse_reference(S, L, views, float(F[v]), fc.FOV, fc.LAMBERTIAN, prm)[v]
+        assert not np.array_equal(runs.view(np.uint32), got[v].view(np.uint32)), v
+
+
+def test_fusion_with_equal_counts_is_the_existing_reference(pkg):
+    S, L, views = fc.inputs(130, 70, 5)
+    for F in (3.0, 4.0, 7.0):
+        assert_same_bits(pkg.ptmi.fuse_reference_frames(S, L, views, [F] * 5, fc.FOV, fc.LAMBERTIAN), pkg.ptmi.fuse_reference(S, L, views, F, fc.FOV, fc.LAMBERTIAN), "F = %g" % F)
+
+
+# ------------------------------------------------------------------------------------------------------------------- pre-division: accumulation
+@pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d" % s)
+@pytest.mark.parametrize("frames", ac.FRAMES_PER_VIEW)
+def test_accumulation_with_counts_is_accumulation_of_the_predivided_sums(pkg, size, frames):
+    S, M, L, views, _ = ac.inputs(size[0], size[1], 5, frames)
+    F = cf.counts(5)
+    for prm in (None, pkg.ptmi.default_accumulate_params(max_history=2.0, min_frames=2)):
+        got = pkg.ptmi.accumulate_reference_frames(S, M, L, views, F, ac.FOV, ac.LAMBERTIAN, prm)
+        want = pkg.ptmi.accumulate_reference(cf.predivided(S, F), M, L, views, 1.0, ac.FOV, ac.LAMBERTIAN, prm)
+        assert_same_bits(got, want, "accumulate_reference_frames against the pre-divided sums")
+    other = pkg.ptmi.accumulate_reference(S, M, L, views, float(F[1]), ac.FOV, ac.LAMBERTIAN)
+    assert not np.array_equal(other[0, 2].view(np.uint32), got[0, 2].view(np.uint32))
+
+
+def test_accumulation_from_a_given_state_reads_image_0s_count_for_the_lookup(pkg):
+    S, M, L, views, _ = ac.inputs(100, 37, 5, 4)
+    F = cf.counts(5)
+    whole = pkg.ptmi.accumulate_reference_frames(S, M, L, views, F, ac.FOV, ac.LAMBERTIAN)
+    hist = np.stack([whole[1, 1], whole[2, 1]])
+    step = pkg.ptmi.accumulate_reference_frames(S[1:3], M[1:3], L[1:3], views[1:3], F[1:3], ac.FOV, ac.LAMBERTIAN, history=hist)
+    assert_same_bits(step[:, 1], whole[:, 2], "one step from view 1's state")
+    want = pkg.ptmi.accumulate_reference(cf.predivided(S[1:3], F[1:3]), M[1:3], L[1:3], views[1:3], 1.0, ac.FOV, ac.LAMBERTIAN, history=hist)
+    assert_same_bits(step, want, "the step against the pre-divided sums")
+    with pytest.raises(pkg.PtmiError):
+        pkg.ptmi.accumulate_reference_frames(S[1:3], M[1:3], L[1:3], views[1:3], (np.nan, 2.0), ac.FOV, ac.LAMBERTIAN, history=hist)  # image 0's entry IS read
+
+
+def test_accumulation_with_equal_counts_is_the_existing_reference(pkg):
+    S, M, L, views, F = ac.inputs(130, 70, 5, 4)
+    assert_same_bits(pkg.ptmi.accumulate_reference_frames(S, M, L, views, [F] * 5, ac.FOV, ac.LAMBERTIAN), pkg.ptmi.accumulate_reference(S, M, L, views, F, ac.FOV, ac.LAMBERTIAN), "equal counts")
+
+
+def test_a_pixel_finite_under_its_own_count_only_keeps_its_history(pkg):
+    """consumer_frames_cases.planted on the CPU: the lookup in view 0 divides by F_0, under which the planted pixel is valid."""
+    S, M, L, views, F, (y, x) = cf.planted()
+    out = pkg.ptmi.accumulate_reference_frames(S, M, L, views, F, ac.FOV, None)
+    assert out[1, 1, y, x, 3] > M[1, y, x, 3], "the history of the planted pixel is taken: it is valid under F_0 = 2"
+    wrong = pkg.ptmi.accumulate_reference(cf.predivided(S, (0.5, 0.5)), M, L, views, 1.0, ac.FOV, None)
+    assert wrong[1, 1, y, x, 3] == M[1, y, x, 3], "under view 1's count it is infinite, and nothing is taken"
+
+
+# ------------------------------------------------------------------------------------------------------------------- per view: the two denoisers
+def _stack(make, w, h, n=5):
+    imgs = [make(w, h, seed) for seed in range(n)]
+    return [np.stack([im[k] for im in imgs]) for k in range(len(imgs[0]))]
+
+
+@pytest.mark.parametrize("size", dc.SIZES[1:], ids=lambda s: "%dx%d" % s)
+def test_the_plain_filter_with_counts_is_the_existing_reference_view_by_view(pkg, size):
+    S, L = _stack(dc.synthetic, *size)
+    F = cf.counts(5)
+    for prm in (None, pkg.ptmi.default_denoise_params(levels=2, sigma_colour=2.0)):
+        got = pkg.ptmi.denoise_reference_frames(S, L, F, prm)
+        for v in range(5):
+            assert_same_bits(got[v], pkg.ptmi.denoise_reference(S[v], L[v], float(F[v]), prm)[0], "view %d" % v)
+    assert_same_bits(pkg.ptmi.denoise_reference_frames(S, L, [4.0] * 5), pkg.ptmi.denoise_reference(S, L, 4.0), "equal counts")
+
+
+@pytest.mark.parametrize("size", gc.SIZES[1:], ids=lambda s: "%dx%d" % s)
+def test_the_guided_filter_with_counts_is_the_existing_reference_view_by_view(pkg, size):
+    S, M, L = _stack(gc.synthetic, *size)
+    F = cf.counts(5)
+    for prm in (None, pkg.ptmi.default_guided_params(levels=2, sigma_luma=0.0)):
+        got, var = pkg.ptmi.denoise_guided_reference_frames(S, M, L, F, prm, want_var=True)
+        for v in range(5):
+            want, wvar = pkg.ptmi.denoise_guided_reference(S[v], M[v], L[v], float(F[v]), prm, want_var=True)
+            assert_same_bits(got[v], want[0], "view %d" % v)
+            assert_same_bits(var[v], wvar[0], "variance of view %d" % v)
+    assert_same_bits(pkg.ptmi.denoise_guided_reference_frames(S, M, L, [4.0] * 5), pkg.ptmi.denoise_guided_reference(S, M, L, 4.0), "equal counts")
+
+
+# ------------------------------------------------------------------------------------------------------------------- the sources
+def test_one_launch_plan_and_optional_tables(pkg):
+    src = open(os.path.join(ROOT, "webgpu-path-tracer_amd", "csrc", "ptmi.hip")).read()
+    assert len(re.findall(r"^static int (atrous_enqueue|fuse_enqueue|accumulate_enqueue)\(", src, re.M)) == 3, "no twin of a launch plan"
+    for kernel in ("k_denoise_prepare", "k_denoise_prepare_frames", "k_fuse", "k_fuse_frames", "k_accumulate_view", "k_accumulate_view_frames", "k_denoise_level_frames", "k_guided_level_frames"):
+        assert len(re.findall(r"hipLaunchKernelGGL\(%s," % kernel, src)) == 1, kernel
+    host = open(os.path.join(ROOT, "webgpu-path-tracer_amd", "csrc", "ptmi_host.cpp")).read()
+    assert len(re.findall(r"^static int (atrous_reference|fuse_reference|accumulate_reference)\(", host, re.M)) == 3
+
+
+node = shutil.which("node")
+
+
+@pytest.mark.skipif(node is None, reason="node not installed")
+def test_addon_wrapper_and_mock_list_the_calls(pkg):
+    js = os.path.join(ROOT, "webgpu-path-tracer_amd", "js")
+    assert os.path.exists(os.path.join(js, "ptmi.node")), "run __graft_entry__.build()"
+    names = ["denoiseViewsFrames", "denoiseViewsGuidedFrames", "fuseViewsFrames", "accumulateViewsFrames"]
+    r = subprocess.run([node, "-e", "console.log(JSON.stringify(Object.keys(require('./ptmi.node')).sort()))"], cwd=js, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, r.stderr
+    assert set(json.loads(r.stdout)) >= set(names)
+    src = open(os.path.join(js, "ptmi.mjs")).read()
+    for m in names:
+        assert m + "(" in src, m
+    r = subprocess.run([node, "--input-type=module", "-e", "import { MockBackend } from './mock_backend.mjs'; const m = new MockBackend(); const v = new Float32Array(32);"
+                        "m.denoiseViewsFrames(new Uint32Array([8, 12]), 0, 2); m.denoiseViewsGuidedFrames([1, 3], 1, 1, { levels: 2 }); m.fuseViewsFrames(v, [1, 3], 0, 2);"
+                        "m.accumulateViewsFrames(v, new Float32Array([0.5, 2]), 1, 1, true); console.log(JSON.stringify(m.calls));"],
+                       cwd=js, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, r.stderr
+    assert json.loads(r.stdout) == [["denoiseViewsFrames", [8, 12], 0, 2, None], ["denoiseViewsGuidedFrames", [1, 3], 1, 1, {"levels": 2}], ["fuseViewsFrames", 2, [1, 3], 0, 2, None],
+                                    ["accumulateViewsFrames", 2, [0.5, 2], 1, 1, True, None]]
+
+
+# ------------------------------------------------------------------------------------------------------------------- purpose
+def test_fusing_with_each_views_own_count_is_closer_than_runs_of_equal_count(pkg, oracle):
+    """Nine oracle renders of c2 at 96 x 64 on fuse_cases' arc whose frame counts differ between neighbours (consumer_frames_cases.PURPOSE_COUNTS), fused with the
+    defaults: the middle view's RMSE against the oracle's mean of 256 other frames, over its fusable pixels, with every view's own count against the one-count call on
+    the same stack — all that "runs of views of equal count" leaves a caller, whose neighbours then come out F_u / F too bright.  Figures: cf.MEASURED."""
+    noisy, per_view, runs, n_fusable = cf.purpose(pkg, oracle)
+    print("RMSE over %d fusable pixels: the view's own mean %.5f, fused per view %.5f, fused with one count %.5f" % (n_fusable, noisy, per_view, runs))
+    assert per_view < runs, (per_view, runs)

@@ -1,4 +1,4 @@
-// Sanitizer driver for the host natives of libptmi (ptmi_host.cpp): both BVH builders (1 thread vs many; the edge and the outside of their domain on tables of exactly 2n - 1 rows), the OBJ parser, cross-view fusion, temporal accumulation, the noise statistic, the variance-guided filter and the slot plan of ptmi_render_views_frames.
+// Sanitizer driver for the host natives of libptmi (ptmi_host.cpp): both BVH builders (1 thread vs many; the edge and the outside of their domain on tables of exactly 2n - 1 rows), the OBJ parser, cross-view fusion, temporal accumulation, the noise statistic, the variance-guided filter, the slot plan of ptmi_render_views_frames and the four *_reference_frames with one frame count per image.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -pthread tools/sanitize_host.cpp webgpu-path-tracer_amd/csrc/ptmi_host.cpp -o /tmp/san/asan && /tmp/san/asan
 //   g++ -std=c++17 -O1 -g -fsanitize=thread -pthread ... -o /tmp/san/tsan && /tmp/san/tsan
 #include <algorithm>
@@ -93,6 +93,31 @@ int main() {
       if (ptmi_accumulate_reference(S.data(), M.data(), L.data(), views.data(), w, h, 2, 2.0f, 60.0f, nullptr, 0, nullptr, hist.data(), step.data(), 2)) return 18;
       if (ptmi_accumulate_reference(S.data(), M.data(), L.data(), views.data(), w, h, 1, 2.0f, 60.0f, nullptr, 0, nullptr, hist.data(), step.data(), 1) != PTMI_ERR_INVALID_ARG) return 19;
       if (ptmi_denoise_accumulated_reference(acc.data(), &acc[(size_t)2 * n * npix * 4], L.data(), w, h, n, nullptr, den.data(), var.data(), 1)) return 20;
+      {  // the four loops with one frame count per image (ptmi_*_reference_frames): equal counts give the one-count result, differing counts run, and a NaN entry or
+         // a null array is refused
+        const float F2[3] = {2.0f, 2.0f, 2.0f}, Fd[3] = {1.0f, 3.0f, 0.5f}, Fbad[3] = {1.0f, NAN, 2.0f};
+        std::vector<float> o2(out.size()), a2(acc.size()), d1(S.size()), d2(S.size());
+        if (ptmi_fuse_reference_frames(S.data(), L.data(), views.data(), w, h, n, F2, 60.0f, nullptr, 0, nullptr, o2.data()) || memcmp(o2.data(), out.data(), out.size() * 4)) return 21;
+        if (ptmi_accumulate_reference_frames(S.data(), M.data(), L.data(), views.data(), w, h, n, F2, 60.0f, lamb, 2, &A, nullptr, a2.data(), 3) || memcmp(a2.data(), acc.data(), acc.size() * 4)) return 22;
+        if (ptmi_denoise_reference(S.data(), L.data(), w, h, n, 2.0f, nullptr, d1.data()) || ptmi_denoise_reference_frames(S.data(), L.data(), w, h, n, F2, nullptr, d2.data()) ||
+            memcmp(d1.data(), d2.data(), d1.size() * 4))
+          return 23;
+        if (ptmi_denoise_guided_reference(S.data(), M.data(), L.data(), w, h, n, 2.0f, nullptr, d1.data(), var.data()) ||
+            ptmi_denoise_guided_reference_frames(S.data(), M.data(), L.data(), w, h, n, F2, nullptr, d2.data(), nullptr) || memcmp(d1.data(), d2.data(), d1.size() * 4))
+          return 24;
+        if (ptmi_fuse_reference_frames(S.data(), L.data(), views.data(), w, h, n, Fd, 60.0f, lamb, 2, &P, o2.data()) ||
+            ptmi_accumulate_reference_frames(S.data(), M.data(), L.data(), views.data(), w, h, n, Fd, 60.0f, lamb, 2, &A, nullptr, a2.data(), 2) ||
+            ptmi_accumulate_reference_frames(S.data(), M.data(), L.data(), views.data(), w, h, 2, Fd, 60.0f, nullptr, 0, nullptr, hist.data(), step.data(), 1) ||
+            ptmi_denoise_reference_frames(S.data(), L.data(), w, h, n, Fd, nullptr, d2.data()) ||
+            ptmi_denoise_guided_reference_frames(S.data(), M.data(), L.data(), w, h, n, Fd, nullptr, d2.data(), var.data()))
+          return 25;
+        for (const float* bad : {(const float*)Fbad, (const float*)nullptr})
+          if (ptmi_fuse_reference_frames(S.data(), L.data(), views.data(), w, h, n, bad, 60.0f, nullptr, 0, nullptr, o2.data()) != PTMI_ERR_INVALID_ARG ||
+              ptmi_accumulate_reference_frames(S.data(), M.data(), L.data(), views.data(), w, h, n, bad, 60.0f, nullptr, 0, nullptr, nullptr, a2.data(), 1) != PTMI_ERR_INVALID_ARG ||
+              ptmi_denoise_reference_frames(S.data(), L.data(), w, h, n, bad, nullptr, d2.data()) != PTMI_ERR_INVALID_ARG ||
+              ptmi_denoise_guided_reference_frames(S.data(), M.data(), L.data(), w, h, n, bad, nullptr, d2.data(), nullptr) != PTMI_ERR_INVALID_ARG)
+            return 26;
+      }
     }
     views[0] = 0.0f;
     if (ptmi_fuse_reference(S.data(), L.data(), views.data(), w, h, n, 2.0f, 60.0f, nullptr, 0, nullptr, out.data()) != PTMI_ERR_INVALID_ARG) return 8;  // a singular matrix

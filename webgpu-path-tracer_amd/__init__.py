@@ -12,3 +12,4 @@ The directory name has a hyphen; load it with `importlib` as module `webgpu_path
 from . import _build  # noqa: F401
 from . import ptmi, scenes  # noqa: F401
 from .ptmi import Context, DenoiseParams, FuseParams, GuidedParams, NoiseParams, Params, PtmiError, default_denoise_params, default_fuse_params, default_guided_params, default_noise_params, default_params, denoise_guided_reference, denoise_reference, fuse_reference, load_library, noise_reference  # noqa: F401
+from .ptmi import accumulate_reference_frames, denoise_guided_reference_frames, denoise_reference_frames, fuse_reference_frames  # noqa: F401

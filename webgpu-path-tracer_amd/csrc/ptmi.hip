@@ -156,7 +156,8 @@ struct ptmi_ctx {
   Stack stacks[N_STACKS];
   DBuf d_denoise_scratch;  // ptmi_denoise_views: three packed float4 images (d ping, d pong, n + z) per view of a batch (atrous_batch_views); ptmi_denoise_views_guided: and three f32 images (v ping, v pong, vg)
   StagedTable view_rows;   // the last ptmi_render_views / ptmi_render_aov call's view table (ViewTab: kViewRow float4 per view)
-  StagedTable fuse_tab;    // the last ptmi_fuse_views / ptmi_accumulate_views call's table (kFuseRow float4 per view of the stack, then one byte per material)
+  StagedTable fuse_tab;    // the last ptmi_fuse_views / ptmi_accumulate_views call's table (kFuseRow float4 per view of the stack, then one byte per material; the *_frames calls: then one f32 per view, its frame count)
+  StagedTable denoise_tab; // the last ptmi_denoise_views_frames / ptmi_denoise_views_guided_frames call's frame counts: one f32 per view of the stack
   bool view_moments = false;  // ptmi_set_view_moments: ptmi_render_views folds second moments into stacks[STACK_MOMENTS] too
   DBuf d_noise_rec;           // ptmi_view_noise_stats: one record (kNoiseRecordBytes) per view of the call
   int rank = 0, world = 1, tile = 64;
@@ -1626,6 +1627,7 @@ void ptmi_destroy(ptmi_ctx* c) {
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   c->view_rows.release();
   c->fuse_tab.release();
+  c->denoise_tab.release();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;  // its device buffers (DBuf) are freed here, with its device current and its stream drained
 }
@@ -2143,7 +2145,7 @@ static int release_stack(ptmi_ctx* c, StackKind k) {
     HIP_TRY(q, hipSetDevice(q->device));
     HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still read or write a stack that is about to go
     drop_stack(q, k);
-    if (k == STACK_DENOISED) q->d_denoise_scratch.release();
+    if (k == STACK_DENOISED) q->d_denoise_scratch.release(), q->denoise_tab.dev.release();
     if (k == STACK_FUSED || k == STACK_ACCUMULATED) q->fuse_tab.dev.release();  // (every call that reads the table stages it again)
     return PTMI_OK;
   });
@@ -2265,7 +2267,10 @@ struct AtrousGuide {
 // Either filter on device arrays: colour [n][H][W] float4 sums, layers [n][3][H][W] float4, out [n][H][W] float4; G = nullptr: the plain filter.  c->d_denoise_scratch
 // holds atrous_scratch_bytes already: nothing here allocates.  Per batch one k_denoise_prepare and one level kernel per level, the last of which writes `out`; the
 // guided filter also one k_guided_variance, per level one k_guided_blur (with a luminance term only: the blur feeds nothing else), and its last level writes `var_out`.
-static int atrous_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, uint32_t n, int W, int H, float F, const ptmi_denoise_params& P, const AtrousGuide* G) {
+// frames: nullptr, or the device table of the views' own divisors, one f32 per view, at the call's first view (F is then not read): the prepare pass and the last level
+// are then the *_frames entries, which index it by the batch's first view + the view of the batch.
+static int atrous_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, uint32_t n, int W, int H, float F, const ptmi_denoise_params& P, const AtrousGuide* G,
+                          const float* frames = nullptr) {
   const size_t npix = (size_t)W * (size_t)H;
   const uint32_t B = atrous_batch_views(npix, n, G ? kGuidedScratchBytes : kDenoiseScratchBytes);
   float4* d[2] = {c->d_denoise_scratch.as<float4>(), c->d_denoise_scratch.as<float4>() + (size_t)B * npix};
@@ -2281,7 +2286,8 @@ static int atrous_enqueue(ptmi_ctx* c, const float4* colour, const float4* layer
     const float4* lay = layers + (size_t)v0 * 3 * npix;
     const size_t items = (size_t)nv * npix;
     const unsigned pgrid = (unsigned)std::min<size_t>((items + kBlock - 1) / kBlock, (size_t)c->num_cus * 32);
-    hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, F, P.albedo_floor, d[0], g);
+    if (frames) hipLaunchKernelGGL(k_denoise_prepare_frames, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, frames + v0, P.albedo_floor, d[0], g);
+    else hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, F, P.albedo_floor, d[0], g);
     HIP_TRY(c, hipGetLastError());
     const dim3 tgrid((unsigned)((W + kDenoiseTX - 1) / kDenoiseTX), (unsigned)((H + kGuidedTY - 1) / kGuidedTY), nv);
     if (G && G->given) {
@@ -2304,8 +2310,13 @@ static int atrous_enqueue(ptmi_ctx* c, const float4* colour, const float4* layer
           HIP_TRY(c, hipGetLastError());
         }
         float* vout = !last ? v[(l + 1) & 1] : G->var_out ? G->var_out + (size_t)v0 * npix : nullptr;
-        hipLaunchKernelGGL(last ? k_guided_level<true> : k_guided_level<false>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, dout, vout, col, lay, W, H, step, ty, k,
-                           G->kg, F);
+        if (last && frames)
+          hipLaunchKernelGGL(k_guided_level_frames, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, dout, vout, col, lay, W, H, step, ty, k, G->kg, frames + v0);
+        else
+          hipLaunchKernelGGL(last ? k_guided_level<true> : k_guided_level<false>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, dout, vout, col, lay, W, H, step, ty, k,
+                             G->kg, F);
+      } else if (last && frames) {
+        hipLaunchKernelGGL(k_denoise_level_frames, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, dout, col, lay, W, H, step, ty, k, frames + v0);
       } else {
         hipLaunchKernelGGL(last ? k_denoise_level<true> : k_denoise_level<false>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, dout, col, lay, W, H, step, ty, k, F);
       }
@@ -2338,6 +2349,21 @@ static int check_view_range(ptmi_ctx* c, const char* who, uint32_t first_view, u
   return PTMI_OK;
 }
 
+// The *_frames calls: entries [lo, hi) of frame_nums are the ones the call reads, and each has to be a divisor — finite and > 0; the others may hold anything.
+static int check_frame_nums(ptmi_ctx* c, const char* who, const float* frame_nums, uint32_t lo, uint32_t hi) {
+  if (!frame_nums) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null frame_nums");
+  for (uint32_t v = lo; v < hi; v++)
+    if (!(frame_nums[v] > 0.0f) || !ptmd_finite(frame_nums[v]))
+      return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": frame_nums[" + std::to_string(v) + "] must be finite and > 0: view " + std::to_string(v) + " is read by this call");
+  return PTMI_OK;
+}
+
+// A device copy of `n` frame counts for a *_images_frames call, which is synchronous: `buf` is the call's own; the copy is enqueued by the caller (send_frame_nums).
+static int send_frame_nums(ptmi_ctx* c, DBuf& buf, const float* frame_nums, uint32_t n) {
+  HIP_TRY(c, hipMemcpyAsync(buf.p, frame_nums, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  return PTMI_OK;
+}
+
 static int denoise_check_args(ptmi_ctx* c, const char* who, const ptmi_denoise_params* params, float frame_num, ptmi_denoise_params* P) {
   if (params) *P = *params;
   else ptmi_default_denoise_params(P);
@@ -2359,7 +2385,9 @@ static int check_source_stacks(ptmi_ctx* c, const char* who, bool need_denoised,
 // Either filter from the context's stacks into its denoised stack, the arguments checked.  The stack and the scratch, everything that can fail for want of memory, come
 // before anything is enqueued.  G: as atrous_enqueue's, its `moments` (or, with `accumulated`, its `given`) filled in here.  accumulated: the colour is plane 0 of the
 // accumulated stack, not the view stack.
-static int atrous_views(ptmi_ctx* c, const ptmi_denoise_params& P, AtrousGuide* G, float frame_num, uint32_t first_view, uint32_t n_views, bool accumulated = false) {
+// frame_nums: nullptr, or the stack's frame counts, one per view (checked): they go up through c->denoise_tab, and frame_num is not read.
+static int atrous_views(ptmi_ctx* c, const ptmi_denoise_params& P, AtrousGuide* G, float frame_num, uint32_t first_view, uint32_t n_views, bool accumulated = false,
+                        const float* frame_nums = nullptr) {
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
   const size_t npix = (size_t)c->W * (size_t)c->H;
@@ -2368,19 +2396,36 @@ static int atrous_views(ptmi_ctx* c, const ptmi_denoise_params& P, AtrousGuide* 
   DBuf stack;
   if (int r = reserve_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
   HIP_TRY(c, c->d_denoise_scratch.ensure_idle(atrous_scratch_bytes(npix, n_views, G ? kGuidedScratchBytes : kDenoiseScratchBytes), c->stream));
+  if (frame_nums) {
+    void* staged = nullptr;
+    HIP_TRY(c, c->denoise_tab.stage((size_t)n_stack * 4, c->stream, &staged));
+    memcpy(staged, frame_nums, (size_t)n_stack * 4);
+  }
   if (int r = commit_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
+  if (frame_nums) HIP_TRY(c, c->denoise_tab.send((size_t)n_stack * 4, c->stream));
   if (G && accumulated) G->given = c->stacks[STACK_ACCUMULATED].buf.as<float4>() + ((size_t)2 * n_stack + first_view) * npix;
   else if (G) G->moments = c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix;
   return atrous_enqueue(c, c->stacks[source].buf.as<float4>() + (size_t)first_view * npix, c->stacks[STACK_FEATURES].buf.as<float4>() + (size_t)first_view * 3 * npix,
-                        c->stacks[STACK_DENOISED].buf.as<float4>() + (size_t)first_view * npix, n_views, c->W, c->H, frame_num, P, G);
+                        c->stacks[STACK_DENOISED].buf.as<float4>() + (size_t)first_view * npix, n_views, c->W, c->H, frame_num, P, G,
+                        frame_nums ? c->denoise_tab.dev.as<float>() + first_view : nullptr);
 }
 
-int ptmi_denoise_views(ptmi_ctx* c, const ptmi_denoise_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
+// ptmi_denoise_views (per_view false: frame_num) and ptmi_denoise_views_frames (per_view: frame_nums, one per view of the stack)
+static int denoise_views(ptmi_ctx* c, const char* who, const ptmi_denoise_params* params, float frame_num, const float* frame_nums, bool per_view, uint32_t first_view, uint32_t n_views) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   ptmi_denoise_params P;
-  if (int r = denoise_check_args(c, "ptmi_denoise_views", params, frame_num, &P)) return r;
-  if (int r = check_source_stacks(c, "ptmi_denoise_views", false, first_view, n_views)) return r;
-  return atrous_views(c, P, nullptr, frame_num, first_view, n_views);
+  if (int r = denoise_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
+  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = check_source_stacks(c, who, false, first_view, n_views)) return r;
+  if (per_view)
+    if (int r = check_frame_nums(c, who, frame_nums, first_view, first_view + n_views)) return r;
+  return atrous_views(c, P, nullptr, frame_num, first_view, n_views, false, per_view ? frame_nums : nullptr);
+}
+int ptmi_denoise_views(ptmi_ctx* c, const ptmi_denoise_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
+  return denoise_views(c, "ptmi_denoise_views", params, frame_num, nullptr, false, first_view, n_views);
+}
+int ptmi_denoise_views_frames(ptmi_ctx* c, const ptmi_denoise_params* params, const float* frame_nums, uint32_t first_view, uint32_t n_views) {
+  return denoise_views(c, "ptmi_denoise_views_frames", params, 1.0f, frame_nums, true, first_view, n_views);
 }
 
 int ptmi_read_denoised(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_DENOISED, "ptmi_read_denoised", view, 0, dst, bytes); }
@@ -2418,14 +2463,36 @@ static int on_host_images(ptmi_ctx* c, const char* who, const float* colour, con
   return r;
 }
 
-int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params, float* out) {
-  if (!c || !colour_sums || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images: null argument");
+// ptmi_denoise_images (per_view false) and ptmi_denoise_images_frames (frame_nums: one per image)
+static int denoise_images(ptmi_ctx* c, const char* who, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const float* frame_nums,
+                          bool per_view, const ptmi_denoise_params* params, float* out) {
+  if (!c || !colour_sums || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_denoise_params P;
-  if (int r = denoise_check_args(c, "ptmi_denoise_images", params, frame_num, &P)) return r;
-  if (int r = check_image_size(c, "ptmi_denoise_images", w, h, n_images)) return r;
+  if (int r = denoise_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
+  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = check_image_size(c, who, w, h, n_images)) return r;
+  if (per_view)
+    if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
   const size_t npix = (size_t)w * (size_t)h;
-  return on_host_images(c, "ptmi_denoise_images", colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kDenoiseScratchBytes),
-                        [&](const float4* col, const float4* lay, float4* res) { return atrous_enqueue(c, col, lay, res, n_images, w, h, frame_num, P, nullptr); });
+  DBuf dfr;  // (the frame counts: this call's own, had before anything is enqueued)
+  if (per_view) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    HIP_TRY(c, dfr.ensure((size_t)n_images * 4));
+  }
+  return on_host_images(c, who, colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kDenoiseScratchBytes),
+                        [&](const float4* col, const float4* lay, float4* res) -> int {
+                          if (per_view)
+                            if (int e = send_frame_nums(c, dfr, frame_nums, n_images)) return e;
+                          return atrous_enqueue(c, col, lay, res, n_images, w, h, frame_num, P, nullptr, dfr.as<float>());
+                        });
+}
+int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params, float* out) {
+  return denoise_images(c, "ptmi_denoise_images", colour_sums, layers, w, h, n_images, frame_num, nullptr, false, params, out);
+}
+int ptmi_denoise_images_frames(ptmi_ctx* c, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const float* frame_nums,
+                               const ptmi_denoise_params* params, float* out) {
+  return denoise_images(c, "ptmi_denoise_images_frames", colour_sums, layers, w, h, n_images, 1.0f, frame_nums, true, params, out);
 }
 
 // The guided filter's params as the launch plan takes them: the levels' part, with no colour term (P), and the rest (G, whose arrays the caller fills in)
@@ -2440,46 +2507,79 @@ static int guided_check_args(ptmi_ctx* c, const char* who, const ptmi_guided_par
                           ok ? nullptr : "levels in 1..6, sigma_normal, sigma_depth and albedo_floor > 0, sigma_luma >= 0, min_frames >= 2, var_eps a normal f32 > 0, all finite", true, frame_num);
 }
 
-int ptmi_denoise_views_guided(ptmi_ctx* c, const ptmi_guided_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
+// ptmi_denoise_views_guided (per_view false: frame_num) and ptmi_denoise_views_guided_frames (per_view: frame_nums, one per view of the stack)
+static int denoise_views_guided(ptmi_ctx* c, const char* who, const ptmi_guided_params* params, float frame_num, const float* frame_nums, bool per_view, uint32_t first_view,
+                                uint32_t n_views) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   ptmi_denoise_params P;
   AtrousGuide G;
-  if (int r = guided_check_args(c, "ptmi_denoise_views_guided", params, frame_num, &P, &G)) return r;
-  if (int r = check_stack(c, STACK_MOMENTS, "ptmi_denoise_views_guided", 0)) return r;  // (the moment stack first, then what ptmi_denoise_views asks: the order decides which error a caller sees)
-  if (int r = check_stack(c, STACK_VIEWS, "ptmi_denoise_views_guided", 0)) return r;
+  if (int r = guided_check_args(c, who, params, per_view ? 1.0f : frame_num, &P, &G)) return r;
+  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = check_stack(c, STACK_MOMENTS, who, 0)) return r;  // (the moment stack first, then what ptmi_denoise_views asks: the order decides which error a caller sees)
+  if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
   if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
-    return fail(c, PTMI_ERR_STATE, "ptmi_denoise_views_guided: the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
-  if (int r = check_source_stacks(c, "ptmi_denoise_views_guided", false, first_view, n_views)) return r;
-  return atrous_views(c, P, &G, frame_num, first_view, n_views);
+    return fail(c, PTMI_ERR_STATE, std::string(who) + ": the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
+  if (int r = check_source_stacks(c, who, false, first_view, n_views)) return r;
+  if (per_view)
+    if (int r = check_frame_nums(c, who, frame_nums, first_view, first_view + n_views)) return r;
+  return atrous_views(c, P, &G, frame_num, first_view, n_views, false, per_view ? frame_nums : nullptr);
+}
+int ptmi_denoise_views_guided(ptmi_ctx* c, const ptmi_guided_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
+  return denoise_views_guided(c, "ptmi_denoise_views_guided", params, frame_num, nullptr, false, first_view, n_views);
+}
+int ptmi_denoise_views_guided_frames(ptmi_ctx* c, const ptmi_guided_params* params, const float* frame_nums, uint32_t first_view, uint32_t n_views) {
+  return denoise_views_guided(c, "ptmi_denoise_views_guided_frames", params, 1.0f, frame_nums, true, first_view, n_views);
 }
 
-int ptmi_denoise_images_guided(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
-                               const ptmi_guided_params* params, float* out, float* var_out) {
-  if (!c || !colour_sums || !moments || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images_guided: null argument");
+// ptmi_denoise_images_guided (per_view false) and ptmi_denoise_images_guided_frames (frame_nums: one per image)
+static int denoise_images_guided(ptmi_ctx* c, const char* who, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
+                                 const float* frame_nums, bool per_view, const ptmi_guided_params* params, float* out, float* var_out) {
+  if (!c || !colour_sums || !moments || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_denoise_params P;
   AtrousGuide G;
-  if (int r = guided_check_args(c, "ptmi_denoise_images_guided", params, frame_num, &P, &G)) return r;
-  if (int r = check_image_size(c, "ptmi_denoise_images_guided", w, h, n_images)) return r;
+  if (int r = guided_check_args(c, who, params, per_view ? 1.0f : frame_num, &P, &G)) return r;
+  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = check_image_size(c, who, w, h, n_images)) return r;
+  if (per_view)
+    if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
   const size_t npix = (size_t)w * (size_t)h, bytes = npix * 16 * n_images, var_bytes = var_out ? npix * 4 * n_images : 0;
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
-  DBuf mom, var;  // (on_host_images brings the colour, the layers and the output; these two are this call's own, had before anything is enqueued)
+  DBuf mom, var, dfr;  // (on_host_images brings the colour, the layers and the output; these are this call's own, had before anything is enqueued)
   HIP_TRY(c, mom.ensure(bytes));
   HIP_TRY(c, var.ensure(var_bytes));
+  if (per_view) HIP_TRY(c, dfr.ensure((size_t)n_images * 4));
   G.moments = mom.as<float4>(), G.var_out = var.as<float>();
-  return on_host_images(c, "ptmi_denoise_images_guided", colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kGuidedScratchBytes),
+  return on_host_images(c, who, colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kGuidedScratchBytes),
                         [&](const float4* col, const float4* lay, float4* res) -> int {
                           HIP_TRY(c, hipMemcpyAsync(mom.p, moments, bytes, hipMemcpyHostToDevice, c->stream));
-                          if (int e = atrous_enqueue(c, col, lay, res, n_images, w, h, frame_num, P, &G)) return e;
+                          if (per_view)
+                            if (int e = send_frame_nums(c, dfr, frame_nums, n_images)) return e;
+                          if (int e = atrous_enqueue(c, col, lay, res, n_images, w, h, frame_num, P, &G, dfr.as<float>())) return e;
                           if (var_out) HIP_TRY(c, hipMemcpyAsync(var_out, var.p, var_bytes, hipMemcpyDeviceToHost, c->stream));
                           return PTMI_OK;
                         });
 }
+int ptmi_denoise_images_guided(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
+                               const ptmi_guided_params* params, float* out, float* var_out) {
+  return denoise_images_guided(c, "ptmi_denoise_images_guided", colour_sums, moments, layers, w, h, n_images, frame_num, nullptr, false, params, out, var_out);
+}
+int ptmi_denoise_images_guided_frames(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, const float* frame_nums,
+                                      const ptmi_guided_params* params, float* out, float* var_out) {
+  return denoise_images_guided(c, "ptmi_denoise_images_guided_frames", colour_sums, moments, layers, w, h, n_images, 1.0f, frame_nums, true, params, out, var_out);
+}
 
 // ---- the fused stack (ptmi_fuse_views, ptmi_fuse_images) ----
 // (ptmi_default_fuse_params and ptmi_fuse_reference need no GPU: ptmi_host.cpp)
-// The call's table as the kernel reads it: kFuseRow float4 per view of the stack, then one byte per material index.
-static size_t fuse_tab_bytes(uint32_t n_stack, uint32_t n_materials) { return (size_t)n_stack * kFuseRow * 16 + std::max<size_t>(16, n_materials); }
+// The call's table as the kernel reads it: kFuseRow float4 per view of the stack, then one byte per material index, padded to a multiple of 16; the *_frames calls put
+// the views' frame counts, one f32 per view of the stack, behind those bytes (fuse_tab_frames: where).
+static size_t fuse_tab_frames(uint32_t n_stack, uint32_t n_materials) { return (size_t)n_stack * kFuseRow * 16 + ((std::max<size_t>(16, n_materials) + 15) & ~(size_t)15); }
+static size_t fuse_tab_bytes(uint32_t n_stack, uint32_t n_materials, bool frames = false) {
+  return frames ? fuse_tab_frames(n_stack, n_materials) + (size_t)n_stack * 4 : (size_t)n_stack * kFuseRow * 16 + std::max<size_t>(16, n_materials);
+}
+static const float* fuse_tab_frames_ptr(const void* tab, uint32_t n_stack, uint32_t n_materials) {
+  return reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(tab) + fuse_tab_frames(n_stack, n_materials));
+}
 
 // Fills `tab` (fuse_tab_bytes) from the matrices of all views and the material-type bytes; PTMI_ERR_INVALID_ARG for a matrix that cannot be inverted.
 static int fuse_fill_tab(ptmi_ctx* c, const char* who, const float* views16, uint32_t n_stack, const uint8_t* lamb, uint32_t n_materials, float* tab) {
@@ -2497,15 +2597,20 @@ static int fuse_fill_tab(ptmi_ctx* c, const char* who, const float* views16, uin
 
 // The kernel on device arrays: colour [n_stack][H][W] float4, layers [n_stack][3][H][W] float4, out [n_stack][H][W] float4, of which views [first, first + n) are
 // written; `tab` as fuse_fill_tab made it, `has_lamb`: whether its material bytes are to be used.  One launch; more only where n exceeds the grid's z limit.
+// frames: nullptr, or the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_fuse_frames.
 static int fuse_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, const void* tab, bool has_lamb, uint32_t n_materials, int W, int H,
-                        uint32_t n_stack, uint32_t first, uint32_t n, const ptmf_consts& k) {
+                        uint32_t n_stack, uint32_t first, uint32_t n, const ptmf_consts& k, const float* frames = nullptr) {
   const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
   const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
   const uint8_t* lamb = has_lamb ? reinterpret_cast<const uint8_t*>(tab) + (size_t)n_stack * kFuseRow * 16 : nullptr;
   for (uint32_t v0 = 0; v0 < n; v0 += 65535u) {
     const uint32_t nv = std::min(65535u, n - v0);
-    hipLaunchKernelGGL(k_fuse, dim3(gx, 1, nv), dim3(kBlock), 0, c->stream, colour, layers, out, reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, n_stack,
-                       first + v0, k);
+    if (frames)
+      hipLaunchKernelGGL(k_fuse_frames, dim3(gx, 1, nv), dim3(kBlock), 0, c->stream, colour, layers, out, reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, n_stack,
+                         first + v0, k, frames);
+    else
+      hipLaunchKernelGGL(k_fuse, dim3(gx, 1, nv), dim3(kBlock), 0, c->stream, colour, layers, out, reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, n_stack,
+                         first + v0, k);
     HIP_TRY(c, hipGetLastError());
   }
   return PTMI_OK;
@@ -2520,10 +2625,10 @@ static int fuse_check_args(ptmi_ctx* c, const char* who, const ptmi_fuse_params*
 
 // What ptmi_fuse_views and ptmi_accumulate_views do before they enqueue a kernel: the table of all views of the stack with the uploaded materials' types, the call's
 // stack `k` (of the view stack's size) and the table's two copies — everything that can fail for want of memory, before anything is enqueued — and then the
-// table's upload.
-static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, const float* views16) {
+// table's upload.  frame_nums: nullptr, or the stack's frame counts (checked), which go behind the table's material bytes.
+static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, const float* views16, const float* frame_nums = nullptr) {
   const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  const size_t tab_bytes = fuse_tab_bytes(n_stack, n_mat);
+  const size_t tab_bytes = fuse_tab_bytes(n_stack, n_mat, frame_nums != nullptr);
   std::vector<float> tab;
   std::vector<uint8_t> lamb;
   try {
@@ -2534,6 +2639,7 @@ static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, cons
   }
   for (uint32_t i = 0; i < n_mat; i++) lamb[i] = c->h_mats[16 * (size_t)i + 14] == PTMF_LAMBERTIAN;
   if (int r = fuse_fill_tab(c, who, views16, n_stack, lamb.data(), n_mat, tab.data())) return r;
+  if (frame_nums) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_frames(n_stack, n_mat), frame_nums, (size_t)n_stack * 4);
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
   DBuf stack;
@@ -2546,19 +2652,32 @@ static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, cons
   return PTMI_OK;
 }
 
-int ptmi_fuse_views(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, float frame_num, int source, uint32_t first_view, uint32_t n_views) {
+// ptmi_fuse_views (per_view false: frame_num) and ptmi_fuse_views_frames (per_view: the view stack as source, frame_nums one per view of the stack)
+static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* params, const float* views16, float frame_num, const float* frame_nums, bool per_view, int source,
+                      uint32_t first_view, uint32_t n_views) {
   if (!c) return PTMI_ERR_INVALID_ARG;
-  if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_views: null argument");
-  if (source != 0 && source != 1) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_views: source must be 0 (the view stack) or 1 (the denoised stack)");
+  if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (source != 0 && source != 1) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": source must be 0 (the view stack) or 1 (the denoised stack)");
   ptmi_fuse_params P;
-  if (int r = fuse_check_args(c, "ptmi_fuse_views", params, frame_num, source == 0, &P)) return r;
-  if (int r = check_source_stacks(c, "ptmi_fuse_views", source == 1, first_view, n_views)) return r;
+  if (int r = fuse_check_args(c, who, params, frame_num, source == 0 && !per_view, &P)) return r;
+  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = check_source_stacks(c, who, source == 1, first_view, n_views)) return r;
   const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  if (int r = make_stack_with_table(c, "ptmi_fuse_views", STACK_FUSED, views16)) return r;
+  if (per_view) {  // the call's range widened by the radius on both sides, clipped to the stack: the window of its output views
+    const uint32_t R = (uint32_t)P.radius, lo = first_view > R ? first_view - R : 0u, hi = (uint32_t)std::min<uint64_t>(n_stack, (uint64_t)first_view + n_views + R);
+    if (int r = check_frame_nums(c, who, frame_nums, lo, hi)) return r;
+  }
+  if (int r = make_stack_with_table(c, who, STACK_FUSED, views16, per_view ? frame_nums : nullptr)) return r;
   const float fov_factor = (float)(1.0 / std::tan((double)c->prm.fov_degrees * (3.14159265358979323846 / 180.0) / 2.0));  // as make_render_const folds it
   const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, source == 0 ? frame_num : 1.0f, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   return fuse_enqueue(c, c->stacks[source == 0 ? STACK_VIEWS : STACK_DENOISED].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(), c->stacks[STACK_FUSED].buf.as<float4>(),
-                      c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, k);
+                      c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, k, per_view ? fuse_tab_frames_ptr(c->fuse_tab.dev.p, n_stack, n_mat) : nullptr);
+}
+int ptmi_fuse_views(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, float frame_num, int source, uint32_t first_view, uint32_t n_views) {
+  return fuse_views(c, "ptmi_fuse_views", params, views16, frame_num, nullptr, false, source, first_view, n_views);
+}
+int ptmi_fuse_views_frames(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, uint32_t first_view, uint32_t n_views) {
+  return fuse_views(c, "ptmi_fuse_views_frames", params, views16, 1.0f, frame_nums, true, 0, first_view, n_views);
 }
 
 int ptmi_read_fused(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_FUSED, "ptmi_read_fused", view, 0, dst, bytes); }
@@ -2568,36 +2687,51 @@ int ptmi_resolve_fused_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t by
 int ptmi_fused_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) { return stack_device_ptr(c, STACK_FUSED, "ptmi_fused_device_ptr", nullptr, p, bytes, n_views); }
 int ptmi_release_fused(ptmi_ctx* c) { return release_stack(c, STACK_FUSED); }
 
-int ptmi_fuse_images(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
-                     const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
-  if (!c || !colour || !layers || !views16 || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_images: null argument");
+// ptmi_fuse_images (per_view false) and ptmi_fuse_images_frames (frame_nums: one per image)
+static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
+                       const float* frame_nums, bool per_view, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
+  if (!c || !colour || !layers || !views16 || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_fuse_params P;
-  if (int r = fuse_check_args(c, "ptmi_fuse_images", params, frame_num, true, &P)) return r;
-  if (int r = check_image_size(c, "ptmi_fuse_images", w, h, n_images)) return r;
-  if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_images: fov_degrees must be in (0,180)");
+  if (int r = fuse_check_args(c, who, params, frame_num, !per_view, &P)) return r;
+  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = check_image_size(c, who, w, h, n_images)) return r;
+  if (per_view)
+    if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
+  if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": fov_degrees must be in (0,180)");
   if (!lambertian) n_materials = 0;
-  const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials);
+  const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials, per_view);
   std::vector<float> tab;
   try {
     tab.resize(tab_bytes / 4 + 1);
   } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_fuse_images: no host memory for the view table");
+    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the view table");
   }
-  if (int r = fuse_fill_tab(c, "ptmi_fuse_images", views16, n_images, lambertian, n_materials, tab.data())) return r;
+  if (int r = fuse_fill_tab(c, who, views16, n_images, lambertian, n_materials, tab.data())) return r;
+  if (per_view) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_frames(n_images, n_materials), frame_nums, (size_t)n_images * 4);
   const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   DBuf dtab;
-  return on_host_images(c, "ptmi_fuse_images", colour, layers, (size_t)w * (size_t)h, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
+  return on_host_images(c, who, colour, layers, (size_t)w * (size_t)h, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
     HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
-    return fuse_enqueue(c, col, lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, 0, n_images, k);
+    return fuse_enqueue(c, col, lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, 0, n_images, k,
+                        per_view ? fuse_tab_frames_ptr(dtab.p, n_images, n_materials) : nullptr);
   });
+}
+int ptmi_fuse_images(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
+                     const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
+  return fuse_images(c, "ptmi_fuse_images", colour, layers, views16, w, h, n_images, frame_num, nullptr, false, fov_degrees, lambertian, n_materials, params, out);
+}
+int ptmi_fuse_images_frames(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums, float fov_degrees,
+                            const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
+  return fuse_images(c, "ptmi_fuse_images_frames", colour, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params, out);
 }
 
 // ---- the accumulated stack (ptmi_accumulate_views, ptmi_accumulate_images) and the guided filter on it (ptmi_denoise_views_accumulated, ptmi_denoise_images_accumulated) ----
 // (ptmi_default_accumulate_params, ptmi_accumulate_reference and ptmi_denoise_accumulated_reference need no GPU: ptmi_host.cpp)
 // The kernel on device arrays: colour, moments [n_stack][H][W] float4, layers [n_stack][3][H][W] float4, planes [3][n_stack][H][W] float4, of which views
 // [first, first + n) are written, one launch per view in ascending order; view `first` takes its history from view first - 1 of `planes` when `resume`.
+// frames: nullptr, or the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_accumulate_view_frames.
 static int accumulate_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, const float4* layers, float4* planes, const void* tab, bool has_lamb, uint32_t n_materials,
-                              int W, int H, uint32_t n_stack, uint32_t first, uint32_t n, bool resume, const ptmf_consts& k, const ptma_consts& ka) {
+                              int W, int H, uint32_t n_stack, uint32_t first, uint32_t n, bool resume, const ptmf_consts& k, const ptma_consts& ka, const float* frames = nullptr) {
   const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
   const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
   const uint8_t* lamb = has_lamb ? reinterpret_cast<const uint8_t*>(tab) + (size_t)n_stack * kFuseRow * 16 : nullptr;
@@ -2605,8 +2739,12 @@ static int accumulate_enqueue(ptmi_ctx* c, const float4* colour, const float4* m
   auto plane = [&](uint32_t pl, uint32_t v) { return planes + ((size_t)pl * n_stack + v) * npix; };
   for (uint32_t v = first; v < first + n; v++) {
     const bool has_prev = v > 0 && (v > first || resume);
-    hipLaunchKernelGGL(k_accumulate_view, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr, has_prev ? plane(2, v - 1) : nullptr,
-                       plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka);
+    if (frames)
+      hipLaunchKernelGGL(k_accumulate_view_frames, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr,
+                         has_prev ? plane(2, v - 1) : nullptr, plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka, frames);
+    else
+      hipLaunchKernelGGL(k_accumulate_view, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr, has_prev ? plane(2, v - 1) : nullptr,
+                         plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka);
     HIP_TRY(c, hipGetLastError());
   }
   return PTMI_OK;
@@ -2619,27 +2757,38 @@ static int accumulate_check_args(ptmi_ctx* c, const char* who, const ptmi_accumu
   return check_stack_call(c, who, "a view's pixels", "several", ok ? nullptr : "max_history, sigma_normal, sigma_depth and albedo_floor > 0, all finite, and min_frames >= 2", true, frame_num);
 }
 
-int ptmi_accumulate_views(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, float frame_num, uint32_t first_view, uint32_t n_views, int resume) {
+// ptmi_accumulate_views (per_view false: frame_num) and ptmi_accumulate_views_frames (per_view: frame_nums, one per view of the stack)
+static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_params* params, const float* views16, float frame_num, const float* frame_nums, bool per_view,
+                            uint32_t first_view, uint32_t n_views, int resume) {
   if (!c) return PTMI_ERR_INVALID_ARG;
-  if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_accumulate_views: null argument");
+  if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_accumulate_params P;
-  if (int r = accumulate_check_args(c, "ptmi_accumulate_views", params, frame_num, &P)) return r;
-  if (int r = check_stack(c, STACK_MOMENTS, "ptmi_accumulate_views", 0)) return r;  // (the moment stack first, as ptmi_denoise_views_guided asks)
-  if (int r = check_stack(c, STACK_VIEWS, "ptmi_accumulate_views", 0)) return r;
+  if (int r = accumulate_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
+  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = check_stack(c, STACK_MOMENTS, who, 0)) return r;  // (the moment stack first, as ptmi_denoise_views_guided asks)
+  if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
   if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
-    return fail(c, PTMI_ERR_STATE, "ptmi_accumulate_views: the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
-  if (int r = check_source_stacks(c, "ptmi_accumulate_views", false, first_view, n_views)) return r;
+    return fail(c, PTMI_ERR_STATE, std::string(who) + ": the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
+  if (int r = check_source_stacks(c, who, false, first_view, n_views)) return r;
   if (resume) {
-    if (first_view == 0) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_accumulate_views: resume needs first_view > 0: view 0 has no predecessor");
-    if (int r = check_stack(c, STACK_ACCUMULATED, "ptmi_accumulate_views (resume)", 0)) return r;
+    if (first_view == 0) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": resume needs first_view > 0: view 0 has no predecessor");
+    if (int r = check_stack(c, STACK_ACCUMULATED, (std::string(who) + " (resume)").c_str(), 0)) return r;
   }
+  if (per_view)  // the call's range, and the view before it where its state is taken over
+    if (int r = check_frame_nums(c, who, frame_nums, resume ? first_view - 1u : first_view, first_view + n_views)) return r;
   const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  if (int r = make_stack_with_table(c, "ptmi_accumulate_views", STACK_ACCUMULATED, views16)) return r;
+  if (int r = make_stack_with_table(c, who, STACK_ACCUMULATED, views16, per_view ? frame_nums : nullptr)) return r;
   const float fov_factor = (float)(1.0 / std::tan((double)c->prm.fov_degrees * (3.14159265358979323846 / 180.0) / 2.0));  // as make_render_const folds it
   const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   return accumulate_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>(), c->stacks[STACK_MOMENTS].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(),
                             c->stacks[STACK_ACCUMULATED].buf.as<float4>(), c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, resume != 0, k,
-                            ptma_make_consts(P.max_history, P.min_frames));
+                            ptma_make_consts(P.max_history, P.min_frames), per_view ? fuse_tab_frames_ptr(c->fuse_tab.dev.p, n_stack, n_mat) : nullptr);
+}
+int ptmi_accumulate_views(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, float frame_num, uint32_t first_view, uint32_t n_views, int resume) {
+  return accumulate_views(c, "ptmi_accumulate_views", params, views16, frame_num, nullptr, false, first_view, n_views, resume);
+}
+int ptmi_accumulate_views_frames(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, uint32_t first_view, uint32_t n_views, int resume) {
+  return accumulate_views(c, "ptmi_accumulate_views_frames", params, views16, 1.0f, frame_nums, true, first_view, n_views, resume);
 }
 
 int ptmi_read_accumulated(ptmi_ctx* c, uint32_t view, int plane, float* dst, size_t bytes) { return read_stack(c, STACK_ACCUMULATED, "ptmi_read_accumulated", view, plane, dst, bytes); }
@@ -2651,23 +2800,29 @@ int ptmi_accumulated_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* 
 }
 int ptmi_release_accumulated(ptmi_ctx* c) { return release_stack(c, STACK_ACCUMULATED); }
 
-int ptmi_accumulate_images(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
-                           float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out) {
-  if (!c || !colour_sums || !moments || !layers || !views16 || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_accumulate_images: null argument");
+// ptmi_accumulate_images (per_view false) and ptmi_accumulate_images_frames (frame_nums: one per image)
+static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                             float frame_num, const float* frame_nums, bool per_view, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
+                             const ptmi_accumulate_params* params, const float* history_in, float* out) {
+  if (!c || !colour_sums || !moments || !layers || !views16 || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_accumulate_params P;
-  if (int r = accumulate_check_args(c, "ptmi_accumulate_images", params, frame_num, &P)) return r;
-  if (int r = check_image_size(c, "ptmi_accumulate_images", w, h, n_images)) return r;
-  if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_accumulate_images: fov_degrees must be in (0,180)");
-  if (history_in && n_images < 2) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_accumulate_images: history_in makes image 0 the view before the first: need n_images >= 2");
+  if (int r = accumulate_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
+  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = check_image_size(c, who, w, h, n_images)) return r;
+  if (per_view)
+    if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
+  if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": fov_degrees must be in (0,180)");
+  if (history_in && n_images < 2) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": history_in makes image 0 the view before the first: need n_images >= 2");
   if (!lambertian) n_materials = 0;
-  const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials);
+  const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials, per_view);
   std::vector<float> tab;
   try {
     tab.resize(tab_bytes / 4 + 1);
   } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_accumulate_images: no host memory for the view table");
+    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the view table");
   }
-  if (int r = fuse_fill_tab(c, "ptmi_accumulate_images", views16, n_images, lambertian, n_materials, tab.data())) return r;
+  if (int r = fuse_fill_tab(c, who, views16, n_images, lambertian, n_materials, tab.data())) return r;
+  if (per_view) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_frames(n_images, n_materials), frame_nums, (size_t)n_images * 4);
   const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   const ptma_consts ka = ptma_make_consts(P.max_history, P.min_frames);
   const size_t npix = (size_t)w * (size_t)h, bytes = npix * 16 * n_images;
@@ -2675,7 +2830,7 @@ int ptmi_accumulate_images(ptmi_ctx* c, const float* colour_sums, const float* m
   (void)hipGetLastError();
   DBuf mom, dtab;  // (on_host_images brings the colour, the layers, the three planes and the table; the moments are this call's own, had before anything is enqueued)
   HIP_TRY(c, mom.ensure(bytes));
-  return on_host_images(c, "ptmi_accumulate_images", colour_sums, layers, npix, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
+  return on_host_images(c, who, colour_sums, layers, npix, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
     HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(mom.p, moments, bytes, hipMemcpyHostToDevice, c->stream));
     if (history_in) {  // image 0 is the view before the first: its state is given, its mean is not made
@@ -2684,8 +2839,20 @@ int ptmi_accumulate_images(ptmi_ctx* c, const float* colour_sums, const float* m
       HIP_TRY(c, hipMemcpyAsync(res + (size_t)2 * n_images * npix, history_in + npix * 4, npix * 16, hipMemcpyHostToDevice, c->stream));
     }
     const uint32_t first = history_in ? 1u : 0u;
-    return accumulate_enqueue(c, col, mom.as<float4>(), lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, first, n_images - first, history_in != nullptr, k, ka);
+    return accumulate_enqueue(c, col, mom.as<float4>(), lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, first, n_images - first, history_in != nullptr, k, ka,
+                              per_view ? fuse_tab_frames_ptr(dtab.p, n_images, n_materials) : nullptr);
   }, 3, 48);
+}
+int ptmi_accumulate_images(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
+                           float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out) {
+  return accumulate_images(c, "ptmi_accumulate_images", colour_sums, moments, layers, views16, w, h, n_images, frame_num, nullptr, false, fov_degrees, lambertian, n_materials, params,
+                           history_in, out);
+}
+int ptmi_accumulate_images_frames(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                  const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
+                                  const float* history_in, float* out) {
+  return accumulate_images(c, "ptmi_accumulate_images_frames", colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params,
+                           history_in, out);
 }
 
 int ptmi_denoise_views_accumulated(ptmi_ctx* c, const ptmi_guided_params* params, uint32_t first_view, uint32_t n_views) {

@@ -2,7 +2,8 @@
 // "Temporal accumulation").  Every f32 operation of a pixel is in include/ptmi_accumulate.h, which the host natives include too; this file only decides where the
 // operands come from.
 //
-// k_accumulate_view     One lane owns one pixel of ONE view, a wave 64 neighbouring pixels of one row, a block four such waves: k_fuse's row tiles.  A call launches
+// k_accumulate_view, k_accumulate_view_frames (one body, accumulate_view)
+//                       One lane owns one pixel of ONE view, a wave 64 neighbouring pixels of one row, a block four such waves: k_fuse's row tiles.  A call launches
 //                       its views one after the other on one stream, so view v's launch finds what view v-1's wrote.  The own view's matrix and the previous view's
 //                       B, o come through scalar loads (fuse_load_own, fuse_load_neighbour).  The lane loads S, M, N, A, I of p together; after an accepted projection
 //                       it issues S, N, A, I and planes 1 and 2 of view v-1 at q as one group of six independent 16-byte gathers, kept together by an operand fence
@@ -28,10 +29,11 @@ DEV void accumulate_loaded(const float4& S, const float4& N, const float4& A, co
 // colour, moments: [n_stack][npix] float4 sums; layers: [n_stack][3][npix] float4; prev1, prev2: planes 1 and 2 of view v - 1 ([npix] float4 each), nullptr: view v has
 // no history; out0, out1, out2: view v's image of planes 0, 1, 2; tab: kFuseRow float4 per view of the stack; lamb: one byte per material index or nullptr.
 // grid: x = (tiles of 64 columns x rows) / 4; block 256.
-__global__ __launch_bounds__(kBlock) void k_accumulate_view(const float4* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ layers,
-                                                            const float4* prev1, const float4* prev2, float4* out0, float4* out1, float4* out2,
-                                                            const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t v,
-                                                            ptmf_consts k, ptma_consts ka) {
+// FRAMES: frames [n_stack] f32, F_u of every view of the stack; k.F is then not read: own, mean and the pass-through take F_v, the lookup's validity test F_{v-1}.
+template <bool FRAMES>
+DEV void accumulate_view(const float4* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ layers, const float4* prev1, const float4* prev2,
+                         float4* out0, float4* out1, float4* out2, const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t v,
+                         ptmf_consts k, ptma_consts ka, const float* __restrict__ frames) {
   const uint32_t tiles_x = ((uint32_t)W + 63u) / 64u;
   const uint32_t tile = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);  // wave-uniform
   const uint32_t y = tile / tiles_x;
@@ -40,6 +42,7 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_view(const float4* __rest
   if (x >= W) return;
   const size_t npix = (size_t)W * (size_t)H;
   const uint32_t idx = y * (uint32_t)W + (uint32_t)x;
+  if (FRAMES) k.F = ldu(frames + v);
   const float4* Lv = layers + (size_t)v * 3 * npix;
   const float4 Sp = colour[(size_t)v * npix + idx], Mp = moments[(size_t)v * npix + idx], Np = Lv[idx], Ap = Lv[npix + idx], Ip = Lv[2 * npix + idx];
   fuse_loaded(Sp, Np, Ap, Ip);
@@ -62,13 +65,36 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_view(const float4* __rest
       const float4 Sq = colour[(size_t)(v - 1u) * npix + q], Nq = Lu[q], Aq = Lu[npix + q], Iq = Lu[2 * npix + q], H1 = prev1[q], H2 = prev2[q];  // six independent gathers
       accumulate_loaded(Sq, Nq, Aq, Iq, H1, H2);
       float wgt;
-      if (ptma_weight(&k, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), &wgt)) ptma_take(&ka, wgt, dn_f4(H1), dn_f4(H2), &P1, &P2);
+      int taken;
+      if (FRAMES) {
+        ptmf_consts ku = k;
+        ku.F = ldu(frames + (v - 1u));
+        taken = ptma_weight(&ku, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), &wgt);
+      } else {
+        taken = ptma_weight(&k, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), &wgt);
+      }
+      if (taken) ptma_take(&ka, wgt, dn_f4(H1), dn_f4(H2), &P1, &P2);
     }
   }
   P2.w = ptma_v0(&ka, valid, P1, P2);
   out0[idx] = dn_float4(ptma_mean(&k, S, A, accumulates, P1));
   out1[idx] = dn_float4(P1);
   out2[idx] = dn_float4(P2);
+}
+
+__global__ __launch_bounds__(kBlock) void k_accumulate_view(const float4* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ layers,
+                                                            const float4* prev1, const float4* prev2, float4* out0, float4* out1, float4* out2,
+                                                            const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t v,
+                                                            ptmf_consts k, ptma_consts ka) {
+  accumulate_view<false>(colour, moments, layers, prev1, prev2, out0, out1, out2, tab, lamb, n_materials, W, H, v, k, ka, nullptr);
+}
+
+// k_accumulate_view with every view's own divisor (ptmi_accumulate_views_frames); frames: [n_stack] f32, behind the table's material bytes
+__global__ __launch_bounds__(kBlock) void k_accumulate_view_frames(const float4* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ layers,
+                                                                   const float4* prev1, const float4* prev2, float4* out0, float4* out1, float4* out2,
+                                                                   const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H,
+                                                                   uint32_t v, ptmf_consts k, ptma_consts ka, const float* __restrict__ frames) {
+  accumulate_view<true>(colour, moments, layers, prev1, prev2, out0, out1, out2, tab, lamb, n_materials, W, H, v, k, ka, frames);
 }
 
 // grid: x = tiles of 64 columns, y = tiles of kGuidedTY rows, z = view of the batch.  d0: [n][npix] packed (prepare); plane2: [n][npix] float4, w = the given v0 or NaN

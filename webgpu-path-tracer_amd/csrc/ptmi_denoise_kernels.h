@@ -14,6 +14,9 @@
 //                     GUIDED: a third plane of one float2 per tile pixel, v_l and l(d_l), the luminance taken once when the pixel is staged instead of once per tap
 //                     (the same bits): 40 B per tile pixel, 60 KB at s = 16 and at s = 32; vg(p) is one coalesced f32 load per pixel.
 //                     LAST: the level writes the output image (remodulated, or S / F where invalid) and, GUIDED and where asked for, v_levels (NaN where invalid).
+// The *_frames entry points (ptmi_denoise_views_frames, ..., include/ptmi.h "PER-VIEW FRAME NUMBERS AND COUNTS") divide view u's sums by F_u, read from a table of one
+// f32 per view: k_denoise_prepare_frames per lane (v = i / npix: a wave straddles two views wherever npix is no multiple of 64), the two LAST levels for the block's
+// view, blockIdx.z, through a scalar load.  The levels before the last read no F and are the instances above.
 #pragma once
 
 #include "../../include/ptmi_guided.h"
@@ -34,6 +37,19 @@ __global__ __launch_bounds__(kBlock) void k_denoise_prepare(const float4* __rest
     const float4* L = layers + v * 3 * npix;
     ptmd_f4 d, gg;
     ptmd_prepare(dn_f4(colour[i]), dn_f4(L[p]), dn_f4(L[npix + p]), dn_f4(L[2 * npix + p]), F, floor, &d, &gg);
+    d0[i] = dn_float4(d);
+    g[i] = dn_float4(gg);
+  }
+}
+
+// k_denoise_prepare with view v's own divisor: F [n] f32, the table at the batch's first view
+__global__ __launch_bounds__(kBlock) void k_denoise_prepare_frames(const float4* __restrict__ colour, const float4* __restrict__ layers, size_t n_items, size_t npix,
+                                                                   const float* __restrict__ F, float floor, float4* __restrict__ d0, float4* __restrict__ g) {
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_items; i += (size_t)gridDim.x * kBlock) {
+    const size_t v = i / npix, p = i - v * npix;
+    const float4* L = layers + v * 3 * npix;
+    ptmd_f4 d, gg;
+    ptmd_prepare(dn_f4(colour[i]), dn_f4(L[p]), dn_f4(L[npix + p]), dn_f4(L[2 * npix + p]), F[v], floor, &d, &gg);
     d0[i] = dn_float4(d);
     g[i] = dn_float4(gg);
   }
@@ -131,6 +147,19 @@ __global__ __launch_bounds__(kBlock) void k_guided_level(const float4* __restric
                                                          float4* __restrict__ dout, float* __restrict__ vout, const float4* __restrict__ colour, const float4* __restrict__ layers,
                                                          int W, int H, int step, int ty, ptmd_consts k, ptmg_consts kg, float F) {
   atrous_level<true, LAST>(din, g, vin, vg, dout, vout, colour, layers, W, H, step, ty, k, kg, F);
+}
+
+// The last level of either filter with the block's view's own divisor: F [n] f32, the table at the batch's first view
+__global__ __launch_bounds__(kBlock) void k_denoise_level_frames(const float4* __restrict__ din, const float4* __restrict__ g, float4* __restrict__ dout, const float4* __restrict__ colour,
+                                                                 const float4* __restrict__ layers, int W, int H, int step, int ty, ptmd_consts k, const float* __restrict__ F) {
+  atrous_level<false, true>(din, g, nullptr, nullptr, dout, nullptr, colour, layers, W, H, step, ty, k, ptmg_consts{}, ldu(F + blockIdx.z));
+}
+
+__global__ __launch_bounds__(kBlock) void k_guided_level_frames(const float4* __restrict__ din, const float4* __restrict__ g, const float* __restrict__ vin, const float* __restrict__ vg,
+                                                                float4* __restrict__ dout, float* __restrict__ vout, const float4* __restrict__ colour,
+                                                                const float4* __restrict__ layers, int W, int H, int step, int ty, ptmd_consts k, ptmg_consts kg,
+                                                                const float* __restrict__ F) {
+  atrous_level<true, true>(din, g, vin, vg, dout, vout, colour, layers, W, H, step, ty, k, kg, ldu(F + blockIdx.z));
 }
 
 }  // namespace ptmi

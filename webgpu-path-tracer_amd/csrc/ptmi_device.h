@@ -457,6 +457,7 @@ DEV int2 ldu(const int2* p) {
   return make_int2(v.x, v.y);
 }
 DEV int ldu(const int* p) { return *(const PTMI_CONST_AS int*)(p); }
+DEV float ldu(const float* p) { return *(const PTMI_CONST_AS float*)(p); }
 
 // ---- multi-view batches (ptmi_render_views) ------------------------------------------------------------
 // A batch whose frame slots belong to different views.  The call's V views lie in a device table, kViewRow float4 per view: the matrix's four columns, then

@@ -2,7 +2,8 @@
 // neighbour view of its window, the one pixel its first hit projects into.  Every f32 operation of a pixel is in include/ptmi_fuse.h, which the host native
 // ptmi_fuse_reference includes too; this file only decides where the operands come from.
 //
-// k_fuse   One lane owns one output pixel, a wave 64 neighbouring pixels of one row, a block four such waves; the grid's z axis runs over the call's output views, so
+// k_fuse, k_fuse_frames (one body, fuse_view)
+//          One lane owns one output pixel, a wave 64 neighbouring pixels of one row, a block four such waves; the grid's z axis runs over the call's output views, so
 //          a call is one launch.  The neighbour view u of the window loop is the same for the whole wave: its row of the view table (B_u, o_u: three float4) comes
 //          through scalar loads, as load_view_row's does, and so does the output view's own row (M_v, o_v).  An accepted projection reads S, N, A and I of q
 //          straight from the stacks — four 16-byte gathers that do not depend on one another, issued together; neighbouring lanes project to neighbouring q, so a
@@ -51,8 +52,11 @@ DEV void fuse_loaded(const float4& S, const float4& N, const float4& A, const fl
 
 // colour: [n_stack][npix] float4 (sums, or means with k.F = 1); layers: [n_stack][3][npix] float4; out: [n_stack][npix] float4; tab: kFuseRow float4 per view of the
 // stack; lamb: one byte per material index or nullptr.  grid: x = (tiles of 64 columns x rows) / 4, z = output view - view0; block 256.
-__global__ __launch_bounds__(kBlock) void k_fuse(const float4* __restrict__ colour, const float4* __restrict__ layers, float4* __restrict__ out, const float4* __restrict__ tab,
-                                                 const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k) {
+// FRAMES: frames [n_stack] f32, F_u of every view of the stack; k.F is then not read: p and the output take F_v, a neighbour's q takes F_u — u is wave-uniform, so the
+// count comes through a scalar load as the view's row does.
+template <bool FRAMES>
+DEV void fuse_view(const float4* __restrict__ colour, const float4* __restrict__ layers, float4* __restrict__ out, const float4* __restrict__ tab, const uint8_t* __restrict__ lamb,
+                   uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k, const float* __restrict__ frames) {
   const uint32_t tiles_x = ((uint32_t)W + 63u) / 64u;
   const uint32_t tile = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);  // wave-uniform
   const uint32_t y = tile / tiles_x;
@@ -62,6 +66,7 @@ __global__ __launch_bounds__(kBlock) void k_fuse(const float4* __restrict__ colo
   const size_t npix = (size_t)W * (size_t)H;
   const uint32_t v = view0 + blockIdx.z;
   const uint32_t idx = y * (uint32_t)W + (uint32_t)x;
+  if (FRAMES) k.F = ldu(frames + v);
   const float4* Lv = layers + (size_t)v * 3 * npix;
   const float4 Sp = colour[(size_t)v * npix + idx], Np = Lv[idx], Ap = Lv[npix + idx], Ip = Lv[2 * npix + idx];
   fuse_loaded(Sp, Np, Ap, Ip);
@@ -90,10 +95,28 @@ __global__ __launch_bounds__(kBlock) void k_fuse(const float4* __restrict__ colo
       const float4* Lu = layers + (size_t)u * 3 * npix;
       const float4 Sq = colour[(size_t)u * npix + q], Nq = Lu[q], Aq = Lu[npix + q], Iq = Lu[2 * npix + q];  // four independent gathers
       fuse_loaded(Sq, Nq, Aq, Iq);
-      ptmf_sample(&k, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), num, &den);
+      if (FRAMES) {
+        ptmf_consts ku = k;
+        ku.F = ldu(frames + u);
+        ptmf_sample(&ku, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), num, &den);
+      } else {
+        ptmf_sample(&k, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), num, &den);
+      }
     }
   }
   out[(size_t)v * npix + idx] = dn_float4(ptmf_output(&k, S, A, fused, num, den));
+}
+
+__global__ __launch_bounds__(kBlock) void k_fuse(const float4* __restrict__ colour, const float4* __restrict__ layers, float4* __restrict__ out, const float4* __restrict__ tab,
+                                                 const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k) {
+  fuse_view<false>(colour, layers, out, tab, lamb, n_materials, W, H, n_stack, view0, k, nullptr);
+}
+
+// k_fuse with every view's own divisor (ptmi_fuse_views_frames); frames: [n_stack] f32, behind the table's material bytes
+__global__ __launch_bounds__(kBlock) void k_fuse_frames(const float4* __restrict__ colour, const float4* __restrict__ layers, float4* __restrict__ out, const float4* __restrict__ tab,
+                                                        const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k,
+                                                        const float* __restrict__ frames) {
+  fuse_view<true>(colour, layers, out, tab, lamb, n_materials, W, H, n_stack, view0, k, frames);
 }
 
 }  // namespace ptmi

@@ -706,11 +706,20 @@ struct HostGuide {
   const float* given;  // ptmi_denoise_accumulated_reference: plane 2 of an accumulated stack, whose w is the initial variance where it is not NaN (moments is then nullptr)
 };
 
+// What the *_reference_frames calls ask of their frame counts: an array, every entry finite and > 0
+static int frame_nums_ok(const float* frame_nums, uint32_t n) {
+  if (!frame_nums) return 0;
+  for (uint32_t v = 0; v < n; v++)
+    if (!(frame_nums[v] > 0.0f) || !ptmd_finite(frame_nums[v])) return 0;
+  return 1;
+}
+
 // Both filters: a plain loop over pixels through include/ptmi_denoise.h and include/ptmi_guided.h, the headers the kernels of ptmi_denoise_views and
 // ptmi_denoise_views_guided compile: prepare, (guided: the initial variance,) per level (guided: the blur of the variance and) the 25 taps between two packed images,
 // remodulate.  One image after the other; nothing is tiled, threaded or reordered.  G = nullptr: the plain filter, which has no variance or luminance planes.
+// frame_nums: nullptr, or every image's own divisor (the *_reference_frames calls); the argument frame_num is then not read.
 static int atrous_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params& P, const HostGuide* G,
-                            float* out) {
+                            float* out, const float* frame_nums = nullptr) {
   const size_t npix = (size_t)w * (size_t)h;
   std::vector<ptmd_f4> d[2], g;
   std::vector<float> var[2], vg, lum;
@@ -727,6 +736,7 @@ static int atrous_reference(const float* colour_sums, const float* layers, int w
     const ptmd_f4* P2 = G && G->given ? reinterpret_cast<const ptmd_f4*>(G->given) + (size_t)v * npix : nullptr;
     const ptmd_f4* L = reinterpret_cast<const ptmd_f4*>(layers) + (size_t)v * 3 * npix;
     ptmd_f4* O = reinterpret_cast<ptmd_f4*>(out) + (size_t)v * npix;
+    if (frame_nums) frame_num = frame_nums[v];
     for (size_t p = 0; p < npix; p++) {
       ptmd_prepare(S[p], L[p], L[npix + p], L[2 * npix + p], frame_num, P.albedo_floor, &d[0][p], &g[p]);
       if (G) lum[p] = ptmg_luma(d[0][p].x, d[0][p].y, d[0][p].z);
@@ -810,19 +820,28 @@ static int atrous_reference(const float* colour_sums, const float* layers, int w
   return PTMI_OK;
 }
 
-extern "C" int ptmi_denoise_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params,
-                                      float* out) {
+static int denoise_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const float* frame_nums,
+                             const ptmi_denoise_params* params, float* out) {
   if (!colour_sums || !layers || !out || w <= 0 || h <= 0 || n_images == 0) return PTMI_ERR_INVALID_ARG;
   ptmi_denoise_params P;
   if (params) P = *params;
   else ptmi_default_denoise_params(&P);
   if (!ptmd_params_ok(P.levels, P.sigma_normal, P.sigma_depth, P.sigma_colour, P.albedo_floor)) return PTMI_ERR_INVALID_ARG;
   if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
-  return atrous_reference(colour_sums, layers, w, h, n_images, frame_num, P, nullptr, out);
+  return atrous_reference(colour_sums, layers, w, h, n_images, frame_num, P, nullptr, out, frame_nums);
+}
+extern "C" int ptmi_denoise_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params,
+                                      float* out) {
+  return denoise_reference(colour_sums, layers, w, h, n_images, frame_num, nullptr, params, out);
+}
+extern "C" int ptmi_denoise_reference_frames(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const float* frame_nums,
+                                             const ptmi_denoise_params* params, float* out) {
+  if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
+  return denoise_reference(colour_sums, layers, w, h, n_images, 1.0f, frame_nums, params, out);
 }
 
-extern "C" int ptmi_denoise_guided_reference(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
-                                             const ptmi_guided_params* params, float* out, float* var_out) {
+static int denoise_guided_reference(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
+                                    const float* frame_nums, const ptmi_guided_params* params, float* out, float* var_out) {
   if (!colour_sums || !moments || !layers || !out || w <= 0 || h <= 0 || n_images == 0) return PTMI_ERR_INVALID_ARG;
   ptmi_guided_params P;
   if (params) P = *params;
@@ -830,7 +849,17 @@ extern "C" int ptmi_denoise_guided_reference(const float* colour_sums, const flo
   if (!ptmg_params_ok(P.levels, P.sigma_normal, P.sigma_depth, P.sigma_luma, P.albedo_floor, P.min_frames, P.var_eps)) return PTMI_ERR_INVALID_ARG;
   if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
   const HostGuide G{moments, var_out, ptmg_make_consts(P.sigma_luma, P.var_eps), P.min_frames, nullptr};
-  return atrous_reference(colour_sums, layers, w, h, n_images, frame_num, ptmi_denoise_params{P.levels, P.sigma_normal, P.sigma_depth, 0.0f, P.albedo_floor, {}}, &G, out);
+  return atrous_reference(colour_sums, layers, w, h, n_images, frame_num, ptmi_denoise_params{P.levels, P.sigma_normal, P.sigma_depth, 0.0f, P.albedo_floor, {}}, &G, out,
+                          frame_nums);
+}
+extern "C" int ptmi_denoise_guided_reference(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
+                                             const ptmi_guided_params* params, float* out, float* var_out) {
+  return denoise_guided_reference(colour_sums, moments, layers, w, h, n_images, frame_num, nullptr, params, out, var_out);
+}
+extern "C" int ptmi_denoise_guided_reference_frames(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images,
+                                                    const float* frame_nums, const ptmi_guided_params* params, float* out, float* var_out) {
+  if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
+  return denoise_guided_reference(colour_sums, moments, layers, w, h, n_images, 1.0f, frame_nums, params, out, var_out);
 }
 
 extern "C" int ptmi_denoise_accumulated_reference(const float* means, const float* plane2, const float* layers, int w, int h, uint32_t n_images, const ptmi_guided_params* params,
@@ -856,9 +885,9 @@ extern "C" void ptmi_default_fuse_params(ptmi_fuse_params* p) {
 }
 
 // A plain loop over output views, pixels and neighbour views through include/ptmi_fuse.h, the header the kernel of ptmi_fuse_views compiles.  Nothing is tiled,
-// threaded or reordered.
-extern "C" int ptmi_fuse_reference(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
-                                   const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
+// threaded or reordered.  frame_nums: nullptr, or every image's own divisor (ptmi_fuse_reference_frames): view v's p and output take F_v, a neighbour's q takes F_u.
+static int fuse_reference(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, const float* frame_nums,
+                          float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
   if (!colour || !layers || !views16 || !out || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
   ptmi_fuse_params P;
   if (params) P = *params;
@@ -874,12 +903,13 @@ extern "C" int ptmi_fuse_reference(const float* colour, const float* layers, con
   }
   for (uint32_t v = 0; v < n_images; v++)
     if (!ptmf_make_view(views16 + 16 * (size_t)v, &tab[v])) return PTMI_ERR_INVALID_ARG;
-  const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
+  ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   const size_t npix = (size_t)w * (size_t)h;
   const ptmd_f4* S = reinterpret_cast<const ptmd_f4*>(colour);
   const ptmd_f4* L = reinterpret_cast<const ptmd_f4*>(layers);
   ptmd_f4* O = reinterpret_cast<ptmd_f4*>(out);
   for (uint32_t v = 0; v < n_images; v++) {
+    if (frame_nums) k.F = frame_nums[v];
     const ptmd_f4* Lv = L + (size_t)v * 3 * npix;
     const uint32_t u0 = v > (uint32_t)P.radius ? v - (uint32_t)P.radius : 0u, u1 = std::min(n_images - 1u, v + (uint32_t)P.radius);
     for (int y = 0; y < h; y++)
@@ -902,13 +932,24 @@ extern "C" int ptmi_fuse_reference(const float* colour, const float* layers, con
             if (!ptmf_project(&k, &tab[u], X, &qx, &qy, &r)) continue;
             const size_t q = (size_t)qy * (size_t)w + (size_t)qx;
             const ptmd_f4* Lu = L + (size_t)u * 3 * npix;
-            ptmf_sample(&k, dp, gp, r, S[(size_t)u * npix + q], Lu[q], Lu[npix + q], Lu[2 * npix + q], num, &den);
+            ptmf_consts ku = k;
+            if (frame_nums) ku.F = frame_nums[u];
+            ptmf_sample(&ku, dp, gp, r, S[(size_t)u * npix + q], Lu[q], Lu[npix + q], Lu[2 * npix + q], num, &den);
           }
         }
         O[(size_t)v * npix + idx] = ptmf_output(&k, Sp, Ap, fused, num, den);
       }
   }
   return PTMI_OK;
+}
+extern "C" int ptmi_fuse_reference(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
+                                   const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
+  return fuse_reference(colour, layers, views16, w, h, n_images, frame_num, nullptr, fov_degrees, lambertian, n_materials, params, out);
+}
+extern "C" int ptmi_fuse_reference_frames(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
+                                          float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
+  if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
+  return fuse_reference(colour, layers, views16, w, h, n_images, 1.0f, frame_nums, fov_degrees, lambertian, n_materials, params, out);
 }
 
 // ---- temporal accumulation on the host (ptmi_accumulate_reference) ----
@@ -924,9 +965,10 @@ extern "C" void ptmi_default_accumulate_params(ptmi_accumulate_params* p) {
 
 // A plain loop over views, in order, and pixels through include/ptmi_accumulate.h, the header the kernel of ptmi_accumulate_views compiles.  View v reads planes 1 and 2
 // of view v-1 in `out`, as the kernel does.  Nothing is tiled or reordered; `threads` > 1 share the rows of a view, whose pixels do not depend on one another.
-extern "C" int ptmi_accumulate_reference(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
-                                         float frame_num, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
-                                         const float* history_in, float* out, int threads) {
+// frame_nums: nullptr, or every image's own divisor (ptmi_accumulate_reference_frames): own, mean and the pass-through of view v take F_v, the lookup in view v-1 F_{v-1}.
+static int accumulate_reference(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
+                                const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
+                                const float* history_in, float* out, int threads) {
   if (!colour_sums || !moments || !layers || !views16 || !out || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
   ptmi_accumulate_params P;
   if (params) P = *params;
@@ -943,7 +985,7 @@ extern "C" int ptmi_accumulate_reference(const float* colour_sums, const float* 
   }
   for (uint32_t v = 0; v < n_images; v++)
     if (!ptmf_make_view(views16 + 16 * (size_t)v, &tab[v])) return PTMI_ERR_INVALID_ARG;
-  const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
+  ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor), ku = k;
   const ptma_consts ka = ptma_make_consts(P.max_history, P.min_frames);
   const size_t npix = (size_t)w * (size_t)h;
   const ptmd_f4* S = reinterpret_cast<const ptmd_f4*>(colour_sums);
@@ -962,6 +1004,7 @@ extern "C" int ptmi_accumulate_reference(const float* colour_sums, const float* 
   for (uint32_t v = first; v < n_images; v++) {
     const ptmd_f4* Lv = L + (size_t)v * 3 * npix;
     const bool has_prev = v > 0;
+    if (frame_nums) k.F = frame_nums[v], ku.F = frame_nums[has_prev ? v - 1 : v];
     const ptmd_f4* Lu = has_prev ? L + (size_t)(v - 1) * 3 * npix : nullptr;
     const ptmd_f4 *prev1 = has_prev ? plane(1, v - 1) : nullptr, *prev2 = has_prev ? plane(2, v - 1) : nullptr;
     ptmd_f4 *o0 = plane(0, v), *o1 = plane(1, v), *o2 = plane(2, v);
@@ -980,7 +1023,7 @@ extern "C" int ptmi_accumulate_reference(const float* colour_sums, const float* 
             ptmf_world(&k, &tab[v], x, idx, gp.w, X);
             if (ptmf_project(&k, &tab[v - 1], X, &qx, &qy, &r)) {
               const size_t q = (size_t)qy * (size_t)w + (size_t)qx;
-              if (ptma_weight(&k, dp, gp, r, S[(size_t)(v - 1) * npix + q], Lu[q], Lu[npix + q], Lu[2 * npix + q], &wgt)) ptma_take(&ka, wgt, prev1[q], prev2[q], &P1, &P2);
+              if (ptma_weight(&ku, dp, gp, r, S[(size_t)(v - 1) * npix + q], Lu[q], Lu[npix + q], Lu[2 * npix + q], &wgt)) ptma_take(&ka, wgt, prev1[q], prev2[q], &P1, &P2);
             }
           }
           P2.w = ptma_v0(&ka, valid, P1, P2);
@@ -993,6 +1036,17 @@ extern "C" int ptmi_accumulate_reference(const float* colour_sums, const float* 
     else if (!run_workers(nt, rows)) return PTMI_ERR_NO_MEMORY;
   }
   return PTMI_OK;
+}
+extern "C" int ptmi_accumulate_reference(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                         float frame_num, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
+                                         const float* history_in, float* out, int threads) {
+  return accumulate_reference(colour_sums, moments, layers, views16, w, h, n_images, frame_num, nullptr, fov_degrees, lambertian, n_materials, params, history_in, out, threads);
+}
+extern "C" int ptmi_accumulate_reference_frames(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                                const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
+                                                const ptmi_accumulate_params* params, const float* history_in, float* out, int threads) {
+  if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
+  return accumulate_reference(colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, fov_degrees, lambertian, n_materials, params, history_in, out, threads);
 }
 
 // ---- the noise statistic on the host (ptmi_noise_reference) ----

@@ -60,6 +60,11 @@ FN(ptmi_read_accumulated)
 FN(ptmi_release_accumulated)
 FN(ptmi_denoise_views_accumulated)
 FN(ptmi_set_view_moments)
+FN(ptmi_views_device_ptr)
+FN(ptmi_denoise_views_frames)
+FN(ptmi_denoise_views_guided_frames)
+FN(ptmi_fuse_views_frames)
+FN(ptmi_accumulate_views_frames)
 FN(ptmi_read_moments)
 FN(ptmi_release_moments)
 FN(ptmi_default_noise_params)
@@ -118,6 +123,7 @@ static int load_lib(char* err, size_t errlen) {
   LOAD(ptmi_version) LOAD(ptmi_last_error) LOAD(ptmi_create) LOAD(ptmi_create_multi) LOAD(ptmi_prepare) LOAD(ptmi_destroy) LOAD(ptmi_default_params) LOAD(ptmi_default_denoise_params) LOAD(ptmi_set_params)
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
   LOAD(ptmi_render_views_frames) LOAD(ptmi_render_aov_frames) LOAD(ptmi_render_views_until_each)
+  LOAD(ptmi_views_device_ptr) LOAD(ptmi_denoise_views_frames) LOAD(ptmi_denoise_views_guided_frames) LOAD(ptmi_fuse_views_frames) LOAD(ptmi_accumulate_views_frames)
   LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_default_guided_params) LOAD(ptmi_denoise_views_guided) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_default_accumulate_params) LOAD(ptmi_accumulate_views) LOAD(ptmi_read_accumulated) LOAD(ptmi_release_accumulated) LOAD(ptmi_denoise_views_accumulated) LOAD(ptmi_set_view_moments) LOAD(ptmi_read_moments) LOAD(ptmi_release_moments) LOAD(ptmi_default_noise_params) LOAD(ptmi_view_noise_stats) LOAD(ptmi_render_views_until) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
   LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_check_bvh_boxes) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah)
   LOAD(ptmi_obj_parse) LOAD(ptmi_free) LOAD(ptmi_device_count) LOAD(ptmi_reduce_info)
@@ -582,14 +588,35 @@ static napi_value js_read_aov(napi_env env, napi_callback_info info) {
 
 /* denoiseViews(ctx, frameNum, firstView, nViews, params | null): ptmi_denoise_views — params = {levels, sigmaNormal, sigmaDepth, sigmaColour, albedoFloor}, every
  * field optional (ptmi_default_denoise_params fills the rest) */
-static napi_value js_denoise_views(napi_env env, napi_callback_info info) {
+/* The frameNums argument of the *Frames calls: a Float32Array with one count per view OF THE STACK (the library copies that many; a context whose view stack it
+ * cannot ask — none yet, several devices — is refused by the call itself before anything is read).  0, *out set; non-zero: thrown. */
+static int frame_nums_arg(napi_env env, ptmi_ctx* c, napi_value v, const char* what, const float** out) {
+  void* data;
+  size_t len;
+  if (typed(env, v, napi_float32_array, what, &data, &len)) return -1;
+  void* dev;
+  uint32_t n_stack = 0;
+  if (p_ptmi_views_device_ptr(c, &dev, NULL, &n_stack) == PTMI_OK && len < n_stack) {
+    napi_throw_range_error(env, NULL, "frameNums must hold one count for each view of the stack");
+    return -1;
+  }
+  *out = (const float*)data;
+  return 0;
+}
+
+static napi_value denoise_views_common(napi_env env, napi_callback_info info, int frames) {
   napi_value a[5];
   if (get_args(env, info, 5, a)) return NULL;
   ptmi_ctx* c = ctx_of(env, a[0]);
   if (!c) return NULL;
-  double frame_num;
+  double frame_num = 1.0;
+  const float* frame_nums = NULL;
   uint32_t first, n_views;
-  CHECK_NAPI(napi_get_value_double(env, a[1], &frame_num));
+  if (frames) {
+    if (frame_nums_arg(env, c, a[1], "denoiseViewsFrames(frameNums)", &frame_nums)) return NULL;
+  } else {
+    CHECK_NAPI(napi_get_value_double(env, a[1], &frame_num));
+  }
   CHECK_NAPI(napi_get_value_uint32(env, a[2], &first));
   CHECK_NAPI(napi_get_value_uint32(env, a[3], &n_views));
   ptmi_denoise_params P;
@@ -600,21 +627,29 @@ static napi_value js_denoise_views(napi_env env, napi_callback_info info) {
                                        {"sigmaColour", 0, offsetof(ptmi_denoise_params, sigma_colour)},
                                        {"albedoFloor", 0, offsetof(ptmi_denoise_params, albedo_floor)}};
   CHECK_PARAMS(a[4], fields, &P, "denoiseViews")
-  int st = p_ptmi_denoise_views(c, &P, (float)frame_num, first, n_views);
-  if (st) return throw_status(env, c, st, "ptmi_denoise_views");
+  int st = frames ? p_ptmi_denoise_views_frames(c, &P, frame_nums, first, n_views) : p_ptmi_denoise_views(c, &P, (float)frame_num, first, n_views);
+  if (st) return throw_status(env, c, st, frames ? "ptmi_denoise_views_frames" : "ptmi_denoise_views");
   return NULL;
 }
+static napi_value js_denoise_views(napi_env env, napi_callback_info info) { return denoise_views_common(env, info, 0); }
+/* denoiseViewsFrames(ctx, Float32Array frameNums, firstView, nViews, params | null): ptmi_denoise_views_frames — one frame count per view of the stack */
+static napi_value js_denoise_views_frames(napi_env env, napi_callback_info info) { return denoise_views_common(env, info, 1); }
 
 /* denoiseViewsGuided(ctx, frameNum, firstView, nViews, params | null): ptmi_denoise_views_guided — params = {levels, sigmaNormal, sigmaDepth, sigmaLuma, albedoFloor,
  * minFrames, varEps}, every field optional (ptmi_default_guided_params fills the rest) */
-static napi_value js_denoise_views_guided(napi_env env, napi_callback_info info) {
+static napi_value denoise_views_guided_common(napi_env env, napi_callback_info info, int frames) {
   napi_value a[5];
   if (get_args(env, info, 5, a)) return NULL;
   ptmi_ctx* c = ctx_of(env, a[0]);
   if (!c) return NULL;
-  double frame_num;
+  double frame_num = 1.0;
+  const float* frame_nums = NULL;
   uint32_t first, n_views;
-  CHECK_NAPI(napi_get_value_double(env, a[1], &frame_num));
+  if (frames) {
+    if (frame_nums_arg(env, c, a[1], "denoiseViewsGuidedFrames(frameNums)", &frame_nums)) return NULL;
+  } else {
+    CHECK_NAPI(napi_get_value_double(env, a[1], &frame_num));
+  }
   CHECK_NAPI(napi_get_value_uint32(env, a[2], &first));
   CHECK_NAPI(napi_get_value_uint32(env, a[3], &n_views));
   ptmi_guided_params P;
@@ -627,16 +662,20 @@ static napi_value js_denoise_views_guided(napi_env env, napi_callback_info info)
                                        {"albedoFloor", 0, offsetof(ptmi_guided_params, albedo_floor)},
                                        {"varEps", 0, offsetof(ptmi_guided_params, var_eps)}};
   CHECK_PARAMS(a[4], fields, &P, "denoiseViewsGuided")
-  int st = p_ptmi_denoise_views_guided(c, &P, (float)frame_num, first, n_views);
-  if (st) return throw_status(env, c, st, "ptmi_denoise_views_guided");
+  int st = frames ? p_ptmi_denoise_views_guided_frames(c, &P, frame_nums, first, n_views) : p_ptmi_denoise_views_guided(c, &P, (float)frame_num, first, n_views);
+  if (st) return throw_status(env, c, st, frames ? "ptmi_denoise_views_guided_frames" : "ptmi_denoise_views_guided");
   return NULL;
 }
+static napi_value js_denoise_views_guided(napi_env env, napi_callback_info info) { return denoise_views_guided_common(env, info, 0); }
+/* denoiseViewsGuidedFrames(ctx, Float32Array frameNums, firstView, nViews, params | null): ptmi_denoise_views_guided_frames */
+static napi_value js_denoise_views_guided_frames(napi_env env, napi_callback_info info) { return denoise_views_guided_common(env, info, 1); }
 
 /* fuseViews(ctx, views, frameNum, source, firstView, nViews, params | null): ptmi_fuse_views — views holds the matrices of ALL views of the stack; params =
  * {radius, sigmaNormal, sigmaDepth, albedoFloor}, every field optional (ptmi_default_fuse_params fills the rest) */
-static napi_value js_fuse_views(napi_env env, napi_callback_info info) {
+static napi_value fuse_views_common(napi_env env, napi_callback_info info, int frames) {
   napi_value a[7];
-  if (get_args(env, info, 7, a)) return NULL;
+  if (get_args(env, info, frames ? 6 : 7, a)) return NULL;
+  if (frames) a[6] = a[5], a[5] = a[4], a[4] = a[3];  /* (no `source`: the view stack) */
   ptmi_ctx* c = ctx_of(env, a[0]);
   if (!c) return NULL;
   void* data;
@@ -646,11 +685,16 @@ static napi_value js_fuse_views(napi_env env, napi_callback_info info) {
     napi_throw_range_error(env, NULL, "fuseViews: views must hold 16 floats for each view of the stack, one view at least");
     return NULL;
   }
-  double frame_num;
-  int32_t source;
+  double frame_num = 1.0;
+  const float* frame_nums = NULL;
+  int32_t source = 0;
   uint32_t first, n_views;
-  CHECK_NAPI(napi_get_value_double(env, a[2], &frame_num));
-  CHECK_NAPI(napi_get_value_int32(env, a[3], &source));
+  if (frames) {
+    if (frame_nums_arg(env, c, a[2], "fuseViewsFrames(frameNums)", &frame_nums)) return NULL;
+  } else {
+    CHECK_NAPI(napi_get_value_double(env, a[2], &frame_num));
+    CHECK_NAPI(napi_get_value_int32(env, a[3], &source));
+  }
   CHECK_NAPI(napi_get_value_uint32(env, a[4], &first));
   CHECK_NAPI(napi_get_value_uint32(env, a[5], &n_views));
   if ((uint64_t)first + n_views > len / 16) {
@@ -664,14 +708,17 @@ static napi_value js_fuse_views(napi_env env, napi_callback_info info) {
                                        {"sigmaDepth", 0, offsetof(ptmi_fuse_params, sigma_depth)},
                                        {"albedoFloor", 0, offsetof(ptmi_fuse_params, albedo_floor)}};
   CHECK_PARAMS(a[6], fields, &P, "fuseViews")
-  int st = p_ptmi_fuse_views(c, &P, (const float*)data, (float)frame_num, source, first, n_views);
-  if (st) return throw_status(env, c, st, "ptmi_fuse_views");
+  int st = frames ? p_ptmi_fuse_views_frames(c, &P, (const float*)data, frame_nums, first, n_views) : p_ptmi_fuse_views(c, &P, (const float*)data, (float)frame_num, source, first, n_views);
+  if (st) return throw_status(env, c, st, frames ? "ptmi_fuse_views_frames" : "ptmi_fuse_views");
   return NULL;
 }
+static napi_value js_fuse_views(napi_env env, napi_callback_info info) { return fuse_views_common(env, info, 0); }
+/* fuseViewsFrames(ctx, views, Float32Array frameNums, firstView, nViews, params | null): ptmi_fuse_views_frames — the view stack as source */
+static napi_value js_fuse_views_frames(napi_env env, napi_callback_info info) { return fuse_views_common(env, info, 1); }
 
 /* accumulateViews(ctx, views, frameNum, firstView, nViews, resume, params | null): ptmi_accumulate_views — views holds the matrices of ALL views of the stack; params =
  * {maxHistory, minFrames, sigmaNormal, sigmaDepth, albedoFloor}, every field optional (ptmi_default_accumulate_params fills the rest) */
-static napi_value js_accumulate_views(napi_env env, napi_callback_info info) {
+static napi_value accumulate_views_common(napi_env env, napi_callback_info info, int frames) {
   napi_value a[7];
   if (get_args(env, info, 7, a)) return NULL;
   ptmi_ctx* c = ctx_of(env, a[0]);
@@ -683,9 +730,14 @@ static napi_value js_accumulate_views(napi_env env, napi_callback_info info) {
     napi_throw_range_error(env, NULL, "accumulateViews: views must hold 16 floats for each view of the stack, one view at least");
     return NULL;
   }
-  double frame_num;
+  double frame_num = 1.0;
+  const float* frame_nums = NULL;
   uint32_t first, n_views;
-  CHECK_NAPI(napi_get_value_double(env, a[2], &frame_num));
+  if (frames) {
+    if (frame_nums_arg(env, c, a[2], "accumulateViewsFrames(frameNums)", &frame_nums)) return NULL;
+  } else {
+    CHECK_NAPI(napi_get_value_double(env, a[2], &frame_num));
+  }
   CHECK_NAPI(napi_get_value_uint32(env, a[3], &first));
   CHECK_NAPI(napi_get_value_uint32(env, a[4], &n_views));
   if ((uint64_t)first + n_views > len / 16) {
@@ -703,10 +755,14 @@ static napi_value js_accumulate_views(napi_env env, napi_callback_info info) {
                                        {"sigmaDepth", 0, offsetof(ptmi_accumulate_params, sigma_depth)},
                                        {"albedoFloor", 0, offsetof(ptmi_accumulate_params, albedo_floor)}};
   CHECK_PARAMS(a[6], fields, &P, "accumulateViews")
-  int st = p_ptmi_accumulate_views(c, &P, (const float*)data, (float)frame_num, first, n_views, resume ? 1 : 0);
-  if (st) return throw_status(env, c, st, "ptmi_accumulate_views");
+  int st = frames ? p_ptmi_accumulate_views_frames(c, &P, (const float*)data, frame_nums, first, n_views, resume ? 1 : 0)
+                  : p_ptmi_accumulate_views(c, &P, (const float*)data, (float)frame_num, first, n_views, resume ? 1 : 0);
+  if (st) return throw_status(env, c, st, frames ? "ptmi_accumulate_views_frames" : "ptmi_accumulate_views");
   return NULL;
 }
+static napi_value js_accumulate_views(napi_env env, napi_callback_info info) { return accumulate_views_common(env, info, 0); }
+/* accumulateViewsFrames(ctx, views, Float32Array frameNums, firstView, nViews, resume, params | null): ptmi_accumulate_views_frames */
+static napi_value js_accumulate_views_frames(napi_env env, napi_callback_info info) { return accumulate_views_common(env, info, 1); }
 
 /* readAccumulated(ctx, view, plane, Float32Array out): image `view` of plane `plane` (0 .. 2) of the accumulated stack */
 static napi_value js_read_accumulated(napi_env env, napi_callback_info info) {
@@ -1233,7 +1289,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"version", js_version}, {"create", js_create}, {"destroy", js_destroy}, {"defaultParams", js_default_params}, {"setParams", js_set_params},
       {"upload", js_upload}, {"resize", js_resize}, {"clear", js_clear}, {"setShard", js_set_shard}, {"renderFrame", js_render_frame},
       {"renderViewsFrames", js_render_views_frames}, {"renderAovFrames", js_render_aov_frames}, {"renderViewsUntilEach", js_render_views_until_each},
-      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"denoiseViewsGuided", js_denoise_views_guided}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"accumulateViews", js_accumulate_views}, {"readAccumulated", js_read_accumulated}, {"releaseAccumulated", js_release_accumulated}, {"denoiseViewsAccumulated", js_denoise_views_accumulated}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
+      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"denoiseViewsGuided", js_denoise_views_guided}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"accumulateViews", js_accumulate_views}, {"readAccumulated", js_read_accumulated}, {"releaseAccumulated", js_release_accumulated}, {"denoiseViewsAccumulated", js_denoise_views_accumulated}, {"denoiseViewsFrames", js_denoise_views_frames}, {"denoiseViewsGuidedFrames", js_denoise_views_guided_frames}, {"fuseViewsFrames", js_fuse_views_frames}, {"accumulateViewsFrames", js_accumulate_views_frames}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
       {"resolveRGBA8", js_resolve}, {"setCounters", js_set_counters}, {"setTiming", js_set_timing}, {"stats", js_stats},
       {"resetStats", js_reset_stats}, {"buildBVH", js_build_bvh}, {"buildBVHSAH", js_build_bvh_sah}, {"buildBVHDevice", js_build_bvh_device}, {"parseObj", js_parse_obj},
       {"deviceCount", js_device_count}, {"reduceInfo", js_reduce_info},

@@ -30,5 +30,9 @@ export class MockBackend {
     this.calls.push(['renderViewsUntil', views.length / 16, firstFrame, framesPerRound, maxFrames, target, params]);
     return { framesDone: maxFrames, noise: Array.from({ length: views.length / 16 }, () => ({ counted: 0, sumQ: 0, above: 0, maxQ: 0 })) };
   }
+  denoiseViewsFrames(frameNums, firstView, nViews, params = null) { this.calls.push(['denoiseViewsFrames', Array.from(frameNums), firstView, nViews, params]); }
+  denoiseViewsGuidedFrames(frameNums, firstView, nViews, params = null) { this.calls.push(['denoiseViewsGuidedFrames', Array.from(frameNums), firstView, nViews, params]); }
+  fuseViewsFrames(views, frameNums, firstView, nViews, params = null) { this.calls.push(['fuseViewsFrames', views.length / 16, Array.from(frameNums), firstView, nViews, params]); }
+  accumulateViewsFrames(views, frameNums, firstView, nViews, resume = false, params = null) { this.calls.push(['accumulateViewsFrames', views.length / 16, Array.from(frameNums), firstView, nViews, !!resume, params]); }
   synchronize() {}
 }

@@ -82,6 +82,15 @@ export class Ptmi {
   renderViewsUntilEach(views, firstFrames, framesPerRound, maxFrames, target, params = null) {
     return this.native.renderViewsUntilEach(this.h, views, firstFrames, framesPerRound, maxFrames, target, params);
   }
+  // The consumers with one frame count per view (ptmi_denoise_views_frames ...): frameNums = one count per view OF THE STACK, a Float32Array or anything
+  // Float32Array.from takes — renderViewsUntilEach's framesDone as it is; only the entries a call reads are checked (the denoisers: the range; fusion: the range
+  // widened by the radius; accumulation: the range and, resuming, the view before it).  fuseViewsFrames reads the view stack (the denoised stack holds means).
+  denoiseViewsFrames(frameNums, firstView, nViews, params = null) { this.native.denoiseViewsFrames(this.h, Float32Array.from(frameNums), firstView, nViews, params); }
+  denoiseViewsGuidedFrames(frameNums, firstView, nViews, params = null) { this.native.denoiseViewsGuidedFrames(this.h, Float32Array.from(frameNums), firstView, nViews, params); }
+  fuseViewsFrames(views, frameNums, firstView, nViews, params = null) { this.native.fuseViewsFrames(this.h, views, Float32Array.from(frameNums), firstView, nViews, params); }
+  accumulateViewsFrames(views, frameNums, firstView, nViews, resume = false, params = null) {
+    this.native.accumulateViewsFrames(this.h, views, Float32Array.from(frameNums), firstView, nViews, resume, params);
+  }
   synchronize() { this.native.synchronize(this.h); }
   prepare() { this.native.prepare(this.h); }
   buildSceneBVHSAH() { this.native.buildSceneBVHSAH(this.h); }   // the same with the reference's never-called SAH builder (lib/BVH/bvhNode.js:108-283): opt-in

@@ -34,6 +34,9 @@ SYMBOLS = [
     "ptmi_default_noise_params", "ptmi_view_noise_stats", "ptmi_noise_images", "ptmi_noise_reference", "ptmi_render_views_until",
     "ptmi_render_views_frames", "ptmi_render_aov_frames", "ptmi_render_views_until_each", "ptmi_view_slot_plan",
     "ptmi_check_bvh_boxes",
+    "ptmi_denoise_views_frames", "ptmi_denoise_views_guided_frames", "ptmi_fuse_views_frames", "ptmi_accumulate_views_frames",
+    "ptmi_denoise_images_frames", "ptmi_denoise_images_guided_frames", "ptmi_fuse_images_frames", "ptmi_accumulate_images_frames",
+    "ptmi_denoise_reference_frames", "ptmi_denoise_guided_reference_frames", "ptmi_fuse_reference_frames", "ptmi_accumulate_reference_frames",
 ]
 
 VIEW_SLOT_TABLE_MAX_WORDS = 1 << 24  # PTMI_VIEW_SLOT_TABLE_MAX_WORDS
@@ -256,6 +259,20 @@ def load_library(build=False, path=None):
         L.ptmi_render_aov_frames.argtypes = [vp, fp, u32, fp, fp, i32]
         L.ptmi_render_views_until_each.argtypes = [vp, fp, u32, fp, u32, u32, ctypes.POINTER(NoiseParams), ctypes.c_float, fp, fp]
         L.ptmi_view_slot_plan.argtypes = [u32, fp, fp, fp, sz, up]
+    if hasattr(L, "ptmi_denoise_views_frames"):  # (an older A/B build loaded through PTMI_LIB takes one frame_num per call)
+        dp, gp, up, ap = ctypes.POINTER(DenoiseParams), ctypes.POINTER(GuidedParams), ctypes.POINTER(FuseParams), ctypes.POINTER(AccumulateParams)
+        L.ptmi_denoise_views_frames.argtypes = [vp, dp, fp, u32, u32]
+        L.ptmi_denoise_views_guided_frames.argtypes = [vp, gp, fp, u32, u32]
+        L.ptmi_fuse_views_frames.argtypes = [vp, up, fp, fp, u32, u32]
+        L.ptmi_accumulate_views_frames.argtypes = [vp, ap, fp, fp, u32, u32, i32]
+        L.ptmi_denoise_images_frames.argtypes = [vp, fp, fp, i32, i32, u32, fp, dp, fp]
+        L.ptmi_denoise_images_guided_frames.argtypes = [vp, fp, fp, fp, i32, i32, u32, fp, gp, fp, fp]
+        L.ptmi_fuse_images_frames.argtypes = [vp, fp, fp, fp, i32, i32, u32, fp, ctypes.c_float, fp, u32, up, fp]
+        L.ptmi_accumulate_images_frames.argtypes = [vp, fp, fp, fp, fp, i32, i32, u32, fp, ctypes.c_float, fp, u32, ap, fp, fp]
+        L.ptmi_denoise_reference_frames.argtypes = [fp, fp, i32, i32, u32, fp, dp, fp]
+        L.ptmi_denoise_guided_reference_frames.argtypes = [fp, fp, fp, i32, i32, u32, fp, gp, fp, fp]
+        L.ptmi_fuse_reference_frames.argtypes = [fp, fp, fp, i32, i32, u32, fp, ctypes.c_float, fp, u32, up, fp]
+        L.ptmi_accumulate_reference_frames.argtypes = [fp, fp, fp, fp, i32, i32, u32, fp, ctypes.c_float, fp, u32, ap, fp, fp, i32]
     if explicit:
         _libs[path] = L
     else:
@@ -272,6 +289,20 @@ def _frame_arrays(n_views, first_frames, frame_counts):
     f = np.ascontiguousarray(np.broadcast_to(np.asarray(first_frames, np.uint32), (n_views,)))
     k = np.ascontiguousarray(np.broadcast_to(np.asarray(frame_counts, np.uint32), (n_views,)))
     return f, k
+
+
+def _frame_nums(frame_nums, n):
+    """The per-view f32 divisors of the *_frames consumers: any sequence of n numbers — render_views_until_each's frames_done as it is; None stays a null pointer,
+    which the library refuses."""
+    if frame_nums is None:
+        return None
+    f = np.ascontiguousarray(frame_nums, np.float32).reshape(-1)
+    assert f.size == n, "frame_nums: one count per view, %d of them" % n
+    return f
+
+
+def _optr(a):
+    return None if a is None else _ptr(a)
 
 
 def view_slot_plan(first_frames, frame_counts):
@@ -332,6 +363,16 @@ def denoise_reference(colour_sums, layers, frame_num, params=None, lib=None):
     return out
 
 
+def denoise_reference_frames(colour_sums, layers, frame_nums, params=None, lib=None):
+    """ptmi_denoise_reference_frames: denoise_reference with one frame count per image, frame_nums (n,): image v's sums are divided by frame_nums[v]."""
+    c, l, out = _denoise_arrays(colour_sums, layers)
+    f = _frame_nums(frame_nums, c.shape[0])
+    st = (lib or load_library()).ptmi_denoise_reference_frames(_ptr(c), _ptr(l), c.shape[2], c.shape[1], c.shape[0], _optr(f), None if params is None else ctypes.byref(params), _ptr(out))
+    if st != 0:
+        raise PtmiError(st, "ptmi_denoise_reference_frames failed")
+    return out
+
+
 def default_guided_params(lib=None, **kw):
     """ptmi_default_guided_params (levels 5, sigma_normal 0.25, sigma_depth 0.1, sigma_luma 4, albedo_floor 1e-3, min_frames 4, var_eps 1e-10) with fields replaced
     by keyword."""
@@ -357,6 +398,17 @@ def denoise_guided_reference(colour_sums, moments, layers, frame_num, params=Non
                                                                None if params is None else ctypes.byref(params), _ptr(out), None if var is None else _ptr(var))
     if st != 0:
         raise PtmiError(st, "ptmi_denoise_guided_reference failed")
+    return (out, var) if want_var else out
+
+
+def denoise_guided_reference_frames(colour_sums, moments, layers, frame_nums, params=None, want_var=False, lib=None):
+    """ptmi_denoise_guided_reference_frames: denoise_guided_reference with one frame count per image, frame_nums (n,)."""
+    c, m, l, out, var = _guided_arrays(colour_sums, moments, layers, want_var)
+    f = _frame_nums(frame_nums, c.shape[0])
+    st = (lib or load_library()).ptmi_denoise_guided_reference_frames(_ptr(c), _ptr(m), _ptr(l), c.shape[2], c.shape[1], c.shape[0], _optr(f),
+                                                                      None if params is None else ctypes.byref(params), _ptr(out), _optr(var))
+    if st != 0:
+        raise PtmiError(st, "ptmi_denoise_guided_reference_frames failed")
     return (out, var) if want_var else out
 
 
@@ -389,6 +441,18 @@ def fuse_reference(colour, layers, views, frame_num, fov_degrees=60.0, lambertia
     return out
 
 
+def fuse_reference_frames(colour, layers, views, frame_nums, fov_degrees=60.0, lambertian=None, params=None, lib=None):
+    """ptmi_fuse_reference_frames: fuse_reference with one frame count per image, frame_nums (n,): the output view's own count divides its pixel and the output, a
+    neighbour view's count the pixel looked up in it."""
+    c, l, v, t, out = _fuse_arrays(colour, layers, views, lambertian)
+    f = _frame_nums(frame_nums, c.shape[0])
+    st = (lib or load_library()).ptmi_fuse_reference_frames(_ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), float(fov_degrees),
+                                                            _optr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params), _ptr(out))
+    if st != 0:
+        raise PtmiError(st, "ptmi_fuse_reference_frames failed")
+    return out
+
+
 def default_accumulate_params(lib=None, **kw):
     """ptmi_default_accumulate_params (max_history 32, min_frames 4, sigma_normal 0.25, sigma_depth 0.1, albedo_floor 1e-3) with fields replaced by keyword."""
     p = AccumulateParams()
@@ -416,6 +480,19 @@ def accumulate_reference(colour_sums, moments, layers, views, frame_num, fov_deg
                                                            None if hist is None else _ptr(hist), _ptr(out), int(threads))
     if st != 0:
         raise PtmiError(st, "ptmi_accumulate_reference failed")
+    return out
+
+
+def accumulate_reference_frames(colour_sums, moments, layers, views, frame_nums, fov_degrees=60.0, lambertian=None, params=None, history=None, threads=1, lib=None):
+    """ptmi_accumulate_reference_frames: accumulate_reference with one frame count per image, frame_nums (n,): view v's own count divides its sums, view v-1's the
+    pixel looked up there (with `history`, image 0's entry serves that lookup)."""
+    c, m, l, v, t, hist, out = _accumulate_arrays(colour_sums, moments, layers, views, lambertian, history)
+    f = _frame_nums(frame_nums, c.shape[0])
+    st = (lib or load_library()).ptmi_accumulate_reference_frames(_ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), float(fov_degrees),
+                                                                  _optr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params),
+                                                                  _optr(hist), _ptr(out), int(threads))
+    if st != 0:
+        raise PtmiError(st, "ptmi_accumulate_reference_frames failed")
     return out
 
 
@@ -787,6 +864,78 @@ class Context:
         self._ck(self.lib.ptmi_denoise_images_accumulated(self.h, _ptr(c), _ptr(p2), _ptr(l), c.shape[2], c.shape[1], c.shape[0], None if params is None else ctypes.byref(params),
                                                           _ptr(out), None if var is None else _ptr(var)))
         return (out, var) if want_var else out
+
+    # ---- the consumers with one frame count per view (include/ptmi.h, "CONSUMERS WITH PER-VIEW FRAME COUNTS") ----
+    def _stack_frame_nums(self, frame_nums):
+        return _frame_nums(frame_nums, self.views_device_ptr()[2])
+
+    def denoise_views_frames(self, frame_nums, first_view=0, n_views=None, params=None):
+        """ptmi_denoise_views_frames: denoise_views for a stack whose views sum different numbers of frames.  frame_nums: one count per view OF THE STACK, any
+        sequence — render_views_until_each's frames_done as it is; only the entries of the range are read.  Asynchronous."""
+        f = self._stack_frame_nums(frame_nums)
+        if n_views is None:
+            n_views = self.views_device_ptr()[2] - first_view
+        self._ck(self.lib.ptmi_denoise_views_frames(self.h, None if params is None else ctypes.byref(params), _optr(f), first_view, n_views))
+
+    def denoise_views_guided_frames(self, frame_nums, first_view=0, n_views=None, params=None):
+        """ptmi_denoise_views_guided_frames: denoise_views_guided with one frame count per view of the stack (see denoise_views_frames).  Asynchronous."""
+        f = self._stack_frame_nums(frame_nums)
+        if n_views is None:
+            n_views = self.views_device_ptr()[2] - first_view
+        self._ck(self.lib.ptmi_denoise_views_guided_frames(self.h, None if params is None else ctypes.byref(params), _optr(f), first_view, n_views))
+
+    def fuse_views_frames(self, views, frame_nums, first_view=0, n_views=None, params=None):
+        """ptmi_fuse_views_frames: fuse_views on the view stack (source 0) with one frame count per view of the stack; the entries of the range widened by the radius
+        are read.  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        n_stack = self.views_device_ptr()[2]
+        assert v.shape[0] == n_stack, "views: the matrices of all %d views of the stack" % n_stack
+        f = _frame_nums(frame_nums, n_stack)
+        if n_views is None:
+            n_views = n_stack - first_view
+        self._ck(self.lib.ptmi_fuse_views_frames(self.h, None if params is None else ctypes.byref(params), _ptr(v), _optr(f), first_view, n_views))
+
+    def accumulate_views_frames(self, views, frame_nums, first_view=0, n_views=None, resume=False, params=None):
+        """ptmi_accumulate_views_frames: accumulate_views with one frame count per view of the stack; the entries of the range are read, and with resume the one
+        before it.  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        n_stack = self.views_device_ptr()[2]
+        assert v.shape[0] == n_stack, "views: the matrices of all %d views of the stack" % n_stack
+        f = _frame_nums(frame_nums, n_stack)
+        if n_views is None:
+            n_views = n_stack - first_view
+        self._ck(self.lib.ptmi_accumulate_views_frames(self.h, None if params is None else ctypes.byref(params), _ptr(v), _optr(f), first_view, n_views, 1 if resume else 0))
+
+    def denoise_images_frames(self, colour_sums, layers, frame_nums, params=None):
+        """ptmi_denoise_images_frames: denoise_images with one frame count per image; synchronous."""
+        c, l, out = _denoise_arrays(colour_sums, layers)
+        f = _frame_nums(frame_nums, c.shape[0])
+        self._ck(self.lib.ptmi_denoise_images_frames(self.h, _ptr(c), _ptr(l), c.shape[2], c.shape[1], c.shape[0], _optr(f), None if params is None else ctypes.byref(params), _ptr(out)))
+        return out
+
+    def denoise_images_guided_frames(self, colour_sums, moments, layers, frame_nums, params=None, want_var=False):
+        """ptmi_denoise_images_guided_frames: denoise_images_guided with one frame count per image; synchronous."""
+        c, m, l, out, var = _guided_arrays(colour_sums, moments, layers, want_var)
+        f = _frame_nums(frame_nums, c.shape[0])
+        self._ck(self.lib.ptmi_denoise_images_guided_frames(self.h, _ptr(c), _ptr(m), _ptr(l), c.shape[2], c.shape[1], c.shape[0], _optr(f),
+                                                            None if params is None else ctypes.byref(params), _ptr(out), _optr(var)))
+        return (out, var) if want_var else out
+
+    def fuse_images_frames(self, colour, layers, views, frame_nums, fov_degrees=60.0, lambertian=None, params=None):
+        """ptmi_fuse_images_frames: fuse_images with one frame count per image; synchronous."""
+        c, l, v, t, out = _fuse_arrays(colour, layers, views, lambertian)
+        f = _frame_nums(frame_nums, c.shape[0])
+        self._ck(self.lib.ptmi_fuse_images_frames(self.h, _ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), float(fov_degrees),
+                                                  _optr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params), _ptr(out)))
+        return out
+
+    def accumulate_images_frames(self, colour_sums, moments, layers, views, frame_nums, fov_degrees=60.0, lambertian=None, params=None, history=None):
+        """ptmi_accumulate_images_frames: accumulate_images with one frame count per image; synchronous."""
+        c, m, l, v, t, hist, out = _accumulate_arrays(colour_sums, moments, layers, views, lambertian, history)
+        f = _frame_nums(frame_nums, c.shape[0])
+        self._ck(self.lib.ptmi_accumulate_images_frames(self.h, _ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), float(fov_degrees),
+                                                        _optr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params), _optr(hist), _ptr(out)))
+        return out
 
     def set_view_moments(self, on=True):
         """ptmi_set_view_moments: while on, render_views also folds the frames' squared colours into the context's moment stack (read_moments); off frees it."""
