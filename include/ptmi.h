@@ -14,6 +14,16 @@
  * such as the Node program needs; (b) one process per GPU (ptmi_create + ptmi_set_shard) with the reduce done by the host
  * program's own collective (bench.py: torch.distributed).
  * Every call returns PTMI_OK (0) or a negative ptmi_status; ptmi_last_error() gives the message.
+ *
+ * STATE CARRIED FROM CALL TO CALL.  A context's images are its accumulation buffer (ptmi_resize) and its stacks (ptmi_render_views and the calls after it).
+ *  - ptmi_upload and ptmi_set_params leave the accumulation buffer and every stack untouched: they change what LATER frames are rendered from.  Call order
+ *    defines the result: frames asked for before the call are the old scene's and parameters' even where they had not finished, frames asked for after it the
+ *    new ones' — those ptmi_render_frame had traced ahead included.
+ *  - A call that returns a status other than PTMI_OK leaves the accumulation buffer and every stack bit for bit as they were and sets ptmi_last_error (the
+ *    exceptions are PTMI_ERR_DEVICE, after which the device's state is whatever the failed HIP call left, and what a call's own comment says).
+ *  - The uploaded buffers are checked together by the next call that renders or traces, not by ptmi_upload: an index out of range is that call's
+ *    PTMI_ERR_BAD_SCENE, naming the element, before anything is enqueued; every such call fails the same way until an upload repairs the scene, and renders
+ *    from then on are what they would have been had the bad buffer never been sent.
  */
 #ifndef PTMI_H
 #define PTMI_H
@@ -166,7 +176,12 @@ int ptmi_clear_framebuffer(ptmi_ctx* ctx);
 /* Pixel-tile sharding for multi-GPU: this context renders only pixels p with
  * (p / tile_pixels) % world == rank; other pixels of its framebuffer stay untouched (zero).
  * On a multi-device context the n local devices subdivide this shard: device i renders the tiles of
- * rank * n + i out of world * n. */
+ * rank * n + i out of world * n.
+ * A single-device context may be re-sharded at any time: pixels outside the new shard keep what they hold.  On a multi-device context every device holds
+ * the pixels of its OWN tiles only and a read-back takes each pixel from its current owner, so a call that would CHANGE the assignment (another rank, world
+ * or tile_pixels) while the context holds accumulated pixels — a ptmi_render / ptmi_render_frame / ptmi_write_framebuffer since the last
+ * ptmi_clear_framebuffer or ptmi_resize, or a stack of any kind — returns PTMI_ERR_STATE ("ptmi_set_shard: a multi-device context holds pixels accumulated
+ * under the current tile assignment; clear the framebuffer and release the stacks first") and leaves everything as it was.  The same triple again is a no-op. */
 int ptmi_set_shard(ptmi_ctx* ctx, int rank, int world, int tile_pixels);
 
 /* replaces queue.writeBuffer(uniforms) + computePass(...) of one animation frame

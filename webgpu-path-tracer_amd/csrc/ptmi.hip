@@ -194,6 +194,7 @@ struct ptmi_ctx {
   bool shares_device = false;  // another shard of the same multi-device context lives on this GPU
   std::vector<ptmi_ctx*> peers;
   std::unique_ptr<PeerWorker> worker;  // a peer's host thread (created on first use)
+  bool fb_holds_pixels = false;  // (the root's field) a render or ptmi_write_framebuffer since the last clear / resize: ptmi_set_shard on a multi-device context asks
   int proc_rank = 0, proc_world = 1, proc_tile = 4032;  // (63 waves of pixels; not 4096: see dist.py — a rank's pixel count must not be a large power of two)
   bool use_rccl = false;
   bool use_gather = false;        // the default collective of a multi-device context: every device's OWN tiles are copied into place on the root (1/N of the bytes, no arithmetic)
@@ -1845,6 +1846,7 @@ int ptmi_resize(ptmi_ctx* c, int width, int height) {
   HIP_TRY(c, hipSetDevice(c->device));
   size_t bytes = (size_t)width * height * 16;
   c->ahead.valid = false;
+  c->fb_holds_pixels = false;
   HIP_TRY(c, c->d_fb_own.ensure(bytes));
   c->fb = c->d_fb_own.as<float4>();
   c->fb_bytes = bytes;
@@ -1864,6 +1866,7 @@ int ptmi_clear_framebuffer(ptmi_ctx* c) {
   if (!c || !c->fb) return fail(c, PTMI_ERR_STATE, "ptmi_clear_framebuffer: no framebuffer");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipMemsetAsync(c->fb, 0, c->fb_bytes, c->stream));
+  c->fb_holds_pixels = false;
   for (ptmi_ctx* q : c->peers) {
     int r = ptmi_clear_framebuffer(q);
     if (r) return fail(c, r, q->err);
@@ -1876,12 +1879,26 @@ int ptmi_set_shard(ptmi_ctx* c, int rank, int world, int tile_pixels) {
   if (world < 1 || rank < 0 || rank >= world || tile_pixels < 1) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_set_shard: need 0 <= rank < world, tile_pixels >= 1");
   if (c->multi) {
     if ((int64_t)world * (int64_t)(c->peers.size() + 1) > (1 << 30)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_set_shard: world too large");
+    if (rank == c->proc_rank && world == c->proc_world && tile_pixels == c->proc_tile) return PTMI_OK;  // the same triple again: nothing is re-dealt
+    // Every device holds the pixels of its OWN tiles only, and the default gather reads each pixel from its current owner: after a re-deal the new owner never
+    // rendered the earlier frames, which would vanish from the read-back without a word.
+    bool holds = c->fb_holds_pixels;
+    for (int k = 0; k < N_STACKS; k++) holds = holds || c->stacks[k].buf.p != nullptr;
+    if (holds && !c->peers.empty())
+      return fail(c, PTMI_ERR_STATE, "ptmi_set_shard: a multi-device context holds pixels accumulated under the current tile assignment; clear the framebuffer and release the stacks first");
     c->proc_rank = rank, c->proc_world = world, c->proc_tile = tile_pixels;
     return apply_shard(c);
   }
   c->rank = rank, c->world = world, c->tile = tile_pixels;
   c->ahead.valid = false;
   return PTMI_OK;
+}
+
+// ptmi_render_frame / ptmi_render hand their status through here: unless the call was refused before anything was enqueued (an argument, the call order, the scene,
+// the parameters), the accumulation buffer now holds pixels rendered under the current tile assignment (ptmi_set_shard on a multi-device context asks).
+static int rendered_into_framebuffer(ptmi_ctx* c, int r) {
+  if (r != PTMI_ERR_INVALID_ARG && r != PTMI_ERR_STATE && r != PTMI_ERR_BAD_SCENE && r != PTMI_ERR_UNSUPPORTED) c->fb_holds_pixels = true;
+  return r;
 }
 
 static int render_frame_one(ptmi_ctx* c, const float* u) {
@@ -1938,7 +1955,7 @@ static int render_frame_one(ptmi_ctx* c, const float* u) {
 
 int ptmi_render_frame(ptmi_ctx* c, const float* u) {
   if (!c || !u) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_frame: null argument");
-  return on_all_devices(c, [u](ptmi_ctx* q) { return render_frame_one(q, u); }, true);
+  return rendered_into_framebuffer(c, on_all_devices(c, [u](ptmi_ctx* q) { return render_frame_one(q, u); }, true));
 }
 
 static int render_one(ptmi_ctx* c, const float* view16, uint32_t first_frame, uint32_t n_frames) {
@@ -1976,7 +1993,7 @@ static int render_one(ptmi_ctx* c, const float* view16, uint32_t first_frame, ui
 
 int ptmi_render(ptmi_ctx* c, const float* view16, uint32_t first_frame, uint32_t n_frames) {
   if (!c || !view16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render: null argument");
-  return on_all_devices(c, [=](ptmi_ctx* q) { return render_one(q, view16, first_frame, n_frames); }, true);
+  return rendered_into_framebuffer(c, on_all_devices(c, [=](ptmi_ctx* q) { return render_one(q, view16, first_frame, n_frames); }, true));
 }
 
 // A call's view table (ViewTab: kViewRow float4 per view) for ptmi_render_views and ptmi_render_aov, in two halves so that everything that can fail for want of
@@ -3126,6 +3143,7 @@ int ptmi_write_framebuffer(ptmi_ctx* c, const float* src, size_t bytes) {
   if (!c || !src) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_write_framebuffer: null argument");
   if (!c->fb) return fail(c, PTMI_ERR_STATE, "ptmi_write_framebuffer: no framebuffer");
   if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_write_framebuffer: bytes != W*H*16");
+  c->fb_holds_pixels = true;
   if (c->multi && !c->peers.empty()) {
     // every device gets its own tiles of the image and zeros elsewhere, as if it had rendered them itself
     const size_t npix = (size_t)c->W * c->H;
