@@ -706,7 +706,7 @@ int ptmi_selftest(ptmi_ctx* ctx, int which, uint64_t* mismatches, uint32_t* firs
  * the BVH rows (byte-identical to ptmi_build_bvh's and the reference's) stay in device memory as binding 9 and the traversal digests are
  * made from them there.  871 k triangles: ~15 ms (the reference's JavaScript: seconds; benchmarks.txt:19).  A later ptmi_upload(PTMI_BUF_BVH)
  * replaces the tree; after an upload of triangles, meshes or transforms the tree is stale and every render fails with PTMI_ERR_BAD_SCENE
- * until it is built again (or a BVH is uploaded).  At most 2^23 triangles: node ids are f32 in the rows (exact below 2^24), as in the
+ * until it is built again, refitted (ptmi_refit_scene_bvh, below) or replaced by an uploaded BVH.  At most 2^23 triangles: node ids are f32 in the rows (exact below 2^24), as in the
  * reference's own format — more returns PTMI_ERR_UNSUPPORTED. */
 int ptmi_build_scene_bvh(ptmi_ctx* ctx);
 /* API v5.  The same with the reference's OTHER builder, BVH.generate_bvh_heirarchy_SAH (lib/BVH/bvhNode.js:108-283: 8 bins per axis, leaf when the best plane
@@ -743,6 +743,39 @@ int ptmi_read_scene_buffer(ptmi_ctx* ctx, int which, void* dst, size_t bytes);
 /* The domain check on its own, without a build: PTMI_OK, or PTMI_ERR_BAD_SCENE with the sentence the builders with a context report in
  * msg (msg may be NULL).  sah != 0 adds rule 4. */
 int ptmi_check_bvh_boxes(size_t n_prims, const double* bmin, const double* bmax, int sah, char* msg, size_t msg_len);
+
+/* ---- Refitting ----------------------------------------------------------------------------------
+ * When primitives move a little, the tree's topology can stay and only its boxes need to follow.  A refit of rows R (12 f32 each, the
+ * reference's layout) over primitive boxes (bmin, bmax) keeps fields 3 and 7-11 of every row as they are — right child, primitive type,
+ * first primitive, count, skip link, split axis — and sets fields 0-2 (box min) and 4-6 (box max):
+ *   leaf row     the f32 conversion of the union of the boxes of primitives row[8] .. row[8] + row[9] - 1, the union taken in double
+ *                with Math.min / Math.max (-0 below +0, lib/BVH/AABB.js:8-28) as the builders take it;
+ *   inner row i  the union of rows i + 1 and row[3] (its children), taken the same way.
+ * That is the box the builders give a node that holds those primitives: min / max are exact and the f32 conversion is monotone, so a
+ * refit of a tree over the boxes it was built from returns the build's rows byte for byte.  The boxes must lie in the builders' domain,
+ * rules 1-3 (rule 4 concerns the choice of planes, and a refit chooses none).  A refitted tree is a correct BVH of the moved
+ * primitives; how good a one depends on how far they moved — node visits per ray grow with the motion, and a caller rebuilds when that
+ * costs more than the build (profiles/refit_probe.txt has figures). */
+
+/* The refit on the host, no GPU: the CPU reference of ptmi_refit_scene_bvh, and the call for callers who upload trees they built
+ * themselves.  bmin / bmax: n_prims x 3 doubles in the tree's leaf order, i.e. indexed by row[8] (the order ptmi_build_bvh[_sah] return
+ * through order_out).  rows_inout: n_nodes x 12 f32.  Before the first write it checks the domain and the row structure — pre-order, left
+ * child = i + 1, i < right child < n_nodes, the rows exactly one tree, every leaf's range non-empty and inside n_prims — and returns
+ * PTMI_ERR_BAD_SCENE with the rows untouched otherwise.  PTMI_ERR_INVALID_ARG: a null pointer. */
+int ptmi_refit_bvh(size_t n_prims, const double* bmin, const double* bmax, float* rows_inout, size_t n_nodes);
+
+/* The refit of the scene's device-resident tree (ptmi_build_scene_bvh[_sah], or an earlier refit) over the triangles, meshes and transforms
+ * that are uploaded NOW: the way out of the stale state that costs no build.  Triangles uploaded since the build (in the caller's original
+ * order, as always) are put into the tree's leaf order through the order the build kept; their world-space boxes are made as the build
+ * makes them; a copy of the rows is refitted level by level from the deepest to the root, one kernel launch per level (k_refit_level,
+ * csrc/ptmi_bvh_device.hip: the launch boundary is the only ordering between child and parent); then rows and triangles are swapped in, the
+ * tree is no longer stale, and the next render remakes the traversal digests as after any upload.  ptmi_scene_bvh_info is unchanged.  A
+ * tree that is not stale is refitted all the same, to the same bytes.  On every device of a multi-device context.  Synchronous.
+ * PTMI_ERR_STATE: the context holds no device-resident tree, or the uploaded triangle count differs from the one it was built over
+ * (ptmi_last_error says which); nothing changes.  PTMI_ERR_BAD_SCENE: a triangle whose mesh / transform index is out of range or whose
+ * world-space box is outside rules 1-2 of the builders' domain, named by its position in the caller's upload order; the context is left as
+ * before the call (stale, nothing swapped) and a repaired upload can be refitted. */
+int ptmi_refit_scene_bvh(ptmi_ctx* ctx);
 
 /* ---- host-side natives (no GPU needed) -------------------------------------------------------- */
 

@@ -1,13 +1,15 @@
 #!/bin/bash
 # usage: tools/kernel_resources.sh out.s [extra flags]  -- compile ptmi.hip device-only to asm and list per-kernel resources
+#        PTMI_SRC=ptmi_bvh_device.hip tools/kernel_resources.sh out.s   -- the same for another translation unit of csrc/ (PTMI_SRC may also be a path)
 out=$1; shift
-src=$(cd "$(dirname "$0")/.." && pwd)/webgpu-path-tracer_amd/csrc/ptmi.hip
+src=${PTMI_SRC:-ptmi.hip}
+case "$src" in */*) ;; *) src=$(cd "$(dirname "$0")/.." && pwd)/webgpu-path-tracer_amd/csrc/$src ;; esac
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize -Wno-unused-command-line-argument "$@" --cuda-device-only -S -o $out "$src" 2>&1 | grep -v warning | head
 python3 - $out <<'PY'
 import re,sys,subprocess
 txt=open(sys.argv[1]).read()
 for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, re.S):
-    name=subprocess.run(["c++filt",m.group(1)],stdout=subprocess.PIPE,text=True).stdout.strip().split("(")[0].replace("void ptmi::","")
+    name=subprocess.run(["c++filt",m.group(1)],stdout=subprocess.PIPE,text=True).stdout.strip().replace("(anonymous namespace)::","").split("(")[0].replace("void ptmi::","").replace("void ","")
     body=m.group(2)
     g=lambda k: re.search(r"\.amdhsa_"+k+r"\s+(\d+)",body).group(1)
     # count instructions

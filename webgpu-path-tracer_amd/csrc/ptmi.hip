@@ -34,7 +34,11 @@ using namespace ptmi;
 
 // csrc/ptmi_bvh_device.hip
 int ptmi_bvhdev_build_scene(void* stream, const float* d_tris, uint32_t n, const int32_t* h_meshes, int n_meshes, const float* h_xforms, int n_xforms, float* d_rows,
-                            float* d_tris_out, int* depth_out, uint32_t* bad_tri, int sah, uint32_t* n_nodes_out, int* refused);
+                            float* d_tris_out, int* depth_out, uint32_t* bad_tri, int sah, uint32_t* n_nodes_out, int* refused, const uint32_t* d_prev_order,
+                            uint32_t* d_order_out, uint32_t* d_level_rows, std::vector<uint32_t>* level_off);
+int ptmi_bvhdev_refit_scene(void* stream, const float* d_tris, float* d_tris_out, const uint32_t* d_order, uint32_t n, const int32_t* h_meshes, int n_meshes,
+                            const float* h_xforms, int n_xforms, const float* d_rows, uint32_t nn, const uint32_t* d_level_rows, const std::vector<uint32_t>& level_off,
+                            float* d_rows_out, uint32_t* bad_tri, uint32_t* bad_upload);
 int ptmi_bvhdev_make_pairs(void* stream, const float* d_rows, uint32_t nn, float* d_pairs, int* d_leaf_table, uint32_t* n_multi);
 
 namespace {
@@ -140,6 +144,11 @@ struct ptmi_ctx {
   bool bvh_dev_sah = false;  // built by ptmi_build_scene_bvh_sah
   bool bvh_dev_stale = false;  // triangles / meshes / transforms were uploaded after the build: its boxes and leaf order describe another scene
   int bvh_dev_depth = 0;
+  // ... and what ptmi_refit_scene_bvh needs of the build (drop_refit_state releases it where the tree goes)
+  DBuf d_bvh_order;       // u32 per triangle: leaf position -> position in the caller's upload order
+  DBuf d_bvh_level_rows;  // u32 per row: the row ids grouped by level, root level first
+  std::vector<uint32_t> bvh_level_off;  // where each level starts in d_bvh_level_rows, and the total
+  bool tris_in_upload_order = true;     // d_tris as ptmi_upload(PTMI_BUF_TRIANGLES) left it; false: in the leaf order of d_bvh_order (a build or a refit put it there)
   DBuf d_spheres, d_sphere_info, d_quads, d_quad_mat, d_tris, d_pretri, d_trinorm, d_meshes, d_xforms, d_mats, d_pairs, d_leaf_table;
   DevScene S{};
   int bvh_depth = 0;             // max number of inner nodes on a root-to-leaf path
@@ -1667,6 +1676,14 @@ int ptmi_get_params(const ptmi_ctx* c, ptmi_params* p) {
   return PTMI_OK;
 }
 
+// The device-resident tree is gone (or there never was one): what ptmi_refit_scene_bvh kept of its build goes too (with the stream drained, or nothing enqueued that
+// reads it).  The order stays while d_tris still sits in it: a scene build over those triangles has to compose it with its own (build_scene_bvh_one).
+static void drop_refit_state(ptmi_ctx* c) {
+  c->d_bvh_level_rows.release();
+  c->bvh_level_off.clear();
+  if (c->tris_in_upload_order) c->d_bvh_order.release();
+}
+
 // One device's share of ptmi_upload.  The triangles (the largest buffer: 84 MB at 871 k triangles) go straight from the caller's memory to
 // the device — no host copy — in two steps, so that a failure leaves every device of a multi-device context with the scene it had:
 // upload_stage allocates what the new array needs WITHOUT touching the old one; upload_commit copies and swaps.
@@ -1697,6 +1714,8 @@ static int upload_commit(ptmi_ctx* c, int which, const void* data, size_t bytes,
       }
       c->n_tris_uploaded = bytes / 96;
       c->bvh_dev_stale = true;  // (meaningful only while bvh_on_device: mesh-order triangles under a tree built over leaf-order ones)
+      c->tris_in_upload_order = true;
+      if (!c->bvh_on_device) drop_refit_state(c);  // (an order kept only because the old triangles sat in it)
       break;
     }
     case PTMI_BUF_MESHES:
@@ -1711,6 +1730,7 @@ static int upload_commit(ptmi_ctx* c, int which, const void* data, size_t bytes,
     case PTMI_BUF_BVH:
       c->h_bvh.assign(f, f + bytes / 4);
       c->bvh_on_device = false;  // an uploaded BVH replaces a device-resident one
+      drop_refit_state(c);       // (the build and the refit drain the stream before they return: nothing in flight reads it)
       break;
   }
   c->scene_dirty = true;
@@ -1755,6 +1775,8 @@ static int build_scene_bvh_one(ptmi_ctx* c, bool sah) {
   const size_t n = c->n_tris_uploaded;
   if (n == 0) {
     c->bvh_on_device = false;
+    c->tris_in_upload_order = true;
+    drop_refit_state(c);
     c->h_bvh.clear();
     c->scene_dirty = true;
     return PTMI_OK;
@@ -1763,15 +1785,20 @@ static int build_scene_bvh_one(ptmi_ctx* c, bool sah) {
   // made: exact only below 2^24 = 2n - 1 nodes
   if (n > ((size_t)1 << 23)) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_build_scene_bvh: more than 2^23 triangles (node ids are f32 in the BVH rows, exact below 2^24)");
   const int n_mesh = (int)(c->h_meshes.size() / 4), n_xf = (int)(c->h_xforms.size() / 32);
-  DBuf rows, tris2;
+  DBuf rows, tris2, order, level_rows;
+  std::vector<uint32_t> level_off;
   hipError_t e = rows.ensure((2 * n - 1) * 48);
   if (e == hipSuccess) e = tris2.ensure(n * 96);
+  if (e == hipSuccess) e = order.ensure(n * 4);
+  if (e == hipSuccess) e = level_rows.ensure((2 * n - 1) * 4);
   if (e != hipSuccess) return fail(c, PTMI_ERR_NO_MEMORY, std::string("ptmi_build_scene_bvh: ") + hipGetErrorString(e));
+  // triangles that still sit in an earlier tree's leaf order: the new order goes through the old one, so that it keeps naming positions of the caller's upload
+  const uint32_t* prev_order = c->tris_in_upload_order ? nullptr : c->d_bvh_order.as<uint32_t>();
   int depth = 0;
   uint32_t bad_pair[2] = {0xffffffffu, 0xffffffffu}, n_nodes = 0;  // [0] an index out of range, [1] a box outside the builders' domain
   int refused = 0;
   const int r = ptmi_bvhdev_build_scene((void*)c->stream, c->d_tris.as<float>(), (uint32_t)n, c->h_meshes.data(), n_mesh, c->h_xforms.data(), n_xf, rows.as<float>(), tris2.as<float>(),
-                                         &depth, bad_pair, sah ? 1 : 0, &n_nodes, &refused);
+                                         &depth, bad_pair, sah ? 1 : 0, &n_nodes, &refused, prev_order, order.as<uint32_t>(), level_rows.as<uint32_t>(), &level_off);
   const uint32_t bad = bad_pair[0];
   if (r || bad != 0xffffffffu || bad_pair[1] != 0xffffffffu || refused) {
     if (r == (int)hipErrorNotSupported) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_build_scene_bvh_sah: the SAH tree of these triangles is deeper than 4096 levels (no STACK_SIZE <= 64 can traverse it)");
@@ -1790,6 +1817,10 @@ static int build_scene_bvh_one(ptmi_ctx* c, bool sah) {
   }
   c->d_tris = std::move(tris2);  // the triangles now sit in leaf order (the reference reorders them on the host, lib/scene.js:257)
   c->d_bvh_rows = std::move(rows);
+  c->d_bvh_order = std::move(order);
+  c->d_bvh_level_rows = std::move(level_rows);
+  c->bvh_level_off = std::move(level_off);
+  c->tris_in_upload_order = false;
   c->bvh_on_device = true;
   c->bvh_dev_stale = false;
   c->bvh_dev_prims = n;
@@ -1810,6 +1841,51 @@ int ptmi_build_scene_bvh(ptmi_ctx* c) {
 int ptmi_build_scene_bvh_sah(ptmi_ctx* c) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   return on_all_devices(c, [](ptmi_ctx* q) { return build_scene_bvh_one(q, true); }, true);
+}
+
+// The device-resident tree's boxes recomputed over what is uploaded now, its topology kept (include/ptmi.h, "Refitting").
+static int refit_scene_bvh_one(ptmi_ctx* c) {
+  if (!c->bvh_on_device || c->bvh_level_off.size() < 2)
+    return fail(c, PTMI_ERR_STATE, "ptmi_refit_scene_bvh: the context holds no device-resident BVH (ptmi_build_scene_bvh[_sah] makes one; an uploaded BVH is refitted on the host: ptmi_refit_bvh)");
+  const size_t n = c->n_tris_uploaded, nn = c->bvh_dev_nodes;
+  if (n != c->bvh_dev_prims) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "ptmi_refit_scene_bvh: the device-resident BVH was built over %zu triangles, %zu are uploaded now (a refit keeps the topology: build again)", c->bvh_dev_prims, n);
+    return fail(c, PTMI_ERR_STATE, msg);
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const int n_mesh = (int)(c->h_meshes.size() / 4), n_xf = (int)(c->h_xforms.size() / 32);
+  DBuf rows, tris2;
+  hipError_t e = rows.ensure(nn * 48);
+  if (e == hipSuccess && c->tris_in_upload_order) e = tris2.ensure(n * 96);
+  if (e != hipSuccess) return fail(c, PTMI_ERR_NO_MEMORY, std::string("ptmi_refit_scene_bvh: ") + hipGetErrorString(e));
+  uint32_t bad_pair[2] = {0xffffffffu, 0xffffffffu}, bad_upload = 0;  // [0] an index out of range, [1] a box outside the builders' domain
+  const int r = ptmi_bvhdev_refit_scene((void*)c->stream, c->d_tris.as<float>(), c->tris_in_upload_order ? tris2.as<float>() : nullptr, c->d_bvh_order.as<uint32_t>(), (uint32_t)n,
+                                         c->h_meshes.data(), n_mesh, c->h_xforms.data(), n_xf, c->d_bvh_rows.as<float>(), (uint32_t)nn, c->d_bvh_level_rows.as<uint32_t>(),
+                                         c->bvh_level_off, rows.as<float>(), bad_pair, &bad_upload);
+  if (r) return fail(c, r == (int)hipErrorOutOfMemory ? PTMI_ERR_NO_MEMORY : PTMI_ERR_DEVICE, std::string("ptmi_refit_scene_bvh: ") + hipGetErrorString((hipError_t)r));
+  if (bad_pair[0] != 0xffffffffu || bad_pair[1] != 0xffffffffu) {
+    // (the context's triangles, rows and flags are untouched — still stale: `rows` and `tris2` are dropped here)
+    char msg[200];
+    if (bad_pair[0] != 0xffffffffu)
+      snprintf(msg, sizeof msg, "ptmi_refit_scene_bvh: triangle %u: mesh_id / the mesh's global_id out of range (meshes %d, transforms %d)", bad_upload, n_mesh, n_xf);
+    else
+      snprintf(msg, sizeof msg, "ptmi_refit_scene_bvh: triangle %u: its world-space box is outside the builders' domain (rules 1-2: every coordinate finite and |x| < 1e30)", bad_upload);
+    return fail(c, PTMI_ERR_BAD_SCENE, msg);
+  }
+  if (c->tris_in_upload_order) c->d_tris = std::move(tris2);  // leaf order again, as after the build
+  c->tris_in_upload_order = false;
+  c->d_bvh_rows = std::move(rows);
+  c->bvh_dev_stale = false;
+  c->scene_dirty = true;
+  c->ahead.valid = false;
+  return PTMI_OK;
+}
+
+int ptmi_refit_scene_bvh(ptmi_ctx* c) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  return on_all_devices(c, [](ptmi_ctx* q) { return refit_scene_bvh_one(q); }, true);
 }
 
 int ptmi_scene_bvh_info(ptmi_ctx* c, uint64_t* n_nodes, int32_t* depth, int32_t* on_device) {

@@ -167,6 +167,13 @@ __global__ void k_iota(uint32_t* __restrict__ order, int32_t* __restrict__ seg_o
   seg_of[i] = 0;
 }
 
+// the rows of one level, for the refit (k_refit_level): ids[j] = pre-order id of the level's j-th node
+__global__ void k_level_ids(const LevelNode* __restrict__ nodes, uint32_t m, uint32_t* __restrict__ ids) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  ids[j] = nodes[j].id;
+}
+
 struct Dev {  // frees everything on scope exit
   std::vector<void*> ptrs;
   template <class T>
@@ -190,8 +197,9 @@ struct Dev {  // frees everything on scope exit
 
 // The level loop on boxes that are already on the device; leaves the rows (12 floats per node, 2n-1 nodes) and the primitive order on
 // the device too (the caller's buffers).  `d` owns the scratch.
+// With level_rows_out (room for 2n-1) and level_off: the row ids grouped by level, root level first, and where each level starts (one more entry: the total).
 hipError_t build_levels(hipStream_t stream, Dev& d, uint32_t n, const double* bmin, const double* bmax, int prim_type, float* rows, uint32_t* order_out,
-                        int* depth_out = nullptr) {
+                        int* depth_out = nullptr, uint32_t* level_rows_out = nullptr, std::vector<uint32_t>* level_off = nullptr) {
   double* keys[2];
   uint64_t* packed[2];
   uint32_t *order[2], *major[2], *inner, *rank, *n_runs;
@@ -240,8 +248,15 @@ hipError_t build_levels(hipStream_t stream, Dev& d, uint32_t n, const double* bm
   uint32_t m = 1;
   int cur = 0, ocur = 0;  // ping-pong indices of the level arrays and of the order arrays
   int levels = 0;
+  uint32_t listed = 0;  // rows written to level_rows_out so far
+  if (level_off) level_off->assign(1, 0u);
   while (m > 0) {
     levels++;
+    if (level_off) {
+      hipLaunchKernelGGL(k_level_ids, dim3((m + B - 1) / B), dim3(B), 0, stream, level[cur], m, level_rows_out + listed);
+      listed += m;
+      level_off->push_back(listed);
+    }
     // node boxes of ALL nodes of the level (leaves included): one run of equal seg_of per node
     {
       auto in = rocprim::make_transform_iterator(order[ocur], box_of);
@@ -591,8 +606,9 @@ struct SahRefusal {
 };
 // The SAH level loop on boxes that are on the device: rows (12 floats per node; room for 2n-1) and the primitive order into the caller's
 // buffers, the number of rows into *n_nodes_out.  `d` owns the scratch.
+// level_rows_out / level_off: as build_levels'.
 hipError_t build_levels_sah(hipStream_t stream, Dev& d, uint32_t n, const double* bmin, const double* bmax, int prim_type, float* rows, uint32_t* order_out, uint32_t* n_nodes_out,
-                            int* depth_out = nullptr, SahRefusal* refusal = nullptr) {
+                            int* depth_out = nullptr, SahRefusal* refusal = nullptr, uint32_t* level_rows_out = nullptr, std::vector<uint32_t>* level_off = nullptr) {
   double *keys[2], *split_pos;
   uint64_t* packed[2];
   uint32_t *order[2], *major[2], *inner, *rank, *n_runs, *split_first, *size, *flat;
@@ -726,6 +742,12 @@ hipError_t build_levels_sah(hipStream_t stream, Dev& d, uint32_t n, const double
   hipLaunchKernelGGL(k_sah_rows, dim3((total + B - 1) / B), dim3(B), 0, stream, tree, total, flat, next, prim_type, rows);
   TRY(hipGetLastError());
   TRY(hipMemcpyAsync(order_out, order[ocur], (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
+  if (level_off) {  // temporary ids are level order already: flat[] is the list, `levels` its offsets
+    TRY(hipMemcpyAsync(level_rows_out, flat, (size_t)total * 4, hipMemcpyDeviceToDevice, stream));
+    level_off->clear();
+    for (const auto& lv : levels) level_off->push_back(lv.first);
+    level_off->push_back(total);
+  }
   TRY(hipStreamSynchronize(stream));  // (`zero` / `none` are stack variables; the bins die with `bins`)
   *n_nodes_out = total;
   if (depth_out) *depth_out = (int)levels.size() - 1;  // inner nodes on the longest root-to-leaf path
@@ -809,6 +831,41 @@ __global__ void k_permute_triangles(const float4* __restrict__ src, const uint32
   if (g >= 6u * n) return;
   const uint32_t k = g / 6u, part = g - 6u * k;
   dst[g] = src[6 * (size_t)order[k] + part];
+}
+
+// a scene build over triangles that still sit in an earlier tree's leaf order: leaf position -> the caller's upload position through both orders
+__global__ void k_compose_order(const uint32_t* __restrict__ order, const uint32_t* __restrict__ prev, uint32_t n, uint32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = prev[order[i]];
+}
+
+// Refitting (include/ptmi.h): one level of the tree, one thread per row.  A leaf takes the f32 of the union of its triangles' boxes (what k_level_rows /
+// k_sah_rows store for a node over them), an inner row the union of its two child rows, which sit on deeper levels: an EARLIER LAUNCH wrote them.  That
+// kernel boundary is the only ordering between child and parent — rows are 48 bytes in 128-byte lines, sibling rows written by other CUs share lines a CU
+// may already hold, and no in-kernel hand-off is used.  Fields 3 and 7-11 are not touched.
+__global__ void k_refit_level(float* __restrict__ rows, const uint32_t* __restrict__ ids, uint32_t m, uint32_t nn, const double* __restrict__ bmin, const double* __restrict__ bmax,
+                              uint32_t n) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const uint32_t i = ids[j];
+  if (i >= nn) return;
+  float* row = rows + 12 * (size_t)i;
+  double lo[3], hi[3];
+  if (row[7] == -1.0f) {  // inner (bvhBuilder.js:45,49)
+    const uint32_t r = (uint32_t)row[3];
+    if (i + 1u >= nn || r >= nn) return;
+    const float *a = row + 12, *b = rows + 12 * (size_t)r;
+    for (int k = 0; k < 3; k++) lo[k] = js_min((double)a[k], (double)b[k]), hi[k] = js_max((double)a[4 + k], (double)b[4 + k]);
+  } else {
+    const uint32_t first = (uint32_t)row[8], count = (uint32_t)row[9];
+    if (first >= n || count == 0u || count > n - first) return;
+    for (int k = 0; k < 3; k++) lo[k] = bmin[3 * (size_t)first + k], hi[k] = bmax[3 * (size_t)first + k];
+    for (uint32_t p = first + 1u; p < first + count; p++)
+      for (int k = 0; k < 3; k++) lo[k] = js_min(bmin[3 * (size_t)p + k], lo[k]), hi[k] = js_max(bmax[3 * (size_t)p + k], hi[k]);
+  }
+  row[0] = (float)lo[0], row[1] = (float)lo[1], row[2] = (float)lo[2];
+  row[4] = (float)hi[0], row[5] = (float)hi[1], row[6] = (float)hi[2];
 }
 
 // pair64 (csrc/ptmi_device.h) from rows that stay on the device: is_inner -> exclusive scan = the pair index, then one record per inner node
@@ -907,8 +964,11 @@ extern "C" int ptmi_build_bvh_sah_device(ptmi_ctx* ctx, size_t n_prims, const do
 // triangle whose mesh / transform index is out of range, bad_tri[1] = first triangle whose padded box breaks rules 1-2 of the builders' domain (0xffffffff = none); *refused = 4 or
 // 5 when the SAH level loop stopped on rule 4 or on its node-count guard (SahRefusal).  In each of these cases nothing was written to d_rows / d_tris_out that matters and the
 // result is hipSuccess: the caller reports it.  Returns a hipError_t.
+// For the refit: d_order_out (n words) receives the order, leaf position -> the caller's upload position — through d_prev_order (or null) when d_tris sits in an earlier
+// tree's leaf order —, d_level_rows (2n-1 words) the row ids grouped by level and *level_off where each level starts (build_levels).
 int ptmi_bvhdev_build_scene(void* stream_, const float* d_tris, uint32_t n, const int32_t* h_meshes, int n_meshes, const float* h_xforms, int n_xforms, float* d_rows,
-                            float* d_tris_out, int* depth_out, uint32_t* bad_tri, int sah, uint32_t* n_nodes_out, int* refused) {
+                            float* d_tris_out, int* depth_out, uint32_t* bad_tri, int sah, uint32_t* n_nodes_out, int* refused, const uint32_t* d_prev_order,
+                            uint32_t* d_order_out, uint32_t* d_level_rows, std::vector<uint32_t>* level_off) {
   hipStream_t stream = (hipStream_t)stream_;
   try {
     Dev d;
@@ -935,17 +995,69 @@ int ptmi_bvhdev_build_scene(void* stream_, const float* d_tris, uint32_t n, cons
     *n_nodes_out = 2 * n - 1;
     if (sah) {  // BVH.generate_bvh_heirarchy_SAH (bvhNode.js:108-283), the opt-in
       SahRefusal refusal;
-      const hipError_t e = build_levels_sah(stream, d, n, bmin, bmax, 2, d_rows, order, n_nodes_out, depth_out, &refusal);
+      const hipError_t e = build_levels_sah(stream, d, n, bmin, bmax, 2, d_rows, order, n_nodes_out, depth_out, &refusal, d_level_rows, level_off);
       if (refusal.rule) {
         *refused = refusal.rule;
         return (int)hipSuccess;  // the caller reports it
       }
       TRY(e);
     } else {
-      TRY(build_levels(stream, d, n, bmin, bmax, 2, d_rows, order, depth_out));
+      TRY(build_levels(stream, d, n, bmin, bmax, 2, d_rows, order, depth_out, d_level_rows, level_off));
     }
+    if (d_prev_order) hipLaunchKernelGGL(k_compose_order, dim3((n + B - 1) / B), dim3(B), 0, stream, order, d_prev_order, n, d_order_out);
+    else TRY(hipMemcpyAsync(d_order_out, order, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
     hipLaunchKernelGGL(k_permute_triangles, dim3((6 * n + B - 1) / B), dim3(B), 0, stream, reinterpret_cast<const float4*>(d_tris), order, n,
                        reinterpret_cast<float4*>(d_tris_out));
+    TRY(hipGetLastError());
+    TRY(hipStreamSynchronize(stream));  // the scratch dies with `d`
+    return (int)hipSuccess;
+  } catch (...) {
+    return (int)hipErrorOutOfMemory;
+  }
+}
+
+// ptmi_refit_scene_bvh's device half, all on the stream.  d_tris: the n uploaded triangles, in upload order when d_tris_out is given — they go through d_order
+// into d_tris_out (leaf order) first — and in leaf order already when it is null.  Boxes as the scene build makes them (k_scene_boxes), bad_tri as there but counted in
+// leaf order; when either is set nothing else happened and *bad_upload is the offender's position in the caller's upload order.  Otherwise d_rows_out becomes a copy of
+// d_rows (nn rows) refitted level by level from the deepest to the root, one launch per level (d_level_rows / level_off: ptmi_bvhdev_build_scene).  Returns a hipError_t.
+int ptmi_bvhdev_refit_scene(void* stream_, const float* d_tris, float* d_tris_out, const uint32_t* d_order, uint32_t n, const int32_t* h_meshes, int n_meshes,
+                            const float* h_xforms, int n_xforms, const float* d_rows, uint32_t nn, const uint32_t* d_level_rows, const std::vector<uint32_t>& level_off,
+                            float* d_rows_out, uint32_t* bad_tri, uint32_t* bad_upload) {
+  hipStream_t stream = (hipStream_t)stream_;
+  try {
+    Dev d;
+    double *bmin, *bmax;
+    int32_t* meshes;
+    float* xforms;
+    uint32_t* bad;
+    TRY(d.alloc(&bmin, 3 * (size_t)n));
+    TRY(d.alloc(&bmax, 3 * (size_t)n));
+    TRY(d.alloc(&meshes, 4 * (size_t)n_meshes));
+    TRY(d.alloc(&xforms, 32 * (size_t)n_xforms));
+    TRY(d.alloc(&bad, 2));
+    const uint32_t none = 0xffffffffu, none2[2] = {none, none};
+    TRY(hipMemcpyAsync(bad, none2, 8, hipMemcpyHostToDevice, stream));
+    if (n_meshes) TRY(hipMemcpyAsync(meshes, h_meshes, 16 * (size_t)n_meshes, hipMemcpyHostToDevice, stream));
+    if (n_xforms) TRY(hipMemcpyAsync(xforms, h_xforms, 128 * (size_t)n_xforms, hipMemcpyHostToDevice, stream));
+    const unsigned B = 256;
+    const float* leaf_tris = d_tris;
+    if (d_tris_out) {
+      hipLaunchKernelGGL(k_permute_triangles, dim3((6 * n + B - 1) / B), dim3(B), 0, stream, reinterpret_cast<const float4*>(d_tris), d_order, n, reinterpret_cast<float4*>(d_tris_out));
+      leaf_tris = d_tris_out;
+    }
+    hipLaunchKernelGGL(k_scene_boxes, dim3((n + B - 1) / B), dim3(B), 0, stream, leaf_tris, n, meshes, n_meshes, xforms, n_xforms, bmin, bmax, bad);
+    TRY(hipMemcpyAsync(bad_tri, bad, 8, hipMemcpyDeviceToHost, stream));
+    TRY(hipStreamSynchronize(stream));
+    if (bad_tri[0] != none || bad_tri[1] != none) {
+      const uint32_t at = bad_tri[0] != none ? bad_tri[0] : bad_tri[1];
+      TRY(hipMemcpy(bad_upload, d_order + at, 4, hipMemcpyDeviceToHost));
+      return (int)hipSuccess;  // the caller reports it
+    }
+    TRY(hipMemcpyAsync(d_rows_out, d_rows, (size_t)nn * 48, hipMemcpyDeviceToDevice, stream));
+    for (size_t l = level_off.size() - 1; l-- > 0;) {
+      const uint32_t first = level_off[l], m = level_off[l + 1] - first;
+      if (m) hipLaunchKernelGGL(k_refit_level, dim3((m + B - 1) / B), dim3(B), 0, stream, d_rows_out, d_level_rows + first, m, nn, bmin, bmax, n);
+    }
     TRY(hipGetLastError());
     TRY(hipStreamSynchronize(stream));  // the scratch dies with `d`
     return (int)hipSuccess;

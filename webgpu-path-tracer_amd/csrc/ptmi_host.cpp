@@ -408,6 +408,59 @@ extern "C" int ptmi_check_bvh_boxes(size_t n_prims, const double* bmin, const do
 }
 
 
+// ---- refitting (include/ptmi.h, "Refitting") --------------------------------------------------------------------------
+// The topology stays, the boxes are recomputed bottom-up.  A leaf takes the f32 of the union of its primitives' boxes — what gen() /
+// the SAH builder store for a node over those primitives —, an inner row the union of its two child rows: min / max are exact and the
+// f32 conversion is monotone (with -0 below +0 on both sides of it), so that is the f32 of the union of everything below.
+extern "C" int ptmi_refit_bvh(size_t n_prims, const double* bmin, const double* bmax, float* rows, size_t n_nodes) {
+  if (n_prims == 0 && n_nodes == 0) return PTMI_OK;
+  if (!bmin || !bmax || !rows) return PTMI_ERR_INVALID_ARG;
+  if (n_prims == 0 || n_nodes == 0 || n_nodes >= (size_t)1 << 24) return PTMI_ERR_BAD_SCENE;  // (row ids are f32 in the rows: exact below 2^24)
+  if (ptmi_bvh_domain::check(n_prims, bmin, bmax, false, nullptr, 0, "")) return PTMI_ERR_BAD_SCENE;
+  // The row structure, before the first write: pre-order with the left child at i + 1 and i < right child < n_nodes; every leaf's range
+  // non-empty and inside the primitives; the rows are exactly one tree (the subtree of row i ends where its right subtree ends, and
+  // the root's ends at n_nodes), so every row is written once and every child before its parent.
+  std::vector<size_t> end_of;  // one past the last row of the subtree
+  try {
+    end_of.assign(n_nodes, 0);
+  } catch (...) {
+    return PTMI_ERR_NO_MEMORY;
+  }
+  for (size_t i = n_nodes; i-- > 0;) {
+    const float* row = rows + 12 * i;
+    if (row[7] == -1.0f) {  // inner (bvhBuilder.js:45,49)
+      const float r = row[3];
+      if (!(r > (float)i) || !(r < (float)n_nodes) || r != std::floor(r)) return PTMI_ERR_BAD_SCENE;
+      const size_t right = (size_t)r;
+      if (right < i + 2 || end_of[i + 1] != right) return PTMI_ERR_BAD_SCENE;  // the left subtree is the rows between
+      end_of[i] = end_of[right];
+    } else {
+      const float first = row[8], count = row[9];
+      if (!(first >= 0.0f) || !(count >= 1.0f) || first != std::floor(first) || count != std::floor(count)) return PTMI_ERR_BAD_SCENE;
+      if (!((double)first + (double)count <= (double)n_prims)) return PTMI_ERR_BAD_SCENE;
+      end_of[i] = i + 1;
+    }
+  }
+  if (end_of[0] != n_nodes) return PTMI_ERR_BAD_SCENE;
+  for (size_t i = n_nodes; i-- > 0;) {  // children have larger indices than their parent
+    float* row = rows + 12 * i;
+    double lo[3], hi[3];
+    if (row[7] == -1.0f) {
+      const float *a = row + 12, *b = rows + 12 * (size_t)row[3];
+      for (int k = 0; k < 3; k++) lo[k] = js_min((double)a[k], (double)b[k]), hi[k] = js_max((double)a[4 + k], (double)b[4 + k]);
+    } else {
+      const size_t first = (size_t)row[8], count = (size_t)row[9];
+      for (int k = 0; k < 3; k++) lo[k] = bmin[3 * first + k], hi[k] = bmax[3 * first + k];
+      for (size_t p = first + 1; p < first + count; p++)
+        for (int k = 0; k < 3; k++) lo[k] = js_min(bmin[3 * p + k], lo[k]), hi[k] = js_max(bmax[3 * p + k], hi[k]);
+    }
+    row[0] = (float)lo[0], row[1] = (float)lo[1], row[2] = (float)lo[2];
+    row[4] = (float)hi[0], row[5] = (float)hi[1], row[6] = (float)hi[2];
+  }
+  return PTMI_OK;
+}
+
+
 // ---- OBJ parsing with the reference's grammar (lib/primitives/objReader.js:10-68) ---------------------------------
 namespace {
 

@@ -37,6 +37,7 @@ SYMBOLS = [
     "ptmi_denoise_views_frames", "ptmi_denoise_views_guided_frames", "ptmi_fuse_views_frames", "ptmi_accumulate_views_frames",
     "ptmi_denoise_images_frames", "ptmi_denoise_images_guided_frames", "ptmi_fuse_images_frames", "ptmi_accumulate_images_frames",
     "ptmi_denoise_reference_frames", "ptmi_denoise_guided_reference_frames", "ptmi_fuse_reference_frames", "ptmi_accumulate_reference_frames",
+    "ptmi_refit_bvh", "ptmi_refit_scene_bvh",
 ]
 
 VIEW_SLOT_TABLE_MAX_WORDS = 1 << 24  # PTMI_VIEW_SLOT_TABLE_MAX_WORDS
@@ -273,6 +274,9 @@ def load_library(build=False, path=None):
         L.ptmi_denoise_guided_reference_frames.argtypes = [fp, fp, fp, i32, i32, u32, fp, gp, fp, fp]
         L.ptmi_fuse_reference_frames.argtypes = [fp, fp, fp, i32, i32, u32, fp, ctypes.c_float, fp, u32, up, fp]
         L.ptmi_accumulate_reference_frames.argtypes = [fp, fp, fp, fp, i32, i32, u32, fp, ctypes.c_float, fp, u32, ap, fp, fp, i32]
+    if hasattr(L, "ptmi_refit_scene_bvh"):  # (an older A/B build loaded through PTMI_LIB rebuilds a stale tree)
+        L.ptmi_refit_bvh.argtypes = [sz, fp, fp, fp, sz]
+        L.ptmi_refit_scene_bvh.argtypes = [vp]
     if explicit:
         _libs[path] = L
     else:
@@ -574,6 +578,18 @@ class NativeHost:
         if st != 0:
             raise PtmiError(st, self._why(bmin, bmax, True) or "ptmi_build_bvh_sah failed")
         return nodes[: count.value].copy(), order
+
+    def refit_bvh(self, bmin, bmax, rows):
+        """ptmi_refit_bvh: `rows` (n_nodes, 12) with their boxes recomputed bottom-up over the primitive boxes bmin / bmax (n, 3), which are given in the tree's leaf
+        order (indexed by row[8]); topology, links and leaf ranges stay.  Returns a new array; `rows` is not written."""
+        bmin = np.ascontiguousarray(bmin, np.float64)
+        bmax = np.ascontiguousarray(bmax, np.float64)
+        out = np.array(rows, np.float32, order="C", copy=True).reshape(-1, 12)
+        assert bmin.shape == bmax.shape and bmin.ndim == 2 and bmin.shape[1] == 3
+        st = self.lib.ptmi_refit_bvh(bmin.shape[0], _ptr(bmin), _ptr(bmax), _ptr(out), out.shape[0])
+        if st != 0:
+            raise PtmiError(st, self._why(bmin, bmax, False) or "ptmi_refit_bvh: the rows are not a pre-order tree over these primitives")
+        return out
 
     def parse_obj(self, text):
         """ObjReader.parse in native code: {vertices, normals} float32 arrays (lib/primitives/objReader.js grammar)."""
@@ -1073,6 +1089,10 @@ class Context:
         """ptmi_build_scene_bvh: Scene.create_bvh() on the GPU over the uploaded (unordered) triangles, meshes and transforms; nothing comes back.
         sah=True: the reference's other builder (lib/BVH/bvhNode.js:108-283), the opt-in."""
         self._ck((self.lib.ptmi_build_scene_bvh_sah if sah else self.lib.ptmi_build_scene_bvh)(self.h))
+
+    def refit_scene_bvh(self):
+        """ptmi_refit_scene_bvh: the device-resident tree's boxes recomputed over the triangles, meshes and transforms uploaded now, its topology kept."""
+        self._ck(self.lib.ptmi_refit_scene_bvh(self.h))
 
     def scene_bvh_info(self):
         """{nodes, depth, on_device} of the scene's BVH (ptmi_scene_bvh_info)."""
