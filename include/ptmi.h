@@ -24,6 +24,23 @@
  *  - The uploaded buffers are checked together by the next call that renders or traces, not by ptmi_upload: an index out of range is that call's
  *    PTMI_ERR_BAD_SCENE, naming the element, before anything is enqueued; every such call fails the same way until an upload repairs the scene, and renders
  *    from then on are what they would have been had the bad buffer never been sent.
+ *  - Which tree a render walks, and in which order the triangles lie on the device (tests/context_model.py numbers these rules 7 to 12):
+ *    ptmi_build_scene_bvh[_sah] builds over the triangles in the order they lie in NOW — the caller's upload order after ptmi_upload(PTMI_BUF_TRIANGLES), the
+ *    leaf order of the last build or refit otherwise — and leaves a device-resident tree that is not stale, the triangles in its leaf order, and an order that
+ *    names positions of the caller's last upload (composed through the earlier order where the triangles lay in one).  With no triangles uploaded it leaves no
+ *    tree of either kind.  A refused build leaves the context as it was: a stale tree stays stale.
+ *  - ptmi_refit_scene_bvh leaves the tree not stale, the triangles in leaf order and ptmi_scene_bvh_info as it was.  Each of its refusals — no device-resident
+ *    tree, another triangle count, a triangle outside the builders' domain — leaves rows, triangles and staleness as they were, and the same call again gives
+ *    the same answer.
+ *  - Under a device-resident tree every ptmi_upload of triangles, meshes or transforms makes the tree stale, whether or not a byte differs, and uploaded
+ *    triangles lie in upload order.  Every call that renders or traces then returns PTMI_ERR_BAD_SCENE before anything is enqueued: "built over N
+ *    triangles, M are uploaded now" where the count differs, "build again" otherwise.  Uploads of spheres, quads and materials leave the tree alone.
+ *  - ptmi_upload(PTMI_BUF_BVH) replaces a device-resident tree by the uploaded one (by none, if it is empty); ptmi_refit_scene_bvh then returns
+ *    PTMI_ERR_STATE.  The triangles stay where they lie, and while they lie in a leaf order a later build composes its order through it.  An uploaded tree
+ *    must bound its triangles; the library cannot check that, and traverses the rows as they stand.
+ *  - Triangles under no tree (nothing built, no BVH or an empty one uploaded) are not an error: renders and traces skip the traversal, as the reference's
+ *    shader does with an empty tree, and no triangle is hit.
+ *  - Every successful ptmi_upload, build and refit drops the frames ptmi_render_frame had traced ahead: the next frame is rendered from the new buffers.
  */
 #ifndef PTMI_H
 #define PTMI_H

@@ -5,7 +5,11 @@ ptmi_refit_bvh's (the CPU reference, itself checked in test_refit_cpu.py) on box
 triangles are the moved ones in the old leaf order; the render and its work counters are the oracle's on the read-back buffers, bit for bit; traced rays find
 what the oracle's brute-force search finds.  Then call sequences, refusals, a context of two shards, and an eight-step animation.
 
-The refusals here are refused on the host from two words k_scene_boxes wrote (or before anything is enqueued): nothing provokes a device fault."""
+The refusals here are refused on the host from two words k_scene_boxes wrote (or before anything is enqueued): nothing provokes a device fault.
+
+This module holds the refit's arithmetic and its launch geometry, on buffers read back from the device.  The orders in which builds, refits and uploads may
+follow each other, through ptmi_render_frame and ptmi_render_views too and against triangles and rows predicted without a read-back, are
+test_context_walk_gpu.py's along context_model.tree_walks()."""
 import numpy as np
 import pytest
 

@@ -11,7 +11,10 @@ The moments:  synced — the edit follows a read-back;  in-flight — it follows
 frames after the edit must come from the NEW scene.
 
 The refused stages (M3 under importance sampling, S2) are refused by prepare_scene / check_renderable on the host, before anything is enqueued: nothing here
-provokes a device fault.  The oracle's side is memoised per session, so the three pipelines pay for it once."""
+provokes a device fault.  The oracle's side is memoised per session, so the three pipelines pay for it once.
+
+Call ORDERS — uploads that make a device-resident tree stale, builds, refits and uploaded trees in every order, under ptmi_render_frame's frames traced ahead —
+are test_context_walk_gpu.py's along context_model.tree_walks(); test_edits_under_a_device_built_tree here holds only the edits that must not make it stale."""
 import numpy as np
 import pytest
 
