@@ -694,6 +694,10 @@ int ptmi_stream(ptmi_ctx* ctx, void** stream);
 int ptmi_resolve_rgba8(ptmi_ctx* ctx, float frame_num, uint8_t* dst, size_t bytes);
 
 int ptmi_set_counters(ptmi_ctx* ctx, int enabled);
+/* The table of quad records (csrc/ptmi_device.h, DevScene::quad_onb): k_shade's wave-by-wave variants keep, for scenes of 1 to 16 quads, every quad's unit
+ * normal and the frame of a Lambertian bounce off its front side in LDS instead of fetching the one and building the other per hit.  The same bits either
+ * way.  On by default; enabled = 0 keeps the per-hit code (A/B measurements, tests).  Takes effect with the next render. */
+int ptmi_set_onb_table(ptmi_ctx* ctx, int enabled);
 /* 0 = off; 1 = HIP events around every kernel launch; 2 / 3 / 4 / 5 / 6 = only around k_bvh / k_shade / k_generate /
  * k_accumulate / k_tail: fewer stream markers, for timing ONE kernel inside a region whose wall clock also matters. */
 int ptmi_set_timing(ptmi_ctx* ctx, int enabled);
@@ -714,7 +718,10 @@ int ptmi_math_eval(ptmi_ctx* ctx, int fn, size_t n, const float* x, const float*
 
 /* Test hook: exhaustive check ON THE DEVICE of the unary shortcuts the kernels use instead of the compiler's IEEE expansions
  * (csrc/ptmi_device.h): which = 0: 1/x, 1: sqrt(x), 2: the three-component reciprocal — each against the IEEE operation over all
- * 2^32 arguments; 3 / 4: the bare v_rcp_f32 / v_sqrt_f32 instructions (controls that must report mismatches).  *mismatches = number of arguments whose bits differ (NaNs compare equal), *first_bad_bits = the smallest. */
+ * 2^32 arguments; 3 / 4: the bare v_rcp_f32 / v_sqrt_f32 instructions (controls that must report mismatches).  *mismatches = number of arguments whose bits differ (NaNs compare equal), *first_bad_bits = the smallest.
+ * which = 8: the UPLOADED scene's quad records (ptmi_set_onb_table) — for every quad, the record's unit normal against normalize(quad.normal) and its frame against
+ * onb_build_from_w of that normal, recomputed on the device; *mismatches = records that differ (must be 0), *first_bad_bits = the number of quads whose frame of the
+ * BACK side (-n) is not the record's negated, which is why back-facing hits never take the record (informative; an axis-aligned quad is one: the zeros of its frame keep their sign when n changes its own). */
 int ptmi_selftest(ptmi_ctx* ctx, int which, uint64_t* mismatches, uint32_t* first_bad_bits);
 
 /* Scene.create_bvh() (lib/scene.js:253-259 -> lib/BVH/bvhBuilder.js:6, bvhNode.js:28-73) for the triangles that are ALREADY uploaded (binding 5,

@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 
 POINTS = ["GROUP", "VALID", "MISS", "HIT", "RH_SPHERE", "RH_VOLUME", "RH_QUAD", "RH_TRI", "MS_LAMBERT", "MS_MIRROR", "MS_GLASS", "MS_ISO", "RR", "ACC_CONT", "END_SAMPLE",
           "END_CHANGES", "FLUSH", "QUAD_LOOP", "QUAD_FRONT", "QUAD_DENOM", "QUAD_T", "QUAD_ACCEPT", "ROOT_BOX", "MISS_SHORTCUT", "KEEP", "DIV3_SLOW", "RCP_SLOW", "SQRT_SLOW",
-          "SPHERE_LOOP", "IS_LIGHT", "STAGE", "CONT", "HOLE"]
+          "SPHERE_LOOP", "IS_LIGHT", "STAGE", "CONT", "HOLE", "ONB_TAB"]
 VARIANT = os.path.join(ROOT, "webgpu-path-tracer_amd", "variants", "libptmi_lanes.so")
 
 

@@ -121,6 +121,9 @@ struct Stack {
 
 // (Tuning — the PTMI_* environment knobs, their domains and their parsing: ptmi_tuning.h)
 
+#ifndef PTMI_ONB_TABLE_DEFAULT
+#define PTMI_ONB_TABLE_DEFAULT 1  // (-DPTMI_ONB_TABLE_DEFAULT=0: an A/B build whose contexts start with the table of quad records off — bench.py never calls ptmi_set_onb_table)
+#endif
 struct ptmi_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -135,7 +138,8 @@ struct ptmi_ctx {
   std::vector<int32_t> h_meshes;
   bool scene_dirty = true;
 
-  DBuf d_quad_unit_n;
+  DBuf d_quad_unit_n, d_quad_onb;  // k_quad_digest's two tables (DevScene)
+  bool onb_table = PTMI_ONB_TABLE_DEFAULT != 0;  // ptmi_set_onb_table
   // ptmi_build_scene_bvh: the BVH rows (binding 9's layout) live on the device only — no host copy, pair64 made there too
   DBuf d_bvh_rows;
   bool bvh_on_device = false;
@@ -357,6 +361,9 @@ bool id_from_float(float f, int n, int* out) {  // i32(f32) of an index field, r
   return true;
 }
 
+// DevScene::onb_tab: the table of quad records fits a k_shade block's LDS share (kOnbTabQuads) and the caller has not switched it off
+int onb_tab_of(const ptmi_ctx* c, int n_quad) { return c->onb_table && n_quad > 0 && n_quad <= kOnbTabQuads ? 1 : 0; }
+
 // Validate every index the kernels will dereference and build the digests (see DevScene).
 int prepare_scene(ptmi_ctx* c) {
   if (!c->scene_dirty) return PTMI_OK;
@@ -558,8 +565,10 @@ int prepare_scene(ptmi_ctx* c) {
   HIP_TRY(c, up(c->d_quads, c->h_quads.data(), c->h_quads.size() * 4));
   HIP_TRY(c, up(c->d_quad_mat, quad_mat.data(), quad_mat.size() * 4));
   HIP_TRY(c, c->d_quad_unit_n.ensure(std::max<size_t>((size_t)n_quad * 16, 16)));
+  HIP_TRY(c, c->d_quad_onb.ensure(std::max<size_t>((size_t)n_quad, (size_t)kOnbTabQuads) * 48));
   if (n_quad > 0) {
-    hipLaunchKernelGGL(k_quad_digest, dim3((unsigned)((n_quad + 63) / 64)), dim3(64), 0, c->stream, c->d_quads.as<float4>(), n_quad, c->d_quad_unit_n.as<float4>());
+    hipLaunchKernelGGL(k_quad_digest, dim3((unsigned)((n_quad + 63) / 64)), dim3(64), 0, c->stream, c->d_quads.as<float4>(), n_quad, c->d_quad_unit_n.as<float4>(),
+                       c->d_quad_onb.as<float4>());
     HIP_TRY(c, hipGetLastError());
   }
   HIP_TRY(c, up(c->d_meshes, c->h_meshes.data(), c->h_meshes.size() * 4));
@@ -594,6 +603,7 @@ int prepare_scene(ptmi_ctx* c) {
   S.quads = c->d_quads.as<float4>();
   S.quad_mat = c->d_quad_mat.as<int>();
   S.quad_unit_n = c->d_quad_unit_n.as<float4>();
+  S.quad_onb = c->d_quad_onb.as<float4>();
   S.tris = c->d_tris.as<float4>();
   S.pretri = c->d_pretri.as<float4>();
   S.trinorm = c->d_trinorm.as<float4>();
@@ -610,6 +620,7 @@ int prepare_scene(ptmi_ctx* c) {
   for (int i = 1; i < n_mesh; i++)
     if (c->h_meshes[4 * (size_t)i + 2] != S.uniform_gid) S.uniform_gid = -1;
   S.tmin = c->prm.tmin;
+  S.onb_tab = onb_tab_of(c, n_quad);
   c->scene_dirty = false;
   return PTMI_OK;
 }
@@ -3284,6 +3295,15 @@ int ptmi_set_counters(ptmi_ctx* c, int on) {
   for (ptmi_ctx* q : local_devices(c)) q->counters = on != 0;
   return PTMI_OK;
 }
+int ptmi_set_onb_table(ptmi_ctx* c, int on) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  for (ptmi_ctx* q : local_devices(c)) {
+    q->onb_table = on != 0;
+    q->S.onb_tab = onb_tab_of(q, q->S.n_quads);  // (a scene prepared later: prepare_scene)
+    q->ahead.valid = false;
+  }
+  return PTMI_OK;
+}
 int ptmi_set_timing(ptmi_ctx* c, int on) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   for (ptmi_ctx* q : local_devices(c)) q->timing = (on < 0 || on > 6) ? 0 : on;
@@ -3433,13 +3453,20 @@ int ptmi_bvh_tally(ptmi_ctx* c, uint64_t* out, int n_regions, int reset_and_whic
 
 int ptmi_selftest(ptmi_ctx* c, int which, uint64_t* mismatches, uint32_t* first_bad_bits) {
   if (!c || !mismatches) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_selftest: null argument");
-  if (which < 0 || which > 7) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_selftest: unknown test id");
+  if (which < 0 || which > 8) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_selftest: unknown test id");
   HIP_TRY(c, hipSetDevice(c->device));
+  if (which == 8) {  // the uploaded scene's quad records (k_quad_digest) against the bounce's own evaluation
+    int st = prepare_scene(c);
+    if (st != PTMI_OK) return st;
+  }
   DBuf d;
   HIP_TRY(c, d.ensure(16));
-  unsigned long long init[2] = {0ull, 0xffffffffull};
+  unsigned long long init[2] = {0ull, which == 8 ? 0ull : 0xffffffffull};
   hipError_t e = hipMemcpyAsync(d.p, init, 16, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
+  if (e == hipSuccess && which == 8) {
+    if (c->S.n_quads > 0) hipLaunchKernelGGL(k_selftest_quad_onb, dim3((unsigned)((c->S.n_quads + 63) / 64)), dim3(64), 0, c->stream, c->S, d.as<unsigned long long>());
+    e = hipGetLastError();
+  } else if (e == hipSuccess) {
     hipLaunchKernelGGL(k_selftest, dim3((unsigned)c->num_cus * 16), dim3(256), 0, c->stream, which, d.as<unsigned long long>(), reinterpret_cast<uint32_t*>(d.as<unsigned long long>() + 1));
     e = hipGetLastError();
   }

@@ -64,7 +64,7 @@ enum : int {
   LT_GROUP = 0, LT_VALID = 1, LT_MISS = 2, LT_HIT = 3, LT_RH_SPHERE = 4, LT_RH_VOLUME = 5, LT_RH_QUAD = 6, LT_RH_TRI = 7, LT_MS_LAMBERT = 8, LT_MS_MIRROR = 9,
   LT_MS_GLASS = 10, LT_MS_ISO = 11, LT_RR = 12, LT_ACC_CONT = 13, LT_END_SAMPLE = 14, LT_END_CHANGES = 15, LT_FLUSH = 16, LT_QUAD_LOOP = 17, LT_QUAD_FRONT = 18,
   LT_QUAD_DENOM = 19, LT_QUAD_T = 20, LT_QUAD_ACCEPT = 21, LT_ROOT_BOX = 22, LT_MISS_SHORTCUT = 23, LT_KEEP = 24, LT_DIV3_SLOW = 25, LT_RCP_SLOW = 26, LT_SQRT_SLOW = 27,
-  LT_SPHERE_LOOP = 28, LT_IS_LIGHT = 29, LT_STAGE = 30, LT_CONT = 31, LT_HOLE = 32
+  LT_SPHERE_LOOP = 28, LT_IS_LIGHT = 29, LT_STAGE = 30, LT_CONT = 31, LT_HOLE = 32, LT_ONB_TAB = 33
 };
 
 // ---- constants of shaders/header.wgsl:1-13,37 (abstract-float consts folded in f64, rounded once) ----
@@ -255,6 +255,8 @@ struct DevScene {
   const float4* trinorm;      // 3 x float4 per triangle: the vertex normals nA, nB, nC (common.wgsl:230) with the mesh's transform index in nA.w — what
                               // resolve_hit needs of a triangle hit in one 48-byte run (the raw 96-byte record + the pretri record: three cache lines)
   const float4* quad_unit_n;  // normalize(quad.normal), evaluated once per quad by k_quad_digest with the very same norm3()
+  const float4* quad_onb;     // 3 float4 / quad: {n, w, v, u} — n as in quad_unit_n, {w, v, u} = onb_build_from_w(n), the frame of a Lambertian
+                              // bounce off the quad's front side; written by k_quad_digest with the very device functions the bounce calls
   const float4* tris;    // 6 float4 / triangle (raw)
   const float4* pretri;  // 4 float4 / triangle
   const int4* meshes;
@@ -268,7 +270,9 @@ struct DevScene {
   int uniform_gid;  // the transform index all meshes share (one mesh: every configuration of BASELINE.json), -1 if they differ: a triangle hit's
                     // normal matrix then comes through the scalar cache with the hit's other data instead of one dependent VMEM round trip later
   float tmin;      // ray_tmin (header.wgsl:37; ptmi_params.tmin, 0.000001 by default)
+  int onb_tab;     // 1: k_shade's wave-by-wave body keeps quad_onb in LDS and takes a front-facing quad hit's frame from there (0 < n_quads <= kOnbTabQuads, ptmi_set_onb_table)
 };
+constexpr int kOnbTabQuads = 16;  // 768 bytes of LDS per block
 
 // ---- path state ----------------------------------------------------------------------------------------
 // Live state is indexed by QUEUE SLOT and compacted every step: step s reads the `in` buffers, k_shade writes the
@@ -903,7 +907,13 @@ struct TriFetch {
   // (the mesh's transform index is nA.w — = meshes[i32(nC.w)].global_id, put there by k_pretri_digest — read where it is used: a copy made here would make
   // the fetch wait for the record before the material's loads are even issued)
 };
-DEV TriFetch tri_fetch(const DevScene& S, const float2* __restrict__ uvbuf, uint32_t slot, uint32_t prim) {
+// The quads' records of DevScene::quad_onb in LDS, copied by the block that runs with S.onb_tab (shade_body_wave): 48 bytes per quad,
+//   {n.x, n.y, n.z, w.x} {w.y, w.z, v.x, v.y} {v.z, u.x, u.y, u.z}
+// A quad hit reads {n, w.x} where it read quad_unit_n — into the registers of a triangle's first vertex normal (tri_fetch) — and the frame only where
+// material_scatter uses it: held in TriFetch::nB, nC from the fetch on, or read here, k_shade6<false,false> needs a register it does not have (profiles/onb_table_ab.txt).
+__shared__ float4 s_quad_onb[3 * kOnbTabQuads];
+// `tab` (wave-uniform): the block holds s_quad_onb — a quad hit takes its unit normal from there, not from memory
+DEV TriFetch tri_fetch(const DevScene& S, const float2* __restrict__ uvbuf, uint32_t slot, uint32_t prim, bool tab = false) {
   TriFetch f;  // (read by resolve_hit's K_TRI and K_QUAD branches only: nothing to initialise for the other lanes — 14 moves per group)
   const uint32_t idx = prim & 0x0fffffffu;
   if ((prim >> 28) == K_TRI) {
@@ -911,7 +921,11 @@ DEV TriFetch tri_fetch(const DevScene& S, const float2* __restrict__ uvbuf, uint
     const float4* tn = S.trinorm + 3 * (size_t)idx;
     f.nA = tn[0], f.nB = tn[1], f.nC = tn[2];
   } else if ((prim >> 28) == K_QUAD) {
-    f.nA = S.quad_unit_n[idx];  // a quad hit's unit normal rides in the same registers: asked for here, with everything else, instead of in the middle of resolve_hit (round 4)
+    if (tab) {  // (idx < n_quads <= kOnbTabQuads: hitScene's quad loop made it)
+      f.nA = s_quad_onb[3 * idx];
+    } else {
+      f.nA = S.quad_unit_n[idx];  // a quad hit's unit normal rides in the same registers: asked for here, with everything else, instead of in the middle of resolve_hit (round 4)
+    }
   }
   return f;
 }
@@ -977,6 +991,16 @@ DEV Onb onb_build_from_w(f3 wdir) {  // :60-67
   f3 a = (ptm_abs(b.w.x) > 0.9f) ? mk3(0, 1, 0) : mk3(1, 0, 0);
   b.v = norm3(cross3(b.w, a));
   b.u = cross3(b.w, b.v);
+  return b;
+}
+// The frame in a quad's record (s_quad_onb, DevScene::quad_onb): onb_build_from_w(n) as k_quad_digest evaluated it, once per quad
+DEV Onb onb_of_record(const float4* rec) {
+  const float wx = rec[0].w;
+  const float4 r1 = rec[1], r2 = rec[2];
+  Onb b;
+  b.w = mk3(wx, r1.x, r1.y);
+  b.v = mk3(r1.z, r1.w, r2.x);
+  b.u = mk3(r2.y, r2.z, r2.w);
   return b;
 }
 DEV f3 onb_get_local(const Onb& b, f3 a) { return b.u * a.x + b.v * a.y + b.w * a.z; }  // :69-71
@@ -1065,12 +1089,23 @@ DEV Material load_material(const DevScene& S, int id) {
 // shaders/scatterRay.wgsl:2-95.  `bin` is the wave-uniform material class the path was sorted into.
 // Returns the scattered direction (origin is hitRec.p); sets doSpecular, skip_pdf and, for
 // LAMBERTIAN, the ONB w axis that onb_lambertian_scattering_pdf reads afterwards.
-DEV f3 material_scatter(int bin, const Material& m, const HitGeom& g, f3 din, uint32_t& rng, float& doSpecular, bool& skip_pdf, f3& unit_w) {
+// `tab` (wave-uniform): the block holds s_quad_onb, `prim` names this lane's record there; `quad_front`: this lane's hit is a quad's front side, so g.n is the record's n
+// bit for bit and the record's frame is onb_build_from_w(g.n).  The frame is taken from the records only when EVERY lane here can take it — one wave-uniform
+// branch, no lane runs both — and built as ever otherwise: a triangle or sphere hit among the lanes, or a back-facing quad hit (the frame of -n is not the
+// negated frame of n: zero signs differ), which takes a non-finite ray or a normal whose rounding separates it from its unit normal.
+DEV f3 material_scatter(int bin, const Material& m, const HitGeom& g, f3 din, uint32_t& rng, float& doSpecular, bool& skip_pdf, f3& unit_w, uint32_t prim, bool tab,
+                        bool quad_front) {
   doSpecular = 0.0f;
   skip_pdf = true;
   if (bin == BIN_LAMBERTIAN) {
     LT(LT_MS_LAMBERT);
-    Onb b = onb_build_from_w(g.n);
+    Onb b;
+    if (tab && __ballot(!quad_front) == 0ull) {
+      LT(LT_ONB_TAB);
+      b = onb_of_record(s_quad_onb + 3 * (prim & 0x0fffffffu));
+    } else {
+      b = onb_build_from_w(g.n);
+    }
     unit_w = b.w;
     f3 diffuse = cosine_sampling_wrt_Z(rng);
     diffuse = norm3(onb_get_local(b, diffuse));

@@ -552,8 +552,10 @@ DEV void end_sample_progressive(const Paths& P, uint32_t pid, f3 add, bool writt
 // MULTI = NUM_SAMPLES > 1 (the per-pixel sample loop of shootRay.wgsl:5-49 lives in the slot: pixsum, in-slot camera ray); the
 // reference's progressive mode (NUM_SAMPLES = 1) compiles without it, which also frees the scalar registers the view matrix and
 // the image constants would occupy through the whole kernel.
+// `tab` (wave-uniform): the block holds the table of quad records, and `tf` came from it (tri_fetch, material_scatter).
 template <bool IS, bool MULTI, int MV>
-DEV bool shade_one(const DevScene& S, const RenderConst& rc, const Paths& P, const SlotState& st, const TriFetch& tf, const QuadL& L, NewState& ns, const ViewTab& vt) {
+DEV bool shade_one(const DevScene& S, const RenderConst& rc, const Paths& P, const SlotState& st, const TriFetch& tf, const QuadL& L, NewState& ns, const ViewTab& vt,
+                   bool tab = false) {
   const uint32_t pid = __float_as_uint(st.q1.w);
   const f3 o = mk3(st.q0), d = mk3(st.q1);
   const float4 T4 = st.q2;
@@ -587,7 +589,7 @@ DEV bool shade_one(const DevScene& S, const RenderConst& rc, const Paths& P, con
     float doSpecular;
     bool skip_pdf;
     f3 unit_w = mk3(0, 0, 0);
-    f3 sdir = material_scatter(bin, m, g, d, rng, doSpecular, skip_pdf, unit_w);
+    f3 sdir = material_scatter(bin, m, g, d, rng, doSpecular, skip_pdf, unit_w, prim, tab, (prim >> 28) == K_QUAD && g.front);
     f3 sorg = (bin == BIN_OTHER) ? mk3(0, 0, 0) : g.p;
     bool roulette = true;
     add = emission * T;  // acc_radiance += emissionColor * throughput (traceRay.wgsl:26,55,64)
@@ -710,6 +712,8 @@ constexpr int kSChunk = 512;  // slots a k_shade block sorts, shades and compact
 constexpr uint32_t kR0Empty = 0xffffffffu, kR0Busy = 0xfffffffeu, kR0Full = 0xfffffffdu;
 __shared__ uint32_t s_region0;  // the block's first claim: kR0Empty until a wave makes it (set by thread 0, visible after the block's first barrier)
 constexpr uint32_t kNoSlot = 0xffffffffu;
+// The wave's index in its block as the scalar it is (threadIdx.x >> 6 alone is a vector register that lives as long as its last use)
+DEV uint32_t wave_in_block() { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 struct OutRegion {
   uint32_t cur, rend;
   // The slot of the next queue for this lane's survivor (`keep`), kNoSlot for a lane without one.  What no longer fits the current region continues in the
@@ -746,7 +750,7 @@ struct OutRegion {
           }
         }
         full = nb == kR0Full;
-        nb += (threadIdx.x >> 6) * wregion;
+        nb += wave_in_block() * wregion;
       } else {
         claimed = wregion_later;
         if (lane == 0) nb = atomicAdd(&ctl[1].n_rays, claimed);
@@ -773,7 +777,7 @@ struct OutRegion {
   // `block_claim`: s_region0 is this wave's to read (a barrier lies between the block's last place() and here).
   DEV void close(const Paths& P, uint32_t wregion, bool block_claim) {
     if (rend == 0u && block_claim && s_region0 < kR0Full) {
-      cur = s_region0 + (threadIdx.x >> 6) * wregion;
+      cur = s_region0 + wave_in_block() * wregion;
       rend = cur + wregion;
     }
     for (uint32_t i = cur + (uint32_t)lane_id(); i < rend; i += 64u) {
@@ -957,6 +961,10 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
   static_assert((size_t)kWaves * kRing == (size_t)kSChunk, "the rings take the LDS the block version's staging arrays take");
   __shared__ float4 s_q0[kWaves * kRing], s_q1[kWaves * kRing], s_q2[kWaves * kRing];
   if (threadIdx.x == 0) s_region0 = kR0Empty;
+  // The quads' records (DevScene::quad_onb), once per block: a quad hit reads its unit normal and the frame of its Lambertian bounce from here (tri_fetch)
+  // (S.onb_tab is wave-uniform; the host sets it only with 0 < n_quads <= kOnbTabQuads, and its table always has kOnbTabQuads records' room)
+  static_assert(3 * kOnbTabQuads <= kBlock, "one thread per float4 of the table");
+  if (S.onb_tab && threadIdx.x < 3u * (uint32_t)kOnbTabQuads) s_quad_onb[threadIdx.x] = S.quad_onb[threadIdx.x];
 #ifdef PTMI_LANE_TALLY
   if (threadIdx.x < kLaneTallies * 2) s_lane_tally[threadIdx.x] = 0u;
   if (threadIdx.x < 4 * kTimeTallies) s_time_tally[threadIdx.x] = 0ull;
@@ -965,7 +973,7 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
   __syncthreads();
   const QuadL L = load_light(S);
   const int lane = lane_id();
-  const uint32_t wv = threadIdx.x >> 6;
+  const uint32_t wv = wave_in_block();
   float4 *const r0 = s_q0 + wv * kRing, *const r1 = s_q1 + wv * kRing, *const r2 = s_q2 + wv * kRing;
   const QueueExtent qe = queue_extent(ctl, resv);
   const uint32_t n = qe.n, n_carried = qe.n_carried;
@@ -1050,8 +1058,8 @@ DEV void shade_body_wave(const DevScene& S, const RenderConst& rc, const Paths& 
       valid = __float_as_uint(st.q1.w) != PID_HOLE;
       if (valid) {
         LT(LT_VALID);
-        const TriFetch tf = tri_fetch(S, P.uv, st.slot, __float_as_uint(st.tp.y));  // (issued ahead of the material's loads, consumed after them)
-        survive = shade_one<IS, MULTI, MV>(S, rc, P, st, tf, L, ns, vt);
+        const TriFetch tf = tri_fetch(S, P.uv, st.slot, __float_as_uint(st.tp.y), S.onb_tab != 0);  // (issued ahead of the material's loads, consumed after them)
+        survive = shade_one<IS, MULTI, MV>(S, rc, P, st, tf, L, ns, vt, S.onb_tab != 0);
       }
     }
     TT(TT_SHADE, ns.o.x + ns.T.x);  // material + hit geometry fetched (TT_LOAD2, marked inside shade_one) and the bounce computed
@@ -1734,11 +1742,34 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_frames(RenderConst rc, Pa
 
 // Upload-time digest: the unit normal resolve_hit needs for a quad hit (common.wgsl:176), computed once per quad by the
 // same device function the shading path would call per hit — same instructions, same bits.
-__global__ void k_quad_digest(const float4* __restrict__ quads, int n, float4* __restrict__ unit_n) {
+__global__ void k_quad_digest(const float4* __restrict__ quads, int n, float4* __restrict__ unit_n, float4* __restrict__ onb) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= n) return;
   const f3 u = norm3(mk3(quads[5 * i + 3]));
   unit_n[i] = make_float4(u.x, u.y, u.z, 0.0f);
+  const Onb b = onb_build_from_w(u);  // the frame of a Lambertian bounce off the front side (material_scatter: g.n = u there)
+  float4* rec = onb + 3 * (size_t)i;    // layout: s_quad_onb (ptmi_device.h)
+  rec[0] = make_float4(u.x, u.y, u.z, b.w.x);
+  rec[1] = make_float4(b.w.y, b.w.z, b.v.x, b.v.y);
+  rec[2] = make_float4(b.v.z, b.u.x, b.u.y, b.u.z);
+}
+
+// ptmi_selftest 8: the records of k_quad_digest against the bounce's own evaluation, for every quad and both facings.  A front-facing hit has g.n = n and takes
+// the record's frame: it must be onb_build_from_w(n) bit for bit, and n must be quad_unit_n's.  A back-facing hit has g.n = -n and never takes the record;
+// `bad[1]` counts the quads whose frame of -n is NOT the record's negated — the reason it does not (for the record, not a failure).
+__global__ void k_selftest_quad_onb(DevScene S, unsigned long long* __restrict__ bad) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= S.n_quads) return;
+  auto same = [](float a, float b) { return __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b); };
+  auto same3 = [&](f3 a, f3 b) { return same(a.x, b.x) && same(a.y, b.y) && same(a.z, b.z); };
+  const float4 r0 = S.quad_onb[3 * i];
+  const f3 n = mk3(S.quad_unit_n[i]);
+  const Onb rec = onb_of_record(S.quad_onb + 3 * i), front = onb_build_from_w(n), back = onb_build_from_w(-n);
+  unsigned long long mine = 0;
+  if (!same3(mk3(r0), n) || !same3(n, norm3(mk3(S.quads[5 * i + 3])))) mine++;
+  if (!same3(rec.w, front.w) || !same3(rec.v, front.v) || !same3(rec.u, front.u)) mine++;
+  if (mine) atomicAdd(&bad[0], mine);
+  if (!same3(-rec.w, back.w) || !same3(-rec.v, back.v) || !same3(-rec.u, back.u)) atomicAdd(&bad[1], 1ull);
 }
 
 // Upload-time digest: pretri (DevScene) from the raw triangles, one thread per triangle — the subtractions and the cross product

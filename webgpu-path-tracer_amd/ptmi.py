@@ -16,7 +16,7 @@ SYMBOLS = [
     "ptmi_version", "ptmi_status_string", "ptmi_last_error", "ptmi_create", "ptmi_create_multi", "ptmi_destroy", "ptmi_default_params",
     "ptmi_set_params", "ptmi_get_params", "ptmi_upload", "ptmi_resize", "ptmi_clear_framebuffer", "ptmi_set_shard",
     "ptmi_render_frame", "ptmi_render", "ptmi_synchronize", "ptmi_prepare", "ptmi_read_framebuffer", "ptmi_write_framebuffer", "ptmi_reduce_framebuffer",
-    "ptmi_framebuffer_device_ptr", "ptmi_bind_framebuffer", "ptmi_stream", "ptmi_resolve_rgba8", "ptmi_set_counters",
+    "ptmi_framebuffer_device_ptr", "ptmi_bind_framebuffer", "ptmi_stream", "ptmi_resolve_rgba8", "ptmi_set_counters", "ptmi_set_onb_table",
     "ptmi_set_timing", "ptmi_get_stats", "ptmi_reset_stats", "ptmi_trace", "ptmi_math_eval", "ptmi_selftest", "ptmi_build_bvh",
     "ptmi_build_bvh_sah", "ptmi_build_bvh_device", "ptmi_build_scene_bvh", "ptmi_read_scene_buffer", "ptmi_obj_parse", "ptmi_free",
     "ptmi_device_count", "ptmi_reduce_info", "ptmi_reload_tuning", "ptmi_build_scene_bvh_sah", "ptmi_scene_bvh_info", "ptmi_build_bvh_sah_device",
@@ -163,6 +163,8 @@ def load_library(build=False, path=None):
     L.ptmi_stream.argtypes = [vp, ctypes.POINTER(vp)]
     L.ptmi_resolve_rgba8.argtypes = [vp, ctypes.c_float, fp, sz]
     L.ptmi_set_counters.argtypes = [vp, i32]
+    if hasattr(L, "ptmi_set_onb_table"):  # (an older A/B build loaded through PTMI_LIB lacks it)
+        L.ptmi_set_onb_table.argtypes = [vp, i32]
     L.ptmi_set_timing.argtypes = [vp, i32]
     L.ptmi_get_stats.argtypes = [vp, ctypes.POINTER(Stats)]
     L.ptmi_reset_stats.argtypes = [vp]
@@ -1063,6 +1065,10 @@ class Context:
     def set_counters(self, on):
         self._ck(self.lib.ptmi_set_counters(self.h, int(on)))
 
+    def set_onb_table(self, on):
+        """k_shade's LDS table of quad records (ptmi_set_onb_table): on by default, the same bits either way."""
+        self._ck(self.lib.ptmi_set_onb_table(self.h, int(on)))
+
     def set_timing(self, mode):
         """0/False off, 1/True every kernel, 2 / 3 / 4 / 5 only k_bvh / k_shade / k_generate / k_accumulate."""
         self._ck(self.lib.ptmi_set_timing(self.h, int(mode)))
@@ -1126,7 +1132,8 @@ class Context:
         return out, g
 
     def selftest(self, which):
-        """Exhaustive device-side check of a unary shortcut against the IEEE operation: (mismatches, first bad argument bits)."""
+        """Exhaustive device-side check of a unary shortcut against the IEEE operation: (mismatches, first bad argument bits).
+        which = 8: the uploaded scene's quad records: (records that differ from the bounce's own evaluation, quads whose back-side frame is not the record's negated)."""
         n, first = ctypes.c_uint64(), ctypes.c_uint32()
         self._ck(self.lib.ptmi_selftest(self.h, which, ctypes.byref(n), ctypes.byref(first)))
         return n.value, first.value
