@@ -24,6 +24,9 @@
  *  - The uploaded buffers are checked together by the next call that renders or traces, not by ptmi_upload: an index out of range is that call's
  *    PTMI_ERR_BAD_SCENE, naming the element, before anything is enqueued; every such call fails the same way until an upload repairs the scene, and renders
  *    from then on are what they would have been had the bad buffer never been sent.
+ *  - Only the INDICES of a scene are restricted (materials, meshes, transforms).  The values of spheres (centre, radius), quads (Q, u, v, the stored normal, D, w),
+ *    materials (every field, the type included) and shading normals are any f32 — zeros of either sign, subnormals, infinities, NaN — and render as the oracle
+ *    renders them (tests/edge_records.py).  Triangle positions, transforms and tree rows have the builders' domain (ptmi_check_bvh_boxes).
  *  - Which tree a render walks, and in which order the triangles lie on the device (tests/context_model.py numbers these rules 7 to 12):
  *    ptmi_build_scene_bvh[_sah] builds over the triangles in the order they lie in NOW — the caller's upload order after ptmi_upload(PTMI_BUF_TRIANGLES), the
  *    leaf order of the last build or refit otherwise — and leaves a device-resident tree that is not stale, the triangles in its leaf order, and an order that

@@ -70,6 +70,13 @@ def _mix(a, b, t):
     return a * (1 - t) + b * t  # Q12: arithmetic, never a select
 
 
+def _pow(x, y):
+    """WGSL's pow, whose accuracy is stated as that of exp2(y * log2(x)): for x < 0 that is NaN, whatever y.  numpy's power
+    gives (-x)^2 there.  A NaN in a lane gives it margin 0, so the reading does not speak about such lanes either way."""
+    with np.errstate(invalid="ignore"):
+        return np.where(x < 0, x.dtype.type(np.nan), np.power(np.where(x < 0, -x, x), y))
+
+
 def _rel(lhs, rhs, scale):
     """Margin of comparing lhs with rhs; non-finite (or 0 / 0) gives 0."""
     m = np.abs(lhs - rhs) / scale
@@ -491,7 +498,7 @@ def _scatter(sc, st, alive, o_in, d_in, mat, PI, TWO_PI):
         xi = st.rand(draw)
         r0 = (1 - ir) / (1 + ir)
         r0 = r0 * r0
-        refl = r0 + (1 - r0) * np.power(1 - cos_t, dt(5))
+        refl = r0 + (1 - r0) * _pow(1 - cos_t, dt(5))
         st.note(draw, _rel(refl, xi, np.abs(refl) + xi))
         use_reflect = tir | (refl > xi)
         dn = _dot(nrm, unit)
@@ -505,7 +512,9 @@ def _scatter(sc, st, alive, o_in, d_in, mat, PI, TWO_PI):
     if iso.any():
         g = mat[:, 11]
         lhs = 1 + g * g
-        rhs = np.power((1 - g * g) / (1 - g + 2 * g * st.rand(iso)), dt(2))
+        base = (1 - g * g) / (1 - g + 2 * g * st.rand(iso))
+        rhs = _pow(base, dt(2))
+        st.note(iso & ~(base >= 0), np.zeros(n))  # |g| > 1: pow of a negative base (Q14)
         st.note(iso, _rel(lhs, rhs, np.abs(lhs) + np.abs(rhs)))  # the value's own cancellation (module docstring)
         cos_hg = (lhs - rhs) / (2 * g)
         sin_hg = np.sqrt(1 - cos_hg * cos_hg)
