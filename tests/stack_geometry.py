@@ -3,7 +3,7 @@ fusion, the moment fold, the noise statistic, the multi-shard read-back) read fr
 for each limit the smallest shape of a given width that crosses it on a device of `cus` compute units.  A GPU test asks for its shape here and ASSERTS that the shape
 crosses the limit before it trusts a result: a cap that someone raises fails the test instead of quietly moving it back under the limit.
 
-The limits (ptmi.hip; `cus` = the device's CU count, full_frames.compute_units()):
+The limits (ptmi_stacks.hip, and ptmi.hip for aov, moments, gather and add; `cus` = the device's CU count, full_frames.compute_units()):
   rows          k_denoise_level / k_guided_level: blockIdx.y covers chunks of step x ty rows (ty = 4 from step 32 on, else 8): 128 rows at steps 16 and 32
   batch         atrous_enqueue (both filters): B views per batch, scratch cap / (pixels x 48 or 60 bytes); a -DPTMI_TEST_HOOKS build takes the cap from
                 PTMI_TEST_DENOISE_SCRATCH
@@ -20,20 +20,20 @@ from full_frames import CSRC, _constant
 EDGE_WIDTHS = dict(prepare=1000, aov=384, moments=1216, noise=130, readback=1216)  # no multiple of 64 where the kernel has tiles; the render sizes multiples of 64 as production's are
 
 
-def _source(name="ptmi.hip"):
+def _source(name):
     return open(os.path.join(CSRC, name)).read()
 
 
-def _factor(pattern, what, count=1):
-    """the N of `c->num_cus * N` in the statement(s) of ptmi.hip that `pattern` (one group: N) matches; `count` statements, which must agree"""
-    found = re.findall(pattern, _source())
+def _factor(name, pattern, what, count=1):
+    """the N of `c->num_cus * N` in the statement(s) of csrc/`name` that `pattern` (one group: N) matches; `count` statements, which must agree"""
+    found = re.findall(pattern, _source(name))
     assert len(found) == count and len(set(found)) == 1, "%s: %d statements match, factors %s" % (what, len(found), sorted(set(found)))
     return int(found[0])
 
 
 def constants():
     """Every number the limits are made of, as the compiler reads it."""
-    src = _source()
+    src = _source("ptmi_stacks.hip")
     ty = re.findall(r"const int step = 1 << l, ty = step >= (\d+) \? (\d+) : (\d+);", src)
     assert len(ty) == 1, ty  # atrous_enqueue: the one launch plan of both filters
     cap = re.search(r"denoise_scratch_cap\(\) \{.*?return \(size_t\)(\d+) << (\d+);\s*\}", src, re.S)
@@ -41,25 +41,25 @@ def constants():
     bpp = []
     for name in ("kDenoiseScratchBytes", "kGuidedScratchBytes"):  # each defined once, and used by name wherever a batch is sized
         assert len(re.findall(r"\b%s\s*=" % name, src)) == 1, name
-        bpp.append(_constant("ptmi.hip", name))
+        bpp.append(_constant("ptmi_stacks.hip", name))
     assert len(re.findall(r"denoise_scratch_cap\(\) /", src)) == 1 and re.search(
         r"static uint32_t atrous_batch_views\(size_t npix, uint32_t n, size_t bytes_per_pixel\) \{\s*return \(uint32_t\)std::max<size_t>\(1, std::min<size_t>\(n, denoise_scratch_cap\(\) / \(npix \* bytes_per_pixel\)\)\);\s*\}", src), "the batch formula"
     assert re.search(r"static size_t atrous_scratch_bytes\(size_t npix, uint32_t n, size_t bytes_per_pixel\) \{ return \(size_t\)atrous_batch_views\(npix, n, bytes_per_pixel\) \* npix \* bytes_per_pixel; \}", src), "the scratch size"
     assert not re.search(r"npix \* (48|60)\b", src), "a batch sized by a literal"
     return dict(
-        block=_constant("ptmi_kernels.h", "kBlock"),
+        block=_constant("ptmi_device.h", "kBlock"),
         denoise_tx=_constant("ptmi_denoise_kernels.h", "kDenoiseTX"),
         guided_ty=_constant("ptmi_guided_kernels.h", "kGuidedTY"),
         noise_chunks=_constant("ptmi_noise_kernels.h", "kNoiseChunks"),
-        multi_tile=_constant("ptmi.hip", "proc_tile"),  # the tile a multi-device context deals its pixels by until ptmi_set_shard says otherwise
+        multi_tile=_constant("ptmi_ctx.h", "proc_tile"),  # the tile a multi-device context deals its pixels by until ptmi_set_shard says otherwise
         ty_from_step=int(ty[0][0]), ty_wide=int(ty[0][1]), ty=int(ty[0][2]),
         scratch_cap=int(cap.group(1)) << int(cap.group(2)),
         denoise_bytes=bpp[0], guided_bytes=bpp[1],
-        prepare_blocks=_factor(r"const unsigned pgrid = \(unsigned\)std::min<size_t>\(\(items \+ kBlock - 1\) / kBlock, \(size_t\)c->num_cus \* (\d+)\);", "k_denoise_prepare's grid"),
-        aov_waves=_factor(r"const uint32_t grid = \(uint32_t\)std::max<uint64_t>\(1, std::min<uint64_t>\(waves, \(uint64_t\)c->num_cus \* (\d+)\)\);", "k_aov's grid"),
-        fold_blocks=_factor(r"const uint32_t ew_grid = std::max<uint32_t>\(1, std::min<uint32_t>\(\(total \+ kBlock - 1\) / kBlock, \(uint32_t\)c->num_cus \* (\d+)\)\);", "k_accumulate's grid"),
-        gather_blocks=_factor(r"std::min<size_t>\(\(\(size_t\)n_local \+ kBlock - 1\) / kBlock, \(size_t\)c->num_cus \* (\d+)\);", "k_gather_tiles' grid"),
-        add_blocks=_factor(r"std::min<size_t>\(\(n4 \+ kBlock - 1\) / kBlock, \(size_t\)c->num_cus \* (\d+)\);", "k_add_into's grid"),
+        prepare_blocks=_factor("ptmi_stacks.hip", r"const unsigned pgrid = \(unsigned\)std::min<size_t>\(\(items \+ kBlock - 1\) / kBlock, \(size_t\)c->num_cus \* (\d+)\);", "k_denoise_prepare's grid"),
+        aov_waves=_factor("ptmi.hip", r"const uint32_t grid = \(uint32_t\)std::max<uint64_t>\(1, std::min<uint64_t>\(waves, \(uint64_t\)c->num_cus \* (\d+)\)\);", "k_aov's grid"),
+        fold_blocks=_factor("ptmi.hip", r"const uint32_t ew_grid = std::max<uint32_t>\(1, std::min<uint32_t>\(\(total \+ kBlock - 1\) / kBlock, \(uint32_t\)c->num_cus \* (\d+)\)\);", "k_accumulate's grid"),
+        gather_blocks=_factor("ptmi.hip", r"std::min<size_t>\(\(\(size_t\)n_local \+ kBlock - 1\) / kBlock, \(size_t\)c->num_cus \* (\d+)\);", "k_gather_tiles' grid"),
+        add_blocks=_factor("ptmi.hip", r"std::min<size_t>\(\(n4 \+ kBlock - 1\) / kBlock, \(size_t\)c->num_cus \* (\d+)\);", "k_add_into's grid"),
     )
 
 

@@ -174,12 +174,31 @@ def test_the_guided_filter_with_counts_is_the_existing_reference_view_by_view(pk
 
 # ------------------------------------------------------------------------------------------------------------------- the sources
 def test_one_launch_plan_and_optional_tables(pkg):
-    src = open(os.path.join(ROOT, "webgpu-path-tracer_amd", "csrc", "ptmi.hip")).read()
+    src = open(os.path.join(ROOT, "webgpu-path-tracer_amd", "csrc", "ptmi_stacks.hip")).read()
     assert len(re.findall(r"^static int (atrous_enqueue|fuse_enqueue|accumulate_enqueue)\(", src, re.M)) == 3, "no twin of a launch plan"
     for kernel in ("k_denoise_prepare", "k_denoise_prepare_frames", "k_fuse", "k_fuse_frames", "k_accumulate_view", "k_accumulate_view_frames", "k_denoise_level_frames", "k_guided_level_frames"):
         assert len(re.findall(r"hipLaunchKernelGGL\(%s," % kernel, src)) == 1, kernel
     host = open(os.path.join(ROOT, "webgpu-path-tracer_amd", "csrc", "ptmi_host.cpp")).read()
     assert len(re.findall(r"^static int (atrous_reference|fuse_reference|accumulate_reference)\(", host, re.M)) == 3
+
+
+def test_the_renderer_and_the_stack_consumers_are_separate_units():
+    """ptmi.hip compiles none of the image-stack kernels, ptmi_stacks.hip and their headers none of the render kernels, and each launch plan lives in one file."""
+    csrc = os.path.join(ROOT, "webgpu-path-tracer_amd", "csrc")
+    text = {name: open(os.path.join(csrc, name)).read() for name in sorted(os.listdir(csrc))}
+    stack_headers = ["ptmi_%s_kernels.h" % k for k in ("denoise", "guided", "fuse", "accumulate", "noise")]
+    includes = {name: re.findall(r'^\s*#\s*include\s*"([^"]+)"', t, re.M) for name, t in text.items()}
+    assert not set(includes["ptmi.hip"]) & set(stack_headers), includes["ptmi.hip"]
+    reached, todo = set(), ["ptmi_stacks.hip"]  # everything of csrc/ that ptmi_stacks.hip includes, directly or not
+    while todo:
+        for inc in map(os.path.basename, includes[todo.pop()]):
+            if inc in text and inc not in reached:
+                reached.add(inc)
+                todo.append(inc)
+    assert set(stack_headers) <= reached and "ptmi_kernels.h" not in reached, sorted(reached)
+    for fn in ("atrous_enqueue", "fuse_enqueue", "accumulate_enqueue", "noise_enqueue"):
+        assert [name for name, t in text.items() if re.search(r"^static int %s\(" % fn, t, re.M)] == ["ptmi_stacks.hip"], fn
+        assert sum(len(re.findall(r"^[\w:<>*& ]*\b%s\([^;{]*\{" % fn, t, re.M)) for t in text.values()) == 1, fn
 
 
 node = shutil.which("node")

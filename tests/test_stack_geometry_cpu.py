@@ -61,7 +61,7 @@ def test_batches():
     K = sg.constants()
     w, h = 100, 37
     for guided in (False, True):
-        assert sg.batch_views(K, w, h, 64, guided) == 64 and sg.batch_views(K, 1920, 1080, 64, guided) == (8 if guided else 10)  # (ptmi.hip's comments)
+        assert sg.batch_views(K, w, h, 64, guided) == 64 and sg.batch_views(K, 1920, 1080, 64, guided) == (8 if guided else 10)  # (ptmi_stacks.hip's comments)
         for B, n in ((1, 3), (2, 5), (2, 3)):
             cap = sg.cap_for_batch(K, w, h, B, guided)
             assert sg.batch_views(K, w, h, n, guided, cap) == B < n and sg.batch_views(K, w, h, n, guided, cap - 1) == max(1, B - 1)
@@ -69,7 +69,7 @@ def test_batches():
 
 
 def test_the_hook_is_in_the_test_build_only():
-    src = open(os.path.join(ROOT, "webgpu-path-tracer_amd", "csrc", "ptmi.hip")).read()
+    src = open(os.path.join(ROOT, "webgpu-path-tracer_amd", "csrc", "ptmi_stacks.hip")).read()
     body = re.search(r"static inline size_t denoise_scratch_cap\(\) \{(.*?)\n\}", src, re.S).group(1)
     assert re.fullmatch(r'\s*#ifdef PTMI_TEST_HOOKS\s*if \(const char\* cap = getenv\("PTMI_TEST_DENOISE_SCRATCH"\)\) return \(size_t\)strtoull\(cap, nullptr, 10\);\s*#endif\s*'
                         r"return \(size_t\)1 << 30;", body), body

@@ -1,6 +1,7 @@
 #!/bin/bash
-# usage: tools/kernel_resources.sh out.s [extra flags]  -- compile ptmi.hip device-only to asm and list per-kernel resources
-#        PTMI_SRC=ptmi_bvh_device.hip tools/kernel_resources.sh out.s   -- the same for another translation unit of csrc/ (PTMI_SRC may also be a path)
+# usage: tools/kernel_resources.sh out.s [extra flags]  -- compile ptmi.hip (the render kernels) device-only to asm and list per-kernel resources
+#        PTMI_SRC=ptmi_stacks.hip tools/kernel_resources.sh out.s   -- the same for another translation unit of csrc/: ptmi_stacks.hip (the image-stack kernels: denoise, fuse,
+#                                                                      accumulate, noise), ptmi_bvh_device.hip (PTMI_SRC may also be a path)
 out=$1; shift
 src=${PTMI_SRC:-ptmi.hip}
 case "$src" in */*) ;; *) src=$(cd "$(dirname "$0")/.." && pwd)/webgpu-path-tracer_amd/csrc/$src ;; esac

@@ -1,6 +1,7 @@
 """Build recipes for the native pieces (explicit hipcc / gcc commands, outputs in-tree).
 
-libptmi.so   = csrc/ptmi.hip (HIP kernels + C ABI, gfx950) + csrc/ptmi_bvh_device.hip (BVH build on the GPU, rocPRIM)
+libptmi.so   = csrc/ptmi.hip (the renderer: render kernels + its part of the C ABI, gfx950) + csrc/ptmi_stacks.hip (the image-stack consumers:
+               denoise, fuse, accumulate, noise — their kernels and calls) + csrc/ptmi_bvh_device.hip (BVH build on the GPU, rocPRIM)
                + csrc/ptmi_host.cpp (host natives)
 ptmi.node    = csrc/ptmi_napi.c (raw N-API binding of include/ptmi.h for the Node host), if the
                Node headers are present.
@@ -40,17 +41,17 @@ def _run(cmd):
     return r.stdout
 
 
-SOURCES = ("ptmi.hip", "ptmi_bvh_device.hip", "ptmi_host.cpp")
+SOURCES = ("ptmi.hip", "ptmi_stacks.hip", "ptmi_bvh_device.hip", "ptmi_host.cpp")
 TESTHOOKS_LIB = os.path.join(PKG, "variants", "libptmi_testhooks.so")
 
 
 def _deps():
-    return [os.path.join(CSRC, f) for f in SOURCES + ("ptmi_dbuf.h", "ptmi_bvh_domain.h","ptmi_device.h", "ptmi_kernels.h", "ptmi_denoise_kernels.h", "ptmi_guided_kernels.h", "ptmi_fuse_kernels.h", "ptmi_accumulate_kernels.h", "ptmi_noise_kernels.h", "ptmi_tuning.h")] + [os.path.join(ROOT, "include", f) for f in ("ptmi.h", "ptmi_math.h", "ptmi_denoise.h", "ptmi_guided.h", "ptmi_fuse.h", "ptmi_accumulate.h", "ptmi_noise.h")]
+    return [os.path.join(CSRC, f) for f in SOURCES + ("ptmi_ctx.h", "ptmi_dbuf.h", "ptmi_bvh_domain.h","ptmi_device.h", "ptmi_kernels.h", "ptmi_denoise_kernels.h", "ptmi_guided_kernels.h", "ptmi_fuse_kernels.h", "ptmi_accumulate_kernels.h", "ptmi_noise_kernels.h", "ptmi_tuning.h")] + [os.path.join(ROOT, "include", f) for f in ("ptmi.h", "ptmi_math.h", "ptmi_denoise.h", "ptmi_guided.h", "ptmi_fuse.h", "ptmi_accumulate.h", "ptmi_noise.h")]
 
 
 def _link(out, units, csrc=None):
-    """units: [(source file name, extra flags, tag)].  One hipcc -c per translation unit, all at once (the three compile independently: ptmi.hip
-    is ~45 s of the 55 a single command takes), then one link.  Objects: webgpu-path-tracer_amd/build/ (not shipped).  `csrc`: another source directory."""
+    """units: [(source file name, extra flags, tag)].  One hipcc -c per translation unit, all at once (they compile independently: ptmi.hip,
+    with its ~150 render-kernel instances, is ~45 s of the 55 a single command takes — ptmi_stacks.hip a fifteenth of that), then one link.  Objects: webgpu-path-tracer_amd/build/ (not shipped).  `csrc`: another source directory."""
     from concurrent.futures import ThreadPoolExecutor
 
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -75,7 +76,7 @@ def build_testhooks(force=False):
     """The tests' own build of the library: -DPTMI_TEST_HOOKS compiles in the fault injection the product build does not carry
     (PTMI_TEST_ALLOC_LIMIT: device allocations above N bytes fail; PTMI_TEST_RCCL_FAIL=init|reduce|mid: that RCCL call reports an error) and
     PTMI_TEST_DENOISE_SCRATCH=<bytes>, which takes the place of the 1 GiB cap of the denoisers' scratch, so that a small stack goes through several view batches.
-    Only ptmi.hip differs; the tests load it next to the product library (ptmi.load_library(path=...))."""
+    ptmi.hip (the RCCL faults) and ptmi_stacks.hip (the scratch cap) read the macro, and every .hip unit through ptmi_dbuf.h (the allocation limit); the tests load it next to the product library (ptmi.load_library(path=...))."""
     if not force and _newer(TESTHOOKS_LIB, _deps()):
         return TESTHOOKS_LIB
     return _link(TESTHOOKS_LIB, [(src, ("-DPTMI_TEST_HOOKS",), "_testhooks") for src in SOURCES])
@@ -84,7 +85,8 @@ def build_testhooks(force=False):
 def build_variant(name, extra_flags, csrc=None):
     """A/B builds of the library with extra -D flags: webgpu-path-tracer_amd/variants/libptmi_<name>.so; run with PTMI_LIB=<path>.
     `csrc`: build another tree's sources (a csrc/ directory that finds its ../../include/ptmi.h), e.g. an earlier commit's (tools/views_probe.py)."""
-    return _link(os.path.join(PKG, "variants", "libptmi_%s.so" % name), [(src, tuple(extra_flags), "_" + name) for src in SOURCES], csrc=csrc)
+    units = [src for src in SOURCES if csrc is None or os.path.exists(os.path.join(csrc, src))]  # (an earlier commit's tree may have fewer units: ptmi_stacks.hip was part of ptmi.hip)
+    return _link(os.path.join(PKG, "variants", "libptmi_%s.so" % name), [(src, tuple(extra_flags), "_" + name) for src in units], csrc=csrc)
 
 
 def build_addon(force=False):

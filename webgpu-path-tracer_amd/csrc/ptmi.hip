@@ -1,5 +1,6 @@
-// ptmi.hip — libptmi.so: context management, scene upload/validation/digests, wavefront scheduling and
-// the C ABI of include/ptmi.h.  gfx950 (MI355X) only; build: see webgpu-path-tracer_amd/_build.py.
+// ptmi.hip — libptmi.so, the renderer: context management, scene upload/validation/digests, wavefront scheduling, the multi-device gather, the view and
+// feature stacks, and their part of the C ABI of include/ptmi.h.  The calls that consume the image stacks (denoise, fuse, accumulate, noise) are in
+// ptmi_stacks.hip; the two meet at ptmi_ctx.h.  gfx950 (MI355X) only; build: see webgpu-path-tracer_amd/_build.py.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types and prototypes only: librccl is loaded on first multi-device use (see Rccl below)
@@ -20,17 +21,8 @@
 #include <type_traits>
 #include <vector>
 
-#include "../../include/ptmi.h"
-#include "ptmi_dbuf.h"
+#include "ptmi_ctx.h"
 #include "ptmi_kernels.h"
-#include "ptmi_denoise_kernels.h"
-#include "ptmi_guided_kernels.h"
-#include "ptmi_fuse_kernels.h"
-#include "ptmi_accumulate_kernels.h"
-#include "ptmi_noise_kernels.h"
-#include "ptmi_tuning.h"
-
-using namespace ptmi;
 
 // csrc/ptmi_bvh_device.hip
 int ptmi_bvhdev_build_scene(void* stream, const float* d_tris, uint32_t n, const int32_t* h_meshes, int n_meshes, const float* h_xforms, int n_xforms, float* d_rows,
@@ -49,192 +41,7 @@ enum TimerTag { T_PRIMS = 0, T_SHADE = 1, T_GENERATE = 2, T_RENDER = 3, T_BVH = 
 
 }  // namespace
 
-// One persistent host thread per peer of a multi-device context: the calls that may block (allocation, the occasional queue-length
-// readback of a long render) run concurrently on all devices without starting a thread per call (ptmi_render_frame is per displayed frame).
-struct PeerWorker {
-  std::thread th;
-  std::mutex m;
-  std::condition_variable cv;
-  std::function<int()> job;
-  int result = 0;
-  bool has_job = false, done = false, quit = false;
-  void loop() {
-    std::unique_lock<std::mutex> lk(m);
-    for (;;) {
-      cv.wait(lk, [this] { return has_job || quit; });
-      if (quit) return;
-      std::function<int()> j = std::move(job);
-      has_job = false;
-      lk.unlock();
-      const int r = j();
-      lk.lock();
-      result = r;
-      done = true;
-      cv.notify_all();
-    }
-  }
-  void post(std::function<int()> j) {
-    std::lock_guard<std::mutex> lk(m);
-    if (!th.joinable()) th = std::thread([this] { loop(); });
-    job = std::move(j);
-    has_job = true;
-    done = false;
-    cv.notify_all();
-  }
-  int wait() {
-    std::unique_lock<std::mutex> lk(m);
-    cv.wait(lk, [this] { return done; });
-    return result;
-  }
-  ~PeerWorker() {
-    {
-      std::lock_guard<std::mutex> lk(m);
-      quit = true;
-      cv.notify_all();
-    }
-    if (th.joinable()) th.join();
-  }
-};
-
-// The context's stacks of W x H float4 images, one allocation per kind.  A row per kind: images per view, the noun and the making call of the error texts, and whether
-// the stack is derived from the view stack (it has that stack's size and goes with it), and whether its images lie plane by plane ([images per view][n] instead of
-// [n][images per view]).
-enum StackKind { STACK_NONE = -1, STACK_VIEWS = 0, STACK_FEATURES, STACK_DENOISED, STACK_FUSED, STACK_MOMENTS, STACK_ACCUMULATED, N_STACKS };  // (STACK_NONE: ImageRef's accumulation buffer)
-struct StackInfo {
-  uint32_t images_per_view;
-  const char *noun, *maker;
-  bool derived;
-  bool plane_major = false;
-};
-constexpr StackInfo kStackInfo[N_STACKS] = {
-    {1, "view stack", "ptmi_render_views", false},      // RGBA f32 sums
-    {3, "feature stack", "ptmi_render_aov", false},     // k_aov's three layers per view
-    {1, "denoised stack", "ptmi_denoise_views", true},  // RGBA f32 means
-    {1, "fused stack", "ptmi_fuse_views", true},        // RGBA f32 means
-    {1, "moment stack", "ptmi_render_views with ptmi_set_view_moments on", true},  // sums of squared frame colours, frame count in w
-    {3, "accumulated stack", "ptmi_accumulate_views", true, true},  // planes: RGBA f32 means; (D, n); (Q, v0)
-};
-struct Stack {
-  DBuf buf;
-  uint32_t n = 0;  // views
-};
-
-// (Tuning — the PTMI_* environment knobs, their domains and their parsing: ptmi_tuning.h)
-
-#ifndef PTMI_ONB_TABLE_DEFAULT
-#define PTMI_ONB_TABLE_DEFAULT 1  // (-DPTMI_ONB_TABLE_DEFAULT=0: an A/B build whose contexts start with the table of quad records off — bench.py never calls ptmi_set_onb_table)
-#endif
-struct ptmi_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  ptmi_params prm;
-  Tuning tun;
-  int num_cus = 256;
-
-  // host copies of the uploaded arrays (reference layouts)
-  std::vector<float> h_spheres, h_quads, h_xforms, h_mats, h_bvh;
-  size_t n_tris_uploaded = 0;  // the triangles go straight to the device (d_tris): the host never needs their values again
-  std::vector<int32_t> h_meshes;
-  bool scene_dirty = true;
-
-  DBuf d_quad_unit_n, d_quad_onb;  // k_quad_digest's two tables (DevScene)
-  bool onb_table = PTMI_ONB_TABLE_DEFAULT != 0;  // ptmi_set_onb_table
-  // ptmi_build_scene_bvh: the BVH rows (binding 9's layout) live on the device only — no host copy, pair64 made there too
-  DBuf d_bvh_rows;
-  bool bvh_on_device = false;
-  size_t bvh_dev_prims = 0;  // triangles the device-resident tree was built over
-  size_t bvh_dev_nodes = 0;  // its rows: 2 x triangles - 1 from the median builder, fewer from the SAH one (leaves of several triangles)
-  bool bvh_dev_sah = false;  // built by ptmi_build_scene_bvh_sah
-  bool bvh_dev_stale = false;  // triangles / meshes / transforms were uploaded after the build: its boxes and leaf order describe another scene
-  int bvh_dev_depth = 0;
-  // ... and what ptmi_refit_scene_bvh needs of the build (drop_refit_state releases it where the tree goes)
-  DBuf d_bvh_order;       // u32 per triangle: leaf position -> position in the caller's upload order
-  DBuf d_bvh_level_rows;  // u32 per row: the row ids grouped by level, root level first
-  std::vector<uint32_t> bvh_level_off;  // where each level starts in d_bvh_level_rows, and the total
-  bool tris_in_upload_order = true;     // d_tris as ptmi_upload(PTMI_BUF_TRIANGLES) left it; false: in the leaf order of d_bvh_order (a build or a refit put it there)
-  DBuf d_spheres, d_sphere_info, d_quads, d_quad_mat, d_tris, d_pretri, d_trinorm, d_meshes, d_xforms, d_mats, d_pairs, d_leaf_table;
-  DevScene S{};
-  int bvh_depth = 0;             // max number of inner nodes on a root-to-leaf path
-  bool has_unknown_material = false;
-  int material_classes = 0;      // distinct shade bins among the materials: k_shade sorts only when > 1
-  std::map<const void*, int> shade_blocks_per_cu;  // per k_shade instance (shade_kernel): resident 256-thread blocks per CU, asked once
-
-  int W = 0, H = 0;
-  DBuf d_fb_own;
-  float4* fb = nullptr;
-  size_t fb_bytes = 0;
-  // The image stacks (StackKind, kStackInfo): per kind one allocation of n x images-per-view images of W x H float4.  The denoised and fused stacks have the view stack's
-  // size and go with it (drop_stack).
-  Stack stacks[N_STACKS];
-  DBuf d_denoise_scratch;  // ptmi_denoise_views: three packed float4 images (d ping, d pong, n + z) per view of a batch (atrous_batch_views); ptmi_denoise_views_guided: and three f32 images (v ping, v pong, vg)
-  StagedTable view_rows;   // the last ptmi_render_views / ptmi_render_aov call's view table (ViewTab: kViewRow float4 per view)
-  StagedTable fuse_tab;    // the last ptmi_fuse_views / ptmi_accumulate_views call's table (kFuseRow float4 per view of the stack, then one byte per material; the *_frames calls: then one f32 per view, its frame count)
-  StagedTable denoise_tab; // the last ptmi_denoise_views_frames / ptmi_denoise_views_guided_frames call's frame counts: one f32 per view of the stack
-  bool view_moments = false;  // ptmi_set_view_moments: ptmi_render_views folds second moments into stacks[STACK_MOMENTS] too
-  DBuf d_noise_rec;           // ptmi_view_noise_stats: one record (kNoiseRecordBytes) per view of the call
-  int rank = 0, world = 1, tile = 64;
-
-  size_t path_cap = 0;
-  bool pixsum_alloc = false;
-  size_t slot_cap = 0;  // slots per queue buffer (paths + room for the holes k_shade's regions leave)
-  DBuf d_q0[2], d_q1[2], d_q2[2], d_tp[2], d_hm[2];  // slot-indexed live state and hit records, ping-pong
-  DBuf d_uv, d_acc, d_pixsum, d_touched, d_ctl, d_totals, d_scratch, d_spill, d_heads;
-  DBuf d_carry[2];  // Carry: the pools of saved traversal state, ping-pong like the queues
-  int ctl_cap = 0;
-
-  // Render-ahead of ptmi_render_frame (see there): per-frame colours of frames [frame0, frame0 + count) sit in d_acc,
-  // the first `next` of them are already in the framebuffer.
-  struct Ahead {
-    bool valid = false;
-    float view[16];
-    uint32_t frame0 = 0;
-    int count = 0, next = 0;
-    RenderConst rc;
-    uint32_t grid = 1;
-  } ahead;
-  bool have_last_frame = false;
-  uint32_t last_frame = 0;
-  float last_view[16];
-  int static_streak = 0;  // consecutive ptmi_render_frame calls with the same view, frame numbers +1, no reset
-  bool placement_pending = false;  // ensure_paths has just (re)allocated the queue arrays of a batch worth a placement search: render_batch runs it
-  bool interactive = false;  // inside ptmi_render_frame: its batches grow 8 -> 64 frames while the user watches — no placement search (40 ms each)
-  int ahead_batch = 8;
-
-  // Multi-device context (ptmi_create_multi): this object is local device 0, `peers` are the contexts of local devices
-  // 1..n-1 (plain single-device contexts).  The caller's shard (ptmi_set_shard) is subdivided among the n of them.
-  bool multi = false;
-  bool shares_device = false;  // another shard of the same multi-device context lives on this GPU
-  std::vector<ptmi_ctx*> peers;
-  std::unique_ptr<PeerWorker> worker;  // a peer's host thread (created on first use)
-  bool fb_holds_pixels = false;  // (the root's field) a render or ptmi_write_framebuffer since the last clear / resize: ptmi_set_shard on a multi-device context asks
-  int proc_rank = 0, proc_world = 1, proc_tile = 4032;  // (63 waves of pixels; not 4096: see dist.py — a rank's pixel count must not be a large power of two)
-  bool use_rccl = false;
-  bool use_gather = false;        // the default collective of a multi-device context: every device's OWN tiles are copied into place on the root (1/N of the bytes, no arithmetic)
-  bool root_reads = false;        // (a peer's field) the root device can read this device's memory directly: peer access is on, or it is the same GPU
-  uint64_t gather_bytes = 0;      // bytes that crossed between GPUs in the last tile gather
-  int test_rccl_fail = 0;  // -DPTMI_TEST_HOOKS builds: PTMI_TEST_RCCL_FAIL=init|reduce|mid read at ptmi_create_multi — pretend ncclCommInitAll (1) / ncclGroupStart (2) failed, or
-                           // a call in the middle of the reduce's group after the first ncclReduce was enqueued (3); 0 in the product build
-  std::vector<ncclComm_t> comms;  // one per local device, same order as {this, peers...}
-  int reduce_mode = 0;            // ptmi_stats.reduce_mode: how the multi-device sum runs (0 single device, 1 RCCL, 2 peer copies + add, 3 the same as a FALLBACK)
-  int peer_links = 0;             // directed device pairs (root <-> peer) with peer access enabled
-  std::string reduce_info;        // ptmi_reduce_info
-  DBuf d_fb_gather, d_fb_stage;   // on this device: the sum of all local accumulation buffers / a peer's buffer in transit
-
-  bool batch_enqueued = false;  // render_batch: has anything been put on the stream yet? (a failure before that point may be retried)
-  bool counters = false;
-  int timing = 0;  // 0 off, 1 every kernel, 2 only k_bvh (the dominant kernel) — see ptmi_set_timing
-  ptmi_stats stats{};
-  std::vector<hipEvent_t> ev_pool;
-  struct Span {
-    hipEvent_t a, b;
-    int tag;
-  };
-  std::vector<Span> spans;
-};
-
-namespace {
-
+// ---- what ptmi_stacks.hip calls too (declared in ptmi_ctx.h); the rest of this unit's helpers are private to it ----
 int fail(ptmi_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
   else g_create_error = msg;
@@ -248,19 +55,11 @@ std::vector<ptmi_ctx*> local_devices(ptmi_ctx* c) {
   return v;
 }
 
-#define HIP_TRY(c, expr)                                                                              \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess)                                                                             \
-      return fail((c), _e == hipErrorOutOfMemory ? PTMI_ERR_NO_MEMORY : PTMI_ERR_DEVICE,              \
-                  std::string(#expr) + ": " + hipGetErrorString(_e));                                 \
-  } while (0)
-
 // ---- the image stacks (StackKind): what their calls share ----
-size_t stack_bytes(const ptmi_ctx* c, StackKind k, uint32_t n) { return (size_t)n * kStackInfo[k].images_per_view * (size_t)c->W * (size_t)c->H * 16; }
+static size_t stack_bytes(const ptmi_ctx* c, StackKind k, uint32_t n) { return (size_t)n * kStackInfo[k].images_per_view * (size_t)c->W * (size_t)c->H * 16; }
 
 // One device's stack `k` goes — and with the view stack those derived from it, which have its size: the one place that says so.
-void drop_stack(ptmi_ctx* q, StackKind k) {
+static void drop_stack(ptmi_ctx* q, StackKind k) {
   q->stacks[k].buf.release();
   q->stacks[k].n = 0;
   if (k == STACK_VIEWS)
@@ -292,6 +91,46 @@ int commit_stack(ptmi_ctx* c, StackKind k, uint32_t n, DBuf* fresh) {
   return PTMI_OK;
 }
 
+void drain_spans(ptmi_ctx* c) {  // call after the stream is idle
+  for (auto& s : c->spans) {
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) {
+      if (s.tag == T_PRIMS) c->stats.prims_ms += ms, c->stats.intersect_ms += ms;
+      else if (s.tag == T_BVH) c->stats.bvh_ms += ms, c->stats.intersect_ms += ms;
+      else if (s.tag == T_SHADE) c->stats.shade_ms += ms;
+      else if (s.tag == T_GENERATE) c->stats.generate_ms += ms, c->stats.other_ms += ms;
+      else if (s.tag == T_ACCUM) c->stats.accumulate_ms += ms, c->stats.other_ms += ms;
+      else if (s.tag == T_TAIL) c->stats.tail_ms += ms;
+      else c->stats.render_ms += ms;
+    }
+    c->ev_pool.push_back(s.a);
+    c->ev_pool.push_back(s.b);
+  }
+  c->spans.clear();
+}
+
+uint32_t count_local(uint32_t npix, int rank, int world, int tile) {
+  uint64_t n = 0;
+  uint64_t ntiles = ((uint64_t)npix + tile - 1) / tile;
+  for (uint64_t t = (uint64_t)rank; t < ntiles; t += (uint64_t)world) {
+    uint64_t b = t * tile, e = std::min<uint64_t>(b + tile, npix);
+    n += e - b;
+  }
+  return (uint32_t)n;
+}
+
+// totals[15]: a k_shade block found the next queue full and dropped paths (cannot happen with ensure_paths' sizing).  Every
+// synchronising call reports it, so that a damaged image is never handed out as a good one.  Call with the stream idle.
+int check_queue_overflow(ptmi_ctx* c) {
+  if (!c->d_totals.p) return PTMI_OK;
+  unsigned long long flag = 0;
+  HIP_TRY(c, hipMemcpy(&flag, c->d_totals.as<unsigned long long>() + 15, sizeof flag, hipMemcpyDeviceToHost));
+  if (flag) return fail(c, PTMI_ERR_STATE, "internal: a step's queue outgrew its buffer (paths were dropped); the framebuffer is incomplete");
+  return PTMI_OK;
+}
+
+namespace {
+
 hipEvent_t get_event(ptmi_ctx* c) {
   if (!c->ev_pool.empty()) {
     hipEvent_t e = c->ev_pool.back();
@@ -322,23 +161,6 @@ struct ScopedSpan {  // records a begin/end event pair around launches when timi
     c->spans.push_back(s);
   }
 };
-void drain_spans(ptmi_ctx* c) {  // call after the stream is idle
-  for (auto& s : c->spans) {
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) {
-      if (s.tag == T_PRIMS) c->stats.prims_ms += ms, c->stats.intersect_ms += ms;
-      else if (s.tag == T_BVH) c->stats.bvh_ms += ms, c->stats.intersect_ms += ms;
-      else if (s.tag == T_SHADE) c->stats.shade_ms += ms;
-      else if (s.tag == T_GENERATE) c->stats.generate_ms += ms, c->stats.other_ms += ms;
-      else if (s.tag == T_ACCUM) c->stats.accumulate_ms += ms, c->stats.other_ms += ms;
-      else if (s.tag == T_TAIL) c->stats.tail_ms += ms;
-      else c->stats.render_ms += ms;
-    }
-    c->ev_pool.push_back(s.a);
-    c->ev_pool.push_back(s.b);
-  }
-  c->spans.clear();
-}
 
 size_t stride_of(int which) {
   switch (which) {
@@ -623,16 +445,6 @@ int prepare_scene(ptmi_ctx* c) {
   S.onb_tab = onb_tab_of(c, n_quad);
   c->scene_dirty = false;
   return PTMI_OK;
-}
-
-uint32_t count_local(uint32_t npix, int rank, int world, int tile) {
-  uint64_t n = 0;
-  uint64_t ntiles = ((uint64_t)npix + tile - 1) / tile;
-  for (uint64_t t = (uint64_t)rank; t < ntiles; t += (uint64_t)world) {
-    uint64_t b = t * tile, e = std::min<uint64_t>(b + tile, npix);
-    n += e - b;
-  }
-  return (uint32_t)n;
 }
 
 Paths paths_of(ptmi_ctx* c, int step, bool with_pixsum);
@@ -1167,16 +979,6 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   return PTMI_OK;
 }
 
-// totals[15]: a k_shade block found the next queue full and dropped paths (cannot happen with ensure_paths' sizing).  Every
-// synchronising call reports it, so that a damaged image is never handed out as a good one.  Call with the stream idle.
-int check_queue_overflow(ptmi_ctx* c) {
-  if (!c->d_totals.p) return PTMI_OK;
-  unsigned long long flag = 0;
-  HIP_TRY(c, hipMemcpy(&flag, c->d_totals.as<unsigned long long>() + 15, sizeof flag, hipMemcpyDeviceToHost));
-  if (flag) return fail(c, PTMI_ERR_STATE, "internal: a step's queue outgrew its buffer (paths were dropped); the framebuffer is incomplete");
-  return PTMI_OK;
-}
-
 int check_renderable(ptmi_ctx* c) {
   if (!c->fb || c->W <= 0) return fail(c, PTMI_ERR_STATE, "no framebuffer: call ptmi_resize first");
   const ptmi_params& p = c->prm;
@@ -1249,31 +1051,6 @@ bool rccl_loaded() {
     ncclResult_t _r = (expr);                                                                                        \
     if (_r != ncclSuccess) return fail((c), PTMI_ERR_DEVICE, std::string(#expr) + ": " + g_rccl.GetErrorString(_r)); \
   } while (0)
-
-// fn(ctx) on the context itself and on every peer; `parallel` = one host thread per device, so that calls which block
-// (allocation, the occasional queue-length readback of a long render) do not serialise the GPUs.
-template <class F>
-int on_all_devices(ptmi_ctx* c, F fn, bool parallel = false) {
-  const std::vector<ptmi_ctx*> devs = local_devices(c);
-  std::vector<int> rcs(devs.size(), PTMI_OK);
-  if (parallel) {
-    for (ptmi_ctx* q : c->peers) {
-      if (!q->worker) q->worker = std::make_unique<PeerWorker>();
-      q->worker->post([&fn, q] { return fn(q); });
-    }
-    rcs[0] = fn(c);
-    for (size_t i = 1; i < devs.size(); i++) rcs[i] = devs[i]->worker->wait();
-  } else {
-    for (size_t i = 0; i < devs.size(); i++)
-      if ((rcs[i] = fn(devs[i]))) break;  // stop at the first device that fails
-  }
-  for (size_t i = 1; i < devs.size(); i++)
-    if (rcs[i] && !rcs[0]) {
-      c->err = "local device #" + std::to_string(i) + " (GPU " + std::to_string(devs[i]->device) + "): " + devs[i]->err;
-      return rcs[i];
-    }
-  return rcs[0];
-}
 
 // One device's own tiles (ptmi_set_shard: pixels p with (p / tile) % world == rank) copied from its accumulation buffer into place in the root's gather buffer.  `src` may be
 // the peer's memory itself (peer access over xGMI: the kernel reads exactly the bytes it needs, 1/N of the buffer) or a staged copy of it.
@@ -1456,6 +1233,77 @@ uint32_t u32_of_f32(float f) {  // WGSL u32(f32): truncation, clamped to the u32
 }
 
 }  // namespace
+
+// ptmi_read_framebuffer / ptmi_read_view / ptmi_read_aov: the image, gathered from the devices of a multi-device context, copied to the host
+static int read_image(ptmi_ctx* c, ImageRef img, float* dst, size_t bytes) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  float4* src = nullptr;
+  int r = gather_framebuffer(c, &src, img);  // multi-device: the one reduce of the render (RCCL over xGMI); else the image itself
+  if (r) return r;
+  HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  drain_spans(c);
+  return on_all_devices(c, [](ptmi_ctx* q) -> int {
+    HIP_TRY(q, hipSetDevice(q->device));
+    drain_spans(q);
+    return check_queue_overflow(q);
+  });
+}
+// ptmi_resolve_rgba8 / ptmi_resolve_view_rgba8: the display pass on the gathered image
+static int resolve_image(ptmi_ctx* c, ImageRef img, float frame_num, uint8_t* dst, size_t bytes) {
+  const size_t npix = (size_t)c->W * c->H;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, c->d_scratch.ensure(bytes));
+  float4* src = nullptr;
+  int gr = gather_framebuffer(c, &src, img);
+  if (gr) return gr;
+  hipLaunchKernelGGL(k_resolve_rgba8, dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, src, (uint32_t)npix, frame_num,
+                     c->d_scratch.as<uchar4>());
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(dst, c->d_scratch.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return PTMI_OK;
+}
+
+// What the exported calls on a stack come to after their own argument checks.  The order of the checks decides which status a caller sees: a null argument,
+// (the device pointer of a stack that exists once per GPU: a multi-device context,) the stack, the view, the layer, the byte count.
+int read_stack(ptmi_ctx* c, StackKind k, const char* who, uint32_t view, int layer, float* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (int r = check_stack(c, k, who, view)) return r;
+  const int layers = (int)kStackInfo[k].images_per_view;
+  if (layer < 0 || layer >= layers) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": layer " + std::to_string(layer) + " of " + std::to_string(layers));
+  if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": bytes != W*H*16");
+  const size_t index = kStackInfo[k].plane_major ? (size_t)layer * c->stacks[k].n + (size_t)view : (size_t)view * layers + (size_t)layer;
+  return read_image(c, ImageRef{k, index}, dst, bytes);
+}
+int resolve_stack(ptmi_ctx* c, StackKind k, const char* who, uint32_t view, float frame_num, uint8_t* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (int r = check_stack(c, k, who, view)) return r;
+  if (bytes != (size_t)c->W * c->H * 4) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": bytes != W*H*4");
+  return resolve_image(c, ImageRef{k, view}, frame_num, dst, bytes);
+}
+// `read_fn`: the call a multi-device context is sent to instead; nullptr for the stacks that only single-device contexts have
+int stack_device_ptr(ptmi_ctx* c, StackKind k, const char* who, const char* read_fn, void** p, size_t* bytes, uint32_t* n_views) {
+  if (!c || !p) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (read_fn && !c->peers.empty()) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a multi-device context has one stack per GPU; use " + read_fn);
+  if (int r = check_stack(c, k, who, 0)) return r;
+  *p = c->stacks[k].buf.p;
+  if (bytes) *bytes = stack_bytes(c, k, c->stacks[k].n);
+  if (n_views) *n_views = c->stacks[k].n;
+  return PTMI_OK;
+}
+// The stack goes on every device, and what only it needed: the filter's scratch with the denoised stack, the table with the fused one (and see drop_stack).
+int release_stack(ptmi_ctx* c, StackKind k) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  return on_all_devices(c, [k](ptmi_ctx* q) -> int {
+    HIP_TRY(q, hipSetDevice(q->device));
+    HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still read or write a stack that is about to go
+    drop_stack(q, k);
+    if (k == STACK_DENOISED) q->d_denoise_scratch.release(), q->denoise_tab.dev.release();
+    if (k == STACK_FUSED || k == STACK_ACCUMULATED) q->fuse_tab.dev.release();  // (every call that reads the table stages it again)
+    return PTMI_OK;
+  });
+}
 
 // for the other translation units of the library (ptmi_bvh_device.hip)
 int ptmi_ctx_set_device(ptmi_ctx* c) {
@@ -2184,77 +2032,6 @@ int ptmi_render_views_frames(ptmi_ctx* c, const float* views16, uint32_t n_views
   return on_all_devices(c, [=](ptmi_ctx* q) { return render_views_one(q, views16, n_views, 0u, 0u, reset, &vf); }, true);
 }
 
-// ptmi_read_framebuffer / ptmi_read_view / ptmi_read_aov: the image, gathered from the devices of a multi-device context, copied to the host
-static int read_image(ptmi_ctx* c, ImageRef img, float* dst, size_t bytes) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  float4* src = nullptr;
-  int r = gather_framebuffer(c, &src, img);  // multi-device: the one reduce of the render (RCCL over xGMI); else the image itself
-  if (r) return r;
-  HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  drain_spans(c);
-  return on_all_devices(c, [](ptmi_ctx* q) -> int {
-    HIP_TRY(q, hipSetDevice(q->device));
-    drain_spans(q);
-    return check_queue_overflow(q);
-  });
-}
-// ptmi_resolve_rgba8 / ptmi_resolve_view_rgba8: the display pass on the gathered image
-static int resolve_image(ptmi_ctx* c, ImageRef img, float frame_num, uint8_t* dst, size_t bytes) {
-  const size_t npix = (size_t)c->W * c->H;
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, c->d_scratch.ensure(bytes));
-  float4* src = nullptr;
-  int gr = gather_framebuffer(c, &src, img);
-  if (gr) return gr;
-  hipLaunchKernelGGL(k_resolve_rgba8, dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, src, (uint32_t)npix, frame_num,
-                     c->d_scratch.as<uchar4>());
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(dst, c->d_scratch.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return PTMI_OK;
-}
-
-// What the exported calls on a stack come to after their own argument checks.  The order of the checks decides which status a caller sees: a null argument,
-// (the device pointer of a stack that exists once per GPU: a multi-device context,) the stack, the view, the layer, the byte count.
-static int read_stack(ptmi_ctx* c, StackKind k, const char* who, uint32_t view, int layer, float* dst, size_t bytes) {
-  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  if (int r = check_stack(c, k, who, view)) return r;
-  const int layers = (int)kStackInfo[k].images_per_view;
-  if (layer < 0 || layer >= layers) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": layer " + std::to_string(layer) + " of " + std::to_string(layers));
-  if (bytes != (size_t)c->W * c->H * 16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": bytes != W*H*16");
-  const size_t index = kStackInfo[k].plane_major ? (size_t)layer * c->stacks[k].n + (size_t)view : (size_t)view * layers + (size_t)layer;
-  return read_image(c, ImageRef{k, index}, dst, bytes);
-}
-static int resolve_stack(ptmi_ctx* c, StackKind k, const char* who, uint32_t view, float frame_num, uint8_t* dst, size_t bytes) {
-  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  if (int r = check_stack(c, k, who, view)) return r;
-  if (bytes != (size_t)c->W * c->H * 4) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": bytes != W*H*4");
-  return resolve_image(c, ImageRef{k, view}, frame_num, dst, bytes);
-}
-// `read_fn`: the call a multi-device context is sent to instead; nullptr for the stacks that only single-device contexts have
-static int stack_device_ptr(ptmi_ctx* c, StackKind k, const char* who, const char* read_fn, void** p, size_t* bytes, uint32_t* n_views) {
-  if (!c || !p) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  if (read_fn && !c->peers.empty()) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a multi-device context has one stack per GPU; use " + read_fn);
-  if (int r = check_stack(c, k, who, 0)) return r;
-  *p = c->stacks[k].buf.p;
-  if (bytes) *bytes = stack_bytes(c, k, c->stacks[k].n);
-  if (n_views) *n_views = c->stacks[k].n;
-  return PTMI_OK;
-}
-// The stack goes on every device, and what only it needed: the filter's scratch with the denoised stack, the table with the fused one (and see drop_stack).
-static int release_stack(ptmi_ctx* c, StackKind k) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  return on_all_devices(c, [k](ptmi_ctx* q) -> int {
-    HIP_TRY(q, hipSetDevice(q->device));
-    HIP_TRY(q, hipStreamSynchronize(q->stream));  // nothing may still read or write a stack that is about to go
-    drop_stack(q, k);
-    if (k == STACK_DENOISED) q->d_denoise_scratch.release(), q->denoise_tab.dev.release();
-    if (k == STACK_FUSED || k == STACK_ACCUMULATED) q->fuse_tab.dev.release();  // (every call that reads the table stages it again)
-    return PTMI_OK;
-  });
-}
-
 int ptmi_read_view(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_VIEWS, "ptmi_read_view", view, 0, dst, bytes); }
 int ptmi_resolve_view_rgba8(ptmi_ctx* c, uint32_t view, float frame_num, uint8_t* dst, size_t bytes) {
   return resolve_stack(c, STACK_VIEWS, "ptmi_resolve_view_rgba8", view, frame_num, dst, bytes);
@@ -2336,852 +2113,6 @@ int ptmi_camera_rays(ptmi_ctx* c, const float* view16, uint32_t frame, float* ra
   HIP_TRY(c, hipMemcpyAsync(rays6, d_rays, n * 24, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(rng_out, d_rng, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return PTMI_OK;
-}
-
-// ---- the denoised stack: the plain filter (ptmi_denoise_views, ptmi_denoise_images) and the variance-guided one (ptmi_denoise_views_guided, ptmi_denoise_images_guided) ----
-// (the default params and ptmi_denoise_reference / ptmi_denoise_guided_reference need no GPU: ptmi_host.cpp)
-// Views per batch of either filter: its scratch is held to 1 GiB (plain: 10 views at 1080p, guided: 8) so that a call on a large stack does not need another full
-// copy of it; the views of a batch go through every level in one launch.  Both filters use the same scratch buffer.
-// The cap itself: a constant in the product build, so that it folds into the divisions below; a -DPTMI_TEST_HOOKS build reads PTMI_TEST_DENOISE_SCRATCH=<bytes> at
-// every call, as ptmi_dbuf.h reads PTMI_TEST_ALLOC_LIMIT, so that a test can have several batches on a small stack.
-static inline size_t denoise_scratch_cap() {
-#ifdef PTMI_TEST_HOOKS
-  if (const char* cap = getenv("PTMI_TEST_DENOISE_SCRATCH")) return (size_t)strtoull(cap, nullptr, 10);
-#endif
-  return (size_t)1 << 30;
-}
-// Scratch bytes per pixel of a view of the batch
-constexpr size_t kDenoiseScratchBytes = 48;  // the plain filter: three packed float4 images (d ping, d pong, n + z)
-constexpr size_t kGuidedScratchBytes = 60;   // the guided filter: those and three f32 images (v ping, v pong, vg)
-static uint32_t atrous_batch_views(size_t npix, uint32_t n, size_t bytes_per_pixel) {
-  return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, denoise_scratch_cap() / (npix * bytes_per_pixel)));
-}
-static size_t atrous_scratch_bytes(size_t npix, uint32_t n, size_t bytes_per_pixel) { return (size_t)atrous_batch_views(npix, n, bytes_per_pixel) * npix * bytes_per_pixel; }
-
-// What the guided filter has beside the plain one's operands: moments [n][H][W] float4 sums, var_out [n][H][W] f32 or nullptr
-struct AtrousGuide {
-  const float4* moments;
-  float* var_out;
-  ptmg_consts kg;
-  int min_frames;
-  const float4* given = nullptr;  // plane 2 of an accumulated stack, [n][H][W] float4: its w is v0 where it is not NaN (k_accumulated_variance); `moments` is then not read
-};
-
-// Either filter on device arrays: colour [n][H][W] float4 sums, layers [n][3][H][W] float4, out [n][H][W] float4; G = nullptr: the plain filter.  c->d_denoise_scratch
-// holds atrous_scratch_bytes already: nothing here allocates.  Per batch one k_denoise_prepare and one level kernel per level, the last of which writes `out`; the
-// guided filter also one k_guided_variance, per level one k_guided_blur (with a luminance term only: the blur feeds nothing else), and its last level writes `var_out`.
-// frames: nullptr, or the device table of the views' own divisors, one f32 per view, at the call's first view (F is then not read): the prepare pass and the last level
-// are then the *_frames entries, which index it by the batch's first view + the view of the batch.
-static int atrous_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, uint32_t n, int W, int H, float F, const ptmi_denoise_params& P, const AtrousGuide* G,
-                          const float* frames = nullptr) {
-  const size_t npix = (size_t)W * (size_t)H;
-  const uint32_t B = atrous_batch_views(npix, n, G ? kGuidedScratchBytes : kDenoiseScratchBytes);
-  float4* d[2] = {c->d_denoise_scratch.as<float4>(), c->d_denoise_scratch.as<float4>() + (size_t)B * npix};
-  float4* g = c->d_denoise_scratch.as<float4>() + 2 * (size_t)B * npix;
-  float *v[2] = {nullptr, nullptr}, *vg = nullptr;  // the guided filter's part of the scratch
-  if (G) {
-    float* f = reinterpret_cast<float*>(c->d_denoise_scratch.as<float4>() + 3 * (size_t)B * npix);
-    v[0] = f, v[1] = f + (size_t)B * npix, vg = f + 2 * (size_t)B * npix;
-  }
-  for (uint32_t v0 = 0; v0 < n; v0 += B) {
-    const uint32_t nv = std::min(B, n - v0);
-    const float4* col = colour + (size_t)v0 * npix;
-    const float4* lay = layers + (size_t)v0 * 3 * npix;
-    const size_t items = (size_t)nv * npix;
-    const unsigned pgrid = (unsigned)std::min<size_t>((items + kBlock - 1) / kBlock, (size_t)c->num_cus * 32);
-    if (frames) hipLaunchKernelGGL(k_denoise_prepare_frames, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, frames + v0, P.albedo_floor, d[0], g);
-    else hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, F, P.albedo_floor, d[0], g);
-    HIP_TRY(c, hipGetLastError());
-    const dim3 tgrid((unsigned)((W + kDenoiseTX - 1) / kDenoiseTX), (unsigned)((H + kGuidedTY - 1) / kGuidedTY), nv);
-    if (G && G->given) {
-      hipLaunchKernelGGL(k_accumulated_variance, tgrid, dim3(kBlock), 0, c->stream, d[0], G->given + (size_t)v0 * npix, W, H, v[0]);
-      HIP_TRY(c, hipGetLastError());
-    } else if (G) {
-      hipLaunchKernelGGL(k_guided_variance, tgrid, dim3(kBlock), 0, c->stream, d[0], col, G->moments + (size_t)v0 * npix, lay, W, H, P.albedo_floor, G->min_frames, v[0]);
-      HIP_TRY(c, hipGetLastError());
-    }
-    for (int l = 0; l < P.levels; l++) {
-      const int step = 1 << l, ty = step >= 32 ? 4 : 8;
-      const bool last = l == P.levels - 1;
-      const ptmd_consts k = ptmd_level_consts(P.sigma_normal, P.sigma_depth, P.sigma_colour, P.albedo_floor, l);
-      const dim3 grid((unsigned)((W + kDenoiseTX - 1) / kDenoiseTX), (unsigned)(((H + step * ty - 1) / (step * ty)) * step), nv);
-      const size_t lds = (size_t)(ty + 4) * (kDenoiseTX + 4 * step) * (2 * sizeof(float4) + (G ? sizeof(float2) : 0));  // at most (step 16 and 32) 48 KB, guided 60 KB
-      float4* dout = last ? out + (size_t)v0 * npix : d[(l + 1) & 1];
-      if (G) {
-        if (G->kg.luma) {
-          hipLaunchKernelGGL(k_guided_blur, tgrid, dim3(kBlock), 0, c->stream, d[l & 1], v[l & 1], W, H, vg);
-          HIP_TRY(c, hipGetLastError());
-        }
-        float* vout = !last ? v[(l + 1) & 1] : G->var_out ? G->var_out + (size_t)v0 * npix : nullptr;
-        if (last && frames)
-          hipLaunchKernelGGL(k_guided_level_frames, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, dout, vout, col, lay, W, H, step, ty, k, G->kg, frames + v0);
-        else
-          hipLaunchKernelGGL(last ? k_guided_level<true> : k_guided_level<false>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, dout, vout, col, lay, W, H, step, ty, k,
-                             G->kg, F);
-      } else if (last && frames) {
-        hipLaunchKernelGGL(k_denoise_level_frames, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, dout, col, lay, W, H, step, ty, k, frames + v0);
-      } else {
-        hipLaunchKernelGGL(last ? k_denoise_level<true> : k_denoise_level<false>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, dout, col, lay, W, H, step, ty, k, F);
-      }
-      HIP_TRY(c, hipGetLastError());
-    }
-  }
-  return PTMI_OK;
-}
-
-// What the calls on whole image stacks check first, in this order: a context that deals an image's pixels to several devices or processes cannot run them (`what` such a
-// context keeps on `where` GPUs: the words of the call's refusal); the call's own params (`need`: nullptr, or what they have to be); frame_num where the call uses it.
-static int check_stack_call(ptmi_ctx* c, const char* who, const char* what, const char* where, const char* need, bool need_frames, float frame_num) {
-  if (!c->peers.empty() || c->multi) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a multi-device context keeps " + what + " on " + where + " GPUs");
-  if (c->world > 1) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a sharded context (ptmi_set_shard) keeps " + what + " in " + where + " processes");
-  if (need) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need " + need);
-  if (need_frames && (!(frame_num > 0.0f) || !ptmd_finite(frame_num))) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": frame_num must be finite and > 0");
-  return PTMI_OK;
-}
-
-// The shape of the host arrays of a *_images call
-static int check_image_size(ptmi_ctx* c, const char* who, int w, int h, uint32_t n_images) {
-  if (w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need w, h, n_images >= 1 and w * h < 2^31");
-  return PTMI_OK;
-}
-
-// Views [first_view, first_view + n_views) of a stack of n
-static int check_view_range(ptmi_ctx* c, const char* who, uint32_t first_view, uint32_t n_views, uint32_t n) {
-  if (n_views == 0 || first_view >= n || n_views > n - first_view)
-    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": views [" + std::to_string(first_view) + ", " + std::to_string((uint64_t)first_view + n_views) + ") of " + std::to_string(n));
-  return PTMI_OK;
-}
-
-// The *_frames calls: entries [lo, hi) of frame_nums are the ones the call reads, and each has to be a divisor — finite and > 0; the others may hold anything.
-static int check_frame_nums(ptmi_ctx* c, const char* who, const float* frame_nums, uint32_t lo, uint32_t hi) {
-  if (!frame_nums) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null frame_nums");
-  for (uint32_t v = lo; v < hi; v++)
-    if (!(frame_nums[v] > 0.0f) || !ptmd_finite(frame_nums[v]))
-      return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": frame_nums[" + std::to_string(v) + "] must be finite and > 0: view " + std::to_string(v) + " is read by this call");
-  return PTMI_OK;
-}
-
-// A device copy of `n` frame counts for a *_images_frames call, which is synchronous: `buf` is the call's own; the copy is enqueued by the caller (send_frame_nums).
-static int send_frame_nums(ptmi_ctx* c, DBuf& buf, const float* frame_nums, uint32_t n) {
-  HIP_TRY(c, hipMemcpyAsync(buf.p, frame_nums, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  return PTMI_OK;
-}
-
-static int denoise_check_args(ptmi_ctx* c, const char* who, const ptmi_denoise_params* params, float frame_num, ptmi_denoise_params* P) {
-  if (params) *P = *params;
-  else ptmi_default_denoise_params(P);
-  const bool ok = ptmd_params_ok(P->levels, P->sigma_normal, P->sigma_depth, P->sigma_colour, P->albedo_floor);
-  return check_stack_call(c, who, "a pixel's neighbours", "other", ok ? nullptr : "levels in 1..6, sigma_normal, sigma_depth and albedo_floor > 0, sigma_colour >= 0, all finite", true, frame_num);
-}
-
-// What ptmi_denoise_views and ptmi_fuse_views ask of their inputs: a view stack and a feature stack of the same number of views, (the denoised stack too where it is
-// the source,) and a range of views inside them.
-static int check_source_stacks(ptmi_ctx* c, const char* who, bool need_denoised, uint32_t first_view, uint32_t n_views) {
-  if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
-  if (int r = check_stack(c, STACK_FEATURES, who, 0)) return r;
-  const uint32_t n = c->stacks[STACK_VIEWS].n, na = c->stacks[STACK_FEATURES].n;
-  if (n != na) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the view stack has " + std::to_string(n) + " views, the feature stack " + std::to_string(na));
-  if (need_denoised && c->stacks[STACK_DENOISED].n != n) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no denoised stack: call ptmi_denoise_views first");
-  return check_view_range(c, who, first_view, n_views, n);
-}
-
-// Either filter from the context's stacks into its denoised stack, the arguments checked.  The stack and the scratch, everything that can fail for want of memory, come
-// before anything is enqueued.  G: as atrous_enqueue's, its `moments` (or, with `accumulated`, its `given`) filled in here.  accumulated: the colour is plane 0 of the
-// accumulated stack, not the view stack.
-// frame_nums: nullptr, or the stack's frame counts, one per view (checked): they go up through c->denoise_tab, and frame_num is not read.
-static int atrous_views(ptmi_ctx* c, const ptmi_denoise_params& P, AtrousGuide* G, float frame_num, uint32_t first_view, uint32_t n_views, bool accumulated = false,
-                        const float* frame_nums = nullptr) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  (void)hipGetLastError();
-  const size_t npix = (size_t)c->W * (size_t)c->H;
-  const StackKind source = accumulated ? STACK_ACCUMULATED : STACK_VIEWS;
-  const uint32_t n_stack = c->stacks[source].n;
-  DBuf stack;
-  if (int r = reserve_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
-  HIP_TRY(c, c->d_denoise_scratch.ensure_idle(atrous_scratch_bytes(npix, n_views, G ? kGuidedScratchBytes : kDenoiseScratchBytes), c->stream));
-  if (frame_nums) {
-    void* staged = nullptr;
-    HIP_TRY(c, c->denoise_tab.stage((size_t)n_stack * 4, c->stream, &staged));
-    memcpy(staged, frame_nums, (size_t)n_stack * 4);
-  }
-  if (int r = commit_stack(c, STACK_DENOISED, n_stack, &stack)) return r;
-  if (frame_nums) HIP_TRY(c, c->denoise_tab.send((size_t)n_stack * 4, c->stream));
-  if (G && accumulated) G->given = c->stacks[STACK_ACCUMULATED].buf.as<float4>() + ((size_t)2 * n_stack + first_view) * npix;
-  else if (G) G->moments = c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix;
-  return atrous_enqueue(c, c->stacks[source].buf.as<float4>() + (size_t)first_view * npix, c->stacks[STACK_FEATURES].buf.as<float4>() + (size_t)first_view * 3 * npix,
-                        c->stacks[STACK_DENOISED].buf.as<float4>() + (size_t)first_view * npix, n_views, c->W, c->H, frame_num, P, G,
-                        frame_nums ? c->denoise_tab.dev.as<float>() + first_view : nullptr);
-}
-
-// ptmi_denoise_views (per_view false: frame_num) and ptmi_denoise_views_frames (per_view: frame_nums, one per view of the stack)
-static int denoise_views(ptmi_ctx* c, const char* who, const ptmi_denoise_params* params, float frame_num, const float* frame_nums, bool per_view, uint32_t first_view, uint32_t n_views) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  ptmi_denoise_params P;
-  if (int r = denoise_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
-  if (int r = check_source_stacks(c, who, false, first_view, n_views)) return r;
-  if (per_view)
-    if (int r = check_frame_nums(c, who, frame_nums, first_view, first_view + n_views)) return r;
-  return atrous_views(c, P, nullptr, frame_num, first_view, n_views, false, per_view ? frame_nums : nullptr);
-}
-int ptmi_denoise_views(ptmi_ctx* c, const ptmi_denoise_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
-  return denoise_views(c, "ptmi_denoise_views", params, frame_num, nullptr, false, first_view, n_views);
-}
-int ptmi_denoise_views_frames(ptmi_ctx* c, const ptmi_denoise_params* params, const float* frame_nums, uint32_t first_view, uint32_t n_views) {
-  return denoise_views(c, "ptmi_denoise_views_frames", params, 1.0f, frame_nums, true, first_view, n_views);
-}
-
-int ptmi_read_denoised(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_DENOISED, "ptmi_read_denoised", view, 0, dst, bytes); }
-int ptmi_resolve_denoised_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t bytes) {
-  return resolve_stack(c, STACK_DENOISED, "ptmi_resolve_denoised_rgba8", view, 1.0f, dst, bytes);  // (the stack holds means: the display pass at frameNum 1)
-}
-int ptmi_denoised_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
-  return stack_device_ptr(c, STACK_DENOISED, "ptmi_denoised_device_ptr", nullptr, p, bytes, n_views);
-}
-int ptmi_release_denoised(ptmi_ctx* c) { return release_stack(c, STACK_DENOISED); }
-
-// ptmi_denoise_images / ptmi_fuse_images / ptmi_noise_images: the kernels on host arrays — colour [n][npix] float4, layers [n][layer_images][npix] float4, out [n][npix] of
-// out_pixel_bytes each (nullptr: the call wants none, and `enqueue` is handed nullptr) — through device copies of this call's own: the context's stacks are not touched.
-// `extra`: what else the kernels need on the device, allocated after the copies and, as everything that can fail for want of memory, before anything is enqueued.  `enqueue(colour, layers, out)` puts the kernels on the stream; whatever it returns, the stream drains before the
-// copies (and whatever `enqueue` captured) die.  The first error wins.
-static int on_host_images(ptmi_ctx* c, const char* who, const float* colour, const float* layers, size_t npix, uint32_t n, float* out, DBuf& extra, size_t extra_bytes,
-                          const std::function<int(const float4*, const float4*, float4*)>& enqueue, size_t layer_images = 3, size_t out_pixel_bytes = 16) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  (void)hipGetLastError();
-  const size_t bytes = npix * 16 * n, out_bytes = out ? npix * out_pixel_bytes * n : 0;
-  DBuf col, lay, res;
-  HIP_TRY(c, col.ensure(bytes));
-  HIP_TRY(c, lay.ensure(bytes * layer_images));
-  HIP_TRY(c, res.ensure(out_bytes));
-  HIP_TRY(c, extra.ensure_idle(extra_bytes, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(col.p, colour, bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(lay.p, layers, bytes * layer_images, hipMemcpyHostToDevice, c->stream));
-  int r = enqueue(col.as<float4>(), lay.as<float4>(), res.as<float4>());
-  if (r == PTMI_OK && out) {
-    const hipError_t e = hipMemcpyAsync(out, res.p, out_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e != hipSuccess) r = fail(c, PTMI_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-  }
-  const hipError_t e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess && r == PTMI_OK) r = fail(c, PTMI_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-  return r;
-}
-
-// ptmi_denoise_images (per_view false) and ptmi_denoise_images_frames (frame_nums: one per image)
-static int denoise_images(ptmi_ctx* c, const char* who, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const float* frame_nums,
-                          bool per_view, const ptmi_denoise_params* params, float* out) {
-  if (!c || !colour_sums || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  ptmi_denoise_params P;
-  if (int r = denoise_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
-  if (int r = check_image_size(c, who, w, h, n_images)) return r;
-  if (per_view)
-    if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
-  const size_t npix = (size_t)w * (size_t)h;
-  DBuf dfr;  // (the frame counts: this call's own, had before anything is enqueued)
-  if (per_view) {
-    HIP_TRY(c, hipSetDevice(c->device));
-    (void)hipGetLastError();
-    HIP_TRY(c, dfr.ensure((size_t)n_images * 4));
-  }
-  return on_host_images(c, who, colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kDenoiseScratchBytes),
-                        [&](const float4* col, const float4* lay, float4* res) -> int {
-                          if (per_view)
-                            if (int e = send_frame_nums(c, dfr, frame_nums, n_images)) return e;
-                          return atrous_enqueue(c, col, lay, res, n_images, w, h, frame_num, P, nullptr, dfr.as<float>());
-                        });
-}
-int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params, float* out) {
-  return denoise_images(c, "ptmi_denoise_images", colour_sums, layers, w, h, n_images, frame_num, nullptr, false, params, out);
-}
-int ptmi_denoise_images_frames(ptmi_ctx* c, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const float* frame_nums,
-                               const ptmi_denoise_params* params, float* out) {
-  return denoise_images(c, "ptmi_denoise_images_frames", colour_sums, layers, w, h, n_images, 1.0f, frame_nums, true, params, out);
-}
-
-// The guided filter's params as the launch plan takes them: the levels' part, with no colour term (P), and the rest (G, whose arrays the caller fills in)
-static int guided_check_args(ptmi_ctx* c, const char* who, const ptmi_guided_params* params, float frame_num, ptmi_denoise_params* P, AtrousGuide* G) {
-  ptmi_guided_params Q;
-  if (params) Q = *params;
-  else ptmi_default_guided_params(&Q);
-  const bool ok = ptmg_params_ok(Q.levels, Q.sigma_normal, Q.sigma_depth, Q.sigma_luma, Q.albedo_floor, Q.min_frames, Q.var_eps);
-  *P = ptmi_denoise_params{Q.levels, Q.sigma_normal, Q.sigma_depth, 0.0f, Q.albedo_floor, {}};
-  *G = AtrousGuide{nullptr, nullptr, ptmg_make_consts(Q.sigma_luma, Q.var_eps), Q.min_frames};
-  return check_stack_call(c, who, "a pixel's neighbours", "other",
-                          ok ? nullptr : "levels in 1..6, sigma_normal, sigma_depth and albedo_floor > 0, sigma_luma >= 0, min_frames >= 2, var_eps a normal f32 > 0, all finite", true, frame_num);
-}
-
-// ptmi_denoise_views_guided (per_view false: frame_num) and ptmi_denoise_views_guided_frames (per_view: frame_nums, one per view of the stack)
-static int denoise_views_guided(ptmi_ctx* c, const char* who, const ptmi_guided_params* params, float frame_num, const float* frame_nums, bool per_view, uint32_t first_view,
-                                uint32_t n_views) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  ptmi_denoise_params P;
-  AtrousGuide G;
-  if (int r = guided_check_args(c, who, params, per_view ? 1.0f : frame_num, &P, &G)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
-  if (int r = check_stack(c, STACK_MOMENTS, who, 0)) return r;  // (the moment stack first, then what ptmi_denoise_views asks: the order decides which error a caller sees)
-  if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
-  if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
-    return fail(c, PTMI_ERR_STATE, std::string(who) + ": the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
-  if (int r = check_source_stacks(c, who, false, first_view, n_views)) return r;
-  if (per_view)
-    if (int r = check_frame_nums(c, who, frame_nums, first_view, first_view + n_views)) return r;
-  return atrous_views(c, P, &G, frame_num, first_view, n_views, false, per_view ? frame_nums : nullptr);
-}
-int ptmi_denoise_views_guided(ptmi_ctx* c, const ptmi_guided_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
-  return denoise_views_guided(c, "ptmi_denoise_views_guided", params, frame_num, nullptr, false, first_view, n_views);
-}
-int ptmi_denoise_views_guided_frames(ptmi_ctx* c, const ptmi_guided_params* params, const float* frame_nums, uint32_t first_view, uint32_t n_views) {
-  return denoise_views_guided(c, "ptmi_denoise_views_guided_frames", params, 1.0f, frame_nums, true, first_view, n_views);
-}
-
-// ptmi_denoise_images_guided (per_view false) and ptmi_denoise_images_guided_frames (frame_nums: one per image)
-static int denoise_images_guided(ptmi_ctx* c, const char* who, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
-                                 const float* frame_nums, bool per_view, const ptmi_guided_params* params, float* out, float* var_out) {
-  if (!c || !colour_sums || !moments || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  ptmi_denoise_params P;
-  AtrousGuide G;
-  if (int r = guided_check_args(c, who, params, per_view ? 1.0f : frame_num, &P, &G)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
-  if (int r = check_image_size(c, who, w, h, n_images)) return r;
-  if (per_view)
-    if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
-  const size_t npix = (size_t)w * (size_t)h, bytes = npix * 16 * n_images, var_bytes = var_out ? npix * 4 * n_images : 0;
-  HIP_TRY(c, hipSetDevice(c->device));
-  (void)hipGetLastError();
-  DBuf mom, var, dfr;  // (on_host_images brings the colour, the layers and the output; these are this call's own, had before anything is enqueued)
-  HIP_TRY(c, mom.ensure(bytes));
-  HIP_TRY(c, var.ensure(var_bytes));
-  if (per_view) HIP_TRY(c, dfr.ensure((size_t)n_images * 4));
-  G.moments = mom.as<float4>(), G.var_out = var.as<float>();
-  return on_host_images(c, who, colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kGuidedScratchBytes),
-                        [&](const float4* col, const float4* lay, float4* res) -> int {
-                          HIP_TRY(c, hipMemcpyAsync(mom.p, moments, bytes, hipMemcpyHostToDevice, c->stream));
-                          if (per_view)
-                            if (int e = send_frame_nums(c, dfr, frame_nums, n_images)) return e;
-                          if (int e = atrous_enqueue(c, col, lay, res, n_images, w, h, frame_num, P, &G, dfr.as<float>())) return e;
-                          if (var_out) HIP_TRY(c, hipMemcpyAsync(var_out, var.p, var_bytes, hipMemcpyDeviceToHost, c->stream));
-                          return PTMI_OK;
-                        });
-}
-int ptmi_denoise_images_guided(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
-                               const ptmi_guided_params* params, float* out, float* var_out) {
-  return denoise_images_guided(c, "ptmi_denoise_images_guided", colour_sums, moments, layers, w, h, n_images, frame_num, nullptr, false, params, out, var_out);
-}
-int ptmi_denoise_images_guided_frames(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, const float* frame_nums,
-                                      const ptmi_guided_params* params, float* out, float* var_out) {
-  return denoise_images_guided(c, "ptmi_denoise_images_guided_frames", colour_sums, moments, layers, w, h, n_images, 1.0f, frame_nums, true, params, out, var_out);
-}
-
-// ---- the fused stack (ptmi_fuse_views, ptmi_fuse_images) ----
-// (ptmi_default_fuse_params and ptmi_fuse_reference need no GPU: ptmi_host.cpp)
-// The call's table as the kernel reads it: kFuseRow float4 per view of the stack, then one byte per material index, padded to a multiple of 16; the *_frames calls put
-// the views' frame counts, one f32 per view of the stack, behind those bytes (fuse_tab_frames: where).
-static size_t fuse_tab_frames(uint32_t n_stack, uint32_t n_materials) { return (size_t)n_stack * kFuseRow * 16 + ((std::max<size_t>(16, n_materials) + 15) & ~(size_t)15); }
-static size_t fuse_tab_bytes(uint32_t n_stack, uint32_t n_materials, bool frames = false) {
-  return frames ? fuse_tab_frames(n_stack, n_materials) + (size_t)n_stack * 4 : (size_t)n_stack * kFuseRow * 16 + std::max<size_t>(16, n_materials);
-}
-static const float* fuse_tab_frames_ptr(const void* tab, uint32_t n_stack, uint32_t n_materials) {
-  return reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(tab) + fuse_tab_frames(n_stack, n_materials));
-}
-
-// Fills `tab` (fuse_tab_bytes) from the matrices of all views and the material-type bytes; PTMI_ERR_INVALID_ARG for a matrix that cannot be inverted.
-static int fuse_fill_tab(ptmi_ctx* c, const char* who, const float* views16, uint32_t n_stack, const uint8_t* lamb, uint32_t n_materials, float* tab) {
-  for (uint32_t v = 0; v < n_stack; v++) {
-    ptmf_view row;
-    if (!ptmf_make_view(views16 + 16 * (size_t)v, &row))
-      return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the 3x3 of view matrix " + std::to_string(v) + " has a zero or non-finite determinant");
-    fuse_pack_row(row, tab + (size_t)v * kFuseRow * 4);
-  }
-  uint8_t* bytes = reinterpret_cast<uint8_t*>(tab + (size_t)n_stack * kFuseRow * 4);
-  memset(bytes, 0, std::max<size_t>(16, n_materials));
-  if (lamb) memcpy(bytes, lamb, n_materials);
-  return PTMI_OK;
-}
-
-// The kernel on device arrays: colour [n_stack][H][W] float4, layers [n_stack][3][H][W] float4, out [n_stack][H][W] float4, of which views [first, first + n) are
-// written; `tab` as fuse_fill_tab made it, `has_lamb`: whether its material bytes are to be used.  One launch; more only where n exceeds the grid's z limit.
-// frames: nullptr, or the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_fuse_frames.
-static int fuse_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, const void* tab, bool has_lamb, uint32_t n_materials, int W, int H,
-                        uint32_t n_stack, uint32_t first, uint32_t n, const ptmf_consts& k, const float* frames = nullptr) {
-  const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
-  const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
-  const uint8_t* lamb = has_lamb ? reinterpret_cast<const uint8_t*>(tab) + (size_t)n_stack * kFuseRow * 16 : nullptr;
-  for (uint32_t v0 = 0; v0 < n; v0 += 65535u) {
-    const uint32_t nv = std::min(65535u, n - v0);
-    if (frames)
-      hipLaunchKernelGGL(k_fuse_frames, dim3(gx, 1, nv), dim3(kBlock), 0, c->stream, colour, layers, out, reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, n_stack,
-                         first + v0, k, frames);
-    else
-      hipLaunchKernelGGL(k_fuse, dim3(gx, 1, nv), dim3(kBlock), 0, c->stream, colour, layers, out, reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, n_stack,
-                         first + v0, k);
-    HIP_TRY(c, hipGetLastError());
-  }
-  return PTMI_OK;
-}
-
-static int fuse_check_args(ptmi_ctx* c, const char* who, const ptmi_fuse_params* params, float frame_num, bool need_frames, ptmi_fuse_params* P) {
-  if (params) *P = *params;
-  else ptmi_default_fuse_params(P);
-  const bool ok = ptmf_params_ok(P->radius, P->sigma_normal, P->sigma_depth, P->albedo_floor);
-  return check_stack_call(c, who, "a view's pixels", "several", ok ? nullptr : "radius in 1..8, sigma_normal, sigma_depth and albedo_floor > 0, all finite", need_frames, frame_num);
-}
-
-// What ptmi_fuse_views and ptmi_accumulate_views do before they enqueue a kernel: the table of all views of the stack with the uploaded materials' types, the call's
-// stack `k` (of the view stack's size) and the table's two copies — everything that can fail for want of memory, before anything is enqueued — and then the
-// table's upload.  frame_nums: nullptr, or the stack's frame counts (checked), which go behind the table's material bytes.
-static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, const float* views16, const float* frame_nums = nullptr) {
-  const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  const size_t tab_bytes = fuse_tab_bytes(n_stack, n_mat, frame_nums != nullptr);
-  std::vector<float> tab;
-  std::vector<uint8_t> lamb;
-  try {
-    tab.resize(tab_bytes / 4 + 1);
-    lamb.resize(n_mat);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the view table");
-  }
-  for (uint32_t i = 0; i < n_mat; i++) lamb[i] = c->h_mats[16 * (size_t)i + 14] == PTMF_LAMBERTIAN;
-  if (int r = fuse_fill_tab(c, who, views16, n_stack, lamb.data(), n_mat, tab.data())) return r;
-  if (frame_nums) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_frames(n_stack, n_mat), frame_nums, (size_t)n_stack * 4);
-  HIP_TRY(c, hipSetDevice(c->device));
-  (void)hipGetLastError();
-  DBuf stack;
-  if (int r = reserve_stack(c, k, n_stack, &stack)) return r;
-  void* staged = nullptr;
-  HIP_TRY(c, c->fuse_tab.stage(tab_bytes, c->stream, &staged));
-  memcpy(staged, tab.data(), tab_bytes);
-  if (int r = commit_stack(c, k, n_stack, &stack)) return r;
-  HIP_TRY(c, c->fuse_tab.send(tab_bytes, c->stream));
-  return PTMI_OK;
-}
-
-// ptmi_fuse_views (per_view false: frame_num) and ptmi_fuse_views_frames (per_view: the view stack as source, frame_nums one per view of the stack)
-static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* params, const float* views16, float frame_num, const float* frame_nums, bool per_view, int source,
-                      uint32_t first_view, uint32_t n_views) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  if (source != 0 && source != 1) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": source must be 0 (the view stack) or 1 (the denoised stack)");
-  ptmi_fuse_params P;
-  if (int r = fuse_check_args(c, who, params, frame_num, source == 0 && !per_view, &P)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
-  if (int r = check_source_stacks(c, who, source == 1, first_view, n_views)) return r;
-  const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  if (per_view) {  // the call's range widened by the radius on both sides, clipped to the stack: the window of its output views
-    const uint32_t R = (uint32_t)P.radius, lo = first_view > R ? first_view - R : 0u, hi = (uint32_t)std::min<uint64_t>(n_stack, (uint64_t)first_view + n_views + R);
-    if (int r = check_frame_nums(c, who, frame_nums, lo, hi)) return r;
-  }
-  if (int r = make_stack_with_table(c, who, STACK_FUSED, views16, per_view ? frame_nums : nullptr)) return r;
-  const float fov_factor = (float)(1.0 / std::tan((double)c->prm.fov_degrees * (3.14159265358979323846 / 180.0) / 2.0));  // as make_render_const folds it
-  const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, source == 0 ? frame_num : 1.0f, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
-  return fuse_enqueue(c, c->stacks[source == 0 ? STACK_VIEWS : STACK_DENOISED].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(), c->stacks[STACK_FUSED].buf.as<float4>(),
-                      c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, k, per_view ? fuse_tab_frames_ptr(c->fuse_tab.dev.p, n_stack, n_mat) : nullptr);
-}
-int ptmi_fuse_views(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, float frame_num, int source, uint32_t first_view, uint32_t n_views) {
-  return fuse_views(c, "ptmi_fuse_views", params, views16, frame_num, nullptr, false, source, first_view, n_views);
-}
-int ptmi_fuse_views_frames(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, uint32_t first_view, uint32_t n_views) {
-  return fuse_views(c, "ptmi_fuse_views_frames", params, views16, 1.0f, frame_nums, true, 0, first_view, n_views);
-}
-
-int ptmi_read_fused(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_FUSED, "ptmi_read_fused", view, 0, dst, bytes); }
-int ptmi_resolve_fused_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t bytes) {
-  return resolve_stack(c, STACK_FUSED, "ptmi_resolve_fused_rgba8", view, 1.0f, dst, bytes);  // (the stack holds means: the display pass at frameNum 1)
-}
-int ptmi_fused_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) { return stack_device_ptr(c, STACK_FUSED, "ptmi_fused_device_ptr", nullptr, p, bytes, n_views); }
-int ptmi_release_fused(ptmi_ctx* c) { return release_stack(c, STACK_FUSED); }
-
-// ptmi_fuse_images (per_view false) and ptmi_fuse_images_frames (frame_nums: one per image)
-static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
-                       const float* frame_nums, bool per_view, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
-  if (!c || !colour || !layers || !views16 || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  ptmi_fuse_params P;
-  if (int r = fuse_check_args(c, who, params, frame_num, !per_view, &P)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
-  if (int r = check_image_size(c, who, w, h, n_images)) return r;
-  if (per_view)
-    if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
-  if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": fov_degrees must be in (0,180)");
-  if (!lambertian) n_materials = 0;
-  const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials, per_view);
-  std::vector<float> tab;
-  try {
-    tab.resize(tab_bytes / 4 + 1);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the view table");
-  }
-  if (int r = fuse_fill_tab(c, who, views16, n_images, lambertian, n_materials, tab.data())) return r;
-  if (per_view) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_frames(n_images, n_materials), frame_nums, (size_t)n_images * 4);
-  const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
-  DBuf dtab;
-  return on_host_images(c, who, colour, layers, (size_t)w * (size_t)h, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
-    HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
-    return fuse_enqueue(c, col, lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, 0, n_images, k,
-                        per_view ? fuse_tab_frames_ptr(dtab.p, n_images, n_materials) : nullptr);
-  });
-}
-int ptmi_fuse_images(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
-                     const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
-  return fuse_images(c, "ptmi_fuse_images", colour, layers, views16, w, h, n_images, frame_num, nullptr, false, fov_degrees, lambertian, n_materials, params, out);
-}
-int ptmi_fuse_images_frames(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums, float fov_degrees,
-                            const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
-  return fuse_images(c, "ptmi_fuse_images_frames", colour, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params, out);
-}
-
-// ---- the accumulated stack (ptmi_accumulate_views, ptmi_accumulate_images) and the guided filter on it (ptmi_denoise_views_accumulated, ptmi_denoise_images_accumulated) ----
-// (ptmi_default_accumulate_params, ptmi_accumulate_reference and ptmi_denoise_accumulated_reference need no GPU: ptmi_host.cpp)
-// The kernel on device arrays: colour, moments [n_stack][H][W] float4, layers [n_stack][3][H][W] float4, planes [3][n_stack][H][W] float4, of which views
-// [first, first + n) are written, one launch per view in ascending order; view `first` takes its history from view first - 1 of `planes` when `resume`.
-// frames: nullptr, or the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_accumulate_view_frames.
-static int accumulate_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, const float4* layers, float4* planes, const void* tab, bool has_lamb, uint32_t n_materials,
-                              int W, int H, uint32_t n_stack, uint32_t first, uint32_t n, bool resume, const ptmf_consts& k, const ptma_consts& ka, const float* frames = nullptr) {
-  const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
-  const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
-  const uint8_t* lamb = has_lamb ? reinterpret_cast<const uint8_t*>(tab) + (size_t)n_stack * kFuseRow * 16 : nullptr;
-  const size_t npix = (size_t)W * (size_t)H;
-  auto plane = [&](uint32_t pl, uint32_t v) { return planes + ((size_t)pl * n_stack + v) * npix; };
-  for (uint32_t v = first; v < first + n; v++) {
-    const bool has_prev = v > 0 && (v > first || resume);
-    if (frames)
-      hipLaunchKernelGGL(k_accumulate_view_frames, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr,
-                         has_prev ? plane(2, v - 1) : nullptr, plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka, frames);
-    else
-      hipLaunchKernelGGL(k_accumulate_view, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr, has_prev ? plane(2, v - 1) : nullptr,
-                         plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka);
-    HIP_TRY(c, hipGetLastError());
-  }
-  return PTMI_OK;
-}
-
-static int accumulate_check_args(ptmi_ctx* c, const char* who, const ptmi_accumulate_params* params, float frame_num, ptmi_accumulate_params* P) {
-  if (params) *P = *params;
-  else ptmi_default_accumulate_params(P);
-  const bool ok = ptma_params_ok(P->max_history, P->min_frames, P->sigma_normal, P->sigma_depth, P->albedo_floor);
-  return check_stack_call(c, who, "a view's pixels", "several", ok ? nullptr : "max_history, sigma_normal, sigma_depth and albedo_floor > 0, all finite, and min_frames >= 2", true, frame_num);
-}
-
-// ptmi_accumulate_views (per_view false: frame_num) and ptmi_accumulate_views_frames (per_view: frame_nums, one per view of the stack)
-static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_params* params, const float* views16, float frame_num, const float* frame_nums, bool per_view,
-                            uint32_t first_view, uint32_t n_views, int resume) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  ptmi_accumulate_params P;
-  if (int r = accumulate_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
-  if (int r = check_stack(c, STACK_MOMENTS, who, 0)) return r;  // (the moment stack first, as ptmi_denoise_views_guided asks)
-  if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
-  if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
-    return fail(c, PTMI_ERR_STATE, std::string(who) + ": the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
-  if (int r = check_source_stacks(c, who, false, first_view, n_views)) return r;
-  if (resume) {
-    if (first_view == 0) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": resume needs first_view > 0: view 0 has no predecessor");
-    if (int r = check_stack(c, STACK_ACCUMULATED, (std::string(who) + " (resume)").c_str(), 0)) return r;
-  }
-  if (per_view)  // the call's range, and the view before it where its state is taken over
-    if (int r = check_frame_nums(c, who, frame_nums, resume ? first_view - 1u : first_view, first_view + n_views)) return r;
-  const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  if (int r = make_stack_with_table(c, who, STACK_ACCUMULATED, views16, per_view ? frame_nums : nullptr)) return r;
-  const float fov_factor = (float)(1.0 / std::tan((double)c->prm.fov_degrees * (3.14159265358979323846 / 180.0) / 2.0));  // as make_render_const folds it
-  const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
-  return accumulate_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>(), c->stacks[STACK_MOMENTS].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(),
-                            c->stacks[STACK_ACCUMULATED].buf.as<float4>(), c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, resume != 0, k,
-                            ptma_make_consts(P.max_history, P.min_frames), per_view ? fuse_tab_frames_ptr(c->fuse_tab.dev.p, n_stack, n_mat) : nullptr);
-}
-int ptmi_accumulate_views(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, float frame_num, uint32_t first_view, uint32_t n_views, int resume) {
-  return accumulate_views(c, "ptmi_accumulate_views", params, views16, frame_num, nullptr, false, first_view, n_views, resume);
-}
-int ptmi_accumulate_views_frames(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, uint32_t first_view, uint32_t n_views, int resume) {
-  return accumulate_views(c, "ptmi_accumulate_views_frames", params, views16, 1.0f, frame_nums, true, first_view, n_views, resume);
-}
-
-int ptmi_read_accumulated(ptmi_ctx* c, uint32_t view, int plane, float* dst, size_t bytes) { return read_stack(c, STACK_ACCUMULATED, "ptmi_read_accumulated", view, plane, dst, bytes); }
-int ptmi_resolve_accumulated_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t bytes) {
-  return resolve_stack(c, STACK_ACCUMULATED, "ptmi_resolve_accumulated_rgba8", view, 1.0f, dst, bytes);  // (plane 0, whose image `view` is the stack's image `view`: means, the display pass at frameNum 1)
-}
-int ptmi_accumulated_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
-  return stack_device_ptr(c, STACK_ACCUMULATED, "ptmi_accumulated_device_ptr", nullptr, p, bytes, n_views);
-}
-int ptmi_release_accumulated(ptmi_ctx* c) { return release_stack(c, STACK_ACCUMULATED); }
-
-// ptmi_accumulate_images (per_view false) and ptmi_accumulate_images_frames (frame_nums: one per image)
-static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
-                             float frame_num, const float* frame_nums, bool per_view, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
-                             const ptmi_accumulate_params* params, const float* history_in, float* out) {
-  if (!c || !colour_sums || !moments || !layers || !views16 || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  ptmi_accumulate_params P;
-  if (int r = accumulate_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
-  if (int r = check_image_size(c, who, w, h, n_images)) return r;
-  if (per_view)
-    if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
-  if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": fov_degrees must be in (0,180)");
-  if (history_in && n_images < 2) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": history_in makes image 0 the view before the first: need n_images >= 2");
-  if (!lambertian) n_materials = 0;
-  const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials, per_view);
-  std::vector<float> tab;
-  try {
-    tab.resize(tab_bytes / 4 + 1);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the view table");
-  }
-  if (int r = fuse_fill_tab(c, who, views16, n_images, lambertian, n_materials, tab.data())) return r;
-  if (per_view) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_frames(n_images, n_materials), frame_nums, (size_t)n_images * 4);
-  const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
-  const ptma_consts ka = ptma_make_consts(P.max_history, P.min_frames);
-  const size_t npix = (size_t)w * (size_t)h, bytes = npix * 16 * n_images;
-  HIP_TRY(c, hipSetDevice(c->device));
-  (void)hipGetLastError();
-  DBuf mom, dtab;  // (on_host_images brings the colour, the layers, the three planes and the table; the moments are this call's own, had before anything is enqueued)
-  HIP_TRY(c, mom.ensure(bytes));
-  return on_host_images(c, who, colour_sums, layers, npix, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
-    HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(mom.p, moments, bytes, hipMemcpyHostToDevice, c->stream));
-    if (history_in) {  // image 0 is the view before the first: its state is given, its mean is not made
-      HIP_TRY(c, hipMemsetAsync(res, 0, npix * 16, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(res + (size_t)n_images * npix, history_in, npix * 16, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(res + (size_t)2 * n_images * npix, history_in + npix * 4, npix * 16, hipMemcpyHostToDevice, c->stream));
-    }
-    const uint32_t first = history_in ? 1u : 0u;
-    return accumulate_enqueue(c, col, mom.as<float4>(), lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, first, n_images - first, history_in != nullptr, k, ka,
-                              per_view ? fuse_tab_frames_ptr(dtab.p, n_images, n_materials) : nullptr);
-  }, 3, 48);
-}
-int ptmi_accumulate_images(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
-                           float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out) {
-  return accumulate_images(c, "ptmi_accumulate_images", colour_sums, moments, layers, views16, w, h, n_images, frame_num, nullptr, false, fov_degrees, lambertian, n_materials, params,
-                           history_in, out);
-}
-int ptmi_accumulate_images_frames(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
-                                  const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
-                                  const float* history_in, float* out) {
-  return accumulate_images(c, "ptmi_accumulate_images_frames", colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params,
-                           history_in, out);
-}
-
-int ptmi_denoise_views_accumulated(ptmi_ctx* c, const ptmi_guided_params* params, uint32_t first_view, uint32_t n_views) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  ptmi_denoise_params P;
-  AtrousGuide G;
-  if (int r = guided_check_args(c, "ptmi_denoise_views_accumulated", params, 1.0f, &P, &G)) return r;
-  if (int r = check_stack(c, STACK_ACCUMULATED, "ptmi_denoise_views_accumulated", 0)) return r;
-  if (int r = check_stack(c, STACK_FEATURES, "ptmi_denoise_views_accumulated", 0)) return r;
-  const uint32_t n = c->stacks[STACK_ACCUMULATED].n, na = c->stacks[STACK_FEATURES].n;
-  if (n != na) return fail(c, PTMI_ERR_STATE, "ptmi_denoise_views_accumulated: the accumulated stack has " + std::to_string(n) + " views, the feature stack " + std::to_string(na));
-  if (int r = check_view_range(c, "ptmi_denoise_views_accumulated", first_view, n_views, n)) return r;
-  return atrous_views(c, P, &G, 1.0f, first_view, n_views, true);
-}
-
-int ptmi_denoise_images_accumulated(ptmi_ctx* c, const float* means, const float* plane2, const float* layers, int w, int h, uint32_t n_images, const ptmi_guided_params* params,
-                                    float* out, float* var_out) {
-  if (!c || !means || !plane2 || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_denoise_images_accumulated: null argument");
-  ptmi_denoise_params P;
-  AtrousGuide G;
-  if (int r = guided_check_args(c, "ptmi_denoise_images_accumulated", params, 1.0f, &P, &G)) return r;
-  if (int r = check_image_size(c, "ptmi_denoise_images_accumulated", w, h, n_images)) return r;
-  const size_t npix = (size_t)w * (size_t)h, bytes = npix * 16 * n_images, var_bytes = var_out ? npix * 4 * n_images : 0;
-  HIP_TRY(c, hipSetDevice(c->device));
-  (void)hipGetLastError();
-  DBuf giv, var;  // (as ptmi_denoise_images_guided's moments and variance)
-  HIP_TRY(c, giv.ensure(bytes));
-  HIP_TRY(c, var.ensure(var_bytes));
-  G.given = giv.as<float4>(), G.var_out = var.as<float>();
-  return on_host_images(c, "ptmi_denoise_images_accumulated", means, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kGuidedScratchBytes),
-                        [&](const float4* col, const float4* lay, float4* res) -> int {
-                          HIP_TRY(c, hipMemcpyAsync(giv.p, plane2, bytes, hipMemcpyHostToDevice, c->stream));
-                          if (int e = atrous_enqueue(c, col, lay, res, n_images, w, h, 1.0f, P, &G)) return e;
-                          if (var_out) HIP_TRY(c, hipMemcpyAsync(var_out, var.p, var_bytes, hipMemcpyDeviceToHost, c->stream));
-                          return PTMI_OK;
-                        });
-}
-
-// ---- the moment stack and the noise statistic (ptmi_set_view_moments, ptmi_view_noise_stats, ptmi_noise_images, ptmi_render_views_until) ----
-// (ptmi_default_noise_params and ptmi_noise_reference need no GPU: ptmi_host.cpp)
-int ptmi_set_view_moments(ptmi_ctx* c, int enabled) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  for (ptmi_ctx* q : local_devices(c)) q->view_moments = enabled != 0;
-  // off: the moment stack goes, so that one that exists always describes the frames its view stack sums
-  return enabled ? PTMI_OK : release_stack(c, STACK_MOMENTS);
-}
-int ptmi_read_moments(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_MOMENTS, "ptmi_read_moments", view, 0, dst, bytes); }
-int ptmi_moments_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) {
-  return stack_device_ptr(c, STACK_MOMENTS, "ptmi_moments_device_ptr", "ptmi_read_moments", p, bytes, n_views);
-}
-int ptmi_release_moments(ptmi_ctx* c) { return release_stack(c, STACK_MOMENTS); }
-
-static int noise_check_args(ptmi_ctx* c, const char* who, const ptmi_noise_params* params, ptmi_noise_params* P) {
-  if (params) *P = *params;
-  else ptmi_default_noise_params(P);
-  if (!ptmn_params_ok(P->floor, P->threshold)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need floor > 0 and threshold >= 0, both finite");
-  return PTMI_OK;
-}
-
-// The kernel on device arrays: colour and moments [n][npix] float4 of which a device reads its shard (n_local pixels of rank / world / tile), `records` n zeroed records,
-// map [n][npix] f32 or nullptr.  One launch; more only where n exceeds the grid's y limit.
-static int noise_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, uint32_t n, uint32_t npix, uint32_t n_local, int rank, int world, int tile,
-                         const ptmi_noise_params& P, unsigned char* records, float* map) {
-  HIP_TRY(c, hipMemsetAsync(records, 0, (size_t)n * kNoiseRecordBytes, c->stream));
-  if (n_local == 0) return PTMI_OK;
-  const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((n_local + kBlock - 1) / kBlock, kNoiseChunks));
-  for (uint32_t v0 = 0; v0 < n; v0 += 65535u) {
-    const uint32_t nv = std::min(65535u, n - v0);
-    hipLaunchKernelGGL(k_view_noise, dim3(gx, nv), dim3(kBlock), 0, c->stream, colour + (size_t)v0 * npix, moments + (size_t)v0 * npix, npix, n_local, rank, world, tile, P.floor,
-                       ptmn_threshold_q(P.threshold), records + (size_t)v0 * kNoiseRecordBytes, map ? map + (size_t)v0 * npix : nullptr);
-    HIP_TRY(c, hipGetLastError());
-  }
-  return PTMI_OK;
-}
-
-// records (kNoiseRecordBytes apart, on the host) added into out[0 .. n)
-static void noise_add_records(const unsigned char* rec, uint32_t n, ptmi_view_noise* out) {
-  for (uint32_t v = 0; v < n; v++) {
-    NoiseRecord r;
-    memcpy(&r, rec + (size_t)v * kNoiseRecordBytes, sizeof r);
-    out[v].counted += r.counted, out[v].sum_q += r.sum_q, out[v].above += r.above;
-    out[v].max_q = std::max(out[v].max_q, r.max_q);
-  }
-}
-
-int ptmi_view_noise_stats(ptmi_ctx* c, const ptmi_noise_params* params, uint32_t first_view, uint32_t n_views, ptmi_view_noise* out) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  if (!out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_view_noise_stats: null argument");
-  ptmi_noise_params P;
-  if (int r = noise_check_args(c, "ptmi_view_noise_stats", params, &P)) return r;
-  if (int r = check_stack(c, STACK_VIEWS, "ptmi_view_noise_stats", 0)) return r;
-  if (int r = check_stack(c, STACK_MOMENTS, "ptmi_view_noise_stats", 0)) return r;
-  const uint32_t n = c->stacks[STACK_VIEWS].n;
-  if (int r = check_view_range(c, "ptmi_view_noise_stats", first_view, n_views, n)) return r;
-  const std::vector<ptmi_ctx*> devs = local_devices(c);
-  std::vector<unsigned char> host;
-  try {
-    host.resize(devs.size() * (size_t)n_views * kNoiseRecordBytes);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_view_noise_stats: no host memory for the records");
-  }
-  // every device reduces its own tiles of its own stacks, all of them at once; the copies land in `host`, which outlives the synchronisation below
-  int r = on_all_devices(c, [&](ptmi_ctx* q) -> int {
-    HIP_TRY(q, hipSetDevice(q->device));
-    (void)hipGetLastError();
-    const size_t i = (size_t)(std::find(devs.begin(), devs.end(), q) - devs.begin());
-    const uint32_t npix = (uint32_t)q->W * (uint32_t)q->H;
-    HIP_TRY(q, q->d_noise_rec.ensure_idle((size_t)n_views * kNoiseRecordBytes, q->stream));
-    int e = noise_enqueue(q, q->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)first_view * npix, q->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix, n_views, npix,
-                          count_local(npix, q->rank, q->world, q->tile), q->rank, q->world, q->tile, P, q->d_noise_rec.as<unsigned char>(), nullptr);
-    if (e) return e;
-    HIP_TRY(q, hipMemcpyAsync(host.data() + i * (size_t)n_views * kNoiseRecordBytes, q->d_noise_rec.p, (size_t)n_views * kNoiseRecordBytes, hipMemcpyDeviceToHost, q->stream));
-    return PTMI_OK;
-  });
-  const int s = on_all_devices(c, [](ptmi_ctx* q) -> int {  // (whatever was enqueued drains before `host` goes)
-    HIP_TRY(q, hipSetDevice(q->device));
-    HIP_TRY(q, hipStreamSynchronize(q->stream));
-    drain_spans(q);
-    return check_queue_overflow(q);
-  });
-  (void)hipSetDevice(c->device);
-  if (r) return r;
-  if (s) return s;
-  memset(out, 0, (size_t)n_views * sizeof(ptmi_view_noise));
-  for (size_t i = 0; i < devs.size(); i++) noise_add_records(host.data() + i * (size_t)n_views * kNoiseRecordBytes, n_views, out);
-  return PTMI_OK;
-}
-
-int ptmi_noise_images(ptmi_ctx* c, const float* colour_sums, const float* moments, int w, int h, uint32_t n_images, const ptmi_noise_params* params, ptmi_view_noise* out,
-                      float* map_out) {
-  if (!c || !colour_sums || !moments || !out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_noise_images: null argument");
-  ptmi_noise_params P;
-  if (int r = noise_check_args(c, "ptmi_noise_images", params, &P)) return r;
-  if (int r = check_image_size(c, "ptmi_noise_images", w, h, n_images)) return r;
-  const uint32_t npix = (uint32_t)w * (uint32_t)h;
-  const size_t rec_bytes = (size_t)n_images * kNoiseRecordBytes;
-  std::vector<unsigned char> host;
-  try {
-    host.resize(rec_bytes);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_noise_images: no host memory for the records");
-  }
-  DBuf rec;
-  const int r = on_host_images(
-      c, "ptmi_noise_images", colour_sums, moments, npix, n_images, reinterpret_cast<float*>(map_out), rec, rec_bytes,
-      [&](const float4* col, const float4* mom, float4* map) -> int {
-        if (int e = noise_enqueue(c, col, mom, n_images, npix, npix, 0, 1, 64, P, rec.as<unsigned char>(), reinterpret_cast<float*>(map))) return e;
-        HIP_TRY(c, hipMemcpyAsync(host.data(), rec.p, rec_bytes, hipMemcpyDeviceToHost, c->stream));
-        return PTMI_OK;
-      },
-      1, sizeof(float));
-  if (r) return r;
-  memset(out, 0, (size_t)n_images * sizeof(ptmi_view_noise));
-  noise_add_records(host.data(), n_images, out);
-  return PTMI_OK;
-}
-
-int ptmi_render_views_until(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t first_frame, uint32_t frames_per_round, uint32_t max_frames,
-                            const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  if (!views16 || !frames_done) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until: null argument");
-  *frames_done = 0;
-  if (n_views == 0 || frames_per_round == 0 || max_frames == 0) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until: need n_views, frames_per_round and max_frames >= 1");
-  if ((uint64_t)n_views * max_frames > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until: n_views * max_frames must stay below 2^31");
-  if (!(target >= 0.0f) || !ptmn_finite(target)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until: target must be finite and >= 0");
-  ptmi_noise_params P;
-  if (int r = noise_check_args(c, "ptmi_render_views_until", params, &P)) return r;
-  if (!c->view_moments) return fail(c, PTMI_ERR_STATE, "ptmi_render_views_until: moments are off: call ptmi_set_view_moments first");
-  std::vector<ptmi_view_noise> stats;
-  try {
-    stats.resize(n_views);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_render_views_until: no host memory for the records");
-  }
-  for (uint32_t done = 0; done < max_frames;) {
-    const uint32_t nf = std::min(frames_per_round, max_frames - done);
-    if (int r = ptmi_render_views(c, views16, n_views, first_frame + done, nf, done == 0 ? 1 : 0)) return r;
-    done += nf;
-    *frames_done = done;
-    if (int r = ptmi_view_noise_stats(c, &P, 0, n_views, stats.data())) return r;
-    bool met = true;
-    for (uint32_t v = 0; v < n_views && met; v++) met = ptmn_target_met(stats[v].counted, stats[v].sum_q, target);
-    if (met) break;
-  }
-  if (out) memcpy(out, stats.data(), (size_t)n_views * sizeof(ptmi_view_noise));
-  return PTMI_OK;
-}
-
-int ptmi_render_views_until_each(ptmi_ctx* c, const float* views16, uint32_t n_views, const uint32_t* first_frames, uint32_t frames_per_round, uint32_t max_frames,
-                                 const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out) {
-  if (!c) return PTMI_ERR_INVALID_ARG;
-  if (!views16 || !frames_done) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until_each: null argument");
-  if (n_views == 0 || frames_per_round == 0 || max_frames == 0) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until_each: need n_views, frames_per_round and max_frames >= 1");
-  for (uint32_t v = 0; v < n_views; v++) frames_done[v] = 0;
-  if ((uint64_t)n_views * max_frames > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until_each: n_views * max_frames must stay below 2^31");
-  if (!(target >= 0.0f) || !ptmn_finite(target)) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_views_until_each: target must be finite and >= 0");
-  ptmi_noise_params P;
-  if (int r = noise_check_args(c, "ptmi_render_views_until_each", params, &P)) return r;
-  if (!c->view_moments) return fail(c, PTMI_ERR_STATE, "ptmi_render_views_until_each: moments are off: call ptmi_set_view_moments first");
-  std::vector<ptmi_view_noise> stats;
-  std::vector<uint32_t> firsts, counts;
-  std::vector<char> met;
-  try {
-    stats.resize(n_views);
-    firsts.resize(n_views);
-    counts.resize(n_views);
-    met.assign(n_views, 0);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_render_views_until_each: no host memory for the records");
-  }
-  for (bool round0 = true;; round0 = false) {
-    uint32_t open = 0;
-    for (uint32_t v = 0; v < n_views; v++) {
-      counts[v] = met[v] ? 0u : std::min(frames_per_round, max_frames - frames_done[v]);
-      firsts[v] = (first_frames ? first_frames[v] : 0u) + frames_done[v];
-      open += counts[v] != 0u;
-    }
-    if (!open) break;
-    if (int r = ptmi_render_views_frames(c, views16, n_views, firsts.data(), counts.data(), round0 ? 1 : 0)) return r;
-    for (uint32_t v = 0; v < n_views; v++) frames_done[v] += counts[v];
-    if (int r = ptmi_view_noise_stats(c, &P, 0, n_views, stats.data())) return r;
-    for (uint32_t v = 0; v < n_views; v++)
-      if (!met[v]) met[v] = ptmn_target_met(stats[v].counted, stats[v].sum_q, target);
-  }
-  if (out) memcpy(out, stats.data(), (size_t)n_views * sizeof(ptmi_view_noise));
   return PTMI_OK;
 }
 

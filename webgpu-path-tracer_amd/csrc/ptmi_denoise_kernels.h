@@ -20,7 +20,7 @@
 #pragma once
 
 #include "../../include/ptmi_guided.h"
-#include "ptmi_kernels.h"
+#include "ptmi_device.h"
 
 namespace ptmi {
 

@@ -15,6 +15,8 @@
 
 namespace ptmi {
 
+constexpr int kBlock = 256;  // threads of a block of the render kernels and of the image-stack kernels alike (the single-wave ones apart)
+
 // ---- lane tallies (measurement builds only: -DPTMI_LANE_TALLY, tools/shade_lanes.py) ------------------------------------------------------
 // LT(k) at the head of a region of k_shade's code counts how often a wave enters it and with how many lanes of its exec mask set:
 // where do the idle lanes of the kernel's instructions go?  Tallied in LDS per block, flushed by k_shade alone (the other kernels that share
@@ -23,7 +25,7 @@ namespace ptmi {
 #ifdef PTMI_LANE_TALLY
 constexpr int kLaneTallies = 48;
 __shared__ uint32_t s_lane_tally[kLaneTallies * 2];  // {visits, lanes} per point
-__device__ unsigned long long g_lane_tally[kLaneTallies * 2];
+static __device__ unsigned long long g_lane_tally[kLaneTallies * 2];  // (static, as g_time_tally: more than one unit of the library includes this header; ptmi.hip's copy is the one k_shade fills and ptmi_lane_tally reads)
 template <int K>
 DEV void lane_tally() {
   static_assert(K >= 0 && K < kLaneTallies, "tally point out of range");
@@ -40,7 +42,7 @@ DEV void lane_tally() {
 constexpr int kTimeTallies = 12;
 __shared__ unsigned long long s_time_tally[4 * kTimeTallies];  // per wave of the block: cycles per region
 __shared__ unsigned long long s_time_last[4];
-__device__ unsigned long long g_time_tally[2 * kTimeTallies];  // {cycles, marks} per region
+static __device__ unsigned long long g_time_tally[2 * kTimeTallies];  // {cycles, marks} per region
 template <int K>
 DEV void time_tally(float dep) {
   unsigned long long now;

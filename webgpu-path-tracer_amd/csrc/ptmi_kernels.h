@@ -16,8 +16,6 @@
 
 namespace ptmi {
 
-constexpr int kBlock = 256;
-
 // (k_bvh's claim counters, kHeadStride / kMaxTeams: ptmi_tuning.h)
 DEV void reset_heads(uint32_t* __restrict__ heads) {
   if (blockIdx.x == 0 && threadIdx.x < kMaxTeams) heads[threadIdx.x * kHeadStride] = 0u;
