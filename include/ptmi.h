@@ -659,6 +659,66 @@ int ptmi_accumulate_reference_frames(const float* colour_sums, const float* mome
                                      const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
                                      const float* history_in, float* out, int threads);
 
+/* ACCUMULATION WITH PER-OBJECT MOTION (the motion-vector half of SVGF).  "Temporal accumulation" reprojects through a STATIC world: view v carries pixel p to its
+ * world point X and projects that same X into view v-1.  Where p's object moved between the two views — a mesh animated through ptmi_refit_scene_bvh — X is not where
+ * that surface point was at the time of view v-1: the lookup lands on another point of the object and takes over its history (ghosting), or is refused (noise).  The
+ * calls below are ptmi_accumulate_views_frames and its *_images / *_reference forms with a per-view, per-object motion applied between the two steps; they build on
+ * "Temporal accumulation" and "CONSUMERS WITH PER-VIEW FRAME COUNTS" and change only what is said here.
+ *
+ * MOTIONS.  motions16 is [n_views of the stack][n_objects][16] f32: column-major matrices, as views16 and the transform table (binding 7) are, indexed by absolute
+ * view number and by global_id.  G(v, o) maps a world point of object o at the time of view v to the world point of the same material point at the time of view v-1.
+ * Only the affine part is read — elements 0-2, 4-6, 8-10, 12-14; the bottom row is ignored.  The entries a call reads are those of views first_view + 1 ..
+ * first_view + n_views - 1, and first_view too when resume != 0; every other entry may hold anything (frame_nums' rule).  The host turns each entry it reads into one
+ * record, once per call, the same records for the CPU and the GPU path (include/ptmi_motion.h): the twelve elements as passed; Gn, the inverse transpose of the 3x3, by
+ * cofactors in f64 with each element rounded to f32 once, as the view table's B is made; and an identity flag, set when the twelve elements equal the identity's as
+ * values (-0.0 counts as 0).  A read entry with an element that is not finite, or with a 3x3 whose determinant is zero or not finite, gives PTMI_ERR_INVALID_ARG naming
+ * the view and the object; so does a null motions16, and so do more than PTMI_MOTION_MAX_RECORDS entries (n_views of the stack x n_objects; 96 MiB of records): all
+ * before any allocation or launch.  n_objects = 0 is allowed: every pixel is then static.  Everything that can fail for want of memory is allocated before anything
+ * is enqueued.
+ *
+ * THE OBJECT OF A PIXEL is read from I = layer 2 of view v at p: kind 1 (sphere): spheres[prim][4]; kind 2 (quad): quads[prim][11]; kind 3 (triangle):
+ * mesh = triangles[prim][23], then meshes[mesh][2]; kind 0 or anything else: none.  Every index is range-checked against the uploaded counts before it is used, and
+ * an f32 index or id g counts only when g >= 0, g < its count (for a global_id: 2^31) and g == floor(g) — scene values may be any f32, nothing is trusted.  A pixel
+ * with no object, or with an object >= n_objects, is STATIC.  The triangles are read in the order they lie in NOW: THE CALLER is responsible for that being the order
+ * the feature stack was rendered in.  ptmi_refit_scene_bvh keeps it; a build or an upload of triangles changes it.
+ *
+ * PER PIXEL.  A static pixel runs exactly ptmi_accumulate_views_frames' arithmetic, bit for bit, and so does a pixel whose record has the identity flag.  Otherwise,
+ * between step 1 and step 2 of "Fusion" with u = v-1: X'_i = ((G_i0 X_0 + G_i1 X_1) + G_i2 X_2) + G_i3;  m_i = (Gn_i0 n_0 + Gn_i1 n_1) + Gn_i2 n_2 on n(p);
+ * len = sqrt((m_0^2 + m_1^2) + m_2^2); nothing is taken over unless len is finite and > 0; n' = m / len (three divisions).  X' is projected into view v-1 in X's
+ * place, which gives q and r, and the weight is "Temporal accumulation"'s with n' in n(p)'s place.  Own state, history, mean, variance, pass-through and the three
+ * planes are untouched.  The operation order is fixed in include/ptmi_motion.h, which the kernel and the host reference both compile.  A camera that moves WITH an
+ * object (both translated by T, G the translation by -T) has q = p and wgt exactly 1 on that object: n after k such views of one frame each is exactly k.
+ *
+ * OUT OF SCOPE: fusion (ptmi_fuse_views) with motions; an object test at q — q's object would need a second dependent chain, so the material, normal and depth tests
+ * stay the disocclusion tests; deforming meshes (per-vertex motion); multi-device contexts. */
+#define PTMI_MOTION_MAX_RECORDS (1u << 20)
+/* ptmi_accumulate_views_frames with motions; there is no one-frame_num twin.  Writes the same ACCUMULATED STACK: ptmi_read_accumulated,
+ * ptmi_resolve_accumulated_rgba8, ptmi_accumulated_device_ptr, ptmi_release_accumulated and ptmi_denoise_views_accumulated work on its result unchanged.  The object of
+ * a pixel is resolved inside the kernel from the scene as it is uploaded at the time of the call (k_accumulate_view_motion, csrc/ptmi_accumulate_kernels.h, which
+ * stands beside the two entries the other calls keep launching).  Errors and their order are ptmi_accumulate_views_frames', the null motions16 with the null
+ * frame_nums, the entries' checks after frame_nums'.  Asynchronous; one launch per view, in order on the context's stream. */
+int ptmi_accumulate_views_motion(ptmi_ctx* ctx, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, const float* motions16,
+                                 uint32_t n_objects, uint32_t first_view, uint32_t n_views, int resume);
+/* ptmi_accumulate_images_frames / ptmi_accumulate_reference_frames with motions16 [n_images][n_objects][16] and, these forms having no scene, the objects themselves:
+ * object_ids [n_images][h][w] i32, -1 (or any id outside [0, n_objects)) = static.  The motions of images 1 .. n_images - 1 are read; image 0's never is, with
+ * history_in or without.  history_in works as before. */
+int ptmi_accumulate_images_motion(ptmi_ctx* ctx, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                  const float* frame_nums, const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees,
+                                  const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out);
+int ptmi_accumulate_reference_motion(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                     const float* frame_nums, const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees,
+                                     const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out,
+                                     int threads);
+/* No GPU: THE OBJECT OF A PIXEL (above) for every pixel of layers [n_images][3][h][w][4] (of which layer 2 is read) over host copies of the scene buffers in their
+ * reference layouts — spheres 8 f32 each, quads 20, triangles 24 (in the order the layers were rendered in: ptmi_read_scene_buffer(5)), meshes 4 i32; an array whose
+ * count is 0 may be NULL — into ids_out [n_images][h][w] i32, -1 = none: the id image the two calls above take, through the header the kernel resolves it with. */
+int ptmi_object_ids_reference(const float* layers, int w, int h, uint32_t n_images, const float* spheres, uint32_t n_spheres, const float* quads, uint32_t n_quads,
+                              const float* triangles, uint32_t n_triangles, const int32_t* meshes, uint32_t n_meshes, int32_t* ids_out);
+/* No GPU: the motions of one step from the transform tables (binding 7: per object model[16], invModel[16], 128 bytes) of the earlier view, prev32, and the later one,
+ * cur32, n_objects records each, into motions16_out [n_objects][16].  An object whose two records are bytewise equal gets the exact identity.  Every other object gets
+ * model_prev . invModel_cur: element (i, j) = ((P_i0 C_0j + P_i1 C_1j) + P_i2 C_2j) + P_i3 C_3j in f64 from the stored f32 elements, rounded to f32 once. */
+int ptmi_motions_from_transforms(const float* prev32, const float* cur32, uint32_t n_objects, float* motions16_out);
+
 /* Test hook, no GPU: the SLOT TABLE ptmi_render_views_frames and ptmi_render_aov_frames upload behind the call's view matrices, u32 words:
  *   words [4 v .. 4 v + 3], v < n_views   view v's record {first slot, frame count, first frame number, next view with a non-zero count or n_views}; a view with
  *                                         count 0 has the first slot of the view that follows it (n_slots behind the last)

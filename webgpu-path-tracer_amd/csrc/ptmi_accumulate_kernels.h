@@ -10,11 +10,17 @@
 //                       as k_fuse's are.  Three float4 stores per pixel.  No LDS, no scratch, no atomics.  The planes read and the planes written are parts of one
 //                       allocation: none of the six pointers is __restrict__.  Per pixel, as compiled (of I only z is read, of plane 2 at q only
 //                       xyz): 68 B read of p, up to 80 B gathered at q, 48 B stored, and one material-type byte (profiles/accumulate_kernel_resources.txt).
+// k_accumulate_view_motion  The same body with MOTION (ptmi_accumulate_views_motion, include/ptmi_motion.h): between the world point and its projection a lane finds its
+//                       pixel's object — from the call's id image where there is one (ptmi_accumulate_images_motion), else INSIDE the kernel from I of p, which it
+//                       holds already, through the call's three small id tables and, for a triangle, one 4-byte gather of its mesh index — and, where that object has a
+//                       record, loads the record's six float4 PER LANE (the object varies within a wave) and moves the point and the normal unless the record is the
+//                       identity.  Up to three dependent gathers (triangle, mesh id, record) stand before the six at q; the other two entries compile none of it.
 // k_accumulated_variance  k_guided_variance (ptmi_guided_kernels.h: the same tile, the same staging, the same 7 x 7 walk) for a stack that brings its variance
 //                       with it: v0 is plane 2's w where that is not NaN, the spatial estimate elsewhere.  A second kernel beside k_guided_variance, which stays as it is.
 #pragma once
 
 #include "../../include/ptmi_accumulate.h"
+#include "../../include/ptmi_motion.h"
 #include "ptmi_fuse_kernels.h"
 #include "ptmi_guided_kernels.h"
 
@@ -26,14 +32,39 @@ DEV void accumulate_loaded(const float4& S, const float4& N, const float4& A, co
   asm volatile("" ::"v"(P1.x), "v"(P1.y), "v"(P1.z), "v"(P1.w), "v"(P2.x), "v"(P2.y), "v"(P2.z));
 }
 
+// What k_accumulate_view_motion has beside its siblings' operands.  records: view v's n_objects records (ptmm_record: six float4 each); ids: view v's [npix] object ids
+// (-1: none), or nullptr: the object comes from I through sphere_obj [n_spheres], quad_obj [n_quads], mesh_obj [n_meshes] (one i32 each) and tris (24 f32 per triangle).
+struct MotionArgs {
+  const float4* records;
+  const int32_t* ids;
+  const int32_t *sphere_obj, *quad_obj, *mesh_obj;
+  const float* tris;
+  uint32_t n_objects, n_spheres, n_quads, n_tris, n_meshes;
+};
+
+// The motion of pixel idx's object on its world point X and on the normal in gw (ptmm_move); 0: nothing is taken over.  A static pixel and an identity record leave both.
+DEV int accumulate_move(const MotionArgs& mo, uint32_t idx, const float4& Ip, float* X, ptmd_f4* gw) {
+  const int32_t obj = mo.ids ? mo.ids[idx] : ptmm_object(dn_f4(Ip), mo.sphere_obj, mo.n_spheres, mo.quad_obj, mo.n_quads, mo.tris, mo.n_tris, mo.mesh_obj, mo.n_meshes);
+  if (!ptmm_has_record(obj, mo.n_objects)) return 1;
+  const float4* rp = mo.records + 6 * (size_t)obj;
+  const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3], r4 = rp[4], r5 = rp[5];  // six independent loads
+  if (__float_as_uint(r5.y) != 0u) return 1;  // ptmm_record::identity
+  ptmm_record R;
+  R.g[0] = r0.x, R.g[1] = r0.y, R.g[2] = r0.z, R.g[3] = r0.w, R.g[4] = r1.x, R.g[5] = r1.y, R.g[6] = r1.z, R.g[7] = r1.w;
+  R.g[8] = r2.x, R.g[9] = r2.y, R.g[10] = r2.z, R.g[11] = r2.w;
+  R.gn[0] = r3.x, R.gn[1] = r3.y, R.gn[2] = r3.z, R.gn[3] = r3.w, R.gn[4] = r4.x, R.gn[5] = r4.y, R.gn[6] = r4.z, R.gn[7] = r4.w, R.gn[8] = r5.x;
+  return ptmm_move(&R, X, gw);
+}
+
 // colour, moments: [n_stack][npix] float4 sums; layers: [n_stack][3][npix] float4; prev1, prev2: planes 1 and 2 of view v - 1 ([npix] float4 each), nullptr: view v has
 // no history; out0, out1, out2: view v's image of planes 0, 1, 2; tab: kFuseRow float4 per view of the stack; lamb: one byte per material index or nullptr.
 // grid: x = (tiles of 64 columns x rows) / 4; block 256.
 // FRAMES: frames [n_stack] f32, F_u of every view of the stack; k.F is then not read: own, mean and the pass-through take F_v, the lookup's validity test F_{v-1}.
-template <bool FRAMES>
+// MOTION: mo as above; every other instance is handed an empty one and reads none of it.
+template <bool FRAMES, bool MOTION = false>
 DEV void accumulate_view(const float4* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ layers, const float4* prev1, const float4* prev2,
                          float4* out0, float4* out1, float4* out2, const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t v,
-                         ptmf_consts k, ptma_consts ka, const float* __restrict__ frames) {
+                         ptmf_consts k, ptma_consts ka, const float* __restrict__ frames, const MotionArgs& mo = MotionArgs{}) {
   const uint32_t tiles_x = ((uint32_t)W + 63u) / 64u;
   const uint32_t tile = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);  // wave-uniform
   const uint32_t y = tile / tiles_x;
@@ -59,7 +90,9 @@ DEV void accumulate_view(const float4* __restrict__ colour, const float4* __rest
     float X[3], r;
     int qx, qy;
     ptmf_world(&k, &V, x, idx, gp.w, X);
-    if (ptmf_project(&k, &U, X, &qx, &qy, &r)) {
+    int moved = 1;
+    if constexpr (MOTION) moved = accumulate_move(mo, idx, Ip, X, &gp);  // (gp's normal is read by the weight alone from here on)
+    if (moved && ptmf_project(&k, &U, X, &qx, &qy, &r)) {
       const size_t q = (size_t)qy * (size_t)W + (size_t)qx;
       const float4* Lu = layers + (size_t)(v - 1u) * 3 * npix;
       const float4 Sq = colour[(size_t)(v - 1u) * npix + q], Nq = Lu[q], Aq = Lu[npix + q], Iq = Lu[2 * npix + q], H1 = prev1[q], H2 = prev2[q];  // six independent gathers
@@ -95,6 +128,14 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_view_frames(const float4*
                                                                    const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H,
                                                                    uint32_t v, ptmf_consts k, ptma_consts ka, const float* __restrict__ frames) {
   accumulate_view<true>(colour, moments, layers, prev1, prev2, out0, out1, out2, tab, lamb, n_materials, W, H, v, k, ka, frames);
+}
+
+// k_accumulate_view_frames with the motions of the views' objects (ptmi_accumulate_views_motion, ptmi_accumulate_images_motion)
+__global__ __launch_bounds__(kBlock) void k_accumulate_view_motion(const float4* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ layers,
+                                                                   const float4* prev1, const float4* prev2, float4* out0, float4* out1, float4* out2,
+                                                                   const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H,
+                                                                   uint32_t v, ptmf_consts k, ptma_consts ka, const float* __restrict__ frames, MotionArgs mo) {
+  accumulate_view<true, true>(colour, moments, layers, prev1, prev2, out0, out1, out2, tab, lamb, n_materials, W, H, v, k, ka, frames, mo);
 }
 
 // grid: x = tiles of 64 columns, y = tiles of kGuidedTY rows, z = view of the batch.  d0: [n][npix] packed (prepare); plane2: [n][npix] float4, w = the given v0 or NaN

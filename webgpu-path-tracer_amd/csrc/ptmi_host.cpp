@@ -23,6 +23,7 @@
 #include "../../include/ptmi_guided.h"
 #include "../../include/ptmi_fuse.h"
 #include "../../include/ptmi_accumulate.h"
+#include "../../include/ptmi_motion.h"
 #include "../../include/ptmi_noise.h"
 #include "ptmi_bvh_domain.h"
 
@@ -1019,9 +1020,16 @@ extern "C" void ptmi_default_accumulate_params(ptmi_accumulate_params* p) {
 // A plain loop over views, in order, and pixels through include/ptmi_accumulate.h, the header the kernel of ptmi_accumulate_views compiles.  View v reads planes 1 and 2
 // of view v-1 in `out`, as the kernel does.  Nothing is tiled or reordered; `threads` > 1 share the rows of a view, whose pixels do not depend on one another.
 // frame_nums: nullptr, or every image's own divisor (ptmi_accumulate_reference_frames): own, mean and the pass-through of view v take F_v, the lookup in view v-1 F_{v-1}.
+// motion: nullptr, or the motions and the id images of ptmi_accumulate_reference_motion: between the world point and its projection a pixel whose object has a record
+// that is not the identity moves the point and the normal (include/ptmi_motion.h); every other pixel runs what it ran.
+struct ReferenceMotion {
+  const float* motions16;  // [n_images][n_objects][16]
+  uint32_t n_objects;
+  const int32_t* object_ids;  // [n_images][h][w]
+};
 static int accumulate_reference(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
                                 const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
-                                const float* history_in, float* out, int threads) {
+                                const float* history_in, float* out, int threads, const ReferenceMotion* motion = nullptr) {
   if (!colour_sums || !moments || !layers || !views16 || !out || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
   ptmi_accumulate_params P;
   if (params) P = *params;
@@ -1038,6 +1046,18 @@ static int accumulate_reference(const float* colour_sums, const float* moments, 
   }
   for (uint32_t v = 0; v < n_images; v++)
     if (!ptmf_make_view(views16 + 16 * (size_t)v, &tab[v])) return PTMI_ERR_INVALID_ARG;
+  std::vector<ptmm_record> rec;  // images 1 .. n_images - 1 have a predecessor: their motions are the ones read
+  if (motion) {
+    if (!motion->motions16 || !motion->object_ids || (uint64_t)n_images * motion->n_objects > (uint64_t)PTMI_MOTION_MAX_RECORDS) return PTMI_ERR_INVALID_ARG;
+    try {
+      rec.resize((size_t)(n_images - 1) * motion->n_objects);
+    } catch (const std::bad_alloc&) {
+      return PTMI_ERR_NO_MEMORY;
+    }
+    for (uint32_t v = 1; v < n_images; v++)
+      for (uint32_t o = 0; o < motion->n_objects; o++)
+        if (!ptmm_make_record(motion->motions16 + 16 * ((size_t)v * motion->n_objects + o), &rec[(size_t)(v - 1) * motion->n_objects + o])) return PTMI_ERR_INVALID_ARG;
+  }
   ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor), ku = k;
   const ptma_consts ka = ptma_make_consts(P.max_history, P.min_frames);
   const size_t npix = (size_t)w * (size_t)h;
@@ -1074,7 +1094,15 @@ static int accumulate_reference(const float* colour_sums, const float* moments, 
             float X[3], r, wgt;
             int qx, qy;
             ptmf_world(&k, &tab[v], x, idx, gp.w, X);
-            if (ptmf_project(&k, &tab[v - 1], X, &qx, &qy, &r)) {
+            int moved = 1;
+            if (motion) {
+              const int32_t obj = motion->object_ids[(size_t)v * npix + idx];
+              if (ptmm_has_record(obj, motion->n_objects)) {
+                const ptmm_record* R = &rec[(size_t)(v - 1) * motion->n_objects + (uint32_t)obj];
+                if (!R->identity) moved = ptmm_move(R, X, &gp);  // (gp's normal is read by the weight alone from here on)
+              }
+            }
+            if (moved && ptmf_project(&k, &tab[v - 1], X, &qx, &qy, &r)) {
               const size_t q = (size_t)qy * (size_t)w + (size_t)qx;
               if (ptma_weight(&ku, dp, gp, r, S[(size_t)(v - 1) * npix + q], Lu[q], Lu[npix + q], Lu[2 * npix + q], &wgt)) ptma_take(&ka, wgt, prev1[q], prev2[q], &P1, &P2);
             }
@@ -1100,6 +1128,56 @@ extern "C" int ptmi_accumulate_reference_frames(const float* colour_sums, const 
                                                 const ptmi_accumulate_params* params, const float* history_in, float* out, int threads) {
   if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
   return accumulate_reference(colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, fov_degrees, lambertian, n_materials, params, history_in, out, threads);
+}
+extern "C" int ptmi_accumulate_reference_motion(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                                const float* frame_nums, const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees,
+                                                const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out,
+                                                int threads) {
+  if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
+  const ReferenceMotion motion{motions16, n_objects, object_ids};
+  return accumulate_reference(colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, fov_degrees, lambertian, n_materials, params, history_in, out, threads,
+                              &motion);
+}
+
+// The object of every pixel (include/ptmi_motion.h, ptmm_object): the three id tables the kernel of ptmi_accumulate_views_motion is handed, made here from the records.
+extern "C" int ptmi_object_ids_reference(const float* layers, int w, int h, uint32_t n_images, const float* spheres, uint32_t n_spheres, const float* quads, uint32_t n_quads,
+                                         const float* triangles, uint32_t n_triangles, const int32_t* meshes, uint32_t n_meshes, int32_t* ids_out) {
+  if (!layers || !ids_out || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
+  if ((n_spheres && !spheres) || (n_quads && !quads) || (n_triangles && !triangles) || (n_meshes && !meshes)) return PTMI_ERR_INVALID_ARG;
+  std::vector<int32_t> obj;
+  try {
+    obj.resize((size_t)n_spheres + n_quads + n_meshes);
+  } catch (const std::bad_alloc&) {
+    return PTMI_ERR_NO_MEMORY;
+  }
+  int32_t *sphere_obj = obj.data(), *quad_obj = sphere_obj + n_spheres, *mesh_obj = quad_obj + n_quads;
+  for (uint32_t i = 0; i < n_spheres; i++) sphere_obj[i] = ptmm_f32_object(spheres[8 * (size_t)i + 4]);
+  for (uint32_t i = 0; i < n_quads; i++) quad_obj[i] = ptmm_f32_object(quads[20 * (size_t)i + 11]);
+  for (uint32_t i = 0; i < n_meshes; i++) mesh_obj[i] = ptmm_i32_object(meshes[4 * (size_t)i + 2]);
+  const size_t npix = (size_t)w * (size_t)h;
+  const ptmd_f4* L = reinterpret_cast<const ptmd_f4*>(layers);
+  for (uint32_t v = 0; v < n_images; v++)
+    for (size_t p = 0; p < npix; p++)
+      ids_out[(size_t)v * npix + p] = ptmm_object(L[((size_t)v * 3 + 2) * npix + p], sphere_obj, n_spheres, quad_obj, n_quads, triangles, n_triangles, mesh_obj, n_meshes);
+  return PTMI_OK;
+}
+
+// The motion of every object from one transform table to the next: model_prev . invModel_cur in f64, one fixed summation order, rounded once.
+extern "C" int ptmi_motions_from_transforms(const float* prev32, const float* cur32, uint32_t n_objects, float* motions16_out) {
+  if (!prev32 || !cur32 || !motions16_out) return PTMI_ERR_INVALID_ARG;
+  for (uint32_t o = 0; o < n_objects; o++) {
+    const float *P = prev32 + 32 * (size_t)o, *C = cur32 + 32 * (size_t)o + 16;  // model of the earlier view, invModel of the later; column-major
+    float* G = motions16_out + 16 * (size_t)o;
+    if (memcmp(prev32 + 32 * (size_t)o, cur32 + 32 * (size_t)o, 128) == 0) {
+      for (int e = 0; e < 16; e++) G[e] = (e % 5 == 0) ? 1.0f : 0.0f;
+      continue;
+    }
+    for (int j = 0; j < 4; j++)
+      for (int i = 0; i < 4; i++)
+        G[4 * j + i] = (float)((((double)P[i] * (double)C[4 * j] + (double)P[4 + i] * (double)C[4 * j + 1]) + (double)P[8 + i] * (double)C[4 * j + 2]) +
+                               (double)P[12 + i] * (double)C[4 * j + 3]);
+  }
+  return PTMI_OK;
 }
 
 // ---- the noise statistic on the host (ptmi_noise_reference) ----

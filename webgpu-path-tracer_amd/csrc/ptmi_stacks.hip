@@ -361,6 +361,8 @@ static size_t fuse_tab_bytes(uint32_t n_stack, uint32_t n_materials, bool frames
 static const float* fuse_tab_frames_ptr(const void* tab, uint32_t n_stack, uint32_t n_materials) {
   return reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(tab) + fuse_tab_frames(n_stack, n_materials));
 }
+// ... and the *_motion calls their records and id tables behind the frame counts, on the next multiple of 16 (motion_args: the layout)
+static size_t fuse_tab_extra(uint32_t n_stack, uint32_t n_materials) { return (fuse_tab_bytes(n_stack, n_materials, true) + 15) & ~(size_t)15; }
 
 // Fills `tab` (fuse_tab_bytes) from the matrices of all views and the material-type bytes; PTMI_ERR_INVALID_ARG for a matrix that cannot be inverted.
 static int fuse_fill_tab(ptmi_ctx* c, const char* who, const float* views16, uint32_t n_stack, const uint8_t* lamb, uint32_t n_materials, float* tab) {
@@ -407,9 +409,11 @@ static int fuse_check_args(ptmi_ctx* c, const char* who, const ptmi_fuse_params*
 // What ptmi_fuse_views and ptmi_accumulate_views do before they enqueue a kernel: the table of all views of the stack with the uploaded materials' types, the call's
 // stack `k` (of the view stack's size) and the table's two copies — everything that can fail for want of memory, before anything is enqueued — and then the
 // table's upload.  frame_nums: nullptr, or the stack's frame counts (checked), which go behind the table's material bytes.
-static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, const float* views16, const float* frame_nums = nullptr) {
+// extra: nullptr, or extra_bytes that a call with frame_nums puts behind them, 16-byte aligned (fuse_tab_extra: where).
+static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, const float* views16, const float* frame_nums = nullptr, const void* extra = nullptr,
+                                 size_t extra_bytes = 0) {
   const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  const size_t tab_bytes = fuse_tab_bytes(n_stack, n_mat, frame_nums != nullptr);
+  const size_t tab_bytes = extra ? fuse_tab_extra(n_stack, n_mat) + extra_bytes : fuse_tab_bytes(n_stack, n_mat, frame_nums != nullptr);
   std::vector<float> tab;
   std::vector<uint8_t> lamb;
   try {
@@ -421,6 +425,7 @@ static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, cons
   for (uint32_t i = 0; i < n_mat; i++) lamb[i] = c->h_mats[16 * (size_t)i + 14] == PTMF_LAMBERTIAN;
   if (int r = fuse_fill_tab(c, who, views16, n_stack, lamb.data(), n_mat, tab.data())) return r;
   if (frame_nums) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_frames(n_stack, n_mat), frame_nums, (size_t)n_stack * 4);
+  if (extra) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_extra(n_stack, n_mat), extra, extra_bytes);
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
   DBuf stack;
@@ -512,7 +517,8 @@ int ptmi_fuse_images_frames(ptmi_ctx* c, const float* colour, const float* layer
 // [first, first + n) are written, one launch per view in ascending order; view `first` takes its history from view first - 1 of `planes` when `resume`.
 // frames: nullptr, or the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_accumulate_view_frames.
 static int accumulate_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, const float4* layers, float4* planes, const void* tab, bool has_lamb, uint32_t n_materials,
-                              int W, int H, uint32_t n_stack, uint32_t first, uint32_t n, bool resume, const ptmf_consts& k, const ptma_consts& ka, const float* frames = nullptr) {
+                              int W, int H, uint32_t n_stack, uint32_t first, uint32_t n, bool resume, const ptmf_consts& k, const ptma_consts& ka, const float* frames = nullptr,
+                              const MotionArgs* motion = nullptr) {
   const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
   const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
   const uint8_t* lamb = has_lamb ? reinterpret_cast<const uint8_t*>(tab) + (size_t)n_stack * kFuseRow * 16 : nullptr;
@@ -520,7 +526,13 @@ static int accumulate_enqueue(ptmi_ctx* c, const float4* colour, const float4* m
   auto plane = [&](uint32_t pl, uint32_t v) { return planes + ((size_t)pl * n_stack + v) * npix; };
   for (uint32_t v = first; v < first + n; v++) {
     const bool has_prev = v > 0 && (v > first || resume);
-    if (frames)
+    if (motion) {  // (with frames.)  The records of the call lie view after view from the first view that has a predecessor; a view without one reads none.
+      MotionArgs mo = *motion;
+      if (has_prev) mo.records += (size_t)(v - (resume ? first : first + 1u)) * mo.n_objects * 6;
+      if (mo.ids) mo.ids += (size_t)v * npix;
+      hipLaunchKernelGGL(k_accumulate_view_motion, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr,
+                         has_prev ? plane(2, v - 1) : nullptr, plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka, frames, mo);
+    } else if (frames)
       hipLaunchKernelGGL(k_accumulate_view_frames, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr,
                          has_prev ? plane(2, v - 1) : nullptr, plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka, frames);
     else
@@ -538,14 +550,35 @@ static int accumulate_check_args(ptmi_ctx* c, const char* who, const ptmi_accumu
   return check_stack_call(c, who, "a view's pixels", "several", ok ? nullptr : "max_history, sigma_normal, sigma_depth and albedo_floor > 0, all finite, and min_frames >= 2", true, frame_num);
 }
 
-// ptmi_accumulate_views (per_view false: frame_num) and ptmi_accumulate_views_frames (per_view: frame_nums, one per view of the stack)
+// The *_motion calls: the records (include/ptmi_motion.h) of views [lo, hi) of motions16 [n_all][n_objects][16], the entries the call reads, view after view into
+// `rec`; each has to be finite with a 3x3 that can be inverted — the others may hold anything.  Allocates host memory only.
+static int make_motion_records(ptmi_ctx* c, const char* who, const float* motions16, uint32_t n_objects, uint32_t n_all, uint32_t lo, uint32_t hi, std::vector<ptmm_record>* rec) {
+  if (!motions16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null motions16");
+  if ((uint64_t)n_all * n_objects > (uint64_t)PTMI_MOTION_MAX_RECORDS)
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": " + std::to_string(n_all) + " views x " + std::to_string(n_objects) + " objects are more than PTMI_MOTION_MAX_RECORDS motions");
+  try {
+    rec->resize((size_t)(hi > lo ? hi - lo : 0) * n_objects);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the motion records");
+  }
+  for (uint32_t v = lo; v < hi; v++)
+    for (uint32_t o = 0; o < n_objects; o++)
+      if (!ptmm_make_record(motions16 + 16 * ((size_t)v * n_objects + o), &(*rec)[(size_t)(v - lo) * n_objects + o]))
+        return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the motion of view " + std::to_string(v) + ", object " + std::to_string(o) +
+                                                 " has a non-finite element or a 3x3 with a zero or non-finite determinant: view " + std::to_string(v) + " is read by this call");
+  return PTMI_OK;
+}
+
+// ptmi_accumulate_views (per_view false: frame_num), ptmi_accumulate_views_frames (per_view: frame_nums, one per view of the stack) and ptmi_accumulate_views_motion
+// (motion: per_view, and motions16 [n_views of the stack][n_objects][16])
 static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_params* params, const float* views16, float frame_num, const float* frame_nums, bool per_view,
-                            uint32_t first_view, uint32_t n_views, int resume) {
+                            uint32_t first_view, uint32_t n_views, int resume, bool motion = false, const float* motions16 = nullptr, uint32_t n_objects = 0) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_accumulate_params P;
   if (int r = accumulate_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
   if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (motion && !motions16) return make_motion_records(c, who, nullptr, 0, 0, 0, 0, nullptr);
   if (int r = check_stack(c, STACK_MOMENTS, who, 0)) return r;  // (the moment stack first, as ptmi_denoise_views_guided asks)
   if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
   if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
@@ -558,12 +591,41 @@ static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_
   if (per_view)  // the call's range, and the view before it where its state is taken over
     if (int r = check_frame_nums(c, who, frame_nums, resume ? first_view - 1u : first_view, first_view + n_views)) return r;
   const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  if (int r = make_stack_with_table(c, who, STACK_ACCUMULATED, views16, per_view ? frame_nums : nullptr)) return r;
+  // A *_motion call's part of the table: the records of the views it reads, then one object id per sphere, per quad and per mesh of the scene as it is uploaded now —
+  // from the host copies, so that no device buffer a render has yet to refresh is read.  The triangles are on the device already (ptmi_upload puts them there).
+  std::vector<uint32_t> blob;
+  MotionArgs mo{};
+  if (motion) {
+    std::vector<ptmm_record> rec;
+    if (int r = make_motion_records(c, who, motions16, n_objects, n_stack, resume ? first_view : first_view + 1u, first_view + n_views, &rec)) return r;
+    mo.n_objects = n_objects, mo.n_spheres = (uint32_t)(c->h_spheres.size() / 8), mo.n_quads = (uint32_t)(c->h_quads.size() / 20);
+    mo.n_tris = (uint32_t)c->n_tris_uploaded, mo.n_meshes = (uint32_t)(c->h_meshes.size() / 4);
+    const size_t rec_words = rec.size() * (sizeof(ptmm_record) / 4);
+    try {
+      blob.resize(std::max<size_t>(1, rec_words + mo.n_spheres + mo.n_quads + mo.n_meshes));  // (one word at least: blob.data() tells make_stack_with_table that there is such a part)
+    } catch (const std::bad_alloc&) {
+      return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the motion table");
+    }
+    if (rec_words) memcpy(blob.data(), rec.data(), rec_words * 4);
+    int32_t* ids = reinterpret_cast<int32_t*>(blob.data() + rec_words);
+    for (uint32_t i = 0; i < mo.n_spheres; i++) *ids++ = ptmm_f32_object(c->h_spheres[8 * (size_t)i + 4]);
+    for (uint32_t i = 0; i < mo.n_quads; i++) *ids++ = ptmm_f32_object(c->h_quads[20 * (size_t)i + 11]);
+    for (uint32_t i = 0; i < mo.n_meshes; i++) *ids++ = ptmm_i32_object(c->h_meshes[4 * (size_t)i + 2]);
+    if (int r = make_stack_with_table(c, who, STACK_ACCUMULATED, views16, frame_nums, blob.data(), blob.size() * 4)) return r;
+    const uint8_t* extra = reinterpret_cast<const uint8_t*>(c->fuse_tab.dev.p) + fuse_tab_extra(n_stack, n_mat);
+    mo.records = reinterpret_cast<const float4*>(extra);
+    mo.sphere_obj = reinterpret_cast<const int32_t*>(extra) + rec_words, mo.quad_obj = mo.sphere_obj + mo.n_spheres, mo.mesh_obj = mo.quad_obj + mo.n_quads;
+    mo.tris = c->d_tris.as<float>();
+  } else if (int r = make_stack_with_table(c, who, STACK_ACCUMULATED, views16, per_view ? frame_nums : nullptr)) return r;
   const float fov_factor = (float)(1.0 / std::tan((double)c->prm.fov_degrees * (3.14159265358979323846 / 180.0) / 2.0));  // as make_render_const folds it
   const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   return accumulate_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>(), c->stacks[STACK_MOMENTS].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(),
                             c->stacks[STACK_ACCUMULATED].buf.as<float4>(), c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, resume != 0, k,
-                            ptma_make_consts(P.max_history, P.min_frames), per_view ? fuse_tab_frames_ptr(c->fuse_tab.dev.p, n_stack, n_mat) : nullptr);
+                            ptma_make_consts(P.max_history, P.min_frames), per_view ? fuse_tab_frames_ptr(c->fuse_tab.dev.p, n_stack, n_mat) : nullptr, motion ? &mo : nullptr);
+}
+int ptmi_accumulate_views_motion(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects,
+                                 uint32_t first_view, uint32_t n_views, int resume) {
+  return accumulate_views(c, "ptmi_accumulate_views_motion", params, views16, 1.0f, frame_nums, true, first_view, n_views, resume, true, motions16, n_objects);
 }
 int ptmi_accumulate_views(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, float frame_num, uint32_t first_view, uint32_t n_views, int resume) {
   return accumulate_views(c, "ptmi_accumulate_views", params, views16, frame_num, nullptr, false, first_view, n_views, resume);
@@ -581,11 +643,18 @@ int ptmi_accumulated_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* 
 }
 int ptmi_release_accumulated(ptmi_ctx* c) { return release_stack(c, STACK_ACCUMULATED); }
 
-// ptmi_accumulate_images (per_view false) and ptmi_accumulate_images_frames (frame_nums: one per image)
+// What ptmi_accumulate_images_motion has beside ptmi_accumulate_images_frames' arguments: motions16 [n_images][n_objects][16], object_ids [n_images][h][w] i32
+struct MotionImages {
+  const float* motions16;
+  uint32_t n_objects;
+  const int32_t* object_ids;
+};
+
+// ptmi_accumulate_images (per_view false), ptmi_accumulate_images_frames (frame_nums: one per image) and ptmi_accumulate_images_motion (motion, with per_view)
 static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
                              float frame_num, const float* frame_nums, bool per_view, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
-                             const ptmi_accumulate_params* params, const float* history_in, float* out) {
-  if (!c || !colour_sums || !moments || !layers || !views16 || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+                             const ptmi_accumulate_params* params, const float* history_in, float* out, const MotionImages* motion = nullptr) {
+  if (!c || !colour_sums || !moments || !layers || !views16 || !out || (motion && !motion->object_ids)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_accumulate_params P;
   if (int r = accumulate_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
   if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
@@ -594,6 +663,9 @@ static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_s
     if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
   if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": fov_degrees must be in (0,180)");
   if (history_in && n_images < 2) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": history_in makes image 0 the view before the first: need n_images >= 2");
+  std::vector<ptmm_record> rec;  // (images 1 .. n_images - 1 have a predecessor, with or without history_in)
+  if (motion)
+    if (int r = make_motion_records(c, who, motion->motions16, motion->n_objects, n_images, 1, n_images, &rec)) return r;
   if (!lambertian) n_materials = 0;
   const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials, per_view);
   std::vector<float> tab;
@@ -611,9 +683,20 @@ static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_s
   (void)hipGetLastError();
   DBuf mom, dtab;  // (on_host_images brings the colour, the layers, the three planes and the table; the moments are this call's own, had before anything is enqueued)
   HIP_TRY(c, mom.ensure(bytes));
+  DBuf drec, dids;  // (a *_motion call's records and id images: its own too)
+  MotionArgs mo{};
+  if (motion) {
+    HIP_TRY(c, drec.ensure(std::max<size_t>(rec.size() * sizeof(ptmm_record), 16)));
+    HIP_TRY(c, dids.ensure(npix * 4 * n_images));
+    mo.records = drec.as<float4>(), mo.ids = dids.as<int32_t>(), mo.n_objects = motion->n_objects;
+  }
   return on_host_images(c, who, colour_sums, layers, npix, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
     HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(mom.p, moments, bytes, hipMemcpyHostToDevice, c->stream));
+    if (motion) {
+      if (!rec.empty()) HIP_TRY(c, hipMemcpyAsync(drec.p, rec.data(), rec.size() * sizeof(ptmm_record), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(dids.p, motion->object_ids, npix * 4 * n_images, hipMemcpyHostToDevice, c->stream));
+    }
     if (history_in) {  // image 0 is the view before the first: its state is given, its mean is not made
       HIP_TRY(c, hipMemsetAsync(res, 0, npix * 16, c->stream));
       HIP_TRY(c, hipMemcpyAsync(res + (size_t)n_images * npix, history_in, npix * 16, hipMemcpyHostToDevice, c->stream));
@@ -621,7 +704,7 @@ static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_s
     }
     const uint32_t first = history_in ? 1u : 0u;
     return accumulate_enqueue(c, col, mom.as<float4>(), lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, first, n_images - first, history_in != nullptr, k, ka,
-                              per_view ? fuse_tab_frames_ptr(dtab.p, n_images, n_materials) : nullptr);
+                              per_view ? fuse_tab_frames_ptr(dtab.p, n_images, n_materials) : nullptr, motion ? &mo : nullptr);
   }, 3, 48);
 }
 int ptmi_accumulate_images(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
@@ -634,6 +717,13 @@ int ptmi_accumulate_images_frames(ptmi_ctx* c, const float* colour_sums, const f
                                   const float* history_in, float* out) {
   return accumulate_images(c, "ptmi_accumulate_images_frames", colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params,
                            history_in, out);
+}
+int ptmi_accumulate_images_motion(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                  const float* frame_nums, const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian,
+                                  uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out) {
+  const MotionImages motion{motions16, n_objects, object_ids};
+  return accumulate_images(c, "ptmi_accumulate_images_motion", colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params,
+                           history_in, out, &motion);
 }
 
 int ptmi_denoise_views_accumulated(ptmi_ctx* c, const ptmi_guided_params* params, uint32_t first_view, uint32_t n_views) {

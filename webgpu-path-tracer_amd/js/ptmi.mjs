@@ -91,6 +91,11 @@ export class Ptmi {
   accumulateViewsFrames(views, frameNums, firstView, nViews, resume = false, params = null) {
     this.native.accumulateViewsFrames(this.h, views, Float32Array.from(frameNums), firstView, nViews, resume, params);
   }
+  // ptmi_accumulate_views_motion: motions holds, per view of the stack and object (global_id), the column-major matrix that carries a world point of the object at
+  // the time of view v to the same material point at the time of view v - 1: Float32Array [view][object][16]
+  accumulateViewsMotion(views, frameNums, motions, nObjects, firstView, nViews, resume = false, params = null) {
+    this.native.accumulateViewsMotion(this.h, views, Float32Array.from(frameNums), motions, nObjects, firstView, nViews, resume, params);
+  }
   synchronize() { this.native.synchronize(this.h); }
   prepare() { this.native.prepare(this.h); }
   buildSceneBVHSAH() { this.native.buildSceneBVHSAH(this.h); }   // the same with the reference's never-called SAH builder (lib/BVH/bvhNode.js:108-283): opt-in

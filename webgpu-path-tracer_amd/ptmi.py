@@ -38,7 +38,10 @@ SYMBOLS = [
     "ptmi_denoise_images_frames", "ptmi_denoise_images_guided_frames", "ptmi_fuse_images_frames", "ptmi_accumulate_images_frames",
     "ptmi_denoise_reference_frames", "ptmi_denoise_guided_reference_frames", "ptmi_fuse_reference_frames", "ptmi_accumulate_reference_frames",
     "ptmi_refit_bvh", "ptmi_refit_scene_bvh",
+    "ptmi_accumulate_views_motion", "ptmi_accumulate_images_motion", "ptmi_accumulate_reference_motion", "ptmi_object_ids_reference", "ptmi_motions_from_transforms",
 ]
+
+MOTION_MAX_RECORDS = 1 << 20  # PTMI_MOTION_MAX_RECORDS
 
 VIEW_SLOT_TABLE_MAX_WORDS = 1 << 24  # PTMI_VIEW_SLOT_TABLE_MAX_WORDS
 
@@ -279,6 +282,13 @@ def load_library(build=False, path=None):
     if hasattr(L, "ptmi_refit_scene_bvh"):  # (an older A/B build loaded through PTMI_LIB rebuilds a stale tree)
         L.ptmi_refit_bvh.argtypes = [sz, fp, fp, fp, sz]
         L.ptmi_refit_scene_bvh.argtypes = [vp]
+    if hasattr(L, "ptmi_accumulate_views_motion"):  # (an older A/B build loaded through PTMI_LIB accumulates through a static world)
+        ap = ctypes.POINTER(AccumulateParams)
+        L.ptmi_accumulate_views_motion.argtypes = [vp, ap, fp, fp, fp, u32, u32, u32, i32]
+        L.ptmi_accumulate_images_motion.argtypes = [vp, fp, fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, ctypes.c_float, fp, u32, ap, fp, fp]
+        L.ptmi_accumulate_reference_motion.argtypes = [fp, fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, ctypes.c_float, fp, u32, ap, fp, fp, i32]
+        L.ptmi_object_ids_reference.argtypes = [fp, i32, i32, u32, fp, u32, fp, u32, fp, u32, fp, u32, fp]
+        L.ptmi_motions_from_transforms.argtypes = [fp, fp, u32, fp]
     if explicit:
         _libs[path] = L
     else:
@@ -499,6 +509,62 @@ def accumulate_reference_frames(colour_sums, moments, layers, views, frame_nums,
                                                                   _optr(hist), _ptr(out), int(threads))
     if st != 0:
         raise PtmiError(st, "ptmi_accumulate_reference_frames failed")
+    return out
+
+
+def _motion_arrays(motions, object_ids, n, image_shape=None):
+    """The motions (n, n_objects, 16) and, where the call takes them, the id images (n, H, W) of the *_motion calls; None stays a null pointer, which the library
+    refuses.  Returns (motions, n_objects, object_ids)."""
+    g = None if motions is None else np.ascontiguousarray(motions, np.float32).reshape(n, -1, 16)
+    ids = None if object_ids is None else np.ascontiguousarray(object_ids, np.int32).reshape((n,) + tuple(image_shape))
+    return g, 0 if g is None else g.shape[1], ids
+
+
+def accumulate_reference_motion(colour_sums, moments, layers, views, frame_nums, motions, object_ids, fov_degrees=60.0, lambertian=None, params=None, history=None,
+                                threads=1, n_objects=None, lib=None):
+    """ptmi_accumulate_reference_motion: accumulate_reference_frames through a world whose objects move — motions (n, n_objects, 16): per image and object the
+    column-major matrix that carries a world point of the object at the time of image v to the same material point at the time of image v-1 (image 0's are not
+    read); object_ids (n, H, W) int32: every pixel's object, -1 = static (object_ids_reference).  n_objects: for a call with no motions array (tests)."""
+    c, m, l, v, t, hist, out = _accumulate_arrays(colour_sums, moments, layers, views, lambertian, history)
+    f = _frame_nums(frame_nums, c.shape[0])
+    g, n_obj, ids = _motion_arrays(motions, object_ids, c.shape[0], c.shape[1:3])
+    st = (lib or load_library()).ptmi_accumulate_reference_motion(_ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), _optr(g),
+                                                                  n_obj if n_objects is None else n_objects, _optr(ids), float(fov_degrees), _optr(t),
+                                                                  0 if t is None else t.size, None if params is None else ctypes.byref(params), _optr(hist), _ptr(out),
+                                                                  int(threads))
+    if st != 0:
+        raise PtmiError(st, "ptmi_accumulate_reference_motion failed")
+    return out
+
+
+def object_ids_reference(layers, spheres=None, quads=None, triangles=None, meshes=None, lib=None):
+    """ptmi_object_ids_reference: every pixel's object (global_id) from layer 2 of layers (n, 3, H, W, 4) and host copies of the scene buffers in their reference
+    layouts — spheres (., 8), quads (., 20), triangles (., 24) float32 IN THE ORDER THE LAYERS WERE RENDERED IN (Context.read_scene_buffer(5, n)), meshes (., 4)
+    int32; None: none of that kind.  Returns (n, H, W) int32, -1 where a pixel has no object."""
+    l = np.ascontiguousarray(layers, np.float32)
+    assert l.ndim == 5 and l.shape[1] == 3 and l.shape[4] == 4, "layers: (n, 3, H, W, 4)"
+    arrs = [None if a is None or np.size(a) == 0 else np.ascontiguousarray(a, ty).reshape(-1, k)
+            for a, ty, k in ((spheres, np.float32, 8), (quads, np.float32, 20), (triangles, np.float32, 24), (meshes, np.int32, 4))]
+    out = np.empty((l.shape[0], l.shape[2], l.shape[3]), np.int32)
+    args = []
+    for a in arrs:
+        args += [_optr(a), 0 if a is None else a.shape[0]]
+    st = (lib or load_library()).ptmi_object_ids_reference(_ptr(l), l.shape[3], l.shape[2], l.shape[0], *args, _ptr(out))
+    if st != 0:
+        raise PtmiError(st, "ptmi_object_ids_reference failed")
+    return out
+
+
+def motions_from_transforms(prev, cur, lib=None):
+    """ptmi_motions_from_transforms: the motions of one step, (n_objects, 16) float32, from the transform tables (n_objects, 32) of the earlier view (prev) and the
+    later one (cur): model_prev . invModel_cur, the exact identity for an object whose two records are bytewise equal."""
+    p = np.ascontiguousarray(prev, np.float32).reshape(-1, 32)
+    c = np.ascontiguousarray(cur, np.float32).reshape(-1, 32)
+    assert p.shape == c.shape, "prev and cur: the same number of objects"
+    out = np.empty((p.shape[0], 16), np.float32)
+    st = (lib or load_library()).ptmi_motions_from_transforms(_ptr(p), _ptr(c), p.shape[0], _ptr(out))
+    if st != 0:
+        raise PtmiError(st, "ptmi_motions_from_transforms failed")
     return out
 
 
@@ -954,6 +1020,54 @@ class Context:
         self._ck(self.lib.ptmi_accumulate_images_frames(self.h, _ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), float(fov_degrees),
                                                         _optr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params), _optr(hist), _ptr(out)))
         return out
+
+    # ---- accumulation through a world whose objects move (include/ptmi.h, "ACCUMULATION WITH PER-OBJECT MOTION") ----
+    def accumulate_views_motion(self, views, frame_nums, motions, first_view=0, n_views=None, resume=False, params=None, n_objects=None):
+        """ptmi_accumulate_views_motion: accumulate_views_frames with motions (n_views of the stack, n_objects, 16) — per view and object (global_id) the column-major
+        matrix that carries a world point of the object at the time of view v to the same material point at the time of view v-1 (render_moving_path returns them);
+        the entries of views first_view + 1 .. are read, and first_view's with resume.  The pixel's object is found in the scene AS IT IS UPLOADED NOW: it has
+        to be the one the feature stack was rendered from, its triangles in the order they lay in then.  refit_scene_bvh keeps that order; build_scene_bvh or an
+        upload of triangles between render_moving_path and this call changes it, and the call then takes wrong ids — every index is checked, so nothing worse.
+        Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        n_stack = self.views_device_ptr()[2]
+        assert v.shape[0] == n_stack, "views: the matrices of all %d views of the stack" % n_stack
+        f = _frame_nums(frame_nums, n_stack)
+        g, n_obj, _ = _motion_arrays(motions, None, n_stack)
+        if n_views is None:
+            n_views = n_stack - first_view
+        self._ck(self.lib.ptmi_accumulate_views_motion(self.h, None if params is None else ctypes.byref(params), _ptr(v), _optr(f), _optr(g),
+                                                       n_obj if n_objects is None else n_objects, first_view, n_views, 1 if resume else 0))
+
+    def accumulate_images_motion(self, colour_sums, moments, layers, views, frame_nums, motions, object_ids, fov_degrees=60.0, lambertian=None, params=None, history=None,
+                                 n_objects=None):
+        """ptmi_accumulate_images_motion: the kernel of accumulate_views_motion on host arrays of any size (see accumulate_reference_motion); synchronous."""
+        c, m, l, v, t, hist, out = _accumulate_arrays(colour_sums, moments, layers, views, lambertian, history)
+        f = _frame_nums(frame_nums, c.shape[0])
+        g, n_obj, ids = _motion_arrays(motions, object_ids, c.shape[0], c.shape[1:3])
+        self._ck(self.lib.ptmi_accumulate_images_motion(self.h, _ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), _optr(g),
+                                                        n_obj if n_objects is None else n_objects, _optr(ids), float(fov_degrees), _optr(t), 0 if t is None else t.size,
+                                                        None if params is None else ctypes.byref(params), _optr(hist), _ptr(out)))
+        return out
+
+    def render_moving_path(self, views, transforms_seq, first_frames, frame_counts):
+        """A camera path through a scene whose objects move, a host loop over existing calls: for every view v it uploads transforms_seq[v] ((n_objects, 32) float32,
+        binding 7's layout), refits the scene's device-resident tree (refit_scene_bvh) and renders that view alone — render_views_frames and render_aov_frames with
+        every other view's count 0, reset as those calls define it per view.  The view moments must be on (set_view_moments), so that the stacks are the ones
+        accumulate_views_motion needs.  Returns the motions it takes, (V, n_objects, 16): motions_from_transforms over the sequence, view 0's the identity."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        t = np.ascontiguousarray(transforms_seq, np.float32).reshape(v.shape[0], -1, 32)
+        f, k = _frame_arrays(v.shape[0], first_frames, frame_counts)
+        motions = np.empty((v.shape[0], t.shape[1], 16), np.float32)
+        for i in range(v.shape[0]):
+            self.upload("transforms", t[i])
+            self.refit_scene_bvh()
+            only = np.where(np.arange(v.shape[0]) == i, k, 0).astype(np.uint32)
+            self.render_views_frames(v, f, only, reset=True)
+            self.moments_device_ptr()  # (PTMI_ERR_STATE while the view moments are off: say so after the first view, not after the last)
+            self.render_aov_frames(v, f, only, reset=True)
+            motions[i] = motions_from_transforms(t[i - 1] if i else t[i], t[i], lib=self.lib)
+        return motions
 
     def set_view_moments(self, on=True):
         """ptmi_set_view_moments: while on, render_views also folds the frames' squared colours into the context's moment stack (read_moments); off frees it."""
