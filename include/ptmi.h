@@ -689,7 +689,7 @@ int ptmi_accumulate_reference_frames(const float* colour_sums, const float* mome
  * planes are untouched.  The operation order is fixed in include/ptmi_motion.h, which the kernel and the host reference both compile.  A camera that moves WITH an
  * object (both translated by T, G the translation by -T) has q = p and wgt exactly 1 on that object: n after k such views of one frame each is exactly k.
  *
- * OUT OF SCOPE: fusion (ptmi_fuse_views) with motions; an object test at q — q's object would need a second dependent chain, so the material, normal and depth tests
+ * OUT OF SCOPE: an object test at q — q's object would need a second dependent chain, so the material, normal and depth tests
  * stay the disocclusion tests; deforming meshes (per-vertex motion); multi-device contexts. */
 #define PTMI_MOTION_MAX_RECORDS (1u << 20)
 /* ptmi_accumulate_views_frames with motions; there is no one-frame_num twin.  Writes the same ACCUMULATED STACK: ptmi_read_accumulated,
@@ -718,6 +718,57 @@ int ptmi_object_ids_reference(const float* layers, int w, int h, uint32_t n_imag
  * cur32, n_objects records each, into motions16_out [n_objects][16].  An object whose two records are bytewise equal gets the exact identity.  Every other object gets
  * model_prev . invModel_cur: element (i, j) = ((P_i0 C_0j + P_i1 C_1j) + P_i2 C_2j) + P_i3 C_3j in f64 from the stored f32 elements, rounded to f32 once. */
 int ptmi_motions_from_transforms(const float* prev32, const float* cur32, uint32_t n_objects, float* motions16_out);
+
+/* FUSION WITH PER-OBJECT MOTION.  "Fusion" carries a pixel's world point X UNCHANGED into the up to 2 x 8 neighbouring views of its window; where p's object moved, X
+ * lands on another material point of that object or is refused by the depth or normal test — across up to eight steps of motion, not one.  The calls below are
+ * ptmi_fuse_views_frames and its *_images / *_reference forms with the motions of "ACCUMULATION WITH PER-OBJECT MOTION" composed across the window; they build on
+ * "Fusion", "CONSUMERS WITH PER-VIEW FRAME COUNTS" and that section, and change only what is said here.
+ *
+ * MOTIONS.  motions16 is exactly the accumulation call's array, [n_views of the stack][n_objects][16]: G(w, o) carries a world point of object o at the time of view
+ * w to the same material point at the time of view w-1; only the affine part is read.
+ *
+ * THE COMPOSED MOTION C(v -> u, o), for an output view v and a neighbour u != v, is made ON THE HOST, once per call, the same for the CPU and the GPU path
+ * (include/ptmi_fuse_motion.h).  A(w) is the 4 x 4 affine matrix of G(w, o) in f64 from its f32 elements, bottom row 0 0 0 1.  D(a, b) = A(a+1) A(a+2) ... A(b) for
+ * a < b, built from the right: P = A(b), then P <- A(w) P for w = b-1 ... a+1, every element ((x0 y0 + x1 y1) + x2 y2) + x3 y3 in f64.  u < v: C = D(u, v).  u > v:
+ * C = D(v, u)^-1 — the 3x3 inverse B by cofactors in f64 as the view table's B is made, the translation -B t evaluated as -((B_i0 t_0 + B_i1 t_1) + B_i2 t_2).  The
+ * twelve elements are rounded to f32 ONCE, and the record of (v, u, o) is "ACCUMULATION WITH PER-OBJECT MOTION"'s record of that f32 matrix, unchanged: its Gn, its
+ * identity flag and its refusal.
+ *
+ * VALIDATION.  A call over output views [a, b) with radius R reads entries max(0, a-R)+1 .. min(n-1, b-1+R) of motions16, n the views of the stack; every other
+ * entry may hold anything (frame_nums' rule).  PTMI_ERR_INVALID_ARG, before any allocation or launch: a read step entry that the record refuses (an element that is
+ * not finite, a 3x3 with a zero or non-finite determinant), naming the view and the object; a composed matrix that is refused (an overflowed product), naming v, u
+ * and the object; a null motions16; more than PTMI_MOTION_MAX_RECORDS composed records, n_views of the call x (2R+1) x n_objects.  n_objects = 0 is allowed.
+ *
+ * PER PIXEL.  The object of p comes from layer 2 of view v by "THE OBJECT OF A PIXEL", resolved once per pixel.  A static pixel runs ptmi_fuse_views_frames'
+ * arithmetic bit for bit, and so does a neighbour whose composed record carries the identity flag.  Otherwise, for that neighbour u only, the record's motion (X', n'
+ * of "ACCUMULATION WITH PER-OBJECT MOTION", PER PIXEL) is applied to a COPY of X and of n(p); the view is skipped when nothing is taken over (len not finite or 0);
+ * X' is projected into u in X's place, n' enters the weight in n(p)'s.  Unchanged: the ascending order of u, the own view in its place, the tests at q (material,
+ * validity, normal, depth against r of X') and the output.  The operation order is in include/ptmi_fuse.h and include/ptmi_motion.h and nowhere else.  A camera that
+ * moves WITH an object (both translated by T per view, G the translation by -T) has q = p and weight exactly 1 in every window view on that object.
+ *
+ * OUT OF SCOPE: an object test at q (as for accumulation); deforming meshes; multi-device or sharded contexts (PTMI_ERR_UNSUPPORTED, as the siblings); lighting that
+ * changed between the views — fusion averages radiance across time, as accumulation does. */
+/* ptmi_fuse_views_frames with motions.  Writes the same FUSED STACK: ptmi_read_fused, ptmi_resolve_fused_rgba8, ptmi_fused_device_ptr and ptmi_release_fused work on
+ * its result.  source 0 reads the view stack with frame_nums per view; source 1 reads the denoised stack: frame_nums is then ignored and may be NULL, every count is
+ * 1, and a static scene gives ptmi_fuse_views(source = 1)'s bits.  The object of a pixel is resolved inside the kernel (k_fuse_motion, csrc/ptmi_fuse_kernels.h)
+ * from the scene as it is uploaded at the time of the call, as ptmi_accumulate_views_motion resolves it.  Errors and their order are ptmi_fuse_views_frames', the
+ * null motions16 with the null frame_nums, the entries' checks after frame_nums'.  Asynchronous on the context's stream, one launch; everything that can fail for
+ * want of memory is had before anything is enqueued, and a failing call leaves the fused stack as it found it. */
+int ptmi_fuse_views_motion(ptmi_ctx* ctx, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects,
+                           int source, uint32_t first_view, uint32_t n_views);
+/* ptmi_fuse_images_frames / ptmi_fuse_reference_frames with motions16 [n_images][n_objects][16] and object_ids [n_images][h][w] i32, -1 (or any id outside
+ * [0, n_objects)) = static; ptmi_object_ids_reference makes that image.  weight_out (the CPU reference alone): NULL, or [n_images][h][w] f32 — den of every fused
+ * pixel, 0 where the pixel passes through. */
+int ptmi_fuse_images_motion(ptmi_ctx* ctx, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
+                            const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
+                            const ptmi_fuse_params* params, float* out);
+int ptmi_fuse_reference_motion(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
+                               const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
+                               const ptmi_fuse_params* params, float* out, float* weight_out);
+/* No GPU: THE COMPOSED MOTION (above) of one pair, C(from_view -> to_view, o) for every object, as the f32 matrices the records are made from, into motions16_out
+ * [n_objects][16] (bottom rows 0 0 0 1).  from_view == to_view gives exact identities.  The steps between the two views are the entries read; a refused step or a
+ * refused composition gives PTMI_ERR_INVALID_ARG, as does a view >= n_views. */
+int ptmi_compose_motions(const float* motions16, uint32_t n_views, uint32_t n_objects, uint32_t from_view, uint32_t to_view, float* motions16_out);
 
 /* Test hook, no GPU: the SLOT TABLE ptmi_render_views_frames and ptmi_render_aov_frames upload behind the call's view matrices, u32 words:
  *   words [4 v .. 4 v + 3], v < n_views   view v's record {first slot, frame count, first frame number, next view with a non-zero count or n_views}; a view with

@@ -32,28 +32,12 @@ DEV void accumulate_loaded(const float4& S, const float4& N, const float4& A, co
   asm volatile("" ::"v"(P1.x), "v"(P1.y), "v"(P1.z), "v"(P1.w), "v"(P2.x), "v"(P2.y), "v"(P2.z));
 }
 
-// What k_accumulate_view_motion has beside its siblings' operands.  records: view v's n_objects records (ptmm_record: six float4 each); ids: view v's [npix] object ids
-// (-1: none), or nullptr: the object comes from I through sphere_obj [n_spheres], quad_obj [n_quads], mesh_obj [n_meshes] (one i32 each) and tris (24 f32 per triangle).
-struct MotionArgs {
-  const float4* records;
-  const int32_t* ids;
-  const int32_t *sphere_obj, *quad_obj, *mesh_obj;
-  const float* tris;
-  uint32_t n_objects, n_spheres, n_quads, n_tris, n_meshes;
-};
-
 // The motion of pixel idx's object on its world point X and on the normal in gw (ptmm_move); 0: nothing is taken over.  A static pixel and an identity record leave both.
+// mo (MotionArgs, ptmi_motion_kernels.h): records = view v's n_objects records, ids = view v's id image or nullptr.
 DEV int accumulate_move(const MotionArgs& mo, uint32_t idx, const float4& Ip, float* X, ptmd_f4* gw) {
-  const int32_t obj = mo.ids ? mo.ids[idx] : ptmm_object(dn_f4(Ip), mo.sphere_obj, mo.n_spheres, mo.quad_obj, mo.n_quads, mo.tris, mo.n_tris, mo.mesh_obj, mo.n_meshes);
+  const int32_t obj = motion_object(mo, mo.ids, idx, Ip);
   if (!ptmm_has_record(obj, mo.n_objects)) return 1;
-  const float4* rp = mo.records + 6 * (size_t)obj;
-  const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3], r4 = rp[4], r5 = rp[5];  // six independent loads
-  if (__float_as_uint(r5.y) != 0u) return 1;  // ptmm_record::identity
-  ptmm_record R;
-  R.g[0] = r0.x, R.g[1] = r0.y, R.g[2] = r0.z, R.g[3] = r0.w, R.g[4] = r1.x, R.g[5] = r1.y, R.g[6] = r1.z, R.g[7] = r1.w;
-  R.g[8] = r2.x, R.g[9] = r2.y, R.g[10] = r2.z, R.g[11] = r2.w;
-  R.gn[0] = r3.x, R.gn[1] = r3.y, R.gn[2] = r3.z, R.gn[3] = r3.w, R.gn[4] = r4.x, R.gn[5] = r4.y, R.gn[6] = r4.z, R.gn[7] = r4.w, R.gn[8] = r5.x;
-  return ptmm_move(&R, X, gw);
+  return motion_apply(mo.records + 6 * (size_t)obj, X, gw);
 }
 
 // colour, moments: [n_stack][npix] float4 sums; layers: [n_stack][3][npix] float4; prev1, prev2: planes 1 and 2 of view v - 1 ([npix] float4 each), nullptr: view v has

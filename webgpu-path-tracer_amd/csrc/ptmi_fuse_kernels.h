@@ -9,10 +9,19 @@
 //          straight from the stacks — four 16-byte gathers that do not depend on one another, issued together; neighbouring lanes project to neighbouring q, so a
 //          wave's gather touches few lines.  No LDS tile (q's offset from p differs per view and per depth), no packed scratch images, no prepare pass: q's packed
 //          pixel is remade from its sums by the arithmetic ptmi_denoise.h's prepare uses.  The material-type table is read once per pixel, for p.
+// k_fuse_motion  The same body with MOTION (ptmi_fuse_views_motion, include/ptmi_fuse_motion.h): a fusable lane finds its pixel's object ONCE, before the window loop —
+//          from the call's id image where there is one (ptmi_fuse_images_motion), else from I of p through the call's three id tables and, for a triangle, one gather
+//          of its mesh index, as k_accumulate_view_motion does (motion_object, ptmi_motion_kernels.h) — and, where that object has records, one word more: the MOVING
+//          MASK of (v, object), which the host leaves in the table's own-view slot (include/ptmi_fuse_motion.h).  A neighbour whose bit is clear (an identity record)
+//          costs what it costs the sibling: no record is read.  For a neighbour whose bit is set the lane loads the record the HOST composed for (v, u, object) —
+//          six float4 PER LANE (the object varies within a wave) from the table [v - first][u - v + R][n_objects], fenced into one round trip — and moves a COPY of
+//          the point and of the normal.  u, its row and its count stay wave-uniform.  That round trip stands in front of the projection's four gathers for a moving
+//          pixel; the other two entries compile none of it.
 #pragma once
 
 #include "../../include/ptmi_fuse.h"
 #include "ptmi_denoise_kernels.h"
+#include "ptmi_motion_kernels.h"
 
 namespace ptmi {
 
@@ -54,9 +63,11 @@ DEV void fuse_loaded(const float4& S, const float4& N, const float4& A, const fl
 // stack; lamb: one byte per material index or nullptr.  grid: x = (tiles of 64 columns x rows) / 4, z = output view - view0; block 256.
 // FRAMES: frames [n_stack] f32, F_u of every view of the stack; k.F is then not read: p and the output take F_v, a neighbour's q takes F_u — u is wave-uniform, so the
 // count comes through a scalar load as the view's row does.
-template <bool FRAMES>
+// MOTION: mo.records = the composed records of output view view0 (slot [blockIdx.z][u - v + radius]), mo.ids = the id images of the whole stack or nullptr; every
+// other instance is handed an empty one and reads none of it.
+template <bool FRAMES, bool MOTION = false>
 DEV void fuse_view(const float4* __restrict__ colour, const float4* __restrict__ layers, float4* __restrict__ out, const float4* __restrict__ tab, const uint8_t* __restrict__ lamb,
-                   uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k, const float* __restrict__ frames) {
+                   uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k, const float* __restrict__ frames, const MotionArgs& mo = MotionArgs{}) {
   const uint32_t tiles_x = ((uint32_t)W + 63u) / 64u;
   const uint32_t tile = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);  // wave-uniform
   const uint32_t y = tile / tiles_x;
@@ -79,6 +90,15 @@ DEV void fuse_view(const float4* __restrict__ colour, const float4* __restrict__
     fuse_load_own(tab, v, V);
     float X[3];
     ptmf_world(&k, &V, x, idx, gp.w, X);
+    const float4* rec = nullptr;  // MOTION: the records of p's object in the slot of u = v - radius ...
+    uint32_t moving = 0;          // ... and the mask of the slots whose record is not the identity: 0 for a static pixel
+    if constexpr (MOTION) {
+      const int32_t obj = motion_object(mo, mo.ids ? mo.ids + (size_t)v * npix : nullptr, idx, Ip);
+      if (ptmm_has_record(obj, mo.n_objects)) {
+        rec = mo.records + ((size_t)blockIdx.z * (2u * (uint32_t)k.radius + 1u) * mo.n_objects + (uint32_t)obj) * 6;
+        moving = __float_as_uint(rec[(size_t)k.radius * mo.n_objects * 6 + 5].z);  // ptmm_record::pad[0] of the own-view slot
+      }
+    }
     const uint32_t u0 = v > (uint32_t)k.radius ? v - (uint32_t)k.radius : 0u;
     const uint32_t u1 = min(n_stack - 1u, v + (uint32_t)k.radius);
     for (uint32_t u = u0; u <= u1; u++) {
@@ -90,7 +110,18 @@ DEV void fuse_view(const float4* __restrict__ colour, const float4* __restrict__
       fuse_load_neighbour(tab, u, U);
       int qx, qy;
       float r;
-      if (!ptmf_project(&k, &U, X, &qx, &qy, &r)) continue;
+      float Xu[3] = {X[0], X[1], X[2]};
+      ptmd_f4 gu = gp;  // (gu's normal is read by the sample alone)
+      if constexpr (MOTION) {
+        const uint32_t slot = u + (uint32_t)k.radius - v;
+        if ((moving >> slot) & 1u) {
+          const float4* rp = rec + (size_t)slot * mo.n_objects * 6;
+          const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3], r4 = rp[4], r5 = rp[5];  // six independent loads, one round trip
+          motion_loaded(r0, r1, r2, r3, r4, r5);
+          if (!motion_move_loaded(r0, r1, r2, r3, r4, r5, Xu, &gu)) continue;
+        }
+      }
+      if (!ptmf_project(&k, &U, Xu, &qx, &qy, &r)) continue;
       const size_t q = (size_t)qy * (size_t)W + (size_t)qx;
       const float4* Lu = layers + (size_t)u * 3 * npix;
       const float4 Sq = colour[(size_t)u * npix + q], Nq = Lu[q], Aq = Lu[npix + q], Iq = Lu[2 * npix + q];  // four independent gathers
@@ -98,9 +129,9 @@ DEV void fuse_view(const float4* __restrict__ colour, const float4* __restrict__
       if (FRAMES) {
         ptmf_consts ku = k;
         ku.F = ldu(frames + u);
-        ptmf_sample(&ku, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), num, &den);
+        ptmf_sample(&ku, dp, gu, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), num, &den);
       } else {
-        ptmf_sample(&k, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), num, &den);
+        ptmf_sample(&k, dp, gu, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), num, &den);
       }
     }
   }
@@ -117,6 +148,13 @@ __global__ __launch_bounds__(kBlock) void k_fuse_frames(const float4* __restrict
                                                         const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k,
                                                         const float* __restrict__ frames) {
   fuse_view<true>(colour, layers, out, tab, lamb, n_materials, W, H, n_stack, view0, k, frames);
+}
+
+// k_fuse_frames with the composed motions of the views' objects (ptmi_fuse_views_motion, ptmi_fuse_images_motion)
+__global__ __launch_bounds__(kBlock) void k_fuse_motion(const float4* __restrict__ colour, const float4* __restrict__ layers, float4* __restrict__ out, const float4* __restrict__ tab,
+                                                        const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k,
+                                                        const float* __restrict__ frames, MotionArgs mo) {
+  fuse_view<true, true>(colour, layers, out, tab, lamb, n_materials, W, H, n_stack, view0, k, frames, mo);
 }
 
 }  // namespace ptmi

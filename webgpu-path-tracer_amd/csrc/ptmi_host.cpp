@@ -24,6 +24,7 @@
 #include "../../include/ptmi_fuse.h"
 #include "../../include/ptmi_accumulate.h"
 #include "../../include/ptmi_motion.h"
+#include "../../include/ptmi_fuse_motion.h"
 #include "../../include/ptmi_noise.h"
 #include "ptmi_bvh_domain.h"
 
@@ -940,8 +941,17 @@ extern "C" void ptmi_default_fuse_params(ptmi_fuse_params* p) {
 
 // A plain loop over output views, pixels and neighbour views through include/ptmi_fuse.h, the header the kernel of ptmi_fuse_views compiles.  Nothing is tiled,
 // threaded or reordered.  frame_nums: nullptr, or every image's own divisor (ptmi_fuse_reference_frames): view v's p and output take F_v, a neighbour's q takes F_u.
+// motion: nullptr, or the motions and the id images of ptmi_fuse_reference_motion: a pixel whose object has a composed record (include/ptmi_fuse_motion.h) for the
+// neighbour that is not the identity moves a copy of the point and of the normal (include/ptmi_motion.h) for that neighbour; every other pixel runs what it ran.
+// weight_out: nullptr, or [n_images][h][w]: den of every fused pixel, 0 where the pixel passes through.
+struct ReferenceMotion {  // (accumulate_reference's too)
+  const float* motions16;  // [n_images][n_objects][16]
+  uint32_t n_objects;
+  const int32_t* object_ids;  // [n_images][h][w]
+};
 static int fuse_reference(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, const float* frame_nums,
-                          float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
+                          float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out,
+                          const ReferenceMotion* motion = nullptr, float* weight_out = nullptr) {
   if (!colour || !layers || !views16 || !out || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
   ptmi_fuse_params P;
   if (params) P = *params;
@@ -957,6 +967,21 @@ static int fuse_reference(const float* colour, const float* layers, const float*
   }
   for (uint32_t v = 0; v < n_images; v++)
     if (!ptmf_make_view(views16 + 16 * (size_t)v, &tab[v])) return PTMI_ERR_INVALID_ARG;
+  std::vector<ptmm_record> rec;  // [v][u - v + radius][n_objects], as the kernel's table
+  const uint32_t span = 2u * (uint32_t)P.radius + 1u;
+  if (motion) {
+    if (!motion->motions16 || !motion->object_ids || (uint64_t)n_images * span * motion->n_objects > (uint64_t)PTMI_MOTION_MAX_RECORDS) return PTMI_ERR_INVALID_ARG;
+    int kind;
+    uint32_t bv, bu, bo;
+    if (!ptmfm_compose_table(motion->motions16, n_images, motion->n_objects, 0, n_images, (uint32_t)P.radius, nullptr, &kind, &bv, &bu, &bo)) return PTMI_ERR_INVALID_ARG;
+    try {
+      rec.resize((size_t)n_images * span * motion->n_objects);
+    } catch (const std::bad_alloc&) {
+      return PTMI_ERR_NO_MEMORY;
+    }
+    if (!rec.empty() && !ptmfm_compose_table(motion->motions16, n_images, motion->n_objects, 0, n_images, (uint32_t)P.radius, rec.data(), &kind, &bv, &bu, &bo))
+      return PTMI_ERR_INVALID_ARG;
+  }
   ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   const size_t npix = (size_t)w * (size_t)h;
   const ptmd_f4* S = reinterpret_cast<const ptmd_f4*>(colour);
@@ -976,6 +1001,11 @@ static int fuse_reference(const float* colour, const float* layers, const float*
         if (fused) {
           float X[3];
           ptmf_world(&k, &tab[v], x, idx, gp.w, X);
+          const ptmm_record* R0 = nullptr;  // the records of p's object in the slot of u = v - radius; nullptr: a static pixel
+          if (motion) {
+            const int32_t obj = motion->object_ids[(size_t)v * npix + idx];
+            if (ptmm_has_record(obj, motion->n_objects)) R0 = &rec[(size_t)v * span * motion->n_objects + (uint32_t)obj];
+          }
           for (uint32_t u = u0; u <= u1; u++) {
             if (u == v) {
               ptmf_own(dp, num, &den);
@@ -983,15 +1013,22 @@ static int fuse_reference(const float* colour, const float* layers, const float*
             }
             int qx, qy;
             float r;
-            if (!ptmf_project(&k, &tab[u], X, &qx, &qy, &r)) continue;
+            float Xu[3] = {X[0], X[1], X[2]};
+            ptmd_f4 gu = gp;  // (gu's normal is read by the sample alone)
+            if (R0) {
+              const ptmm_record* R = R0 + (size_t)(u + (uint32_t)P.radius - v) * motion->n_objects;
+              if (!R->identity && !ptmm_move(R, Xu, &gu)) continue;
+            }
+            if (!ptmf_project(&k, &tab[u], Xu, &qx, &qy, &r)) continue;
             const size_t q = (size_t)qy * (size_t)w + (size_t)qx;
             const ptmd_f4* Lu = L + (size_t)u * 3 * npix;
             ptmf_consts ku = k;
             if (frame_nums) ku.F = frame_nums[u];
-            ptmf_sample(&ku, dp, gp, r, S[(size_t)u * npix + q], Lu[q], Lu[npix + q], Lu[2 * npix + q], num, &den);
+            ptmf_sample(&ku, dp, gu, r, S[(size_t)u * npix + q], Lu[q], Lu[npix + q], Lu[2 * npix + q], num, &den);
           }
         }
         O[(size_t)v * npix + idx] = ptmf_output(&k, Sp, Ap, fused, num, den);
+        if (weight_out) weight_out[(size_t)v * npix + idx] = fused ? den : 0.0f;
       }
   }
   return PTMI_OK;
@@ -1004,6 +1041,20 @@ extern "C" int ptmi_fuse_reference_frames(const float* colour, const float* laye
                                           float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
   if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
   return fuse_reference(colour, layers, views16, w, h, n_images, 1.0f, frame_nums, fov_degrees, lambertian, n_materials, params, out);
+}
+extern "C" int ptmi_fuse_reference_motion(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
+                                          const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian,
+                                          uint32_t n_materials, const ptmi_fuse_params* params, float* out, float* weight_out) {
+  if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
+  const ReferenceMotion motion{motions16, n_objects, object_ids};
+  return fuse_reference(colour, layers, views16, w, h, n_images, 1.0f, frame_nums, fov_degrees, lambertian, n_materials, params, out, &motion, weight_out);
+}
+// The composed motions of one (from, to) pair of views (include/ptmi_fuse_motion.h): what the fusion calls put into their table for that pair, as f32 matrices.
+extern "C" int ptmi_compose_motions(const float* motions16, uint32_t n_views, uint32_t n_objects, uint32_t from_view, uint32_t to_view, float* motions16_out) {
+  if (!motions16 || !motions16_out || from_view >= n_views || to_view >= n_views) return PTMI_ERR_INVALID_ARG;
+  int kind;
+  uint32_t bv, bu, bo;
+  return ptmfm_compose_pair(motions16, n_objects, from_view, to_view, motions16_out, &kind, &bv, &bu, &bo) ? PTMI_OK : PTMI_ERR_INVALID_ARG;
 }
 
 // ---- temporal accumulation on the host (ptmi_accumulate_reference) ----
@@ -1022,11 +1073,6 @@ extern "C" void ptmi_default_accumulate_params(ptmi_accumulate_params* p) {
 // frame_nums: nullptr, or every image's own divisor (ptmi_accumulate_reference_frames): own, mean and the pass-through of view v take F_v, the lookup in view v-1 F_{v-1}.
 // motion: nullptr, or the motions and the id images of ptmi_accumulate_reference_motion: between the world point and its projection a pixel whose object has a record
 // that is not the identity moves the point and the normal (include/ptmi_motion.h); every other pixel runs what it ran.
-struct ReferenceMotion {
-  const float* motions16;  // [n_images][n_objects][16]
-  uint32_t n_objects;
-  const int32_t* object_ids;  // [n_images][h][w]
-};
 static int accumulate_reference(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
                                 const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
                                 const float* history_in, float* out, int threads, const ReferenceMotion* motion = nullptr) {

@@ -13,6 +13,7 @@
 #include "ptmi_fuse_kernels.h"
 #include "ptmi_accumulate_kernels.h"
 #include "ptmi_noise_kernels.h"
+#include "../../include/ptmi_fuse_motion.h"
 
 extern "C" {
 
@@ -381,14 +382,20 @@ static int fuse_fill_tab(ptmi_ctx* c, const char* who, const float* views16, uin
 // The kernel on device arrays: colour [n_stack][H][W] float4, layers [n_stack][3][H][W] float4, out [n_stack][H][W] float4, of which views [first, first + n) are
 // written; `tab` as fuse_fill_tab made it, `has_lamb`: whether its material bytes are to be used.  One launch; more only where n exceeds the grid's z limit.
 // frames: nullptr, or the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_fuse_frames.
+// motion (with frames): nullptr, or k_fuse_motion's operands, records = the composed records of view `first` (fuse_motion_table: the layout).
 static int fuse_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, const void* tab, bool has_lamb, uint32_t n_materials, int W, int H,
-                        uint32_t n_stack, uint32_t first, uint32_t n, const ptmf_consts& k, const float* frames = nullptr) {
+                        uint32_t n_stack, uint32_t first, uint32_t n, const ptmf_consts& k, const float* frames = nullptr, const MotionArgs* motion = nullptr) {
   const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
   const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
   const uint8_t* lamb = has_lamb ? reinterpret_cast<const uint8_t*>(tab) + (size_t)n_stack * kFuseRow * 16 : nullptr;
   for (uint32_t v0 = 0; v0 < n; v0 += 65535u) {
     const uint32_t nv = std::min(65535u, n - v0);
-    if (frames)
+    if (motion) {
+      MotionArgs mo = *motion;
+      mo.records += (size_t)v0 * (2u * (uint32_t)k.radius + 1u) * mo.n_objects * 6;
+      hipLaunchKernelGGL(k_fuse_motion, dim3(gx, 1, nv), dim3(kBlock), 0, c->stream, colour, layers, out, reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, n_stack,
+                         first + v0, k, frames, mo);
+    } else if (frames)
       hipLaunchKernelGGL(k_fuse_frames, dim3(gx, 1, nv), dim3(kBlock), 0, c->stream, colour, layers, out, reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, n_stack,
                          first + v0, k, frames);
     else
@@ -438,26 +445,87 @@ static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, cons
   return PTMI_OK;
 }
 
-// ptmi_fuse_views (per_view false: frame_num) and ptmi_fuse_views_frames (per_view: the view stack as source, frame_nums one per view of the stack)
+// The *_motion fusion calls: the composed records (include/ptmi_fuse_motion.h) of output views [first, first + n) of a stack of n_all views, radius R, from
+// motions16 [n_all][n_objects][16], into `rec` as [n][2 R + 1][n_objects]; the step entries the call reads are checked first, the composed ones as they are made.
+// Allocates host memory only.
+static int fuse_motion_table(ptmi_ctx* c, const char* who, const float* motions16, uint32_t n_objects, uint32_t n_all, uint32_t first, uint32_t n, uint32_t R,
+                             std::vector<ptmm_record>* rec) {
+  if (!motions16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null motions16");
+  const uint64_t count = (uint64_t)n * (2u * R + 1u) * n_objects;
+  if (count > (uint64_t)PTMI_MOTION_MAX_RECORDS)
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": " + std::to_string(n) + " views x " + std::to_string(2u * R + 1u) + " window views x " + std::to_string(n_objects) +
+                                             " objects are more than PTMI_MOTION_MAX_RECORDS composed motions");
+  int kind = 0;
+  uint32_t bv = 0, bu = 0, bo = 0;
+  if (!ptmfm_compose_table(motions16, n_all, n_objects, first, n, R, nullptr, &kind, &bv, &bu, &bo))  // (the steps alone: nothing allocated for a refused call)
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the motion of view " + std::to_string(bv) + ", object " + std::to_string(bo) +
+                                             " has a non-finite element or a 3x3 with a zero or non-finite determinant: view " + std::to_string(bv) + " is read by this call");
+  try {
+    rec->resize((size_t)count);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the composed motions");
+  }
+  if (count && !ptmfm_compose_table(motions16, n_all, n_objects, first, n, R, rec->data(), &kind, &bv, &bu, &bo))
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the motion composed from view " + std::to_string(bv) + " to view " + std::to_string(bu) + ", object " + std::to_string(bo) +
+                                             ", has a non-finite element or a 3x3 with a zero or non-finite determinant");
+  return PTMI_OK;
+}
+
+// ptmi_fuse_views (per_view false: frame_num), ptmi_fuse_views_frames (per_view: the view stack as source, frame_nums one per view of the stack) and
+// ptmi_fuse_views_motion (motion: per_view, motions16 [n_views of the stack][n_objects][16]; with source 1 the counts are all 1 and frame_nums is not read)
 static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* params, const float* views16, float frame_num, const float* frame_nums, bool per_view, int source,
-                      uint32_t first_view, uint32_t n_views) {
+                      uint32_t first_view, uint32_t n_views, bool motion = false, const float* motions16 = nullptr, uint32_t n_objects = 0) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   if (source != 0 && source != 1) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": source must be 0 (the view stack) or 1 (the denoised stack)");
   ptmi_fuse_params P;
   if (int r = fuse_check_args(c, who, params, frame_num, source == 0 && !per_view, &P)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (motion && source == 1) frame_nums = nullptr;  // (ignored: the denoised stack holds means)
+  if (per_view && !frame_nums && !(motion && source == 1)) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (motion && !motions16) return fuse_motion_table(c, who, nullptr, 0, 0, 0, 0, 0, nullptr);
   if (int r = check_source_stacks(c, who, source == 1, first_view, n_views)) return r;
   const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  if (per_view) {  // the call's range widened by the radius on both sides, clipped to the stack: the window of its output views
+  if (per_view && frame_nums) {  // the call's range widened by the radius on both sides, clipped to the stack: the window of its output views
     const uint32_t R = (uint32_t)P.radius, lo = first_view > R ? first_view - R : 0u, hi = (uint32_t)std::min<uint64_t>(n_stack, (uint64_t)first_view + n_views + R);
     if (int r = check_frame_nums(c, who, frame_nums, lo, hi)) return r;
   }
-  if (int r = make_stack_with_table(c, who, STACK_FUSED, views16, per_view ? frame_nums : nullptr)) return r;
+  // A *_motion call's part of the table, behind the frame counts: the composed records, then one object id per sphere, per quad and per mesh of the scene as it is
+  // uploaded now, from the host copies (as ptmi_accumulate_views_motion's).  The triangles are on the device already.
+  std::vector<uint32_t> blob;
+  std::vector<float> ones;
+  MotionArgs mo{};
+  if (motion) {
+    std::vector<ptmm_record> rec;
+    if (int r = fuse_motion_table(c, who, motions16, n_objects, n_stack, first_view, n_views, (uint32_t)P.radius, &rec)) return r;
+    mo.n_objects = n_objects, mo.n_spheres = (uint32_t)(c->h_spheres.size() / 8), mo.n_quads = (uint32_t)(c->h_quads.size() / 20);
+    mo.n_tris = (uint32_t)c->n_tris_uploaded, mo.n_meshes = (uint32_t)(c->h_meshes.size() / 4);
+    const size_t rec_words = rec.size() * (sizeof(ptmm_record) / 4);
+    try {
+      blob.resize(std::max<size_t>(1, rec_words + mo.n_spheres + mo.n_quads + mo.n_meshes));  // (one word at least: blob.data() tells make_stack_with_table that there is such a part)
+      if (!frame_nums) ones.assign(n_stack, 1.0f);
+    } catch (const std::bad_alloc&) {
+      return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the motion table");
+    }
+    if (rec_words) memcpy(blob.data(), rec.data(), rec_words * 4);
+    int32_t* ids = reinterpret_cast<int32_t*>(blob.data() + rec_words);
+    for (uint32_t i = 0; i < mo.n_spheres; i++) *ids++ = ptmm_f32_object(c->h_spheres[8 * (size_t)i + 4]);
+    for (uint32_t i = 0; i < mo.n_quads; i++) *ids++ = ptmm_f32_object(c->h_quads[20 * (size_t)i + 11]);
+    for (uint32_t i = 0; i < mo.n_meshes; i++) *ids++ = ptmm_i32_object(c->h_meshes[4 * (size_t)i + 2]);
+    if (int r = make_stack_with_table(c, who, STACK_FUSED, views16, frame_nums ? frame_nums : ones.data(), blob.data(), blob.size() * 4)) return r;
+    const uint8_t* extra = reinterpret_cast<const uint8_t*>(c->fuse_tab.dev.p) + fuse_tab_extra(n_stack, n_mat);
+    mo.records = reinterpret_cast<const float4*>(extra);
+    mo.sphere_obj = reinterpret_cast<const int32_t*>(extra) + rec_words, mo.quad_obj = mo.sphere_obj + mo.n_spheres, mo.mesh_obj = mo.quad_obj + mo.n_quads;
+    mo.tris = c->d_tris.as<float>();
+  } else if (int r = make_stack_with_table(c, who, STACK_FUSED, views16, per_view ? frame_nums : nullptr)) return r;
   const float fov_factor = (float)(1.0 / std::tan((double)c->prm.fov_degrees * (3.14159265358979323846 / 180.0) / 2.0));  // as make_render_const folds it
   const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, source == 0 ? frame_num : 1.0f, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   return fuse_enqueue(c, c->stacks[source == 0 ? STACK_VIEWS : STACK_DENOISED].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(), c->stacks[STACK_FUSED].buf.as<float4>(),
-                      c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, k, per_view ? fuse_tab_frames_ptr(c->fuse_tab.dev.p, n_stack, n_mat) : nullptr);
+                      c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, k, per_view ? fuse_tab_frames_ptr(c->fuse_tab.dev.p, n_stack, n_mat) : nullptr,
+                      motion ? &mo : nullptr);
+}
+int ptmi_fuse_views_motion(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects, int source,
+                           uint32_t first_view, uint32_t n_views) {
+  return fuse_views(c, "ptmi_fuse_views_motion", params, views16, 1.0f, frame_nums, true, source, first_view, n_views, true, motions16, n_objects);
 }
 int ptmi_fuse_views(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, float frame_num, int source, uint32_t first_view, uint32_t n_views) {
   return fuse_views(c, "ptmi_fuse_views", params, views16, frame_num, nullptr, false, source, first_view, n_views);
@@ -473,10 +541,18 @@ int ptmi_resolve_fused_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t by
 int ptmi_fused_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) { return stack_device_ptr(c, STACK_FUSED, "ptmi_fused_device_ptr", nullptr, p, bytes, n_views); }
 int ptmi_release_fused(ptmi_ctx* c) { return release_stack(c, STACK_FUSED); }
 
-// ptmi_fuse_images (per_view false) and ptmi_fuse_images_frames (frame_nums: one per image)
+// What the *_images_motion calls have beside the *_images_frames calls' arguments: motions16 [n_images][n_objects][16], object_ids [n_images][h][w] i32
+struct MotionImages {
+  const float* motions16;
+  uint32_t n_objects;
+  const int32_t* object_ids;
+};
+
+// ptmi_fuse_images (per_view false), ptmi_fuse_images_frames (frame_nums: one per image) and ptmi_fuse_images_motion (motion, with per_view)
 static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
-                       const float* frame_nums, bool per_view, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
-  if (!c || !colour || !layers || !views16 || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+                       const float* frame_nums, bool per_view, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out,
+                       const MotionImages* motion = nullptr) {
+  if (!c || !colour || !layers || !views16 || !out || (motion && !motion->object_ids)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_fuse_params P;
   if (int r = fuse_check_args(c, who, params, frame_num, !per_view, &P)) return r;
   if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
@@ -484,6 +560,9 @@ static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const 
   if (per_view)
     if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
   if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": fov_degrees must be in (0,180)");
+  std::vector<ptmm_record> rec;
+  if (motion)
+    if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_images, 0, n_images, (uint32_t)P.radius, &rec)) return r;
   if (!lambertian) n_materials = 0;
   const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials, per_view);
   std::vector<float> tab;
@@ -495,12 +574,31 @@ static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const 
   if (int r = fuse_fill_tab(c, who, views16, n_images, lambertian, n_materials, tab.data())) return r;
   if (per_view) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_frames(n_images, n_materials), frame_nums, (size_t)n_images * 4);
   const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
-  DBuf dtab;
-  return on_host_images(c, who, colour, layers, (size_t)w * (size_t)h, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
+  const size_t npix = (size_t)w * (size_t)h;
+  DBuf dtab, drec, dids;  // (a *_motion call's records and id images are its own, had before anything is enqueued)
+  MotionArgs mo{};
+  if (motion) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    HIP_TRY(c, drec.ensure(std::max<size_t>(rec.size() * sizeof(ptmm_record), 16)));
+    HIP_TRY(c, dids.ensure(npix * 4 * n_images));
+    mo.records = drec.as<float4>(), mo.ids = dids.as<int32_t>(), mo.n_objects = motion->n_objects;
+  }
+  return on_host_images(c, who, colour, layers, npix, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
     HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+    if (motion) {
+      if (!rec.empty()) HIP_TRY(c, hipMemcpyAsync(drec.p, rec.data(), rec.size() * sizeof(ptmm_record), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(dids.p, motion->object_ids, npix * 4 * n_images, hipMemcpyHostToDevice, c->stream));
+    }
     return fuse_enqueue(c, col, lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, 0, n_images, k,
-                        per_view ? fuse_tab_frames_ptr(dtab.p, n_images, n_materials) : nullptr);
+                        per_view ? fuse_tab_frames_ptr(dtab.p, n_images, n_materials) : nullptr, motion ? &mo : nullptr);
   });
+}
+int ptmi_fuse_images_motion(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
+                            const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
+                            const ptmi_fuse_params* params, float* out) {
+  const MotionImages motion{motions16, n_objects, object_ids};
+  return fuse_images(c, "ptmi_fuse_images_motion", colour, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params, out, &motion);
 }
 int ptmi_fuse_images(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
                      const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
@@ -642,13 +740,6 @@ int ptmi_accumulated_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* 
   return stack_device_ptr(c, STACK_ACCUMULATED, "ptmi_accumulated_device_ptr", nullptr, p, bytes, n_views);
 }
 int ptmi_release_accumulated(ptmi_ctx* c) { return release_stack(c, STACK_ACCUMULATED); }
-
-// What ptmi_accumulate_images_motion has beside ptmi_accumulate_images_frames' arguments: motions16 [n_images][n_objects][16], object_ids [n_images][h][w] i32
-struct MotionImages {
-  const float* motions16;
-  uint32_t n_objects;
-  const int32_t* object_ids;
-};
 
 // ptmi_accumulate_images (per_view false), ptmi_accumulate_images_frames (frame_nums: one per image) and ptmi_accumulate_images_motion (motion, with per_view)
 static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,

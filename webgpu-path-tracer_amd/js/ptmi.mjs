@@ -96,6 +96,11 @@ export class Ptmi {
   accumulateViewsMotion(views, frameNums, motions, nObjects, firstView, nViews, resume = false, params = null) {
     this.native.accumulateViewsMotion(this.h, views, Float32Array.from(frameNums), motions, nObjects, firstView, nViews, resume, params);
   }
+  // ptmi_fuse_views_motion: fuseViewsFrames through a world whose objects move — motions as accumulateViewsMotion takes them, composed across each output view's
+  // window by the library; source 1 reads the denoised stack, frameNums may then be null
+  fuseViewsMotion(views, frameNums, motions, nObjects, source, firstView, nViews, params = null) {
+    this.native.fuseViewsMotion(this.h, views, frameNums == null ? null : Float32Array.from(frameNums), motions, nObjects, source, firstView, nViews, params);
+  }
   synchronize() { this.native.synchronize(this.h); }
   prepare() { this.native.prepare(this.h); }
   buildSceneBVHSAH() { this.native.buildSceneBVHSAH(this.h); }   // the same with the reference's never-called SAH builder (lib/BVH/bvhNode.js:108-283): opt-in

@@ -39,6 +39,7 @@ SYMBOLS = [
     "ptmi_denoise_reference_frames", "ptmi_denoise_guided_reference_frames", "ptmi_fuse_reference_frames", "ptmi_accumulate_reference_frames",
     "ptmi_refit_bvh", "ptmi_refit_scene_bvh",
     "ptmi_accumulate_views_motion", "ptmi_accumulate_images_motion", "ptmi_accumulate_reference_motion", "ptmi_object_ids_reference", "ptmi_motions_from_transforms",
+    "ptmi_fuse_views_motion", "ptmi_fuse_images_motion", "ptmi_fuse_reference_motion", "ptmi_compose_motions",
 ]
 
 MOTION_MAX_RECORDS = 1 << 20  # PTMI_MOTION_MAX_RECORDS
@@ -289,6 +290,12 @@ def load_library(build=False, path=None):
         L.ptmi_accumulate_reference_motion.argtypes = [fp, fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, ctypes.c_float, fp, u32, ap, fp, fp, i32]
         L.ptmi_object_ids_reference.argtypes = [fp, i32, i32, u32, fp, u32, fp, u32, fp, u32, fp, u32, fp]
         L.ptmi_motions_from_transforms.argtypes = [fp, fp, u32, fp]
+    if hasattr(L, "ptmi_fuse_views_motion"):  # (an older A/B build loaded through PTMI_LIB fuses through a static world)
+        up = ctypes.POINTER(FuseParams)
+        L.ptmi_fuse_views_motion.argtypes = [vp, up, fp, fp, fp, u32, i32, u32, u32]
+        L.ptmi_fuse_images_motion.argtypes = [vp, fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, ctypes.c_float, fp, u32, up, fp]
+        L.ptmi_fuse_reference_motion.argtypes = [fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, ctypes.c_float, fp, u32, up, fp, fp]
+        L.ptmi_compose_motions.argtypes = [fp, u32, u32, u32, u32, fp]
     if explicit:
         _libs[path] = L
     else:
@@ -565,6 +572,35 @@ def motions_from_transforms(prev, cur, lib=None):
     st = (lib or load_library()).ptmi_motions_from_transforms(_ptr(p), _ptr(c), p.shape[0], _ptr(out))
     if st != 0:
         raise PtmiError(st, "ptmi_motions_from_transforms failed")
+    return out
+
+
+def fuse_reference_motion(colour, layers, views, frame_nums, motions, object_ids, fov_degrees=60.0, lambertian=None, params=None, want_weight=False, n_objects=None,
+                          lib=None):
+    """ptmi_fuse_reference_motion: fuse_reference_frames through a world whose objects move — motions (n, n_objects, 16) as accumulate_reference_motion takes them
+    (per image and object the matrix from the time of image v to the time of image v-1; composed across the window by the library); object_ids (n, H, W) int32,
+    -1 = static.  want_weight: also return (n, H, W) float32, the summed weight (den) of every fused pixel, 0 where the pixel passes through."""
+    c, l, v, t, out = _fuse_arrays(colour, layers, views, lambertian)
+    f = _frame_nums(frame_nums, c.shape[0])
+    g, n_obj, ids = _motion_arrays(motions, object_ids, c.shape[0], c.shape[1:3])
+    wgt = np.empty(c.shape[:3], np.float32) if want_weight else None
+    st = (lib or load_library()).ptmi_fuse_reference_motion(_ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), _optr(g),
+                                                            n_obj if n_objects is None else n_objects, _optr(ids), float(fov_degrees), _optr(t), 0 if t is None else t.size,
+                                                            None if params is None else ctypes.byref(params), _ptr(out), _optr(wgt))
+    if st != 0:
+        raise PtmiError(st, "ptmi_fuse_reference_motion failed")
+    return (out, wgt) if want_weight else out
+
+
+def compose_motions(motions, from_view, to_view, lib=None):
+    """ptmi_compose_motions: the composed motion of every object from the time of view from_view to the time of view to_view, (n_objects, 16) float32, out of the
+    per-step motions (n_views, n_objects, 16): what the *_motion fusion calls make their records from for that pair."""
+    g = np.ascontiguousarray(motions, np.float32)
+    assert g.ndim == 3 and g.shape[2] == 16, "motions: (n_views, n_objects, 16)"
+    out = np.empty((g.shape[1], 16), np.float32)
+    st = (lib or load_library()).ptmi_compose_motions(_ptr(g), g.shape[0], g.shape[1], int(from_view), int(to_view), _ptr(out))
+    if st != 0:
+        raise PtmiError(st, "ptmi_compose_motions failed")
     return out
 
 
@@ -1048,6 +1084,31 @@ class Context:
         self._ck(self.lib.ptmi_accumulate_images_motion(self.h, _ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), _optr(g),
                                                         n_obj if n_objects is None else n_objects, _optr(ids), float(fov_degrees), _optr(t), 0 if t is None else t.size,
                                                         None if params is None else ctypes.byref(params), _optr(hist), _ptr(out)))
+        return out
+
+    # ---- fusion through a world whose objects move (include/ptmi.h, "FUSION WITH PER-OBJECT MOTION") ----
+    def fuse_views_motion(self, views, frame_nums, motions, source=0, first_view=0, n_views=None, params=None, n_objects=None):
+        """ptmi_fuse_views_motion: fuse_views_frames with motions (n_views of the stack, n_objects, 16), the array accumulate_views_motion takes (render_moving_path
+        returns it), composed across each output view's window; source 1 reads the denoised stack, frame_nums may then be None.  The pixel's object is found in the
+        scene AS IT IS UPLOADED NOW, as accumulate_views_motion finds it.  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        n_stack = self.views_device_ptr()[2]
+        assert v.shape[0] == n_stack, "views: the matrices of all %d views of the stack" % n_stack
+        f = _frame_nums(frame_nums, n_stack)
+        g, n_obj, _ = _motion_arrays(motions, None, n_stack)
+        if n_views is None:
+            n_views = n_stack - first_view
+        self._ck(self.lib.ptmi_fuse_views_motion(self.h, None if params is None else ctypes.byref(params), _ptr(v), _optr(f), _optr(g),
+                                                 n_obj if n_objects is None else n_objects, int(source), first_view, n_views))
+
+    def fuse_images_motion(self, colour, layers, views, frame_nums, motions, object_ids, fov_degrees=60.0, lambertian=None, params=None, n_objects=None):
+        """ptmi_fuse_images_motion: the kernel of fuse_views_motion on host arrays of any size (see fuse_reference_motion); synchronous."""
+        c, l, v, t, out = _fuse_arrays(colour, layers, views, lambertian)
+        f = _frame_nums(frame_nums, c.shape[0])
+        g, n_obj, ids = _motion_arrays(motions, object_ids, c.shape[0], c.shape[1:3])
+        self._ck(self.lib.ptmi_fuse_images_motion(self.h, _ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), _optr(g),
+                                                  n_obj if n_objects is None else n_objects, _optr(ids), float(fov_degrees), _optr(t), 0 if t is None else t.size,
+                                                  None if params is None else ctypes.byref(params), _ptr(out)))
         return out
 
     def render_moving_path(self, views, transforms_seq, first_frames, frame_counts):
