@@ -690,7 +690,7 @@ int ptmi_accumulate_reference_frames(const float* colour_sums, const float* mome
  * object (both translated by T, G the translation by -T) has q = p and wgt exactly 1 on that object: n after k such views of one frame each is exactly k.
  *
  * OUT OF SCOPE: an object test at q — q's object would need a second dependent chain, so the material, normal and depth tests
- * stay the disocclusion tests; deforming meshes (per-vertex motion); multi-device contexts. */
+ * stay the disocclusion tests; deforming meshes (per-vertex motion: "ACCUMULATION THROUGH DEFORMING MESHES" below); multi-device contexts. */
 #define PTMI_MOTION_MAX_RECORDS (1u << 20)
 /* ptmi_accumulate_views_frames with motions; there is no one-frame_num twin.  Writes the same ACCUMULATED STACK: ptmi_read_accumulated,
  * ptmi_resolve_accumulated_rgba8, ptmi_accumulated_device_ptr, ptmi_release_accumulated and ptmi_denoise_views_accumulated work on its result unchanged.  The object of
@@ -718,6 +718,85 @@ int ptmi_object_ids_reference(const float* layers, int w, int h, uint32_t n_imag
  * cur32, n_objects records each, into motions16_out [n_objects][16].  An object whose two records are bytewise equal gets the exact identity.  Every other object gets
  * model_prev . invModel_cur: element (i, j) = ((P_i0 C_0j + P_i1 C_1j) + P_i2 C_2j) + P_i3 C_3j in f64 from the stored f32 elements, rounded to f32 once. */
 int ptmi_motions_from_transforms(const float* prev32, const float* cur32, uint32_t n_objects, float* motions16_out);
+
+/* ACCUMULATION THROUGH DEFORMING MESHES (per-vertex motion).  "ACCUMULATION WITH PER-OBJECT MOTION" follows an object through one matrix per view.  A skinned or
+ * morphing mesh — triangles uploaded again, ptmi_refit_scene_bvh, render — has no such matrix: its pixels ghost or lose their history.  What is needed is the geometry
+ * of the previous view: layer 2 of the feature stack names the hit triangle by its index in device order, and ptmi_refit_scene_bvh keeps that order from view to
+ * view, so a triangle pixel can be carried from its triangle NOW to the same triangle THEN by barycentric coordinates.  The calls below are
+ * ptmi_accumulate_views_motion and its *_images / *_reference forms with that step for triangle pixels; they change only what is said here.
+ *
+ * THE GEOMETRY STACK.  ptmi_capture_view_geometry copies into slot `view` of a device-resident stack the context's device triangles in the order they lie in now
+ * (96 bytes each, what ptmi_read_scene_buffer returns for buffer 5) and the transform table as uploaded now (binding 7, 32 f32 per object): [n_views][n_triangles][24]
+ * f32 plus [n_views][n_transforms][32] f32.  A device-to-device copy on the context's stream; only the small transform table goes through the host, which keeps a
+ * copy of it to make a call's records from.  The stack is keyed by (n_views, triangle count, transform count): a capture under another key drops it and allocates a
+ * new one, every slot marked not captured.  It holds no image, so ptmi_resize leaves it alone.  Errors, in this order: a multi-device or sharded context
+ * PTMI_ERR_UNSUPPORTED; n_views == 0, view >= n_views or a scene without triangles PTMI_ERR_INVALID_ARG; a stale tree (triangles, meshes or transforms uploaded
+ * since the build or refit) PTMI_ERR_STATE — the triangles are then in upload order and not in the order a render would see; a stack above PTMI_GEOMETRY_MAX_BYTES
+ * PTMI_ERR_UNSUPPORTED.  All memory is obtained before anything is enqueued, and a failing call leaves the stack as it found it.
+ *
+ * WHICH PIXELS.  Pixel p of view v is a DEFORM pixel when its layer-2 sample I has kind 3, its primitive index counts against the triangle count, the mesh index in
+ * word 23 of that triangle in slot v counts against the mesh count, and that mesh's transform index meshes[mesh][2] is in [0, n_transforms): every index checked
+ * before it is used, as THE OBJECT OF A PIXEL checks them.  EVERY OTHER PIXEL — spheres, quads, misses, triangle pixels whose indices do not count — is handled
+ * exactly as ptmi_accumulate_views_motion handles it, through motions16 / n_objects, where n_objects = 0 with a null motions16 means a static world.
+ *
+ * THE RECORD of (view v, transform o) is made on the host, once per call, from the two captured tables AS STORED, with no inversion of its own: the affine part of
+ * invModel of view v; the affine part of model of view v-1; the 3x3 of invModel of view v-1; a `same` flag, set when the object's two 128-byte records are bytewise
+ * equal.  An element of those that is not finite gives PTMI_ERR_INVALID_ARG naming the view and the object.  At most PTMI_MOTION_MAX_RECORDS of them
+ * (n_views x n_transforms).
+ *
+ * PER DEFORM PIXEL.  STATIC SHORTCUT: when the 18 position and normal words of triangle prim are bitwise equal in slots v and v-1 and `same` is set, the pixel runs
+ * ptmi_accumulate_views_frames' arithmetic bit for bit.  Otherwise, between step 1 and step 2 of "Fusion" with u = v-1:
+ *   1  x = invModel_v . X
+ *   2  with A, B, C of slot v: e1 = B - A, e2 = C - A, d = x - A; d00 = e1.e1, d01 = e1.e2, d11 = e2.e2, d20 = d.e1, d21 = d.e2; den = d00 d11 - d01 d01;
+ *      b = (d11 d20 - d01 d21) / den; c = (d00 d21 - d01 d20) / den; a = (1 - b) - c: the orthogonal projection of x onto the triangle's plane (X comes from a mean
+ *      depth along the pixel's centre ray and need not lie in it)
+ *   3  nothing is taken over unless den is finite and > 0 and a, b, c are finite and in [-1, 2] — one triangle's width of extrapolation, since the pixel's centre
+ *      may lie on a neighbour of the triangle its first ray hit; the bound is a constant of the definition (PTMDF_BARY_MIN, PTMDF_BARY_MAX)
+ *   4  x' = (a A' + b B') + c C' with the vertices of slot v-1; X' = model_{v-1} . x'
+ *   5  m = (a nA + b nB) + c nC from slot v and m' likewise from slot v-1 (the weights as hit_triangle pairs them: A with w, B with u, C with v);
+ *      s = the sign of (invModel_v^T m) . n(p); k = invModel_{v-1}^T m'; len = |k|; nothing is taken over unless len is finite and > 0; n' = k / len, negated when
+ *      s < 0: the shading normal the previous view's renderer computed for that material point, facing as p's does
+ *   6  X' goes into the projection in X's place, n' into the weight in n(p)'s.
+ * Own state, history, mean, variance, pass-through and the three planes are untouched.  The f32 operation order is fixed in include/ptmi_deform.h, which the kernel
+ * (k_accumulate_view_deform, csrc/ptmi_accumulate_kernels.h, a fourth entry beside the three the other calls keep launching) and the host reference both compile.
+ * A camera that moves WITH a mesh (every vertex and the camera translated by T per view) has q = p and wgt exactly 1 on it: n after k such one-frame views is k.
+ *
+ * OUT OF SCOPE: fusion through deformation (it needs this stack and no composed matrices); meshes whose triangle count or order changes between views (a build, or
+ * an upload without a refit); an object test at q; lighting that changed between the views; multi-device contexts. */
+#define PTMI_GEOMETRY_MAX_BYTES (1ull << 34) /* 16 GiB: some 190 views of an 871 k-triangle scene.  The stack is ONE allocation beside the context's six image
+                                                stacks and is sized by an argument (n_views), not by the scene alone: a mistaken count is to be refused by name
+                                                and not to take the board's memory from the stacks the call after it needs */
+int ptmi_capture_view_geometry(ptmi_ctx* ctx, uint32_t view, uint32_t n_views);
+/* Test and tool hook: slot `view` back on the host.  triangles_out (tri_bytes = 96 x n_triangles) and transforms_out (tf_bytes = 128 x n_transforms) may each be
+ * NULL.  A slot that was never captured is PTMI_ERR_STATE.  Synchronises the stream. */
+int ptmi_read_view_geometry(ptmi_ctx* ctx, uint32_t view, float* triangles_out, size_t tri_bytes, float* transforms_out, size_t tf_bytes);
+/* The stack's two device arrays (transforms: NULL when the scene has none) and its key; any out pointer may be NULL.  PTMI_ERR_STATE when there is no stack. */
+int ptmi_geometry_device_ptr(ptmi_ctx* ctx, void** triangles, void** transforms, uint32_t* n_views, uint64_t* n_triangles, uint64_t* n_transforms);
+int ptmi_release_geometry(ptmi_ctx* ctx);
+/* ptmi_accumulate_views_motion through the geometry stack.  Writes the same ACCUMULATED STACK: ptmi_read_accumulated, ptmi_resolve_accumulated_rgba8 and
+ * ptmi_denoise_views_accumulated work on its result unchanged.  Reads geometry slots first_view .. first_view + n_views - 1, and first_view - 1 when resuming.
+ * Errors and their order are ptmi_accumulate_views_motion's (a null motions16 is allowed with n_objects = 0); then, after frame_nums' checks: no geometry stack, a
+ * stack whose view count differs from the view stack's, a stack whose triangle or transform count differs from the scene's now, a slot it reads that was never
+ * captured (naming the view): PTMI_ERR_STATE; then the records' and the motions' checks.  Asynchronous; one launch per view, in order on the context's stream. */
+int ptmi_accumulate_views_deform(ptmi_ctx* ctx, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, const float* motions16,
+                                 uint32_t n_objects, uint32_t first_view, uint32_t n_views, int resume);
+/* The kernel on host arrays, and the host reference (no GPU): ptmi_accumulate_images_motion / ptmi_accumulate_reference_motion with the geometry itself —
+ * triangles_seq [n_images][n_triangles][24] (n_triangles >= 1), transforms_seq [n_images][n_transforms][32], meshes [n_meshes][4] i32; a table whose count is 0
+ * may be NULL — and motions16 / object_ids for the pixels that are no deform pixels (motions16 NULL with n_objects = 0: a static world, object_ids is then not
+ * read).  Image 0's geometry is read only as the predecessor of image 1.  The reference reports a transform that is not finite as PTMI_ERR_INVALID_ARG. */
+int ptmi_accumulate_images_deform(ptmi_ctx* ctx, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                  const float* frame_nums, const float* triangles_seq, uint32_t n_triangles, const float* transforms_seq, uint32_t n_transforms,
+                                  const int32_t* meshes, uint32_t n_meshes, const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees,
+                                  const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out);
+int ptmi_accumulate_reference_deform(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                     const float* frame_nums, const float* triangles_seq, uint32_t n_triangles, const float* transforms_seq, uint32_t n_transforms,
+                                     const int32_t* meshes, uint32_t n_meshes, const float* motions16, uint32_t n_objects, const int32_t* object_ids,
+                                     float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in,
+                                     float* out, int threads);
+/* No GPU: THE RECORD (above) of every transform of one view, cur32, against the view before it, prev32 (n_transforms x 32 f32 each), as the calls make them, into
+ * records_out [n_transforms][36] 32-bit words (include/ptmi_deform.h, ptmdf_record).  PTMI_ERR_INVALID_ARG with the object in *bad_object (may be NULL) where an
+ * element read is not finite. */
+int ptmi_deform_records(const float* prev32, const float* cur32, uint32_t n_transforms, uint32_t* records_out, uint32_t* bad_object);
 
 /* FUSION WITH PER-OBJECT MOTION.  "Fusion" carries a pixel's world point X UNCHANGED into the up to 2 x 8 neighbouring views of its window; where p's object moved, X
  * lands on another material point of that object or is refused by the depth or normal test — across up to eight steps of motion, not one.  The calls below are

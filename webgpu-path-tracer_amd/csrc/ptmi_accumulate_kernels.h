@@ -15,12 +15,19 @@
 //                       holds already, through the call's three small id tables and, for a triangle, one 4-byte gather of its mesh index — and, where that object has a
 //                       record, loads the record's six float4 PER LANE (the object varies within a wave) and moves the point and the normal unless the record is the
 //                       identity.  Up to three dependent gathers (triangle, mesh id, record) stand before the six at q; the other two entries compile none of it.
+// k_accumulate_view_deform  The motion body with DEFORMATION (ptmi_accumulate_images_deform, include/ptmi_deform.h): a lane whose I names a triangle whose index counts
+//                       gathers that triangle from the geometry of view v and of view v-1 — the same offset in both slots, so ONE group of twelve independent 16-byte
+//                       loads under one operand fence (deform_loaded) —, then, from the mesh word it now holds, the mesh's transform index (4 bytes) and that
+//                       transform's record, nine float4 under a fence of their own.  The static shortcut is tested per lane on the loaded words.  Every other
+//                       lane takes the motion entry's path.  Up to three dependent gathers (triangles, transform index, record) stand before the six at q.  Up to
+//                       192 B of triangles and 144 B of record per deforming triangle pixel.  No LDS, no atomics (profiles/deform_kernel_resources.txt).
 // k_accumulated_variance  k_guided_variance (ptmi_guided_kernels.h: the same tile, the same staging, the same 7 x 7 walk) for a stack that brings its variance
 //                       with it: v0 is plane 2's w where that is not NaN, the spatial estimate elsewhere.  A second kernel beside k_guided_variance, which stays as it is.
 #pragma once
 
 #include "../../include/ptmi_accumulate.h"
 #include "../../include/ptmi_motion.h"
+#include "../../include/ptmi_deform.h"
 #include "ptmi_fuse_kernels.h"
 #include "ptmi_guided_kernels.h"
 
@@ -40,15 +47,60 @@ DEV int accumulate_move(const MotionArgs& mo, uint32_t idx, const float4& Ip, fl
   return motion_apply(mo.records + 6 * (size_t)obj, X, gw);
 }
 
+// What k_accumulate_view_deform has beside the motion entry's operands.  tris_cur, tris_prev: the triangles (six float4 each) as view v and view v-1 were rendered,
+// in one order; records: view v's n_transforms records (ptmdf_record: nine float4 each); meshes: 4 i32 per mesh.  A view without a predecessor reads none of it.
+struct DeformArgs {
+  const float4 *tris_cur, *tris_prev;
+  const float4* records;
+  const int32_t* meshes;
+  uint32_t n_tris, n_meshes, n_transforms;
+};
+
+// Keeps the twelve loads of a triangle's two slots together, as motion_loaded keeps a record's six: every word that is read is an operand here
+DEV void deform_loaded(const float4& c0, const float4& c1, const float4& c2, const float4& c3, const float4& c4, const float4& c5, const float4& p0, const float4& p1,
+                       const float4& p2, const float4& p3, const float4& p4, const float4& p5) {
+  asm volatile("" ::"v"(c0.x), "v"(c0.y), "v"(c0.z), "v"(c1.x), "v"(c1.y), "v"(c1.z), "v"(c2.x), "v"(c2.y), "v"(c2.z), "v"(c3.x), "v"(c3.y), "v"(c3.z), "v"(c4.x), "v"(c4.y),
+               "v"(c4.z), "v"(c5.x), "v"(c5.y), "v"(c5.z), "v"(c5.w));
+  asm volatile("" ::"v"(p0.x), "v"(p0.y), "v"(p0.z), "v"(p1.x), "v"(p1.y), "v"(p1.z), "v"(p2.x), "v"(p2.y), "v"(p2.z), "v"(p3.x), "v"(p3.y), "v"(p3.z), "v"(p4.x), "v"(p4.y),
+               "v"(p4.z), "v"(p5.x), "v"(p5.y), "v"(p5.z));
+}
+DEV void deform_put(float* T, int i, const float4& a) { T[4 * i] = a.x, T[4 * i + 1] = a.y, T[4 * i + 2] = a.z, T[4 * i + 3] = a.w; }
+
+// The deformation of pixel idx's triangle on its world point X and on the normal in gw (ptmdf_move); 0: nothing is taken over.  A pixel that takes the static
+// shortcut leaves both; a pixel that is no deform pixel (include/ptmi_deform.h, WHICH PIXELS) is accumulate_move's.
+DEV int accumulate_deform(const DeformArgs& de, const MotionArgs& mo, uint32_t idx, const float4& Ip, float* X, ptmd_f4* gw) {
+  uint32_t prim, tf;
+  if (ptmdf_prim(dn_f4(Ip), de.n_tris, &prim)) {
+    const float4 *tc = de.tris_cur + 6 * (size_t)prim, *tp = de.tris_prev + 6 * (size_t)prim;
+    const float4 c0 = tc[0], c1 = tc[1], c2 = tc[2], c3 = tc[3], c4 = tc[4], c5 = tc[5], p0 = tp[0], p1 = tp[1], p2 = tp[2], p3 = tp[3], p4 = tp[4], p5 = tp[5];  // twelve independent gathers
+    deform_loaded(c0, c1, c2, c3, c4, c5, p0, p1, p2, p3, p4, p5);
+    if (ptmdf_transform(c5.w, de.meshes, de.n_meshes, de.n_transforms, &tf)) {
+      const float4* rp = de.records + 9 * (size_t)tf;
+      const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3], r4 = rp[4], r5 = rp[5], r6 = rp[6], r7 = rp[7], r8 = rp[8];  // nine independent loads
+      motion_loaded(r0, r1, r2, r3, r4, r5);
+      asm volatile("" ::"v"(r6.x), "v"(r6.y), "v"(r6.z), "v"(r6.w), "v"(r7.x), "v"(r7.y), "v"(r7.z), "v"(r7.w), "v"(r8.x), "v"(r8.y));
+      float Tc[24], Tp[24];
+      deform_put(Tc, 0, c0), deform_put(Tc, 1, c1), deform_put(Tc, 2, c2), deform_put(Tc, 3, c3), deform_put(Tc, 4, c4), deform_put(Tc, 5, c5);
+      deform_put(Tp, 0, p0), deform_put(Tp, 1, p1), deform_put(Tp, 2, p2), deform_put(Tp, 3, p3), deform_put(Tp, 4, p4), deform_put(Tp, 5, p5);
+      if (__float_as_uint(r8.y) != 0u && ptmdf_static(Tc, Tp)) return 1;  // ptmdf_record::same
+      ptmdf_record R;
+      deform_put(R.ic, 0, r0), deform_put(R.ic, 1, r1), deform_put(R.ic, 2, r2), deform_put(R.mp, 0, r3), deform_put(R.mp, 1, r4), deform_put(R.mp, 2, r5);
+      deform_put(R.ip, 0, r6), deform_put(R.ip, 1, r7), R.ip[8] = r8.x;
+      return ptmdf_move(&R, Tc, Tp, X, gw);
+    }
+  }
+  return accumulate_move(mo, idx, Ip, X, gw);
+}
+
 // colour, moments: [n_stack][npix] float4 sums; layers: [n_stack][3][npix] float4; prev1, prev2: planes 1 and 2 of view v - 1 ([npix] float4 each), nullptr: view v has
 // no history; out0, out1, out2: view v's image of planes 0, 1, 2; tab: kFuseRow float4 per view of the stack; lamb: one byte per material index or nullptr.
 // grid: x = (tiles of 64 columns x rows) / 4; block 256.
 // FRAMES: frames [n_stack] f32, F_u of every view of the stack; k.F is then not read: own, mean and the pass-through take F_v, the lookup's validity test F_{v-1}.
-// MOTION: mo as above; every other instance is handed an empty one and reads none of it.
-template <bool FRAMES, bool MOTION = false>
+// MOTION: mo as above; every other instance is handed an empty one and reads none of it.  DEFORM (with MOTION): de as above, likewise.
+template <bool FRAMES, bool MOTION = false, bool DEFORM = false>
 DEV void accumulate_view(const float4* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ layers, const float4* prev1, const float4* prev2,
                          float4* out0, float4* out1, float4* out2, const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t v,
-                         ptmf_consts k, ptma_consts ka, const float* __restrict__ frames, const MotionArgs& mo = MotionArgs{}) {
+                         ptmf_consts k, ptma_consts ka, const float* __restrict__ frames, const MotionArgs& mo = MotionArgs{}, const DeformArgs& de = DeformArgs{}) {
   const uint32_t tiles_x = ((uint32_t)W + 63u) / 64u;
   const uint32_t tile = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);  // wave-uniform
   const uint32_t y = tile / tiles_x;
@@ -75,7 +127,8 @@ DEV void accumulate_view(const float4* __restrict__ colour, const float4* __rest
     int qx, qy;
     ptmf_world(&k, &V, x, idx, gp.w, X);
     int moved = 1;
-    if constexpr (MOTION) moved = accumulate_move(mo, idx, Ip, X, &gp);  // (gp's normal is read by the weight alone from here on)
+    if constexpr (DEFORM) moved = accumulate_deform(de, mo, idx, Ip, X, &gp);
+    else if constexpr (MOTION) moved = accumulate_move(mo, idx, Ip, X, &gp);  // (gp's normal is read by the weight alone from here on)
     if (moved && ptmf_project(&k, &U, X, &qx, &qy, &r)) {
       const size_t q = (size_t)qy * (size_t)W + (size_t)qx;
       const float4* Lu = layers + (size_t)(v - 1u) * 3 * npix;
@@ -120,6 +173,14 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_view_motion(const float4*
                                                                    const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H,
                                                                    uint32_t v, ptmf_consts k, ptma_consts ka, const float* __restrict__ frames, MotionArgs mo) {
   accumulate_view<true, true>(colour, moments, layers, prev1, prev2, out0, out1, out2, tab, lamb, n_materials, W, H, v, k, ka, frames, mo);
+}
+
+// k_accumulate_view_motion with the geometry of the view and of its predecessor (ptmi_accumulate_images_deform)
+__global__ __launch_bounds__(kBlock) void k_accumulate_view_deform(const float4* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ layers,
+                                                                   const float4* prev1, const float4* prev2, float4* out0, float4* out1, float4* out2,
+                                                                   const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H,
+                                                                   uint32_t v, ptmf_consts k, ptma_consts ka, const float* __restrict__ frames, MotionArgs mo, DeformArgs de) {
+  accumulate_view<true, true, true>(colour, moments, layers, prev1, prev2, out0, out1, out2, tab, lamb, n_materials, W, H, v, k, ka, frames, mo, de);
 }
 
 // grid: x = tiles of 64 columns, y = tiles of kGuidedTY rows, z = view of the batch.  d0: [n][npix] packed (prepare); plane2: [n][npix] float4, w = the given v0 or NaN

@@ -142,6 +142,15 @@ struct ptmi_ctx {
   StagedTable view_rows;   // the last ptmi_render_views / ptmi_render_aov call's view table (ViewTab: kViewRow float4 per view)
   StagedTable fuse_tab;    // the last ptmi_fuse_views / ptmi_accumulate_views call's table (kFuseRow float4 per view of the stack, then one byte per material; the *_frames calls: then one f32 per view, its frame count)
   StagedTable denoise_tab; // the last ptmi_denoise_views_frames / ptmi_denoise_views_guided_frames call's frame counts: one f32 per view of the stack
+  // The GEOMETRY STACK (ptmi_capture_view_geometry): per view of a path the triangles and the transform table as they were when the view was rendered.  It holds no
+  // image: ptmi_resize leaves it alone.  Keyed by (n_views, n_tris, n_xforms); the transforms also on the host, where a call's records are made from them.
+  struct GeometryStack {
+    DBuf tris, xforms;             // [n_views][n_tris][24] f32, [n_views][n_xforms][32] f32
+    std::vector<float> h_xforms;   // [n_views][n_xforms][32]
+    std::vector<uint8_t> captured; // [n_views]: 1 once the slot has been written
+    uint32_t n_views = 0;
+    size_t n_tris = 0, n_xforms = 0;
+  } geometry;
   bool view_moments = false;  // ptmi_set_view_moments: ptmi_render_views folds second moments into stacks[STACK_MOMENTS] too
   DBuf d_noise_rec;           // ptmi_view_noise_stats: one record (kNoiseRecordBytes) per view of the call
   int rank = 0, world = 1, tile = 64;

@@ -25,6 +25,7 @@
 #include "../../include/ptmi_accumulate.h"
 #include "../../include/ptmi_motion.h"
 #include "../../include/ptmi_fuse_motion.h"
+#include "../../include/ptmi_deform.h"
 #include "../../include/ptmi_noise.h"
 #include "ptmi_bvh_domain.h"
 
@@ -1073,9 +1074,19 @@ extern "C" void ptmi_default_accumulate_params(ptmi_accumulate_params* p) {
 // frame_nums: nullptr, or every image's own divisor (ptmi_accumulate_reference_frames): own, mean and the pass-through of view v take F_v, the lookup in view v-1 F_{v-1}.
 // motion: nullptr, or the motions and the id images of ptmi_accumulate_reference_motion: between the world point and its projection a pixel whose object has a record
 // that is not the identity moves the point and the normal (include/ptmi_motion.h); every other pixel runs what it ran.
+// deform: nullptr, or the geometry of ptmi_accumulate_reference_deform: a triangle pixel whose indices count is carried from its triangle in image v to the same
+// triangle in image v-1 (include/ptmi_deform.h) unless it takes the static shortcut; every other pixel is `motion`'s, which may then be nullptr (a static world).
+struct ReferenceDeform {
+  const float* triangles_seq;   // [n_images][n_triangles][24]
+  uint32_t n_triangles;
+  const float* transforms_seq;  // [n_images][n_transforms][32]
+  uint32_t n_transforms;
+  const int32_t* meshes;  // [n_meshes][4]
+  uint32_t n_meshes;
+};
 static int accumulate_reference(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
                                 const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
-                                const float* history_in, float* out, int threads, const ReferenceMotion* motion = nullptr) {
+                                const float* history_in, float* out, int threads, const ReferenceMotion* motion = nullptr, const ReferenceDeform* deform = nullptr) {
   if (!colour_sums || !moments || !layers || !views16 || !out || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
   ptmi_accumulate_params P;
   if (params) P = *params;
@@ -1103,6 +1114,22 @@ static int accumulate_reference(const float* colour_sums, const float* moments, 
     for (uint32_t v = 1; v < n_images; v++)
       for (uint32_t o = 0; o < motion->n_objects; o++)
         if (!ptmm_make_record(motion->motions16 + 16 * ((size_t)v * motion->n_objects + o), &rec[(size_t)(v - 1) * motion->n_objects + o])) return PTMI_ERR_INVALID_ARG;
+  }
+  std::vector<ptmdf_record> drec;  // likewise: image v's records pair its transforms with image v-1's
+  if (deform) {
+    if (!deform->triangles_seq || !deform->n_triangles || (deform->n_transforms && !deform->transforms_seq) || (deform->n_meshes && !deform->meshes) ||
+        (uint64_t)n_images * deform->n_transforms > (uint64_t)PTMI_MOTION_MAX_RECORDS)
+      return PTMI_ERR_INVALID_ARG;
+    try {
+      drec.resize((size_t)(n_images - 1) * deform->n_transforms);
+    } catch (const std::bad_alloc&) {
+      return PTMI_ERR_NO_MEMORY;
+    }
+    for (uint32_t v = 1; v < n_images; v++)
+      for (uint32_t o = 0; o < deform->n_transforms; o++)
+        if (!ptmdf_make_record(deform->transforms_seq + 32 * ((size_t)v * deform->n_transforms + o), deform->transforms_seq + 32 * ((size_t)(v - 1) * deform->n_transforms + o),
+                               &drec[(size_t)(v - 1) * deform->n_transforms + o]))
+          return PTMI_ERR_INVALID_ARG;
   }
   ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor), ku = k;
   const ptma_consts ka = ptma_make_consts(P.max_history, P.min_frames);
@@ -1140,8 +1167,20 @@ static int accumulate_reference(const float* colour_sums, const float* moments, 
             float X[3], r, wgt;
             int qx, qy;
             ptmf_world(&k, &tab[v], x, idx, gp.w, X);
-            int moved = 1;
-            if (motion) {
+            int moved = 1, deformed = 0;
+            if (deform) {
+              uint32_t prim, tf;
+              if (ptmdf_prim(Lv[2 * npix + idx], deform->n_triangles, &prim)) {
+                const float* Tc = deform->triangles_seq + 24 * ((size_t)v * deform->n_triangles + prim);
+                const float* Tp = deform->triangles_seq + 24 * ((size_t)(v - 1) * deform->n_triangles + prim);
+                if (ptmdf_transform(Tc[23], deform->meshes, deform->n_meshes, deform->n_transforms, &tf)) {
+                  const ptmdf_record* R = &drec[(size_t)(v - 1) * deform->n_transforms + tf];
+                  deformed = 1;
+                  if (!(R->same && ptmdf_static(Tc, Tp))) moved = ptmdf_move(R, Tc, Tp, X, &gp);  // (gp's normal is read by the weight alone from here on)
+                }
+              }
+            }
+            if (motion && !deformed) {
               const int32_t obj = motion->object_ids[(size_t)v * npix + idx];
               if (ptmm_has_record(obj, motion->n_objects)) {
                 const ptmm_record* R = &rec[(size_t)(v - 1) * motion->n_objects + (uint32_t)obj];
@@ -1183,6 +1222,32 @@ extern "C" int ptmi_accumulate_reference_motion(const float* colour_sums, const 
   const ReferenceMotion motion{motions16, n_objects, object_ids};
   return accumulate_reference(colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, fov_degrees, lambertian, n_materials, params, history_in, out, threads,
                               &motion);
+}
+extern "C" int ptmi_accumulate_reference_deform(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                                const float* frame_nums, const float* triangles_seq, uint32_t n_triangles, const float* transforms_seq, uint32_t n_transforms,
+                                                const int32_t* meshes, uint32_t n_meshes, const float* motions16, uint32_t n_objects, const int32_t* object_ids,
+                                                float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
+                                                const float* history_in, float* out, int threads) {
+  if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
+  if (n_objects && !motions16) return PTMI_ERR_INVALID_ARG;
+  const ReferenceMotion motion{motions16, n_objects, object_ids};
+  const ReferenceDeform deform{triangles_seq, n_triangles, transforms_seq, n_transforms, meshes, n_meshes};
+  return accumulate_reference(colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, fov_degrees, lambertian, n_materials, params, history_in, out, threads,
+                              motions16 ? &motion : nullptr, &deform);  // (a null motions16 with n_objects = 0: every pixel that is no deforming triangle's is static)
+}
+// The records of one view against its predecessor (include/ptmi_deform.h, ptmdf_make_record) as the calls make them: records_out [n_transforms][36] words.
+// PTMI_ERR_INVALID_ARG with the object in *bad_object (may be NULL): one of the elements its record takes is not finite.
+extern "C" int ptmi_deform_records(const float* prev32, const float* cur32, uint32_t n_transforms, uint32_t* records_out, uint32_t* bad_object) {
+  if (!prev32 || !cur32 || !records_out) return PTMI_ERR_INVALID_ARG;
+  for (uint32_t o = 0; o < n_transforms; o++) {
+    ptmdf_record R;
+    if (!ptmdf_make_record(cur32 + 32 * (size_t)o, prev32 + 32 * (size_t)o, &R)) {
+      if (bad_object) *bad_object = o;
+      return PTMI_ERR_INVALID_ARG;
+    }
+    memcpy(records_out + 36 * (size_t)o, &R, sizeof R);
+  }
+  return PTMI_OK;
 }
 
 // The object of every pixel (include/ptmi_motion.h, ptmm_object): the three id tables the kernel of ptmi_accumulate_views_motion is handed, made here from the records.

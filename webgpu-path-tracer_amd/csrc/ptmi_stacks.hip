@@ -609,14 +609,99 @@ int ptmi_fuse_images_frames(ptmi_ctx* c, const float* colour, const float* layer
   return fuse_images(c, "ptmi_fuse_images_frames", colour, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params, out);
 }
 
+// ---- the geometry stack (ptmi_capture_view_geometry): what ptmi_accumulate_views_deform reads of a view beside its images ----
+static int check_geometry_view(ptmi_ctx* c, const char* who, uint32_t view) {
+  const ptmi_ctx::GeometryStack& g = c->geometry;
+  if (!g.n_views) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no geometry stack: ptmi_capture_view_geometry makes it, view by view");
+  if (view >= g.n_views) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": view " + std::to_string(view) + " of " + std::to_string(g.n_views));
+  if (!g.captured[view]) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry of view " + std::to_string(view) + " was never captured");
+  return PTMI_OK;
+}
+int ptmi_capture_view_geometry(ptmi_ctx* c, uint32_t view, uint32_t n_views) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  const char* who = "ptmi_capture_view_geometry";
+  if (int r = check_stack_call(c, who, "a scene's copies", "several", nullptr, false, 0.0f)) return r;
+  const size_t n_tris = c->n_tris_uploaded, n_xf = c->h_xforms.size() / 32;
+  if (n_views == 0 || view >= n_views) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": view " + std::to_string(view) + " of " + std::to_string(n_views));
+  if (n_tris == 0) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the scene has no triangles");
+  if (c->bvh_on_device && c->bvh_dev_stale)
+    return fail(c, PTMI_ERR_STATE, std::string(who) + ": the scene's tree is stale, so its triangles lie in upload order and not in the order a render would see: "
+                                                       "ptmi_refit_scene_bvh or ptmi_build_scene_bvh first");
+  const uint64_t per_view = (uint64_t)n_tris * 96 + (uint64_t)n_xf * 128;
+  if (per_view > (uint64_t)PTMI_GEOMETRY_MAX_BYTES / n_views)
+    return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": " + std::to_string(n_views) + " views x " + std::to_string(per_view) + " bytes are more than PTMI_GEOMETRY_MAX_BYTES");
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  ptmi_ctx::GeometryStack& g = c->geometry;
+  if (g.n_views != n_views || g.n_tris != n_tris || g.n_xforms != n_xf) {  // another key: a new stack, had whole before the old one goes
+    ptmi_ctx::GeometryStack fresh;
+    HIP_TRY(c, fresh.tris.ensure((size_t)n_views * n_tris * 96));
+    HIP_TRY(c, fresh.xforms.ensure(std::max<size_t>((size_t)n_views * n_xf * 128, 16)));
+    try {
+      fresh.h_xforms.resize((size_t)n_views * n_xf * 32);
+      fresh.captured.assign(n_views, 0);
+    } catch (const std::bad_alloc&) {
+      return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the geometry stack");
+    }
+    fresh.n_views = n_views, fresh.n_tris = n_tris, fresh.n_xforms = n_xf;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a call enqueued earlier may still read the old stack)
+    g = std::move(fresh);
+  }
+  if (g.captured[view]) HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the slot's host transforms may still be on their way from its last capture)
+  if (n_xf) memcpy(g.h_xforms.data() + (size_t)view * n_xf * 32, c->h_xforms.data(), n_xf * 128);
+  HIP_TRY(c, hipMemcpyAsync(g.tris.as<uint8_t>() + (size_t)view * n_tris * 96, c->d_tris.p, n_tris * 96, hipMemcpyDeviceToDevice, c->stream));
+  if (n_xf) HIP_TRY(c, hipMemcpyAsync(g.xforms.as<uint8_t>() + (size_t)view * n_xf * 128, g.h_xforms.data() + (size_t)view * n_xf * 32, n_xf * 128, hipMemcpyHostToDevice, c->stream));
+  g.captured[view] = 1;
+  return PTMI_OK;
+}
+int ptmi_read_view_geometry(ptmi_ctx* c, uint32_t view, float* triangles_out, size_t tri_bytes, float* transforms_out, size_t tf_bytes) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  const char* who = "ptmi_read_view_geometry";
+  if (int r = check_geometry_view(c, who, view)) return r;
+  const ptmi_ctx::GeometryStack& g = c->geometry;
+  if ((triangles_out && tri_bytes != g.n_tris * 96) || (transforms_out && tf_bytes != g.n_xforms * 128))
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": byte size differs from the slot's (" + std::to_string(g.n_tris * 96) + " of triangles, " + std::to_string(g.n_xforms * 128) + " of transforms)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (triangles_out) HIP_TRY(c, hipMemcpy(triangles_out, g.tris.as<uint8_t>() + (size_t)view * g.n_tris * 96, g.n_tris * 96, hipMemcpyDeviceToHost));
+  if (transforms_out && g.n_xforms) HIP_TRY(c, hipMemcpy(transforms_out, g.xforms.as<uint8_t>() + (size_t)view * g.n_xforms * 128, g.n_xforms * 128, hipMemcpyDeviceToHost));
+  return PTMI_OK;
+}
+int ptmi_geometry_device_ptr(ptmi_ctx* c, void** triangles, void** transforms, uint32_t* n_views, uint64_t* n_triangles, uint64_t* n_transforms) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  const ptmi_ctx::GeometryStack& g = c->geometry;
+  if (!g.n_views) return fail(c, PTMI_ERR_STATE, "ptmi_geometry_device_ptr: no geometry stack: ptmi_capture_view_geometry makes it, view by view");
+  if (triangles) *triangles = g.tris.p;
+  if (transforms) *transforms = g.n_xforms ? g.xforms.p : nullptr;
+  if (n_views) *n_views = g.n_views;
+  if (n_triangles) *n_triangles = g.n_tris;
+  if (n_transforms) *n_transforms = g.n_xforms;
+  return PTMI_OK;
+}
+int ptmi_release_geometry(ptmi_ctx* c) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  if (c->geometry.n_views) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  c->geometry = ptmi_ctx::GeometryStack{};
+  return PTMI_OK;
+}
+
 // ---- the accumulated stack (ptmi_accumulate_views, ptmi_accumulate_images) and the guided filter on it (ptmi_denoise_views_accumulated, ptmi_denoise_images_accumulated) ----
 // (ptmi_default_accumulate_params, ptmi_accumulate_reference and ptmi_denoise_accumulated_reference need no GPU: ptmi_host.cpp)
 // The kernel on device arrays: colour, moments [n_stack][H][W] float4, layers [n_stack][3][H][W] float4, planes [3][n_stack][H][W] float4, of which views
 // [first, first + n) are written, one launch per view in ascending order; view `first` takes its history from view first - 1 of `planes` when `resume`.
 // frames: nullptr, or the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_accumulate_view_frames.
+// deform (with frames; motion may be nullptr: a static world beside the triangles): k_accumulate_view_deform's operands, args.tris_cur = slot 0 of the geometry, slot
+// after slot `slot` float4 apart, indexed by the view's number; args.records laid out as the motion records are.
+struct DeformCall {
+  DeformArgs args;
+  size_t slot;
+};
 static int accumulate_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, const float4* layers, float4* planes, const void* tab, bool has_lamb, uint32_t n_materials,
                               int W, int H, uint32_t n_stack, uint32_t first, uint32_t n, bool resume, const ptmf_consts& k, const ptma_consts& ka, const float* frames = nullptr,
-                              const MotionArgs* motion = nullptr) {
+                              const MotionArgs* motion = nullptr, const DeformCall* deform = nullptr) {
   const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
   const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
   const uint8_t* lamb = has_lamb ? reinterpret_cast<const uint8_t*>(tab) + (size_t)n_stack * kFuseRow * 16 : nullptr;
@@ -624,7 +709,20 @@ static int accumulate_enqueue(ptmi_ctx* c, const float4* colour, const float4* m
   auto plane = [&](uint32_t pl, uint32_t v) { return planes + ((size_t)pl * n_stack + v) * npix; };
   for (uint32_t v = first; v < first + n; v++) {
     const bool has_prev = v > 0 && (v > first || resume);
-    if (motion) {  // (with frames.)  The records of the call lie view after view from the first view that has a predecessor; a view without one reads none.
+    if (deform) {
+      MotionArgs mo = motion ? *motion : MotionArgs{};
+      DeformArgs de = deform->args;
+      if (has_prev) {
+        const size_t rel = v - (resume ? first : first + 1u);
+        if (motion) mo.records += rel * mo.n_objects * 6;
+        de.records += rel * de.n_transforms * 9;
+      }
+      if (mo.ids) mo.ids += (size_t)v * npix;
+      de.tris_cur = deform->args.tris_cur + (size_t)v * deform->slot, de.tris_prev = deform->args.tris_cur + (size_t)(has_prev ? v - 1u : v) * deform->slot;
+      hipLaunchKernelGGL(k_accumulate_view_deform, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr,
+                         has_prev ? plane(2, v - 1) : nullptr, plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka, frames, mo,
+                         de);
+    } else if (motion) {  // (with frames.)  The records of the call lie view after view from the first view that has a predecessor; a view without one reads none.
       MotionArgs mo = *motion;
       if (has_prev) mo.records += (size_t)(v - (resume ? first : first + 1u)) * mo.n_objects * 6;
       if (mo.ids) mo.ids += (size_t)v * npix;
@@ -667,15 +765,36 @@ static int make_motion_records(ptmi_ctx* c, const char* who, const float* motion
   return PTMI_OK;
 }
 
+// The *_deform calls: the records (include/ptmi_deform.h) of views [lo, hi) — each from the transforms of its view and of the view before, slot after slot of
+// n_transforms x 32 f32 from `tf0` = slot 0 — view after view into `rec`.  Allocates host memory only.
+static int make_deform_records(ptmi_ctx* c, const char* who, const float* tf0, uint32_t n_transforms, uint32_t n_all, uint32_t lo, uint32_t hi, std::vector<ptmdf_record>* rec) {
+  if ((uint64_t)n_all * n_transforms > (uint64_t)PTMI_MOTION_MAX_RECORDS)
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": " + std::to_string(n_all) + " views x " + std::to_string(n_transforms) + " transforms are more than PTMI_MOTION_MAX_RECORDS records");
+  try {
+    rec->resize((size_t)(hi > lo ? hi - lo : 0) * n_transforms);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the deformation records");
+  }
+  for (uint32_t v = std::max(lo, 1u); v < hi; v++)
+    for (uint32_t o = 0; o < n_transforms; o++)
+      if (!ptmdf_make_record(tf0 + 32 * ((size_t)v * n_transforms + o), tf0 + 32 * ((size_t)(v - 1) * n_transforms + o), &(*rec)[(size_t)(v - lo) * n_transforms + o]))
+        return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the transform of view " + std::to_string(v) + " or of view " + std::to_string(v - 1) + ", object " + std::to_string(o) +
+                                                 ", has an element that is not finite: view " + std::to_string(v) + " is read by this call");
+  return PTMI_OK;
+}
+
 // ptmi_accumulate_views (per_view false: frame_num), ptmi_accumulate_views_frames (per_view: frame_nums, one per view of the stack) and ptmi_accumulate_views_motion
-// (motion: per_view, and motions16 [n_views of the stack][n_objects][16])
+// (motion: per_view, and motions16 [n_views of the stack][n_objects][16]) and ptmi_accumulate_views_deform (deform: motion, whose motions16 may then be null with
+// n_objects = 0, and the geometry stack)
 static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_params* params, const float* views16, float frame_num, const float* frame_nums, bool per_view,
-                            uint32_t first_view, uint32_t n_views, int resume, bool motion = false, const float* motions16 = nullptr, uint32_t n_objects = 0) {
+                            uint32_t first_view, uint32_t n_views, int resume, bool motion = false, const float* motions16 = nullptr, uint32_t n_objects = 0, bool deform = false) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_accumulate_params P;
   if (int r = accumulate_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
   if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  static const float no_motions[16] = {};
+  if (deform && !motions16 && n_objects == 0) motions16 = no_motions;  // (a static world beside the triangles: no entry is read)
   if (motion && !motions16) return make_motion_records(c, who, nullptr, 0, 0, 0, 0, nullptr);
   if (int r = check_stack(c, STACK_MOMENTS, who, 0)) return r;  // (the moment stack first, as ptmi_denoise_views_guided asks)
   if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
@@ -693,14 +812,29 @@ static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_
   // from the host copies, so that no device buffer a render has yet to refresh is read.  The triangles are on the device already (ptmi_upload puts them there).
   std::vector<uint32_t> blob;
   MotionArgs mo{};
+  DeformCall dc{};
+  std::vector<ptmdf_record> drec;
+  if (deform) {  // the geometry the call reads: slots first_view .. first_view + n_views - 1, and first_view - 1 when resuming
+    const ptmi_ctx::GeometryStack& g = c->geometry;
+    if (!g.n_views) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no geometry stack: ptmi_capture_view_geometry makes it, view by view");
+    if (g.n_views != n_stack) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry stack has " + std::to_string(g.n_views) + " views, the view stack " + std::to_string(n_stack));
+    if (g.n_tris != c->n_tris_uploaded || g.n_xforms != c->h_xforms.size() / 32)
+      return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry stack holds " + std::to_string(g.n_tris) + " triangles and " + std::to_string(g.n_xforms) + " transforms, the scene now " +
+                                         std::to_string(c->n_tris_uploaded) + " and " + std::to_string(c->h_xforms.size() / 32));
+    for (uint32_t v = resume ? first_view - 1u : first_view; v < first_view + n_views; v++)
+      if (!g.captured[v]) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry of view " + std::to_string(v) + " was never captured: view " + std::to_string(v) + " is read by this call");
+    if (int r = make_deform_records(c, who, g.h_xforms.data(), (uint32_t)g.n_xforms, n_stack, resume ? first_view : first_view + 1u, first_view + n_views, &drec)) return r;
+  }
   if (motion) {
     std::vector<ptmm_record> rec;
     if (int r = make_motion_records(c, who, motions16, n_objects, n_stack, resume ? first_view : first_view + 1u, first_view + n_views, &rec)) return r;
     mo.n_objects = n_objects, mo.n_spheres = (uint32_t)(c->h_spheres.size() / 8), mo.n_quads = (uint32_t)(c->h_quads.size() / 20);
     mo.n_tris = (uint32_t)c->n_tris_uploaded, mo.n_meshes = (uint32_t)(c->h_meshes.size() / 4);
     const size_t rec_words = rec.size() * (sizeof(ptmm_record) / 4);
+    // (a *_deform call: then, on the next multiple of four words, its own records and the mesh table, four i32 per mesh, from the host copy too)
+    const size_t drec_at = (rec_words + mo.n_spheres + mo.n_quads + mo.n_meshes + 3) & ~(size_t)3, drec_words = drec.size() * (sizeof(ptmdf_record) / 4);
     try {
-      blob.resize(std::max<size_t>(1, rec_words + mo.n_spheres + mo.n_quads + mo.n_meshes));  // (one word at least: blob.data() tells make_stack_with_table that there is such a part)
+      blob.resize(std::max<size_t>(1, deform ? drec_at + drec_words + c->h_meshes.size() : rec_words + mo.n_spheres + mo.n_quads + mo.n_meshes));  // (one word at least: blob.data() tells make_stack_with_table that there is such a part)
     } catch (const std::bad_alloc&) {
       return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the motion table");
     }
@@ -709,8 +843,18 @@ static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_
     for (uint32_t i = 0; i < mo.n_spheres; i++) *ids++ = ptmm_f32_object(c->h_spheres[8 * (size_t)i + 4]);
     for (uint32_t i = 0; i < mo.n_quads; i++) *ids++ = ptmm_f32_object(c->h_quads[20 * (size_t)i + 11]);
     for (uint32_t i = 0; i < mo.n_meshes; i++) *ids++ = ptmm_i32_object(c->h_meshes[4 * (size_t)i + 2]);
+    if (deform) {
+      if (drec_words) memcpy(blob.data() + drec_at, drec.data(), drec_words * 4);
+      if (!c->h_meshes.empty()) memcpy(blob.data() + drec_at + drec_words, c->h_meshes.data(), c->h_meshes.size() * 4);
+    }
     if (int r = make_stack_with_table(c, who, STACK_ACCUMULATED, views16, frame_nums, blob.data(), blob.size() * 4)) return r;
     const uint8_t* extra = reinterpret_cast<const uint8_t*>(c->fuse_tab.dev.p) + fuse_tab_extra(n_stack, n_mat);
+    if (deform) {
+      dc.args.records = reinterpret_cast<const float4*>(extra + drec_at * 4);
+      dc.args.meshes = reinterpret_cast<const int32_t*>(extra + (drec_at + drec_words) * 4);
+      dc.args.tris_cur = c->geometry.tris.as<float4>(), dc.slot = c->geometry.n_tris * 6;
+      dc.args.n_tris = (uint32_t)c->geometry.n_tris, dc.args.n_meshes = mo.n_meshes, dc.args.n_transforms = (uint32_t)c->geometry.n_xforms;
+    }
     mo.records = reinterpret_cast<const float4*>(extra);
     mo.sphere_obj = reinterpret_cast<const int32_t*>(extra) + rec_words, mo.quad_obj = mo.sphere_obj + mo.n_spheres, mo.mesh_obj = mo.quad_obj + mo.n_quads;
     mo.tris = c->d_tris.as<float>();
@@ -719,7 +863,11 @@ static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_
   const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   return accumulate_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>(), c->stacks[STACK_MOMENTS].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(),
                             c->stacks[STACK_ACCUMULATED].buf.as<float4>(), c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, resume != 0, k,
-                            ptma_make_consts(P.max_history, P.min_frames), per_view ? fuse_tab_frames_ptr(c->fuse_tab.dev.p, n_stack, n_mat) : nullptr, motion ? &mo : nullptr);
+                            ptma_make_consts(P.max_history, P.min_frames), per_view ? fuse_tab_frames_ptr(c->fuse_tab.dev.p, n_stack, n_mat) : nullptr, motion ? &mo : nullptr, deform ? &dc : nullptr);
+}
+int ptmi_accumulate_views_deform(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects,
+                                 uint32_t first_view, uint32_t n_views, int resume) {
+  return accumulate_views(c, "ptmi_accumulate_views_deform", params, views16, 1.0f, frame_nums, true, first_view, n_views, resume, true, motions16, n_objects, true);
 }
 int ptmi_accumulate_views_motion(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects,
                                  uint32_t first_view, uint32_t n_views, int resume) {
@@ -741,11 +889,25 @@ int ptmi_accumulated_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* 
 }
 int ptmi_release_accumulated(ptmi_ctx* c) { return release_stack(c, STACK_ACCUMULATED); }
 
-// ptmi_accumulate_images (per_view false), ptmi_accumulate_images_frames (frame_nums: one per image) and ptmi_accumulate_images_motion (motion, with per_view)
+// What ptmi_accumulate_images_deform has beside ptmi_accumulate_images_motion's arguments
+struct DeformImages {
+  const float* triangles_seq;  // [n_images][n_triangles][24]
+  uint32_t n_triangles;
+  const float* transforms_seq;  // [n_images][n_transforms][32]
+  uint32_t n_transforms;
+  const int32_t* meshes;  // [n_meshes][4]
+  uint32_t n_meshes;
+};
+
+// ptmi_accumulate_images (per_view false), ptmi_accumulate_images_frames (frame_nums: one per image), ptmi_accumulate_images_motion (motion, with per_view) and
+// ptmi_accumulate_images_deform (deform, with per_view; motion may then be nullptr)
 static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
                              float frame_num, const float* frame_nums, bool per_view, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
-                             const ptmi_accumulate_params* params, const float* history_in, float* out, const MotionImages* motion = nullptr) {
+                             const ptmi_accumulate_params* params, const float* history_in, float* out, const MotionImages* motion = nullptr, const DeformImages* deform = nullptr) {
   if (!c || !colour_sums || !moments || !layers || !views16 || !out || (motion && !motion->object_ids)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (deform && (!deform->triangles_seq || (deform->n_transforms && !deform->transforms_seq) || (deform->n_meshes && !deform->meshes)))
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (deform && deform->n_triangles == 0) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": no triangles");
   ptmi_accumulate_params P;
   if (int r = accumulate_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
   if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
@@ -757,6 +919,9 @@ static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_s
   std::vector<ptmm_record> rec;  // (images 1 .. n_images - 1 have a predecessor, with or without history_in)
   if (motion)
     if (int r = make_motion_records(c, who, motion->motions16, motion->n_objects, n_images, 1, n_images, &rec)) return r;
+  std::vector<ptmdf_record> drec_h;  // (likewise)
+  if (deform)
+    if (int r = make_deform_records(c, who, deform->transforms_seq, deform->n_transforms, n_images, 1, n_images, &drec_h)) return r;
   if (!lambertian) n_materials = 0;
   const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials, per_view);
   std::vector<float> tab;
@@ -781,9 +946,26 @@ static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_s
     HIP_TRY(c, dids.ensure(npix * 4 * n_images));
     mo.records = drec.as<float4>(), mo.ids = dids.as<int32_t>(), mo.n_objects = motion->n_objects;
   }
+  DBuf dtris, ddrec, dmesh;  // (a *_deform call's geometry, records and meshes: its own too)
+  DeformCall dc{};
+  size_t tri_bytes = 0;
+  if (deform) {
+    tri_bytes = (size_t)n_images * deform->n_triangles * 96;
+    HIP_TRY(c, dtris.ensure(tri_bytes));
+    HIP_TRY(c, ddrec.ensure(std::max<size_t>(drec_h.size() * sizeof(ptmdf_record), 16)));
+    HIP_TRY(c, dmesh.ensure(std::max<size_t>((size_t)deform->n_meshes * 16, 16)));
+    dc.args.tris_cur = dtris.as<float4>(), dc.args.records = ddrec.as<float4>(), dc.args.meshes = dmesh.as<int32_t>();
+    dc.args.n_tris = deform->n_triangles, dc.args.n_meshes = deform->n_meshes, dc.args.n_transforms = deform->n_transforms;
+    dc.slot = (size_t)deform->n_triangles * 6;
+  }
   return on_host_images(c, who, colour_sums, layers, npix, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
     HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(mom.p, moments, bytes, hipMemcpyHostToDevice, c->stream));
+    if (deform) {
+      HIP_TRY(c, hipMemcpyAsync(dtris.p, deform->triangles_seq, tri_bytes, hipMemcpyHostToDevice, c->stream));
+      if (!drec_h.empty()) HIP_TRY(c, hipMemcpyAsync(ddrec.p, drec_h.data(), drec_h.size() * sizeof(ptmdf_record), hipMemcpyHostToDevice, c->stream));
+      if (deform->n_meshes) HIP_TRY(c, hipMemcpyAsync(dmesh.p, deform->meshes, (size_t)deform->n_meshes * 16, hipMemcpyHostToDevice, c->stream));
+    }
     if (motion) {
       if (!rec.empty()) HIP_TRY(c, hipMemcpyAsync(drec.p, rec.data(), rec.size() * sizeof(ptmm_record), hipMemcpyHostToDevice, c->stream));
       HIP_TRY(c, hipMemcpyAsync(dids.p, motion->object_ids, npix * 4 * n_images, hipMemcpyHostToDevice, c->stream));
@@ -795,7 +977,7 @@ static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_s
     }
     const uint32_t first = history_in ? 1u : 0u;
     return accumulate_enqueue(c, col, mom.as<float4>(), lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, first, n_images - first, history_in != nullptr, k, ka,
-                              per_view ? fuse_tab_frames_ptr(dtab.p, n_images, n_materials) : nullptr, motion ? &mo : nullptr);
+                              per_view ? fuse_tab_frames_ptr(dtab.p, n_images, n_materials) : nullptr, motion ? &mo : nullptr, deform ? &dc : nullptr);
   }, 3, 48);
 }
 int ptmi_accumulate_images(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
@@ -815,6 +997,16 @@ int ptmi_accumulate_images_motion(ptmi_ctx* c, const float* colour_sums, const f
   const MotionImages motion{motions16, n_objects, object_ids};
   return accumulate_images(c, "ptmi_accumulate_images_motion", colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params,
                            history_in, out, &motion);
+}
+int ptmi_accumulate_images_deform(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                  const float* frame_nums, const float* triangles_seq, uint32_t n_triangles, const float* transforms_seq, uint32_t n_transforms,
+                                  const int32_t* meshes, uint32_t n_meshes, const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees,
+                                  const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out) {
+  if (c && n_objects && !motions16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_accumulate_images_deform: null motions16 with n_objects > 0");
+  const MotionImages motion{motions16, n_objects, object_ids};  // (a null motions16 with n_objects = 0: a static world beside the triangles)
+  const DeformImages deform{triangles_seq, n_triangles, transforms_seq, n_transforms, meshes, n_meshes};
+  return accumulate_images(c, "ptmi_accumulate_images_deform", colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params,
+                           history_in, out, motions16 ? &motion : nullptr, &deform);
 }
 
 int ptmi_denoise_views_accumulated(ptmi_ctx* c, const ptmi_guided_params* params, uint32_t first_view, uint32_t n_views) {

@@ -35,6 +35,8 @@ export class MockBackend {
   fuseViewsFrames(views, frameNums, firstView, nViews, params = null) { this.calls.push(['fuseViewsFrames', views.length / 16, Array.from(frameNums), firstView, nViews, params]); }
   accumulateViewsFrames(views, frameNums, firstView, nViews, resume = false, params = null) { this.calls.push(['accumulateViewsFrames', views.length / 16, Array.from(frameNums), firstView, nViews, !!resume, params]); }
   accumulateViewsMotion(views, frameNums, motions, nObjects, firstView, nViews, resume = false, params = null) { this.calls.push(['accumulateViewsMotion', views.length / 16, Array.from(frameNums), motions.length / 16, nObjects, firstView, nViews, !!resume, params]); }
+  captureViewGeometry(view, nViews) { this.calls.push(['captureViewGeometry', view, nViews]); }
+  accumulateViewsDeform(views, frameNums, motions, nObjects, firstView, nViews, resume = false, params = null) { this.calls.push(['accumulateViewsDeform', views.length / 16, Array.from(frameNums), motions ? motions.length / 16 : null, nObjects, firstView, nViews, !!resume, params]); }
   fuseViewsMotion(views, frameNums, motions, nObjects, source, firstView, nViews, params = null) { this.calls.push(['fuseViewsMotion', views.length / 16, frameNums ? Array.from(frameNums) : null, motions.length / 16, nObjects, source, firstView, nViews, params]); }
   synchronize() {}
 }

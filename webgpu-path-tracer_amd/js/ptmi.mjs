@@ -96,6 +96,14 @@ export class Ptmi {
   accumulateViewsMotion(views, frameNums, motions, nObjects, firstView, nViews, resume = false, params = null) {
     this.native.accumulateViewsMotion(this.h, views, Float32Array.from(frameNums), motions, nObjects, firstView, nViews, resume, params);
   }
+  // ptmi_capture_view_geometry: the device triangles in the order they lie in now and the transform table as uploaded now, into slot `view` of the context's
+  // geometry stack of nViews slots — after refitSceneBVH and the view's render, before the next upload
+  captureViewGeometry(view, nViews) { this.native.captureViewGeometry(this.h, view, nViews); }
+  // ptmi_accumulate_views_deform: accumulateViewsMotion through the geometry stack — a triangle pixel is carried from its triangle in view v to the same triangle in
+  // view v - 1; motions (null with nObjects 0: a static world) serve every other pixel
+  accumulateViewsDeform(views, frameNums, motions, nObjects, firstView, nViews, resume = false, params = null) {
+    this.native.accumulateViewsDeform(this.h, views, Float32Array.from(frameNums), motions, nObjects, firstView, nViews, resume, params);
+  }
   // ptmi_fuse_views_motion: fuseViewsFrames through a world whose objects move — motions as accumulateViewsMotion takes them, composed across each output view's
   // window by the library; source 1 reads the denoised stack, frameNums may then be null
   fuseViewsMotion(views, frameNums, motions, nObjects, source, firstView, nViews, params = null) {

@@ -40,6 +40,8 @@ SYMBOLS = [
     "ptmi_refit_bvh", "ptmi_refit_scene_bvh",
     "ptmi_accumulate_views_motion", "ptmi_accumulate_images_motion", "ptmi_accumulate_reference_motion", "ptmi_object_ids_reference", "ptmi_motions_from_transforms",
     "ptmi_fuse_views_motion", "ptmi_fuse_images_motion", "ptmi_fuse_reference_motion", "ptmi_compose_motions",
+    "ptmi_accumulate_images_deform", "ptmi_accumulate_reference_deform", "ptmi_deform_records",
+    "ptmi_capture_view_geometry", "ptmi_read_view_geometry", "ptmi_geometry_device_ptr", "ptmi_release_geometry", "ptmi_accumulate_views_deform",
 ]
 
 MOTION_MAX_RECORDS = 1 << 20  # PTMI_MOTION_MAX_RECORDS
@@ -296,6 +298,17 @@ def load_library(build=False, path=None):
         L.ptmi_fuse_images_motion.argtypes = [vp, fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, ctypes.c_float, fp, u32, up, fp]
         L.ptmi_fuse_reference_motion.argtypes = [fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, ctypes.c_float, fp, u32, up, fp, fp]
         L.ptmi_compose_motions.argtypes = [fp, u32, u32, u32, u32, fp]
+    if hasattr(L, "ptmi_accumulate_images_deform"):  # (an older A/B build loaded through PTMI_LIB knows rigid motions alone)
+        ap = ctypes.POINTER(AccumulateParams)
+        L.ptmi_accumulate_images_deform.argtypes = [vp, fp, fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, u32, fp, u32, fp, u32, fp, ctypes.c_float, fp, u32, ap, fp, fp]
+        L.ptmi_accumulate_reference_deform.argtypes = [fp, fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, u32, fp, u32, fp, u32, fp, ctypes.c_float, fp, u32, ap, fp, fp, i32]
+        L.ptmi_deform_records.argtypes = [fp, fp, u32, fp, fp]
+        L.ptmi_capture_view_geometry.argtypes = [vp, u32, u32]
+        L.ptmi_read_view_geometry.argtypes = [vp, u32, fp, sz, fp, sz]
+        L.ptmi_geometry_device_ptr.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint32),
+                                               ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        L.ptmi_release_geometry.argtypes = [vp]
+        L.ptmi_accumulate_views_deform.argtypes = [vp, ap, fp, fp, fp, u32, u32, u32, i32]
     if explicit:
         _libs[path] = L
     else:
@@ -541,6 +554,48 @@ def accumulate_reference_motion(colour_sums, moments, layers, views, frame_nums,
                                                                   int(threads))
     if st != 0:
         raise PtmiError(st, "ptmi_accumulate_reference_motion failed")
+    return out
+
+
+def _deform_arrays(triangles_seq, transforms_seq, meshes, n):
+    """The geometry of the *_deform calls: triangles (n, n_triangles, 24) and transforms (n, n_transforms, 32) float32, meshes (n_meshes, 4) int32; an empty transform
+    or mesh table stays a null pointer.  Returns the argument run (triangles, n_triangles, transforms, n_transforms, meshes, n_meshes) and the arrays, to keep alive."""
+    tr = np.ascontiguousarray(triangles_seq, np.float32).reshape(n, -1, 24)
+    tf = None if transforms_seq is None or np.size(transforms_seq) == 0 else np.ascontiguousarray(transforms_seq, np.float32).reshape(n, -1, 32)
+    me = None if meshes is None or np.size(meshes) == 0 else np.ascontiguousarray(meshes, np.int32).reshape(-1, 4)
+    return [_ptr(tr), tr.shape[1], _optr(tf), 0 if tf is None else tf.shape[1], _optr(me), 0 if me is None else me.shape[0]], (tr, tf, me)
+
+
+def accumulate_reference_deform(colour_sums, moments, layers, views, frame_nums, triangles_seq, transforms_seq, meshes, motions=None, object_ids=None, fov_degrees=60.0,
+                                lambertian=None, params=None, history=None, threads=1, n_objects=None, lib=None):
+    """ptmi_accumulate_reference_deform: accumulate_reference_motion through a world whose meshes DEFORM — triangles_seq (n, n_triangles, 24): every image's triangles
+    in the order its layers were rendered in, the same order in all; transforms_seq (n, n_transforms, 32): every image's transform table; meshes (n_meshes, 4) int32.
+    A triangle pixel whose indices count is carried from its triangle in image v to the same triangle in image v-1; every other pixel goes through motions /
+    object_ids as accumulate_reference_motion's do (both None: a static world).  Image 0's geometry is read only as image 1's predecessor."""
+    c, m, l, v, t, hist, out = _accumulate_arrays(colour_sums, moments, layers, views, lambertian, history)
+    f = _frame_nums(frame_nums, c.shape[0])
+    g, n_obj, ids = _motion_arrays(motions, object_ids, c.shape[0], c.shape[1:3])
+    geo, keep = _deform_arrays(triangles_seq, transforms_seq, meshes, c.shape[0])
+    st = (lib or load_library()).ptmi_accumulate_reference_deform(_ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), *geo, _optr(g),
+                                                                  n_obj if n_objects is None else n_objects, _optr(ids), float(fov_degrees), _optr(t),
+                                                                  0 if t is None else t.size, None if params is None else ctypes.byref(params), _optr(hist), _ptr(out),
+                                                                  int(threads))
+    if st != 0:
+        raise PtmiError(st, "ptmi_accumulate_reference_deform failed")
+    return out
+
+
+def deform_records(prev, cur, lib=None):
+    """ptmi_deform_records: the records the *_deform calls make for one view, (n_transforms, 36) uint32 words (include/ptmi_deform.h, ptmdf_record), from the
+    transform tables (n_transforms, 32) of the earlier view (prev) and the later one (cur).  PtmiError naming the object where an element read is not finite."""
+    p = np.ascontiguousarray(prev, np.float32).reshape(-1, 32)
+    c = np.ascontiguousarray(cur, np.float32).reshape(-1, 32)
+    assert p.shape == c.shape, "prev and cur: the same number of transforms"
+    out = np.zeros((p.shape[0], 36), np.uint32)
+    bad = np.zeros(1, np.uint32)
+    st = (lib or load_library()).ptmi_deform_records(_ptr(p), _ptr(c), p.shape[0], _ptr(out), _ptr(bad))
+    if st != 0:
+        raise PtmiError(st, "ptmi_deform_records failed: object %d" % int(bad[0]))
     return out
 
 
@@ -1085,6 +1140,72 @@ class Context:
                                                         n_obj if n_objects is None else n_objects, _optr(ids), float(fov_degrees), _optr(t), 0 if t is None else t.size,
                                                         None if params is None else ctypes.byref(params), _optr(hist), _ptr(out)))
         return out
+
+    # ---- accumulation through deforming meshes (include/ptmi.h, "ACCUMULATION THROUGH DEFORMING MESHES") ----
+    def accumulate_images_deform(self, colour_sums, moments, layers, views, frame_nums, triangles_seq, transforms_seq, meshes, motions=None, object_ids=None,
+                                 fov_degrees=60.0, lambertian=None, params=None, history=None, n_objects=None):
+        """ptmi_accumulate_images_deform: k_accumulate_view_deform on host arrays of any size (see accumulate_reference_deform); synchronous."""
+        c, m, l, v, t, hist, out = _accumulate_arrays(colour_sums, moments, layers, views, lambertian, history)
+        f = _frame_nums(frame_nums, c.shape[0])
+        g, n_obj, ids = _motion_arrays(motions, object_ids, c.shape[0], c.shape[1:3])
+        geo, keep = _deform_arrays(triangles_seq, transforms_seq, meshes, c.shape[0])
+        self._ck(self.lib.ptmi_accumulate_images_deform(self.h, _ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), *geo, _optr(g),
+                                                        n_obj if n_objects is None else n_objects, _optr(ids), float(fov_degrees), _optr(t), 0 if t is None else t.size,
+                                                        None if params is None else ctypes.byref(params), _optr(hist), _ptr(out)))
+        return out
+
+    def capture_view_geometry(self, view, n_views):
+        """ptmi_capture_view_geometry: the device triangles in the order they lie in now and the transform table as uploaded now, into slot `view` of the context's
+        geometry stack of n_views slots.  Asynchronous."""
+        self._ck(self.lib.ptmi_capture_view_geometry(self.h, int(view), int(n_views)))
+
+    def geometry_device_ptr(self):
+        """ptmi_geometry_device_ptr: (triangles pointer, transforms pointer or None, n_views, n_triangles, n_transforms) of the geometry stack."""
+        t, x, n, nt, nx = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._ck(self.lib.ptmi_geometry_device_ptr(self.h, ctypes.byref(t), ctypes.byref(x), ctypes.byref(n), ctypes.byref(nt), ctypes.byref(nx)))
+        return t.value, x.value, n.value, nt.value, nx.value
+
+    def read_view_geometry(self, view):
+        """ptmi_read_view_geometry: slot `view` of the geometry stack as (triangles (n_triangles, 24), transforms (n_transforms, 32)) float32."""
+        _, _, _, nt, nx = self.geometry_device_ptr()
+        tr, tf = np.empty((nt, 24), np.float32), np.empty((nx, 32), np.float32)
+        self._ck(self.lib.ptmi_read_view_geometry(self.h, int(view), _ptr(tr), tr.nbytes, _ptr(tf), tf.nbytes))
+        return tr, tf
+
+    def release_geometry(self):
+        self._ck(self.lib.ptmi_release_geometry(self.h))
+
+    def accumulate_views_deform(self, views, frame_nums, motions=None, first_view=0, n_views=None, resume=False, params=None, n_objects=None):
+        """ptmi_accumulate_views_deform: accumulate_views_motion through the geometry stack (capture_view_geometry; render_deforming_path fills it) — a triangle pixel
+        is carried from its triangle in view v to the same triangle in view v-1; every other pixel goes through motions as accumulate_views_motion's do (None: a
+        static world).  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        n_stack = self.views_device_ptr()[2]
+        assert v.shape[0] == n_stack, "views: the matrices of all %d views of the stack" % n_stack
+        f = _frame_nums(frame_nums, n_stack)
+        g, n_obj, _ = _motion_arrays(motions, None, n_stack)
+        if n_views is None:
+            n_views = n_stack - first_view
+        self._ck(self.lib.ptmi_accumulate_views_deform(self.h, None if params is None else ctypes.byref(params), _ptr(v), _optr(f), _optr(g),
+                                                       n_obj if n_objects is None else n_objects, first_view, n_views, 1 if resume else 0))
+
+    def render_deforming_path(self, views, triangles_seq, transforms_seq, first_frames, frame_counts):
+        """A camera path through a scene whose meshes deform, a host loop over existing calls: for every view v it uploads triangles_seq[v] ((n_triangles, 24) float32
+        IN THE CALLER'S ORIGINAL ORDER, the one the tree was built over) and transforms_seq[v] ((n_objects, 32)), refits the scene's device-resident tree
+        (refit_scene_bvh), renders that view alone as render_moving_path does, and captures its geometry (capture_view_geometry).  The view moments must be on."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        tr = np.ascontiguousarray(triangles_seq, np.float32).reshape(v.shape[0], -1, 24)
+        t = np.ascontiguousarray(transforms_seq, np.float32).reshape(v.shape[0], -1, 32)
+        f, k = _frame_arrays(v.shape[0], first_frames, frame_counts)
+        for i in range(v.shape[0]):
+            self.upload("triangles", tr[i])
+            self.upload("transforms", t[i])
+            self.refit_scene_bvh()
+            only = np.where(np.arange(v.shape[0]) == i, k, 0).astype(np.uint32)
+            self.render_views_frames(v, f, only, reset=True)
+            self.moments_device_ptr()  # (PTMI_ERR_STATE while the view moments are off: say so after the first view, not after the last)
+            self.render_aov_frames(v, f, only, reset=True)
+            self.capture_view_geometry(i, v.shape[0])
 
     # ---- fusion through a world whose objects move (include/ptmi.h, "FUSION WITH PER-OBJECT MOTION") ----
     def fuse_views_motion(self, views, frame_nums, motions, source=0, first_view=0, n_views=None, params=None, n_objects=None):
