@@ -1,0 +1,125 @@
+// ptmi_call_table.h — the one small table that a fuse or accumulate call puts on the device (c->fuse_tab for the *_views forms, a buffer of the call's own for the
+// *_images forms), defined ONCE: which parts it has, where each lies, and how each is filled.  Host only, and no HIP type: standard headers and include/*.h, so that
+// g++ compiles it (tools/sanitize_call_table.cpp runs all of it under ASan and UBSan).  The kernels are handed pointers into the table, never offsets, so nothing on the
+// device knows this order.
+//
+// The parts, in the table's order, and what the layout guarantees of each:
+//   views       kFuseRow float4 per view of the stack (fuse_pack_row)                                          read as float4: starts on 16 bytes
+//   motion      the *_motion calls' records, ptmm_record (six float4) each, in the order the call's kernel reads them      read as float4: starts on 16 bytes
+//   deform      the *_deform call's records, ptmdf_record (nine float4) each                                   read as float4: starts on 16 bytes
+//   frames      the *_frames calls' divisors, one f32 per view of the stack                                    starts on 4 bytes
+//   sphere_obj, quad_obj, mesh_obj   one i32 object id per sphere, quad and mesh of the uploaded scene         start on 4 bytes
+//   meshes      the *_deform call's mesh table, i32 words (four per mesh)                                      starts on 4 bytes
+//   materials   one byte per material index, 1 = fuses: max(16, n_materials) bytes, zero-filled, so that it can be read with n_materials = 0
+// A part that a call does not have has length 0; its offset is still inside [0, total], though nothing is read there.  No part is padded: the three kinds of float4
+// part come first and each is a whole number of float4 long, the words follow, the bytes are last, so every start is aligned by what lies before it.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+
+#include "../../include/ptmi_deform.h"
+#include "../../include/ptmi_fuse.h"
+#include "../../include/ptmi_motion.h"
+
+namespace ptmi {
+
+constexpr int kFuseRow = 7;  // float4 per view of the table: the matrix's four columns, then (B row 0, o.x), (B row 1, o.y), (B row 2, o.z)
+
+// What decides the layout: counts alone
+struct CallTableCounts {
+  uint32_t n_views = 0;      // of the stack
+  uint32_t n_materials = 0;
+  bool frames = false;
+  size_t motion_records = 0;
+  uint32_t n_spheres = 0, n_quads = 0, n_meshes = 0;  // the id tables' entries
+  size_t deform_records = 0;
+  size_t mesh_words = 0;
+};
+
+struct CallTable {
+  struct Part {
+    size_t at = 0, bytes = 0;
+  };
+  Part views, motion, deform, frames, sphere_obj, quad_obj, mesh_obj, meshes, materials;
+  size_t total = 0;
+
+  CallTable() = default;
+  explicit CallTable(const CallTableCounts& n) {
+    static_assert(sizeof(ptmm_record) == 96 && sizeof(ptmdf_record) == 144, "records are whole float4");
+    auto put = [this](Part& p, size_t bytes) { p.at = total, p.bytes = bytes, total += bytes; };
+    put(views, (size_t)n.n_views * kFuseRow * 16);
+    put(motion, n.motion_records * sizeof(ptmm_record));
+    put(deform, n.deform_records * sizeof(ptmdf_record));
+    put(frames, n.frames ? (size_t)n.n_views * 4 : 0);
+    put(sphere_obj, (size_t)n.n_spheres * 4);
+    put(quad_obj, (size_t)n.n_quads * 4);
+    put(mesh_obj, (size_t)n.n_meshes * 4);
+    put(meshes, n.mesh_words * 4);
+    put(materials, std::max<size_t>(16, n.n_materials));
+  }
+  // Where part p lies in the copy of the table at `tab`, host or device
+  template <class T>
+  T* ptr(void* tab, const Part& p) const {
+    return reinterpret_cast<T*>(static_cast<uint8_t*>(tab) + p.at);
+  }
+  template <class T>
+  const T* ptr(const void* tab, const Part& p) const {
+    return reinterpret_cast<const T*>(static_cast<const uint8_t*>(tab) + p.at);
+  }
+};
+
+// The table row of view v packed for the device
+inline void fuse_pack_row(const ptmf_view& v, float* row) {
+  for (int k = 0; k < 16; k++) row[k] = v.m[k];
+  for (int i = 0; i < 3; i++) {
+    row[16 + 4 * i + 0] = v.B[3 * i + 0], row[16 + 4 * i + 1] = v.B[3 * i + 1], row[16 + 4 * i + 2] = v.B[3 * i + 2];
+    row[16 + 4 * i + 3] = v.o[i];
+  }
+}
+
+// ---- the fill functions: each writes one part of `tab`, a buffer of exactly L.total bytes ----
+// views from views16 [n_views][16].  Returns -1, or the number of the first view whose 3x3 has a zero or non-finite determinant (the table is then unfinished).
+inline int64_t call_table_fill_views(const CallTable& L, void* tab, const float* views16) {
+  const size_t n_views = L.views.bytes / ((size_t)kFuseRow * 16);
+  float* rows = L.ptr<float>(tab, L.views);
+  for (size_t v = 0; v < n_views; v++) {
+    ptmf_view row;
+    if (!ptmf_make_view(views16 + 16 * v, &row)) return (int64_t)v;
+    fuse_pack_row(row, rows + v * kFuseRow * 4);
+  }
+  return -1;
+}
+// materials from a caller's bytes (nullptr: all zero; the kernels are then told that there is no such table) ...
+inline void call_table_fill_materials(const CallTable& L, void* tab, const uint8_t* lambertian, uint32_t n_materials) {
+  uint8_t* bytes = L.ptr<uint8_t>(tab, L.materials);
+  memset(bytes, 0, L.materials.bytes);
+  if (lambertian && n_materials) memcpy(bytes, lambertian, n_materials);
+}
+// ... or from the uploaded materials, 16 f32 each, of which float 14 is the type
+inline void call_table_fill_scene_materials(const CallTable& L, void* tab, const float* mats16, uint32_t n_materials) {
+  uint8_t* bytes = L.ptr<uint8_t>(tab, L.materials);
+  memset(bytes, 0, L.materials.bytes);
+  for (uint32_t i = 0; i < n_materials; i++) bytes[i] = mats16[16 * (size_t)i + 14] == PTMF_LAMBERTIAN;
+}
+// frames from the caller's counts, one per view of the stack; nullptr: every view counts 1
+inline void call_table_fill_frames(const CallTable& L, void* tab, const float* frame_nums) {
+  float* f = L.ptr<float>(tab, L.frames);
+  if (frame_nums && L.frames.bytes) memcpy(f, frame_nums, L.frames.bytes);
+  else std::fill(f, f + L.frames.bytes / 4, 1.0f);
+}
+// The three id tables from the scene's host arrays as they are uploaded: spheres of 8 f32 (global_id: float 4), quads of 20 f32 (float 11), meshes of 4 i32 (word 2)
+inline void call_table_fill_object_ids(const CallTable& L, void* tab, const float* spheres, const float* quads, const int32_t* meshes4) {
+  int32_t *s = L.ptr<int32_t>(tab, L.sphere_obj), *q = L.ptr<int32_t>(tab, L.quad_obj), *m = L.ptr<int32_t>(tab, L.mesh_obj);
+  for (size_t i = 0; i < L.sphere_obj.bytes / 4; i++) s[i] = ptmm_f32_object(spheres[8 * i + 4]);
+  for (size_t i = 0; i < L.quad_obj.bytes / 4; i++) q[i] = ptmm_f32_object(quads[20 * i + 11]);
+  for (size_t i = 0; i < L.mesh_obj.bytes / 4; i++) m[i] = ptmm_i32_object(meshes4[4 * i + 2]);
+}
+// meshes: a plain copy of L.meshes.bytes
+inline void call_table_fill_meshes(const CallTable& L, void* tab, const int32_t* mesh_words) {
+  if (L.meshes.bytes) memcpy(L.ptr<int32_t>(tab, L.meshes), mesh_words, L.meshes.bytes);
+}
+// (the records are made straight into their parts, L.ptr<ptmm_record>(tab, L.motion) and L.ptr<ptmdf_record>(tab, L.deform), by the calls' own makers)
+
+}  // namespace ptmi

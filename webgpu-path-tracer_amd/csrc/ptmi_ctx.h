@@ -140,7 +140,7 @@ struct ptmi_ctx {
   Stack stacks[N_STACKS];
   DBuf d_denoise_scratch;  // ptmi_denoise_views: three packed float4 images (d ping, d pong, n + z) per view of a batch (atrous_batch_views); ptmi_denoise_views_guided: and three f32 images (v ping, v pong, vg)
   StagedTable view_rows;   // the last ptmi_render_views / ptmi_render_aov call's view table (ViewTab: kViewRow float4 per view)
-  StagedTable fuse_tab;    // the last ptmi_fuse_views / ptmi_accumulate_views call's table (kFuseRow float4 per view of the stack, then one byte per material; the *_frames calls: then one f32 per view, its frame count)
+  StagedTable fuse_tab;    // the last ptmi_fuse_views / ptmi_accumulate_views call's table (its parts and their order: ptmi_call_table.h)
   StagedTable denoise_tab; // the last ptmi_denoise_views_frames / ptmi_denoise_views_guided_frames call's frame counts: one f32 per view of the stack
   // The GEOMETRY STACK (ptmi_capture_view_geometry): per view of a path the triangles and the transform table as they were when the view was rendered.  It holds no
   // image: ptmi_resize leaves it alone.  Keyed by (n_views, n_tris, n_xforms); the transforms also on the host, where a call's records are made from them.

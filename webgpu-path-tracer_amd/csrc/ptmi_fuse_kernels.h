@@ -20,21 +20,11 @@
 #pragma once
 
 #include "../../include/ptmi_fuse.h"
+#include "ptmi_call_table.h"  // kFuseRow and fuse_pack_row: a view's row of the table, host side
 #include "ptmi_denoise_kernels.h"
 #include "ptmi_motion_kernels.h"
 
 namespace ptmi {
-
-constexpr int kFuseRow = 7;  // float4 per view of the table: the matrix's four columns, then (B row 0, o.x), (B row 1, o.y), (B row 2, o.z)
-
-// The table row of view v packed for the device (host side of the layout above)
-inline void fuse_pack_row(const ptmf_view& v, float* row) {
-  for (int k = 0; k < 16; k++) row[k] = v.m[k];
-  for (int i = 0; i < 3; i++) {
-    row[16 + 4 * i + 0] = v.B[3 * i + 0], row[16 + 4 * i + 1] = v.B[3 * i + 1], row[16 + 4 * i + 2] = v.B[3 * i + 2];
-    row[16 + 4 * i + 3] = v.o[i];
-  }
-}
 
 // what the neighbour loop needs of view u (wave-uniform u: scalar loads)
 DEV void fuse_load_neighbour(const float4* __restrict__ tab, uint32_t u, ptmf_view& U) {

@@ -131,8 +131,21 @@ static int check_view_range(ptmi_ctx* c, const char* who, uint32_t first_view, u
   return PTMI_OK;
 }
 
-// The *_frames calls: entries [lo, hi) of frame_nums are the ones the call reads, and each has to be a divisor — finite and > 0; the others may hold anything.
-static int check_frame_nums(ptmi_ctx* c, const char* who, const float* frame_nums, uint32_t lo, uint32_t hi) {
+// The divisor of a call's colour sums: one frame_num for every view, or (each: the *_frames, *_motion and *_deform entries) the views' own, frame_nums, one f32 per view
+// of the stack or per image.  frame_num is then 1: what frame_num's check passes and no kernel reads.
+struct FrameDivisor {
+  float frame_num;
+  const float* frame_nums;
+  bool each;
+  static FrameDivisor of(float frame_num) { return {frame_num, nullptr, false}; }
+  static FrameDivisor per_view(const float* frame_nums) { return {1.0f, frame_nums, true}; }
+};
+
+// A per-view divisor: entries [lo, hi) of frame_nums are the ones the call reads, and each has to be a divisor — finite and > 0; the others may hold anything.  (With
+// lo = hi = 0 the null pointer alone is refused: what a call asks before it knows its range.)
+static int check_frame_nums(ptmi_ctx* c, const char* who, const FrameDivisor& F, uint32_t lo, uint32_t hi) {
+  if (!F.each) return PTMI_OK;
+  const float* frame_nums = F.frame_nums;
   if (!frame_nums) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null frame_nums");
   for (uint32_t v = lo; v < hi; v++)
     if (!(frame_nums[v] > 0.0f) || !ptmd_finite(frame_nums[v]))
@@ -167,9 +180,9 @@ static int check_source_stacks(ptmi_ctx* c, const char* who, bool need_denoised,
 // Either filter from the context's stacks into its denoised stack, the arguments checked.  The stack and the scratch, everything that can fail for want of memory, come
 // before anything is enqueued.  G: as atrous_enqueue's, its `moments` (or, with `accumulated`, its `given`) filled in here.  accumulated: the colour is plane 0 of the
 // accumulated stack, not the view stack.
-// frame_nums: nullptr, or the stack's frame counts, one per view (checked): they go up through c->denoise_tab, and frame_num is not read.
-static int atrous_views(ptmi_ctx* c, const ptmi_denoise_params& P, AtrousGuide* G, float frame_num, uint32_t first_view, uint32_t n_views, bool accumulated = false,
-                        const float* frame_nums = nullptr) {
+// F (checked): the views' own frame counts go up through c->denoise_tab.
+static int atrous_views(ptmi_ctx* c, const ptmi_denoise_params& P, AtrousGuide* G, const FrameDivisor& F, uint32_t first_view, uint32_t n_views, bool accumulated = false) {
+  const float* frame_nums = F.frame_nums;
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
   const size_t npix = (size_t)c->W * (size_t)c->H;
@@ -188,26 +201,25 @@ static int atrous_views(ptmi_ctx* c, const ptmi_denoise_params& P, AtrousGuide* 
   if (G && accumulated) G->given = c->stacks[STACK_ACCUMULATED].buf.as<float4>() + ((size_t)2 * n_stack + first_view) * npix;
   else if (G) G->moments = c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix;
   return atrous_enqueue(c, c->stacks[source].buf.as<float4>() + (size_t)first_view * npix, c->stacks[STACK_FEATURES].buf.as<float4>() + (size_t)first_view * 3 * npix,
-                        c->stacks[STACK_DENOISED].buf.as<float4>() + (size_t)first_view * npix, n_views, c->W, c->H, frame_num, P, G,
+                        c->stacks[STACK_DENOISED].buf.as<float4>() + (size_t)first_view * npix, n_views, c->W, c->H, F.frame_num, P, G,
                         frame_nums ? c->denoise_tab.dev.as<float>() + first_view : nullptr);
 }
 
-// ptmi_denoise_views (per_view false: frame_num) and ptmi_denoise_views_frames (per_view: frame_nums, one per view of the stack)
-static int denoise_views(ptmi_ctx* c, const char* who, const ptmi_denoise_params* params, float frame_num, const float* frame_nums, bool per_view, uint32_t first_view, uint32_t n_views) {
+// ptmi_denoise_views and ptmi_denoise_views_frames
+static int denoise_views(ptmi_ctx* c, const char* who, const ptmi_denoise_params* params, const FrameDivisor& F, uint32_t first_view, uint32_t n_views) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   ptmi_denoise_params P;
-  if (int r = denoise_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = denoise_check_args(c, who, params, F.frame_num, &P)) return r;
+  if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
   if (int r = check_source_stacks(c, who, false, first_view, n_views)) return r;
-  if (per_view)
-    if (int r = check_frame_nums(c, who, frame_nums, first_view, first_view + n_views)) return r;
-  return atrous_views(c, P, nullptr, frame_num, first_view, n_views, false, per_view ? frame_nums : nullptr);
+  if (int r = check_frame_nums(c, who, F, first_view, first_view + n_views)) return r;
+  return atrous_views(c, P, nullptr, F, first_view, n_views);
 }
 int ptmi_denoise_views(ptmi_ctx* c, const ptmi_denoise_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
-  return denoise_views(c, "ptmi_denoise_views", params, frame_num, nullptr, false, first_view, n_views);
+  return denoise_views(c, "ptmi_denoise_views", params, FrameDivisor::of(frame_num), first_view, n_views);
 }
 int ptmi_denoise_views_frames(ptmi_ctx* c, const ptmi_denoise_params* params, const float* frame_nums, uint32_t first_view, uint32_t n_views) {
-  return denoise_views(c, "ptmi_denoise_views_frames", params, 1.0f, frame_nums, true, first_view, n_views);
+  return denoise_views(c, "ptmi_denoise_views_frames", params, FrameDivisor::per_view(frame_nums), first_view, n_views);
 }
 
 int ptmi_read_denoised(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_DENOISED, "ptmi_read_denoised", view, 0, dst, bytes); }
@@ -245,36 +257,35 @@ static int on_host_images(ptmi_ctx* c, const char* who, const float* colour, con
   return r;
 }
 
-// ptmi_denoise_images (per_view false) and ptmi_denoise_images_frames (frame_nums: one per image)
-static int denoise_images(ptmi_ctx* c, const char* who, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const float* frame_nums,
-                          bool per_view, const ptmi_denoise_params* params, float* out) {
+// ptmi_denoise_images and ptmi_denoise_images_frames (F's frame_nums: one per image)
+static int denoise_images(ptmi_ctx* c, const char* who, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const FrameDivisor& F,
+                          const ptmi_denoise_params* params, float* out) {
   if (!c || !colour_sums || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_denoise_params P;
-  if (int r = denoise_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = denoise_check_args(c, who, params, F.frame_num, &P)) return r;
+  if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
   if (int r = check_image_size(c, who, w, h, n_images)) return r;
-  if (per_view)
-    if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
+  if (int r = check_frame_nums(c, who, F, 0, n_images)) return r;
   const size_t npix = (size_t)w * (size_t)h;
   DBuf dfr;  // (the frame counts: this call's own, had before anything is enqueued)
-  if (per_view) {
+  if (F.each) {
     HIP_TRY(c, hipSetDevice(c->device));
     (void)hipGetLastError();
     HIP_TRY(c, dfr.ensure((size_t)n_images * 4));
   }
   return on_host_images(c, who, colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kDenoiseScratchBytes),
                         [&](const float4* col, const float4* lay, float4* res) -> int {
-                          if (per_view)
-                            if (int e = send_frame_nums(c, dfr, frame_nums, n_images)) return e;
-                          return atrous_enqueue(c, col, lay, res, n_images, w, h, frame_num, P, nullptr, dfr.as<float>());
+                          if (F.each)
+                            if (int e = send_frame_nums(c, dfr, F.frame_nums, n_images)) return e;
+                          return atrous_enqueue(c, col, lay, res, n_images, w, h, F.frame_num, P, nullptr, dfr.as<float>());
                         });
 }
 int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params, float* out) {
-  return denoise_images(c, "ptmi_denoise_images", colour_sums, layers, w, h, n_images, frame_num, nullptr, false, params, out);
+  return denoise_images(c, "ptmi_denoise_images", colour_sums, layers, w, h, n_images, FrameDivisor::of(frame_num), params, out);
 }
 int ptmi_denoise_images_frames(ptmi_ctx* c, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const float* frame_nums,
                                const ptmi_denoise_params* params, float* out) {
-  return denoise_images(c, "ptmi_denoise_images_frames", colour_sums, layers, w, h, n_images, 1.0f, frame_nums, true, params, out);
+  return denoise_images(c, "ptmi_denoise_images_frames", colour_sums, layers, w, h, n_images, FrameDivisor::per_view(frame_nums), params, out);
 }
 
 // The guided filter's params as the launch plan takes them: the levels' part, with no colour term (P), and the rest (G, whose arrays the caller fills in)
@@ -289,118 +300,165 @@ static int guided_check_args(ptmi_ctx* c, const char* who, const ptmi_guided_par
                           ok ? nullptr : "levels in 1..6, sigma_normal, sigma_depth and albedo_floor > 0, sigma_luma >= 0, min_frames >= 2, var_eps a normal f32 > 0, all finite", true, frame_num);
 }
 
-// ptmi_denoise_views_guided (per_view false: frame_num) and ptmi_denoise_views_guided_frames (per_view: frame_nums, one per view of the stack)
-static int denoise_views_guided(ptmi_ctx* c, const char* who, const ptmi_guided_params* params, float frame_num, const float* frame_nums, bool per_view, uint32_t first_view,
-                                uint32_t n_views) {
+// ptmi_denoise_views_guided and ptmi_denoise_views_guided_frames
+static int denoise_views_guided(ptmi_ctx* c, const char* who, const ptmi_guided_params* params, const FrameDivisor& F, uint32_t first_view, uint32_t n_views) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   ptmi_denoise_params P;
   AtrousGuide G;
-  if (int r = guided_check_args(c, who, params, per_view ? 1.0f : frame_num, &P, &G)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = guided_check_args(c, who, params, F.frame_num, &P, &G)) return r;
+  if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
   if (int r = check_stack(c, STACK_MOMENTS, who, 0)) return r;  // (the moment stack first, then what ptmi_denoise_views asks: the order decides which error a caller sees)
   if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
   if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
     return fail(c, PTMI_ERR_STATE, std::string(who) + ": the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
   if (int r = check_source_stacks(c, who, false, first_view, n_views)) return r;
-  if (per_view)
-    if (int r = check_frame_nums(c, who, frame_nums, first_view, first_view + n_views)) return r;
-  return atrous_views(c, P, &G, frame_num, first_view, n_views, false, per_view ? frame_nums : nullptr);
+  if (int r = check_frame_nums(c, who, F, first_view, first_view + n_views)) return r;
+  return atrous_views(c, P, &G, F, first_view, n_views);
 }
 int ptmi_denoise_views_guided(ptmi_ctx* c, const ptmi_guided_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
-  return denoise_views_guided(c, "ptmi_denoise_views_guided", params, frame_num, nullptr, false, first_view, n_views);
+  return denoise_views_guided(c, "ptmi_denoise_views_guided", params, FrameDivisor::of(frame_num), first_view, n_views);
 }
 int ptmi_denoise_views_guided_frames(ptmi_ctx* c, const ptmi_guided_params* params, const float* frame_nums, uint32_t first_view, uint32_t n_views) {
-  return denoise_views_guided(c, "ptmi_denoise_views_guided_frames", params, 1.0f, frame_nums, true, first_view, n_views);
+  return denoise_views_guided(c, "ptmi_denoise_views_guided_frames", params, FrameDivisor::per_view(frame_nums), first_view, n_views);
 }
 
-// ptmi_denoise_images_guided (per_view false) and ptmi_denoise_images_guided_frames (frame_nums: one per image)
-static int denoise_images_guided(ptmi_ctx* c, const char* who, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
-                                 const float* frame_nums, bool per_view, const ptmi_guided_params* params, float* out, float* var_out) {
+// ptmi_denoise_images_guided and ptmi_denoise_images_guided_frames (F's frame_nums: one per image)
+static int denoise_images_guided(ptmi_ctx* c, const char* who, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images,
+                                 const FrameDivisor& F, const ptmi_guided_params* params, float* out, float* var_out) {
   if (!c || !colour_sums || !moments || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_denoise_params P;
   AtrousGuide G;
-  if (int r = guided_check_args(c, who, params, per_view ? 1.0f : frame_num, &P, &G)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = guided_check_args(c, who, params, F.frame_num, &P, &G)) return r;
+  if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
   if (int r = check_image_size(c, who, w, h, n_images)) return r;
-  if (per_view)
-    if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
+  if (int r = check_frame_nums(c, who, F, 0, n_images)) return r;
   const size_t npix = (size_t)w * (size_t)h, bytes = npix * 16 * n_images, var_bytes = var_out ? npix * 4 * n_images : 0;
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
   DBuf mom, var, dfr;  // (on_host_images brings the colour, the layers and the output; these are this call's own, had before anything is enqueued)
   HIP_TRY(c, mom.ensure(bytes));
   HIP_TRY(c, var.ensure(var_bytes));
-  if (per_view) HIP_TRY(c, dfr.ensure((size_t)n_images * 4));
+  if (F.each) HIP_TRY(c, dfr.ensure((size_t)n_images * 4));
   G.moments = mom.as<float4>(), G.var_out = var.as<float>();
   return on_host_images(c, who, colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kGuidedScratchBytes),
                         [&](const float4* col, const float4* lay, float4* res) -> int {
                           HIP_TRY(c, hipMemcpyAsync(mom.p, moments, bytes, hipMemcpyHostToDevice, c->stream));
-                          if (per_view)
-                            if (int e = send_frame_nums(c, dfr, frame_nums, n_images)) return e;
-                          if (int e = atrous_enqueue(c, col, lay, res, n_images, w, h, frame_num, P, &G, dfr.as<float>())) return e;
+                          if (F.each)
+                            if (int e = send_frame_nums(c, dfr, F.frame_nums, n_images)) return e;
+                          if (int e = atrous_enqueue(c, col, lay, res, n_images, w, h, F.frame_num, P, &G, dfr.as<float>())) return e;
                           if (var_out) HIP_TRY(c, hipMemcpyAsync(var_out, var.p, var_bytes, hipMemcpyDeviceToHost, c->stream));
                           return PTMI_OK;
                         });
 }
 int ptmi_denoise_images_guided(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
                                const ptmi_guided_params* params, float* out, float* var_out) {
-  return denoise_images_guided(c, "ptmi_denoise_images_guided", colour_sums, moments, layers, w, h, n_images, frame_num, nullptr, false, params, out, var_out);
+  return denoise_images_guided(c, "ptmi_denoise_images_guided", colour_sums, moments, layers, w, h, n_images, FrameDivisor::of(frame_num), params, out, var_out);
 }
 int ptmi_denoise_images_guided_frames(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, const float* frame_nums,
                                       const ptmi_guided_params* params, float* out, float* var_out) {
-  return denoise_images_guided(c, "ptmi_denoise_images_guided_frames", colour_sums, moments, layers, w, h, n_images, 1.0f, frame_nums, true, params, out, var_out);
+  return denoise_images_guided(c, "ptmi_denoise_images_guided_frames", colour_sums, moments, layers, w, h, n_images, FrameDivisor::per_view(frame_nums), params, out, var_out);
 }
 
 // ---- the fused stack (ptmi_fuse_views, ptmi_fuse_images) ----
 // (ptmi_default_fuse_params and ptmi_fuse_reference need no GPU: ptmi_host.cpp)
-// The call's table as the kernel reads it: kFuseRow float4 per view of the stack, then one byte per material index, padded to a multiple of 16; the *_frames calls put
-// the views' frame counts, one f32 per view of the stack, behind those bytes (fuse_tab_frames: where).
-static size_t fuse_tab_frames(uint32_t n_stack, uint32_t n_materials) { return (size_t)n_stack * kFuseRow * 16 + ((std::max<size_t>(16, n_materials) + 15) & ~(size_t)15); }
-static size_t fuse_tab_bytes(uint32_t n_stack, uint32_t n_materials, bool frames = false) {
-  return frames ? fuse_tab_frames(n_stack, n_materials) + (size_t)n_stack * 4 : (size_t)n_stack * kFuseRow * 16 + std::max<size_t>(16, n_materials);
-}
-static const float* fuse_tab_frames_ptr(const void* tab, uint32_t n_stack, uint32_t n_materials) {
-  return reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(tab) + fuse_tab_frames(n_stack, n_materials));
-}
-// ... and the *_motion calls their records and id tables behind the frame counts, on the next multiple of 16 (motion_args: the layout)
-static size_t fuse_tab_extra(uint32_t n_stack, uint32_t n_materials) { return (fuse_tab_bytes(n_stack, n_materials, true) + 15) & ~(size_t)15; }
+// What fusion and accumulation share, in all four forms of a call (fuse_views, fuse_images, accumulate_views, accumulate_images).  THE ORDER of every one of them: every
+// argument refusal comes before any device allocation, and everything that can fail for want of memory comes before anything is enqueued.  Each checks its arguments,
+// computes the layout of its table from counts (ptmi_call_table.h: the one place that knows the table), builds the table in one host buffer — the records made
+// straight into their parts — puts it on the device in one copy, and turns the layout into the kernels' pointers (table_ptrs, table_args).
 
-// Fills `tab` (fuse_tab_bytes) from the matrices of all views and the material-type bytes; PTMI_ERR_INVALID_ARG for a matrix that cannot be inverted.
-static int fuse_fill_tab(ptmi_ctx* c, const char* who, const float* views16, uint32_t n_stack, const uint8_t* lamb, uint32_t n_materials, float* tab) {
-  for (uint32_t v = 0; v < n_stack; v++) {
-    ptmf_view row;
-    if (!ptmf_make_view(views16 + 16 * (size_t)v, &row))
-      return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the 3x3 of view matrix " + std::to_string(v) + " has a zero or non-finite determinant");
-    fuse_pack_row(row, tab + (size_t)v * kFuseRow * 4);
+// The parts that a *_motion or *_deform entry has beside its siblings' arguments; a call takes each as a pointer, null where it has none.
+struct MotionPart {
+  const float* motions16;  // [n_views of the stack, or n_images][n_objects][16]
+  uint32_t n_objects;
+  const int32_t* object_ids;  // the *_images forms: [n_images][h][w] i32; the *_views forms: nullptr, the object comes from the feature stack and the uploaded scene
+};
+struct DeformPart {  // (the *_images form's arrays; ptmi_accumulate_views_deform reads none of them: its geometry is the context's geometry stack)
+  const float* triangles_seq = nullptr;  // [n_images][n_triangles][24]
+  uint32_t n_triangles = 0;
+  const float* transforms_seq = nullptr;  // [n_images][n_transforms][32]
+  uint32_t n_transforms = 0;
+  const int32_t* meshes = nullptr;  // [n_meshes][4]
+  uint32_t n_meshes = 0;
+};
+
+// The counts of a *_views call's table: all views of the stack and the uploaded materials, and, with_ids, an object id per sphere, quad and mesh of the scene as it
+// is uploaded now — from the host copies, so that no device buffer a render has yet to refresh is read.
+static CallTableCounts scene_table_counts(const ptmi_ctx* c, bool with_ids) {
+  CallTableCounts n;
+  n.n_views = c->stacks[STACK_VIEWS].n, n.n_materials = (uint32_t)(c->h_mats.size() / 16);
+  if (with_ids) n.n_spheres = (uint32_t)(c->h_spheres.size() / 8), n.n_quads = (uint32_t)(c->h_quads.size() / 20), n.n_meshes = (uint32_t)(c->h_meshes.size() / 4);
+  return n;
+}
+// ... and those parts, and the mesh table where the layout has one, filled from the same host copies
+static void fill_scene_parts(const ptmi_ctx* c, const CallTable& L, void* tab) {
+  call_table_fill_scene_materials(L, tab, c->h_mats.data(), (uint32_t)(c->h_mats.size() / 16));
+  call_table_fill_object_ids(L, tab, c->h_spheres.data(), c->h_quads.data(), c->h_meshes.data());
+  call_table_fill_meshes(L, tab, c->h_meshes.data());
+}
+
+// The host buffer of a call's table, L.total bytes
+static int alloc_table(ptmi_ctx* c, const char* who, const CallTable& L, std::vector<uint8_t>* tab) {
+  try {
+    tab->resize(L.total);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the view table");
   }
-  uint8_t* bytes = reinterpret_cast<uint8_t*>(tab + (size_t)n_stack * kFuseRow * 4);
-  memset(bytes, 0, std::max<size_t>(16, n_materials));
-  if (lamb) memcpy(bytes, lamb, n_materials);
+  return PTMI_OK;
+}
+// The rows of all views and the frame counts (frame_nums = nullptr with such a part: ones); PTMI_ERR_INVALID_ARG for a matrix that cannot be inverted.
+static int fill_views_and_frames(ptmi_ctx* c, const char* who, const CallTable& L, void* tab, const float* views16, const float* frame_nums) {
+  const int64_t bad = call_table_fill_views(L, tab, views16);
+  if (bad >= 0) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the 3x3 of view matrix " + std::to_string(bad) + " has a zero or non-finite determinant");
+  call_table_fill_frames(L, tab, frame_nums);
   return PTMI_OK;
 }
 
+// What every kernel takes of the table whose device copy is at `dev`: the rows, the material bytes (has_lamb false: nullptr, every material fuses) and the views' own
+// divisors (nullptr: the call has none, and the kernels read k.F)
+struct TablePtrs {
+  const float4* rows;
+  const uint8_t* lamb;
+  const float* frames;
+};
+static TablePtrs table_ptrs(const CallTable& L, const void* dev, bool has_lamb) {
+  return {L.ptr<float4>(dev, L.views), has_lamb ? L.ptr<uint8_t>(dev, L.materials) : nullptr, L.frames.bytes ? L.ptr<float>(dev, L.frames) : nullptr};
+}
+// ... and what the *_motion and *_deform kernels take of it beside (n: the counts L was made from).  A part of length 0 gives a pointer that is not read.
+static void table_args(const CallTable& L, const CallTableCounts& n, const void* dev, MotionArgs* mo, DeformArgs* de) {
+  mo->records = L.ptr<float4>(dev, L.motion);
+  mo->sphere_obj = L.ptr<int32_t>(dev, L.sphere_obj), mo->quad_obj = L.ptr<int32_t>(dev, L.quad_obj), mo->mesh_obj = L.ptr<int32_t>(dev, L.mesh_obj);
+  mo->n_spheres = n.n_spheres, mo->n_quads = n.n_quads, mo->n_meshes = n.n_meshes;
+  de->records = L.ptr<float4>(dev, L.deform), de->meshes = L.ptr<int32_t>(dev, L.meshes);
+  de->n_meshes = (uint32_t)(n.mesh_words / 4);
+}
+
+// fovFactor of the context's own camera, as make_render_const folds it
+static float context_fov_factor(const ptmi_ctx* c) { return ptmf_fov_factor(c->prm.fov_degrees); }
+
+// An accumulation's records lie view after view from the first view of the call that has a predecessor: `first` itself when the call resumes, first + 1 otherwise.
+static uint32_t first_view_with_history(uint32_t first, bool resume) { return resume ? first : first + 1u; }
+
 // The kernel on device arrays: colour [n_stack][H][W] float4, layers [n_stack][3][H][W] float4, out [n_stack][H][W] float4, of which views [first, first + n) are
-// written; `tab` as fuse_fill_tab made it, `has_lamb`: whether its material bytes are to be used.  One launch; more only where n exceeds the grid's z limit.
-// frames: nullptr, or the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_fuse_frames.
-// motion (with frames): nullptr, or k_fuse_motion's operands, records = the composed records of view `first` (fuse_motion_table: the layout).
-static int fuse_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, const void* tab, bool has_lamb, uint32_t n_materials, int W, int H,
-                        uint32_t n_stack, uint32_t first, uint32_t n, const ptmf_consts& k, const float* frames = nullptr, const MotionArgs* motion = nullptr) {
+// written; t: the table's parts (table_ptrs).  One launch; more only where n exceeds the grid's z limit.
+// t.frames: the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_fuse_frames.
+// motion (with t.frames): nullptr, or k_fuse_motion's operands, records = the composed records of view `first` (fuse_motion_table: their order).
+static int fuse_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, const TablePtrs& t, uint32_t n_materials, int W, int H, uint32_t n_stack,
+                        uint32_t first, uint32_t n, const ptmf_consts& k, const MotionArgs* motion = nullptr) {
   const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
   const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
-  const uint8_t* lamb = has_lamb ? reinterpret_cast<const uint8_t*>(tab) + (size_t)n_stack * kFuseRow * 16 : nullptr;
   for (uint32_t v0 = 0; v0 < n; v0 += 65535u) {
     const uint32_t nv = std::min(65535u, n - v0);
+    const dim3 grid(gx, 1, nv);
+    auto shared = [&](auto launch) { launch(colour, layers, out, t.rows, t.lamb, n_materials, W, H, n_stack, first + v0, k); };  // what every entry takes: its own operands follow
     if (motion) {
       MotionArgs mo = *motion;
       mo.records += (size_t)v0 * (2u * (uint32_t)k.radius + 1u) * mo.n_objects * 6;
-      hipLaunchKernelGGL(k_fuse_motion, dim3(gx, 1, nv), dim3(kBlock), 0, c->stream, colour, layers, out, reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, n_stack,
-                         first + v0, k, frames, mo);
-    } else if (frames)
-      hipLaunchKernelGGL(k_fuse_frames, dim3(gx, 1, nv), dim3(kBlock), 0, c->stream, colour, layers, out, reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, n_stack,
-                         first + v0, k, frames);
-    else
-      hipLaunchKernelGGL(k_fuse, dim3(gx, 1, nv), dim3(kBlock), 0, c->stream, colour, layers, out, reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, n_stack,
-                         first + v0, k);
+      shared([&](auto... a) { hipLaunchKernelGGL(k_fuse_motion, grid, dim3(kBlock), 0, c->stream, a..., t.frames, mo); });
+    } else if (t.frames) {
+      shared([&](auto... a) { hipLaunchKernelGGL(k_fuse_frames, grid, dim3(kBlock), 0, c->stream, a..., t.frames); });
+    } else {
+      shared([&](auto... a) { hipLaunchKernelGGL(k_fuse, grid, dim3(kBlock), 0, c->stream, a...); });
+    }
     HIP_TRY(c, hipGetLastError());
   }
   return PTMI_OK;
@@ -413,125 +471,90 @@ static int fuse_check_args(ptmi_ctx* c, const char* who, const ptmi_fuse_params*
   return check_stack_call(c, who, "a view's pixels", "several", ok ? nullptr : "radius in 1..8, sigma_normal, sigma_depth and albedo_floor > 0, all finite", need_frames, frame_num);
 }
 
-// What ptmi_fuse_views and ptmi_accumulate_views do before they enqueue a kernel: the table of all views of the stack with the uploaded materials' types, the call's
-// stack `k` (of the view stack's size) and the table's two copies — everything that can fail for want of memory, before anything is enqueued — and then the
-// table's upload.  frame_nums: nullptr, or the stack's frame counts (checked), which go behind the table's material bytes.
-// extra: nullptr, or extra_bytes that a call with frame_nums puts behind them, 16-byte aligned (fuse_tab_extra: where).
-static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, const float* views16, const float* frame_nums = nullptr, const void* extra = nullptr,
-                                 size_t extra_bytes = 0) {
-  const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  const size_t tab_bytes = extra ? fuse_tab_extra(n_stack, n_mat) + extra_bytes : fuse_tab_bytes(n_stack, n_mat, frame_nums != nullptr);
-  std::vector<float> tab;
-  std::vector<uint8_t> lamb;
-  try {
-    tab.resize(tab_bytes / 4 + 1);
-    lamb.resize(n_mat);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the view table");
-  }
-  for (uint32_t i = 0; i < n_mat; i++) lamb[i] = c->h_mats[16 * (size_t)i + 14] == PTMF_LAMBERTIAN;
-  if (int r = fuse_fill_tab(c, who, views16, n_stack, lamb.data(), n_mat, tab.data())) return r;
-  if (frame_nums) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_frames(n_stack, n_mat), frame_nums, (size_t)n_stack * 4);
-  if (extra) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_extra(n_stack, n_mat), extra, extra_bytes);
+// What ptmi_fuse_views and ptmi_accumulate_views do, their table finished (`tab`, `bytes`), before they enqueue a kernel: the call's stack `k` (of the view stack's
+// size) and the table's two copies, pinned and on the device — everything that can fail for want of memory — and then the table's upload into c->fuse_tab.
+static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, const void* tab, size_t bytes) {
+  const uint32_t n_stack = c->stacks[STACK_VIEWS].n;
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
   DBuf stack;
   if (int r = reserve_stack(c, k, n_stack, &stack)) return r;
   void* staged = nullptr;
-  HIP_TRY(c, c->fuse_tab.stage(tab_bytes, c->stream, &staged));
-  memcpy(staged, tab.data(), tab_bytes);
+  HIP_TRY(c, c->fuse_tab.stage(bytes, c->stream, &staged));
+  memcpy(staged, tab, bytes);
   if (int r = commit_stack(c, k, n_stack, &stack)) return r;
-  HIP_TRY(c, c->fuse_tab.send(tab_bytes, c->stream));
+  HIP_TRY(c, c->fuse_tab.send(bytes, c->stream));
   return PTMI_OK;
 }
 
 // The *_motion fusion calls: the composed records (include/ptmi_fuse_motion.h) of output views [first, first + n) of a stack of n_all views, radius R, from
-// motions16 [n_all][n_objects][16], into `rec` as [n][2 R + 1][n_objects]; the step entries the call reads are checked first, the composed ones as they are made.
-// Allocates host memory only.
-static int fuse_motion_table(ptmi_ctx* c, const char* who, const float* motions16, uint32_t n_objects, uint32_t n_all, uint32_t first, uint32_t n, uint32_t R,
-                             std::vector<ptmm_record>* rec) {
+// motions16 [n_all][n_objects][16], into `rec` as [n][2 R + 1][n_objects] — fuse_motion_count of them.  rec = nullptr: the checks that need no room alone, which a
+// call makes before it allocates (the pointer, the count, the step entries the call reads); the composed entries are checked as they are made.  Allocates nothing.
+static size_t fuse_motion_count(uint32_t n_objects, uint32_t n, uint32_t R) { return (size_t)n * (2u * R + 1u) * n_objects; }
+static int fuse_motion_table(ptmi_ctx* c, const char* who, const float* motions16, uint32_t n_objects, uint32_t n_all, uint32_t first, uint32_t n, uint32_t R, ptmm_record* rec) {
   if (!motions16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null motions16");
-  const uint64_t count = (uint64_t)n * (2u * R + 1u) * n_objects;
-  if (count > (uint64_t)PTMI_MOTION_MAX_RECORDS)
+  if ((uint64_t)n * (2u * R + 1u) * n_objects > (uint64_t)PTMI_MOTION_MAX_RECORDS)
     return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": " + std::to_string(n) + " views x " + std::to_string(2u * R + 1u) + " window views x " + std::to_string(n_objects) +
                                              " objects are more than PTMI_MOTION_MAX_RECORDS composed motions");
   int kind = 0;
   uint32_t bv = 0, bu = 0, bo = 0;
-  if (!ptmfm_compose_table(motions16, n_all, n_objects, first, n, R, nullptr, &kind, &bv, &bu, &bo))  // (the steps alone: nothing allocated for a refused call)
+  if (ptmfm_compose_table(motions16, n_all, n_objects, first, n, R, rec, &kind, &bv, &bu, &bo)) return PTMI_OK;
+  if (kind == PTMFM_BAD_STEP)
     return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the motion of view " + std::to_string(bv) + ", object " + std::to_string(bo) +
                                              " has a non-finite element or a 3x3 with a zero or non-finite determinant: view " + std::to_string(bv) + " is read by this call");
-  try {
-    rec->resize((size_t)count);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the composed motions");
-  }
-  if (count && !ptmfm_compose_table(motions16, n_all, n_objects, first, n, R, rec->data(), &kind, &bv, &bu, &bo))
-    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the motion composed from view " + std::to_string(bv) + " to view " + std::to_string(bu) + ", object " + std::to_string(bo) +
-                                             ", has a non-finite element or a 3x3 with a zero or non-finite determinant");
-  return PTMI_OK;
+  return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the motion composed from view " + std::to_string(bv) + " to view " + std::to_string(bu) + ", object " + std::to_string(bo) +
+                                           ", has a non-finite element or a 3x3 with a zero or non-finite determinant");
 }
 
-// ptmi_fuse_views (per_view false: frame_num), ptmi_fuse_views_frames (per_view: the view stack as source, frame_nums one per view of the stack) and
-// ptmi_fuse_views_motion (motion: per_view, motions16 [n_views of the stack][n_objects][16]; with source 1 the counts are all 1 and frame_nums is not read)
-static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* params, const float* views16, float frame_num, const float* frame_nums, bool per_view, int source,
-                      uint32_t first_view, uint32_t n_views, bool motion = false, const float* motions16 = nullptr, uint32_t n_objects = 0) {
+// ptmi_fuse_views, ptmi_fuse_views_frames (the view stack as source) and ptmi_fuse_views_motion (motion: its motions16 [n_views of the stack][n_objects][16])
+static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* params, const float* views16, FrameDivisor F, int source, uint32_t first_view, uint32_t n_views,
+                      const MotionPart* motion = nullptr) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   if (source != 0 && source != 1) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": source must be 0 (the view stack) or 1 (the denoised stack)");
   ptmi_fuse_params P;
-  if (int r = fuse_check_args(c, who, params, frame_num, source == 0 && !per_view, &P)) return r;
-  if (motion && source == 1) frame_nums = nullptr;  // (ignored: the denoised stack holds means)
-  if (per_view && !frame_nums && !(motion && source == 1)) return check_frame_nums(c, who, nullptr, 0, 0);
-  if (motion && !motions16) return fuse_motion_table(c, who, nullptr, 0, 0, 0, 0, 0, nullptr);
+  if (int r = fuse_check_args(c, who, params, F.frame_num, source == 0, &P)) return r;
+  // The one special case: a *_motion call on the denoised stack, which holds means.  Its frame_nums is not read; its kernel still takes per-view counts, so the table
+  // has that part, all ones (fill_views_and_frames with no frame_nums).
+  if (motion && source == 1) F = FrameDivisor::of(1.0f);
+  if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
+  if (motion && !motion->motions16) return fuse_motion_table(c, who, nullptr, 0, 0, 0, 0, 0, nullptr);
   if (int r = check_source_stacks(c, who, source == 1, first_view, n_views)) return r;
-  const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  if (per_view && frame_nums) {  // the call's range widened by the radius on both sides, clipped to the stack: the window of its output views
-    const uint32_t R = (uint32_t)P.radius, lo = first_view > R ? first_view - R : 0u, hi = (uint32_t)std::min<uint64_t>(n_stack, (uint64_t)first_view + n_views + R);
-    if (int r = check_frame_nums(c, who, frame_nums, lo, hi)) return r;
-  }
-  // A *_motion call's part of the table, behind the frame counts: the composed records, then one object id per sphere, per quad and per mesh of the scene as it is
-  // uploaded now, from the host copies (as ptmi_accumulate_views_motion's).  The triangles are on the device already.
-  std::vector<uint32_t> blob;
-  std::vector<float> ones;
-  MotionArgs mo{};
+  const uint32_t n_stack = c->stacks[STACK_VIEWS].n, R = (uint32_t)P.radius;
+  // the counts the call reads: its range widened by the radius on both sides, clipped to the stack — the window of its output views
+  if (int r = check_frame_nums(c, who, F, first_view > R ? first_view - R : 0u, (uint32_t)std::min<uint64_t>(n_stack, (uint64_t)first_view + n_views + R))) return r;
+  CallTableCounts n = scene_table_counts(c, motion != nullptr);
+  n.frames = F.each || motion;
   if (motion) {
-    std::vector<ptmm_record> rec;
-    if (int r = fuse_motion_table(c, who, motions16, n_objects, n_stack, first_view, n_views, (uint32_t)P.radius, &rec)) return r;
-    mo.n_objects = n_objects, mo.n_spheres = (uint32_t)(c->h_spheres.size() / 8), mo.n_quads = (uint32_t)(c->h_quads.size() / 20);
-    mo.n_tris = (uint32_t)c->n_tris_uploaded, mo.n_meshes = (uint32_t)(c->h_meshes.size() / 4);
-    const size_t rec_words = rec.size() * (sizeof(ptmm_record) / 4);
-    try {
-      blob.resize(std::max<size_t>(1, rec_words + mo.n_spheres + mo.n_quads + mo.n_meshes));  // (one word at least: blob.data() tells make_stack_with_table that there is such a part)
-      if (!frame_nums) ones.assign(n_stack, 1.0f);
-    } catch (const std::bad_alloc&) {
-      return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the motion table");
-    }
-    if (rec_words) memcpy(blob.data(), rec.data(), rec_words * 4);
-    int32_t* ids = reinterpret_cast<int32_t*>(blob.data() + rec_words);
-    for (uint32_t i = 0; i < mo.n_spheres; i++) *ids++ = ptmm_f32_object(c->h_spheres[8 * (size_t)i + 4]);
-    for (uint32_t i = 0; i < mo.n_quads; i++) *ids++ = ptmm_f32_object(c->h_quads[20 * (size_t)i + 11]);
-    for (uint32_t i = 0; i < mo.n_meshes; i++) *ids++ = ptmm_i32_object(c->h_meshes[4 * (size_t)i + 2]);
-    if (int r = make_stack_with_table(c, who, STACK_FUSED, views16, frame_nums ? frame_nums : ones.data(), blob.data(), blob.size() * 4)) return r;
-    const uint8_t* extra = reinterpret_cast<const uint8_t*>(c->fuse_tab.dev.p) + fuse_tab_extra(n_stack, n_mat);
-    mo.records = reinterpret_cast<const float4*>(extra);
-    mo.sphere_obj = reinterpret_cast<const int32_t*>(extra) + rec_words, mo.quad_obj = mo.sphere_obj + mo.n_spheres, mo.mesh_obj = mo.quad_obj + mo.n_quads;
-    mo.tris = c->d_tris.as<float>();
-  } else if (int r = make_stack_with_table(c, who, STACK_FUSED, views16, per_view ? frame_nums : nullptr)) return r;
-  const float fov_factor = (float)(1.0 / std::tan((double)c->prm.fov_degrees * (3.14159265358979323846 / 180.0) / 2.0));  // as make_render_const folds it
-  const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, source == 0 ? frame_num : 1.0f, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
+    if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_stack, first_view, n_views, R, nullptr)) return r;
+    n.motion_records = fuse_motion_count(motion->n_objects, n_views, R);
+  }
+  const CallTable L(n);
+  std::vector<uint8_t> tab;
+  if (int r = alloc_table(c, who, L, &tab)) return r;
+  if (motion)
+    if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_stack, first_view, n_views, R, L.ptr<ptmm_record>(tab.data(), L.motion))) return r;
+  if (int r = fill_views_and_frames(c, who, L, tab.data(), views16, F.frame_nums)) return r;
+  fill_scene_parts(c, L, tab.data());
+  if (int r = make_stack_with_table(c, who, STACK_FUSED, tab.data(), L.total)) return r;
+  MotionArgs mo{};
+  DeformArgs none{};
+  table_args(L, n, c->fuse_tab.dev.p, &mo, &none);
+  if (motion) mo.n_objects = motion->n_objects, mo.tris = c->d_tris.as<float>(), mo.n_tris = (uint32_t)c->n_tris_uploaded;  // (the triangles are on the device already)
+  const ptmf_consts k = ptmf_make_consts(c->W, c->H, context_fov_factor(c), source == 0 ? F.frame_num : 1.0f, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   return fuse_enqueue(c, c->stacks[source == 0 ? STACK_VIEWS : STACK_DENOISED].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(), c->stacks[STACK_FUSED].buf.as<float4>(),
-                      c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, k, per_view ? fuse_tab_frames_ptr(c->fuse_tab.dev.p, n_stack, n_mat) : nullptr,
-                      motion ? &mo : nullptr);
+                      table_ptrs(L, c->fuse_tab.dev.p, true), n.n_materials, c->W, c->H, n_stack, first_view, n_views, k, motion ? &mo : nullptr);
 }
 int ptmi_fuse_views_motion(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects, int source,
                            uint32_t first_view, uint32_t n_views) {
-  return fuse_views(c, "ptmi_fuse_views_motion", params, views16, 1.0f, frame_nums, true, source, first_view, n_views, true, motions16, n_objects);
+  const MotionPart motion{motions16, n_objects, nullptr};
+  return fuse_views(c, "ptmi_fuse_views_motion", params, views16, FrameDivisor::per_view(frame_nums), source, first_view, n_views, &motion);
 }
 int ptmi_fuse_views(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, float frame_num, int source, uint32_t first_view, uint32_t n_views) {
-  return fuse_views(c, "ptmi_fuse_views", params, views16, frame_num, nullptr, false, source, first_view, n_views);
+  return fuse_views(c, "ptmi_fuse_views", params, views16, FrameDivisor::of(frame_num), source, first_view, n_views);
 }
 int ptmi_fuse_views_frames(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, uint32_t first_view, uint32_t n_views) {
-  return fuse_views(c, "ptmi_fuse_views_frames", params, views16, 1.0f, frame_nums, true, 0, first_view, n_views);
+  return fuse_views(c, "ptmi_fuse_views_frames", params, views16, FrameDivisor::per_view(frame_nums), 0, first_view, n_views);
 }
 
 int ptmi_read_fused(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_FUSED, "ptmi_read_fused", view, 0, dst, bytes); }
@@ -541,72 +564,64 @@ int ptmi_resolve_fused_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t by
 int ptmi_fused_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) { return stack_device_ptr(c, STACK_FUSED, "ptmi_fused_device_ptr", nullptr, p, bytes, n_views); }
 int ptmi_release_fused(ptmi_ctx* c) { return release_stack(c, STACK_FUSED); }
 
-// What the *_images_motion calls have beside the *_images_frames calls' arguments: motions16 [n_images][n_objects][16], object_ids [n_images][h][w] i32
-struct MotionImages {
-  const float* motions16;
-  uint32_t n_objects;
-  const int32_t* object_ids;
-};
-
-// ptmi_fuse_images (per_view false), ptmi_fuse_images_frames (frame_nums: one per image) and ptmi_fuse_images_motion (motion, with per_view)
-static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
-                       const float* frame_nums, bool per_view, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out,
-                       const MotionImages* motion = nullptr) {
+// ptmi_fuse_images, ptmi_fuse_images_frames (F's frame_nums: one per image) and ptmi_fuse_images_motion (motion)
+static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const FrameDivisor& F,
+                       float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out, const MotionPart* motion = nullptr) {
   if (!c || !colour || !layers || !views16 || !out || (motion && !motion->object_ids)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_fuse_params P;
-  if (int r = fuse_check_args(c, who, params, frame_num, !per_view, &P)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = fuse_check_args(c, who, params, F.frame_num, true, &P)) return r;
+  if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
   if (int r = check_image_size(c, who, w, h, n_images)) return r;
-  if (per_view)
-    if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
+  if (int r = check_frame_nums(c, who, F, 0, n_images)) return r;
   if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": fov_degrees must be in (0,180)");
-  std::vector<ptmm_record> rec;
-  if (motion)
-    if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_images, 0, n_images, (uint32_t)P.radius, &rec)) return r;
   if (!lambertian) n_materials = 0;
-  const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials, per_view);
-  std::vector<float> tab;
-  try {
-    tab.resize(tab_bytes / 4 + 1);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the view table");
+  CallTableCounts n;
+  n.n_views = n_images, n.n_materials = n_materials, n.frames = F.each;
+  if (motion) {
+    if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_images, 0, n_images, (uint32_t)P.radius, nullptr)) return r;
+    n.motion_records = fuse_motion_count(motion->n_objects, n_images, (uint32_t)P.radius);
   }
-  if (int r = fuse_fill_tab(c, who, views16, n_images, lambertian, n_materials, tab.data())) return r;
-  if (per_view) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_frames(n_images, n_materials), frame_nums, (size_t)n_images * 4);
-  const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
+  const CallTable L(n);
+  std::vector<uint8_t> tab;
+  if (int r = alloc_table(c, who, L, &tab)) return r;
+  if (motion)
+    if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_images, 0, n_images, (uint32_t)P.radius, L.ptr<ptmm_record>(tab.data(), L.motion))) return r;
+  if (int r = fill_views_and_frames(c, who, L, tab.data(), views16, F.frame_nums)) return r;
+  call_table_fill_materials(L, tab.data(), lambertian, n_materials);
+  const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), F.frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   const size_t npix = (size_t)w * (size_t)h;
-  DBuf dtab, drec, dids;  // (a *_motion call's records and id images are its own, had before anything is enqueued)
-  MotionArgs mo{};
+  DBuf dtab, dids;  // (a *_motion call's id images are its own, had before anything is enqueued)
   if (motion) {
     HIP_TRY(c, hipSetDevice(c->device));
     (void)hipGetLastError();
-    HIP_TRY(c, drec.ensure(std::max<size_t>(rec.size() * sizeof(ptmm_record), 16)));
     HIP_TRY(c, dids.ensure(npix * 4 * n_images));
-    mo.records = drec.as<float4>(), mo.ids = dids.as<int32_t>(), mo.n_objects = motion->n_objects;
   }
-  return on_host_images(c, who, colour, layers, npix, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
-    HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+  return on_host_images(c, who, colour, layers, npix, n_images, out, dtab, L.total, [&](const float4* col, const float4* lay, float4* res) -> int {
+    HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), L.total, hipMemcpyHostToDevice, c->stream));
+    MotionArgs mo{};
+    DeformArgs none{};
+    table_args(L, n, dtab.p, &mo, &none);
     if (motion) {
-      if (!rec.empty()) HIP_TRY(c, hipMemcpyAsync(drec.p, rec.data(), rec.size() * sizeof(ptmm_record), hipMemcpyHostToDevice, c->stream));
+      mo.ids = dids.as<int32_t>(), mo.n_objects = motion->n_objects;
       HIP_TRY(c, hipMemcpyAsync(dids.p, motion->object_ids, npix * 4 * n_images, hipMemcpyHostToDevice, c->stream));
     }
-    return fuse_enqueue(c, col, lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, 0, n_images, k,
-                        per_view ? fuse_tab_frames_ptr(dtab.p, n_images, n_materials) : nullptr, motion ? &mo : nullptr);
+    return fuse_enqueue(c, col, lay, res, table_ptrs(L, dtab.p, lambertian != nullptr), n_materials, w, h, n_images, 0, n_images, k, motion ? &mo : nullptr);
   });
 }
 int ptmi_fuse_images_motion(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
                             const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
                             const ptmi_fuse_params* params, float* out) {
-  const MotionImages motion{motions16, n_objects, object_ids};
-  return fuse_images(c, "ptmi_fuse_images_motion", colour, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params, out, &motion);
+  const MotionPart motion{motions16, n_objects, object_ids};
+  return fuse_images(c, "ptmi_fuse_images_motion", colour, layers, views16, w, h, n_images, FrameDivisor::per_view(frame_nums), fov_degrees, lambertian, n_materials, params, out,
+                     &motion);
 }
 int ptmi_fuse_images(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, float fov_degrees,
                      const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
-  return fuse_images(c, "ptmi_fuse_images", colour, layers, views16, w, h, n_images, frame_num, nullptr, false, fov_degrees, lambertian, n_materials, params, out);
+  return fuse_images(c, "ptmi_fuse_images", colour, layers, views16, w, h, n_images, FrameDivisor::of(frame_num), fov_degrees, lambertian, n_materials, params, out);
 }
 int ptmi_fuse_images_frames(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums, float fov_degrees,
                             const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
-  return fuse_images(c, "ptmi_fuse_images_frames", colour, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params, out);
+  return fuse_images(c, "ptmi_fuse_images_frames", colour, layers, views16, w, h, n_images, FrameDivisor::per_view(frame_nums), fov_degrees, lambertian, n_materials, params, out);
 }
 
 // ---- the geometry stack (ptmi_capture_view_geometry): what ptmi_accumulate_views_deform reads of a view beside its images ----
@@ -691,49 +706,45 @@ int ptmi_release_geometry(ptmi_ctx* c) {
 // ---- the accumulated stack (ptmi_accumulate_views, ptmi_accumulate_images) and the guided filter on it (ptmi_denoise_views_accumulated, ptmi_denoise_images_accumulated) ----
 // (ptmi_default_accumulate_params, ptmi_accumulate_reference and ptmi_denoise_accumulated_reference need no GPU: ptmi_host.cpp)
 // The kernel on device arrays: colour, moments [n_stack][H][W] float4, layers [n_stack][3][H][W] float4, planes [3][n_stack][H][W] float4, of which views
-// [first, first + n) are written, one launch per view in ascending order; view `first` takes its history from view first - 1 of `planes` when `resume`.
-// frames: nullptr, or the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_accumulate_view_frames.
-// deform (with frames; motion may be nullptr: a static world beside the triangles): k_accumulate_view_deform's operands, args.tris_cur = slot 0 of the geometry, slot
+// [first, first + n) are written, one launch per view in ascending order; view `first` takes its history from view first - 1 of `planes` when `resume`.  t: the
+// table's parts (table_ptrs).
+// t.frames: the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_accumulate_view_frames.
+// motion (with t.frames): k_accumulate_view_motion's operands, records = those of the first view that has a predecessor (first_view_with_history), n_objects per view.
+// deform (with t.frames; motion may be nullptr: a static world beside the triangles): k_accumulate_view_deform's operands, args.tris_cur = slot 0 of the geometry, slot
 // after slot `slot` float4 apart, indexed by the view's number; args.records laid out as the motion records are.
 struct DeformCall {
   DeformArgs args;
   size_t slot;
 };
-static int accumulate_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, const float4* layers, float4* planes, const void* tab, bool has_lamb, uint32_t n_materials,
-                              int W, int H, uint32_t n_stack, uint32_t first, uint32_t n, bool resume, const ptmf_consts& k, const ptma_consts& ka, const float* frames = nullptr,
-                              const MotionArgs* motion = nullptr, const DeformCall* deform = nullptr) {
+static int accumulate_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, const float4* layers, float4* planes, const TablePtrs& t, uint32_t n_materials, int W, int H,
+                              uint32_t n_stack, uint32_t first, uint32_t n, bool resume, const ptmf_consts& k, const ptma_consts& ka, const MotionArgs* motion = nullptr,
+                              const DeformCall* deform = nullptr) {
   const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
   const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
-  const uint8_t* lamb = has_lamb ? reinterpret_cast<const uint8_t*>(tab) + (size_t)n_stack * kFuseRow * 16 : nullptr;
   const size_t npix = (size_t)W * (size_t)H;
   auto plane = [&](uint32_t pl, uint32_t v) { return planes + ((size_t)pl * n_stack + v) * npix; };
   for (uint32_t v = first; v < first + n; v++) {
     const bool has_prev = v > 0 && (v > first || resume);
+    float4 *prev1 = has_prev ? plane(1, v - 1) : nullptr, *prev2 = has_prev ? plane(2, v - 1) : nullptr;
+    auto shared = [&](auto launch) {  // what every entry takes: its own operands follow
+      launch(colour, moments, layers, prev1, prev2, plane(0, v), plane(1, v), plane(2, v), t.rows, t.lamb, n_materials, W, H, v, k, ka);
+    };
+    const size_t rel = has_prev ? v - first_view_with_history(first, resume) : 0;  // a view without a predecessor reads no record
+    MotionArgs mo = motion ? *motion : MotionArgs{};
+    mo.records += rel * mo.n_objects * 6;
+    if (mo.ids) mo.ids += (size_t)v * npix;
     if (deform) {
-      MotionArgs mo = motion ? *motion : MotionArgs{};
       DeformArgs de = deform->args;
-      if (has_prev) {
-        const size_t rel = v - (resume ? first : first + 1u);
-        if (motion) mo.records += rel * mo.n_objects * 6;
-        de.records += rel * de.n_transforms * 9;
-      }
-      if (mo.ids) mo.ids += (size_t)v * npix;
+      de.records += rel * de.n_transforms * 9;
       de.tris_cur = deform->args.tris_cur + (size_t)v * deform->slot, de.tris_prev = deform->args.tris_cur + (size_t)(has_prev ? v - 1u : v) * deform->slot;
-      hipLaunchKernelGGL(k_accumulate_view_deform, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr,
-                         has_prev ? plane(2, v - 1) : nullptr, plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka, frames, mo,
-                         de);
-    } else if (motion) {  // (with frames.)  The records of the call lie view after view from the first view that has a predecessor; a view without one reads none.
-      MotionArgs mo = *motion;
-      if (has_prev) mo.records += (size_t)(v - (resume ? first : first + 1u)) * mo.n_objects * 6;
-      if (mo.ids) mo.ids += (size_t)v * npix;
-      hipLaunchKernelGGL(k_accumulate_view_motion, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr,
-                         has_prev ? plane(2, v - 1) : nullptr, plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka, frames, mo);
-    } else if (frames)
-      hipLaunchKernelGGL(k_accumulate_view_frames, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr,
-                         has_prev ? plane(2, v - 1) : nullptr, plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka, frames);
-    else
-      hipLaunchKernelGGL(k_accumulate_view, dim3(gx), dim3(kBlock), 0, c->stream, colour, moments, layers, has_prev ? plane(1, v - 1) : nullptr, has_prev ? plane(2, v - 1) : nullptr,
-                         plane(0, v), plane(1, v), plane(2, v), reinterpret_cast<const float4*>(tab), lamb, n_materials, W, H, v, k, ka);
+      shared([&](auto... a) { hipLaunchKernelGGL(k_accumulate_view_deform, dim3(gx), dim3(kBlock), 0, c->stream, a..., t.frames, mo, de); });
+    } else if (motion) {
+      shared([&](auto... a) { hipLaunchKernelGGL(k_accumulate_view_motion, dim3(gx), dim3(kBlock), 0, c->stream, a..., t.frames, mo); });
+    } else if (t.frames) {
+      shared([&](auto... a) { hipLaunchKernelGGL(k_accumulate_view_frames, dim3(gx), dim3(kBlock), 0, c->stream, a..., t.frames); });
+    } else {
+      shared([&](auto... a) { hipLaunchKernelGGL(k_accumulate_view, dim3(gx), dim3(kBlock), 0, c->stream, a...); });
+    }
     HIP_TRY(c, hipGetLastError());
   }
   return PTMI_OK;
@@ -747,53 +758,48 @@ static int accumulate_check_args(ptmi_ctx* c, const char* who, const ptmi_accumu
 }
 
 // The *_motion calls: the records (include/ptmi_motion.h) of views [lo, hi) of motions16 [n_all][n_objects][16], the entries the call reads, view after view into
-// `rec`; each has to be finite with a 3x3 that can be inverted — the others may hold anything.  Allocates host memory only.
-static int make_motion_records(ptmi_ctx* c, const char* who, const float* motions16, uint32_t n_objects, uint32_t n_all, uint32_t lo, uint32_t hi, std::vector<ptmm_record>* rec) {
+// `rec`, record_count of them; each has to be finite with a 3x3 that can be inverted — the others may hold anything.  rec = nullptr: the checks alone, nothing is
+// written: what a call does before it allocates, so that its refusals come in their order.  Allocates nothing.
+static size_t record_count(uint32_t per_view, uint32_t lo, uint32_t hi) { return (size_t)(hi > lo ? hi - lo : 0) * per_view; }
+static int make_motion_records(ptmi_ctx* c, const char* who, const float* motions16, uint32_t n_objects, uint32_t n_all, uint32_t lo, uint32_t hi, ptmm_record* rec) {
   if (!motions16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null motions16");
   if ((uint64_t)n_all * n_objects > (uint64_t)PTMI_MOTION_MAX_RECORDS)
     return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": " + std::to_string(n_all) + " views x " + std::to_string(n_objects) + " objects are more than PTMI_MOTION_MAX_RECORDS motions");
-  try {
-    rec->resize((size_t)(hi > lo ? hi - lo : 0) * n_objects);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the motion records");
-  }
+  ptmm_record unkept;
   for (uint32_t v = lo; v < hi; v++)
     for (uint32_t o = 0; o < n_objects; o++)
-      if (!ptmm_make_record(motions16 + 16 * ((size_t)v * n_objects + o), &(*rec)[(size_t)(v - lo) * n_objects + o]))
+      if (!ptmm_make_record(motions16 + 16 * ((size_t)v * n_objects + o), rec ? &rec[(size_t)(v - lo) * n_objects + o] : &unkept))
         return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the motion of view " + std::to_string(v) + ", object " + std::to_string(o) +
                                                  " has a non-finite element or a 3x3 with a zero or non-finite determinant: view " + std::to_string(v) + " is read by this call");
   return PTMI_OK;
 }
 
-// The *_deform calls: the records (include/ptmi_deform.h) of views [lo, hi) — each from the transforms of its view and of the view before, slot after slot of
-// n_transforms x 32 f32 from `tf0` = slot 0 — view after view into `rec`.  Allocates host memory only.
-static int make_deform_records(ptmi_ctx* c, const char* who, const float* tf0, uint32_t n_transforms, uint32_t n_all, uint32_t lo, uint32_t hi, std::vector<ptmdf_record>* rec) {
+// The *_deform calls: the records (include/ptmi_deform.h) of views [lo, hi), lo >= 1 — each from the transforms of its view and of the view before, slot after slot
+// of n_transforms x 32 f32 from `tf0` = slot 0 — view after view into `rec`; rec = nullptr as above.  Allocates nothing.
+static int make_deform_records(ptmi_ctx* c, const char* who, const float* tf0, uint32_t n_transforms, uint32_t n_all, uint32_t lo, uint32_t hi, ptmdf_record* rec) {
   if ((uint64_t)n_all * n_transforms > (uint64_t)PTMI_MOTION_MAX_RECORDS)
     return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": " + std::to_string(n_all) + " views x " + std::to_string(n_transforms) + " transforms are more than PTMI_MOTION_MAX_RECORDS records");
-  try {
-    rec->resize((size_t)(hi > lo ? hi - lo : 0) * n_transforms);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the deformation records");
-  }
-  for (uint32_t v = std::max(lo, 1u); v < hi; v++)
+  ptmdf_record unkept;
+  for (uint32_t v = lo; v < hi; v++)
     for (uint32_t o = 0; o < n_transforms; o++)
-      if (!ptmdf_make_record(tf0 + 32 * ((size_t)v * n_transforms + o), tf0 + 32 * ((size_t)(v - 1) * n_transforms + o), &(*rec)[(size_t)(v - lo) * n_transforms + o]))
+      if (!ptmdf_make_record(tf0 + 32 * ((size_t)v * n_transforms + o), tf0 + 32 * ((size_t)(v - 1) * n_transforms + o), rec ? &rec[(size_t)(v - lo) * n_transforms + o] : &unkept))
         return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the transform of view " + std::to_string(v) + " or of view " + std::to_string(v - 1) + ", object " + std::to_string(o) +
                                                  ", has an element that is not finite: view " + std::to_string(v) + " is read by this call");
   return PTMI_OK;
 }
 
-// ptmi_accumulate_views (per_view false: frame_num), ptmi_accumulate_views_frames (per_view: frame_nums, one per view of the stack) and ptmi_accumulate_views_motion
-// (motion: per_view, and motions16 [n_views of the stack][n_objects][16]) and ptmi_accumulate_views_deform (deform: motion, whose motions16 may then be null with
-// n_objects = 0, and the geometry stack)
-static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_params* params, const float* views16, float frame_num, const float* frame_nums, bool per_view,
-                            uint32_t first_view, uint32_t n_views, int resume, bool motion = false, const float* motions16 = nullptr, uint32_t n_objects = 0, bool deform = false) {
+// ptmi_accumulate_views, ptmi_accumulate_views_frames, ptmi_accumulate_views_motion (motion: its motions16 [n_views of the stack][n_objects][16]) and
+// ptmi_accumulate_views_deform (deform: the context's geometry stack, with motion, whose motions16 may then be null with n_objects = 0)
+static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_params* params, const float* views16, const FrameDivisor& F, uint32_t first_view, uint32_t n_views,
+                            int resume, const MotionPart* motion = nullptr, const DeformPart* deform = nullptr) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_accumulate_params P;
-  if (int r = accumulate_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = accumulate_check_args(c, who, params, F.frame_num, &P)) return r;
+  if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
   static const float no_motions[16] = {};
+  const float* motions16 = motion ? motion->motions16 : nullptr;
+  const uint32_t n_objects = motion ? motion->n_objects : 0u;
   if (deform && !motions16 && n_objects == 0) motions16 = no_motions;  // (a static world beside the triangles: no entry is read)
   if (motion && !motions16) return make_motion_records(c, who, nullptr, 0, 0, 0, 0, nullptr);
   if (int r = check_stack(c, STACK_MOMENTS, who, 0)) return r;  // (the moment stack first, as ptmi_denoise_views_guided asks)
@@ -805,79 +811,64 @@ static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_
     if (first_view == 0) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": resume needs first_view > 0: view 0 has no predecessor");
     if (int r = check_stack(c, STACK_ACCUMULATED, (std::string(who) + " (resume)").c_str(), 0)) return r;
   }
-  if (per_view)  // the call's range, and the view before it where its state is taken over
-    if (int r = check_frame_nums(c, who, frame_nums, resume ? first_view - 1u : first_view, first_view + n_views)) return r;
-  const uint32_t n_stack = c->stacks[STACK_VIEWS].n, n_mat = (uint32_t)(c->h_mats.size() / 16);
-  // A *_motion call's part of the table: the records of the views it reads, then one object id per sphere, per quad and per mesh of the scene as it is uploaded now —
-  // from the host copies, so that no device buffer a render has yet to refresh is read.  The triangles are on the device already (ptmi_upload puts them there).
-  std::vector<uint32_t> blob;
-  MotionArgs mo{};
-  DeformCall dc{};
-  std::vector<ptmdf_record> drec;
-  if (deform) {  // the geometry the call reads: slots first_view .. first_view + n_views - 1, and first_view - 1 when resuming
-    const ptmi_ctx::GeometryStack& g = c->geometry;
+  // what the call reads: its range, and the view before it where its state is taken over; records have the views of it that have a predecessor
+  const uint32_t first_read = resume ? first_view - 1u : first_view, end = first_view + n_views, first_rec = first_view_with_history(first_view, resume != 0);
+  if (int r = check_frame_nums(c, who, F, first_read, end)) return r;
+  const ptmi_ctx::GeometryStack& g = c->geometry;
+  CallTableCounts n = scene_table_counts(c, motion != nullptr);
+  const uint32_t n_stack = n.n_views;
+  n.frames = F.each;
+  if (deform) {  // the geometry the call reads: the slots of those views
     if (!g.n_views) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no geometry stack: ptmi_capture_view_geometry makes it, view by view");
     if (g.n_views != n_stack) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry stack has " + std::to_string(g.n_views) + " views, the view stack " + std::to_string(n_stack));
     if (g.n_tris != c->n_tris_uploaded || g.n_xforms != c->h_xforms.size() / 32)
       return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry stack holds " + std::to_string(g.n_tris) + " triangles and " + std::to_string(g.n_xforms) + " transforms, the scene now " +
                                          std::to_string(c->n_tris_uploaded) + " and " + std::to_string(c->h_xforms.size() / 32));
-    for (uint32_t v = resume ? first_view - 1u : first_view; v < first_view + n_views; v++)
+    for (uint32_t v = first_read; v < end; v++)
       if (!g.captured[v]) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry of view " + std::to_string(v) + " was never captured: view " + std::to_string(v) + " is read by this call");
-    if (int r = make_deform_records(c, who, g.h_xforms.data(), (uint32_t)g.n_xforms, n_stack, resume ? first_view : first_view + 1u, first_view + n_views, &drec)) return r;
+    if (int r = make_deform_records(c, who, g.h_xforms.data(), (uint32_t)g.n_xforms, n_stack, first_rec, end, nullptr)) return r;
+    n.deform_records = record_count((uint32_t)g.n_xforms, first_rec, end), n.mesh_words = c->h_meshes.size();
   }
   if (motion) {
-    std::vector<ptmm_record> rec;
-    if (int r = make_motion_records(c, who, motions16, n_objects, n_stack, resume ? first_view : first_view + 1u, first_view + n_views, &rec)) return r;
-    mo.n_objects = n_objects, mo.n_spheres = (uint32_t)(c->h_spheres.size() / 8), mo.n_quads = (uint32_t)(c->h_quads.size() / 20);
-    mo.n_tris = (uint32_t)c->n_tris_uploaded, mo.n_meshes = (uint32_t)(c->h_meshes.size() / 4);
-    const size_t rec_words = rec.size() * (sizeof(ptmm_record) / 4);
-    // (a *_deform call: then, on the next multiple of four words, its own records and the mesh table, four i32 per mesh, from the host copy too)
-    const size_t drec_at = (rec_words + mo.n_spheres + mo.n_quads + mo.n_meshes + 3) & ~(size_t)3, drec_words = drec.size() * (sizeof(ptmdf_record) / 4);
-    try {
-      blob.resize(std::max<size_t>(1, deform ? drec_at + drec_words + c->h_meshes.size() : rec_words + mo.n_spheres + mo.n_quads + mo.n_meshes));  // (one word at least: blob.data() tells make_stack_with_table that there is such a part)
-    } catch (const std::bad_alloc&) {
-      return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the motion table");
-    }
-    if (rec_words) memcpy(blob.data(), rec.data(), rec_words * 4);
-    int32_t* ids = reinterpret_cast<int32_t*>(blob.data() + rec_words);
-    for (uint32_t i = 0; i < mo.n_spheres; i++) *ids++ = ptmm_f32_object(c->h_spheres[8 * (size_t)i + 4]);
-    for (uint32_t i = 0; i < mo.n_quads; i++) *ids++ = ptmm_f32_object(c->h_quads[20 * (size_t)i + 11]);
-    for (uint32_t i = 0; i < mo.n_meshes; i++) *ids++ = ptmm_i32_object(c->h_meshes[4 * (size_t)i + 2]);
-    if (deform) {
-      if (drec_words) memcpy(blob.data() + drec_at, drec.data(), drec_words * 4);
-      if (!c->h_meshes.empty()) memcpy(blob.data() + drec_at + drec_words, c->h_meshes.data(), c->h_meshes.size() * 4);
-    }
-    if (int r = make_stack_with_table(c, who, STACK_ACCUMULATED, views16, frame_nums, blob.data(), blob.size() * 4)) return r;
-    const uint8_t* extra = reinterpret_cast<const uint8_t*>(c->fuse_tab.dev.p) + fuse_tab_extra(n_stack, n_mat);
-    if (deform) {
-      dc.args.records = reinterpret_cast<const float4*>(extra + drec_at * 4);
-      dc.args.meshes = reinterpret_cast<const int32_t*>(extra + (drec_at + drec_words) * 4);
-      dc.args.tris_cur = c->geometry.tris.as<float4>(), dc.slot = c->geometry.n_tris * 6;
-      dc.args.n_tris = (uint32_t)c->geometry.n_tris, dc.args.n_meshes = mo.n_meshes, dc.args.n_transforms = (uint32_t)c->geometry.n_xforms;
-    }
-    mo.records = reinterpret_cast<const float4*>(extra);
-    mo.sphere_obj = reinterpret_cast<const int32_t*>(extra) + rec_words, mo.quad_obj = mo.sphere_obj + mo.n_spheres, mo.mesh_obj = mo.quad_obj + mo.n_quads;
-    mo.tris = c->d_tris.as<float>();
-  } else if (int r = make_stack_with_table(c, who, STACK_ACCUMULATED, views16, per_view ? frame_nums : nullptr)) return r;
-  const float fov_factor = (float)(1.0 / std::tan((double)c->prm.fov_degrees * (3.14159265358979323846 / 180.0) / 2.0));  // as make_render_const folds it
-  const ptmf_consts k = ptmf_make_consts(c->W, c->H, fov_factor, frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
+    if (int r = make_motion_records(c, who, motions16, n_objects, n_stack, first_rec, end, nullptr)) return r;
+    n.motion_records = record_count(n_objects, first_rec, end);
+  }
+  const CallTable L(n);
+  std::vector<uint8_t> tab;
+  if (int r = alloc_table(c, who, L, &tab)) return r;
+  if (deform)
+    if (int r = make_deform_records(c, who, g.h_xforms.data(), (uint32_t)g.n_xforms, n_stack, first_rec, end, L.ptr<ptmdf_record>(tab.data(), L.deform))) return r;
+  if (motion)
+    if (int r = make_motion_records(c, who, motions16, n_objects, n_stack, first_rec, end, L.ptr<ptmm_record>(tab.data(), L.motion))) return r;
+  if (int r = fill_views_and_frames(c, who, L, tab.data(), views16, F.frame_nums)) return r;
+  fill_scene_parts(c, L, tab.data());
+  if (int r = make_stack_with_table(c, who, STACK_ACCUMULATED, tab.data(), L.total)) return r;
+  MotionArgs mo{};
+  DeformCall dc{};
+  table_args(L, n, c->fuse_tab.dev.p, &mo, &dc.args);
+  if (motion) mo.n_objects = n_objects, mo.tris = c->d_tris.as<float>(), mo.n_tris = (uint32_t)c->n_tris_uploaded;  // (the triangles are on the device already: ptmi_upload puts them there)
+  if (deform) dc.args.tris_cur = g.tris.as<float4>(), dc.slot = g.n_tris * 6, dc.args.n_tris = (uint32_t)g.n_tris, dc.args.n_transforms = (uint32_t)g.n_xforms;
+  const ptmf_consts k = ptmf_make_consts(c->W, c->H, context_fov_factor(c), F.frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   return accumulate_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>(), c->stacks[STACK_MOMENTS].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(),
-                            c->stacks[STACK_ACCUMULATED].buf.as<float4>(), c->fuse_tab.dev.p, true, n_mat, c->W, c->H, n_stack, first_view, n_views, resume != 0, k,
-                            ptma_make_consts(P.max_history, P.min_frames), per_view ? fuse_tab_frames_ptr(c->fuse_tab.dev.p, n_stack, n_mat) : nullptr, motion ? &mo : nullptr, deform ? &dc : nullptr);
+                            c->stacks[STACK_ACCUMULATED].buf.as<float4>(), table_ptrs(L, c->fuse_tab.dev.p, true), n.n_materials, c->W, c->H, n_stack, first_view, n_views, resume != 0, k,
+                            ptma_make_consts(P.max_history, P.min_frames), motion ? &mo : nullptr, deform ? &dc : nullptr);
 }
 int ptmi_accumulate_views_deform(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects,
                                  uint32_t first_view, uint32_t n_views, int resume) {
-  return accumulate_views(c, "ptmi_accumulate_views_deform", params, views16, 1.0f, frame_nums, true, first_view, n_views, resume, true, motions16, n_objects, true);
+  const MotionPart motion{motions16, n_objects, nullptr};
+  const DeformPart deform{};
+  return accumulate_views(c, "ptmi_accumulate_views_deform", params, views16, FrameDivisor::per_view(frame_nums), first_view, n_views, resume, &motion, &deform);
 }
 int ptmi_accumulate_views_motion(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects,
                                  uint32_t first_view, uint32_t n_views, int resume) {
-  return accumulate_views(c, "ptmi_accumulate_views_motion", params, views16, 1.0f, frame_nums, true, first_view, n_views, resume, true, motions16, n_objects);
+  const MotionPart motion{motions16, n_objects, nullptr};
+  return accumulate_views(c, "ptmi_accumulate_views_motion", params, views16, FrameDivisor::per_view(frame_nums), first_view, n_views, resume, &motion);
 }
 int ptmi_accumulate_views(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, float frame_num, uint32_t first_view, uint32_t n_views, int resume) {
-  return accumulate_views(c, "ptmi_accumulate_views", params, views16, frame_num, nullptr, false, first_view, n_views, resume);
+  return accumulate_views(c, "ptmi_accumulate_views", params, views16, FrameDivisor::of(frame_num), first_view, n_views, resume);
 }
 int ptmi_accumulate_views_frames(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, uint32_t first_view, uint32_t n_views, int resume) {
-  return accumulate_views(c, "ptmi_accumulate_views_frames", params, views16, 1.0f, frame_nums, true, first_view, n_views, resume);
+  return accumulate_views(c, "ptmi_accumulate_views_frames", params, views16, FrameDivisor::per_view(frame_nums), first_view, n_views, resume);
 }
 
 int ptmi_read_accumulated(ptmi_ctx* c, uint32_t view, int plane, float* dst, size_t bytes) { return read_stack(c, STACK_ACCUMULATED, "ptmi_read_accumulated", view, plane, dst, bytes); }
@@ -889,86 +880,68 @@ int ptmi_accumulated_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* 
 }
 int ptmi_release_accumulated(ptmi_ctx* c) { return release_stack(c, STACK_ACCUMULATED); }
 
-// What ptmi_accumulate_images_deform has beside ptmi_accumulate_images_motion's arguments
-struct DeformImages {
-  const float* triangles_seq;  // [n_images][n_triangles][24]
-  uint32_t n_triangles;
-  const float* transforms_seq;  // [n_images][n_transforms][32]
-  uint32_t n_transforms;
-  const int32_t* meshes;  // [n_meshes][4]
-  uint32_t n_meshes;
-};
-
-// ptmi_accumulate_images (per_view false), ptmi_accumulate_images_frames (frame_nums: one per image), ptmi_accumulate_images_motion (motion, with per_view) and
-// ptmi_accumulate_images_deform (deform, with per_view; motion may then be nullptr)
+// ptmi_accumulate_images, ptmi_accumulate_images_frames (F's frame_nums: one per image), ptmi_accumulate_images_motion (motion) and ptmi_accumulate_images_deform
+// (deform; motion may then be nullptr)
 static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
-                             float frame_num, const float* frame_nums, bool per_view, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
-                             const ptmi_accumulate_params* params, const float* history_in, float* out, const MotionImages* motion = nullptr, const DeformImages* deform = nullptr) {
+                             const FrameDivisor& F, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in,
+                             float* out, const MotionPart* motion = nullptr, const DeformPart* deform = nullptr) {
   if (!c || !colour_sums || !moments || !layers || !views16 || !out || (motion && !motion->object_ids)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   if (deform && (!deform->triangles_seq || (deform->n_transforms && !deform->transforms_seq) || (deform->n_meshes && !deform->meshes)))
     return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   if (deform && deform->n_triangles == 0) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": no triangles");
   ptmi_accumulate_params P;
-  if (int r = accumulate_check_args(c, who, params, per_view ? 1.0f : frame_num, &P)) return r;
-  if (per_view && !frame_nums) return check_frame_nums(c, who, nullptr, 0, 0);
+  if (int r = accumulate_check_args(c, who, params, F.frame_num, &P)) return r;
+  if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
   if (int r = check_image_size(c, who, w, h, n_images)) return r;
-  if (per_view)
-    if (int r = check_frame_nums(c, who, frame_nums, 0, n_images)) return r;
+  if (int r = check_frame_nums(c, who, F, 0, n_images)) return r;
   if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": fov_degrees must be in (0,180)");
   if (history_in && n_images < 2) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": history_in makes image 0 the view before the first: need n_images >= 2");
-  std::vector<ptmm_record> rec;  // (images 1 .. n_images - 1 have a predecessor, with or without history_in)
-  if (motion)
-    if (int r = make_motion_records(c, who, motion->motions16, motion->n_objects, n_images, 1, n_images, &rec)) return r;
-  std::vector<ptmdf_record> drec_h;  // (likewise)
-  if (deform)
-    if (int r = make_deform_records(c, who, deform->transforms_seq, deform->n_transforms, n_images, 1, n_images, &drec_h)) return r;
   if (!lambertian) n_materials = 0;
-  const size_t tab_bytes = fuse_tab_bytes(n_images, n_materials, per_view);
-  std::vector<float> tab;
-  try {
-    tab.resize(tab_bytes / 4 + 1);
-  } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the view table");
+  CallTableCounts n;  // (images 1 .. n_images - 1 have a predecessor, with or without history_in: theirs are the records)
+  n.n_views = n_images, n.n_materials = n_materials, n.frames = F.each;
+  if (motion) {
+    if (int r = make_motion_records(c, who, motion->motions16, motion->n_objects, n_images, 1, n_images, nullptr)) return r;
+    n.motion_records = record_count(motion->n_objects, 1, n_images);
   }
-  if (int r = fuse_fill_tab(c, who, views16, n_images, lambertian, n_materials, tab.data())) return r;
-  if (per_view) memcpy(reinterpret_cast<uint8_t*>(tab.data()) + fuse_tab_frames(n_images, n_materials), frame_nums, (size_t)n_images * 4);
-  const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
+  if (deform) {
+    if (int r = make_deform_records(c, who, deform->transforms_seq, deform->n_transforms, n_images, 1, n_images, nullptr)) return r;
+    n.deform_records = record_count(deform->n_transforms, 1, n_images), n.mesh_words = (size_t)deform->n_meshes * 4;
+  }
+  const CallTable L(n);
+  std::vector<uint8_t> tab;
+  if (int r = alloc_table(c, who, L, &tab)) return r;
+  if (motion)
+    if (int r = make_motion_records(c, who, motion->motions16, motion->n_objects, n_images, 1, n_images, L.ptr<ptmm_record>(tab.data(), L.motion))) return r;
+  if (deform) {
+    if (int r = make_deform_records(c, who, deform->transforms_seq, deform->n_transforms, n_images, 1, n_images, L.ptr<ptmdf_record>(tab.data(), L.deform))) return r;
+    call_table_fill_meshes(L, tab.data(), deform->meshes);
+  }
+  if (int r = fill_views_and_frames(c, who, L, tab.data(), views16, F.frame_nums)) return r;
+  call_table_fill_materials(L, tab.data(), lambertian, n_materials);
+  const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), F.frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   const ptma_consts ka = ptma_make_consts(P.max_history, P.min_frames);
-  const size_t npix = (size_t)w * (size_t)h, bytes = npix * 16 * n_images;
+  const size_t npix = (size_t)w * (size_t)h, bytes = npix * 16 * n_images, tri_bytes = deform ? (size_t)n_images * deform->n_triangles * 96 : 0;
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
-  DBuf mom, dtab;  // (on_host_images brings the colour, the layers, the three planes and the table; the moments are this call's own, had before anything is enqueued)
+  // (on_host_images brings the colour, the layers, the three planes and the table; the per-pixel arrays beside them are this call's own, had before anything is enqueued:
+  // the moments, a *_motion call's id images, a *_deform call's triangle sequence)
+  DBuf mom, dtab, dids, dtris;
   HIP_TRY(c, mom.ensure(bytes));
-  DBuf drec, dids;  // (a *_motion call's records and id images: its own too)
-  MotionArgs mo{};
-  if (motion) {
-    HIP_TRY(c, drec.ensure(std::max<size_t>(rec.size() * sizeof(ptmm_record), 16)));
-    HIP_TRY(c, dids.ensure(npix * 4 * n_images));
-    mo.records = drec.as<float4>(), mo.ids = dids.as<int32_t>(), mo.n_objects = motion->n_objects;
-  }
-  DBuf dtris, ddrec, dmesh;  // (a *_deform call's geometry, records and meshes: its own too)
-  DeformCall dc{};
-  size_t tri_bytes = 0;
-  if (deform) {
-    tri_bytes = (size_t)n_images * deform->n_triangles * 96;
-    HIP_TRY(c, dtris.ensure(tri_bytes));
-    HIP_TRY(c, ddrec.ensure(std::max<size_t>(drec_h.size() * sizeof(ptmdf_record), 16)));
-    HIP_TRY(c, dmesh.ensure(std::max<size_t>((size_t)deform->n_meshes * 16, 16)));
-    dc.args.tris_cur = dtris.as<float4>(), dc.args.records = ddrec.as<float4>(), dc.args.meshes = dmesh.as<int32_t>();
-    dc.args.n_tris = deform->n_triangles, dc.args.n_meshes = deform->n_meshes, dc.args.n_transforms = deform->n_transforms;
-    dc.slot = (size_t)deform->n_triangles * 6;
-  }
-  return on_host_images(c, who, colour_sums, layers, npix, n_images, out, dtab, tab_bytes, [&](const float4* col, const float4* lay, float4* res) -> int {
-    HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+  if (motion) HIP_TRY(c, dids.ensure(npix * 4 * n_images));
+  HIP_TRY(c, dtris.ensure(tri_bytes));
+  return on_host_images(c, who, colour_sums, layers, npix, n_images, out, dtab, L.total, [&](const float4* col, const float4* lay, float4* res) -> int {
+    HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), L.total, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(mom.p, moments, bytes, hipMemcpyHostToDevice, c->stream));
+    MotionArgs mo{};
+    DeformCall dc{};
+    table_args(L, n, dtab.p, &mo, &dc.args);
     if (deform) {
       HIP_TRY(c, hipMemcpyAsync(dtris.p, deform->triangles_seq, tri_bytes, hipMemcpyHostToDevice, c->stream));
-      if (!drec_h.empty()) HIP_TRY(c, hipMemcpyAsync(ddrec.p, drec_h.data(), drec_h.size() * sizeof(ptmdf_record), hipMemcpyHostToDevice, c->stream));
-      if (deform->n_meshes) HIP_TRY(c, hipMemcpyAsync(dmesh.p, deform->meshes, (size_t)deform->n_meshes * 16, hipMemcpyHostToDevice, c->stream));
+      dc.args.tris_cur = dtris.as<float4>(), dc.slot = (size_t)deform->n_triangles * 6, dc.args.n_tris = deform->n_triangles, dc.args.n_transforms = deform->n_transforms;
     }
     if (motion) {
-      if (!rec.empty()) HIP_TRY(c, hipMemcpyAsync(drec.p, rec.data(), rec.size() * sizeof(ptmm_record), hipMemcpyHostToDevice, c->stream));
       HIP_TRY(c, hipMemcpyAsync(dids.p, motion->object_ids, npix * 4 * n_images, hipMemcpyHostToDevice, c->stream));
+      mo.ids = dids.as<int32_t>(), mo.n_objects = motion->n_objects;
     }
     if (history_in) {  // image 0 is the view before the first: its state is given, its mean is not made
       HIP_TRY(c, hipMemsetAsync(res, 0, npix * 16, c->stream));
@@ -976,37 +949,37 @@ static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_s
       HIP_TRY(c, hipMemcpyAsync(res + (size_t)2 * n_images * npix, history_in + npix * 4, npix * 16, hipMemcpyHostToDevice, c->stream));
     }
     const uint32_t first = history_in ? 1u : 0u;
-    return accumulate_enqueue(c, col, mom.as<float4>(), lay, res, dtab.p, lambertian != nullptr, n_materials, w, h, n_images, first, n_images - first, history_in != nullptr, k, ka,
-                              per_view ? fuse_tab_frames_ptr(dtab.p, n_images, n_materials) : nullptr, motion ? &mo : nullptr, deform ? &dc : nullptr);
+    return accumulate_enqueue(c, col, mom.as<float4>(), lay, res, table_ptrs(L, dtab.p, lambertian != nullptr), n_materials, w, h, n_images, first, n_images - first,
+                              history_in != nullptr, k, ka, motion ? &mo : nullptr, deform ? &dc : nullptr);
   }, 3, 48);
 }
 int ptmi_accumulate_images(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
                            float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out) {
-  return accumulate_images(c, "ptmi_accumulate_images", colour_sums, moments, layers, views16, w, h, n_images, frame_num, nullptr, false, fov_degrees, lambertian, n_materials, params,
+  return accumulate_images(c, "ptmi_accumulate_images", colour_sums, moments, layers, views16, w, h, n_images, FrameDivisor::of(frame_num), fov_degrees, lambertian, n_materials, params,
                            history_in, out);
 }
 int ptmi_accumulate_images_frames(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
                                   const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
                                   const float* history_in, float* out) {
-  return accumulate_images(c, "ptmi_accumulate_images_frames", colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params,
-                           history_in, out);
+  return accumulate_images(c, "ptmi_accumulate_images_frames", colour_sums, moments, layers, views16, w, h, n_images, FrameDivisor::per_view(frame_nums), fov_degrees, lambertian,
+                           n_materials, params, history_in, out);
 }
 int ptmi_accumulate_images_motion(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
                                   const float* frame_nums, const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian,
                                   uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out) {
-  const MotionImages motion{motions16, n_objects, object_ids};
-  return accumulate_images(c, "ptmi_accumulate_images_motion", colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params,
-                           history_in, out, &motion);
+  const MotionPart motion{motions16, n_objects, object_ids};
+  return accumulate_images(c, "ptmi_accumulate_images_motion", colour_sums, moments, layers, views16, w, h, n_images, FrameDivisor::per_view(frame_nums), fov_degrees, lambertian,
+                           n_materials, params, history_in, out, &motion);
 }
 int ptmi_accumulate_images_deform(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
                                   const float* frame_nums, const float* triangles_seq, uint32_t n_triangles, const float* transforms_seq, uint32_t n_transforms,
                                   const int32_t* meshes, uint32_t n_meshes, const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees,
                                   const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out) {
   if (c && n_objects && !motions16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_accumulate_images_deform: null motions16 with n_objects > 0");
-  const MotionImages motion{motions16, n_objects, object_ids};  // (a null motions16 with n_objects = 0: a static world beside the triangles)
-  const DeformImages deform{triangles_seq, n_triangles, transforms_seq, n_transforms, meshes, n_meshes};
-  return accumulate_images(c, "ptmi_accumulate_images_deform", colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, true, fov_degrees, lambertian, n_materials, params,
-                           history_in, out, motions16 ? &motion : nullptr, &deform);
+  const MotionPart motion{motions16, n_objects, object_ids};  // (a null motions16 with n_objects = 0: a static world beside the triangles)
+  const DeformPart deform{triangles_seq, n_triangles, transforms_seq, n_transforms, meshes, n_meshes};
+  return accumulate_images(c, "ptmi_accumulate_images_deform", colour_sums, moments, layers, views16, w, h, n_images, FrameDivisor::per_view(frame_nums), fov_degrees, lambertian,
+                           n_materials, params, history_in, out, motions16 ? &motion : nullptr, &deform);
 }
 
 int ptmi_denoise_views_accumulated(ptmi_ctx* c, const ptmi_guided_params* params, uint32_t first_view, uint32_t n_views) {
@@ -1019,7 +992,7 @@ int ptmi_denoise_views_accumulated(ptmi_ctx* c, const ptmi_guided_params* params
   const uint32_t n = c->stacks[STACK_ACCUMULATED].n, na = c->stacks[STACK_FEATURES].n;
   if (n != na) return fail(c, PTMI_ERR_STATE, "ptmi_denoise_views_accumulated: the accumulated stack has " + std::to_string(n) + " views, the feature stack " + std::to_string(na));
   if (int r = check_view_range(c, "ptmi_denoise_views_accumulated", first_view, n_views, n)) return r;
-  return atrous_views(c, P, &G, 1.0f, first_view, n_views, true);
+  return atrous_views(c, P, &G, FrameDivisor::of(1.0f), first_view, n_views, true);
 }
 
 int ptmi_denoise_images_accumulated(ptmi_ctx* c, const float* means, const float* plane2, const float* layers, int w, int h, uint32_t n_images, const ptmi_guided_params* params,
