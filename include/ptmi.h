@@ -761,7 +761,8 @@ int ptmi_motions_from_transforms(const float* prev32, const float* cur32, uint32
  * (k_accumulate_view_deform, csrc/ptmi_accumulate_kernels.h, a fourth entry beside the three the other calls keep launching) and the host reference both compile.
  * A camera that moves WITH a mesh (every vertex and the camera translated by T per view) has q = p and wgt exactly 1 on it: n after k such one-frame views is k.
  *
- * OUT OF SCOPE: fusion through deformation (it needs this stack and no composed matrices); meshes whose triangle count or order changes between views (a build, or
+ * For fusion through deformation see "FUSION THROUGH DEFORMING MESHES" below: it reads this stack and composes no matrices.
+ * OUT OF SCOPE: meshes whose triangle count or order changes between views (a build, or
  * an upload without a refit); an object test at q; lighting that changed between the views; multi-device contexts. */
 #define PTMI_GEOMETRY_MAX_BYTES (1ull << 34) /* 16 GiB: some 190 views of an 871 k-triangle scene.  The stack is ONE allocation beside the context's six image
                                                 stacks and is sized by an argument (n_views), not by the scene alone: a mistaken count is to be refused by name
@@ -825,7 +826,8 @@ int ptmi_deform_records(const float* prev32, const float* cur32, uint32_t n_tran
  * validity, normal, depth against r of X') and the output.  The operation order is in include/ptmi_fuse.h and include/ptmi_motion.h and nowhere else.  A camera that
  * moves WITH an object (both translated by T per view, G the translation by -T) has q = p and weight exactly 1 in every window view on that object.
  *
- * OUT OF SCOPE: an object test at q (as for accumulation); deforming meshes; multi-device or sharded contexts (PTMI_ERR_UNSUPPORTED, as the siblings); lighting that
+ * A path through deforming meshes is fused by "FUSION THROUGH DEFORMING MESHES" below.
+ * OUT OF SCOPE: an object test at q (as for accumulation); multi-device or sharded contexts (PTMI_ERR_UNSUPPORTED, as the siblings); lighting that
  * changed between the views — fusion averages radiance across time, as accumulation does. */
 /* ptmi_fuse_views_frames with motions.  Writes the same FUSED STACK: ptmi_read_fused, ptmi_resolve_fused_rgba8, ptmi_fused_device_ptr and ptmi_release_fused work on
  * its result.  source 0 reads the view stack with frame_nums per view; source 1 reads the denoised stack: frame_nums is then ignored and may be NULL, every count is
@@ -848,6 +850,58 @@ int ptmi_fuse_reference_motion(const float* colour, const float* layers, const f
  * [n_objects][16] (bottom rows 0 0 0 1).  from_view == to_view gives exact identities.  The steps between the two views are the entries read; a refused step or a
  * refused composition gives PTMI_ERR_INVALID_ARG, as does a view >= n_views. */
 int ptmi_compose_motions(const float* motions16, uint32_t n_views, uint32_t n_objects, uint32_t from_view, uint32_t to_view, float* motions16_out);
+
+/* FUSION THROUGH DEFORMING MESHES (per-vertex motion).  "FUSION WITH PER-OBJECT MOTION" follows an object through matrices composed across the window; a skinned or
+ * morphing mesh has none, and fusion carries its pixels up to eight views away: the point lands on another material point, or the depth and normal tests reject
+ * it.  The calls below are ptmi_fuse_views_motion and its *_images / *_reference forms with "ACCUMULATION THROUGH DEFORMING MESHES"' barycentric carry for triangle
+ * pixels, through THE GEOMETRY STACK of that section; they change only what is said here.  A triangle has the same barycentric coordinates in every slot, so nothing
+ * is composed: a pixel goes straight from its triangle in slot v to the same triangle in slot u.
+ *
+ * WHICH PIXELS is "ACCUMULATION THROUGH DEFORMING MESHES"', unchanged, every index checked; the mesh word is slot v's.  EVERY OTHER PIXEL is handled exactly as
+ * ptmi_fuse_views_motion handles it, through motions16 / n_objects, where n_objects = 0 with a null motions16 means a static world beside the mesh.
+ *
+ * THE RECORD is per (view, transform), not per pair: the affine part of model, then the affine part of invModel, column after column AS STORED — nothing is inverted
+ * —, six float4 (include/ptmi_fuse_deform.h, ptmfd_record).  The host makes it once per call for every view the call READS: the slots
+ * max(0, first_view - R) .. min(n_stack - 1, first_view + n_views - 1 + R); slots outside that may be uncaptured.  An element that is not finite gives
+ * PTMI_ERR_INVALID_ARG naming the view and the object.  At most PTMI_MOTION_MAX_RECORDS records (views read x n_transforms).
+ *
+ * PER DEFORM PIXEL, ONCE, from invModel_v and the triangle of slot v: steps 1 - 3 of "ACCUMULATION THROUGH DEFORMING MESHES" (x; den, b, c, a with their refusals)
+ * and the slot-v half of step 5 (m; t = invModel_v^T m; s = t . n(p)).  PER NEIGHBOUR u, from the triangle of slot u, model_u and the 3x3 of invModel_u: step 4 (x', X')
+ * and the rest of step 5 (m', k, len with its refusal, n' negated when s < 0).  No f32 operation order is added: every operation and its operand order is that
+ * section's, and for u = v-1 the result and the refusal are the accumulation call's bit for bit.
+ * STATIC SHORTCUT, per neighbour: the host makes a MOVED MASK per (output view, transform), bit s set when the object's 128-byte transform in slot u = v + s - R is not
+ * bytewise equal to the one in slot v (slots outside the stack, and s = R, clear).  When the bit is clear and the 18 position and normal words of the triangle are
+ * bitwise equal in slots v and u, that neighbour runs ptmi_fuse_views_frames' arithmetic bit for bit.  ORDER per neighbour: the static shortcut is tested; if it does
+ * not apply and the per-pixel part was refused, the neighbour is skipped; otherwise the per-neighbour part runs and the neighbour is skipped if len is refused.  A
+ * pixel whose barycentrics are refused and whose geometry moved everywhere is fused from its own view alone.  Unchanged: the ascending order of u, the own view in
+ * its place, the tests at q and the output.
+ *
+ * OUT OF SCOPE: meshes whose triangle count or order changes between views; an object or triangle test at q; lighting that changed between the views; multi-device
+ * or sharded contexts (PTMI_ERR_UNSUPPORTED, as the siblings). */
+/* ptmi_fuse_views_motion through the geometry stack (k_fuse_deform, csrc/ptmi_fuse_kernels.h, a fourth entry beside the three the other calls keep launching).  Writes
+ * the same FUSED STACK, so the ptmi_read_fused family works on its result; source 1 reads the denoised stack, as the sibling does.  Errors and their order are
+ * ptmi_fuse_views_motion's (a null motions16 is allowed with n_objects = 0); then, after frame_nums' checks: no geometry stack, a stack whose view count differs from
+ * the view stack's, a stack whose triangle or transform count differs from the scene's now, a slot it reads that was never captured (naming the view):
+ * PTMI_ERR_STATE; then the records' and the motions' checks.  Asynchronous on the context's stream, one launch; all memory is obtained before anything is enqueued,
+ * and a failing call leaves the fused stack as it found it. */
+int ptmi_fuse_views_deform(ptmi_ctx* ctx, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects,
+                           int source, uint32_t first_view, uint32_t n_views);
+/* The kernel on host arrays, and the host reference (no GPU; weight_out as ptmi_fuse_reference_motion's; `threads` > 1 share the rows of a view and change no bit):
+ * ptmi_fuse_images_motion / ptmi_fuse_reference_motion with the geometry itself — triangles_seq [n_images][n_triangles][24] (n_triangles >= 1), transforms_seq
+ * [n_images][n_transforms][32], meshes [n_meshes][4] i32; a table whose count is 0 may be NULL — and motions16 / object_ids for the pixels that are no deform pixels
+ * (motions16 NULL with n_objects = 0: a static world, object_ids is then not read).  Argument rules are ptmi_accumulate_images_deform's.  Every image's geometry is
+ * read: each lies in some output image's window. */
+int ptmi_fuse_images_deform(ptmi_ctx* ctx, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
+                            const float* triangles_seq, uint32_t n_triangles, const float* transforms_seq, uint32_t n_transforms, const int32_t* meshes, uint32_t n_meshes,
+                            const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
+                            const ptmi_fuse_params* params, float* out);
+int ptmi_fuse_reference_deform(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
+                               const float* triangles_seq, uint32_t n_triangles, const float* transforms_seq, uint32_t n_transforms, const int32_t* meshes, uint32_t n_meshes,
+                               const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
+                               const ptmi_fuse_params* params, float* out, float* weight_out, int threads);
+/* No GPU: THE RECORD (above) of every transform of ONE view, transforms32 (n_transforms x 32 f32), as the calls make them, into records_out [n_transforms][24]
+ * 32-bit words (include/ptmi_fuse_deform.h, ptmfd_record).  PTMI_ERR_INVALID_ARG with the object in *bad_object (may be NULL) where an element read is not finite. */
+int ptmi_fuse_deform_records(const float* transforms32, uint32_t n_transforms, uint32_t* records_out, uint32_t* bad_object);
 
 /* Test hook, no GPU: the SLOT TABLE ptmi_render_views_frames and ptmi_render_aov_frames upload behind the call's view matrices, u32 words:
  *   words [4 v .. 4 v + 3], v < n_views   view v's record {first slot, frame count, first frame number, next view with a non-zero count or n_views}; a view with

@@ -64,7 +64,7 @@ DEV void deform_loaded(const float4& c0, const float4& c1, const float4& c2, con
   asm volatile("" ::"v"(p0.x), "v"(p0.y), "v"(p0.z), "v"(p1.x), "v"(p1.y), "v"(p1.z), "v"(p2.x), "v"(p2.y), "v"(p2.z), "v"(p3.x), "v"(p3.y), "v"(p3.z), "v"(p4.x), "v"(p4.y),
                "v"(p4.z), "v"(p5.x), "v"(p5.y), "v"(p5.z));
 }
-DEV void deform_put(float* T, int i, const float4& a) { T[4 * i] = a.x, T[4 * i + 1] = a.y, T[4 * i + 2] = a.z, T[4 * i + 3] = a.w; }
+// (deform_put: ptmi_fuse_kernels.h)
 
 // The deformation of pixel idx's triangle on its world point X and on the normal in gw (ptmdf_move); 0: nothing is taken over.  A pixel that takes the static
 // shortcut leaves both; a pixel that is no deform pixel (include/ptmi_deform.h, WHICH PIXELS) is accumulate_move's.

@@ -6,12 +6,14 @@
 // The parts, in the table's order, and what the layout guarantees of each:
 //   views       kFuseRow float4 per view of the stack (fuse_pack_row)                                          read as float4: starts on 16 bytes
 //   motion      the *_motion calls' records, ptmm_record (six float4) each, in the order the call's kernel reads them      read as float4: starts on 16 bytes
-//   deform      the *_deform call's records, ptmdf_record (nine float4) each                                   read as float4: starts on 16 bytes
+//   deform      the accumulation *_deform call's records, ptmdf_record (nine float4) each                      read as float4: starts on 16 bytes
+//   fuse_deform the fusion *_deform call's per-view records, ptmfd_record (six float4) each, [view read][transform]           read as float4: starts on 16 bytes
 //   frames      the *_frames calls' divisors, one f32 per view of the stack                                    starts on 4 bytes
 //   sphere_obj, quad_obj, mesh_obj   one i32 object id per sphere, quad and mesh of the uploaded scene         start on 4 bytes
-//   meshes      the *_deform call's mesh table, i32 words (four per mesh)                                      starts on 4 bytes
+//   meshes      the *_deform calls' mesh table, i32 words (four per mesh)                                      starts on 4 bytes
+//   moved       the fusion *_deform call's moved masks, one u32 per (output view of the call, transform)       starts on 4 bytes
 //   materials   one byte per material index, 1 = fuses: max(16, n_materials) bytes, zero-filled, so that it can be read with n_materials = 0
-// A part that a call does not have has length 0; its offset is still inside [0, total], though nothing is read there.  No part is padded: the three kinds of float4
+// A part that a call does not have has length 0; its offset is still inside [0, total], though nothing is read there.  No part is padded: the four kinds of float4
 // part come first and each is a whole number of float4 long, the words follow, the bytes are last, so every start is aligned by what lies before it.
 #pragma once
 #include <algorithm>
@@ -21,6 +23,7 @@
 
 #include "../../include/ptmi_deform.h"
 #include "../../include/ptmi_fuse.h"
+#include "../../include/ptmi_fuse_deform.h"
 #include "../../include/ptmi_motion.h"
 
 namespace ptmi {
@@ -36,27 +39,31 @@ struct CallTableCounts {
   uint32_t n_spheres = 0, n_quads = 0, n_meshes = 0;  // the id tables' entries
   size_t deform_records = 0;
   size_t mesh_words = 0;
+  size_t fuse_deform_records = 0;  // ptmi_fuse_views_deform / ptmi_fuse_images_deform: views read x transforms
+  size_t moved_words = 0;          // ... and output views x transforms
 };
 
 struct CallTable {
   struct Part {
     size_t at = 0, bytes = 0;
   };
-  Part views, motion, deform, frames, sphere_obj, quad_obj, mesh_obj, meshes, materials;
+  Part views, motion, deform, fuse_deform, frames, sphere_obj, quad_obj, mesh_obj, meshes, moved, materials;
   size_t total = 0;
 
   CallTable() = default;
   explicit CallTable(const CallTableCounts& n) {
-    static_assert(sizeof(ptmm_record) == 96 && sizeof(ptmdf_record) == 144, "records are whole float4");
+    static_assert(sizeof(ptmm_record) == 96 && sizeof(ptmdf_record) == 144 && sizeof(ptmfd_record) == 96, "records are whole float4");
     auto put = [this](Part& p, size_t bytes) { p.at = total, p.bytes = bytes, total += bytes; };
     put(views, (size_t)n.n_views * kFuseRow * 16);
     put(motion, n.motion_records * sizeof(ptmm_record));
     put(deform, n.deform_records * sizeof(ptmdf_record));
+    put(fuse_deform, n.fuse_deform_records * sizeof(ptmfd_record));
     put(frames, n.frames ? (size_t)n.n_views * 4 : 0);
     put(sphere_obj, (size_t)n.n_spheres * 4);
     put(quad_obj, (size_t)n.n_quads * 4);
     put(mesh_obj, (size_t)n.n_meshes * 4);
     put(meshes, n.mesh_words * 4);
+    put(moved, n.moved_words * 4);
     put(materials, std::max<size_t>(16, n.n_materials));
   }
   // Where part p lies in the copy of the table at `tab`, host or device
@@ -120,6 +127,24 @@ inline void call_table_fill_object_ids(const CallTable& L, void* tab, const floa
 inline void call_table_fill_meshes(const CallTable& L, void* tab, const int32_t* mesh_words) {
   if (L.meshes.bytes) memcpy(L.ptr<int32_t>(tab, L.meshes), mesh_words, L.meshes.bytes);
 }
-// (the records are made straight into their parts, L.ptr<ptmm_record>(tab, L.motion) and L.ptr<ptmdf_record>(tab, L.deform), by the calls' own makers)
+// The fusion *_deform call's two parts from the transforms of the whole stack, n_transforms x 32 f32 per slot from tf0 = slot 0 (slots outside [lo, hi] are not
+// read): the records of views [lo, hi], view after view, and the moved masks of output views [first, first + n) (include/ptmi_fuse_deform.h).  tab = nullptr: the
+// checks alone.  Returns -1, or (view << 32 | transform) of the first transform with an element that is not finite (the parts are then unfinished).
+inline int64_t call_table_fill_fuse_deform(const CallTable& L, void* tab, const float* tf0, uint32_t n_transforms, uint32_t n_all, uint32_t lo, uint32_t hi, uint32_t first,
+                                           uint32_t n, uint32_t radius) {
+  ptmfd_record unkept;
+  ptmfd_record* rec = tab ? L.ptr<ptmfd_record>(tab, L.fuse_deform) : nullptr;
+  for (uint32_t v = lo; v <= hi; v++)
+    for (uint32_t o = 0; o < n_transforms; o++)
+      if (!ptmfd_make_record(tf0 + PTMDF_TRANSFORM_WORDS * ((size_t)v * n_transforms + o), rec ? &rec[(size_t)(v - lo) * n_transforms + o] : &unkept))
+        return (int64_t)(((uint64_t)v << 32) | o);
+  if (!tab) return -1;
+  uint32_t* moved = L.ptr<uint32_t>(tab, L.moved);
+  for (uint32_t v = first; v < first + n; v++)
+    for (uint32_t o = 0; o < n_transforms; o++)  // (v's window, clipped to the stack, lies inside [lo, hi]: no slot outside it is compared)
+      moved[(size_t)(v - first) * n_transforms + o] = ptmfd_moved_mask(tf0, n_transforms, n_all, v, o, radius);
+  return -1;
+}
+// (the other records are made straight into their parts, L.ptr<ptmm_record>(tab, L.motion) and L.ptr<ptmdf_record>(tab, L.deform), by the calls' own makers)
 
 }  // namespace ptmi

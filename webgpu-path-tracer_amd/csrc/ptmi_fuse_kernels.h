@@ -17,9 +17,20 @@
 //          six float4 PER LANE (the object varies within a wave) from the table [v - first][u - v + R][n_objects], fenced into one round trip — and moves a COPY of
 //          the point and of the normal.  u, its row and its count stay wave-uniform.  That round trip stands in front of the projection's four gathers for a moving
 //          pixel; the other two entries compile none of it.
+// k_fuse_deform  The motion body with DEFORMATION (ptmi_fuse_views_deform, include/ptmi_fuse_deform.h).  A lane whose I names a triangle whose index counts gathers
+//          that triangle from geometry slot v ONCE — six float4 under one fence —, from the mesh word it now holds the mesh's transform index (4 bytes), then the
+//          record of (v, transform) and the moved-mask word of (v, transform) together, and runs the per-pixel part: a, b, c and s stay in registers, and so do the
+//          18 position and normal words of slot v, which the static test of every neighbour compares.  Per neighbour u the triangle of slot u lies at the same offset
+//          u x n_triangles x 6 and the record of (u, transform) at an address known before the loop (u is wave-uniform: both bases are scalar), so the lane issues ONE
+//          group of twelve independent 16-byte loads under one fence — also for a neighbour that then turns out static, whose record is read and not used: the
+//          record is shared by every lane of the transform, so it costs a cache hit, where testing the triangle first would put a second round trip in front of
+//          every neighbour whose vertices moved under a transform at rest, the skinned mesh's usual case.  A neighbour whose mask bit is set while the per-pixel part
+//          was refused loads nothing.  Then the projection's four gathers: two round trips per neighbour, as in k_fuse_motion.  Every other lane takes the motion
+//          entry's path.  No LDS, no atomics (profiles/fuse_deform_kernel_resources.txt).
 #pragma once
 
 #include "../../include/ptmi_fuse.h"
+#include "../../include/ptmi_fuse_deform.h"
 #include "ptmi_call_table.h"  // kFuseRow and fuse_pack_row: a view's row of the table, host side
 #include "ptmi_denoise_kernels.h"
 #include "ptmi_motion_kernels.h"
@@ -49,15 +60,43 @@ DEV void fuse_loaded(const float4& S, const float4& N, const float4& A, const fl
   asm volatile("" ::"v"(S.x), "v"(S.y), "v"(S.z), "v"(S.w), "v"(N.x), "v"(N.y), "v"(N.z), "v"(N.w), "v"(A.x), "v"(A.y), "v"(A.z), "v"(A.w), "v"(I.z));
 }
 
+// What k_fuse_deform has beside the motion entry's operands.  tris: slot 0 of the geometry, the triangles (six float4 each) of view u `slot` float4 further per view;
+// records: [view - lo][n_transforms] ptmfd_record (six float4 each) of the views the call reads, lo the first of them; moved: [blockIdx.z][n_transforms] masks;
+// meshes: 4 i32 per mesh.
+struct FuseDeformArgs {
+  const float4* tris;
+  size_t slot;
+  const float4* records;
+  const uint32_t* moved;
+  const int32_t* meshes;
+  uint32_t lo, n_tris, n_meshes, n_transforms;
+};
+
+DEV void deform_put(float* T, int i, const float4& a) { T[4 * i] = a.x, T[4 * i + 1] = a.y, T[4 * i + 2] = a.z, T[4 * i + 3] = a.w; }
+DEV void fuse_deform_record(ptmfd_record& R, const float4& r0, const float4& r1, const float4& r2, const float4& r3, const float4& r4, const float4& r5) {
+  deform_put(R.mp, 0, r0), deform_put(R.mp, 1, r1), deform_put(R.mp, 2, r2), deform_put(R.ic, 0, r3), deform_put(R.ic, 1, r4), deform_put(R.ic, 2, r5);
+}
+// Keeps the six loads of one slot's triangle together: every word that is read is an operand here (w: the mesh word, read of slot v alone)
+DEV void fuse_deform_loaded(const float4& c0, const float4& c1, const float4& c2, const float4& c3, const float4& c4, const float4& c5) {
+  asm volatile("" ::"v"(c0.x), "v"(c0.y), "v"(c0.z), "v"(c1.x), "v"(c1.y), "v"(c1.z), "v"(c2.x), "v"(c2.y), "v"(c2.z), "v"(c3.x), "v"(c3.y), "v"(c3.z), "v"(c4.x), "v"(c4.y),
+               "v"(c4.z), "v"(c5.x), "v"(c5.y), "v"(c5.z), "v"(c5.w));
+}
+// ... and a whole record's six (motion_loaded fences the 22 words of a ptmm_record: here all 24 are read)
+DEV void fuse_deform_record_loaded(const float4& r0, const float4& r1, const float4& r2, const float4& r3, const float4& r4, const float4& r5) {
+  motion_loaded(r0, r1, r2, r3, r4, r5);
+  asm volatile("" ::"v"(r5.z), "v"(r5.w));
+}
+
 // colour: [n_stack][npix] float4 (sums, or means with k.F = 1); layers: [n_stack][3][npix] float4; out: [n_stack][npix] float4; tab: kFuseRow float4 per view of the
 // stack; lamb: one byte per material index or nullptr.  grid: x = (tiles of 64 columns x rows) / 4, z = output view - view0; block 256.
 // FRAMES: frames [n_stack] f32, F_u of every view of the stack; k.F is then not read: p and the output take F_v, a neighbour's q takes F_u — u is wave-uniform, so the
 // count comes through a scalar load as the view's row does.
 // MOTION: mo.records = the composed records of output view view0 (slot [blockIdx.z][u - v + radius]), mo.ids = the id images of the whole stack or nullptr; every
-// other instance is handed an empty one and reads none of it.
-template <bool FRAMES, bool MOTION = false>
+// other instance is handed an empty one and reads none of it.  DEFORM (with MOTION): de as above, moved = the masks of output view view0; likewise.
+template <bool FRAMES, bool MOTION = false, bool DEFORM = false>
 DEV void fuse_view(const float4* __restrict__ colour, const float4* __restrict__ layers, float4* __restrict__ out, const float4* __restrict__ tab, const uint8_t* __restrict__ lamb,
-                   uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k, const float* __restrict__ frames, const MotionArgs& mo = MotionArgs{}) {
+                   uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k, const float* __restrict__ frames, const MotionArgs& mo = MotionArgs{},
+                   const FuseDeformArgs& de = FuseDeformArgs{}) {
   const uint32_t tiles_x = ((uint32_t)W + 63u) / 64u;
   const uint32_t tile = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);  // wave-uniform
   const uint32_t y = tile / tiles_x;
@@ -82,11 +121,42 @@ DEV void fuse_view(const float4* __restrict__ colour, const float4* __restrict__
     ptmf_world(&k, &V, x, idx, gp.w, X);
     const float4* rec = nullptr;  // MOTION: the records of p's object in the slot of u = v - radius ...
     uint32_t moving = 0;          // ... and the mask of the slots whose record is not the identity: 0 for a static pixel
+    // DEFORM: a deform pixel (include/ptmi_deform.h, WHICH PIXELS) holds its triangle of slot v, the per-pixel part's result and the moved mask of its transform
+    [[maybe_unused]] bool deform = false;
+    [[maybe_unused]] int carried = 0;  // the per-pixel part was not refused
+    [[maybe_unused]] uint32_t moved = 0;
+    [[maybe_unused]] float Tc[24];
+    [[maybe_unused]] ptmfd_pixel px;
+    [[maybe_unused]] const float4 *tri0 = nullptr, *rec0 = nullptr;  // the triangle in slot 0, the transform's record of view de.lo
+    if constexpr (DEFORM) {
+      uint32_t prim, tf;
+      if (ptmdf_prim(dn_f4(Ip), de.n_tris, &prim)) {
+        tri0 = de.tris + 6 * (size_t)prim;
+        const float4* tc = tri0 + (size_t)v * de.slot;
+        const float4 c0 = tc[0], c1 = tc[1], c2 = tc[2], c3 = tc[3], c4 = tc[4], c5 = tc[5];  // six independent gathers
+        fuse_deform_loaded(c0, c1, c2, c3, c4, c5);
+        if (ptmdf_transform(c5.w, de.meshes, de.n_meshes, de.n_transforms, &tf)) {
+          deform = true;
+          rec0 = de.records + 6 * (size_t)tf;
+          const float4* rp = rec0 + (size_t)(v - de.lo) * de.n_transforms * 6;
+          const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3], r4 = rp[4], r5 = rp[5];  // the record and the mask word: one round trip
+          moved = de.moved[(size_t)blockIdx.z * de.n_transforms + tf];
+          fuse_deform_record_loaded(r0, r1, r2, r3, r4, r5);
+          asm volatile("" ::"v"(moved));
+          deform_put(Tc, 0, c0), deform_put(Tc, 1, c1), deform_put(Tc, 2, c2), deform_put(Tc, 3, c3), deform_put(Tc, 4, c4), deform_put(Tc, 5, c5);
+          ptmfd_record Rv;
+          fuse_deform_record(Rv, r0, r1, r2, r3, r4, r5);
+          carried = ptmfd_pixel_part(&Rv, Tc, X, &gp, &px);
+        }
+      }
+    }
     if constexpr (MOTION) {
-      const int32_t obj = motion_object(mo, mo.ids ? mo.ids + (size_t)v * npix : nullptr, idx, Ip);
-      if (ptmm_has_record(obj, mo.n_objects)) {
-        rec = mo.records + ((size_t)blockIdx.z * (2u * (uint32_t)k.radius + 1u) * mo.n_objects + (uint32_t)obj) * 6;
-        moving = __float_as_uint(rec[(size_t)k.radius * mo.n_objects * 6 + 5].z);  // ptmm_record::pad[0] of the own-view slot
+      if (!DEFORM || !deform) {
+        const int32_t obj = motion_object(mo, mo.ids ? mo.ids + (size_t)v * npix : nullptr, idx, Ip);
+        if (ptmm_has_record(obj, mo.n_objects)) {
+          rec = mo.records + ((size_t)blockIdx.z * (2u * (uint32_t)k.radius + 1u) * mo.n_objects + (uint32_t)obj) * 6;
+          moving = __float_as_uint(rec[(size_t)k.radius * mo.n_objects * 6 + 5].z);  // ptmm_record::pad[0] of the own-view slot
+        }
       }
     }
     const uint32_t u0 = v > (uint32_t)k.radius ? v - (uint32_t)k.radius : 0u;
@@ -102,6 +172,25 @@ DEV void fuse_view(const float4* __restrict__ colour, const float4* __restrict__
       float r;
       float Xu[3] = {X[0], X[1], X[2]};
       ptmd_f4 gu = gp;  // (gu's normal is read by the sample alone)
+      if constexpr (DEFORM) {
+        if (deform) {
+          const uint32_t bit = (moved >> (u + (uint32_t)k.radius - v)) & 1u;
+          if (bit && !carried) continue;  // (no static shortcut, and nothing to carry: nothing is loaded)
+          const float4 *tu = tri0 + (size_t)u * de.slot, *ru = rec0 + (size_t)(u - de.lo) * de.n_transforms * 6;
+          const float4 t0 = tu[0], t1 = tu[1], t2 = tu[2], t3 = tu[3], t4 = tu[4], t5 = tu[5], r0 = ru[0], r1 = ru[1], r2 = ru[2], r3 = ru[3], r4 = ru[4],
+                       r5 = ru[5];  // twelve independent loads, one round trip
+          fuse_deform_loaded(t0, t1, t2, t3, t4, t5);
+          fuse_deform_record_loaded(r0, r1, r2, r3, r4, r5);
+          float Tu[24];
+          deform_put(Tu, 0, t0), deform_put(Tu, 1, t1), deform_put(Tu, 2, t2), deform_put(Tu, 3, t3), deform_put(Tu, 4, t4), deform_put(Tu, 5, t5);
+          if (bit || !ptmdf_static(Tc, Tu)) {
+            if (!carried) continue;
+            ptmfd_record Ru;
+            fuse_deform_record(Ru, r0, r1, r2, r3, r4, r5);
+            if (!ptmfd_neighbour_part(&px, &Ru, Tu, Xu, &gu)) continue;
+          }
+        }
+      }
       if constexpr (MOTION) {
         const uint32_t slot = u + (uint32_t)k.radius - v;
         if ((moving >> slot) & 1u) {
@@ -145,6 +234,13 @@ __global__ __launch_bounds__(kBlock) void k_fuse_motion(const float4* __restrict
                                                         const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k,
                                                         const float* __restrict__ frames, MotionArgs mo) {
   fuse_view<true, true>(colour, layers, out, tab, lamb, n_materials, W, H, n_stack, view0, k, frames, mo);
+}
+
+// k_fuse_motion with the geometry of every view of the window (ptmi_fuse_views_deform, ptmi_fuse_images_deform)
+__global__ __launch_bounds__(kBlock) void k_fuse_deform(const float4* __restrict__ colour, const float4* __restrict__ layers, float4* __restrict__ out, const float4* __restrict__ tab,
+                                                        const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k,
+                                                        const float* __restrict__ frames, MotionArgs mo, FuseDeformArgs de) {
+  fuse_view<true, true, true>(colour, layers, out, tab, lamb, n_materials, W, H, n_stack, view0, k, frames, mo, de);
 }
 
 }  // namespace ptmi

@@ -26,6 +26,7 @@
 #include "../../include/ptmi_motion.h"
 #include "../../include/ptmi_fuse_motion.h"
 #include "../../include/ptmi_deform.h"
+#include "../../include/ptmi_fuse_deform.h"
 #include "../../include/ptmi_noise.h"
 #include "ptmi_bvh_domain.h"
 
@@ -944,15 +945,26 @@ extern "C" void ptmi_default_fuse_params(ptmi_fuse_params* p) {
 // threaded or reordered.  frame_nums: nullptr, or every image's own divisor (ptmi_fuse_reference_frames): view v's p and output take F_v, a neighbour's q takes F_u.
 // motion: nullptr, or the motions and the id images of ptmi_fuse_reference_motion: a pixel whose object has a composed record (include/ptmi_fuse_motion.h) for the
 // neighbour that is not the identity moves a copy of the point and of the normal (include/ptmi_motion.h) for that neighbour; every other pixel runs what it ran.
+// deform: nullptr, or the geometry of ptmi_fuse_reference_deform: a triangle pixel whose indices count is carried from its triangle in image v to the same triangle in
+// every image u of its window (include/ptmi_fuse_deform.h) unless that neighbour takes the static shortcut; every other pixel is `motion`'s, which may then be nullptr
+// (a static world).  `threads` > 1 share the rows of a view, whose pixels do not depend on one another.
 // weight_out: nullptr, or [n_images][h][w]: den of every fused pixel, 0 where the pixel passes through.
 struct ReferenceMotion {  // (accumulate_reference's too)
   const float* motions16;  // [n_images][n_objects][16]
   uint32_t n_objects;
   const int32_t* object_ids;  // [n_images][h][w]
 };
+struct ReferenceDeform {  // (accumulate_reference's too)
+  const float* triangles_seq;   // [n_images][n_triangles][24]
+  uint32_t n_triangles;
+  const float* transforms_seq;  // [n_images][n_transforms][32]
+  uint32_t n_transforms;
+  const int32_t* meshes;  // [n_meshes][4]
+  uint32_t n_meshes;
+};
 static int fuse_reference(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, const float* frame_nums,
                           float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out,
-                          const ReferenceMotion* motion = nullptr, float* weight_out = nullptr) {
+                          const ReferenceMotion* motion = nullptr, float* weight_out = nullptr, const ReferenceDeform* deform = nullptr, int threads = 1) {
   if (!colour || !layers || !views16 || !out || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
   ptmi_fuse_params P;
   if (params) P = *params;
@@ -983,16 +995,36 @@ static int fuse_reference(const float* colour, const float* layers, const float*
     if (!rec.empty() && !ptmfm_compose_table(motion->motions16, n_images, motion->n_objects, 0, n_images, (uint32_t)P.radius, rec.data(), &kind, &bv, &bu, &bo))
       return PTMI_ERR_INVALID_ARG;
   }
+  std::vector<ptmfd_record> drec;  // [image][n_transforms]: every image is in some output view's window
+  std::vector<uint32_t> dmoved;    // [image][n_transforms]
+  if (deform) {
+    if (!deform->triangles_seq || !deform->n_triangles || (deform->n_transforms && !deform->transforms_seq) || (deform->n_meshes && !deform->meshes) ||
+        (uint64_t)n_images * deform->n_transforms > (uint64_t)PTMI_MOTION_MAX_RECORDS)
+      return PTMI_ERR_INVALID_ARG;
+    try {
+      drec.resize((size_t)n_images * deform->n_transforms);
+      dmoved.resize((size_t)n_images * deform->n_transforms);
+    } catch (const std::bad_alloc&) {
+      return PTMI_ERR_NO_MEMORY;
+    }
+    for (uint32_t v = 0; v < n_images; v++)
+      for (uint32_t o = 0; o < deform->n_transforms; o++) {
+        if (!ptmfd_make_record(deform->transforms_seq + 32 * ((size_t)v * deform->n_transforms + o), &drec[(size_t)v * deform->n_transforms + o])) return PTMI_ERR_INVALID_ARG;
+        dmoved[(size_t)v * deform->n_transforms + o] = ptmfd_moved_mask(deform->transforms_seq, deform->n_transforms, n_images, v, o, (uint32_t)P.radius);
+      }
+  }
   ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   const size_t npix = (size_t)w * (size_t)h;
   const ptmd_f4* S = reinterpret_cast<const ptmd_f4*>(colour);
   const ptmd_f4* L = reinterpret_cast<const ptmd_f4*>(layers);
   ptmd_f4* O = reinterpret_cast<ptmd_f4*>(out);
+  const unsigned nt = (unsigned)std::max(1, std::min(std::min(threads, 64), h));
   for (uint32_t v = 0; v < n_images; v++) {
     if (frame_nums) k.F = frame_nums[v];
     const ptmd_f4* Lv = L + (size_t)v * 3 * npix;
     const uint32_t u0 = v > (uint32_t)P.radius ? v - (uint32_t)P.radius : 0u, u1 = std::min(n_images - 1u, v + (uint32_t)P.radius);
-    for (int y = 0; y < h; y++)
+    auto rows = [&](unsigned t) {
+    for (int y = (int)(((size_t)h * t) / nt), y1 = (int)(((size_t)h * (t + 1)) / nt); y < y1; y++)
       for (int x = 0; x < w; x++) {
         const uint32_t idx = (uint32_t)y * (uint32_t)w + (uint32_t)x;
         const ptmd_f4 Sp = S[(size_t)v * npix + idx], Ap = Lv[npix + idx];
@@ -1003,7 +1035,19 @@ static int fuse_reference(const float* colour, const float* layers, const float*
           float X[3];
           ptmf_world(&k, &tab[v], x, idx, gp.w, X);
           const ptmm_record* R0 = nullptr;  // the records of p's object in the slot of u = v - radius; nullptr: a static pixel
-          if (motion) {
+          const float* Tc = nullptr;        // a deform pixel's triangle in image v; nullptr: no deform pixel
+          uint32_t prim = 0, tf = 0, moved = 0;
+          ptmfd_pixel px;
+          int carried = 0;  // the per-pixel part was not refused
+          if (deform && ptmdf_prim(Lv[2 * npix + idx], deform->n_triangles, &prim)) {
+            const float* T = deform->triangles_seq + 24 * ((size_t)v * deform->n_triangles + prim);
+            if (ptmdf_transform(T[23], deform->meshes, deform->n_meshes, deform->n_transforms, &tf)) {
+              Tc = T;
+              moved = dmoved[(size_t)v * deform->n_transforms + tf];
+              carried = ptmfd_pixel_part(&drec[(size_t)v * deform->n_transforms + tf], Tc, X, &gp, &px);
+            }
+          }
+          if (motion && !Tc) {
             const int32_t obj = motion->object_ids[(size_t)v * npix + idx];
             if (ptmm_has_record(obj, motion->n_objects)) R0 = &rec[(size_t)v * span * motion->n_objects + (uint32_t)obj];
           }
@@ -1016,6 +1060,12 @@ static int fuse_reference(const float* colour, const float* layers, const float*
             float r;
             float Xu[3] = {X[0], X[1], X[2]};
             ptmd_f4 gu = gp;  // (gu's normal is read by the sample alone)
+            if (Tc) {
+              const float* Tu = deform->triangles_seq + 24 * ((size_t)u * deform->n_triangles + prim);
+              if (((moved >> (u + (uint32_t)P.radius - v)) & 1u) || !ptmdf_static(Tc, Tu)) {
+                if (!carried || !ptmfd_neighbour_part(&px, &drec[(size_t)u * deform->n_transforms + tf], Tu, Xu, &gu)) continue;
+              }
+            }
             if (R0) {
               const ptmm_record* R = R0 + (size_t)(u + (uint32_t)P.radius - v) * motion->n_objects;
               if (!R->identity && !ptmm_move(R, Xu, &gu)) continue;
@@ -1031,6 +1081,9 @@ static int fuse_reference(const float* colour, const float* layers, const float*
         O[(size_t)v * npix + idx] = ptmf_output(&k, Sp, Ap, fused, num, den);
         if (weight_out) weight_out[(size_t)v * npix + idx] = fused ? den : 0.0f;
       }
+    };
+    if (nt == 1) rows(0);
+    else if (!run_workers(nt, rows)) return PTMI_ERR_NO_MEMORY;
   }
   return PTMI_OK;
 }
@@ -1049,6 +1102,31 @@ extern "C" int ptmi_fuse_reference_motion(const float* colour, const float* laye
   if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
   const ReferenceMotion motion{motions16, n_objects, object_ids};
   return fuse_reference(colour, layers, views16, w, h, n_images, 1.0f, frame_nums, fov_degrees, lambertian, n_materials, params, out, &motion, weight_out);
+}
+extern "C" int ptmi_fuse_reference_deform(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
+                                          const float* triangles_seq, uint32_t n_triangles, const float* transforms_seq, uint32_t n_transforms, const int32_t* meshes,
+                                          uint32_t n_meshes, const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees,
+                                          const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out, float* weight_out, int threads) {
+  if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
+  if (n_objects && !motions16) return PTMI_ERR_INVALID_ARG;
+  const ReferenceMotion motion{motions16, n_objects, object_ids};
+  const ReferenceDeform deform{triangles_seq, n_triangles, transforms_seq, n_transforms, meshes, n_meshes};
+  return fuse_reference(colour, layers, views16, w, h, n_images, 1.0f, frame_nums, fov_degrees, lambertian, n_materials, params, out, motions16 ? &motion : nullptr, weight_out,
+                        &deform, threads);  // (a null motions16 with n_objects = 0: every pixel that is no deforming triangle's is static)
+}
+// One view's records (include/ptmi_fuse_deform.h, ptmfd_make_record) as the fusion *_deform calls make them: records_out [n_transforms][24] words.
+// PTMI_ERR_INVALID_ARG with the object in *bad_object (may be NULL): one of the elements its record takes is not finite.
+extern "C" int ptmi_fuse_deform_records(const float* transforms32, uint32_t n_transforms, uint32_t* records_out, uint32_t* bad_object) {
+  if (!transforms32 || !records_out) return PTMI_ERR_INVALID_ARG;
+  for (uint32_t o = 0; o < n_transforms; o++) {
+    ptmfd_record R;
+    if (!ptmfd_make_record(transforms32 + 32 * (size_t)o, &R)) {
+      if (bad_object) *bad_object = o;
+      return PTMI_ERR_INVALID_ARG;
+    }
+    memcpy(records_out + 24 * (size_t)o, &R, sizeof R);
+  }
+  return PTMI_OK;
 }
 // The composed motions of one (from, to) pair of views (include/ptmi_fuse_motion.h): what the fusion calls put into their table for that pair, as f32 matrices.
 extern "C" int ptmi_compose_motions(const float* motions16, uint32_t n_views, uint32_t n_objects, uint32_t from_view, uint32_t to_view, float* motions16_out) {
@@ -1076,14 +1154,6 @@ extern "C" void ptmi_default_accumulate_params(ptmi_accumulate_params* p) {
 // that is not the identity moves the point and the normal (include/ptmi_motion.h); every other pixel runs what it ran.
 // deform: nullptr, or the geometry of ptmi_accumulate_reference_deform: a triangle pixel whose indices count is carried from its triangle in image v to the same
 // triangle in image v-1 (include/ptmi_deform.h) unless it takes the static shortcut; every other pixel is `motion`'s, which may then be nullptr (a static world).
-struct ReferenceDeform {
-  const float* triangles_seq;   // [n_images][n_triangles][24]
-  uint32_t n_triangles;
-  const float* transforms_seq;  // [n_images][n_transforms][32]
-  uint32_t n_transforms;
-  const int32_t* meshes;  // [n_meshes][4]
-  uint32_t n_meshes;
-};
 static int accumulate_reference(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
                                 const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
                                 const float* history_in, float* out, int threads, const ReferenceMotion* motion = nullptr, const ReferenceDeform* deform = nullptr) {

@@ -69,6 +69,7 @@ FN(ptmi_accumulate_views_motion)
 FN(ptmi_accumulate_views_deform)
 FN(ptmi_capture_view_geometry)
 FN(ptmi_fuse_views_motion)
+FN(ptmi_fuse_views_deform)
 FN(ptmi_read_moments)
 FN(ptmi_release_moments)
 FN(ptmi_default_noise_params)
@@ -128,7 +129,7 @@ static int load_lib(char* err, size_t errlen) {
   LOAD(ptmi_version) LOAD(ptmi_last_error) LOAD(ptmi_create) LOAD(ptmi_create_multi) LOAD(ptmi_prepare) LOAD(ptmi_destroy) LOAD(ptmi_default_params) LOAD(ptmi_default_denoise_params) LOAD(ptmi_set_params)
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
   LOAD(ptmi_render_views_frames) LOAD(ptmi_render_aov_frames) LOAD(ptmi_render_views_until_each)
-  LOAD(ptmi_views_device_ptr) LOAD(ptmi_denoise_views_frames) LOAD(ptmi_denoise_views_guided_frames) LOAD(ptmi_fuse_views_frames) LOAD(ptmi_accumulate_views_frames) LOAD(ptmi_accumulate_views_motion) LOAD(ptmi_accumulate_views_deform) LOAD(ptmi_capture_view_geometry) LOAD(ptmi_fuse_views_motion)
+  LOAD(ptmi_views_device_ptr) LOAD(ptmi_denoise_views_frames) LOAD(ptmi_denoise_views_guided_frames) LOAD(ptmi_fuse_views_frames) LOAD(ptmi_accumulate_views_frames) LOAD(ptmi_accumulate_views_motion) LOAD(ptmi_accumulate_views_deform) LOAD(ptmi_capture_view_geometry) LOAD(ptmi_fuse_views_motion) LOAD(ptmi_fuse_views_deform)
   LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_default_guided_params) LOAD(ptmi_denoise_views_guided) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_default_accumulate_params) LOAD(ptmi_accumulate_views) LOAD(ptmi_read_accumulated) LOAD(ptmi_release_accumulated) LOAD(ptmi_denoise_views_accumulated) LOAD(ptmi_set_view_moments) LOAD(ptmi_read_moments) LOAD(ptmi_release_moments) LOAD(ptmi_default_noise_params) LOAD(ptmi_view_noise_stats) LOAD(ptmi_render_views_until) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
   LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_check_bvh_boxes) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah) LOAD(ptmi_refit_scene_bvh)
   LOAD(ptmi_obj_parse) LOAD(ptmi_free) LOAD(ptmi_device_count) LOAD(ptmi_reduce_info)
@@ -723,13 +724,13 @@ static napi_value js_fuse_views_frames(napi_env env, napi_callback_info info) { 
 
 /* fuseViewsMotion(ctx, views, Float32Array frameNums | null, Float32Array motions, nObjects, source, firstView, nViews, params | null): ptmi_fuse_views_motion —
  * motions holds 16 floats per view OF THE STACK and object, [view][object][16]; frameNums may be null with source 1 (the denoised stack), which does not read it */
-static napi_value js_fuse_views_motion(napi_env env, napi_callback_info info) {
+static napi_value fuse_views_motion_common(napi_env env, napi_callback_info info, int deform) {
   napi_value a[9];
   if (get_args(env, info, 9, a)) return NULL;
   ptmi_ctx* c = ctx_of(env, a[0]);
   if (!c) return NULL;
-  void *data, *mdata;
-  size_t len, mlen;
+  void *data, *mdata = NULL;
+  size_t len, mlen = 0;
   if (typed(env, a[1], napi_float32_array, "fuseViewsMotion(views)", &data, &len)) return NULL;
   if (len == 0 || len % 16 != 0) {
     napi_throw_range_error(env, NULL, "fuseViewsMotion: views must hold 16 floats for each view of the stack, one view at least");
@@ -740,7 +741,9 @@ static napi_value js_fuse_views_motion(napi_env env, napi_callback_info info) {
   CHECK_NAPI(napi_typeof(env, a[2], &ft));
   if (ft != napi_null && ft != napi_undefined)
     if (frame_nums_arg(env, c, a[2], "fuseViewsMotion(frameNums)", &frame_nums)) return NULL;
-  if (typed(env, a[3], napi_float32_array, "fuseViewsMotion(motions)", &mdata, &mlen)) return NULL;
+  napi_valuetype mt = napi_undefined;
+  napi_typeof(env, a[3], &mt);
+  if (!(deform && (mt == napi_null || mt == napi_undefined)) && typed(env, a[3], napi_float32_array, "fuseViewsMotion(motions)", &mdata, &mlen)) return NULL;
   uint32_t n_objects, first, n_views;
   int32_t source = 0;
   CHECK_NAPI(napi_get_value_uint32(env, a[4], &n_objects));
@@ -758,10 +761,14 @@ static napi_value js_fuse_views_motion(napi_env env, napi_callback_info info) {
                                        {"sigmaDepth", 0, offsetof(ptmi_fuse_params, sigma_depth)},
                                        {"albedoFloor", 0, offsetof(ptmi_fuse_params, albedo_floor)}};
   CHECK_PARAMS(a[8], fields, &P, "fuseViewsMotion")
-  int st = p_ptmi_fuse_views_motion(c, &P, (const float*)data, frame_nums, (const float*)mdata, n_objects, source, first, n_views);
-  if (st) return throw_status(env, c, st, "ptmi_fuse_views_motion");
+  int st = (deform ? p_ptmi_fuse_views_deform : p_ptmi_fuse_views_motion)(c, &P, (const float*)data, frame_nums, (const float*)mdata, n_objects, source, first, n_views);
+  if (st) return throw_status(env, c, st, deform ? "ptmi_fuse_views_deform" : "ptmi_fuse_views_motion");
   return NULL;
 }
+static napi_value js_fuse_views_motion(napi_env env, napi_callback_info info) { return fuse_views_motion_common(env, info, 0); }
+/* fuseViewsDeform(ctx, views, frameNums | null, Float32Array motions | null, nObjects, source, firstView, nViews, params | null): ptmi_fuse_views_deform —
+ * fuseViewsMotion through the geometry stack (captureViewGeometry); motions null with nObjects 0: a static world beside the deforming triangles */
+static napi_value js_fuse_views_deform(napi_env env, napi_callback_info info) { return fuse_views_motion_common(env, info, 1); }
 
 /* accumulateViews(ctx, views, frameNum, firstView, nViews, resume, params | null): ptmi_accumulate_views — views holds the matrices of ALL views of the stack; params =
  * {maxHistory, minFrames, sigmaNormal, sigmaDepth, albedoFloor}, every field optional (ptmi_default_accumulate_params fills the rest) */
@@ -1408,7 +1415,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"version", js_version}, {"create", js_create}, {"destroy", js_destroy}, {"defaultParams", js_default_params}, {"setParams", js_set_params},
       {"upload", js_upload}, {"resize", js_resize}, {"clear", js_clear}, {"setShard", js_set_shard}, {"renderFrame", js_render_frame},
       {"renderViewsFrames", js_render_views_frames}, {"renderAovFrames", js_render_aov_frames}, {"renderViewsUntilEach", js_render_views_until_each},
-      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"denoiseViewsGuided", js_denoise_views_guided}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"accumulateViews", js_accumulate_views}, {"readAccumulated", js_read_accumulated}, {"releaseAccumulated", js_release_accumulated}, {"denoiseViewsAccumulated", js_denoise_views_accumulated}, {"denoiseViewsFrames", js_denoise_views_frames}, {"denoiseViewsGuidedFrames", js_denoise_views_guided_frames}, {"fuseViewsFrames", js_fuse_views_frames}, {"accumulateViewsFrames", js_accumulate_views_frames}, {"accumulateViewsMotion", js_accumulate_views_motion}, {"accumulateViewsDeform", js_accumulate_views_deform}, {"captureViewGeometry", js_capture_view_geometry}, {"fuseViewsMotion", js_fuse_views_motion}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"refitSceneBVH", js_refit_scene_bvh}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
+      {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"denoiseViewsGuided", js_denoise_views_guided}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"accumulateViews", js_accumulate_views}, {"readAccumulated", js_read_accumulated}, {"releaseAccumulated", js_release_accumulated}, {"denoiseViewsAccumulated", js_denoise_views_accumulated}, {"denoiseViewsFrames", js_denoise_views_frames}, {"denoiseViewsGuidedFrames", js_denoise_views_guided_frames}, {"fuseViewsFrames", js_fuse_views_frames}, {"accumulateViewsFrames", js_accumulate_views_frames}, {"accumulateViewsMotion", js_accumulate_views_motion}, {"accumulateViewsDeform", js_accumulate_views_deform}, {"captureViewGeometry", js_capture_view_geometry}, {"fuseViewsMotion", js_fuse_views_motion}, {"fuseViewsDeform", js_fuse_views_deform}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"refitSceneBVH", js_refit_scene_bvh}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
       {"resolveRGBA8", js_resolve}, {"setCounters", js_set_counters}, {"setTiming", js_set_timing}, {"stats", js_stats},
       {"resetStats", js_reset_stats}, {"buildBVH", js_build_bvh}, {"buildBVHSAH", js_build_bvh_sah}, {"buildBVHDevice", js_build_bvh_device}, {"parseObj", js_parse_obj},
       {"deviceCount", js_device_count}, {"reduceInfo", js_reduce_info},

@@ -424,7 +424,11 @@ static TablePtrs table_ptrs(const CallTable& L, const void* dev, bool has_lamb) 
   return {L.ptr<float4>(dev, L.views), has_lamb ? L.ptr<uint8_t>(dev, L.materials) : nullptr, L.frames.bytes ? L.ptr<float>(dev, L.frames) : nullptr};
 }
 // ... and what the *_motion and *_deform kernels take of it beside (n: the counts L was made from).  A part of length 0 gives a pointer that is not read.
-static void table_args(const CallTable& L, const CallTableCounts& n, const void* dev, MotionArgs* mo, DeformArgs* de) {
+static void table_args(const CallTable& L, const CallTableCounts& n, const void* dev, MotionArgs* mo, DeformArgs* de, FuseDeformArgs* fd = nullptr) {
+  if (fd) {
+    fd->records = L.ptr<float4>(dev, L.fuse_deform), fd->moved = L.ptr<uint32_t>(dev, L.moved), fd->meshes = L.ptr<int32_t>(dev, L.meshes);
+    fd->n_meshes = (uint32_t)(n.mesh_words / 4);
+  }
   mo->records = L.ptr<float4>(dev, L.motion);
   mo->sphere_obj = L.ptr<int32_t>(dev, L.sphere_obj), mo->quad_obj = L.ptr<int32_t>(dev, L.quad_obj), mo->mesh_obj = L.ptr<int32_t>(dev, L.mesh_obj);
   mo->n_spheres = n.n_spheres, mo->n_quads = n.n_quads, mo->n_meshes = n.n_meshes;
@@ -442,15 +446,22 @@ static uint32_t first_view_with_history(uint32_t first, bool resume) { return re
 // written; t: the table's parts (table_ptrs).  One launch; more only where n exceeds the grid's z limit.
 // t.frames: the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_fuse_frames.
 // motion (with t.frames): nullptr, or k_fuse_motion's operands, records = the composed records of view `first` (fuse_motion_table: their order).
+// deform (with t.frames and motion, whose n_objects may be 0: a static world beside the triangles): k_fuse_deform's operands, moved = the masks of view `first`.
 static int fuse_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, const TablePtrs& t, uint32_t n_materials, int W, int H, uint32_t n_stack,
-                        uint32_t first, uint32_t n, const ptmf_consts& k, const MotionArgs* motion = nullptr) {
+                        uint32_t first, uint32_t n, const ptmf_consts& k, const MotionArgs* motion = nullptr, const FuseDeformArgs* deform = nullptr) {
   const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
   const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
   for (uint32_t v0 = 0; v0 < n; v0 += 65535u) {
     const uint32_t nv = std::min(65535u, n - v0);
     const dim3 grid(gx, 1, nv);
     auto shared = [&](auto launch) { launch(colour, layers, out, t.rows, t.lamb, n_materials, W, H, n_stack, first + v0, k); };  // what every entry takes: its own operands follow
-    if (motion) {
+    if (deform) {
+      MotionArgs mo = *motion;
+      mo.records += (size_t)v0 * (2u * (uint32_t)k.radius + 1u) * mo.n_objects * 6;
+      FuseDeformArgs de = *deform;
+      de.moved += (size_t)v0 * de.n_transforms;
+      shared([&](auto... a) { hipLaunchKernelGGL(k_fuse_deform, grid, dim3(kBlock), 0, c->stream, a..., t.frames, mo, de); });
+    } else if (motion) {
       MotionArgs mo = *motion;
       mo.records += (size_t)v0 * (2u * (uint32_t)k.radius + 1u) * mo.n_objects * 6;
       shared([&](auto... a) { hipLaunchKernelGGL(k_fuse_motion, grid, dim3(kBlock), 0, c->stream, a..., t.frames, mo); });
@@ -506,9 +517,30 @@ static int fuse_motion_table(ptmi_ctx* c, const char* who, const float* motions1
                                            ", has a non-finite element or a 3x3 with a zero or non-finite determinant");
 }
 
-// ptmi_fuse_views, ptmi_fuse_views_frames (the view stack as source) and ptmi_fuse_views_motion (motion: its motions16 [n_views of the stack][n_objects][16])
+// The fusion *_deform calls: the per-view records and the moved masks (include/ptmi_fuse_deform.h) of a call over output views [first, first + n) of n_all views,
+// radius R, from the transforms tf0 = slot 0, n_transforms x 32 f32 per slot.  tab = nullptr: the checks that need no room alone.  Allocates nothing.
+static int fuse_deform_parts(ptmi_ctx* c, const char* who, const CallTable& L, void* tab, const float* tf0, uint32_t n_transforms, uint32_t n_all, uint32_t first, uint32_t n,
+                             uint32_t R) {
+  uint32_t lo, hi;
+  ptmfd_read_range(n_all, first, n, R, &lo, &hi);
+  if ((uint64_t)(hi - lo + 1u) * n_transforms > (uint64_t)PTMI_MOTION_MAX_RECORDS)
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": " + std::to_string(hi - lo + 1u) + " views x " + std::to_string(n_transforms) + " transforms are more than PTMI_MOTION_MAX_RECORDS records");
+  const int64_t bad = call_table_fill_fuse_deform(L, tab, tf0, n_transforms, n_all, lo, hi, first, n, R);
+  if (bad < 0) return PTMI_OK;
+  const uint32_t bv = (uint32_t)((uint64_t)bad >> 32), bo = (uint32_t)((uint64_t)bad & 0xffffffffu);
+  return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the transform of view " + std::to_string(bv) + ", object " + std::to_string(bo) + ", has an element that is not finite: view " +
+                                           std::to_string(bv) + " is read by this call");
+}
+static void fuse_deform_counts(CallTableCounts* n, uint32_t n_transforms, uint32_t n_all, uint32_t first, uint32_t n_out, uint32_t R, size_t mesh_words) {
+  uint32_t lo, hi;
+  ptmfd_read_range(n_all, first, n_out, R, &lo, &hi);
+  n->fuse_deform_records = (size_t)(hi - lo + 1u) * n_transforms, n->moved_words = (size_t)n_out * n_transforms, n->mesh_words = mesh_words;
+}
+
+// ptmi_fuse_views, ptmi_fuse_views_frames (the view stack as source), ptmi_fuse_views_motion (motion: its motions16 [n_views of the stack][n_objects][16]) and
+// ptmi_fuse_views_deform (deform: the context's geometry stack, with motion, whose motions16 may then be null with n_objects = 0)
 static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* params, const float* views16, FrameDivisor F, int source, uint32_t first_view, uint32_t n_views,
-                      const MotionPart* motion = nullptr) {
+                      const MotionPart* motion = nullptr, const DeformPart* deform = nullptr) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   if (!views16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   if (source != 0 && source != 1) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": source must be 0 (the view stack) or 1 (the denoised stack)");
@@ -518,6 +550,9 @@ static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* para
   // has that part, all ones (fill_views_and_frames with no frame_nums).
   if (motion && source == 1) F = FrameDivisor::of(1.0f);
   if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
+  static const float no_motions[16] = {};
+  MotionPart still{no_motions, 0, nullptr};
+  if (deform && !motion->motions16 && motion->n_objects == 0) motion = &still;  // (a static world beside the triangles: no entry is read)
   if (motion && !motion->motions16) return fuse_motion_table(c, who, nullptr, 0, 0, 0, 0, 0, nullptr);
   if (int r = check_source_stacks(c, who, source == 1, first_view, n_views)) return r;
   const uint32_t n_stack = c->stacks[STACK_VIEWS].n, R = (uint32_t)P.radius;
@@ -525,6 +560,20 @@ static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* para
   if (int r = check_frame_nums(c, who, F, first_view > R ? first_view - R : 0u, (uint32_t)std::min<uint64_t>(n_stack, (uint64_t)first_view + n_views + R))) return r;
   CallTableCounts n = scene_table_counts(c, motion != nullptr);
   n.frames = F.each || motion;
+  const ptmi_ctx::GeometryStack& g = c->geometry;
+  if (deform) {  // the geometry the call reads: the slots of its range widened by the radius
+    if (!g.n_views) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no geometry stack: ptmi_capture_view_geometry makes it, view by view");
+    if (g.n_views != n_stack) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry stack has " + std::to_string(g.n_views) + " views, the view stack " + std::to_string(n_stack));
+    if (g.n_tris != c->n_tris_uploaded || g.n_xforms != c->h_xforms.size() / 32)
+      return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry stack holds " + std::to_string(g.n_tris) + " triangles and " + std::to_string(g.n_xforms) + " transforms, the scene now " +
+                                         std::to_string(c->n_tris_uploaded) + " and " + std::to_string(c->h_xforms.size() / 32));
+    uint32_t lo, hi;
+    ptmfd_read_range(n_stack, first_view, n_views, R, &lo, &hi);
+    for (uint32_t v = lo; v <= hi; v++)
+      if (!g.captured[v]) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry of view " + std::to_string(v) + " was never captured: view " + std::to_string(v) + " is read by this call");
+    if (int r = fuse_deform_parts(c, who, CallTable(), nullptr, g.h_xforms.data(), (uint32_t)g.n_xforms, n_stack, first_view, n_views, R)) return r;
+    fuse_deform_counts(&n, (uint32_t)g.n_xforms, n_stack, first_view, n_views, R, c->h_meshes.size());
+  }
   if (motion) {
     if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_stack, first_view, n_views, R, nullptr)) return r;
     n.motion_records = fuse_motion_count(motion->n_objects, n_views, R);
@@ -532,6 +581,8 @@ static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* para
   const CallTable L(n);
   std::vector<uint8_t> tab;
   if (int r = alloc_table(c, who, L, &tab)) return r;
+  if (deform)
+    if (int r = fuse_deform_parts(c, who, L, tab.data(), g.h_xforms.data(), (uint32_t)g.n_xforms, n_stack, first_view, n_views, R)) return r;
   if (motion)
     if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_stack, first_view, n_views, R, L.ptr<ptmm_record>(tab.data(), L.motion))) return r;
   if (int r = fill_views_and_frames(c, who, L, tab.data(), views16, F.frame_nums)) return r;
@@ -539,11 +590,22 @@ static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* para
   if (int r = make_stack_with_table(c, who, STACK_FUSED, tab.data(), L.total)) return r;
   MotionArgs mo{};
   DeformArgs none{};
-  table_args(L, n, c->fuse_tab.dev.p, &mo, &none);
+  FuseDeformArgs fd{};
+  table_args(L, n, c->fuse_tab.dev.p, &mo, &none, &fd);
+  if (deform) {
+    fd.tris = g.tris.as<float4>(), fd.slot = g.n_tris * 6, fd.n_tris = (uint32_t)g.n_tris, fd.n_transforms = (uint32_t)g.n_xforms;
+    fd.lo = first_view > R ? first_view - R : 0u;
+  }
   if (motion) mo.n_objects = motion->n_objects, mo.tris = c->d_tris.as<float>(), mo.n_tris = (uint32_t)c->n_tris_uploaded;  // (the triangles are on the device already)
   const ptmf_consts k = ptmf_make_consts(c->W, c->H, context_fov_factor(c), source == 0 ? F.frame_num : 1.0f, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   return fuse_enqueue(c, c->stacks[source == 0 ? STACK_VIEWS : STACK_DENOISED].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(), c->stacks[STACK_FUSED].buf.as<float4>(),
-                      table_ptrs(L, c->fuse_tab.dev.p, true), n.n_materials, c->W, c->H, n_stack, first_view, n_views, k, motion ? &mo : nullptr);
+                      table_ptrs(L, c->fuse_tab.dev.p, true), n.n_materials, c->W, c->H, n_stack, first_view, n_views, k, motion ? &mo : nullptr, deform ? &fd : nullptr);
+}
+int ptmi_fuse_views_deform(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects, int source,
+                           uint32_t first_view, uint32_t n_views) {
+  const MotionPart motion{motions16, n_objects, nullptr};
+  const DeformPart deform{};
+  return fuse_views(c, "ptmi_fuse_views_deform", params, views16, FrameDivisor::per_view(frame_nums), source, first_view, n_views, &motion, &deform);
 }
 int ptmi_fuse_views_motion(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects, int source,
                            uint32_t first_view, uint32_t n_views) {
@@ -564,10 +626,15 @@ int ptmi_resolve_fused_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t by
 int ptmi_fused_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) { return stack_device_ptr(c, STACK_FUSED, "ptmi_fused_device_ptr", nullptr, p, bytes, n_views); }
 int ptmi_release_fused(ptmi_ctx* c) { return release_stack(c, STACK_FUSED); }
 
-// ptmi_fuse_images, ptmi_fuse_images_frames (F's frame_nums: one per image) and ptmi_fuse_images_motion (motion)
+// ptmi_fuse_images, ptmi_fuse_images_frames (F's frame_nums: one per image), ptmi_fuse_images_motion (motion) and ptmi_fuse_images_deform (deform; motion may then
+// be nullptr)
 static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const FrameDivisor& F,
-                       float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out, const MotionPart* motion = nullptr) {
+                       float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out, const MotionPart* motion = nullptr,
+                       const DeformPart* deform = nullptr) {
   if (!c || !colour || !layers || !views16 || !out || (motion && !motion->object_ids)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (deform && (!deform->triangles_seq || (deform->n_transforms && !deform->transforms_seq) || (deform->n_meshes && !deform->meshes)))
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (deform && deform->n_triangles == 0) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": no triangles");
   ptmi_fuse_params P;
   if (int r = fuse_check_args(c, who, params, F.frame_num, true, &P)) return r;
   if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
@@ -577,6 +644,10 @@ static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const 
   if (!lambertian) n_materials = 0;
   CallTableCounts n;
   n.n_views = n_images, n.n_materials = n_materials, n.frames = F.each;
+  if (deform) {
+    if (int r = fuse_deform_parts(c, who, CallTable(), nullptr, deform->transforms_seq, deform->n_transforms, n_images, 0, n_images, (uint32_t)P.radius)) return r;
+    fuse_deform_counts(&n, deform->n_transforms, n_images, 0, n_images, (uint32_t)P.radius, (size_t)deform->n_meshes * 4);
+  }
   if (motion) {
     if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_images, 0, n_images, (uint32_t)P.radius, nullptr)) return r;
     n.motion_records = fuse_motion_count(motion->n_objects, n_images, (uint32_t)P.radius);
@@ -584,29 +655,51 @@ static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const 
   const CallTable L(n);
   std::vector<uint8_t> tab;
   if (int r = alloc_table(c, who, L, &tab)) return r;
+  if (deform) {
+    if (int r = fuse_deform_parts(c, who, L, tab.data(), deform->transforms_seq, deform->n_transforms, n_images, 0, n_images, (uint32_t)P.radius)) return r;
+    call_table_fill_meshes(L, tab.data(), deform->meshes);
+  }
   if (motion)
     if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_images, 0, n_images, (uint32_t)P.radius, L.ptr<ptmm_record>(tab.data(), L.motion))) return r;
   if (int r = fill_views_and_frames(c, who, L, tab.data(), views16, F.frame_nums)) return r;
   call_table_fill_materials(L, tab.data(), lambertian, n_materials);
   const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), F.frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   const size_t npix = (size_t)w * (size_t)h;
-  DBuf dtab, dids;  // (a *_motion call's id images are its own, had before anything is enqueued)
-  if (motion) {
+  const size_t tri_bytes = deform ? (size_t)n_images * deform->n_triangles * 96 : 0;
+  DBuf dtab, dids, dtris;  // (a *_motion call's id images and a *_deform call's triangle sequence are its own, had before anything is enqueued)
+  if (motion || deform) {
     HIP_TRY(c, hipSetDevice(c->device));
     (void)hipGetLastError();
-    HIP_TRY(c, dids.ensure(npix * 4 * n_images));
+    if (motion) HIP_TRY(c, dids.ensure(npix * 4 * n_images));
+    HIP_TRY(c, dtris.ensure(tri_bytes));
   }
   return on_host_images(c, who, colour, layers, npix, n_images, out, dtab, L.total, [&](const float4* col, const float4* lay, float4* res) -> int {
     HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), L.total, hipMemcpyHostToDevice, c->stream));
     MotionArgs mo{};
     DeformArgs none{};
-    table_args(L, n, dtab.p, &mo, &none);
+    FuseDeformArgs fd{};
+    table_args(L, n, dtab.p, &mo, &none, &fd);
     if (motion) {
       mo.ids = dids.as<int32_t>(), mo.n_objects = motion->n_objects;
       HIP_TRY(c, hipMemcpyAsync(dids.p, motion->object_ids, npix * 4 * n_images, hipMemcpyHostToDevice, c->stream));
     }
-    return fuse_enqueue(c, col, lay, res, table_ptrs(L, dtab.p, lambertian != nullptr), n_materials, w, h, n_images, 0, n_images, k, motion ? &mo : nullptr);
+    if (deform) {
+      HIP_TRY(c, hipMemcpyAsync(dtris.p, deform->triangles_seq, tri_bytes, hipMemcpyHostToDevice, c->stream));
+      fd.tris = dtris.as<float4>(), fd.slot = (size_t)deform->n_triangles * 6, fd.n_tris = deform->n_triangles, fd.n_transforms = deform->n_transforms, fd.lo = 0;
+    }
+    return fuse_enqueue(c, col, lay, res, table_ptrs(L, dtab.p, lambertian != nullptr), n_materials, w, h, n_images, 0, n_images, k, motion || deform ? &mo : nullptr,
+                        deform ? &fd : nullptr);
   });
+}
+int ptmi_fuse_images_deform(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
+                            const float* triangles_seq, uint32_t n_triangles, const float* transforms_seq, uint32_t n_transforms, const int32_t* meshes, uint32_t n_meshes,
+                            const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,
+                            const ptmi_fuse_params* params, float* out) {
+  if (c && n_objects && !motions16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_fuse_images_deform: null motions16 with n_objects > 0");
+  const MotionPart motion{motions16, n_objects, object_ids};  // (a null motions16 with n_objects = 0: a static world beside the triangles)
+  const DeformPart deform{triangles_seq, n_triangles, transforms_seq, n_transforms, meshes, n_meshes};
+  return fuse_images(c, "ptmi_fuse_images_deform", colour, layers, views16, w, h, n_images, FrameDivisor::per_view(frame_nums), fov_degrees, lambertian, n_materials, params, out,
+                     motions16 ? &motion : nullptr, &deform);
 }
 int ptmi_fuse_images_motion(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
                             const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials,

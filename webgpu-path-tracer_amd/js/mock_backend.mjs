@@ -38,5 +38,6 @@ export class MockBackend {
   captureViewGeometry(view, nViews) { this.calls.push(['captureViewGeometry', view, nViews]); }
   accumulateViewsDeform(views, frameNums, motions, nObjects, firstView, nViews, resume = false, params = null) { this.calls.push(['accumulateViewsDeform', views.length / 16, Array.from(frameNums), motions ? motions.length / 16 : null, nObjects, firstView, nViews, !!resume, params]); }
   fuseViewsMotion(views, frameNums, motions, nObjects, source, firstView, nViews, params = null) { this.calls.push(['fuseViewsMotion', views.length / 16, frameNums ? Array.from(frameNums) : null, motions.length / 16, nObjects, source, firstView, nViews, params]); }
+  fuseViewsDeform(views, frameNums, motions, nObjects, source, firstView, nViews, params = null) { this.calls.push(['fuseViewsDeform', views.length / 16, frameNums ? Array.from(frameNums) : null, motions ? motions.length / 16 : null, nObjects, source, firstView, nViews, params]); }
   synchronize() {}
 }

@@ -109,6 +109,11 @@ export class Ptmi {
   fuseViewsMotion(views, frameNums, motions, nObjects, source, firstView, nViews, params = null) {
     this.native.fuseViewsMotion(this.h, views, frameNums == null ? null : Float32Array.from(frameNums), motions, nObjects, source, firstView, nViews, params);
   }
+  // ptmi_fuse_views_deform: fuseViewsMotion through the geometry stack — a triangle pixel is carried from its triangle in view v to the same triangle in every view
+  // of its window; motions (null with nObjects 0: a static world) serve every other pixel
+  fuseViewsDeform(views, frameNums, motions, nObjects, source, firstView, nViews, params = null) {
+    this.native.fuseViewsDeform(this.h, views, frameNums == null ? null : Float32Array.from(frameNums), motions, nObjects, source, firstView, nViews, params);
+  }
   synchronize() { this.native.synchronize(this.h); }
   prepare() { this.native.prepare(this.h); }
   buildSceneBVHSAH() { this.native.buildSceneBVHSAH(this.h); }   // the same with the reference's never-called SAH builder (lib/BVH/bvhNode.js:108-283): opt-in

@@ -42,6 +42,7 @@ SYMBOLS = [
     "ptmi_fuse_views_motion", "ptmi_fuse_images_motion", "ptmi_fuse_reference_motion", "ptmi_compose_motions",
     "ptmi_accumulate_images_deform", "ptmi_accumulate_reference_deform", "ptmi_deform_records",
     "ptmi_capture_view_geometry", "ptmi_read_view_geometry", "ptmi_geometry_device_ptr", "ptmi_release_geometry", "ptmi_accumulate_views_deform",
+    "ptmi_fuse_views_deform", "ptmi_fuse_images_deform", "ptmi_fuse_reference_deform", "ptmi_fuse_deform_records",
 ]
 
 MOTION_MAX_RECORDS = 1 << 20  # PTMI_MOTION_MAX_RECORDS
@@ -298,6 +299,12 @@ def load_library(build=False, path=None):
         L.ptmi_fuse_images_motion.argtypes = [vp, fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, ctypes.c_float, fp, u32, up, fp]
         L.ptmi_fuse_reference_motion.argtypes = [fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, ctypes.c_float, fp, u32, up, fp, fp]
         L.ptmi_compose_motions.argtypes = [fp, u32, u32, u32, u32, fp]
+    if hasattr(L, "ptmi_fuse_views_deform"):  # (an older A/B build loaded through PTMI_LIB fuses no deforming mesh)
+        up = ctypes.POINTER(FuseParams)
+        L.ptmi_fuse_views_deform.argtypes = [vp, up, fp, fp, fp, u32, i32, u32, u32]
+        L.ptmi_fuse_images_deform.argtypes = [vp, fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, u32, fp, u32, fp, u32, fp, ctypes.c_float, fp, u32, up, fp]
+        L.ptmi_fuse_reference_deform.argtypes = [fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, u32, fp, u32, fp, u32, fp, ctypes.c_float, fp, u32, up, fp, fp, i32]
+        L.ptmi_fuse_deform_records.argtypes = [fp, u32, fp, fp]
     if hasattr(L, "ptmi_accumulate_images_deform"):  # (an older A/B build loaded through PTMI_LIB knows rigid motions alone)
         ap = ctypes.POINTER(AccumulateParams)
         L.ptmi_accumulate_images_deform.argtypes = [vp, fp, fp, fp, fp, i32, i32, u32, fp, fp, u32, fp, u32, fp, u32, fp, u32, fp, ctypes.c_float, fp, u32, ap, fp, fp]
@@ -645,6 +652,37 @@ def fuse_reference_motion(colour, layers, views, frame_nums, motions, object_ids
     if st != 0:
         raise PtmiError(st, "ptmi_fuse_reference_motion failed")
     return (out, wgt) if want_weight else out
+
+
+def fuse_reference_deform(colour, layers, views, frame_nums, triangles_seq, transforms_seq, meshes, motions=None, object_ids=None, fov_degrees=60.0, lambertian=None,
+                          params=None, want_weight=False, threads=1, n_objects=None, lib=None):
+    """ptmi_fuse_reference_deform: fuse_reference_motion through a world whose meshes DEFORM — triangles_seq (n, n_triangles, 24), transforms_seq (n, n_transforms, 32)
+    and meshes (n_meshes, 4) int32 as accumulate_reference_deform takes them.  A triangle pixel whose indices count is carried from its triangle in image v to the
+    same triangle in every image of its window; every other pixel goes through motions / object_ids as fuse_reference_motion's do (both None: a static world).
+    want_weight: also return (n, H, W) float32, the summed weight of every fused pixel.  threads > 1 share a view's rows and change no bit."""
+    c, l, v, t, out = _fuse_arrays(colour, layers, views, lambertian)
+    f = _frame_nums(frame_nums, c.shape[0])
+    g, n_obj, ids = _motion_arrays(motions, object_ids, c.shape[0], c.shape[1:3])
+    geo, keep = _deform_arrays(triangles_seq, transforms_seq, meshes, c.shape[0])
+    wgt = np.empty(c.shape[:3], np.float32) if want_weight else None
+    st = (lib or load_library()).ptmi_fuse_reference_deform(_ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), *geo, _optr(g),
+                                                            n_obj if n_objects is None else n_objects, _optr(ids), float(fov_degrees), _optr(t), 0 if t is None else t.size,
+                                                            None if params is None else ctypes.byref(params), _ptr(out), _optr(wgt), int(threads))
+    if st != 0:
+        raise PtmiError(st, "ptmi_fuse_reference_deform failed")
+    return (out, wgt) if want_weight else out
+
+
+def fuse_deform_records(transforms, lib=None):
+    """ptmi_fuse_deform_records: the records the fusion *_deform calls make for ONE view, (n_transforms, 24) uint32 words (include/ptmi_fuse_deform.h, ptmfd_record),
+    from that view's transform table (n_transforms, 32).  PtmiError naming the object where an element read is not finite."""
+    t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 32)
+    out = np.zeros((t.shape[0], 24), np.uint32)
+    bad = np.zeros(1, np.uint32)
+    st = (lib or load_library()).ptmi_fuse_deform_records(_ptr(t), t.shape[0], _ptr(out), _ptr(bad))
+    if st != 0:
+        raise PtmiError(st, "ptmi_fuse_deform_records failed: object %d" % int(bad[0]))
+    return out
 
 
 def compose_motions(motions, from_view, to_view, lib=None):
@@ -1228,6 +1266,33 @@ class Context:
         f = _frame_nums(frame_nums, c.shape[0])
         g, n_obj, ids = _motion_arrays(motions, object_ids, c.shape[0], c.shape[1:3])
         self._ck(self.lib.ptmi_fuse_images_motion(self.h, _ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), _optr(g),
+                                                  n_obj if n_objects is None else n_objects, _optr(ids), float(fov_degrees), _optr(t), 0 if t is None else t.size,
+                                                  None if params is None else ctypes.byref(params), _ptr(out)))
+        return out
+
+    # ---- fusion through deforming meshes (include/ptmi.h, "FUSION THROUGH DEFORMING MESHES") ----
+    def fuse_views_deform(self, views, frame_nums, motions=None, source=0, first_view=0, n_views=None, params=None, n_objects=None):
+        """ptmi_fuse_views_deform: fuse_views_motion through the geometry stack (capture_view_geometry; render_deforming_path fills it) — a triangle pixel is carried
+        from its triangle in view v to the same triangle in every view of its window; every other pixel goes through motions as fuse_views_motion's do (None: a
+        static world).  source 1 reads the denoised stack, frame_nums may then be None.  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        n_stack = self.views_device_ptr()[2]
+        assert v.shape[0] == n_stack, "views: the matrices of all %d views of the stack" % n_stack
+        f = _frame_nums(frame_nums, n_stack)
+        g, n_obj, _ = _motion_arrays(motions, None, n_stack)
+        if n_views is None:
+            n_views = n_stack - first_view
+        self._ck(self.lib.ptmi_fuse_views_deform(self.h, None if params is None else ctypes.byref(params), _ptr(v), _optr(f), _optr(g),
+                                                 n_obj if n_objects is None else n_objects, int(source), first_view, n_views))
+
+    def fuse_images_deform(self, colour, layers, views, frame_nums, triangles_seq, transforms_seq, meshes, motions=None, object_ids=None, fov_degrees=60.0,
+                           lambertian=None, params=None, n_objects=None):
+        """ptmi_fuse_images_deform: k_fuse_deform on host arrays of any size (see fuse_reference_deform); synchronous."""
+        c, l, v, t, out = _fuse_arrays(colour, layers, views, lambertian)
+        f = _frame_nums(frame_nums, c.shape[0])
+        g, n_obj, ids = _motion_arrays(motions, object_ids, c.shape[0], c.shape[1:3])
+        geo, keep = _deform_arrays(triangles_seq, transforms_seq, meshes, c.shape[0])
+        self._ck(self.lib.ptmi_fuse_images_deform(self.h, _ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), *geo, _optr(g),
                                                   n_obj if n_objects is None else n_objects, _optr(ids), float(fov_degrees), _optr(t), 0 if t is None else t.size,
                                                   None if params is None else ctypes.byref(params), _ptr(out)))
         return out
