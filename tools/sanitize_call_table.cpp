@@ -98,27 +98,26 @@ int main() {
                     call_table_fill_frames(L, tab, ones ? nullptr : frame_nums.data());
                     call_table_fill_object_ids(L, tab, spheres.data(), quads.data(), meshes4.data());
                     call_table_fill_meshes(L, tab, meshes4.data());
-                    ptmm_record* rec = L.ptr<ptmm_record>(tab, L.motion);
+                    // the records: the table's makers into the table (the checks alone first, as the calls run them), the headers' own into vectors to compare with
                     std::vector<ptmm_record> rec_src(n.motion_records);
                     int kind = 0;
                     uint32_t bv = 0, bu = 0, bo = 0;
                     if (radius) {
-                      CHECK(ptmfm_compose_table(motions16.data(), n_views, n_obj, 0, n_views, radius, rec, &kind, &bv, &bu, &bo));
+                      CHECK(call_table_fill_composed_motion(CallTable(), nullptr, motions16.data(), n_obj, n_views, 0, n_views, radius, &bu) == -1);
+                      CHECK(call_table_fill_composed_motion(L, tab, motions16.data(), n_obj, n_views, 0, n_views, radius, &bu) == -1);
                       CHECK(ptmfm_compose_table(motions16.data(), n_views, n_obj, 0, n_views, radius, rec_src.data(), &kind, &bv, &bu, &bo));
                     } else {
+                      CHECK(call_table_fill_motion(CallTable(), nullptr, motions16.data(), n_obj, n_views, 1, n_views) == -1);
+                      CHECK(call_table_fill_motion(L, tab, motions16.data(), n_obj, n_views, 1, n_views) == -1);
                       for (uint32_t v = 1; v < n_views; v++)
-                        for (uint32_t o = 0; o < n_obj; o++) {
-                          CHECK(ptmm_make_record(&motions16[16 * ((size_t)v * n_obj + o)], &rec[(size_t)(v - 1) * n_obj + o]));
-                          CHECK(ptmm_make_record(&motions16[16 * ((size_t)v * n_obj + o)], &rec_src[(size_t)(v - 1) * n_obj + o]));
-                        }
+                        for (uint32_t o = 0; o < n_obj; o++) CHECK(ptmm_make_record(&motions16[16 * ((size_t)v * n_obj + o)], &rec_src[(size_t)(v - 1) * n_obj + o]));
                     }
-                    ptmdf_record* drec = L.ptr<ptmdf_record>(tab, L.deform);
                     std::vector<ptmdf_record> drec_src(n.deform_records);
+                    CHECK(call_table_fill_deform(CallTable(), nullptr, tf.data(), n_tf, n_views, 1, n_views) == -1);
+                    CHECK(call_table_fill_deform(L, tab, tf.data(), n_tf, n_views, 1, n_views) == -1);
                     for (uint32_t v = 1; v < n_views; v++)
-                      for (uint32_t o = 0; o < n_tf; o++) {
-                        CHECK(ptmdf_make_record(&tf[32 * ((size_t)v * n_tf + o)], &tf[32 * ((size_t)(v - 1) * n_tf + o)], &drec[(size_t)(v - 1) * n_tf + o]));
+                      for (uint32_t o = 0; o < n_tf; o++)
                         CHECK(ptmdf_make_record(&tf[32 * ((size_t)v * n_tf + o)], &tf[32 * ((size_t)(v - 1) * n_tf + o)], &drec_src[(size_t)(v - 1) * n_tf + o]));
-                      }
 
                     // ---- every part read back ----
                     const CallTable& K = L;
@@ -143,6 +142,19 @@ int main() {
                     const uint32_t bad = (uint32_t)(combination % n_views);
                     for (int i = 0; i < 16; i++) views16[16 * (size_t)bad + i] = 0.0f;
                     CHECK(call_table_fill_views(L, tab, views16.data()) == (int64_t)bad);
+                    // ... and so are a motion and a transform of the last view that cannot become records, and a count past the bound
+                    if (n_views > 1 && n_obj) {
+                      motions16[16 * ((size_t)(n_views - 1u) * n_obj + n_obj - 1u) + 5] = NAN;
+                      if (radius) CHECK(call_table_fill_composed_motion(L, tab, motions16.data(), n_obj, n_views, 0, n_views, radius, &bu) == record_fault(n_views - 1u, n_obj - 1u) && bu == n_views - 1u);
+                      else CHECK(call_table_fill_motion(L, tab, motions16.data(), n_obj, n_views, 1, n_views) == record_fault(n_views - 1u, n_obj - 1u));
+                    }
+                    if (n_views > 1 && n_tf) {
+                      tf[32 * ((size_t)(n_views - 2u) * n_tf + n_tf - 1u)] = INFINITY;  // (the model of the view before the last: the last view's record alone reads it)
+                      CHECK(call_table_fill_deform(L, tab, tf.data(), n_tf, n_views, 1, n_views) == record_fault(n_views - 1u, n_tf - 1u));
+                    }
+                    CHECK(call_table_fill_motion(CallTable(), nullptr, nullptr, PTMI_MOTION_MAX_RECORDS / n_views + 1u, n_views, 1, 1) == kTooManyRecords);
+                    CHECK(call_table_fill_deform(CallTable(), nullptr, nullptr, PTMI_MOTION_MAX_RECORDS / n_views + 1u, n_views, 1, 1) == kTooManyRecords);
+                    CHECK(call_table_fill_composed_motion(CallTable(), nullptr, nullptr, PTMI_MOTION_MAX_RECORDS / (n_views * 5u) + 1u, n_views, 0, n_views, 2, &bu) == kTooManyRecords);
                     free(tab);
                   }
   printf("sanitize_call_table: ok (%ld combinations)\n", combination);

@@ -1,7 +1,7 @@
 // ptmi_call_table.h — the one small table that a fuse or accumulate call puts on the device (c->fuse_tab for the *_views forms, a buffer of the call's own for the
 // *_images forms), defined ONCE: which parts it has, where each lies, and how each is filled.  Host only, and no HIP type: standard headers and include/*.h, so that
-// g++ compiles it (tools/sanitize_call_table.cpp runs all of it under ASan and UBSan).  The kernels are handed pointers into the table, never offsets, so nothing on the
-// device knows this order.
+// g++ compiles it (tools/sanitize_call_table.cpp runs all of it under ASan and UBSan) — and so that the host references (ptmi_host.cpp) lay their records out as the
+// same table, filled by the same makers.  The kernels are handed pointers into the table, never offsets, so nothing on the device knows this order.
 //
 // The parts, in the table's order, and what the layout guarantees of each:
 //   views       kFuseRow float4 per view of the stack (fuse_pack_row)                                          read as float4: starts on 16 bytes
@@ -21,9 +21,11 @@
 #include <cstdint>
 #include <cstring>
 
+#include "../../include/ptmi.h"
 #include "../../include/ptmi_deform.h"
 #include "../../include/ptmi_fuse.h"
 #include "../../include/ptmi_fuse_deform.h"
+#include "../../include/ptmi_fuse_motion.h"
 #include "../../include/ptmi_motion.h"
 
 namespace ptmi {
@@ -127,11 +129,54 @@ inline void call_table_fill_object_ids(const CallTable& L, void* tab, const floa
 inline void call_table_fill_meshes(const CallTable& L, void* tab, const int32_t* mesh_words) {
   if (L.meshes.bytes) memcpy(L.ptr<int32_t>(tab, L.meshes), mesh_words, L.meshes.bytes);
 }
-// The fusion *_deform call's two parts from the transforms of the whole stack, n_transforms x 32 f32 per slot from tf0 = slot 0 (slots outside [lo, hi] are not
-// read): the records of views [lo, hi], view after view, and the moved masks of output views [first, first + n) (include/ptmi_fuse_deform.h).  tab = nullptr: the
-// checks alone.  Returns -1, or (view << 32 | transform) of the first transform with an element that is not finite (the parts are then unfinished).
+
+// ---- the record makers: one per kind of record, for the calls and for the host references alike.  tab = nullptr: the checks alone, nothing is written (what a call
+// does before it allocates, with L = CallTable()).  Each returns -1, kTooManyRecords when the part would hold more than PTMI_MOTION_MAX_RECORDS records, or
+// (view << 32 | object) of the first record that cannot be made (the part is then unfinished).  None allocates. ----
+constexpr int64_t kTooManyRecords = -2;
+inline int64_t record_fault(uint32_t view, uint32_t object) { return (int64_t)(((uint64_t)view << 32) | object); }
+inline bool too_many_records(uint64_t views, uint64_t per_view) { return per_view && views > (uint64_t)PTMI_MOTION_MAX_RECORDS / per_view; }  // views x per_view > the bound
+
+// motion, an accumulation's: the records (include/ptmi_motion.h) of views [lo, hi) of motions16 [n_all][n_objects][16], view after view; each has to be finite with a
+// 3x3 that can be inverted — the entries of other views may hold anything.
+inline int64_t call_table_fill_motion(const CallTable& L, void* tab, const float* motions16, uint32_t n_objects, uint32_t n_all, uint32_t lo, uint32_t hi) {
+  if (too_many_records(n_all, n_objects)) return kTooManyRecords;
+  ptmm_record unkept;
+  ptmm_record* rec = tab ? L.ptr<ptmm_record>(tab, L.motion) : nullptr;
+  for (uint32_t v = lo; v < hi; v++)
+    for (uint32_t o = 0; o < n_objects; o++)
+      if (!ptmm_make_record(motions16 + 16 * ((size_t)v * n_objects + o), rec ? &rec[(size_t)(v - lo) * n_objects + o] : &unkept)) return record_fault(v, o);
+  return -1;
+}
+// motion, a fusion's: the composed records (include/ptmi_fuse_motion.h) of output views [first, first + n), [n][2 radius + 1][n_objects].  A fault with
+// *neighbour == view is a step entry that the call reads (the checks alone find these); one with another *neighbour is the motion composed from view to *neighbour.
+inline int64_t call_table_fill_composed_motion(const CallTable& L, void* tab, const float* motions16, uint32_t n_objects, uint32_t n_all, uint32_t first, uint32_t n,
+                                               uint32_t radius, uint32_t* neighbour) {
+  if (too_many_records((uint64_t)n * (2u * radius + 1u), n_objects)) return kTooManyRecords;
+  int kind = 0;
+  uint32_t bv = 0, bo = 0;
+  if (ptmfm_compose_table(motions16, n_all, n_objects, first, n, radius, tab ? L.ptr<ptmm_record>(tab, L.motion) : nullptr, &kind, &bv, neighbour, &bo)) return -1;
+  return record_fault(bv, bo);
+}
+// deform, an accumulation's: the records (include/ptmi_deform.h) of views [lo, hi), lo >= 1 — each from the transforms of its view and of the view before, slot after
+// slot of n_transforms x 32 f32 from tf0 = slot 0 —, view after view.
+inline int64_t call_table_fill_deform(const CallTable& L, void* tab, const float* tf0, uint32_t n_transforms, uint32_t n_all, uint32_t lo, uint32_t hi) {
+  if (too_many_records(n_all, n_transforms)) return kTooManyRecords;
+  ptmdf_record unkept;
+  ptmdf_record* rec = tab ? L.ptr<ptmdf_record>(tab, L.deform) : nullptr;
+  for (uint32_t v = lo; v < hi; v++)
+    for (uint32_t o = 0; o < n_transforms; o++)
+      if (!ptmdf_make_record(tf0 + PTMDF_TRANSFORM_WORDS * ((size_t)v * n_transforms + o), tf0 + PTMDF_TRANSFORM_WORDS * ((size_t)(v - 1) * n_transforms + o),
+                             rec ? &rec[(size_t)(v - lo) * n_transforms + o] : &unkept))
+        return record_fault(v, o);
+  return -1;
+}
+// fuse_deform and moved, a fusion's, from the transforms of the whole stack, n_transforms x 32 f32 per slot from tf0 = slot 0 (slots outside [lo, hi] are not read):
+// the records of views [lo, hi] = the call's read range (ptmfd_read_range), view after view, and the moved masks of output views [first, first + n)
+// (include/ptmi_fuse_deform.h).
 inline int64_t call_table_fill_fuse_deform(const CallTable& L, void* tab, const float* tf0, uint32_t n_transforms, uint32_t n_all, uint32_t lo, uint32_t hi, uint32_t first,
                                            uint32_t n, uint32_t radius) {
+  if (too_many_records((uint64_t)hi - lo + 1u, n_transforms)) return kTooManyRecords;
   ptmfd_record unkept;
   ptmfd_record* rec = tab ? L.ptr<ptmfd_record>(tab, L.fuse_deform) : nullptr;
   for (uint32_t v = lo; v <= hi; v++)
@@ -145,6 +190,5 @@ inline int64_t call_table_fill_fuse_deform(const CallTable& L, void* tab, const 
       moved[(size_t)(v - first) * n_transforms + o] = ptmfd_moved_mask(tf0, n_transforms, n_all, v, o, radius);
   return -1;
 }
-// (the other records are made straight into their parts, L.ptr<ptmm_record>(tab, L.motion) and L.ptr<ptmdf_record>(tab, L.deform), by the calls' own makers)
 
 }  // namespace ptmi

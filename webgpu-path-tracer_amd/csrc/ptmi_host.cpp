@@ -29,6 +29,7 @@
 #include "../../include/ptmi_fuse_deform.h"
 #include "../../include/ptmi_noise.h"
 #include "ptmi_bvh_domain.h"
+#include "ptmi_call_table.h"
 
 namespace {
 // Math.min / Math.max (lib/BVH/AABB.js:8-28) on finite values: -0 < +0 whatever the argument order
@@ -962,6 +963,26 @@ struct ReferenceDeform {  // (accumulate_reference's too)
   const int32_t* meshes;  // [n_meshes][4]
   uint32_t n_meshes;
 };
+// What both references refuse of these two before they look at a record: a null array that the counts say is read, and a deformation without triangles
+static bool reference_parts_ok(const ReferenceMotion* motion, const ReferenceDeform* deform) {
+  if (motion && (!motion->motions16 || !motion->object_ids)) return false;
+  return !deform || (deform->triangles_seq && deform->n_triangles && (!deform->n_transforms || deform->transforms_seq) && (!deform->n_meshes || deform->meshes));
+}
+// The records of a reference, laid out as the calls' table from counts (ptmi_call_table.h) and made by the calls' makers: `fill` runs the makers of the kinds the
+// reference has (false: one refused), `count` sets their counts.  The checks alone first, as the calls do, then the table, then the fill.
+template <class Fill, class Count>
+static int reference_records(Fill fill, Count count, ptmi::CallTable* L, std::vector<uint8_t>* tab) {
+  if (!fill(ptmi::CallTable(), nullptr)) return PTMI_ERR_INVALID_ARG;
+  ptmi::CallTableCounts n;
+  count(&n);
+  *L = ptmi::CallTable(n);
+  try {
+    tab->resize(L->total);
+  } catch (const std::bad_alloc&) {
+    return PTMI_ERR_NO_MEMORY;
+  }
+  return fill(*L, tab->data()) ? PTMI_OK : PTMI_ERR_INVALID_ARG;
+}
 static int fuse_reference(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, const float* frame_nums,
                           float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out,
                           const ReferenceMotion* motion = nullptr, float* weight_out = nullptr, const ReferenceDeform* deform = nullptr, int threads = 1) {
@@ -980,39 +1001,27 @@ static int fuse_reference(const float* colour, const float* layers, const float*
   }
   for (uint32_t v = 0; v < n_images; v++)
     if (!ptmf_make_view(views16 + 16 * (size_t)v, &tab[v])) return PTMI_ERR_INVALID_ARG;
-  std::vector<ptmm_record> rec;  // [v][u - v + radius][n_objects], as the kernel's table
+  // the composed motion records [v][u - v + radius][n_objects]; the deform records and the moved masks, both [image][n_transforms]: every image is in some output
+  // view's window, so the read range is the whole stack
+  if (!reference_parts_ok(motion, deform)) return PTMI_ERR_INVALID_ARG;
   const uint32_t span = 2u * (uint32_t)P.radius + 1u;
-  if (motion) {
-    if (!motion->motions16 || !motion->object_ids || (uint64_t)n_images * span * motion->n_objects > (uint64_t)PTMI_MOTION_MAX_RECORDS) return PTMI_ERR_INVALID_ARG;
-    int kind;
-    uint32_t bv, bu, bo;
-    if (!ptmfm_compose_table(motion->motions16, n_images, motion->n_objects, 0, n_images, (uint32_t)P.radius, nullptr, &kind, &bv, &bu, &bo)) return PTMI_ERR_INVALID_ARG;
-    try {
-      rec.resize((size_t)n_images * span * motion->n_objects);
-    } catch (const std::bad_alloc&) {
-      return PTMI_ERR_NO_MEMORY;
-    }
-    if (!rec.empty() && !ptmfm_compose_table(motion->motions16, n_images, motion->n_objects, 0, n_images, (uint32_t)P.radius, rec.data(), &kind, &bv, &bu, &bo))
-      return PTMI_ERR_INVALID_ARG;
-  }
-  std::vector<ptmfd_record> drec;  // [image][n_transforms]: every image is in some output view's window
-  std::vector<uint32_t> dmoved;    // [image][n_transforms]
-  if (deform) {
-    if (!deform->triangles_seq || !deform->n_triangles || (deform->n_transforms && !deform->transforms_seq) || (deform->n_meshes && !deform->meshes) ||
-        (uint64_t)n_images * deform->n_transforms > (uint64_t)PTMI_MOTION_MAX_RECORDS)
-      return PTMI_ERR_INVALID_ARG;
-    try {
-      drec.resize((size_t)n_images * deform->n_transforms);
-      dmoved.resize((size_t)n_images * deform->n_transforms);
-    } catch (const std::bad_alloc&) {
-      return PTMI_ERR_NO_MEMORY;
-    }
-    for (uint32_t v = 0; v < n_images; v++)
-      for (uint32_t o = 0; o < deform->n_transforms; o++) {
-        if (!ptmfd_make_record(deform->transforms_seq + 32 * ((size_t)v * deform->n_transforms + o), &drec[(size_t)v * deform->n_transforms + o])) return PTMI_ERR_INVALID_ARG;
-        dmoved[(size_t)v * deform->n_transforms + o] = ptmfd_moved_mask(deform->transforms_seq, deform->n_transforms, n_images, v, o, (uint32_t)P.radius);
-      }
-  }
+  ptmi::CallTable layout;
+  std::vector<uint8_t> records;
+  const int made = reference_records(
+      [&](const ptmi::CallTable& L, void* tab) {
+        uint32_t to;
+        if (motion && ptmi::call_table_fill_composed_motion(L, tab, motion->motions16, motion->n_objects, n_images, 0, n_images, (uint32_t)P.radius, &to) != -1) return false;
+        return !deform || ptmi::call_table_fill_fuse_deform(L, tab, deform->transforms_seq, deform->n_transforms, n_images, 0, n_images - 1u, 0, n_images, (uint32_t)P.radius) == -1;
+      },
+      [&](ptmi::CallTableCounts* n) {
+        if (motion) n->motion_records = (size_t)n_images * span * motion->n_objects;
+        if (deform) n->fuse_deform_records = n->moved_words = (size_t)n_images * deform->n_transforms;
+      },
+      &layout, &records);
+  if (made != PTMI_OK) return made;
+  const ptmm_record* rec = layout.ptr<ptmm_record>(records.data(), layout.motion);
+  const ptmfd_record* drec = layout.ptr<ptmfd_record>(records.data(), layout.fuse_deform);
+  const uint32_t* dmoved = layout.ptr<uint32_t>(records.data(), layout.moved);
   ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   const size_t npix = (size_t)w * (size_t)h;
   const ptmd_f4* S = reinterpret_cast<const ptmd_f4*>(colour);
@@ -1173,34 +1182,24 @@ static int accumulate_reference(const float* colour_sums, const float* moments, 
   }
   for (uint32_t v = 0; v < n_images; v++)
     if (!ptmf_make_view(views16 + 16 * (size_t)v, &tab[v])) return PTMI_ERR_INVALID_ARG;
-  std::vector<ptmm_record> rec;  // images 1 .. n_images - 1 have a predecessor: their motions are the ones read
-  if (motion) {
-    if (!motion->motions16 || !motion->object_ids || (uint64_t)n_images * motion->n_objects > (uint64_t)PTMI_MOTION_MAX_RECORDS) return PTMI_ERR_INVALID_ARG;
-    try {
-      rec.resize((size_t)(n_images - 1) * motion->n_objects);
-    } catch (const std::bad_alloc&) {
-      return PTMI_ERR_NO_MEMORY;
-    }
-    for (uint32_t v = 1; v < n_images; v++)
-      for (uint32_t o = 0; o < motion->n_objects; o++)
-        if (!ptmm_make_record(motion->motions16 + 16 * ((size_t)v * motion->n_objects + o), &rec[(size_t)(v - 1) * motion->n_objects + o])) return PTMI_ERR_INVALID_ARG;
-  }
-  std::vector<ptmdf_record> drec;  // likewise: image v's records pair its transforms with image v-1's
-  if (deform) {
-    if (!deform->triangles_seq || !deform->n_triangles || (deform->n_transforms && !deform->transforms_seq) || (deform->n_meshes && !deform->meshes) ||
-        (uint64_t)n_images * deform->n_transforms > (uint64_t)PTMI_MOTION_MAX_RECORDS)
-      return PTMI_ERR_INVALID_ARG;
-    try {
-      drec.resize((size_t)(n_images - 1) * deform->n_transforms);
-    } catch (const std::bad_alloc&) {
-      return PTMI_ERR_NO_MEMORY;
-    }
-    for (uint32_t v = 1; v < n_images; v++)
-      for (uint32_t o = 0; o < deform->n_transforms; o++)
-        if (!ptmdf_make_record(deform->transforms_seq + 32 * ((size_t)v * deform->n_transforms + o), deform->transforms_seq + 32 * ((size_t)(v - 1) * deform->n_transforms + o),
-                               &drec[(size_t)(v - 1) * deform->n_transforms + o]))
-          return PTMI_ERR_INVALID_ARG;
-  }
+  // images 1 .. n_images - 1 have a predecessor: theirs are the motion records, [image - 1][n_objects], and the deform records, [image - 1][n_transforms], each of
+  // which pairs its image's transforms with those of the image before
+  if (!reference_parts_ok(motion, deform)) return PTMI_ERR_INVALID_ARG;
+  ptmi::CallTable layout;
+  std::vector<uint8_t> records;
+  const int made = reference_records(
+      [&](const ptmi::CallTable& L, void* tab) {
+        if (motion && ptmi::call_table_fill_motion(L, tab, motion->motions16, motion->n_objects, n_images, 1, n_images) != -1) return false;
+        return !deform || ptmi::call_table_fill_deform(L, tab, deform->transforms_seq, deform->n_transforms, n_images, 1, n_images) == -1;
+      },
+      [&](ptmi::CallTableCounts* n) {
+        if (motion) n->motion_records = (size_t)(n_images - 1) * motion->n_objects;
+        if (deform) n->deform_records = (size_t)(n_images - 1) * deform->n_transforms;
+      },
+      &layout, &records);
+  if (made != PTMI_OK) return made;
+  const ptmm_record* rec = layout.ptr<ptmm_record>(records.data(), layout.motion);
+  const ptmdf_record* drec = layout.ptr<ptmdf_record>(records.data(), layout.deform);
   ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor), ku = k;
   const ptma_consts ka = ptma_make_consts(P.max_history, P.min_frames);
   const size_t npix = (size_t)w * (size_t)h;

@@ -445,7 +445,7 @@ static uint32_t first_view_with_history(uint32_t first, bool resume) { return re
 // The kernel on device arrays: colour [n_stack][H][W] float4, layers [n_stack][3][H][W] float4, out [n_stack][H][W] float4, of which views [first, first + n) are
 // written; t: the table's parts (table_ptrs).  One launch; more only where n exceeds the grid's z limit.
 // t.frames: the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_fuse_frames.
-// motion (with t.frames): nullptr, or k_fuse_motion's operands, records = the composed records of view `first` (fuse_motion_table: their order).
+// motion (with t.frames): nullptr, or k_fuse_motion's operands, records = the composed records of view `first` (call_table_fill_composed_motion: their order).
 // deform (with t.frames and motion, whose n_objects may be 0: a static world beside the triangles): k_fuse_deform's operands, moved = the masks of view `first`.
 static int fuse_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, const TablePtrs& t, uint32_t n_materials, int W, int H, uint32_t n_stack,
                         uint32_t first, uint32_t n, const ptmf_consts& k, const MotionArgs* motion = nullptr, const FuseDeformArgs* deform = nullptr) {
@@ -498,43 +498,89 @@ static int make_stack_with_table(ptmi_ctx* c, const char* who, StackKind k, cons
   return PTMI_OK;
 }
 
-// The *_motion fusion calls: the composed records (include/ptmi_fuse_motion.h) of output views [first, first + n) of a stack of n_all views, radius R, from
-// motions16 [n_all][n_objects][16], into `rec` as [n][2 R + 1][n_objects] — fuse_motion_count of them.  rec = nullptr: the checks that need no room alone, which a
-// call makes before it allocates (the pointer, the count, the step entries the call reads); the composed entries are checked as they are made.  Allocates nothing.
-static size_t fuse_motion_count(uint32_t n_objects, uint32_t n, uint32_t R) { return (size_t)n * (2u * R + 1u) * n_objects; }
-static int fuse_motion_table(ptmi_ctx* c, const char* who, const float* motions16, uint32_t n_objects, uint32_t n_all, uint32_t first, uint32_t n, uint32_t R, ptmm_record* rec) {
-  if (!motions16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null motions16");
-  if ((uint64_t)n * (2u * R + 1u) * n_objects > (uint64_t)PTMI_MOTION_MAX_RECORDS)
-    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": " + std::to_string(n) + " views x " + std::to_string(2u * R + 1u) + " window views x " + std::to_string(n_objects) +
-                                             " objects are more than PTMI_MOTION_MAX_RECORDS composed motions");
-  int kind = 0;
-  uint32_t bv = 0, bu = 0, bo = 0;
-  if (ptmfm_compose_table(motions16, n_all, n_objects, first, n, R, rec, &kind, &bv, &bu, &bo)) return PTMI_OK;
-  if (kind == PTMFM_BAD_STEP)
-    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the motion of view " + std::to_string(bv) + ", object " + std::to_string(bo) +
+// The records of a *_motion or *_deform call, in all four forms: which kinds it has, from what, and for which views.  A fusion (radius > 0) has, for its output views
+// [first, first + n), the composed motion records [n][2 radius + 1][n_objects] and the per-view deform records of its read range with the moved masks; an
+// accumulation (radius = 0) has the per-step motion and deform records of views [first, first + n), which all have a predecessor.
+struct CallRecords {
+  bool motion = false, deform = false;
+  bool motion_first = false;         // the order of the two kinds' checks (ptmi_accumulate_images: motion, then deform; the other three forms: deform, then motion)
+  const float* motions16 = nullptr;  // [n_all][n_objects][16]
+  uint32_t n_objects = 0;
+  const float* tf0 = nullptr;  // the transforms from slot 0, n_transforms x 32 f32 per slot
+  uint32_t n_transforms = 0;
+  size_t mesh_words = 0;
+  uint32_t n_all = 0, first = 0, n = 0, radius = 0;  // n_all: the views of the stack, or the images
+};
+static int null_motions(ptmi_ctx* c, const char* who) { return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null motions16"); }
+static void count_call_records(const CallRecords& q, CallTableCounts* n) {
+  if (q.motion) n->motion_records = (size_t)q.n * (q.radius ? 2u * q.radius + 1u : 1u) * q.n_objects;
+  if (!q.deform) return;
+  n->mesh_words = q.mesh_words;
+  if (q.radius) {
+    uint32_t lo, hi;
+    ptmfd_read_range(q.n_all, q.first, q.n, q.radius, &lo, &hi);
+    n->fuse_deform_records = (size_t)(hi - lo + 1u) * q.n_transforms, n->moved_words = (size_t)q.n * q.n_transforms;
+  } else {
+    n->deform_records = (size_t)q.n * q.n_transforms;
+  }
+}
+// The makers of ptmi_call_table.h in the call's order, and a maker's fault turned into the refusal's words.  tab = nullptr (with L = CallTable()): the checks alone,
+// which a call runs before it allocates, so that its refusals come in their order; then once more with the table, to fill it.  Allocates nothing.
+static int make_call_records(ptmi_ctx* c, const char* who, const CallRecords& q, const CallTable& L, void* tab) {
+  const std::string w(who);
+  auto view_object = [](int64_t bad, uint32_t* v, uint32_t* o) { *v = (uint32_t)((uint64_t)bad >> 32), *o = (uint32_t)((uint64_t)bad & 0xffffffffu); };
+  auto motion = [&]() -> int {
+    if (!q.motions16) return null_motions(c, who);
+    uint32_t bv, bo, bu = 0;
+    const int64_t bad = q.radius ? call_table_fill_composed_motion(L, tab, q.motions16, q.n_objects, q.n_all, q.first, q.n, q.radius, &bu)
+                                 : call_table_fill_motion(L, tab, q.motions16, q.n_objects, q.n_all, q.first, q.first + q.n);
+    if (bad == -1) return PTMI_OK;
+    if (bad == kTooManyRecords)
+      return fail(c, PTMI_ERR_INVALID_ARG,
+                  q.radius ? w + ": " + std::to_string(q.n) + " views x " + std::to_string(2u * q.radius + 1u) + " window views x " + std::to_string(q.n_objects) +
+                                 " objects are more than PTMI_MOTION_MAX_RECORDS composed motions"
+                           : w + ": " + std::to_string(q.n_all) + " views x " + std::to_string(q.n_objects) + " objects are more than PTMI_MOTION_MAX_RECORDS motions");
+    view_object(bad, &bv, &bo);
+    if (q.radius && bu != bv)
+      return fail(c, PTMI_ERR_INVALID_ARG, w + ": the motion composed from view " + std::to_string(bv) + " to view " + std::to_string(bu) + ", object " + std::to_string(bo) +
+                                               ", has a non-finite element or a 3x3 with a zero or non-finite determinant");
+    return fail(c, PTMI_ERR_INVALID_ARG, w + ": the motion of view " + std::to_string(bv) + ", object " + std::to_string(bo) +
                                              " has a non-finite element or a 3x3 with a zero or non-finite determinant: view " + std::to_string(bv) + " is read by this call");
-  return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the motion composed from view " + std::to_string(bv) + " to view " + std::to_string(bu) + ", object " + std::to_string(bo) +
-                                           ", has a non-finite element or a 3x3 with a zero or non-finite determinant");
+  };
+  auto deform = [&]() -> int {
+    uint32_t lo = 0, hi = 0, bv, bo;
+    if (q.radius) ptmfd_read_range(q.n_all, q.first, q.n, q.radius, &lo, &hi);
+    const int64_t bad = q.radius ? call_table_fill_fuse_deform(L, tab, q.tf0, q.n_transforms, q.n_all, lo, hi, q.first, q.n, q.radius)
+                                 : call_table_fill_deform(L, tab, q.tf0, q.n_transforms, q.n_all, q.first, q.first + q.n);
+    if (bad == -1) return PTMI_OK;
+    if (bad == kTooManyRecords)
+      return fail(c, PTMI_ERR_INVALID_ARG, w + ": " + std::to_string(q.radius ? hi - lo + 1u : q.n_all) + " views x " + std::to_string(q.n_transforms) +
+                                               " transforms are more than PTMI_MOTION_MAX_RECORDS records");
+    view_object(bad, &bv, &bo);
+    return fail(c, PTMI_ERR_INVALID_ARG, w + ": the transform of view " + std::to_string(bv) + (q.radius ? "" : " or of view " + std::to_string(bv - 1)) + ", object " + std::to_string(bo) +
+                                             ", has an element that is not finite: view " + std::to_string(bv) + " is read by this call");
+  };
+  if (q.motion && q.motion_first)
+    if (int r = motion()) return r;
+  if (q.deform)
+    if (int r = deform()) return r;
+  if (q.motion && !q.motion_first)
+    if (int r = motion()) return r;
+  return PTMI_OK;
 }
 
-// The fusion *_deform calls: the per-view records and the moved masks (include/ptmi_fuse_deform.h) of a call over output views [first, first + n) of n_all views,
-// radius R, from the transforms tf0 = slot 0, n_transforms x 32 f32 per slot.  tab = nullptr: the checks that need no room alone.  Allocates nothing.
-static int fuse_deform_parts(ptmi_ctx* c, const char* who, const CallTable& L, void* tab, const float* tf0, uint32_t n_transforms, uint32_t n_all, uint32_t first, uint32_t n,
-                             uint32_t R) {
-  uint32_t lo, hi;
-  ptmfd_read_range(n_all, first, n, R, &lo, &hi);
-  if ((uint64_t)(hi - lo + 1u) * n_transforms > (uint64_t)PTMI_MOTION_MAX_RECORDS)
-    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": " + std::to_string(hi - lo + 1u) + " views x " + std::to_string(n_transforms) + " transforms are more than PTMI_MOTION_MAX_RECORDS records");
-  const int64_t bad = call_table_fill_fuse_deform(L, tab, tf0, n_transforms, n_all, lo, hi, first, n, R);
-  if (bad < 0) return PTMI_OK;
-  const uint32_t bv = (uint32_t)((uint64_t)bad >> 32), bo = (uint32_t)((uint64_t)bad & 0xffffffffu);
-  return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the transform of view " + std::to_string(bv) + ", object " + std::to_string(bo) + ", has an element that is not finite: view " +
-                                           std::to_string(bv) + " is read by this call");
-}
-static void fuse_deform_counts(CallTableCounts* n, uint32_t n_transforms, uint32_t n_all, uint32_t first, uint32_t n_out, uint32_t R, size_t mesh_words) {
-  uint32_t lo, hi;
-  ptmfd_read_range(n_all, first, n_out, R, &lo, &hi);
-  n->fuse_deform_records = (size_t)(hi - lo + 1u) * n_transforms, n->moved_words = (size_t)n_out * n_transforms, n->mesh_words = mesh_words;
+// What a *_views_deform call needs of the context's geometry stack: that there is one, of the view stack's size, that holds the scene's triangle and transform counts
+// as they are now, and that every slot the call reads, [lo, hi], was captured.
+static int check_geometry_stack(ptmi_ctx* c, const char* who, uint32_t n_stack, uint32_t lo, uint32_t hi) {
+  const ptmi_ctx::GeometryStack& g = c->geometry;
+  if (!g.n_views) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no geometry stack: ptmi_capture_view_geometry makes it, view by view");
+  if (g.n_views != n_stack) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry stack has " + std::to_string(g.n_views) + " views, the view stack " + std::to_string(n_stack));
+  if (g.n_tris != c->n_tris_uploaded || g.n_xforms != c->h_xforms.size() / 32)
+    return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry stack holds " + std::to_string(g.n_tris) + " triangles and " + std::to_string(g.n_xforms) + " transforms, the scene now " +
+                                       std::to_string(c->n_tris_uploaded) + " and " + std::to_string(c->h_xforms.size() / 32));
+  for (uint32_t v = lo; v <= hi; v++)
+    if (!g.captured[v]) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry of view " + std::to_string(v) + " was never captured: view " + std::to_string(v) + " is read by this call");
+  return PTMI_OK;
 }
 
 // ptmi_fuse_views, ptmi_fuse_views_frames (the view stack as source), ptmi_fuse_views_motion (motion: its motions16 [n_views of the stack][n_objects][16]) and
@@ -553,7 +599,7 @@ static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* para
   static const float no_motions[16] = {};
   MotionPart still{no_motions, 0, nullptr};
   if (deform && !motion->motions16 && motion->n_objects == 0) motion = &still;  // (a static world beside the triangles: no entry is read)
-  if (motion && !motion->motions16) return fuse_motion_table(c, who, nullptr, 0, 0, 0, 0, 0, nullptr);
+  if (motion && !motion->motions16) return null_motions(c, who);
   if (int r = check_source_stacks(c, who, source == 1, first_view, n_views)) return r;
   const uint32_t n_stack = c->stacks[STACK_VIEWS].n, R = (uint32_t)P.radius;
   // the counts the call reads: its range widened by the radius on both sides, clipped to the stack — the window of its output views
@@ -561,30 +607,21 @@ static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* para
   CallTableCounts n = scene_table_counts(c, motion != nullptr);
   n.frames = F.each || motion;
   const ptmi_ctx::GeometryStack& g = c->geometry;
+  CallRecords q;
+  q.n_all = n_stack, q.first = first_view, q.n = n_views, q.radius = R;
+  if (motion) q.motion = true, q.motions16 = motion->motions16, q.n_objects = motion->n_objects;
   if (deform) {  // the geometry the call reads: the slots of its range widened by the radius
-    if (!g.n_views) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no geometry stack: ptmi_capture_view_geometry makes it, view by view");
-    if (g.n_views != n_stack) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry stack has " + std::to_string(g.n_views) + " views, the view stack " + std::to_string(n_stack));
-    if (g.n_tris != c->n_tris_uploaded || g.n_xforms != c->h_xforms.size() / 32)
-      return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry stack holds " + std::to_string(g.n_tris) + " triangles and " + std::to_string(g.n_xforms) + " transforms, the scene now " +
-                                         std::to_string(c->n_tris_uploaded) + " and " + std::to_string(c->h_xforms.size() / 32));
     uint32_t lo, hi;
     ptmfd_read_range(n_stack, first_view, n_views, R, &lo, &hi);
-    for (uint32_t v = lo; v <= hi; v++)
-      if (!g.captured[v]) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry of view " + std::to_string(v) + " was never captured: view " + std::to_string(v) + " is read by this call");
-    if (int r = fuse_deform_parts(c, who, CallTable(), nullptr, g.h_xforms.data(), (uint32_t)g.n_xforms, n_stack, first_view, n_views, R)) return r;
-    fuse_deform_counts(&n, (uint32_t)g.n_xforms, n_stack, first_view, n_views, R, c->h_meshes.size());
+    if (int r = check_geometry_stack(c, who, n_stack, lo, hi)) return r;
+    q.deform = true, q.tf0 = g.h_xforms.data(), q.n_transforms = (uint32_t)g.n_xforms, q.mesh_words = c->h_meshes.size();
   }
-  if (motion) {
-    if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_stack, first_view, n_views, R, nullptr)) return r;
-    n.motion_records = fuse_motion_count(motion->n_objects, n_views, R);
-  }
+  if (int r = make_call_records(c, who, q, CallTable(), nullptr)) return r;
+  count_call_records(q, &n);
   const CallTable L(n);
   std::vector<uint8_t> tab;
   if (int r = alloc_table(c, who, L, &tab)) return r;
-  if (deform)
-    if (int r = fuse_deform_parts(c, who, L, tab.data(), g.h_xforms.data(), (uint32_t)g.n_xforms, n_stack, first_view, n_views, R)) return r;
-  if (motion)
-    if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_stack, first_view, n_views, R, L.ptr<ptmm_record>(tab.data(), L.motion))) return r;
+  if (int r = make_call_records(c, who, q, L, tab.data())) return r;
   if (int r = fill_views_and_frames(c, who, L, tab.data(), views16, F.frame_nums)) return r;
   fill_scene_parts(c, L, tab.data());
   if (int r = make_stack_with_table(c, who, STACK_FUSED, tab.data(), L.total)) return r;
@@ -644,23 +681,17 @@ static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const 
   if (!lambertian) n_materials = 0;
   CallTableCounts n;
   n.n_views = n_images, n.n_materials = n_materials, n.frames = F.each;
-  if (deform) {
-    if (int r = fuse_deform_parts(c, who, CallTable(), nullptr, deform->transforms_seq, deform->n_transforms, n_images, 0, n_images, (uint32_t)P.radius)) return r;
-    fuse_deform_counts(&n, deform->n_transforms, n_images, 0, n_images, (uint32_t)P.radius, (size_t)deform->n_meshes * 4);
-  }
-  if (motion) {
-    if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_images, 0, n_images, (uint32_t)P.radius, nullptr)) return r;
-    n.motion_records = fuse_motion_count(motion->n_objects, n_images, (uint32_t)P.radius);
-  }
+  CallRecords q;
+  q.n_all = n_images, q.first = 0, q.n = n_images, q.radius = (uint32_t)P.radius;
+  if (motion) q.motion = true, q.motions16 = motion->motions16, q.n_objects = motion->n_objects;
+  if (deform) q.deform = true, q.tf0 = deform->transforms_seq, q.n_transforms = deform->n_transforms, q.mesh_words = (size_t)deform->n_meshes * 4;
+  if (int r = make_call_records(c, who, q, CallTable(), nullptr)) return r;
+  count_call_records(q, &n);
   const CallTable L(n);
   std::vector<uint8_t> tab;
   if (int r = alloc_table(c, who, L, &tab)) return r;
-  if (deform) {
-    if (int r = fuse_deform_parts(c, who, L, tab.data(), deform->transforms_seq, deform->n_transforms, n_images, 0, n_images, (uint32_t)P.radius)) return r;
-    call_table_fill_meshes(L, tab.data(), deform->meshes);
-  }
-  if (motion)
-    if (int r = fuse_motion_table(c, who, motion->motions16, motion->n_objects, n_images, 0, n_images, (uint32_t)P.radius, L.ptr<ptmm_record>(tab.data(), L.motion))) return r;
+  if (int r = make_call_records(c, who, q, L, tab.data())) return r;
+  if (deform) call_table_fill_meshes(L, tab.data(), deform->meshes);
   if (int r = fill_views_and_frames(c, who, L, tab.data(), views16, F.frame_nums)) return r;
   call_table_fill_materials(L, tab.data(), lambertian, n_materials);
   const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), F.frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
@@ -850,37 +881,6 @@ static int accumulate_check_args(ptmi_ctx* c, const char* who, const ptmi_accumu
   return check_stack_call(c, who, "a view's pixels", "several", ok ? nullptr : "max_history, sigma_normal, sigma_depth and albedo_floor > 0, all finite, and min_frames >= 2", true, frame_num);
 }
 
-// The *_motion calls: the records (include/ptmi_motion.h) of views [lo, hi) of motions16 [n_all][n_objects][16], the entries the call reads, view after view into
-// `rec`, record_count of them; each has to be finite with a 3x3 that can be inverted — the others may hold anything.  rec = nullptr: the checks alone, nothing is
-// written: what a call does before it allocates, so that its refusals come in their order.  Allocates nothing.
-static size_t record_count(uint32_t per_view, uint32_t lo, uint32_t hi) { return (size_t)(hi > lo ? hi - lo : 0) * per_view; }
-static int make_motion_records(ptmi_ctx* c, const char* who, const float* motions16, uint32_t n_objects, uint32_t n_all, uint32_t lo, uint32_t hi, ptmm_record* rec) {
-  if (!motions16) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null motions16");
-  if ((uint64_t)n_all * n_objects > (uint64_t)PTMI_MOTION_MAX_RECORDS)
-    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": " + std::to_string(n_all) + " views x " + std::to_string(n_objects) + " objects are more than PTMI_MOTION_MAX_RECORDS motions");
-  ptmm_record unkept;
-  for (uint32_t v = lo; v < hi; v++)
-    for (uint32_t o = 0; o < n_objects; o++)
-      if (!ptmm_make_record(motions16 + 16 * ((size_t)v * n_objects + o), rec ? &rec[(size_t)(v - lo) * n_objects + o] : &unkept))
-        return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the motion of view " + std::to_string(v) + ", object " + std::to_string(o) +
-                                                 " has a non-finite element or a 3x3 with a zero or non-finite determinant: view " + std::to_string(v) + " is read by this call");
-  return PTMI_OK;
-}
-
-// The *_deform calls: the records (include/ptmi_deform.h) of views [lo, hi), lo >= 1 — each from the transforms of its view and of the view before, slot after slot
-// of n_transforms x 32 f32 from `tf0` = slot 0 — view after view into `rec`; rec = nullptr as above.  Allocates nothing.
-static int make_deform_records(ptmi_ctx* c, const char* who, const float* tf0, uint32_t n_transforms, uint32_t n_all, uint32_t lo, uint32_t hi, ptmdf_record* rec) {
-  if ((uint64_t)n_all * n_transforms > (uint64_t)PTMI_MOTION_MAX_RECORDS)
-    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": " + std::to_string(n_all) + " views x " + std::to_string(n_transforms) + " transforms are more than PTMI_MOTION_MAX_RECORDS records");
-  ptmdf_record unkept;
-  for (uint32_t v = lo; v < hi; v++)
-    for (uint32_t o = 0; o < n_transforms; o++)
-      if (!ptmdf_make_record(tf0 + 32 * ((size_t)v * n_transforms + o), tf0 + 32 * ((size_t)(v - 1) * n_transforms + o), rec ? &rec[(size_t)(v - lo) * n_transforms + o] : &unkept))
-        return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the transform of view " + std::to_string(v) + " or of view " + std::to_string(v - 1) + ", object " + std::to_string(o) +
-                                                 ", has an element that is not finite: view " + std::to_string(v) + " is read by this call");
-  return PTMI_OK;
-}
-
 // ptmi_accumulate_views, ptmi_accumulate_views_frames, ptmi_accumulate_views_motion (motion: its motions16 [n_views of the stack][n_objects][16]) and
 // ptmi_accumulate_views_deform (deform: the context's geometry stack, with motion, whose motions16 may then be null with n_objects = 0)
 static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_params* params, const float* views16, const FrameDivisor& F, uint32_t first_view, uint32_t n_views,
@@ -894,7 +894,7 @@ static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_
   const float* motions16 = motion ? motion->motions16 : nullptr;
   const uint32_t n_objects = motion ? motion->n_objects : 0u;
   if (deform && !motions16 && n_objects == 0) motions16 = no_motions;  // (a static world beside the triangles: no entry is read)
-  if (motion && !motions16) return make_motion_records(c, who, nullptr, 0, 0, 0, 0, nullptr);
+  if (motion && !motions16) return null_motions(c, who);
   if (int r = check_stack(c, STACK_MOMENTS, who, 0)) return r;  // (the moment stack first, as ptmi_denoise_views_guided asks)
   if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
   if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
@@ -911,28 +911,19 @@ static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_
   CallTableCounts n = scene_table_counts(c, motion != nullptr);
   const uint32_t n_stack = n.n_views;
   n.frames = F.each;
+  CallRecords q;  // (deform, then motion)
+  q.n_all = n_stack, q.first = first_rec, q.n = end - first_rec;
+  if (motion) q.motion = true, q.motions16 = motions16, q.n_objects = n_objects;
   if (deform) {  // the geometry the call reads: the slots of those views
-    if (!g.n_views) return fail(c, PTMI_ERR_STATE, std::string(who) + ": no geometry stack: ptmi_capture_view_geometry makes it, view by view");
-    if (g.n_views != n_stack) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry stack has " + std::to_string(g.n_views) + " views, the view stack " + std::to_string(n_stack));
-    if (g.n_tris != c->n_tris_uploaded || g.n_xforms != c->h_xforms.size() / 32)
-      return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry stack holds " + std::to_string(g.n_tris) + " triangles and " + std::to_string(g.n_xforms) + " transforms, the scene now " +
-                                         std::to_string(c->n_tris_uploaded) + " and " + std::to_string(c->h_xforms.size() / 32));
-    for (uint32_t v = first_read; v < end; v++)
-      if (!g.captured[v]) return fail(c, PTMI_ERR_STATE, std::string(who) + ": the geometry of view " + std::to_string(v) + " was never captured: view " + std::to_string(v) + " is read by this call");
-    if (int r = make_deform_records(c, who, g.h_xforms.data(), (uint32_t)g.n_xforms, n_stack, first_rec, end, nullptr)) return r;
-    n.deform_records = record_count((uint32_t)g.n_xforms, first_rec, end), n.mesh_words = c->h_meshes.size();
+    if (int r = check_geometry_stack(c, who, n_stack, first_read, end - 1u)) return r;
+    q.deform = true, q.tf0 = g.h_xforms.data(), q.n_transforms = (uint32_t)g.n_xforms, q.mesh_words = c->h_meshes.size();
   }
-  if (motion) {
-    if (int r = make_motion_records(c, who, motions16, n_objects, n_stack, first_rec, end, nullptr)) return r;
-    n.motion_records = record_count(n_objects, first_rec, end);
-  }
+  if (int r = make_call_records(c, who, q, CallTable(), nullptr)) return r;
+  count_call_records(q, &n);
   const CallTable L(n);
   std::vector<uint8_t> tab;
   if (int r = alloc_table(c, who, L, &tab)) return r;
-  if (deform)
-    if (int r = make_deform_records(c, who, g.h_xforms.data(), (uint32_t)g.n_xforms, n_stack, first_rec, end, L.ptr<ptmdf_record>(tab.data(), L.deform))) return r;
-  if (motion)
-    if (int r = make_motion_records(c, who, motions16, n_objects, n_stack, first_rec, end, L.ptr<ptmm_record>(tab.data(), L.motion))) return r;
+  if (int r = make_call_records(c, who, q, L, tab.data())) return r;
   if (int r = fill_views_and_frames(c, who, L, tab.data(), views16, F.frame_nums)) return r;
   fill_scene_parts(c, L, tab.data());
   if (int r = make_stack_with_table(c, who, STACK_ACCUMULATED, tab.data(), L.total)) return r;
@@ -992,23 +983,17 @@ static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_s
   if (!lambertian) n_materials = 0;
   CallTableCounts n;  // (images 1 .. n_images - 1 have a predecessor, with or without history_in: theirs are the records)
   n.n_views = n_images, n.n_materials = n_materials, n.frames = F.each;
-  if (motion) {
-    if (int r = make_motion_records(c, who, motion->motions16, motion->n_objects, n_images, 1, n_images, nullptr)) return r;
-    n.motion_records = record_count(motion->n_objects, 1, n_images);
-  }
-  if (deform) {
-    if (int r = make_deform_records(c, who, deform->transforms_seq, deform->n_transforms, n_images, 1, n_images, nullptr)) return r;
-    n.deform_records = record_count(deform->n_transforms, 1, n_images), n.mesh_words = (size_t)deform->n_meshes * 4;
-  }
+  CallRecords q;
+  q.n_all = n_images, q.first = 1, q.n = n_images - 1u, q.motion_first = true;
+  if (motion) q.motion = true, q.motions16 = motion->motions16, q.n_objects = motion->n_objects;
+  if (deform) q.deform = true, q.tf0 = deform->transforms_seq, q.n_transforms = deform->n_transforms, q.mesh_words = (size_t)deform->n_meshes * 4;
+  if (int r = make_call_records(c, who, q, CallTable(), nullptr)) return r;
+  count_call_records(q, &n);
   const CallTable L(n);
   std::vector<uint8_t> tab;
   if (int r = alloc_table(c, who, L, &tab)) return r;
-  if (motion)
-    if (int r = make_motion_records(c, who, motion->motions16, motion->n_objects, n_images, 1, n_images, L.ptr<ptmm_record>(tab.data(), L.motion))) return r;
-  if (deform) {
-    if (int r = make_deform_records(c, who, deform->transforms_seq, deform->n_transforms, n_images, 1, n_images, L.ptr<ptmdf_record>(tab.data(), L.deform))) return r;
-    call_table_fill_meshes(L, tab.data(), deform->meshes);
-  }
+  if (int r = make_call_records(c, who, q, L, tab.data())) return r;
+  if (deform) call_table_fill_meshes(L, tab.data(), deform->meshes);
   if (int r = fill_views_and_frames(c, who, L, tab.data(), views16, F.frame_nums)) return r;
   call_table_fill_materials(L, tab.data(), lambertian, n_materials);
   const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), F.frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
