@@ -617,6 +617,73 @@ int ptmi_render_aov_frames(ptmi_ctx* ctx, const float* views16, uint32_t n_views
 int ptmi_render_views_until_each(ptmi_ctx* ctx, const float* views16, uint32_t n_views, const uint32_t* first_frames, uint32_t frames_per_round, uint32_t max_frames,
                                  const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out);
 
+/* RENDERING TO A NOISE TARGET BY RUNS.  ptmi_render_views_until_each stops a whole view once its MEAN noise meets the target; inside a view the noise is far from even,
+ * and a view that is done on average still holds regions well above the target.  The calls below sample where the noise is, in units of RUNS.
+ *
+ * A RUN is 64 consecutive pixels of an image in row-major order: run r covers pixels [64 r, min(64 r + 64, npix)), npix = W * H; an image has n_runs = ceil(npix / 64)
+ * of them, and only the last is partial (npix % 64 pixels) when npix is no multiple of 64.  A run's record is the per-pixel integers of THE NOISE STATISTIC above — e
+ * and q unchanged — added up over the run's pixels; a run is MET when it has counted > 0 and (double)sum_q <= (double)target * 65536.0 * (double)counted, the rule
+ * views have, and OPEN otherwise (a run that counted nothing is open).  The arithmetic is include/ptmi_noise.h's, which the kernels and ptmi_run_noise_reference both
+ * compile: they agree integer for integer.
+ *
+ * After these calls a view's pixels no longer share one divisor: pixel p of view v sums M.w frames, its own count in the moment stack.  ptmi_read_view_mean and
+ * ptmi_resolve_view_mean_rgba8 read such a view.  OUT OF SCOPE: the denoise, fuse and accumulate calls on the device stacks take one divisor per view, and after run
+ * rounds they are defined only for a view whose runs all hold the same count; a caller can pass the means (ptmi_read_view_mean) with frame_num = 1 to the *_images
+ * calls.  ptmi_view_noise_stats divides by each pixel's own M.w already and needs no change. */
+struct ptmi_run_noise { /* one run's record: four u32, 16 bytes */
+  uint32_t counted; /* pixels of the run that entered the sums */
+  uint32_t sum_q;   /* sum of q over them: at most 64 * 255 * 65536 */
+  uint32_t max_q;
+  uint32_t open;    /* 1: the run has not met the target, 0: it has */
+};
+typedef struct ptmi_run_noise ptmi_run_noise;
+/* LAYER 1.  Adds frames first_frame .. first_frame + n_frames - 1 of view16 to image `view` of the existing view stack and moment stack, for the pixels of the listed
+ * runs alone: every other pixel of every image keeps its bits.  runs: n_listed run numbers, strictly ascending, each below n_runs (a host array, copied before the call
+ * returns).  A listed pixel receives what ptmi_render_views_frames with reset == 0 would add to it — the same paths (a pixel's frame depends on the pixel, the frame
+ * number, the view and the scene alone), the same sums in frame order, M.w + 1 per frame — however the frames are split into wavefront batches
+ * (ptmi_params.frames_in_flight if set, else the path budget divided by the listed pixels).  Asynchronous on the context's stream; never resets an image.  The batch's
+ * local pixel j is pixel runs[j >> 6] * 64 + (j & 63), n_local = 64 * (n_listed - 1) + (the last listed run is the image's partial run ? npix % 64 : 64) of them;
+ * between k_generate_runs and k_accumulate_runs, the two kernels that need the pixel, the batch runs through the kernels of ptmi_render.  ptmi_stats.paths grows by
+ * n_local * n_frames.  A refused call leaves the stacks as they were.  PTMI_ERR_UNSUPPORTED: a multi-device context or a shard (ptmi_set_shard with world > 1); more
+ * than one sample per frame (num_samples > 1: a later sample's camera ray is rebuilt from the path id by the shard formula).  PTMI_ERR_STATE: moments are off, a stack
+ * is missing.  PTMI_ERR_INVALID_ARG: a null array, a view past the stack, n_frames or n_listed of 0, a run >= n_runs, a list that is not strictly ascending (the
+ * message names the entry). */
+int ptmi_render_view_runs(ptmi_ctx* ctx, const float* view16, uint32_t view, uint32_t first_frame, uint32_t n_frames, const uint32_t* runs, uint32_t n_listed);
+/* LAYER 2.  The records of every run of views [first_view, first_view + n_views) of the view and moment stacks, and per view the ascending list of its open runs;
+ * synchronises.  records, where not NULL: [n_views][n_runs].  n_open: [n_views], the open runs of each view.  open_runs, where not NULL: [n_views][n_runs] — view v's row
+ * holds its n_open[v] open runs in ascending order (so the partial run, if open, comes last), then 0xffffffff.  params = NULL: the defaults; `threshold` is not used.
+ * Two launches on the context's stream: k_run_noise, one wave per (view, run) and one lane per pixel, reduced by shuffles; k_run_list, one block per view, compacting
+ * by ballot and popcount prefixes.  Touches no stack.  PTMI_ERR_UNSUPPORTED: a multi-device context or a shard.  PTMI_ERR_STATE: a stack is missing.
+ * PTMI_ERR_INVALID_ARG: a null n_open, a range past the stack, a target that is negative or not finite, parameters outside their domain. */
+int ptmi_view_run_noise(ptmi_ctx* ctx, const ptmi_noise_params* params, float target, uint32_t first_view, uint32_t n_views, ptmi_run_noise* records, uint32_t* n_open,
+                        uint32_t* open_runs);
+/* The same kernels on host arrays of any size: colour_sums and moments [n_images][h][w][4] f32; the outputs as above with n_runs = ceil(w * h / 64).  Synchronous;
+ * uses device copies of its own.  Errors as above (no PTMI_ERR_STATE, no PTMI_ERR_UNSUPPORTED). */
+int ptmi_run_noise_images(ptmi_ctx* ctx, const float* colour_sums, const float* moments, int w, int h, uint32_t n_images, const ptmi_noise_params* params, float target,
+                          ptmi_run_noise* records, uint32_t* n_open, uint32_t* open_runs);
+/* LAYER 3.  Every RUN of every view to the target:
+ *   A       one ptmi_render_views_frames call — the batched path across views — with min(min_frames, max_frames) frames of every view from first_frames[v]
+ *           (first_frames == NULL: 0), with reset; frames_done[v] = that count.
+ *   rounds  k_run_noise + k_run_list over the views that may still get frames; only the per-view counts come back to the host.  Every view with an open run and
+ *           frames_done[v] < max_frames gets ONE layer-1 batch straight from its device list: nf = min(frames_per_round, max_frames - frames_done[v]) frames numbered
+ *           from first_frames[v] + frames_done[v]; frames_done[v] += nf.  The call returns when no view has an open run below max_frames.
+ * A met run is never sampled again, so its record cannot change and it stays met: all open runs of a view hold the same count, frames_done[v] — THE MOST ANY RUN OF THE
+ * VIEW GOT (n_views entries); a pixel's own count is its M.w.  out, where not NULL: ptmi_view_noise_stats of all views at the end.  *paths_traced, where not NULL:
+ * n_views * npix * phase A's frames + the sum over the run batches of n_local * nf.
+ * min_frames >= 2 answers the caveat of the view statistic — frames that are mostly black agree at first and read too low: no run is judged on fewer frames; pooling
+ * 64 pixels answers it further, since a run is met on its pixels' mean, not on a lucky pixel.  Per-view batches in the rounds give up the cross-view batching of phase
+ * A: the saving is in paths, and whether it survives in wall time depends on how small the batches get.
+ * Errors: those of ptmi_render_view_runs for the context (before anything is rendered), and PTMI_ERR_INVALID_ARG for a null views16 or frames_done, n_views,
+ * frames_per_round or max_frames of 0, min_frames < 2, n_views * max_frames >= 2^31, a target that is negative or not finite, parameters outside their domain. */
+int ptmi_render_views_until_runs(ptmi_ctx* ctx, const float* views16, uint32_t n_views, const uint32_t* first_frames, uint32_t frames_per_round, uint32_t min_frames,
+                                 uint32_t max_frames, const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out, uint64_t* paths_traced);
+/* Image `view` with every pixel's own divisor: rgb = S.rgb / M.w, 0 where M.w == 0; w = M.w.  Synchronises; bytes must be W*H*16.  Single-device, unsharded contexts;
+ * PTMI_ERR_STATE: a stack is missing. */
+int ptmi_read_view_mean(ptmi_ctx* ctx, uint32_t view, float* dst, size_t bytes);
+/* The display pass (ptmi_resolve_rgba8) for image `view` with the pixel's own divisor M.w in place of frame_num (a pixel with M.w == 0 is black); where every count
+ * equals frame_num, the bytes are ptmi_resolve_view_rgba8's.  bytes must be W*H*4. */
+int ptmi_resolve_view_mean_rgba8(ptmi_ctx* ctx, uint32_t view, uint8_t* dst, size_t bytes);
+
 /* CONSUMERS WITH PER-VIEW FRAME COUNTS.  The four calls on the stacks, their *_images forms and their CPU references with one divisor PER VIEW in place of the one
  * frame_num: everywhere a definition above divides a colour sum S by F — "prepare" (c = S.rgb / F), the denoisers' remodulation and pass-through (S.rgb / F, S.a / F),
  * "Fusion" steps 2-3 and its pass-through, "Temporal accumulation" own, mean and pass-through — it divides by F_u, THE FRAME COUNT OF THE VIEW u THAT S BELONGS TO: the
@@ -1108,6 +1175,10 @@ int ptmi_denoise_accumulated_reference(const float* means, const float* plane2, 
  * same bits and the same integers.  PTMI_ERR_INVALID_ARG as there. */
 int ptmi_noise_reference(const float* colour_sums, const float* moments, int w, int h, uint32_t n_images, const ptmi_noise_params* params, ptmi_view_noise* out,
                          float* map_out);
+/* ptmi_run_noise_images without a GPU: the same loop with the integers added up per run, the open runs listed per image — the same arguments, the same integers, the
+ * same lists.  records and open_runs may be NULL.  PTMI_ERR_INVALID_ARG as there. */
+int ptmi_run_noise_reference(const float* colour_sums, const float* moments, int w, int h, uint32_t n_images, const ptmi_noise_params* params, float target,
+                             ptmi_run_noise* records, uint32_t* n_open, uint32_t* open_runs);
 
 /* OBJ text -> de-indexed vertex / normal arrays with the reference's accepted grammar and quirks
  * (lib/primitives/objReader.js:10-68: `v`, `vn`, `f a/b/c` triangles; tokens go through JS Number()).  The arrays are

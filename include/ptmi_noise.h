@@ -69,4 +69,36 @@ PTM_HD int ptmn_target_met(uint64_t counted, uint64_t sum_q, float target) {
   return counted > 0 && (double)sum_q <= (double)target * 65536.0 * (double)counted;
 }
 
+/*
+ * RUNS (ptmi_view_run_noise / ptmi_run_noise_images / ptmi_run_noise_reference, ptmi_render_views_until_runs).  A run is 64 consecutive pixels of an image in
+ * row-major order: run r covers pixels [64 r, min(64 r + 64, npix)), an image has ceil(npix / 64) of them, and only the last can be partial.  A run's record is the
+ * per-pixel integers above — e by ptmn_error, q by ptmn_quantise, both as they are — added up over the run's pixels: counted, sum_q (at most 64 * 255 * 65536 < 2^32)
+ * and max_q.  A run is MET when ptmn_target_met(counted, sum_q, target) holds — a run that counted nothing is not met, the rule views have — and OPEN otherwise.
+ */
+#define PTMN_RUN_PIXELS 64u
+
+typedef struct ptmn_run {
+  uint32_t counted, sum_q, max_q;
+} ptmn_run;
+
+PTM_HD uint32_t ptmn_run_count(uint32_t npix) { return (npix + PTMN_RUN_PIXELS - 1u) / PTMN_RUN_PIXELS; }
+
+/* one pixel's e (ptmn_error: NaN = not counted) into its run's record */
+PTM_HD void ptmn_run_add(ptmn_run* r, float e) {
+  if (e != e) return;
+  const uint32_t q = ptmn_quantise(e);
+  r->counted += 1u;
+  r->sum_q += q;
+  r->max_q = r->max_q > q ? r->max_q : q;
+}
+
+PTM_HD int ptmn_run_open(ptmn_run r, float target) { return !ptmn_target_met(r.counted, r.sum_q, target); }
+
+/* The pixels an ascending list of n_listed runs names, of which `last` is the highest: 64 per run, but for the image's partial run what it has */
+PTM_HD uint32_t ptmn_runs_pixels(uint32_t n_listed, uint32_t last, uint32_t npix) {
+  if (n_listed == 0u) return 0u;
+  const uint32_t tail = npix % PTMN_RUN_PIXELS;
+  return PTMN_RUN_PIXELS * (n_listed - 1u) + (tail != 0u && last == ptmn_run_count(npix) - 1u ? tail : PTMN_RUN_PIXELS);
+}
+
 #endif /* PTMI_NOISE_H */

@@ -817,11 +817,25 @@ struct ViewBatch {
   bool tab = false;
 };
 
+// A run batch (ptmi_render_view_runs): one view — view16, frame numbers from frame0, as a lone-view batch — whose local pixels are those of `list`, a device array of
+// ascending run numbers (run_pixel, ptmi_device.h), n_local of them in all; its frames are ADDED to `image` and `moments`, the view's own images in the two stacks.
+// Between k_generate_runs and k_accumulate_runs the batch is a lone-view batch of n_local pixels: the VK_ONE instances work on path ids and never ask for the pixel.
+struct RunBatch {
+  const uint32_t* list;
+  uint32_t n_local;
+  float4 *image, *moments;
+};
+
 // `fold` = how many of the batch's leading frames are added to the framebuffer now (-1 = all of them); dry_steps > 0: placement_search's timing run
-int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames, int reset_first, int fold = -1, int dry_steps = 0, const ViewBatch* views = nullptr) {
+int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames, int reset_first, int fold = -1, int dry_steps = 0, const ViewBatch* views = nullptr,
+                 const RunBatch* runs = nullptr) {
   const ptmi_params& p = c->prm;
   c->ahead.valid = false;  // the path buffers are about to be overwritten
-  const RenderConst rc = make_render_const(c, view16, frame0, n_frames, reset_first);
+  const RenderConst rc = [&] {
+    RenderConst r = make_render_const(c, view16, frame0, n_frames, reset_first);
+    if (runs) r.n_local = runs->n_local;
+    return r;
+  }();
   if (rc.n_local == 0) return PTMI_OK;
   ViewTab vtab{};
   if (views) vtab = views->vt, vtab.n_local = rc.n_local;
@@ -884,7 +898,7 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     c->placement_pending = false;
     if (total > tail.limit_first) {  // (a batch that k_tail takes whole reads its queue once: nothing to search for)
       // (two steps: the whole batch as the probe — eight steps — chose no better: profiles/r05_placement_dry_run.txt)
-      int r = placement_search(c, [&]() { return render_batch(c, view16, frame0, n_frames, reset_first, fold, 2, views); });
+      int r = placement_search(c, [&]() { return render_batch(c, view16, frame0, n_frames, reset_first, fold, 2, views, runs); });
       if (r) return r;
     }
   }
@@ -901,6 +915,9 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
         else return &k_generate_views<cn>;
       }, tab, c->counters);
       hipLaunchKernelGGL(generate, dim3(ew_grid), dim3(kBlock), 0, c->stream, c->S, rc, paths_of(c, 0, rc.num_samples > 1), ctl, c->d_heads.as<uint32_t>(), tot, vtab);
+    } else if (runs) {
+      const auto generate = with_flags([](auto cn) { return &k_generate_runs<cn>; }, c->counters);
+      hipLaunchKernelGGL(generate, dim3(ew_grid), dim3(kBlock), 0, c->stream, c->S, rc, paths_of(c, 0, rc.num_samples > 1), ctl, c->d_heads.as<uint32_t>(), tot, runs->list);
     } else {
       const auto generate = with_flags([](auto cn) { return &k_generate<cn>; }, c->counters);
       hipLaunchKernelGGL(generate, dim3(ew_grid), dim3(kBlock), 0, c->stream, c->S, rc, paths_of(c, 0, rc.num_samples > 1), ctl, c->d_heads.as<uint32_t>(), tot);
@@ -969,6 +986,8 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     else if (views && views->moments)
       hipLaunchKernelGGL(k_accumulate_moments, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), views->stack, views->moments, n_steps, tot, 0, f_end, vtab);
     else if (views) hipLaunchKernelGGL(k_accumulate<true>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), views->stack, n_steps, tot, 0, f_end, vtab);
+    else if (runs)
+      hipLaunchKernelGGL(k_accumulate_runs, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), runs->image, runs->moments, runs->list, n_steps, tot, 0, f_end);
     else hipLaunchKernelGGL(k_accumulate<false>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), c->fb, n_steps, tot, 0, f_end, vtab);
     c->stats.accumulate_launches++;
   }
@@ -1497,6 +1516,7 @@ void ptmi_destroy(ptmi_ctx* c) {
   c->view_rows.release();
   c->fuse_tab.release();
   c->denoise_tab.release();
+  c->run_tab.release();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;  // its device buffers (DBuf) are freed here, with its device current and its stream drained
 }
@@ -2030,6 +2050,119 @@ int ptmi_render_views_frames(ptmi_ctx* c, const float* views16, uint32_t n_views
   ViewFrames vf{first_frames, frame_counts, 0u};
   if (int r = check_view_frames(c, "ptmi_render_views_frames", views16, n_views, first_frames, frame_counts, &vf.n_slots)) return r;
   return on_all_devices(c, [=](ptmi_ctx* q) { return render_views_one(q, views16, n_views, 0u, 0u, reset, &vf); }, true);
+}
+
+}  // extern "C"
+
+// ---- run batches (ptmi_render_view_runs, ptmi_render_views_until_runs) ----
+// What a call that renders runs asks of the context, in this order; nothing is enqueued or changed by the check.
+int check_run_render(ptmi_ctx* c, const char* who, const uint32_t* view) {
+  if (!c->peers.empty() || c->multi) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a multi-device context keeps a view's runs on several GPUs");
+  if (c->world > 1) return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": a sharded context (ptmi_set_shard) keeps a view's runs in several processes");
+  static const float kUnit[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  const int traced = make_render_const(c, kUnit, 0, 1, 0).num_samples;  // (side * side when stratified)
+  if (traced > 1)
+    return fail(c, PTMI_ERR_UNSUPPORTED, std::string(who) + ": num_samples " + std::to_string(traced) +
+                                             ": a later sample's camera ray is rebuilt from the path id by the shard formula; runs need one sample per frame");
+  if (!c->view_moments) return fail(c, PTMI_ERR_STATE, std::string(who) + ": moments are off: call ptmi_set_view_moments first");
+  if (!view) return PTMI_OK;  // (the caller makes the stacks itself)
+  if (int r = check_stack(c, STACK_VIEWS, who, *view)) return r;
+  return check_stack(c, STACK_MOMENTS, who, *view);
+}
+
+// n_frames more frames of `view16`, numbered from first_frame, for the n_local pixels of the runs in `d_list` (a device array the stream has written by the time the
+// batch reads it), added to image `view` of the view and moment stacks.  render_one's loop over batches; the caller has run check_run_render.
+int render_runs_enqueue(ptmi_ctx* c, const float* view16, uint32_t view, uint32_t first_frame, uint32_t n_frames, const uint32_t* d_list, uint32_t n_local) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();  // a stale error of an earlier, already reported failure must not be blamed on this call
+  int r = prepare_scene(c);
+  if (r) return r;
+  r = check_renderable(c);
+  if (r) return r;
+  if (n_local == 0 || n_frames == 0) return PTMI_OK;
+  const size_t npix = (size_t)c->W * (size_t)c->H;
+  const RunBatch rb{d_list, n_local, c->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)view * npix, c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)view * npix};
+  // (the same budget of frames per wavefront pass as render_one's, for the listed pixels, and the same halving)
+  uint32_t F = c->prm.frames_in_flight > 0 ? (uint32_t)c->prm.frames_in_flight : (uint32_t)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)1 << c->tun.path_budget_log2) / n_local));
+  F = (uint32_t)std::min<size_t>(F, std::max<size_t>(1, ((size_t)1 << 31) / n_local));
+  for (uint32_t done = 0; done < n_frames;) {
+    const uint32_t nb = std::min(F, n_frames - done);
+    r = render_batch(c, view16, first_frame + done, (int)nb, 0, -1, 0, nullptr, &rb);
+    if (r == PTMI_ERR_NO_MEMORY && !c->batch_enqueued && nb > 1 && c->prm.frames_in_flight <= 0) {
+      F = std::max<uint32_t>(1, nb / 2);
+      continue;
+    }
+    if (r) return r;
+    done += nb;
+  }
+  return PTMI_OK;
+}
+
+extern "C" {
+
+int ptmi_render_view_runs(ptmi_ctx* c, const float* view16, uint32_t view, uint32_t first_frame, uint32_t n_frames, const uint32_t* runs, uint32_t n_listed) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  if (!view16 || !runs) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_view_runs: null argument");
+  if (n_frames == 0 || n_listed == 0) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_view_runs: need n_frames >= 1 and n_listed >= 1");
+  if (int r = check_run_render(c, "ptmi_render_view_runs", &view)) return r;
+  const uint32_t npix = (uint32_t)c->W * (uint32_t)c->H, n_runs = (npix + kRunPixels - 1) / kRunPixels;
+  for (uint32_t i = 0; i < n_listed; i++) {
+    if (runs[i] >= n_runs)
+      return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_view_runs: runs[" + std::to_string(i) + "] = " + std::to_string(runs[i]) + ": the image has " + std::to_string(n_runs) + " runs");
+    if (i && runs[i] <= runs[i - 1])
+      return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_render_view_runs: runs[" + std::to_string(i) + "] = " + std::to_string(runs[i]) + " after " + std::to_string(runs[i - 1]) + ": the list must be strictly ascending");
+  }
+  const uint32_t last_pixels = runs[n_listed - 1] == n_runs - 1 && npix % kRunPixels ? npix % kRunPixels : kRunPixels;
+  const uint32_t n_local = kRunPixels * (n_listed - 1) + last_pixels;
+  HIP_TRY(c, hipSetDevice(c->device));
+  uint32_t* staged = nullptr;
+  HIP_TRY(c, c->run_tab.stage((size_t)n_listed * 4, c->stream, (void**)&staged));
+  memcpy(staged, runs, (size_t)n_listed * 4);
+  if (int r = prepare_scene(c)) return r;  // (what can refuse the call does so before the list is on the stream)
+  if (int r = check_renderable(c)) return r;
+  HIP_TRY(c, c->run_tab.send((size_t)n_listed * 4, c->stream));
+  return render_runs_enqueue(c, view16, view, first_frame, n_frames, c->run_tab.dev.as<uint32_t>(), n_local);
+}
+
+// The per-pixel means of image `view`: k_view_mean into a device image of the call's own, then to the host; synchronises.
+int ptmi_read_view_mean(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_view_mean: null argument");
+  if (!c->peers.empty() || c->multi) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_read_view_mean: a multi-device context keeps a view's pixels on several GPUs");
+  if (c->world > 1) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_read_view_mean: a sharded context (ptmi_set_shard) keeps a view's pixels in several processes");
+  if (int r = check_stack(c, STACK_VIEWS, "ptmi_read_view_mean", view)) return r;
+  if (int r = check_stack(c, STACK_MOMENTS, "ptmi_read_view_mean", view)) return r;
+  const size_t npix = (size_t)c->W * (size_t)c->H;
+  if (bytes != npix * 16) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_read_view_mean: bytes must be W*H*16");
+  HIP_TRY(c, hipSetDevice(c->device));
+  DBuf tmp;
+  HIP_TRY(c, tmp.ensure(bytes));
+  hipLaunchKernelGGL(k_view_mean, dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, c->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)view * npix,
+                     c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)view * npix, (uint32_t)npix, tmp.as<float4>());
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(dst, tmp.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  drain_spans(c);
+  return check_queue_overflow(c);
+}
+
+int ptmi_resolve_view_mean_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t bytes) {
+  if (!c || !dst) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_view_mean_rgba8: null argument");
+  if (!c->peers.empty() || c->multi) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_resolve_view_mean_rgba8: a multi-device context keeps a view's pixels on several GPUs");
+  if (c->world > 1) return fail(c, PTMI_ERR_UNSUPPORTED, "ptmi_resolve_view_mean_rgba8: a sharded context (ptmi_set_shard) keeps a view's pixels in several processes");
+  if (int r = check_stack(c, STACK_VIEWS, "ptmi_resolve_view_mean_rgba8", view)) return r;
+  if (int r = check_stack(c, STACK_MOMENTS, "ptmi_resolve_view_mean_rgba8", view)) return r;
+  const size_t npix = (size_t)c->W * (size_t)c->H;
+  if (bytes != npix * 4) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_resolve_view_mean_rgba8: bytes must be W*H*4");
+  HIP_TRY(c, hipSetDevice(c->device));
+  DBuf tmp;
+  HIP_TRY(c, tmp.ensure(bytes));
+  hipLaunchKernelGGL(k_resolve_mean_rgba8, dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, c->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)view * npix,
+                     c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)view * npix, (uint32_t)npix, tmp.as<uchar4>());
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(dst, tmp.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  drain_spans(c);
+  return check_queue_overflow(c);
 }
 
 int ptmi_read_view(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_VIEWS, "ptmi_read_view", view, 0, dst, bytes); }

@@ -153,6 +153,8 @@ struct ptmi_ctx {
   } geometry;
   bool view_moments = false;  // ptmi_set_view_moments: ptmi_render_views folds second moments into stacks[STACK_MOMENTS] too
   DBuf d_noise_rec;           // ptmi_view_noise_stats: one record (kNoiseRecordBytes) per view of the call
+  StagedTable run_tab;        // the last ptmi_render_view_runs call's run list: one u32 per listed run
+  DBuf d_run_noise;           // ptmi_view_run_noise / ptmi_render_views_until_runs: per view of the call the runs' records, its list of open runs and its header (RunNoiseLayout)
   int rank = 0, world = 1, tile = 64;
 
   size_t path_cap = 0;
@@ -238,6 +240,10 @@ PTMI_HIDDEN int release_stack(ptmi_ctx* c, StackKind k);
 PTMI_HIDDEN void drain_spans(ptmi_ctx* c);          // with the stream idle: the timing spans go into c's stats
 PTMI_HIDDEN int check_queue_overflow(ptmi_ctx* c);  // with the stream idle: PTMI_ERR_STATE if a render dropped paths
 PTMI_HIDDEN uint32_t count_local(uint32_t npix, int rank, int world, int tile);  // the pixels p of npix with (p / tile) % world == rank
+// Run batches (ptmi_render_view_runs): what such a call asks of the context (one device, no shard, one sample per frame, moments on, both stacks with *view — view == nullptr: the caller makes the stacks), and the
+// batches themselves — n_frames more frames of view16 from first_frame for the n_local pixels of the ascending device list d_list, added to image `view` of both stacks.
+PTMI_HIDDEN int check_run_render(ptmi_ctx* c, const char* who, const uint32_t* view);
+PTMI_HIDDEN int render_runs_enqueue(ptmi_ctx* c, const float* view16, uint32_t view, uint32_t first_frame, uint32_t n_frames, const uint32_t* d_list, uint32_t n_local);
 
 // fn(ctx) on the context itself and on every peer; `parallel` = one host thread per device, so that calls which block
 // (allocation, the occasional queue-length readback of a long render) do not serialise the GPUs.

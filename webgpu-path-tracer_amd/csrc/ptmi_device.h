@@ -532,6 +532,20 @@ DEV ViewRec load_view_rec(const ViewTab& vt, uint32_t v) {
   const float4 r = __ballot(v != vu) == 0ull ? ldu(recs + vu) : recs[v];
   return ViewRec{__float_as_uint(r.x), __float_as_uint(r.y), __float_as_uint(r.z), __float_as_uint(r.w)};
 }
+// ---- run batches (ptmi_render_view_runs) ---------------------------------------------------------------
+// A batch of one view whose local pixels come from a LIST OF RUNS instead of the shard formula: a run is 64 consecutive pixels of the image in row-major order, the
+// list is strictly ascending, and local pixel j is pixel runs[j >> 6] * 64 + (j & 63).  Only the image's last run can be partial, and in an ascending list it comes
+// last: n_local counts exactly the listed pixels.  Two kernels need the pixel (k_generate_runs, k_accumulate_runs); everything between them works on path ids.
+constexpr uint32_t kRunPixels = 64;
+enum PixelMap : int { PX_SHARD = 0, PX_RUNS = 1 };  // local_to_pixel / run_pixel
+// The lanes of a wave nearly always agree on the list entry (64 neighbours of one run; a wave of k_generate_runs straddles two where n_local is no multiple of 64):
+// then it comes through a scalar load, as load_view_row's row.  The list is written before the launch (an upload, or k_run_list in an earlier launch).
+DEV uint32_t run_pixel(const uint32_t* __restrict__ runs, uint32_t j) {
+  const uint32_t k = j >> 6, ku = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
+  const uint32_t r = __ballot(k != ku) == 0ull ? (uint32_t)ldu(reinterpret_cast<const int*>(runs) + ku) : runs[k];
+  return r * kRunPixels + (j & 63u);
+}
+
 template <int MV>
 DEV uint32_t view_of_path(const ViewTab& vt, uint32_t pid) {
   if (MV == VK_TAB) return view_of_slot(vt, vt.slot0 + pid / vt.n_local);

@@ -1398,6 +1398,39 @@ extern "C" int ptmi_noise_reference(const float* colour_sums, const float* momen
   return PTMI_OK;
 }
 
+// ptmi_run_noise_images without a GPU: the same loop, the integers added up per run of 64 pixels (include/ptmi_noise.h, "RUNS"), and each image's open runs listed in
+// ascending order, the rest of its row 0xffffffff.
+extern "C" int ptmi_run_noise_reference(const float* colour_sums, const float* moments, int w, int h, uint32_t n_images, const ptmi_noise_params* params, float target,
+                                        ptmi_run_noise* records, uint32_t* n_open, uint32_t* open_runs) {
+  if (!colour_sums || !moments || !n_open || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
+  if (!(target >= 0.0f) || !ptmn_finite(target)) return PTMI_ERR_INVALID_ARG;
+  ptmi_noise_params P;
+  if (params) P = *params;
+  else ptmi_default_noise_params(&P);
+  if (!ptmn_params_ok(P.floor, P.threshold)) return PTMI_ERR_INVALID_ARG;
+  const uint32_t npix = (uint32_t)w * (uint32_t)h, n_runs = ptmn_run_count(npix);
+  const ptmn_f4* S = reinterpret_cast<const ptmn_f4*>(colour_sums);
+  const ptmn_f4* M = reinterpret_cast<const ptmn_f4*>(moments);
+  for (uint32_t v = 0; v < n_images; v++) {
+    uint32_t open = 0;
+    for (uint32_t run = 0; run < n_runs; run++) {
+      ptmn_run r = {0u, 0u, 0u};
+      const uint32_t p_end = std::min(npix, (run + 1u) * PTMN_RUN_PIXELS);
+      for (uint32_t p = run * PTMN_RUN_PIXELS; p < p_end; p++) ptmn_run_add(&r, ptmn_error(S[(size_t)v * npix + p], M[(size_t)v * npix + p], P.floor));
+      const bool is_open = ptmn_run_open(r, target) != 0;
+      if (records) records[(size_t)v * n_runs + run] = ptmi_run_noise{r.counted, r.sum_q, r.max_q, is_open ? 1u : 0u};
+      if (is_open) {
+        if (open_runs) open_runs[(size_t)v * n_runs + open] = run;
+        open++;
+      }
+    }
+    if (open_runs)
+      for (uint32_t k = open; k < n_runs; k++) open_runs[(size_t)v * n_runs + k] = 0xffffffffu;
+    n_open[v] = open;
+  }
+  return PTMI_OK;
+}
+
 // ---- the slot table of a multi-view call with per-view frame numbers and counts (ptmi_render_views_frames, ptmi_render_aov_frames) ----
 // The layout is include/ptmi.h's (ptmi_view_slot_plan); the kernels read it through ptmi_device.h's ViewTab.  Everything is checked before anything is written.
 extern "C" int ptmi_view_slot_plan(uint32_t n_views, const uint32_t* first_frames, const uint32_t* frame_counts, uint32_t* table, size_t table_words, uint32_t* n_slots) {

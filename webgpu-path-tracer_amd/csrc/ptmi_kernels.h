@@ -42,8 +42,11 @@ DEV uint32_t* rng0_of(const Paths& P) { return reinterpret_cast<uint32_t*>(P.in.
 // one integer division — and stepped from slot to slot; the view's row is loaded anew only where the view changes (every slot with one frame per view).
 // Every render kernel comes twice: under its own name for a batch with one view — rc carries it, the ViewTab is empty and never read — and as k_*_views, the MV
 // instances of the same body with the table as one more argument (ptmi_render_views).
-template <bool COUNT, int MV>
-DEV void generate_body(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads, unsigned long long* __restrict__ totals, ViewTab vt) {
+// PX (PixelMap): where a local pixel lies in the image — PX_SHARD: the shard formula (local_to_pixel), PX_RUNS: the batch's run list (run_pixel; `runs` is read by
+// that instance alone, the others are handed nullptr and compile to what they were without the argument).
+template <bool COUNT, int MV, int PX = PX_SHARD>
+DEV void generate_body(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads, unsigned long long* __restrict__ totals, ViewTab vt,
+                       const uint32_t* __restrict__ runs = nullptr) {
   reset_heads(heads);
   const bool trace = rc.max_bounces > 0;  // MAX_BOUNCES = 0: ray_color's loop body never runs, no hitScene at all
   uint32_t total = rc.n_local * (uint32_t)rc.n_frames;
@@ -55,7 +58,7 @@ DEV void generate_body(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict_
   const uint32_t chunks = ((uint32_t)rc.n_frames + kGenFrames - 1u) / kGenFrames, work = rc.n_local * chunks;
   for (uint32_t w = blockIdx.x * kBlock + threadIdx.x; w < work; w += gridDim.x * kBlock) {
    const uint32_t chunk = w / rc.n_local, j = w - chunk * rc.n_local;
-   const uint32_t pix = local_to_pixel(rc, j);
+   const uint32_t pix = PX == PX_RUNS ? run_pixel(runs, j) : local_to_pixel(rc, j);
    float px, py;
    camera_pixel(rc, pix, px, py);
    const uint32_t f_end = min((chunk + 1u) * kGenFrames, (uint32_t)rc.n_frames);
@@ -136,6 +139,13 @@ template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_generate_frames(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
                                                             unsigned long long* __restrict__ totals, ViewTab vt) {
   generate_body<COUNT, VK_TAB>(S, rc, P, ctl, heads, totals, vt);
+}
+
+// ... of a run batch (ptmi_render_view_runs): one view, rc carries it as it does for k_generate; the pixels are those of the listed runs
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_generate_runs(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
+                                                          unsigned long long* __restrict__ totals, const uint32_t* __restrict__ runs) {
+  generate_body<COUNT, VK_ONE, PX_RUNS>(S, rc, P, ctl, heads, totals, ViewTab{}, runs);
 }
 
 // 96 VGPRs (5 waves/SIMD, no spills) measured 27 % faster than the compiler's default 106 VGPRs / 4 waves: the kernel
@@ -1738,6 +1748,51 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_frames(RenderConst rc, Pa
   }
 }
 
+// k_accumulate_moments for a run batch (ptmi_render_view_runs): one view, no reset and no view change — `fb` and `mom` are the view's own images, the lane's pixel is
+// the run list's (run_pixel), and the frames ADD to what both hold.  The arithmetic is k_accumulate_moments': frame order, the colours fetched eight ahead, the square a
+// product and then an add, m.w + 1.0f per frame.  (An entry of its own for the reason given above k_accumulate.)
+__global__ __launch_bounds__(kBlock) void k_accumulate_runs(RenderConst rc, Paths P, float4* __restrict__ fb, float4* __restrict__ mom, const uint32_t* __restrict__ runs,
+                                                            int n_steps, unsigned long long* __restrict__ totals, int f_begin, int f_end) {
+  for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < rc.n_local; j += gridDim.x * kBlock) {
+    if (f_begin >= f_end) break;
+    const uint32_t pix = run_pixel(runs, j);
+    f3 c = mk3(fb[pix]);
+    float4 m = mom[pix];
+    constexpr int kAhead = 8;
+    for (int f0 = f_begin; f0 < f_end; f0 += kAhead) {
+      bool have[kAhead];
+      float4 colv[kAhead];
+#pragma unroll
+      for (int k = 0; k < kAhead; k++) {
+        const int f = f0 + k;
+        have[k] = f < f_end && (!P.touched || P.touched[(size_t)f * rc.n_local + j]);
+      }
+#pragma unroll
+      for (int k = 0; k < kAhead; k++) {
+        colv[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // a path that never wrote its acc_radiance returned (0,0,0)
+        if (have[k]) colv[k] = P.acc[(size_t)(f0 + k) * rc.n_local + j];
+      }
+#pragma unroll
+      for (int k = 0; k < kAhead; k++) {
+        if (f0 + k >= f_end) break;
+        const f3 col = mk3(colv[k]);
+        const f3 sq = mk3(col.x * col.x, col.y * col.y, col.z * col.z);
+        c = c + col;
+        m = make_float4(m.x + sq.x, m.y + sq.y, m.z + sq.z, m.w + 1.0f);
+      }
+    }
+    fb[pix] = make_float4(c.x, c.y, c.z, 1.0f);
+    mom[pix] = m;
+  }
+  if (f_begin == 0 && blockIdx.x == 0 && threadIdx.x == 0) {  // the slot-0 tally, as k_accumulate's
+    unsigned long long rays = 0;
+    if (n_steps > 0)
+      for (int k = 0; k < kTallyLines; k++) rays += *tally_line(totals, (uint32_t)k);
+    totals[0] += rays;
+    totals[1] += (unsigned long long)rc.n_local * (unsigned long long)rc.n_frames * (unsigned long long)rc.num_samples;
+  }
+}
+
 // Upload-time digest: the unit normal resolve_hit needs for a quad hit (common.wgsl:176), computed once per quad by the
 // same device function the shading path would call per hit — same instructions, same bits.
 __global__ void k_quad_digest(const float4* __restrict__ quads, int n, float4* __restrict__ unit_n, float4* __restrict__ onb) {
@@ -1896,10 +1951,7 @@ __global__ __launch_bounds__(256) void k_selftest(int which, unsigned long long*
 }
 
 // shaders/fragment.js:22-36 + shaders/common.wgsl:273-282: colour = fb/frameNum -> ACES approx -> gamma
-__global__ __launch_bounds__(kBlock) void k_resolve_rgba8(const float4* __restrict__ fb, uint32_t npix, float frame_num, uchar4* __restrict__ out) {
-  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= npix) return;
-  float4 c = fb[i];
+DEV uchar4 resolve_pixel(float4 c, float frame_num) {
   float v[3] = {c.x / frame_num, c.y / frame_num, c.z / frame_num};
   unsigned char q[3];
   const float inv_gamma = 1 / 2.2;
@@ -1913,7 +1965,29 @@ __global__ __launch_bounds__(kBlock) void k_resolve_rgba8(const float4* __restri
     s = ptm_min(ptm_max(s, 0.0f), 255.0f);
     q[k] = (unsigned char)s;
   }
-  out[i] = make_uchar4(q[0], q[1], q[2], 255);
+  return make_uchar4(q[0], q[1], q[2], 255);
+}
+__global__ __launch_bounds__(kBlock) void k_resolve_rgba8(const float4* __restrict__ fb, uint32_t npix, float frame_num, uchar4* __restrict__ out) {
+  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= npix) return;
+  out[i] = resolve_pixel(fb[i], frame_num);
+}
+
+// ... with every pixel's own divisor, the frame count in its moment-stack pixel (ptmi_resolve_view_mean_rgba8): after ptmi_render_view_runs a view's pixels no longer
+// share one.  A pixel without a frame (M.w == 0) resolves as black — the mean ptmi_read_view_mean gives it.
+__global__ __launch_bounds__(kBlock) void k_resolve_mean_rgba8(const float4* __restrict__ fb, const float4* __restrict__ mom, uint32_t npix, uchar4* __restrict__ out) {
+  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= npix) return;
+  const float n = mom[i].w;
+  out[i] = n == 0.0f ? resolve_pixel(make_float4(0.0f, 0.0f, 0.0f, 0.0f), 1.0f) : resolve_pixel(fb[i], n);
+}
+// rgb = S.rgb / M.w per pixel, 0 where M.w == 0; w = M.w (ptmi_read_view_mean)
+__global__ __launch_bounds__(kBlock) void k_view_mean(const float4* __restrict__ fb, const float4* __restrict__ mom, uint32_t npix, float4* __restrict__ out) {
+  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= npix) return;
+  const float4 s = fb[i];
+  const float n = mom[i].w;
+  out[i] = n == 0.0f ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(s.x / n, s.y / n, s.z / n, n);
 }
 
 }  // namespace ptmi

@@ -78,6 +78,10 @@ FN(ptmi_render_views_until)
 FN(ptmi_render_views_frames)
 FN(ptmi_render_aov_frames)
 FN(ptmi_render_views_until_each)
+FN(ptmi_render_view_runs)
+FN(ptmi_view_run_noise)
+FN(ptmi_render_views_until_runs)
+FN(ptmi_read_view_mean)
 FN(ptmi_synchronize)
 FN(ptmi_read_framebuffer)
 FN(ptmi_write_framebuffer)
@@ -129,6 +133,7 @@ static int load_lib(char* err, size_t errlen) {
   LOAD(ptmi_version) LOAD(ptmi_last_error) LOAD(ptmi_create) LOAD(ptmi_create_multi) LOAD(ptmi_prepare) LOAD(ptmi_destroy) LOAD(ptmi_default_params) LOAD(ptmi_default_denoise_params) LOAD(ptmi_set_params)
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
   LOAD(ptmi_render_views_frames) LOAD(ptmi_render_aov_frames) LOAD(ptmi_render_views_until_each)
+  LOAD(ptmi_render_view_runs) LOAD(ptmi_view_run_noise) LOAD(ptmi_render_views_until_runs) LOAD(ptmi_read_view_mean)
   LOAD(ptmi_views_device_ptr) LOAD(ptmi_denoise_views_frames) LOAD(ptmi_denoise_views_guided_frames) LOAD(ptmi_fuse_views_frames) LOAD(ptmi_accumulate_views_frames) LOAD(ptmi_accumulate_views_motion) LOAD(ptmi_accumulate_views_deform) LOAD(ptmi_capture_view_geometry) LOAD(ptmi_fuse_views_motion) LOAD(ptmi_fuse_views_deform)
   LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_default_guided_params) LOAD(ptmi_denoise_views_guided) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_default_accumulate_params) LOAD(ptmi_accumulate_views) LOAD(ptmi_read_accumulated) LOAD(ptmi_release_accumulated) LOAD(ptmi_denoise_views_accumulated) LOAD(ptmi_set_view_moments) LOAD(ptmi_read_moments) LOAD(ptmi_release_moments) LOAD(ptmi_default_noise_params) LOAD(ptmi_view_noise_stats) LOAD(ptmi_render_views_until) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
   LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_check_bvh_boxes) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah) LOAD(ptmi_refit_scene_bvh)
@@ -1127,6 +1132,150 @@ static napi_value js_render_views_until_each(napi_env env, napi_callback_info in
   return out;
 }
 
+/* renderViewRuns(ctx, Float32Array(16) view, viewIndex, firstFrame, nFrames, Uint32Array runs): ptmi_render_view_runs — more frames for the listed runs of one view */
+static napi_value js_render_view_runs(napi_env env, napi_callback_info info) {
+  napi_value a[6];
+  if (get_args(env, info, 6, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  void *view, *runs;
+  size_t len, n_listed;
+  if (typed(env, a[1], napi_float32_array, "renderViewRuns(view)", &view, &len)) return NULL;
+  if (len != 16) {
+    napi_throw_range_error(env, NULL, "renderViewRuns: view must hold 16 floats");
+    return NULL;
+  }
+  uint32_t index, first, n_frames;
+  CHECK_NAPI(napi_get_value_uint32(env, a[2], &index));
+  CHECK_NAPI(napi_get_value_uint32(env, a[3], &first));
+  CHECK_NAPI(napi_get_value_uint32(env, a[4], &n_frames));
+  if (typed(env, a[5], napi_uint32_array, "renderViewRuns(runs)", &runs, &n_listed)) return NULL;
+  if (n_listed > 0xffffffffu) {
+    napi_throw_range_error(env, NULL, "renderViewRuns: too many runs");
+    return NULL;
+  }
+  int st = p_ptmi_render_view_runs(c, (const float*)view, index, first, n_frames, n_listed ? (const uint32_t*)runs : NULL, (uint32_t)n_listed);
+  if (st) return throw_status(env, c, st, "ptmi_render_view_runs");
+  return NULL;
+}
+
+/* viewRunNoise(ctx, target, firstView, nViews, params | null): ptmi_view_run_noise -> {nRuns, nOpen: Uint32Array(nViews), records: Uint32Array(nViews * nRuns * 4) —
+ * counted, sumQ, maxQ, open per run —, openRuns: Uint32Array(nViews * nRuns): per view its open runs ascending, then 0xffffffff}.  nRuns = ceil(width * height / 64),
+ * taken from the size of the view stack itself (ptmi_views_device_ptr), so that the arrays are the size the library writes. */
+static napi_value js_view_run_noise(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (get_args(env, info, 5, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  double target;
+  uint32_t first, n_views, n_runs = 0;
+  CHECK_NAPI(napi_get_value_double(env, a[1], &target));
+  CHECK_NAPI(napi_get_value_uint32(env, a[2], &first));
+  CHECK_NAPI(napi_get_value_uint32(env, a[3], &n_views));
+  {
+    void* stack = NULL;
+    size_t bytes = 0;
+    uint32_t in_stack = 0;
+    int st = p_ptmi_views_device_ptr(c, &stack, &bytes, &in_stack);
+    if (st) return throw_status(env, c, st, "ptmi_view_run_noise");
+    if (in_stack) n_runs = (uint32_t)((bytes / 16 / in_stack + 63) / 64);
+  }
+  ptmi_noise_params P;
+  if (noise_params_of(env, a[4], &P)) {
+    napi_throw_type_error(env, NULL, "viewRunNoise(params): {floor, threshold} of numbers, or null");
+    return NULL;
+  }
+  if (n_views == 0 || n_views > (1u << 24) || n_runs == 0 || (uint64_t)n_views * n_runs > (1u << 28)) {
+    napi_throw_range_error(env, NULL, "viewRunNoise: nViews must be 1 .. 2^24, nViews * nRuns 1 .. 2^28");
+    return NULL;
+  }
+  const size_t n = (size_t)n_views * n_runs;
+  napi_value out = NULL, ab[3], arr[3];
+  void* mem[3];
+  const size_t words[3] = {n_views, 4 * n, n};
+  for (int k = 0; k < 3; k++)
+    if (napi_create_arraybuffer(env, words[k] * 4, &mem[k], &ab[k]) != napi_ok || napi_create_typedarray(env, napi_uint32_array, words[k], ab[k], 0, &arr[k]) != napi_ok) {
+      napi_throw_error(env, NULL, "viewRunNoise: out of memory");
+      return NULL;
+    }
+  int st = p_ptmi_view_run_noise(c, &P, (float)target, first, n_views, (ptmi_run_noise*)mem[1], (uint32_t*)mem[0], (uint32_t*)mem[2]);
+  if (st) return throw_status(env, c, st, "ptmi_view_run_noise");
+  napi_value x;
+  if (napi_create_object(env, &out) != napi_ok || napi_create_uint32(env, n_runs, &x) != napi_ok) return NULL;
+  napi_set_named_property(env, out, "nRuns", x);
+  napi_set_named_property(env, out, "nOpen", arr[0]);
+  napi_set_named_property(env, out, "records", arr[1]);
+  napi_set_named_property(env, out, "openRuns", arr[2]);
+  return out;
+}
+
+/* renderViewsUntilRuns(ctx, views, Uint32Array(V) firstFrames | null, framesPerRound, minFrames, maxFrames, target, params | null): ptmi_render_views_until_runs ->
+ * {framesDone: Uint32Array(V), noise: [records], pathsTraced} */
+static napi_value js_render_views_until_runs(napi_env env, napi_callback_info info) {
+  napi_value a[8];
+  if (get_args(env, info, 8, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  void *data, *firsts = NULL;
+  size_t len, nf = 0;
+  if (typed(env, a[1], napi_float32_array, "renderViewsUntilRuns(views)", &data, &len)) return NULL;
+  if (len == 0 || len % 16 != 0 || len / 16 > (1u << 24)) {
+    napi_throw_range_error(env, NULL, "renderViewsUntilRuns: views must hold 16 floats per view, one view at least");
+    return NULL;
+  }
+  const uint32_t n_views = (uint32_t)(len / 16);
+  napi_valuetype vt;
+  CHECK_NAPI(napi_typeof(env, a[2], &vt));
+  if (vt != napi_null && vt != napi_undefined) {
+    if (typed(env, a[2], napi_uint32_array, "renderViewsUntilRuns(firstFrames)", &firsts, &nf)) return NULL;
+    if (nf != n_views) {
+      napi_throw_range_error(env, NULL, "renderViewsUntilRuns: firstFrames must hold one entry per view");
+      return NULL;
+    }
+  }
+  uint32_t per_round, min_frames, max_frames;
+  double target;
+  CHECK_NAPI(napi_get_value_uint32(env, a[3], &per_round));
+  CHECK_NAPI(napi_get_value_uint32(env, a[4], &min_frames));
+  CHECK_NAPI(napi_get_value_uint32(env, a[5], &max_frames));
+  CHECK_NAPI(napi_get_value_double(env, a[6], &target));
+  ptmi_noise_params P;
+  if (noise_params_of(env, a[7], &P)) {
+    napi_throw_type_error(env, NULL, "renderViewsUntilRuns(params): {floor, threshold} of numbers, or null");
+    return NULL;
+  }
+  ptmi_view_noise* rec = (ptmi_view_noise*)calloc(n_views, sizeof *rec);
+  if (!rec) {
+    napi_throw_error(env, NULL, "renderViewsUntilRuns: out of memory");
+    return NULL;
+  }
+  napi_value out = NULL, ab, done_arr;
+  void* done = NULL;
+  if (napi_create_arraybuffer(env, (size_t)n_views * 4, &done, &ab) != napi_ok || napi_create_typedarray(env, napi_uint32_array, n_views, ab, 0, &done_arr) != napi_ok) {
+    free(rec);
+    napi_throw_error(env, NULL, "renderViewsUntilRuns: out of memory");
+    return NULL;
+  }
+  uint64_t paths = 0;
+  int st = p_ptmi_render_views_until_runs(c, (const float*)data, n_views, (const uint32_t*)firsts, per_round, min_frames, max_frames, &P, (float)target, (uint32_t*)done, rec, &paths);
+  if (st) {
+    throw_status(env, c, st, "ptmi_render_views_until_runs");
+  } else {
+    napi_value noise = noise_records_to_js(env, rec, n_views), x;
+    if (noise && napi_create_object(env, &out) == napi_ok && napi_create_double(env, (double)paths, &x) == napi_ok) {
+      napi_set_named_property(env, out, "framesDone", done_arr);
+      napi_set_named_property(env, out, "noise", noise);
+      napi_set_named_property(env, out, "pathsTraced", x);
+    } else {
+      out = NULL;
+    }
+  }
+  free(rec);
+  return out;
+}
+
+static napi_value js_read_view_mean(napi_env env, napi_callback_info info) { return read_stack_common(env, info, p_ptmi_read_view_mean, "readViewMean(out)", "ptmi_read_view_mean"); }
+
 static napi_value js_synchronize(napi_env env, napi_callback_info info) {
   napi_value a[1];
   if (get_args(env, info, 1, a)) return NULL;
@@ -1415,6 +1564,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"version", js_version}, {"create", js_create}, {"destroy", js_destroy}, {"defaultParams", js_default_params}, {"setParams", js_set_params},
       {"upload", js_upload}, {"resize", js_resize}, {"clear", js_clear}, {"setShard", js_set_shard}, {"renderFrame", js_render_frame},
       {"renderViewsFrames", js_render_views_frames}, {"renderAovFrames", js_render_aov_frames}, {"renderViewsUntilEach", js_render_views_until_each},
+      {"renderViewRuns", js_render_view_runs}, {"viewRunNoise", js_view_run_noise}, {"renderViewsUntilRuns", js_render_views_until_runs}, {"readViewMean", js_read_view_mean},
       {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"denoiseViewsGuided", js_denoise_views_guided}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"accumulateViews", js_accumulate_views}, {"readAccumulated", js_read_accumulated}, {"releaseAccumulated", js_release_accumulated}, {"denoiseViewsAccumulated", js_denoise_views_accumulated}, {"denoiseViewsFrames", js_denoise_views_frames}, {"denoiseViewsGuidedFrames", js_denoise_views_guided_frames}, {"fuseViewsFrames", js_fuse_views_frames}, {"accumulateViewsFrames", js_accumulate_views_frames}, {"accumulateViewsMotion", js_accumulate_views_motion}, {"accumulateViewsDeform", js_accumulate_views_deform}, {"captureViewGeometry", js_capture_view_geometry}, {"fuseViewsMotion", js_fuse_views_motion}, {"fuseViewsDeform", js_fuse_views_deform}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"refitSceneBVH", js_refit_scene_bvh}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
       {"resolveRGBA8", js_resolve}, {"setCounters", js_set_counters}, {"setTiming", js_set_timing}, {"stats", js_stats},
       {"resetStats", js_reset_stats}, {"buildBVH", js_build_bvh}, {"buildBVHSAH", js_build_bvh_sah}, {"buildBVHDevice", js_build_bvh_device}, {"parseObj", js_parse_obj},

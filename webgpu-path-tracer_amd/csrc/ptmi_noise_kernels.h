@@ -73,4 +73,86 @@ __global__ __launch_bounds__(kBlock) void k_view_noise(const float4* __restrict_
   }
 }
 
+// ---- runs (ptmi_view_run_noise, ptmi_run_noise_images, ptmi_render_views_until_runs) ----
+// One call's device block for n views of n_runs runs each: the records [n][n_runs], behind them the lists of open runs [n][n_runs] u32 — view v's first n_open
+// entries ascending, the rest 0xffffffff — and one header per view.
+struct RunRecord {  // = ptmi_run_noise (include/ptmi.h)
+  uint32_t counted, sum_q, max_q, open;
+};
+struct RunHeader {
+  uint32_t n_open, n_local;  // the open runs of the view, and the pixels they cover (ptmn_runs_pixels)
+};
+struct RunNoiseBlock {
+  RunRecord* records;
+  uint32_t* lists;
+  RunHeader* heads;
+  static size_t bytes(uint32_t n, uint32_t n_runs) { return (size_t)n * n_runs * (sizeof(RunRecord) + 4) + (size_t)n * sizeof(RunHeader); }
+  static RunNoiseBlock at(void* p, uint32_t n, uint32_t n_runs) {
+    RunNoiseBlock b;
+    b.records = reinterpret_cast<RunRecord*>(p);
+    b.lists = reinterpret_cast<uint32_t*>(b.records + (size_t)n * n_runs);
+    b.heads = reinterpret_cast<RunHeader*>(b.lists + (size_t)n * n_runs);
+    return b;
+  }
+};
+
+// k_run_noise   One wave per (view, run), one lane per pixel: the lane's e (ptmn_error) becomes its three integers, lanes past the image's end contribute nothing,
+//               the wave adds them up by shuffles and lane 0 writes the run's record with its open flag.  Integers: the result does not depend on the launch shape.
+// grid (ceil(n_runs / (kBlock / 64)), views); colour, moments: [views][npix] float4
+__global__ __launch_bounds__(kBlock) void k_run_noise(const float4* __restrict__ colour, const float4* __restrict__ moments, uint32_t npix, uint32_t n_runs, float floor, float target,
+                                                      RunRecord* __restrict__ records) {
+  const uint32_t v = blockIdx.y, run = blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6);
+  if (run >= n_runs) return;  // (wave-uniform)
+  const uint32_t pix = run * PTMN_RUN_PIXELS + (threadIdx.x & 63u);
+  ptmn_run r = {0u, 0u, 0u};
+  if (pix < npix) {
+    const size_t at = (size_t)v * npix + pix;
+    ptmn_run_add(&r, ptmn_error(nz_f4(colour[at]), nz_f4(moments[at]), floor));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    r.counted += __shfl_xor(r.counted, o);
+    r.sum_q += __shfl_xor(r.sum_q, o);
+    r.max_q = max(r.max_q, __shfl_xor(r.max_q, o));
+  }
+  if ((threadIdx.x & 63u) == 0) records[(size_t)v * n_runs + run] = RunRecord{r.counted, r.sum_q, r.max_q, ptmn_run_open(r, target) ? 1u : 0u};
+}
+
+// k_run_list    One block per view: the view's open runs, compacted into an ASCENDING list — the partial run, the image's last, must come last in it.  The block walks
+//               the records kBlock at a time; a wave's ballot gives a lane its place among the wave's open runs, the waves' counts meet in LDS, and a running base
+//               carries over from chunk to chunk.  Thread 0 writes the header: the count and the pixels the list covers.  The list's tail keeps the 0xffffffff the
+//               host filled it with.
+__global__ __launch_bounds__(kBlock) void k_run_list(const RunRecord* __restrict__ records, uint32_t npix, uint32_t n_runs, uint32_t* __restrict__ lists, RunHeader* __restrict__ heads) {
+  const uint32_t v = blockIdx.x;
+  const RunRecord* rec = records + (size_t)v * n_runs;
+  uint32_t* list = lists + (size_t)v * n_runs;
+  __shared__ uint32_t s_cnt[kBlock / 64];
+  uint32_t base = 0, last_open = 0;
+  for (uint32_t r0 = 0; r0 < n_runs; r0 += kBlock) {  // (block-uniform trip count)
+    const uint32_t run = r0 + threadIdx.x;
+    const bool open = run < n_runs && rec[run].open != 0u;
+    const uint64_t mk = __ballot(open);
+    if ((threadIdx.x & 63u) == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(mk);
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kBlock / 64u; w++) {
+      const uint32_t n = s_cnt[w];
+      before += w < (threadIdx.x >> 6) ? n : 0u;
+      all += n;
+    }
+    if (open) list[base + before + lanes_below(mk)] = run;
+    if (run == n_runs - 1u && open) last_open = 1u;
+    base += all;
+    __syncthreads();  // (s_cnt is rewritten by the next chunk)
+  }
+  // the thread that saw the image's last run knows whether the list ends with it
+  __shared__ uint32_t s_last;
+  if (threadIdx.x == 0) s_last = 0u;
+  __syncthreads();
+  if (last_open) s_last = 1u;
+  __syncthreads();
+  if (threadIdx.x == 0) heads[v] = RunHeader{base, ptmn_runs_pixels(base, s_last ? n_runs - 1u : 0xffffffffu, npix)};
+}
+
 }  // namespace ptmi

@@ -1287,3 +1287,162 @@ int ptmi_render_views_until_each(ptmi_ctx* c, const float* views16, uint32_t n_v
 }
 
 }  // extern "C"
+
+// ---- the noise statistic per run and rendering to a target by runs (ptmi_view_run_noise, ptmi_run_noise_images, ptmi_render_views_until_runs) ----
+// (ptmi_run_noise_reference needs no GPU: ptmi_host.cpp)
+static_assert(sizeof(RunRecord) == sizeof(ptmi_run_noise), "the device record is the ABI's");
+
+// The two kernels on device arrays: colour and moments [n][npix] float4, `blk` the call's block of records, lists and headers (RunNoiseBlock::at).
+static int run_noise_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, uint32_t n, uint32_t npix, float floor, float target, const RunNoiseBlock& blk) {
+  const uint32_t n_runs = ptmn_run_count(npix);
+  HIP_TRY(c, hipMemsetAsync(blk.lists, 0xff, (size_t)n * n_runs * 4, c->stream));
+  const uint32_t gx = (n_runs + kBlock / 64 - 1) / (kBlock / 64);
+  for (uint32_t v0 = 0; v0 < n; v0 += 65535u) {
+    const uint32_t nv = std::min(65535u, n - v0);
+    hipLaunchKernelGGL(k_run_noise, dim3(gx, nv), dim3(kBlock), 0, c->stream, colour + (size_t)v0 * npix, moments + (size_t)v0 * npix, npix, n_runs, floor, target,
+                       blk.records + (size_t)v0 * n_runs);
+    HIP_TRY(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_run_list, dim3(n), dim3(kBlock), 0, c->stream, blk.records, npix, n_runs, blk.lists, blk.heads);
+  HIP_TRY(c, hipGetLastError());
+  return PTMI_OK;
+}
+
+// What the stream has left in `blk` to the caller's arrays (any of them nullptr: not wanted); the copies are on the stream, `heads` [n] must outlive its drain.
+static int run_noise_fetch(ptmi_ctx* c, const RunNoiseBlock& blk, uint32_t n, uint32_t n_runs, RunHeader* heads, ptmi_run_noise* records, uint32_t* open_runs) {
+  HIP_TRY(c, hipMemcpyAsync(heads, blk.heads, (size_t)n * sizeof(RunHeader), hipMemcpyDeviceToHost, c->stream));
+  if (records) HIP_TRY(c, hipMemcpyAsync(records, blk.records, (size_t)n * n_runs * sizeof(RunRecord), hipMemcpyDeviceToHost, c->stream));
+  if (open_runs) HIP_TRY(c, hipMemcpyAsync(open_runs, blk.lists, (size_t)n * n_runs * 4, hipMemcpyDeviceToHost, c->stream));
+  return PTMI_OK;
+}
+
+static int run_noise_check_args(ptmi_ctx* c, const char* who, const ptmi_noise_params* params, float target, ptmi_noise_params* P) {
+  if (!(target >= 0.0f) || !ptmn_finite(target)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": target must be finite and >= 0");
+  return noise_check_args(c, who, params, P);
+}
+
+extern "C" {
+
+int ptmi_view_run_noise(ptmi_ctx* c, const ptmi_noise_params* params, float target, uint32_t first_view, uint32_t n_views, ptmi_run_noise* records, uint32_t* n_open,
+                        uint32_t* open_runs) {
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  if (!n_open) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_view_run_noise: null argument");
+  if (int r = check_stack_call(c, "ptmi_view_run_noise", "a view's runs", "several", nullptr, false, 0.0f)) return r;
+  ptmi_noise_params P;
+  if (int r = run_noise_check_args(c, "ptmi_view_run_noise", params, target, &P)) return r;
+  if (int r = check_stack(c, STACK_VIEWS, "ptmi_view_run_noise", 0)) return r;
+  if (int r = check_stack(c, STACK_MOMENTS, "ptmi_view_run_noise", 0)) return r;
+  if (int r = check_view_range(c, "ptmi_view_run_noise", first_view, n_views, c->stacks[STACK_VIEWS].n)) return r;
+  const uint32_t npix = (uint32_t)c->W * (uint32_t)c->H, n_runs = ptmn_run_count(npix);
+  std::vector<RunHeader> heads;
+  try {
+    heads.resize(n_views);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_view_run_noise: no host memory for the headers");
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  HIP_TRY(c, c->d_run_noise.ensure_idle(RunNoiseBlock::bytes(n_views, n_runs), c->stream));
+  const RunNoiseBlock blk = RunNoiseBlock::at(c->d_run_noise.p, n_views, n_runs);
+  int r = run_noise_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)first_view * npix, c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix, n_views,
+                            npix, P.floor, target, blk);
+  if (r == PTMI_OK) r = run_noise_fetch(c, blk, n_views, n_runs, heads.data(), records, open_runs);
+  const hipError_t e = hipStreamSynchronize(c->stream);  // (whatever was enqueued drains before `heads` goes)
+  if (r) return r;
+  HIP_TRY(c, e);
+  drain_spans(c);
+  if (int q = check_queue_overflow(c)) return q;
+  for (uint32_t v = 0; v < n_views; v++) n_open[v] = heads[v].n_open;
+  return PTMI_OK;
+}
+
+int ptmi_run_noise_images(ptmi_ctx* c, const float* colour_sums, const float* moments, int w, int h, uint32_t n_images, const ptmi_noise_params* params, float target,
+                          ptmi_run_noise* records, uint32_t* n_open, uint32_t* open_runs) {
+  if (!c || !colour_sums || !moments || !n_open) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_run_noise_images: null argument");
+  ptmi_noise_params P;
+  if (int r = run_noise_check_args(c, "ptmi_run_noise_images", params, target, &P)) return r;
+  if (int r = check_image_size(c, "ptmi_run_noise_images", w, h, n_images)) return r;
+  const uint32_t npix = (uint32_t)w * (uint32_t)h, n_runs = ptmn_run_count(npix);
+  std::vector<RunHeader> heads;
+  try {
+    heads.resize(n_images);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, "ptmi_run_noise_images: no host memory for the headers");
+  }
+  DBuf block;  // (a block of the call's own: the context's keeps what ptmi_view_run_noise left)
+  const int r = on_host_images(
+      c, "ptmi_run_noise_images", colour_sums, moments, npix, n_images, nullptr, block, RunNoiseBlock::bytes(n_images, n_runs),
+      [&](const float4* col, const float4* mom, float4*) -> int {
+        const RunNoiseBlock blk = RunNoiseBlock::at(block.p, n_images, n_runs);
+        if (int e = run_noise_enqueue(c, col, mom, n_images, npix, P.floor, target, blk)) return e;
+        return run_noise_fetch(c, blk, n_images, n_runs, heads.data(), records, open_runs);
+      },
+      1);
+  if (r) return r;
+  for (uint32_t v = 0; v < n_images; v++) n_open[v] = heads[v].n_open;
+  return PTMI_OK;
+}
+
+int ptmi_render_views_until_runs(ptmi_ctx* c, const float* views16, uint32_t n_views, const uint32_t* first_frames, uint32_t frames_per_round, uint32_t min_frames,
+                                 uint32_t max_frames, const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out, uint64_t* paths_traced) {
+  const char* who = "ptmi_render_views_until_runs";
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  if (!views16 || !frames_done) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (n_views == 0 || frames_per_round == 0 || max_frames == 0) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need n_views, frames_per_round and max_frames >= 1");
+  for (uint32_t v = 0; v < n_views; v++) frames_done[v] = 0;
+  if (paths_traced) *paths_traced = 0;
+  if (min_frames < 2) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": min_frames " + std::to_string(min_frames) + ": a pixel is counted from two frames on");
+  if ((uint64_t)n_views * max_frames > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": n_views * max_frames must stay below 2^31");
+  ptmi_noise_params P;
+  if (int r = run_noise_check_args(c, who, params, target, &P)) return r;
+  if (int r = check_run_render(c, who, nullptr)) return r;
+  if (!c->fb || c->W <= 0) return fail(c, PTMI_ERR_STATE, "no framebuffer: call ptmi_resize first");
+  const uint32_t npix = (uint32_t)c->W * (uint32_t)c->H, n_runs = ptmn_run_count(npix);
+  std::vector<uint32_t> firsts, counts;
+  std::vector<RunHeader> heads;
+  try {
+    firsts.resize(n_views);
+    counts.resize(n_views);
+    heads.resize(n_views);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the headers");
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();
+  HIP_TRY(c, c->d_run_noise.ensure_idle(RunNoiseBlock::bytes(n_views, n_runs), c->stream));  // (before anything is enqueued)
+  // Phase A: every view's first frames in one batched call across the views, with reset
+  const uint32_t fa = std::min(min_frames, max_frames);
+  for (uint32_t v = 0; v < n_views; v++) firsts[v] = first_frames ? first_frames[v] : 0u, counts[v] = fa;
+  if (int r = ptmi_render_views_frames(c, views16, n_views, firsts.data(), counts.data(), 1)) return r;
+  for (uint32_t v = 0; v < n_views; v++) frames_done[v] = fa;
+  uint64_t paths = (uint64_t)n_views * npix * fa;
+  // Rounds: the statistic and the lists of the views that may still get frames (a met run is never sampled again, so it stays met and a view without an open run stays
+  // without), the headers to the host, and per view with an open run one run batch straight from the device list.  All open runs of a view hold the view's count.
+  uint32_t lo = 0, hi = n_views;  // the views still open lie in [lo, hi)
+  while (fa < max_frames && lo < hi) {
+    const uint32_t n = hi - lo;
+    const RunNoiseBlock blk = RunNoiseBlock::at(c->d_run_noise.p, n, n_runs);
+    int r = run_noise_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)lo * npix, c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)lo * npix, n, npix, P.floor, target, blk);
+    if (r == PTMI_OK) r = run_noise_fetch(c, blk, n, n_runs, heads.data(), nullptr, nullptr);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (r) return r;
+    HIP_TRY(c, e);
+    uint32_t new_lo = hi, new_hi = lo;
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t v = lo + i;
+      if (heads[i].n_open == 0 || frames_done[v] >= max_frames) continue;
+      const uint32_t nf = std::min(frames_per_round, max_frames - frames_done[v]);
+      r = render_runs_enqueue(c, views16 + 16 * (size_t)v, v, firsts[v] + frames_done[v], nf, blk.lists + (size_t)i * n_runs, heads[i].n_local);
+      if (r) return r;
+      frames_done[v] += nf;
+      paths += (uint64_t)heads[i].n_local * nf;
+      if (frames_done[v] < max_frames) new_lo = std::min(new_lo, v), new_hi = std::max(new_hi, v + 1);
+    }
+    lo = new_lo, hi = new_hi;
+  }
+  if (paths_traced) *paths_traced = paths;
+  if (out) return ptmi_view_noise_stats(c, &P, 0, n_views, out);
+  return PTMI_OK;
+}
+
+}  // extern "C"

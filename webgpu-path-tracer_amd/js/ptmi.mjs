@@ -82,6 +82,18 @@ export class Ptmi {
   renderViewsUntilEach(views, firstFrames, framesPerRound, maxFrames, target, params = null) {
     return this.native.renderViewsUntilEach(this.h, views, firstFrames, framesPerRound, maxFrames, target, params);
   }
+  // Rendering to a noise target by runs (ptmi_render_view_runs ...): a run is 64 consecutive pixels of an image in row-major order.  renderViewRuns adds frames
+  // firstFrame .. firstFrame + nFrames - 1 of view16 to image `view` of the view and moment stacks for the pixels of the listed runs alone (Uint32Array, strictly
+  // ascending); viewRunNoise gives {nRuns, nOpen: Uint32Array(nViews), records: Uint32Array(nViews * nRuns * 4) — counted, sumQ, maxQ, open per run —, openRuns:
+  // Uint32Array(nViews * nRuns) — per view its open runs ascending, then 0xffffffff}; renderViewsUntilRuns gives every view minFrames frames and then rounds of
+  // framesPerRound to the runs that have not met target: {framesDone: Uint32Array — the most any run of the view got —, noise, pathsTraced}; readViewMean divides
+  // every pixel by its own frame count (w = that count).
+  renderViewRuns(view16, view, firstFrame, nFrames, runs) { this.native.renderViewRuns(this.h, view16, view, firstFrame, nFrames, Uint32Array.from(runs)); }
+  viewRunNoise(target, firstView, nViews, params = null) { return this.native.viewRunNoise(this.h, target, firstView, nViews, params); }
+  renderViewsUntilRuns(views, firstFrames, framesPerRound, minFrames, maxFrames, target, params = null) {
+    return this.native.renderViewsUntilRuns(this.h, views, firstFrames, framesPerRound, minFrames, maxFrames, target, params);
+  }
+  readViewMean(view, out = new Float32Array(this.width * this.height * 4)) { return this.native.readViewMean(this.h, view, out); }
   // The consumers with one frame count per view (ptmi_denoise_views_frames ...): frameNums = one count per view OF THE STACK, a Float32Array or anything
   // Float32Array.from takes — renderViewsUntilEach's framesDone as it is; only the entries a call reads are checked (the denoisers: the range; fusion: the range
   // widened by the radius; accumulation: the range and, resuming, the view before it).  fuseViewsFrames reads the view stack (the denoised stack holds means).

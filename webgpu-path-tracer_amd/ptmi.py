@@ -43,7 +43,11 @@ SYMBOLS = [
     "ptmi_accumulate_images_deform", "ptmi_accumulate_reference_deform", "ptmi_deform_records",
     "ptmi_capture_view_geometry", "ptmi_read_view_geometry", "ptmi_geometry_device_ptr", "ptmi_release_geometry", "ptmi_accumulate_views_deform",
     "ptmi_fuse_views_deform", "ptmi_fuse_images_deform", "ptmi_fuse_reference_deform", "ptmi_fuse_deform_records",
+    "ptmi_render_view_runs", "ptmi_view_run_noise", "ptmi_run_noise_images", "ptmi_run_noise_reference", "ptmi_render_views_until_runs",
+    "ptmi_read_view_mean", "ptmi_resolve_view_mean_rgba8",
 ]
+
+RUN_PIXELS = 64  # a run: 64 consecutive pixels of an image in row-major order (include/ptmi.h, "RENDERING TO A NOISE TARGET BY RUNS")
 
 MOTION_MAX_RECORDS = 1 << 20  # PTMI_MOTION_MAX_RECORDS
 
@@ -94,6 +98,7 @@ class ViewNoise(ctypes.Structure):
 
 
 VIEW_NOISE_DTYPE = np.dtype([("counted", "<u8"), ("sum_q", "<u8"), ("above", "<u8"), ("max_q", "<u4"), ("reserved", "<u4")])
+RUN_NOISE_DTYPE = np.dtype([("counted", "<u4"), ("sum_q", "<u4"), ("max_q", "<u4"), ("open", "<u4")])  # ptmi_run_noise
 
 
 class Stats(ctypes.Structure):
@@ -316,6 +321,15 @@ def load_library(build=False, path=None):
                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.ptmi_release_geometry.argtypes = [vp]
         L.ptmi_accumulate_views_deform.argtypes = [vp, ap, fp, fp, fp, u32, u32, u32, i32]
+    if hasattr(L, "ptmi_render_view_runs"):  # (an older A/B build loaded through PTMI_LIB renders whole views)
+        qp = ctypes.POINTER(NoiseParams)
+        L.ptmi_render_view_runs.argtypes = [vp, fp, u32, u32, u32, fp, u32]
+        L.ptmi_view_run_noise.argtypes = [vp, qp, ctypes.c_float, u32, u32, fp, fp, fp]
+        L.ptmi_run_noise_images.argtypes = [vp, fp, fp, i32, i32, u32, qp, ctypes.c_float, fp, fp, fp]
+        L.ptmi_run_noise_reference.argtypes = [fp, fp, i32, i32, u32, qp, ctypes.c_float, fp, fp, fp]
+        L.ptmi_render_views_until_runs.argtypes = [vp, fp, u32, fp, u32, u32, u32, qp, ctypes.c_float, fp, fp, ctypes.POINTER(ctypes.c_uint64)]
+        L.ptmi_read_view_mean.argtypes = [vp, u32, fp, sz]
+        L.ptmi_resolve_view_mean_rgba8.argtypes = [vp, u32, fp, sz]
     if explicit:
         _libs[path] = L
     else:
@@ -737,6 +751,29 @@ def noise_reference(colour_sums, moments, params=None, want_map=False, lib=None)
     if st != 0:
         raise PtmiError(st, "ptmi_noise_reference failed")
     return (out, emap) if want_map else out
+
+
+def _run_noise_arrays(colour_sums, moments):
+    c, m, _, _ = _noise_arrays(colour_sums, moments, False)
+    n, n_runs = c.shape[0], (c.shape[1] * c.shape[2] + RUN_PIXELS - 1) // RUN_PIXELS
+    return c, m, np.zeros((n, n_runs), RUN_NOISE_DTYPE), np.zeros(n, np.uint32), np.zeros((n, n_runs), np.uint32)
+
+
+def _run_noise_result(records, n_open, open_runs):
+    """(records (n, n_runs) RUN_NOISE_DTYPE, n_open (n,) uint32, the n ascending lists of open runs as uint32 arrays)"""
+    return records, n_open, [open_runs[v, :int(k)].copy() for v, k in enumerate(n_open)]
+
+
+def run_noise_reference(colour_sums, moments, target, params=None, lib=None):
+    """ptmi_run_noise_reference: the noise statistic per RUN of 64 consecutive pixels, on the CPU (no GPU needed) — colour_sums and moments (n, H, W, 4) as for
+    noise_reference.  Returns (records (n, n_runs) RUN_NOISE_DTYPE — counted, sum_q, max_q, open —, n_open (n,) uint32, [per image the ascending uint32 array of its
+    open runs]): a run is open until it has counted > 0 and sum_q <= target * 65536 * counted."""
+    c, m, rec, n_open, runs = _run_noise_arrays(colour_sums, moments)
+    st = (lib or load_library()).ptmi_run_noise_reference(_ptr(c), _ptr(m), c.shape[2], c.shape[1], c.shape[0], None if params is None else ctypes.byref(params), float(target),
+                                                          _ptr(rec), _ptr(n_open), _ptr(runs))
+    if st != 0:
+        raise PtmiError(st, "ptmi_run_noise_reference failed")
+    return _run_noise_result(rec, n_open, runs)
 
 
 class NativeHost:
@@ -1370,6 +1407,54 @@ class Context:
         self._ck(self.lib.ptmi_render_views_until_each(self.h, _ptr(v), v.shape[0], None if f is None else _ptr(f), frames_per_round, max_frames,
                                                        None if params is None else ctypes.byref(params), float(target), _ptr(done), _ptr(out)))
         return done, out
+
+    def render_view_runs(self, view16, view, first_frame, n_frames, runs):
+        """ptmi_render_view_runs: adds frames first_frame .. first_frame + n_frames - 1 of view16 to image `view` of the view and moment stacks, for the pixels of the
+        listed runs alone (run r = pixels [64 r, 64 r + 64) in row-major order).  runs: strictly ascending uint32.  Needs set_view_moments and both stacks.  Asynchronous."""
+        v = np.ascontiguousarray(view16, np.float32)
+        assert v.size == 16
+        r = np.ascontiguousarray(runs, np.uint32).reshape(-1)
+        self._ck(self.lib.ptmi_render_view_runs(self.h, _ptr(v), view, first_frame, n_frames, _ptr(r) if r.size else None, r.size))
+
+    def view_run_noise(self, target, first_view=0, n_views=None, params=None):
+        """ptmi_view_run_noise: run_noise_reference's result for views [first_view, first_view + n_views) of the view and moment stacks.  n_views=None: up to the end
+        of the stack.  Synchronises."""
+        if n_views is None:
+            n_views = self.moments_device_ptr()[2] - first_view
+        n_runs = (self.width * self.height + RUN_PIXELS - 1) // RUN_PIXELS
+        rec, n_open, runs = np.zeros((n_views, n_runs), RUN_NOISE_DTYPE), np.zeros(n_views, np.uint32), np.zeros((n_views, n_runs), np.uint32)
+        self._ck(self.lib.ptmi_view_run_noise(self.h, None if params is None else ctypes.byref(params), float(target), first_view, n_views, _ptr(rec), _ptr(n_open), _ptr(runs)))
+        return _run_noise_result(rec, n_open, runs)
+
+    def run_noise_images(self, colour_sums, moments, target, params=None):
+        """ptmi_run_noise_images: the kernels of view_run_noise on host arrays of any size (see run_noise_reference for the shapes and the result); synchronous."""
+        c, m, rec, n_open, runs = _run_noise_arrays(colour_sums, moments)
+        self._ck(self.lib.ptmi_run_noise_images(self.h, _ptr(c), _ptr(m), c.shape[2], c.shape[1], c.shape[0], None if params is None else ctypes.byref(params), float(target),
+                                                _ptr(rec), _ptr(n_open), _ptr(runs)))
+        return _run_noise_result(rec, n_open, runs)
+
+    def render_views_until_runs(self, views, first_frames, frames_per_round, min_frames, max_frames, target, params=None):
+        """ptmi_render_views_until_runs: min(min_frames, max_frames) frames of every view in one batched call, then rounds of frames_per_round frames for the RUNS of
+        each view that have not met `target`, until none is open below max_frames.  first_frames: (V,) uint32, a scalar, or None for 0.  Needs set_view_moments.
+        Returns (frames_done (V,) uint32 — the most any run of the view got; a pixel's own count is read_moments' w —, records: view_noise of all views at the end,
+        paths_traced)."""
+        v = np.ascontiguousarray(views, np.float32)
+        assert v.ndim == 2 and v.shape[1] == 16, "views: (V, 16) float32"
+        f = None if first_frames is None else _frame_arrays(v.shape[0], first_frames, 0)[0]
+        done = np.zeros(v.shape[0], np.uint32)
+        out = np.zeros(v.shape[0], VIEW_NOISE_DTYPE)
+        paths = ctypes.c_uint64()
+        self._ck(self.lib.ptmi_render_views_until_runs(self.h, _ptr(v), v.shape[0], _optr(f), frames_per_round, min_frames, max_frames,
+                                                       None if params is None else ctypes.byref(params), float(target), _ptr(done), _ptr(out), ctypes.byref(paths)))
+        return done, out, paths.value
+
+    def read_view_mean(self, view):
+        """ptmi_read_view_mean: image `view` as (H, W, 4) float32 with every pixel's own divisor — rgb = S.rgb / M.w, 0 where M.w == 0; w = M.w."""
+        return self._read_image(self.lib.ptmi_read_view_mean, view)
+
+    def resolve_view_mean_rgba8(self, view):
+        """ptmi_resolve_view_mean_rgba8: resolve_view_rgba8 with every pixel's own frame count (read_moments' w) in place of frame_num."""
+        return self._resolve_image(self.lib.ptmi_resolve_view_mean_rgba8, view)
 
     def camera_rays(self, view16, frame):
         """Test hook (ptmi_camera_rays): (rays (W*H, 6) float32, rng (W*H,) uint32) — the first camera ray of `frame` for every pixel and the RNG state its
