@@ -665,16 +665,18 @@ int ptmi_run_noise_images(ptmi_ctx* ctx, const float* colour_sums, const float* 
  *   A       one ptmi_render_views_frames call — the batched path across views — with min(min_frames, max_frames) frames of every view from first_frames[v]
  *           (first_frames == NULL: 0), with reset; frames_done[v] = that count.
  *   rounds  k_run_noise + k_run_list over the views that may still get frames; only the per-view counts come back to the host.  Every view with an open run and
- *           frames_done[v] < max_frames gets ONE layer-1 batch straight from its device list: nf = min(frames_per_round, max_frames - frames_done[v]) frames numbered
+ *           frames_done[v] < max_frames gets frames in the round's ONE batch across the views, straight from the device list: nf = min(frames_per_round, max_frames - frames_done[v]) frames numbered
  *           from first_frames[v] + frames_done[v]; frames_done[v] += nf.  The call returns when no view has an open run below max_frames.
  * A met run is never sampled again, so its record cannot change and it stays met: all open runs of a view hold the same count, frames_done[v] — THE MOST ANY RUN OF THE
  * VIEW GOT (n_views entries); a pixel's own count is its M.w.  out, where not NULL: ptmi_view_noise_stats of all views at the end.  *paths_traced, where not NULL:
  * n_views * npix * phase A's frames + the sum over the run batches of n_local * nf.
  * min_frames >= 2 answers the caveat of the view statistic — frames that are mostly black agree at first and read too low: no run is judged on fewer frames; pooling
- * 64 pixels answers it further, since a run is met on its pixels' mean, not on a lucky pixel.  Per-view batches in the rounds give up the cross-view batching of phase
- * A: the saving is in paths, and whether it survives in wall time depends on how small the batches get.
+ * 64 pixels answers it further, since a run is met on its pixels' mean, not on a lucky pixel.  The saving is in paths; whether it survives in wall time depends on how
+ * small the rounds' batches get, and every round synchronises once.
  * Errors: those of ptmi_render_view_runs for the context (before anything is rendered), and PTMI_ERR_INVALID_ARG for a null views16 or frames_done, n_views,
  * frames_per_round or max_frames of 0, min_frames < 2, n_views * max_frames >= 2^31, a target that is negative or not finite, parameters outside their domain. */
+/* (A round is ONE run batch across the views now — RUN BATCHES ACROSS VIEWS below: the statistic, the per-view lists, k_run_refs for the round's list, its 12-byte
+ * header to the host, one ptmi_render_views_runs-shaped batch from the device list.  Every result is what the per-view batches gave, bit for bit.) */
 int ptmi_render_views_until_runs(ptmi_ctx* ctx, const float* views16, uint32_t n_views, const uint32_t* first_frames, uint32_t frames_per_round, uint32_t min_frames,
                                  uint32_t max_frames, const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out, uint64_t* paths_traced);
 /* Image `view` with every pixel's own divisor: rgb = S.rgb / M.w, 0 where M.w == 0; w = M.w.  Synchronises; bytes must be W*H*16.  Single-device, unsharded contexts;
@@ -683,6 +685,38 @@ int ptmi_read_view_mean(ptmi_ctx* ctx, uint32_t view, float* dst, size_t bytes);
 /* The display pass (ptmi_resolve_rgba8) for image `view` with the pixel's own divisor M.w in place of frame_num (a pixel with M.w == 0 is black); where every count
  * equals frame_num, the bytes are ptmi_resolve_view_rgba8's.  bytes must be W*H*4. */
 int ptmi_resolve_view_mean_rgba8(ptmi_ctx* ctx, uint32_t view, uint8_t* dst, size_t bytes);
+
+/* RUN BATCHES ACROSS VIEWS.  ptmi_render_view_runs traces one view's runs per batch, and a round of ptmi_render_views_until_runs used to be one such batch per open view:
+ * small batches, each a pipeline of its own.  The calls below put the listed runs of MANY views into one wavefront batch, as ptmi_render_views does with whole views.
+ *
+ * A call lists RUN REFERENCES {view, run}.  Only an image's last run can be partial (p = npix % 64 pixels, the same for every view), so on the device the list has two
+ * sections: n_full references to full runs, ascending by (view, run), then n_part references to partial runs, ascending by view.  n_local = 64 * n_full + p * n_part
+ * counts exactly the listed pixels; local pixel j is lane j & 63 of reference j >> 6 while j < 64 * n_full, and lane (j - 64 n_full) % p of reference
+ * n_full + (j - 64 n_full) / p behind that.  The path of frame slot f and local pixel j has id f * n_local + j, as in every other batch.  ptmi_stats.paths grows by
+ * n_local * n_frames.
+ *
+ * ptmi_render_views_runs adds frames first_frames[v] .. first_frames[v] + n_frames - 1 of views16[v] to the listed runs of image v of the view stack and the moment
+ * stack, for every listed view v, and leaves every other pixel's bits alone.  (run_views[i], runs[i]), i < n_listed: host arrays, copied before the call returns,
+ * strictly ascending by (view, run); every listed view is below n_views and below the stacks' count, every run below n_runs.  views16 and first_frames hold n_views
+ * entries; only the listed views' are used by the batch.  A listed pixel receives what ptmi_render_view_runs would add to it — the same paths, the same sums in frame
+ * order, M.w + 1 per frame — however the frames are split into batches (ptmi_params.frames_in_flight if set, else the path budget divided by n_local).  Asynchronous on
+ * the context's stream.  Between k_generate_runs_views and k_accumulate_runs_views step 0's kernels look a path's camera origin up through its reference (the VK_RUN
+ * instances of k_bvh2, k_shade and k_tail); later steps are the kernels of every batch.  A refused call leaves the stacks as they were, and nothing on the stream.
+ * Errors, in this order: PTMI_ERR_INVALID_ARG a null array, n_views, n_frames or n_listed of 0; then ptmi_render_view_runs' conditions of the context
+ * (PTMI_ERR_UNSUPPORTED a multi-device context, a shard, num_samples > 1; PTMI_ERR_STATE moments off, a stack missing); then PTMI_ERR_INVALID_ARG for the first entry
+ * with a view past the call or the stacks, a run >= n_runs, or a pair that is not above the one before it (the message names the entry). */
+int ptmi_render_views_runs(ptmi_ctx* ctx, const float* views16, uint32_t n_views, const uint32_t* first_frames, uint32_t n_frames, const uint32_t* run_views,
+                           const uint32_t* runs, uint32_t n_listed);
+/* The two-section list on the CPU — THE DEFINITION OF ITS ORDER, which the kernels and ptmi_render_views_runs lay out byte for byte.  n_open[v] and open_runs
+ * [n_views][n_runs] as ptmi_view_run_noise gives them (view v's first n_open[v] entries ascending, n_runs = ceil(npix / 64)).  refs_out, where not NULL: sum(n_open)
+ * references, two u32 each {view, run}.  header_out: three u32 {n_full, n_part, n_local}.  PTMI_ERR_INVALID_ARG: a null n_open, open_runs or header_out, n_views or
+ * npix of 0, a count above n_runs, a run >= n_runs, a list that is not strictly ascending, 2^31 listed pixels or more; nothing is written then. */
+int ptmi_run_refs_reference(uint32_t n_views, uint32_t npix, const uint32_t* n_open, const uint32_t* open_runs, uint32_t* refs_out, uint32_t* header_out);
+/* ptmi_run_noise_images' sibling: k_run_noise, k_run_list and k_run_refs — the kernels of a round of ptmi_render_views_until_runs — on host arrays of any size, and
+ * the device's list back.  refs_out: [n_images * n_runs][2] u32, the list's references first, 0xffffffff behind them; header_out: three u32.  Synchronous; uses device
+ * copies of its own.  Errors as ptmi_run_noise_images. */
+int ptmi_run_refs_images(ptmi_ctx* ctx, const float* colour_sums, const float* moments, int w, int h, uint32_t n_images, const ptmi_noise_params* params, float target,
+                         uint32_t* refs_out, uint32_t* header_out);
 
 /* CONSUMERS WITH PER-VIEW FRAME COUNTS.  The four calls on the stacks, their *_images forms and their CPU references with one divisor PER VIEW in place of the one
  * frame_num: everywhere a definition above divides a colour sum S by F — "prepare" (c = S.rgb / F), the denoisers' remodulation and pass-through (S.rgb / F, S.a / F),

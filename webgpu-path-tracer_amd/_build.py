@@ -46,7 +46,7 @@ TESTHOOKS_LIB = os.path.join(PKG, "variants", "libptmi_testhooks.so")
 
 
 def _deps():
-    return [os.path.join(CSRC, f) for f in SOURCES + ("ptmi_ctx.h", "ptmi_dbuf.h", "ptmi_call_table.h","ptmi_bvh_domain.h","ptmi_device.h", "ptmi_kernels.h", "ptmi_denoise_kernels.h", "ptmi_guided_kernels.h", "ptmi_fuse_kernels.h", "ptmi_motion_kernels.h", "ptmi_accumulate_kernels.h", "ptmi_noise_kernels.h", "ptmi_tuning.h")] + [os.path.join(ROOT, "include", f) for f in ("ptmi.h", "ptmi_math.h", "ptmi_denoise.h", "ptmi_guided.h", "ptmi_fuse.h", "ptmi_accumulate.h", "ptmi_motion.h", "ptmi_fuse_motion.h", "ptmi_deform.h", "ptmi_fuse_deform.h", "ptmi_noise.h")]
+    return [os.path.join(CSRC, f) for f in SOURCES + ("ptmi_ctx.h", "ptmi_dbuf.h", "ptmi_call_table.h", "ptmi_run_refs.h", "ptmi_bvh_domain.h","ptmi_device.h", "ptmi_kernels.h", "ptmi_denoise_kernels.h", "ptmi_guided_kernels.h", "ptmi_fuse_kernels.h", "ptmi_motion_kernels.h", "ptmi_accumulate_kernels.h", "ptmi_noise_kernels.h", "ptmi_tuning.h")] + [os.path.join(ROOT, "include", f) for f in ("ptmi.h", "ptmi_math.h", "ptmi_denoise.h", "ptmi_guided.h", "ptmi_fuse.h", "ptmi_accumulate.h", "ptmi_motion.h", "ptmi_fuse_motion.h", "ptmi_deform.h", "ptmi_fuse_deform.h", "ptmi_noise.h")]
 
 
 def _link(out, units, csrc=None):

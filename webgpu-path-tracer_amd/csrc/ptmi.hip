@@ -562,6 +562,19 @@ constexpr auto tail_views_kernel() {
   }
 }
 
+// ... and for a run batch across views (ptmi_render_views_runs): the k_*_runs kernels, which find a path's view through its local pixel's run reference.  One sample
+// per frame only (check_run_render), so there is no MULTI flag and those instances are never made.
+template <bool IS, bool SORT, bool COUNT>
+constexpr auto shade_runs_kernel() {
+  if constexpr (!IS) return &k_shade6_runs<SORT, COUNT>;
+  else return &k_shade_runs<IS, SORT, COUNT>;
+}
+template <bool SIX, bool IS, bool COUNT, bool NOABORT>
+constexpr auto tail_runs_kernel() {
+  if constexpr (SIX) return &k_tail6_runs<COUNT, NOABORT>;
+  else return &k_tail_runs<IS, COUNT, NOABORT>;
+}
+
 int stack_alloc_for(const ptmi_ctx* c) { return std::max(1, std::min(c->prm.stack_size, std::max(c->bvh_depth, 1))); }
 
 // A tree walk's stack (k_bvh, k_tail): stack_alloc_for + `extra` entries per lane, the first tun.lds_stack (10) in LDS — 2 words per entry and lane —,
@@ -604,9 +617,10 @@ void load_tuning(ptmi_ctx* c) { c->tun = load_tuning_env(); }  // (every value i
 
 // hitScene, part 2 for the step's queue (k_bvh).  Part 1 has already been run by whoever created the rays (k_generate,
 // k_shade); ptmi_trace's rays come from the host, so it asks for k_prims first.
-// `vt`: the batch is a multi-view one (only step 0's launch, `first_rc`, reads the table); `tab`: with a slot table (ptmi_render_views_frames)
+// `vt`: the batch is a multi-view one (only step 0's launch, `first_rc`, reads the table); `kind`: how it finds a path's view — VK_DIV, VK_TAB (with a slot table:
+// ptmi_render_views_frames) or VK_RUN (through run references: ptmi_render_views_runs)
 int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_items, bool with_prims, const RenderConst* first_rc = nullptr, const Carry& cy = Carry{},
-                     const ViewTab* vt = nullptr, bool tab = false) {
+                     const ViewTab* vt = nullptr, int kind = VK_ONE) {
   unsigned long long* tot = c->d_totals.as<unsigned long long>();
   const uint32_t pgrid = std::max<uint32_t>(1, std::min<uint32_t>((max_items + kBlock - 1) / kBlock, (uint32_t)c->num_cus * 32));
   if (with_prims) {
@@ -634,11 +648,15 @@ int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_ite
   // step 0's queue does not store the rays' common origin (k_generate): the kernel is handed cam_origin
   float4 cam = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (first_rc) cam = make_float4(first_rc->cam_o[0], first_rc->cam_o[1], first_rc->cam_o[2], 1.0f);
-  if (vt && first_rc) {
+  if (vt && first_rc && kind == VK_RUN) {
+    const auto bvh = with_flags([](auto cn, auto na) { return &k_bvh2_runs<cn, na>; }, c->counters, st.noabort);
+    hipLaunchKernelGGL(bvh, dim3(grid), dim3(64), lds, c->stream, c->S, P, ctl, c->d_heads.as<uint32_t>(), n_teams, c->prm.stack_size, st.lds_entries, st.spill_entries,
+                       c->d_spill.as<int2>(), tun.refill, tun.leaf_batch, tot, (uint32_t)tun.bvh_range, cam, cy, *vt);
+  } else if (vt && first_rc) {
     const auto bvh = with_flags([](auto tb, auto cn, auto na) {
       if constexpr (tb) return &k_bvh2_frames<cn, na>;
       else return &k_bvh2_views<cn, na>;
-    }, tab, c->counters, st.noabort);
+    }, kind == VK_TAB, c->counters, st.noabort);
     hipLaunchKernelGGL(bvh, dim3(grid), dim3(64), lds, c->stream, c->S, P, ctl, c->d_heads.as<uint32_t>(), n_teams, c->prm.stack_size, st.lds_entries, st.spill_entries,
                        c->d_spill.as<int2>(), tun.refill, tun.leaf_batch, tot, (uint32_t)tun.bvh_range, cam, cy, *vt);
   } else {
@@ -651,7 +669,7 @@ int launch_intersect(ptmi_ctx* c, const Paths& P, StepCtl* ctl, uint32_t max_ite
 }
 
 // k_tail in front of a step: traces the step's queue to the end if it is short (at most `limit` slots), else returns at once.  `six`: k_tail6 (tail_plan).
-int launch_tail(ptmi_ctx* c, const RenderConst& rc, const Paths& P, StepCtl* ctl, int first, uint32_t limit, bool six, const Carry& cy_in, const ViewTab* vt, bool tab) {
+int launch_tail(ptmi_ctx* c, const RenderConst& rc, const Paths& P, StepCtl* ctl, int first, uint32_t limit, bool six, const Carry& cy_in, const ViewTab* vt, int kind) {
   // On trees of 12 levels and more a walk stops once fewer than tun.tail_park lanes are left in it while other lanes have work; the stragglers' state waits in kParkEntries
   // entries on top of their stacks (park, ptmi_device.h).  Shallow trees never park: their walks are short, and a parked ray's path waits for the next walk (round 4 measured both).
   Carry cy = cy_in;
@@ -661,8 +679,13 @@ int launch_tail(ptmi_ctx* c, const RenderConst& rc, const Paths& P, StepCtl* ctl
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)limit + 63) / 64, (uint64_t)c->num_cus * (uint64_t)waves_per_cu));
   HIP_TRY(c, c->d_spill.ensure(std::max<size_t>(16, (size_t)c->num_cus * 32 * (size_t)st.spill_entries * 64 * sizeof(int2))));  // (k_bvh's grids are no larger: one size for both)
   ScopedSpan sp(c, T_TAIL);
-  if (vt) {
-    const auto tail = with_flags([](auto tb, auto s6, auto is, auto cn, auto mu, auto na) { return tail_views_kernel<tb, s6, is, cn, mu, na>(); }, tab, six,
+  if (vt && kind == VK_RUN) {
+    const auto tail = with_flags([](auto s6, auto is, auto cn, auto na) { return tail_runs_kernel<s6, is, cn, na>(); }, six, c->prm.importance_sampling != 0, c->counters,
+                                 st.noabort);
+    hipLaunchKernelGGL(tail, dim3(grid), dim3(64), st.lds_bytes, c->stream, c->S, rc, P, ctl, c->d_totals.as<unsigned long long>(), first, limit, c->prm.stack_size,
+                       st.lds_entries, st.spill_entries, c->d_spill.as<int2>(), cy, *vt);
+  } else if (vt) {
+    const auto tail = with_flags([](auto tb, auto s6, auto is, auto cn, auto mu, auto na) { return tail_views_kernel<tb, s6, is, cn, mu, na>(); }, kind == VK_TAB, six,
                                  c->prm.importance_sampling != 0, c->counters, rc.num_samples > 1, st.noabort);
     hipLaunchKernelGGL(tail, dim3(grid), dim3(64), st.lds_bytes, c->stream, c->S, rc, P, ctl, c->d_totals.as<unsigned long long>(), first, limit, c->prm.stack_size,
                        st.lds_entries, st.spill_entries, c->d_spill.as<int2>(), cy, *vt);
@@ -820,10 +843,16 @@ struct ViewBatch {
 // A run batch (ptmi_render_view_runs): one view — view16, frame numbers from frame0, as a lone-view batch — whose local pixels are those of `list`, a device array of
 // ascending run numbers (run_pixel, ptmi_device.h), n_local of them in all; its frames are ADDED to `image` and `moments`, the view's own images in the two stacks.
 // Between k_generate_runs and k_accumulate_runs the batch is a lone-view batch of n_local pixels: the VK_ONE instances work on path ids and never ask for the pixel.
+// Its second form (ptmi_render_views_runs), `across`: the listed runs belong to different views.  `vt` holds the call's view rows with the two-section list of
+// references behind them (ptmi_run_refs.h; vt.n_full, vt.part and vt.n_views say how to read it), `image` and `moments` are the two STACKS, `list` is not used, and
+// frame0 is the batch's offset into the call's frames: view v's frames are numbered from its row's first frame number + frame0.  Such a batch is a VK_RUN batch from
+// k_generate_runs_views to k_accumulate_runs_views: step 0's readers look a path's camera origin up through its reference.
 struct RunBatch {
   const uint32_t* list;
   uint32_t n_local;
   float4 *image, *moments;
+  bool across = false;
+  ViewTab vt{};
 };
 
 // `fold` = how many of the batch's leading frames are added to the framebuffer now (-1 = all of them); dry_steps > 0: placement_search's timing run
@@ -839,8 +868,11 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   if (rc.n_local == 0) return PTMI_OK;
   ViewTab vtab{};
   if (views) vtab = views->vt, vtab.n_local = rc.n_local;
-  const ViewTab* vt = views ? &vtab : nullptr;
+  const bool across = runs && runs->across;
+  if (across) vtab = runs->vt, vtab.n_local = rc.n_local;
+  const ViewTab* vt = views || across ? &vtab : nullptr;
   const bool tab = views && views->tab;
+  const int kind = across ? VK_RUN : tab ? VK_TAB : views ? VK_DIV : VK_ONE;
 
   const int n_steps = rc.num_samples * p.max_bounces;
   const size_t npaths = (size_t)rc.n_local * (size_t)n_frames;
@@ -877,14 +909,17 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
                                 rc.num_samples > 1);
   const auto shade_views = with_flags([](auto tb, auto is, auto so, auto cn, auto mu) { return shade_views_kernel<tb, is, so, cn, mu>(); }, tab, p.importance_sampling != 0, sort,
                                       c->counters, rc.num_samples > 1);
+  const auto shade_runs = with_flags([](auto is, auto so, auto cn) { return shade_runs_kernel<is, so, cn>(); }, p.importance_sampling != 0, sort, c->counters);
   // k_shade's grid: as many blocks per CU as the instance's registers and LDS admit (the progressive-mode ones need 79 VGPRs since
   // the build dropped the SLP vectoriser: 6 blocks = 6 waves per SIMD; the importance-sampling ones 93: 5) — asked of the runtime once per instance
   int shade_bpc = c->tun.shade_blocks_per_cu;
   if (shade_bpc <= 0) {
-    int& cached = c->shade_blocks_per_cu[views ? reinterpret_cast<const void*>(shade_views) : reinterpret_cast<const void*>(shade)];
+    int& cached = c->shade_blocks_per_cu[across ? reinterpret_cast<const void*>(shade_runs) : views ? reinterpret_cast<const void*>(shade_views) : reinterpret_cast<const void*>(shade)];
     if (cached == 0) {
       int nb = 0;
-      const hipError_t oe = views ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, shade_views, kBlock, 0) : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, shade, kBlock, 0);
+      const hipError_t oe = across  ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, shade_runs, kBlock, 0)
+                            : views ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, shade_views, kBlock, 0)
+                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, shade, kBlock, 0);
       if (oe != hipSuccess || nb < 1) nb = 5;
       cached = nb;
     }
@@ -914,6 +949,9 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
         if constexpr (tb) return &k_generate_frames<cn>;
         else return &k_generate_views<cn>;
       }, tab, c->counters);
+      hipLaunchKernelGGL(generate, dim3(ew_grid), dim3(kBlock), 0, c->stream, c->S, rc, paths_of(c, 0, rc.num_samples > 1), ctl, c->d_heads.as<uint32_t>(), tot, vtab);
+    } else if (across) {
+      const auto generate = with_flags([](auto cn) { return &k_generate_runs_views<cn>; }, c->counters);
       hipLaunchKernelGGL(generate, dim3(ew_grid), dim3(kBlock), 0, c->stream, c->S, rc, paths_of(c, 0, rc.num_samples > 1), ctl, c->d_heads.as<uint32_t>(), tot, vtab);
     } else if (runs) {
       const auto generate = with_flags([](auto cn) { return &k_generate_runs<cn>; }, c->counters);
@@ -945,7 +983,7 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     // (dry runs: k_generate and k_shade only — the kernels whose time depends on where the queue arrays lie; k_bvh reads them sparsely, and on a deep tree it would
     // be nine tenths of the search's time.  Rays that entered the root box are then shaded with what part 1 of hitScene found: other paths, the same access pattern.)
     if (const uint32_t tail_limit = dry_steps > 0 ? 0u : (s == 0 ? tail.limit_first : tail.limit_later)) {
-      int lr = launch_tail(c, rc, P, ctl + s, s == 0 ? 1 : 0, tail_limit, tail.six, carry_of(s), vt, tab);
+      int lr = launch_tail(c, rc, P, ctl + s, s == 0 ? 1 : 0, tail_limit, tail.six, carry_of(s), vt, kind);
       if (lr) return lr;
       // step 0's queue is the whole batch (k_generate fills one slot per path): if that fits the limit k_tail has just been handed all of it —
       // nothing is left for the per-bounce kernels, and a lone frame is three launches instead of 3 x MAX_BOUNCES + 2
@@ -957,12 +995,13 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     if (dry_steps == 0) {
       Carry cy = carry_of(s);
       if (!carry || s >= n_steps - c->tun.bvh_carry_last) cy.resv_next = 0u;
-      int lr = launch_intersect(c, P, ctl + s, bound, false, s == 0 ? &rc : nullptr, cy, vt, tab);
+      int lr = launch_intersect(c, P, ctl + s, bound, false, s == 0 ? &rc : nullptr, cy, vt, kind);
       if (lr) return lr;
     }
     {
       ScopedSpan sp(c, T_SHADE);
-      if (views) hipLaunchKernelGGL(shade_views, dim3(sgrid), dim3(kBlock), 0, c->stream, c->S, rc, P, ctl + s, c->d_heads.as<uint32_t>(), tot, s == 0 ? 1 : 0, s == 0 ? 0u : resv, vtab);
+      if (across) hipLaunchKernelGGL(shade_runs, dim3(sgrid), dim3(kBlock), 0, c->stream, c->S, rc, P, ctl + s, c->d_heads.as<uint32_t>(), tot, s == 0 ? 1 : 0, s == 0 ? 0u : resv, vtab);
+      else if (views) hipLaunchKernelGGL(shade_views, dim3(sgrid), dim3(kBlock), 0, c->stream, c->S, rc, P, ctl + s, c->d_heads.as<uint32_t>(), tot, s == 0 ? 1 : 0, s == 0 ? 0u : resv, vtab);
       else hipLaunchKernelGGL(shade, dim3(sgrid), dim3(kBlock), 0, c->stream, c->S, rc, P, ctl + s, c->d_heads.as<uint32_t>(), tot, s == 0 ? 1 : 0, s == 0 ? 0u : resv);
       HIP_TRY(c, hipGetLastError());  // launch errors surface per step, before k_accumulate touches the framebuffer
     }
@@ -973,7 +1012,7 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
   if (carry && !drained && n_steps > 0) {
     // paths that were carried over lag behind the step count: whatever the last k_shade left in the queue (and what the last k_bvh carried) is
     // traced to its end by one k_tail launch — a few thousand paths at most
-    int lr = launch_tail(c, rc, paths_of(c, n_steps, rc.num_samples > 1), ctl + n_steps, 0, 0xffffffffu, tail.six, carry_of(n_steps), vt, tab);
+    int lr = launch_tail(c, rc, paths_of(c, n_steps, rc.num_samples > 1), ctl + n_steps, 0, 0xffffffffu, tail.six, carry_of(n_steps), vt, kind);
     if (lr) return lr;
   }
   {
@@ -986,6 +1025,8 @@ int render_batch(ptmi_ctx* c, const float* view16, uint32_t frame0, int n_frames
     else if (views && views->moments)
       hipLaunchKernelGGL(k_accumulate_moments, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), views->stack, views->moments, n_steps, tot, 0, f_end, vtab);
     else if (views) hipLaunchKernelGGL(k_accumulate<true>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), views->stack, n_steps, tot, 0, f_end, vtab);
+    else if (across)
+      hipLaunchKernelGGL(k_accumulate_runs_views, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), runs->image, runs->moments, vtab, n_steps, tot, 0, f_end);
     else if (runs)
       hipLaunchKernelGGL(k_accumulate_runs, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), runs->image, runs->moments, runs->list, n_steps, tot, 0, f_end);
     else hipLaunchKernelGGL(k_accumulate<false>, dim3(ew_grid), dim3(kBlock), 0, c->stream, rc, paths_of(c, 0, rc.num_samples > 1), c->fb, n_steps, tot, 0, f_end, vtab);
@@ -1517,6 +1558,7 @@ void ptmi_destroy(ptmi_ctx* c) {
   c->fuse_tab.release();
   c->denoise_tab.release();
   c->run_tab.release();
+  c->run_refs.release();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;  // its device buffers (DBuf) are freed here, with its device current and its stream drained
 }
@@ -2098,7 +2140,97 @@ int render_runs_enqueue(ptmi_ctx* c, const float* view16, uint32_t view, uint32_
   return PTMI_OK;
 }
 
+// ---- run batches across views (ptmi_render_views_runs, ptmi_render_views_until_runs) ----
+// The call's table in c->run_refs (ptmi_run_refs.h): the rows of all n_views views — row 4's .w the view's first frame number —, the header and room for `cap`
+// references.  Allocates and fills the pinned copy's rows; *host is that copy, for a caller that has a list to put behind them.  Enqueues nothing.
+int stage_run_refs_table(ptmi_ctx* c, const float* views16, uint32_t n_views, const uint32_t* first_frames, size_t cap, uint8_t** host) {
+  HIP_TRY(c, c->run_refs.stage(run_refs_table_bytes(n_views, cap), c->stream, (void**)host));
+  for (uint32_t v = 0; v < n_views; v++) {
+    const float* m = views16 + 16 * (size_t)v;
+    float* row = reinterpret_cast<float*>(*host + (size_t)v * kRunViewRowBytes);
+    memcpy(row, m, 64);
+    for (int k = 0; k < 3; k++) row[16 + k] = ((m[k] * 0.0f + m[4 + k] * 0.0f) + m[8 + k] * 0.0f) + m[12 + k] * 1.0f;  // cam_origin, as make_render_const computes it
+    const uint32_t first = first_frames ? first_frames[v] : 0u;
+    memcpy(row + 19, &first, 4);
+  }
+  return PTMI_OK;
+}
+
+// n_frames more frames for the listed runs of the table in c->run_refs (on the device by the time the batch reads it: an upload, or k_run_refs), `h` its header;
+// view v's frames are numbered from its row's first frame number + frame_offset.  render_runs_enqueue's loop over batches: the same path budget, frames_in_flight,
+// 2^31 cap and halving.  The caller has run check_run_render with the stacks.
+int render_views_runs_enqueue(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t frame_offset, uint32_t n_frames, const RunRefsHeader& h) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  (void)hipGetLastError();  // a stale error of an earlier, already reported failure must not be blamed on this call
+  int r = prepare_scene(c);
+  if (r) return r;
+  r = check_renderable(c);
+  if (r) return r;
+  if (h.n_local == 0 || n_frames == 0) return PTMI_OK;
+  const uint32_t npix = (uint32_t)c->W * (uint32_t)c->H;
+  RunBatch rb{nullptr, h.n_local, c->stacks[STACK_VIEWS].buf.as<float4>(), c->stacks[STACK_MOMENTS].buf.as<float4>(), true, ViewTab{}};
+  rb.vt.rows = c->run_refs.dev.as<float4>();
+  rb.vt.n_full = h.n_full, rb.vt.n_views = n_views, rb.vt.part = npix % kRunPixels;
+  const uint32_t n_local = h.n_local;
+  uint32_t F = c->prm.frames_in_flight > 0 ? (uint32_t)c->prm.frames_in_flight : (uint32_t)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)1 << c->tun.path_budget_log2) / n_local));
+  F = (uint32_t)std::min<size_t>(F, std::max<size_t>(1, ((size_t)1 << 31) / n_local));
+  for (uint32_t done = 0; done < n_frames;) {
+    const uint32_t nb = std::min(F, n_frames - done);
+    r = render_batch(c, views16, frame_offset + done, (int)nb, 0, -1, 0, nullptr, &rb);  // (views16: the kernels of such a batch take every view from the table)
+    if (r == PTMI_ERR_NO_MEMORY && !c->batch_enqueued && nb > 1 && c->prm.frames_in_flight <= 0) {
+      F = std::max<uint32_t>(1, nb / 2);
+      continue;
+    }
+    if (r) return r;
+    done += nb;
+  }
+  return PTMI_OK;
+}
+
 extern "C" {
+
+int ptmi_render_views_runs(ptmi_ctx* c, const float* views16, uint32_t n_views, const uint32_t* first_frames, uint32_t n_frames, const uint32_t* run_views, const uint32_t* runs,
+                           uint32_t n_listed) {
+  const char* who = "ptmi_render_views_runs";
+  if (!c) return PTMI_ERR_INVALID_ARG;
+  if (!views16 || !first_frames || !run_views || !runs) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (n_frames == 0 || n_listed == 0 || n_views == 0) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": need n_views >= 1, n_frames >= 1 and n_listed >= 1");
+  const uint32_t view0 = 0;
+  if (int r = check_run_render(c, who, &view0)) return r;
+  const uint32_t npix = (uint32_t)c->W * (uint32_t)c->H, n_runs = ptmn_run_count(npix);
+  const uint32_t in_stack = std::min(c->stacks[STACK_VIEWS].n, c->stacks[STACK_MOMENTS].n), view_limit = std::min(n_views, in_stack);
+  uint32_t at = 0;
+  if (const int fault = run_pairs_check(run_views, runs, n_listed, view_limit, n_runs, &at)) {
+    const std::string entry = std::string(who) + ": entry " + std::to_string(at) + " = (view " + std::to_string(run_views[at]) + ", run " + std::to_string(runs[at]) + ")";
+    if (fault == RUN_PAIR_VIEW) return fail(c, PTMI_ERR_INVALID_ARG, entry + ": the call has " + std::to_string(n_views) + " views and the stacks hold " + std::to_string(in_stack));
+    if (fault == RUN_PAIR_RUN) return fail(c, PTMI_ERR_INVALID_ARG, entry + ": an image has " + std::to_string(n_runs) + " runs");
+    return fail(c, PTMI_ERR_INVALID_ARG, entry + " after (view " + std::to_string(run_views[at - 1]) + ", run " + std::to_string(runs[at - 1]) + "): the pairs must be strictly ascending by (view, run)");
+  }
+  // the pairs are the views' ascending lists one after the other: ptmi_run_refs_reference's input with one row of `runs` per view
+  std::vector<uint32_t> n_open, start;
+  try {
+    n_open.assign(view_limit, 0u);
+    start.assign(view_limit, 0u);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the list");
+  }
+  for (uint32_t i = 0; i < n_listed; i++) {
+    if (n_open[run_views[i]]++ == 0u) start[run_views[i]] = i;
+  }
+  const auto list_of = [&](uint32_t v) { return runs + start[v]; };
+  const RunRefsHeader h = run_refs_fill(view_limit, npix, n_open.data(), list_of, nullptr);
+  if ((uint64_t)h.n_full * kRunPixels + (uint64_t)h.n_part * (npix % kRunPixels) > 0x7fffffffull) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": the listed pixels must stay below 2^31");
+  HIP_TRY(c, hipSetDevice(c->device));
+  uint8_t* host = nullptr;
+  if (int r = stage_run_refs_table(c, views16, n_views, first_frames, n_listed, &host)) return r;
+  const uint32_t head4[4] = {h.n_full, h.n_part, h.n_local, 0u};
+  memcpy(host + run_refs_header_at(n_views), head4, kRunRefsHeaderBytes);
+  run_refs_fill(view_limit, npix, n_open.data(), list_of, reinterpret_cast<RunRef*>(host + run_refs_at(n_views)));
+  if (int r = prepare_scene(c)) return r;  // (what can refuse the call does so before the table is on the stream)
+  if (int r = check_renderable(c)) return r;
+  HIP_TRY(c, c->run_refs.send(run_refs_table_bytes(n_views, n_listed), c->stream));
+  return render_views_runs_enqueue(c, views16, n_views, 0u, n_frames, h);
+}
 
 int ptmi_render_view_runs(ptmi_ctx* c, const float* view16, uint32_t view, uint32_t first_frame, uint32_t n_frames, const uint32_t* runs, uint32_t n_listed) {
   if (!c) return PTMI_ERR_INVALID_ARG;

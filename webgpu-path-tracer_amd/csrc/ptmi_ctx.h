@@ -154,6 +154,7 @@ struct ptmi_ctx {
   bool view_moments = false;  // ptmi_set_view_moments: ptmi_render_views folds second moments into stacks[STACK_MOMENTS] too
   DBuf d_noise_rec;           // ptmi_view_noise_stats: one record (kNoiseRecordBytes) per view of the call
   StagedTable run_tab;        // the last ptmi_render_view_runs call's run list: one u32 per listed run
+  StagedTable run_refs;       // the last run batch across views' table (ptmi_run_refs.h): the call's view rows, the header and the {view, run} references
   DBuf d_run_noise;           // ptmi_view_run_noise / ptmi_render_views_until_runs: per view of the call the runs' records, its list of open runs and its header (RunNoiseLayout)
   int rank = 0, world = 1, tile = 64;
 
@@ -243,6 +244,10 @@ PTMI_HIDDEN uint32_t count_local(uint32_t npix, int rank, int world, int tile); 
 // Run batches (ptmi_render_view_runs): what such a call asks of the context (one device, no shard, one sample per frame, moments on, both stacks with *view — view == nullptr: the caller makes the stacks), and the
 // batches themselves — n_frames more frames of view16 from first_frame for the n_local pixels of the ascending device list d_list, added to image `view` of both stacks.
 PTMI_HIDDEN int check_run_render(ptmi_ctx* c, const char* who, const uint32_t* view);
+// Run batches across views (ptmi_render_views_runs): the call's table in c->run_refs — rows for n_views views (first_frames == nullptr: 0) and room for `cap`
+// references behind the header, *host the pinned copy, nothing enqueued — and the batches themselves for the table the stream has on the device by then, `h` its header.
+PTMI_HIDDEN int stage_run_refs_table(ptmi_ctx* c, const float* views16, uint32_t n_views, const uint32_t* first_frames, size_t cap, uint8_t** host);
+PTMI_HIDDEN int render_views_runs_enqueue(ptmi_ctx* c, const float* views16, uint32_t n_views, uint32_t frame_offset, uint32_t n_frames, const RunRefsHeader& h);
 PTMI_HIDDEN int render_runs_enqueue(ptmi_ctx* c, const float* view16, uint32_t view, uint32_t first_frame, uint32_t n_frames, const uint32_t* d_list, uint32_t n_local);
 
 // fn(ctx) on the context itself and on every peer; `parallel` = one host thread per device, so that calls which block

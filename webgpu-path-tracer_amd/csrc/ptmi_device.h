@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/ptmi_math.h"
+#include "ptmi_run_refs.h"
 
 #define DEV __device__ __forceinline__
 
@@ -477,17 +478,25 @@ DEV float ldu(const float* p) { return *(const PTMI_CONST_AS float*)(p); }
 // view.  A slot's view and frame number then come from the call's SLOT TABLE (include/ptmi.h, ptmi_view_slot_plan: one 16-byte record per view — first slot, count, first
 // frame number, next view with a frame — and a u32 view per slot), which lies behind the rows in the same allocation; `fpv` is not read, `n_views` says where the table begins.
 // The kernel instances are told apart by their MV template argument:
-enum ViewKind : int { VK_ONE = 0, VK_DIV = 1, VK_TAB = 2 };  // one view in rc / ViewTab's division / the slot table
+// The fourth (ptmi_render_views_runs): a batch whose local pixels are the RUNS of a two-section list of {view, run} references (ptmi_run_refs.h), which lies behind the
+// rows as the slot table does; the view of a path follows from its local pixel, not from its frame slot, and every listed view gets the batch's n_frames frames.
+enum ViewKind : int { VK_ONE = 0, VK_DIV = 1, VK_TAB = 2, VK_RUN = 3 };  // one view in rc / ViewTab's division / the slot table / the run references
 constexpr int kViewRow = 5;
+static_assert(kViewRow * 16 == kRunViewRowBytes, "ptmi_run_refs.h lays the references out behind rows of this size");
 struct ViewTab {
   const float4* rows;
-  uint32_t slot0;    // the batch's first frame slot among the call's
+  union {
+    uint32_t slot0;   // the batch's first frame slot among the call's
+    uint32_t n_full;  // VK_RUN: the list's references to full runs
+  };
   union {
     uint32_t fpv;      // VK_DIV: frames per view
-    uint32_t n_views;  // VK_TAB: the call's views — the slot table begins at rows + kViewRow * n_views
+    uint32_t n_views;  // VK_TAB, VK_RUN: the call's views — the slot table / the run references begin at rows + kViewRow * n_views
   };
   uint32_t n_local;  // = rc.n_local, for the kernels that are not handed rc (k_bvh)
+  uint32_t part;     // VK_RUN: the pixels of a partial run, npix % 64 (in what was the struct's padding: the other kinds neither set nor read it)
 };
+static_assert(sizeof(ViewTab) == 24, "the kernels of the other view kinds take the argument block they always took");
 struct ViewRow {
   float m[16];
   f3 o;
@@ -546,8 +555,32 @@ DEV uint32_t run_pixel(const uint32_t* __restrict__ runs, uint32_t j) {
   return r * kRunPixels + (j & 63u);
 }
 
+// ---- run batches across views (ptmi_render_views_runs; the layout is ptmi_run_refs.h's) -------------------------------
+// Local pixel j's reference.  The lanes of a wave nearly always agree on its index (64 neighbours of one run; a wave straddles two in the tail section, and where
+// step 0's queue has holes): then it comes through one 8-byte scalar load, as run_pixel's entry; else per lane.  Call from converged or diverged code alike: the vote
+// is among the active lanes.  The list is written before the launch (an upload, or k_run_refs in an earlier launch).
+DEV const int2* run_refs_of(const ViewTab& vt) {
+  return reinterpret_cast<const int2*>(reinterpret_cast<const uint8_t*>(vt.rows) + run_refs_at(vt.n_views));
+}
+DEV RunRef load_run_ref(const ViewTab& vt, uint32_t j, uint32_t& lane) {
+  const uint32_t k = run_ref_index(j, vt.n_full, vt.part, &lane), ku = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
+  const int2 r = __ballot(k != ku) == 0ull ? ldu(run_refs_of(vt) + ku) : run_refs_of(vt)[k];
+  return RunRef{(uint32_t)r.x, (uint32_t)r.y};
+}
+// View v's first frame number for the batch: row 4's .w, fetched the way load_view_row fetches the row
+DEV uint32_t view_first_frame(const ViewTab& vt, uint32_t v) {
+  const float* w = reinterpret_cast<const float*>(vt.rows) + ((size_t)kViewRow * v + 4) * 4 + 3;
+  const uint32_t vu = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+  if (__ballot(v != vu) == 0ull) return __float_as_uint(ldu(reinterpret_cast<const float*>(vt.rows) + ((size_t)kViewRow * vu + 4) * 4 + 3));
+  return __float_as_uint(*w);
+}
+
 template <int MV>
 DEV uint32_t view_of_path(const ViewTab& vt, uint32_t pid) {
+  if (MV == VK_RUN) {
+    uint32_t lane;
+    return load_run_ref(vt, pid % vt.n_local, lane).view;
+  }
   if (MV == VK_TAB) return view_of_slot(vt, vt.slot0 + pid / vt.n_local);
   return (vt.slot0 + pid / vt.n_local) / vt.fpv;
 }

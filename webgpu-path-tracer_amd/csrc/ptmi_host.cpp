@@ -30,6 +30,7 @@
 #include "../../include/ptmi_noise.h"
 #include "ptmi_bvh_domain.h"
 #include "ptmi_call_table.h"
+#include "ptmi_run_refs.h"
 
 namespace {
 // Math.min / Math.max (lib/BVH/AABB.js:8-28) on finite values: -0 < +0 whatever the argument order
@@ -1428,6 +1429,25 @@ extern "C" int ptmi_run_noise_reference(const float* colour_sums, const float* m
       for (uint32_t k = open; k < n_runs; k++) open_runs[(size_t)v * n_runs + k] = 0xffffffffu;
     n_open[v] = open;
   }
+  return PTMI_OK;
+}
+
+// The two-section list of a run batch across views (ptmi_run_refs.h defines the order; the kernels' k_run_refs and ptmi_render_views_runs lay out the same bytes):
+// open_runs [n_views][n_runs] as ptmi_view_run_noise leaves it, view v's first n_open[v] entries ascending.  Everything is checked before anything is written.
+extern "C" int ptmi_run_refs_reference(uint32_t n_views, uint32_t npix, const uint32_t* n_open, const uint32_t* open_runs, uint32_t* refs_out, uint32_t* header_out) {
+  if (!n_open || !open_runs || !header_out || n_views == 0 || npix == 0 || npix > 0x7fffffffu) return PTMI_ERR_INVALID_ARG;
+  const uint32_t n_runs = ptmn_run_count(npix);
+  uint64_t pixels = 0;
+  for (uint32_t v = 0; v < n_views; v++) {
+    if (n_open[v] > n_runs) return PTMI_ERR_INVALID_ARG;
+    const uint32_t* l = open_runs + (size_t)v * n_runs;
+    for (uint32_t k = 0; k < n_open[v]; k++)
+      if (l[k] >= n_runs || (k && l[k] <= l[k - 1])) return PTMI_ERR_INVALID_ARG;
+    pixels += n_open[v] ? ptmn_runs_pixels(n_open[v], l[n_open[v] - 1], npix) : 0u;
+  }
+  if (pixels > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
+  const ptmi::RunRefsHeader h = ptmi::run_refs_fill(n_views, npix, n_open, [&](uint32_t v) { return open_runs + (size_t)v * n_runs; }, reinterpret_cast<ptmi::RunRef*>(refs_out));
+  header_out[0] = h.n_full, header_out[1] = h.n_part, header_out[2] = h.n_local;
   return PTMI_OK;
 }
 

@@ -58,7 +58,10 @@ DEV void generate_body(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict_
   const uint32_t chunks = ((uint32_t)rc.n_frames + kGenFrames - 1u) / kGenFrames, work = rc.n_local * chunks;
   for (uint32_t w = blockIdx.x * kBlock + threadIdx.x; w < work; w += gridDim.x * kBlock) {
    const uint32_t chunk = w / rc.n_local, j = w - chunk * rc.n_local;
-   const uint32_t pix = PX == PX_RUNS ? run_pixel(runs, j) : local_to_pixel(rc, j);
+   uint32_t run_lane = 0;
+   RunRef ref = {0u, 0u};  // (VK_RUN) the lane's reference: its view and its pixel for the whole chunk
+   if (MV == VK_RUN) ref = load_run_ref(vt, j, run_lane);
+   const uint32_t pix = MV == VK_RUN ? ref.run * kRunPixels + run_lane : PX == PX_RUNS ? run_pixel(runs, j) : local_to_pixel(rc, j);
    float px, py;
    camera_pixel(rc, pix, px, py);
    const uint32_t f_end = min((chunk + 1u) * kGenFrames, (uint32_t)rc.n_frames);
@@ -66,7 +69,11 @@ DEV void generate_body(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict_
    ViewRow vr;
    ViewRec rec = {0u, 0u, 0u, 0u};  // (VK_TAB) the view's record, and the frame number of the slot
    uint32_t frame = 0;
-   if (MV == VK_TAB) {  // the chunk may begin in the middle of a view
+   if (MV == VK_RUN) {  // the view is the reference's, for every frame of the batch: nothing is reloaded in the loop
+     view = ref.view;
+     frame = view_first_frame(vt, view) + rc.frame0 + chunk * kGenFrames;
+     vr = load_view_row(vt, view);
+   } else if (MV == VK_TAB) {  // the chunk may begin in the middle of a view
      const uint32_t s = vt.slot0 + chunk * kGenFrames;
      view = view_of_slot_voted(vt, s);
      rec = load_view_rec(vt, view);
@@ -82,14 +89,16 @@ DEV void generate_body(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict_
     const uint32_t g = f * rc.n_local + j;
     uint32_t pid = g;  // path id = frame_slot * n_local + local pixel index (dense per rank)
     // u32(uniforms.frameNum): the frame number travels through an f32 uniform (renderer.js:173)
-    uint32_t rng = pix + (uint32_t)(float)(MV == VK_TAB ? frame : rc.frame0 + (MV ? fiv : f)) * 719393u;
+    uint32_t rng = pix + (uint32_t)(float)(MV == VK_TAB || MV == VK_RUN ? frame : rc.frame0 + (MV ? fiv : f)) * 719393u;
     f3 o, d;
     if (MV) {
       float a, b;
       camera_plane(rc, px, py, 0, rng, a, b);
       d = camera_dir(vr.m, -rc.fov_factor, a, b);
       o = vr.o;
-      if (MV == VK_TAB) {
+      if (MV == VK_RUN) {
+        frame++;
+      } else if (MV == VK_TAB) {
         frame++;
         if (++fiv == rec.count) {  // the next slot opens the next view that has a frame (the batch's last slot may be the call's last: nothing is loaded then)
           view = rec.next;
@@ -139,6 +148,14 @@ template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_generate_frames(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
                                                             unsigned long long* __restrict__ totals, ViewTab vt) {
   generate_body<COUNT, VK_TAB>(S, rc, P, ctl, heads, totals, vt);
+}
+
+// ... of a run batch across views (ptmi_render_views_runs): pixel and view both come from the lane's reference in the list behind vt's rows; rc.frame0 is the
+// batch's offset into the call's frames, added to each view's own first frame number (row 4's .w)
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_generate_runs_views(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
+                                                                unsigned long long* __restrict__ totals, ViewTab vt) {
+  generate_body<COUNT, VK_RUN>(S, rc, P, ctl, heads, totals, vt);
 }
 
 // ... of a run batch (ptmi_render_view_runs): one view, rc carries it as it does for k_generate; the pixels are those of the listed runs
@@ -482,7 +499,15 @@ __global__ __launch_bounds__(64) PTMI_BVH_ATTR void k_bvh2_frames(DevScene S, Pa
   bvh2_body<COUNT, NOABORT, VK_TAB>(S, P, ctl, heads, n_teams, stack_size, lds_entries, spill_entries, spill, refill_threshold, leaf_batch, totals, range_cap, cam, cy, vt, lds_stack,
                                     blockIdx.x, gridDim.x);
 }
-
+// ... of a run batch across views (ptmi_render_views_runs): the slot's view comes from its local pixel's reference
+template <bool COUNT, bool NOABORT>
+__global__ __launch_bounds__(64) PTMI_BVH_ATTR void k_bvh2_runs(DevScene S, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads, uint32_t n_teams, int stack_size,
+                                                                int lds_entries, int spill_entries, int2* __restrict__ spill, int refill_threshold, int leaf_batch,
+                                                                unsigned long long* __restrict__ totals, uint32_t range_cap, float4 cam, Carry cy, ViewTab vt) {
+  extern __shared__ int lds_stack[];
+  bvh2_body<COUNT, NOABORT, VK_RUN>(S, P, ctl, heads, n_teams, stack_size, lds_entries, spill_entries, spill, refill_threshold, leaf_batch, totals, range_cap, cam, cy, vt, lds_stack,
+                                    blockIdx.x, gridDim.x);
+}
 
 // What a surviving path carries into the next step's queue.
 struct NewState {
@@ -1199,6 +1224,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) 
   if constexpr (SORT) shade_body<false, COUNT, false, VK_TAB>(S, rc, P, ctl, heads, totals, first, resv, vt);
   else shade_body_wave<false, COUNT, false, VK_TAB>(S, rc, P, ctl, heads, totals, first, resv, vt);
 }
+// ... of a run batch across views (ptmi_render_views_runs).  One sample per frame only (run batches refuse num_samples > 1): no MULTI argument.
+template <bool IS, bool SORT, bool COUNT>
+__global__ __launch_bounds__(kBlock) PTMI_SHADE_ATTR void k_shade_runs(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, uint32_t* __restrict__ heads,
+                                                                       unsigned long long* __restrict__ totals, int first, uint32_t resv, ViewTab vt) {
+  if constexpr (SORT) shade_body<IS, COUNT, false, VK_RUN>(S, rc, P, ctl, heads, totals, first, resv, vt);
+  else shade_body_wave<IS, COUNT, false, VK_RUN>(S, rc, P, ctl, heads, totals, first, resv, vt);
+}
+template <bool SORT, bool COUNT>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_shade6_runs(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl,
+                                                                                                     uint32_t* __restrict__ heads, unsigned long long* __restrict__ totals, int first,
+                                                                                                     uint32_t resv, ViewTab vt) {
+  if constexpr (SORT) shade_body<false, COUNT, false, VK_RUN>(S, rc, P, ctl, heads, totals, first, resv, vt);
+  else shade_body_wave<false, COUNT, false, VK_RUN>(S, rc, P, ctl, heads, totals, first, resv, vt);
+}
 
 // k_tail — a SHORT queue traced to the end in one launch: every lane takes a path and runs ray_color's loop for it (hitScene part 2 on
 // LDS stacks with the state machine of k_bvh, ray_color's body by shade_one, hitScene part 1 for the new ray) until the path ends —
@@ -1399,6 +1438,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void
                                                                                                 unsigned long long* __restrict__ totals, int first, uint32_t limit, int stack_size,
                                                                                                 int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy, ViewTab vt) {
   tail_body<false, COUNT, false, NOABORT, VK_TAB>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, vt);
+}
+// ... of a run batch across views (ptmi_render_views_runs): one sample per frame only
+template <bool IS, bool COUNT, bool NOABORT>
+__global__ __launch_bounds__(64) void k_tail_runs(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl, unsigned long long* __restrict__ totals, int first,
+                                                  uint32_t limit, int stack_size, int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy, ViewTab vt) {
+  tail_body<IS, COUNT, false, NOABORT, VK_RUN>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, vt);
+}
+template <bool COUNT, bool NOABORT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_tail6_runs(DevScene S, RenderConst rc, Paths P, StepCtl* __restrict__ ctl,
+                                                                                              unsigned long long* __restrict__ totals, int first, uint32_t limit, int stack_size,
+                                                                                              int lds_entries, int spill_entries, int2* __restrict__ spill, Carry cy, ViewTab vt) {
+  tail_body<false, COUNT, false, NOABORT, VK_RUN>(S, rc, P, ctl, totals, first, limit, stack_size, lds_entries, spill_entries, spill, cy, vt);
 }
 
 // k_aov — the feature pass (ptmi_render_aov): what the FIRST hitScene call of every frame's path sees, and nothing after it.  No queues, no path state, no
@@ -1756,6 +1807,53 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_runs(RenderConst rc, Path
   for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < rc.n_local; j += gridDim.x * kBlock) {
     if (f_begin >= f_end) break;
     const uint32_t pix = run_pixel(runs, j);
+    f3 c = mk3(fb[pix]);
+    float4 m = mom[pix];
+    constexpr int kAhead = 8;
+    for (int f0 = f_begin; f0 < f_end; f0 += kAhead) {
+      bool have[kAhead];
+      float4 colv[kAhead];
+#pragma unroll
+      for (int k = 0; k < kAhead; k++) {
+        const int f = f0 + k;
+        have[k] = f < f_end && (!P.touched || P.touched[(size_t)f * rc.n_local + j]);
+      }
+#pragma unroll
+      for (int k = 0; k < kAhead; k++) {
+        colv[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // a path that never wrote its acc_radiance returned (0,0,0)
+        if (have[k]) colv[k] = P.acc[(size_t)(f0 + k) * rc.n_local + j];
+      }
+#pragma unroll
+      for (int k = 0; k < kAhead; k++) {
+        if (f0 + k >= f_end) break;
+        const f3 col = mk3(colv[k]);
+        const f3 sq = mk3(col.x * col.x, col.y * col.y, col.z * col.z);
+        c = c + col;
+        m = make_float4(m.x + sq.x, m.y + sq.y, m.z + sq.z, m.w + 1.0f);
+      }
+    }
+    fb[pix] = make_float4(c.x, c.y, c.z, 1.0f);
+    mom[pix] = m;
+  }
+  if (f_begin == 0 && blockIdx.x == 0 && threadIdx.x == 0) {  // the slot-0 tally, as k_accumulate's
+    unsigned long long rays = 0;
+    if (n_steps > 0)
+      for (int k = 0; k < kTallyLines; k++) rays += *tally_line(totals, (uint32_t)k);
+    totals[0] += rays;
+    totals[1] += (unsigned long long)rc.n_local * (unsigned long long)rc.n_frames * (unsigned long long)rc.num_samples;
+  }
+}
+
+// k_accumulate_runs for a run batch across views (ptmi_render_views_runs): `fb` and `mom` are the two STACKS, [views][npix]; the lane's view and pixel are its
+// reference's (load_run_ref), and its frames ADD to what both stacks hold at view * npix + pixel.  The arithmetic is k_accumulate_runs', unchanged: frame order, the
+// colours fetched eight ahead, the square a product and then an add, m.w + 1.0f per frame.  (An entry of its own for the reason given above k_accumulate.)
+__global__ __launch_bounds__(kBlock) void k_accumulate_runs_views(RenderConst rc, Paths P, float4* __restrict__ fb, float4* __restrict__ mom, ViewTab vt, int n_steps,
+                                                                  unsigned long long* __restrict__ totals, int f_begin, int f_end) {
+  for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < rc.n_local; j += gridDim.x * kBlock) {
+    if (f_begin >= f_end) break;
+    uint32_t lane;
+    const RunRef ref = load_run_ref(vt, j, lane);
+    const size_t pix = (size_t)ref.view * rc.npix + (ref.run * kRunPixels + lane);
     f3 c = mk3(fb[pix]);
     float4 m = mom[pix];
     constexpr int kAhead = 8;

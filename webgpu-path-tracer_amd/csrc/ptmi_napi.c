@@ -82,6 +82,7 @@ FN(ptmi_render_view_runs)
 FN(ptmi_view_run_noise)
 FN(ptmi_render_views_until_runs)
 FN(ptmi_read_view_mean)
+FN(ptmi_render_views_runs)
 FN(ptmi_synchronize)
 FN(ptmi_read_framebuffer)
 FN(ptmi_write_framebuffer)
@@ -133,7 +134,7 @@ static int load_lib(char* err, size_t errlen) {
   LOAD(ptmi_version) LOAD(ptmi_last_error) LOAD(ptmi_create) LOAD(ptmi_create_multi) LOAD(ptmi_prepare) LOAD(ptmi_destroy) LOAD(ptmi_default_params) LOAD(ptmi_default_denoise_params) LOAD(ptmi_set_params)
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
   LOAD(ptmi_render_views_frames) LOAD(ptmi_render_aov_frames) LOAD(ptmi_render_views_until_each)
-  LOAD(ptmi_render_view_runs) LOAD(ptmi_view_run_noise) LOAD(ptmi_render_views_until_runs) LOAD(ptmi_read_view_mean)
+  LOAD(ptmi_render_view_runs) LOAD(ptmi_view_run_noise) LOAD(ptmi_render_views_until_runs) LOAD(ptmi_read_view_mean) LOAD(ptmi_render_views_runs)
   LOAD(ptmi_views_device_ptr) LOAD(ptmi_denoise_views_frames) LOAD(ptmi_denoise_views_guided_frames) LOAD(ptmi_fuse_views_frames) LOAD(ptmi_accumulate_views_frames) LOAD(ptmi_accumulate_views_motion) LOAD(ptmi_accumulate_views_deform) LOAD(ptmi_capture_view_geometry) LOAD(ptmi_fuse_views_motion) LOAD(ptmi_fuse_views_deform)
   LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_default_guided_params) LOAD(ptmi_denoise_views_guided) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_default_accumulate_params) LOAD(ptmi_accumulate_views) LOAD(ptmi_read_accumulated) LOAD(ptmi_release_accumulated) LOAD(ptmi_denoise_views_accumulated) LOAD(ptmi_set_view_moments) LOAD(ptmi_read_moments) LOAD(ptmi_release_moments) LOAD(ptmi_default_noise_params) LOAD(ptmi_view_noise_stats) LOAD(ptmi_render_views_until) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
   LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_check_bvh_boxes) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah) LOAD(ptmi_refit_scene_bvh)
@@ -1159,6 +1160,40 @@ static napi_value js_render_view_runs(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* renderViewsRuns(ctx, Float32Array(16 V) views, Uint32Array(V) firstFrames, nFrames, Uint32Array runViews, Uint32Array runs): ptmi_render_views_runs — more frames
+ * for the listed runs of many views, in one batch across the views */
+static napi_value js_render_views_runs(napi_env env, napi_callback_info info) {
+  napi_value a[6];
+  if (get_args(env, info, 6, a)) return NULL;
+  ptmi_ctx* c = ctx_of(env, a[0]);
+  if (!c) return NULL;
+  void *views, *firsts, *run_views, *runs;
+  size_t len, nf, n_rv, n_listed;
+  if (typed(env, a[1], napi_float32_array, "renderViewsRuns(views)", &views, &len)) return NULL;
+  if (len == 0 || len % 16 != 0 || len / 16 > (1u << 24)) {
+    napi_throw_range_error(env, NULL, "renderViewsRuns: views must hold 16 floats per view, one view at least");
+    return NULL;
+  }
+  const uint32_t n_views = (uint32_t)(len / 16);
+  if (typed(env, a[2], napi_uint32_array, "renderViewsRuns(firstFrames)", &firsts, &nf)) return NULL;
+  if (nf != n_views) {
+    napi_throw_range_error(env, NULL, "renderViewsRuns: firstFrames must hold one entry per view");
+    return NULL;
+  }
+  uint32_t n_frames;
+  CHECK_NAPI(napi_get_value_uint32(env, a[3], &n_frames));
+  if (typed(env, a[4], napi_uint32_array, "renderViewsRuns(runViews)", &run_views, &n_rv)) return NULL;
+  if (typed(env, a[5], napi_uint32_array, "renderViewsRuns(runs)", &runs, &n_listed)) return NULL;
+  if (n_rv != n_listed || n_listed > 0xffffffffu) {
+    napi_throw_range_error(env, NULL, "renderViewsRuns: runViews and runs must hold one entry per listed run, fewer than 2^32");
+    return NULL;
+  }
+  int st = p_ptmi_render_views_runs(c, (const float*)views, n_views, (const uint32_t*)firsts, n_frames, n_listed ? (const uint32_t*)run_views : NULL,
+                                    n_listed ? (const uint32_t*)runs : NULL, (uint32_t)n_listed);
+  if (st) return throw_status(env, c, st, "ptmi_render_views_runs");
+  return NULL;
+}
+
 /* viewRunNoise(ctx, target, firstView, nViews, params | null): ptmi_view_run_noise -> {nRuns, nOpen: Uint32Array(nViews), records: Uint32Array(nViews * nRuns * 4) —
  * counted, sumQ, maxQ, open per run —, openRuns: Uint32Array(nViews * nRuns): per view its open runs ascending, then 0xffffffff}.  nRuns = ceil(width * height / 64),
  * taken from the size of the view stack itself (ptmi_views_device_ptr), so that the arrays are the size the library writes. */
@@ -1564,7 +1599,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"version", js_version}, {"create", js_create}, {"destroy", js_destroy}, {"defaultParams", js_default_params}, {"setParams", js_set_params},
       {"upload", js_upload}, {"resize", js_resize}, {"clear", js_clear}, {"setShard", js_set_shard}, {"renderFrame", js_render_frame},
       {"renderViewsFrames", js_render_views_frames}, {"renderAovFrames", js_render_aov_frames}, {"renderViewsUntilEach", js_render_views_until_each},
-      {"renderViewRuns", js_render_view_runs}, {"viewRunNoise", js_view_run_noise}, {"renderViewsUntilRuns", js_render_views_until_runs}, {"readViewMean", js_read_view_mean},
+      {"renderViewRuns", js_render_view_runs}, {"viewRunNoise", js_view_run_noise}, {"renderViewsUntilRuns", js_render_views_until_runs}, {"readViewMean", js_read_view_mean}, {"renderViewsRuns", js_render_views_runs},
       {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"denoiseViewsGuided", js_denoise_views_guided}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"accumulateViews", js_accumulate_views}, {"readAccumulated", js_read_accumulated}, {"releaseAccumulated", js_release_accumulated}, {"denoiseViewsAccumulated", js_denoise_views_accumulated}, {"denoiseViewsFrames", js_denoise_views_frames}, {"denoiseViewsGuidedFrames", js_denoise_views_guided_frames}, {"fuseViewsFrames", js_fuse_views_frames}, {"accumulateViewsFrames", js_accumulate_views_frames}, {"accumulateViewsMotion", js_accumulate_views_motion}, {"accumulateViewsDeform", js_accumulate_views_deform}, {"captureViewGeometry", js_capture_view_geometry}, {"fuseViewsMotion", js_fuse_views_motion}, {"fuseViewsDeform", js_fuse_views_deform}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"refitSceneBVH", js_refit_scene_bvh}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},
       {"resolveRGBA8", js_resolve}, {"setCounters", js_set_counters}, {"setTiming", js_set_timing}, {"stats", js_stats},
       {"resetStats", js_reset_stats}, {"buildBVH", js_build_bvh}, {"buildBVHSAH", js_build_bvh_sah}, {"buildBVHDevice", js_build_bvh_device}, {"parseObj", js_parse_obj},

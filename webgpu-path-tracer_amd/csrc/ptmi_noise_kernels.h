@@ -155,4 +155,49 @@ __global__ __launch_bounds__(kBlock) void k_run_list(const RunRecord* __restrict
   if (threadIdx.x == 0) heads[v] = RunHeader{base, ptmn_runs_pixels(base, s_last ? n_runs - 1u : 0xffffffffu, npix)};
 }
 
+// k_run_refs    From the headers and lists k_run_list leaves for n views: the call's two-section list of references (ptmi_run_refs.h) — the full runs view by view,
+//               then the partial runs view by view — and its header.  grid (gx, rows), row y = view v_base + y of the n: the blocks of row v add up the full and partial counts of the views before v (an
+//               exclusive scan, each block for itself: n is small against a list) and of all views, then copy view v's full runs to their place, gx blocks sharing
+//               the copy; block (0, v) places v's partial run, block (0, 0) writes the header.  A view's reference names view view0 + v.
+//               `done` (ptmi_render_views_until_runs; else nullptr): every view with an open run is about to get nf more frames — done[view0 + v] += nf, after a
+//               check that it stood at `expect` like every other open view's (one n_frames serves the whole batch); a view that did not is counted in done[n_done].
+__global__ __launch_bounds__(kBlock) void k_run_refs(const RunHeader* __restrict__ heads, const uint32_t* __restrict__ lists, uint32_t n, uint32_t npix, uint32_t n_runs, uint32_t view0,
+                                                     uint32_t* __restrict__ header, RunRef* __restrict__ refs, uint32_t* __restrict__ done, uint32_t n_done, uint32_t expect,
+                                                     uint32_t nf, uint32_t v_base) {
+  const uint32_t v = v_base + blockIdx.y, p = npix % PTMN_RUN_PIXELS;
+  uint32_t full_before = 0, part_before = 0, full_all = 0, part_all = 0;
+  for (uint32_t u = threadIdx.x; u < n; u += kBlock) {
+    const RunHeader h = heads[u];
+    const uint32_t part = h.n_local != PTMN_RUN_PIXELS * h.n_open ? 1u : 0u;  // (the view's list ends with the image's partial run)
+    full_all += h.n_open - part, part_all += part;
+    if (u < v) full_before += h.n_open - part, part_before += part;
+  }
+  __shared__ uint32_t s_sum[kBlock / 64][4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    full_before += __shfl_xor(full_before, o), part_before += __shfl_xor(part_before, o);
+    full_all += __shfl_xor(full_all, o), part_all += __shfl_xor(part_all, o);
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    uint32_t* s = s_sum[threadIdx.x >> 6];
+    s[0] = full_before, s[1] = part_before, s[2] = full_all, s[3] = part_all;
+  }
+  __syncthreads();
+  full_before = part_before = full_all = part_all = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < kBlock / 64u; w++) full_before += s_sum[w][0], part_before += s_sum[w][1], full_all += s_sum[w][2], part_all += s_sum[w][3];
+  const RunHeader mine = heads[v];
+  const uint32_t my_part = mine.n_local != PTMN_RUN_PIXELS * mine.n_open ? 1u : 0u, my_full = mine.n_open - my_part;
+  const uint32_t* list = lists + (size_t)v * n_runs;
+  for (uint32_t k = blockIdx.x * kBlock + threadIdx.x; k < my_full; k += gridDim.x * kBlock) refs[full_before + k] = RunRef{view0 + v, list[k]};
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (my_part) refs[full_all + part_before] = RunRef{view0 + v, n_runs - 1u};
+    if (v == 0) header[0] = full_all, header[1] = part_all, header[2] = PTMN_RUN_PIXELS * full_all + p * part_all, header[3] = 0u;
+    if (done && mine.n_open != 0u) {
+      if (done[view0 + v] != expect) atomicAdd(done + n_done, 1u);
+      done[view0 + v] += nf;
+    }
+  }
+}
+
 }  // namespace ptmi

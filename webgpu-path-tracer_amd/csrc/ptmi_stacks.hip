@@ -1308,6 +1308,19 @@ static int run_noise_enqueue(ptmi_ctx* c, const float4* colour, const float4* mo
   return PTMI_OK;
 }
 
+// k_run_refs behind run_noise_enqueue: the two-section list of the n views' open runs (ptmi_run_refs.h) into `refs`, its header into `header` (four u32), view v of the
+// block named view0 + v.  `done` (or nullptr), n_done, expect, nf: see the kernel.
+static int run_refs_enqueue(ptmi_ctx* c, const RunNoiseBlock& blk, uint32_t n, uint32_t npix, uint32_t view0, uint32_t* header, RunRef* refs, uint32_t* done, uint32_t n_done,
+                            uint32_t expect, uint32_t nf) {
+  const uint32_t n_runs = ptmn_run_count(npix);
+  const uint32_t gx = std::max(1u, std::min(64u, (n_runs + kBlock - 1) / kBlock));
+  for (uint32_t v0 = 0; v0 < n; v0 += 65535u) {
+    hipLaunchKernelGGL(k_run_refs, dim3(gx, std::min(65535u, n - v0)), dim3(kBlock), 0, c->stream, blk.heads, blk.lists, n, npix, n_runs, view0, header, refs, done, n_done, expect, nf, v0);
+    HIP_TRY(c, hipGetLastError());
+  }
+  return PTMI_OK;
+}
+
 // What the stream has left in `blk` to the caller's arrays (any of them nullptr: not wanted); the copies are on the stream, `heads` [n] must outlive its drain.
 static int run_noise_fetch(ptmi_ctx* c, const RunNoiseBlock& blk, uint32_t n, uint32_t n_runs, RunHeader* heads, ptmi_run_noise* records, uint32_t* open_runs) {
   HIP_TRY(c, hipMemcpyAsync(heads, blk.heads, (size_t)n * sizeof(RunHeader), hipMemcpyDeviceToHost, c->stream));
@@ -1383,6 +1396,35 @@ int ptmi_run_noise_images(ptmi_ctx* c, const float* colour_sums, const float* mo
   return PTMI_OK;
 }
 
+int ptmi_run_refs_images(ptmi_ctx* c, const float* colour_sums, const float* moments, int w, int h, uint32_t n_images, const ptmi_noise_params* params, float target,
+                         uint32_t* refs_out, uint32_t* header_out) {
+  if (!c || !colour_sums || !moments || !refs_out || !header_out) return fail(c, PTMI_ERR_INVALID_ARG, "ptmi_run_refs_images: null argument");
+  ptmi_noise_params P;
+  if (int r = run_noise_check_args(c, "ptmi_run_refs_images", params, target, &P)) return r;
+  if (int r = check_image_size(c, "ptmi_run_refs_images", w, h, n_images)) return r;
+  const uint32_t npix = (uint32_t)w * (uint32_t)h, n_runs = ptmn_run_count(npix);
+  const size_t cap = (size_t)n_images * n_runs, noise_bytes = (RunNoiseBlock::bytes(n_images, n_runs) + 15) / 16 * 16;
+  uint32_t head4[4] = {0u, 0u, 0u, 0u};
+  DBuf block;  // (the call's own: the records, lists and headers, then the list's header and its references)
+  const int r = on_host_images(
+      c, "ptmi_run_refs_images", colour_sums, moments, npix, n_images, nullptr, block, noise_bytes + kRunRefsHeaderBytes + cap * sizeof(RunRef),
+      [&](const float4* col, const float4* mom, float4*) -> int {
+        const RunNoiseBlock blk = RunNoiseBlock::at(block.p, n_images, n_runs);
+        uint32_t* header = reinterpret_cast<uint32_t*>(block.as<uint8_t>() + noise_bytes);
+        RunRef* refs = reinterpret_cast<RunRef*>(block.as<uint8_t>() + noise_bytes + kRunRefsHeaderBytes);
+        if (int e = run_noise_enqueue(c, col, mom, n_images, npix, P.floor, target, blk)) return e;
+        HIP_TRY(c, hipMemsetAsync(refs, 0xff, cap * sizeof(RunRef), c->stream));  // (what the list does not reach reads 0xffffffff, as the per-view lists' tails)
+        if (int e = run_refs_enqueue(c, blk, n_images, npix, 0u, header, refs, nullptr, 0u, 0u, 0u)) return e;
+        HIP_TRY(c, hipMemcpyAsync(head4, header, sizeof head4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(refs_out, refs, cap * sizeof(RunRef), hipMemcpyDeviceToHost, c->stream));
+        return PTMI_OK;
+      },
+      1);
+  if (r) return r;
+  memcpy(header_out, head4, 12);
+  return PTMI_OK;
+}
+
 int ptmi_render_views_until_runs(ptmi_ctx* c, const float* views16, uint32_t n_views, const uint32_t* first_frames, uint32_t frames_per_round, uint32_t min_frames,
                                  uint32_t max_frames, const ptmi_noise_params* params, float target, uint32_t* frames_done, ptmi_view_noise* out, uint64_t* paths_traced) {
   const char* who = "ptmi_render_views_until_runs";
@@ -1399,46 +1441,68 @@ int ptmi_render_views_until_runs(ptmi_ctx* c, const float* views16, uint32_t n_v
   if (!c->fb || c->W <= 0) return fail(c, PTMI_ERR_STATE, "no framebuffer: call ptmi_resize first");
   const uint32_t npix = (uint32_t)c->W * (uint32_t)c->H, n_runs = ptmn_run_count(npix);
   std::vector<uint32_t> firsts, counts;
-  std::vector<RunHeader> heads;
   try {
     firsts.resize(n_views);
     counts.resize(n_views);
-    heads.resize(n_views);
   } catch (const std::bad_alloc&) {
-    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the headers");
+    return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the frame numbers");
   }
   HIP_TRY(c, hipSetDevice(c->device));
   (void)hipGetLastError();
-  HIP_TRY(c, c->d_run_noise.ensure_idle(RunNoiseBlock::bytes(n_views, n_runs), c->stream));  // (before anything is enqueued)
-  // Phase A: every view's first frames in one batched call across the views, with reset
+  // (before anything is enqueued: the statistic's block with the views' frame counts and one word of complaints behind it, and the rounds' table)
+  const size_t noise_bytes = (RunNoiseBlock::bytes(n_views, n_runs) + 3) / 4 * 4;
+  HIP_TRY(c, c->d_run_noise.ensure_idle(noise_bytes + ((size_t)n_views + 1) * 4, c->stream));
+  uint32_t* d_done = reinterpret_cast<uint32_t*>(c->d_run_noise.as<uint8_t>() + noise_bytes);
   const uint32_t fa = std::min(min_frames, max_frames);
   for (uint32_t v = 0; v < n_views; v++) firsts[v] = first_frames ? first_frames[v] : 0u, counts[v] = fa;
+  uint8_t* tab_host = nullptr;
+  if (fa < max_frames)
+    if (int r = stage_run_refs_table(c, views16, n_views, firsts.data(), (size_t)n_views * n_runs, &tab_host)) return r;
+  // Phase A: every view's first frames in one batched call across the views, with reset
   if (int r = ptmi_render_views_frames(c, views16, n_views, firsts.data(), counts.data(), 1)) return r;
   for (uint32_t v = 0; v < n_views; v++) frames_done[v] = fa;
   uint64_t paths = (uint64_t)n_views * npix * fa;
-  // Rounds: the statistic and the lists of the views that may still get frames (a met run is never sampled again, so it stays met and a view without an open run stays
-  // without), the headers to the host, and per view with an open run one run batch straight from the device list.  All open runs of a view hold the view's count.
-  uint32_t lo = 0, hi = n_views;  // the views still open lie in [lo, hi)
-  while (fa < max_frames && lo < hi) {
-    const uint32_t n = hi - lo;
-    const RunNoiseBlock blk = RunNoiseBlock::at(c->d_run_noise.p, n, n_runs);
-    int r = run_noise_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>() + (size_t)lo * npix, c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)lo * npix, n, npix, P.floor, target, blk);
-    if (r == PTMI_OK) r = run_noise_fetch(c, blk, n, n_runs, heads.data(), nullptr, nullptr);
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    if (r) return r;
-    HIP_TRY(c, e);
-    uint32_t new_lo = hi, new_hi = lo;
-    for (uint32_t i = 0; i < n; i++) {
-      const uint32_t v = lo + i;
-      if (heads[i].n_open == 0 || frames_done[v] >= max_frames) continue;
-      const uint32_t nf = std::min(frames_per_round, max_frames - frames_done[v]);
-      r = render_runs_enqueue(c, views16 + 16 * (size_t)v, v, firsts[v] + frames_done[v], nf, blk.lists + (size_t)i * n_runs, heads[i].n_local);
-      if (r) return r;
-      frames_done[v] += nf;
-      paths += (uint64_t)heads[i].n_local * nf;
-      if (frames_done[v] < max_frames) new_lo = std::min(new_lo, v), new_hi = std::max(new_hi, v + 1);
+  // Rounds: the statistic and the lists of all views (a met run is never sampled again, so it stays met and a view without an open run stays without), k_run_refs —
+  // the round's ONE list across the views, on the device —, its 12-byte header to the host, and one run batch across the views straight from that list.  Every view
+  // that is still open has got every round so far, so all of them hold the same count, `done`, and one n_frames serves the batch: k_run_refs checks it where it adds
+  // the round's frames to the views' counts, which come back once, at the end.
+  if (fa < max_frames) {
+    uint8_t* tab_dev = c->run_refs.dev.as<uint8_t>();
+    uint32_t* d_header = reinterpret_cast<uint32_t*>(tab_dev + run_refs_header_at(n_views));
+    RunRef* d_refs = reinterpret_cast<RunRef*>(tab_dev + run_refs_at(n_views));
+    HIP_TRY(c, c->run_refs.send(run_refs_header_at(n_views), c->stream));  // (the rows; k_run_refs writes what lies behind them)
+    for (uint32_t v0 = 0; v0 < n_views; v0 += 1u << 20) {  // (the counts start at phase A's: a memset writes bytes, so they go up from the host)
+      const uint32_t nv = std::min(1u << 20, n_views - v0);
+      HIP_TRY(c, hipMemcpyAsync(d_done + v0, frames_done + v0, (size_t)nv * 4, hipMemcpyHostToDevice, c->stream));
     }
-    lo = new_lo, hi = new_hi;
+    HIP_TRY(c, hipMemsetAsync(d_done + n_views, 0, 4, c->stream));
+    const RunNoiseBlock blk = RunNoiseBlock::at(c->d_run_noise.p, n_views, n_runs);
+    for (uint32_t done = fa; done < max_frames;) {
+      const uint32_t nf = std::min(frames_per_round, max_frames - done);
+      uint32_t head[3] = {0u, 0u, 0u};
+      int r = run_noise_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>(), c->stacks[STACK_MOMENTS].buf.as<float4>(), n_views, npix, P.floor, target, blk);
+      if (r == PTMI_OK) r = run_refs_enqueue(c, blk, n_views, npix, 0u, d_header, d_refs, d_done, n_views, done, nf);
+      if (r == PTMI_OK && hipMemcpyAsync(head, d_header, sizeof head, hipMemcpyDeviceToHost, c->stream) != hipSuccess) r = fail(c, PTMI_ERR_DEVICE, std::string(who) + ": the header's read-back failed");
+      const hipError_t e = hipStreamSynchronize(c->stream);
+      if (r) return r;
+      HIP_TRY(c, e);
+      const RunRefsHeader h{head[0], head[1], head[2]};
+      if (h.n_local == 0) break;  // no view has an open run
+      r = render_views_runs_enqueue(c, views16, n_views, done, nf, h);
+      if (r) return r;
+      done += nf;
+      paths += (uint64_t)h.n_local * nf;
+    }
+    std::vector<uint32_t> got;
+    try {
+      got.resize((size_t)n_views + 1);
+    } catch (const std::bad_alloc&) {
+      return fail(c, PTMI_ERR_NO_MEMORY, std::string(who) + ": no host memory for the frame counts");
+    }
+    HIP_TRY(c, hipMemcpyAsync(got.data(), d_done, got.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (got[n_views] != 0u) return fail(c, PTMI_ERR_STATE, std::string(who) + ": internal: a round's open views did not all hold the same frame count");
+    memcpy(frames_done, got.data(), (size_t)n_views * 4);
   }
   if (paths_traced) *paths_traced = paths;
   if (out) return ptmi_view_noise_stats(c, &P, 0, n_views, out);

@@ -89,6 +89,11 @@ export class Ptmi {
   // framesPerRound to the runs that have not met target: {framesDone: Uint32Array — the most any run of the view got —, noise, pathsTraced}; readViewMean divides
   // every pixel by its own frame count (w = that count).
   renderViewRuns(view16, view, firstFrame, nFrames, runs) { this.native.renderViewRuns(this.h, view16, view, firstFrame, nFrames, Uint32Array.from(runs)); }
+  // renderViewsRuns (ptmi_render_views_runs): ONE batch for the listed runs of many views — frames firstFrames[v] .. firstFrames[v] + nFrames - 1 of view v for every
+  // listed view; (runViews[i], runs[i]) strictly ascending by (view, run).  views: Float32Array(16 V); the other arrays: Uint32Array or anything Uint32Array.from takes.
+  renderViewsRuns(views, firstFrames, nFrames, runViews, runs) {
+    this.native.renderViewsRuns(this.h, views, Uint32Array.from(firstFrames), nFrames, Uint32Array.from(runViews), Uint32Array.from(runs));
+  }
   viewRunNoise(target, firstView, nViews, params = null) { return this.native.viewRunNoise(this.h, target, firstView, nViews, params); }
   renderViewsUntilRuns(views, firstFrames, framesPerRound, minFrames, maxFrames, target, params = null) {
     return this.native.renderViewsUntilRuns(this.h, views, firstFrames, framesPerRound, minFrames, maxFrames, target, params);

@@ -45,6 +45,7 @@ SYMBOLS = [
     "ptmi_fuse_views_deform", "ptmi_fuse_images_deform", "ptmi_fuse_reference_deform", "ptmi_fuse_deform_records",
     "ptmi_render_view_runs", "ptmi_view_run_noise", "ptmi_run_noise_images", "ptmi_run_noise_reference", "ptmi_render_views_until_runs",
     "ptmi_read_view_mean", "ptmi_resolve_view_mean_rgba8",
+    "ptmi_render_views_runs", "ptmi_run_refs_reference", "ptmi_run_refs_images",
 ]
 
 RUN_PIXELS = 64  # a run: 64 consecutive pixels of an image in row-major order (include/ptmi.h, "RENDERING TO A NOISE TARGET BY RUNS")
@@ -330,6 +331,11 @@ def load_library(build=False, path=None):
         L.ptmi_render_views_until_runs.argtypes = [vp, fp, u32, fp, u32, u32, u32, qp, ctypes.c_float, fp, fp, ctypes.POINTER(ctypes.c_uint64)]
         L.ptmi_read_view_mean.argtypes = [vp, u32, fp, sz]
         L.ptmi_resolve_view_mean_rgba8.argtypes = [vp, u32, fp, sz]
+    if hasattr(L, "ptmi_render_views_runs"):  # (an older A/B build loaded through PTMI_LIB renders one view's runs per batch)
+        qp = ctypes.POINTER(NoiseParams)
+        L.ptmi_render_views_runs.argtypes = [vp, fp, u32, fp, u32, fp, fp, u32]
+        L.ptmi_run_refs_reference.argtypes = [u32, u32, fp, fp, fp, fp]
+        L.ptmi_run_refs_images.argtypes = [vp, fp, fp, i32, i32, u32, qp, ctypes.c_float, fp, fp]
     if explicit:
         _libs[path] = L
     else:
@@ -774,6 +780,29 @@ def run_noise_reference(colour_sums, moments, target, params=None, lib=None):
     if st != 0:
         raise PtmiError(st, "ptmi_run_noise_reference failed")
     return _run_noise_result(rec, n_open, runs)
+
+
+def _run_refs_result(refs, header):
+    """(refs (n_listed, 2) uint32 — {view, run}, the full runs' section and then the partial runs' —, (n_full, n_part, n_local))"""
+    n_full, n_part, n_local = (int(x) for x in header)
+    return refs[:n_full + n_part].copy(), (n_full, n_part, n_local)
+
+
+def run_refs_reference(n_open, open_runs, npix, lib=None):
+    """ptmi_run_refs_reference: the two-section list of a run batch across views, on the CPU (no GPU needed) — THE DEFINITION of its order.  n_open: (V,) uint32;
+    open_runs: per view its ascending open runs — the list of arrays run_noise_reference / view_run_noise return, or a (V, n_runs) array whose rows begin with them.
+    Returns (refs (n_full + n_part, 2) uint32 {view, run}: the full runs ascending by (view, run), then the partial runs ascending by view; (n_full, n_part, n_local))."""
+    n = np.ascontiguousarray(n_open, np.uint32).reshape(-1)
+    n_runs = (int(npix) + RUN_PIXELS - 1) // RUN_PIXELS
+    rows = np.full((n.size, max(n_runs, 1)), 0xFFFFFFFF, np.uint32)
+    for v in range(n.size):
+        l = np.asarray(open_runs[v], np.uint32).reshape(-1)[:min(int(n[v]), n_runs)]
+        rows[v, :l.size] = l
+    refs, header = np.full((max(int(n.sum()), 1), 2), 0xFFFFFFFF, np.uint32), np.zeros(3, np.uint32)
+    st = (lib or load_library()).ptmi_run_refs_reference(n.size, int(npix), _ptr(n), _ptr(rows), _ptr(refs), _ptr(header))
+    if st != 0:
+        raise PtmiError(st, "ptmi_run_refs_reference failed")
+    return _run_refs_result(refs, header)
 
 
 class NativeHost:
@@ -1447,6 +1476,29 @@ class Context:
         self._ck(self.lib.ptmi_render_views_until_runs(self.h, _ptr(v), v.shape[0], _optr(f), frames_per_round, min_frames, max_frames,
                                                        None if params is None else ctypes.byref(params), float(target), _ptr(done), _ptr(out), ctypes.byref(paths)))
         return done, out, paths.value
+
+    def render_views_runs(self, views, first_frames, n_frames, run_views, runs):
+        """ptmi_render_views_runs: ONE wavefront batch for the listed runs of many views — adds frames first_frames[v] .. first_frames[v] + n_frames - 1 of views[v] to
+        the listed runs of image v of the view and moment stacks, for every listed view; every other pixel keeps its bits.  views: (V, 16); first_frames: (V,) uint32 or
+        a scalar; (run_views[i], runs[i]): strictly ascending by (view, run).  Needs set_view_moments and both stacks.  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32)
+        assert v.ndim == 2 and v.shape[1] == 16, "views: (V, 16) float32"
+        f = _frame_arrays(v.shape[0], first_frames, 0)[0]
+        rv = np.ascontiguousarray(run_views, np.uint32).reshape(-1)
+        r = np.ascontiguousarray(runs, np.uint32).reshape(-1)
+        assert rv.size == r.size, "one view per listed run"
+        self._ck(self.lib.ptmi_render_views_runs(self.h, _ptr(v), v.shape[0], _ptr(f), n_frames, _ptr(rv) if rv.size else None, _ptr(r) if r.size else None, r.size))
+
+    def run_refs_images(self, colour_sums, moments, target, params=None):
+        """ptmi_run_refs_images: the kernels of a round of render_views_until_runs (k_run_noise, k_run_list, k_run_refs) on host arrays of any size — the device's
+        two-section list, in run_refs_reference's form; synchronous."""
+        c, m, _, _, runs = _run_noise_arrays(colour_sums, moments)
+        refs, header = np.zeros((max(runs.size, 1), 2), np.uint32), np.zeros(3, np.uint32)
+        self._ck(self.lib.ptmi_run_refs_images(self.h, _ptr(c), _ptr(m), c.shape[2], c.shape[1], c.shape[0], None if params is None else ctypes.byref(params), float(target),
+                                               _ptr(refs), _ptr(header)))
+        full = _run_refs_result(refs, header)
+        assert (refs[full[0].shape[0]:runs.size] == 0xFFFFFFFF).all(), "behind the list the device block keeps its fill"
+        return full
 
     def read_view_mean(self, view):
         """ptmi_read_view_mean: image `view` as (H, W, 4) float32 with every pixel's own divisor — rgb = S.rgb / M.w, 0 where M.w == 0; w = M.w."""
