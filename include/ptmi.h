@@ -627,9 +627,11 @@ int ptmi_render_views_until_each(ptmi_ctx* ctx, const float* views16, uint32_t n
  * compile: they agree integer for integer.
  *
  * After these calls a view's pixels no longer share one divisor: pixel p of view v sums M.w frames, its own count in the moment stack.  ptmi_read_view_mean and
- * ptmi_resolve_view_mean_rgba8 read such a view.  OUT OF SCOPE: the denoise, fuse and accumulate calls on the device stacks take one divisor per view, and after run
- * rounds they are defined only for a view whose runs all hold the same count; a caller can pass the means (ptmi_read_view_mean) with frame_num = 1 to the *_images
- * calls.  ptmi_view_noise_stats divides by each pixel's own M.w already and needs no change. */
+ * ptmi_resolve_view_mean_rgba8 read such a view.  THE CONSUMERS of such stacks are the *_counts calls below ("CONSUMERS WITH PER-PIXEL FRAME COUNTS"):
+ * ptmi_denoise_views_counts, ptmi_denoise_views_guided_counts, ptmi_fuse_views_counts and ptmi_accumulate_views_counts divide every colour sum by the M.w of the pixel it
+ * belongs to, on the device, where the counts already lie.  (The one-divisor and *_frames calls stay defined only for a view whose runs all hold the same count; and
+ * handing means to them with frame_num = 1 is wrong for the guided filter and for accumulation, whose variance reads the SUMS beside M.)  ptmi_view_noise_stats
+ * divides by each pixel's own M.w already and needs no change. */
 struct ptmi_run_noise { /* one run's record: four u32, 16 bytes */
   uint32_t counted; /* pixels of the run that entered the sums */
   uint32_t sum_q;   /* sum of q over them: at most 64 * 255 * 65536 */
@@ -759,6 +761,53 @@ int ptmi_fuse_reference_frames(const float* colour, const float* layers, const f
 int ptmi_accumulate_reference_frames(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
                                      const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
                                      const float* history_in, float* out, int threads);
+
+/* CONSUMERS WITH PER-PIXEL FRAME COUNTS.  After ptmi_render_view_runs, ptmi_render_views_runs or ptmi_render_views_until_runs the pixels of ONE view differ in frame
+ * count: pixel p of view v sums M.w frames, its own count in the moment stack.  The calls below are the four consumers, their *_images forms and their CPU references
+ * with one divisor PER PIXEL: everywhere a definition above divides a colour sum S by F — "prepare" (c = S.rgb / F), the denoisers' remodulation and pass-through,
+ * "Fusion" steps 2-3 and its pass-through, "Temporal accumulation" own, mean and pass-through — it divides by THE COUNT OF THE PIXEL THAT S BELONGS TO: the output
+ * pixel p of view v takes the count of (v, p); the pixel q that fusion samples in neighbour u takes the count of (u, q); the pixel q that accumulation looks up in view
+ * v-1 takes the count of (v-1, q), so its validity test is the one view v-1 itself applied to q.  Nothing else in the arithmetic changes — include/ptmi_denoise.h,
+ * ptmi_guided.h, ptmi_fuse.h and ptmi_accumulate.h take F as an argument — and the guided filter's temporal variance and accumulation's own state read M.w already.
+ * With all counts equal to F every result is the one-frame_num call's (and the *_frames call's), bit for bit; for the plain denoiser, fusion and accumulation, where S
+ * enters only as S / F, the result is also the one-frame_num call's on S' = S / count with frame_num = 1, bit for bit.
+ * A COUNT OF 0 (or any other value) is no special case and is never refused: S / 0 is NaN or +-inf by IEEE, the finite tests of "prepare" make that pixel invalid —
+ * it is not filtered, not fused, not sampled, not taken over — and its pass-through output is what the division gives.
+ * *_views_counts read the counts WHERE THEY LIE, in .w of the moment stack: no table travels, and the calls take no frame_nums.  They run on the view, moment and
+ * feature stacks and write the denoised, fused and accumulated stacks their siblings write; every reader of those (ptmi_read_*, ptmi_resolve_*, the device pointers,
+ * ptmi_denoise_views_accumulated, ptmi_fuse_views with source = 1) works on the results.  Asynchronous where the siblings are.  Errors, in the siblings' order:
+ * PTMI_ERR_UNSUPPORTED a multi-device or sharded context; PTMI_ERR_INVALID_ARG params outside their domain; PTMI_ERR_STATE moments are off, a stack is missing, or
+ * the moment stack has another size than the view stack (the plain denoiser and fusion ask this too, since they read M.w); PTMI_ERR_INVALID_ARG the range.  Everything
+ * that can fail for want of memory is had before anything is enqueued; a refused call leaves every stack as it was.  ptmi_fuse_views_counts has no `source`: it reads
+ * the view stack.
+ * *_images_counts and *_reference_counts: the plain denoiser and fusion, which take no moments, take `counts` [n_images][h][w] f32; the guided filter and accumulation
+ * take the moments they already take, whose w is the count.
+ * The kernels (csrc/: k_denoise_prepare_counts, k_denoise_level_counts, k_guided_level_counts, k_fuse_counts, k_accumulate_view_counts) stand beside the *_frames ones and
+ * take the counts as a pointer and a stride in f32 — 4 into the moment stack, 1 into a count image — as per-lane loads issued with the pixel's other operands.
+ * The *_motion and *_deform variants with per-pixel counts come later. */
+int ptmi_denoise_views_counts(ptmi_ctx* ctx, const ptmi_denoise_params* params, uint32_t first_view, uint32_t n_views);
+int ptmi_denoise_views_guided_counts(ptmi_ctx* ctx, const ptmi_guided_params* params, uint32_t first_view, uint32_t n_views);
+int ptmi_fuse_views_counts(ptmi_ctx* ctx, const ptmi_fuse_params* params, const float* views16, uint32_t first_view, uint32_t n_views);
+int ptmi_accumulate_views_counts(ptmi_ctx* ctx, const ptmi_accumulate_params* params, const float* views16, uint32_t first_view, uint32_t n_views, int resume);
+int ptmi_denoise_images_counts(ptmi_ctx* ctx, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const float* counts,
+                               const ptmi_denoise_params* params, float* out);
+int ptmi_denoise_images_guided_counts(ptmi_ctx* ctx, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images,
+                                      const ptmi_guided_params* params, float* out, float* var_out);
+int ptmi_fuse_images_counts(ptmi_ctx* ctx, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* counts,
+                            float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out);
+int ptmi_accumulate_images_counts(ptmi_ctx* ctx, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                  float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in,
+                                  float* out);
+/* ... and without a GPU.  PTMI_ERR_INVALID_ARG: what the siblings refuse, and a null counts. */
+int ptmi_denoise_reference_counts(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const float* counts, const ptmi_denoise_params* params,
+                                  float* out);
+int ptmi_denoise_guided_reference_counts(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images,
+                                         const ptmi_guided_params* params, float* out, float* var_out);
+int ptmi_fuse_reference_counts(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* counts, float fov_degrees,
+                               const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out);
+int ptmi_accumulate_reference_counts(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                     float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in,
+                                     float* out, int threads);
 
 /* ACCUMULATION WITH PER-OBJECT MOTION (the motion-vector half of SVGF).  "Temporal accumulation" reprojects through a STATIC world: view v carries pixel p to its
  * world point X and projects that same X into view v-1.  Where p's object moved between the two views — a mesh animated through ptmi_refit_scene_bvh — X is not where

@@ -13,3 +13,4 @@ from . import _build  # noqa: F401
 from . import ptmi, scenes  # noqa: F401
 from .ptmi import Context, DenoiseParams, FuseParams, GuidedParams, NoiseParams, Params, PtmiError, default_denoise_params, default_fuse_params, default_guided_params, default_noise_params, default_params, denoise_guided_reference, denoise_reference, fuse_reference, load_library, noise_reference  # noqa: F401
 from .ptmi import accumulate_reference_frames, denoise_guided_reference_frames, denoise_reference_frames, fuse_reference_frames  # noqa: F401
+from .ptmi import accumulate_reference_counts, denoise_guided_reference_counts, denoise_reference_counts, fuse_reference_counts  # noqa: F401

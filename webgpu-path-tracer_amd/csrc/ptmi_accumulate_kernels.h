@@ -2,7 +2,7 @@
 // "Temporal accumulation").  Every f32 operation of a pixel is in include/ptmi_accumulate.h, which the host natives include too; this file only decides where the
 // operands come from.
 //
-// k_accumulate_view, k_accumulate_view_frames (one body, accumulate_view)
+// k_accumulate_view, k_accumulate_view_frames, k_accumulate_view_counts (one body, accumulate_view)
 //                       One lane owns one pixel of ONE view, a wave 64 neighbouring pixels of one row, a block four such waves: k_fuse's row tiles.  A call launches
 //                       its views one after the other on one stream, so view v's launch finds what view v-1's wrote.  The own view's matrix and the previous view's
 //                       B, o come through scalar loads (fuse_load_own, fuse_load_neighbour).  The lane loads S, M, N, A, I of p together; after an accepted projection
@@ -96,8 +96,10 @@ DEV int accumulate_deform(const DeformArgs& de, const MotionArgs& mo, uint32_t i
 // no history; out0, out1, out2: view v's image of planes 0, 1, 2; tab: kFuseRow float4 per view of the stack; lamb: one byte per material index or nullptr.
 // grid: x = (tiles of 64 columns x rows) / 4; block 256.
 // FRAMES: frames [n_stack] f32, F_u of every view of the stack; k.F is then not read: own, mean and the pass-through take F_v, the lookup's validity test F_{v-1}.
+// COUNTS (without FRAMES): neither k.F nor frames is read: own, mean and the pass-through of p take the Mp.w the lane holds already; the lookup's validity test takes M.w of (v-1, q),
+// a seventh gather — of that one f32 — inside the fenced group at q.  The count differs from lane to lane.
 // MOTION: mo as above; every other instance is handed an empty one and reads none of it.  DEFORM (with MOTION): de as above, likewise.
-template <bool FRAMES, bool MOTION = false, bool DEFORM = false>
+template <bool FRAMES, bool MOTION = false, bool DEFORM = false, bool COUNTS = false>
 DEV void accumulate_view(const float4* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ layers, const float4* prev1, const float4* prev2,
                          float4* out0, float4* out1, float4* out2, const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t v,
                          ptmf_consts k, ptma_consts ka, const float* __restrict__ frames, const MotionArgs& mo = MotionArgs{}, const DeformArgs& de = DeformArgs{}) {
@@ -114,6 +116,7 @@ DEV void accumulate_view(const float4* __restrict__ colour, const float4* __rest
   const float4 Sp = colour[(size_t)v * npix + idx], Mp = moments[(size_t)v * npix + idx], Np = Lv[idx], Ap = Lv[npix + idx], Ip = Lv[2 * npix + idx];
   fuse_loaded(Sp, Np, Ap, Ip);
   asm volatile("" ::"v"(Mp.x), "v"(Mp.y), "v"(Mp.z), "v"(Mp.w));
+  if (COUNTS) k.F = Mp.w;
   const ptmd_f4 S = dn_f4(Sp), A = dn_f4(Ap);
   ptmd_f4 dp, gp, P1, P2;
   const int valid = ptmd_prepare(S, dn_f4(Np), A, dn_f4(Ip), k.F, k.floor, &dp, &gp);
@@ -133,14 +136,22 @@ DEV void accumulate_view(const float4* __restrict__ colour, const float4* __rest
       const size_t q = (size_t)qy * (size_t)W + (size_t)qx;
       const float4* Lu = layers + (size_t)(v - 1u) * 3 * npix;
       const float4 Sq = colour[(size_t)(v - 1u) * npix + q], Nq = Lu[q], Aq = Lu[npix + q], Iq = Lu[2 * npix + q], H1 = prev1[q], H2 = prev2[q];  // six independent gathers
-      accumulate_loaded(Sq, Nq, Aq, Iq, H1, H2);
       float wgt;
       int taken;
-      if (FRAMES) {
+      if constexpr (COUNTS) {
+        const float Cq = reinterpret_cast<const float*>(moments + (size_t)(v - 1u) * npix + q)[3];  // ... and a seventh: M.w of q
+        accumulate_loaded(Sq, Nq, Aq, Iq, H1, H2);
+        asm volatile("" ::"v"(Cq));
+        ptmf_consts ku = k;
+        ku.F = Cq;
+        taken = ptma_weight(&ku, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), &wgt);
+      } else if constexpr (FRAMES) {
+        accumulate_loaded(Sq, Nq, Aq, Iq, H1, H2);
         ptmf_consts ku = k;
         ku.F = ldu(frames + (v - 1u));
         taken = ptma_weight(&ku, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), &wgt);
       } else {
+        accumulate_loaded(Sq, Nq, Aq, Iq, H1, H2);
         taken = ptma_weight(&k, dp, gp, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), &wgt);
       }
       if (taken) ptma_take(&ka, wgt, dn_f4(H1), dn_f4(H2), &P1, &P2);
@@ -165,6 +176,14 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_view_frames(const float4*
                                                                    const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H,
                                                                    uint32_t v, ptmf_consts k, ptma_consts ka, const float* __restrict__ frames) {
   accumulate_view<true>(colour, moments, layers, prev1, prev2, out0, out1, out2, tab, lamb, n_materials, W, H, v, k, ka, frames);
+}
+
+// k_accumulate_view with every pixel's own divisor, M.w (ptmi_accumulate_views_counts, ptmi_accumulate_images_counts)
+__global__ __launch_bounds__(kBlock) void k_accumulate_view_counts(const float4* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ layers,
+                                                                   const float4* prev1, const float4* prev2, float4* out0, float4* out1, float4* out2,
+                                                                   const float4* __restrict__ tab, const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H,
+                                                                   uint32_t v, ptmf_consts k, ptma_consts ka) {
+  accumulate_view<false, false, false, true>(colour, moments, layers, prev1, prev2, out0, out1, out2, tab, lamb, n_materials, W, H, v, k, ka, nullptr);
 }
 
 // k_accumulate_view_frames with the motions of the views' objects (ptmi_accumulate_views_motion, ptmi_accumulate_images_motion)

@@ -17,6 +17,9 @@
 // The *_frames entry points (ptmi_denoise_views_frames, ..., include/ptmi.h "PER-VIEW FRAME NUMBERS AND COUNTS") divide view u's sums by F_u, read from a table of one
 // f32 per view: k_denoise_prepare_frames per lane (v = i / npix: a wave straddles two views wherever npix is no multiple of 64), the two LAST levels for the block's
 // view, blockIdx.z, through a scalar load.  The levels before the last read no F and are the instances above.
+// The *_counts entry points (ptmi_denoise_views_counts, ..., include/ptmi.h "CONSUMERS WITH PER-PIXEL FRAME COUNTS") divide pixel p's sums by p's OWN count, which
+// varies inside a wave: a per-lane load beside the pixel's colour sum, never a scalar one.  counts + (view * npix + p) * cstride is pixel p's count, cstride in f32:
+// 4 where `counts` points at .w of a moment stack, 1 for a count image — so the stack calls and the *_images_counts calls share the entries.
 #pragma once
 
 #include "../../include/ptmi_guided.h"
@@ -55,13 +58,27 @@ __global__ __launch_bounds__(kBlock) void k_denoise_prepare_frames(const float4*
   }
 }
 
+// k_denoise_prepare with every pixel's own divisor: counts at the batch's first view, item i's count cstride f32 apart
+__global__ __launch_bounds__(kBlock) void k_denoise_prepare_counts(const float4* __restrict__ colour, const float4* __restrict__ layers, size_t n_items, size_t npix,
+                                                                   const float* __restrict__ counts, uint32_t cstride, float floor, float4* __restrict__ d0, float4* __restrict__ g) {
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_items; i += (size_t)gridDim.x * kBlock) {
+    const size_t v = i / npix, p = i - v * npix;
+    const float4* L = layers + v * 3 * npix;
+    ptmd_f4 d, gg;
+    ptmd_prepare(dn_f4(colour[i]), dn_f4(L[p]), dn_f4(L[npix + p]), dn_f4(L[2 * npix + p]), counts[i * cstride], floor, &d, &gg);
+    d0[i] = dn_float4(d);
+    g[i] = dn_float4(gg);
+  }
+}
+
 // One level of a block's tile.  grid: x = tiles of 64 columns, y = chunks x step (chunk = blockIdx.y / step, residue = blockIdx.y % step), z = view of the batch; dynamic LDS
 // (ty + 4) * (64 + 4 step) * 32 B, GUIDED 40 B.  GUIDED: vin, vg, vout: [n][npix] f32 of the batch; LAST: dout and vout (may be nullptr) are the call's output arrays
 // at the batch's first view.  Not GUIDED: vin, vg, vout and kg are not read.
-template <bool GUIDED, bool LAST>
+// COUNTS (with LAST): F is not read; the remodulation of pixel p divides by counts[(view * npix + p) * cstride], loaded beside colour and A of p.
+template <bool GUIDED, bool LAST, bool COUNTS = false>
 DEV void atrous_level(const float4* __restrict__ din, const float4* __restrict__ g, const float* __restrict__ vin, const float* __restrict__ vg, float4* __restrict__ dout,
                       float* __restrict__ vout, const float4* __restrict__ colour, const float4* __restrict__ layers, int W, int H, int step, int ty, const ptmd_consts& k,
-                      const ptmg_consts& kg, float F) {
+                      const ptmg_consts& kg, float F, const float* __restrict__ counts = nullptr, uint32_t cstride = 0) {
   extern __shared__ float4 dn_lds[];
   const int cols = kDenoiseTX + 4 * step, rows = ty + 4;
   float4* sd = dn_lds;
@@ -127,6 +144,7 @@ DEV void atrous_level(const float4* __restrict__ din, const float4* __restrict__
     }
     if (LAST) {
       const float4* L = layers + view * 3 * npix;
+      if constexpr (COUNTS) F = counts[(view * npix + p) * cstride];
       dout[view * npix + p] = dn_float4(ptmd_remodulate(dn_f4(colour[view * npix + p]), dn_f4(L[npix + p]), F, k.floor, d));
       if (GUIDED && vout) vout[view * npix + p] = d.w == d.w ? vp : ptmd_nan();
     } else {
@@ -160,6 +178,20 @@ __global__ __launch_bounds__(kBlock) void k_guided_level_frames(const float4* __
                                                                 const float4* __restrict__ layers, int W, int H, int step, int ty, ptmd_consts k, ptmg_consts kg,
                                                                 const float* __restrict__ F) {
   atrous_level<true, true>(din, g, vin, vg, dout, vout, colour, layers, W, H, step, ty, k, kg, ldu(F + blockIdx.z));
+}
+
+// The last level of either filter with every pixel's own divisor: counts at the batch's first view
+__global__ __launch_bounds__(kBlock) void k_denoise_level_counts(const float4* __restrict__ din, const float4* __restrict__ g, float4* __restrict__ dout, const float4* __restrict__ colour,
+                                                                 const float4* __restrict__ layers, int W, int H, int step, int ty, ptmd_consts k, const float* __restrict__ counts,
+                                                                 uint32_t cstride) {
+  atrous_level<false, true, true>(din, g, nullptr, nullptr, dout, nullptr, colour, layers, W, H, step, ty, k, ptmg_consts{}, 0.0f, counts, cstride);
+}
+
+__global__ __launch_bounds__(kBlock) void k_guided_level_counts(const float4* __restrict__ din, const float4* __restrict__ g, const float* __restrict__ vin, const float* __restrict__ vg,
+                                                                float4* __restrict__ dout, float* __restrict__ vout, const float4* __restrict__ colour,
+                                                                const float4* __restrict__ layers, int W, int H, int step, int ty, ptmd_consts k, ptmg_consts kg,
+                                                                const float* __restrict__ counts, uint32_t cstride) {
+  atrous_level<true, true, true>(din, g, vin, vg, dout, vout, colour, layers, W, H, step, ty, k, kg, 0.0f, counts, cstride);
 }
 
 }  // namespace ptmi

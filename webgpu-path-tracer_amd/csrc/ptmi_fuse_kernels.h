@@ -2,7 +2,7 @@
 // neighbour view of its window, the one pixel its first hit projects into.  Every f32 operation of a pixel is in include/ptmi_fuse.h, which the host native
 // ptmi_fuse_reference includes too; this file only decides where the operands come from.
 //
-// k_fuse, k_fuse_frames (one body, fuse_view)
+// k_fuse, k_fuse_frames, k_fuse_counts (one body, fuse_view)
 //          One lane owns one output pixel, a wave 64 neighbouring pixels of one row, a block four such waves; the grid's z axis runs over the call's output views, so
 //          a call is one launch.  The neighbour view u of the window loop is the same for the whole wave: its row of the view table (B_u, o_u: three float4) comes
 //          through scalar loads, as load_view_row's does, and so does the output view's own row (M_v, o_v).  An accepted projection reads S, N, A and I of q
@@ -87,16 +87,24 @@ DEV void fuse_deform_record_loaded(const float4& r0, const float4& r1, const flo
   asm volatile("" ::"v"(r5.z), "v"(r5.w));
 }
 
+// ... and a pixel's own count with them (COUNTS): one more operand behind the same fence, so that the count's load is issued with the four and not after a test
+DEV void fuse_loaded_count(const float4& S, const float4& N, const float4& A, const float4& I, const float& C) {
+  fuse_loaded(S, N, A, I);
+  asm volatile("" ::"v"(C));
+}
+
 // colour: [n_stack][npix] float4 (sums, or means with k.F = 1); layers: [n_stack][3][npix] float4; out: [n_stack][npix] float4; tab: kFuseRow float4 per view of the
 // stack; lamb: one byte per material index or nullptr.  grid: x = (tiles of 64 columns x rows) / 4, z = output view - view0; block 256.
 // FRAMES: frames [n_stack] f32, F_u of every view of the stack; k.F is then not read: p and the output take F_v, a neighbour's q takes F_u — u is wave-uniform, so the
 // count comes through a scalar load as the view's row does.
+// COUNTS (without FRAMES): counts + ((size_t)u * npix + q) * cstride is the count of pixel q of view u (cstride in f32: 4 into .w of a moment stack, 1 into a count image); k.F and
+// frames are not read.  The count differs from lane to lane: p's is loaded with p's four sums, q's is a fifth gather issued with S, N, A, I of q under their fence.
 // MOTION: mo.records = the composed records of output view view0 (slot [blockIdx.z][u - v + radius]), mo.ids = the id images of the whole stack or nullptr; every
 // other instance is handed an empty one and reads none of it.  DEFORM (with MOTION): de as above, moved = the masks of output view view0; likewise.
-template <bool FRAMES, bool MOTION = false, bool DEFORM = false>
+template <bool FRAMES, bool MOTION = false, bool DEFORM = false, bool COUNTS = false>
 DEV void fuse_view(const float4* __restrict__ colour, const float4* __restrict__ layers, float4* __restrict__ out, const float4* __restrict__ tab, const uint8_t* __restrict__ lamb,
                    uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k, const float* __restrict__ frames, const MotionArgs& mo = MotionArgs{},
-                   const FuseDeformArgs& de = FuseDeformArgs{}) {
+                   const FuseDeformArgs& de = FuseDeformArgs{}, const float* __restrict__ counts = nullptr, uint32_t cstride = 0) {
   const uint32_t tiles_x = ((uint32_t)W + 63u) / 64u;
   const uint32_t tile = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);  // wave-uniform
   const uint32_t y = tile / tiles_x;
@@ -109,7 +117,13 @@ DEV void fuse_view(const float4* __restrict__ colour, const float4* __restrict__
   if (FRAMES) k.F = ldu(frames + v);
   const float4* Lv = layers + (size_t)v * 3 * npix;
   const float4 Sp = colour[(size_t)v * npix + idx], Np = Lv[idx], Ap = Lv[npix + idx], Ip = Lv[2 * npix + idx];
-  fuse_loaded(Sp, Np, Ap, Ip);
+  if constexpr (COUNTS) {
+    const float Cp = counts[((size_t)v * npix + idx) * cstride];
+    fuse_loaded_count(Sp, Np, Ap, Ip, Cp);
+    k.F = Cp;
+  } else {
+    fuse_loaded(Sp, Np, Ap, Ip);
+  }
   const ptmd_f4 S = dn_f4(Sp), N = dn_f4(Np), A = dn_f4(Ap), I = dn_f4(Ip);
   ptmd_f4 dp, gp;
   float num[3] = {0.0f, 0.0f, 0.0f}, den = 0.0f;
@@ -204,6 +218,14 @@ DEV void fuse_view(const float4* __restrict__ colour, const float4* __restrict__
       const size_t q = (size_t)qy * (size_t)W + (size_t)qx;
       const float4* Lu = layers + (size_t)u * 3 * npix;
       const float4 Sq = colour[(size_t)u * npix + q], Nq = Lu[q], Aq = Lu[npix + q], Iq = Lu[2 * npix + q];  // four independent gathers
+      if constexpr (COUNTS) {
+        const float Cq = counts[((size_t)u * npix + q) * cstride];  // ... and a fifth
+        fuse_loaded_count(Sq, Nq, Aq, Iq, Cq);
+        ptmf_consts ku = k;
+        ku.F = Cq;
+        ptmf_sample(&ku, dp, gu, r, dn_f4(Sq), dn_f4(Nq), dn_f4(Aq), dn_f4(Iq), num, &den);
+        continue;
+      }
       fuse_loaded(Sq, Nq, Aq, Iq);
       if (FRAMES) {
         ptmf_consts ku = k;
@@ -227,6 +249,13 @@ __global__ __launch_bounds__(kBlock) void k_fuse_frames(const float4* __restrict
                                                         const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k,
                                                         const float* __restrict__ frames) {
   fuse_view<true>(colour, layers, out, tab, lamb, n_materials, W, H, n_stack, view0, k, frames);
+}
+
+// k_fuse with every pixel's own divisor (ptmi_fuse_views_counts, ptmi_fuse_images_counts); counts, cstride: as fuse_view's
+__global__ __launch_bounds__(kBlock) void k_fuse_counts(const float4* __restrict__ colour, const float4* __restrict__ layers, float4* __restrict__ out, const float4* __restrict__ tab,
+                                                        const uint8_t* __restrict__ lamb, uint32_t n_materials, int W, int H, uint32_t n_stack, uint32_t view0, ptmf_consts k,
+                                                        const float* __restrict__ counts, uint32_t cstride) {
+  fuse_view<false, false, false, true>(colour, layers, out, tab, lamb, n_materials, W, H, n_stack, view0, k, nullptr, MotionArgs{}, FuseDeformArgs{}, counts, cstride);
 }
 
 // k_fuse_frames with the composed motions of the views' objects (ptmi_fuse_views_motion, ptmi_fuse_images_motion)

@@ -773,12 +773,22 @@ static int frame_nums_ok(const float* frame_nums, uint32_t n) {
   return 1;
 }
 
+// The *_reference_counts calls' divisors, one per pixel: the count of pixel p of image v is p[((size_t)v * npix + p) * stride] — stride 4 from .w of the moments, 1 in
+// a count image.  Any value may stand there: S / 0 is what IEEE makes it, and the finite tests of the arithmetic then refuse the pixel.
+struct PixelCounts {
+  const float* p;
+  size_t stride;
+  float at(size_t v, size_t npix, size_t q) const { return p[(v * npix + q) * stride]; }
+};
+static PixelCounts counts_in_moments(const float* moments) { return PixelCounts{moments + 3, 4}; }
+
 // Both filters: a plain loop over pixels through include/ptmi_denoise.h and include/ptmi_guided.h, the headers the kernels of ptmi_denoise_views and
 // ptmi_denoise_views_guided compile: prepare, (guided: the initial variance,) per level (guided: the blur of the variance and) the 25 taps between two packed images,
 // remodulate.  One image after the other; nothing is tiled, threaded or reordered.  G = nullptr: the plain filter, which has no variance or luminance planes.
 // frame_nums: nullptr, or every image's own divisor (the *_reference_frames calls); the argument frame_num is then not read.
+// counts: nullptr, or every pixel's own divisor (the *_reference_counts calls): prepare and the remodulation of pixel p take p's count; neither of the other two is read.
 static int atrous_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params& P, const HostGuide* G,
-                            float* out, const float* frame_nums = nullptr) {
+                            float* out, const float* frame_nums = nullptr, const PixelCounts* counts = nullptr) {
   const size_t npix = (size_t)w * (size_t)h;
   std::vector<ptmd_f4> d[2], g;
   std::vector<float> var[2], vg, lum;
@@ -797,7 +807,7 @@ static int atrous_reference(const float* colour_sums, const float* layers, int w
     ptmd_f4* O = reinterpret_cast<ptmd_f4*>(out) + (size_t)v * npix;
     if (frame_nums) frame_num = frame_nums[v];
     for (size_t p = 0; p < npix; p++) {
-      ptmd_prepare(S[p], L[p], L[npix + p], L[2 * npix + p], frame_num, P.albedo_floor, &d[0][p], &g[p]);
+      ptmd_prepare(S[p], L[p], L[npix + p], L[2 * npix + p], counts ? counts->at(v, npix, p) : frame_num, P.albedo_floor, &d[0][p], &g[p]);
       if (G) lum[p] = ptmg_luma(d[0][p].x, d[0][p].y, d[0][p].z);
     }
     if (G)
@@ -872,7 +882,7 @@ static int atrous_reference(const float* colour_sums, const float* layers, int w
     }
     const std::vector<ptmd_f4>& last = d[P.levels & 1];
     for (size_t p = 0; p < npix; p++) {
-      O[p] = ptmd_remodulate(S[p], L[npix + p], frame_num, P.albedo_floor, last[p]);
+      O[p] = ptmd_remodulate(S[p], L[npix + p], counts ? counts->at(v, npix, p) : frame_num, P.albedo_floor, last[p]);
       if (G && G->var_out) G->var_out[(size_t)v * npix + p] = last[p].w == last[p].w ? var[P.levels & 1][p] : ptmd_nan();
     }
   }
@@ -880,14 +890,14 @@ static int atrous_reference(const float* colour_sums, const float* layers, int w
 }
 
 static int denoise_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const float* frame_nums,
-                             const ptmi_denoise_params* params, float* out) {
+                             const ptmi_denoise_params* params, float* out, const PixelCounts* counts = nullptr) {
   if (!colour_sums || !layers || !out || w <= 0 || h <= 0 || n_images == 0) return PTMI_ERR_INVALID_ARG;
   ptmi_denoise_params P;
   if (params) P = *params;
   else ptmi_default_denoise_params(&P);
   if (!ptmd_params_ok(P.levels, P.sigma_normal, P.sigma_depth, P.sigma_colour, P.albedo_floor)) return PTMI_ERR_INVALID_ARG;
   if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
-  return atrous_reference(colour_sums, layers, w, h, n_images, frame_num, P, nullptr, out, frame_nums);
+  return atrous_reference(colour_sums, layers, w, h, n_images, frame_num, P, nullptr, out, frame_nums, counts);
 }
 extern "C" int ptmi_denoise_reference(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params,
                                       float* out) {
@@ -898,9 +908,15 @@ extern "C" int ptmi_denoise_reference_frames(const float* colour_sums, const flo
   if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
   return denoise_reference(colour_sums, layers, w, h, n_images, 1.0f, frame_nums, params, out);
 }
+extern "C" int ptmi_denoise_reference_counts(const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const float* counts,
+                                             const ptmi_denoise_params* params, float* out) {
+  if (!counts) return PTMI_ERR_INVALID_ARG;
+  const PixelCounts C{counts, 1};
+  return denoise_reference(colour_sums, layers, w, h, n_images, 1.0f, nullptr, params, out, &C);
+}
 
 static int denoise_guided_reference(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
-                                    const float* frame_nums, const ptmi_guided_params* params, float* out, float* var_out) {
+                                    const float* frame_nums, const ptmi_guided_params* params, float* out, float* var_out, bool pixel_counts = false) {
   if (!colour_sums || !moments || !layers || !out || w <= 0 || h <= 0 || n_images == 0) return PTMI_ERR_INVALID_ARG;
   ptmi_guided_params P;
   if (params) P = *params;
@@ -908,8 +924,9 @@ static int denoise_guided_reference(const float* colour_sums, const float* momen
   if (!ptmg_params_ok(P.levels, P.sigma_normal, P.sigma_depth, P.sigma_luma, P.albedo_floor, P.min_frames, P.var_eps)) return PTMI_ERR_INVALID_ARG;
   if (!(frame_num > 0.0f) || !ptmd_finite(frame_num)) return PTMI_ERR_INVALID_ARG;
   const HostGuide G{moments, var_out, ptmg_make_consts(P.sigma_luma, P.var_eps), P.min_frames, nullptr};
+  const PixelCounts C = counts_in_moments(moments);
   return atrous_reference(colour_sums, layers, w, h, n_images, frame_num, ptmi_denoise_params{P.levels, P.sigma_normal, P.sigma_depth, 0.0f, P.albedo_floor, {}}, &G, out,
-                          frame_nums);
+                          frame_nums, pixel_counts ? &C : nullptr);
 }
 extern "C" int ptmi_denoise_guided_reference(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, float frame_num,
                                              const ptmi_guided_params* params, float* out, float* var_out) {
@@ -919,6 +936,10 @@ extern "C" int ptmi_denoise_guided_reference_frames(const float* colour_sums, co
                                                     const float* frame_nums, const ptmi_guided_params* params, float* out, float* var_out) {
   if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
   return denoise_guided_reference(colour_sums, moments, layers, w, h, n_images, 1.0f, frame_nums, params, out, var_out);
+}
+extern "C" int ptmi_denoise_guided_reference_counts(const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images,
+                                                    const ptmi_guided_params* params, float* out, float* var_out) {
+  return denoise_guided_reference(colour_sums, moments, layers, w, h, n_images, 1.0f, nullptr, params, out, var_out, true);
 }
 
 extern "C" int ptmi_denoise_accumulated_reference(const float* means, const float* plane2, const float* layers, int w, int h, uint32_t n_images, const ptmi_guided_params* params,
@@ -951,6 +972,7 @@ extern "C" void ptmi_default_fuse_params(ptmi_fuse_params* p) {
 // every image u of its window (include/ptmi_fuse_deform.h) unless that neighbour takes the static shortcut; every other pixel is `motion`'s, which may then be nullptr
 // (a static world).  `threads` > 1 share the rows of a view, whose pixels do not depend on one another.
 // weight_out: nullptr, or [n_images][h][w]: den of every fused pixel, 0 where the pixel passes through.
+// counts: nullptr, or every pixel's own divisor (ptmi_fuse_reference_counts): p and the output take the count of (v, p), a neighbour's q the count of (u, q).
 struct ReferenceMotion {  // (accumulate_reference's too)
   const float* motions16;  // [n_images][n_objects][16]
   uint32_t n_objects;
@@ -986,7 +1008,8 @@ static int reference_records(Fill fill, Count count, ptmi::CallTable* L, std::ve
 }
 static int fuse_reference(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num, const float* frame_nums,
                           float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out,
-                          const ReferenceMotion* motion = nullptr, float* weight_out = nullptr, const ReferenceDeform* deform = nullptr, int threads = 1) {
+                          const ReferenceMotion* motion = nullptr, float* weight_out = nullptr, const ReferenceDeform* deform = nullptr, int threads = 1,
+                          const PixelCounts* counts = nullptr) {
   if (!colour || !layers || !views16 || !out || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
   ptmi_fuse_params P;
   if (params) P = *params;
@@ -1033,11 +1056,13 @@ static int fuse_reference(const float* colour, const float* layers, const float*
     if (frame_nums) k.F = frame_nums[v];
     const ptmd_f4* Lv = L + (size_t)v * 3 * npix;
     const uint32_t u0 = v > (uint32_t)P.radius ? v - (uint32_t)P.radius : 0u, u1 = std::min(n_images - 1u, v + (uint32_t)P.radius);
-    auto rows = [&](unsigned t) {
+    auto rows = [&, kv = k](unsigned t) {
     for (int y = (int)(((size_t)h * t) / nt), y1 = (int)(((size_t)h * (t + 1)) / nt); y < y1; y++)
       for (int x = 0; x < w; x++) {
         const uint32_t idx = (uint32_t)y * (uint32_t)w + (uint32_t)x;
         const ptmd_f4 Sp = S[(size_t)v * npix + idx], Ap = Lv[npix + idx];
+        ptmf_consts k = kv;  // (the view's consts, and with counts the pixel's own divisor in them)
+        if (counts) k.F = counts->at(v, npix, idx);
         ptmd_f4 dp, gp;
         float num[3] = {0.0f, 0.0f, 0.0f}, den = 0.0f;
         const int fused = ptmd_prepare(Sp, Lv[idx], Ap, Lv[2 * npix + idx], k.F, k.floor, &dp, &gp) && ptmf_fusable(dp.w, lambertian, n_materials);
@@ -1085,6 +1110,7 @@ static int fuse_reference(const float* colour, const float* layers, const float*
             const ptmd_f4* Lu = L + (size_t)u * 3 * npix;
             ptmf_consts ku = k;
             if (frame_nums) ku.F = frame_nums[u];
+            if (counts) ku.F = counts->at(u, npix, q);
             ptmf_sample(&ku, dp, gu, r, S[(size_t)u * npix + q], Lu[q], Lu[npix + q], Lu[2 * npix + q], num, &den);
           }
         }
@@ -1105,6 +1131,12 @@ extern "C" int ptmi_fuse_reference_frames(const float* colour, const float* laye
                                           float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
   if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
   return fuse_reference(colour, layers, views16, w, h, n_images, 1.0f, frame_nums, fov_degrees, lambertian, n_materials, params, out);
+}
+extern "C" int ptmi_fuse_reference_counts(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* counts,
+                                          float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
+  if (!counts) return PTMI_ERR_INVALID_ARG;
+  const PixelCounts C{counts, 1};
+  return fuse_reference(colour, layers, views16, w, h, n_images, 1.0f, nullptr, fov_degrees, lambertian, n_materials, params, out, nullptr, nullptr, nullptr, 1, &C);
 }
 extern "C" int ptmi_fuse_reference_motion(const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
                                           const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian,
@@ -1160,13 +1192,15 @@ extern "C" void ptmi_default_accumulate_params(ptmi_accumulate_params* p) {
 // A plain loop over views, in order, and pixels through include/ptmi_accumulate.h, the header the kernel of ptmi_accumulate_views compiles.  View v reads planes 1 and 2
 // of view v-1 in `out`, as the kernel does.  Nothing is tiled or reordered; `threads` > 1 share the rows of a view, whose pixels do not depend on one another.
 // frame_nums: nullptr, or every image's own divisor (ptmi_accumulate_reference_frames): own, mean and the pass-through of view v take F_v, the lookup in view v-1 F_{v-1}.
+// pixel_counts (ptmi_accumulate_reference_counts): neither divisor above is read; own, mean and the pass-through of pixel p take M.w of (v, p), the lookup M.w of (v-1, q).
 // motion: nullptr, or the motions and the id images of ptmi_accumulate_reference_motion: between the world point and its projection a pixel whose object has a record
 // that is not the identity moves the point and the normal (include/ptmi_motion.h); every other pixel runs what it ran.
 // deform: nullptr, or the geometry of ptmi_accumulate_reference_deform: a triangle pixel whose indices count is carried from its triangle in image v to the same
 // triangle in image v-1 (include/ptmi_deform.h) unless it takes the static shortcut; every other pixel is `motion`'s, which may then be nullptr (a static world).
 static int accumulate_reference(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
                                 const float* frame_nums, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
-                                const float* history_in, float* out, int threads, const ReferenceMotion* motion = nullptr, const ReferenceDeform* deform = nullptr) {
+                                const float* history_in, float* out, int threads, const ReferenceMotion* motion = nullptr, const ReferenceDeform* deform = nullptr,
+                                bool pixel_counts = false) {
   if (!colour_sums || !moments || !layers || !views16 || !out || w <= 0 || h <= 0 || n_images == 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return PTMI_ERR_INVALID_ARG;
   ptmi_accumulate_params P;
   if (params) P = *params;
@@ -1224,11 +1258,13 @@ static int accumulate_reference(const float* colour_sums, const float* moments, 
     const ptmd_f4* Lu = has_prev ? L + (size_t)(v - 1) * 3 * npix : nullptr;
     const ptmd_f4 *prev1 = has_prev ? plane(1, v - 1) : nullptr, *prev2 = has_prev ? plane(2, v - 1) : nullptr;
     ptmd_f4 *o0 = plane(0, v), *o1 = plane(1, v), *o2 = plane(2, v);
-    auto rows = [&](unsigned t) {
+    auto rows = [&, kv = k, kp = ku](unsigned t) {
       for (int y = (int)(((size_t)h * t) / nt), y1 = (int)(((size_t)h * (t + 1)) / nt); y < y1; y++)
         for (int x = 0; x < w; x++) {
           const uint32_t idx = (uint32_t)y * (uint32_t)w + (uint32_t)x;
           const ptmd_f4 Sp = S[(size_t)v * npix + idx], Ap = Lv[npix + idx];
+          ptmf_consts k = kv, ku = kp;  // (the view's consts, and with pixel_counts the pixel's own divisor in them)
+          if (pixel_counts) k.F = M[(size_t)v * npix + idx].w;
           ptmd_f4 dp, gp, P1, P2;
           const int valid = ptmd_prepare(Sp, Lv[idx], Ap, Lv[2 * npix + idx], k.F, k.floor, &dp, &gp);
           const int accumulates = valid && ptmf_fusable(dp.w, lambertian, n_materials);
@@ -1259,6 +1295,7 @@ static int accumulate_reference(const float* colour_sums, const float* moments, 
             }
             if (moved && ptmf_project(&k, &tab[v - 1], X, &qx, &qy, &r)) {
               const size_t q = (size_t)qy * (size_t)w + (size_t)qx;
+              if (pixel_counts) ku.F = M[(size_t)(v - 1) * npix + q].w;
               if (ptma_weight(&ku, dp, gp, r, S[(size_t)(v - 1) * npix + q], Lu[q], Lu[npix + q], Lu[2 * npix + q], &wgt)) ptma_take(&ka, wgt, prev1[q], prev2[q], &P1, &P2);
             }
           }
@@ -1283,6 +1320,12 @@ extern "C" int ptmi_accumulate_reference_frames(const float* colour_sums, const 
                                                 const ptmi_accumulate_params* params, const float* history_in, float* out, int threads) {
   if (!frame_nums_ok(frame_nums, n_images)) return PTMI_ERR_INVALID_ARG;
   return accumulate_reference(colour_sums, moments, layers, views16, w, h, n_images, 1.0f, frame_nums, fov_degrees, lambertian, n_materials, params, history_in, out, threads);
+}
+extern "C" int ptmi_accumulate_reference_counts(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                                float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params,
+                                                const float* history_in, float* out, int threads) {
+  return accumulate_reference(colour_sums, moments, layers, views16, w, h, n_images, 1.0f, nullptr, fov_degrees, lambertian, n_materials, params, history_in, out, threads, nullptr,
+                              nullptr, true);
 }
 extern "C" int ptmi_accumulate_reference_motion(const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
                                                 const float* frame_nums, const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees,

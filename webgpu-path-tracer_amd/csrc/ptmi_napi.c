@@ -65,6 +65,10 @@ FN(ptmi_denoise_views_frames)
 FN(ptmi_denoise_views_guided_frames)
 FN(ptmi_fuse_views_frames)
 FN(ptmi_accumulate_views_frames)
+FN(ptmi_denoise_views_counts)
+FN(ptmi_denoise_views_guided_counts)
+FN(ptmi_fuse_views_counts)
+FN(ptmi_accumulate_views_counts)
 FN(ptmi_accumulate_views_motion)
 FN(ptmi_accumulate_views_deform)
 FN(ptmi_capture_view_geometry)
@@ -135,7 +139,7 @@ static int load_lib(char* err, size_t errlen) {
   LOAD(ptmi_get_params) LOAD(ptmi_upload) LOAD(ptmi_resize) LOAD(ptmi_clear_framebuffer) LOAD(ptmi_set_shard) LOAD(ptmi_render_frame)
   LOAD(ptmi_render_views_frames) LOAD(ptmi_render_aov_frames) LOAD(ptmi_render_views_until_each)
   LOAD(ptmi_render_view_runs) LOAD(ptmi_view_run_noise) LOAD(ptmi_render_views_until_runs) LOAD(ptmi_read_view_mean) LOAD(ptmi_render_views_runs)
-  LOAD(ptmi_views_device_ptr) LOAD(ptmi_denoise_views_frames) LOAD(ptmi_denoise_views_guided_frames) LOAD(ptmi_fuse_views_frames) LOAD(ptmi_accumulate_views_frames) LOAD(ptmi_accumulate_views_motion) LOAD(ptmi_accumulate_views_deform) LOAD(ptmi_capture_view_geometry) LOAD(ptmi_fuse_views_motion) LOAD(ptmi_fuse_views_deform)
+  LOAD(ptmi_views_device_ptr) LOAD(ptmi_denoise_views_frames) LOAD(ptmi_denoise_views_guided_frames) LOAD(ptmi_fuse_views_frames) LOAD(ptmi_accumulate_views_frames) LOAD(ptmi_denoise_views_counts) LOAD(ptmi_denoise_views_guided_counts) LOAD(ptmi_fuse_views_counts) LOAD(ptmi_accumulate_views_counts) LOAD(ptmi_accumulate_views_motion) LOAD(ptmi_accumulate_views_deform) LOAD(ptmi_capture_view_geometry) LOAD(ptmi_fuse_views_motion) LOAD(ptmi_fuse_views_deform)
   LOAD(ptmi_render) LOAD(ptmi_render_views) LOAD(ptmi_read_view) LOAD(ptmi_resolve_view_rgba8) LOAD(ptmi_release_views) LOAD(ptmi_render_aov) LOAD(ptmi_read_aov) LOAD(ptmi_release_aov) LOAD(ptmi_denoise_views) LOAD(ptmi_default_guided_params) LOAD(ptmi_denoise_views_guided) LOAD(ptmi_read_denoised) LOAD(ptmi_release_denoised) LOAD(ptmi_default_fuse_params) LOAD(ptmi_fuse_views) LOAD(ptmi_read_fused) LOAD(ptmi_release_fused) LOAD(ptmi_default_accumulate_params) LOAD(ptmi_accumulate_views) LOAD(ptmi_read_accumulated) LOAD(ptmi_release_accumulated) LOAD(ptmi_denoise_views_accumulated) LOAD(ptmi_set_view_moments) LOAD(ptmi_read_moments) LOAD(ptmi_release_moments) LOAD(ptmi_default_noise_params) LOAD(ptmi_view_noise_stats) LOAD(ptmi_render_views_until) LOAD(ptmi_synchronize) LOAD(ptmi_read_framebuffer) LOAD(ptmi_write_framebuffer) LOAD(ptmi_resolve_rgba8)
   LOAD(ptmi_set_counters) LOAD(ptmi_set_timing) LOAD(ptmi_get_stats) LOAD(ptmi_reset_stats) LOAD(ptmi_build_bvh) LOAD(ptmi_build_bvh_sah) LOAD(ptmi_check_bvh_boxes) LOAD(ptmi_build_bvh_device) LOAD(ptmi_build_scene_bvh) LOAD(ptmi_build_scene_bvh_sah) LOAD(ptmi_refit_scene_bvh)
   LOAD(ptmi_obj_parse) LOAD(ptmi_free) LOAD(ptmi_device_count) LOAD(ptmi_reduce_info)
@@ -616,17 +620,19 @@ static int frame_nums_arg(napi_env env, ptmi_ctx* c, napi_value v, const char* w
   return 0;
 }
 
+/* (frames: 0 one frameNum, 1 the *Frames call, 2 the *Counts call, which has no divisor argument: the others move up by one) */
 static napi_value denoise_views_common(napi_env env, napi_callback_info info, int frames) {
   napi_value a[5];
-  if (get_args(env, info, 5, a)) return NULL;
+  if (get_args(env, info, frames == 2 ? 4 : 5, a)) return NULL;
+  if (frames == 2) a[4] = a[3], a[3] = a[2], a[2] = a[1];
   ptmi_ctx* c = ctx_of(env, a[0]);
   if (!c) return NULL;
   double frame_num = 1.0;
   const float* frame_nums = NULL;
   uint32_t first, n_views;
-  if (frames) {
+  if (frames == 1) {
     if (frame_nums_arg(env, c, a[1], "denoiseViewsFrames(frameNums)", &frame_nums)) return NULL;
-  } else {
+  } else if (frames == 0) {
     CHECK_NAPI(napi_get_value_double(env, a[1], &frame_num));
   }
   CHECK_NAPI(napi_get_value_uint32(env, a[2], &first));
@@ -639,10 +645,14 @@ static napi_value denoise_views_common(napi_env env, napi_callback_info info, in
                                        {"sigmaColour", 0, offsetof(ptmi_denoise_params, sigma_colour)},
                                        {"albedoFloor", 0, offsetof(ptmi_denoise_params, albedo_floor)}};
   CHECK_PARAMS(a[4], fields, &P, "denoiseViews")
-  int st = frames ? p_ptmi_denoise_views_frames(c, &P, frame_nums, first, n_views) : p_ptmi_denoise_views(c, &P, (float)frame_num, first, n_views);
-  if (st) return throw_status(env, c, st, frames ? "ptmi_denoise_views_frames" : "ptmi_denoise_views");
+  int st = frames == 2 ? p_ptmi_denoise_views_counts(c, &P, first, n_views)
+           : frames ? p_ptmi_denoise_views_frames(c, &P, frame_nums, first, n_views)
+                    : p_ptmi_denoise_views(c, &P, (float)frame_num, first, n_views);
+  if (st) return throw_status(env, c, st, frames == 2 ? "ptmi_denoise_views_counts" : frames ? "ptmi_denoise_views_frames" : "ptmi_denoise_views");
   return NULL;
 }
+/* denoiseViewsCounts(ctx, firstView, nViews, params | null): ptmi_denoise_views_counts — every pixel's own frame count, M.w of the moment stack */
+static napi_value js_denoise_views_counts(napi_env env, napi_callback_info info) { return denoise_views_common(env, info, 2); }
 static napi_value js_denoise_views(napi_env env, napi_callback_info info) { return denoise_views_common(env, info, 0); }
 /* denoiseViewsFrames(ctx, Float32Array frameNums, firstView, nViews, params | null): ptmi_denoise_views_frames — one frame count per view of the stack */
 static napi_value js_denoise_views_frames(napi_env env, napi_callback_info info) { return denoise_views_common(env, info, 1); }
@@ -651,15 +661,16 @@ static napi_value js_denoise_views_frames(napi_env env, napi_callback_info info)
  * minFrames, varEps}, every field optional (ptmi_default_guided_params fills the rest) */
 static napi_value denoise_views_guided_common(napi_env env, napi_callback_info info, int frames) {
   napi_value a[5];
-  if (get_args(env, info, 5, a)) return NULL;
+  if (get_args(env, info, frames == 2 ? 4 : 5, a)) return NULL;
+  if (frames == 2) a[4] = a[3], a[3] = a[2], a[2] = a[1];
   ptmi_ctx* c = ctx_of(env, a[0]);
   if (!c) return NULL;
   double frame_num = 1.0;
   const float* frame_nums = NULL;
   uint32_t first, n_views;
-  if (frames) {
+  if (frames == 1) {
     if (frame_nums_arg(env, c, a[1], "denoiseViewsGuidedFrames(frameNums)", &frame_nums)) return NULL;
-  } else {
+  } else if (frames == 0) {
     CHECK_NAPI(napi_get_value_double(env, a[1], &frame_num));
   }
   CHECK_NAPI(napi_get_value_uint32(env, a[2], &first));
@@ -674,10 +685,14 @@ static napi_value denoise_views_guided_common(napi_env env, napi_callback_info i
                                        {"albedoFloor", 0, offsetof(ptmi_guided_params, albedo_floor)},
                                        {"varEps", 0, offsetof(ptmi_guided_params, var_eps)}};
   CHECK_PARAMS(a[4], fields, &P, "denoiseViewsGuided")
-  int st = frames ? p_ptmi_denoise_views_guided_frames(c, &P, frame_nums, first, n_views) : p_ptmi_denoise_views_guided(c, &P, (float)frame_num, first, n_views);
-  if (st) return throw_status(env, c, st, frames ? "ptmi_denoise_views_guided_frames" : "ptmi_denoise_views_guided");
+  int st = frames == 2 ? p_ptmi_denoise_views_guided_counts(c, &P, first, n_views)
+           : frames ? p_ptmi_denoise_views_guided_frames(c, &P, frame_nums, first, n_views)
+                    : p_ptmi_denoise_views_guided(c, &P, (float)frame_num, first, n_views);
+  if (st) return throw_status(env, c, st, frames == 2 ? "ptmi_denoise_views_guided_counts" : frames ? "ptmi_denoise_views_guided_frames" : "ptmi_denoise_views_guided");
   return NULL;
 }
+/* denoiseViewsGuidedCounts(ctx, firstView, nViews, params | null): ptmi_denoise_views_guided_counts */
+static napi_value js_denoise_views_guided_counts(napi_env env, napi_callback_info info) { return denoise_views_guided_common(env, info, 2); }
 static napi_value js_denoise_views_guided(napi_env env, napi_callback_info info) { return denoise_views_guided_common(env, info, 0); }
 /* denoiseViewsGuidedFrames(ctx, Float32Array frameNums, firstView, nViews, params | null): ptmi_denoise_views_guided_frames */
 static napi_value js_denoise_views_guided_frames(napi_env env, napi_callback_info info) { return denoise_views_guided_common(env, info, 1); }
@@ -686,8 +701,9 @@ static napi_value js_denoise_views_guided_frames(napi_env env, napi_callback_inf
  * {radius, sigmaNormal, sigmaDepth, albedoFloor}, every field optional (ptmi_default_fuse_params fills the rest) */
 static napi_value fuse_views_common(napi_env env, napi_callback_info info, int frames) {
   napi_value a[7];
-  if (get_args(env, info, frames ? 6 : 7, a)) return NULL;
-  if (frames) a[6] = a[5], a[5] = a[4], a[4] = a[3];  /* (no `source`: the view stack) */
+  if (get_args(env, info, frames == 2 ? 5 : frames ? 6 : 7, a)) return NULL;
+  if (frames == 1) a[6] = a[5], a[5] = a[4], a[4] = a[3];  /* (no `source`: the view stack) */
+  if (frames == 2) a[6] = a[4], a[5] = a[3], a[4] = a[2]; /* (neither a divisor nor `source`) */
   ptmi_ctx* c = ctx_of(env, a[0]);
   if (!c) return NULL;
   void* data;
@@ -701,9 +717,9 @@ static napi_value fuse_views_common(napi_env env, napi_callback_info info, int f
   const float* frame_nums = NULL;
   int32_t source = 0;
   uint32_t first, n_views;
-  if (frames) {
+  if (frames == 1) {
     if (frame_nums_arg(env, c, a[2], "fuseViewsFrames(frameNums)", &frame_nums)) return NULL;
-  } else {
+  } else if (frames == 0) {
     CHECK_NAPI(napi_get_value_double(env, a[2], &frame_num));
     CHECK_NAPI(napi_get_value_int32(env, a[3], &source));
   }
@@ -720,10 +736,14 @@ static napi_value fuse_views_common(napi_env env, napi_callback_info info, int f
                                        {"sigmaDepth", 0, offsetof(ptmi_fuse_params, sigma_depth)},
                                        {"albedoFloor", 0, offsetof(ptmi_fuse_params, albedo_floor)}};
   CHECK_PARAMS(a[6], fields, &P, "fuseViews")
-  int st = frames ? p_ptmi_fuse_views_frames(c, &P, (const float*)data, frame_nums, first, n_views) : p_ptmi_fuse_views(c, &P, (const float*)data, (float)frame_num, source, first, n_views);
-  if (st) return throw_status(env, c, st, frames ? "ptmi_fuse_views_frames" : "ptmi_fuse_views");
+  int st = frames == 2 ? p_ptmi_fuse_views_counts(c, &P, (const float*)data, first, n_views)
+           : frames ? p_ptmi_fuse_views_frames(c, &P, (const float*)data, frame_nums, first, n_views)
+                    : p_ptmi_fuse_views(c, &P, (const float*)data, (float)frame_num, source, first, n_views);
+  if (st) return throw_status(env, c, st, frames == 2 ? "ptmi_fuse_views_counts" : frames ? "ptmi_fuse_views_frames" : "ptmi_fuse_views");
   return NULL;
 }
+/* fuseViewsCounts(ctx, views, firstView, nViews, params | null): ptmi_fuse_views_counts — the view stack as source, every pixel's own frame count */
+static napi_value js_fuse_views_counts(napi_env env, napi_callback_info info) { return fuse_views_common(env, info, 2); }
 static napi_value js_fuse_views(napi_env env, napi_callback_info info) { return fuse_views_common(env, info, 0); }
 /* fuseViewsFrames(ctx, views, Float32Array frameNums, firstView, nViews, params | null): ptmi_fuse_views_frames — the view stack as source */
 static napi_value js_fuse_views_frames(napi_env env, napi_callback_info info) { return fuse_views_common(env, info, 1); }
@@ -780,7 +800,8 @@ static napi_value js_fuse_views_deform(napi_env env, napi_callback_info info) { 
  * {maxHistory, minFrames, sigmaNormal, sigmaDepth, albedoFloor}, every field optional (ptmi_default_accumulate_params fills the rest) */
 static napi_value accumulate_views_common(napi_env env, napi_callback_info info, int frames) {
   napi_value a[7];
-  if (get_args(env, info, 7, a)) return NULL;
+  if (get_args(env, info, frames == 2 ? 6 : 7, a)) return NULL;
+  if (frames == 2) a[6] = a[5], a[5] = a[4], a[4] = a[3], a[3] = a[2];
   ptmi_ctx* c = ctx_of(env, a[0]);
   if (!c) return NULL;
   void* data;
@@ -793,9 +814,9 @@ static napi_value accumulate_views_common(napi_env env, napi_callback_info info,
   double frame_num = 1.0;
   const float* frame_nums = NULL;
   uint32_t first, n_views;
-  if (frames) {
+  if (frames == 1) {
     if (frame_nums_arg(env, c, a[2], "accumulateViewsFrames(frameNums)", &frame_nums)) return NULL;
-  } else {
+  } else if (frames == 0) {
     CHECK_NAPI(napi_get_value_double(env, a[2], &frame_num));
   }
   CHECK_NAPI(napi_get_value_uint32(env, a[3], &first));
@@ -815,11 +836,14 @@ static napi_value accumulate_views_common(napi_env env, napi_callback_info info,
                                        {"sigmaDepth", 0, offsetof(ptmi_accumulate_params, sigma_depth)},
                                        {"albedoFloor", 0, offsetof(ptmi_accumulate_params, albedo_floor)}};
   CHECK_PARAMS(a[6], fields, &P, "accumulateViews")
-  int st = frames ? p_ptmi_accumulate_views_frames(c, &P, (const float*)data, frame_nums, first, n_views, resume ? 1 : 0)
-                  : p_ptmi_accumulate_views(c, &P, (const float*)data, (float)frame_num, first, n_views, resume ? 1 : 0);
-  if (st) return throw_status(env, c, st, frames ? "ptmi_accumulate_views_frames" : "ptmi_accumulate_views");
+  int st = frames == 2 ? p_ptmi_accumulate_views_counts(c, &P, (const float*)data, first, n_views, resume ? 1 : 0)
+           : frames ? p_ptmi_accumulate_views_frames(c, &P, (const float*)data, frame_nums, first, n_views, resume ? 1 : 0)
+                    : p_ptmi_accumulate_views(c, &P, (const float*)data, (float)frame_num, first, n_views, resume ? 1 : 0);
+  if (st) return throw_status(env, c, st, frames == 2 ? "ptmi_accumulate_views_counts" : frames ? "ptmi_accumulate_views_frames" : "ptmi_accumulate_views");
   return NULL;
 }
+/* accumulateViewsCounts(ctx, views, firstView, nViews, resume, params | null): ptmi_accumulate_views_counts */
+static napi_value js_accumulate_views_counts(napi_env env, napi_callback_info info) { return accumulate_views_common(env, info, 2); }
 static napi_value js_accumulate_views(napi_env env, napi_callback_info info) { return accumulate_views_common(env, info, 0); }
 /* accumulateViewsFrames(ctx, views, Float32Array frameNums, firstView, nViews, resume, params | null): ptmi_accumulate_views_frames */
 static napi_value js_accumulate_views_frames(napi_env env, napi_callback_info info) { return accumulate_views_common(env, info, 1); }
@@ -1598,6 +1622,8 @@ static napi_value init(napi_env env, napi_value exports) {
   } fns[] = {
       {"version", js_version}, {"create", js_create}, {"destroy", js_destroy}, {"defaultParams", js_default_params}, {"setParams", js_set_params},
       {"upload", js_upload}, {"resize", js_resize}, {"clear", js_clear}, {"setShard", js_set_shard}, {"renderFrame", js_render_frame},
+      {"denoiseViewsCounts", js_denoise_views_counts}, {"denoiseViewsGuidedCounts", js_denoise_views_guided_counts}, {"fuseViewsCounts", js_fuse_views_counts},
+      {"accumulateViewsCounts", js_accumulate_views_counts},
       {"renderViewsFrames", js_render_views_frames}, {"renderAovFrames", js_render_aov_frames}, {"renderViewsUntilEach", js_render_views_until_each},
       {"renderViewRuns", js_render_view_runs}, {"viewRunNoise", js_view_run_noise}, {"renderViewsUntilRuns", js_render_views_until_runs}, {"readViewMean", js_read_view_mean}, {"renderViewsRuns", js_render_views_runs},
       {"render", js_render}, {"renderViews", js_render_views}, {"readView", js_read_view}, {"resolveViewRGBA8", js_resolve_view}, {"releaseViews", js_release_views}, {"renderAov", js_render_aov}, {"readAov", js_read_aov}, {"releaseAov", js_release_aov}, {"denoiseViews", js_denoise_views}, {"denoiseViewsGuided", js_denoise_views_guided}, {"readDenoised", js_read_denoised}, {"releaseDenoised", js_release_denoised}, {"fuseViews", js_fuse_views}, {"readFused", js_read_fused}, {"releaseFused", js_release_fused}, {"accumulateViews", js_accumulate_views}, {"readAccumulated", js_read_accumulated}, {"releaseAccumulated", js_release_accumulated}, {"denoiseViewsAccumulated", js_denoise_views_accumulated}, {"denoiseViewsFrames", js_denoise_views_frames}, {"denoiseViewsGuidedFrames", js_denoise_views_guided_frames}, {"fuseViewsFrames", js_fuse_views_frames}, {"accumulateViewsFrames", js_accumulate_views_frames}, {"accumulateViewsMotion", js_accumulate_views_motion}, {"accumulateViewsDeform", js_accumulate_views_deform}, {"captureViewGeometry", js_capture_view_geometry}, {"fuseViewsMotion", js_fuse_views_motion}, {"fuseViewsDeform", js_fuse_views_deform}, {"setViewMoments", js_set_view_moments}, {"readMoments", js_read_moments}, {"releaseMoments", js_release_moments}, {"viewNoise", js_view_noise}, {"renderViewsUntil", js_render_views_until}, {"synchronize", js_synchronize}, {"prepare", js_prepare}, {"buildSceneBVH", js_build_scene_bvh}, {"buildSceneBVHSAH", js_build_scene_bvh_sah}, {"refitSceneBVH", js_refit_scene_bvh}, {"readFramebuffer", js_read_fb}, {"writeFramebuffer", js_write_fb},

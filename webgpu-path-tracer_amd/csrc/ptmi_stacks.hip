@@ -51,8 +51,10 @@ struct AtrousGuide {
 // guided filter also one k_guided_variance, per level one k_guided_blur (with a luminance term only: the blur feeds nothing else), and its last level writes `var_out`.
 // frames: nullptr, or the device table of the views' own divisors, one f32 per view, at the call's first view (F is then not read): the prepare pass and the last level
 // are then the *_frames entries, which index it by the batch's first view + the view of the batch.
+// counts (frames is then nullptr): nullptr, or the device address of the count of pixel 0 of the call's first view, pixel after pixel cstride f32 apart (4: .w of a
+// moment stack, 1: a count image): the prepare pass and the last level are then the *_counts entries.
 static int atrous_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, uint32_t n, int W, int H, float F, const ptmi_denoise_params& P, const AtrousGuide* G,
-                          const float* frames = nullptr) {
+                          const float* frames = nullptr, const float* counts = nullptr, uint32_t cstride = 0) {
   const size_t npix = (size_t)W * (size_t)H;
   const uint32_t B = atrous_batch_views(npix, n, G ? kGuidedScratchBytes : kDenoiseScratchBytes);
   float4* d[2] = {c->d_denoise_scratch.as<float4>(), c->d_denoise_scratch.as<float4>() + (size_t)B * npix};
@@ -67,8 +69,10 @@ static int atrous_enqueue(ptmi_ctx* c, const float4* colour, const float4* layer
     const float4* col = colour + (size_t)v0 * npix;
     const float4* lay = layers + (size_t)v0 * 3 * npix;
     const size_t items = (size_t)nv * npix;
+    const float* cnt = counts ? counts + (size_t)v0 * npix * cstride : nullptr;
     const unsigned pgrid = (unsigned)std::min<size_t>((items + kBlock - 1) / kBlock, (size_t)c->num_cus * 32);
-    if (frames) hipLaunchKernelGGL(k_denoise_prepare_frames, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, frames + v0, P.albedo_floor, d[0], g);
+    if (cnt) hipLaunchKernelGGL(k_denoise_prepare_counts, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, cnt, cstride, P.albedo_floor, d[0], g);
+    else if (frames) hipLaunchKernelGGL(k_denoise_prepare_frames, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, frames + v0, P.albedo_floor, d[0], g);
     else hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, c->stream, col, lay, items, npix, F, P.albedo_floor, d[0], g);
     HIP_TRY(c, hipGetLastError());
     const dim3 tgrid((unsigned)((W + kDenoiseTX - 1) / kDenoiseTX), (unsigned)((H + kGuidedTY - 1) / kGuidedTY), nv);
@@ -92,11 +96,15 @@ static int atrous_enqueue(ptmi_ctx* c, const float4* colour, const float4* layer
           HIP_TRY(c, hipGetLastError());
         }
         float* vout = !last ? v[(l + 1) & 1] : G->var_out ? G->var_out + (size_t)v0 * npix : nullptr;
-        if (last && frames)
+        if (last && cnt)
+          hipLaunchKernelGGL(k_guided_level_counts, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, dout, vout, col, lay, W, H, step, ty, k, G->kg, cnt, cstride);
+        else if (last && frames)
           hipLaunchKernelGGL(k_guided_level_frames, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, dout, vout, col, lay, W, H, step, ty, k, G->kg, frames + v0);
         else
           hipLaunchKernelGGL(last ? k_guided_level<true> : k_guided_level<false>, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, v[l & 1], vg, dout, vout, col, lay, W, H, step, ty, k,
                              G->kg, F);
+      } else if (last && cnt) {
+        hipLaunchKernelGGL(k_denoise_level_counts, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, dout, col, lay, W, H, step, ty, k, cnt, cstride);
       } else if (last && frames) {
         hipLaunchKernelGGL(k_denoise_level_frames, grid, dim3(kBlock), lds, c->stream, d[l & 1], g, dout, col, lay, W, H, step, ty, k, frames + v0);
       } else {
@@ -132,14 +140,20 @@ static int check_view_range(ptmi_ctx* c, const char* who, uint32_t first_view, u
 }
 
 // The divisor of a call's colour sums: one frame_num for every view, or (each: the *_frames, *_motion and *_deform entries) the views' own, frame_nums, one f32 per view
-// of the stack or per image.  frame_num is then 1: what frame_num's check passes and no kernel reads.
+// of the stack or per image, or (pixel: the *_counts entries) every pixel's own — M.w of the moment stack or of the call's moments, or (the plain and fuse *_images_counts
+// forms, which take no moments) the count image `counts`, [n_images][h][w] f32.  frame_num is then 1: what frame_num's check passes and no kernel reads.
 struct FrameDivisor {
   float frame_num;
   const float* frame_nums;
   bool each;
+  bool pixel = false;
+  const float* counts = nullptr;
   static FrameDivisor of(float frame_num) { return {frame_num, nullptr, false}; }
   static FrameDivisor per_view(const float* frame_nums) { return {1.0f, frame_nums, true}; }
+  static FrameDivisor per_pixel(const float* counts = nullptr) { return {1.0f, nullptr, false, true, counts}; }
 };
+// Where the kernels of a *_counts call find their counts: .w of float4 image `moments`, 4 f32 from pixel to pixel
+static const float* counts_in_moments(const float4* moments) { return reinterpret_cast<const float*>(moments) + 3; }
 
 // A per-view divisor: entries [lo, hi) of frame_nums are the ones the call reads, and each has to be a divisor — finite and > 0; the others may hold anything.  (With
 // lo = hi = 0 the null pointer alone is refused: what a call asks before it knows its range.)
@@ -177,10 +191,20 @@ static int check_source_stacks(ptmi_ctx* c, const char* who, bool need_denoised,
   return check_view_range(c, who, first_view, n_views, n);
 }
 
+// What the calls that read the moment stack ask of it: that it exists (moments on, not released) and has the view stack's size.  The moment stack first, then the view
+// stack: the order decides which error a caller sees.
+static int check_moment_stack(ptmi_ctx* c, const char* who) {
+  if (int r = check_stack(c, STACK_MOMENTS, who, 0)) return r;
+  if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
+  if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
+    return fail(c, PTMI_ERR_STATE, std::string(who) + ": the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
+  return PTMI_OK;
+}
+
 // Either filter from the context's stacks into its denoised stack, the arguments checked.  The stack and the scratch, everything that can fail for want of memory, come
 // before anything is enqueued.  G: as atrous_enqueue's, its `moments` (or, with `accumulated`, its `given`) filled in here.  accumulated: the colour is plane 0 of the
 // accumulated stack, not the view stack.
-// F (checked): the views' own frame counts go up through c->denoise_tab.
+// F (checked): the views' own frame counts go up through c->denoise_tab; the pixels' own (F.pixel) are read where they lie, in .w of the moment stack.
 static int atrous_views(ptmi_ctx* c, const ptmi_denoise_params& P, AtrousGuide* G, const FrameDivisor& F, uint32_t first_view, uint32_t n_views, bool accumulated = false) {
   const float* frame_nums = F.frame_nums;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -202,18 +226,24 @@ static int atrous_views(ptmi_ctx* c, const ptmi_denoise_params& P, AtrousGuide* 
   else if (G) G->moments = c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix;
   return atrous_enqueue(c, c->stacks[source].buf.as<float4>() + (size_t)first_view * npix, c->stacks[STACK_FEATURES].buf.as<float4>() + (size_t)first_view * 3 * npix,
                         c->stacks[STACK_DENOISED].buf.as<float4>() + (size_t)first_view * npix, n_views, c->W, c->H, F.frame_num, P, G,
-                        frame_nums ? c->denoise_tab.dev.as<float>() + first_view : nullptr);
+                        frame_nums ? c->denoise_tab.dev.as<float>() + first_view : nullptr,
+                        F.pixel ? counts_in_moments(c->stacks[STACK_MOMENTS].buf.as<float4>() + (size_t)first_view * npix) : nullptr, 4);
 }
 
-// ptmi_denoise_views and ptmi_denoise_views_frames
+// ptmi_denoise_views, ptmi_denoise_views_frames and ptmi_denoise_views_counts
 static int denoise_views(ptmi_ctx* c, const char* who, const ptmi_denoise_params* params, const FrameDivisor& F, uint32_t first_view, uint32_t n_views) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   ptmi_denoise_params P;
   if (int r = denoise_check_args(c, who, params, F.frame_num, &P)) return r;
   if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
+  if (F.pixel)
+    if (int r = check_moment_stack(c, who)) return r;
   if (int r = check_source_stacks(c, who, false, first_view, n_views)) return r;
   if (int r = check_frame_nums(c, who, F, first_view, first_view + n_views)) return r;
   return atrous_views(c, P, nullptr, F, first_view, n_views);
+}
+int ptmi_denoise_views_counts(ptmi_ctx* c, const ptmi_denoise_params* params, uint32_t first_view, uint32_t n_views) {
+  return denoise_views(c, "ptmi_denoise_views_counts", params, FrameDivisor::per_pixel(), first_view, n_views);
 }
 int ptmi_denoise_views(ptmi_ctx* c, const ptmi_denoise_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
   return denoise_views(c, "ptmi_denoise_views", params, FrameDivisor::of(frame_num), first_view, n_views);
@@ -257,27 +287,29 @@ static int on_host_images(ptmi_ctx* c, const char* who, const float* colour, con
   return r;
 }
 
-// ptmi_denoise_images and ptmi_denoise_images_frames (F's frame_nums: one per image)
+// ptmi_denoise_images, ptmi_denoise_images_frames (F's frame_nums: one per image) and ptmi_denoise_images_counts (F's counts: one per pixel)
 static int denoise_images(ptmi_ctx* c, const char* who, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const FrameDivisor& F,
                           const ptmi_denoise_params* params, float* out) {
-  if (!c || !colour_sums || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (!c || !colour_sums || !layers || !out || (F.pixel && !F.counts)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   ptmi_denoise_params P;
   if (int r = denoise_check_args(c, who, params, F.frame_num, &P)) return r;
   if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
   if (int r = check_image_size(c, who, w, h, n_images)) return r;
   if (int r = check_frame_nums(c, who, F, 0, n_images)) return r;
   const size_t npix = (size_t)w * (size_t)h;
-  DBuf dfr;  // (the frame counts: this call's own, had before anything is enqueued)
-  if (F.each) {
+  DBuf dfr, dcnt;  // (the frame counts, per image or per pixel: this call's own, had before anything is enqueued)
+  if (F.each || F.pixel) {
     HIP_TRY(c, hipSetDevice(c->device));
     (void)hipGetLastError();
-    HIP_TRY(c, dfr.ensure((size_t)n_images * 4));
+    if (F.each) HIP_TRY(c, dfr.ensure((size_t)n_images * 4));
+    if (F.pixel) HIP_TRY(c, dcnt.ensure(npix * 4 * n_images));
   }
   return on_host_images(c, who, colour_sums, layers, npix, n_images, out, c->d_denoise_scratch, atrous_scratch_bytes(npix, n_images, kDenoiseScratchBytes),
                         [&](const float4* col, const float4* lay, float4* res) -> int {
                           if (F.each)
                             if (int e = send_frame_nums(c, dfr, F.frame_nums, n_images)) return e;
-                          return atrous_enqueue(c, col, lay, res, n_images, w, h, F.frame_num, P, nullptr, dfr.as<float>());
+                          if (F.pixel) HIP_TRY(c, hipMemcpyAsync(dcnt.p, F.counts, npix * 4 * n_images, hipMemcpyHostToDevice, c->stream));
+                          return atrous_enqueue(c, col, lay, res, n_images, w, h, F.frame_num, P, nullptr, dfr.as<float>(), dcnt.as<float>(), 1);
                         });
 }
 int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, float frame_num, const ptmi_denoise_params* params, float* out) {
@@ -286,6 +318,10 @@ int ptmi_denoise_images(ptmi_ctx* c, const float* colour_sums, const float* laye
 int ptmi_denoise_images_frames(ptmi_ctx* c, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const float* frame_nums,
                                const ptmi_denoise_params* params, float* out) {
   return denoise_images(c, "ptmi_denoise_images_frames", colour_sums, layers, w, h, n_images, FrameDivisor::per_view(frame_nums), params, out);
+}
+int ptmi_denoise_images_counts(ptmi_ctx* c, const float* colour_sums, const float* layers, int w, int h, uint32_t n_images, const float* counts, const ptmi_denoise_params* params,
+                               float* out) {
+  return denoise_images(c, "ptmi_denoise_images_counts", colour_sums, layers, w, h, n_images, FrameDivisor::per_pixel(counts), params, out);
 }
 
 // The guided filter's params as the launch plan takes them: the levels' part, with no colour term (P), and the rest (G, whose arrays the caller fills in)
@@ -300,20 +336,20 @@ static int guided_check_args(ptmi_ctx* c, const char* who, const ptmi_guided_par
                           ok ? nullptr : "levels in 1..6, sigma_normal, sigma_depth and albedo_floor > 0, sigma_luma >= 0, min_frames >= 2, var_eps a normal f32 > 0, all finite", true, frame_num);
 }
 
-// ptmi_denoise_views_guided and ptmi_denoise_views_guided_frames
+// ptmi_denoise_views_guided, ptmi_denoise_views_guided_frames and ptmi_denoise_views_guided_counts
 static int denoise_views_guided(ptmi_ctx* c, const char* who, const ptmi_guided_params* params, const FrameDivisor& F, uint32_t first_view, uint32_t n_views) {
   if (!c) return PTMI_ERR_INVALID_ARG;
   ptmi_denoise_params P;
   AtrousGuide G;
   if (int r = guided_check_args(c, who, params, F.frame_num, &P, &G)) return r;
   if (int r = check_frame_nums(c, who, F, 0, 0)) return r;
-  if (int r = check_stack(c, STACK_MOMENTS, who, 0)) return r;  // (the moment stack first, then what ptmi_denoise_views asks: the order decides which error a caller sees)
-  if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
-  if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
-    return fail(c, PTMI_ERR_STATE, std::string(who) + ": the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
+  if (int r = check_moment_stack(c, who)) return r;  // (then what ptmi_denoise_views asks)
   if (int r = check_source_stacks(c, who, false, first_view, n_views)) return r;
   if (int r = check_frame_nums(c, who, F, first_view, first_view + n_views)) return r;
   return atrous_views(c, P, &G, F, first_view, n_views);
+}
+int ptmi_denoise_views_guided_counts(ptmi_ctx* c, const ptmi_guided_params* params, uint32_t first_view, uint32_t n_views) {
+  return denoise_views_guided(c, "ptmi_denoise_views_guided_counts", params, FrameDivisor::per_pixel(), first_view, n_views);
 }
 int ptmi_denoise_views_guided(ptmi_ctx* c, const ptmi_guided_params* params, float frame_num, uint32_t first_view, uint32_t n_views) {
   return denoise_views_guided(c, "ptmi_denoise_views_guided", params, FrameDivisor::of(frame_num), first_view, n_views);
@@ -322,7 +358,7 @@ int ptmi_denoise_views_guided_frames(ptmi_ctx* c, const ptmi_guided_params* para
   return denoise_views_guided(c, "ptmi_denoise_views_guided_frames", params, FrameDivisor::per_view(frame_nums), first_view, n_views);
 }
 
-// ptmi_denoise_images_guided and ptmi_denoise_images_guided_frames (F's frame_nums: one per image)
+// ptmi_denoise_images_guided, ptmi_denoise_images_guided_frames (F's frame_nums: one per image) and ptmi_denoise_images_guided_counts (the counts: the moments' w)
 static int denoise_images_guided(ptmi_ctx* c, const char* who, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images,
                                  const FrameDivisor& F, const ptmi_guided_params* params, float* out, float* var_out) {
   if (!c || !colour_sums || !moments || !layers || !out) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
@@ -345,7 +381,8 @@ static int denoise_images_guided(ptmi_ctx* c, const char* who, const float* colo
                           HIP_TRY(c, hipMemcpyAsync(mom.p, moments, bytes, hipMemcpyHostToDevice, c->stream));
                           if (F.each)
                             if (int e = send_frame_nums(c, dfr, F.frame_nums, n_images)) return e;
-                          if (int e = atrous_enqueue(c, col, lay, res, n_images, w, h, F.frame_num, P, &G, dfr.as<float>())) return e;
+                          if (int e = atrous_enqueue(c, col, lay, res, n_images, w, h, F.frame_num, P, &G, dfr.as<float>(), F.pixel ? counts_in_moments(mom.as<float4>()) : nullptr, 4))
+                            return e;
                           if (var_out) HIP_TRY(c, hipMemcpyAsync(var_out, var.p, var_bytes, hipMemcpyDeviceToHost, c->stream));
                           return PTMI_OK;
                         });
@@ -357,6 +394,10 @@ int ptmi_denoise_images_guided(ptmi_ctx* c, const float* colour_sums, const floa
 int ptmi_denoise_images_guided_frames(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images, const float* frame_nums,
                                       const ptmi_guided_params* params, float* out, float* var_out) {
   return denoise_images_guided(c, "ptmi_denoise_images_guided_frames", colour_sums, moments, layers, w, h, n_images, FrameDivisor::per_view(frame_nums), params, out, var_out);
+}
+int ptmi_denoise_images_guided_counts(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, int w, int h, uint32_t n_images,
+                                      const ptmi_guided_params* params, float* out, float* var_out) {
+  return denoise_images_guided(c, "ptmi_denoise_images_guided_counts", colour_sums, moments, layers, w, h, n_images, FrameDivisor::per_pixel(), params, out, var_out);
 }
 
 // ---- the fused stack (ptmi_fuse_views, ptmi_fuse_images) ----
@@ -447,8 +488,10 @@ static uint32_t first_view_with_history(uint32_t first, bool resume) { return re
 // t.frames: the views' own divisors on the device, one f32 per view of the stack (k.F is then not read): k_fuse_frames.
 // motion (with t.frames): nullptr, or k_fuse_motion's operands, records = the composed records of view `first` (call_table_fill_composed_motion: their order).
 // deform (with t.frames and motion, whose n_objects may be 0: a static world beside the triangles): k_fuse_deform's operands, moved = the masks of view `first`.
+// counts (without any of those): nullptr, or the device address of the count of pixel 0 of view 0 OF THE STACK, pixel after pixel cstride f32 apart: k_fuse_counts.
 static int fuse_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers, float4* out, const TablePtrs& t, uint32_t n_materials, int W, int H, uint32_t n_stack,
-                        uint32_t first, uint32_t n, const ptmf_consts& k, const MotionArgs* motion = nullptr, const FuseDeformArgs* deform = nullptr) {
+                        uint32_t first, uint32_t n, const ptmf_consts& k, const MotionArgs* motion = nullptr, const FuseDeformArgs* deform = nullptr, const float* counts = nullptr,
+                        uint32_t cstride = 0) {
   const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
   const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
   for (uint32_t v0 = 0; v0 < n; v0 += 65535u) {
@@ -465,6 +508,8 @@ static int fuse_enqueue(ptmi_ctx* c, const float4* colour, const float4* layers,
       MotionArgs mo = *motion;
       mo.records += (size_t)v0 * (2u * (uint32_t)k.radius + 1u) * mo.n_objects * 6;
       shared([&](auto... a) { hipLaunchKernelGGL(k_fuse_motion, grid, dim3(kBlock), 0, c->stream, a..., t.frames, mo); });
+    } else if (counts) {
+      shared([&](auto... a) { hipLaunchKernelGGL(k_fuse_counts, grid, dim3(kBlock), 0, c->stream, a..., counts, cstride); });
     } else if (t.frames) {
       shared([&](auto... a) { hipLaunchKernelGGL(k_fuse_frames, grid, dim3(kBlock), 0, c->stream, a..., t.frames); });
     } else {
@@ -583,7 +628,7 @@ static int check_geometry_stack(ptmi_ctx* c, const char* who, uint32_t n_stack, 
   return PTMI_OK;
 }
 
-// ptmi_fuse_views, ptmi_fuse_views_frames (the view stack as source), ptmi_fuse_views_motion (motion: its motions16 [n_views of the stack][n_objects][16]) and
+// ptmi_fuse_views, ptmi_fuse_views_frames, ptmi_fuse_views_counts (the view stack as source), ptmi_fuse_views_motion (motion: its motions16 [n_views of the stack][n_objects][16]) and
 // ptmi_fuse_views_deform (deform: the context's geometry stack, with motion, whose motions16 may then be null with n_objects = 0)
 static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* params, const float* views16, FrameDivisor F, int source, uint32_t first_view, uint32_t n_views,
                       const MotionPart* motion = nullptr, const DeformPart* deform = nullptr) {
@@ -600,6 +645,8 @@ static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* para
   MotionPart still{no_motions, 0, nullptr};
   if (deform && !motion->motions16 && motion->n_objects == 0) motion = &still;  // (a static world beside the triangles: no entry is read)
   if (motion && !motion->motions16) return null_motions(c, who);
+  if (F.pixel)
+    if (int r = check_moment_stack(c, who)) return r;
   if (int r = check_source_stacks(c, who, source == 1, first_view, n_views)) return r;
   const uint32_t n_stack = c->stacks[STACK_VIEWS].n, R = (uint32_t)P.radius;
   // the counts the call reads: its range widened by the radius on both sides, clipped to the stack — the window of its output views
@@ -636,7 +683,8 @@ static int fuse_views(ptmi_ctx* c, const char* who, const ptmi_fuse_params* para
   if (motion) mo.n_objects = motion->n_objects, mo.tris = c->d_tris.as<float>(), mo.n_tris = (uint32_t)c->n_tris_uploaded;  // (the triangles are on the device already)
   const ptmf_consts k = ptmf_make_consts(c->W, c->H, context_fov_factor(c), source == 0 ? F.frame_num : 1.0f, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   return fuse_enqueue(c, c->stacks[source == 0 ? STACK_VIEWS : STACK_DENOISED].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(), c->stacks[STACK_FUSED].buf.as<float4>(),
-                      table_ptrs(L, c->fuse_tab.dev.p, true), n.n_materials, c->W, c->H, n_stack, first_view, n_views, k, motion ? &mo : nullptr, deform ? &fd : nullptr);
+                      table_ptrs(L, c->fuse_tab.dev.p, true), n.n_materials, c->W, c->H, n_stack, first_view, n_views, k, motion ? &mo : nullptr, deform ? &fd : nullptr,
+                      F.pixel ? counts_in_moments(c->stacks[STACK_MOMENTS].buf.as<float4>()) : nullptr, 4);
 }
 int ptmi_fuse_views_deform(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects, int source,
                            uint32_t first_view, uint32_t n_views) {
@@ -655,6 +703,9 @@ int ptmi_fuse_views(ptmi_ctx* c, const ptmi_fuse_params* params, const float* vi
 int ptmi_fuse_views_frames(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, const float* frame_nums, uint32_t first_view, uint32_t n_views) {
   return fuse_views(c, "ptmi_fuse_views_frames", params, views16, FrameDivisor::per_view(frame_nums), 0, first_view, n_views);
 }
+int ptmi_fuse_views_counts(ptmi_ctx* c, const ptmi_fuse_params* params, const float* views16, uint32_t first_view, uint32_t n_views) {
+  return fuse_views(c, "ptmi_fuse_views_counts", params, views16, FrameDivisor::per_pixel(), 0, first_view, n_views);
+}
 
 int ptmi_read_fused(ptmi_ctx* c, uint32_t view, float* dst, size_t bytes) { return read_stack(c, STACK_FUSED, "ptmi_read_fused", view, 0, dst, bytes); }
 int ptmi_resolve_fused_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t bytes) {
@@ -663,12 +714,13 @@ int ptmi_resolve_fused_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t by
 int ptmi_fused_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* n_views) { return stack_device_ptr(c, STACK_FUSED, "ptmi_fused_device_ptr", nullptr, p, bytes, n_views); }
 int ptmi_release_fused(ptmi_ctx* c) { return release_stack(c, STACK_FUSED); }
 
-// ptmi_fuse_images, ptmi_fuse_images_frames (F's frame_nums: one per image), ptmi_fuse_images_motion (motion) and ptmi_fuse_images_deform (deform; motion may then
+// ptmi_fuse_images, ptmi_fuse_images_frames (F's frame_nums: one per image), ptmi_fuse_images_counts (F's counts: one per pixel), ptmi_fuse_images_motion (motion) and ptmi_fuse_images_deform (deform; motion may then
 // be nullptr)
 static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const FrameDivisor& F,
                        float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out, const MotionPart* motion = nullptr,
                        const DeformPart* deform = nullptr) {
-  if (!c || !colour || !layers || !views16 || !out || (motion && !motion->object_ids)) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (!c || !colour || !layers || !views16 || !out || (motion && !motion->object_ids) || (F.pixel && !F.counts))
+    return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   if (deform && (!deform->triangles_seq || (deform->n_transforms && !deform->transforms_seq) || (deform->n_meshes && !deform->meshes)))
     return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": null argument");
   if (deform && deform->n_triangles == 0) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": no triangles");
@@ -697,12 +749,13 @@ static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const 
   const ptmf_consts k = ptmf_make_consts(w, h, ptmf_fov_factor(fov_degrees), F.frame_num, P.radius, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   const size_t npix = (size_t)w * (size_t)h;
   const size_t tri_bytes = deform ? (size_t)n_images * deform->n_triangles * 96 : 0;
-  DBuf dtab, dids, dtris;  // (a *_motion call's id images and a *_deform call's triangle sequence are its own, had before anything is enqueued)
-  if (motion || deform) {
+  DBuf dtab, dids, dtris, dcnt;  // (a *_motion call's id images, a *_deform call's triangle sequence and a *_counts call's count images are its own, had before anything is enqueued)
+  if (motion || deform || F.pixel) {
     HIP_TRY(c, hipSetDevice(c->device));
     (void)hipGetLastError();
     if (motion) HIP_TRY(c, dids.ensure(npix * 4 * n_images));
     HIP_TRY(c, dtris.ensure(tri_bytes));
+    if (F.pixel) HIP_TRY(c, dcnt.ensure(npix * 4 * n_images));
   }
   return on_host_images(c, who, colour, layers, npix, n_images, out, dtab, L.total, [&](const float4* col, const float4* lay, float4* res) -> int {
     HIP_TRY(c, hipMemcpyAsync(dtab.p, tab.data(), L.total, hipMemcpyHostToDevice, c->stream));
@@ -718,8 +771,9 @@ static int fuse_images(ptmi_ctx* c, const char* who, const float* colour, const 
       HIP_TRY(c, hipMemcpyAsync(dtris.p, deform->triangles_seq, tri_bytes, hipMemcpyHostToDevice, c->stream));
       fd.tris = dtris.as<float4>(), fd.slot = (size_t)deform->n_triangles * 6, fd.n_tris = deform->n_triangles, fd.n_transforms = deform->n_transforms, fd.lo = 0;
     }
+    if (F.pixel) HIP_TRY(c, hipMemcpyAsync(dcnt.p, F.counts, npix * 4 * n_images, hipMemcpyHostToDevice, c->stream));
     return fuse_enqueue(c, col, lay, res, table_ptrs(L, dtab.p, lambertian != nullptr), n_materials, w, h, n_images, 0, n_images, k, motion || deform ? &mo : nullptr,
-                        deform ? &fd : nullptr);
+                        deform ? &fd : nullptr, dcnt.as<float>(), 1);
   });
 }
 int ptmi_fuse_images_deform(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums,
@@ -746,6 +800,10 @@ int ptmi_fuse_images(ptmi_ctx* c, const float* colour, const float* layers, cons
 int ptmi_fuse_images_frames(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* frame_nums, float fov_degrees,
                             const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
   return fuse_images(c, "ptmi_fuse_images_frames", colour, layers, views16, w, h, n_images, FrameDivisor::per_view(frame_nums), fov_degrees, lambertian, n_materials, params, out);
+}
+int ptmi_fuse_images_counts(ptmi_ctx* c, const float* colour, const float* layers, const float* views16, int w, int h, uint32_t n_images, const float* counts, float fov_degrees,
+                            const uint8_t* lambertian, uint32_t n_materials, const ptmi_fuse_params* params, float* out) {
+  return fuse_images(c, "ptmi_fuse_images_counts", colour, layers, views16, w, h, n_images, FrameDivisor::per_pixel(counts), fov_degrees, lambertian, n_materials, params, out);
 }
 
 // ---- the geometry stack (ptmi_capture_view_geometry): what ptmi_accumulate_views_deform reads of a view beside its images ----
@@ -836,13 +894,14 @@ int ptmi_release_geometry(ptmi_ctx* c) {
 // motion (with t.frames): k_accumulate_view_motion's operands, records = those of the first view that has a predecessor (first_view_with_history), n_objects per view.
 // deform (with t.frames; motion may be nullptr: a static world beside the triangles): k_accumulate_view_deform's operands, args.tris_cur = slot 0 of the geometry, slot
 // after slot `slot` float4 apart, indexed by the view's number; args.records laid out as the motion records are.
+// pixel_counts (without any of those): every pixel's divisor is its own M.w in `moments`: k_accumulate_view_counts.
 struct DeformCall {
   DeformArgs args;
   size_t slot;
 };
 static int accumulate_enqueue(ptmi_ctx* c, const float4* colour, const float4* moments, const float4* layers, float4* planes, const TablePtrs& t, uint32_t n_materials, int W, int H,
                               uint32_t n_stack, uint32_t first, uint32_t n, bool resume, const ptmf_consts& k, const ptma_consts& ka, const MotionArgs* motion = nullptr,
-                              const DeformCall* deform = nullptr) {
+                              const DeformCall* deform = nullptr, bool pixel_counts = false) {
   const uint64_t tiles = (uint64_t)((W + 63) / 64) * (uint64_t)H;
   const unsigned gx = (unsigned)((tiles + kBlock / 64 - 1) / (kBlock / 64));
   const size_t npix = (size_t)W * (size_t)H;
@@ -864,6 +923,8 @@ static int accumulate_enqueue(ptmi_ctx* c, const float4* colour, const float4* m
       shared([&](auto... a) { hipLaunchKernelGGL(k_accumulate_view_deform, dim3(gx), dim3(kBlock), 0, c->stream, a..., t.frames, mo, de); });
     } else if (motion) {
       shared([&](auto... a) { hipLaunchKernelGGL(k_accumulate_view_motion, dim3(gx), dim3(kBlock), 0, c->stream, a..., t.frames, mo); });
+    } else if (pixel_counts) {
+      shared([&](auto... a) { hipLaunchKernelGGL(k_accumulate_view_counts, dim3(gx), dim3(kBlock), 0, c->stream, a...); });
     } else if (t.frames) {
       shared([&](auto... a) { hipLaunchKernelGGL(k_accumulate_view_frames, dim3(gx), dim3(kBlock), 0, c->stream, a..., t.frames); });
     } else {
@@ -881,7 +942,7 @@ static int accumulate_check_args(ptmi_ctx* c, const char* who, const ptmi_accumu
   return check_stack_call(c, who, "a view's pixels", "several", ok ? nullptr : "max_history, sigma_normal, sigma_depth and albedo_floor > 0, all finite, and min_frames >= 2", true, frame_num);
 }
 
-// ptmi_accumulate_views, ptmi_accumulate_views_frames, ptmi_accumulate_views_motion (motion: its motions16 [n_views of the stack][n_objects][16]) and
+// ptmi_accumulate_views, ptmi_accumulate_views_frames, ptmi_accumulate_views_counts, ptmi_accumulate_views_motion (motion: its motions16 [n_views of the stack][n_objects][16]) and
 // ptmi_accumulate_views_deform (deform: the context's geometry stack, with motion, whose motions16 may then be null with n_objects = 0)
 static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_params* params, const float* views16, const FrameDivisor& F, uint32_t first_view, uint32_t n_views,
                             int resume, const MotionPart* motion = nullptr, const DeformPart* deform = nullptr) {
@@ -895,10 +956,7 @@ static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_
   const uint32_t n_objects = motion ? motion->n_objects : 0u;
   if (deform && !motions16 && n_objects == 0) motions16 = no_motions;  // (a static world beside the triangles: no entry is read)
   if (motion && !motions16) return null_motions(c, who);
-  if (int r = check_stack(c, STACK_MOMENTS, who, 0)) return r;  // (the moment stack first, as ptmi_denoise_views_guided asks)
-  if (int r = check_stack(c, STACK_VIEWS, who, 0)) return r;
-  if (c->stacks[STACK_MOMENTS].n != c->stacks[STACK_VIEWS].n)
-    return fail(c, PTMI_ERR_STATE, std::string(who) + ": the view stack has " + std::to_string(c->stacks[STACK_VIEWS].n) + " views, the moment stack " + std::to_string(c->stacks[STACK_MOMENTS].n));
+  if (int r = check_moment_stack(c, who)) return r;  // (as ptmi_denoise_views_guided asks)
   if (int r = check_source_stacks(c, who, false, first_view, n_views)) return r;
   if (resume) {
     if (first_view == 0) return fail(c, PTMI_ERR_INVALID_ARG, std::string(who) + ": resume needs first_view > 0: view 0 has no predecessor");
@@ -935,7 +993,7 @@ static int accumulate_views(ptmi_ctx* c, const char* who, const ptmi_accumulate_
   const ptmf_consts k = ptmf_make_consts(c->W, c->H, context_fov_factor(c), F.frame_num, 1, P.sigma_normal, P.sigma_depth, P.albedo_floor);
   return accumulate_enqueue(c, c->stacks[STACK_VIEWS].buf.as<float4>(), c->stacks[STACK_MOMENTS].buf.as<float4>(), c->stacks[STACK_FEATURES].buf.as<float4>(),
                             c->stacks[STACK_ACCUMULATED].buf.as<float4>(), table_ptrs(L, c->fuse_tab.dev.p, true), n.n_materials, c->W, c->H, n_stack, first_view, n_views, resume != 0, k,
-                            ptma_make_consts(P.max_history, P.min_frames), motion ? &mo : nullptr, deform ? &dc : nullptr);
+                            ptma_make_consts(P.max_history, P.min_frames), motion ? &mo : nullptr, deform ? &dc : nullptr, F.pixel);
 }
 int ptmi_accumulate_views_deform(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, const float* motions16, uint32_t n_objects,
                                  uint32_t first_view, uint32_t n_views, int resume) {
@@ -954,6 +1012,9 @@ int ptmi_accumulate_views(ptmi_ctx* c, const ptmi_accumulate_params* params, con
 int ptmi_accumulate_views_frames(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, const float* frame_nums, uint32_t first_view, uint32_t n_views, int resume) {
   return accumulate_views(c, "ptmi_accumulate_views_frames", params, views16, FrameDivisor::per_view(frame_nums), first_view, n_views, resume);
 }
+int ptmi_accumulate_views_counts(ptmi_ctx* c, const ptmi_accumulate_params* params, const float* views16, uint32_t first_view, uint32_t n_views, int resume) {
+  return accumulate_views(c, "ptmi_accumulate_views_counts", params, views16, FrameDivisor::per_pixel(), first_view, n_views, resume);
+}
 
 int ptmi_read_accumulated(ptmi_ctx* c, uint32_t view, int plane, float* dst, size_t bytes) { return read_stack(c, STACK_ACCUMULATED, "ptmi_read_accumulated", view, plane, dst, bytes); }
 int ptmi_resolve_accumulated_rgba8(ptmi_ctx* c, uint32_t view, uint8_t* dst, size_t bytes) {
@@ -964,7 +1025,7 @@ int ptmi_accumulated_device_ptr(ptmi_ctx* c, void** p, size_t* bytes, uint32_t* 
 }
 int ptmi_release_accumulated(ptmi_ctx* c) { return release_stack(c, STACK_ACCUMULATED); }
 
-// ptmi_accumulate_images, ptmi_accumulate_images_frames (F's frame_nums: one per image), ptmi_accumulate_images_motion (motion) and ptmi_accumulate_images_deform
+// ptmi_accumulate_images, ptmi_accumulate_images_frames (F's frame_nums: one per image), ptmi_accumulate_images_counts (the counts: the moments' w), ptmi_accumulate_images_motion (motion) and ptmi_accumulate_images_deform
 // (deform; motion may then be nullptr)
 static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
                              const FrameDivisor& F, float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in,
@@ -1028,7 +1089,7 @@ static int accumulate_images(ptmi_ctx* c, const char* who, const float* colour_s
     }
     const uint32_t first = history_in ? 1u : 0u;
     return accumulate_enqueue(c, col, mom.as<float4>(), lay, res, table_ptrs(L, dtab.p, lambertian != nullptr), n_materials, w, h, n_images, first, n_images - first,
-                              history_in != nullptr, k, ka, motion ? &mo : nullptr, deform ? &dc : nullptr);
+                              history_in != nullptr, k, ka, motion ? &mo : nullptr, deform ? &dc : nullptr, F.pixel);
   }, 3, 48);
 }
 int ptmi_accumulate_images(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images, float frame_num,
@@ -1041,6 +1102,11 @@ int ptmi_accumulate_images_frames(ptmi_ctx* c, const float* colour_sums, const f
                                   const float* history_in, float* out) {
   return accumulate_images(c, "ptmi_accumulate_images_frames", colour_sums, moments, layers, views16, w, h, n_images, FrameDivisor::per_view(frame_nums), fov_degrees, lambertian,
                            n_materials, params, history_in, out);
+}
+int ptmi_accumulate_images_counts(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
+                                  float fov_degrees, const uint8_t* lambertian, uint32_t n_materials, const ptmi_accumulate_params* params, const float* history_in, float* out) {
+  return accumulate_images(c, "ptmi_accumulate_images_counts", colour_sums, moments, layers, views16, w, h, n_images, FrameDivisor::per_pixel(), fov_degrees, lambertian, n_materials,
+                           params, history_in, out);
 }
 int ptmi_accumulate_images_motion(ptmi_ctx* c, const float* colour_sums, const float* moments, const float* layers, const float* views16, int w, int h, uint32_t n_images,
                                   const float* frame_nums, const float* motions16, uint32_t n_objects, const int32_t* object_ids, float fov_degrees, const uint8_t* lambertian,

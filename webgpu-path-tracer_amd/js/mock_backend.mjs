@@ -34,6 +34,10 @@ export class MockBackend {
   denoiseViewsGuidedFrames(frameNums, firstView, nViews, params = null) { this.calls.push(['denoiseViewsGuidedFrames', Array.from(frameNums), firstView, nViews, params]); }
   fuseViewsFrames(views, frameNums, firstView, nViews, params = null) { this.calls.push(['fuseViewsFrames', views.length / 16, Array.from(frameNums), firstView, nViews, params]); }
   accumulateViewsFrames(views, frameNums, firstView, nViews, resume = false, params = null) { this.calls.push(['accumulateViewsFrames', views.length / 16, Array.from(frameNums), firstView, nViews, !!resume, params]); }
+  denoiseViewsCounts(firstView, nViews, params = null) { this.calls.push(['denoiseViewsCounts', firstView, nViews, params]); }
+  denoiseViewsGuidedCounts(firstView, nViews, params = null) { this.calls.push(['denoiseViewsGuidedCounts', firstView, nViews, params]); }
+  fuseViewsCounts(views, firstView, nViews, params = null) { this.calls.push(['fuseViewsCounts', views.length / 16, firstView, nViews, params]); }
+  accumulateViewsCounts(views, firstView, nViews, resume = false, params = null) { this.calls.push(['accumulateViewsCounts', views.length / 16, firstView, nViews, !!resume, params]); }
   accumulateViewsMotion(views, frameNums, motions, nObjects, firstView, nViews, resume = false, params = null) { this.calls.push(['accumulateViewsMotion', views.length / 16, Array.from(frameNums), motions.length / 16, nObjects, firstView, nViews, !!resume, params]); }
   captureViewGeometry(view, nViews) { this.calls.push(['captureViewGeometry', view, nViews]); }
   accumulateViewsDeform(views, frameNums, motions, nObjects, firstView, nViews, resume = false, params = null) { this.calls.push(['accumulateViewsDeform', views.length / 16, Array.from(frameNums), motions ? motions.length / 16 : null, nObjects, firstView, nViews, !!resume, params]); }

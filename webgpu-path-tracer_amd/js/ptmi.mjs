@@ -108,6 +108,12 @@ export class Ptmi {
   accumulateViewsFrames(views, frameNums, firstView, nViews, resume = false, params = null) {
     this.native.accumulateViewsFrames(this.h, views, Float32Array.from(frameNums), firstView, nViews, resume, params);
   }
+  // Per-pixel frame counts (ptmi_denoise_views_counts ...): the consumers for a stack whose PIXELS differ in frame count (renderViewRuns, renderViewsRuns,
+  // renderViewsUntilRuns).  Every pixel's divisor is its own M.w in the moment stack, read on the device: no count argument.  setViewMoments must have been on.
+  denoiseViewsCounts(firstView, nViews, params = null) { this.native.denoiseViewsCounts(this.h, firstView, nViews, params); }
+  denoiseViewsGuidedCounts(firstView, nViews, params = null) { this.native.denoiseViewsGuidedCounts(this.h, firstView, nViews, params); }
+  fuseViewsCounts(views, firstView, nViews, params = null) { this.native.fuseViewsCounts(this.h, views, firstView, nViews, params); }
+  accumulateViewsCounts(views, firstView, nViews, resume = false, params = null) { this.native.accumulateViewsCounts(this.h, views, firstView, nViews, resume, params); }
   // ptmi_accumulate_views_motion: motions holds, per view of the stack and object (global_id), the column-major matrix that carries a world point of the object at
   // the time of view v to the same material point at the time of view v - 1: Float32Array [view][object][16]
   accumulateViewsMotion(views, frameNums, motions, nObjects, firstView, nViews, resume = false, params = null) {

@@ -37,6 +37,9 @@ SYMBOLS = [
     "ptmi_denoise_views_frames", "ptmi_denoise_views_guided_frames", "ptmi_fuse_views_frames", "ptmi_accumulate_views_frames",
     "ptmi_denoise_images_frames", "ptmi_denoise_images_guided_frames", "ptmi_fuse_images_frames", "ptmi_accumulate_images_frames",
     "ptmi_denoise_reference_frames", "ptmi_denoise_guided_reference_frames", "ptmi_fuse_reference_frames", "ptmi_accumulate_reference_frames",
+    "ptmi_denoise_views_counts", "ptmi_denoise_views_guided_counts", "ptmi_fuse_views_counts", "ptmi_accumulate_views_counts",
+    "ptmi_denoise_images_counts", "ptmi_denoise_images_guided_counts", "ptmi_fuse_images_counts", "ptmi_accumulate_images_counts",
+    "ptmi_denoise_reference_counts", "ptmi_denoise_guided_reference_counts", "ptmi_fuse_reference_counts", "ptmi_accumulate_reference_counts",
     "ptmi_refit_bvh", "ptmi_refit_scene_bvh",
     "ptmi_accumulate_views_motion", "ptmi_accumulate_images_motion", "ptmi_accumulate_reference_motion", "ptmi_object_ids_reference", "ptmi_motions_from_transforms",
     "ptmi_fuse_views_motion", "ptmi_fuse_images_motion", "ptmi_fuse_reference_motion", "ptmi_compose_motions",
@@ -289,6 +292,20 @@ def load_library(build=False, path=None):
         L.ptmi_denoise_guided_reference_frames.argtypes = [fp, fp, fp, i32, i32, u32, fp, gp, fp, fp]
         L.ptmi_fuse_reference_frames.argtypes = [fp, fp, fp, i32, i32, u32, fp, ctypes.c_float, fp, u32, up, fp]
         L.ptmi_accumulate_reference_frames.argtypes = [fp, fp, fp, fp, i32, i32, u32, fp, ctypes.c_float, fp, u32, ap, fp, fp, i32]
+    if hasattr(L, "ptmi_denoise_views_counts"):  # (an older A/B build loaded through PTMI_LIB takes one divisor per call or per view)
+        dp, gp, up, ap = ctypes.POINTER(DenoiseParams), ctypes.POINTER(GuidedParams), ctypes.POINTER(FuseParams), ctypes.POINTER(AccumulateParams)
+        L.ptmi_denoise_views_counts.argtypes = [vp, dp, u32, u32]
+        L.ptmi_denoise_views_guided_counts.argtypes = [vp, gp, u32, u32]
+        L.ptmi_fuse_views_counts.argtypes = [vp, up, fp, u32, u32]
+        L.ptmi_accumulate_views_counts.argtypes = [vp, ap, fp, u32, u32, i32]
+        L.ptmi_denoise_images_counts.argtypes = [vp, fp, fp, i32, i32, u32, fp, dp, fp]
+        L.ptmi_denoise_images_guided_counts.argtypes = [vp, fp, fp, fp, i32, i32, u32, gp, fp, fp]
+        L.ptmi_fuse_images_counts.argtypes = [vp, fp, fp, fp, i32, i32, u32, fp, ctypes.c_float, fp, u32, up, fp]
+        L.ptmi_accumulate_images_counts.argtypes = [vp, fp, fp, fp, fp, i32, i32, u32, ctypes.c_float, fp, u32, ap, fp, fp]
+        L.ptmi_denoise_reference_counts.argtypes = [fp, fp, i32, i32, u32, fp, dp, fp]
+        L.ptmi_denoise_guided_reference_counts.argtypes = [fp, fp, fp, i32, i32, u32, gp, fp, fp]
+        L.ptmi_fuse_reference_counts.argtypes = [fp, fp, fp, i32, i32, u32, fp, ctypes.c_float, fp, u32, up, fp]
+        L.ptmi_accumulate_reference_counts.argtypes = [fp, fp, fp, fp, i32, i32, u32, ctypes.c_float, fp, u32, ap, fp, fp, i32]
     if hasattr(L, "ptmi_refit_scene_bvh"):  # (an older A/B build loaded through PTMI_LIB rebuilds a stale tree)
         L.ptmi_refit_bvh.argtypes = [sz, fp, fp, fp, sz]
         L.ptmi_refit_scene_bvh.argtypes = [vp]
@@ -368,6 +385,16 @@ def _optr(a):
     return None if a is None else _ptr(a)
 
 
+def _pixel_counts(counts, shape):
+    """The per-pixel f32 divisors of the plain and fuse *_counts forms, (n, H, W) — a moment stack's [..., 3] as it is; None stays a null pointer, which the library
+    refuses."""
+    if counts is None:
+        return None
+    k = np.ascontiguousarray(counts, np.float32)
+    assert k.size == int(np.prod(shape)), "counts: one count per pixel, (n, H, W) = %r" % (tuple(shape),)
+    return k.reshape(shape)
+
+
 def view_slot_plan(first_frames, frame_counts):
     """Test hook, no GPU (ptmi_view_slot_plan): the slot table render_views_frames uploads for these per-view first frame numbers and frame counts, as
     (records (V, 4) uint32 — first slot, count, first frame, next view with a frame —, view_of_slot (n_slots,) uint32).  Raises PtmiError where the call would."""
@@ -436,6 +463,17 @@ def denoise_reference_frames(colour_sums, layers, frame_nums, params=None, lib=N
     return out
 
 
+def denoise_reference_counts(colour_sums, layers, counts, params=None, lib=None):
+    """ptmi_denoise_reference_counts: denoise_reference with one frame count per PIXEL, counts (n, H, W): every pixel's sums are divided by its own count (a moment
+    stack's M.w).  A count of 0 is no special case: the division's NaN or inf makes the pixel invalid."""
+    c, l, out = _denoise_arrays(colour_sums, layers)
+    k = _pixel_counts(counts, c.shape[:3])
+    st = (lib or load_library()).ptmi_denoise_reference_counts(_ptr(c), _ptr(l), c.shape[2], c.shape[1], c.shape[0], _optr(k), None if params is None else ctypes.byref(params), _ptr(out))
+    if st != 0:
+        raise PtmiError(st, "ptmi_denoise_reference_counts failed")
+    return out
+
+
 def default_guided_params(lib=None, **kw):
     """ptmi_default_guided_params (levels 5, sigma_normal 0.25, sigma_depth 0.1, sigma_luma 4, albedo_floor 1e-3, min_frames 4, var_eps 1e-10) with fields replaced
     by keyword."""
@@ -472,6 +510,16 @@ def denoise_guided_reference_frames(colour_sums, moments, layers, frame_nums, pa
                                                                       None if params is None else ctypes.byref(params), _ptr(out), _optr(var))
     if st != 0:
         raise PtmiError(st, "ptmi_denoise_guided_reference_frames failed")
+    return (out, var) if want_var else out
+
+
+def denoise_guided_reference_counts(colour_sums, moments, layers, params=None, want_var=False, lib=None):
+    """ptmi_denoise_guided_reference_counts: denoise_guided_reference with every pixel's own frame count, the w of its moments."""
+    c, m, l, out, var = _guided_arrays(colour_sums, moments, layers, want_var)
+    st = (lib or load_library()).ptmi_denoise_guided_reference_counts(_ptr(c), _ptr(m), _ptr(l), c.shape[2], c.shape[1], c.shape[0],
+                                                                      None if params is None else ctypes.byref(params), _ptr(out), _optr(var))
+    if st != 0:
+        raise PtmiError(st, "ptmi_denoise_guided_reference_counts failed")
     return (out, var) if want_var else out
 
 
@@ -516,6 +564,18 @@ def fuse_reference_frames(colour, layers, views, frame_nums, fov_degrees=60.0, l
     return out
 
 
+def fuse_reference_counts(colour, layers, views, counts, fov_degrees=60.0, lambertian=None, params=None, lib=None):
+    """ptmi_fuse_reference_counts: fuse_reference with one frame count per PIXEL, counts (n, H, W): the output pixel takes its own count, the pixel sampled in a
+    neighbour view that pixel's."""
+    c, l, v, t, out = _fuse_arrays(colour, layers, views, lambertian)
+    k = _pixel_counts(counts, c.shape[:3])
+    st = (lib or load_library()).ptmi_fuse_reference_counts(_ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(k), float(fov_degrees),
+                                                            _optr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params), _ptr(out))
+    if st != 0:
+        raise PtmiError(st, "ptmi_fuse_reference_counts failed")
+    return out
+
+
 def default_accumulate_params(lib=None, **kw):
     """ptmi_default_accumulate_params (max_history 32, min_frames 4, sigma_normal 0.25, sigma_depth 0.1, albedo_floor 1e-3) with fields replaced by keyword."""
     p = AccumulateParams()
@@ -556,6 +616,18 @@ def accumulate_reference_frames(colour_sums, moments, layers, views, frame_nums,
                                                                   _optr(hist), _ptr(out), int(threads))
     if st != 0:
         raise PtmiError(st, "ptmi_accumulate_reference_frames failed")
+    return out
+
+
+def accumulate_reference_counts(colour_sums, moments, layers, views, fov_degrees=60.0, lambertian=None, params=None, history=None, threads=1, lib=None):
+    """ptmi_accumulate_reference_counts: accumulate_reference with every pixel's own frame count, the w of its moments: pixel p of view v divides by M.w of (v, p),
+    the pixel q looked up in view v-1 by M.w of (v-1, q)."""
+    c, m, l, v, t, hist, out = _accumulate_arrays(colour_sums, moments, layers, views, lambertian, history)
+    st = (lib or load_library()).ptmi_accumulate_reference_counts(_ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], float(fov_degrees),
+                                                                  _optr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params),
+                                                                  _optr(hist), _ptr(out), int(threads))
+    if st != 0:
+        raise PtmiError(st, "ptmi_accumulate_reference_counts failed")
     return out
 
 
@@ -1213,6 +1285,65 @@ class Context:
         c, m, l, v, t, hist, out = _accumulate_arrays(colour_sums, moments, layers, views, lambertian, history)
         f = _frame_nums(frame_nums, c.shape[0])
         self._ck(self.lib.ptmi_accumulate_images_frames(self.h, _ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(f), float(fov_degrees),
+                                                        _optr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params), _optr(hist), _ptr(out)))
+        return out
+
+    # ---- the consumers with every pixel's own frame count (include/ptmi.h, "CONSUMERS WITH PER-PIXEL FRAME COUNTS") ----
+    def denoise_views_counts(self, first_view=0, n_views=None, params=None):
+        """ptmi_denoise_views_counts: denoise_views for a stack whose PIXELS sum different numbers of frames (render_views_until_runs): every pixel's divisor is its
+        M.w in the moment stack, read on the device.  Needs set_view_moments.  Asynchronous."""
+        if n_views is None:
+            n_views = self.views_device_ptr()[2] - first_view
+        self._ck(self.lib.ptmi_denoise_views_counts(self.h, None if params is None else ctypes.byref(params), first_view, n_views))
+
+    def denoise_views_guided_counts(self, first_view=0, n_views=None, params=None):
+        """ptmi_denoise_views_guided_counts: denoise_views_guided with every pixel's own frame count (see denoise_views_counts).  Asynchronous."""
+        if n_views is None:
+            n_views = self.views_device_ptr()[2] - first_view
+        self._ck(self.lib.ptmi_denoise_views_guided_counts(self.h, None if params is None else ctypes.byref(params), first_view, n_views))
+
+    def fuse_views_counts(self, views, first_view=0, n_views=None, params=None):
+        """ptmi_fuse_views_counts: fuse_views on the view stack (source 0) with every pixel's own frame count: the output pixel's M.w and, for a sample in a
+        neighbour view, that pixel's.  views: (n_views of the stack, 16).  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        if n_views is None:
+            n_views = v.shape[0] - first_view
+        self._ck(self.lib.ptmi_fuse_views_counts(self.h, None if params is None else ctypes.byref(params), _ptr(v), first_view, n_views))
+
+    def accumulate_views_counts(self, views, first_view=0, n_views=None, resume=False, params=None):
+        """ptmi_accumulate_views_counts: accumulate_views with every pixel's own frame count: M.w of the pixel, and M.w of the pixel looked up in the view before.
+        views: (n_views of the stack, 16).  Asynchronous."""
+        v = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        if n_views is None:
+            n_views = v.shape[0] - first_view
+        self._ck(self.lib.ptmi_accumulate_views_counts(self.h, None if params is None else ctypes.byref(params), _ptr(v), first_view, n_views, 1 if resume else 0))
+
+    def denoise_images_counts(self, colour_sums, layers, counts, params=None):
+        """ptmi_denoise_images_counts: denoise_images with one frame count per pixel, counts (n, H, W); synchronous."""
+        c, l, out = _denoise_arrays(colour_sums, layers)
+        k = _pixel_counts(counts, c.shape[:3])
+        self._ck(self.lib.ptmi_denoise_images_counts(self.h, _ptr(c), _ptr(l), c.shape[2], c.shape[1], c.shape[0], _optr(k), None if params is None else ctypes.byref(params), _ptr(out)))
+        return out
+
+    def denoise_images_guided_counts(self, colour_sums, moments, layers, params=None, want_var=False):
+        """ptmi_denoise_images_guided_counts: denoise_images_guided with every pixel's own frame count, the w of its moments; synchronous."""
+        c, m, l, out, var = _guided_arrays(colour_sums, moments, layers, want_var)
+        self._ck(self.lib.ptmi_denoise_images_guided_counts(self.h, _ptr(c), _ptr(m), _ptr(l), c.shape[2], c.shape[1], c.shape[0],
+                                                            None if params is None else ctypes.byref(params), _ptr(out), _optr(var)))
+        return (out, var) if want_var else out
+
+    def fuse_images_counts(self, colour, layers, views, counts, fov_degrees=60.0, lambertian=None, params=None):
+        """ptmi_fuse_images_counts: fuse_images with one frame count per pixel, counts (n, H, W); synchronous."""
+        c, l, v, t, out = _fuse_arrays(colour, layers, views, lambertian)
+        k = _pixel_counts(counts, c.shape[:3])
+        self._ck(self.lib.ptmi_fuse_images_counts(self.h, _ptr(c), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], _optr(k), float(fov_degrees),
+                                                  _optr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params), _ptr(out)))
+        return out
+
+    def accumulate_images_counts(self, colour_sums, moments, layers, views, fov_degrees=60.0, lambertian=None, params=None, history=None):
+        """ptmi_accumulate_images_counts: accumulate_images with every pixel's own frame count, the w of its moments; synchronous."""
+        c, m, l, v, t, hist, out = _accumulate_arrays(colour_sums, moments, layers, views, lambertian, history)
+        self._ck(self.lib.ptmi_accumulate_images_counts(self.h, _ptr(c), _ptr(m), _ptr(l), _ptr(v), c.shape[2], c.shape[1], c.shape[0], float(fov_degrees),
                                                         _optr(t), 0 if t is None else t.size, None if params is None else ctypes.byref(params), _optr(hist), _ptr(out)))
         return out
 
